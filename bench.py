@@ -8,7 +8,8 @@ CartPole-v1, n_envs = 65 536 per GPU, hidden [64,64], PPO defaults, n_steps = 20
 episodes (termination disabled, truncation every 500 steps), batch_size = N/32 (BASELINE.json leaves it open;
 SURVEY.md §8d) — all state resident in HBM before the timed region.  Prints ONE JSON line on rank 0, kept under 8 KB
 (the driver keeps the last 8 KB of stdout): the other configs' runs appear in it as compact `secondary` entries and
-in full on stderr (`--full`: in full in the line).
+in full on stderr (`--full`: in full in the line).  `--dump-outputs DIR` writes what the last timed step of the headline workload
+returned as DIR/<name>.npy (dump_outputs below); it runs after the timed region and changes no timing.
 
 N > 1: envs are sharded (weak scaling, 65 536 per GPU), the only data-path collective is the RCCL all-reduce of
 [gradients | loss sums] per optimiser step (+ the 3-double advantage-moment reduce), issued inside the library
@@ -87,6 +88,55 @@ def mfma_roofline(ach_tflops: float, arith: str) -> dict:
             "f32_mfma_peak": PEAK_F32_MFMA_TFLOPS, "frac_vs_f32_peak": ach_tflops / PEAK_F32_MFMA_TFLOPS, "arithmetic": arith}
 
 
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files of one dump together
+DUMP_ROWS = 1 << 19           # ... and the rows kept of an array with more (a rollout field of configs[1] has 134 217 728)
+
+
+def dump_rows(n: int) -> np.ndarray:
+    """the rows of an n-row output that --dump-outputs keeps: all of them up to DUMP_ROWS, else a fixed sample (seeded, sorted, the same for every array of n rows and
+    in every run — two builds dump the same rows)"""
+    return np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).integers(0, n, DUMP_ROWS))
+
+
+def dump_outputs(dump_dir: str, arrays: dict) -> dict:
+    """--dump-outputs DIR: DIR/<name>.npy per array, float64 kept, everything else as float32 (exact for the int32 actions of a discrete env); refuses more than
+    DUMP_MAX_BYTES.  -> what goes into the JSON line"""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes + 128 for a in arrays.values())      # + the .npy header
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes in {sorted(arrays)}, the limit is {DUMP_MAX_BYTES}")
+    d = Path(dump_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    return {"dir": str(d), "bytes": total, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
+def ppo_outputs(pkg, h, stats) -> dict:
+    """what a caller of one PPO iteration holds after it: the statistics ppo_update returned (struct dril_ppo_stats in field order), the parameters it left, and the
+    rollout buffer collect_rollout filled (time-major rows n = t*E + e; dump_rows of them), read back one field at a time"""
+    capi = pkg._capi
+    out = {"ppo_stats": np.array([getattr(stats, k) for k, _ in stats._fields_], np.float64), "params": h.get_params()}
+    rows = dump_rows(h.N)
+    for name, which in (("observations", capi.BUF_OBSERVATIONS), ("actions", capi.BUF_ACTIONS), ("rewards", capi.BUF_REWARDS), ("values", capi.BUF_VALUES),
+                        ("logprobs", capi.BUF_LOGPROBS), ("advantages", capi.BUF_ADVANTAGES), ("returns", capi.BUF_RETURNS)):
+        out["rollout_" + name] = h.buffer(which)[rows]
+    return out
+
+
+def sac_outputs(pkg, h, stats) -> dict:
+    """what a caller of one SAC bench step holds after it: the statistics of every gradient step of the last iterate call (struct dril_sac_stats in field order, one
+    row per step; the fps figures are timings, not results), the parameters, target parameters and entropy coefficient it left, and the replay ring (dump_rows of it)"""
+    capi = pkg._capi
+    fields = [k for k, _ in capi.DrilSacStats._fields_ if k != "reserved"]
+    out = {"sac_stats": np.array([[getattr(s, k) for k in fields] for s in stats], np.float64).reshape(len(stats), len(fields)),
+           "params": h.get_params(), "target_params": h.get_target_params(), "log_ent_coef": np.array([h.get_log_ent_coef()], np.float64)}
+    rows = dump_rows(h.replay_size())
+    for name, which in (("observations", capi.RB_OBSERVATIONS), ("actions", capi.RB_ACTIONS), ("rewards", capi.RB_REWARDS), ("next_observations", capi.RB_NEXT_OBSERVATIONS)):
+        out["replay_" + name] = h.replay(which)[rows]
+    return out
+
+
 def cpu_baseline(pkg, seed: int) -> dict:
     """The CPU oracle (a C restatement of the reference algorithm, OpenMP over envs/samples like the reference's
     @threads) timed on this box's host cores on a bounded sample of the same workload.  kind = "port": the real
@@ -124,7 +174,7 @@ def sac_flops(D: int, A: int, H: int, B: int, E: int) -> tuple:
     return upd, E * fa
 
 
-def run_sac(pkg, *, steps: int, warmup: int, iters: int, E: int = 4096, H: int = 512, events: bool = True, cpu: bool = True) -> dict:
+def run_sac(pkg, *, steps: int, warmup: int, iters: int, E: int = 4096, H: int = 512, events: bool = True, cpu: bool = True, dump_dir: str | None = None) -> dict:
     """BASELINE.json configs[4]: SAC on Pendulum-v1, n_envs = 4096, SACLayer [512,512] relu, SAC() defaults (batch 256, train_freq 1,
     gradient_steps 1).  One bench "step" = `iters` iterations of train!'s loop body (sac.jl:464-535): collect one env step over all
     envs into the device replay ring, then one update!.  Single GPU (the path has one learner; N > 1 would be replicas)."""
@@ -144,8 +194,9 @@ def run_sac(pkg, *, steps: int, warmup: int, iters: int, E: int = 4096, H: int =
         h.iterate(iters)
     h.profile_reset()
     t0 = time.perf_counter()
+    last = []
     for _ in range(steps):
-        h.iterate(iters)
+        last, _ = h.iterate(iters)
     dt = time.perf_counter() - t0
     prof = h.profile()
     n_it = steps * iters
@@ -163,6 +214,8 @@ def run_sac(pkg, *, steps: int, warmup: int, iters: int, E: int = 4096, H: int =
         out["roofline"] = dict(mfma_roofline(ach, "f32 (update!: v_mfma_f32_32x32x2_f32; the collection's second layer: two f16 pieces per operand, three v_mfma_f32_32x32x16_f16 per k16 step, f32 accumulate)"), traffic=None,
                                kernel="all launches of one SAC iteration (sac_gemm_lds_kernel / sac_gemm_multi_kernel / head kernels of update!; sac_collect_l1 / l2 / env kernels of the collection step); in-kernel wall-clock stamps at the phase boundaries",
                                update_ms=u_ms, collect_step_ms=c_ms, flops_per_update=f_upd, flops_per_collect_step=f_col)
+    if dump_dir:
+        out["outputs_dumped"] = dump_outputs(dump_dir, sac_outputs(pkg, h, last))
     if cpu:
         sys.path.insert(0, str(ROOT / "tests"))
         import oracle_lib
@@ -182,7 +235,7 @@ def run_sac(pkg, *, steps: int, warmup: int, iters: int, E: int = 4096, H: int =
 
 def run_ppo(pkg, *, env_name: str, E: int, T: int, hidden: int, minibatches: int, epochs: int, normalize: bool, steps: int, warmup: int, events: int = 7,
             batch_size: int | None = None, fixed_length: bool = True, label: str = "", rank: int = 0, local_rank: int = 0, world: int = 1, dist=None,
-            grad_variant: str | None = None) -> dict | None:
+            grad_variant: str | None = None, dump_dir: str | None = None) -> dict | None:
     """one PPO workload: `warmup` untimed iterations, then exactly `steps` iterations (rollout + GAE + epochs x minibatches update) between a barrier +
     stream synchronisation on both sides, max over ranks; returns the result dict on rank 0."""
     N_local = E * T
@@ -305,6 +358,8 @@ def run_ppo(pkg, *, env_name: str, E: int, T: int, hidden: int, minibatches: int
             rk = prof.get("rollout_kernel", {"total_ms": 0, "launches": 0})
             if rk["launches"]:                           # what the reference logs as env/fps (rollout_buffer.jl:60-64, ppo.jl:176): env steps per second of the collection alone (HIP events around the rollout)
                 out["rollout_only_env_steps_per_s"] = N_local * world * steps / (rk["total_ms"] * 1e-3)
+        if dump_dir:                                     # rank 0's shard, after the timed region and its records
+            out["outputs_dumped"] = dump_outputs(dump_dir, ppo_outputs(pkg, h, last))
     h.close()
     return out
 
@@ -526,6 +581,9 @@ def main() -> None:
     ap.add_argument("--event-stride", type=int, default=7, help="bracket every K-th launch of the per-optimiser-step kernels with HIP events (1 = every launch; "
                     "an event record costs the stream ~3.5 us, 960 launches an iteration: 2 %% of configs[1] at K = 1).  7 is coprime to the 32 minibatches of an epoch: the "
                     "sampled launches visit every position of the epoch in turn (a stride of 8 always sampled positions 0, 8, 16, 24 — position 0 follows the epoch's index / moments kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them returned (statistics, parameters, the rollout "
+                    "buffer / replay ring: a fixed seeded sample of the large arrays) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; seeds are fixed, so two builds "
+                    "run with the same arguments can be compared array by array")
     ap.add_argument("--launch-timeout", type=float, default=1800.0, help="--gpus N > 1 without WORLD_SIZE: seconds the self-started ranks may take in total")
     ap.add_argument("--silent-timeout", type=float, default=420.0, help="... and seconds one rank may stay without a progress line (the first import of a fresh box takes 1-2 min)")
     args = ap.parse_args()
@@ -547,7 +605,7 @@ def main() -> None:
         if args.gpus != 1:
             raise SystemExit("--algo sac is a single-learner path: --gpus 1 only")
         print(json.dumps(run_sac(pkg, steps=args.steps, warmup=args.warmup, iters=args.sac_iters, E=args.n_envs if args.n_envs != 65536 else 4096,
-                                 H=args.hidden if args.hidden != 64 else 512, events=not args.no_events, cpu=not args.no_cpu_baseline)), flush=True)
+                                 H=args.hidden if args.hidden != 64 else 512, events=not args.no_events, cpu=not args.no_cpu_baseline, dump_dir=args.dump_outputs)), flush=True)
         return
 
     rank = int(os.environ.get("RANK", "0"))
@@ -561,7 +619,8 @@ def main() -> None:
         progress(rank, f"gloo rendezvous of {world} ranks done")
 
     out = run_ppo(pkg, env_name=args.env, E=args.n_envs, T=args.n_steps, hidden=args.hidden, minibatches=args.minibatches, epochs=args.epochs, normalize=args.normalize,
-                  steps=args.steps, warmup=args.warmup, events=0 if args.no_events else max(1, args.event_stride), rank=rank, local_rank=local_rank, world=world, dist=dist)
+                  steps=args.steps, warmup=args.warmup, events=0 if args.no_events else max(1, args.event_stride), rank=rank, local_rank=local_rank, world=world, dist=dist,
+                  dump_dir=args.dump_outputs)
     if rank == 0:
         default_workload = (args.env, args.n_envs, args.n_steps, args.hidden, args.minibatches, args.epochs, args.normalize) == ("cartpole", 65536, 2048, 64, 32, 10, False)
         out["metric"] = "env-steps/s (rollout+PPO update) at n_envs=65536" if args.n_envs == 65536 else out["metric"]

@@ -15,7 +15,8 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 def run_bench(extra_env, *argv, timeout=180):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY")}
+    # what the launcher sets or defaults is dropped from the inherited environment: the tests state their own (a machine that exports NCCL_DEBUG must not decide them)
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY", "NCCL_DEBUG")}
     env.update(DRIL_BENCH_STUB="1", **extra_env)
     t0 = time.monotonic()
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *argv], env=env, capture_output=True, text=True, timeout=timeout)
@@ -199,3 +200,79 @@ def test_the_json_line_fits_the_drivers_tail():
     assert c2["roofline"]["kernel"] == "ppo_grad_wide_split_kernel" and 0 < c2["roofline"]["frac"] < 1 and c2["value"] > 0
     c0 = [c for c in compact if "configs[0]" in c["workload"]][0]
     assert c0["cpu_baseline"]["kind"] == "port" and c0["cpu_baseline"]["value"] > 0
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_writes_float_arrays_within_its_limit(pkg, oracle_mod, tmp_path):
+    """--dump-outputs without a GPU: the pure helpers, and ppo_outputs on the CPU oracle (the same buffer / get_params verbs as the device handle) — every file is
+    float32 or float64, integer actions survive exactly, a large array is cut to one fixed sorted sample of rows, more than 64 MB is refused"""
+    import numpy as np
+    b = _bench_module()
+    assert np.array_equal(b.dump_rows(1000), np.arange(1000))
+    big = b.dump_rows(1 << 27)
+    assert len(big) == b.DUMP_ROWS and np.array_equal(big, b.dump_rows(1 << 27)) and np.all(np.diff(big) >= 0) and 0 <= big[0] and big[-1] < 1 << 27
+    capi = pkg._capi
+    cfg = capi.default_config(capi.ENV_CARTPOLE)
+    cfg.n_envs, cfg.n_steps, cfg.batch_size, cfg.epochs, cfg.episode_len = 8, 16, 64, 2, 20
+    o = oracle_mod.Oracle(cfg)
+    layer = pkg.ActorCriticLayer(pkg.CartPoleEnv().observation_space(), pkg.CartPoleEnv().action_space())
+    o.set_params(pkg.flatten_params(layer.initialparameters(np.random.default_rng(0)))); o.env_reset(1)
+    o.collect_rollout()
+    stats = o.ppo_update()
+    rec = b.dump_outputs(str(tmp_path / "d"), b.ppo_outputs(pkg, o, stats))
+    files = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert set(files) == set(rec["arrays"]) == {"ppo_stats", "params", "rollout_observations", "rollout_actions", "rollout_rewards", "rollout_values",
+                                                "rollout_logprobs", "rollout_advantages", "rollout_returns"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in (tmp_path / "d").glob("*.npy")) <= rec["bytes"] <= b.DUMP_MAX_BYTES
+    assert files["rollout_observations"].shape == (128, 4) and np.array_equal(files["rollout_actions"], o.buffer(capi.BUF_ACTIONS))
+    assert np.array_equal(files["params"], o.get_params()) and files["ppo_stats"][5] == np.float64(stats.loss) and files["ppo_stats"][10] == stats.n_updates
+    with pytest.raises(SystemExit):
+        b.dump_outputs(str(tmp_path / "e"), {"too_big": np.zeros((b.DUMP_MAX_BYTES // 4) + 1, np.float32)})
+    assert not (tmp_path / "e").exists()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeats_and_steps_sets_the_timed_steps(tmp_path):
+    """two runs of bench.py with the same arguments dump the same arrays (fixed seeds: inputs identical from run to run), as float32 / float64; --steps is the number of
+    timed iterations (one rollout_kernel launch each) and a run with another --steps ends elsewhere"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "DRIL_BENCH_STUB")}
+    dumps = []
+    for tag, steps in (("a", 3), ("b", 3), ("c", 2)):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--n-envs", "1024", "--n-steps", "64",
+                            "--no-cpu-baseline", "--no-secondary", "--event-stride", "1", "--dump-outputs", str(tmp_path / tag)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert rec["steps"] == steps and {k["kernel"]: k["launches"] for k in rec["hbm_kernels"]}["rollout_kernel"] == steps
+        files = {p.stem: np.load(p) for p in (tmp_path / tag).glob("*.npy")}
+        assert set(files) == set(rec["outputs_dumped"]["arrays"]) and len(files) == 9 and all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert files["rollout_values"].shape == (1024 * 64,) and files["ppo_stats"][5] == np.float64(np.float32(rec["loss_last"])) and np.isfinite(files["params"]).all()
+        dumps.append(files)
+    a, b, c = dumps
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert not np.array_equal(a["params"], c["params"])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_sac_path(tmp_path):
+    """--algo sac --dump-outputs: the statistics of every gradient step of the last timed step, the parameters it left and the replay ring, float32 / float64"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "DRIL_BENCH_STUB")}
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--algo", "sac", "--steps", "2", "--warmup", "1", "--sac-iters", "20", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path / "s")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    files = {p.stem: np.load(p) for p in (tmp_path / "s").glob("*.npy")}
+    assert set(files) == set(rec["outputs_dumped"]["arrays"]) == {"sac_stats", "params", "target_params", "log_ent_coef", "replay_observations", "replay_actions",
+                                                                 "replay_rewards", "replay_next_observations"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert files["sac_stats"].shape == (20, 7) and files["replay_observations"].shape[1] == 3 and len(files["replay_rewards"]) == len(files["replay_actions"])
+    assert sum(p.stat().st_size for p in (tmp_path / "s").glob("*.npy")) <= rec["outputs_dumped"]["bytes"] <= 64 << 20

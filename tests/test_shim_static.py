@@ -1,5 +1,5 @@
 """CPU: static checks of the Julia shim (tools/check_shim.py) — the image has no Julia, so dispatch specificity, the callback-locals keys and the
-ccall surface are verified by parsing DRiLHIP.jl against the reference's sources (when present) and include/*.h."""
+ccall surface are verified by parsing DRiLHIP.jl against the stored index of the reference's interface (tests/golden/reference_api.json) and include/*.h."""
 import subprocess
 import sys
 from pathlib import Path
@@ -21,9 +21,6 @@ def test_shim_passes_static_checks():
 
 def test_checker_catches_the_round1_ambiguity(tmp_path):
     """round 1 declared `train!(agent::Agent, env::DeviceParallelEnv, ...)`: wider than the reference in argument 1, narrower in argument 2"""
-    if not Path("/root/reference/src").exists():
-        import pytest
-        pytest.skip("needs the reference sources")
     bad = tmp_path / "DRiLHIP.jl"
     import shutil
     for f in SHIM.parent.glob("DRiLHIP_*.jl"): shutil.copy(f, tmp_path / f.name)

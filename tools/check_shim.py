@@ -2,7 +2,7 @@
 """Static checks of the Julia shim (dril.jl_amd/julia/DRiLHIP.jl) — what stands in for running it in an image without Julia.
 
   1. DISPATCH.  Every method the shim adds to one of DRiL's generic functions is compared, argument by argument, with every reference method of
-     the same name and positional arity (parsed from /root/reference/src).  Julia picks a method only if it is at least as specific in EVERY
+     the same name and positional arity (tests/golden/reference_api.json).  Julia picks a method only if it is at least as specific in EVERY
      positional argument and strictly more specific in at least one; "narrower in one argument, wider in another" is `MethodError: ambiguous`
      (round 1's bug: `agent::Agent` against the reference's `Agent{<:AbstractActorCriticLayer,<:PPO,...}`).  Keyword arguments take no part.
   2. CALLBACK LOCALS.  The keys the shim puts into the `locals` Dict == the Python mirror's (dril.jl_amd/host.py) and ⊇ the keys the reference's
@@ -12,11 +12,12 @@
   4. ccall PROTOTYPES.  Arity, pointer-ness and scalar width / kind of every argument type and of the result type of every ccall against the C prototype.
   5. BLOCK BALANCE.  Per .jl file: block openers == `end`s.
 
-Exit status 0 = all checks pass.  `--markdown` prints the dispatch table of INTEGRATION.md §2.  Without /root/reference (the GPU box) check 1 and the
-test-file half of check 2 are skipped and said so.
+Exit status 0 = all checks pass.  `--markdown` prints the dispatch table of INTEGRATION.md §2.  What checks 1 and 2 know about the reference is the stored index
+tests/golden/reference_api.json (written from a DRiL.jl checkout by tests/golden/make_reference_api.py, with this file's parsers), so they run wherever the repository is.
 """
 from __future__ import annotations
 
+import json
 import re
 import sys
 from pathlib import Path
@@ -32,7 +33,7 @@ def read_shim(path: Path) -> str:
         f = path.parent / m.group(1)
         return f.read_text() if f.exists() else m.group(0)
     return re.sub(r'^include\("([^"]+)"\).*$', sub, text, flags=re.M)
-REF = Path("/root/reference")
+REF_API = ROOT / "tests" / "golden" / "reference_api.json"
 
 BUILTIN_PARENTS = {"Int": "Signed", "Int64": "Signed", "Int32": "Signed", "Signed": "Integer", "Integer": "Real", "Real": "Number", "Number": "Any",
                    "Float32": "AbstractFloat", "Float64": "AbstractFloat", "AbstractFloat": "Real", "String": "AbstractString", "AbstractString": "Any",
@@ -165,24 +166,29 @@ def aliases_of(src: str) -> dict:
     return {m.group(1): m.group(2).strip() for m in re.finditer(r"^const\s+(\w+)\s*=\s*(\w[\w.]*\{.*\})\s*$", src, re.M)}
 
 
+def generic_names(shim: str) -> set[str]:
+    """the generic functions of DRiL the shim adds methods to: its `import DRiL:` list + the four it extends by qualified name"""
+    generic = set(re.findall(r"import DRiL:\s*([^\n]+(?:\n\s+[^\n]+)*)", shim)[0].replace("\n", " ").replace(" ", "").split(","))
+    return generic | {"evaluate_agent", "log_stats", "save_normalization_stats", "load_normalization_stats!"}
+
+
 def check_dispatch(markdown: bool) -> list[str]:
     errors = []
     shim = read_shim(SHIM)
-    if not REF.exists():
-        print("dispatch: /root/reference is absent here — skipped"); return errors
-    ref = julia_sources(REF / "src")
-    parents = type_parents(ref); parents.update({k: v for k, v in type_parents(shim).items() if k not in parents})
+    api = json.loads(REF_API.read_text())
+    parents = dict(BUILTIN_PARENTS); parents.update(api["types"]); parents.update({k: v for k, v in type_parents(shim).items() if k not in parents})
     al = aliases_of(shim)
-    generic = set(re.findall(r"import DRiL:\s*([^\n]+(?:\n\s+[^\n]+)*)", shim)[0].replace("\n", " ").replace(" ", "").split(","))
-    generic |= {"evaluate_agent", "log_stats", "save_normalization_stats", "load_normalization_stats!"}
+    generic = generic_names(shim)
+    if not generic <= set(api["generic_functions"]):
+        errors.append(f"tests/golden/reference_api.json holds no methods of {sorted(generic - set(api['generic_functions']))}: rerun tests/golden/make_reference_api.py")
     rows = []
     for sm in methods(shim, generic):
         s_types = [parse_type(t, al, sm["typevars"]) for _, t in sm["args"]]
-        for rm in methods(ref, {sm["name"]}):
+        for rm in (m for m in api["methods"] if m["name"] == sm["name"]):
             if len(rm["args"]) != len(sm["args"]):
                 continue
             try:
-                r_types = [parse_type(t, {}, rm["typevars"]) for _, t in rm["args"]]
+                r_types = [parse_type(t, {}, rm["typevars"]) for t in rm["args"]]
             except ValueError:
                 continue                                        # Union-typed positional etc.: not a method the shim competes with
             rel = []
@@ -199,9 +205,8 @@ def check_dispatch(markdown: bool) -> list[str]:
                 verdict = "reference more specific"; errors.append(f"DRiLHIP.jl:{sm['line']} {sm['name']}: the reference method is MORE specific {rel}")
             else:
                 verdict = "IDENTICAL SIGNATURE (overwrites the reference method)"; errors.append(f"DRiLHIP.jl:{sm['line']} {sm['name']} redefines a reference method")
-            sig = lambda mm: ", ".join(t for _, t in mm["args"])
             if "x" not in rel:                                  # disjoint pairs are noise in the table
-                rows.append((f"`{sm['name']}({sig(sm)})` :{sm['line']}", f"`{sm['name']}({sig(rm)})`", " ".join(rel), verdict))
+                rows.append((f"`{sm['name']}({', '.join(t for _, t in sm['args'])})` :{sm['line']}", f"`{sm['name']}({', '.join(rm['args'])})`", " ".join(rel), verdict))
     if markdown:
         print("| shim method (DRiLHIP.jl:line) | reference method | per-argument (shim vs reference) | dispatch |\n|---|---|---|---|")
         for r in rows:
@@ -230,18 +235,13 @@ def check_locals() -> list[str]:
     for ks in dict_keys:
         if not (start | roll) <= ks:
             errors.append(f"a locals() Dict lacks {sorted((start | roll) - ks)}")
-    test = REF / "test" / "test_callbacks.jl"
-    if test.exists():
-        t = test.read_text()
-        need_start = set(re.findall(r":(\w+)", re.search(r"OnTrainingStartCheckLocalsCallback.*?keys::Vector\{Symbol\} = \[(.*?)\]", t, re.S).group(1)))
-        need_roll = set(re.findall(r":(\w+)", re.search(r"first_keys::Vector\{Symbol\} = \[(.*?)\]", t, re.S).group(1)))
-        if not need_start <= start:
-            errors.append(f"training-start locals lack {sorted(need_start - start)} (test/test_callbacks.jl:25-27)")
-        if not need_roll <= start | roll:
-            errors.append(f"rollout-start locals lack {sorted(need_roll - (start | roll))} (test/test_callbacks.jl:36-39)")
-        print(f"locals: test_callbacks.jl needs {sorted(need_start | need_roll)}; shim provides {sorted(start | roll)}")
-    else:
-        print("locals: /root/reference/test/test_callbacks.jl is absent here — only shim == python mirror was checked")
+    need = json.loads(REF_API.read_text())["callback_locals"]
+    need_start, need_roll = set(need["training_start"]), set(need["rollout_start"])
+    if not need_start <= start:
+        errors.append(f"training-start locals lack {sorted(need_start - start)} (test/test_callbacks.jl:25-27)")
+    if not need_roll <= start | roll:
+        errors.append(f"rollout-start locals lack {sorted(need_roll - (start | roll))} (test/test_callbacks.jl:36-39)")
+    print(f"locals: test_callbacks.jl needs {sorted(need_start | need_roll)}; shim provides {sorted(start | roll)}")
     return errors
 
 
