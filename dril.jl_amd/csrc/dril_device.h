@@ -64,6 +64,37 @@ __device__ inline float randn_f32(uint32_t a, uint32_t b) {
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
+// Philox streams: every random number of the library is a word of philox4x32_10(key; c0, c1, c2, c3), and counter word c2 is the STREAM id — the one place that
+// says who owns which words (the CPU oracle under oracle/ restates them independently):
+//   c2          key                       c0, c1              c3                   owner
+//   0           env seed (seed0 + e)      episode, 0          0                    env_reset<KIND>: the initial state of an episode
+//   1           env seed                  gstep, 0            component / 2        env_noise_*: the action noise of a device env at its global step — the same draw on
+//                                                                                  every collection path (policy_kernel / generic head with device envs, both rollout kernels, SAC)
+//   2           handle seed               update counter      epoch                perm_key (dril_api.hip): key of the epoch's index bijection
+//   3 + 16 i    call seed                 row (64 bit)        call counter         call_noise_*: dril_policy_forward on a host batch (no device envs), action component i
+//   4           SAC update key            update counter      sample               sac_gather_kernel / sac_gather_l1_kernel (dril_sac.hip): replay indices
+//   5 .. 8      SAC update / aux key      counter             4 sample + a / 2     sac_noise (dril_sac.hip): the update's three noise draws, sac_noise_fill_kernel
+__device__ __forceinline__ double env_noise_u01(uint64_t env_seed, uint32_t gstep) {                      // Categorical: the uniform of the inverse-CDF draw
+    uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gstep, 0, 1, 0, r);
+    return u01_f64(r[0], r[1]);
+}
+__device__ __forceinline__ float env_noise_randn(uint64_t env_seed, uint32_t gstep, int i) {              // DiagGaussian: the standard normal of action component i (two per block)
+    uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gstep, 0, 1, (uint32_t)(i / 2), r);
+    return (i & 1) ? randn_f32(r[2], r[3]) : randn_f32(r[0], r[1]);
+}
+__device__ __forceinline__ float env_noise_u01_f32(uint64_t env_seed, uint32_t gstep, int i) {            // SAC's random-action phase: a uniform from the block env_noise_randn(i) uses
+    uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gstep, 0, 1, (uint32_t)(i / 2), r);
+    return u01_f32((i & 1) ? r[2] : r[0]);
+}
+__device__ __forceinline__ double call_noise_u01(uint64_t seed, int64_t row, uint32_t call_counter) {
+    uint32_t r[4]; philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)row, (uint32_t)(row >> 32), 3, call_counter, r);
+    return u01_f64(r[0], r[1]);
+}
+__device__ __forceinline__ float call_noise_randn(uint64_t seed, int64_t row, int i, uint32_t call_counter) {
+    uint32_t r[4]; philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)row, (uint32_t)(row >> 32), 3 + 16 * (uint32_t)i, call_counter, r);
+    return randn_f32(r[0], r[1]);
+}
+
 // keyed bijection on [0, n): position in the epoch -> buffer index (DataLoader(shuffle=true), ppo.jl:188-195)
 __host__ __device__ inline uint64_t mix_bij(uint64_t x, uint64_t key, int bits) {
     const uint64_t mask = bits >= 64 ? ~0ull : (((uint64_t)1 << bits) - 1);
@@ -402,6 +433,55 @@ template <int KIND> __device__ inline float env_step(float* st, float act_f, int
         *terminated = false;
         return -cost;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// act! with auto-reset under MonitorWrapperEnv (multithreadedParallelEnv.jl:56-71, monitorWrapperEnv.jl:46-60): the ONE definition of an env's transition.  Every
+// collection path — env_step_kernel, norm_step_kernel, rollout_kernel, rollout_duo_kernel, sac_collect_env_kernel — is
+//     EnvCursor::load -> { env_advance -> [terminal observation = env_obs of the cursor HERE: after the step, before the reset] -> env_end_episode }* -> EnvCursor::store
+// (the per-step kernels run the braces once, the persistent ones T times with the cursor in registers) and keeps only what is its own: where the results are stored,
+// and under which condition it computes the terminal observation.
+// ---------------------------------------------------------------------------------------------
+struct EnvArrays { float* state; int32_t* step_count; uint32_t* episode; uint32_t* gstep; float* mon_cur_ret; int32_t* mon_cur_len; };   // mon_*: null = MonitorWrapperEnv off
+template <int KIND> struct EnvCursor {
+    static constexpr int S = EnvSpec<KIND>::S;
+    float st[S]; int sc; uint32_t ep, gs;       // simulator state, steps into the episode, episode number, steps since reset! (the noise stream's position)
+    float mon_ret; int mon_len;                 // MonitorWrapperEnv's running episode return / length (no load, no store with the monitor off)
+    __device__ __forceinline__ void load(const EnvArrays& a, int e) {
+#pragma unroll
+        for (int i = 0; i < S; ++i) st[i] = a.state[(size_t)e * S + i];
+        sc = a.step_count[e]; ep = a.episode[e]; gs = a.gstep[e];
+        mon_ret = a.mon_cur_ret ? a.mon_cur_ret[e] : 0.f;
+        mon_len = a.mon_cur_len ? a.mon_cur_len[e] : 0;
+    }
+    __device__ __forceinline__ void store(const EnvArrays& a, int e) const {
+#pragma unroll
+        for (int i = 0; i < S; ++i) a.state[(size_t)e * S + i] = st[i];
+        a.step_count[e] = sc; a.episode[e] = ep; a.gstep[e] = gs;
+        if (a.mon_cur_ret) { a.mon_cur_ret[e] = mon_ret; a.mon_cur_len[e] = mon_len; }
+    }
+};
+struct StepOut {
+    float rew; bool term, trunc;
+    __device__ __forceinline__ bool done() const { return term || trunc; }
+    __device__ __forceinline__ uint8_t flags() const { return (uint8_t)((term ? 1 : 0) | (trunc ? 2 : 0)); }   // the BUF_FLAGS encoding
+};
+// the step: physics, counters, truncation at episode_len, the monitor's sums (raw reward)
+template <int KIND> __device__ __forceinline__ StepOut env_advance(EnvCursor<KIND>& c, float act_f, int act_i, int episode_len, bool fixed_len) {
+    StepOut o;
+    o.rew = env_step<KIND>(c.st, act_f, act_i, fixed_len, &o.term);
+    c.sc += 1; c.gs += 1;
+    o.trunc = c.sc >= episode_len;
+    c.mon_ret += o.rew; c.mon_len += 1;
+    return o;
+}
+// where the episode ended (o.done()): the finished episode's return / length (monitorWrapperEnv.jl:53-58) go to *fin_ret / *fin_len (null: nowhere — monitor off, or
+// not this lane's to write), the next episode starts (reset!) and the monitor's sums restart
+template <int KIND> __device__ __forceinline__ void env_end_episode(EnvCursor<KIND>& c, uint64_t env_seed, const StepOut& o, float* fin_ret, int32_t* fin_len) {
+    if (!o.done()) return;
+    if (fin_ret) { *fin_ret = c.mon_ret; *fin_len = c.mon_len; }
+    c.ep += 1; c.sc = 0; env_reset<KIND>(env_seed, c.ep, c.st);
+    c.mon_ret = 0.f; c.mon_len = 0;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -128,8 +128,8 @@ __global__ void generic_policy_head_kernel(PolicyHeadArgs g) {
             } else {
                 double u;
                 if (a.noise) u = ((const double*)a.noise)[b];
-                else if (a.gstep) { const uint64_t k = a.env_seed0 + (uint64_t)b; uint32_t r[4]; philox4x32_10((uint32_t)k, (uint32_t)(k >> 32), a.gstep[b], 0, 1, 0, r); u = u01_f64(r[0], r[1]); }   // device envs: the env-keyed stream of rollout_kernel
-                else { uint32_t r[4]; philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)b, (uint32_t)(b >> 32), 3, a.call_counter, r); u = u01_f64(r[0], r[1]); }
+                else if (a.gstep) u = env_noise_u01(a.env_seed0 + (uint64_t)b, a.gstep[b]);   // device envs: the env-keyed stream of rollout_kernel
+                else u = call_noise_u01(a.seed, b, a.call_counter);
                 float cs = 0.f; act = A - 1;                                          // findfirst(cumsum(p) .>= u), categorical.jl:47-52
                 for (int k = 0; k < A; ++k) { cs += expf(z[k] - m) / s; if ((double)cs >= u) { act = k; break; } }
             }
@@ -145,8 +145,8 @@ __global__ void generic_policy_head_kernel(PolicyHeadArgs g) {
             for (int k = 0; k < A; ++k) {
                 float n01;
                 if (a.noise) n01 = ((const float*)a.noise)[b * A + k];
-                else if (a.gstep) { const uint64_t kk = a.env_seed0 + (uint64_t)b; uint32_t r[4]; philox4x32_10((uint32_t)kk, (uint32_t)(kk >> 32), a.gstep[b], 0, 1, (uint32_t)(k / 2), r); n01 = (k & 1) ? randn_f32(r[2], r[3]) : randn_f32(r[0], r[1]); }
-                else { uint32_t r[4]; philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)b, (uint32_t)(b >> 32), 3 + 16 * (uint32_t)k, a.call_counter, r); n01 = randn_f32(r[0], r[1]); }
+                else if (a.gstep) n01 = env_noise_randn(a.env_seed0 + (uint64_t)b, a.gstep[b], k);
+                else n01 = call_noise_randn(a.seed, b, k, a.call_counter);
                 x[k] = a.deterministic ? z[k] : z[k] + expf(ls[k]) * n01;                // diagGaussian.jl:13-17, mode(d) = mean :45-47
             }
         }

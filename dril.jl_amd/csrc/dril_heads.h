@@ -52,5 +52,18 @@ template <int A> __device__ __forceinline__ float gauss_entropy(const float* ls)
     return 0.5f * (float)A * (1.0f + kLog2Pi) + lss;
 }
 
+// rand(d) and logpdf(d, action) of the sampling forward (layer_forward.jl:10-11 / :36-37) — policy_kernel mode 0, rollout_kernel, rollout_duo_kernel.  The caller brings
+// the noise (injected buffer, env stream or call stream: dril_device.h) and does the stores
+template <int A> __device__ __forceinline__ int sample_categorical(const float (&out)[A], double u, float* logp) {
+    float p[A]; softmax_n<A>(out, p);
+    const int act = categorical_sample<A>(p, u);
+    *logp = flog(pick<A>(p, act));
+    return act;
+}
+template <int A> __device__ __forceinline__ void sample_gaussian(const float (&out)[A], const float* ls, const float (&z)[A], float (&x)[A], float* logp) {
+#pragma unroll
+    for (int i = 0; i < A; ++i) x[i] = out[i] + fexp(ls[i]) * z[i];
+    *logp = gauss_logpdf<A>(x, out, ls);
+}
 
 }  // namespace dril

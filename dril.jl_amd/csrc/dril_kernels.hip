@@ -57,29 +57,19 @@ __global__ void env_step_kernel(int E, uint64_t seed0, int episode_len, int fixe
                                 uint32_t* gstep, float* rewards, uint8_t* term, uint8_t* trunc, float* terminal_obs, MonitorArgs mon) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    constexpr int S = EnvSpec<KIND>::S, D = EnvSpec<KIND>::D;
-    float st[S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) st[i] = state[(size_t)e * S + i];
+    constexpr int D = EnvSpec<KIND>::D;
+    const EnvArrays env{state, step_count, episode, gstep, mon.cur_ret, mon.cur_len};
+    EnvCursor<KIND> cur; cur.load(env, e);
     int ai = 0; float af = 0.f;
     if (EnvSpec<KIND>::discrete) ai = ((const int32_t*)actions)[e] - action_start; else af = ((const float*)actions)[e];
-    bool t;
-    const float r = env_step<KIND>(st, af, ai, fixed_len != 0, &t);
-    const int sc = step_count[e] + 1;
-    const bool tr = sc >= episode_len;
-    rewards[e] = r; term[e] = t; trunc[e] = tr; gstep[e] += 1;
-    if (mon.cur_ret) {                                             // MonitorWrapperEnv.act! (monitorWrapperEnv.jl:46-60), raw reward
-        const float cr = mon.cur_ret[e] + r; const int cl = mon.cur_len[e] + 1;
-        if (t || tr) { mon.ep_ret[e] = cr; mon.ep_len[e] = cl; mon.cur_ret[e] = 0.f; mon.cur_len[e] = 0; } else { mon.cur_ret[e] = cr; mon.cur_len[e] = cl; }
-        mon.flags_out[e] = (uint8_t)((t ? 1 : 0) | (tr ? 2 : 0));
-    }
-    if (tr) { float o[D]; env_obs<KIND>(st, o);
+    const StepOut so = env_advance<KIND>(cur, af, ai, episode_len, fixed_len != 0);
+    rewards[e] = so.rew; term[e] = so.term; trunc[e] = so.trunc;
+    if (mon.cur_ret) mon.flags_out[e] = so.flags();
+    if (so.trunc) { float o[D]; env_obs<KIND>(cur.st, o);
 #pragma unroll
         for (int i = 0; i < D; ++i) terminal_obs[(size_t)e * D + i] = o[i]; }
-    if (t || tr) { const uint32_t ep = episode[e] + 1; episode[e] = ep; step_count[e] = 0; env_reset<KIND>(seed0 + (uint64_t)e, ep, st); }
-    else step_count[e] = sc;
-#pragma unroll
-    for (int i = 0; i < S; ++i) state[(size_t)e * S + i] = st[i];
+    env_end_episode<KIND>(cur, seed0 + (uint64_t)e, so, mon.cur_ret ? mon.ep_ret + e : nullptr, mon.ep_len + e);
+    cur.store(env, e);
 }
 
 // =============================================================================================
@@ -225,38 +215,28 @@ __global__ void norm_rew_apply_kernel(NormRewArgs a) {
 // normalizeWrapperEnv.jl:157-163) and the next observations (NEW statistics, :123-137).  7 launches per env step -> 3.
 template <int KIND>
 __global__ void norm_step_kernel(NormStepArgs a) {
-    constexpr int S = EnvSpec<KIND>::S, D = EnvSpec<KIND>::D;
+    constexpr int D = EnvSpec<KIND>::D;
+    const EnvArrays env{a.state, a.step_count, a.episode, a.gstep, a.mon_cur_ret, a.mon_cur_len};   // MonitorWrapperEnv sits inside the normaliser: raw reward
     __shared__ double sh[16];
     double acc[2 + 2 * D];
 #pragma unroll
     for (int i = 0; i < 2 + 2 * D; ++i) acc[i] = 0;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < a.E; e += gridDim.x * blockDim.x) {
-        float st[S];
-#pragma unroll
-        for (int i = 0; i < S; ++i) st[i] = a.state[(size_t)e * S + i];
+        EnvCursor<KIND> cur; cur.load(env, e);
         int ai = 0; float af = 0.f;
         if (EnvSpec<KIND>::discrete) ai = ((const int32_t*)a.actions)[e] - a.action_start; else af = ((const float*)a.actions)[e];
-        bool t;
-        const float r = env_step<KIND>(st, af, ai, a.fixed_len != 0, &t);
-        const int sc = a.step_count[e] + 1;
-        const bool tr = sc >= a.episode_len;
-        a.rew_raw[e] = r; a.term[e] = t; a.trunc[e] = tr; a.gstep[e] += 1;
-        if (a.flags_out) a.flags_out[e] = (uint8_t)((t ? 1 : 0) | (tr ? 2 : 0));
-        if (a.mon_cur_ret) {                                       // MonitorWrapperEnv sits inside the normaliser: raw reward
-            const float cr = a.mon_cur_ret[e] + r; const int cl = a.mon_cur_len[e] + 1;
-            if (t || tr) { a.ep_ret[e] = cr; a.ep_len[e] = cl; a.mon_cur_ret[e] = 0.f; a.mon_cur_len[e] = 0; } else { a.mon_cur_ret[e] = cr; a.mon_cur_len[e] = cl; }
-        }
+        const StepOut so = env_advance<KIND>(cur, af, ai, a.episode_len, a.fixed_len != 0);
+        a.rew_raw[e] = so.rew; a.term[e] = so.term; a.trunc[e] = so.trunc;
+        if (a.flags_out) a.flags_out[e] = so.flags();
         float disc = a.disc_returns[e];
-        if (a.update_ret) { disc = disc * a.gamma + r; a.disc_returns[e] = disc; }       // update_reward_stats! :167-171 (reset of done envs happens in norm_apply_kernel)
+        if (a.update_ret) { disc = disc * a.gamma + so.rew; a.disc_returns[e] = disc; }  // update_reward_stats! :167-171 (reset of done envs happens in norm_apply_kernel)
         acc[0] += disc; acc[1] += (double)disc * disc;
-        if (tr) { float o[D]; env_obs<KIND>(st, o);
+        if (so.trunc) { float o[D]; env_obs<KIND>(cur.st, o);
 #pragma unroll
             for (int i = 0; i < D; ++i) a.tobs_raw[(size_t)e * D + i] = o[i]; }
-        if (t || tr) { const uint32_t ep = a.episode[e] + 1; a.episode[e] = ep; a.step_count[e] = 0; env_reset<KIND>(a.seed0 + (uint64_t)e, ep, st); }
-        else a.step_count[e] = sc;
-#pragma unroll
-        for (int i = 0; i < S; ++i) a.state[(size_t)e * S + i] = st[i];
-        float o[D]; env_obs<KIND>(st, o);
+        env_end_episode<KIND>(cur, a.seed0 + (uint64_t)e, so, a.mon_cur_ret ? a.ep_ret + e : nullptr, a.ep_len + e);
+        cur.store(env, e);
+        float o[D]; env_obs<KIND>(cur.st, o);
 #pragma unroll
         for (int d = 0; d < D; ++d) { a.obs_raw[(size_t)e * D + d] = o[d]; acc[2 + 2 * d] += o[d]; acc[3 + 2 * d] += (double)o[d] * o[d]; }
     }
@@ -613,48 +593,89 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void policy_kernel(PolicyArgs a)
         if (a.mode == 2) continue;
         float out[A];
         eval_net<D, H, A, WIDE, SPLIT>(la, a.w2a_actor, xk, out, lane);
+        const bool sample = a.mode == 0 && !a.deterministic, store = valid && h == 0;
+        float logp;
         if (DISC) {
-            float p[A]; softmax_n<A>(out, p);
             int act;
-            if (a.mode == 0) {
+            if (sample) {
                 double u;
                 if (a.noise) u = ((const double*)a.noise)[bb];
-                else if (a.gstep) { const uint64_t k = a.env_seed0 + (uint64_t)bb; uint32_t r[4]; philox4x32_10((uint32_t)k, (uint32_t)(k >> 32), a.gstep[bb], 0, 1, 0, r); u = u01_f64(r[0], r[1]); }
-                else { uint32_t r[4]; philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)bb, (uint32_t)(bb >> 32), 3, a.call_counter, r); u = u01_f64(r[0], r[1]); }
-                act = categorical_sample<A>(p, u);
-                if (a.deterministic) {                                   // mode(d) = argmax(p) (first maximum), categorical.jl:42-44
+                else if (a.gstep) u = env_noise_u01(a.env_seed0 + (uint64_t)bb, a.gstep[bb]);
+                else u = call_noise_u01(a.seed, bb, a.call_counter);
+                act = sample_categorical<A>(out, u, &logp);
+            } else {
+                float p[A]; softmax_n<A>(out, p);
+                if (a.mode == 0) {                                       // mode(d) = argmax(p) (first maximum), categorical.jl:42-44
                     act = 0; float best = p[0];
 #pragma unroll
                     for (int i = 1; i < A; ++i) if (p[i] > best) { best = p[i]; act = i; }
-                }
-                if (valid && h == 0) ((int32_t*)a.actions)[b] = act + a.action_start;
-            } else act = ((const int32_t*)a.actions)[bb] - a.action_start;
-            if (valid && h == 0) {
-                a.logp[b] = flog(pick<A>(p, act));
-                if (a.mode == 1 && a.entropy) a.entropy[b] = categorical_entropy<A>(p);
+                } else act = ((const int32_t*)a.actions)[bb] - a.action_start;
+                logp = flog(pick<A>(p, act));
+                if (store && a.mode == 1 && a.entropy) a.entropy[b] = categorical_entropy<A>(p);
             }
+            if (store && a.mode == 0) ((int32_t*)a.actions)[b] = act + a.action_start;
         } else {
             const float* ls = a.params + a.log_std_off;
             float x[A];
-            if (a.mode == 0) {
+            if (sample) {
+                float z[A];
 #pragma unroll
                 for (int i = 0; i < A; ++i) {
-                    float z;
-                    if (a.noise) z = ((const float*)a.noise)[bb * A + i];
-                    else if (a.gstep) { const uint64_t k = a.env_seed0 + (uint64_t)bb; uint32_t r[4]; philox4x32_10((uint32_t)k, (uint32_t)(k >> 32), a.gstep[bb], 0, 1, (uint32_t)(i / 2), r); z = (i & 1) ? randn_f32(r[2], r[3]) : randn_f32(r[0], r[1]); }
-                    else { uint32_t r[4]; philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)bb, (uint32_t)(bb >> 32), 3 + 16 * (uint32_t)i, a.call_counter, r); z = randn_f32(r[0], r[1]); }
-                    x[i] = a.deterministic ? out[i] : out[i] + fexp(ls[i]) * z;            // mode(d) = mean, diagGaussian.jl:45-47
-                    if (valid && h == 0) ((float*)a.actions)[b * A + i] = x[i];
+                    if (a.noise) z[i] = ((const float*)a.noise)[bb * A + i];
+                    else if (a.gstep) z[i] = env_noise_randn(a.env_seed0 + (uint64_t)bb, a.gstep[bb], i);
+                    else z[i] = call_noise_randn(a.seed, bb, i, a.call_counter);
                 }
+                sample_gaussian<A>(out, ls, z, x, &logp);
             } else {
 #pragma unroll
-                for (int i = 0; i < A; ++i) x[i] = ((const float*)a.actions)[bb * A + i];
+                for (int i = 0; i < A; ++i) x[i] = a.mode == 0 ? out[i] : ((const float*)a.actions)[bb * A + i];   // mode(d) = mean, diagGaussian.jl:45-47
+                logp = gauss_logpdf<A>(x, out, ls);
             }
-            if (valid && h == 0) {
-                a.logp[b] = gauss_logpdf<A>(x, out, ls);
-                if (a.mode == 1 && a.entropy) a.entropy[b] = gauss_entropy<A>(ls);
+            if (store && a.mode == 0) {
+#pragma unroll
+                for (int i = 0; i < A; ++i) ((float*)a.actions)[b * A + i] = x[i];
             }
+            if (store && a.mode == 1 && a.entropy) a.entropy[b] = gauss_entropy<A>(ls);
         }
+        if (store) a.logp[b] = logp;
+    }
+}
+
+// =============================================================================================
+// what rollout_kernel and rollout_duo_kernel share around their own schedules: the prologue's log_std, and the sampling block of a step
+// =============================================================================================
+// log_std in registers for the whole rollout (the parameters are read-only during it)
+template <int KIND> __device__ __forceinline__ void rollout_log_std(const RolloutArgs& a, float (&lsr)[4]) {
+    constexpr int A = EnvSpec<KIND>::A;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) lsr[i] = 0.f;
+    if (!EnvSpec<KIND>::discrete) {
+#pragma unroll
+        for (int i = 0; i < (A < 4 ? A : 4); ++i) lsr[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.params[a.log_std_off + i])));
+    }
+}
+// sample (layer_forward.jl:10-11 / :36-37) for buffer row k: the noise (injected buffer, or the env's stream at global step gs), the head, the store of the RAW action
+// (trajectory.jl:48), the action the env receives, and the log-probability (stored by the caller with the row's other values: one store region per step)
+template <int KIND>
+__device__ __forceinline__ void rollout_sample(const RolloutArgs& a, size_t k, uint64_t env_seed, uint32_t gs, const float (&out)[EnvSpec<KIND>::A], const float* ls,
+                                               bool writer, int* act_env, float* actf_env, float* logp) {
+    constexpr int A = EnvSpec<KIND>::A;
+    if (EnvSpec<KIND>::discrete) {
+        double u;
+        if (a.noise) u = ((const double*)a.noise)[k]; else u = env_noise_u01(env_seed, gs);
+        const int act = sample_categorical<A>(out, u, logp);
+        *act_env = act;                                                      // DiscreteAdapter: identity (default_adapters.jl:34-38)
+        if (writer) ((int32_t*)a.act)[k] = act + a.action_start;
+    } else {
+        float z[A], x[A];
+#pragma unroll
+        for (int i = 0; i < A; ++i) { if (a.noise) z[i] = ((const float*)a.noise)[k * A + i]; else z[i] = env_noise_randn(env_seed, gs, i); }
+        sample_gaussian<A>(out, ls, z, x, logp);
+        if (writer) {
+#pragma unroll
+            for (int i = 0; i < A; ++i) ((float*)a.act)[k * A + i] = x[i];
+        }
+        *actf_env = fminf(fmaxf(x[0], -act_bound<KIND>()), act_bound<KIND>());   // ClampAdapter on action_space(env) (default_adapters.jl:4-11)
     }
 }
 
@@ -666,8 +687,7 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void policy_kernel(PolicyArgs a)
 // =============================================================================================
 template <int KIND, int H, bool WIDE, bool SPLIT>
 __global__ __launch_bounds__(256, WIDE ? 1 : 2) void rollout_kernel(RolloutArgs a) {
-    constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A, S = EnvSpec<KIND>::S;
-    constexpr bool DISC = EnvSpec<KIND>::discrete;
+    constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* la = smem; float* lc = smem + FwdLds<D, H, A, WIDE, SPLIT>::SIZE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -681,22 +701,12 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void rollout_kernel(RolloutArgs 
     const int e = valid ? e_raw : a.E - 1;
     const bool writer = valid && h == 0;
     const uint64_t env_seed = a.env_seed0 + (uint64_t)e;
+    const EnvArrays env{a.state, a.step_count, a.episode, a.gstep, a.mon_cur_ret, a.mon_cur_len};
 
-    float st[S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) st[i] = a.state[(size_t)e * S + i];
-    int sc = a.step_count[e];
-    uint32_t ep = a.episode[e], gs = a.gstep[e];
+    EnvCursor<KIND> cur; cur.load(env, e);
     float obs[D];
-    env_obs<KIND>(st, obs);
-    float lsr[4] = {0.f, 0.f, 0.f, 0.f};                               // log_std in registers for the whole rollout (the parameters are read-only during it)
-    if (!DISC) {
-#pragma unroll
-        for (int i = 0; i < (A < 4 ? A : 4); ++i) lsr[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.params[a.log_std_off + i])));
-    }
-    const float* ls = lsr;
-    float mon_ret = a.mon_cur_ret ? a.mon_cur_ret[e] : 0.f;           // MonitorWrapperEnv running episode return / length
-    int mon_len = a.mon_cur_len ? a.mon_cur_len[e] : 0;
+    env_obs<KIND>(cur.st, obs);
+    float lsr[4]; rollout_log_std<KIND>(a, lsr);
 
     for (int t = 0; t < a.T; ++t) {
         const size_t k = (size_t)t * a.E + e;
@@ -711,30 +721,8 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void rollout_kernel(RolloutArgs 
         __builtin_amdgcn_sched_barrier(0);   // do not interleave the two nets: that doubles the live weight fragments
         eval_net<D, H, A, WIDE, SPLIT>(la_t, a.w2a_actor, xk, out, lane);
         __builtin_amdgcn_sched_barrier(0);
-        // ---- sample (layer_forward.jl:10-11 / :36-37) ----
-        int act_env = 0; float actf_env = 0.f; float logp;
-        if (DISC) {
-            float p[A]; softmax_n<A>(out, p);
-            double u;
-            if (a.noise) u = ((const double*)a.noise)[k];
-            else { uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gs, 0, 1, 0, r); u = u01_f64(r[0], r[1]); }
-            const int act = categorical_sample<A>(p, u);
-            logp = flog(pick<A>(p, act));
-            act_env = act;                                                   // DiscreteAdapter: identity (default_adapters.jl:34-38)
-            if (writer) ((int32_t*)a.act)[k] = act + a.action_start;         // raw action stored (trajectory.jl:48)
-        } else {
-            float x[A];
-#pragma unroll
-            for (int i = 0; i < A; ++i) {
-                float z;
-                if (a.noise) z = ((const float*)a.noise)[k * A + i];
-                else { uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gs, 0, 1, (uint32_t)(i / 2), r); z = (i & 1) ? randn_f32(r[2], r[3]) : randn_f32(r[0], r[1]); }
-                x[i] = out[i] + fexp(ls[i]) * z;
-                if (writer) ((float*)a.act)[k * A + i] = x[i];
-            }
-            logp = gauss_logpdf<A>(x, out, ls);
-            actf_env = fminf(fmaxf(x[0], -act_bound<KIND>()), act_bound<KIND>());   // ClampAdapter on action_space(env) (default_adapters.jl:4-11)
-        }
+        int act_env = 0; float actf_env = 0.f, logp;
+        rollout_sample<KIND>(a, k, env_seed, cur.gs, out, lsr, writer, &act_env, &actf_env, &logp);
         if (writer) {
             if (D == 4) *reinterpret_cast<float4*>(a.obs + k * 4) = make_float4(obs[0], obs[1], obs[2], obs[3]);
             else {
@@ -743,27 +731,19 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void rollout_kernel(RolloutArgs 
             }
             a.val[k] = v[0]; a.logp[k] = logp;
         }
-        // ---- act! with auto-reset (multithreadedParallelEnv.jl:56-71) ----
-        bool term;
-        const float rew = env_step<KIND>(st, actf_env, act_env, a.fixed_len != 0, &term);
-        sc += 1; gs += 1;
-        const bool trunc = sc >= a.episode_len;
-        if (__any(trunc && valid)) {                                         // V(terminal_observation), trajectory.jl:57-61
-            float tobs[D]; env_obs<KIND>(st, tobs);
+        // ---- act! with auto-reset (EnvCursor, dril_device.h) ----
+        const StepOut so = env_advance<KIND>(cur, actf_env, act_env, a.episode_len, a.fixed_len != 0);
+        if (__any(so.trunc && valid)) {                                      // V(terminal_observation), trajectory.jl:57-61
+            float tobs[D]; env_obs<KIND>(cur.st, tobs);
             float tk[FirstLayer<D>::KS];
             pair_obs<D>(tobs, h, tk);
             float bv[1];
             eval_net<D, H, 1, WIDE, SPLIT>(lc_t, a.w2a_critic, tk, bv, lane);
-            if (writer && trunc) a.boot[k] = bv[0];
+            if (writer && so.trunc) a.boot[k] = bv[0];
         }
-        mon_ret += rew; mon_len += 1;
-        if (term || trunc) {
-            ep += 1; sc = 0; env_reset<KIND>(env_seed, ep, st);
-            if (writer && a.ep_ret) { a.ep_ret[k] = mon_ret; a.ep_len[k] = mon_len; }     // finished episode (monitorWrapperEnv.jl:53-58)
-            mon_ret = 0.f; mon_len = 0;
-        }
-        if (writer) { a.rew[k] = rew; a.flags[k] = (uint8_t)((term ? 1 : 0) | (trunc ? 2 : 0)); }
-        env_obs<KIND>(st, obs);                                              // observe(env), trajectory.jl:45
+        env_end_episode<KIND>(cur, env_seed, so, writer && a.ep_ret ? a.ep_ret + k : nullptr, a.ep_len + k);
+        if (writer) { a.rew[k] = so.rew; a.flags[k] = so.flags(); }
+        env_obs<KIND>(cur.st, obs);                                          // observe(env), trajectory.jl:45
     }
     {   // V(new_obs) for rollout-limited trajectories, trajectory.jl:65-70 (computed for every env; GAE uses it when needed)
         float xk[FirstLayer<D>::KS];
@@ -772,12 +752,7 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void rollout_kernel(RolloutArgs 
         eval_net<D, H, 1, WIDE, SPLIT>(lc, a.w2a_critic, xk, v, lane);
         if (writer) a.last_values[e] = v[0];
     }
-    if (writer) {
-#pragma unroll
-        for (int i = 0; i < S; ++i) a.state[(size_t)e * S + i] = st[i];
-        a.step_count[e] = sc; a.episode[e] = ep; a.gstep[e] = gs;
-        if (a.mon_cur_ret) { a.mon_cur_ret[e] = mon_ret; a.mon_cur_len[e] = mon_len; }
-    }
+    if (writer) cur.store(env, e);
 }
 
 // =============================================================================================
@@ -785,12 +760,12 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void rollout_kernel(RolloutArgs 
 // rollout_kernel ONE wave walks both nets for its 32 envs, step after step: with a handful of envs the rollout is a single dependent chain of ~10 k cycles per env step
 // (critic forward -> actor forward -> sample -> physics).  Here a tile of 32 envs has TWO waves: wave 0 runs the actor, the sampling and the simulator, wave 1 the critic
 // (value of every observation, V(terminal_observation) of truncated steps, the last values), one step behind through a double-buffered observation slot in LDS and ONE
-// barrier per env step.  Same device functions as rollout_kernel (eval_net, env_step, heads), so every stored number is bit-identical to the one-wave kernel.
+// barrier per env step.  The step itself is rollout_kernel's — eval_net, rollout_sample, EnvCursor / env_advance / env_end_episode — so every stored number is bit-identical to the
+// one-wave kernel (tests/test_gpu_parity.py, test_stepwise_path_equals_persistent_kernel).
 // =============================================================================================
 template <int KIND, int H, bool SPLIT>
 __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
-    constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A, S = EnvSpec<KIND>::S;
-    constexpr bool DISC = EnvSpec<KIND>::discrete;
+    constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
     constexpr int LA = FwdLds<D, H, A, false, SPLIT>::SIZE, LC = FwdLds<D, H, 1, false, SPLIT>::SIZE;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* la = smem; float* lc = smem + LA;
@@ -808,25 +783,15 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
     if (wave == 0) {
         // ================= actor + simulator =================
         const uint64_t env_seed = a.env_seed0 + (uint64_t)e;
-        float st[S];
-#pragma unroll
-        for (int i = 0; i < S; ++i) st[i] = a.state[(size_t)e * S + i];
-        int sc = a.step_count[e];
-        uint32_t ep = a.episode[e], gs = a.gstep[e];
+        const EnvArrays env{a.state, a.step_count, a.episode, a.gstep, a.mon_cur_ret, a.mon_cur_len};
+        EnvCursor<KIND> cur; cur.load(env, e);
         float obs[D];
-        env_obs<KIND>(st, obs);
+        env_obs<KIND>(cur.st, obs);
         if (h == 0) {
 #pragma unroll
             for (int i = 0; i < D; ++i) slot[i * 32 + c] = obs[i];     // parity 0: the observation of step 0
         }
-        float lsr[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!DISC) {
-#pragma unroll
-            for (int i = 0; i < (A < 4 ? A : 4); ++i) lsr[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.params[a.log_std_off + i])));
-        }
-        const float* ls = lsr;
-        float mon_ret = a.mon_cur_ret ? a.mon_cur_ret[e] : 0.f;
-        int mon_len = a.mon_cur_len ? a.mon_cur_len[e] : 0;
+        float lsr[4]; rollout_log_std<KIND>(a, lsr);
         __syncthreads();                                                // weights staged, slot 0 published
         for (int t = 0; t < a.T; ++t) {
             const size_t k = (size_t)t * a.E + e;
@@ -836,29 +801,8 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
             pair_obs<D>(obs, h, xk);
             float out[A];
             eval_net<D, H, A, false, SPLIT>(la_t, a.w2a_actor, xk, out, lane);
-            int act_env = 0; float actf_env = 0.f; float logp;
-            if (DISC) {
-                float p[A]; softmax_n<A>(out, p);
-                double u;
-                if (a.noise) u = ((const double*)a.noise)[k];
-                else { uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gs, 0, 1, 0, r); u = u01_f64(r[0], r[1]); }
-                const int act = categorical_sample<A>(p, u);
-                logp = flog(pick<A>(p, act));
-                act_env = act;
-                if (writer) ((int32_t*)a.act)[k] = act + a.action_start;
-            } else {
-                float x[A];
-#pragma unroll
-                for (int i = 0; i < A; ++i) {
-                    float z;
-                    if (a.noise) z = ((const float*)a.noise)[k * A + i];
-                    else { uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gs, 0, 1, (uint32_t)(i / 2), r); z = (i & 1) ? randn_f32(r[2], r[3]) : randn_f32(r[0], r[1]); }
-                    x[i] = out[i] + fexp(ls[i]) * z;
-                    if (writer) ((float*)a.act)[k * A + i] = x[i];
-                }
-                logp = gauss_logpdf<A>(x, out, ls);
-                actf_env = fminf(fmaxf(x[0], -act_bound<KIND>()), act_bound<KIND>());
-            }
+            int act_env = 0; float actf_env = 0.f, logp;
+            rollout_sample<KIND>(a, k, env_seed, cur.gs, out, lsr, writer, &act_env, &actf_env, &logp);
             if (writer) {
                 if (D == 4) *reinterpret_cast<float4*>(a.obs + k * 4) = make_float4(obs[0], obs[1], obs[2], obs[3]);
                 else {
@@ -867,37 +811,24 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
                 }
                 a.logp[k] = logp;
             }
-            bool term;
-            const float rew = env_step<KIND>(st, actf_env, act_env, a.fixed_len != 0, &term);
-            sc += 1; gs += 1;
-            const bool trunc = sc >= a.episode_len;
+            const StepOut so = env_advance<KIND>(cur, actf_env, act_env, a.episode_len, a.fixed_len != 0);
             float* sl = slot + ((t + 1) & 1) * SLOT;                    // what the critic reads during step t + 1
             if (h == 0) {
-                float tobs[D]; env_obs<KIND>(st, tobs);                 // terminal_observation (only read where truncated)
+                float tobs[D]; env_obs<KIND>(cur.st, tobs);             // terminal_observation (only read where truncated)
 #pragma unroll
                 for (int i = 0; i < D; ++i) sl[(D + i) * 32 + c] = tobs[i];
-                sl[2 * D * 32 + c] = (trunc && valid) ? 1.0f : 0.0f;
+                sl[2 * D * 32 + c] = (so.trunc && valid) ? 1.0f : 0.0f;
             }
-            mon_ret += rew; mon_len += 1;
-            if (term || trunc) {
-                ep += 1; sc = 0; env_reset<KIND>(env_seed, ep, st);
-                if (writer && a.ep_ret) { a.ep_ret[k] = mon_ret; a.ep_len[k] = mon_len; }
-                mon_ret = 0.f; mon_len = 0;
-            }
-            if (writer) { a.rew[k] = rew; a.flags[k] = (uint8_t)((term ? 1 : 0) | (trunc ? 2 : 0)); }
-            env_obs<KIND>(st, obs);
+            env_end_episode<KIND>(cur, env_seed, so, writer && a.ep_ret ? a.ep_ret + k : nullptr, a.ep_len + k);
+            if (writer) { a.rew[k] = so.rew; a.flags[k] = so.flags(); }
+            env_obs<KIND>(cur.st, obs);
             if (h == 0) {
 #pragma unroll
                 for (int i = 0; i < D; ++i) sl[i * 32 + c] = obs[i];
             }
             lds_barrier();                                              // step t published; the critic is done with the other slot (LDS only: the buffer stores stay in flight)
         }
-        if (writer) {
-#pragma unroll
-            for (int i = 0; i < S; ++i) a.state[(size_t)e * S + i] = st[i];
-            a.step_count[e] = sc; a.episode[e] = ep; a.gstep[e] = gs;
-            if (a.mon_cur_ret) { a.mon_cur_ret[e] = mon_ret; a.mon_cur_len[e] = mon_len; }
-        }
+        if (writer) cur.store(env, e);
     } else {
         // ================= critic: V(obs_t), V(terminal_observation) of step t - 1, the last values =================
         __syncthreads();

@@ -953,6 +953,19 @@ __device__ __forceinline__ void sac_mu_block(const CollectHeadArgs& g, int a, in
         if (lane == r) mu_s[kMuRows * wave + r] = s2 + b;
     }
 }
+// action component a of env e in the collection step: the noise (injected, or the env's stream at its global step: dril_device.h) -> the raw action the replay stores ->
+// the action the env receives (*envact); the caller stores them
+__device__ __forceinline__ void sac_collect_action(const CollectHeadArgs& g, int e, uint32_t gstep, int a, float mu, float* raw, float* envact) {
+    float z, r, ev;
+    if (g.inj_noise) z = g.inj_noise[e * g.A + a];
+    else z = g.use_random ? env_noise_u01_f32(g.seed0 + (uint64_t)e, gstep, a) : env_noise_randn(g.seed0 + (uint64_t)e, gstep, a);
+    if (g.use_random) { r = g.low + z * (g.high - g.low); ev = r; }                              // rand(rng, act_space): already env space, :50-53
+    else {
+        r = tanhf(mu + expf(g.log_std[a]) * z);                                                  // rand(SquashedDiagGaussian) squashedDiagGaussian.jl:24-27
+        ev = tanhf(r) * (g.high - g.low) / 2.0f + (g.low + g.high) / 2.0f;                       // to_env(TanhScaleAdapter) default_adapters.jl:13-21
+    }
+    *raw = r; *envact = ev;
+}
 // 256 threads per kEnvsPerBlock envs: the output layer by all four waves (g.h2 set), then one thread per env
 __global__ __launch_bounds__(256) void sac_collect_head_kernel(CollectHeadArgs g) {
     __shared__ float mu_s[kEnvsPerBlock];
@@ -966,23 +979,11 @@ __global__ __launch_bounds__(256) void sac_collect_head_kernel(CollectHeadArgs g
         }
     }
     if (threadIdx.x >= kEnvsPerBlock || e >= g.E) return;
-    for (int a0 = 0; a0 < g.A; a0 += 2) {
-        float z[2];
-        if (g.inj_noise) { z[0] = g.inj_noise[e * g.A + a0]; z[1] = a0 + 1 < g.A ? g.inj_noise[e * g.A + a0 + 1] : 0.f; }
-        else {
-            uint32_t o[4]; const uint64_t k = g.seed0 + (uint64_t)e;
-            philox4x32_10((uint32_t)k, (uint32_t)(k >> 32), g.gstep[e], 0u, 1u, (uint32_t)(a0 / 2), o);
-            if (g.use_random) { z[0] = u01_f32(o[0]); z[1] = u01_f32(o[2]); } else { z[0] = randn_f32(o[0], o[1]); z[1] = randn_f32(o[2], o[3]); }
-        }
-        for (int t = 0; t < 2 && a0 + t < g.A; ++t) {
-            const int a = a0 + t; float r, ev;
-            if (g.use_random) { r = g.low + z[t] * (g.high - g.low); ev = r; }               // rand(rng, act_space): already env space, :50-53
-            else {
-                r = tanhf(g.mu[(size_t)e * g.A + a] + expf(g.log_std[a]) * z[t]);            // rand(SquashedDiagGaussian) squashedDiagGaussian.jl:24-27
-                ev = tanhf(r) * (g.high - g.low) / 2.0f + (g.low + g.high) / 2.0f;           // to_env(TanhScaleAdapter) default_adapters.jl:13-21
-            }
-            g.raw[e * g.A + a] = r; g.envact[e * g.A + a] = ev;
-        }
+    const uint32_t gs = g.gstep[e];
+    for (int a = 0; a < g.A; ++a) {
+        float r, ev;
+        sac_collect_action(g, e, gs, a, g.use_random ? 0.f : g.mu[(size_t)e * g.A + a], &r, &ev);
+        g.raw[e * g.A + a] = r; g.envact[e * g.A + a] = ev;
     }
 }
 struct PushArgs {
@@ -990,27 +991,31 @@ struct PushArgs {
     float *rb_obs, *rb_next, *rb_act, *rb_rew; uint8_t *rb_term, *rb_trunc;
     unsigned long long* stamp;   // phase_stamp (null: none)
 };
+// push! of env e's transition into its ring slot: D / A the row widths, tobs / nobs / raw the env's rows (memory or registers)
+__device__ __forceinline__ void sac_push_row(const PushArgs& g, int e, int D, int A, const float* tobs, const float* nobs, const float* raw, float rew, bool term, bool trunc) {
+    const long long slot = (g.tail + e) % g.cap;
+    for (int d = 0; d < D; ++d) {
+        g.rb_obs[slot * D + d] = g.obs[(size_t)e * D + d];
+        g.rb_next[slot * D + d] = trunc ? tobs[d] : nobs[d];                                    // truncated_observation | next observation
+    }
+    for (int a = 0; a < A; ++a) g.rb_act[slot * A + a] = raw[a];                                // unprocessed action, :72
+    g.rb_rew[slot] = rew; g.rb_term[slot] = term; g.rb_trunc[slot] = trunc;
+}
 __global__ void sac_push_kernel(PushArgs g) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     phase_stamp(g.stamp);                                    // (within a microsecond of the kernel's end: the stamp feeds a per-iteration fps statistic)
     if (e >= g.E) return;
-    const long long slot = (g.tail + e) % g.cap;
-    const bool tr = g.trunc[e] != 0;
-    for (int d = 0; d < g.D; ++d) {
-        g.rb_obs[slot * g.D + d] = g.obs[(size_t)e * g.D + d];
-        g.rb_next[slot * g.D + d] = tr ? g.tobs[(size_t)e * g.D + d] : g.nobs[(size_t)e * g.D + d];   // truncated_observation | next observation
-    }
-    for (int a = 0; a < g.A; ++a) g.rb_act[slot * g.A + a] = g.raw[e * g.A + a];               // unprocessed action, :72
-    g.rb_rew[slot] = g.rew[e]; g.rb_term[slot] = g.term[e]; g.rb_trunc[slot] = g.trunc[e];
+    sac_push_row(g, e, g.D, g.A, g.tobs + (size_t)e * g.D, g.nobs + (size_t)e * g.D, g.raw + e * g.A, g.rew[e], g.term[e] != 0, g.trunc[e] != 0);
 }
 // One env step of the collection for a DEVICE env in ONE launch: sac_collect_head_kernel -> env_step_kernel -> env_observe_kernel -> sac_push_kernel are all one thread per env
-// on data of that env only (four dependent launches of 4 - 5 us and their boundaries per collected step).  Same device functions, same order of operations, and every
-// intermediate buffer (e_raw, e_envact, e_rew, e_term, e_trunc, e_tobs, obs_nxt) still written: bit-identical to the four-launch sequence (A = 1: every device Box env).
+// on data of that env only (four dependent launches of 4 - 5 us and their boundaries per collected step).  The same four definitions in the same order — sac_collect_action,
+// the EnvCursor transition (env_advance / env_end_episode, dril_device.h), env_obs, sac_push_row — and every intermediate buffer (e_raw, e_envact, e_rew, e_term, e_trunc,
+// e_tobs, obs_nxt) still written: bit-identical to the four-launch sequence (A = 1: every device Box env).
 struct CollectEnvArgs { CollectHeadArgs head; PushArgs push; uint64_t seed0; int episode_len; float* state; int32_t* step_count; uint32_t* episode; uint32_t* gstep;
                         float* rew; uint8_t* term; uint8_t* trunc; float* tobs; float* nobs; };
 template <int KIND>
 __global__ __launch_bounds__(256) void sac_collect_env_kernel(CollectEnvArgs c) {
-    constexpr int S = EnvSpec<KIND>::S, D = EnvSpec<KIND>::D;
+    constexpr int D = EnvSpec<KIND>::D;
     __shared__ float mu_s[kEnvsPerBlock];
     const CollectHeadArgs& g = c.head;
     const int e = blockIdx.x * kEnvsPerBlock + threadIdx.x;          // 256 threads per kEnvsPerBlock envs: all four waves on the output layer, then one thread per env
@@ -1018,52 +1023,31 @@ __global__ __launch_bounds__(256) void sac_collect_env_kernel(CollectEnvArgs c) 
     if (threadIdx.x >= kEnvsPerBlock || e >= g.E) return;
     float mu_e = 0.f;
     if (!g.use_random) { if (g.h2) { mu_e = mu_s[threadIdx.x]; g.mu[e] = mu_e; } else mu_e = g.mu[e]; }
+    const EnvArrays env{c.state, c.step_count, c.episode, c.gstep, nullptr, nullptr};
+    EnvCursor<KIND> cur; cur.load(env, e);
     // ---- the action (sac_collect_head_kernel, A = 1) ----
-    float z;
-    if (g.inj_noise) z = g.inj_noise[e];
-    else {
-        uint32_t o[4]; const uint64_t k = g.seed0 + (uint64_t)e;
-        philox4x32_10((uint32_t)k, (uint32_t)(k >> 32), c.gstep[e], 0u, 1u, 0u, o);
-        z = g.use_random ? u01_f32(o[0]) : randn_f32(o[0], o[1]);
-    }
     float r, ev;
-    if (g.use_random) { r = g.low + z * (g.high - g.low); ev = r; }
-    else {
-        r = tanhf(mu_e + expf(g.log_std[0]) * z);
-        ev = tanhf(r) * (g.high - g.low) / 2.0f + (g.low + g.high) / 2.0f;
-    }
+    sac_collect_action(g, e, cur.gs, 0, mu_e, &r, &ev);
     g.raw[e] = r; g.envact[e] = ev;
     // ---- act! with auto-reset (env_step_kernel) ----
-    float st[S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) st[i] = c.state[(size_t)e * S + i];
-    bool t;
-    const float rw = env_step<KIND>(st, ev, 0, false, &t);
-    const int sc = c.step_count[e] + 1;
-    const bool tr = sc >= c.episode_len;
-    c.rew[e] = rw; c.term[e] = t; c.trunc[e] = tr; c.gstep[e] += 1;
+    const StepOut so = env_advance<KIND>(cur, ev, 0, c.episode_len, false);
+    c.rew[e] = so.rew; c.term[e] = so.term; c.trunc[e] = so.trunc;
     float to[D];
-    env_obs<KIND>(st, to);                                                              // terminal_observation (stored where truncated)
-    if (tr) {
+    env_obs<KIND>(cur.st, to);                                                          // terminal_observation (stored where truncated)
+    if (so.trunc) {
 #pragma unroll
         for (int i = 0; i < D; ++i) c.tobs[(size_t)e * D + i] = to[i];
     }
-    if (t || tr) { const uint32_t ep = c.episode[e] + 1; c.episode[e] = ep; c.step_count[e] = 0; env_reset<KIND>(c.seed0 + (uint64_t)e, ep, st); }
-    else c.step_count[e] = sc;
-#pragma unroll
-    for (int i = 0; i < S; ++i) c.state[(size_t)e * S + i] = st[i];
+    env_end_episode<KIND>(cur, c.seed0 + (uint64_t)e, so, nullptr, nullptr);
+    cur.store(env, e);
     // ---- observe (env_observe_kernel) ----
     float no[D];
-    env_obs<KIND>(st, no);
+    env_obs<KIND>(cur.st, no);
 #pragma unroll
     for (int i = 0; i < D; ++i) c.nobs[(size_t)e * D + i] = no[i];
     // ---- push! (sac_push_kernel) ----
-    const PushArgs& q = c.push;
-    const long long slot = (q.tail + e) % q.cap;
-#pragma unroll
-    for (int d = 0; d < D; ++d) { q.rb_obs[slot * D + d] = q.obs[(size_t)e * D + d]; q.rb_next[slot * D + d] = tr ? to[d] : no[d]; }
-    q.rb_act[slot] = r; q.rb_rew[slot] = rw; q.rb_term[slot] = t; q.rb_trunc[slot] = tr;
-    phase_stamp(q.stamp);                                               // thread 0 of the last workgroup owns a live env (grid = ceil(E / kEnvsPerBlock)): the end of its work ~ the end of the phase
+    sac_push_row(c.push, e, D, 1, to, no, &r, so.rew, so.term, so.trunc);
+    phase_stamp(c.push.stamp);                                               // thread 0 of the last workgroup owns a live env (grid = ceil(E / kEnvsPerBlock)): the end of its work ~ the end of the phase
 }
 // host-batch helpers
 __global__ void sac_squash_eval_kernel(int B, int A, const float* mu, const float* log_std, const float* noise, int deterministic, float low, float high,

@@ -648,25 +648,61 @@ def test_normalize_wrapper_env_verbs_and_training_flag(pkg, oracle_mod):
     assert after["ret_var"] == before["ret_var"]
 
 
-def test_stepwise_path_equals_persistent_kernel(pkg, monkeypatch):
-    """the step-granular launch sequence and the fused persistent rollout_kernel are the same algorithm"""
+def _collect_two_rollouts(pkg, kind):
+    """two consecutive rollouts (the second starts from the env state, counters and monitor sums the first wrote back) -> the ten BUF_* arrays of each + monitor_stats()"""
+    cfg = _cfg(pkg, kind, n_envs=200, n_steps=40, episode_len=13, batch_size=400, epochs=1, monitor_window=64)
+    h = pkg.Handle(cfg); h.set_params(_params(h.P, 8, 0.4)); h.env_reset(21)
+    out = {}
+    for r in range(2):
+        h.collect_rollout()
+        out.update({f"r{r}_buf{w}": h.buffer(w) for w in range(10)})
+    out["monitor"] = np.asarray(h.monitor_stats(), np.float64)
+    h.close()
+    return out
+
+
+def test_stepwise_path_equals_persistent_kernel(pkg, monkeypatch, tmp_path):
+    """the step-granular launch sequence (env_step_kernel + policy_kernel), the two-wave rollout_duo_kernel (what 200 envs run by default) and the one-wave
+    rollout_kernel are the same algorithm: same actions, flags, rewards, observations, log-probabilities and finished-episode statistics, bit for bit —
+    for CartPole (Categorical), Pendulum (DiagGaussian) and Acrobot (D = 6, three actions)"""
+    import os, subprocess, sys
     capi = pkg._capi
-    cfg = _cfg(pkg, 0, n_envs=200, n_steps=40, episode_len=13, batch_size=400, epochs=1)
-    flat = _params(9155, 8, 0.4)
-    outs = []
-    for force in ("0", "1"):
-        monkeypatch.setenv("DRIL_FORCE_STEPWISE", force)
-        h = pkg.Handle(cfg); h.set_params(flat); h.env_reset(21); h.collect_rollout()
-        outs.append({w: h.buffer(w) for w in range(10)})
-        h.close()
-    for w in range(10):
-        if w in (capi.BUF_BOOTSTRAP,):
-            m = (outs[0][capi.BUF_FLAGS] & 2).astype(bool)
-            np.testing.assert_allclose(outs[0][w][m], outs[1][w][m], atol=1e-6)
-        elif w == capi.BUF_LAST_VALUES:
-            np.testing.assert_allclose(outs[0][w], outs[1][w], atol=1e-6)
-        else:
-            np.testing.assert_allclose(outs[0][w].astype(np.float64), outs[1][w].astype(np.float64), atol=1e-6)
+    kinds = (0, 1, 6)
+    duo = {kind: _collect_two_rollouts(pkg, kind) for kind in kinds}
+    monkeypatch.setenv("DRIL_FORCE_STEPWISE", "1")
+    others = {(kind, "stepwise"): _collect_two_rollouts(pkg, kind) for kind in kinds}
+    monkeypatch.delenv("DRIL_FORCE_STEPWISE")
+    # DRIL_NO_ROLLOUT_DUO is latched at the first rollout of a process: the one-wave kernel runs in a child process of its own
+    root = Path(__file__).resolve().parents[1]
+    code = ("import sys, numpy as np\n"
+            f"sys.path.insert(0, {str(root)!r}); sys.path.insert(0, {str(root / 'tests')!r})\n"
+            "import __graft_entry__ as g; pkg = g.load_package()\n"
+            "import test_gpu_parity as T\n"
+            f"for kind in {kinds!r}: np.savez({str(tmp_path)!r} + f'/one_wave_{{kind}}.npz', **T._collect_two_rollouts(pkg, kind))\n")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, DRIL_DEBUG="1", DRIL_NO_ROLLOUT_DUO="1"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for kind in kinds:
+        with np.load(tmp_path / f"one_wave_{kind}.npz") as z:
+            others[(kind, "one_wave")] = {k: z[k] for k in z.files}
+    exact = (capi.BUF_OBSERVATIONS, capi.BUF_ACTIONS, capi.BUF_REWARDS, capi.BUF_LOGPROBS, capi.BUF_FLAGS)
+    for (kind, path), other in others.items():
+        where = f"kind {kind}, two-wave kernel vs {path}"
+        assert duo[kind]["monitor"][2] > 0, where                   # episodes finished: the monitor comparison is not vacuous
+        np.testing.assert_array_equal(duo[kind]["monitor"], other["monitor"], err_msg=where)
+        for r in range(2):
+            a, b = ({w: o[f"r{r}_buf{w}"] for w in range(10)} for o in (duo[kind], other))
+            assert (a[capi.BUF_FLAGS] & 2).any(), where
+            for w in range(10):
+                msg = f"{where}, rollout {r}, buffer {w}"
+                if w in exact:
+                    np.testing.assert_array_equal(a[w], b[w], err_msg=msg)
+                elif w in (capi.BUF_BOOTSTRAP,):
+                    m = (a[capi.BUF_FLAGS] & 2).astype(bool)
+                    np.testing.assert_allclose(a[w][m], b[w][m], atol=1e-6, err_msg=msg)
+                elif w == capi.BUF_LAST_VALUES:
+                    np.testing.assert_allclose(a[w], b[w], atol=1e-6, err_msg=msg)
+                else:
+                    np.testing.assert_allclose(a[w].astype(np.float64), b[w].astype(np.float64), atol=1e-6, err_msg=msg)
 
 
 # ---- hidden_dims = [256, 256] (BASELINE configs[2]) and [128, 128]: wide forward (W2 streamed from L2) and the workgroup-cooperative grad
