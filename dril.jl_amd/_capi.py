@@ -17,6 +17,7 @@ LIB_PATH = Path(os.environ["DRIL_HIP_LIBRARY"]) if os.environ.get("DRIL_HIP_LIBR
 
 ABI_VERSION = 2
 ENV_CARTPOLE, ENV_PENDULUM, ENV_PENDULUM_SCALED, ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONTINUOUS, ENV_EXTERNAL, ENV_ACROBOT, ENV_MOUNTAINCAR_CONTINUOUS_SCALED = 0, 1, 2, 3, 4, 5, 6, 7
+ENV_MODULE = 8   # a device env plug-in (include/device/dril_env_plugin.h), created with dril_create_with_env_module
 (BUF_OBSERVATIONS, BUF_ACTIONS, BUF_REWARDS, BUF_ADVANTAGES, BUF_RETURNS, BUF_LOGPROBS, BUF_VALUES,
  BUF_FLAGS, BUF_BOOTSTRAP, BUF_LAST_VALUES) = range(10)
 (K_ROLLOUT, K_GAE, K_ADV_MOMENTS, K_PPO_GRAD, K_GRAD_REDUCE, K_ADAM, K_ALLREDUCE, K_PACK_RECORDS, K_EXPLAINED_VAR, K_COUNT) = range(10)
@@ -69,6 +70,12 @@ class DrilEvalStats(C.Structure):
                 ("n_episodes", C.c_int32), ("n_steps", C.c_int32)]
 
 
+class DrilEnvModuleInfo(C.Structure):
+    """struct dril_env_module_info, include/dril_hip.h"""
+    _fields_ = [("plugin_abi", C.c_uint32), ("state_dim", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("discrete", C.c_int32),
+                ("episode_len", C.c_int32), ("action_low", C.c_float * 64), ("action_high", C.c_float * 64), ("name", C.c_char * 64)]
+
+
 class DrilSacConfig(C.Structure):
     """struct dril_sac_config, include/dril_sac.h"""
     _fields_ = [
@@ -101,7 +108,7 @@ def default_config(env_kind: int) -> DrilConfig:
     c.env_kind = env_kind
     c.n_envs, c.n_steps = 4, 2048
     c.hidden1 = c.hidden2 = 64
-    c.episode_len = 500 if env_kind in (ENV_CARTPOLE, ENV_ACROBOT) else 999 if env_kind in (ENV_MOUNTAINCAR_CONTINUOUS, ENV_MOUNTAINCAR_CONTINUOUS_SCALED) else 200   # the Gymnasium time limits
+    c.episode_len = 0 if env_kind == ENV_MODULE else 500 if env_kind in (ENV_CARTPOLE, ENV_ACROBOT) else 999 if env_kind in (ENV_MOUNTAINCAR_CONTINUOUS, ENV_MOUNTAINCAR_CONTINUOUS_SCALED) else 200   # the Gymnasium time limits
     c.fixed_length_episodes = 0
     c.action_start = 1
     c.gamma, c.gae_lambda, c.clip_range = 0.99, 0.95, 0.2
@@ -129,6 +136,9 @@ _P = C.c_void_p
 _SIG = {
     "dril_config_default": (C.c_int32, [C.POINTER(DrilConfig), C.c_int32]),
     "dril_create": (C.c_int32, [C.POINTER(DrilConfig), C.POINTER(_P)]),
+    "dril_create_with_env_module": (C.c_int32, [C.POINTER(DrilConfig), C.c_char_p, C.POINTER(_P)]),
+    "dril_env_module_describe": (C.c_int32, [C.c_char_p, C.c_int32, C.POINTER(DrilEnvModuleInfo)]),
+    "dril_env_module_info_of": (C.c_int32, [_P, C.POINTER(DrilEnvModuleInfo)]),
     "dril_destroy": (C.c_int32, [_P]),
     "dril_last_error": (C.c_char_p, [_P]),
     "dril_synchronize": (C.c_int32, [_P]),

@@ -16,6 +16,7 @@
 
 #include "../../include/dril_hip.h"
 #include "dril_internal.h"
+#include "../../include/device/dril_env_plugin.h"   // DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with
 
 using namespace dril;
 
@@ -133,6 +134,8 @@ struct dril_handle {
     bool external = false; bool generic = false; float* gen_tmp = nullptr;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
     GenericDims gd{}; GenericWs gws; int ext_t = 0; bool ext_acted = false;   // DRIL_ENV_EXTERNAL: host envs, generic kernels
     float* ext_stage_rew = nullptr; uint8_t* ext_stage_flags = nullptr;   // pinned [T][E] staging: dril_ext_record returns without draining the stream
+    // DRIL_ENV_MODULE: a device env plug-in (include/device/dril_env_plugin.h) loaded as a HIP module; its three kernels stand in for env_reset / env_observe / env_step_kernel
+    bool module = false; hipModule_t env_module = nullptr; hipFunction_t mod_reset = nullptr, mod_observe = nullptr, mod_step = nullptr; DrilEnvPluginDesc mod_desc{};
     void* comm = nullptr;
     LoopGroup* loop = nullptr;   // debug loopback communicator (dril_debug_comm_loopback)
     int64_t allreduce_calls = 0;
@@ -308,6 +311,41 @@ int monitor_collect_rollout(dril_handle* h) {
     return DRIL_OK;
 }
 
+// ---- device env plug-ins (DRIL_ENV_MODULE) ----
+// One argument block for the three kernels; ceil(E / 256) workgroups of 256 threads, one thread per env (the kernels check e < E).
+DrilEnvPluginArgs module_args(dril_handle* h) {
+    DrilEnvPluginArgs a{};
+    a.E = h->cfg.n_envs; a.episode_len = h->cfg.episode_len; a.fixed_len = h->cfg.fixed_length_episodes; a.action_start = h->cfg.action_start; a.seed0 = h->env_seed0;
+    a.state = h->state; a.step_count = h->step_count; a.episode = h->episode; a.gstep = h->gstep;
+    return a;
+}
+hipError_t module_launch(dril_handle* h, hipFunction_t f, DrilEnvPluginArgs a) {
+    void* params[] = {&a};
+    return hipModuleLaunchKernel(f, (unsigned)((a.E + DRIL_ENV_PLUGIN_BLOCK - 1) / DRIL_ENV_PLUGIN_BLOCK), 1, 1, DRIL_ENV_PLUGIN_BLOCK, 1, 1, 0, h->stream, params, nullptr);
+}
+// reset!(env) / observe(env) / act!(env, actions) of whichever env the handle holds: a built-in kind's kernels or the plug-in's
+hipError_t env_reset_any(dril_handle* h) {
+    if (h->module) return module_launch(h, h->mod_reset, module_args(h));
+    return launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, h->env_seed0, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream);
+}
+hipError_t env_observe_any(dril_handle* h, float* obs) {
+    if (h->module) { DrilEnvPluginArgs a = module_args(h); a.obs = obs; return module_launch(h, h->mod_observe, a); }
+    return launch_env_observe(h->cfg.env_kind, h->cfg.n_envs, h->state, obs, h->stream);
+}
+// the step through the E-sized per-step arrays (dril_env_step, dril_evaluate_agent)
+hipError_t env_step_any(dril_handle* h, const void* actions) {
+    const MonitorArgs mon = monitor_step_args(h);
+    if (h->module) {
+        DrilEnvPluginArgs a = module_args(h);
+        a.actions = actions; a.rewards = h->e_rew; a.terminated = h->e_term; a.truncated = h->e_trunc; a.terminal_obs = h->e_tobs; a.flags = mon.flags_out;
+        a.mon_cur_ret = mon.cur_ret; a.mon_cur_len = mon.cur_len; a.ep_ret = mon.ep_ret; a.ep_len = mon.ep_len;
+        return module_launch(h, h->mod_step, a);
+    }
+    return launch_env_step(h->cfg.env_kind, h->cfg.n_envs, h->env_seed0, h->cfg.episode_len, h->cfg.fixed_length_episodes, h->cfg.action_start, actions,
+                           h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, mon, h->stream);
+}
+#define NOT_MODULE(h, what) do { if ((h)->module) return fail(h, DRIL_ERR_UNSUPPORTED, what ": NormalizeWrapperEnv is not available for a device env plug-in (DRIL_ENV_MODULE): its running-moment tables hold 8 observation dims"); } while (0)
+
 // data-parallel runs: NormalizeWrapperEnv's batch moments cover every env of the job (the reference has ONE vector env, normalizeWrapperEnv.jl:21-26):
 // this rank's partial table is folded to one row, RCCL sums the rows, and the apply kernels merge that row with n_stats = world * E.  One 128-byte
 // all-reduce per env step; every rank applies the identical update, so the running statistics stay bit-identical across ranks
@@ -324,6 +362,7 @@ int global_partials(dril_handle* h, bool update, const double*& partials, int& n
 // ---- step-granular env verbs on device (NormalizeWrapperEnv.observe / act!, normalizeWrapperEnv.jl:123-165) ----
 int observe_dev(dril_handle* h, bool update_stats) {
     const int E = h->cfg.n_envs;
+    if (h->module) { HIPCHK(h, env_observe_any(h, h->e_obs)); return DRIL_OK; }   // no NormalizeWrapperEnv on a plug-in env: the observation as it is
     int nb = (E + 255) / 256; if (nb > h->rms_blocks) nb = h->rms_blocks;
     HIPCHK(h, launch_obs_partials(h->cfg.env_kind, E, h->state, h->e_obs_raw, h->rms_partials, nb, h->stream));
     NormObsArgs a{};
@@ -339,6 +378,12 @@ int observe_dev(dril_handle* h, bool update_stats) {
 // actions: device pointer (stored/raw policy actions; the kernels apply the adapters); rew_out/flags_out: device destinations
 int step_dev(dril_handle* h, const void* actions, float* rew_out, uint8_t* flags_out) {
     const int E = h->cfg.n_envs;
+    if (h->module) {                                                               // plug-in env: the raw step is the whole step
+        HIPCHK(h, env_step_any(h, actions));
+        { int rcm = monitor_collect_step(h); if (rcm) return rcm; }
+        if (rew_out && rew_out != h->e_rew) HIPCHK(h, hipMemcpyAsync(rew_out, h->e_rew, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
+        return DRIL_OK;
+    }
     HIPCHK(h, launch_env_step(h->cfg.env_kind, E, h->env_seed0, h->cfg.episode_len, h->cfg.fixed_length_episodes, h->cfg.action_start, actions,
                               h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, monitor_step_args(h), h->stream));
     { int rcm = monitor_collect_step(h); if (rcm) return rcm; }
@@ -501,10 +546,10 @@ void* buf_ptr(dril_handle* h, int which, size_t* bytes) {
 
 // ================================================================================================
 DRIL_EXPORT int32_t dril_config_default(dril_config* c, int32_t env_kind) {
-    if (!c || env_kind < DRIL_ENV_CARTPOLE || env_kind > DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) return fail(nullptr, DRIL_ERR_INVALID_ARG, "bad cfg/env_kind");
+    if (!c || env_kind < DRIL_ENV_CARTPOLE || env_kind > DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "bad cfg/env_kind");
     std::memset(c, 0, sizeof(*c));
     c->abi_version = DRIL_ABI_VERSION; c->env_kind = env_kind; c->n_envs = 4; c->n_steps = 2048; c->hidden1 = c->hidden2 = 64;
-    c->episode_len = (env_kind == DRIL_ENV_CARTPOLE || env_kind == DRIL_ENV_ACROBOT) ? 500 : (env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 999 : 200; c->action_start = 1;   // the Gymnasium time limits
+    c->episode_len = env_kind == DRIL_ENV_MODULE ? 0 /* the descriptor's */ : (env_kind == DRIL_ENV_CARTPOLE || env_kind == DRIL_ENV_ACROBOT) ? 500 : (env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 999 : 200; c->action_start = 1;   // the Gymnasium time limits
     c->gamma = 0.99f; c->gae_lambda = 0.95f; c->clip_range = 0.2f; c->ent_coef = 0.0f; c->vf_coef = 0.5f;
     c->max_grad_norm = 0.5f; c->has_max_grad_norm = 1; c->normalize_advantage = 1; c->batch_size = 64; c->epochs = 10;
     c->learning_rate = 3.0e-4f; c->adam_beta1 = 0.9f; c->adam_beta2 = 0.999f; c->adam_eps = 1.0e-5f;
@@ -512,10 +557,90 @@ DRIL_EXPORT int32_t dril_config_default(dril_config* c, int32_t env_kind) {
     return DRIL_OK;
 }
 
+namespace {
+// ---- loading a device env plug-in ----
+// the checks that need no GPU: a path, a readable file, the magic of a code object (ELF, or the clang-offload-bundle hipcc writes without --no-gpu-bundle-output)
+int check_code_object_path(const char* path, std::string& msg) {
+    if (!path || !*path) { msg = "null code_object_path"; return DRIL_ERR_INVALID_ARG; }
+    FILE* f = std::fopen(path, "rb");
+    if (!f) { msg = std::string("cannot read code object ") + path; return DRIL_ERR_INVALID_ARG; }
+    char magic[24] = {0}; const size_t n = std::fread(magic, 1, sizeof(magic), f); std::fclose(f);
+    const bool elf = n >= 4 && std::memcmp(magic, "\x7f" "ELF", 4) == 0, bundle = n >= 24 && std::memcmp(magic, "__CLANG_OFFLOAD_BUNDLE__", 24) == 0;
+    if (!elf && !bundle) { msg = std::string(path) + " is not a code object (neither an ELF nor a clang-offload-bundle): build it with hipcc --genco --offload-arch=gfx950"; return DRIL_ERR_INVALID_ARG; }
+    return DRIL_OK;
+}
+int check_plugin_desc(const DrilEnvPluginDesc& d, std::string& msg) {
+    if (d.abi_version != DRIL_ENV_PLUGIN_ABI) { msg = "env plug-in ABI " + std::to_string(d.abi_version) + ", this library speaks " + std::to_string(DRIL_ENV_PLUGIN_ABI) + ": recompile the plug-in against this library's include/device/dril_env_plugin.h"; return DRIL_ERR_UNSUPPORTED; }
+    if (d.args_size != sizeof(DrilEnvPluginArgs)) { msg = "env plug-in kernel argument block is " + std::to_string(d.args_size) + " bytes, this library passes " + std::to_string(sizeof(DrilEnvPluginArgs)) + ": recompile the plug-in against this library's include/device/dril_env_plugin.h"; return DRIL_ERR_UNSUPPORTED; }
+    if (d.S < 1 || d.S > DRIL_ENV_PLUGIN_MAX_S || d.D < 1 || d.D > DRIL_ENV_PLUGIN_MAX_D || d.A < 1 || d.A > DRIL_ENV_PLUGIN_MAX_A || d.episode_len < 1) {
+        msg = "env plug-in descriptor out of range: S " + std::to_string(d.S) + " (1..64), D " + std::to_string(d.D) + " (1..1024), A " + std::to_string(d.A) + " (1..64), episode_len " + std::to_string(d.episode_len) + " (>= 1)"; return DRIL_ERR_UNSUPPORTED; }
+    return DRIL_OK;
+}
+// path checks -> hipModuleLoad -> descriptor out and checked; on success the caller owns *mod (nothing of the module has been launched)
+int load_env_module(const char* path, int device, hipModule_t* mod, DrilEnvPluginDesc* desc, std::string& msg) {
+    *mod = nullptr;
+    int rc = check_code_object_path(path, msg); if (rc) return rc;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) { msg = std::string("hipSetDevice: ") + hipGetErrorString(e); return DRIL_ERR_HIP; }
+    e = hipModuleLoad(mod, path);
+    if (e != hipSuccess) { *mod = nullptr; (void)hipGetLastError(); msg = std::string("hipModuleLoad(") + path + "): " + hipGetErrorString(e) + " (a code object for gfx950 is needed)"; return DRIL_ERR_HIP; }
+    hipDeviceptr_t dptr = nullptr; size_t bytes = 0;
+    e = hipModuleGetGlobal(&dptr, &bytes, *mod, "dril_env_plugin_desc");
+    if (e != hipSuccess) { msg = std::string(path) + " has no symbol dril_env_plugin_desc (not built with DRIL_ENV_PLUGIN): " + hipGetErrorString(e); rc = DRIL_ERR_UNSUPPORTED; }
+    else if (bytes != sizeof(DrilEnvPluginDesc)) { msg = std::string(path) + ": dril_env_plugin_desc is " + std::to_string(bytes) + " bytes, this library reads " + std::to_string(sizeof(DrilEnvPluginDesc)) + " (another plug-in ABI)"; rc = DRIL_ERR_UNSUPPORTED; }
+    else {
+        e = hipMemcpy(desc, dptr, sizeof(*desc), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { msg = std::string("copying dril_env_plugin_desc: ") + hipGetErrorString(e); rc = DRIL_ERR_HIP; }
+        else { desc->name[sizeof(desc->name) - 1] = 0; rc = check_plugin_desc(*desc, msg); }
+    }
+    if (rc) { (void)hipModuleUnload(*mod); *mod = nullptr; (void)hipGetLastError(); }   // (a refused module must not leave its error behind: the launchers read hipGetLastError after their launches)
+    return rc;
+}
+void fill_module_info(const DrilEnvPluginDesc& d, dril_env_module_info* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->plugin_abi = d.abi_version; o->state_dim = d.S; o->obs_dim = d.D; o->action_dim = d.A; o->discrete = d.discrete ? 1 : 0; o->episode_len = d.episode_len;
+    static_assert(sizeof(o->action_low) == sizeof(d.action_low) && sizeof(o->name) == sizeof(d.name), "dril_env_module_info mirrors DrilEnvPluginDesc");
+    std::memcpy(o->action_low, d.action_low, sizeof(d.action_low)); std::memcpy(o->action_high, d.action_high, sizeof(d.action_high)); std::memcpy(o->name, d.name, sizeof(d.name));
+}
+int create_impl(const dril_config* cfg, const char* module_path, dril_handle** out);
+}  // namespace
+
 DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
+    if (cfg && cfg->abi_version == DRIL_ABI_VERSION && cfg->env_kind == DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_MODULE needs a code object: use dril_create_with_env_module(cfg, code_object_path, out)");
+    return create_impl(cfg, nullptr, out);
+}
+DRIL_EXPORT int32_t dril_create_with_env_module(const dril_config* cfg, const char* code_object_path, dril_handle** out) {
     if (!cfg || !out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "null cfg/out");
     if (cfg->abi_version != DRIL_ABI_VERSION) return fail(nullptr, DRIL_ERR_INVALID_ARG, "abi_version mismatch");
-    if (cfg->env_kind < DRIL_ENV_CARTPOLE || cfg->env_kind > DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) return fail(nullptr, DRIL_ERR_INVALID_ARG, "unknown env_kind");
+    if (cfg->env_kind != DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_create_with_env_module: cfg->env_kind must be DRIL_ENV_MODULE");
+    std::string msg; const int rc = check_code_object_path(code_object_path, msg);
+    if (rc) return fail(nullptr, rc, "dril_create_with_env_module: " + msg);
+    return create_impl(cfg, code_object_path, out);
+}
+DRIL_EXPORT int32_t dril_env_module_describe(const char* code_object_path, int32_t device, dril_env_module_info* out) {
+    if (!out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_env_module_describe: null out");
+    hipModule_t mod = nullptr; DrilEnvPluginDesc d{}; std::string msg;
+    const int rc = load_env_module(code_object_path, device, &mod, &d, msg);
+    if (rc) return fail(nullptr, rc, "dril_env_module_describe: " + msg);
+    (void)hipModuleUnload(mod);
+    fill_module_info(d, out);
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_env_module_info_of(const dril_handle* h, dril_env_module_info* out) {
+    if (!h || !out) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle / out");
+    if (!h->module) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_env_module_info_of: the handle was not created with dril_create_with_env_module");
+    fill_module_info(h->mod_desc, out);
+    return DRIL_OK;
+}
+
+namespace {
+int create_impl(const dril_config* cfg, const char* module_path, dril_handle** out) {
+    if (!cfg || !out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "null cfg/out");
+    if (cfg->abi_version != DRIL_ABI_VERSION) return fail(nullptr, DRIL_ERR_INVALID_ARG, "abi_version mismatch");
+    if (cfg->env_kind < DRIL_ENV_CARTPOLE || cfg->env_kind > DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "unknown env_kind");
+    const bool is_module = cfg->env_kind == DRIL_ENV_MODULE;
+    if (is_module && (cfg->norm_obs || cfg->norm_reward)) return fail(nullptr, DRIL_ERR_UNSUPPORTED, "DRIL_ENV_MODULE: NormalizeWrapperEnv (norm_obs / norm_reward) is not available for a device env plug-in: its running-moment tables hold 8 observation dims");
+    if (is_module && cfg->episode_len < 0) return fail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_MODULE: episode_len must be > 0, or 0 for the plug-in's own time limit");
     const bool ext = cfg->env_kind == DRIL_ENV_EXTERNAL;
     if (ext && (cfg->ext_obs_dim < 1 || cfg->ext_obs_dim > 1024 || cfg->ext_action_dim < 1 || cfg->ext_action_dim > 64)) return fail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_EXTERNAL: ext_obs_dim must be 1..1024 and ext_action_dim 1..64");
     // hidden_dims / activation: n_hidden == 0 is the two-layer form (hidden1, hidden2); otherwise hidden[0 .. n_hidden-1]
@@ -530,15 +655,23 @@ DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
     if (cfg->monitor_window < 0) return fail(nullptr, DRIL_ERR_INVALID_ARG, "monitor_window must be >= 0");
     if (cfg->world_size < 1 || cfg->rank < 0 || cfg->rank >= cfg->world_size) return fail(nullptr, DRIL_ERR_INVALID_ARG, "bad rank/world_size");
     if (cfg->batch_size % cfg->world_size != 0) return fail(nullptr, DRIL_ERR_INVALID_ARG, "batch_size must be divisible by world_size");
+    hipModule_t mod = nullptr; DrilEnvPluginDesc desc{};
+    if (is_module) {                                                                     // the descriptor gives the spaces: load it before anything is sized
+        if (cfg->world_size > 1) setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", /*overwrite=*/0);   // (see below: must precede the process's first HIP call)
+        std::string msg; const int rcm = load_env_module(module_path, cfg->device, &mod, &desc, msg);
+        if (rcm) return fail(nullptr, rcm, "dril_create_with_env_module: " + msg);
+    }
     dril_handle* h = nullptr;
-    try { h = new dril_handle(); } catch (...) { return fail(nullptr, DRIL_ERR_INVALID_ARG, "out of host memory"); }
+    try { h = new dril_handle(); } catch (...) { if (mod) (void)hipModuleUnload(mod); return fail(nullptr, DRIL_ERR_INVALID_ARG, "out of host memory"); }
     h->cfg = *cfg;
+    if (is_module) { h->module = true; h->env_module = mod; h->mod_desc = desc; if (cfg->episode_len == 0) h->cfg.episode_len = desc.episode_len; }
     h->cfg.hidden1 = hd[0]; h->cfg.hidden2 = nh > 1 ? hd[1] : hd[0];   // the fused kernels read hidden1 (only reached with two equal layers)
     switch (cfg->env_kind) {
         case DRIL_ENV_CARTPOLE: h->discrete = true; h->D = 4; h->A = 2; h->S = 4; break;
         case DRIL_ENV_MOUNTAINCAR: h->discrete = true; h->D = 2; h->A = 3; h->S = 2; break;
         case DRIL_ENV_MOUNTAINCAR_CONTINUOUS: case DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED: h->discrete = false; h->D = 2; h->A = 1; h->S = 2; break;
         case DRIL_ENV_ACROBOT: h->discrete = true; h->D = 6; h->A = 3; h->S = 4; h->generic = !fused_shape; break;   // six observation dims: four first-layer k-steps and three-quad records in every fused kernel (round 3)
+        case DRIL_ENV_MODULE: h->discrete = desc.discrete != 0; h->D = desc.D; h->A = desc.A; h->S = desc.S; h->generic = true; break;   // no fused kernels for a plug-in env
         case DRIL_ENV_EXTERNAL: h->discrete = cfg->ext_discrete != 0; h->D = cfg->ext_obs_dim; h->A = cfg->ext_action_dim; h->S = 0; h->external = true; h->generic = true; break;
         default: h->discrete = false; h->D = 3; h->A = 1; h->S = 2; break;                    // Pendulum, ScalingWrapperEnv(Pendulum)
     }
@@ -578,6 +711,10 @@ DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
                          ", HIP_VISIBLE_DEVICES=" + (hv ? hv : "(unset)") + " ROCR_VISIBLE_DEVICES=" + (rv ? rv : "(unset)");
     }
     CCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (is_module) {
+        CCHK(hipModuleGetFunction(&h->mod_reset, h->env_module, "dril_env_plugin_reset")); CCHK(hipModuleGetFunction(&h->mod_observe, h->env_module, "dril_env_plugin_observe"));
+        CCHK(hipModuleGetFunction(&h->mod_step, h->env_module, "dril_env_plugin_step"));
+    }
     const size_t E = cfg->n_envs, N = (size_t)h->N, P = h->P;
     CCHK(dmalloc(&h->params, P)); CCHK(dmalloc(&h->adam_m, P)); CCHK(dmalloc(&h->adam_v, P)); CCHK(dmalloc(&h->bt, 4));
     CCHK(dmalloc(&h->flat, P + 8)); CCHK(dmalloc(&h->norm_out, 1)); CCHK(dmalloc(&h->w2max_dev, 1));
@@ -632,6 +769,7 @@ DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
     *out = h;
     return DRIL_OK;
 }
+}  // namespace
 
 DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     if (h) (void)hipSetDevice(h->cfg.device);
@@ -645,6 +783,7 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
         h->loop = nullptr;
     }
     generic_ws_free(h->gws);
+    if (h->env_module) (void)hipModuleUnload(h->env_module);
     if (h->ext_stage_rew) (void)hipHostFree(h->ext_stage_rew); if (h->ext_stage_flags) (void)hipHostFree(h->ext_stage_flags);
     void* ptrs[] = {h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->state,
                     h->step_count, h->episode, h->gstep, h->disc_returns, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
@@ -707,7 +846,7 @@ DRIL_EXPORT int32_t dril_set_optimizer_state(dril_handle* h, const float* m, con
 DRIL_EXPORT int32_t dril_env_reset(dril_handle* h, uint64_t seed) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_reset");
     h->env_seed0 = seed + (uint64_t)h->cfg.rank * (uint64_t)h->cfg.n_envs;
-    HIPCHK(h, launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, h->env_seed0, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
+    HIPCHK(h, env_reset_any(h));
     if (h->mon_cur_ret) { HIPCHK(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)h->cfg.n_envs * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)h->cfg.n_envs * 4, h->stream)); }   // MonitorWrapperEnv.reset! :38-44
     h->env_ready = true;
     return sync(h);
@@ -717,7 +856,7 @@ DRIL_EXPORT int32_t dril_env_observe(dril_handle* h, float* host_obs, int32_t up
     if (!h->env_ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_env_observe before dril_env_reset");
     if (!host_obs) return fail(h, DRIL_ERR_INVALID_ARG, "null host_obs");
     if (normalizing(h)) { int rc = observe_dev(h, update_stats != 0); if (rc) return rc; }
-    else HIPCHK(h, launch_env_observe(h->cfg.env_kind, h->cfg.n_envs, h->state, h->e_obs, h->stream));
+    else HIPCHK(h, env_observe_any(h, h->e_obs));
     HIPCHK(h, hipMemcpyAsync(host_obs, h->e_obs, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
@@ -730,8 +869,7 @@ DRIL_EXPORT int32_t dril_env_step(dril_handle* h, const void* actions, float* re
     float* rew_dev = h->e_rew;
     if (normalizing(h)) { rew_dev = h->e_rew_n; int rc = step_dev(h, h->e_act, rew_dev, nullptr); if (rc) return rc; }
     else {
-        HIPCHK(h, launch_env_step(h->cfg.env_kind, (int)E, h->env_seed0, h->cfg.episode_len, h->cfg.fixed_length_episodes, h->cfg.action_start,
-                                  h->e_act, h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, monitor_step_args(h), h->stream));
+        HIPCHK(h, env_step_any(h, h->e_act));
         int rcm = monitor_collect_step(h); if (rcm) return rcm;
     }
     if (rewards) HIPCHK(h, hipMemcpyAsync(rewards, rew_dev, E * 4, hipMemcpyDeviceToHost, h->stream));
@@ -753,7 +891,7 @@ DRIL_EXPORT int32_t dril_env_set_state(dril_handle* h, const float* state, const
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_norm_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
-    NEED(h); NOT_EXTERNAL(h, "dril_norm_get_stats");
+    NEED(h); NOT_EXTERNAL(h, "dril_norm_get_stats"); NOT_MODULE(h, "dril_norm_get_stats");
     RmsState o, r;
     HIPCHK(h, hipMemcpyAsync(&o, h->obs_rms + h->obs_par, sizeof(o), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(&r, h->ret_rms + h->ret_par, sizeof(r), hipMemcpyDeviceToHost, h->stream));
@@ -763,7 +901,7 @@ DRIL_EXPORT int32_t dril_norm_get_stats(dril_handle* h, float* obs_mean, float* 
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_norm_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
-    NEED(h); NOT_EXTERNAL(h, "dril_norm_set_stats");
+    NEED(h); NOT_EXTERNAL(h, "dril_norm_set_stats"); NOT_MODULE(h, "dril_norm_set_stats");
     if (!obs_mean || !obs_var) return fail(h, DRIL_ERR_INVALID_ARG, "null statistics");
     RmsState o{}, r{};
     for (int d = 0; d < 8; ++d) { o.mean[d] = d < h->D ? obs_mean[d] : 0.f; o.var[d] = d < h->D ? obs_var[d] : 1.f; r.mean[d] = 0.f; r.var[d] = 1.f; }
@@ -774,7 +912,7 @@ DRIL_EXPORT int32_t dril_norm_set_stats(dril_handle* h, const float* obs_mean, c
 }
 
 DRIL_EXPORT int32_t dril_norm_get_original(dril_handle* h, float* obs, float* rewards) {
-    NEED(h); NOT_EXTERNAL(h, "dril_norm_get_original");
+    NEED(h); NOT_EXTERNAL(h, "dril_norm_get_original"); NOT_MODULE(h, "dril_norm_get_original");
     if (!normalizing(h)) return fail(h, DRIL_ERR_NOT_INITIALISED, "NormalizeWrapperEnv is off (cfg.norm_obs == cfg.norm_reward == 0)");
     if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->e_obs_raw, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
     if (rewards) HIPCHK(h, hipMemcpyAsync(rewards, h->e_rew, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
@@ -893,6 +1031,33 @@ int collect_rollout_stepwise(dril_handle* h) {
     return monitor_collect_rollout(h);
 }
 
+// step-granular collect_trajectories for a device env plug-in: two launch groups per env step,
+//   policy (generic forward + sampling head, + V(terminal_observation) of the previous step) -> the plug-in's step kernel
+// which writes reward and BUF_FLAGS byte straight into row t, the terminal observation and the next observation into the per-step arrays (one env launch where
+// the built-in generic path has norm_step_kernel + norm_apply_kernel).  Noise: stream 1 at gstep, or the injected table, exactly as collect_rollout_stepwise.
+int collect_rollout_module(dril_handle* h) {
+    const int E = h->cfg.n_envs, T = h->cfg.n_steps, D = h->D, A = h->A;
+    const size_t ab = act_bytes_per(h);
+    HIPCHK(h, env_observe_any(h, h->e_obs));                                               // new_obs = observe(env), trajectory.jl:32
+    for (int t = 0; t < T; ++t) {
+        const size_t k = (size_t)t * E;
+        const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * (size_t)A)) : nullptr;
+        PolicyArgs p = policy_args(h, h->e_obs, E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);
+        p.gstep = h->gstep; p.env_seed0 = h->env_seed0; p.obs_out = h->obs + k * D;
+        if (t > 0) { p.boot_obs = h->e_tobs; p.boot_where = h->e_trunc; p.boot_out = h->boot + (k - E); }   // :57-61 for step t-1
+        HIPCHK(h, run_policy(h, p));                                                       // get_action_and_values, :41
+        DrilEnvPluginArgs s = module_args(h);
+        s.actions = (const char*)h->act + k * ab; s.rewards = h->rew + k; s.terminated = h->e_term; s.truncated = h->e_trunc; s.flags = h->flags + k;
+        s.terminal_obs = h->e_tobs; s.obs = h->e_obs;
+        if (h->mon_cur_ret) { s.mon_cur_ret = h->mon_cur_ret; s.mon_cur_len = h->mon_cur_len; s.ep_ret = h->ep_ret + k; s.ep_len = h->ep_len + k; }
+        HIPCHK(h, module_launch(h, h->mod_step, s));                                       // to_env + act! + observe, :43-45
+    }
+    PolicyArgs l = policy_args(h, h->e_obs, E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);
+    l.boot_obs = h->e_tobs; l.boot_where = h->e_trunc; l.boot_out = h->boot + (size_t)(T - 1) * E;
+    HIPCHK(h, run_policy(h, l));                                                           // V(new_obs) for rollout-limited tails, :65-70
+    return monitor_collect_rollout(h);
+}
+
 int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
     if (!h->env_ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset");
     { int rcw = ensure_wimg(h); if (rcw) return rcw; }
@@ -900,7 +1065,7 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
         const auto t0s = std::chrono::steady_clock::now();
         if (fps) HIPCHK(h, hipStreamSynchronize(h->stream));
         prof_begin(h, DRIL_K_ROLLOUT);
-        int rcs = collect_rollout_stepwise(h);
+        int rcs = h->module ? collect_rollout_module(h) : collect_rollout_stepwise(h);
         prof_end(h);
         if (rcs) return rcs;
         if (fps) { HIPCHK(h, hipStreamSynchronize(h->stream)); const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0s).count(); *fps = (double)h->N / (dt > 0 ? dt : 1e-12); }
@@ -1377,7 +1542,7 @@ DRIL_EXPORT int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval, int32_t 
     if (n_eval < 1 || !out) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
     const int E = h->cfg.n_envs;
     int rc = ensure_wimg(h); if (rc) return rc;
-    HIPCHK(h, launch_env_reset(h->cfg.env_kind, E, h->env_seed0, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));   // reset!(env), :87
+    HIPCHK(h, env_reset_any(h));   // reset!(env), :87
     if (h->mon_cur_ret) { HIPCHK(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)E * 4, h->stream)); }
     h->env_ready = true;
     const bool raw = h->mon_cur_ret != nullptr;                                  // monitored: infos[i]["episode"]["r"] is the raw return

@@ -15,6 +15,8 @@
 #include <stdint.h>
 
 #include <cstdlib>
+
+#include "../../include/device/dril_philox.h"
 namespace dril {
 
 // Diagnostic / experiment switches (ablation bits, grid caps, the older form of a kernel for an A/B) are honoured only when DRIL_DEBUG=1 is set as well: a stray variable
@@ -41,28 +43,7 @@ constexpr int kTS = 36;     // row stride of the transposed activation images (3
 // ---------------------------------------------------------------------------------------------
 // RNG (spec shared with oracle/dril_oracle.c; both are restatements of the same published Philox)
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ inline void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
-                                              uint32_t c3, uint32_t out[4]) {
-    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += W0; k1 += W1;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__host__ __device__ inline float u01_f32(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
-__host__ __device__ inline double u01_f64(uint32_t hi, uint32_t lo) {
-    return (double)((((uint64_t)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-}
-__device__ inline float randn_f32(uint32_t a, uint32_t b) {
-    const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(b >> 8) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
+// philox4x32_10, u01_f32, u01_f64, randn_f32: include/device/dril_philox.h (shared with the device env plug-in header)
 
 // Philox streams: every random number of the library is a word of philox4x32_10(key; c0, c1, c2, c3), and counter word c2 is the STREAM id — the one place that
 // says who owns which words (the CPU oracle under oracle/ restates them independently):

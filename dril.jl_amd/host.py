@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 import sys
 import time
 from dataclasses import dataclass, field, asdict
@@ -379,14 +380,33 @@ def make_config(env, n_envs: int, alg: PPO, layer: Optional[ActorCriticLayer] = 
     return c
 
 
+def _module_info_dict(info) -> dict:
+    A = info.action_dim
+    return dict(plugin_abi=info.plugin_abi, state_dim=info.state_dim, obs_dim=info.obs_dim, action_dim=A, discrete=bool(info.discrete), episode_len=info.episode_len,
+                action_low=np.asarray(info.action_low[:A], np.float32), action_high=np.asarray(info.action_high[:A], np.float32), name=info.name.decode())
+
+
+def describe_env_module(code_object_path, device: int = 0) -> dict:
+    """dril_env_module_describe: what a device env plug-in's code object says about itself (spaces, bounds, time limit, name)."""
+    lib = capi.load_library()
+    info = capi.DrilEnvModuleInfo()
+    rc = lib.dril_env_module_describe(os.fsencode(code_object_path), device, C.byref(info))
+    if rc != capi.OK:
+        raise DrilError(rc, (lib.dril_last_error(None) or b"").decode())
+    return _module_info_dict(info)
+
+
 class Handle:
     """Owns one dril_handle*; every method is a thin typed wrapper of one C entry point."""
 
-    def __init__(self, cfg: DrilConfig, lib: Optional[C.CDLL] = None):
+    def __init__(self, cfg: DrilConfig, lib: Optional[C.CDLL] = None, env_module: Optional[os.PathLike] = None):
         self.lib = lib or capi.load_library()
         self.cfg = cfg
         self._h = C.c_void_p()
-        rc = self.lib.dril_create(C.byref(cfg), C.byref(self._h))
+        if env_module is not None:      # cfg.env_kind == ENV_MODULE: the env is a code object built from include/device/dril_env_plugin.h
+            rc = self.lib.dril_create_with_env_module(C.byref(cfg), os.fsencode(env_module), C.byref(self._h))
+        else:
+            rc = self.lib.dril_create(C.byref(cfg), C.byref(self._h))
         if rc != capi.OK:
             raise DrilError(rc, (self.lib.dril_last_error(None) or b"").decode())
         self.D = self.lib.dril_obs_dim(self._h)
@@ -446,6 +466,11 @@ class Handle:
         self._chk(self.lib.dril_set_learning_rate(self._h, lr))
 
     # env verbs
+    def env_module_info(self) -> dict:
+        info = capi.DrilEnvModuleInfo()
+        self._chk(self.lib.dril_env_module_info_of(self._h, C.byref(info)))
+        return _module_info_dict(info)
+
     def env_reset(self, seed: int):
         self._chk(self.lib.dril_env_reset(self._h, seed))
 
@@ -464,7 +489,7 @@ class Handle:
         return rew, term.astype(bool), trunc.astype(bool), tobs
 
     def env_get_state(self):
-        S = 4 if self.cfg.env_kind in (capi.ENV_CARTPOLE, capi.ENV_ACROBOT) else 2      # CartPole / Acrobot (theta1, theta2, dtheta1, dtheta2); (x, x_dot, theta, theta_dot); Pendulum (theta, theta_dot); MountainCar (position, velocity)
+        S = self.env_module_info()["state_dim"] if self.cfg.env_kind == capi.ENV_MODULE else 4 if self.cfg.env_kind in (capi.ENV_CARTPOLE, capi.ENV_ACROBOT) else 2      # CartPole / Acrobot (theta1, theta2, dtheta1, dtheta2); (x, x_dot, theta, theta_dot); Pendulum (theta, theta_dot); MountainCar (position, velocity)
         st = np.empty((self.E, S), np.float32)
         sc = np.empty(self.E, np.int32)
         self._chk(self.lib.dril_env_get_state(self._h, self._p(st), self._p(sc)))
@@ -744,7 +769,7 @@ class DeviceParallelEnv:
             if self.handle is not None:
                 self.handle.close()
             cfg = make_config(self.env, self.n_envs, alg, layer, seed=self.seed, **self._kw)
-            self.handle = Handle(cfg)
+            self.handle = Handle(cfg, env_module=getattr(self.env, "code_object_path", None))
             self.handle.env_reset(self.seed)  # Random.seed!(env, seed) + reset!(env)
             self._bound_key = key
         return self.handle
@@ -782,6 +807,39 @@ class DeviceParallelEnv:
 
     def truncated(self):
         return self._last_trunc
+
+
+@dataclass
+class ModuleEnv:
+    """One env of a device env plug-in: the spaces and the time limit its code object declares."""
+    code_object_path: str
+    info: dict
+    max_steps: int
+    action_start: int = 1
+    kind: int = capi.ENV_MODULE
+
+    def observation_space(self):
+        D = self.info["obs_dim"]
+        return Box((-math.inf,) * D, (math.inf,) * D)
+
+    def action_space(self):
+        if self.info["discrete"]:
+            return Discrete(self.info["action_dim"], self.action_start)
+        return Box(tuple(float(v) for v in self.info["action_low"]), tuple(float(v) for v in self.info["action_high"]))
+
+
+class DeviceModuleEnv(DeviceParallelEnv):
+    """`n_envs` copies of the CALLER'S OWN env, living on the device: the env is a gfx950 code object built from include/device/dril_env_plugin.h
+    (`hipcc --genco`), loaded by the library and stepped by its own kernels where a built-in env's kernels would run — no host env anywhere in the loop.
+    Everything a DeviceParallelEnv does works unchanged (Agent, train_, collect_rollout_, MonitorWrapperEnv, callbacks, evaluate_agent, checkpoints);
+    NormalizeWrapperEnv is refused by the library (docs/external_envs.md)."""
+
+    def __init__(self, code_object_path, n_envs: int, *, seed: int = 42, device: int = 0, max_steps: Optional[int] = None, action_start: int = 1,
+                 fixed_length_episodes: bool = False, rank: int = 0, world_size: int = 1, profile_events: bool = False):
+        info = describe_env_module(code_object_path, device)
+        env = ModuleEnv(os.fspath(code_object_path), info, int(max_steps) if max_steps else info["episode_len"], action_start)
+        super().__init__(env, n_envs, seed=seed, fixed_length_episodes=fixed_length_episodes, device=device, rank=rank, world_size=world_size,
+                         profile_events=profile_events)
 
 
 class HostParallelEnv:
@@ -916,6 +974,8 @@ def NormalizeWrapperEnv(env: DeviceParallelEnv, *, training: bool = True, norm_o
                                 clip_reward=clip_reward, gamma=gamma, epsilon=epsilon)
     if env.handle is not None:
         env.handle.close(); env.handle = None
+    if isinstance(env, DeviceModuleEnv) and (norm_obs or norm_reward):   # not available for plug-in envs: fail here, with the library's message
+        env._h()
     return env
 
 

@@ -76,7 +76,7 @@ struct DrilF32Fallback
     latch_updates_left::Int32; forward_exact_f32::Int32; max_abs_w2::Float32; reserved::Int32
 end
 
-const ENV_KINDS = Dict(:CartPole => Int32(0), :Pendulum => Int32(1), :ScaledPendulum => Int32(2), :MountainCar => Int32(3), :MountainCarContinuous => Int32(4), :Acrobot => Int32(6), :ScaledMountainCarContinuous => Int32(7))   # :ScaledPendulum = ScalingWrapperEnv(PendulumEnv()) on every sub-env (scalingWrapperEnv.jl)
+const ENV_KINDS = Dict(:CartPole => Int32(0), :Pendulum => Int32(1), :ScaledPendulum => Int32(2), :MountainCar => Int32(3), :MountainCarContinuous => Int32(4), :Acrobot => Int32(6), :ScaledMountainCarContinuous => Int32(7), :Module => Int32(8))   # :ScaledPendulum = ScalingWrapperEnv(PendulumEnv()) on every sub-env (scalingWrapperEnv.jl)
 
 """
     DeviceParallelEnv(kind, n_envs; max_steps, seed, fixed_length_episodes, device) <: AbstractParallelEnv
@@ -113,14 +113,34 @@ function DeviceParallelEnv(kind::Symbol, n_envs::Integer; max_steps::Integer = (
 end
 
 number_of_envs(env::DeviceParallelEnv) = env.n_envs
-is_discrete(env) = env.kind === :CartPole || env.kind === :MountainCar || env.kind === :Acrobot
-observation_space(env::DeviceParallelEnv) = env.kind === :Acrobot ? Box(Float32[-1, -1, -1, -1, -4π, -9π], Float32[1, 1, 1, 1, 4π, 9π]) : (env.kind === :MountainCar || env.kind === :MountainCarContinuous) ? Box(Float32[-1.2, -0.07], Float32[0.6, 0.07]) : env.kind === :ScaledMountainCarContinuous ? Box(Float32[-1, -1], Float32[1, 1]) :
+
+# ---- device env plug-ins (DRIL_ENV_MODULE): the caller's own env as a gfx950 code object built from include/device/dril_env_plugin.h ----
+# dril_env_module_info (include/dril_hip.h) read through a byte buffer: u32 abi, i32 S, D, A, discrete, episode_len, f32 low[64], f32 high[64], char name[64]
+const MODULE_INFO_BYTES = 24 + 4 * 64 + 4 * 64 + 64
+const MODULE_ENVS = IdDict{Any, NamedTuple}()            # env => (path, state_dim, obs_dim, action_dim, discrete, episode_len, low, high, name)
+function describe_env_module(path::AbstractString, device::Integer = 0)
+    buf = zeros(UInt8, MODULE_INFO_BYTES)
+    check(ccall((:dril_env_module_describe, LIB[]), Int32, (Cstring, Int32, Ptr{Cvoid}), path, Int32(device), buf))
+    i32 = reinterpret(Int32, buf[5:24]); A = Int(i32[3])
+    low = collect(reinterpret(Float32, buf[25:280]))[1:A]; high = collect(reinterpret(Float32, buf[281:536]))[1:A]
+    name = String(buf[537:(536 + something(findfirst(==(0x00), buf[537:end]), 65) - 1)])
+    return (path = String(path), state_dim = Int(i32[1]), obs_dim = Int(i32[2]), action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]), low = low, high = high, name = name)
+end
+"`OnDeviceModule(path, n_envs)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop)"
+function OnDeviceModule(path::AbstractString, n_envs::Integer; max_steps::Union{Nothing, Integer} = nothing, seed::Integer = 42, device::Integer = 0, monitor_window::Integer = 0)
+    info = describe_env_module(path, device)
+    env = DeviceParallelEnv(:Module, n_envs; max_steps = something(max_steps, info.episode_len), seed = seed, device = device, monitor_window = monitor_window)
+    MODULE_ENVS[env] = info
+    return env
+end
+is_discrete(env) = env.kind === :Module ? MODULE_ENVS[env].discrete : env.kind === :CartPole || env.kind === :MountainCar || env.kind === :Acrobot
+observation_space(env::DeviceParallelEnv) = env.kind === :Module ? Box(fill(-Inf32, MODULE_ENVS[env].obs_dim), fill(Inf32, MODULE_ENVS[env].obs_dim)) : env.kind === :Acrobot ? Box(Float32[-1, -1, -1, -1, -4π, -9π], Float32[1, 1, 1, 1, 4π, 9π]) : (env.kind === :MountainCar || env.kind === :MountainCarContinuous) ? Box(Float32[-1.2, -0.07], Float32[0.6, 0.07]) : env.kind === :ScaledMountainCarContinuous ? Box(Float32[-1, -1], Float32[1, 1]) :
     env.kind === :CartPole ?
     Box(Float32[-4.8, -Inf, -0.41887903, -Inf], Float32[4.8, Inf, 0.41887903, Inf]) :
     env.kind === :ScaledPendulum ? Box(Float32[-1, -1, -1], Float32[1, 1, 1]) : Box(Float32[-1, -1, -8], Float32[1, 1, 8])
-action_space(env::DeviceParallelEnv) = env.kind === :CartPole ? Discrete(2) : (env.kind === :MountainCar || env.kind === :Acrobot) ? Discrete(3) :
+action_space(env::DeviceParallelEnv) = env.kind === :Module ? (MODULE_ENVS[env].discrete ? Discrete(MODULE_ENVS[env].action_dim) : Box(MODULE_ENVS[env].low, MODULE_ENVS[env].high)) : env.kind === :CartPole ? Discrete(2) : (env.kind === :MountainCar || env.kind === :Acrobot) ? Discrete(3) :
     (env.kind === :ScaledPendulum || env.kind === :MountainCarContinuous || env.kind === :ScaledMountainCarContinuous) ? Box(Float32[-1], Float32[1]) : Box(Float32[-2], Float32[2])
-obs_dim(env::DeviceParallelEnv) = env.kind === :CartPole ? 4 : env.kind === :Acrobot ? 6 : (env.kind === :MountainCar || env.kind === :MountainCarContinuous || env.kind === :ScaledMountainCarContinuous) ? 2 : 3
+obs_dim(env::DeviceParallelEnv) = env.kind === :Module ? MODULE_ENVS[env].obs_dim : env.kind === :CartPole ? 4 : env.kind === :Acrobot ? 6 : (env.kind === :MountainCar || env.kind === :MountainCarContinuous || env.kind === :ScaledMountainCarContinuous) ? 2 : 3
 
 last_error(h) = unsafe_string(ccall((:dril_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h))
 function check(rc::Int32, h = C_NULL)
@@ -154,7 +174,11 @@ function bind!(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int} = [64, 64],
         env.handle != C_NULL && ccall((:dril_destroy, LIB[]), Int32, (Ptr{Cvoid},), env.handle)
         cfg = Ref(make_config(env, alg, hidden, log_std_init, act))
         h = Ref{Ptr{Cvoid}}(C_NULL)
-        check(ccall((:dril_create, LIB[]), Int32, (Ref{DrilConfig}, Ref{Ptr{Cvoid}}), cfg, h))
+        if env.kind === :Module                                  # a device env plug-in: the library loads the code object itself
+            check(ccall((:dril_create_with_env_module, LIB[]), Int32, (Ref{DrilConfig}, Cstring, Ref{Ptr{Cvoid}}), cfg, MODULE_ENVS[env].path, h))
+        else
+            check(ccall((:dril_create, LIB[]), Int32, (Ref{DrilConfig}, Ref{Ptr{Cvoid}}), cfg, h))
+        end
         env.handle = h[]; env.bound = key; env.optimizer_owner = nothing
         check(ccall((:dril_env_reset, LIB[]), Int32, (Ptr{Cvoid}, UInt64), env.handle, env.seed), env.handle)
     end
@@ -486,6 +510,6 @@ include("DRiLHIP_host_envs.jl")     # OnDevice(env::AbstractParallelEnv): host e
 include("DRiLHIP_extras.jl")        # normalisation statistics, evaluate_agent
 include("DRiLHIP_sac.jl")           # SAC
 
-export DeviceParallelEnv, OnDevice
+export DeviceParallelEnv, OnDevice, OnDeviceModule, describe_env_module
 
 end # module

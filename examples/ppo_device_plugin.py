@@ -1,0 +1,32 @@
+#!/usr/bin/env python3
+"""PPO on the caller's OWN env, living on the device: examples/envs/reacher3_plugin.hip (a point mass in 3-D pushed towards a per-episode random target; 12
+observation dims, 3 action dims — nothing the built-in kinds can express) is compiled by the library's Makefile into a gfx950 code object; the library loads
+it (DRIL_ENV_MODULE) and steps it with its own kernels.  No host env anywhere in the loop.
+
+usage: python examples/ppo_device_plugin.py [n_envs=256] [iterations=30]"""
+import sys
+from pathlib import Path
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+import __graft_entry__ as g
+
+pkg = g.load_package()
+n_envs = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+iters = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+code_object = ROOT / "examples" / "envs" / "reacher3_plugin.hsaco"        # built by `make -C dril.jl_amd/csrc` (__graft_entry__.build())
+print("env:", pkg.describe_env_module(code_object))
+env = pkg.MonitorWrapperEnv(pkg.DeviceModuleEnv(code_object, n_envs, seed=0), stats_window=n_envs)
+alg = pkg.PPO(n_steps=100, batch_size=n_envs * 100 // 4, epochs=10, learning_rate=1e-3)
+agent = pkg.Agent(pkg.ActorCriticLayer(env.observation_space(), env.action_space()), alg, seed=0)
+
+
+class PrintReturn:
+    def on_rollout_end(self, loc):
+        r, l, n = loc["env"].handle.monitor_stats()
+        print(f"iteration {loc['i']:3d}: episode return {r:8.3f}  length {l:6.1f}  ({n} episodes in the window)  rollout {loc['fps']:.3g} env-steps/s")
+        return True
+
+
+stats, timer = pkg.train_(agent, env, alg, iters * alg.n_steps * n_envs, callbacks=[PrintReturn()])
+print(f"trained {iters} iterations in {timer['training_loop']:.2f} s; last loss {stats['losses'][-1]:.4f}")
+print("evaluate_agent:", pkg.evaluate_agent(agent, env, n_eval_episodes=20))

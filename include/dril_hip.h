@@ -69,7 +69,14 @@ enum dril_env_kind {
     DRIL_ENV_ACROBOT = 6,
     /* ScalingWrapperEnv(MountainCarContinuousEnv()): observations Box((-1.2, -0.07), (0.6, 0.07)) scaled to Box(-1, 1), actions Box(-1, 1) mapped back by the same
      * affine formulas (scalingWrapperEnv.jl:71-79); every kernel that does not touch the simulator is shared with DRIL_ENV_MOUNTAINCAR_CONTINUOUS */
-    DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED = 7
+    DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED = 7,
+    /* a DEVICE ENV PLUG-IN: the caller's own env, written against include/device/dril_env_plugin.h (reset / observe / step of one env as device functions), compiled on
+     * its own into a gfx950 code object (hipcc --genco) and loaded with the HIP module API by dril_create_with_env_module below.  Spaces, bounds and the default
+     * time limit come from the code object's descriptor; its three kernels stand where env_reset_kernel / env_observe_kernel / env_step_kernel stand for a built-in
+     * kind, so every device-env verb works: dril_env_*, dril_collect_rollout (step-granular: policy launches + ONE env launch per step), dril_train,
+     * dril_evaluate_agent, monitor_window.  Always on the generic kernels (any hidden_dims).  Refused: norm_obs / norm_reward (the running-moment tables hold 8
+     * observation dims), the dril_ext_* verbs, SAC.  dril_create itself refuses this kind: it has no code object to load.  docs/external_envs.md */
+    DRIL_ENV_MODULE = 8
 };
 
 /* ids for dril_buffer_copy_out / dril_buffer_copy_in (fields of RolloutBuffer,
@@ -181,6 +188,24 @@ int32_t dril_config_default(dril_config* cfg, int32_t env_kind);
 /* ---- lifetime ------------------------------------------------------------ */
 /* RolloutBuffer(...) ppo.jl:112-115 + Agent(layer, alg) ppo.jl:42-62 (device state only) */
 int32_t dril_create(const dril_config* cfg, dril_handle** out);
+/* the same for cfg->env_kind == DRIL_ENV_MODULE: code_object_path names a gfx950 code object built from include/device/dril_env_plugin.h (a plain ELF or a
+ * clang-offload-bundle).  A null path, an unreadable file and a file that is neither are DRIL_ERR_INVALID_ARG before any HIP call; then the module is loaded, its
+ * descriptor copied out and checked (plug-in ABI number, size of the kernel argument block, S 1..64, D 1..1024, A 1..64, time limit) and its three kernels looked
+ * up: a mismatch is DRIL_ERR_UNSUPPORTED with a message, before anything of the module is launched.  cfg->episode_len == 0 takes the descriptor's time limit;
+ * Box bounds per dimension come from the descriptor (ClampAdapter).  The module is unloaded by dril_destroy and on every failing path of this call. */
+int32_t dril_create_with_env_module(const dril_config* cfg, const char* code_object_path, dril_handle** out);
+/* what a code object says about itself — the host needs the spaces to build the ActorCriticLayer before a handle exists */
+typedef struct dril_env_module_info {
+    uint32_t plugin_abi;                                   /* DRIL_ENV_PLUGIN_ABI the code object was compiled against */
+    int32_t state_dim, obs_dim, action_dim, discrete;      /* S, D, A (Discrete: number of actions), 1 = Discrete(A, action_start) / 0 = Box */
+    int32_t episode_len;                                   /* default time limit */
+    float action_low[64], action_high[64];                 /* Box bounds, entries 0 .. action_dim-1 (continuous) */
+    char name[64];
+} dril_env_module_info;
+/* loads the code object on `device`, reads and checks its descriptor, unloads it again; same checks and statuses as dril_create_with_env_module */
+int32_t dril_env_module_describe(const char* code_object_path, int32_t device, dril_env_module_info* out);
+/* the same record of a live handle (DRIL_ERR_UNSUPPORTED for a handle of another env kind) */
+int32_t dril_env_module_info_of(const dril_handle* h, dril_env_module_info* out);
 int32_t dril_destroy(dril_handle* h);
 /* message of the last failing call on h (or of the last failing create when h == NULL) */
 const char* dril_last_error(const dril_handle* h);
