@@ -203,6 +203,8 @@ _PD, _PF, _PI64 = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int
 _SAC_SIG = {
     "config_default": (C.c_int32, [C.POINTER(DrilSacConfig), C.c_int32]),
     "create": (C.c_int32, [C.POINTER(DrilSacConfig), C.POINTER(_P)]),
+    "create_with_env_module": (C.c_int32, [C.POINTER(DrilSacConfig), C.c_char_p, C.POINTER(_P)]),
+    "env_module_info_of": (C.c_int32, [_P, C.POINTER(DrilEnvModuleInfo)]),
     "destroy": (C.c_int32, [_P]),
     "last_error": (C.c_char_p, [_P]),
     "obs_dim": (C.c_int32, [_P]),

@@ -29,6 +29,8 @@
 #include "../../include/dril_sac.h"
 #include "dril_internal.h"
 #include "dril_gemm.h"
+#include "dril_sac_adapter.h"
+#include "dril_env_module.h"
 
 using namespace dril;
 
@@ -914,7 +916,8 @@ __global__ __launch_bounds__(256) void sac_step_end_kernel(StepEndArgs a) {
 // ---- collection (off_policy_collection.jl:28-96) ---------------------------------------------------------------------------
 struct CollectHeadArgs {
     int E, A, use_random; float* mu; const float* log_std; const float* inj_noise; const uint32_t* gstep; uint64_t seed0;
-    float low, high; float* raw; float* envact;
+    const float* low; const float* high;                              // Box bounds per action dimension, device table [A] each (built-in and external envs: their one pair in every entry)
+    float* raw; float* envact;
     const float* h2; const float* w3; const float* b3; int H2;     // h2 != null: the actor's output layer mu = W3 h2 + b3 is evaluated HERE (sac_mu_rows) instead of in a launch of its own
 };
 // mu[e][a] = W3[a, :] . h2[e, :] + b3[a] for the kEnvsPerBlock envs of a 256-thread block (4096 envs = 256 blocks: every CU takes part in what is a latency-bound
@@ -959,16 +962,16 @@ __device__ __forceinline__ void sac_collect_action(const CollectHeadArgs& g, int
     float z, r, ev;
     if (g.inj_noise) z = g.inj_noise[e * g.A + a];
     else z = g.use_random ? env_noise_u01_f32(g.seed0 + (uint64_t)e, gstep, a) : env_noise_randn(g.seed0 + (uint64_t)e, gstep, a);
-    if (g.use_random) { r = g.low + z * (g.high - g.low); ev = r; }                              // rand(rng, act_space): already env space, :50-53
+    const float lo = g.low[a], hi = g.high[a];
+    if (g.use_random) { r = sac_rand_box(z, lo, hi); ev = r; }                                   // rand(rng, act_space) per dimension: already env space, :50-53
     else {
         r = tanhf(mu + expf(g.log_std[a]) * z);                                                  // rand(SquashedDiagGaussian) squashedDiagGaussian.jl:24-27
-        ev = tanhf(r) * (g.high - g.low) / 2.0f + (g.low + g.high) / 2.0f;                       // to_env(TanhScaleAdapter) default_adapters.jl:13-21
+        ev = sac_to_env(r, lo, hi);                                                              // to_env(TanhScaleAdapter) default_adapters.jl:13-21
     }
     *raw = r; *envact = ev;
 }
-// 256 threads per kEnvsPerBlock envs: the output layer by all four waves (g.h2 set), then one thread per env
-__global__ __launch_bounds__(256) void sac_collect_head_kernel(CollectHeadArgs g) {
-    __shared__ float mu_s[kEnvsPerBlock];
+// the head of the kEnvsPerBlock envs of a 256-thread block: the output layer by all four waves (g.h2 set), then one thread per env
+__device__ __forceinline__ void sac_head_block(const CollectHeadArgs& g, float* mu_s) {
     const int e = blockIdx.x * kEnvsPerBlock + threadIdx.x;
     if (g.h2 && !g.use_random) {                                     // the output layer first (whole block: no early return before it)
         for (int a = 0; a < g.A; ++a) {
@@ -985,6 +988,10 @@ __global__ __launch_bounds__(256) void sac_collect_head_kernel(CollectHeadArgs g
         sac_collect_action(g, e, gs, a, g.use_random ? 0.f : g.mu[(size_t)e * g.A + a], &r, &ev);
         g.raw[e * g.A + a] = r; g.envact[e * g.A + a] = ev;
     }
+}
+__global__ __launch_bounds__(256) void sac_collect_head_kernel(CollectHeadArgs g) {
+    __shared__ float mu_s[kEnvsPerBlock];
+    sac_head_block(g, mu_s);
 }
 struct PushArgs {
     int E, D, A; long long cap, tail; const float *obs, *raw, *rew, *tobs, *nobs; const uint8_t *term, *trunc;
@@ -1006,6 +1013,44 @@ __global__ void sac_push_kernel(PushArgs g) {
     phase_stamp(g.stamp);                                    // (within a microsecond of the kernel's end: the stamp feeds a per-iteration fps statistic)
     if (e >= g.E) return;
     sac_push_row(g, e, g.D, g.A, g.tobs + (size_t)e * g.D, g.nobs + (size_t)e * g.D, g.raw + e * g.A, g.rew[e], g.term[e] != 0, g.trunc[e] != 0);
+}
+// push! of the n envs [e0, e0 + n) by a whole workgroup, memory to memory: the threads walk the flat (env, dim) index of each field, so a wave's stores into rb_obs /
+// rb_next / rb_act are one contiguous run for any D / A (consecutive envs take consecutive ring slots; the run breaks once, where the ring wraps) instead of one lane
+// per env with a D-float stride.  Same rows, same slots as sac_push_row.
+__device__ __forceinline__ void sac_push_block(const PushArgs& g, int e0, int n) {
+    const int D = g.D, A = g.A;
+    for (int i = threadIdx.x; i < n * D; i += blockDim.x) {
+        const int e = e0 + i / D, d = i % D;
+        const long long slot = (g.tail + e) % g.cap;
+        g.rb_obs[slot * D + d] = g.obs[(size_t)e * D + d];
+        g.rb_next[slot * D + d] = g.trunc[e] ? g.tobs[(size_t)e * D + d] : g.nobs[(size_t)e * D + d];   // truncated_observation | next observation
+    }
+    for (int i = threadIdx.x; i < n * A; i += blockDim.x) {
+        const int e = e0 + i / A, a = i % A;
+        g.rb_act[((g.tail + e) % g.cap) * A + a] = g.raw[(size_t)e * A + a];                        // unprocessed action, :72
+    }
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int e = e0 + i;
+        const long long slot = (g.tail + e) % g.cap;
+        g.rb_rew[slot] = g.rew[e]; g.rb_term[slot] = g.term[e] != 0; g.rb_trunc[slot] = g.trunc[e] != 0;
+    }
+}
+constexpr int kPushEnvsPerBlock = 64;
+__global__ __launch_bounds__(256) void sac_push_flat_kernel(PushArgs g) {
+    const int e0 = blockIdx.x * kPushEnvsPerBlock;
+    phase_stamp(g.stamp);
+    sac_push_block(g, e0, min(kPushEnvsPerBlock, g.E - e0));                                        // grid = ceil(E / kPushEnvsPerBlock): n >= 1
+}
+// Collection over a device env plug-in, whose step kernel already returns the next observation: per env step {head, plug-in step, push}.  This kernel is the push of
+// the PREVIOUS step and the head of THIS step of the same kEnvsPerBlock envs in one launch (p.E == 0: nothing to push yet), so n steps are n x {this, plug-in step}
+// and one trailing sac_push_flat_kernel.  The push reads the previous step's e_raw rows before the head overwrites them (the barrier); everything else the two halves
+// touch is disjoint, and a block reads and writes rows of its own envs only.
+struct HeadPushArgs { CollectHeadArgs head; PushArgs push; };
+__global__ __launch_bounds__(256) void sac_collect_head_push_kernel(HeadPushArgs c) {
+    __shared__ float mu_s[kEnvsPerBlock];
+    const int e0 = blockIdx.x * kEnvsPerBlock;
+    if (c.push.E > 0) { sac_push_block(c.push, e0, min(kEnvsPerBlock, c.push.E - e0)); __syncthreads(); }   // (grid = ceil(E / kEnvsPerBlock), push.E == head.E: n >= 1)
+    sac_head_block(c.head, mu_s);
 }
 // One env step of the collection for a DEVICE env in ONE launch: sac_collect_head_kernel -> env_step_kernel -> env_observe_kernel -> sac_push_kernel are all one thread per env
 // on data of that env only (four dependent launches of 4 - 5 us and their boundaries per collected step).  The same four definitions in the same order — sac_collect_action,
@@ -1050,7 +1095,7 @@ __global__ __launch_bounds__(256) void sac_collect_env_kernel(CollectEnvArgs c) 
     phase_stamp(c.push.stamp);                                               // thread 0 of the last workgroup owns a live env (grid = ceil(E / kEnvsPerBlock)): the end of its work ~ the end of the phase
 }
 // host-batch helpers
-__global__ void sac_squash_eval_kernel(int B, int A, const float* mu, const float* log_std, const float* noise, int deterministic, float low, float high,
+__global__ void sac_squash_eval_kernel(int B, int A, const float* mu, const float* log_std, const float* noise, int deterministic, const float* low, const float* high,
                                        float* actions, float* logp, float* envact) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
@@ -1059,7 +1104,7 @@ __global__ void sac_squash_eval_kernel(int B, int A, const float* mu, const floa
     const float lp = squashed_sample_logp(mu + (size_t)i * A, ls, nz, A, a_, gg);              // deterministic: mode(d) = tanh(mean) :48-50
     for (int a = 0; a < A; ++a) {
         if (actions) actions[i * A + a] = a_[a];
-        if (envact) envact[i * A + a] = tanhf(a_[a]) * (high - low) / 2.0f + (low + high) / 2.0f;
+        if (envact) envact[i * A + a] = sac_to_env(a_[a], low[a], high[a]);
     }
     if (logp) logp[i] = lp;
 }
@@ -1096,6 +1141,9 @@ struct dril_sac_handle {
     unsigned long long* it_stamps = nullptr; int it_stamps_cap = 0; double wall_hz = 1e8; bool fused_heads = true; bool fused_dw1 = false; int fl_c = 0, fl_a = 0; bool fused_collect = true; bool fused_fwd = true; bool trace_enqueue = false; std::vector<hipEvent_t> it_events; int iter_chunk = 64;   // fused output-layer + head kernels (DRIL_SAC_NO_FUSED_HEADS=1: the round-1 launch sequence, A/B)
     float bt_actor[2], bt_critic[2], bt_ent[2]; int64_t grad_updates = 0; uint64_t update_counter = 0, aux_counter = 0;
     float target_entropy = 0, act_lo = -2.0f, act_hi = 2.0f; bool external = false;   // bounds of the agent-facing action space: Box(-2,2), Box(-1,1) under ScalingWrapperEnv
+    float* act_bounds = nullptr;                     // device table [low[kMaxA] | high[kMaxA]] the sampling kernels read: the pair above in every entry, or a plug-in's bounds per dimension
+    // DRIL_ENV_MODULE: a device env plug-in (include/device/dril_env_plugin.h) loaded as a HIP module; its three kernels stand in for the env kernels of a built-in kind
+    bool module = false, fused_head_push = true; hipModule_t env_module = nullptr; hipFunction_t mod_reset = nullptr, mod_observe = nullptr, mod_step = nullptr; DrilEnvPluginDesc mod_desc{};
     // env
     float* state = nullptr; int32_t* step_count = nullptr; uint32_t *episode = nullptr, *gstep = nullptr; float* disc_returns = nullptr;
     float *obs_cur = nullptr, *obs_nxt = nullptr, *e_rew = nullptr, *e_tobs = nullptr, *e_raw = nullptr, *e_envact = nullptr; uint8_t *e_term = nullptr, *e_trunc = nullptr;
@@ -1317,13 +1365,62 @@ int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long*
     return DRIL_OK;
 }
 
+// the argument block of a plug-in's kernels: SAC has no MonitorWrapperEnv and no DiscreteAdapter (monitor pointers null, action_start 0)
+DrilEnvPluginArgs module_args(dril_sac_handle* h) {
+    DrilEnvPluginArgs a{};
+    a.E = h->cfg.n_envs; a.episode_len = h->cfg.episode_len; a.seed0 = h->env_seed0;
+    a.state = h->state; a.step_count = h->step_count; a.episode = h->episode; a.gstep = h->gstep;
+    return a;
+}
 int ensure_obs(dril_sac_handle* h) {
     if (!h->env_ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
-    if (!h->obs_valid) { SHIP(h, launch_env_observe(h->cfg.env_kind, h->cfg.n_envs, h->state, h->obs_cur, h->stream)); h->obs_valid = true; }
+    if (!h->obs_valid) {
+        if (h->module) { DrilEnvPluginArgs a = module_args(h); a.obs = h->obs_cur; SHIP(h, env_module_launch(h->mod_observe, a, h->stream)); }
+        else SHIP(h, launch_env_observe(h->cfg.env_kind, h->cfg.n_envs, h->state, h->obs_cur, h->stream));
+        h->obs_valid = true;
+    }
+    return DRIL_OK;
+}
+PushArgs push_args(dril_sac_handle* h, const float* obs, const float* nobs, unsigned long long* stamp) {
+    const long long tail = (h->head + h->size) % h->cap;
+    return PushArgs{h->cfg.n_envs, h->D, h->A, h->cap, tail, obs, h->e_raw, h->e_rew, h->e_tobs, nobs, h->e_term, h->e_trunc,
+                    h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, stamp};
+}
+void ring_advance(dril_sac_handle* h) {                                                            // CircularBuffer: n_envs rows in, overwrite the oldest
+    const long long over = h->size + h->cfg.n_envs - h->cap;
+    if (over > 0) { h->head = (h->head + over) % h->cap; h->size = h->cap; } else h->size += h->cfg.n_envs;
+}
+// head -> act! + observe -> push! of one collection step over a device env plug-in (the actor's hidden layers are already enqueued).  `first` / `last`: the step's
+// place in its collection — the fused form pushes step t's rows in the launch that computes the head of step t + 1, the last step's rows in a launch of their own,
+// so the ring is complete when the collection returns.
+int collect_step_module(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned long long* stamp, bool first, bool last) {
+    const int E = h->cfg.n_envs;
+    DrilEnvPluginArgs st = module_args(h);
+    // `actions` is the env-space action of TanhScaleAdapter / rand(action_space), inside the Box by construction: the wrapper's ClampAdapter is a no-op on it
+    st.actions = h->e_envact; st.rewards = h->e_rew; st.terminated = h->e_term; st.truncated = h->e_trunc; st.terminal_obs = h->e_tobs; st.obs = h->obs_nxt;
+    if (!h->fused_head_push) {                                                                       // DRIL_SAC_NO_FUSED_HEAD_PUSH=1: three launches per step
+        hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
+        SHIP(h, env_module_launch(h->mod_step, st, h->stream));
+        hipLaunchKernelGGL(sac_push_flat_kernel, dim3((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock), dim3(256), 0, h->stream, push_args(h, h->obs_cur, h->obs_nxt, stamp));
+        SHIP(h, hipGetLastError());
+        ring_advance(h); std::swap(h->obs_cur, h->obs_nxt);
+        return DRIL_OK;
+    }
+    // after the previous step's swap obs_nxt holds that step's observation and obs_cur its next observation: the rows of the pending push
+    HeadPushArgs hp{ca, push_args(h, h->obs_nxt, h->obs_cur, nullptr)};
+    if (first) hp.push.E = 0; else ring_advance(h);
+    hipLaunchKernelGGL(sac_collect_head_push_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, hp);
+    SHIP(h, env_module_launch(h->mod_step, st, h->stream));                                          // (overwrites obs_nxt: its old rows went into the ring one launch earlier)
+    std::swap(h->obs_cur, h->obs_nxt);
+    if (last) {
+        hipLaunchKernelGGL(sac_push_flat_kernel, dim3((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock), dim3(256), 0, h->stream, push_args(h, h->obs_nxt, h->obs_cur, stamp));
+        ring_advance(h);
+    }
+    SHIP(h, hipGetLastError());
     return DRIL_OK;
 }
 // one step of collect_trajectories (off_policy_collection.jl:42-93) for all envs
-int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, unsigned long long* stamp = nullptr) {
+int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, unsigned long long* stamp = nullptr, bool first = true, bool last = true) {
     const int E = h->cfg.n_envs, D = h->D, A = h->A;
     // predict_actions_raw :55 — the hidden layers as contractions (the first one inside the second's staging when the input is narrow); the output layer inside the head /
     // env kernel that follows (fused_fwd; DRIL_SAC_NO_FUSED_FWD=1: three contractions and mu through memory, the round 1 - 3 form)
@@ -1343,8 +1440,9 @@ int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, uns
         hipLaunchKernelGGL(sac_collect_l2_kernel, dim3((E + kL2TN - 1) / kL2TN, h->H2 / kL2TM), dim3(256), kL2LdsBytes, h->stream, l2);
         SHIP(h, hipGetLastError());
     } else if (!use_random) SDO(net_forward(h, h->params, h->actor, 0, D, A, h->obs_cur, D, 0, E, actor_bufs(h), 1, 1, mu_in_head));
-    CollectHeadArgs ca{E, A, use_random, h->mu, h->params + h->log_std_off, inj_noise, h->gstep, h->env_seed0, h->act_lo, h->act_hi, h->e_raw, h->e_envact,
+    CollectHeadArgs ca{E, A, use_random, h->mu, h->params + h->log_std_off, inj_noise, h->gstep, h->env_seed0, h->act_bounds, h->act_bounds + kMaxA, h->e_raw, h->e_envact,
                        mu_in_head ? h->ah2 : nullptr, h->params + h->actor.w3, h->params + h->actor.b3, h->H2};
+    if (h->module) return collect_step_module(h, ca, stamp, first, last);
     if (A == 1 && !h->external && h->fused_collect) {                                                            // every device Box env: head + act! + observe + push! in one launch
         const long long tail1 = (h->head + h->size) % h->cap;
         PushArgs pa1{E, D, A, h->cap, tail1, h->obs_cur, h->e_raw, h->e_rew, h->e_tobs, h->obs_nxt, h->e_term, h->e_trunc,
@@ -1384,7 +1482,7 @@ int collect(dril_sac_handle* h, int n_steps, int use_random, double* fps) {
     const auto t0 = std::chrono::steady_clock::now();
     if (h->cfg.profile_events) hipEventRecord(h->ev_a, h->stream);
     for (int t = 0; t < n_steps; ++t)
-        SDO(collect_step(h, use_random, h->collect_noise ? h->collect_noise + (size_t)t * h->cfg.n_envs * h->A : nullptr));
+        SDO(collect_step(h, use_random, h->collect_noise ? h->collect_noise + (size_t)t * h->cfg.n_envs * h->A : nullptr, nullptr, t == 0, t == n_steps - 1));
     if (h->cfg.profile_events) hipEventRecord(h->ev_b, h->stream);
     SDO(ssync(h));
     if (h->cfg.profile_events) { float ms = 0; if (hipEventElapsedTime(&ms, h->ev_a, h->ev_b) == hipSuccess) { h->collect_ms += ms; h->collect_steps += n_steps; } }
@@ -1453,7 +1551,7 @@ int run_iterations(dril_sac_handle* h, int count, int tf, int n_upd, dril_sac_st
         hipLaunchKernelGGL(sac_stamp_kernel, dim3(1), dim3(64), 0, h->stream, h->it_stamps);
     }
     for (int j = 0; j < count; ++j) {
-        for (int t = 0; t < tf; ++t) SDO(collect_step(h, 0, nullptr, timed && t == tf - 1 ? h->it_stamps + 1 + 2 * j : nullptr));
+        for (int t = 0; t < tf; ++t) SDO(collect_step(h, 0, nullptr, timed && t == tf - 1 ? h->it_stamps + 1 + 2 * j : nullptr, t == 0, t == tf - 1));
         for (int k = 0; k < n_upd; ++k) SDO(sac_one_update(h, -1, h->stats_out + ((size_t)j * n_upd + k) * 8, timed && k == n_upd - 1 ? h->it_stamps + 2 + 2 * j : nullptr));
     }
     SDO(ssync(h));
@@ -1507,9 +1605,9 @@ int params_from_device(dril_sac_handle* h, float* host, const float* dev) {
 // exported entry points (include/dril_sac.h)
 // =================================================================================================================
 DRIL_EXPORT int32_t dril_sac_config_default(dril_sac_config* c, int32_t env_kind) {
-    if (!c || (env_kind != DRIL_ENV_PENDULUM && env_kind != DRIL_ENV_PENDULUM_SCALED && env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS && env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED && env_kind != DRIL_ENV_EXTERNAL)) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "SAC needs a Box action space (sac.jl:74): env_kind must be DRIL_ENV_PENDULUM[_SCALED] or DRIL_ENV_EXTERNAL");
+    if (!c || (env_kind != DRIL_ENV_PENDULUM && env_kind != DRIL_ENV_PENDULUM_SCALED && env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS && env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED && env_kind != DRIL_ENV_EXTERNAL && env_kind != DRIL_ENV_MODULE)) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "SAC needs a Box action space (sac.jl:74): env_kind must be DRIL_ENV_PENDULUM[_SCALED], DRIL_ENV_EXTERNAL or DRIL_ENV_MODULE");
     memset(c, 0, sizeof(*c));
-    c->abi_version = DRIL_SAC_ABI_VERSION; c->env_kind = env_kind; c->n_envs = 1; c->episode_len = (env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 999 : 200;
+    c->abi_version = DRIL_SAC_ABI_VERSION; c->env_kind = env_kind; c->n_envs = 1; c->episode_len = env_kind == DRIL_ENV_MODULE ? 0 /* the descriptor's */ : (env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 999 : 200;
     c->hidden1 = 512; c->hidden2 = 512; c->activation = 1;
     c->buffer_capacity = 1000000; c->start_steps = 100; c->batch_size = 256; c->tau = 0.005f; c->gamma = 0.99f;
     c->train_freq = 1; c->gradient_steps = 1; c->target_update_interval = 1;
@@ -1527,38 +1625,82 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
                     h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->obs_cur, h->obs_nxt, h->e_rew, h->e_tobs, h->e_raw, h->e_envact, h->e_term, h->e_trunc,
                     h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, h->xa, h->ah1, h->ah2, h->mu, h->xq, h->xq_pi,
                     h->qh1, h->qh2, h->q_cur, h->q_pi, h->dq, h->dz2, h->dz1, h->dxq, h->dmu, h->b_rew, h->b_ne, h->b_nn, h->b_np,
-                    h->b_nlp, h->a_pi, h->g_pi, h->lp_pi, h->b_term, h->collect_noise, h->inj_idx, h->inj_ne, h->inj_nn, h->inj_np, h->s_in, h->s_act, h->s_noise, h->s_out, h->s_out2};
+                    h->b_nlp, h->a_pi, h->g_pi, h->lp_pi, h->b_term, h->collect_noise, h->act_bounds, h->inj_idx, h->inj_ne, h->inj_nn, h->inj_np, h->s_in, h->s_act, h->s_noise, h->s_out, h->s_out2};
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->ev_a) hipEventDestroy(h->ev_a); if (h->ev_b) hipEventDestroy(h->ev_b);
     for (hipEvent_t e : h->it_events) hipEventDestroy(e);
     if (h->it_stamps) hipFree(h->it_stamps);
     if (h->col_h1p) hipFree(h->col_h1p); if (h->col_w2p) hipFree(h->col_w2p); if (h->col_flags) hipFree(h->col_flags);
     if (h->stream) hipStreamDestroy(h->stream);
+    if (h->env_module) (void)hipModuleUnload(h->env_module);
     delete h;
     return DRIL_OK;
 }
 
+namespace {
+// what SAC asks of a plug-in beyond the loader's checks; decided on the host from the descriptor, before anything of the module is launched
+int check_sac_plugin(const DrilEnvPluginDesc& d, std::string& msg) {
+    if (d.discrete) { msg = std::string("env plug-in \"") + d.name + "\" has a Discrete action space: SAC needs a Box (sac.jl:74); Discrete plug-ins run PPO (dril_create_with_env_module)"; return DRIL_ERR_UNSUPPORTED; }
+    if (d.A > kMaxA) { msg = std::string("env plug-in \"") + d.name + "\" has " + std::to_string(d.A) + " action dims: the SAC kernels hold up to " + std::to_string(kMaxA) + " (the ext_action_dim limit)"; return DRIL_ERR_UNSUPPORTED; }
+    for (int a = 0; a < d.A; ++a)
+        if (!(d.action_low[a] < d.action_high[a])) {
+            msg = std::string("env plug-in \"") + d.name + "\": action dim " + std::to_string(a) + " has action_low " + std::to_string(d.action_low[a]) + " >= action_high " + std::to_string(d.action_high[a]) +
+                  ": TanhScaleAdapter scales into a finite Box (ClampAdapter's \"no clamp\" convention has no meaning for SAC)";
+            return DRIL_ERR_UNSUPPORTED;
+        }
+    return DRIL_OK;
+}
+int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sac_handle** out);
+}  // namespace
+
 DRIL_EXPORT int32_t dril_sac_create(const dril_sac_config* cfg, dril_sac_handle** out) {
+    if (cfg && cfg->abi_version == DRIL_SAC_ABI_VERSION && cfg->env_kind == DRIL_ENV_MODULE) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC on a device env plug-in (DRIL_ENV_MODULE) needs the plug-in's code object: use dril_sac_create_with_env_module(cfg, code_object_path, out)");
+    return sac_create_impl(cfg, nullptr, out);
+}
+DRIL_EXPORT int32_t dril_sac_create_with_env_module(const dril_sac_config* cfg, const char* code_object_path, dril_sac_handle** out) {
     if (!cfg || !out) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "null config / out pointer");
     if (cfg->abi_version != DRIL_SAC_ABI_VERSION) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_config.abi_version mismatch");
-    const bool ext = cfg->env_kind == DRIL_ENV_EXTERNAL;
-    if (cfg->env_kind == DRIL_ENV_MODULE) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC on a device env plug-in (DRIL_ENV_MODULE) is not built: plug-in envs run PPO (dril_create_with_env_module); SAC takes the built-in Box envs or DRIL_ENV_EXTERNAL");
-    if (!ext && cfg->env_kind != DRIL_ENV_PENDULUM && cfg->env_kind != DRIL_ENV_PENDULUM_SCALED && cfg->env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS && cfg->env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC needs a Box action space (sac.jl:74): DRIL_ENV_PENDULUM[_SCALED] or DRIL_ENV_EXTERNAL");
+    if (cfg->env_kind != DRIL_ENV_MODULE) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_create_with_env_module: cfg->env_kind must be DRIL_ENV_MODULE");
+    std::string msg; const int rc = check_code_object_path(code_object_path, msg);
+    if (rc) return sfail(nullptr, rc, "dril_sac_create_with_env_module: " + msg);
+    return sac_create_impl(cfg, code_object_path, out);
+}
+DRIL_EXPORT int32_t dril_sac_env_module_info_of(const dril_sac_handle* h, dril_env_module_info* out) {
+    if (!h || !out) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle / out");
+    if (!h->module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_info_of: the handle was not created with dril_sac_create_with_env_module");
+    fill_module_info(h->mod_desc, out);
+    return DRIL_OK;
+}
+
+namespace {
+int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sac_handle** out) {
+    if (!cfg || !out) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "null config / out pointer");
+    if (cfg->abi_version != DRIL_SAC_ABI_VERSION) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_config.abi_version mismatch");
+    const bool ext = cfg->env_kind == DRIL_ENV_EXTERNAL, is_module = cfg->env_kind == DRIL_ENV_MODULE;
+    if (is_module && cfg->episode_len < 0) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_MODULE: episode_len must be > 0, or 0 for the plug-in's own time limit");
+    if (!ext && !is_module && cfg->env_kind != DRIL_ENV_PENDULUM && cfg->env_kind != DRIL_ENV_PENDULUM_SCALED && cfg->env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS && cfg->env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC needs a Box action space (sac.jl:74): DRIL_ENV_PENDULUM[_SCALED] or DRIL_ENV_EXTERNAL");
     if (ext && (cfg->ext_obs_dim < 1 || cfg->ext_obs_dim > 1024 || cfg->ext_action_dim < 1 || cfg->ext_action_dim > kMaxA || !(cfg->ext_action_low < cfg->ext_action_high)))
         return sfail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_EXTERNAL: ext_obs_dim 1..1024, ext_action_dim 1..16, ext_action_low < ext_action_high");
-    if (cfg->n_envs <= 0 || (!ext && cfg->episode_len <= 0) || cfg->batch_size <= 0 || cfg->buffer_capacity < cfg->n_envs || cfg->train_freq <= 0 || cfg->target_update_interval <= 0)
+    if (cfg->n_envs <= 0 || (!ext && !is_module && cfg->episode_len <= 0) || cfg->batch_size <= 0 || cfg->buffer_capacity < cfg->n_envs || cfg->train_freq <= 0 || cfg->target_update_interval <= 0)
         return sfail(nullptr, DRIL_ERR_INVALID_ARG, "n_envs, episode_len, batch_size, train_freq, target_update_interval must be positive and buffer_capacity >= n_envs");
     if (cfg->hidden1 <= 0 || cfg->hidden2 <= 0 || cfg->hidden1 % 4 || cfg->hidden2 % 4) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "hidden dims must be positive multiples of 4");
     if (cfg->activation != 0 && cfg->activation != 1) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "activation: 0 tanh, 1 relu");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sfail(nullptr, DRIL_ERR_HIP, "no HIP device: libdril_hip has no CPU fallback");
     if (cfg->device < 0 || cfg->device >= ndev) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "device ordinal out of range");
+    hipModule_t mod = nullptr; DrilEnvPluginDesc desc{};
+    if (is_module) {                                                                     // the descriptor gives the spaces and the bounds: load it before anything is sized
+        std::string msg; int rcm = load_env_module(module_path, cfg->device, &mod, &desc, msg);
+        if (!rcm && (rcm = check_sac_plugin(desc, msg)) != DRIL_OK) { (void)hipModuleUnload(mod); (void)hipGetLastError(); }
+        if (rcm) return sfail(nullptr, rcm, "dril_sac_create_with_env_module: " + msg);
+    }
     dril_sac_handle* h = new dril_sac_handle(); h->cfg = *cfg;
+    if (is_module) { h->module = true; h->env_module = mod; h->mod_desc = desc; if (cfg->episode_len == 0) h->cfg.episode_len = desc.episode_len; }   // (dril_sac_destroy unloads it on every failing path below)
 #define CHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(_e); dril_sac_destroy(h); return sfail(nullptr, DRIL_ERR_HIP, m); } } while (0)
     CHK(hipSetDevice(cfg->device));
     CHK(hipStreamCreate(&h->stream));
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->cfg.device) == hipSuccess && khz > 0) h->wall_hz = 1e3 * (double)khz; }   // wall_clock64 ticks per second (phase_stamp)
-    const int D = h->D = ext ? cfg->ext_obs_dim : ((cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 2 : 3), A = h->A = ext ? cfg->ext_action_dim : 1, S = h->S = ext ? 0 : 2, H1 = h->H1 = cfg->hidden1, H2 = h->H2 = cfg->hidden2, E = cfg->n_envs, B = cfg->batch_size, W = D + A;
+    const int D = h->D = is_module ? desc.D : ext ? cfg->ext_obs_dim : ((cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 2 : 3), A = h->A = is_module ? desc.A : ext ? cfg->ext_action_dim : 1, S = h->S = is_module ? desc.S : ext ? 0 : 2, H1 = h->H1 = cfg->hidden1, H2 = h->H2 = cfg->hidden2, E = cfg->n_envs, B = cfg->batch_size, W = D + A;
     h->Pa = D * H1 + H1 + H1 * H2 + H2 + H2 * A + A; h->Pq = W * H1 + H1 + H1 * H2 + H2 + H2 + 1; h->P = h->Pa + 2 * h->Pq + A;
     h->actor = net_off(0, D, H1, H2, A); h->Pqd = round4(h->Pq); h->q0 = net_off(round4(h->actor.end), W, H1, H2, 1);
     h->log_std_off = h->q0.w1 + 4 * h->Pqd; h->Pd = round4(h->log_std_off + A);      // device layout: actor | q1 | q2 | target q1 | target q2 | log_std
@@ -1566,6 +1708,16 @@ DRIL_EXPORT int32_t dril_sac_create(const dril_sac_config* cfg, dril_sac_handle*
     h->target_entropy = cfg->auto_target_entropy ? -(float)A : cfg->target_entropy;
     h->act_hi = (cfg->env_kind == DRIL_ENV_PENDULUM_SCALED || cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 1.0f : 2.0f; h->act_lo = -h->act_hi; h->external = ext;
     if (ext) { h->act_lo = cfg->ext_action_low; h->act_hi = cfg->ext_action_high; }
+    {   // the bounds table of the sampling kernels
+        float tb[2 * kMaxA];
+        for (int a = 0; a < kMaxA; ++a) { const bool own = is_module && a < A; tb[a] = own ? desc.action_low[a] : h->act_lo; tb[kMaxA + a] = own ? desc.action_high[a] : h->act_hi; }
+        CHK(smalloc(&h->act_bounds, 2 * kMaxA)); CHK(hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
+    }
+    if (is_module) {
+        CHK(hipModuleGetFunction(&h->mod_reset, h->env_module, "dril_env_plugin_reset")); CHK(hipModuleGetFunction(&h->mod_observe, h->env_module, "dril_env_plugin_observe"));
+        CHK(hipModuleGetFunction(&h->mod_step, h->env_module, "dril_env_plugin_step"));
+        h->fused_head_push = std::getenv("DRIL_SAC_NO_FUSED_HEAD_PUSH") == nullptr;           // A/B switch, latched here: head + plug-in step + push as three launches per env step
+    }
     CHK(smalloc(&h->params, h->Pd)); CHK(smalloc(&h->adam_m, h->Pd)); CHK(smalloc(&h->adam_v, h->Pd));
     h->target = h->params + h->q0.w1 + 2 * h->Pqd;   // the targets sit right behind the critics so that one launch runs all four Q nets (blockIdx.z stride Pqd)
     CHK(smalloc(&h->g_critic, h->Pd)); CHK(smalloc(&h->g_actor, h->Pd)); CHK(smalloc(&h->sc, 1)); CHK(smalloc(&h->sc_next, 1)); CHK(smalloc(&h->stats, 8));
@@ -1600,6 +1752,7 @@ DRIL_EXPORT int32_t dril_sac_create(const dril_sac_config* cfg, dril_sac_handle*
     *out = h;
     return DRIL_OK;
 }
+}  // namespace
 DRIL_EXPORT const char* dril_sac_last_error(const dril_sac_handle* h) { return h ? h->err.c_str() : g_sac_create_error.c_str(); }
 DRIL_EXPORT int32_t dril_sac_obs_dim(const dril_sac_handle* h) { return h ? h->D : 0; }
 DRIL_EXPORT int32_t dril_sac_action_dim(const dril_sac_handle* h) { return h ? h->A : 0; }
@@ -1647,7 +1800,8 @@ DRIL_EXPORT int32_t dril_sac_reset_optimizer(dril_sac_handle* h) {
 DRIL_EXPORT int32_t dril_sac_env_reset(dril_sac_handle* h, uint64_t seed) {
     SNEED(h); S_NOT_EXTERNAL(h, "dril_sac_env_reset");
     h->env_seed0 = seed;
-    SHIP(h, launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
+    if (h->module) SHIP(h, env_module_launch(h->mod_reset, module_args(h), h->stream));
+    else SHIP(h, launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
     h->env_ready = true; h->obs_valid = false;
     return ssync(h);
 }
@@ -1680,7 +1834,7 @@ DRIL_EXPORT int32_t dril_sac_action_log_prob(dril_sac_handle* h, const float* ob
         const int n = (int)std::min<int64_t>(h->nmax, batch - o);
         SDO(actor_chunk(h, obs + o * h->D, noise ? noise + o * h->A : nullptr, n, 0, o));
         hipLaunchKernelGGL(sac_squash_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, h->A, h->mu, h->params + h->log_std_off, h->s_noise, 0,
-                           h->act_lo, h->act_hi, h->s_out, h->s_out2, (float*)nullptr);
+                           h->act_bounds, h->act_bounds + kMaxA, h->s_out, h->s_out2, (float*)nullptr);
         SDO(ssync(h));
         if (actions) SHIP(h, hipMemcpy(actions + o * h->A, h->s_out, (size_t)n * h->A * 4, hipMemcpyDeviceToHost));
         if (logp) SHIP(h, hipMemcpy(logp + o, h->s_out2, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -1693,7 +1847,7 @@ DRIL_EXPORT int32_t dril_sac_predict_actions(dril_sac_handle* h, const float* ob
         const int n = (int)std::min<int64_t>(h->nmax, batch - o);
         SDO(actor_chunk(h, obs + o * h->D, noise ? noise + o * h->A : nullptr, n, deterministic, o));
         hipLaunchKernelGGL(sac_squash_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, h->A, h->mu, h->params + h->log_std_off, h->s_noise, deterministic,
-                           h->act_lo, h->act_hi, h->s_out, (float*)nullptr, h->s_out2);
+                           h->act_bounds, h->act_bounds + kMaxA, h->s_out, (float*)nullptr, h->s_out2);
         SDO(ssync(h));
         if (raw) SHIP(h, hipMemcpy(raw + o * h->A, h->s_out, (size_t)n * h->A * 4, hipMemcpyDeviceToHost));
         if (env) SHIP(h, hipMemcpy(env + o * h->A, h->s_out2, (size_t)n * h->A * 4, hipMemcpyDeviceToHost));
@@ -1732,6 +1886,7 @@ DRIL_EXPORT int32_t dril_sac_collect_rollout(dril_sac_handle* h, int32_t n_steps
 DRIL_EXPORT int32_t dril_sac_ext_push(dril_sac_handle* h, const float* obs, const float* stored_actions, const float* rewards, const uint8_t* terminated,
                                       const uint8_t* truncated, const float* next_obs, const float* terminal_obs) {
     SNEED(h);
+    if (h->module) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the env of a device env plug-in (DRIL_ENV_MODULE) is on the device, not on the host: dril_sac_collect_rollout steps it");
     if (!h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the handle was not created with DRIL_ENV_EXTERNAL");
     if (!obs || !stored_actions || !rewards || !terminated || !truncated || !next_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: null pointer");
     const size_t E = h->cfg.n_envs, D = h->D, A = h->A;

@@ -56,8 +56,17 @@ function sac_scatter_targets!(tp, flat::Vector{Float32})
     return tp
 end
 
+# dril_sac_env_module_info_of: spaces and bounds of the plug-in behind a live SAC handle (the byte layout describe_env_module reads)
+function sac_env_module_info(h::Ptr{Cvoid})
+    buf = zeros(UInt8, MODULE_INFO_BYTES)
+    sac_check(ccall((:dril_sac_env_module_info_of, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, buf), h)
+    i32 = reinterpret(Int32, buf[5:24]); A = Int(i32[3])
+    return (state_dim = Int(i32[1]), obs_dim = Int(i32[2]), action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]),
+        low = collect(reinterpret(Float32, buf[25:280]))[1:A], high = collect(reinterpret(Float32, buf[281:536]))[1:A])
+end
+
 function sac_config(env::DeviceParallelEnv, alg::DRiL.SAC, agent)
-    is_discrete(env) && error("SAC needs a Box action space (sac.jl:74): DeviceParallelEnv(:Pendulum | :ScaledPendulum | :MountainCarContinuous | :ScaledMountainCarContinuous, ...)")
+    is_discrete(env) && error("SAC needs a Box action space (sac.jl:74): DeviceParallelEnv(:Pendulum | :ScaledPendulum | :MountainCarContinuous | :ScaledMountainCarContinuous, ...) or OnDeviceModule over a Box plug-in")
     hd = hidden_dims_of(agent.train_state.parameters)
     act = agent.layer.actor_head.layers[1].layers[1].activation === DRiL.Lux.relu ? Int32(1) : Int32(0)   # SACLayer default relu (sac.jl:77)
     ec = alg.ent_coef
@@ -85,8 +94,17 @@ function train!(agent::SACAgent, env::DeviceParallelEnv, alg::DRiL.SAC, max_step
     end
     to = TimerOutput()
     cfg = Ref(sac_config(env, alg, agent)); hp = Ref{Ptr{Cvoid}}(C_NULL)
-    sac_check(ccall((:dril_sac_create, LIB[]), Int32, (Ref{DrilSacConfig}, Ref{Ptr{Cvoid}}), cfg, hp)); h = hp[]
+    if env.kind === :Module      # OnDeviceModule: the env is the caller's code object; spaces and per-dimension Box bounds are its descriptor's
+        sac_check(ccall((:dril_sac_create_with_env_module, LIB[]), Int32, (Ref{DrilSacConfig}, Cstring, Ref{Ptr{Cvoid}}), cfg, MODULE_ENVS[env].path, hp))
+    else
+        sac_check(ccall((:dril_sac_create, LIB[]), Int32, (Ref{DrilSacConfig}, Ref{Ptr{Cvoid}}), cfg, hp))
+    end
+    h = hp[]
     try
+        if env.kind === :Module      # the file may have changed since OnDeviceModule described it: the layer was built from that description
+            info = sac_env_module_info(h)
+            (info.obs_dim, info.action_dim) == (obs_dim(env), length(action_space(env).low)) || error("the plug-in behind the SAC handle is not the one OnDeviceModule described")
+        end
         flat = sac_flatten_params(agent.train_state.parameters); tgt = sac_flatten_targets(agent.aux.Q_target_parameters)
         GC.@preserve flat tgt begin
             sac_check(ccall((:dril_sac_set_params, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, flat, length(flat)), h)

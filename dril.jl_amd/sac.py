@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 import time
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
@@ -135,9 +136,19 @@ def sac_unflatten_params(flat: np.ndarray, like: dict) -> dict:
 
 def make_sac_config(env, n_envs: int, alg: SAC, layer: SACLayer, *, seed: int = 42, device: int = 0,
                     profile_events: bool = False) -> DrilSacConfig:
-    external = getattr(env, "kind", None) == capi.ENV_EXTERNAL
-    if not external and getattr(env, "kind", None) not in (capi.ENV_PENDULUM, capi.ENV_PENDULUM_SCALED, capi.ENV_MOUNTAINCAR_CONTINUOUS, capi.ENV_MOUNTAINCAR_CONTINUOUS_SCALED):
-        raise NotImplementedError("SAC needs a Box action space (sac.jl:74); the device envs with one are Pendulum-v1 (optionally under ScalingWrapperEnv) and MountainCarContinuous-v0")
+    """`env`: one env of a DeviceParallelEnv (`.env`), a HostParallelEnv, or a device env plug-in (a DeviceModuleEnv or its ModuleEnv: the spaces and the Box
+    bounds per dimension are the code object's, the handle is made with SacHandle(cfg, env_module=path))"""
+    if getattr(env, "kind", None) is None and getattr(getattr(env, "env", None), "kind", None) == capi.ENV_MODULE:
+        env = env.env                                     # a DeviceModuleEnv: its ModuleEnv
+    external, module = getattr(env, "kind", None) == capi.ENV_EXTERNAL, getattr(env, "kind", None) == capi.ENV_MODULE
+    if module:
+        if env.info["discrete"]:
+            raise NotImplementedError(f"SAC needs a Box action space (sac.jl:74): the device env plug-in {env.info['name']!r} is Discrete")
+        asp = env.action_space()
+        if len(asp.low) != layer.act_dim or env.info["obs_dim"] != layer.obs_dim:
+            raise ValueError(f"SACLayer is ({layer.obs_dim} obs, {layer.act_dim} action dims), the plug-in {env.info['name']!r} ({env.info['obs_dim']}, {len(asp.low)})")
+    if not external and not module and getattr(env, "kind", None) not in (capi.ENV_PENDULUM, capi.ENV_PENDULUM_SCALED, capi.ENV_MOUNTAINCAR_CONTINUOUS, capi.ENV_MOUNTAINCAR_CONTINUOUS_SCALED):
+        raise NotImplementedError("SAC needs a Box action space (sac.jl:74); the device envs with one are Pendulum-v1 (optionally under ScalingWrapperEnv), MountainCarContinuous-v0 and Box device env plug-ins (DeviceModuleEnv)")
     c = DrilSacConfig()
     c.abi_version = capi.SAC_ABI_VERSION
     c.env_kind, c.n_envs, c.episode_len = env.kind, n_envs, getattr(env, "max_steps", 0)
@@ -174,13 +185,16 @@ class SacHandle:
     def _load(cls) -> C.CDLL:
         return capi.load_library()
 
-    def __init__(self, cfg: DrilSacConfig):
+    def __init__(self, cfg: DrilSacConfig, env_module: Optional[os.PathLike] = None):
         self.lib = self._load()
         self.prefix = self._PREFIX
         prefix = self.prefix
         self.cfg = cfg
         self._h = C.c_void_p()
-        rc = self._f("create")(C.byref(cfg), C.byref(self._h))
+        if env_module is not None:      # cfg.env_kind == ENV_MODULE: the env is a code object built from include/device/dril_env_plugin.h
+            rc = self._f("create_with_env_module")(C.byref(cfg), os.fsencode(env_module), C.byref(self._h))
+        else:
+            rc = self._f("create")(C.byref(cfg), C.byref(self._h))
         if rc != capi.OK:
             le = getattr(self.lib, prefix + "last_error", None)
             raise DrilError(rc, (le(None) or b"").decode() if le else "create failed")
@@ -190,6 +204,13 @@ class SacHandle:
 
     def _f(self, name):
         return getattr(self.lib, self.prefix + name)
+
+    def env_module_info(self) -> dict:
+        """dril_sac_env_module_info_of: spaces and bounds of the plug-in behind this handle"""
+        from .host import _module_info_dict
+        info = capi.DrilEnvModuleInfo()
+        self._chk(self._f("env_module_info_of")(self._h, C.byref(info)))
+        return _module_info_dict(info)
 
     def close(self):
         if self._h:
@@ -413,7 +434,7 @@ _SAC_STAT_KEYS = ("actor_losses", "critic_losses", "entropy_losses", "entropy_co
 
 def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer: Optional[ReplayBuffer] = None, callbacks=None):
     """train!(agent, env, alg::SAC, max_steps) sac.jl:406-549 -> (agent, replay_buffer, training_stats, timer); `env` is a
-    DeviceParallelEnv over PendulumEnv.  training_stats carries the fields of SACTrainingStats (sac.jl:243-257)."""
+    DeviceParallelEnv over PendulumEnv / MountainCarContinuousEnv, a DeviceModuleEnv over a Box plug-in, or a HostParallelEnv.  training_stats carries the fields of SACTrainingStats (sac.jl:243-257)."""
     if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
         return _sac_train_host(agent, env, alg, max_steps, replay_buffer, list(callbacks or []))
     if callbacks:
@@ -421,7 +442,7 @@ def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer:
     t0 = time.perf_counter()
     rb = replay_buffer or ReplayBuffer(env.observation_space(), env.action_space(), alg.buffer_capacity)     # sac.jl:411
     cfg = make_sac_config(env.env, env.n_envs, alg, agent.layer, seed=env.seed, device=env._kw.get("device", 0), profile_events=env._kw.get("profile_events", False))
-    h = rb.handle if rb.handle is not None else SacHandle(cfg)
+    h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
     h.set_params(sac_flatten_params(agent.parameters))
     h.set_target_params(agent.q_target_parameters)
@@ -461,7 +482,7 @@ def _sac_train_callbacks(agent: SACAgent, env, alg: SAC, max_steps: int, replay_
     t0 = time.perf_counter()
     rb = replay_buffer or ReplayBuffer(env.observation_space(), env.action_space(), alg.buffer_capacity)
     cfg = make_sac_config(env.env, env.n_envs, alg, agent.layer, seed=env.seed, device=env._kw.get("device", 0), profile_events=env._kw.get("profile_events", False))
-    h = rb.handle if rb.handle is not None else SacHandle(cfg)
+    h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
     h.set_params(sac_flatten_params(agent.parameters)); h.set_target_params(agent.q_target_parameters); h.set_log_ent_coef(agent.log_ent_coef)
     h.env_reset(env.seed)

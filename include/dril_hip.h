@@ -75,7 +75,8 @@ enum dril_env_kind {
      * time limit come from the code object's descriptor; its three kernels stand where env_reset_kernel / env_observe_kernel / env_step_kernel stand for a built-in
      * kind, so every device-env verb works: dril_env_*, dril_collect_rollout (step-granular: policy launches + ONE env launch per step), dril_train,
      * dril_evaluate_agent, monitor_window.  Always on the generic kernels (any hidden_dims).  Refused: norm_obs / norm_reward (the running-moment tables hold 8
-     * observation dims), the dril_ext_* verbs, SAC.  dril_create itself refuses this kind: it has no code object to load.  docs/external_envs.md */
+     * observation dims), the dril_ext_* verbs.  SAC on a Box plug-in is available through dril_sac_create_with_env_module (dril_sac.h).  dril_create and
+     * dril_sac_create themselves refuse this kind: they have no code object to load.  docs/external_envs.md */
     DRIL_ENV_MODULE = 8
 };
 

@@ -49,9 +49,9 @@ enum dril_replay_id {
  * types (src/interfaces/entropy.jl) and the env ctor kwargs */
 typedef struct dril_sac_config {
     uint32_t abi_version;       /* DRIL_SAC_ABI_VERSION */
-    int32_t env_kind;           /* Box action space required (sac.jl:74): DRIL_ENV_PENDULUM[_SCALED], DRIL_ENV_MOUNTAINCAR_CONTINUOUS, or DRIL_ENV_EXTERNAL (host envs: ext_* below) */
+    int32_t env_kind;           /* Box action space required (sac.jl:74): DRIL_ENV_PENDULUM[_SCALED], DRIL_ENV_MOUNTAINCAR_CONTINUOUS, DRIL_ENV_EXTERNAL (host envs: ext_* below), or DRIL_ENV_MODULE (a device env plug-in: dril_sac_create_with_env_module) */
     int32_t n_envs;
-    int32_t episode_len;        /* max_steps kwarg: 200 Pendulum-v1 */
+    int32_t episode_len;        /* max_steps kwarg: 200 Pendulum-v1; DRIL_ENV_MODULE: 0 = the plug-in's own time limit */
     int32_t hidden1, hidden2;   /* SACLayer hidden_dims, default [512, 512] (sac.jl:76); multiples of 32 */
     int32_t activation;         /* 0 tanh, 1 relu (SACLayer default, sac.jl:77) */
     int64_t buffer_capacity;    /* :27 */
@@ -89,6 +89,17 @@ int32_t dril_sac_config_default(dril_sac_config* cfg, int32_t env_kind);
 
 /* ---- lifetime: ReplayBuffer(obs_space, act_space, capacity) sac.jl:411 + Agent(layer, alg::SAC) sac.jl:160-188 */
 int32_t dril_sac_create(const dril_sac_config* cfg, dril_sac_handle** out);
+/* the same for cfg->env_kind == DRIL_ENV_MODULE: SAC on a device env plug-in (include/device/dril_env_plugin.h), the twin of dril_create_with_env_module with the same
+ * load-time order and statuses (null / unreadable / non-code-object path: DRIL_ERR_INVALID_ARG before any HIP call; plug-in ABI number, argument-block size, S / D / A /
+ * time limit: DRIL_ERR_UNSUPPORTED with a message before anything of the module is launched).  Refused in addition, each with a message: a Discrete plug-in (SAC needs
+ * a Box, sac.jl:74), more than 16 action dims (the ext_action_dim limit), a dimension with action_low >= action_high (TanhScaleAdapter scales into a finite Box).
+ * cfg->episode_len == 0 takes the descriptor's time limit; observation / action dims and the Box bounds PER DIMENSION come from the descriptor, the ext_* fields are
+ * ignored.  Every verb below that works on a built-in device env works on such a handle; dril_sac_ext_push stays refused (the env is not on the host).  The module
+ * is unloaded by dril_sac_destroy and on every failing path of this call.  dril_sac_create itself refuses DRIL_ENV_MODULE: it has no code object to load.
+ * dril_env_module_describe (dril_hip.h) describes a path before a handle exists. */
+int32_t dril_sac_create_with_env_module(const dril_sac_config* cfg, const char* code_object_path, dril_sac_handle** out);
+/* spaces and bounds of the plug-in behind a live handle (DRIL_ERR_UNSUPPORTED for a handle of dril_sac_create) */
+int32_t dril_sac_env_module_info_of(const dril_sac_handle* h, dril_env_module_info* out);
 int32_t dril_sac_destroy(dril_sac_handle* h);
 const char* dril_sac_last_error(const dril_sac_handle* h);
 
