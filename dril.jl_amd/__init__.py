@@ -19,6 +19,6 @@ from .host import (  # noqa: F401
 )
 from .sac import (  # noqa: F401
     SAC, AutoEntropyCoefficient, FixedEntropyCoefficient, ReplayBuffer, SACAgent, SACLayer, SacHandle, get_gradient_steps, make_sac_config,
-    sac_flatten_params, sac_train_, sac_unflatten_params,
+    sac_evaluate_agent, sac_flatten_params, sac_train_, sac_unflatten_params,
 )
 from .checkpoint import load_normalization_stats_, load_policy_params_and_state_, save_normalization_stats, save_policy_params_and_state  # noqa: F401

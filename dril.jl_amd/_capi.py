@@ -237,6 +237,9 @@ _SAC_SIG = {
     "iterate": (C.c_int32, [_P, C.c_int32, _P, C.c_int64, _PD, C.c_int64]),
     "profile_get": (C.c_int32, [_P, _PD, _PI64, _PD, _PI64]),
     "profile_reset": (C.c_int32, [_P]),
+    "monitor_enable": (C.c_int32, [_P, C.c_int32]),
+    "monitor_get_stats": (C.c_int32, [_P, _PF, _PF, C.POINTER(C.c_int32)]),
+    "evaluate_agent": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(DrilEvalStats), _P, _P]),
 }
 _SIG.update({"dril_sac_" + k: v for k, v in _SAC_SIG.items()})
 EXPORTED_SYMBOLS = tuple(_SIG)

@@ -30,6 +30,7 @@
 #include "dril_internal.h"
 #include "dril_gemm.h"
 #include "dril_sac_adapter.h"
+#include "dril_sac_eval.h"
 #include "dril_env_module.h"
 
 using namespace dril;
@@ -919,6 +920,7 @@ struct CollectHeadArgs {
     const float* low; const float* high;                              // Box bounds per action dimension, device table [A] each (built-in and external envs: their one pair in every entry)
     float* raw; float* envact;
     const float* h2; const float* w3; const float* b3; int H2;     // h2 != null: the actor's output layer mu = W3 h2 + b3 is evaluated HERE (sac_mu_rows) instead of in a launch of its own
+    int deterministic;                                             // evaluation only (a collection leaves it 0): mode(d) = tanh(mean), squashedDiagGaussian.jl:48-50 — the sample with zero noise
 };
 // mu[e][a] = W3[a, :] . h2[e, :] + b3[a] for the kEnvsPerBlock envs of a 256-thread block (4096 envs = 256 blocks: every CU takes part in what is a latency-bound
 // pass): each of the four waves takes kMuRows envs, the wave across the features — per 256-feature slice all rows' loads (one coalesced 1 KB line run each) are in
@@ -960,7 +962,8 @@ __device__ __forceinline__ void sac_mu_block(const CollectHeadArgs& g, int a, in
 // the action the env receives (*envact); the caller stores them
 __device__ __forceinline__ void sac_collect_action(const CollectHeadArgs& g, int e, uint32_t gstep, int a, float mu, float* raw, float* envact) {
     float z, r, ev;
-    if (g.inj_noise) z = g.inj_noise[e * g.A + a];
+    if (g.deterministic) z = 0.f;                                                                // mode(d): the same expression as sac_squash_eval_kernel's deterministic branch
+    else if (g.inj_noise) z = g.inj_noise[e * g.A + a];
     else z = g.use_random ? env_noise_u01_f32(g.seed0 + (uint64_t)e, gstep, a) : env_noise_randn(g.seed0 + (uint64_t)e, gstep, a);
     const float lo = g.low[a], hi = g.high[a];
     if (g.use_random) { r = sac_rand_box(z, lo, hi); ev = r; }                                   // rand(rng, act_space) per dimension: already env space, :50-53
@@ -1057,42 +1060,134 @@ __global__ __launch_bounds__(256) void sac_collect_head_push_kernel(HeadPushArgs
 // the EnvCursor transition (env_advance / env_end_episode, dril_device.h), env_obs, sac_push_row — and every intermediate buffer (e_raw, e_envact, e_rew, e_term, e_trunc,
 // e_tobs, obs_nxt) still written: bit-identical to the four-launch sequence (A = 1: every device Box env).
 struct CollectEnvArgs { CollectHeadArgs head; PushArgs push; uint64_t seed0; int episode_len; float* state; int32_t* step_count; uint32_t* episode; uint32_t* gstep;
-                        float* rew; uint8_t* term; uint8_t* trunc; float* tobs; float* nobs; };
-template <int KIND>
-__global__ __launch_bounds__(256) void sac_collect_env_kernel(CollectEnvArgs c) {
-    constexpr int D = EnvSpec<KIND>::D;
-    __shared__ float mu_s[kEnvsPerBlock];
-    const CollectHeadArgs& g = c.head;
+                        float* rew; uint8_t* term; uint8_t* trunc; float* tobs; float* nobs;
+                        MonitorArgs mon; };   // MonitorWrapperEnv (dril_sac_monitor_enable): running sums, and row t of the collection's finished-episode block; all null = off
+// the actor's output layer for the kEnvsPerBlock envs of the block (A = 1), then this thread's env: false = the thread owns no env
+__device__ __forceinline__ bool sac_env_thread_mu(const CollectHeadArgs& g, float* mu_s, int* e_out, float* mu_out) {
     const int e = blockIdx.x * kEnvsPerBlock + threadIdx.x;          // 256 threads per kEnvsPerBlock envs: all four waves on the output layer, then one thread per env
-    if (!g.use_random && g.h2) { sac_mu_block(g, 0, blockIdx.x * kEnvsPerBlock, mu_s); __syncthreads(); }   // the actor's output layer (A = 1), same device function as the head kernel
-    if (threadIdx.x >= kEnvsPerBlock || e >= g.E) return;
+    if (!g.use_random && g.h2) { sac_mu_block(g, 0, blockIdx.x * kEnvsPerBlock, mu_s); __syncthreads(); }   // same device function as the head kernel
+    if (threadIdx.x >= kEnvsPerBlock || e >= g.E) return false;
     float mu_e = 0.f;
     if (!g.use_random) { if (g.h2) { mu_e = mu_s[threadIdx.x]; g.mu[e] = mu_e; } else mu_e = g.mu[e]; }
-    const EnvArrays env{c.state, c.step_count, c.episode, c.gstep, nullptr, nullptr};
+    *e_out = e; *mu_out = mu_e;
+    return true;
+}
+// predict_actions -> act! with auto-reset -> observe of env e by its thread: what the collection and the evaluation of a built-in Box env share.  *raw the action the
+// replay stores, to / no the terminal and the next observation (also written to c.tobs where truncated / c.nobs)
+template <int KIND>
+__device__ __forceinline__ StepOut sac_env_thread_step(const CollectEnvArgs& c, int e, float mu_e, float* raw, float* to, float* no) {
+    constexpr int D = EnvSpec<KIND>::D;
+    const CollectHeadArgs& g = c.head;
+    const EnvArrays env{c.state, c.step_count, c.episode, c.gstep, c.mon.cur_ret, c.mon.cur_len};
     EnvCursor<KIND> cur; cur.load(env, e);
     // ---- the action (sac_collect_head_kernel, A = 1) ----
     float r, ev;
     sac_collect_action(g, e, cur.gs, 0, mu_e, &r, &ev);
-    g.raw[e] = r; g.envact[e] = ev;
+    g.raw[e] = r; g.envact[e] = ev; *raw = r;
     // ---- act! with auto-reset (env_step_kernel) ----
     const StepOut so = env_advance<KIND>(cur, ev, 0, c.episode_len, false);
     c.rew[e] = so.rew; c.term[e] = so.term; c.trunc[e] = so.trunc;
-    float to[D];
+    if (c.mon.cur_ret) c.mon.flags_out[e] = so.flags();
     env_obs<KIND>(cur.st, to);                                                          // terminal_observation (stored where truncated)
     if (so.trunc) {
 #pragma unroll
         for (int i = 0; i < D; ++i) c.tobs[(size_t)e * D + i] = to[i];
     }
-    env_end_episode<KIND>(cur, c.seed0 + (uint64_t)e, so, nullptr, nullptr);
+    env_end_episode<KIND>(cur, c.seed0 + (uint64_t)e, so, c.mon.cur_ret ? c.mon.ep_ret + e : nullptr, c.mon.ep_len + e);
     cur.store(env, e);
     // ---- observe (env_observe_kernel) ----
-    float no[D];
     env_obs<KIND>(cur.st, no);
 #pragma unroll
     for (int i = 0; i < D; ++i) c.nobs[(size_t)e * D + i] = no[i];
+    return so;
+}
+template <int KIND>
+__global__ __launch_bounds__(256) void sac_collect_env_kernel(CollectEnvArgs c) {
+    constexpr int D = EnvSpec<KIND>::D;
+    __shared__ float mu_s[kEnvsPerBlock];
+    int e; float mu_e;
+    if (!sac_env_thread_mu(c.head, mu_s, &e, &mu_e)) return;
+    float r, to[D], no[D];
+    const StepOut so = sac_env_thread_step<KIND>(c, e, mu_e, &r, to, no);
     // ---- push! (sac_push_kernel) ----
     sac_push_row(c.push, e, D, 1, to, no, &r, so.rew, so.term, so.trunc);
     phase_stamp(c.push.stamp);                                               // thread 0 of the last workgroup owns a live env (grid = ceil(E / kEnvsPerBlock)): the end of its work ~ the end of the phase
+}
+
+// ---- evaluate_agent on the device (evaluation.jl:90-124; the event list: dril_sac_eval.h) ----------------------------------------------------------
+// The episode accounting of env e after its step, by the env's own thread: current_rewards[e] += reward in float32 and in step order, as the reference's host loop
+// adds them; where the episode ended, one event through the list's counter (slots past the capacity are only counted) and the two sums restart.
+struct EvalAcctArgs { int E; int32_t step; float* cur_ret; int32_t* cur_len; unsigned int* counter; SacEvalEvent* events; unsigned int cap; };
+__device__ __forceinline__ void sac_eval_account(const EvalAcctArgs& a, int e, float rew, bool done) {
+    float r = a.cur_ret[e] + rew; int32_t l = a.cur_len[e] + 1;
+    if (done) {
+        const unsigned int i = atomicAdd(a.counter, 1u);
+        if (i < a.cap) a.events[i] = SacEvalEvent{a.step, e, r, l};
+        r = 0.f; l = 0;
+    }
+    a.cur_ret[e] = r; a.cur_len[e] = l;
+}
+// built-in Box envs: the twin of sac_collect_env_kernel with the accounting where that one has the push (the monitor pointers of `env` are null: an evaluation does
+// not feed the training env's MonitorWrapperEnv)
+struct EvalEnvArgs { CollectEnvArgs env; EvalAcctArgs acct; };
+template <int KIND>
+__global__ __launch_bounds__(256) void sac_eval_env_kernel(EvalEnvArgs c) {
+    constexpr int D = EnvSpec<KIND>::D;
+    __shared__ float mu_s[kEnvsPerBlock];
+    int e; float mu_e;
+    if (!sac_env_thread_mu(c.env.head, mu_s, &e, &mu_e)) return;
+    float r, to[D], no[D];
+    const StepOut so = sac_env_thread_step<KIND>(c.env, e, mu_e, &r, to, no);
+    sac_eval_account(c.acct, e, so.rew, so.done());
+}
+// plug-ins: after the plug-in's step kernel, over its per-step arrays.  One thread per env, flat index.
+__global__ __launch_bounds__(256) void sac_eval_account_kernel(EvalAcctArgs a, const float* __restrict__ rew, const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.E) return;
+    sac_eval_account(a, e, rew[e], (term[e] | trunc[e]) != 0);
+}
+
+// ---- MonitorWrapperEnv's window (monitorWrapperEnv.jl:1-7,53-58) after a collection, in ONE launch ---------------------------------------------------
+// flags / ep_ret / ep_len: the collection's [T][E] block (a row per env step; ep_* valid where the flag is set), whose flat order IS the (step, env) order in which
+// the reference pushes finished episodes.  One workgroup: count the events, then an ordered scan that writes the last min(total, W) of them behind the ring's head.
+// The two-kernel form of dril_kernels.hip (monitor_count_kernel + monitor_collect_kernel) spreads the count over T workgroups, which pays for a PPO rollout of
+// hundreds of steps; a SAC collection is train_freq steps, usually ONE, and a second dependent launch would add a launch gap to every env step — so the count is
+// the first pass of the same workgroup here, and a collection in which no episode ended (nearly all of them) leaves after it.
+constexpr int kMonBlock = 1024;
+__global__ __launch_bounds__(kMonBlock) void sac_monitor_window_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ ep_ret, const int32_t* __restrict__ ep_len,
+                                                                       int n, int W, float* ring_ret, int32_t* ring_len, int* meta) {
+    __shared__ int wsum[kMonBlock / 64], s_total, s_base;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int c = 0;
+    for (int i = threadIdx.x; i < n; i += kMonBlock) c += flags[i] != 0;
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+    if (lane == 0) wsum[wv] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < kMonBlock / 64; ++w) t += wsum[w]; s_total = t; s_base = 0; }
+    __syncthreads();
+    const int total = s_total;
+    if (total == 0) return;
+    const int skip = total > W ? total - W : 0, head0 = meta[1];
+    for (int i0 = 0; i0 < n; i0 += kMonBlock) {
+        const int i = i0 + threadIdx.x;
+        const int f = (i < n && flags[i] != 0) ? 1 : 0;
+        int incl = f;                                                                // inclusive scan within the wave, then across the waves
+        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+        __syncthreads();                                                             // (wsum of the previous pass has been read by everyone)
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        int off = 0, chunk = 0;
+        for (int w = 0; w < kMonBlock / 64; ++w) { if (w < wv) off += wsum[w]; chunk += wsum[w]; }
+        const int gi = s_base + off + incl - f;                                      // this event's index among the collection's events
+        if (f && gi >= skip) { const int pos = (head0 + gi - skip) % W; ring_ret[pos] = ep_ret[i]; ring_len[pos] = ep_len[i]; }
+        __syncthreads();
+        if (threadIdx.x == 0) s_base += chunk;
+    }
+    if (threadIdx.x == 0) {
+        const int pushed = total - skip;
+        meta[1] = (head0 + pushed) % W;
+        const int cnt = meta[0] + pushed; meta[0] = cnt > W ? W : cnt;
+    }
 }
 // host-batch helpers
 __global__ void sac_squash_eval_kernel(int B, int A, const float* mu, const float* log_std, const float* noise, int deterministic, const float* low, const float* high,
@@ -1159,6 +1254,13 @@ struct dril_sac_handle {
     float *dz2 = nullptr, *dz1 = nullptr, *dxq = nullptr, *dmu = nullptr;            // [2][nq][H], [2][nq][D+A], [B][A]
     float *b_rew = nullptr, *b_ne = nullptr, *b_nn = nullptr, *b_np = nullptr, *b_nlp = nullptr, *a_pi = nullptr, *g_pi = nullptr, *lp_pi = nullptr; uint8_t* b_term = nullptr;
     int nq = 0;
+    // MonitorWrapperEnv (dril_sac_monitor_enable; mon_window == 0: off, every pointer null): running sums per env, the ring of the last mon_window finished episodes
+    // with meta = {count, head}, and the finished-episode block [mon_rows_cap][E] of the collection in flight (mon_row: its next row)
+    int mon_window = 0, mon_rows_cap = 0, mon_row = 0; float *mon_cur_ret = nullptr, *mon_ring_ret = nullptr, *mon_ep_ret = nullptr; int32_t *mon_cur_len = nullptr, *mon_ring_len = nullptr, *mon_ep_len = nullptr;
+    int* mon_meta = nullptr; uint8_t* mon_flags = nullptr;
+    // evaluate_agent (dril_sac_evaluate_agent): the env-side snapshot, the per-env running sums, the event list and its counter (pinned host word for the poll)
+    int eval_poll = 0; float *ev_state = nullptr, *ev_obs = nullptr, *ev_mon_ret = nullptr, *ev_cur_ret = nullptr; int32_t *ev_sc = nullptr, *ev_mon_len = nullptr, *ev_cur_len = nullptr; uint32_t *ev_ep = nullptr, *ev_gs = nullptr;
+    unsigned int *ev_counter = nullptr, *ev_counter_host = nullptr; SacEvalEvent* ev_events = nullptr; long long ev_events_cap = 0;
     // injected inputs (tests)
     float* collect_noise = nullptr; size_t collect_noise_count = 0;
     int inj_updates = 0; long long* inj_idx = nullptr; float *inj_ne = nullptr, *inj_nn = nullptr, *inj_np = nullptr;
@@ -1365,7 +1467,7 @@ int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long*
     return DRIL_OK;
 }
 
-// the argument block of a plug-in's kernels: SAC has no MonitorWrapperEnv and no DiscreteAdapter (monitor pointers null, action_start 0)
+// the argument block of a plug-in's kernels: SAC has no DiscreteAdapter (action_start 0); the monitor pointers are filled by the collection step alone (monitor_row)
 DrilEnvPluginArgs module_args(dril_sac_handle* h) {
     DrilEnvPluginArgs a{};
     a.E = h->cfg.n_envs; a.episode_len = h->cfg.episode_len; a.seed0 = h->env_seed0;
@@ -1390,6 +1492,35 @@ void ring_advance(dril_sac_handle* h) {                                         
     const long long over = h->size + h->cfg.n_envs - h->cap;
     if (over > 0) { h->head = (h->head + over) % h->cap; h->size = h->cap; } else h->size += h->cfg.n_envs;
 }
+// MonitorWrapperEnv in a collection: the running sums and row h->mon_row of the collection's finished-episode block for the step being enqueued (all null: off)
+MonitorArgs monitor_row(dril_sac_handle* h) {
+    MonitorArgs m{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (!h->mon_window) return m;
+    const size_t o = (size_t)h->mon_row * h->cfg.n_envs;
+    m.cur_ret = h->mon_cur_ret; m.cur_len = h->mon_cur_len; m.ep_ret = h->mon_ep_ret + o; m.ep_len = h->mon_ep_len + o; m.flags_out = h->mon_flags + o;
+    return m;
+}
+// before a collection of n_steps: its block has n_steps rows (grown on demand: the start phase is the one long collection of a run)
+int monitor_begin(dril_sac_handle* h, int n_steps) {
+    if (!h->mon_window) return DRIL_OK;
+    h->mon_row = 0;
+    if (n_steps <= h->mon_rows_cap) return DRIL_OK;
+    SDO(ssync(h));                                                                                 // (the previous collection's window launch reads the old rows)
+    if (h->mon_ep_ret) hipFree(h->mon_ep_ret); if (h->mon_ep_len) hipFree(h->mon_ep_len); if (h->mon_flags) hipFree(h->mon_flags);
+    h->mon_ep_ret = nullptr; h->mon_ep_len = nullptr; h->mon_flags = nullptr; h->mon_rows_cap = 0;
+    const size_t n = (size_t)n_steps * h->cfg.n_envs;
+    SHIP(h, smalloc(&h->mon_ep_ret, n)); SHIP(h, smalloc(&h->mon_ep_len, n)); SHIP(h, smalloc(&h->mon_flags, n)); h->mon_rows_cap = n_steps;
+    return DRIL_OK;
+}
+// after its last step: the finished episodes of the whole collection into the window, one launch (sac_monitor_window_kernel)
+int monitor_end(dril_sac_handle* h) {
+    if (!h->mon_window || h->mon_row == 0) return DRIL_OK;
+    hipLaunchKernelGGL(sac_monitor_window_kernel, dim3(1), dim3(kMonBlock), 0, h->stream, h->mon_flags, h->mon_ep_ret, h->mon_ep_len, h->mon_row * h->cfg.n_envs, h->mon_window,
+                       h->mon_ring_ret, h->mon_ring_len, h->mon_meta);
+    SHIP(h, hipGetLastError());
+    h->mon_row = 0;
+    return DRIL_OK;
+}
 // head -> act! + observe -> push! of one collection step over a device env plug-in (the actor's hidden layers are already enqueued).  `first` / `last`: the step's
 // place in its collection — the fused form pushes step t's rows in the launch that computes the head of step t + 1, the last step's rows in a launch of their own,
 // so the ring is complete when the collection returns.
@@ -1398,6 +1529,10 @@ int collect_step_module(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned 
     DrilEnvPluginArgs st = module_args(h);
     // `actions` is the env-space action of TanhScaleAdapter / rand(action_space), inside the Box by construction: the wrapper's ClampAdapter is a no-op on it
     st.actions = h->e_envact; st.rewards = h->e_rew; st.terminated = h->e_term; st.truncated = h->e_trunc; st.terminal_obs = h->e_tobs; st.obs = h->obs_nxt;
+    if (h->mon_window) {                                                                             // MonitorWrapperEnv: the wrapper of dril_env_plugin.h keeps the sums and writes this step's row
+        const MonitorArgs mon = monitor_row(h); h->mon_row += 1;
+        st.mon_cur_ret = mon.cur_ret; st.mon_cur_len = mon.cur_len; st.ep_ret = mon.ep_ret; st.ep_len = mon.ep_len; st.flags = mon.flags_out;
+    }
     if (!h->fused_head_push) {                                                                       // DRIL_SAC_NO_FUSED_HEAD_PUSH=1: three launches per step
         hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
         SHIP(h, env_module_launch(h->mod_step, st, h->stream));
@@ -1419,11 +1554,12 @@ int collect_step_module(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned 
     SHIP(h, hipGetLastError());
     return DRIL_OK;
 }
-// one step of collect_trajectories (off_policy_collection.jl:42-93) for all envs
-int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, unsigned long long* stamp = nullptr, bool first = true, bool last = true) {
+// predict_actions_raw (off_policy_collection.jl:55, evaluation.jl:94) up to the output layer, for the envs' current observations: the hidden layers as contractions
+// (the first one inside the second's staging when the input is narrow); the output layer inside the head / env kernel that follows (fused_fwd;
+// DRIL_SAC_NO_FUSED_FWD=1: three contractions and mu through memory, the round 1 - 3 form).  Returns the head's argument block; a collection step and an
+// evaluation step enqueue the same launches here.
+int actor_hidden(dril_sac_handle* h, int use_random, const float* inj_noise, CollectHeadArgs* out) {
     const int E = h->cfg.n_envs, D = h->D, A = h->A;
-    // predict_actions_raw :55 — the hidden layers as contractions (the first one inside the second's staging when the input is narrow); the output layer inside the head /
-    // env kernel that follows (fused_fwd; DRIL_SAC_NO_FUSED_FWD=1: three contractions and mu through memory, the round 1 - 3 form)
     const bool mu_in_head = h->fused_fwd && !use_random && h->H2 % 4 == 0;
     // the hidden layers: for a narrow observation and tile-sized widths the f16-piece form (sac_collect_l1_kernel cuts h1 and, when the actor changed, W2 into f16 planes;
     // sac_collect_l2_kernel contracts them; out-of-range values fall back to f32 MFMAs inside the kernel), else the generic contractions
@@ -1440,14 +1576,25 @@ int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, uns
         hipLaunchKernelGGL(sac_collect_l2_kernel, dim3((E + kL2TN - 1) / kL2TN, h->H2 / kL2TM), dim3(256), kL2LdsBytes, h->stream, l2);
         SHIP(h, hipGetLastError());
     } else if (!use_random) SDO(net_forward(h, h->params, h->actor, 0, D, A, h->obs_cur, D, 0, E, actor_bufs(h), 1, 1, mu_in_head));
-    CollectHeadArgs ca{E, A, use_random, h->mu, h->params + h->log_std_off, inj_noise, h->gstep, h->env_seed0, h->act_bounds, h->act_bounds + kMaxA, h->e_raw, h->e_envact,
-                       mu_in_head ? h->ah2 : nullptr, h->params + h->actor.w3, h->params + h->actor.b3, h->H2};
+    *out = CollectHeadArgs{E, A, use_random, h->mu, h->params + h->log_std_off, inj_noise, h->gstep, h->env_seed0, h->act_bounds, h->act_bounds + kMaxA, h->e_raw, h->e_envact,
+                           mu_in_head ? h->ah2 : nullptr, h->params + h->actor.w3, h->params + h->actor.b3, h->H2, 0};
+    return DRIL_OK;
+}
+// the env kernel's argument block of a built-in Box env (A = 1): head, push (collection only), the env arrays and the per-step results
+CollectEnvArgs env_kernel_args(dril_sac_handle* h, const CollectHeadArgs& ca, const PushArgs& pa, const MonitorArgs& mon) {
+    return CollectEnvArgs{ca, pa, h->env_seed0, h->cfg.episode_len, h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt, mon};
+}
+// one step of collect_trajectories (off_policy_collection.jl:42-93) for all envs
+int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, unsigned long long* stamp = nullptr, bool first = true, bool last = true) {
+    const int E = h->cfg.n_envs, D = h->D, A = h->A;
+    CollectHeadArgs ca; SDO(actor_hidden(h, use_random, inj_noise, &ca));
     if (h->module) return collect_step_module(h, ca, stamp, first, last);
+    const MonitorArgs mon = monitor_row(h); if (h->mon_window) h->mon_row += 1;                                   // MonitorWrapperEnv: this step's row of the collection's block (null: off)
     if (A == 1 && !h->external && h->fused_collect) {                                                            // every device Box env: head + act! + observe + push! in one launch
         const long long tail1 = (h->head + h->size) % h->cap;
         PushArgs pa1{E, D, A, h->cap, tail1, h->obs_cur, h->e_raw, h->e_rew, h->e_tobs, h->obs_nxt, h->e_term, h->e_trunc,
                      h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, stamp};
-        CollectEnvArgs ce{ca, pa1, h->env_seed0, h->cfg.episode_len, h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt};
+        const CollectEnvArgs ce = env_kernel_args(h, ca, pa1, mon);
         const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
         if (h->cfg.env_kind == DRIL_ENV_PENDULUM) hipLaunchKernelGGL(sac_collect_env_kernel<1>, grid, block, 0, h->stream, ce);
         else if (h->cfg.env_kind == DRIL_ENV_PENDULUM_SCALED) hipLaunchKernelGGL(sac_collect_env_kernel<2>, grid, block, 0, h->stream, ce);
@@ -1460,7 +1607,6 @@ int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, uns
         return DRIL_OK;
     }
     hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
-    MonitorArgs mon{nullptr, nullptr, nullptr, nullptr, nullptr};
     SHIP(h, launch_env_step(h->cfg.env_kind, E, h->env_seed0, h->cfg.episode_len, 0, 0, h->e_envact, h->state, h->step_count, h->episode, h->gstep,
                             h->e_rew, h->e_term, h->e_trunc, h->e_tobs, mon, h->stream));                                     // act! :60
     SHIP(h, launch_env_observe(h->cfg.env_kind, E, h->state, h->obs_nxt, h->stream));                                         // observe :61
@@ -1478,11 +1624,12 @@ int collect(dril_sac_handle* h, int n_steps, int use_random, double* fps) {
     if (n_steps <= 0) return sfail(h, DRIL_ERR_INVALID_ARG, "n_steps must be positive");
     if (h->collect_noise && h->collect_noise_count != (size_t)n_steps * h->cfg.n_envs * h->A)
         return sfail(h, DRIL_ERR_INVALID_ARG, "injected collect noise must hold n_steps * n_envs * action_dim values");
-    SDO(ensure_obs(h));
+    SDO(ensure_obs(h)); SDO(monitor_begin(h, n_steps));
     const auto t0 = std::chrono::steady_clock::now();
     if (h->cfg.profile_events) hipEventRecord(h->ev_a, h->stream);
     for (int t = 0; t < n_steps; ++t)
         SDO(collect_step(h, use_random, h->collect_noise ? h->collect_noise + (size_t)t * h->cfg.n_envs * h->A : nullptr, nullptr, t == 0, t == n_steps - 1));
+    SDO(monitor_end(h));                                                                          // MonitorWrapperEnv: this collection's finished episodes into the window
     if (h->cfg.profile_events) hipEventRecord(h->ev_b, h->stream);
     SDO(ssync(h));
     if (h->cfg.profile_events) { float ms = 0; if (hipEventElapsedTime(&ms, h->ev_a, h->ev_b) == hipSuccess) { h->collect_ms += ms; h->collect_steps += n_steps; } }
@@ -1541,7 +1688,7 @@ int run_updates(dril_sac_handle* h, int n_updates, bool injected, dril_sac_stats
 // fps of an iteration = env steps / HIP-event time of its collection (the reference times the same span on the host clock, off_policy_collection.jl:126-128).
 int run_iterations(dril_sac_handle* h, int count, int tf, int n_upd, dril_sac_stats* stats, int64_t stats_room, double* fps, int64_t fps_room) {
     if (count <= 0) return DRIL_OK;
-    SDO(ensure_obs(h));
+    SDO(ensure_obs(h)); SDO(monitor_begin(h, tf));
     if (n_upd > 0) { if (h->size <= 0 && tf <= 0) return sfail(h, DRIL_ERR_NOT_INITIALISED, "the replay buffer is empty"); SDO(ensure_stats(h, count * n_upd)); }
     const bool timed = h->cfg.profile_events || fps;
     const int n_st = 1 + 2 * count;                                                        // [loop start | per iteration: collection end, update end] (phase_stamp)
@@ -1552,6 +1699,7 @@ int run_iterations(dril_sac_handle* h, int count, int tf, int n_upd, dril_sac_st
     }
     for (int j = 0; j < count; ++j) {
         for (int t = 0; t < tf; ++t) SDO(collect_step(h, 0, nullptr, timed && t == tf - 1 ? h->it_stamps + 1 + 2 * j : nullptr, t == 0, t == tf - 1));
+        SDO(monitor_end(h));                                                               // (the next iteration's steps reuse the rows: stream order keeps them apart)
         for (int k = 0; k < n_upd; ++k) SDO(sac_one_update(h, -1, h->stats_out + ((size_t)j * n_upd + k) * 8, timed && k == n_upd - 1 ? h->it_stamps + 2 + 2 * j : nullptr));
     }
     SDO(ssync(h));
@@ -1631,6 +1779,10 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
     for (hipEvent_t e : h->it_events) hipEventDestroy(e);
     if (h->it_stamps) hipFree(h->it_stamps);
     if (h->col_h1p) hipFree(h->col_h1p); if (h->col_w2p) hipFree(h->col_w2p); if (h->col_flags) hipFree(h->col_flags);
+    void* mon_eval[] = {h->mon_cur_ret, h->mon_cur_len, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->mon_ep_ret, h->mon_ep_len, h->mon_flags,
+                        h->ev_state, h->ev_obs, h->ev_mon_ret, h->ev_cur_ret, h->ev_sc, h->ev_mon_len, h->ev_cur_len, h->ev_ep, h->ev_gs, h->ev_counter, h->ev_events};
+    for (void* p : mon_eval) if (p) hipFree(p);
+    if (h->ev_counter_host) hipHostFree(h->ev_counter_host);
     if (h->stream) hipStreamDestroy(h->stream);
     if (h->env_module) (void)hipModuleUnload(h->env_module);
     delete h;
@@ -1728,6 +1880,11 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     CHK(smalloc(&h->counter, 1));
     CHK(smalloc(&h->head_partials, (size_t)(2 * kMaxA + 8) * ((B + kHeadSamplesPerBlock - 1) / kHeadSamplesPerBlock + 1))); CHK(smalloc(&h->head_counter, kMaxA + 1));   // doubles: [critic 2 | actor 2 | log_std kMaxA | entropy 2] x blocks
     h->fused_heads = std::getenv("DRIL_SAC_NO_FUSED_HEADS") == nullptr; h->fused_collect = std::getenv("DRIL_SAC_NO_FUSED_COLLECT") == nullptr; h->fused_fwd = std::getenv("DRIL_SAC_NO_FUSED_FWD") == nullptr; h->f16_fwd = std::getenv("DRIL_SAC_NO_F16_FWD") == nullptr; h->trace_enqueue = false;   // latched here: no getenv on the update path
+    // evaluate_agent: env steps enqueued between two looks of the host at the event counter.  A look is one 4-byte copy and a stream drain (measured: 9 - 10 us per look on
+    // built-in Pendulum, half an env step; docs/sac.md); 32 steps per look put it under half a microsecond per step, and at most 31 steps (under a millisecond) run
+    // past the step that completes the list.  No more than the time limit, after which every env has finished an episode.  DRIL_SAC_EVAL_POLL=<k> overrides; 1 is the step-by-step definition.
+    h->eval_poll = std::max(1, std::min(h->cfg.episode_len, 32));
+    if (const char* ep = std::getenv("DRIL_SAC_EVAL_POLL")) { const long k = std::strtol(ep, nullptr, 10); if (k >= 1) h->eval_poll = (int)std::min<long>(k, 1 << 20); }
     CHK(smalloc(&h->state, (size_t)E * S)); CHK(smalloc(&h->step_count, E)); CHK(smalloc(&h->episode, E)); CHK(smalloc(&h->gstep, E)); CHK(smalloc(&h->disc_returns, E));
     CHK(smalloc(&h->obs_cur, (size_t)E * D)); CHK(smalloc(&h->obs_nxt, (size_t)E * D)); CHK(smalloc(&h->e_rew, E)); CHK(smalloc(&h->e_tobs, (size_t)E * D));
     CHK(smalloc(&h->e_raw, (size_t)E * A)); CHK(smalloc(&h->e_envact, (size_t)E * A)); CHK(smalloc(&h->e_term, E)); CHK(smalloc(&h->e_trunc, E));
@@ -1802,6 +1959,7 @@ DRIL_EXPORT int32_t dril_sac_env_reset(dril_sac_handle* h, uint64_t seed) {
     h->env_seed0 = seed;
     if (h->module) SHIP(h, env_module_launch(h->mod_reset, module_args(h), h->stream));
     else SHIP(h, launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
+    if (h->mon_window) { SHIP(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)h->cfg.n_envs * 4, h->stream)); SHIP(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)h->cfg.n_envs * 4, h->stream)); }   // MonitorWrapperEnv.reset!: the running sums restart, the window stays (monitorWrapperEnv.jl:36-42)
     h->env_ready = true; h->obs_valid = false;
     return ssync(h);
 }
@@ -2035,3 +2193,149 @@ DRIL_EXPORT int32_t dril_sac_profile_get(dril_sac_handle* h, double* collect_ms,
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_profile_reset(dril_sac_handle* h) { SNEED(h); h->collect_ms = h->update_ms = 0; h->collect_steps = h->updates = 0; return DRIL_OK; }
+
+// ---- MonitorWrapperEnv around the handle's device envs (monitorWrapperEnv.jl) ----------------------------------------------------------------------------
+namespace {
+void monitor_free(dril_sac_handle* h) {
+    void* ptrs[] = {h->mon_cur_ret, h->mon_cur_len, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->mon_ep_ret, h->mon_ep_len, h->mon_flags};
+    for (void* p : ptrs) if (p) hipFree(p);
+    h->mon_cur_ret = h->mon_ring_ret = h->mon_ep_ret = nullptr; h->mon_cur_len = h->mon_ring_len = h->mon_ep_len = nullptr; h->mon_meta = nullptr; h->mon_flags = nullptr;
+    h->mon_window = 0; h->mon_rows_cap = 0; h->mon_row = 0;
+}
+}  // namespace
+DRIL_EXPORT int32_t dril_sac_monitor_enable(dril_sac_handle* h, int32_t window) {
+    SNEED(h);
+    if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_monitor_enable: the envs of DRIL_ENV_EXTERNAL live on the host: MonitorWrapperEnv wraps them there");
+    if (window < 0) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_monitor_enable: window must be >= 1 (MonitorWrapperEnv's stats_window), or 0 to switch the monitor off");
+    if (window == h->mon_window) return DRIL_OK;                                      // the same wrapper again: its window and running sums stay
+    SDO(ssync(h));
+    monitor_free(h);
+    if (window == 0) return DRIL_OK;
+    const size_t E = (size_t)h->cfg.n_envs, rows = (size_t)std::max(1, h->cfg.train_freq);
+    hipError_t e = smalloc(&h->mon_cur_ret, E);                                       // (smalloc zeroes: fresh sums, an empty window)
+    if (e == hipSuccess) e = smalloc(&h->mon_cur_len, E);
+    if (e == hipSuccess) e = smalloc(&h->mon_ring_ret, (size_t)window);
+    if (e == hipSuccess) e = smalloc(&h->mon_ring_len, (size_t)window);
+    if (e == hipSuccess) e = smalloc(&h->mon_meta, 2);
+    if (e == hipSuccess) e = smalloc(&h->mon_ep_ret, rows * E);
+    if (e == hipSuccess) e = smalloc(&h->mon_ep_len, rows * E);
+    if (e == hipSuccess) e = smalloc(&h->mon_flags, rows * E);
+    if (e != hipSuccess) { monitor_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_monitor_enable: ") + hipGetErrorString(e)); }
+    h->mon_window = window; h->mon_rows_cap = (int)rows;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_monitor_get_stats(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
+    SNEED(h);
+    if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_monitor_get_stats: the envs of DRIL_ENV_EXTERNAL live on the host: MonitorWrapperEnv wraps them there");
+    if (!h->mon_window) return sfail(h, DRIL_ERR_NOT_INITIALISED, "MonitorWrapperEnv is off (dril_sac_monitor_enable has not been called with a window >= 1)");
+    const int W = h->mon_window;
+    std::vector<float> r(W); std::vector<int32_t> l(W); int meta[2] = {0, 0};
+    SHIP(h, hipMemcpyAsync(r.data(), h->mon_ring_ret, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
+    SHIP(h, hipMemcpyAsync(l.data(), h->mon_ring_len, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
+    SHIP(h, hipMemcpyAsync(meta, h->mon_meta, 8, hipMemcpyDeviceToHost, h->stream));
+    SDO(ssync(h));
+    double sr = 0, sl = 0;
+    for (int i = 0; i < meta[0]; ++i) { sr += r[i]; sl += l[i]; }
+    if (n_episodes) *n_episodes = meta[0];
+    if (meta[0] > 0) {                                                                // log_stats: mean over the CircularBuffer, monitorWrapperEnv.jl:64-70; nothing to log for an empty one
+        if (ep_rew_mean) *ep_rew_mean = (float)(sr / meta[0]);
+        if (ep_len_mean) *ep_len_mean = (float)(sl / meta[0]);
+    }
+    return DRIL_OK;
+}
+
+// ---- evaluate_agent (src/evaluation.jl:54-143) with the handle's actor on the handle's envs -------------------------------------------------------------------
+namespace {
+template <typename T> int ensure_buf(dril_sac_handle* h, T** p, size_t n) { if (!*p) SHIP(h, smalloc(p, n)); return DRIL_OK; }
+// the buffers of an evaluation: allocated by the first one, kept; the event list grows with n_eval
+int eval_buffers(dril_sac_handle* h, long long cap) {
+    const size_t E = (size_t)h->cfg.n_envs;
+    SDO(ensure_buf(h, &h->ev_state, E * h->S)); SDO(ensure_buf(h, &h->ev_obs, E * h->D)); SDO(ensure_buf(h, &h->ev_sc, E)); SDO(ensure_buf(h, &h->ev_ep, E)); SDO(ensure_buf(h, &h->ev_gs, E));
+    SDO(ensure_buf(h, &h->ev_mon_ret, E)); SDO(ensure_buf(h, &h->ev_mon_len, E)); SDO(ensure_buf(h, &h->ev_cur_ret, E)); SDO(ensure_buf(h, &h->ev_cur_len, E)); SDO(ensure_buf(h, &h->ev_counter, 1));
+    if (!h->ev_counter_host) SHIP(h, hipHostMalloc((void**)&h->ev_counter_host, sizeof(unsigned int), hipHostMallocDefault));
+    if (cap > h->ev_events_cap) {
+        if (h->ev_events) hipFree(h->ev_events);
+        h->ev_events = nullptr; h->ev_events_cap = 0;
+        SHIP(h, smalloc(&h->ev_events, (size_t)cap)); h->ev_events_cap = cap;
+    }
+    return DRIL_OK;
+}
+// the env side of the handle, out (save) or back in (restore): simulator state, counters, the noise stream's position, the current observation, the monitor's sums
+int eval_snapshot(dril_sac_handle* h, bool save) {
+    const size_t E = (size_t)h->cfg.n_envs;
+    auto cp = [&](void* snap, void* live, size_t bytes) { return save ? hipMemcpyAsync(snap, live, bytes, hipMemcpyDeviceToDevice, h->stream) : hipMemcpyAsync(live, snap, bytes, hipMemcpyDeviceToDevice, h->stream); };
+    SHIP(h, cp(h->ev_state, h->state, E * h->S * 4)); SHIP(h, cp(h->ev_sc, h->step_count, E * 4)); SHIP(h, cp(h->ev_ep, h->episode, E * 4)); SHIP(h, cp(h->ev_gs, h->gstep, E * 4));
+    SHIP(h, cp(h->ev_obs, h->obs_cur, E * h->D * 4));                                 // (restore: into whichever of the two observation buffers is current now)
+    if (h->mon_window) { SHIP(h, cp(h->ev_mon_ret, h->mon_cur_ret, E * 4)); SHIP(h, cp(h->ev_mon_len, h->mon_cur_len, E * 4)); }
+    return DRIL_OK;
+}
+// one env step of the evaluation, enqueued: the collection step's hidden layers, then head + act! + observe + accounting
+int eval_step(dril_sac_handle* h, int deterministic, int32_t step, unsigned int cap) {
+    const int E = h->cfg.n_envs;
+    CollectHeadArgs ca; SDO(actor_hidden(h, 0, nullptr, &ca));
+    ca.deterministic = deterministic ? 1 : 0;
+    const EvalAcctArgs acct{E, step, h->ev_cur_ret, h->ev_cur_len, h->ev_counter, h->ev_events, cap};
+    if (h->module) {
+        hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
+        DrilEnvPluginArgs st = module_args(h);                                         // (monitor pointers null: evaluation episodes do not feed the window)
+        st.actions = h->e_envact; st.rewards = h->e_rew; st.terminated = h->e_term; st.truncated = h->e_trunc; st.terminal_obs = h->e_tobs; st.obs = h->obs_nxt;
+        SHIP(h, env_module_launch(h->mod_step, st, h->stream));
+        hipLaunchKernelGGL(sac_eval_account_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, h->e_rew, h->e_term, h->e_trunc);
+    } else {                                                                           // every built-in Box env has A = 1
+        const EvalEnvArgs ee{env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr}), acct};
+        const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
+        if (h->cfg.env_kind == DRIL_ENV_PENDULUM) hipLaunchKernelGGL(sac_eval_env_kernel<1>, grid, block, 0, h->stream, ee);
+        else if (h->cfg.env_kind == DRIL_ENV_PENDULUM_SCALED) hipLaunchKernelGGL(sac_eval_env_kernel<2>, grid, block, 0, h->stream, ee);
+        else if (h->cfg.env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) hipLaunchKernelGGL(sac_eval_env_kernel<7>, grid, block, 0, h->stream, ee);
+        else hipLaunchKernelGGL(sac_eval_env_kernel<4>, grid, block, 0, h->stream, ee);
+    }
+    SHIP(h, hipGetLastError());
+    std::swap(h->obs_cur, h->obs_nxt);
+    return DRIL_OK;
+}
+// reset!(env) .. the loop of evaluation.jl:90-122 on the device; the host looks at the event counter once per eval_poll steps
+int eval_run(dril_sac_handle* h, int n_eval, int deterministic, uint64_t seed, std::vector<SacEvalEvent>& events) {
+    const int E = h->cfg.n_envs;
+    const long long cap = sac_eval_event_capacity(n_eval, E);
+    h->env_seed0 = seed;                                                               // env e seeded seed + e; its action noise is that env's stream from step 0
+    if (h->module) SHIP(h, env_module_launch(h->mod_reset, module_args(h), h->stream));
+    else SHIP(h, launch_env_reset(h->cfg.env_kind, E, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
+    h->env_ready = true; h->obs_valid = false;
+    SDO(ensure_obs(h));
+    SHIP(h, hipMemsetAsync(h->ev_cur_ret, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_cur_len, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
+    // every env finishes an episode within the time limit, so n_eval of them take at most ceil(n_eval / E) time limits; one more, and the steps enqueued past a look
+    const long long max_steps = ((long long)(n_eval + E - 1) / E + 1) * (long long)h->cfg.episode_len + h->eval_poll;
+    long long steps = 0; unsigned int seen = 0;
+    while (seen < (unsigned int)n_eval) {
+        if (steps >= max_steps) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_evaluate_agent: no episode finishes");
+        for (int k = 0; k < h->eval_poll; ++k) SDO(eval_step(h, deterministic, (int32_t)(++steps), (unsigned int)cap));
+        SHIP(h, hipMemcpyAsync(h->ev_counter_host, h->ev_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        SDO(ssync(h));
+        seen = *h->ev_counter_host;
+    }
+    events.resize((size_t)std::min<long long>(seen, cap));
+    SHIP(h, hipMemcpy(events.data(), h->ev_events, events.size() * sizeof(SacEvalEvent), hipMemcpyDeviceToHost));
+    return DRIL_OK;
+}
+}  // namespace
+DRIL_EXPORT int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval, int32_t deterministic, uint64_t seed, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) {
+    SNEED(h);
+    if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_evaluate_agent: the envs of DRIL_ENV_EXTERNAL live on the host: evaluate there with dril_sac_predict_actions");
+    if (n_eval < 1 || !out) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
+    SDO(eval_buffers(h, sac_eval_event_capacity(n_eval, h->cfg.n_envs)));
+    // evaluation runs on the handle's own envs: what a collection would continue from is set aside here and put back below, on every path
+    const uint64_t seed0 = h->env_seed0; const bool ready = h->env_ready, obs_valid = h->obs_valid;
+    SDO(eval_snapshot(h, true));
+    std::vector<SacEvalEvent> events;
+    const int rc = eval_run(h, n_eval, deterministic, seed, events);
+    const std::string msg = h->err;
+    h->env_seed0 = seed0; h->env_ready = ready; h->obs_valid = obs_valid;
+    int rr = eval_snapshot(h, false); if (rr == DRIL_OK) rr = ssync(h);
+    if (rc != DRIL_OK) { h->err = msg; return rc; }
+    if (rr != DRIL_OK) return rr;
+    SacEvalSummary sum{};
+    sac_eval_reduce(events.data(), (int64_t)events.size(), n_eval, &sum, ep_rewards, ep_lengths);
+    out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
+    out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
+    return DRIL_OK;
+}

@@ -80,6 +80,66 @@ function sac_config(env::DeviceParallelEnv, alg::DRiL.SAC, agent)
         env.seed, env.device, Int32(0), 0, 0, 0.0f0, 0.0f0, ntuple(_ -> Int32(0), 4))
 end
 
+# a SAC handle over a device env: built-in kind or the caller's code object; MonitorWrapperEnv switched on when the env carries a window
+function sac_create(env::DeviceParallelEnv, alg::DRiL.SAC, agent)
+    cfg = Ref(sac_config(env, alg, agent)); hp = Ref{Ptr{Cvoid}}(C_NULL)
+    if env.kind === :Module      # OnDeviceModule: the env is the caller's code object; spaces and per-dimension Box bounds are its descriptor's
+        sac_check(ccall((:dril_sac_create_with_env_module, LIB[]), Int32, (Ref{DrilSacConfig}, Cstring, Ref{Ptr{Cvoid}}), cfg, MODULE_ENVS[env].path, hp))
+    else
+        sac_check(ccall((:dril_sac_create, LIB[]), Int32, (Ref{DrilSacConfig}, Ref{Ptr{Cvoid}}), cfg, hp))
+    end
+    h = hp[]
+    if env.monitor_window > 0
+        rc = ccall((:dril_sac_monitor_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, env.monitor_window)
+        rc == 0 || (msg = unsafe_string(ccall((:dril_sac_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h)); ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h); error("libdril_hip (SAC) status $rc: " * msg))
+    end
+    return h
+end
+# log_stats(env::MonitorWrapperEnv, logger) (monitorWrapperEnv.jl:64-70, called by sac.jl:307) from the SAC handle's window of finished episodes
+function sac_log_stats(h::Ptr{Cvoid}, env::DeviceParallelEnv, logger)
+    env.monitor_window > 0 || return nothing
+    r = Ref{Float32}(0); l = Ref{Float32}(0); n = Ref{Int32}(0)
+    sac_check(ccall((:dril_sac_monitor_get_stats, LIB[]), Int32, (Ptr{Cvoid}, Ref{Float32}, Ref{Float32}, Ref{Int32}), h, r, l, n), h)
+    if n[] > 0
+        DRiL.log_scalar!(logger, "env/ep_rew_mean", r[]); DRiL.log_scalar!(logger, "env/ep_len_mean", l[])
+    end
+    return (ep_rew_mean = r[], ep_len_mean = l[], n_episodes = Int(n[]))
+end
+function sac_push_agent!(h::Ptr{Cvoid}, agent)
+    flat = sac_flatten_params(agent.train_state.parameters); tgt = sac_flatten_targets(agent.aux.Q_target_parameters)
+    GC.@preserve flat tgt begin
+        sac_check(ccall((:dril_sac_set_params, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, flat, length(flat)), h)
+        sac_check(ccall((:dril_sac_set_target_params, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, tgt, length(tgt)), h)
+    end
+    sac_check(ccall((:dril_sac_set_log_ent_coef, LIB[]), Int32, (Ptr{Cvoid}, Float32), h, first(agent.aux.ent_train_state.parameters.log_ent_coef)), h)
+    return flat, tgt
+end
+
+"""
+    evaluate_agent(agent::SACAgent, env::DeviceParallelEnv; n_eval_episodes = 10, deterministic = true, ...)
+
+`evaluate_agent` (src/evaluation.jl:54-143) of a SAC agent on a device env (built-in Box kind or `OnDeviceModule`): the agent's actor steps `n_envs` envs
+seeded `env.seed + i` on the device, the episode accounting stays there (dril_sac_evaluate_agent).  Same keywords and return shapes as the reference.
+"""
+function DRiL.evaluate_agent(agent::SACAgent, env::DeviceParallelEnv; n_eval_episodes::Int = 10, deterministic::Bool = true,
+        reward_threshold::Union{Nothing, Real} = nothing, return_stats::Bool = true, warn::Bool = true, kwargs...)
+    h = sac_create(env, agent.algorithm, agent)
+    try
+        sac_push_agent!(h, agent)
+        st = Ref{DrilEvalStats}(); er = Vector{Float32}(undef, n_eval_episodes); el = Vector{Int32}(undef, n_eval_episodes)
+        GC.@preserve er el sac_check(ccall((:dril_sac_evaluate_agent, LIB[]), Int32, (Ptr{Cvoid}, Int32, Int32, UInt64, Ref{DrilEvalStats}, Ptr{Float32}, Ptr{Int32}),
+            h, n_eval_episodes, deterministic, env.seed, st, er, el), h)
+        s = st[]
+        if reward_threshold !== nothing && s.mean_reward < reward_threshold
+            error("Mean reward below threshold: $(round(s.mean_reward, digits = 2)) < $(reward_threshold)")            # evaluation.jl:131-135
+        end
+        return return_stats ? (; mean_reward = s.mean_reward, std_reward = s.std_reward, mean_length = s.mean_length, std_length = s.std_length) :
+            (er, Int.(el))
+    finally
+        ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h)
+    end
+end
+
 """
     train!(agent, env::DeviceParallelEnv, alg::SAC, max_steps) -> (agent, nothing, training_stats, to)
 
@@ -93,24 +153,13 @@ function train!(agent::SACAgent, env::DeviceParallelEnv, alg::DRiL.SAC, max_step
         return invoke(train!, Tuple{SACAgent, AbstractParallelEnv, DRiL.SAC, Int}, agent, env, alg, max_steps; kw...)
     end
     to = TimerOutput()
-    cfg = Ref(sac_config(env, alg, agent)); hp = Ref{Ptr{Cvoid}}(C_NULL)
-    if env.kind === :Module      # OnDeviceModule: the env is the caller's code object; spaces and per-dimension Box bounds are its descriptor's
-        sac_check(ccall((:dril_sac_create_with_env_module, LIB[]), Int32, (Ref{DrilSacConfig}, Cstring, Ref{Ptr{Cvoid}}), cfg, MODULE_ENVS[env].path, hp))
-    else
-        sac_check(ccall((:dril_sac_create, LIB[]), Int32, (Ref{DrilSacConfig}, Ref{Ptr{Cvoid}}), cfg, hp))
-    end
-    h = hp[]
+    h = sac_create(env, alg, agent)      # (env.monitor_window > 0: MonitorWrapperEnv on, its statistics logged below)
     try
         if env.kind === :Module      # the file may have changed since OnDeviceModule described it: the layer was built from that description
             info = sac_env_module_info(h)
             (info.obs_dim, info.action_dim) == (obs_dim(env), length(action_space(env).low)) || error("the plug-in behind the SAC handle is not the one OnDeviceModule described")
         end
-        flat = sac_flatten_params(agent.train_state.parameters); tgt = sac_flatten_targets(agent.aux.Q_target_parameters)
-        GC.@preserve flat tgt begin
-            sac_check(ccall((:dril_sac_set_params, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, flat, length(flat)), h)
-            sac_check(ccall((:dril_sac_set_target_params, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, tgt, length(tgt)), h)
-        end
-        sac_check(ccall((:dril_sac_set_log_ent_coef, LIB[]), Int32, (Ptr{Cvoid}, Float32), h, first(agent.aux.ent_train_state.parameters.log_ent_coef)), h)
+        flat, tgt = sac_push_agent!(h, agent)
         sac_check(ccall((:dril_sac_env_reset, LIB[]), Int32, (Ptr{Cvoid}, UInt64), h, env.seed), h)
         n_envs = env.n_envs                                                                       # schedule: sac.jl:436-447
         total_start = alg.start_steps > 0 ? alg.start_steps : alg.train_freq * n_envs
@@ -133,6 +182,7 @@ function train!(agent::SACAgent, env::DeviceParallelEnv, alg::DRiL.SAC, max_step
         end
         append!(ts.fps, T.(fps[1:it[]]))
         DRiL.add_step!(agent, tot[])
+        sac_log_stats(h, env, agent.logger)                                                        # log_stats(env, agent.logger), sac.jl:307: once, the iterations ran inside one library call
         GC.@preserve flat tgt begin
             sac_check(ccall((:dril_sac_get_params, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, flat, length(flat)), h)
             sac_check(ccall((:dril_sac_get_target_params, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, tgt, length(tgt)), h)

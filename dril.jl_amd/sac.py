@@ -15,7 +15,7 @@ import ctypes as C
 import math
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Optional, Sequence
 
 import numpy as np
@@ -369,6 +369,26 @@ class SacHandle:
                                      fps.ctypes.data_as(C.POINTER(C.c_double)) if want_stats else None, C.c_int64(iterations if want_stats else 0)))
         return list(stats[:cap]), fps[:iterations] if want_stats else fps[:0]
 
+    # MonitorWrapperEnv + evaluate_agent on the handle's device envs
+    def monitor_enable(self, window: int = 100):
+        """MonitorWrapperEnv(env, stats_window) around the handle's envs (monitorWrapperEnv.jl:15-24); 0 switches it off"""
+        self._chk(self._f("monitor_enable")(self._h, int(window)))
+
+    def monitor_stats(self):
+        """(ep_rew_mean, ep_len_mean, n_episodes) of MonitorWrapperEnv's window (log_stats, monitorWrapperEnv.jl:64-70); the means are nan while the window is empty"""
+        r, l, n = C.c_float(float("nan")), C.c_float(float("nan")), C.c_int32()
+        self._chk(self._f("monitor_get_stats")(self._h, C.byref(r), C.byref(l), C.byref(n)))
+        return r.value, l.value, n.value
+
+    def evaluate_agent(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None):
+        """evaluate_agent(agent, env; n_eval_episodes, deterministic) -> (stats dict, episode_rewards, episode_lengths), evaluation.jl:54-143; env e is reset
+        with seed + e (default: the config's seed).  Leaves the ring, the parameters and the training envs as they were."""
+        st = capi.DrilEvalStats()
+        er = np.empty(max(n_eval_episodes, 0), np.float32); el = np.empty(max(n_eval_episodes, 0), np.int32)
+        self._chk(self._f("evaluate_agent")(self._h, n_eval_episodes, int(deterministic), self.cfg.seed if seed is None else seed, C.byref(st), self._p(er), self._p(el)))
+        return dict(mean_reward=st.mean_reward, std_reward=st.std_reward, mean_length=st.mean_length, std_length=st.std_length,
+                    n_steps=st.n_steps), er, el
+
     def profile(self) -> dict:
         cm, um, cs, us = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self._f("profile_get")(self._h, C.byref(cm), C.byref(cs), C.byref(um), C.byref(us)))
@@ -432,6 +452,35 @@ _SAC_STAT_KEYS = ("actor_losses", "critic_losses", "entropy_losses", "entropy_co
                   "fps", "steps_taken")
 
 
+def _monitor_from_env(h: SacHandle, env):
+    """MonitorWrapperEnv(env, stats_window) over a device env (host.py: it records the window in the env's keywords): the same wrapper around the SAC handle's envs,
+    so that `replay_buffer.handle.monitor_stats()` gives what the reference logs as env/ep_rew_mean after every iteration (sac.jl:307)"""
+    window = int(getattr(env, "_kw", {}).get("monitor_window", 0) or 0)
+    if window > 0:
+        h.monitor_enable(window)
+
+
+def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, deterministic: bool = True, reward_threshold: Optional[float] = None,
+                       return_stats: bool = True):
+    """evaluate_agent(agent, env; ...) (src/evaluation.jl:54-143) of a SAC agent on a DeviceParallelEnv over a Box env or a DeviceModuleEnv over a Box plug-in:
+    the agent's actor on `env.n_envs` device envs seeded env.seed + i, episode accounting on the device (dril_sac_evaluate_agent).  Return shapes of
+    host.py::evaluate_agent: the statistics dict, or (episode_rewards, episode_lengths) with return_stats=False."""
+    if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
+        raise NotImplementedError("sac_evaluate_agent: host envs (HostParallelEnv) are evaluated on the host; the device verb steps device envs")
+    alg = agent.alg
+    small = replace(alg, buffer_capacity=max(env.n_envs, 1))        # an evaluation never touches the ring: the smallest one the library accepts
+    cfg = make_sac_config(env.env, env.n_envs, small, agent.layer, seed=env.seed, device=env._kw.get("device", 0))
+    h = SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
+    try:
+        h.set_params(sac_flatten_params(agent.parameters))
+        stats, er, el = h.evaluate_agent(n_eval_episodes, deterministic, seed=env.seed)
+    finally:
+        h.close()
+    if reward_threshold is not None and stats["mean_reward"] < reward_threshold:
+        raise RuntimeError(f"Mean reward below threshold: {stats['mean_reward']:.2f} < {reward_threshold}")   # evaluation.jl:131-135
+    return {k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} if return_stats else (er, el.astype(np.int64))
+
+
 def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer: Optional[ReplayBuffer] = None, callbacks=None):
     """train!(agent, env, alg::SAC, max_steps) sac.jl:406-549 -> (agent, replay_buffer, training_stats, timer); `env` is a
     DeviceParallelEnv over PendulumEnv / MountainCarContinuousEnv, a DeviceModuleEnv over a Box plug-in, or a HostParallelEnv.  training_stats carries the fields of SACTrainingStats (sac.jl:243-257)."""
@@ -444,6 +493,7 @@ def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer:
     cfg = make_sac_config(env.env, env.n_envs, alg, agent.layer, seed=env.seed, device=env._kw.get("device", 0), profile_events=env._kw.get("profile_events", False))
     h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
+    _monitor_from_env(h, env)
     h.set_params(sac_flatten_params(agent.parameters))
     h.set_target_params(agent.q_target_parameters)
     h.set_log_ent_coef(agent.log_ent_coef)
@@ -484,6 +534,7 @@ def _sac_train_callbacks(agent: SACAgent, env, alg: SAC, max_steps: int, replay_
     cfg = make_sac_config(env.env, env.n_envs, alg, agent.layer, seed=env.seed, device=env._kw.get("device", 0), profile_events=env._kw.get("profile_events", False))
     h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
+    _monitor_from_env(h, env)
     h.set_params(sac_flatten_params(agent.parameters)); h.set_target_params(agent.q_target_parameters); h.set_log_ent_coef(agent.log_ent_coef)
     h.env_reset(env.seed)
     E = env.n_envs

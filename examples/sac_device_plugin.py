@@ -20,22 +20,13 @@ print("env:", info)
 env = pkg.DeviceModuleEnv(code_object, n_envs, seed=0)
 alg = pkg.SAC(learning_rate=1e-3, buffer_capacity=100_000, start_steps=100 * n_envs, batch_size=256, gradient_steps=8)
 agent = pkg.SACAgent(pkg.SACLayer(env.observation_space(), env.action_space(), hidden_dims=(64, 64)), alg, seed=0)
-T = info["episode_len"]
-
-
-def episode_return(handle, seed=123):
-    """mean return of one episode per env under the current policy: reset, one time limit of policy steps, the rewards of the newest rows of the ring"""
-    handle.env_reset(seed)
-    handle.collect_rollout(T, False)
-    return float(handle.replay(pkg._capi.RB_REWARDS)[-T * n_envs:].reshape(T, n_envs).sum(0).mean())
-
-
-rb = pkg.ReplayBuffer(env.observation_space(), env.action_space(), alg.buffer_capacity)
-rb.handle = pkg.SacHandle(pkg.make_sac_config(env, n_envs, alg, agent.layer, seed=0), env_module=code_object)
-rb.handle.set_params(pkg.sac_flatten_params(agent.parameters))
-before = episode_return(rb.handle)
-agent, rb, stats, timer = pkg.sac_train_(agent, env, alg, max_steps, replay_buffer=rb)
-after = episode_return(rb.handle)
+env = pkg.MonitorWrapperEnv(env, 100)                                     # sac_train_ switches MonitorWrapperEnv on around the handle's envs: ep_rew_mean of the training episodes
+before = pkg.sac_evaluate_agent(agent, env, n_eval_episodes=n_envs)       # evaluate_agent: deterministic policy, episode accounting on the device, no training data touched
+agent, rb, stats, timer = pkg.sac_train_(agent, env, alg, max_steps)
+after = pkg.sac_evaluate_agent(agent, env, n_eval_episodes=n_envs)
+ep_rew_mean, ep_len_mean, n_ep = rb.handle.monitor_stats()
 print(f"trained {agent.steps_taken} env steps, {agent.gradient_updates} gradient steps in {timer['training_loop']:.2f} s; "
       f"critic loss {stats['critic_losses'][-1]:.4f}, entropy coefficient {stats['entropy_coefficients'][-1]:.4f}")
-print(f"episode return: {before:.1f} before -> {after:.1f} after")
+print(f"evaluate_agent ({n_envs} episodes, deterministic): mean return {before['mean_reward']:.1f} +- {before['std_reward']:.1f} before -> "
+      f"{after['mean_reward']:.1f} +- {after['std_reward']:.1f} after (mean length {after['mean_length']:.0f})")
+print(f"monitor: env/ep_rew_mean {ep_rew_mean:.1f}, env/ep_len_mean {ep_len_mean:.1f} over the last {n_ep} training episodes")

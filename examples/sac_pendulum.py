@@ -18,9 +18,12 @@ max_steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200_000
 env = pkg.DeviceParallelEnv(pkg.PendulumEnv(max_steps=200), n_envs, seed=0)
 alg = pkg.SAC(start_steps=5000, buffer_capacity=200_000, gradient_steps=max(1, n_envs // 8))
 agent = pkg.SACAgent(pkg.SACLayer(env.observation_space(), env.action_space(), hidden_dims=(256, 256)), alg, seed=0)
+env = pkg.MonitorWrapperEnv(env, 100)                                     # MonitorWrapperEnv(env, 100): episode statistics of the training episodes
+before = pkg.sac_evaluate_agent(agent, env)                               # evaluate_agent(agent, env): ten episodes of the deterministic policy
 agent, rb, stats, timer = pkg.sac_train_(agent, env, alg, max_steps)
-r = rb.rewards
-k = n_envs * 200
+after = pkg.sac_evaluate_agent(agent, env)
+ep_rew_mean, ep_len_mean, n_ep = rb.handle.monitor_stats()
 print(f"{agent.steps_taken} env steps, {agent.gradient_updates} gradient steps in {timer['training_loop']:.1f} s")
-print(f"mean reward per step: first {k} transitions {r[:k].mean():.3f} -> last {k} transitions {r[-k:].mean():.3f}")
+print(f"evaluate_agent (10 episodes, deterministic): mean return {before['mean_reward']:.1f} +- {before['std_reward']:.1f} before -> {after['mean_reward']:.1f} +- {after['std_reward']:.1f} after")
+print(f"monitor: env/ep_rew_mean {ep_rew_mean:.1f}, env/ep_len_mean {ep_len_mean:.1f} over the last {n_ep} training episodes")
 print(f"critic loss {np.mean(stats['critic_losses'][:50]):.3f} -> {np.mean(stats['critic_losses'][-50:]):.3f}; entropy coefficient {stats['entropy_coefficients'][-1]:.3f}")

@@ -202,6 +202,32 @@ int32_t dril_sac_train(dril_sac_handle* h, int64_t max_steps, dril_sac_stats* st
 int32_t dril_sac_iterate(dril_sac_handle* h, int32_t iterations, dril_sac_stats* stats, int64_t stats_capacity, double* fps,
                          int64_t fps_capacity);
 
+/* ---- MonitorWrapperEnv(env, stats_window) around the handle's device envs (src/environment_wrappers/monitorWrapperEnv.jl) -------------------------------
+ * window >= 1 switches it on (the reference's default is 100): a fresh wrapper with zero running sums and an empty window; the window the handle already has is a
+ * no-op; 0 switches it off and forgets the window.  Running return / length per env are those of the RAW env rewards and accumulate over every collected step
+ * (start phase and policy steps alike: dril_sac_collect_rollout, dril_sac_train, dril_sac_iterate); the finished episodes of a collection enter the window in
+ * (step, env) order by one launch at the collection's end, the ring is written exactly as without the monitor.  dril_sac_env_reset zeroes the running sums and keeps
+ * the window (:36-42).  DRIL_ERR_UNSUPPORTED on a DRIL_ENV_EXTERNAL handle (host envs are wrapped on the host), DRIL_ERR_INVALID_ARG for window < 0. */
+int32_t dril_sac_monitor_enable(dril_sac_handle* h, int32_t window);
+/* log_stats (:64-70): mean return / length over the last min(n, window) finished episodes and their number; n_episodes == 0 leaves the two means untouched.
+ * DRIL_ERR_NOT_INITIALISED while the monitor is off. */
+int32_t dril_sac_monitor_get_stats(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes);
+
+/* ---- evaluate_agent(agent, env; n_eval_episodes, deterministic) (src/evaluation.jl:54-143) with the handle's actor on the handle's envs --------------------
+ * reset (env e seeded seed + e), then predict_actions(; deterministic) -> act! -> observe until the first n_eval_episodes episodes have finished, taken in
+ * (step, env) order.  deterministic: mode(d) = tanh(mean) (squashedDiagGaussian.jl:48-50) through TanhScaleAdapter; otherwise a sample, its noise from env e's
+ * collection stream under `seed`.  dril_eval_stats as in dril_hip.h (Julia mean / corrected std, NaN std for one episode; n_steps = the 1-based env step at which
+ * the last counted episode finished).  episode_rewards / episode_lengths (n_eval_episodes entries each) may be NULL.
+ * The episode accounting lives on the device (running sums per env, finished episodes appended to an event list); the host looks at the list's counter once every
+ * K enqueued env steps (K = min(episode_len, 32); DRIL_SAC_EVAL_POLL=<k> read at create overrides; 1 = step by step).  The result is the same for every K.
+ * Evaluation has no side effect on training: it never writes the replay ring, parameters, targets, optimiser state, update counters or the monitor's window, and the
+ * env side of the handle (state, step / episode counters, the noise stream's position, the current observation, the monitor's running sums) is set aside before and
+ * put back after, on error paths too — the reference evaluates on a separate env object; one handle is agent and envs together.
+ * DRIL_ERR_UNSUPPORTED on a DRIL_ENV_EXTERNAL handle (evaluate host envs on the host with dril_sac_predict_actions) and when no episode finishes within the time
+ * limits n_eval_episodes can take; DRIL_ERR_INVALID_ARG for n_eval_episodes < 1 or out == NULL. */
+int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval_episodes, int32_t deterministic, uint64_t seed,
+                                dril_eval_stats* out, float* episode_rewards, int32_t* episode_lengths);
+
 /* ---- measurement: accumulated HIP-event milliseconds since the last reset --------------------------------------------- */
 int32_t dril_sac_profile_get(dril_sac_handle* h, double* collect_ms, int64_t* collect_steps, double* update_ms,
                              int64_t* updates);
