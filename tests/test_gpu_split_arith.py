@@ -3,7 +3,7 @@ three bf16 pieces, six products) — at the minibatch sizes where the size rule 
 (1) directly against the CPU oracle (ppo.jl:365-407 + hand-written backward), (2) against a float64 gradient with an error budget relative to
 the exact-f32 kernel, (3) with a negative control: the same library built with the `lo` products dropped (an 11-bit product; 16-bit in the bf16 form)
 must BREAK the budget — which is what shows that (2) can tell a 24-bit product from a shorter one, (4) at the full minibatch size of the headline
-config through additivity.
+config through additivity (directly against the oracle at that size: tests/test_gpu_bench_scale.py).
 
 Tolerances: loss 1e-4 rel (BASELINE.json north_star), gradient within 2e-4 of its norm, as for the f32 kernel in tests/test_gpu_parity.py.
 """
@@ -146,9 +146,11 @@ def test_an_update_outside_the_f16_range_is_redone_on_the_exact_f32_kernels(pkg,
 @pytest.mark.parametrize("kind,H,variant", [(0, 64, "ent_vfclip"), (1, 64, "default"), (1, 256, "default")])
 def test_full_size_minibatch_is_the_weighted_mean_of_its_halves(pkg, kind, H, variant):
     """the headline minibatch size of BASELINE configs[1] / configs[2] (B = 65 536 x 2048 / 32 = 4 194 304 samples per launch: 256 tiles per pair of ppo_grad_pair_kernel,
-    the multi-trip loop with the unequal actor / critic division of the chip) is too large for the oracle to be the checker in a test, but the loss is a MEAN over the
-    minibatch (ppo.jl:382-386), so with normalize_advantage off loss / statistics / gradient of the whole minibatch must be the sample-weighted mean of those of two
-    unequal parts — each of which is the size the direct oracle tests above cover per tile, run through different tile -> pair assignments and slab reductions.
+    the multi-trip loop with the unequal actor / critic division of the chip) meets the oracle directly in tests/test_gpu_bench_scale.py
+    (test_bench_minibatch_loss_and_gradient_vs_oracle: the oracle's loss + gradient is OpenMP-parallel, ~5 s for this size at [64,64]).  This test keeps a property the
+    oracle does not give: the loss is a MEAN over the minibatch (ppo.jl:382-386), so with normalize_advantage off loss / statistics / gradient of the whole minibatch
+    must be the sample-weighted mean of those of two unequal parts, run through different tile -> pair assignments and slab reductions — a device-against-device
+    statement, far tighter than the oracle's tolerance.
     f32 sums in different orders: loss and gradient to 2e-6 of their size (measured: loss 1e-9 ... 6e-8, gradient 1.1e-7 ... 1.4e-7 of its norm; tests/diag/full_size_additivity.py)"""
     B = 4194304
     kw = dict(n_envs=2, n_steps=2, batch_size=2, hidden1=H, hidden2=H, normalize_advantage=0)
