@@ -97,6 +97,12 @@ class DrilSacStats(C.Structure):
                 ("entropy_coefficient", C.c_float), ("grad_norm", C.c_float), ("has_entropy_loss", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DrilSacNormalizeConfig(C.Structure):
+    """struct dril_sac_normalize_config, include/dril_sac.h (the keywords of NormalizeWrapperEnv, normalizeWrapperEnv.jl:71-80)"""
+    _fields_ = [("training", C.c_int32), ("norm_obs", C.c_int32), ("norm_reward", C.c_int32), ("clip_obs", C.c_float), ("clip_reward", C.c_float),
+                ("gamma", C.c_float), ("epsilon", C.c_float), ("reserved", C.c_int32)]
+
+
 SAC_ABI_VERSION = 1
 (RB_OBSERVATIONS, RB_ACTIONS, RB_REWARDS, RB_TERMINATED, RB_TRUNCATED, RB_NEXT_OBSERVATIONS) = range(6)
 
@@ -224,6 +230,7 @@ _SAC_SIG = {
     "predict_actions": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     "predict_q": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int32, _P]),
     "collect_rollout": (C.c_int32, [_P, C.c_int32, C.c_int32, _PD]),
+    "collect_continue": (C.c_int32, [_P, C.c_int32, C.c_int32, _PD]),
     "ext_push": (C.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "debug_set_collect_noise": (C.c_int32, [_P, _P, C.c_size_t]),
     "replay_size": (C.c_int64, [_P]),
@@ -240,6 +247,14 @@ _SAC_SIG = {
     "monitor_enable": (C.c_int32, [_P, C.c_int32]),
     "monitor_get_stats": (C.c_int32, [_P, _PF, _PF, C.POINTER(C.c_int32)]),
     "evaluate_agent": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(DrilEvalStats), _P, _P]),
+    "normalize_config_default": (C.c_int32, [C.POINTER(DrilSacNormalizeConfig)]),
+    "normalize_enable": (C.c_int32, [_P, C.POINTER(DrilSacNormalizeConfig)]),
+    "normalize_get_config": (C.c_int32, [_P, C.POINTER(DrilSacNormalizeConfig)]),
+    "normalize_set_training": (C.c_int32, [_P, C.c_int32]),
+    "normalize_get_stats": (C.c_int32, [_P, _P, _P, _PI64, _PF, _PF, _PI64]),
+    "normalize_set_stats": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64]),
+    "normalize_get_original": (C.c_int32, [_P, _P, _P]),
+    "normalize_get_returns": (C.c_int32, [_P, _P]),
 }
 _SIG.update({"dril_sac_" + k: v for k, v in _SAC_SIG.items()})
 EXPORTED_SYMBOLS = tuple(_SIG)

@@ -86,10 +86,22 @@ def load_policy_params_and_state_(agent, alg, path, suffix: str = ".npz"):
 _NORM_KEYS = ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")
 
 
-def save_normalization_stats(env, filepath) -> str:
-    """env: a DeviceParallelEnv with NormalizeWrapperEnv switched on and a bound handle"""
-    st = env.handle.norm_get_stats()
-    kw = env._kw["normalize"]
+def _norm_handle_kw(env):
+    """(the object with norm_get_stats / norm_set_stats, the wrapper's keywords or None): a DeviceParallelEnv with NormalizeWrapperEnv and a bound PPO handle, or a
+    SacHandle with the wrapper on (dril_sac_normalize_enable) — `replay_buffer.handle` after sac_train_"""
+    if hasattr(env, "norm_get_stats"):
+        return env, None
+    return env.handle, env._kw["normalize"]
+
+
+def save_normalization_stats(env, filepath, **keywords) -> str:
+    """env: a DeviceParallelEnv with NormalizeWrapperEnv switched on and a bound handle, or a SacHandle with the wrapper on (clip_obs / clip_reward / gamma /
+    epsilon are read from the handle: dril_sac_normalize_get_config; keywords override).  File keys: those of save_normalization_stats, normalizeWrapperEnv.jl:261-277"""
+    h, kw = _norm_handle_kw(env)
+    if kw is None and hasattr(h, "normalize_config"):
+        kw = h.normalize_config()                                      # a SacHandle holds the wrapper's keywords itself
+    kw = {**dict(clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8), **(kw or {}), **keywords}
+    st = h.norm_get_stats()
     fp = str(filepath) if str(filepath).endswith(".npz") else str(filepath) + ".npz"
     np.savez(fp, **{k: np.asarray(st[k]) for k in _NORM_KEYS}, clip_obs=kw["clip_obs"], clip_reward=kw["clip_reward"], gamma=kw["gamma"], epsilon=kw["epsilon"])
     return fp
@@ -98,5 +110,6 @@ def save_normalization_stats(env, filepath) -> str:
 def load_normalization_stats_(env, filepath):
     fp = str(filepath) if str(filepath).endswith(".npz") else str(filepath) + ".npz"
     d = np.load(fp)
-    env.handle.norm_set_stats(d["obs_mean"], d["obs_var"], int(d["obs_count"]), float(d["ret_mean"]), float(d["ret_var"]), int(d["ret_count"]))
+    h, _ = _norm_handle_kw(env)
+    h.norm_set_stats(d["obs_mean"], d["obs_var"], int(d["obs_count"]), float(d["ret_mean"]), float(d["ret_var"]), int(d["ret_count"]))
     return env

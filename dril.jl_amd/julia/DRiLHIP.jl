@@ -126,10 +126,11 @@ function describe_env_module(path::AbstractString, device::Integer = 0)
     name = String(buf[537:(536 + something(findfirst(==(0x00), buf[537:end]), 65) - 1)])
     return (path = String(path), state_dim = Int(i32[1]), obs_dim = Int(i32[2]), action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]), low = low, high = high, name = name)
 end
-"`OnDeviceModule(path, n_envs)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop)"
-function OnDeviceModule(path::AbstractString, n_envs::Integer; max_steps::Union{Nothing, Integer} = nothing, seed::Integer = 42, device::Integer = 0, monitor_window::Integer = 0)
+"`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv for SAC"
+function OnDeviceModule(path::AbstractString, n_envs::Integer; max_steps::Union{Nothing, Integer} = nothing, seed::Integer = 42, device::Integer = 0, monitor_window::Integer = 0,
+        normalize::Union{Nothing, NamedTuple} = nothing)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (train! / evaluate_agent with alg::SAC); the PPO handle refuses them for a plug-in
     info = describe_env_module(path, device)
-    env = DeviceParallelEnv(:Module, n_envs; max_steps = something(max_steps, info.episode_len), seed = seed, device = device, monitor_window = monitor_window)
+    env = DeviceParallelEnv(:Module, n_envs; max_steps = something(max_steps, info.episode_len), seed = seed, device = device, monitor_window = monitor_window, normalize = normalize)
     MODULE_ENVS[env] = info
     return env
 end

@@ -80,7 +80,49 @@ function sac_config(env::DeviceParallelEnv, alg::DRiL.SAC, agent)
         env.seed, env.device, Int32(0), 0, 0, 0.0f0, 0.0f0, ntuple(_ -> Int32(0), 4))
 end
 
-# a SAC handle over a device env: built-in kind or the caller's code object; MonitorWrapperEnv switched on when the env carries a window
+# struct dril_sac_normalize_config (include/dril_sac.h): the keywords of NormalizeWrapperEnv (normalizeWrapperEnv.jl:71-80)
+struct DrilSacNormalizeConfig
+    training::Int32; norm_obs::Int32; norm_reward::Int32
+    clip_obs::Float32; clip_reward::Float32
+    gamma::Float32; epsilon::Float32
+    reserved::Int32
+end
+# NormalizeWrapperEnv around the handle's device envs from the env's `normalize` keywords (a NamedTuple; missing keys take the reference's defaults); `training`
+# overrides the keyword (evaluate_agent: set_training(eval_env, false))
+function sac_normalize_enable!(h::Ptr{Cvoid}, nz::NamedTuple; training::Union{Nothing, Bool} = nothing)
+    g(k, d) = get(nz, k, d)
+    cfg = Ref(DrilSacNormalizeConfig(Int32(something(training, g(:training, true))), Int32(g(:norm_obs, true)), Int32(g(:norm_reward, true)),
+        Float32(g(:clip_obs, 10.0f0)), Float32(g(:clip_reward, 10.0f0)), Float32(g(:gamma, 0.99f0)), Float32(g(:epsilon, 1.0f-8)), Int32(0)))
+    sac_check(ccall((:dril_sac_normalize_enable, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilSacNormalizeConfig}), h, cfg), h)
+    return h
+end
+sac_normalize_set_training!(h::Ptr{Cvoid}, training::Bool) =
+    (sac_check(ccall((:dril_sac_normalize_set_training, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(training)), h); h)
+# obs_rms / ret_rms of the wrapper behind a SAC handle: the fields of save_normalization_stats (normalizeWrapperEnv.jl:261-277)
+function sac_norm_stats(h::Ptr{Cvoid})
+    D = Int(ccall((:dril_sac_obs_dim, LIB[]), Int32, (Ptr{Cvoid},), h))
+    om = Vector{Float32}(undef, D); ov = Vector{Float32}(undef, D); oc = Ref{Int64}(0); rc = Ref{Int64}(0); rm = Ref{Float32}(0); rv = Ref{Float32}(0)
+    GC.@preserve om ov sac_check(ccall((:dril_sac_normalize_get_stats, LIB[]), Int32,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ref{Int64}, Ref{Float32}, Ref{Float32}, Ref{Int64}), h, om, ov, oc, rm, rv, rc), h)
+    return (obs_mean = om, obs_var = ov, obs_count = oc[], ret_mean = rm[], ret_var = rv[], ret_count = rc[])
+end
+# load_normalization_stats! / sync_normalization_stats! (:280-309) into the wrapper behind a SAC handle
+function sac_set_norm_stats!(h::Ptr{Cvoid}, s)
+    om = Vector{Float32}(vec(s.obs_mean)); ov = Vector{Float32}(vec(s.obs_var))
+    GC.@preserve om ov sac_check(ccall((:dril_sac_normalize_set_stats, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int64, Float32, Float32, Int64),
+        h, om, ov, Int64(s.obs_count), Float32(first(s.ret_mean)), Float32(first(s.ret_var)), Int64(s.ret_count)), h)
+    return h
+end
+# get_original_obs / get_original_rewards (:225-226): (D x n_envs matrix, n_envs vector)
+function sac_norm_original(h::Ptr{Cvoid}, n_envs::Int)
+    D = Int(ccall((:dril_sac_obs_dim, LIB[]), Int32, (Ptr{Cvoid},), h))
+    obs = Matrix{Float32}(undef, D, n_envs); rew = Vector{Float32}(undef, n_envs)
+    GC.@preserve obs rew sac_check(ccall((:dril_sac_normalize_get_original, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h, obs, rew), h)
+    return obs, rew
+end
+
+# a SAC handle over a device env: built-in kind or the caller's code object; MonitorWrapperEnv switched on when the env carries a window, NormalizeWrapperEnv when it
+# carries `normalize` keywords (built-in kinds and OnDeviceModule alike: the SAC handle's wrapper takes any observation width)
 function sac_create(env::DeviceParallelEnv, alg::DRiL.SAC, agent)
     cfg = Ref(sac_config(env, alg, agent)); hp = Ref{Ptr{Cvoid}}(C_NULL)
     if env.kind === :Module      # OnDeviceModule: the env is the caller's code object; spaces and per-dimension Box bounds are its descriptor's
@@ -92,6 +134,14 @@ function sac_create(env::DeviceParallelEnv, alg::DRiL.SAC, agent)
     if env.monitor_window > 0
         rc = ccall((:dril_sac_monitor_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, env.monitor_window)
         rc == 0 || (msg = unsafe_string(ccall((:dril_sac_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h)); ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h); error("libdril_hip (SAC) status $rc: " * msg))
+    end
+    if env.normalize !== nothing
+        try
+            sac_normalize_enable!(h, env.normalize)
+        catch
+            ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h)
+            rethrow()
+        end
     end
     return h
 end
@@ -120,12 +170,18 @@ end
 
 `evaluate_agent` (src/evaluation.jl:54-143) of a SAC agent on a device env (built-in Box kind or `OnDeviceModule`): the agent's actor steps `n_envs` envs
 seeded `env.seed + i` on the device, the episode accounting stays there (dril_sac_evaluate_agent).  Same keywords and return shapes as the reference.
+An env with `normalize` keywords is evaluated under NormalizeWrapperEnv with training off; `normalize_stats` (what `sac_norm_stats` returned for the training handle)
+are the statistics it normalises with.  Episode returns are raw.
 """
 function DRiL.evaluate_agent(agent::SACAgent, env::DeviceParallelEnv; n_eval_episodes::Int = 10, deterministic::Bool = true,
-        reward_threshold::Union{Nothing, Real} = nothing, return_stats::Bool = true, warn::Bool = true, kwargs...)
+        reward_threshold::Union{Nothing, Real} = nothing, return_stats::Bool = true, warn::Bool = true, normalize_stats = nothing, kwargs...)
     h = sac_create(env, agent.algorithm, agent)
     try
         sac_push_agent!(h, agent)
+        if env.normalize !== nothing      # the reference's arrangement (normalizeWrapperEnv.jl:245-249,299-309): the training statistics (sac_norm_stats of the training handle), frozen
+            sac_normalize_set_training!(h, false)
+            normalize_stats === nothing || sac_set_norm_stats!(h, normalize_stats)
+        end
         st = Ref{DrilEvalStats}(); er = Vector{Float32}(undef, n_eval_episodes); el = Vector{Int32}(undef, n_eval_episodes)
         GC.@preserve er el sac_check(ccall((:dril_sac_evaluate_agent, LIB[]), Int32, (Ptr{Cvoid}, Int32, Int32, UInt64, Ref{DrilEvalStats}, Ptr{Float32}, Ptr{Int32}),
             h, n_eval_episodes, deterministic, env.seed, st, er, el), h)
@@ -145,8 +201,11 @@ end
 
 Same contract as `train!(agent, replay_buffer, env, alg::SAC, max_steps)` (sac.jl:414-549) with the ReplayBuffer resident on the device
 (second return value `nothing`; read it through `dril_sac_replay_copy_out`).  Callbacks with `on_step` hooks are not supported on this path.
+An env built with `normalize = (; ...)` trains under NormalizeWrapperEnv on the device (dril_sac_normalize_enable: any observation width, plug-ins included);
+`normalization_stats = Ref{Any}()` receives the final statistics (`sac_norm_stats`), which `evaluate_agent(...; normalize_stats = ...)` takes.
 """
-function train!(agent::SACAgent, env::DeviceParallelEnv, alg::DRiL.SAC, max_steps::Int; ad_type = nothing, callbacks = nothing)
+function train!(agent::SACAgent, env::DeviceParallelEnv, alg::DRiL.SAC, max_steps::Int; ad_type = nothing, callbacks = nothing,
+        normalization_stats::Union{Nothing, Base.RefValue} = nothing)
     T = typeof(alg.learning_rate)
     if has_step_hooks(callbacks)      # on_step hooks: the reference's own train! over this env's step-granular verbs
         kw = isnothing(ad_type) ? (; callbacks = callbacks) : (; ad_type = ad_type, callbacks = callbacks)
@@ -191,6 +250,7 @@ function train!(agent::SACAgent, env::DeviceParallelEnv, alg::DRiL.SAC, max_step
         le = Ref{Float32}(0); sac_check(ccall((:dril_sac_get_log_ent_coef, LIB[]), Int32, (Ptr{Cvoid}, Ref{Float32}), h, le), h)
         agent.aux.ent_train_state.parameters.log_ent_coef[1] = le[]
         !isnothing(callbacks) && all(c -> DRiL.on_training_end(c, Dict{Symbol, Any}(:agent => agent, :env => env, :alg => alg)), callbacks)
+        (env.normalize !== nothing && normalization_stats !== nothing) && (normalization_stats[] = sac_norm_stats(h))   # the wrapper lives in the handle: its statistics leave through the Ref
         return agent, nothing, ts, to
     finally
         ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h)

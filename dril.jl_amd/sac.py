@@ -15,6 +15,7 @@ import ctypes as C
 import math
 import os
 import time
+import warnings
 from dataclasses import dataclass, field, replace
 from typing import Optional, Sequence
 
@@ -303,6 +304,13 @@ class SacHandle:
         self._chk(self._f("collect_rollout")(self._h, n_steps, int(use_random_actions), C.byref(fps)))
         return fps.value
 
+    def collect_continue(self, n_steps: int = 1, use_random_actions: bool = False) -> float:
+        """dril_sac_collect_continue: further steps of the collection the previous collect call left off (host code between the env steps of ONE
+        collect_trajectories: on_step callbacks) — under NormalizeWrapperEnv without the observe a collection begins with"""
+        fps = C.c_double()
+        self._chk(self._f("collect_continue")(self._h, n_steps, int(use_random_actions), C.byref(fps)))
+        return fps.value
+
     def ext_push(self, obs, stored_actions, rewards, terminated, truncated, next_obs, terminal_obs=None):
         """one env step of the caller's host envs into the replay ring (DRIL_ENV_EXTERNAL)"""
         o, a, r, n = self._f32(obs), self._f32(stored_actions), self._f32(rewards), self._f32(next_obs)
@@ -379,6 +387,56 @@ class SacHandle:
         r, l, n = C.c_float(float("nan")), C.c_float(float("nan")), C.c_int32()
         self._chk(self._f("monitor_get_stats")(self._h, C.byref(r), C.byref(l), C.byref(n)))
         return r.value, l.value, n.value
+
+    # NormalizeWrapperEnv around the handle's device envs (dril_sac_normalize_*)
+    def normalize_enable(self, enabled: bool = True, **kw):
+        """NormalizeWrapperEnv(env; training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon) (normalizeWrapperEnv.jl:71-80) around the handle's envs:
+        a fresh wrapper, or nothing when the handle already has this configuration; normalize_enable(False) switches it off"""
+        if not enabled:
+            self._chk(self._f("normalize_enable")(self._h, None)); return
+        c = capi.DrilSacNormalizeConfig()
+        self._chk(self._f("normalize_config_default")(C.byref(c)))
+        for k, v in kw.items():
+            if k not in ("training", "norm_obs", "norm_reward", "clip_obs", "clip_reward", "gamma", "epsilon"):
+                raise TypeError(f"NormalizeWrapperEnv has no keyword {k!r}")
+            setattr(c, k, int(v) if k in ("training", "norm_obs", "norm_reward") else float(v))
+        self._chk(self._f("normalize_enable")(self._h, C.byref(c)))
+
+    def normalize_config(self) -> dict:
+        """the wrapper's keywords as the handle holds them (dril_sac_normalize_get_config)"""
+        c = capi.DrilSacNormalizeConfig()
+        self._chk(self._f("normalize_get_config")(self._h, C.byref(c)))
+        return dict(training=bool(c.training), norm_obs=bool(c.norm_obs), norm_reward=bool(c.norm_reward), clip_obs=c.clip_obs, clip_reward=c.clip_reward,
+                    gamma=c.gamma, epsilon=c.epsilon)
+
+    def normalize_set_training(self, training: bool):
+        """set_training(env, training) (normalizeWrapperEnv.jl:245-249)"""
+        self._chk(self._f("normalize_set_training")(self._h, int(bool(training))))
+
+    def norm_get_stats(self) -> dict:
+        """RunningMeanStd fields of the wrapper (normalizeWrapperEnv.jl:8-19); the keys of Handle.norm_get_stats"""
+        om = np.empty(self.D, np.float32); ov = np.empty(self.D, np.float32)
+        oc, rc = C.c_int64(), C.c_int64(); rm, rv = C.c_float(), C.c_float()
+        self._chk(self._f("normalize_get_stats")(self._h, self._p(om), self._p(ov), C.byref(oc), C.byref(rm), C.byref(rv), C.byref(rc)))
+        return dict(obs_mean=om, obs_var=ov, obs_count=oc.value, ret_mean=rm.value, ret_var=rv.value, ret_count=rc.value)
+
+    def norm_set_stats(self, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count):
+        om = np.ascontiguousarray(obs_mean, np.float32).reshape(-1); ov = np.ascontiguousarray(obs_var, np.float32).reshape(-1)
+        if om.size != self.D or ov.size != self.D:
+            raise ValueError(f"obs_mean / obs_var must hold {self.D} values")
+        self._chk(self._f("normalize_set_stats")(self._h, self._p(om), self._p(ov), int(obs_count), float(ret_mean), float(ret_var), int(ret_count)))
+
+    def norm_get_original(self):
+        """-> (get_original_obs (E, D), get_original_rewards (E)), normalizeWrapperEnv.jl:225-226"""
+        obs = np.empty((self.E, self.D), np.float32); rew = np.empty(self.E, np.float32)
+        self._chk(self._f("normalize_get_original")(self._h, self._p(obs), self._p(rew)))
+        return obs, rew
+
+    def norm_get_returns(self) -> np.ndarray:
+        """env.returns: the discounted running return per env behind ret_rms"""
+        r = np.empty(self.E, np.float32)
+        self._chk(self._f("normalize_get_returns")(self._h, self._p(r)))
+        return r
 
     def evaluate_agent(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None):
         """evaluate_agent(agent, env; n_eval_episodes, deterministic) -> (stats dict, episode_rewards, episode_lengths), evaluation.jl:54-143; env e is reset
@@ -460,11 +518,32 @@ def _monitor_from_env(h: SacHandle, env):
         h.monitor_enable(window)
 
 
+def _normalize_kw(env, normalize: Optional[dict]) -> Optional[dict]:
+    """the NormalizeWrapperEnv keywords of a run: the `normalize=` argument (the one way a DeviceModuleEnv gets the wrapper: host.NormalizeWrapperEnv probes the PPO
+    handle, which refuses plug-ins) wins over what NormalizeWrapperEnv(DeviceParallelEnv(...)) recorded in the env's keywords; None: no wrapper"""
+    if normalize is not None:
+        return dict(normalize)
+    kw = getattr(env, "_kw", {}).get("normalize")
+    return dict(kw) if kw is not None else None
+
+
+def _normalize_from_env(h: SacHandle, env, normalize: Optional[dict]):
+    """the wrapper of this run around the SAC handle's envs (a handle that already carries this configuration keeps its statistics); no keywords: off"""
+    kw = _normalize_kw(env, normalize)
+    if kw is None:
+        h.normalize_enable(False)
+    else:
+        h.normalize_enable(**kw)
+
+
 def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, deterministic: bool = True, reward_threshold: Optional[float] = None,
-                       return_stats: bool = True):
+                       return_stats: bool = True, *, normalize: Optional[dict] = None, normalize_stats=None):
     """evaluate_agent(agent, env; ...) (src/evaluation.jl:54-143) of a SAC agent on a DeviceParallelEnv over a Box env or a DeviceModuleEnv over a Box plug-in:
     the agent's actor on `env.n_envs` device envs seeded env.seed + i, episode accounting on the device (dril_sac_evaluate_agent).  Return shapes of
-    host.py::evaluate_agent: the statistics dict, or (episode_rewards, episode_lengths) with return_stats=False."""
+    host.py::evaluate_agent: the statistics dict, or (episode_rewards, episode_lengths) with return_stats=False.
+    NormalizeWrapperEnv (the env's own keywords, or `normalize=dict(...)`): the evaluation handle is a throw-away one, so the training statistics are loaded into it
+    from `normalize_stats` — the training handle (`replay_buffer.handle`) or a norm_get_stats() dict — with training off; reported returns are raw.  Without
+    them the evaluation would silently run under mean 0 / var 1: that is a RuntimeWarning unless `normalize_stats="fresh"` asks for it (an untrained agent)."""
     if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
         raise NotImplementedError("sac_evaluate_agent: host envs (HostParallelEnv) are evaluated on the host; the device verb steps device envs")
     alg = agent.alg
@@ -473,6 +552,18 @@ def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, determin
     h = SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     try:
         h.set_params(sac_flatten_params(agent.parameters))
+        kw = _normalize_kw(env, normalize)
+        if kw is not None:           # sync_normalization_stats! + set_training(eval_env, false) (normalizeWrapperEnv.jl:245-249,299-309): the training statistics, frozen
+            h.normalize_enable(**{**kw, "training": False})
+            if normalize_stats is None:
+                warnings.warn("sac_evaluate_agent: the env is normalised but no normalize_stats were given: the evaluation runs with fresh statistics (mean 0, var 1), "
+                              "not those the agent was trained under; pass the training handle (replay_buffer.handle), a norm_get_stats() dict, or \"fresh\" to say so",
+                              RuntimeWarning, stacklevel=2)
+            st = None if isinstance(normalize_stats, str) else normalize_stats.norm_get_stats() if hasattr(normalize_stats, "norm_get_stats") else normalize_stats
+            if isinstance(normalize_stats, str) and normalize_stats != "fresh":
+                raise ValueError("normalize_stats: a handle, a norm_get_stats() dict, or \"fresh\"")
+            if st is not None:
+                h.norm_set_stats(*(st[k] for k in ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")))
         stats, er, el = h.evaluate_agent(n_eval_episodes, deterministic, seed=env.seed)
     finally:
         h.close()
@@ -481,19 +572,24 @@ def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, determin
     return {k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} if return_stats else (er, el.astype(np.int64))
 
 
-def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer: Optional[ReplayBuffer] = None, callbacks=None):
+def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer: Optional[ReplayBuffer] = None, callbacks=None, normalize: Optional[dict] = None):
     """train!(agent, env, alg::SAC, max_steps) sac.jl:406-549 -> (agent, replay_buffer, training_stats, timer); `env` is a
-    DeviceParallelEnv over PendulumEnv / MountainCarContinuousEnv, a DeviceModuleEnv over a Box plug-in, or a HostParallelEnv.  training_stats carries the fields of SACTrainingStats (sac.jl:243-257)."""
+    DeviceParallelEnv over PendulumEnv / MountainCarContinuousEnv, a DeviceModuleEnv over a Box plug-in, or a HostParallelEnv.  training_stats carries the fields of SACTrainingStats (sac.jl:243-257).
+    NormalizeWrapperEnv(DeviceParallelEnv(...)) trains on normalised observations and rewards (dril_sac_normalize_enable); `normalize=dict(...)` gives the same wrapper
+    to any device env — a DeviceModuleEnv has no other way to it — and wins over the env's own keywords.  The statistics stay on `replay_buffer.handle` (norm_get_stats)."""
     if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
+        if normalize is not None:
+            raise NotImplementedError("sac_train_: host envs (HostParallelEnv) are normalised on the host; normalize= wraps device envs")
         return _sac_train_host(agent, env, alg, max_steps, replay_buffer, list(callbacks or []))
     if callbacks:
-        return _sac_train_callbacks(agent, env, alg, max_steps, replay_buffer, list(callbacks))
+        return _sac_train_callbacks(agent, env, alg, max_steps, replay_buffer, list(callbacks), normalize)
     t0 = time.perf_counter()
     rb = replay_buffer or ReplayBuffer(env.observation_space(), env.action_space(), alg.buffer_capacity)     # sac.jl:411
     cfg = make_sac_config(env.env, env.n_envs, alg, agent.layer, seed=env.seed, device=env._kw.get("device", 0), profile_events=env._kw.get("profile_events", False))
     h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
     _monitor_from_env(h, env)
+    _normalize_from_env(h, env, normalize)
     h.set_params(sac_flatten_params(agent.parameters))
     h.set_target_params(agent.q_target_parameters)
     h.set_log_ent_coef(agent.log_ent_coef)
@@ -521,12 +617,14 @@ def _jl_div(a: int, b: int) -> int:
     return q if (a >= 0) == (b >= 0) else -q
 
 
-def _sac_train_callbacks(agent: SACAgent, env, alg: SAC, max_steps: int, replay_buffer: Optional[ReplayBuffer], cbs: list):
+def _sac_train_callbacks(agent: SACAgent, env, alg: SAC, max_steps: int, replay_buffer: Optional[ReplayBuffer], cbs: list, normalize: Optional[dict] = None):
     """train!(agent, replay_buffer, env, alg::SAC, max_steps; callbacks) (sac.jl:428-559) step by step, so that the hooks run where the reference runs them:
     on_training_start (:476-483), on_rollout_start (:488-495), on_step before every env step of the collection (off_policy_collection.jl:44-49), on_rollout_end
     (:508-515), on_training_end (:545-552).  Each gets a dict of the reference's locals; a false return stops the training and — as in the reference — the early
     returns are (agent, replay_buffer, training_stats) without the timer.  Differences: the transitions of a collection that on_step interrupted are already in
-    the device ring (the reference drops that partial rollout), and one env step is one `dril_sac_collect_rollout(1)` (a drain per step: callbacks want the state)."""
+    the device ring (the reference drops that partial rollout), and one env step is one device call (a drain per step: callbacks want the state) —
+    `dril_sac_collect_rollout(1)` for the first step of a collection and `dril_sac_collect_continue(1)` for the others, so that NormalizeWrapperEnv observes once at
+    the collection's start as inside the reference's collect_trajectories: statistics, ring and weights are those of the callback-less loop, bit for bit."""
     hook = lambda name, loc: all(getattr(c, name)(loc) for c in cbs if hasattr(c, name))
     step_hooks = [c for c in cbs if hasattr(c, "on_step")]
     t0 = time.perf_counter()
@@ -535,6 +633,7 @@ def _sac_train_callbacks(agent: SACAgent, env, alg: SAC, max_steps: int, replay_
     h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
     _monitor_from_env(h, env)
+    _normalize_from_env(h, env, normalize)
     h.set_params(sac_flatten_params(agent.parameters)); h.set_target_params(agent.q_target_parameters); h.set_log_ent_coef(agent.log_ent_coef)
     h.env_reset(env.seed)
     E = env.n_envs
@@ -567,7 +666,10 @@ def _sac_train_callbacks(agent: SACAgent, env, alg: SAC, max_steps: int, replay_
                 loc.update(i=i, use_random_actions=use_random)
                 if step_hooks and not all(c.on_step(loc) for c in step_hooks):
                     return agent, rb, ts                                                          # "Collecting rollout stopped due to callback failure", :502-505
-                h.collect_rollout(1, use_random)
+                if i == 1:
+                    h.collect_rollout(1, use_random)
+                else:                                                                             # the same collect_trajectories call: NormalizeWrapperEnv observes once, at its start
+                    h.collect_continue(1, use_random)
             fps = n_steps * E / max(time.perf_counter() - a, 1e-9)
             loc.update(fps=fps, success=True)
             if not hook("on_rollout_end", loc):

@@ -149,6 +149,12 @@ int32_t dril_sac_predict_q(dril_sac_handle* h, const float* obs, const float* ac
 /* ---- collection: collect_rollout!(buffer, agent, alg, env, n_steps; use_random_actions) off_policy_collection.jl:117-136
  * = collect_trajectories :28-96 + push!(buffer, traj) replay_buffer.jl:98-114.  fps = steps / wall time (:126-128) */
 int32_t dril_sac_collect_rollout(dril_sac_handle* h, int32_t n_steps, int32_t use_random_actions, double* fps);
+/* further steps of the collection the previous dril_sac_collect_rollout / dril_sac_collect_continue call left off: for step-granular drivers that run host code
+ * (callbacks' on_step, off_policy_collection.jl:43-49) between the env steps of ONE collect_trajectories.  Without NormalizeWrapperEnv the same as
+ * dril_sac_collect_rollout.  Under it there is no opening observe(env): collect_rollout(1) followed by n - 1 x collect_continue(1) updates the statistics
+ * n_envs * (n + 1) times and writes the bits of collect_rollout(n).  DRIL_ERR_NOT_INITIALISED when the wrapper is on and no collection is in progress (the env
+ * was reset, the statistics were set or the wrapper was switched since the last collected step). */
+int32_t dril_sac_collect_continue(dril_sac_handle* h, int32_t n_steps, int32_t use_random_actions, double* fps);
 /* injected noise for the NEXT collect call only, f32 [step][env][A]: standard normals for policy actions, uniforms in
  * [0,1) for random actions (rand(rng, act_space) = low + u * (high - low)); NULL clears */
 int32_t dril_sac_debug_set_collect_noise(dril_sac_handle* h, const float* noise, size_t count);
@@ -212,6 +218,48 @@ int32_t dril_sac_monitor_enable(dril_sac_handle* h, int32_t window);
 /* log_stats (:64-70): mean return / length over the last min(n, window) finished episodes and their number; n_episodes == 0 leaves the two means untouched.
  * DRIL_ERR_NOT_INITIALISED while the monitor is off. */
 int32_t dril_sac_monitor_get_stats(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes);
+
+/* ---- NormalizeWrapperEnv(env; training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon) around the handle's device envs
+ * (src/environment_wrappers/normalizeWrapperEnv.jl), for every observation width the handle accepts (1 .. 1024): built-in Box envs and device env plug-ins alike.
+ * Statistics, `returns`, normalisation and the ring push stay on the device.  While the wrapper is on, every collection (dril_sac_collect_rollout, every iteration of
+ * dril_sac_train / dril_sac_iterate) begins with observe(env) (off_policy_collection.jl:42): one update of the observation statistics over the current raw
+ * observations, which are re-normalised, then per collected step act! (:139-165: returns = returns * gamma + reward, update of the return statistics, reward /
+ * sqrt(ret_var + epsilon) clipped, returns of finished envs to zero, the terminal observation of a truncated env normalised with the observation statistics as they
+ * are before the following observe) and observe (:123-137: batch mean / uncorrected batch variance over all envs merged by update_from_moments! :28-50 in float32,
+ * (obs - mean) / sqrt(var + epsilon) clipped): obs_count grows by n_envs * (n_steps + 1) per collection, ret_count by n_envs * n_steps.  The ring holds what the
+ * reference's ReplayBuffer would: normalised observation, unprocessed action, normalised reward, flags, normalised next | terminal observation; rows already in the
+ * ring are never re-normalised.  training == 0 freezes both statistics and `returns`; norm_obs / norm_reward switch the two halves independently.  MonitorWrapperEnv
+ * sits inside: its sums are those of raw rewards.  dril_sac_env_reset zeroes `returns`, caches the raw observation and keeps the statistics (reset! :110-121).
+ * dril_sac_env_observe returns the observation the actor will see under the statistics in force and updates nothing (docs/deviations.md).
+ * dril_sac_evaluate_agent runs with the statistics in force, frozen (set_training(eval_env, false) after sync_normalization_stats!, :299-309), reports raw episode
+ * returns and leaves statistics, returns, the cached originals and the current observation as they were.  With the wrapper off a handle enqueues exactly the launches
+ * it did before this verb existed.  The PPO handle's norm_obs / norm_reward on a device env plug-in stay refused (dril_create_with_env_module). */
+typedef struct dril_sac_normalize_config {
+    int32_t training, norm_obs, norm_reward;   /* 1, 1, 1 */
+    float clip_obs, clip_reward;               /* 10, 10 */
+    float gamma, epsilon;                      /* 0.99, 1e-8 */
+    int32_t reserved;
+} dril_sac_normalize_config;
+/* the keyword defaults of normalizeWrapperEnv.jl:71-80 */
+int32_t dril_sac_normalize_config_default(dril_sac_normalize_config* cfg);
+/* a fresh wrapper (mean 0, var 1, count 0, returns 0), after which the handle's current observation is invalid so that the next collection observes through it.  A
+ * configuration that differs from the handle's in `training` at most keeps the wrapper as it is — statistics, returns, current observation — and sets `training`
+ * as dril_sac_normalize_set_training would (a second sac_train_ on a handle that evaluated with training off continues with its statistics).  cfg == NULL switches
+ * the wrapper off (nothing to do when it is off); the next collection then observes the env itself.  DRIL_ERR_UNSUPPORTED on a DRIL_ENV_EXTERNAL handle (host envs
+ * are wrapped on the host), DRIL_ERR_INVALID_ARG for a negative clip or epsilon. */
+int32_t dril_sac_normalize_enable(dril_sac_handle* h, const dril_sac_normalize_config* cfg);
+/* the configuration in force (`training` as dril_sac_normalize_set_training left it) */
+int32_t dril_sac_normalize_get_config(dril_sac_handle* h, dril_sac_normalize_config* cfg);
+/* set_training (:245-249).  This and the verbs below: DRIL_ERR_NOT_INITIALISED while the wrapper is off */
+int32_t dril_sac_normalize_set_training(dril_sac_handle* h, int32_t training);
+/* obs_rms / ret_rms: obs_mean, obs_var hold obs_dim floats */
+int32_t dril_sac_normalize_get_stats(dril_sac_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count);
+/* load_normalization_stats! / sync_normalization_stats! (:280-309): DRIL_ERR_INVALID_ARG for null pointers or negative counts */
+int32_t dril_sac_normalize_set_stats(dril_sac_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count);
+/* get_original_obs / get_original_rewards (:225-226): the raw observation of the latest observe (D x E) and the raw rewards of the latest act! (E); either may be NULL */
+int32_t dril_sac_normalize_get_original(dril_sac_handle* h, float* obs, float* rewards);
+/* env.returns (E): the discounted running return per env behind ret_rms */
+int32_t dril_sac_normalize_get_returns(dril_sac_handle* h, float* returns);
 
 /* ---- evaluate_agent(agent, env; n_eval_episodes, deterministic) (src/evaluation.jl:54-143) with the handle's actor on the handle's envs --------------------
  * reset (env e seeded seed + e), then predict_actions(; deterministic) -> act! -> observe until the first n_eval_episodes episodes have finished, taken in
