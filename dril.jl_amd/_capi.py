@@ -103,6 +103,11 @@ class DrilSacNormalizeConfig(C.Structure):
                 ("gamma", C.c_float), ("epsilon", C.c_float), ("reserved", C.c_int32)]
 
 
+class DrilNormalizeConfig(C.Structure):
+    """struct dril_normalize_config, include/dril_hip.h: NormalizeWrapperEnv around a device env plug-in of a PPO handle (the same keywords)"""
+    _fields_ = list(DrilSacNormalizeConfig._fields_)
+
+
 SAC_ABI_VERSION = 1
 (RB_OBSERVATIONS, RB_ACTIONS, RB_REWARDS, RB_TERMINATED, RB_TRUNCATED, RB_NEXT_OBSERVATIONS) = range(6)
 
@@ -166,6 +171,14 @@ _SIG = {
     "dril_norm_get_stats": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
     "dril_norm_set_stats": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64]),
     "dril_norm_get_original": (C.c_int32, [_P, _P, _P]),
+    "dril_normalize_config_default": (C.c_int32, [C.POINTER(DrilNormalizeConfig)]),
+    "dril_normalize_enable": (C.c_int32, [_P, C.POINTER(DrilNormalizeConfig)]),
+    "dril_normalize_get_config": (C.c_int32, [_P, C.POINTER(DrilNormalizeConfig)]),
+    "dril_normalize_set_training": (C.c_int32, [_P, C.c_int32]),
+    "dril_normalize_get_stats": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "dril_normalize_set_stats": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64]),
+    "dril_normalize_get_original": (C.c_int32, [_P, _P, _P]),
+    "dril_normalize_get_returns": (C.c_int32, [_P, _P]),
     "dril_monitor_get_stats": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "dril_policy_forward": (C.c_int32, [_P, _P, C.c_int64, _P, _P, _P, _P]),
     "dril_evaluate_actions": (C.c_int32, [_P, _P, _P, C.c_int64, _P, _P, _P]),

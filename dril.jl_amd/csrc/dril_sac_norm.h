@@ -1,6 +1,7 @@
 // dril_sac_norm.h — NormalizeWrapperEnv (src/environment_wrappers/normalizeWrapperEnv.jl) around the device envs of a SAC handle, for any observation width the
 // handle accepts (1 .. 1024).  Included by dril_sac.hip inside its anonymous namespace, after the collection kernels it builds on (CollectEnvArgs, PushArgs,
-// sac_env_thread_mu / sac_env_thread_step, phase_stamp).  The PPO path's RmsState (8 dims, 16-column partial tables) is not touched.
+// sac_env_thread_mu / sac_env_thread_step, phase_stamp).  The PPO handle's wrapper on built-in envs (RmsState: 8 dims, 16-column partial tables) is not touched; its
+// wrapper on device env plug-ins (dril_ppo_norm.h) is built like this file and shares dril_norm_math.h with it.
 //
 // One collected step has ONE grid-wide dependency: every env's raw observation -> the merged statistics -> every env's normalised row -> the actor's next forward.
 // So a step is two launches of this file where the plain collection is one:
@@ -15,27 +16,11 @@
 // sum is fixed by the launch shape, so two runs give the same bits.
 #pragma once
 
-constexpr int kNzMaxD = 1024;                    // the widest observation the wrapper takes (dril_sac_normalize_enable refuses more); sizes the apply kernel's LDS
+#include "dril_norm_math.h"                     // kNzMaxD, nz_merge, nz_obs: shared with the PPO handle's wrapper on plug-ins (dril_ppo_norm.h)
 static_assert(kNzMaxD == DRIL_ENV_PLUGIN_MAX_D, "the wrapper takes every observation width a plug-in may have");
 // rows of the partial table of sac_norm_moments_kernel.  Every block of the apply kernel re-reads rows x (2 D + 2) doubles, so for wide rows this trades the moments
 // kernel's parallelism (rows x column tiles workgroups) against that fold; 32 is a choice, not a measured optimum (docs/sac.md: 4 096 envs x 512 dims)
 constexpr int kNzMaxRows = 32;
-
-// update_from_moments! (normalizeWrapperEnv.jl:28-50) in the reference's float32 arithmetic — the arithmetic of rms_merge (dril_kernels.hip)
-__device__ __forceinline__ void nz_merge(float& mean, float& var, long long count, float bmean, float bvar, long long bcount) {
-    if (count == 0) { mean = bmean; var = bvar; return; }
-    const long long tot = count + bcount;
-    const float delta = bmean - mean;
-    const float new_mean = mean + delta * (float)bcount / (float)tot;
-    const float m_a = var * (float)count, m_b = bvar * (float)bcount;
-    const float M2 = m_a + m_b + delta * delta * (float)count * (float)bcount / (float)tot;
-    mean = new_mean; var = M2 / (float)tot;
-}
-// normalize_obs! (:174-179)
-__device__ __forceinline__ float nz_obs(float v, float mean, float var, float eps, float clip) {
-    v = (v - mean) / sqrtf(var + eps);
-    return fminf(fmaxf(v, -clip), clip);
-}
 
 // ---- moments, built-in Box envs (A = 1) -----------------------------------------------------------------------------------------------------------------
 // The twin of sac_collect_env_kernel without the push: the 16 env threads of a block sit in lanes 0 - 15 of wave 0, so the block's 2 D + 2 sums are four xor

@@ -523,6 +523,58 @@ class Handle:
         om = np.ascontiguousarray(obs_mean, np.float32); ov = np.ascontiguousarray(obs_var, np.float32)
         self._chk(self.lib.dril_norm_set_stats(self._h, self._p(om), self._p(ov), int(obs_count), float(ret_mean), float(ret_var), int(ret_count)))
 
+    # NormalizeWrapperEnv around a device env plug-in (dril_normalize_*; built-in envs are wrapped at create through cfg.norm_*)
+    _NORMALIZE_KEYS = ("training", "norm_obs", "norm_reward", "clip_obs", "clip_reward", "gamma", "epsilon")
+
+    def normalize_enable(self, enabled: bool = True, **kw):
+        """NormalizeWrapperEnv(env; training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon) (normalizeWrapperEnv.jl:71-80) around the handle's plug-in
+        envs: a fresh wrapper, or nothing when the handle already has this configuration (`training` apart, which is set); normalize_enable(False) switches it off"""
+        if not enabled:
+            self._chk(self.lib.dril_normalize_enable(self._h, None)); return
+        c = capi.DrilNormalizeConfig()
+        self._chk(self.lib.dril_normalize_config_default(C.byref(c)))
+        for k, v in kw.items():
+            if k not in self._NORMALIZE_KEYS:
+                raise TypeError(f"NormalizeWrapperEnv has no keyword {k!r}")
+            setattr(c, k, int(v) if k in ("training", "norm_obs", "norm_reward") else float(v))
+        self._chk(self.lib.dril_normalize_enable(self._h, C.byref(c)))
+
+    def normalize_config(self) -> dict:
+        """the wrapper's keywords as the handle holds them (dril_normalize_get_config)"""
+        c = capi.DrilNormalizeConfig()
+        self._chk(self.lib.dril_normalize_get_config(self._h, C.byref(c)))
+        return dict(training=bool(c.training), norm_obs=bool(c.norm_obs), norm_reward=bool(c.norm_reward), clip_obs=c.clip_obs, clip_reward=c.clip_reward,
+                    gamma=c.gamma, epsilon=c.epsilon)
+
+    def normalize_set_training(self, training: bool):
+        """set_training(env, training) (normalizeWrapperEnv.jl:245-249)"""
+        self._chk(self.lib.dril_normalize_set_training(self._h, int(bool(training))))
+
+    def normalize_get_stats(self) -> dict:
+        """RunningMeanStd fields of the plug-in wrapper; the keys of norm_get_stats"""
+        om = np.empty(self.D, np.float32); ov = np.empty(self.D, np.float32)
+        oc, rc = C.c_int64(), C.c_int64(); rm, rv = C.c_float(), C.c_float()
+        self._chk(self.lib.dril_normalize_get_stats(self._h, self._p(om), self._p(ov), C.byref(oc), C.byref(rm), C.byref(rv), C.byref(rc)))
+        return dict(obs_mean=om, obs_var=ov, obs_count=oc.value, ret_mean=rm.value, ret_var=rv.value, ret_count=rc.value)
+
+    def normalize_set_stats(self, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count):
+        om = np.ascontiguousarray(obs_mean, np.float32).reshape(-1); ov = np.ascontiguousarray(obs_var, np.float32).reshape(-1)
+        if om.size != self.D or ov.size != self.D:
+            raise ValueError(f"obs_mean / obs_var must hold {self.D} values")
+        self._chk(self.lib.dril_normalize_set_stats(self._h, self._p(om), self._p(ov), int(obs_count), float(ret_mean), float(ret_var), int(ret_count)))
+
+    def normalize_get_original(self):
+        """-> (get_original_obs (E, D), get_original_rewards (E)), normalizeWrapperEnv.jl:220-222"""
+        obs = np.empty((self.E, self.D), np.float32); rew = np.empty(self.E, np.float32)
+        self._chk(self.lib.dril_normalize_get_original(self._h, self._p(obs), self._p(rew)))
+        return obs, rew
+
+    def normalize_get_returns(self) -> np.ndarray:
+        """env.returns: the discounted running return per env behind ret_rms"""
+        r = np.empty(self.E, np.float32)
+        self._chk(self.lib.dril_normalize_get_returns(self._h, self._p(r)))
+        return r
+
     # policy on host batches
     def policy_forward(self, obs: np.ndarray, noise: Optional[np.ndarray] = None):
         obs = np.ascontiguousarray(obs, np.float32)
@@ -764,15 +816,23 @@ class DeviceParallelEnv:
     # binding: one handle carries env + agent + alg state; (re)created when the alg/layer shape changes
     def bind(self, alg: PPO, layer: Optional[ActorCriticLayer] = None) -> Handle:
         key = (tuple(sorted(asdict(alg).items())), None if layer is None else (tuple(layer.hidden_dims), layer.log_std_init, getattr(layer, "activation", "tanh")),
-               None if self._kw["normalize"] is None else tuple(sorted(self._kw["normalize"].items())), self._kw["monitor_window"])
+               None if self._kw["normalize"] is None else tuple(sorted(self._kw["normalize"].items())), self._kw["monitor_window"], self._bind_extra())
         if self.handle is None or key != self._bound_key:
             if self.handle is not None:
                 self.handle.close()
             cfg = make_config(self.env, self.n_envs, alg, layer, seed=self.seed, **self._kw)
             self.handle = Handle(cfg, env_module=getattr(self.env, "code_object_path", None))
+            self._after_create(self.handle)
             self.handle.env_reset(self.seed)  # Random.seed!(env, seed) + reset!(env)
             self._bound_key = key
         return self.handle
+
+    def _bind_extra(self):
+        """what a subclass adds to bind's key"""
+        return None
+
+    def _after_create(self, h: Handle):
+        """verbs a subclass applies to a freshly created handle, before its first reset"""
 
     def _h(self) -> Handle:
         return self.handle or self.bind(PPO(n_steps=1, batch_size=self.n_envs * max(1, self._kw["world_size"])))
@@ -831,15 +891,35 @@ class ModuleEnv:
 class DeviceModuleEnv(DeviceParallelEnv):
     """`n_envs` copies of the CALLER'S OWN env, living on the device: the env is a gfx950 code object built from include/device/dril_env_plugin.h
     (`hipcc --genco`), loaded by the library and stepped by its own kernels where a built-in env's kernels would run — no host env anywhere in the loop.
-    Everything a DeviceParallelEnv does works unchanged (Agent, train_, collect_rollout_, MonitorWrapperEnv, callbacks, evaluate_agent, checkpoints);
-    NormalizeWrapperEnv is refused by the library (docs/external_envs.md)."""
+    Everything a DeviceParallelEnv does works unchanged (Agent, train_, collect_rollout_, MonitorWrapperEnv, callbacks, evaluate_agent, checkpoints).
+
+    `normalize=dict(training=..., norm_obs=..., norm_reward=..., clip_obs=..., clip_reward=..., gamma=..., epsilon=...)` (any subset; `{}` = the defaults of
+    normalizeWrapperEnv.jl:71-80) puts NormalizeWrapperEnv around the envs for any observation width: the handle is created plain and the wrapper is switched on with
+    dril_normalize_enable, so train_, collect_rollout_, evaluate_agent (frozen statistics, raw episode returns), unnormalize_obs_ / unnormalize_rewards_ and
+    get_original_obs / get_original_rewards honour it.  The keyword takes part in bind's key.  The statistics live in the handle: a bind that has to re-create the
+    handle (another alg or layer shape) starts a FRESH wrapper — a caller who wants to carry the statistics over saves them before
+    (`env.handle.normalize_get_stats()`) and loads them after (`env.handle.normalize_set_stats(**st)`).
+    The function NormalizeWrapperEnv(DeviceModuleEnv(...)) stays refused: it works through cfg.norm_*, which size the built-in envs' tables (docs/external_envs.md)."""
 
     def __init__(self, code_object_path, n_envs: int, *, seed: int = 42, device: int = 0, max_steps: Optional[int] = None, action_start: int = 1,
-                 fixed_length_episodes: bool = False, rank: int = 0, world_size: int = 1, profile_events: bool = False):
+                 fixed_length_episodes: bool = False, rank: int = 0, world_size: int = 1, profile_events: bool = False, normalize: Optional[dict] = None):
         info = describe_env_module(code_object_path, device)
         env = ModuleEnv(os.fspath(code_object_path), info, int(max_steps) if max_steps else info["episode_len"], action_start)
         super().__init__(env, n_envs, seed=seed, fixed_length_episodes=fixed_length_episodes, device=device, rank=rank, world_size=world_size,
                          profile_events=profile_events)
+        if normalize is not None:
+            bad = [k for k in normalize if k not in Handle._NORMALIZE_KEYS]
+            if bad:
+                raise TypeError(f"NormalizeWrapperEnv has no keyword {bad[0]!r}")
+            normalize = {**dict(training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8), **normalize}
+        self.module_normalize = normalize
+
+    def _bind_extra(self):
+        return None if self.module_normalize is None else tuple(sorted(self.module_normalize.items()))
+
+    def _after_create(self, h: Handle):
+        if self.module_normalize is not None:
+            h.normalize_enable(**self.module_normalize)
 
 
 class HostParallelEnv:
@@ -974,14 +1054,22 @@ def NormalizeWrapperEnv(env: DeviceParallelEnv, *, training: bool = True, norm_o
                                 clip_reward=clip_reward, gamma=gamma, epsilon=epsilon)
     if env.handle is not None:
         env.handle.close(); env.handle = None
-    if isinstance(env, DeviceModuleEnv) and (norm_obs or norm_reward):   # not available for plug-in envs: fail here, with the library's message
-        env._h()
+    if isinstance(env, DeviceModuleEnv) and (norm_obs or norm_reward):   # cfg.norm_* are the built-in envs': fail here, with the library's message and the way that works
+        try:
+            env._h()
+        except DrilError as e:
+            raise DrilError(e.code, str(e).split("] ", 1)[-1] + " — in Python: DeviceModuleEnv(path, n_envs, normalize=dict(...))") from None
     return env
+
+
+def _normalize_kw(env: DeviceParallelEnv) -> Optional[dict]:
+    """the wrapper's keywords: cfg.norm_* of a built-in env, the `normalize` keyword of a DeviceModuleEnv"""
+    return env._kw["normalize"] if env._kw["normalize"] is not None else getattr(env, "module_normalize", None)
 
 
 def unnormalize_obs_(obs: np.ndarray, env: DeviceParallelEnv) -> np.ndarray:
     """unnormalize_obs!(obs, env) (normalizeWrapperEnv.jl:200-210): obs * sqrt(var + eps) + mean with the wrapper's running statistics, in place"""
-    kw = env._kw["normalize"]
+    kw = _normalize_kw(env)
     if kw is None or not kw["norm_obs"]:
         return obs
     st = env.handle.norm_get_stats()
@@ -991,7 +1079,7 @@ def unnormalize_obs_(obs: np.ndarray, env: DeviceParallelEnv) -> np.ndarray:
 
 def unnormalize_rewards_(rewards: np.ndarray, env: DeviceParallelEnv) -> np.ndarray:
     """unnormalize_rewards!(rewards, env) (normalizeWrapperEnv.jl:212-218): rewards * sqrt(var(returns) + eps), in place"""
-    kw = env._kw["normalize"]
+    kw = _normalize_kw(env)
     if kw is None or not kw["norm_reward"]:
         return rewards
     rewards *= np.sqrt(np.float32(env.handle.norm_get_stats()["ret_var"]) + np.float32(kw["epsilon"]))

@@ -126,9 +126,9 @@ function describe_env_module(path::AbstractString, device::Integer = 0)
     name = String(buf[537:(536 + something(findfirst(==(0x00), buf[537:end]), 65) - 1)])
     return (path = String(path), state_dim = Int(i32[1]), obs_dim = Int(i32[2]), action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]), low = low, high = high, name = name)
 end
-"`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv for SAC"
+"`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv, for PPO and SAC alike"
 function OnDeviceModule(path::AbstractString, n_envs::Integer; max_steps::Union{Nothing, Integer} = nothing, seed::Integer = 42, device::Integer = 0, monitor_window::Integer = 0,
-        normalize::Union{Nothing, NamedTuple} = nothing)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (train! / evaluate_agent with alg::SAC); the PPO handle refuses them for a plug-in
+        normalize::Union{Nothing, NamedTuple} = nothing)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (dril_sac_normalize_enable) and by the PPO handle (dril_normalize_enable, applied in bind!)
     info = describe_env_module(path, device)
     env = DeviceParallelEnv(:Module, n_envs; max_steps = something(max_steps, info.episode_len), seed = seed, device = device, monitor_window = monitor_window, normalize = normalize)
     MODULE_ENVS[env] = info
@@ -158,7 +158,7 @@ function make_config(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int}, log_
     start = is_discrete(env) ? Int32(action_space(env).start) : Int32(1)
     nz = env.normalize
     nget(k, d) = isnothing(nz) ? d : get(nz, k, d)
-    on = isnothing(nz) ? Int32(0) : Int32(1)
+    on = (isnothing(nz) || env.kind === :Module) ? Int32(0) : Int32(1)   # cfg.norm_* wrap the built-in envs; a plug-in is wrapped after create (normalize_enable! in bind!)
     return DrilConfig(ABI_VERSION, ENV_KINDS[env.kind], env.n_envs, alg.n_steps, hidden[1], hidden[min(2, end)], env.max_steps,
         Int32(env.fixed_length_episodes), start, alg.gamma, alg.gae_lambda, alg.clip_range, cvf, hcvf, alg.ent_coef,
         alg.vf_coef, mgn, hmgn, tkl, htkl, Int32(alg.normalize_advantage), alg.batch_size, alg.epochs, alg.learning_rate,
@@ -168,7 +168,40 @@ function make_config(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int}, log_
         env.seed, env.device, 0, 1, 8, env.monitor_window, 0, 0, 0, 0.0f0, 0.0f0, layer_fields(hidden, act)..., ntuple(_ -> Int32(0), 1))   # profile_events = 8: HIP-event kernel times fill the TimerOutput sections (per-optimiser-step kernels bracketed at every 8th launch: bracketing all of them costs 1 - 2 %)
 end
 
-"(re)create the handle when the algorithm / layer shape changes; Random.seed!(env, seed) + reset!(env) follow"
+# struct dril_normalize_config (include/dril_hip.h): the keywords of NormalizeWrapperEnv (normalizeWrapperEnv.jl:71-80) around a device env plug-in of a PPO handle
+struct DrilNormalizeConfig
+    training::Int32; norm_obs::Int32; norm_reward::Int32
+    clip_obs::Float32; clip_reward::Float32
+    gamma::Float32; epsilon::Float32
+    reserved::Int32
+end
+# NormalizeWrapperEnv around the plug-in envs of a PPO handle from the env's `normalize` keywords (missing keys take the reference's defaults).  Like the rest of this
+# shim the ccalls below are checked statically (tools/check_shim.py: symbol, arity, struct layout) and have not been executed: no Julia runtime in the build image.
+function normalize_enable!(h::Ptr{Cvoid}, nz::NamedTuple)
+    g(k, d) = get(nz, k, d)
+    cfg = Ref(DrilNormalizeConfig(Int32(g(:training, true)), Int32(g(:norm_obs, true)), Int32(g(:norm_reward, true)),
+        Float32(g(:clip_obs, 10.0f0)), Float32(g(:clip_reward, 10.0f0)), Float32(g(:gamma, 0.99f0)), Float32(g(:epsilon, 1.0f-8)), Int32(0)))
+    check(ccall((:dril_normalize_enable, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilNormalizeConfig}), h, cfg), h)
+    return h
+end
+normalize_set_training!(h::Ptr{Cvoid}, training::Bool) =
+    (check(ccall((:dril_normalize_set_training, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(training)), h); h)
+# obs_rms / ret_rms of that wrapper: the fields of save_normalization_stats (normalizeWrapperEnv.jl:261-277)
+function normalize_stats(h::Ptr{Cvoid}, D::Integer)
+    om = Vector{Float32}(undef, D); ov = Vector{Float32}(undef, D)
+    oc = Ref{Int64}(0); rc = Ref{Int64}(0); rm = Ref{Float32}(0); rv = Ref{Float32}(0)
+    GC.@preserve om ov check(ccall((:dril_normalize_get_stats, LIB[]), Int32,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ref{Int64}, Ref{Float32}, Ref{Float32}, Ref{Int64}), h, om, ov, oc, rm, rv, rc), h)
+    return (; obs_mean = om, obs_var = ov, obs_count = oc[], ret_mean = rm[], ret_var = rv[], ret_count = rc[])
+end
+function set_normalize_stats!(h::Ptr{Cvoid}, st)
+    om = Vector{Float32}(st.obs_mean); ov = Vector{Float32}(st.obs_var)
+    GC.@preserve om ov check(ccall((:dril_normalize_set_stats, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int64, Float32, Float32, Int64),
+        h, om, ov, Int64(st.obs_count), Float32(st.ret_mean), Float32(st.ret_var), Int64(st.ret_count)), h)
+    return h
+end
+
+"(re)create the handle when the algorithm / layer shape changes; Random.seed!(env, seed) + reset!(env) follow.  A plug-in env built with `normalize = (; ...)` gets a FRESH NormalizeWrapperEnv with every new handle: carry statistics over with `normalize_stats` / `set_normalize_stats!`"
 function bind!(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int} = [64, 64], log_std_init::Float32 = 0.0f0, act::Int32 = Int32(0))
     key = (alg, hidden, log_std_init, act)
     if env.handle == C_NULL || env.bound != key
@@ -177,6 +210,7 @@ function bind!(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int} = [64, 64],
         h = Ref{Ptr{Cvoid}}(C_NULL)
         if env.kind === :Module                                  # a device env plug-in: the library loads the code object itself
             check(ccall((:dril_create_with_env_module, LIB[]), Int32, (Ref{DrilConfig}, Cstring, Ref{Ptr{Cvoid}}), cfg, MODULE_ENVS[env].path, h))
+            env.normalize === nothing || normalize_enable!(h[], env.normalize)   # train!(agent, env, alg::PPO, ...) and evaluate_agent then run under the wrapper (evaluation: frozen, raw returns)
         else
             check(ccall((:dril_create, LIB[]), Int32, (Ref{DrilConfig}, Ref{Ptr{Cvoid}}), cfg, h))
         end

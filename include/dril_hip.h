@@ -74,8 +74,9 @@ enum dril_env_kind {
      * its own into a gfx950 code object (hipcc --genco) and loaded with the HIP module API by dril_create_with_env_module below.  Spaces, bounds and the default
      * time limit come from the code object's descriptor; its three kernels stand where env_reset_kernel / env_observe_kernel / env_step_kernel stand for a built-in
      * kind, so every device-env verb works: dril_env_*, dril_collect_rollout (step-granular: policy launches + ONE env launch per step), dril_train,
-     * dril_evaluate_agent, monitor_window.  Always on the generic kernels (any hidden_dims).  Refused: norm_obs / norm_reward (the running-moment tables hold 8
-     * observation dims), the dril_ext_* verbs.  SAC on a Box plug-in is available through dril_sac_create_with_env_module (dril_sac.h).  dril_create and
+     * dril_evaluate_agent, monitor_window.  Always on the generic kernels (any hidden_dims).  NormalizeWrapperEnv arrives as a verb on the created handle,
+     * dril_normalize_enable below, for any observation width; cfg.norm_obs / cfg.norm_reward at create stay refused (they size the built-in envs' 8-dim tables), and
+     * so do the dril_ext_* verbs.  SAC on a Box plug-in is available through dril_sac_create_with_env_module (dril_sac.h).  dril_create and
      * dril_sac_create themselves refuse this kind: they have no code object to load.  docs/external_envs.md */
     DRIL_ENV_MODULE = 8
 };
@@ -257,6 +258,54 @@ int32_t dril_norm_set_stats(dril_handle* h, const float* obs_mean, const float* 
 /* get_original_obs(env) / get_original_rewards(env) (normalizeWrapperEnv.jl:220-222): the un-normalised observations (D x E) of the last
  * observe and the un-normalised rewards (E) of the last act! through the step-granular verbs; either pointer may be NULL */
 int32_t dril_norm_get_original(dril_handle* h, float* obs, float* rewards);
+/* The three verbs above on a DRIL_ENV_MODULE handle: DRIL_ERR_UNSUPPORTED while its wrapper is off (as before dril_normalize_enable existed); with the wrapper on
+ * they forward to dril_normalize_get_stats / _set_stats / _get_original below, so host code written for the built-in envs reads a wrapped plug-in unchanged. */
+
+/* ---- NormalizeWrapperEnv(env; training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon) around a DEVICE ENV PLUG-IN (DRIL_ENV_MODULE), for every
+ * observation width a plug-in may have (1 .. 1024).  The verb family reads like dril_sac_normalize_* (dril_sac.h).  Built-in envs are wrapped at create
+ * (cfg.norm_*) and are not touched by it.  With the wrapper on, every device-env verb honours it with the reference's semantics:
+ *   dril_collect_rollout / dril_train   the opening observe updates the observation statistics over the current raw observations (trajectory.jl:32); then per step
+ *       act! (normalizeWrapperEnv.jl:139-165: returns = returns * gamma + reward, update of the return statistics, reward / sqrt(ret_var + epsilon) clipped, the
+ *       terminal observation of a truncated env normalised with the observation statistics as they are before the following observe, returns of finished envs to
+ *       zero) and observe (:123-137: batch mean / uncorrected batch variance over all envs merged by update_from_moments! :28-50 in float32, (obs - mean) /
+ *       sqrt(var + epsilon) clipped).  Row t of the rollout buffer holds the normalised observation and reward, DRIL_BUF_BOOTSTRAP of a truncated step is
+ *       V(normalised terminal observation), DRIL_BUF_LAST_VALUES is V of the normalised last observation.  obs_count grows by n_envs * (n_steps + 1) per rollout
+ *       and ret_count by n_envs * n_steps.  Two launches more per env step than the unwrapped plug-in path; nothing leaves the device.
+ *   dril_env_observe(update_stats) / dril_env_step   observe / act! of the wrapper; dril_env_reset zeroes `returns`, caches the raw observation and keeps the
+ *       statistics (reset! :110-121).
+ *   MonitorWrapperEnv (monitor_window) sits inside: its sums are those of raw rewards.
+ *   dril_evaluate_agent   runs with the statistics in force, frozen, reports RAW episode returns and leaves statistics, `returns` and the cached originals as they
+ *       were (the envs themselves are reset, as by every dril_evaluate_agent).
+ *   world_size > 1   the batch moments cover every env of the job: one all-reduce of 2 obs_dim + 2 doubles per statistics update, the identical merge with
+ *       n = world_size * n_envs on every rank (the counts grow by that n), statistics bit-identical across ranks.
+ * training == 0 freezes both statistics and `returns`; norm_obs / norm_reward switch the two halves independently.  With the wrapper off a handle enqueues exactly
+ * the launches it did before this family existed. */
+typedef struct dril_normalize_config {
+    int32_t training, norm_obs, norm_reward;   /* 1, 1, 1 */
+    float clip_obs, clip_reward;               /* 10, 10 */
+    float gamma, epsilon;                      /* 0.99, 1e-8 */
+    int32_t reserved;
+} dril_normalize_config;
+/* the keyword defaults of normalizeWrapperEnv.jl:71-80 */
+int32_t dril_normalize_config_default(dril_normalize_config* cfg);
+/* a fresh wrapper: mean 0, var 1, counts 0, returns 0.  A configuration that differs from the handle's in `training` at most keeps the wrapper as it is —
+ * statistics and returns — and sets `training`.  cfg == NULL switches the wrapper off (nothing to do when it is off).  DRIL_ERR_INVALID_ARG for a negative clip or
+ * epsilon; DRIL_ERR_UNSUPPORTED on a handle that is not DRIL_ENV_MODULE: a built-in env is wrapped with cfg.norm_obs / cfg.norm_reward at create, the envs of
+ * DRIL_ENV_EXTERNAL are wrapped on the host. */
+int32_t dril_normalize_enable(dril_handle* h, const dril_normalize_config* cfg);
+/* the configuration in force (`training` as dril_normalize_set_training left it).  This and the verbs below: DRIL_ERR_NOT_INITIALISED while the wrapper is off on a
+ * plug-in handle, DRIL_ERR_UNSUPPORTED on any other handle */
+int32_t dril_normalize_get_config(dril_handle* h, dril_normalize_config* cfg);
+/* set_training (:245-249) */
+int32_t dril_normalize_set_training(dril_handle* h, int32_t training);
+/* obs_rms / ret_rms: obs_mean, obs_var hold obs_dim floats; any out pointer may be NULL */
+int32_t dril_normalize_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count);
+/* load_normalization_stats! (:280-297): DRIL_ERR_INVALID_ARG for null pointers or negative counts */
+int32_t dril_normalize_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count);
+/* get_original_obs / get_original_rewards (:220-222): the raw observation of the latest observe (D x E) and the raw rewards of the latest act! (E); either may be NULL */
+int32_t dril_normalize_get_original(dril_handle* h, float* obs, float* rewards);
+/* env.returns (E): the discounted running return per env behind ret_rms */
+int32_t dril_normalize_get_returns(dril_handle* h, float* returns);
 
 /* MonitorWrapperEnv: mean return / length over the last `monitor_window` finished episodes (log_stats, monitorWrapperEnv.jl:64-70)
  * and the number of episodes currently in the window; rewards are the RAW env rewards (the monitor sits inside the normaliser) */

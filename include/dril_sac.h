@@ -233,7 +233,7 @@ int32_t dril_sac_monitor_get_stats(dril_sac_handle* h, float* ep_rew_mean, float
  * dril_sac_env_observe returns the observation the actor will see under the statistics in force and updates nothing (docs/deviations.md).
  * dril_sac_evaluate_agent runs with the statistics in force, frozen (set_training(eval_env, false) after sync_normalization_stats!, :299-309), reports raw episode
  * returns and leaves statistics, returns, the cached originals and the current observation as they were.  With the wrapper off a handle enqueues exactly the launches
- * it did before this verb existed.  The PPO handle's norm_obs / norm_reward on a device env plug-in stay refused (dril_create_with_env_module). */
+ * it did before this verb existed.  The PPO handle wraps a device env plug-in through the twin family dril_normalize_* (dril_hip.h). */
 typedef struct dril_sac_normalize_config {
     int32_t training, norm_obs, norm_reward;   /* 1, 1, 1 */
     float clip_obs, clip_reward;               /* 10, 10 */

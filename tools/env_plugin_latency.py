@@ -3,6 +3,7 @@
   (a) the CartPole twin plug-in        policy launches + ONE plug-in step launch per env step
   (b) built-in CartPole, DRIL_FORCE_GENERIC=1   policy launches + norm_step_kernel + norm_apply_kernel
   (c) reacher3 plug-in (D = 12, S = 9, A = 3)
+  (d) reacher3 plug-in under NormalizeWrapperEnv (dril_normalize_enable)   (c) + ppo_norm_moments_kernel + ppo_norm_apply_kernel per env step
 hidden [64,64], T = 32 steps per rollout, E = 64 .. 65 536.  Per rollout: wall time around dril_collect_rollout and the library's HIP-event time of the
 rollout class (cfg.profile_events); median and min..max over the rollouts after warm-up, divided by T.   usage: python tools/env_plugin_latency.py [rollouts=20]"""
 import os, sys, time
@@ -17,13 +18,15 @@ R = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 T = 32
 
 
-def measure(label, kind, E, module=None, force_generic=False):
+def measure(label, kind, E, module=None, force_generic=False, normalize=False):
     c = capi.default_config(kind)
     c.n_envs, c.n_steps, c.batch_size, c.epochs, c.profile_events = E, T, E * T, 1, 1
     if force_generic:
         os.environ["DRIL_FORCE_GENERIC"] = "1"
     h = pkg.Handle(c, env_module=module)
     os.environ.pop("DRIL_FORCE_GENERIC", None)
+    if normalize:
+        h.normalize_enable()
     h.set_params((np.random.default_rng(0).standard_normal(h.P) * 0.2).astype(np.float32))
     h.env_reset(1)
     wall, dev = [], []
@@ -42,3 +45,4 @@ for E in (64, 1024, 16384, 65536):
     measure("(a) CartPole twin plug-in", capi.ENV_MODULE, E, module=ROOT / "examples" / "envs" / "cartpole_plugin.hsaco")
     measure("(b) built-in CartPole, generic", capi.ENV_CARTPOLE, E, force_generic=True)
     measure("(c) reacher3 plug-in", capi.ENV_MODULE, E, module=ROOT / "examples" / "envs" / "reacher3_plugin.hsaco")
+    measure("(d) reacher3 plug-in, normalised", capi.ENV_MODULE, E, module=ROOT / "examples" / "envs" / "reacher3_plugin.hsaco", normalize=True)
