@@ -97,15 +97,14 @@ class DrilSacStats(C.Structure):
                 ("entropy_coefficient", C.c_float), ("grad_norm", C.c_float), ("has_entropy_loss", C.c_int32), ("reserved", C.c_int32)]
 
 
-class DrilSacNormalizeConfig(C.Structure):
-    """struct dril_sac_normalize_config, include/dril_sac.h (the keywords of NormalizeWrapperEnv, normalizeWrapperEnv.jl:71-80)"""
+class DrilNormalizeConfig(C.Structure):
+    """struct dril_normalize_config (include/dril_hip.h) and struct dril_sac_normalize_config (include/dril_sac.h): the keywords of NormalizeWrapperEnv,
+    normalizeWrapperEnv.jl:71-80, in one layout for both verb families"""
     _fields_ = [("training", C.c_int32), ("norm_obs", C.c_int32), ("norm_reward", C.c_int32), ("clip_obs", C.c_float), ("clip_reward", C.c_float),
                 ("gamma", C.c_float), ("epsilon", C.c_float), ("reserved", C.c_int32)]
 
 
-class DrilNormalizeConfig(C.Structure):
-    """struct dril_normalize_config, include/dril_hip.h: NormalizeWrapperEnv around a device env plug-in of a PPO handle (the same keywords)"""
-    _fields_ = list(DrilSacNormalizeConfig._fields_)
+DrilSacNormalizeConfig = DrilNormalizeConfig
 
 
 SAC_ABI_VERSION = 1

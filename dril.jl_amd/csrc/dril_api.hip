@@ -17,6 +17,7 @@
 
 #include "../../include/dril_hip.h"
 #include "dril_internal.h"
+#include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper on plug-ins shares with the SAC handle's (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_env_module.h"   // the plug-in loader shared with dril_sac.hip (and, through it, DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with)
 
 using namespace dril;
@@ -137,11 +138,10 @@ struct dril_handle {
     float* ext_stage_rew = nullptr; uint8_t* ext_stage_flags = nullptr;   // pinned [T][E] staging: dril_ext_record returns without draining the stream
     // DRIL_ENV_MODULE: a device env plug-in (include/device/dril_env_plugin.h) loaded as a HIP module; its three kernels stand in for env_reset / env_observe / env_step_kernel
     bool module = false; hipModule_t env_module = nullptr; hipFunction_t mod_reset = nullptr, mod_observe = nullptr, mod_step = nullptr; DrilEnvPluginDesc mod_desc{};
-    // NormalizeWrapperEnv around a plug-in env (dril_normalize_enable; kernels: dril_ppo_norm.h).  pn_stats: the ping-pong pair [2][mean D | var D | ret_mean ret_var],
-    // pn_cur the half in force; the counts are host integers.  The wrapper's other arrays are the handle's own: disc_returns (`returns`), e_obs_raw / e_rew (old_obs /
-    // old_rewards: dril_normalize_get_original), e_rew_n (the rewards dril_env_step delivers)
-    bool pn_on = false; dril_normalize_config pn_cfg{}; int pn_cur = 0, pn_rows_cap = 0; int64_t pn_obs_count = 0, pn_ret_count = 0;
-    float* pn_stats = nullptr; double *pn_partials = nullptr, *pn_red = nullptr;
+    // NormalizeWrapperEnv around a plug-in env (dril_normalize_enable; kernels: dril_norm_wrap.h, dril_ppo_norm.h).  pn_red: the one row a data-parallel job all-reduces.
+    // The wrapper's other arrays are the handle's own: disc_returns (`returns`), e_obs_raw / e_rew (old_obs / old_rewards: dril_normalize_get_original), e_rew_n (the
+    // rewards dril_env_step delivers)
+    NormWrap pn; int pn_rows_cap = 0; double* pn_red = nullptr;
     void* comm = nullptr;
     LoopGroup* loop = nullptr;   // debug loopback communicator (dril_debug_comm_loopback)
     int64_t allreduce_calls = 0;
@@ -364,72 +364,64 @@ int global_partials(dril_handle* h, bool update, const double*& partials, int& n
 
 // ---- NormalizeWrapperEnv around a device env plug-in (dril_normalize_enable) ----
 #include "dril_ppo_norm.h"
-float* pn_half(dril_handle* h, int i) { return h->pn_stats + (size_t)i * (2 * h->D + 2); }
-void pn_free(dril_handle* h) {
-    void* ptrs[] = {h->pn_stats, h->pn_partials, h->pn_red};
-    for (void* p : ptrs) if (p) hipFree(p);
-    h->pn_stats = nullptr; h->pn_partials = h->pn_red = nullptr;
-    h->pn_on = false; h->pn_cur = 0; h->pn_obs_count = h->pn_ret_count = 0;
-}
-// ppo_norm_moments_kernel over e_obs_raw (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
+void pn_free(dril_handle* h) { h->pn.release(); if (h->pn_red) hipFree(h->pn_red); h->pn_red = nullptr; }
+// norm_moments_kernel over e_obs_raw (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
 int pn_moments(dril_handle* h, bool obs, bool ret, int* rows) {
     const int E = h->cfg.n_envs, D = h->D;
     *rows = pn_rows(E, D, h->pn_rows_cap);
     const int R = (E + *rows - 1) / *rows;
     *rows = (E + R - 1) / R;
-    const PnMomArgs m{E, D, R, obs ? h->e_obs_raw : nullptr, ret ? h->e_rew : nullptr, h->disc_returns, h->pn_cfg.gamma, h->pn_partials};
-    hipLaunchKernelGGL(ppo_norm_moments_kernel, dim3(*rows, obs ? pn_tiles(D) : 1), dim3(256), 0, h->stream, m);
+    const NormMomArgs m{E, D, R, obs ? h->e_obs_raw : nullptr, ret ? h->e_rew : nullptr, h->disc_returns, h->pn.cfg.gamma, h->pn.partials};
+    hipLaunchKernelGGL(norm_moments_kernel<kPnTile>, dim3(*rows, obs ? pn_tiles(D) : 1), dim3(256), 0, h->stream, m);
     HIPCHK(h, hipGetLastError());
     return DRIL_OK;
 }
-// ppo_norm_apply_kernel; a launch that updates writes the other half of the pair, which is then the one in force.  Data-parallel jobs: the batch moments cover every
-// env of the job (global_partials does the same for the built-in envs' 16 columns) — this rank's table folded to one row of 2 D + 2 doubles, ONE all-reduce of that
-// row, and every rank applies the identical merge with n = world * E, so the statistics stay bit-identical across ranks
-int pn_apply(dril_handle* h, PnApplyArgs a, int rows, bool upd_obs, bool upd_ret) {
+// ppo_norm_apply_kernel.  Data-parallel jobs: the batch moments cover every env of the job (global_partials does the same for the built-in envs' 16 columns) — this
+// rank's table folded to one row of 2 D + 2 doubles, ONE all-reduce of that row, and every rank applies the identical merge with n = world * E, so the statistics
+// stay bit-identical across ranks
+int pn_apply(dril_handle* h, PnApplyArgs p, int rows, bool upd_obs, bool upd_ret) {
+    NormWrapArgs& a = p.w;
     const int E = h->cfg.n_envs, D = h->D, C = 2 * D + 2;
-    const bool upd = upd_obs || upd_ret;
     const int world = comm_ready(h) ? h->cfg.world_size : 1;
-    a.E = E; a.D = D; a.rows = rows; a.n = E; a.partials = upd ? h->pn_partials : nullptr;
-    if (upd && (world > 1 || (comm_ready(h) && h->force_allreduce))) {
-        hipLaunchKernelGGL(ppo_norm_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, h->stream, h->pn_partials, rows, C, h->pn_red);
+    h->pn.fill(a, upd_obs, upd_ret, E);
+    a.E = E; a.rows = rows;
+    if ((upd_obs || upd_ret) && (world > 1 || (comm_ready(h) && h->force_allreduce))) {
+        hipLaunchKernelGGL(ppo_norm_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, h->stream, h->pn.partials, rows, C, h->pn_red);
         HIPCHK(h, hipGetLastError());
         int rc = rccl_allreduce(h, h->pn_red, (size_t)C, kNcclFloat64); if (rc) return rc;
         a.partials = h->pn_red; a.rows = 1; a.n = (long long)E * world;
     }
     const int W = D > kPnTile ? kPnTile : D;
     a.epb = std::max(std::max(1, 4096 / W), (E + 255) / 256);
-    a.upd_obs = upd_obs; a.upd_ret = upd_ret; a.norm_obs = h->pn_cfg.norm_obs; a.norm_reward = h->pn_cfg.norm_reward;
-    a.obs_count = h->pn_obs_count; a.ret_count = h->pn_ret_count; a.clip_obs = h->pn_cfg.clip_obs; a.clip_reward = h->pn_cfg.clip_reward; a.eps = h->pn_cfg.epsilon;
-    a.st_in = pn_half(h, h->pn_cur); a.st_out = upd ? pn_half(h, h->pn_cur ^ 1) : nullptr;
-    hipLaunchKernelGGL(ppo_norm_apply_kernel, dim3((E + a.epb - 1) / a.epb, pn_tiles(D)), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(ppo_norm_apply_kernel, dim3((E + a.epb - 1) / a.epb, pn_tiles(D)), dim3(256), 0, h->stream, p);
     HIPCHK(h, hipGetLastError());
-    if (upd) { h->pn_cur ^= 1; if (upd_obs) h->pn_obs_count += a.n; if (upd_ret) h->pn_ret_count += a.n; }
+    h->pn.commit(a);
     return DRIL_OK;
 }
 // observe(env) of the wrapper (:123-137): the plug-in's observe kernel into e_obs_raw, then moments + apply into e_obs
 int pn_observe(dril_handle* h, bool update_stats) {
     HIPCHK(h, env_observe_any(h, h->e_obs_raw));
-    const bool upd = update_stats && h->pn_cfg.training && h->pn_cfg.norm_obs;
+    const bool upd = update_stats && h->pn.cfg.training && h->pn.cfg.norm_obs;
     int rows = 0;
     if (upd) { int rc = pn_moments(h, true, false, &rows); if (rc) return rc; }
-    PnApplyArgs a{}; a.raw = h->e_obs_raw; a.obs_out = h->e_obs;
+    PnApplyArgs a{}; a.w.raw = h->e_obs_raw; a.w.obs_out = h->e_obs;
     return pn_apply(h, a, rows, upd, false);
 }
 // act!(env, actions) of the wrapper (:139-165) through the E-sized per-step arrays: raw rewards stay in e_rew, the delivered ones go to rew_out
 int pn_step(dril_handle* h, const void* actions, float* rew_out) {
     HIPCHK(h, env_step_any(h, actions));
     { int rcm = monitor_collect_step(h); if (rcm) return rcm; }                    // MonitorWrapperEnv sits inside: raw rewards
-    const bool upd = h->pn_cfg.training && h->pn_cfg.norm_reward;
+    const bool upd = h->pn.cfg.training && h->pn.cfg.norm_reward;
     int rows = 0;
     if (upd) { int rc = pn_moments(h, false, true, &rows); if (rc) return rc; }
-    PnApplyArgs a{}; a.rew = h->e_rew; a.rew_out = rew_out; a.returns = h->disc_returns; a.term = h->e_term; a.trunc = h->e_trunc; a.tobs = h->e_tobs;
+    PnApplyArgs a{}; a.w.rew = h->e_rew; a.rew_out = rew_out; a.w.returns = h->disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
     return pn_apply(h, a, rows, false, upd);
 }
 
 // ---- step-granular env verbs on device (NormalizeWrapperEnv.observe / act!, normalizeWrapperEnv.jl:123-165) ----
 int observe_dev(dril_handle* h, bool update_stats) {
     const int E = h->cfg.n_envs;
-    if (h->module && h->pn_on) return pn_observe(h, update_stats);                 // a plug-in env under dril_normalize_enable
+    if (h->module && h->pn.on) return pn_observe(h, update_stats);                 // a plug-in env under dril_normalize_enable
     if (h->module) { HIPCHK(h, env_observe_any(h, h->e_obs)); return DRIL_OK; }   // a plug-in env without the wrapper: the observation as it is
     int nb = (E + 255) / 256; if (nb > h->rms_blocks) nb = h->rms_blocks;
     HIPCHK(h, launch_obs_partials(h->cfg.env_kind, E, h->state, h->e_obs_raw, h->rms_partials, nb, h->stream));
@@ -446,7 +438,7 @@ int observe_dev(dril_handle* h, bool update_stats) {
 // actions: device pointer (stored/raw policy actions; the kernels apply the adapters); rew_out/flags_out: device destinations
 int step_dev(dril_handle* h, const void* actions, float* rew_out, uint8_t* flags_out) {
     const int E = h->cfg.n_envs;
-    if (h->module && h->pn_on) return pn_step(h, actions, rew_out ? rew_out : h->e_rew_n);
+    if (h->module && h->pn.on) return pn_step(h, actions, rew_out ? rew_out : h->e_rew_n);
     if (h->module) {                                                               // plug-in env without the wrapper: the raw step is the whole step
         HIPCHK(h, env_step_any(h, actions));
         { int rcm = monitor_collect_step(h); if (rcm) return rcm; }
@@ -873,7 +865,7 @@ DRIL_EXPORT int32_t dril_env_reset(dril_handle* h, uint64_t seed) {
     h->env_seed0 = seed + (uint64_t)h->cfg.rank * (uint64_t)h->cfg.n_envs;
     HIPCHK(h, env_reset_any(h));
     if (h->mon_cur_ret) { HIPCHK(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)h->cfg.n_envs * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)h->cfg.n_envs * 4, h->stream)); }   // MonitorWrapperEnv.reset! :38-44
-    if (h->pn_on) {                                                                  // NormalizeWrapperEnv.reset! :110-121: old_obs = the raw observation, returns = 0, the statistics stay
+    if (h->pn.on) {                                                                  // NormalizeWrapperEnv.reset! :110-121: old_obs = the raw observation, returns = 0, the statistics stay
         HIPCHK(h, hipMemsetAsync(h->disc_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream)); HIPCHK(h, env_observe_any(h, h->e_obs_raw));
     }
     h->env_ready = true;
@@ -883,7 +875,7 @@ DRIL_EXPORT int32_t dril_env_observe(dril_handle* h, float* host_obs, int32_t up
     NEED(h); NOT_EXTERNAL(h, "dril_env_observe");
     if (!h->env_ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_env_observe before dril_env_reset");
     if (!host_obs) return fail(h, DRIL_ERR_INVALID_ARG, "null host_obs");
-    if (normalizing(h) || h->pn_on) { int rc = observe_dev(h, update_stats != 0); if (rc) return rc; }
+    if (normalizing(h) || h->pn.on) { int rc = observe_dev(h, update_stats != 0); if (rc) return rc; }
     else HIPCHK(h, env_observe_any(h, h->e_obs));
     HIPCHK(h, hipMemcpyAsync(host_obs, h->e_obs, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
     return sync(h);
@@ -895,7 +887,7 @@ DRIL_EXPORT int32_t dril_env_step(dril_handle* h, const void* actions, float* re
     const size_t E = h->cfg.n_envs;
     HIPCHK(h, hipMemcpyAsync(h->e_act, actions, E * act_bytes_per(h), hipMemcpyHostToDevice, h->stream));
     float* rew_dev = h->e_rew;
-    if (normalizing(h) || h->pn_on) { rew_dev = h->e_rew_n; int rc = step_dev(h, h->e_act, rew_dev, nullptr); if (rc) return rc; }
+    if (normalizing(h) || h->pn.on) { rew_dev = h->e_rew_n; int rc = step_dev(h, h->e_act, rew_dev, nullptr); if (rc) return rc; }
     else {
         HIPCHK(h, env_step_any(h, h->e_act));
         int rcm = monitor_collect_step(h); if (rcm) return rcm;
@@ -920,7 +912,7 @@ DRIL_EXPORT int32_t dril_env_set_state(dril_handle* h, const float* state, const
 }
 DRIL_EXPORT int32_t dril_norm_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_norm_get_stats");
-    if (h->module && h->pn_on) return dril_normalize_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);   // the wrapper of dril_normalize_enable
+    if (h->module && h->pn.on) return dril_normalize_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);   // the wrapper of dril_normalize_enable
     NOT_MODULE(h, "dril_norm_get_stats");
     RmsState o, r;
     HIPCHK(h, hipMemcpyAsync(&o, h->obs_rms + h->obs_par, sizeof(o), hipMemcpyDeviceToHost, h->stream));
@@ -932,7 +924,7 @@ DRIL_EXPORT int32_t dril_norm_get_stats(dril_handle* h, float* obs_mean, float* 
 }
 DRIL_EXPORT int32_t dril_norm_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_norm_set_stats");
-    if (h->module && h->pn_on) return dril_normalize_set_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+    if (h->module && h->pn.on) return dril_normalize_set_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
     NOT_MODULE(h, "dril_norm_set_stats");
     if (!obs_mean || !obs_var) return fail(h, DRIL_ERR_INVALID_ARG, "null statistics");
     RmsState o{}, r{};
@@ -945,7 +937,7 @@ DRIL_EXPORT int32_t dril_norm_set_stats(dril_handle* h, const float* obs_mean, c
 
 DRIL_EXPORT int32_t dril_norm_get_original(dril_handle* h, float* obs, float* rewards) {
     NEED(h); NOT_EXTERNAL(h, "dril_norm_get_original");
-    if (h->module && h->pn_on) return dril_normalize_get_original(h, obs, rewards);
+    if (h->module && h->pn.on) return dril_normalize_get_original(h, obs, rewards);
     NOT_MODULE(h, "dril_norm_get_original");
     if (!normalizing(h)) return fail(h, DRIL_ERR_NOT_INITIALISED, "NormalizeWrapperEnv is off (cfg.norm_obs == cfg.norm_reward == 0)");
     if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->e_obs_raw, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
@@ -953,7 +945,7 @@ DRIL_EXPORT int32_t dril_norm_get_original(dril_handle* h, float* obs, float* re
     return sync(h);
 }
 
-// ---- NormalizeWrapperEnv around a device env plug-in (kernels: dril_ppo_norm.h) ------------------------------------------------------------------------------------
+// ---- NormalizeWrapperEnv around a device env plug-in (rules and state: dril_norm_wrap.h) ------------------------------------------------------------------------------------
 namespace {
 int pn_kind_check(dril_handle* h, const char* what) {
     if (h->external) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there");
@@ -961,85 +953,67 @@ int pn_kind_check(dril_handle* h, const char* what) {
     return DRIL_OK;
 }
 #define PN_ON(h, what) do { int _rc = pn_kind_check(h, what); if (_rc) return _rc; \
-    if (!(h)->pn_on) return fail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_normalize_enable has not been called with a configuration)"); } while (0)
+    if (!(h)->pn.on) return fail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_normalize_enable has not been called with a configuration)"); } while (0)
 }  // namespace
 DRIL_EXPORT int32_t dril_normalize_config_default(dril_normalize_config* c) {
     if (!c) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_normalize_config_default: null configuration");
-    std::memset(c, 0, sizeof(*c));
-    c->training = 1; c->norm_obs = 1; c->norm_reward = 1; c->clip_obs = 10.0f; c->clip_reward = 10.0f; c->gamma = 0.99f; c->epsilon = 1.0e-8f;   // normalizeWrapperEnv.jl:71-80
+    norm_config_default(c);
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_normalize_enable(dril_handle* h, const dril_normalize_config* cfg) {
     NEED(h);
     { int rc = pn_kind_check(h, "dril_normalize_enable"); if (rc) return rc; }
     if (!cfg) {                                                                        // the wrapper off: the handle enqueues the launches of a handle that never had it
-        if (!h->pn_on) return DRIL_OK;
+        if (!h->pn.on) return DRIL_OK;
         int rc = sync(h); if (rc) return rc;
         pn_free(h);
         return DRIL_OK;
     }
-    if (!(cfg->clip_obs >= 0.f) || !(cfg->clip_reward >= 0.f)) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_enable: clip_obs and clip_reward must be >= 0");
-    if (!(cfg->epsilon >= 0.f)) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_enable: epsilon must be >= 0");
-    if (h->D > kNzMaxD) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_normalize_enable: the wrapper's kernels hold up to " + std::to_string(kNzMaxD) + " observation dims");
-    dril_normalize_config c = *cfg; c.training = c.training != 0; c.norm_obs = c.norm_obs != 0; c.norm_reward = c.norm_reward != 0; c.reserved = 0;
-    if (h->pn_on) {                                                                    // the same wrapper again (training apart): its statistics and returns stay
-        dril_normalize_config a = c, b = h->pn_cfg; a.training = b.training = 0;
-        if (std::memcmp(&a, &b, sizeof(a)) == 0) { h->pn_cfg.training = c.training; return DRIL_OK; }
-    }
+    if (const NormErr err = norm_config_check(*cfg, h->D)) return fail(h, err.code, "dril_normalize_enable: " + err.msg);
+    const dril_normalize_config c = norm_config_canonical(*cfg);
+    if (h->pn.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart): its statistics and returns stay
     { int rc = sync(h); if (rc) return rc; }
     pn_free(h);
     const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D, Cn = 2 * D + 2;
     h->pn_rows_cap = 0;
     if (const char* e = debug_env("DRIL_NORM_ROWS")) { const int r = std::atoi(e); if (r > 0) h->pn_rows_cap = r; }   // measurements: fewer rows in the partial table
-    const size_t rows = (size_t)pn_rows((int)E, (int)D, h->pn_rows_cap);
-    hipError_t e = dmalloc(&h->pn_stats, 2 * Cn);
-    if (e == hipSuccess) e = dmalloc(&h->pn_partials, rows * Cn);
+    hipError_t e = h->pn.alloc((int)D, (size_t)pn_rows((int)E, (int)D, h->pn_rows_cap));
     if (e == hipSuccess) e = dmalloc(&h->pn_red, Cn);
-    if (e == hipSuccess) e = hipMemset(h->pn_partials, 0, rows * Cn * 8);
     if (e == hipSuccess) e = hipMemset(h->pn_red, 0, Cn * 8);
     if (e == hipSuccess) e = hipMemset(h->disc_returns, 0, E * 4);                     // returns, and the cached originals, start at 0
     if (e == hipSuccess) e = hipMemset(h->e_obs_raw, 0, E * D * 4);
     if (e == hipSuccess) e = hipMemset(h->e_rew, 0, E * 4);
-    if (e == hipSuccess) {                                                             // RunningMeanStd(): mean 0, var 1, count 0 (:12-16), both halves
-        std::vector<float> st(2 * Cn, 0.f);
-        for (size_t hf = 0; hf < 2; ++hf) { for (size_t d = 0; d < D; ++d) st[hf * Cn + D + d] = 1.0f; st[hf * Cn + 2 * D + 1] = 1.0f; }
-        e = hipMemcpy(h->pn_stats, st.data(), st.size() * 4, hipMemcpyHostToDevice);
-    }
     if (e != hipSuccess) { pn_free(h); return fail(h, DRIL_ERR_HIP, std::string("dril_normalize_enable: ") + hipGetErrorString(e)); }
-    h->pn_cfg = c; h->pn_on = true;
+    h->pn.cfg = c; h->pn.on = true;
     if (h->env_ready) HIPCHK(h, env_observe_any(h, h->e_obs_raw));                    // old_obs of the envs' present state, as reset! would have stored it
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_normalize_set_training(dril_handle* h, int32_t training) {
     NEED(h); PN_ON(h, "dril_normalize_set_training");
-    h->pn_cfg.training = training != 0;
+    h->pn.cfg.training = training != 0;
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_normalize_get_config(dril_handle* h, dril_normalize_config* cfg) {
     NEED(h); PN_ON(h, "dril_normalize_get_config");
     if (!cfg) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_get_config: null out pointer");
-    *cfg = h->pn_cfg;
+    *cfg = h->pn.cfg;
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_normalize_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
     NEED(h); PN_ON(h, "dril_normalize_get_stats");
-    const size_t D = (size_t)h->D; std::vector<float> st(2 * D + 2);
-    HIPCHK(h, hipMemcpyAsync(st.data(), pn_half(h, h->pn_cur), st.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    std::vector<float> st(h->pn.stats_floats());
+    HIPCHK(h, hipMemcpyAsync(st.data(), h->pn.half(h->pn.cur), st.size() * 4, hipMemcpyDeviceToHost, h->stream));
     int rc = sync(h); if (rc) return rc;
-    if (obs_mean) std::memcpy(obs_mean, st.data(), D * 4); if (obs_var) std::memcpy(obs_var, st.data() + D, D * 4);
-    if (ret_mean) *ret_mean = st[2 * D]; if (ret_var) *ret_var = st[2 * D + 1];
-    if (obs_count) *obs_count = h->pn_obs_count; if (ret_count) *ret_count = h->pn_ret_count;
+    h->pn.unpack(st, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_normalize_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
     NEED(h); PN_ON(h, "dril_normalize_set_stats");
-    if (!obs_mean || !obs_var) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_set_stats: null statistics pointer");
-    if (obs_count < 0 || ret_count < 0) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_set_stats: counts must be >= 0");
-    const size_t D = (size_t)h->D; std::vector<float> st(2 * D + 2);
-    std::memcpy(st.data(), obs_mean, D * 4); std::memcpy(st.data() + D, obs_var, D * 4); st[2 * D] = ret_mean; st[2 * D + 1] = ret_var;
-    HIPCHK(h, hipMemcpyAsync(pn_half(h, h->pn_cur), st.data(), st.size() * 4, hipMemcpyHostToDevice, h->stream));
+    if (const NormErr err = norm_set_stats_check(obs_mean, obs_var, obs_count, ret_count)) return fail(h, err.code, "dril_normalize_set_stats: " + err.msg);
+    const std::vector<float> st = h->pn.pack(obs_mean, obs_var, ret_mean, ret_var);
+    HIPCHK(h, hipMemcpyAsync(h->pn.half(h->pn.cur), st.data(), st.size() * 4, hipMemcpyHostToDevice, h->stream));
     int rc = sync(h); if (rc) return rc;
-    h->pn_obs_count = obs_count; h->pn_ret_count = ret_count;
+    h->pn.obs_count = obs_count; h->pn.ret_count = ret_count;
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_normalize_get_original(dril_handle* h, float* obs, float* rewards) {
@@ -1196,12 +1170,12 @@ int collect_rollout_module(dril_handle* h) {
 }
 
 // the same loop under dril_normalize_enable: the plug-in's step kernel writes raw reward, terminal observation and raw next observation into the per-step arrays, then
-// ppo_norm_moments_kernel + ppo_norm_apply_kernel (dril_ppo_norm.h) put the normalised reward into row t and the normalised next observation where the policy reads it:
+// norm_moments_kernel (dril_norm_wrap.h) + ppo_norm_apply_kernel (dril_ppo_norm.h) put the normalised reward into row t and the normalised next observation where the policy reads it:
 // two launches more per env step than collect_rollout_module, and two for the opening observe.  V(terminal_observation) is V of the normalised terminal observation
 int collect_rollout_module_norm(dril_handle* h) {
     const int E = h->cfg.n_envs, T = h->cfg.n_steps, D = h->D, A = h->A;
     const size_t ab = act_bytes_per(h);
-    const bool upd_obs = h->pn_cfg.training && h->pn_cfg.norm_obs, upd_ret = h->pn_cfg.training && h->pn_cfg.norm_reward;
+    const bool upd_obs = h->pn.cfg.training && h->pn.cfg.norm_obs, upd_ret = h->pn.cfg.training && h->pn.cfg.norm_reward;
     int rc = pn_observe(h, true); if (rc) return rc;                                       // new_obs = observe(env), trajectory.jl:32
     for (int t = 0; t < T; ++t) {
         const size_t k = (size_t)t * E;
@@ -1217,8 +1191,8 @@ int collect_rollout_module_norm(dril_handle* h) {
         HIPCHK(h, module_launch(h, h->mod_step, s));                                       // to_env + the env's own act! + raw observe
         int rows = 0;
         if (upd_obs || upd_ret) { rc = pn_moments(h, upd_obs, upd_ret, &rows); if (rc) return rc; }
-        PnApplyArgs a{}; a.raw = h->e_obs_raw; a.obs_out = h->e_obs;
-        a.rew = h->e_rew; a.rew_out = h->rew + k; a.returns = h->disc_returns; a.term = h->e_term; a.trunc = h->e_trunc; a.tobs = h->e_tobs;
+        PnApplyArgs a{}; a.w.raw = h->e_obs_raw; a.w.obs_out = h->e_obs;
+        a.w.rew = h->e_rew; a.rew_out = h->rew + k; a.w.returns = h->disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
         rc = pn_apply(h, a, rows, upd_obs, upd_ret); if (rc) return rc;                    // the wrapper's act! :139-165 and observe :123-137
     }
     PolicyArgs l = policy_args(h, h->e_obs, E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);
@@ -1234,7 +1208,7 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
         const auto t0s = std::chrono::steady_clock::now();
         if (fps) HIPCHK(h, hipStreamSynchronize(h->stream));
         prof_begin(h, DRIL_K_ROLLOUT);
-        int rcs = h->module ? (h->pn_on ? collect_rollout_module_norm(h) : collect_rollout_module(h)) : collect_rollout_stepwise(h);
+        int rcs = h->module ? (h->pn.on ? collect_rollout_module_norm(h) : collect_rollout_module(h)) : collect_rollout_stepwise(h);
         prof_end(h);
         if (rcs) return rcs;
         if (fps) { HIPCHK(h, hipStreamSynchronize(h->stream)); const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0s).count(); *fps = (double)h->N / (dt > 0 ? dt : 1e-12); }
@@ -1712,17 +1686,17 @@ DRIL_EXPORT int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval, int32_t 
     if (n_eval < 1 || !out) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
     const int E = h->cfg.n_envs;
     int rc = ensure_wimg(h); if (rc) return rc;
-    if (h->module && h->pn_on) {                                                 // a plug-in env under dril_normalize_enable: the statistics in force, frozen; nothing of the wrapper moves
+    if (h->module && h->pn.on) {                                                 // a plug-in env under dril_normalize_enable: the statistics in force, frozen; nothing of the wrapper moves
         const size_t ED = (size_t)E * h->D;
         float* keep = nullptr; HIPCHK(h, dmalloc(&keep, ED + 2 * (size_t)E));    // returns | old_rewards | old_obs
-        const int training = h->pn_cfg.training;
+        const int training = h->pn.cfg.training;
         hipError_t e = hipMemcpyAsync(keep, h->disc_returns, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(keep + E, h->e_rew, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(keep + 2 * (size_t)E, h->e_obs_raw, ED * 4, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) {
-            h->pn_cfg.training = 0;                                              // set_training(eval_env, false): neither statistics nor `returns` are updated
+            h->pn.cfg.training = 0;                                              // set_training(eval_env, false): neither statistics nor `returns` are updated
             rc = evaluate_agent_loop(h, n_eval, deterministic, out, ep_rewards, ep_lengths, /*raw_rewards=*/true);
-            h->pn_cfg.training = training;
+            h->pn.cfg.training = training;
             e = hipMemcpyAsync(h->disc_returns, keep, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(h->e_rew, keep + E, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(h->e_obs_raw, keep + 2 * (size_t)E, ED * 4, hipMemcpyDeviceToDevice, h->stream);

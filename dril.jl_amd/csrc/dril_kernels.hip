@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "dril_internal.h"
+#include "dril_norm_wrap.h"     // nz_merge, nz_reward: the scalars the built-in wrapper (RmsState, 8 dims) shares with the general-width one
 #include "dril_grad_common.h"
 #include "dril_split_pieces.h"
 
@@ -101,19 +102,6 @@ __global__ void obs_partials_kernel(int E, const float* __restrict__ state, floa
     }
 }
 
-// update_from_moments! (normalizeWrapperEnv.jl:28-50) in the reference's f32 arithmetic
-__device__ __forceinline__ void rms_merge(float& mean, float& var, long long count, float bmean, float bvar, long long bcount) {
-    if (count == 0) { mean = bmean; var = bvar; }
-    else {
-        const long long tot = count + bcount;
-        const float delta = bmean - mean;
-        const float new_mean = mean + delta * (float)bcount / (float)tot;
-        const float m_a = var * (float)count, m_b = bvar * (float)bcount;
-        const float M2 = m_a + m_b + delta * delta * (float)count * (float)bcount / (float)tot;
-        mean = new_mean; var = M2 / (float)tot;
-    }
-}
-
 // column sums of the [nblocks][16] partial table with all 256 threads (16 columns x 16 block groups, independent loads in flight, fixed
 // summation order): the serial `for b < nblocks` fold by D + 1 threads cost one dependent global round trip per block — 57 us per env step
 __device__ __forceinline__ void fold_partials16(const double* __restrict__ partials, int nblocks, double (&s_part)[16][17], double (&s_col)[16]) {
@@ -151,7 +139,7 @@ __global__ void norm_obs_apply_kernel(NormObsArgs a) {
         if (a.update) {
             const double s = s_col[2 * d], q = s_col[2 * d + 1];
             const double bm = s / nb_; double bv = q / nb_ - bm * bm; if (bv < 0) bv = 0;      // mean / var(corrected=false), :21-26
-            rms_merge(mean, var, a.in->count, (float)bm, (float)bv, nb_);
+            nz_merge(mean, var, a.in->count, (float)bm, (float)bv, nb_);
         }
         s_mean[d] = mean; s_var[d] = var;
         if (blockIdx.x == 0) { a.out->mean[d] = mean; a.out->var[d] = var; if (d == 0) a.out->count = a.in->count + (a.update ? nb_ : 0); }
@@ -188,7 +176,7 @@ __global__ void norm_rew_apply_kernel(NormRewArgs a) {
         if (a.update) {
             const double s = s_col[0], q = s_col[1];
             const double bm = s / nb_; double bv = q / nb_ - bm * bm; if (bv < 0) bv = 0;
-            rms_merge(mean, var, a.in->count, (float)bm, (float)bv, nb_);
+            nz_merge(mean, var, a.in->count, (float)bm, (float)bv, nb_);
         }
         s_var = var;
         if (blockIdx.x == 0) { a.out->mean[0] = mean; a.out->var[0] = var; a.out->count = a.in->count + (a.update ? nb_ : 0); }
@@ -196,7 +184,7 @@ __global__ void norm_rew_apply_kernel(NormRewArgs a) {
     __syncthreads();
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < a.E; e += gridDim.x * blockDim.x) {
         float r = a.rew_raw[e];
-        if (a.norm_reward) { r = r / sqrtf(s_var + a.eps); r = fminf(fmaxf(r, -a.clip_reward), a.clip_reward); }   // normalize_rewards! :188-197 (no mean subtraction)
+        if (a.norm_reward) r = nz_reward(r, s_var, a.eps, a.clip_reward);
         a.rew_out[e] = r;
         if (a.flags_out) a.flags_out[e] = (uint8_t)((a.term[e] ? 1 : 0) | (a.trunc[e] ? 2 : 0));
         if (a.term[e] || a.trunc[e]) a.disc_returns[e] = 0.f;                                                    // :152-155
@@ -263,7 +251,7 @@ __global__ void norm_apply_kernel(NormApplyArgs a) {
             const int col = i == 0 ? 0 : 2 * i;
             const double s = s_col[col], q = s_col[col + 1];
             const double bm = s / nb_; double bv = q / nb_ - bm * bm; if (bv < 0) bv = 0;
-            rms_merge(mean, var, in->count, (float)bm, (float)bv, nb_);
+            nz_merge(mean, var, in->count, (float)bm, (float)bv, nb_);
         }
         if (i == 0) { s_rvar = var; if (blockIdx.x == 0) { a.ret_out->mean[0] = mean; a.ret_out->var[0] = var; a.ret_out->count = in->count + (upd ? nb_ : 0); } }
         else {
@@ -274,7 +262,7 @@ __global__ void norm_apply_kernel(NormApplyArgs a) {
     __syncthreads();
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < a.E; e += gridDim.x * blockDim.x) {
         float r = a.rew_raw[e];
-        if (a.norm_reward) { r = r / sqrtf(s_rvar + a.eps); r = fminf(fmaxf(r, -a.clip_reward), a.clip_reward); }
+        if (a.norm_reward) r = nz_reward(r, s_rvar, a.eps, a.clip_reward);
         a.rew_out[e] = r;
         const bool tr = a.trunc[e] != 0;
         if (a.term[e] || tr) a.disc_returns[e] = 0.f;

@@ -32,6 +32,7 @@
 #include "dril_sac_adapter.h"
 #include "dril_sac_eval.h"
 #include "dril_env_module.h"
+#include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
 
 using namespace dril;
 
@@ -1127,7 +1128,7 @@ __device__ __forceinline__ void sac_eval_account(const EvalAcctArgs& a, int e, f
     }
     a.cur_ret[e] = r; a.cur_len[e] = l;
 }
-#include "dril_sac_norm.h"   // NormalizeWrapperEnv on the SAC handle (dril_sac_normalize_enable): moments / apply + push kernels, the evaluation's frozen statistics
+#include "dril_sac_norm.h"   // NormalizeWrapperEnv on the SAC handle (dril_sac_normalize_enable): the env-step moments and apply + push kernels, the evaluation's frozen statistics
 // built-in Box envs: the twin of sac_collect_env_kernel with the accounting where that one has the push (the monitor pointers of `env` are null: an evaluation does
 // not feed the training env's MonitorWrapperEnv).  nz.st != null: NormalizeWrapperEnv with training = false — the next observation normalised with the frozen
 // statistics by the env's own thread, in place of the raw row
@@ -1267,10 +1268,10 @@ struct dril_sac_handle {
     // evaluate_agent (dril_sac_evaluate_agent): the env-side snapshot, the per-env running sums, the event list and its counter (pinned host word for the poll)
     int eval_poll = 0; float *ev_state = nullptr, *ev_obs = nullptr, *ev_mon_ret = nullptr, *ev_cur_ret = nullptr; int32_t *ev_sc = nullptr, *ev_mon_len = nullptr, *ev_cur_len = nullptr; uint32_t *ev_ep = nullptr, *ev_gs = nullptr;
     unsigned int *ev_counter = nullptr, *ev_counter_host = nullptr; SacEvalEvent* ev_events = nullptr; long long ev_events_cap = 0;
-    // NormalizeWrapperEnv (dril_sac_normalize_enable; nz_on false: every pointer null).  nz_stats: the ping-pong pair [2][mean D | var D | ret_mean ret_var], nz_cur the
-    // half in force; the counts are host integers; nz_old_obs (E x D) is the raw observation of the envs' present state once nz_raw_valid (dril_sac_norm.h)
-    bool nz_on = false, nz_raw_valid = false; dril_sac_normalize_config nz_cfg{}; int nz_cur = 0; int64_t nz_obs_count = 0, nz_ret_count = 0;
-    float *nz_stats = nullptr, *nz_returns = nullptr, *nz_old_obs = nullptr, *nz_old_rew = nullptr; double* nz_partials = nullptr;
+    // NormalizeWrapperEnv (dril_sac_normalize_enable; nz.on false: every pointer null; kernels: dril_norm_wrap.h, dril_sac_norm.h).  nz_old_obs (E x D) is the raw
+    // observation of the envs' present state once nz_raw_valid
+    NormWrap nz; bool nz_raw_valid = false;
+    float *nz_returns = nullptr, *nz_old_obs = nullptr, *nz_old_rew = nullptr;
     // injected inputs (tests)
     float* collect_noise = nullptr; size_t collect_noise_count = 0;
     int inj_updates = 0; long long* inj_idx = nullptr; float *inj_ne = nullptr, *inj_nn = nullptr, *inj_np = nullptr;
@@ -1596,12 +1597,11 @@ CollectEnvArgs env_kernel_args(dril_sac_handle* h, const CollectHeadArgs& ca, co
 }
 // ---- NormalizeWrapperEnv in a collection (kernels: dril_sac_norm.h) -----------------------------------------------------------------------------------------
 void normalize_free(dril_sac_handle* h) {
-    void* ptrs[] = {h->nz_stats, h->nz_returns, h->nz_old_obs, h->nz_old_rew, h->nz_partials};
+    h->nz.release();
+    void* ptrs[] = {h->nz_returns, h->nz_old_obs, h->nz_old_rew};
     for (void* p : ptrs) if (p) hipFree(p);
-    h->nz_stats = h->nz_returns = h->nz_old_obs = h->nz_old_rew = nullptr; h->nz_partials = nullptr;
-    h->nz_on = false; h->nz_raw_valid = false; h->nz_cur = 0; h->nz_obs_count = h->nz_ret_count = 0;
+    h->nz_returns = h->nz_old_obs = h->nz_old_rew = nullptr; h->nz_raw_valid = false;
 }
-float* nz_half(dril_sac_handle* h, int i) { return h->nz_stats + (size_t)i * (2 * h->D + 2); }
 // the raw observation of the envs' present state in nz_old_obs (reset! :110-121 stores it; so does every observe)
 int nz_ensure_raw(dril_sac_handle* h) {
     if (!h->env_ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
@@ -1611,35 +1611,33 @@ int nz_ensure_raw(dril_sac_handle* h) {
     h->nz_raw_valid = true;
     return DRIL_OK;
 }
-// sac_norm_moments_kernel over nz_old_obs (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
+// norm_moments_kernel over nz_old_obs (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
 int nz_moments(dril_sac_handle* h, bool obs, bool ret, int* rows) {
     const int E = h->cfg.n_envs, D = h->D, R = std::max(kEnvsPerBlock, (E + kNzMaxRows - 1) / kNzMaxRows);
     *rows = (E + R - 1) / R;
-    const NzMomArgs m{E, D, R, obs ? h->nz_old_obs : nullptr, ret ? h->e_rew : nullptr, h->nz_returns, h->nz_cfg.gamma, h->nz_partials};
-    hipLaunchKernelGGL(sac_norm_moments_kernel, dim3(*rows, obs && D > 64 ? (D + 255) / 256 : 1), dim3(256), 0, h->stream, m);
+    const NormMomArgs m{E, D, R, obs ? h->nz_old_obs : nullptr, ret ? h->e_rew : nullptr, h->nz_returns, h->nz.cfg.gamma, h->nz.partials};
+    hipLaunchKernelGGL(norm_moments_kernel<kNzTile>, dim3(*rows, obs && D > 64 ? (D + kNzTile - 1) / kNzTile : 1), dim3(256), 0, h->stream, m);
     SHIP(h, hipGetLastError());
     return DRIL_OK;
 }
-// sac_norm_apply_kernel; a launch that updates writes the other half of the pair, which is then the one in force
-int nz_apply(dril_sac_handle* h, NzApplyArgs a, int rows, bool upd_obs, bool upd_ret) {
+// sac_norm_apply_kernel over the table of `rows` rows the moments launch wrote
+int nz_apply(dril_sac_handle* h, NzApplyArgs p, int rows, bool upd_obs, bool upd_ret) {
+    NormWrapArgs& a = p.w;
     const int E = h->cfg.n_envs, D = h->D;
-    const bool upd = upd_obs || upd_ret;
-    a.E = E; a.D = D; a.rows = rows; a.epb = std::max(std::min(64, std::max(1, 2048 / D)), (E + 127) / 128);
-    a.partials = upd ? h->nz_partials : nullptr; a.upd_obs = upd_obs; a.upd_ret = upd_ret; a.norm_obs = h->nz_cfg.norm_obs; a.norm_reward = h->nz_cfg.norm_reward;
-    a.obs_count = h->nz_obs_count; a.ret_count = h->nz_ret_count; a.clip_obs = h->nz_cfg.clip_obs; a.clip_reward = h->nz_cfg.clip_reward; a.eps = h->nz_cfg.epsilon;
-    a.st_in = nz_half(h, h->nz_cur); a.st_out = upd ? nz_half(h, h->nz_cur ^ 1) : nullptr;
-    hipLaunchKernelGGL(sac_norm_apply_kernel, dim3((E + a.epb - 1) / a.epb), dim3(256), nz_apply_lds(D), h->stream, a);
+    h->nz.fill(a, upd_obs, upd_ret, E);
+    a.E = E; a.rows = rows; a.epb = std::max(std::min(64, std::max(1, 2048 / D)), (E + 127) / 128);
+    hipLaunchKernelGGL(sac_norm_apply_kernel, dim3((E + a.epb - 1) / a.epb), dim3(256), nz_apply_lds(D), h->stream, p);
     SHIP(h, hipGetLastError());
-    if (upd) { h->nz_cur ^= 1; if (upd_obs) h->nz_obs_count += E; if (upd_ret) h->nz_ret_count += E; }
+    h->nz.commit(a);
     return DRIL_OK;
 }
 // observe(env) of the wrapper (:123-137) over the envs' present state into `out`; update = false: a read-only peek
 int nz_observe(dril_sac_handle* h, bool update, float* out) {
     SDO(nz_ensure_raw(h));
-    const bool upd = update && h->nz_cfg.training && h->nz_cfg.norm_obs;
+    const bool upd = update && h->nz.cfg.training && h->nz.cfg.norm_obs;
     int rows = 0;
     if (upd) SDO(nz_moments(h, true, false, &rows));
-    NzApplyArgs a{}; a.raw = h->nz_old_obs; a.obs_out = out;
+    NzApplyArgs a{}; a.w.raw = h->nz_old_obs; a.w.obs_out = out;
     return nz_apply(h, a, rows, upd, false);
 }
 // collect_trajectories begins with observe(env) (off_policy_collection.jl:42): one statistics update over the current raw observations, re-normalised
@@ -1647,7 +1645,7 @@ int nz_collect_begin(dril_sac_handle* h) { SDO(nz_observe(h, true, h->obs_cur));
 // one collected step through the wrapper: {head, act!, raw observe, moments} then {merge, normalise, push}
 int collect_step_norm(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned long long* stamp) {
     const int E = h->cfg.n_envs;
-    const bool upd_obs = h->nz_cfg.training && h->nz_cfg.norm_obs, upd_ret = h->nz_cfg.training && h->nz_cfg.norm_reward;
+    const bool upd_obs = h->nz.cfg.training && h->nz.cfg.norm_obs, upd_ret = h->nz.cfg.training && h->nz.cfg.norm_reward;
     int rows = 0;
     const MonitorArgs mon = monitor_row(h); if (h->mon_window) h->mon_row += 1;                     // MonitorWrapperEnv sits inside the normaliser: raw rewards
     if (h->module) {
@@ -1659,7 +1657,7 @@ int collect_step_norm(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned lo
         if (upd_obs || upd_ret) SDO(nz_moments(h, upd_obs, upd_ret, &rows));
     } else {                                                                                         // every built-in Box env has A = 1
         CollectEnvArgs ce = env_kernel_args(h, ca, PushArgs{}, mon); ce.nobs = h->nz_old_obs;
-        const NormEnvArgs ne{ce, h->nz_returns, upd_ret ? 1 : 0, h->nz_cfg.gamma, h->nz_partials};
+        const NormEnvArgs ne{ce, h->nz_returns, upd_ret ? 1 : 0, h->nz.cfg.gamma, h->nz.partials};
         const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
         rows = (int)grid.x;
         if (h->cfg.env_kind == DRIL_ENV_PENDULUM) hipLaunchKernelGGL(sac_norm_env_kernel<1>, grid, block, 0, h->stream, ne);
@@ -1667,8 +1665,8 @@ int collect_step_norm(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned lo
         else if (h->cfg.env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) hipLaunchKernelGGL(sac_norm_env_kernel<7>, grid, block, 0, h->stream, ne);
         else hipLaunchKernelGGL(sac_norm_env_kernel<4>, grid, block, 0, h->stream, ne);
     }
-    NzApplyArgs a{}; a.raw = h->nz_old_obs; a.obs_out = h->obs_nxt;
-    a.rew = h->e_rew; a.old_rew = h->nz_old_rew; a.returns = h->nz_returns; a.term = h->e_term; a.trunc = h->e_trunc; a.tobs = h->e_tobs;
+    NzApplyArgs a{}; a.w.raw = h->nz_old_obs; a.w.obs_out = h->obs_nxt;
+    a.w.rew = h->e_rew; a.old_rew = h->nz_old_rew; a.w.returns = h->nz_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
     a.push = push_args(h, h->obs_cur, nullptr, stamp);
     SDO(nz_apply(h, a, rows, upd_obs, upd_ret));
     ring_advance(h); std::swap(h->obs_cur, h->obs_nxt);
@@ -1678,7 +1676,7 @@ int collect_step_norm(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned lo
 int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, unsigned long long* stamp = nullptr, bool first = true, bool last = true) {
     const int E = h->cfg.n_envs, D = h->D, A = h->A;
     CollectHeadArgs ca; SDO(actor_hidden(h, use_random, inj_noise, &ca));
-    if (h->nz_on) return collect_step_norm(h, ca, stamp);
+    if (h->nz.on) return collect_step_norm(h, ca, stamp);
     if (h->module) return collect_step_module(h, ca, stamp, first, last);
     const MonitorArgs mon = monitor_row(h); if (h->mon_window) h->mon_row += 1;                                   // MonitorWrapperEnv: this step's row of the collection's block (null: off)
     if (A == 1 && !h->external && h->fused_collect) {                                                            // every device Box env: head + act! + observe + push! in one launch
@@ -1716,12 +1714,12 @@ int collect(dril_sac_handle* h, int n_steps, int use_random, double* fps, bool c
     if (n_steps <= 0) return sfail(h, DRIL_ERR_INVALID_ARG, "n_steps must be positive");
     if (h->collect_noise && h->collect_noise_count != (size_t)n_steps * h->cfg.n_envs * h->A)
         return sfail(h, DRIL_ERR_INVALID_ARG, "injected collect noise must hold n_steps * n_envs * action_dim values");
-    if (h->nz_on && cont && !h->obs_valid) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_collect_continue: no collection is in progress under NormalizeWrapperEnv (env reset, statistics set or wrapper switched since the last collected step): begin one with dril_sac_collect_rollout");
-    if (h->nz_on) SDO(nz_ensure_raw(h)); else SDO(ensure_obs(h));
+    if (h->nz.on && cont && !h->obs_valid) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_collect_continue: no collection is in progress under NormalizeWrapperEnv (env reset, statistics set or wrapper switched since the last collected step): begin one with dril_sac_collect_rollout");
+    if (h->nz.on) SDO(nz_ensure_raw(h)); else SDO(ensure_obs(h));
     SDO(monitor_begin(h, n_steps));
     const auto t0 = std::chrono::steady_clock::now();
     if (h->cfg.profile_events) hipEventRecord(h->ev_a, h->stream);
-    if (h->nz_on && !cont) SDO(nz_collect_begin(h));                                              // NormalizeWrapperEnv: the observe collect_trajectories begins with
+    if (h->nz.on && !cont) SDO(nz_collect_begin(h));                                              // NormalizeWrapperEnv: the observe collect_trajectories begins with
     for (int t = 0; t < n_steps; ++t)
         SDO(collect_step(h, use_random, h->collect_noise ? h->collect_noise + (size_t)t * h->cfg.n_envs * h->A : nullptr, nullptr, t == 0, t == n_steps - 1));
     SDO(monitor_end(h));                                                                          // MonitorWrapperEnv: this collection's finished episodes into the window
@@ -1783,7 +1781,7 @@ int run_updates(dril_sac_handle* h, int n_updates, bool injected, dril_sac_stats
 // fps of an iteration = env steps / HIP-event time of its collection (the reference times the same span on the host clock, off_policy_collection.jl:126-128).
 int run_iterations(dril_sac_handle* h, int count, int tf, int n_upd, dril_sac_stats* stats, int64_t stats_room, double* fps, int64_t fps_room) {
     if (count <= 0) return DRIL_OK;
-    if (h->nz_on) SDO(nz_ensure_raw(h)); else SDO(ensure_obs(h));
+    if (h->nz.on) SDO(nz_ensure_raw(h)); else SDO(ensure_obs(h));
     SDO(monitor_begin(h, tf));
     if (n_upd > 0) { if (h->size <= 0 && tf <= 0) return sfail(h, DRIL_ERR_NOT_INITIALISED, "the replay buffer is empty"); SDO(ensure_stats(h, count * n_upd)); }
     const bool timed = h->cfg.profile_events || fps;
@@ -1794,7 +1792,7 @@ int run_iterations(dril_sac_handle* h, int count, int tf, int n_upd, dril_sac_st
         hipLaunchKernelGGL(sac_stamp_kernel, dim3(1), dim3(64), 0, h->stream, h->it_stamps);
     }
     for (int j = 0; j < count; ++j) {
-        if (h->nz_on && tf > 0) SDO(nz_collect_begin(h));                                  // every iteration is one collect_trajectories call: it begins with observe(env)
+        if (h->nz.on && tf > 0) SDO(nz_collect_begin(h));                                  // every iteration is one collect_trajectories call: it begins with observe(env)
         for (int t = 0; t < tf; ++t) SDO(collect_step(h, 0, nullptr, timed && t == tf - 1 ? h->it_stamps + 1 + 2 * j : nullptr, t == 0, t == tf - 1));
         SDO(monitor_end(h));                                                               // (the next iteration's steps reuse the rows: stream order keeps them apart)
         for (int k = 0; k < n_upd; ++k) SDO(sac_one_update(h, -1, h->stats_out + ((size_t)j * n_upd + k) * 8, timed && k == n_upd - 1 ? h->it_stamps + 2 + 2 * j : nullptr));
@@ -2059,7 +2057,7 @@ DRIL_EXPORT int32_t dril_sac_env_reset(dril_sac_handle* h, uint64_t seed) {
     else SHIP(h, launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
     if (h->mon_window) { SHIP(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)h->cfg.n_envs * 4, h->stream)); SHIP(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)h->cfg.n_envs * 4, h->stream)); }   // MonitorWrapperEnv.reset!: the running sums restart, the window stays (monitorWrapperEnv.jl:36-42)
     h->env_ready = true; h->obs_valid = false;
-    if (h->nz_on) {                                                                   // NormalizeWrapperEnv.reset! (:110-121): old_obs = the raw observation, returns = 0, the statistics stay
+    if (h->nz.on) {                                                                   // NormalizeWrapperEnv.reset! (:110-121): old_obs = the raw observation, returns = 0, the statistics stay
         SHIP(h, hipMemsetAsync(h->nz_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream));
         h->nz_raw_valid = false; SDO(nz_ensure_raw(h));
     }
@@ -2068,7 +2066,7 @@ DRIL_EXPORT int32_t dril_sac_env_reset(dril_sac_handle* h, uint64_t seed) {
 DRIL_EXPORT int32_t dril_sac_env_observe(dril_sac_handle* h, float* host_obs) {
     SNEED(h); S_NOT_EXTERNAL(h, "dril_sac_env_observe"); if (!host_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "null observation buffer");
     const float* src = h->obs_cur;
-    if (h->nz_on) { if (!h->obs_valid) { SDO(nz_observe(h, false, h->obs_nxt)); src = h->obs_nxt; } }   // a peek: what the actor will see under the statistics in force; nothing is updated
+    if (h->nz.on) { if (!h->obs_valid) { SDO(nz_observe(h, false, h->obs_nxt)); src = h->obs_nxt; } }   // a peek: what the actor will see under the statistics in force; nothing is updated
     else SDO(ensure_obs(h));
     SDO(ssync(h));
     SHIP(h, hipMemcpy(host_obs, src, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost));
@@ -2352,80 +2350,72 @@ DRIL_EXPORT int32_t dril_sac_monitor_get_stats(dril_sac_handle* h, float* ep_rew
     return DRIL_OK;
 }
 
-// ---- NormalizeWrapperEnv around the handle's device envs (normalizeWrapperEnv.jl; kernels: dril_sac_norm.h) ------------------------------------------------------
+// ---- NormalizeWrapperEnv around the handle's device envs (normalizeWrapperEnv.jl; rules and state: dril_norm_wrap.h) ------------------------------------------------------
 namespace {
 #define S_NORMALIZE_ON(h, what) do { if ((h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, what ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there"); \
-    if (!(h)->nz_on) return sfail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_sac_normalize_enable has not been called with a configuration)"); } while (0)
+    if (!(h)->nz.on) return sfail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_sac_normalize_enable has not been called with a configuration)"); } while (0)
 }  // namespace
+// the two public configuration structs are one layout; inside the library it is dril_normalize_config
+static_assert(sizeof(dril_sac_normalize_config) == sizeof(dril_normalize_config) && offsetof(dril_sac_normalize_config, training) == offsetof(dril_normalize_config, training) &&
+              offsetof(dril_sac_normalize_config, norm_obs) == offsetof(dril_normalize_config, norm_obs) && offsetof(dril_sac_normalize_config, norm_reward) == offsetof(dril_normalize_config, norm_reward) &&
+              offsetof(dril_sac_normalize_config, clip_obs) == offsetof(dril_normalize_config, clip_obs) && offsetof(dril_sac_normalize_config, clip_reward) == offsetof(dril_normalize_config, clip_reward) &&
+              offsetof(dril_sac_normalize_config, gamma) == offsetof(dril_normalize_config, gamma) && offsetof(dril_sac_normalize_config, epsilon) == offsetof(dril_normalize_config, epsilon) &&
+              offsetof(dril_sac_normalize_config, reserved) == offsetof(dril_normalize_config, reserved), "dril_sac_normalize_config and dril_normalize_config");
 DRIL_EXPORT int32_t dril_sac_normalize_config_default(dril_sac_normalize_config* c) {
     if (!c) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_config_default: null configuration");
-    memset(c, 0, sizeof(*c));
-    c->training = 1; c->norm_obs = 1; c->norm_reward = 1; c->clip_obs = 10.0f; c->clip_reward = 10.0f; c->gamma = 0.99f; c->epsilon = 1.0e-8f;   // normalizeWrapperEnv.jl:71-80
+    dril_normalize_config d; norm_config_default(&d); memcpy(c, &d, sizeof(d));
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_normalize_enable(dril_sac_handle* h, const dril_sac_normalize_config* cfg) {
     SNEED(h);
     if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_normalize_enable: the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there");
     if (!cfg) {                                                                        // the wrapper off: the next collection observes the env itself again
-        if (!h->nz_on) return DRIL_OK;
+        if (!h->nz.on) return DRIL_OK;
         SDO(ssync(h)); normalize_free(h); h->obs_valid = false;
         return DRIL_OK;
     }
-    if (!(cfg->clip_obs >= 0.f) || !(cfg->clip_reward >= 0.f)) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_enable: clip_obs and clip_reward must be >= 0");
-    if (!(cfg->epsilon >= 0.f)) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_enable: epsilon must be >= 0");
-    if (h->D > kNzMaxD) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_normalize_enable: the wrapper's kernels hold up to " + std::to_string(kNzMaxD) + " observation dims");
-    dril_sac_normalize_config c = *cfg; c.training = c.training != 0; c.norm_obs = c.norm_obs != 0; c.norm_reward = c.norm_reward != 0; c.reserved = 0;
-    if (h->nz_on) {                                                                    // the same wrapper again (training apart: that is set_training's to change): its statistics and returns stay
-        dril_sac_normalize_config a = c, b = h->nz_cfg; a.training = b.training = 0;
-        if (memcmp(&a, &b, sizeof(a)) == 0) { h->nz_cfg.training = c.training; return DRIL_OK; }
-    }
+    dril_normalize_config c; memcpy(&c, cfg, sizeof(c));
+    if (const NormErr err = norm_config_check(c, h->D)) return sfail(h, err.code, "dril_sac_normalize_enable: " + err.msg);
+    c = norm_config_canonical(c);
+    if (h->nz.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart: that is set_training's to change): its statistics and returns stay
     SDO(ssync(h));
     normalize_free(h);
-    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D, C = 2 * D + 2;
-    const size_t rows = std::max<size_t>(kNzMaxRows, h->module ? 0 : (E + kEnvsPerBlock - 1) / kEnvsPerBlock);
-    hipError_t e = smalloc(&h->nz_stats, 2 * C);                                       // (smalloc zeroes: means, returns and the cached originals start at 0)
-    if (e == hipSuccess) e = smalloc(&h->nz_returns, E);
+    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
+    hipError_t e = h->nz.alloc((int)D, std::max<size_t>(kNzMaxRows, h->module ? 0 : (E + kEnvsPerBlock - 1) / kEnvsPerBlock));
+    if (e == hipSuccess) e = smalloc(&h->nz_returns, E);                               // (smalloc zeroes: returns and the cached originals start at 0)
     if (e == hipSuccess) e = smalloc(&h->nz_old_obs, E * D);
     if (e == hipSuccess) e = smalloc(&h->nz_old_rew, E);
-    if (e == hipSuccess) e = smalloc(&h->nz_partials, rows * C);
-    if (e == hipSuccess) {                                                             // RunningMeanStd(): mean 0, var 1, count 0 (:12-16)
-        std::vector<float> st(C, 0.f); for (size_t d = 0; d < D; ++d) st[D + d] = 1.0f; st[2 * D + 1] = 1.0f;
-        e = hipMemcpy(h->nz_stats, st.data(), C * 4, hipMemcpyHostToDevice);
-    }
     if (e != hipSuccess) { normalize_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_normalize_enable: ") + hipGetErrorString(e)); }
-    h->nz_cfg = c; h->nz_on = true; h->obs_valid = false;                              // the next collection observes through the wrapper
+    h->nz.cfg = c; h->nz.on = true; h->obs_valid = false;                              // the next collection observes through the wrapper
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_normalize_set_training(dril_sac_handle* h, int32_t training) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_set_training");
-    h->nz_cfg.training = training != 0;
+    h->nz.cfg.training = training != 0;
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_normalize_get_config(dril_sac_handle* h, dril_sac_normalize_config* cfg) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_get_config");
     if (!cfg) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_get_config: null out pointer");
-    *cfg = h->nz_cfg;
+    memcpy(cfg, &h->nz.cfg, sizeof(*cfg));
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_normalize_get_stats(dril_sac_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_get_stats");
     if (!obs_mean || !obs_var || !obs_count || !ret_mean || !ret_var || !ret_count) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_get_stats: null out pointer");
     SDO(ssync(h));
-    const size_t D = (size_t)h->D; std::vector<float> st(2 * D + 2);
-    SHIP(h, hipMemcpy(st.data(), nz_half(h, h->nz_cur), st.size() * 4, hipMemcpyDeviceToHost));
-    memcpy(obs_mean, st.data(), D * 4); memcpy(obs_var, st.data() + D, D * 4); *ret_mean = st[2 * D]; *ret_var = st[2 * D + 1];
-    *obs_count = h->nz_obs_count; *ret_count = h->nz_ret_count;
+    std::vector<float> st(h->nz.stats_floats());
+    SHIP(h, hipMemcpy(st.data(), h->nz.half(h->nz.cur), st.size() * 4, hipMemcpyDeviceToHost));
+    h->nz.unpack(st, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_normalize_set_stats(dril_sac_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_set_stats");
-    if (!obs_mean || !obs_var) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_set_stats: null statistics pointer");
-    if (obs_count < 0 || ret_count < 0) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_set_stats: counts must be >= 0");
+    if (const NormErr err = norm_set_stats_check(obs_mean, obs_var, obs_count, ret_count)) return sfail(h, err.code, "dril_sac_normalize_set_stats: " + err.msg);
     SDO(ssync(h));
-    const size_t D = (size_t)h->D; std::vector<float> st(2 * D + 2);
-    memcpy(st.data(), obs_mean, D * 4); memcpy(st.data() + D, obs_var, D * 4); st[2 * D] = ret_mean; st[2 * D + 1] = ret_var;
-    SHIP(h, hipMemcpy(nz_half(h, h->nz_cur), st.data(), st.size() * 4, hipMemcpyHostToDevice));
-    h->nz_obs_count = obs_count; h->nz_ret_count = ret_count; h->obs_valid = false;   // (the current normalised observation was made with other statistics)
+    const std::vector<float> st = h->nz.pack(obs_mean, obs_var, ret_mean, ret_var);
+    SHIP(h, hipMemcpy(h->nz.half(h->nz.cur), st.data(), st.size() * 4, hipMemcpyHostToDevice));
+    h->nz.obs_count = obs_count; h->nz.ret_count = ret_count; h->obs_valid = false;   // (the current normalised observation was made with other statistics)
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_normalize_get_original(dril_sac_handle* h, float* obs, float* rewards) {
@@ -2476,7 +2466,7 @@ int eval_step(dril_sac_handle* h, int deterministic, int32_t step, unsigned int 
     ca.deterministic = deterministic ? 1 : 0;
     const EvalAcctArgs acct{E, step, h->ev_cur_ret, h->ev_cur_len, h->ev_counter, h->ev_events, cap};
     // NormalizeWrapperEnv with training = false (set_training(eval_env, false) after sync_normalization_stats!, :299-309): the statistics in force, frozen
-    const NzEvalArgs nz{h->nz_on ? nz_half(h, h->nz_cur) : nullptr, h->nz_on ? h->nz_cfg.norm_obs : 0, h->nz_cfg.epsilon, h->nz_cfg.clip_obs};
+    const NzEvalArgs nz{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs};
     if (h->module) {
         hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
         DrilEnvPluginArgs st = module_args(h);                                         // (monitor pointers null: evaluation episodes do not feed the window)
@@ -2507,7 +2497,7 @@ int eval_run(dril_sac_handle* h, int n_eval, int deterministic, uint64_t seed, s
     else SHIP(h, launch_env_reset(h->cfg.env_kind, E, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
     h->env_ready = true; h->obs_valid = false;
     SDO(ensure_obs(h));                                                                // (the raw observation, into obs_cur: the wrapper's old_obs is not the evaluation's to write)
-    if (h->nz_on) { NzApplyArgs a{}; a.raw = h->obs_cur; a.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }   // normalised in place, nothing updated
+    if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }   // normalised in place, nothing updated
     SHIP(h, hipMemsetAsync(h->ev_cur_ret, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_cur_len, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
     // every env finishes an episode within the time limit, so n_eval of them take at most ceil(n_eval / E) time limits; one more, and the steps enqueued past a look
     const long long max_steps = ((long long)(n_eval + E - 1) / E + 1) * (long long)h->cfg.episode_len + h->eval_poll;

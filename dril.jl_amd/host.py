@@ -29,7 +29,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _capi as capi
+from . import _capi as capi, _normalize
 from ._capi import DrilConfig, DrilPPOStats
 
 
@@ -396,6 +396,7 @@ def describe_env_module(code_object_path, device: int = 0) -> dict:
     return _module_info_dict(info)
 
 
+@_normalize.normalize_verbs(lambda self, verb: getattr(self.lib, "dril_normalize_" + verb), "normalize_")
 class Handle:
     """Owns one dril_handle*; every method is a thin typed wrapper of one C entry point."""
 
@@ -523,57 +524,9 @@ class Handle:
         om = np.ascontiguousarray(obs_mean, np.float32); ov = np.ascontiguousarray(obs_var, np.float32)
         self._chk(self.lib.dril_norm_set_stats(self._h, self._p(om), self._p(ov), int(obs_count), float(ret_mean), float(ret_var), int(ret_count)))
 
-    # NormalizeWrapperEnv around a device env plug-in (dril_normalize_*; built-in envs are wrapped at create through cfg.norm_*)
-    _NORMALIZE_KEYS = ("training", "norm_obs", "norm_reward", "clip_obs", "clip_reward", "gamma", "epsilon")
-
-    def normalize_enable(self, enabled: bool = True, **kw):
-        """NormalizeWrapperEnv(env; training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon) (normalizeWrapperEnv.jl:71-80) around the handle's plug-in
-        envs: a fresh wrapper, or nothing when the handle already has this configuration (`training` apart, which is set); normalize_enable(False) switches it off"""
-        if not enabled:
-            self._chk(self.lib.dril_normalize_enable(self._h, None)); return
-        c = capi.DrilNormalizeConfig()
-        self._chk(self.lib.dril_normalize_config_default(C.byref(c)))
-        for k, v in kw.items():
-            if k not in self._NORMALIZE_KEYS:
-                raise TypeError(f"NormalizeWrapperEnv has no keyword {k!r}")
-            setattr(c, k, int(v) if k in ("training", "norm_obs", "norm_reward") else float(v))
-        self._chk(self.lib.dril_normalize_enable(self._h, C.byref(c)))
-
-    def normalize_config(self) -> dict:
-        """the wrapper's keywords as the handle holds them (dril_normalize_get_config)"""
-        c = capi.DrilNormalizeConfig()
-        self._chk(self.lib.dril_normalize_get_config(self._h, C.byref(c)))
-        return dict(training=bool(c.training), norm_obs=bool(c.norm_obs), norm_reward=bool(c.norm_reward), clip_obs=c.clip_obs, clip_reward=c.clip_reward,
-                    gamma=c.gamma, epsilon=c.epsilon)
-
-    def normalize_set_training(self, training: bool):
-        """set_training(env, training) (normalizeWrapperEnv.jl:245-249)"""
-        self._chk(self.lib.dril_normalize_set_training(self._h, int(bool(training))))
-
-    def normalize_get_stats(self) -> dict:
-        """RunningMeanStd fields of the plug-in wrapper; the keys of norm_get_stats"""
-        om = np.empty(self.D, np.float32); ov = np.empty(self.D, np.float32)
-        oc, rc = C.c_int64(), C.c_int64(); rm, rv = C.c_float(), C.c_float()
-        self._chk(self.lib.dril_normalize_get_stats(self._h, self._p(om), self._p(ov), C.byref(oc), C.byref(rm), C.byref(rv), C.byref(rc)))
-        return dict(obs_mean=om, obs_var=ov, obs_count=oc.value, ret_mean=rm.value, ret_var=rv.value, ret_count=rc.value)
-
-    def normalize_set_stats(self, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count):
-        om = np.ascontiguousarray(obs_mean, np.float32).reshape(-1); ov = np.ascontiguousarray(obs_var, np.float32).reshape(-1)
-        if om.size != self.D or ov.size != self.D:
-            raise ValueError(f"obs_mean / obs_var must hold {self.D} values")
-        self._chk(self.lib.dril_normalize_set_stats(self._h, self._p(om), self._p(ov), int(obs_count), float(ret_mean), float(ret_var), int(ret_count)))
-
-    def normalize_get_original(self):
-        """-> (get_original_obs (E, D), get_original_rewards (E)), normalizeWrapperEnv.jl:220-222"""
-        obs = np.empty((self.E, self.D), np.float32); rew = np.empty(self.E, np.float32)
-        self._chk(self.lib.dril_normalize_get_original(self._h, self._p(obs), self._p(rew)))
-        return obs, rew
-
-    def normalize_get_returns(self) -> np.ndarray:
-        """env.returns: the discounted running return per env behind ret_rms"""
-        r = np.empty(self.E, np.float32)
-        self._chk(self.lib.dril_normalize_get_returns(self._h, self._p(r)))
-        return r
+    # NormalizeWrapperEnv around a device env plug-in (dril_normalize_*; built-in envs are wrapped at create through cfg.norm_*): normalize_enable, normalize_config,
+    # normalize_set_training, normalize_get_stats / set_stats / get_original / get_returns come from _normalize.normalize_verbs
+    _NORMALIZE_KEYS = _normalize.KEYS
 
     # policy on host batches
     def policy_forward(self, obs: np.ndarray, noise: Optional[np.ndarray] = None):
@@ -911,7 +864,7 @@ class DeviceModuleEnv(DeviceParallelEnv):
             bad = [k for k in normalize if k not in Handle._NORMALIZE_KEYS]
             if bad:
                 raise TypeError(f"NormalizeWrapperEnv has no keyword {bad[0]!r}")
-            normalize = {**dict(training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8), **normalize}
+            normalize = {**_normalize.DEFAULTS, **normalize}
         self.module_normalize = normalize
 
     def _bind_extra(self):

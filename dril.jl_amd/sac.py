@@ -21,7 +21,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _capi as capi
+from . import _capi as capi, _normalize
 from ._capi import DrilSacConfig, DrilSacStats
 from .host import Box, DrilError, PendulumEnv, ScalingWrapperEnv, _orthogonal
 
@@ -178,6 +178,7 @@ def make_sac_config(env, n_envs: int, alg: SAC, layer: SACLayer, *, seed: int = 
 # --------------------------------------------------------------------------------------------
 # typed wrapper of one dril_sac_handle*
 # --------------------------------------------------------------------------------------------
+@_normalize.normalize_verbs(lambda self, verb: self._f("normalize_" + verb), "norm_")
 class SacHandle:
     """typed wrapper of one dril_sac_handle* of libdril_hip.so (there is no other backend: the CPU oracle is driven by a subclass that lives under tests/)"""
     _PREFIX = "dril_sac_"
@@ -388,55 +389,8 @@ class SacHandle:
         self._chk(self._f("monitor_get_stats")(self._h, C.byref(r), C.byref(l), C.byref(n)))
         return r.value, l.value, n.value
 
-    # NormalizeWrapperEnv around the handle's device envs (dril_sac_normalize_*)
-    def normalize_enable(self, enabled: bool = True, **kw):
-        """NormalizeWrapperEnv(env; training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon) (normalizeWrapperEnv.jl:71-80) around the handle's envs:
-        a fresh wrapper, or nothing when the handle already has this configuration; normalize_enable(False) switches it off"""
-        if not enabled:
-            self._chk(self._f("normalize_enable")(self._h, None)); return
-        c = capi.DrilSacNormalizeConfig()
-        self._chk(self._f("normalize_config_default")(C.byref(c)))
-        for k, v in kw.items():
-            if k not in ("training", "norm_obs", "norm_reward", "clip_obs", "clip_reward", "gamma", "epsilon"):
-                raise TypeError(f"NormalizeWrapperEnv has no keyword {k!r}")
-            setattr(c, k, int(v) if k in ("training", "norm_obs", "norm_reward") else float(v))
-        self._chk(self._f("normalize_enable")(self._h, C.byref(c)))
-
-    def normalize_config(self) -> dict:
-        """the wrapper's keywords as the handle holds them (dril_sac_normalize_get_config)"""
-        c = capi.DrilSacNormalizeConfig()
-        self._chk(self._f("normalize_get_config")(self._h, C.byref(c)))
-        return dict(training=bool(c.training), norm_obs=bool(c.norm_obs), norm_reward=bool(c.norm_reward), clip_obs=c.clip_obs, clip_reward=c.clip_reward,
-                    gamma=c.gamma, epsilon=c.epsilon)
-
-    def normalize_set_training(self, training: bool):
-        """set_training(env, training) (normalizeWrapperEnv.jl:245-249)"""
-        self._chk(self._f("normalize_set_training")(self._h, int(bool(training))))
-
-    def norm_get_stats(self) -> dict:
-        """RunningMeanStd fields of the wrapper (normalizeWrapperEnv.jl:8-19); the keys of Handle.norm_get_stats"""
-        om = np.empty(self.D, np.float32); ov = np.empty(self.D, np.float32)
-        oc, rc = C.c_int64(), C.c_int64(); rm, rv = C.c_float(), C.c_float()
-        self._chk(self._f("normalize_get_stats")(self._h, self._p(om), self._p(ov), C.byref(oc), C.byref(rm), C.byref(rv), C.byref(rc)))
-        return dict(obs_mean=om, obs_var=ov, obs_count=oc.value, ret_mean=rm.value, ret_var=rv.value, ret_count=rc.value)
-
-    def norm_set_stats(self, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count):
-        om = np.ascontiguousarray(obs_mean, np.float32).reshape(-1); ov = np.ascontiguousarray(obs_var, np.float32).reshape(-1)
-        if om.size != self.D or ov.size != self.D:
-            raise ValueError(f"obs_mean / obs_var must hold {self.D} values")
-        self._chk(self._f("normalize_set_stats")(self._h, self._p(om), self._p(ov), int(obs_count), float(ret_mean), float(ret_var), int(ret_count)))
-
-    def norm_get_original(self):
-        """-> (get_original_obs (E, D), get_original_rewards (E)), normalizeWrapperEnv.jl:225-226"""
-        obs = np.empty((self.E, self.D), np.float32); rew = np.empty(self.E, np.float32)
-        self._chk(self._f("normalize_get_original")(self._h, self._p(obs), self._p(rew)))
-        return obs, rew
-
-    def norm_get_returns(self) -> np.ndarray:
-        """env.returns: the discounted running return per env behind ret_rms"""
-        r = np.empty(self.E, np.float32)
-        self._chk(self._f("normalize_get_returns")(self._h, self._p(r)))
-        return r
+    # NormalizeWrapperEnv around the handle's device envs (dril_sac_normalize_*): normalize_enable, normalize_config, normalize_set_training, norm_get_stats /
+    # norm_set_stats / norm_get_original / norm_get_returns come from _normalize.normalize_verbs
 
     def evaluate_agent(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None):
         """evaluate_agent(agent, env; n_eval_episodes, deterministic) -> (stats dict, episode_rewards, episode_lengths), evaluation.jl:54-143; env e is reset

@@ -3,7 +3,7 @@
   (a) the CartPole twin plug-in        policy launches + ONE plug-in step launch per env step
   (b) built-in CartPole, DRIL_FORCE_GENERIC=1   policy launches + norm_step_kernel + norm_apply_kernel
   (c) reacher3 plug-in (D = 12, S = 9, A = 3)
-  (d) reacher3 plug-in under NormalizeWrapperEnv (dril_normalize_enable)   (c) + ppo_norm_moments_kernel + ppo_norm_apply_kernel per env step
+  (d) reacher3 plug-in under NormalizeWrapperEnv (dril_normalize_enable)   (c) + norm_moments_kernel<64> + ppo_norm_apply_kernel per env step
 hidden [64,64], T = 32 steps per rollout, E = 64 .. 65 536.  Per rollout: wall time around dril_collect_rollout and the library's HIP-event time of the
 rollout class (cfg.profile_events); median and min..max over the rollouts after warm-up, divided by T.   usage: python tools/env_plugin_latency.py [rollouts=20]"""
 import os, sys, time
