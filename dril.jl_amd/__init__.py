@@ -7,6 +7,7 @@ __graft_entry__.py / tests/conftest.py) under the module name `dril_jl_amd`.
     _capi.py  ctypes binding of the C ABI (no fallback: raises if the .so is missing)
     host.py   mirror of the reference's Agent / ActorCriticLayer / PPO / train! / AbstractParallelEnv interface
     sac.py    mirror of the reference's SAC / SACLayer / ReplayBuffer / train!(…, ::SAC, …) interface (include/dril_sac.h)
+    deployment.py  mirror of the reference's extract_policy / NeuralPolicy / NormWrapperPolicy / RandomPolicy / ConstantPolicy (include/dril_policy.h)
     checkpoint.py  save/load of agents and normalisation statistics in the reference's key schema (npz twin of the JLD2 files)
     julia/    the `ccall` shim a DRiL.jl user loads (cannot be executed in the build image: no Julia)
 """
@@ -21,4 +22,5 @@ from .sac import (  # noqa: F401
     SAC, AutoEntropyCoefficient, FixedEntropyCoefficient, ReplayBuffer, SACAgent, SACLayer, SacHandle, get_gradient_steps, make_sac_config,
     sac_evaluate_agent, sac_flatten_params, sac_train_, sac_unflatten_params,
 )
-from .checkpoint import load_normalization_stats_, load_policy_params_and_state_, save_normalization_stats, save_policy_params_and_state  # noqa: F401
+from .checkpoint import load_normalization_stats_, load_policy, load_policy_params_and_state_, save_normalization_stats, save_policy, save_policy_params_and_state  # noqa: F401
+from .deployment import ConstantPolicy, NeuralPolicy, NormWrapperPolicy, RandomPolicy, extract_policy  # noqa: F401

@@ -107,6 +107,15 @@ class DrilNormalizeConfig(C.Structure):
 DrilSacNormalizeConfig = DrilNormalizeConfig
 
 
+class DrilPolicyDesc(C.Structure):
+    """struct dril_policy_desc, include/dril_policy.h"""
+    _fields_ = [("abi_version", C.c_uint32), ("kind", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("action_start", C.c_int32),
+                ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 4), ("activation", C.c_int32), ("has_norm", C.c_int32), ("clip_obs", C.c_float), ("epsilon", C.c_float),
+                ("device", C.c_int32), ("reserved", C.c_int32), ("action_low", C.c_float * 64), ("action_high", C.c_float * 64)]
+
+
+POLICY_ABI_VERSION = 1
+POLICY_CATEGORICAL, POLICY_DIAG_GAUSSIAN, POLICY_SQUASHED_DIAG_GAUSSIAN = 0, 1, 2
 SAC_ABI_VERSION = 1
 (RB_OBSERVATIONS, RB_ACTIONS, RB_REWARDS, RB_TERMINATED, RB_TRUNCATED, RB_NEXT_OBSERVATIONS) = range(6)
 
@@ -269,6 +278,22 @@ _SAC_SIG = {
     "normalize_get_returns": (C.c_int32, [_P, _P]),
 }
 _SIG.update({"dril_sac_" + k: v for k, v in _SAC_SIG.items()})
+# every symbol include/dril_policy.h declares
+_SIG.update({
+    "dril_policy_create": (C.c_int32, [C.POINTER(DrilPolicyDesc), _P, C.c_size_t, _P, _P, _P, C.POINTER(_P)]),
+    "dril_policy_from_handle": (C.c_int32, [_P, C.c_int32, C.POINTER(_P)]),
+    "dril_policy_from_sac_handle": (C.c_int32, [_P, C.c_int32, C.POINTER(_P)]),
+    "dril_policy_destroy": (C.c_int32, [_P]),
+    "dril_policy_last_error": (C.c_char_p, [_P]),
+    "dril_policy_act": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    "dril_policy_set_seed": (C.c_int32, [_P, C.c_uint64]),
+    "dril_policy_set_threshold": (C.c_int32, [_P, C.c_int64]),
+    "dril_policy_kernel_time": (C.c_int32, [_P, C.c_int32, _PD]),
+    "dril_policy_describe": (C.c_int32, [_P, C.POINTER(DrilPolicyDesc)]),
+    "dril_policy_param_count": (C.c_int64, [_P]),
+    "dril_policy_get_params": (C.c_int32, [_P, _P, C.c_size_t, _P]),
+    "dril_policy_get_norm": (C.c_int32, [_P, _P, _P]),
+})
 EXPORTED_SYMBOLS = tuple(_SIG)
 
 _lib = None

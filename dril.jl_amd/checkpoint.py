@@ -4,6 +4,8 @@
     load_policy_params_and_state_(agent, alg, path)    src/algorithms/ppo.jl:77-94           (the optimiser state is rebuilt, not loaded)
     save_normalization_stats / load_normalization_stats_   src/environment_wrappers/normalizeWrapperEnv.jl:261-297
                                                        keys: obs_mean obs_var obs_count ret_mean ret_var ret_count clip_obs clip_reward gamma epsilon
+    save_policy(policy, path) / load_policy(path)      a deployment policy (deployment.py) in ONE file: descriptor fields under policy/, the actor tree under
+                                                       parameters/actor_head/layer_k/{weight,bias} (+ parameters/log_std), obs_mean / obs_var when it carries statistics
 
 The reference writes JLD2 (Julia objects); a Julia user keeps doing exactly that on `agent.train_state.parameters`, which DRiLHIP.jl's
 `train!` fills with the device-trained weights.  This Python mirror stores the same keys in an `.npz`, leaves flattened
@@ -113,3 +115,50 @@ def load_normalization_stats_(env, filepath):
     h, _ = _norm_handle_kw(env)
     h.norm_set_stats(d["obs_mean"], d["obs_var"], int(d["obs_count"]), float(d["ret_mean"]), float(d["ret_var"]), int(d["ret_count"]))
     return env
+
+
+_POLICY_FIELDS = ("kind", "obs_dim", "action_dim", "action_start", "activation", "has_norm", "clip_obs", "epsilon")
+
+
+def policy_file_dict(desc, actor_flat, log_std=None, obs_mean=None, obs_var=None) -> dict:
+    """the arrays save_policy stores (host data only): the descriptor of include/dril_policy.h field by field, the actor in the parameter key schema, the statistics"""
+    from .deployment import actor_flat_to_tree
+    A, nh = desc.action_dim, desc.n_hidden
+    hidden = [int(desc.hidden[l]) for l in range(nh)]
+    out = {f"policy/{k}": np.asarray(getattr(desc, k)) for k in _POLICY_FIELDS}
+    out["policy/hidden_dims"] = np.asarray(hidden, np.int32)
+    out["policy/action_low"] = np.asarray([desc.action_low[a] for a in range(A)], np.float32)
+    out["policy/action_high"] = np.asarray([desc.action_high[a] for a in range(A)], np.float32)
+    _flatten("parameters/actor_head", actor_flat_to_tree(np.asarray(actor_flat, np.float32), (desc.obs_dim, *hidden, A)), out)
+    if log_std is not None:
+        out["parameters/log_std"] = np.asarray(log_std, np.float32)
+    if desc.has_norm:
+        out["obs_mean"], out["obs_var"] = np.asarray(obs_mean, np.float32), np.asarray(obs_var, np.float32)
+    return out
+
+
+def policy_from_file_dict(data, device: int = 0):
+    """-> (descriptor, actor parameters flat, log_std | None, obs_mean | None, obs_var | None): the arguments of NeuralPolicy.create"""
+    from .deployment import actor_tree_to_flat, make_policy_desc
+    g = lambda k: data["policy/" + k]
+    has_norm = bool(int(g("has_norm")))
+    desc = make_policy_desc(int(g("kind")), int(g("obs_dim")), int(g("action_dim")), [int(h) for h in g("hidden_dims")], int(g("activation")),
+                            action_start=int(g("action_start")), action_low=g("action_low"), action_high=g("action_high"),
+                            clip_obs=float(g("clip_obs")) if has_norm else None, epsilon=float(g("epsilon")), device=device)
+    tree = _unflatten("parameters", data)
+    return (desc, actor_tree_to_flat(tree["actor_head"]), tree.get("log_std"), data["obs_mean"] if has_norm else None, data["obs_var"] if has_norm else None)
+
+
+def save_policy(policy, path, suffix: str = ".npz") -> str:
+    """a NeuralPolicy / NormWrapperPolicy -> one .npz: enough to deploy on a machine that never saw the training run"""
+    file_path = str(path) if str(path).endswith(suffix) else str(path) + suffix
+    flat, log_std = policy.get_params()
+    mean, var = policy.get_norm() if policy.desc.has_norm else (None, None)
+    np.savez(file_path, **policy_file_dict(policy.desc, flat, log_std, mean, var))
+    return file_path
+
+
+def load_policy(path, device: int = 0, suffix: str = ".npz"):
+    from .deployment import NeuralPolicy
+    file_path = str(path) if str(path).endswith(suffix) else str(path) + suffix
+    return NeuralPolicy.create(*policy_from_file_dict(np.load(file_path, allow_pickle=False), device))

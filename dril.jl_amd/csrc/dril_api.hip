@@ -18,6 +18,7 @@
 #include "../../include/dril_hip.h"
 #include "dril_internal.h"
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper on plug-ins shares with the SAC handle's (NormWrap, norm_moments_kernel, nz_*)
+#include "dril_policy_internal.h"   // dril_policy_from_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_env_module.h"   // the plug-in loader shared with dril_sac.hip (and, through it, DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with)
 
 using namespace dril;
@@ -1090,6 +1091,40 @@ DRIL_EXPORT int32_t dril_predict_actions(dril_handle* h, const float* obs, int64
 }
 DRIL_EXPORT int32_t dril_predict_values(dril_handle* h, const float* obs, int64_t batch, float* values) {
     NEED(h); return policy_host(h, obs, batch, nullptr, nullptr, false, values, nullptr, nullptr, 2);
+}
+
+// extract_policy(agent) / extract_policy(agent, norm_env) (deployment_policy.jl:15-22, :52-58) on the device: the actor, log_std, the adapter's bounds and — with_norm —
+// the observation statistics in force are copied device-to-device into a policy object of its own (include/dril_policy.h).  Reads the handle, changes nothing in it.
+DRIL_EXPORT int32_t dril_policy_from_handle(dril_handle* h, int32_t with_norm, dril_policy** out) {
+    if (!h) { policy_set_create_error("dril_policy_from_handle: null handle"); return DRIL_ERR_NOT_INITIALISED; }
+    NEED(h);
+    auto refuse = [&](int code, const std::string& m) { policy_set_create_error(m); return fail(h, code, m); };
+    if (!out) return refuse(DRIL_ERR_INVALID_ARG, "dril_policy_from_handle: null out pointer");
+    *out = nullptr;
+    PolicyDeviceSource s{}; dril_policy_desc& d = s.desc;
+    d.abi_version = DRIL_POLICY_ABI_VERSION; d.kind = h->discrete ? DRIL_POLICY_CATEGORICAL : DRIL_POLICY_DIAG_GAUSSIAN;
+    d.obs_dim = h->D; d.action_dim = h->A; d.action_start = h->discrete ? h->cfg.action_start : 0;
+    d.n_hidden = h->gd.nh; for (int l = 0; l < h->gd.nh; ++l) d.hidden[l] = h->gd.H[l];
+    d.activation = h->cfg.activation; d.device = h->cfg.device;
+    if (!h->discrete) for (int a = 0; a < h->A; ++a) {                                 // the Box the ClampAdapter clamps to (default_adapters.jl:4-11)
+        if (h->module) { d.action_low[a] = h->mod_desc.action_low[a]; d.action_high[a] = h->mod_desc.action_high[a]; }
+        else if (h->external) { d.action_low[a] = h->cfg.ext_action_low; d.action_high[a] = h->cfg.ext_action_high; }   // low >= high: per-dimension bounds the host env clamps to itself
+        else { const float bnd = h->cfg.env_kind == DRIL_ENV_PENDULUM ? 2.0f : 1.0f; d.action_low[a] = -bnd; d.action_high[a] = bnd; }   // Pendulum's torque; every other built-in Box is [-1, 1]
+    }
+    if (with_norm) {
+        if (h->module && h->pn.on) {                                                   // the wrapper of dril_normalize_enable
+            d.has_norm = 1; d.clip_obs = h->pn.cfg.clip_obs; d.epsilon = h->pn.cfg.epsilon;
+            s.obs_mean = h->pn.half(h->pn.cur); s.obs_var = s.obs_mean + h->D;
+        } else if (!h->module && !h->external && normalizing(h)) {                     // cfg.norm_obs / cfg.norm_reward: the built-in envs' wrapper
+            d.has_norm = 1; d.clip_obs = h->cfg.clip_obs; d.epsilon = h->cfg.norm_epsilon;
+            const RmsState* st = h->obs_rms + h->obs_par;
+            s.obs_mean = st->mean; s.obs_var = st->var;
+        } else return refuse(DRIL_ERR_NOT_INITIALISED, "dril_policy_from_handle: with_norm = 1, but the handle has no NormalizeWrapperEnv (cfg.norm_obs / cfg.norm_reward, or dril_normalize_enable on a plug-in handle)");
+    }
+    s.actor = h->params + h->actor.w1; s.n = (size_t)h->Pa; s.log_std = h->discrete ? nullptr : h->params + h->log_std_off; s.stream = h->stream;
+    std::string msg;
+    const int rc = policy_from_device(s, out, &msg);
+    return rc ? fail(h, rc, "dril_policy_from_handle: " + msg) : DRIL_OK;
 }
 
 // ---- rollout ---------------------------------------------------------------------------------------

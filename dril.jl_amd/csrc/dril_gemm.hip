@@ -10,6 +10,7 @@
 
 #include "dril_device.h"
 #include "dril_gemm.h"
+#include "dril_activations.h"
 
 namespace dril {
 
@@ -45,16 +46,16 @@ constexpr int kGemmWaves = 8, kGemmDepth = 8, kRedStride = 65;
 // the activations beyond tanh / relu (generic PPO path only) live in ONE out-of-line function: inlined into every epilogue of every instantiation their libm
 // expansions grew this file's code by 45 % and cost the SAC collection forward 8 us per step (end of round 3, same-box A/B: 64.8 -> 72.8 us); SAC never calls it
 __device__ __noinline__ float gemm_epilogue_rare(int epi, float v, float y) {
-    if (epi == EPI_SIGMOID) v = 1.0f / (1.0f + expf(-v));
-    else if (epi == EPI_ELU) v = v > 0.f ? v : expm1f(v);
-    else if (epi == EPI_LEAKY) v = v > 0.f ? v : 0.01f * v;
-    else if (epi == EPI_SOFTPLUS) v = fmaxf(v, 0.f) + log1pf(expf(-fabsf(v)));
+    if (epi == EPI_SIGMOID) v = act_sigmoid(v);                                    // the forward formulas: dril_activations.h (one definition, shared with policy_act_kernel)
+    else if (epi == EPI_ELU) v = act_elu(v);
+    else if (epi == EPI_LEAKY) v = act_leakyrelu(v);
+    else if (epi == EPI_SOFTPLUS) v = act_softplus(v);
     else if (epi == EPI_MASK_SIGMOID) v *= y * (1.0f - y);
     else if (epi == EPI_MASK_ELU) v *= y > 0.f ? 1.0f : y + 1.0f;                 // alpha e^x = elu(x) + alpha
     else if (epi == EPI_MASK_LEAKY) v *= y > 0.f ? 1.0f : 0.01f;
     else if (epi == EPI_MASK_SOFTPLUS) v *= -expm1f(-y);                          // sigmoid(x) = 1 - e^(-softplus(x)); expm1: no cancellation for x << 0, where y = softplus(x) ~ e^x is tiny
-    else if (epi == EPI_GELU) { const float u = 0.7978845608028654f * (v + 0.044715f * v * v * v); v = 0.5f * v * (1.0f + tanhf(u)); }   // NNlib.gelu (tanh form)
-    else if (epi == EPI_SWISH) v = v / (1.0f + expf(-v));
+    else if (epi == EPI_GELU) v = act_gelu(v);                                     // NNlib.gelu (tanh form)
+    else if (epi == EPI_SWISH) v = act_swish(v);
     else if (epi == EPI_MASK_GELU) {                                               // y = the pre-activation x
         const float u = 0.7978845608028654f * (y + 0.044715f * y * y * y), t = tanhf(u);
         v *= 0.5f * (1.0f + t) + 0.5f * y * (1.0f - t * t) * 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * y * y);
@@ -63,8 +64,8 @@ __device__ __noinline__ float gemm_epilogue_rare(int epi, float v, float y) {
 }
 __device__ __forceinline__ float gemm_epilogue(const GemmArgs& g, float v, float b, float y) {
     v = v * g.alpha + b;
-    if (g.epi == EPI_RELU) v = relu_nan(v);
-    else if (g.epi == EPI_TANH) v = tanhf(v);
+    if (g.epi == EPI_RELU) v = act_relu(v);
+    else if (g.epi == EPI_TANH) v = act_tanh(v);
     else if (g.epi == EPI_MASK_RELU) v = y > 0.f ? v : 0.f;
     else if (g.epi == EPI_MASK_TANH) v *= 1.0f - y * y;
     else if (g.epi != EPI_NONE) v = gemm_epilogue_rare(g.epi, v, y);

@@ -30,6 +30,7 @@
 #include "dril_internal.h"
 #include "dril_gemm.h"
 #include "dril_sac_adapter.h"
+#include "dril_policy_internal.h"   // dril_policy_from_sac_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_sac_eval.h"
 #include "dril_env_module.h"
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
@@ -2114,6 +2115,30 @@ DRIL_EXPORT int32_t dril_sac_predict_actions(dril_sac_handle* h, const float* ob
         if (env) SHIP(h, hipMemcpy(env + o * h->A, h->s_out2, (size_t)n * h->A * 4, hipMemcpyDeviceToHost));
     }
     return DRIL_OK;
+}
+// extract_policy(agent) / extract_policy(agent, norm_env) of a SAC agent on the device (include/dril_policy.h): actor, log_std, the TanhScaleAdapter's bounds and — with_norm —
+// the wrapper's observation statistics, copied device-to-device into a policy object of its own.  Reads the handle, changes nothing in it.
+DRIL_EXPORT int32_t dril_policy_from_sac_handle(dril_sac_handle* h, int32_t with_norm, dril_policy** out) {
+    if (!h) { policy_set_create_error("dril_policy_from_sac_handle: null handle"); return DRIL_ERR_NOT_INITIALISED; }
+    SNEED(h);
+    auto refuse = [&](int code, const std::string& m) { policy_set_create_error(m); return sfail(h, code, m); };
+    if (!out) return refuse(DRIL_ERR_INVALID_ARG, "dril_policy_from_sac_handle: null out pointer");
+    *out = nullptr;
+    PolicyDeviceSource s{}; dril_policy_desc& d = s.desc;
+    d.abi_version = DRIL_POLICY_ABI_VERSION; d.kind = DRIL_POLICY_SQUASHED_DIAG_GAUSSIAN; d.obs_dim = h->D; d.action_dim = h->A;
+    d.n_hidden = 2; d.hidden[0] = h->H1; d.hidden[1] = h->H2; d.activation = h->cfg.activation ? 1 : 0; d.device = h->cfg.device;
+    float tb[2 * kMaxA];                                                               // the table the sampling kernels read: written once, at creation
+    SHIP(h, hipMemcpy(tb, h->act_bounds, sizeof(tb), hipMemcpyDeviceToHost));
+    for (int a = 0; a < h->A; ++a) { d.action_low[a] = tb[a]; d.action_high[a] = tb[kMaxA + a]; }
+    if (with_norm) {
+        if (!h->nz.on) return refuse(DRIL_ERR_NOT_INITIALISED, "dril_policy_from_sac_handle: with_norm = 1, but the handle has no NormalizeWrapperEnv (dril_sac_normalize_enable)");
+        d.has_norm = 1; d.clip_obs = h->nz.cfg.clip_obs; d.epsilon = h->nz.cfg.epsilon;
+        s.obs_mean = h->nz.half(h->nz.cur); s.obs_var = s.obs_mean + h->D;
+    }
+    s.actor = h->params + h->actor.w1; s.n = (size_t)h->Pa; s.log_std = h->params + h->log_std_off; s.stream = h->stream;
+    std::string msg;
+    const int rc = policy_from_device(s, out, &msg);
+    return rc ? sfail(h, rc, "dril_policy_from_sac_handle: " + msg) : DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_predict_q(dril_sac_handle* h, const float* obs, const float* actions, int64_t batch, int32_t use_target, float* q) {
     SNEED(h); if (!obs || !actions || !q || batch <= 0) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_predict_q: null pointer / empty batch");

@@ -546,5 +546,6 @@ include("DRiLHIP_extras.jl")        # normalisation statistics, evaluate_agent
 include("DRiLHIP_sac.jl")           # SAC
 
 export DeviceParallelEnv, OnDevice, OnDeviceModule, describe_env_module
+export DevicePolicy, extract_device_policy, extract_device_policy_sac
 
 end # module

@@ -42,5 +42,66 @@ function DRiL.evaluate_agent(agent, env::DeviceParallelEnv; n_eval_episodes::Int
 end
 
 
+# ---- deployment policies on the device (include/dril_policy.h): the device twin of extract_policy (src/deployment/deployment_policy.jl) ----
+# DRiL.extract_policy(agent[, norm_env]) keeps working on the host parameters train! writes back; a DevicePolicy is the same thing as one light device object
+# (actor + adapter + frozen observation statistics) that answers in one kernel launch.  Calls on one DevicePolicy must not overlap.
+mutable struct DevicePolicy
+    ptr::Ptr{Cvoid}
+    obs_dim::Int
+    action_dim::Int
+    discrete::Bool
+end
+policy_last_error(p) = unsafe_string(ccall((:dril_policy_last_error, LIB[]), Cstring, (Ptr{Cvoid},), p))
+policy_check(rc::Int32, p = C_NULL) = rc == 0 ? nothing : error("libdril_hip (policy) status $rc: $(policy_last_error(p))")
+function destroy!(p::DevicePolicy)
+    p.ptr == C_NULL || ccall((:dril_policy_destroy, LIB[]), Int32, (Ptr{Cvoid},), p.ptr)
+    p.ptr = C_NULL
+    return nothing
+end
+function wrap_policy(ptr::Ptr{Cvoid}, obs_dim, action_dim, discrete)
+    p = DevicePolicy(ptr, Int(obs_dim), Int(action_dim), discrete)
+    finalizer(destroy!, p)
+    return p
+end
+"`extract_device_policy(agent, env::DeviceParallelEnv; with_norm)`: extract_policy(agent) / extract_policy(agent, norm_env) as a device-to-device snapshot of the env's PPO handle; with_norm defaults to whether the env carries NormalizeWrapperEnv keywords"
+function extract_device_policy(agent, env::DeviceParallelEnv; with_norm::Bool = env.normalize !== nothing)
+    bind_agent!(env, agent, agent.algorithm); push_params!(env, agent)
+    h = env.handle; pp = Ref{Ptr{Cvoid}}(C_NULL)
+    policy_check(ccall((:dril_policy_from_handle, LIB[]), Int32, (Ptr{Cvoid}, Int32, Ref{Ptr{Cvoid}}), h, Int32(with_norm), pp))
+    return wrap_policy(pp[], ccall((:dril_obs_dim, LIB[]), Int32, (Ptr{Cvoid},), h), ccall((:dril_action_dim, LIB[]), Int32, (Ptr{Cvoid},), h),
+        ccall((:dril_is_discrete, LIB[]), Int32, (Ptr{Cvoid},), h) != 0)
+end
+"`extract_device_policy_sac(h; with_norm)`: the same from a live SAC handle (a `Ptr{Cvoid}` of dril_sac_create), e.g. inside a callback of train!(agent, env, alg::SAC, ...)"
+function extract_device_policy_sac(h::Ptr{Cvoid}; with_norm::Bool = false)
+    pp = Ref{Ptr{Cvoid}}(C_NULL)
+    policy_check(ccall((:dril_policy_from_sac_handle, LIB[]), Int32, (Ptr{Cvoid}, Int32, Ref{Ptr{Cvoid}}), h, Int32(with_norm), pp))
+    return wrap_policy(pp[], ccall((:dril_sac_obs_dim, LIB[]), Int32, (Ptr{Cvoid},), h), ccall((:dril_sac_action_dim, LIB[]), Int32, (Ptr{Cvoid},), h), false)
+end
+# policy(obs; deterministic, seed): one observation (a vector) -> one env action; a vector of observations -> a vector of env actions (deployment_policy.jl:25-41).
+# Sampling draws from the policy's own Philox stream; `seed` restarts it
+function (p::DevicePolicy)(obs; deterministic::Bool = true, seed::Union{Nothing, Integer} = nothing)
+    single = obs isa AbstractVector{<:Real}
+    cols = single ? [obs] : obs
+    B = length(cols)
+    x = Matrix{Float32}(undef, p.obs_dim, B)
+    for (j, o) in enumerate(cols)
+        x[:, j] .= vec(o)
+    end
+    seed === nothing || policy_check(ccall((:dril_policy_set_seed, LIB[]), Int32, (Ptr{Cvoid}, UInt64), p.ptr, UInt64(seed)), p.ptr)
+    if p.discrete
+        a = Vector{Int32}(undef, B)
+        GC.@preserve x a policy_check(ccall((:dril_policy_act, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            p.ptr, x, B, Int32(deterministic), C_NULL, C_NULL, a), p.ptr)
+        acts = Int.(a)
+        return single ? acts[1] : acts
+    end
+    a = Matrix{Float32}(undef, p.action_dim, B)
+    GC.@preserve x a policy_check(ccall((:dril_policy_act, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        p.ptr, x, B, Int32(deterministic), C_NULL, C_NULL, a), p.ptr)
+    acts = [a[:, j] for j in 1:B]
+    return single ? acts[1] : acts
+end
+
+
 # =====================================================================================================================
 # SAC: train!(agent, env::DeviceParallelEnv, alg::SAC, max_steps)  (src/algorithms/sac.jl:406-549) over include/dril_sac.h
