@@ -19,7 +19,7 @@
 #include "dril_internal.h"
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper on plug-ins shares with the SAC handle's (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_policy_internal.h"   // dril_policy_from_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
-#include "dril_env_module.h"   // the plug-in loader shared with dril_sac.hip (and, through it, DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with)
+#include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in kind or a device env plug-in), shared with the SAC handle
 
 using namespace dril;
 
@@ -105,7 +105,7 @@ struct dril_handle {
     float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *bt = nullptr, *flat = nullptr, *norm_out = nullptr;
     double* norm_partials = nullptr; int n_norm_partials = 0;
     float *slabs_a = nullptr, *slabs_c = nullptr; int slab_a = 0, slab_c = 0, Gmax = 0;
-    float* state = nullptr; int32_t* step_count = nullptr; uint32_t *episode = nullptr, *gstep = nullptr; float* disc_returns = nullptr;
+    DeviceEnvs env;   // the envs on the device: simulator state and counters, the seed, and for DRIL_ENV_MODULE the loaded plug-in (dril_env_side.h)
     float *obs = nullptr, *rew = nullptr, *adv = nullptr, *ret = nullptr, *logp = nullptr, *val = nullptr, *boot = nullptr, *last_values = nullptr;
     void* act = nullptr; uint8_t* flags = nullptr;
     void* noise_dev = nullptr; bool noise_set = false;
@@ -115,9 +115,8 @@ struct dril_handle {
     float* step_stats = nullptr; int step_stats_cap = 0;
     int *stop_flag = nullptr, *nan_flag = nullptr;
     float *e_obs = nullptr, *e_rew = nullptr, *e_tobs = nullptr; uint8_t *e_term = nullptr, *e_trunc = nullptr; void* e_act = nullptr;
-    uint64_t env_seed0 = 0, adam_steps = 0, update_counter = 0; uint32_t policy_calls = 0;
+    uint64_t adam_steps = 0, update_counter = 0; uint32_t policy_calls = 0;
     float lr = 0;
-    bool env_ready = false;
     unsigned long long* dbg = nullptr;
     bool force_allreduce = false, force_stepwise = false;
     double *epoch_tables = nullptr, *epoch_stats = nullptr; int epoch_blocks = 2048, epoch_nb_cap = 0;   // per-epoch advantage moments
@@ -137,8 +136,6 @@ struct dril_handle {
     bool external = false; bool generic = false; float* gen_tmp = nullptr;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
     GenericDims gd{}; GenericWs gws; int ext_t = 0; bool ext_acted = false;   // DRIL_ENV_EXTERNAL: host envs, generic kernels
     float* ext_stage_rew = nullptr; uint8_t* ext_stage_flags = nullptr;   // pinned [T][E] staging: dril_ext_record returns without draining the stream
-    // DRIL_ENV_MODULE: a device env plug-in (include/device/dril_env_plugin.h) loaded as a HIP module; its three kernels stand in for env_reset / env_observe / env_step_kernel
-    bool module = false; hipModule_t env_module = nullptr; hipFunction_t mod_reset = nullptr, mod_observe = nullptr, mod_step = nullptr; DrilEnvPluginDesc mod_desc{};
     // NormalizeWrapperEnv around a plug-in env (dril_normalize_enable; kernels: dril_norm_wrap.h, dril_ppo_norm.h).  pn_red: the one row a data-parallel job all-reduces.
     // The wrapper's other arrays are the handle's own: disc_returns (`returns`), e_obs_raw / e_rew (old_obs / old_rewards: dril_normalize_get_original), e_rew_n (the
     // rewards dril_env_step delivers)
@@ -307,6 +304,10 @@ MonitorArgs monitor_step_args(dril_handle* h) {   // one env step: finished epis
     MonitorArgs m{}; if (h->mon_cur_ret) { m.cur_ret = h->mon_cur_ret; m.cur_len = h->mon_cur_len; m.ep_ret = h->e_ep_ret; m.ep_len = h->e_ep_len; m.flags_out = h->e_flags; }
     return m;
 }
+MonitorArgs monitor_rollout_args(dril_handle* h, size_t k) {   // row k / E of a step-granular rollout over a plug-in: the BUF_FLAGS byte always, finished episodes with the monitor on
+    MonitorArgs m{}; m.flags_out = h->flags + k; if (h->mon_cur_ret) { m.cur_ret = h->mon_cur_ret; m.cur_len = h->mon_cur_len; m.ep_ret = h->ep_ret + k; m.ep_len = h->ep_len + k; }
+    return m;
+}
 int monitor_collect_step(dril_handle* h) {
     if (!h->mon_cur_ret) return DRIL_OK;
     HIPCHK(h, launch_monitor_collect(h->e_flags, h->e_ep_ret, h->e_ep_len, h->cfg.n_envs, 1, h->cfg.monitor_window, h->mon_cnt, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->stream));
@@ -318,37 +319,12 @@ int monitor_collect_rollout(dril_handle* h) {
     return DRIL_OK;
 }
 
-// ---- device env plug-ins (DRIL_ENV_MODULE) ----
-// One argument block for the three kernels; ceil(E / 256) workgroups of 256 threads, one thread per env (the kernels check e < E).
-DrilEnvPluginArgs module_args(dril_handle* h) {
-    DrilEnvPluginArgs a{};
-    a.E = h->cfg.n_envs; a.episode_len = h->cfg.episode_len; a.fixed_len = h->cfg.fixed_length_episodes; a.action_start = h->cfg.action_start; a.seed0 = h->env_seed0;
-    a.state = h->state; a.step_count = h->step_count; a.episode = h->episode; a.gstep = h->gstep;
-    return a;
+// act!(env, actions) through the E-sized per-step arrays (dril_env_step, dril_evaluate_agent, the step-granular verbs), and MonitorWrapperEnv's window after it
+int env_step_arrays(dril_handle* h, const void* actions) {
+    HIPCHK(h, h->env.step(actions, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, nullptr}, monitor_step_args(h), h->stream));
+    return monitor_collect_step(h);
 }
-hipError_t module_launch(dril_handle* h, hipFunction_t f, DrilEnvPluginArgs a) { return env_module_launch(f, a, h->stream); }
-// reset!(env) / observe(env) / act!(env, actions) of whichever env the handle holds: a built-in kind's kernels or the plug-in's
-hipError_t env_reset_any(dril_handle* h) {
-    if (h->module) return module_launch(h, h->mod_reset, module_args(h));
-    return launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, h->env_seed0, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream);
-}
-hipError_t env_observe_any(dril_handle* h, float* obs) {
-    if (h->module) { DrilEnvPluginArgs a = module_args(h); a.obs = obs; return module_launch(h, h->mod_observe, a); }
-    return launch_env_observe(h->cfg.env_kind, h->cfg.n_envs, h->state, obs, h->stream);
-}
-// the step through the E-sized per-step arrays (dril_env_step, dril_evaluate_agent)
-hipError_t env_step_any(dril_handle* h, const void* actions) {
-    const MonitorArgs mon = monitor_step_args(h);
-    if (h->module) {
-        DrilEnvPluginArgs a = module_args(h);
-        a.actions = actions; a.rewards = h->e_rew; a.terminated = h->e_term; a.truncated = h->e_trunc; a.terminal_obs = h->e_tobs; a.flags = mon.flags_out;
-        a.mon_cur_ret = mon.cur_ret; a.mon_cur_len = mon.cur_len; a.ep_ret = mon.ep_ret; a.ep_len = mon.ep_len;
-        return module_launch(h, h->mod_step, a);
-    }
-    return launch_env_step(h->cfg.env_kind, h->cfg.n_envs, h->env_seed0, h->cfg.episode_len, h->cfg.fixed_length_episodes, h->cfg.action_start, actions,
-                           h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, mon, h->stream);
-}
-#define NOT_MODULE(h, what) do { if ((h)->module) return fail(h, DRIL_ERR_UNSUPPORTED, what ": NormalizeWrapperEnv is off on this device env plug-in handle (DRIL_ENV_MODULE): switch it on with dril_normalize_enable, then this verb forwards to dril_normalize_*"); } while (0)
+#define NOT_MODULE(h, what) do { if ((h)->env.module) return fail(h, DRIL_ERR_UNSUPPORTED, what ": NormalizeWrapperEnv is off on this device env plug-in handle (DRIL_ENV_MODULE): switch it on with dril_normalize_enable, then this verb forwards to dril_normalize_*"); } while (0)
 
 // data-parallel runs: NormalizeWrapperEnv's batch moments cover every env of the job (the reference has ONE vector env, normalizeWrapperEnv.jl:21-26):
 // this rank's partial table is folded to one row, RCCL sums the rows, and the apply kernels merge that row with n_stats = world * E.  One 128-byte
@@ -372,7 +348,7 @@ int pn_moments(dril_handle* h, bool obs, bool ret, int* rows) {
     *rows = pn_rows(E, D, h->pn_rows_cap);
     const int R = (E + *rows - 1) / *rows;
     *rows = (E + R - 1) / R;
-    const NormMomArgs m{E, D, R, obs ? h->e_obs_raw : nullptr, ret ? h->e_rew : nullptr, h->disc_returns, h->pn.cfg.gamma, h->pn.partials};
+    const NormMomArgs m{E, D, R, obs ? h->e_obs_raw : nullptr, ret ? h->e_rew : nullptr, h->env.disc_returns, h->pn.cfg.gamma, h->pn.partials};
     hipLaunchKernelGGL(norm_moments_kernel<kPnTile>, dim3(*rows, obs ? pn_tiles(D) : 1), dim3(256), 0, h->stream, m);
     HIPCHK(h, hipGetLastError());
     return DRIL_OK;
@@ -401,7 +377,7 @@ int pn_apply(dril_handle* h, PnApplyArgs p, int rows, bool upd_obs, bool upd_ret
 }
 // observe(env) of the wrapper (:123-137): the plug-in's observe kernel into e_obs_raw, then moments + apply into e_obs
 int pn_observe(dril_handle* h, bool update_stats) {
-    HIPCHK(h, env_observe_any(h, h->e_obs_raw));
+    HIPCHK(h, h->env.observe(h->e_obs_raw, h->stream));
     const bool upd = update_stats && h->pn.cfg.training && h->pn.cfg.norm_obs;
     int rows = 0;
     if (upd) { int rc = pn_moments(h, true, false, &rows); if (rc) return rc; }
@@ -410,22 +386,21 @@ int pn_observe(dril_handle* h, bool update_stats) {
 }
 // act!(env, actions) of the wrapper (:139-165) through the E-sized per-step arrays: raw rewards stay in e_rew, the delivered ones go to rew_out
 int pn_step(dril_handle* h, const void* actions, float* rew_out) {
-    HIPCHK(h, env_step_any(h, actions));
-    { int rcm = monitor_collect_step(h); if (rcm) return rcm; }                    // MonitorWrapperEnv sits inside: raw rewards
+    { int rcs = env_step_arrays(h, actions); if (rcs) return rcs; }                // (MonitorWrapperEnv sits inside: raw rewards)
     const bool upd = h->pn.cfg.training && h->pn.cfg.norm_reward;
     int rows = 0;
     if (upd) { int rc = pn_moments(h, false, true, &rows); if (rc) return rc; }
-    PnApplyArgs a{}; a.w.rew = h->e_rew; a.rew_out = rew_out; a.w.returns = h->disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
+    PnApplyArgs a{}; a.w.rew = h->e_rew; a.rew_out = rew_out; a.w.returns = h->env.disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
     return pn_apply(h, a, rows, false, upd);
 }
 
 // ---- step-granular env verbs on device (NormalizeWrapperEnv.observe / act!, normalizeWrapperEnv.jl:123-165) ----
 int observe_dev(dril_handle* h, bool update_stats) {
     const int E = h->cfg.n_envs;
-    if (h->module && h->pn.on) return pn_observe(h, update_stats);                 // a plug-in env under dril_normalize_enable
-    if (h->module) { HIPCHK(h, env_observe_any(h, h->e_obs)); return DRIL_OK; }   // a plug-in env without the wrapper: the observation as it is
+    if (h->env.module && h->pn.on) return pn_observe(h, update_stats);                 // a plug-in env under dril_normalize_enable
+    if (h->env.module) { HIPCHK(h, h->env.observe(h->e_obs, h->stream)); return DRIL_OK; }   // a plug-in env without the wrapper: the observation as it is
     int nb = (E + 255) / 256; if (nb > h->rms_blocks) nb = h->rms_blocks;
-    HIPCHK(h, launch_obs_partials(h->cfg.env_kind, E, h->state, h->e_obs_raw, h->rms_partials, nb, h->stream));
+    HIPCHK(h, launch_obs_partials(h->env.kind, E, h->env.state, h->e_obs_raw, h->rms_partials, nb, h->stream));
     NormObsArgs a{};
     a.E = E; a.D = h->D; a.update = (update_stats && h->cfg.norm_training && h->cfg.norm_obs) ? 1 : 0;
     { int rcg = global_partials(h, a.update != 0, a.partials, nb, a.n_stats); if (rcg) return rcg; }
@@ -439,25 +414,21 @@ int observe_dev(dril_handle* h, bool update_stats) {
 // actions: device pointer (stored/raw policy actions; the kernels apply the adapters); rew_out/flags_out: device destinations
 int step_dev(dril_handle* h, const void* actions, float* rew_out, uint8_t* flags_out) {
     const int E = h->cfg.n_envs;
-    if (h->module && h->pn.on) return pn_step(h, actions, rew_out ? rew_out : h->e_rew_n);
-    if (h->module) {                                                               // plug-in env without the wrapper: the raw step is the whole step
-        HIPCHK(h, env_step_any(h, actions));
-        { int rcm = monitor_collect_step(h); if (rcm) return rcm; }
+    if (h->env.module && h->pn.on) return pn_step(h, actions, rew_out ? rew_out : h->e_rew_n);
+    { int rcs = env_step_arrays(h, actions); if (rcs) return rcs; }
+    if (h->env.module) {                                                               // plug-in env without the wrapper: the raw step is the whole step
         if (rew_out && rew_out != h->e_rew) HIPCHK(h, hipMemcpyAsync(rew_out, h->e_rew, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream));
         return DRIL_OK;
     }
-    HIPCHK(h, launch_env_step(h->cfg.env_kind, E, h->env_seed0, h->cfg.episode_len, h->cfg.fixed_length_episodes, h->cfg.action_start, actions,
-                              h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, monitor_step_args(h), h->stream));
-    { int rcm = monitor_collect_step(h); if (rcm) return rcm; }
     int nb = (E + 255) / 256; if (nb > h->rms_blocks) nb = h->rms_blocks;
     const int upd = (h->cfg.norm_reward && h->cfg.norm_training) ? 1 : 0;
-    HIPCHK(h, launch_rew_partials(E, h->e_rew, h->disc_returns, h->cfg.norm_gamma, upd, h->rms_partials, nb, h->stream));
+    HIPCHK(h, launch_rew_partials(E, h->e_rew, h->env.disc_returns, h->cfg.norm_gamma, upd, h->rms_partials, nb, h->stream));
     NormRewArgs a{};
     a.E = E; a.D = h->D; a.update = upd; a.norm_obs = h->cfg.norm_obs; a.norm_reward = h->cfg.norm_reward;
     { int rcg = global_partials(h, upd != 0, a.partials, nb, a.n_stats); if (rcg) return rcg; }
     a.nblocks = nb;
     a.rew_raw = h->e_rew; a.in = h->ret_rms + h->ret_par; a.out = h->ret_rms + (h->ret_par ^ 1);
-    a.obs_stats = h->obs_rms + h->obs_par; a.rew_out = rew_out; a.disc_returns = h->disc_returns; a.term = h->e_term; a.trunc = h->e_trunc;
+    a.obs_stats = h->obs_rms + h->obs_par; a.rew_out = rew_out; a.disc_returns = h->env.disc_returns; a.term = h->e_term; a.trunc = h->e_trunc;
     a.tobs = h->e_tobs; a.clip_obs = h->cfg.clip_obs; a.clip_reward = h->cfg.clip_reward; a.eps = h->cfg.norm_epsilon; a.flags_out = flags_out;
     HIPCHK(h, launch_norm_rew_apply(a, h->stream));
     h->ret_par ^= 1;
@@ -611,7 +582,8 @@ DRIL_EXPORT int32_t dril_config_default(dril_config* c, int32_t env_kind) {
     if (!c || env_kind < DRIL_ENV_CARTPOLE || env_kind > DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "bad cfg/env_kind");
     std::memset(c, 0, sizeof(*c));
     c->abi_version = DRIL_ABI_VERSION; c->env_kind = env_kind; c->n_envs = 4; c->n_steps = 2048; c->hidden1 = c->hidden2 = 64;
-    c->episode_len = env_kind == DRIL_ENV_MODULE ? 0 /* the descriptor's */ : (env_kind == DRIL_ENV_CARTPOLE || env_kind == DRIL_ENV_ACROBOT) ? 500 : (env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 999 : 200; c->action_start = 1;   // the Gymnasium time limits
+    const EnvKindInfo* k = env_kind_info(env_kind);
+    c->episode_len = k ? k->default_episode_len /* the Gymnasium time limit */ : env_kind == DRIL_ENV_MODULE ? 0 /* the descriptor's */ : 200; c->action_start = 1;
     c->gamma = 0.99f; c->gae_lambda = 0.95f; c->clip_range = 0.2f; c->ent_coef = 0.0f; c->vf_coef = 0.5f;
     c->max_grad_norm = 0.5f; c->has_max_grad_norm = 1; c->normalize_advantage = 1; c->batch_size = 64; c->epochs = 10;
     c->learning_rate = 3.0e-4f; c->adam_beta1 = 0.9f; c->adam_beta2 = 0.999f; c->adam_eps = 1.0e-5f;
@@ -646,8 +618,8 @@ DRIL_EXPORT int32_t dril_env_module_describe(const char* code_object_path, int32
 }
 DRIL_EXPORT int32_t dril_env_module_info_of(const dril_handle* h, dril_env_module_info* out) {
     if (!h || !out) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle / out");
-    if (!h->module) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_env_module_info_of: the handle was not created with dril_create_with_env_module");
-    fill_module_info(h->mod_desc, out);
+    if (!h->env.module) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_env_module_info_of: the handle was not created with dril_create_with_env_module");
+    fill_module_info(h->env.desc, out);
     return DRIL_OK;
 }
 
@@ -673,26 +645,25 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     if (cfg->monitor_window < 0) return fail(nullptr, DRIL_ERR_INVALID_ARG, "monitor_window must be >= 0");
     if (cfg->world_size < 1 || cfg->rank < 0 || cfg->rank >= cfg->world_size) return fail(nullptr, DRIL_ERR_INVALID_ARG, "bad rank/world_size");
     if (cfg->batch_size % cfg->world_size != 0) return fail(nullptr, DRIL_ERR_INVALID_ARG, "batch_size must be divisible by world_size");
-    hipModule_t mod = nullptr; DrilEnvPluginDesc desc{};
-    if (is_module) {                                                                     // the descriptor gives the spaces: load it before anything is sized
-        if (cfg->world_size > 1) setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", /*overwrite=*/0);   // (see below: must precede the process's first HIP call)
-        std::string msg; const int rcm = load_env_module(module_path, cfg->device, &mod, &desc, msg);
-        if (rcm) return fail(nullptr, rcm, "dril_create_with_env_module: " + msg);
-    }
+    // Multi-process RCCL on this platform needs dmabuf IPC: with the legacy IPC mode (the ROCr default) `hipIpcGetMemHandle` fails with "invalid argument" on a
+    // host driver that only supports dmabuf, and ncclCommInitRank / the first collective across processes dies with it.  The ROCr runtime reads the variable
+    // when it initialises, i.e. at this process's first HIP call — which for a DRiL user is normally the plug-in load or the hipSetDevice below.  It is only set if the
+    // caller left it unset (bench.py and the tests export it themselves; a process that already touched HIP before dril_create must export it on its own: README "Multi-GPU").
+    if (cfg->world_size > 1) setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", /*overwrite=*/0);
     dril_handle* h = nullptr;
-    try { h = new dril_handle(); } catch (...) { if (mod) (void)hipModuleUnload(mod); return fail(nullptr, DRIL_ERR_INVALID_ARG, "out of host memory"); }
+    try { h = new dril_handle(); } catch (...) { return fail(nullptr, DRIL_ERR_INVALID_ARG, "out of host memory"); }
     h->cfg = *cfg;
-    if (is_module) { h->module = true; h->env_module = mod; h->mod_desc = desc; if (cfg->episode_len == 0) h->cfg.episode_len = desc.episode_len; }
-    h->cfg.hidden1 = hd[0]; h->cfg.hidden2 = nh > 1 ? hd[1] : hd[0];   // the fused kernels read hidden1 (only reached with two equal layers)
-    switch (cfg->env_kind) {
-        case DRIL_ENV_CARTPOLE: h->discrete = true; h->D = 4; h->A = 2; h->S = 4; break;
-        case DRIL_ENV_MOUNTAINCAR: h->discrete = true; h->D = 2; h->A = 3; h->S = 2; break;
-        case DRIL_ENV_MOUNTAINCAR_CONTINUOUS: case DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED: h->discrete = false; h->D = 2; h->A = 1; h->S = 2; break;
-        case DRIL_ENV_ACROBOT: h->discrete = true; h->D = 6; h->A = 3; h->S = 4; h->generic = !fused_shape; break;   // six observation dims: four first-layer k-steps and three-quad records in every fused kernel (round 3)
-        case DRIL_ENV_MODULE: h->discrete = desc.discrete != 0; h->D = desc.D; h->A = desc.A; h->S = desc.S; h->generic = true; break;   // no fused kernels for a plug-in env
-        case DRIL_ENV_EXTERNAL: h->discrete = cfg->ext_discrete != 0; h->D = cfg->ext_obs_dim; h->A = cfg->ext_action_dim; h->S = 0; h->external = true; h->generic = true; break;
-        default: h->discrete = false; h->D = 3; h->A = 1; h->S = 2; break;                    // Pendulum, ScalingWrapperEnv(Pendulum)
+    {   // a plug-in's descriptor gives the spaces: it is loaded here, before anything is sized
+        std::string msg; const int rcm = h->env.open(cfg->env_kind, cfg->n_envs, cfg->episode_len, cfg->fixed_length_episodes, cfg->action_start, module_path, cfg->device, msg);
+        if (rcm) { delete h; return fail(nullptr, rcm, "dril_create_with_env_module: " + msg); }
+        h->cfg.episode_len = h->env.episode_len;
     }
+    const DrilEnvPluginDesc& desc = h->env.desc;
+    h->cfg.hidden1 = hd[0]; h->cfg.hidden2 = nh > 1 ? hd[1] : hd[0];   // the fused kernels read hidden1 (only reached with two equal layers)
+    const EnvKindInfo* kinfo = env_kind_info(cfg->env_kind);
+    if (kinfo) { h->discrete = kinfo->discrete; h->D = kinfo->D; h->A = kinfo->A; h->S = kinfo->S; }                             // a built-in kind: fused kernels at the fused shapes
+    else if (is_module) { h->discrete = desc.discrete != 0; h->D = desc.D; h->A = desc.A; h->S = desc.S; h->generic = true; }   // no fused kernels for a plug-in env
+    else { h->discrete = cfg->ext_discrete != 0; h->D = cfg->ext_obs_dim; h->A = cfg->ext_action_dim; h->S = 0; h->external = true; h->generic = true; }   // DRIL_ENV_EXTERNAL
     h->gd = GenericDims{h->D, h->A, nh, {hd[0], hd[1], hd[2], hd[3]}, h->discrete ? 1 : 0, cfg->activation};
     if (nh == 2) { h->actor = net_off(0, h->D, hd[0], hd[1], h->A); h->critic = net_off(h->actor.end, h->D, hd[0], hd[1], 1); }
     else {                                                                            // other depths exist on the generic path only, which reads just the first offset and the end of a net
@@ -712,11 +683,6 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     if (const char* e = debug_env("DRIL_SMALL_CHUNK")) { const long c = std::atol(e); if (c > 0) h->small_chunk = c; }   // optimiser steps per launch of ppo_update_small_kernel (tests: launch boundaries)
     h->no_small_path = debug_env("DRIL_NO_SMALL_PATH") != nullptr;
     h->no_f32_retry = std::getenv("DRIL_NO_F32_RETRY") != nullptr;
-    // Multi-process RCCL on this platform needs dmabuf IPC: with the legacy IPC mode (the ROCr default) `hipIpcGetMemHandle` fails with "invalid argument" on a
-    // host driver that only supports dmabuf, and ncclCommInitRank / the first collective across processes dies with it.  The ROCr runtime reads the variable
-    // when it initialises, i.e. at this process's first HIP call — which for a DRiL user is normally the hipSetDevice below.  It is only set if the caller left it
-    // unset (bench.py and the tests export it themselves; a process that already touched HIP before dril_create must export it on its own: README "Multi-GPU").
-    if (cfg->world_size > 1) setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", /*overwrite=*/0);
 #define CCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(_e); dril_destroy(h); return fail(nullptr, DRIL_ERR_HIP, m); } } while (0)
     CCHK(hipSetDevice(cfg->device));
     hipDeviceProp_t prop; CCHK(hipGetDeviceProperties(&prop, cfg->device));
@@ -729,10 +695,6 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
                          ", HIP_VISIBLE_DEVICES=" + (hv ? hv : "(unset)") + " ROCR_VISIBLE_DEVICES=" + (rv ? rv : "(unset)");
     }
     CCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    if (is_module) {
-        CCHK(hipModuleGetFunction(&h->mod_reset, h->env_module, "dril_env_plugin_reset")); CCHK(hipModuleGetFunction(&h->mod_observe, h->env_module, "dril_env_plugin_observe"));
-        CCHK(hipModuleGetFunction(&h->mod_step, h->env_module, "dril_env_plugin_step"));
-    }
     const size_t E = cfg->n_envs, N = (size_t)h->N, P = h->P;
     CCHK(dmalloc(&h->params, P)); CCHK(dmalloc(&h->adam_m, P)); CCHK(dmalloc(&h->adam_v, P)); CCHK(dmalloc(&h->bt, 4));
     CCHK(dmalloc(&h->flat, P + 8)); CCHK(dmalloc(&h->norm_out, 1)); CCHK(dmalloc(&h->w2max_dev, 1));
@@ -740,7 +702,7 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
       CCHK(dmalloc(&h->gae_err, 1)); CCHK(hipMemsetAsync(h->gae_err, 0, 4, h->stream)); }
     h->n_norm_partials = (int)((P + 31) / 32); CCHK(dmalloc(&h->norm_partials, h->n_norm_partials));
     if (h->generic) { h->slab_a = generic_slab_size(h->gd, true); h->slab_c = generic_slab_size(h->gd, false); }
-    else { h->slab_a = slab_size_actor(cfg->env_kind, hd[0]); h->slab_c = slab_size_critic(cfg->env_kind, hd[0]); }
+    else { h->slab_a = slab_size_actor(*kinfo, hd[0]); h->slab_c = slab_size_critic(*kinfo, hd[0]); }
     h->wide = !h->generic && hd[0] > 64;
     h->Gmax = (h->wide && hd[0] > 128) ? (h->num_cus / 2 > 0 ? h->num_cus / 2 : 1) : (!h->wide && h->grad_variant != 0) ? 3 * h->num_cus : h->num_cus;   // H = 128: 4 waves and 77 KB LDS per workgroup, two workgroups per CU   // [64,64]: 2 workgroups per CU (actor + critic), 4 waves each; wide: 1 workgroup of H/32 waves per CU
     if (h->generic) h->Gmax = 64;                                                                                                                                                                                             // generic path: one slab per row chunk of the minibatch
@@ -750,8 +712,7 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
         CCHK(hipMalloc(&h->w2pf_actor, pb)); CCHK(hipMalloc(&h->w2pf_critic, pb)); }
     if (h->wide) { const size_t hh = (size_t)hd[0] * hd[0]; CCHK(dmalloc(&h->w2a_actor, hh)); CCHK(dmalloc(&h->w2ta_actor, hh)); CCHK(dmalloc(&h->w2a_critic, hh)); CCHK(dmalloc(&h->w2ta_critic, hh)); }
     CCHK(dmalloc(&h->slabs_a, (size_t)h->Gmax * h->slab_a)); CCHK(dmalloc(&h->slabs_c, (size_t)h->Gmax * h->slab_c));
-    CCHK(dmalloc(&h->state, E * h->S)); CCHK(dmalloc(&h->step_count, E)); CCHK(dmalloc(&h->episode, E)); CCHK(dmalloc(&h->gstep, E));
-    CCHK(dmalloc(&h->disc_returns, E));
+    CCHK(h->env.alloc(h->S));
     CCHK(dmalloc(&h->obs, N * h->D)); CCHK(hipMalloc(&h->act, N * act_bytes_per(h))); CCHK(dmalloc(&h->rew, N)); CCHK(dmalloc(&h->adv, N));
     CCHK(dmalloc(&h->ret, N)); CCHK(dmalloc(&h->logp, N)); CCHK(dmalloc(&h->val, N)); CCHK(dmalloc(&h->boot, N)); CCHK(dmalloc(&h->flags, N));
     CCHK(dmalloc(&h->last_values, E));
@@ -801,10 +762,9 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
         h->loop = nullptr;
     }
     generic_ws_free(h->gws); pn_free(h);
-    if (h->env_module) (void)hipModuleUnload(h->env_module);
+    h->env.release();
     if (h->ext_stage_rew) (void)hipHostFree(h->ext_stage_rew); if (h->ext_stage_flags) (void)hipHostFree(h->ext_stage_flags);
-    void* ptrs[] = {h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->state,
-                    h->step_count, h->episode, h->gstep, h->disc_returns, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
+    void* ptrs[] = {h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
                     h->flags, h->last_values, h->noise_dev, h->perm_dev, h->epoch_index, h->epoch_keys, h->small_xchg, h->w2max_dev, h->gae_carry, h->gae_err, h->w2pf_actor, h->w2pf_critic, h->adv_partials, h->adv_stats, h->ev_partials, h->step_stats,
                     h->stop_flag, h->nan_flag, h->e_obs, h->e_rew, h->e_tobs, h->e_term, h->e_trunc, h->e_act, h->e_obs_raw, h->e_rew_n, h->obs_rms, h->ret_rms, h->rms_partials, h->rms_red, h->gen_tmp, h->dbg, h->rec, h->epoch_tables, h->epoch_stats, h->w2a_actor, h->w2ta_actor, h->w2a_critic, h->w2ta_critic, h->w2p_actor, h->w2tp_actor, h->w2p_critic, h->w2tp_critic, h->mon_cur_ret, h->ep_ret, h->mon_ring_ret, h->e_ep_ret, h->mon_cur_len, h->ep_len,
                     h->mon_ring_len, h->e_ep_len, h->mon_cnt, h->mon_meta, h->e_flags};
@@ -863,36 +823,33 @@ DRIL_EXPORT int32_t dril_set_optimizer_state(dril_handle* h, const float* m, con
 // ---- env verbs -----------------------------------------------------------------------------------
 DRIL_EXPORT int32_t dril_env_reset(dril_handle* h, uint64_t seed) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_reset");
-    h->env_seed0 = seed + (uint64_t)h->cfg.rank * (uint64_t)h->cfg.n_envs;
-    HIPCHK(h, env_reset_any(h));
+    h->env.seed0 = seed + (uint64_t)h->cfg.rank * (uint64_t)h->cfg.n_envs;
+    HIPCHK(h, h->env.reset(h->stream));
     if (h->mon_cur_ret) { HIPCHK(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)h->cfg.n_envs * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)h->cfg.n_envs * 4, h->stream)); }   // MonitorWrapperEnv.reset! :38-44
     if (h->pn.on) {                                                                  // NormalizeWrapperEnv.reset! :110-121: old_obs = the raw observation, returns = 0, the statistics stay
-        HIPCHK(h, hipMemsetAsync(h->disc_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream)); HIPCHK(h, env_observe_any(h, h->e_obs_raw));
+        HIPCHK(h, hipMemsetAsync(h->env.disc_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream)); HIPCHK(h, h->env.observe(h->e_obs_raw, h->stream));
     }
-    h->env_ready = true;
+    h->env.ready = true;
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_env_observe(dril_handle* h, float* host_obs, int32_t update_stats) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_observe");
-    if (!h->env_ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_env_observe before dril_env_reset");
+    if (!h->env.ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_env_observe before dril_env_reset");
     if (!host_obs) return fail(h, DRIL_ERR_INVALID_ARG, "null host_obs");
     if (normalizing(h) || h->pn.on) { int rc = observe_dev(h, update_stats != 0); if (rc) return rc; }
-    else HIPCHK(h, env_observe_any(h, h->e_obs));
+    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
     HIPCHK(h, hipMemcpyAsync(host_obs, h->e_obs, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_env_step(dril_handle* h, const void* actions, float* rewards, uint8_t* terminated, uint8_t* truncated, float* terminal_obs) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_step");
-    if (!h->env_ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_env_step before dril_env_reset");
+    if (!h->env.ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_env_step before dril_env_reset");
     if (!actions) return fail(h, DRIL_ERR_INVALID_ARG, "null actions");
     const size_t E = h->cfg.n_envs;
     HIPCHK(h, hipMemcpyAsync(h->e_act, actions, E * act_bytes_per(h), hipMemcpyHostToDevice, h->stream));
     float* rew_dev = h->e_rew;
     if (normalizing(h) || h->pn.on) { rew_dev = h->e_rew_n; int rc = step_dev(h, h->e_act, rew_dev, nullptr); if (rc) return rc; }
-    else {
-        HIPCHK(h, env_step_any(h, h->e_act));
-        int rcm = monitor_collect_step(h); if (rcm) return rcm;
-    }
+    else { int rc = env_step_arrays(h, h->e_act); if (rc) return rc; }
     if (rewards) HIPCHK(h, hipMemcpyAsync(rewards, rew_dev, E * 4, hipMemcpyDeviceToHost, h->stream));
     if (terminated) HIPCHK(h, hipMemcpyAsync(terminated, h->e_term, E, hipMemcpyDeviceToHost, h->stream));
     if (truncated) HIPCHK(h, hipMemcpyAsync(truncated, h->e_trunc, E, hipMemcpyDeviceToHost, h->stream));
@@ -901,19 +858,19 @@ DRIL_EXPORT int32_t dril_env_step(dril_handle* h, const void* actions, float* re
 }
 DRIL_EXPORT int32_t dril_env_get_state(dril_handle* h, float* state, int32_t* step_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_get_state"); if (!state) return fail(h, DRIL_ERR_INVALID_ARG, "null state");
-    HIPCHK(h, hipMemcpyAsync(state, h->state, (size_t)h->cfg.n_envs * h->S * 4, hipMemcpyDeviceToHost, h->stream));
-    if (step_count) HIPCHK(h, hipMemcpyAsync(step_count, h->step_count, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(state, h->env.state, (size_t)h->cfg.n_envs * h->S * 4, hipMemcpyDeviceToHost, h->stream));
+    if (step_count) HIPCHK(h, hipMemcpyAsync(step_count, h->env.step_count, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_env_set_state(dril_handle* h, const float* state, const int32_t* step_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_set_state"); if (!state) return fail(h, DRIL_ERR_INVALID_ARG, "null state");
-    HIPCHK(h, hipMemcpyAsync(h->state, state, (size_t)h->cfg.n_envs * h->S * 4, hipMemcpyHostToDevice, h->stream));
-    if (step_count) HIPCHK(h, hipMemcpyAsync(h->step_count, step_count, (size_t)h->cfg.n_envs * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->env.state, state, (size_t)h->cfg.n_envs * h->S * 4, hipMemcpyHostToDevice, h->stream));
+    if (step_count) HIPCHK(h, hipMemcpyAsync(h->env.step_count, step_count, (size_t)h->cfg.n_envs * 4, hipMemcpyHostToDevice, h->stream));
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_norm_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_norm_get_stats");
-    if (h->module && h->pn.on) return dril_normalize_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);   // the wrapper of dril_normalize_enable
+    if (h->env.module && h->pn.on) return dril_normalize_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);   // the wrapper of dril_normalize_enable
     NOT_MODULE(h, "dril_norm_get_stats");
     RmsState o, r;
     HIPCHK(h, hipMemcpyAsync(&o, h->obs_rms + h->obs_par, sizeof(o), hipMemcpyDeviceToHost, h->stream));
@@ -925,7 +882,7 @@ DRIL_EXPORT int32_t dril_norm_get_stats(dril_handle* h, float* obs_mean, float* 
 }
 DRIL_EXPORT int32_t dril_norm_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_norm_set_stats");
-    if (h->module && h->pn.on) return dril_normalize_set_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+    if (h->env.module && h->pn.on) return dril_normalize_set_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
     NOT_MODULE(h, "dril_norm_set_stats");
     if (!obs_mean || !obs_var) return fail(h, DRIL_ERR_INVALID_ARG, "null statistics");
     RmsState o{}, r{};
@@ -938,7 +895,7 @@ DRIL_EXPORT int32_t dril_norm_set_stats(dril_handle* h, const float* obs_mean, c
 
 DRIL_EXPORT int32_t dril_norm_get_original(dril_handle* h, float* obs, float* rewards) {
     NEED(h); NOT_EXTERNAL(h, "dril_norm_get_original");
-    if (h->module && h->pn.on) return dril_normalize_get_original(h, obs, rewards);
+    if (h->env.module && h->pn.on) return dril_normalize_get_original(h, obs, rewards);
     NOT_MODULE(h, "dril_norm_get_original");
     if (!normalizing(h)) return fail(h, DRIL_ERR_NOT_INITIALISED, "NormalizeWrapperEnv is off (cfg.norm_obs == cfg.norm_reward == 0)");
     if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->e_obs_raw, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
@@ -950,7 +907,7 @@ DRIL_EXPORT int32_t dril_norm_get_original(dril_handle* h, float* obs, float* re
 namespace {
 int pn_kind_check(dril_handle* h, const char* what) {
     if (h->external) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there");
-    if (!h->module) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": this verb family wraps a device env plug-in (DRIL_ENV_MODULE); a built-in env is wrapped at create with cfg.norm_obs / cfg.norm_reward (dril_norm_get_stats / dril_norm_set_stats / dril_norm_get_original)");
+    if (!h->env.module) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": this verb family wraps a device env plug-in (DRIL_ENV_MODULE); a built-in env is wrapped at create with cfg.norm_obs / cfg.norm_reward (dril_norm_get_stats / dril_norm_set_stats / dril_norm_get_original)");
     return DRIL_OK;
 }
 #define PN_ON(h, what) do { int _rc = pn_kind_check(h, what); if (_rc) return _rc; \
@@ -981,12 +938,12 @@ DRIL_EXPORT int32_t dril_normalize_enable(dril_handle* h, const dril_normalize_c
     hipError_t e = h->pn.alloc((int)D, (size_t)pn_rows((int)E, (int)D, h->pn_rows_cap));
     if (e == hipSuccess) e = dmalloc(&h->pn_red, Cn);
     if (e == hipSuccess) e = hipMemset(h->pn_red, 0, Cn * 8);
-    if (e == hipSuccess) e = hipMemset(h->disc_returns, 0, E * 4);                     // returns, and the cached originals, start at 0
+    if (e == hipSuccess) e = hipMemset(h->env.disc_returns, 0, E * 4);                     // returns, and the cached originals, start at 0
     if (e == hipSuccess) e = hipMemset(h->e_obs_raw, 0, E * D * 4);
     if (e == hipSuccess) e = hipMemset(h->e_rew, 0, E * 4);
     if (e != hipSuccess) { pn_free(h); return fail(h, DRIL_ERR_HIP, std::string("dril_normalize_enable: ") + hipGetErrorString(e)); }
     h->pn.cfg = c; h->pn.on = true;
-    if (h->env_ready) HIPCHK(h, env_observe_any(h, h->e_obs_raw));                    // old_obs of the envs' present state, as reset! would have stored it
+    if (h->env.ready) HIPCHK(h, h->env.observe(h->e_obs_raw, h->stream));                    // old_obs of the envs' present state, as reset! would have stored it
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_normalize_set_training(dril_handle* h, int32_t training) {
@@ -1027,7 +984,7 @@ DRIL_EXPORT int32_t dril_normalize_get_original(dril_handle* h, float* obs, floa
 DRIL_EXPORT int32_t dril_normalize_get_returns(dril_handle* h, float* returns) {
     NEED(h); PN_ON(h, "dril_normalize_get_returns");
     if (!returns) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_get_returns: null out pointer");
-    HIPCHK(h, hipMemcpyAsync(returns, h->disc_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(returns, h->env.disc_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
 
@@ -1107,15 +1064,15 @@ DRIL_EXPORT int32_t dril_policy_from_handle(dril_handle* h, int32_t with_norm, d
     d.n_hidden = h->gd.nh; for (int l = 0; l < h->gd.nh; ++l) d.hidden[l] = h->gd.H[l];
     d.activation = h->cfg.activation; d.device = h->cfg.device;
     if (!h->discrete) for (int a = 0; a < h->A; ++a) {                                 // the Box the ClampAdapter clamps to (default_adapters.jl:4-11)
-        if (h->module) { d.action_low[a] = h->mod_desc.action_low[a]; d.action_high[a] = h->mod_desc.action_high[a]; }
+        if (h->env.module) { d.action_low[a] = h->env.desc.action_low[a]; d.action_high[a] = h->env.desc.action_high[a]; }
         else if (h->external) { d.action_low[a] = h->cfg.ext_action_low; d.action_high[a] = h->cfg.ext_action_high; }   // low >= high: per-dimension bounds the host env clamps to itself
-        else { const float bnd = h->cfg.env_kind == DRIL_ENV_PENDULUM ? 2.0f : 1.0f; d.action_low[a] = -bnd; d.action_high[a] = bnd; }   // Pendulum's torque; every other built-in Box is [-1, 1]
+        else { const EnvKindInfo* k = env_kind_info(h->env.kind); d.action_low[a] = k->act_lo; d.action_high[a] = k->act_hi; }   // a built-in Box: Pendulum's torque [-2, 2], every other [-1, 1]
     }
     if (with_norm) {
-        if (h->module && h->pn.on) {                                                   // the wrapper of dril_normalize_enable
+        if (h->env.module && h->pn.on) {                                                   // the wrapper of dril_normalize_enable
             d.has_norm = 1; d.clip_obs = h->pn.cfg.clip_obs; d.epsilon = h->pn.cfg.epsilon;
             s.obs_mean = h->pn.half(h->pn.cur); s.obs_var = s.obs_mean + h->D;
-        } else if (!h->module && !h->external && normalizing(h)) {                     // cfg.norm_obs / cfg.norm_reward: the built-in envs' wrapper
+        } else if (!h->env.module && !h->external && normalizing(h)) {                     // cfg.norm_obs / cfg.norm_reward: the built-in envs' wrapper
             d.has_norm = 1; d.clip_obs = h->cfg.clip_obs; d.epsilon = h->cfg.norm_epsilon;
             const RmsState* st = h->obs_rms + h->obs_par;
             s.obs_mean = st->mean; s.obs_var = st->var;
@@ -1148,17 +1105,17 @@ int collect_rollout_stepwise(dril_handle* h) {
         const size_t k = (size_t)t * E;
         const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * (size_t)A)) : nullptr;
         PolicyArgs p = policy_args(h, h->e_obs, E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);
-        p.gstep = h->gstep; p.env_seed0 = h->env_seed0; p.obs_out = h->obs + k * D;
+        p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.obs_out = h->obs + k * D;
         if (t > 0) { p.boot_obs = h->e_tobs; p.boot_where = h->e_trunc; p.boot_out = h->boot + (k - E); }   // :57-61 for step t-1
         HIPCHK(h, run_policy(h, p));   // get_action_and_values, :41
         NormStepArgs s{};
-        s.E = E; s.episode_len = h->cfg.episode_len; s.fixed_len = h->cfg.fixed_length_episodes; s.action_start = h->cfg.action_start;
-        s.seed0 = h->env_seed0; s.gamma = h->cfg.norm_gamma; s.update_ret = (h->cfg.norm_reward && h->cfg.norm_training) ? 1 : 0;
-        s.actions = (const char*)h->act + k * ab; s.state = h->state; s.step_count = h->step_count; s.episode = h->episode; s.gstep = h->gstep;
-        s.disc_returns = h->disc_returns; s.rew_raw = h->e_rew; s.term = h->e_term; s.trunc = h->e_trunc; s.flags_out = h->flags + k;
+        s.E = E; s.episode_len = h->env.episode_len; s.fixed_len = h->env.fixed_len; s.action_start = h->env.action_start;
+        s.seed0 = h->env.seed0; s.gamma = h->cfg.norm_gamma; s.update_ret = (h->cfg.norm_reward && h->cfg.norm_training) ? 1 : 0;
+        s.actions = (const char*)h->act + k * ab; s.state = h->env.state; s.step_count = h->env.step_count; s.episode = h->env.episode; s.gstep = h->env.gstep;
+        s.disc_returns = h->env.disc_returns; s.rew_raw = h->e_rew; s.term = h->e_term; s.trunc = h->e_trunc; s.flags_out = h->flags + k;
         s.tobs_raw = h->e_tobs; s.obs_raw = h->e_obs_raw; s.partials = h->rms_partials;
         if (h->mon_cur_ret) { s.mon_cur_ret = h->mon_cur_ret; s.mon_cur_len = h->mon_cur_len; s.ep_ret = h->ep_ret + k; s.ep_len = h->ep_len + k; }
-        HIPCHK(h, launch_norm_step(h->cfg.env_kind, s, nb, h->stream));                              // to_env + act!, :43-44
+        HIPCHK(h, launch_norm_step(h->env.kind, s, nb, h->stream));                              // to_env + act!, :43-44
         NormApplyArgs ap{};
         ap.E = E; ap.D = D; ap.update_obs = (h->cfg.norm_obs && h->cfg.norm_training) ? 1 : 0; ap.update_ret = s.update_ret;
         ap.norm_obs = h->cfg.norm_obs; ap.norm_reward = h->cfg.norm_reward;
@@ -1166,7 +1123,7 @@ int collect_rollout_stepwise(dril_handle* h) {
         { int rcg = global_partials(h, ap.update_obs || ap.update_ret, ap.partials, nba, ap.n_stats); if (rcg) return rcg; }
         ap.nblocks = nba;
         ap.obs_in = h->obs_rms + h->obs_par; ap.obs_out = h->obs_rms + (h->obs_par ^ 1); ap.ret_in = h->ret_rms + h->ret_par; ap.ret_out = h->ret_rms + (h->ret_par ^ 1);
-        ap.rew_raw = h->e_rew; ap.rew_out = h->rew + k; ap.disc_returns = h->disc_returns; ap.term = h->e_term; ap.trunc = h->e_trunc; ap.tobs = h->e_tobs;
+        ap.rew_raw = h->e_rew; ap.rew_out = h->rew + k; ap.disc_returns = h->env.disc_returns; ap.term = h->e_term; ap.trunc = h->e_trunc; ap.tobs = h->e_tobs;
         ap.obs_raw = h->e_obs_raw; ap.obs_n = h->e_obs; ap.clip_obs = h->cfg.clip_obs; ap.clip_reward = h->cfg.clip_reward; ap.eps = h->cfg.norm_epsilon;
         HIPCHK(h, launch_norm_apply(ap, h->stream));                                                 // new_obs = observe(env), :45
         h->obs_par ^= 1; h->ret_par ^= 1;
@@ -1184,19 +1141,15 @@ int collect_rollout_stepwise(dril_handle* h) {
 int collect_rollout_module(dril_handle* h) {
     const int E = h->cfg.n_envs, T = h->cfg.n_steps, D = h->D, A = h->A;
     const size_t ab = act_bytes_per(h);
-    HIPCHK(h, env_observe_any(h, h->e_obs));                                               // new_obs = observe(env), trajectory.jl:32
+    HIPCHK(h, h->env.observe(h->e_obs, h->stream));                                               // new_obs = observe(env), trajectory.jl:32
     for (int t = 0; t < T; ++t) {
         const size_t k = (size_t)t * E;
         const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * (size_t)A)) : nullptr;
         PolicyArgs p = policy_args(h, h->e_obs, E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);
-        p.gstep = h->gstep; p.env_seed0 = h->env_seed0; p.obs_out = h->obs + k * D;
+        p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.obs_out = h->obs + k * D;
         if (t > 0) { p.boot_obs = h->e_tobs; p.boot_where = h->e_trunc; p.boot_out = h->boot + (k - E); }   // :57-61 for step t-1
         HIPCHK(h, run_policy(h, p));                                                       // get_action_and_values, :41
-        DrilEnvPluginArgs s = module_args(h);
-        s.actions = (const char*)h->act + k * ab; s.rewards = h->rew + k; s.terminated = h->e_term; s.truncated = h->e_trunc; s.flags = h->flags + k;
-        s.terminal_obs = h->e_tobs; s.obs = h->e_obs;
-        if (h->mon_cur_ret) { s.mon_cur_ret = h->mon_cur_ret; s.mon_cur_len = h->mon_cur_len; s.ep_ret = h->ep_ret + k; s.ep_len = h->ep_len + k; }
-        HIPCHK(h, module_launch(h, h->mod_step, s));                                       // to_env + act! + observe, :43-45
+        HIPCHK(h, h->env.step((const char*)h->act + k * ab, EnvStepOut{h->rew + k, h->e_term, h->e_trunc, h->e_tobs, h->e_obs}, monitor_rollout_args(h, k), h->stream));   // to_env + act! + observe, :43-45
     }
     PolicyArgs l = policy_args(h, h->e_obs, E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);
     l.boot_obs = h->e_tobs; l.boot_where = h->e_trunc; l.boot_out = h->boot + (size_t)(T - 1) * E;
@@ -1216,18 +1169,14 @@ int collect_rollout_module_norm(dril_handle* h) {
         const size_t k = (size_t)t * E;
         const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * (size_t)A)) : nullptr;
         PolicyArgs p = policy_args(h, h->e_obs, E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);
-        p.gstep = h->gstep; p.env_seed0 = h->env_seed0; p.obs_out = h->obs + k * D;
+        p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.obs_out = h->obs + k * D;
         if (t > 0) { p.boot_obs = h->e_tobs; p.boot_where = h->e_trunc; p.boot_out = h->boot + (k - E); }   // :57-61 for step t-1
         HIPCHK(h, run_policy(h, p));                                                       // get_action_and_values, :41
-        DrilEnvPluginArgs s = module_args(h);
-        s.actions = (const char*)h->act + k * ab; s.rewards = h->e_rew; s.terminated = h->e_term; s.truncated = h->e_trunc; s.flags = h->flags + k;
-        s.terminal_obs = h->e_tobs; s.obs = h->e_obs_raw;
-        if (h->mon_cur_ret) { s.mon_cur_ret = h->mon_cur_ret; s.mon_cur_len = h->mon_cur_len; s.ep_ret = h->ep_ret + k; s.ep_len = h->ep_len + k; }
-        HIPCHK(h, module_launch(h, h->mod_step, s));                                       // to_env + the env's own act! + raw observe
+        HIPCHK(h, h->env.step((const char*)h->act + k * ab, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->e_obs_raw}, monitor_rollout_args(h, k), h->stream));   // to_env + the env's own act! + raw observe
         int rows = 0;
         if (upd_obs || upd_ret) { rc = pn_moments(h, upd_obs, upd_ret, &rows); if (rc) return rc; }
         PnApplyArgs a{}; a.w.raw = h->e_obs_raw; a.w.obs_out = h->e_obs;
-        a.w.rew = h->e_rew; a.rew_out = h->rew + k; a.w.returns = h->disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
+        a.w.rew = h->e_rew; a.rew_out = h->rew + k; a.w.returns = h->env.disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
         rc = pn_apply(h, a, rows, upd_obs, upd_ret); if (rc) return rc;                    // the wrapper's act! :139-165 and observe :123-137
     }
     PolicyArgs l = policy_args(h, h->e_obs, E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);
@@ -1237,13 +1186,13 @@ int collect_rollout_module_norm(dril_handle* h) {
 }
 
 int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
-    if (!h->env_ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset");
+    if (!h->env.ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset");
     { int rcw = ensure_wimg(h); if (rcw) return rcw; }
     if (normalizing(h) || h->force_stepwise || h->generic) {            // generic nets have no fused rollout kernel: step-granular launches
         const auto t0s = std::chrono::steady_clock::now();
         if (fps) HIPCHK(h, hipStreamSynchronize(h->stream));
         prof_begin(h, DRIL_K_ROLLOUT);
-        int rcs = h->module ? (h->pn.on ? collect_rollout_module_norm(h) : collect_rollout_module(h)) : collect_rollout_stepwise(h);
+        int rcs = h->env.module ? (h->pn.on ? collect_rollout_module_norm(h) : collect_rollout_module(h)) : collect_rollout_stepwise(h);
         prof_end(h);
         if (rcs) return rcs;
         if (fps) { HIPCHK(h, hipStreamSynchronize(h->stream)); const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0s).count(); *fps = (double)h->N / (dt > 0 ? dt : 1e-12); }
@@ -1252,18 +1201,18 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
         return do_sync ? sync(h) : DRIL_OK;
     }
     RolloutArgs a{};
-    a.params = h->params; a.state = h->state; a.step_count = h->step_count; a.episode = h->episode; a.gstep = h->gstep;
+    a.params = h->params; a.state = h->env.state; a.step_count = h->env.step_count; a.episode = h->env.episode; a.gstep = h->env.gstep;
     a.obs = h->obs; a.act = h->act; a.rew = h->rew; a.logp = h->logp; a.val = h->val; a.boot = h->boot; a.flags = h->flags; a.last_values = h->last_values;
     a.noise = h->noise_set ? h->noise_dev : nullptr;
-    a.E = h->cfg.n_envs; a.T = h->cfg.n_steps; a.episode_len = h->cfg.episode_len; a.fixed_len = h->cfg.fixed_length_episodes;
-    a.action_start = h->cfg.action_start; a.log_std_off = h->log_std_off; a.env_seed0 = h->env_seed0; a.actor = h->actor; a.critic = h->critic;
+    a.E = h->env.E; a.T = h->cfg.n_steps; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len;
+    a.action_start = h->env.action_start; a.log_std_off = h->log_std_off; a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic;
     a.exact_f32 = fwd_exact(h) ? 1 : 0;
     a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = a.exact_f32 ? h->w2a_critic : (const float*)h->w2pf_critic;
     a.mon_cur_ret = h->mon_cur_ret; a.mon_cur_len = h->mon_cur_len; a.ep_ret = h->ep_ret; a.ep_len = h->ep_len;
     const auto t0 = std::chrono::steady_clock::now();
     if (fps) HIPCHK(h, hipStreamSynchronize(h->stream));
     prof_begin(h, DRIL_K_ROLLOUT);
-    HIPCHK(h, launch_rollout(h->cfg.env_kind, h->cfg.hidden1, a, h->stream));
+    HIPCHK(h, launch_rollout(h->env.kind, h->cfg.hidden1, a, h->stream));
     prof_end(h);
     if (fps) {   // fps = steps / wall time of collect_trajectories, rollout_buffer.jl:60-64
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1721,18 +1670,18 @@ DRIL_EXPORT int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval, int32_t 
     if (n_eval < 1 || !out) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
     const int E = h->cfg.n_envs;
     int rc = ensure_wimg(h); if (rc) return rc;
-    if (h->module && h->pn.on) {                                                 // a plug-in env under dril_normalize_enable: the statistics in force, frozen; nothing of the wrapper moves
+    if (h->env.module && h->pn.on) {                                                 // a plug-in env under dril_normalize_enable: the statistics in force, frozen; nothing of the wrapper moves
         const size_t ED = (size_t)E * h->D;
         float* keep = nullptr; HIPCHK(h, dmalloc(&keep, ED + 2 * (size_t)E));    // returns | old_rewards | old_obs
         const int training = h->pn.cfg.training;
-        hipError_t e = hipMemcpyAsync(keep, h->disc_returns, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
+        hipError_t e = hipMemcpyAsync(keep, h->env.disc_returns, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(keep + E, h->e_rew, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(keep + 2 * (size_t)E, h->e_obs_raw, ED * 4, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) {
             h->pn.cfg.training = 0;                                              // set_training(eval_env, false): neither statistics nor `returns` are updated
             rc = evaluate_agent_loop(h, n_eval, deterministic, out, ep_rewards, ep_lengths, /*raw_rewards=*/true);
             h->pn.cfg.training = training;
-            e = hipMemcpyAsync(h->disc_returns, keep, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
+            e = hipMemcpyAsync(h->env.disc_returns, keep, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(h->e_rew, keep + E, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(h->e_obs_raw, keep + 2 * (size_t)E, ED * 4, hipMemcpyDeviceToDevice, h->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1748,16 +1697,16 @@ namespace {
 int evaluate_agent_loop(dril_handle* h, int32_t n_eval, int32_t deterministic, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths, bool raw) {
     const int E = h->cfg.n_envs;
     int rc = DRIL_OK;
-    HIPCHK(h, env_reset_any(h));   // reset!(env), :87
+    HIPCHK(h, h->env.reset(h->stream));   // reset!(env), :87
     if (h->mon_cur_ret) { HIPCHK(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)E * 4, h->stream)); }
-    h->env_ready = true;
+    h->env.ready = true;
     std::vector<float> rew(E), cur_r(E, 0.f), er; std::vector<uint8_t> term(E), trunc(E); std::vector<int32_t> cur_l(E, 0), el;
     float* rew_n = h->e_rew_n;                                                   // wrapper-delivered rewards (see dril_env_step)
     rc = observe_dev(h, true); if (rc) return rc;                                // observations = observe(env), :88
     int steps = 0;
     while ((int)er.size() < n_eval) {
         PolicyArgs p = policy_args(h, h->e_obs, E, nullptr, h->e_act, nullptr, h->logp /*scratch*/, nullptr, 0);
-        p.gstep = h->gstep; p.env_seed0 = h->env_seed0; p.deterministic = deterministic ? 1 : 0;
+        p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.deterministic = deterministic ? 1 : 0;
         p.logp = h->e_rew;                                                       // logprobs are not needed: park them in a scratch array
         HIPCHK(h, run_policy(h, p));   // predict_actions(agent, observations; deterministic), :92
         rc = step_dev(h, h->e_act, rew_n, nullptr); if (rc) return rc;           // act!(env, actions), :94

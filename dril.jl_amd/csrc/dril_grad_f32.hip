@@ -297,19 +297,6 @@ template <int KIND, int H> static size_t grad_lds_bytes() {
     return sizeof(float) * (wa > wc ? wa : wc);
 }
 
-// kind 2 (ScalingWrapperEnv(Pendulum)) shares every kernel that never touches the simulator with kind 1
-// hidden 64, and 32 (the reference's own benchmark suite shape, benchmark/bench_utils.jl:31,49: one m-tile per layer on the same templates)
-#define DRIL_DISPATCH_HH(K, hidden, CALL) { if ((hidden) == 64) { CALL(K, 64); } else if ((hidden) == 32) { CALL(K, 32); } else return hipErrorInvalidValue; }
-#define DRIL_DISPATCH(kind, hidden, CALL)                                            \
-    do {                                                                             \
-        if ((kind) == 0) DRIL_DISPATCH_HH(0, hidden, CALL)                           \
-        else if ((kind) == 1 || (kind) == 2) DRIL_DISPATCH_HH(1, hidden, CALL)       \
-        else if ((kind) == 3) DRIL_DISPATCH_HH(3, hidden, CALL)                      \
-        else if ((kind) == 4 || (kind) == 7) DRIL_DISPATCH_HH(4, hidden, CALL)       \
-        else if ((kind) == 6) DRIL_DISPATCH_HH(6, hidden, CALL)                      \
-        else return hipErrorInvalidValue;                                            \
-    } while (0)
-
 hipError_t launch_ppo_grad_f32(int kind, int hidden, const GradArgs& a, hipStream_t s) {
 #define CALLR(K, HH, R)                                                                                       \
     {                                                                                                         \
@@ -318,10 +305,13 @@ hipError_t launch_ppo_grad_f32(int kind, int hidden, const GradArgs& a, hipStrea
         ppo_grad_kernel<K, HH, R><<<2 * a.G, 256, lds, s>>>(a);                                               \
     }
 #define CALL(K, HH) { if (a.rec) CALLR(K, HH, true) else CALLR(K, HH, false) }
-    DRIL_DISPATCH(kind, hidden, CALL);
+    return with_env_kind<KindShare::Shape>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;   // hidden 64, and 32 (the reference's own benchmark suite shape, benchmark/bench_utils.jl:31,49: one m-tile per layer on the same templates)
+        if (hidden == 64) CALL(KIND, 64) else if (hidden == 32) CALL(KIND, 32) else return hipErrorInvalidValue;
+        return hipGetLastError();
+    });
 #undef CALL
 #undef CALLR
-    return hipGetLastError();
 }
 
 }  // namespace dril

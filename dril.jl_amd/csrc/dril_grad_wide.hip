@@ -341,7 +341,6 @@ template <int KIND, int H> static size_t grad_wide_split_lds_bytes() {
 }
 
 hipError_t launch_ppo_grad_wide(int kind, int hidden, const GradArgs& a, hipStream_t s) {
-    if (kind == 7) kind = 4;                  // ScalingWrapperEnv(MountainCarContinuous): the update never touches the simulator
     if (a.variant && a.rec) {      // f16 matrix cores (two-piece split)
 #define CALLWS(K, HH)                                                                                         \
     {                                                                                                         \
@@ -350,10 +349,13 @@ hipError_t launch_ppo_grad_wide(int kind, int hidden, const GradArgs& a, hipStre
         ppo_grad_wide_split_kernel<K, HH, 1><<<2 * a.G, HH * 2, lds, s>>>(a);                                    \
     }
 #define CALLWSH(K) { if (hidden == 256) CALLWS(K, 256) else if (hidden == 128) CALLWS(K, 128) else return hipErrorInvalidValue; }
-        if (kind == 0) CALLWSH(0) else if (kind == 3) CALLWSH(3) else if (kind == 4) CALLWSH(4) else if (kind == 6) CALLWSH(6) else CALLWSH(1)
+        return with_env_kind<KindShare::Shape>(kind, [&](auto K) -> hipError_t {
+            constexpr int KIND = decltype(K)::value;
+            CALLWSH(KIND)
+            return hipGetLastError();
+        });
 #undef CALLWSH
 #undef CALLWS
-        return hipGetLastError();
     }
 #define CALLW(K, HH, R)                                                                                       \
     {                                                                                                         \
@@ -363,11 +365,14 @@ hipError_t launch_ppo_grad_wide(int kind, int hidden, const GradArgs& a, hipStre
     }
 #define CALLWK(K, HH) { if (a.rec) CALLW(K, HH, true) else CALLW(K, HH, false) }
 #define CALLWH(K) { if (hidden == 256) CALLWK(K, 256) else if (hidden == 128) CALLWK(K, 128) else return hipErrorInvalidValue; }
-    if (kind == 0) CALLWH(0) else if (kind == 3) CALLWH(3) else if (kind == 4) CALLWH(4) else if (kind == 6) CALLWH(6) else CALLWH(1)
+    return with_env_kind<KindShare::Shape>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;
+        CALLWH(KIND)
+        return hipGetLastError();
+    });
 #undef CALLWH
 #undef CALLWK
 #undef CALLW
-    return hipGetLastError();
 }
 
 }  // namespace dril

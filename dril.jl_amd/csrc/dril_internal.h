@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "dril_device.h"
+#include "dril_env_kinds.h"   // the built-in env kinds: every launcher below that takes `kind` dispatches through with_env_kind
 
 // The forward of rollout_kernel / rollout_duo_kernel / policy_kernel puts ONE operand on f16 pieces: kTanhScale kWScale W2 (h1 = tanh is bounded, L1 and L3 are f32).
 // A W2 entry at or beyond this magnitude would overflow its hi piece (2.885 x 64 x 354.7 = 65 504), so the host tracks max |W2| of both nets (dril_set_params, and with
@@ -173,8 +174,8 @@ hipError_t launch_explained_var(const float* val, const float* ret, int64_t N, d
 hipError_t launch_build_wimg(const float* params, NetOff off, int H, float* w2a, float* w2ta, hipStream_t s);
 hipError_t launch_w2_absmax(const float* params, NetOff actor, NetOff critic, int H, unsigned* out_bits, hipStream_t s);   // max |W2| of both nets, as float bits
 hipError_t launch_build_wimg_split(const float* params, NetOff off, int H, void* w2p, void* w2tp, void* w2pf, hipStream_t s);
-int slab_size_actor(int kind, int hidden);
-int slab_size_critic(int kind, int hidden);
+int slab_size_actor(const EnvKindInfo& k, int hidden);
+int slab_size_critic(const EnvKindInfo& k, int hidden);
 
 // generic (any obs / action / hidden width) on-policy path, dril_generic.hip; same argument blocks and slab format as the fused kernels
 constexpr int kMaxHidden = 4;

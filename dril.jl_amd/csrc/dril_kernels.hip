@@ -1275,41 +1275,9 @@ __global__ __launch_bounds__(256) void explained_var_kernel(const float* __restr
 template <int KIND, int H, bool WIDE, bool SPLIT> static size_t fwd_lds_bytes() {
     return sizeof(float) * (FwdLds<EnvSpec<KIND>::D, H, EnvSpec<KIND>::A, WIDE, SPLIT>::SIZE + FwdLds<EnvSpec<KIND>::D, H, 1, WIDE, SPLIT>::SIZE);
 }
-// kind 2 (ScalingWrapperEnv(Pendulum)) shares every kernel that never touches the simulator with kind 1
-#define DRIL_DISPATCH(kind, hidden, CALL)                                            \
-    do {                                                                             \
-        if ((kind) == 0 && (hidden) == 64) { CALL(0, 64); }                          \
-        else if (((kind) == 1 || (kind) == 2) && (hidden) == 64) { CALL(1, 64); }    \
-        else if ((kind) == 3 && (hidden) == 64) { CALL(3, 64); }                     \
-        else if (((kind) == 4 || (kind) == 7) && (hidden) == 64) { CALL(4, 64); }    \
-        else return hipErrorInvalidValue;                                            \
-    } while (0)
-
-// every kernel below is built for hidden widths 64 (one wave per net), 128 and 256 (wide path)
+// the forward / rollout kernels are built for hidden widths 64 (one wave per net), 128 and 256 (wide path) and 32; the kind comes from with_env_kind (dril_env_kinds.h)
 #define DRIL_DISPATCH_H(K, hidden, CALL)                                             \
     { if ((hidden) == 64) { CALL(K, 64); } else if ((hidden) == 128) { CALL(K, 128); } else if ((hidden) == 256) { CALL(K, 256); } else if ((hidden) == 32) { CALL(K, 32); } else return hipErrorInvalidValue; }
-#define DRIL_DISPATCH_FWD(kind, hidden, CALL)                                        \
-    do {                                                                             \
-        if ((kind) == 0) DRIL_DISPATCH_H(0, hidden, CALL)                            \
-        else if ((kind) == 1 || (kind) == 2) DRIL_DISPATCH_H(1, hidden, CALL)        \
-        else if ((kind) == 3) DRIL_DISPATCH_H(3, hidden, CALL)                       \
-        else if ((kind) == 4 || (kind) == 7) DRIL_DISPATCH_H(4, hidden, CALL)        \
-        else if ((kind) == 6) DRIL_DISPATCH_H(6, hidden, CALL)                       \
-        else return hipErrorInvalidValue;                                            \
-    } while (0)
-
-// kernels that step / observe the simulator: one instantiation per env kind
-#define DRIL_DISPATCH_ENV(kind, hidden, CALL)                                        \
-    do {                                                                             \
-        if ((kind) == 0) DRIL_DISPATCH_H(0, hidden, CALL)                            \
-        else if ((kind) == 1) DRIL_DISPATCH_H(1, hidden, CALL)                       \
-        else if ((kind) == 2) DRIL_DISPATCH_H(2, hidden, CALL)                       \
-        else if ((kind) == 3) DRIL_DISPATCH_H(3, hidden, CALL)                       \
-        else if ((kind) == 4) DRIL_DISPATCH_H(4, hidden, CALL)                       \
-        else if ((kind) == 7) DRIL_DISPATCH_H(7, hidden, CALL)                       \
-        else if ((kind) == 6) DRIL_DISPATCH_H(6, hidden, CALL)                       \
-        else return hipErrorInvalidValue;                                            \
-    } while (0)
 
 hipError_t launch_fold_partials(const double* partials, int nblocks, double* out16, hipStream_t s) {
     fold_partials_kernel<<<1, 256, 0, s>>>(partials, nblocks, out16);
@@ -1342,34 +1310,26 @@ hipError_t launch_build_wimg(const float* params, NetOff off, int H, float* w2a,
 
 hipError_t launch_env_reset(int kind, int E, uint64_t seed0, float* state, int32_t* sc, uint32_t* ep, uint32_t* gs, float* dr, hipStream_t s) {
     const int blocks = (E + 255) / 256;
-    if (kind == 0) env_reset_kernel<0><<<blocks, 256, 0, s>>>(E, seed0, state, sc, ep, gs, dr);
-    else if (kind == 3 || kind == 4 || kind == 7) env_reset_kernel<3><<<blocks, 256, 0, s>>>(E, seed0, state, sc, ep, gs, dr);
-    else if (kind == 6) env_reset_kernel<6><<<blocks, 256, 0, s>>>(E, seed0, state, sc, ep, gs, dr);
-    else env_reset_kernel<1><<<blocks, 256, 0, s>>>(E, seed0, state, sc, ep, gs, dr);
-    return hipGetLastError();
+    return with_env_kind<KindShare::Reset>(kind, [&](auto K) {
+        env_reset_kernel<decltype(K)::value><<<blocks, 256, 0, s>>>(E, seed0, state, sc, ep, gs, dr);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_env_observe(int kind, int E, const float* state, float* obs, hipStream_t s) {
     const int blocks = (E + 255) / 256;
-    if (kind == 0) env_observe_kernel<0><<<blocks, 256, 0, s>>>(E, state, obs);
-    else if (kind == 1) env_observe_kernel<1><<<blocks, 256, 0, s>>>(E, state, obs);
-    else if (kind == 2) env_observe_kernel<2><<<blocks, 256, 0, s>>>(E, state, obs);
-    else if (kind == 6) env_observe_kernel<6><<<blocks, 256, 0, s>>>(E, state, obs);
-    else if (kind == 7) env_observe_kernel<7><<<blocks, 256, 0, s>>>(E, state, obs);
-    else env_observe_kernel<3><<<blocks, 256, 0, s>>>(E, state, obs);
-    return hipGetLastError();
+    return with_env_kind<KindShare::Observe>(kind, [&](auto K) {
+        env_observe_kernel<decltype(K)::value><<<blocks, 256, 0, s>>>(E, state, obs);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_env_step(int kind, int E, uint64_t seed0, int episode_len, int fixed_len, int action_start, const void* actions,
                            float* state, int32_t* sc, uint32_t* ep, uint32_t* gs, float* rew, uint8_t* term, uint8_t* trunc,
                            float* tobs, MonitorArgs mon, hipStream_t s) {
     const int blocks = (E + 255) / 256;
-    if (kind == 0) env_step_kernel<0><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
-    else if (kind == 1) env_step_kernel<1><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
-    else if (kind == 2) env_step_kernel<2><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
-    else if (kind == 3) env_step_kernel<3><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
-    else if (kind == 6) env_step_kernel<6><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
-    else if (kind == 7) env_step_kernel<7><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
-    else env_step_kernel<4><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
-    return hipGetLastError();
+    return with_env_kind<KindShare::None>(kind, [&](auto K) {
+        env_step_kernel<decltype(K)::value><<<blocks, 256, 0, s>>>(E, seed0, episode_len, fixed_len, action_start, actions, state, sc, ep, gs, rew, term, trunc, tobs, mon);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_monitor_collect(const uint8_t* flags, const float* ep_ret, const int32_t* ep_len, int E, int T, int W, int* cnt,
                                   float* ring_ret, int32_t* ring_len, int* meta, hipStream_t s) {
@@ -1379,9 +1339,10 @@ hipError_t launch_monitor_collect(const uint8_t* flags, const float* ep_ret, con
 }
 
 hipError_t launch_norm_step(int kind, const NormStepArgs& a, int nblocks, hipStream_t s) {
-    if (kind == 0) norm_step_kernel<0><<<nblocks, 256, 0, s>>>(a); else if (kind == 1) norm_step_kernel<1><<<nblocks, 256, 0, s>>>(a); else if (kind == 2) norm_step_kernel<2><<<nblocks, 256, 0, s>>>(a);
-    else if (kind == 3) norm_step_kernel<3><<<nblocks, 256, 0, s>>>(a); else if (kind == 6) norm_step_kernel<6><<<nblocks, 256, 0, s>>>(a); else if (kind == 7) norm_step_kernel<7><<<nblocks, 256, 0, s>>>(a); else norm_step_kernel<4><<<nblocks, 256, 0, s>>>(a);
-    return hipGetLastError();
+    return with_env_kind<KindShare::None>(kind, [&](auto K) {
+        norm_step_kernel<decltype(K)::value><<<nblocks, 256, 0, s>>>(a);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_norm_apply(const NormApplyArgs& a, hipStream_t s) {
     int blocks = (a.E + 255) / 256; if (blocks > 1024) blocks = 1024;
@@ -1389,13 +1350,10 @@ hipError_t launch_norm_apply(const NormApplyArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 hipError_t launch_obs_partials(int kind, int E, const float* state, float* raw, double* partials, int nblocks, hipStream_t s) {
-    if (kind == 0) obs_partials_kernel<0><<<nblocks, 256, 0, s>>>(E, state, raw, partials);
-    else if (kind == 1) obs_partials_kernel<1><<<nblocks, 256, 0, s>>>(E, state, raw, partials);
-    else if (kind == 2) obs_partials_kernel<2><<<nblocks, 256, 0, s>>>(E, state, raw, partials);
-    else if (kind == 6) obs_partials_kernel<6><<<nblocks, 256, 0, s>>>(E, state, raw, partials);
-    else if (kind == 7) obs_partials_kernel<7><<<nblocks, 256, 0, s>>>(E, state, raw, partials);
-    else obs_partials_kernel<3><<<nblocks, 256, 0, s>>>(E, state, raw, partials);
-    return hipGetLastError();
+    return with_env_kind<KindShare::Observe>(kind, [&](auto K) {
+        obs_partials_kernel<decltype(K)::value><<<nblocks, 256, 0, s>>>(E, state, raw, partials);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_norm_obs_apply(const NormObsArgs& a, hipStream_t s) {
     int blocks = (a.E * a.D + 255) / 256; if (blocks > 1024) blocks = 1024;
@@ -1425,10 +1383,12 @@ hipError_t launch_policy(int kind, int hidden, const PolicyArgs& a, int max_bloc
     }
 // (hidden 32 — the reference's benchmark-suite shape — exists on the f32-MFMA forward only: the f16-piece images are laid out for 64-wide layers)
 #define CALL(K, HH) { if constexpr (HH == 32) { CALLS(K, HH, false) } else { if (a.exact_f32) CALLS(K, HH, false) else CALLS(K, HH, true) } }
-    DRIL_DISPATCH_FWD(kind, hidden, CALL);
+    return with_env_kind<KindShare::Shape>(kind, [&](auto K) -> hipError_t {
+        DRIL_DISPATCH_H(decltype(K)::value, hidden, CALL)
+        return hipGetLastError();
+    });
 #undef CALL
 #undef CALLS
-    return hipGetLastError();
 }
 
 template <int KIND, int H, bool SPLIT> static size_t duo_lds_bytes() {
@@ -1437,16 +1397,17 @@ template <int KIND, int H, bool SPLIT> static size_t duo_lds_bytes() {
 }
 hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_t s) {
     static const bool no_duo = debug_env("DRIL_NO_ROLLOUT_DUO") != nullptr;             // A/B (DRIL_DEBUG=1)
-    if ((hidden == 64 || hidden == 32) && a.E <= 16384 && !no_duo && ((kind >= 0 && kind <= 4) || kind == 6 || kind == 7)) {                                      // env counts that leave SIMDs idle: two waves per tile of 32 envs
+    if ((hidden == 64 || hidden == 32) && a.E <= 16384 && !no_duo) {                                      // env counts that leave SIMDs idle: two waves per tile of 32 envs
         const int blocks = (a.E + kTile - 1) / kTile;
 #define CALLDS(K, HH, SP) { const size_t lds = duo_lds_bytes<K, HH, SP>(); \
             { hipError_t e = set_max_dynamic_lds((const void*)rollout_duo_kernel<K, HH, SP>, lds); if (e != hipSuccess) return e; } \
             rollout_duo_kernel<K, HH, SP><<<blocks, 128, lds, s>>>(a); }
-#define CALLD(K) { if (hidden == 32) CALLDS(K, 32, false) else if (a.exact_f32) CALLDS(K, 64, false) else CALLDS(K, 64, true) }
-        if (kind == 0) CALLD(0) else if (kind == 1) CALLD(1) else if (kind == 2) CALLD(2) else if (kind == 3) CALLD(3) else if (kind == 6) CALLD(6) else if (kind == 7) CALLD(7) else CALLD(4)
-#undef CALLD
+        return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
+            constexpr int KIND = decltype(K)::value;
+            if (hidden == 32) CALLDS(KIND, 32, false) else if (a.exact_f32) CALLDS(KIND, 64, false) else CALLDS(KIND, 64, true)
+            return hipGetLastError();
+        });
 #undef CALLDS
-        return hipGetLastError();
     }
     const int blocks = (a.E + 4 * kTile - 1) / (4 * kTile);
 #define CALLS(K, HH, SP)                                                                                      \
@@ -1456,10 +1417,12 @@ hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_
         rollout_kernel<K, HH, (HH > 64), SP><<<blocks, 256, lds, s>>>(a);                                     \
     }
 #define CALL(K, HH) { if constexpr (HH == 32) { CALLS(K, HH, false) } else { if (a.exact_f32) CALLS(K, HH, false) else CALLS(K, HH, true) } }
-    DRIL_DISPATCH_ENV(kind, hidden, CALL);
+    return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
+        DRIL_DISPATCH_H(decltype(K)::value, hidden, CALL)
+        return hipGetLastError();
+    });
 #undef CALL
 #undef CALLS
-    return hipGetLastError();
 }
 
 int gae_chunks(int T) { return (T + kGaeRows - 1) / kGaeRows; }
@@ -1509,12 +1472,10 @@ hipError_t launch_epoch_index(int64_t N, uint64_t key, int bits, int32_t* out, h
 }
 hipError_t launch_pack_records(int kind, int64_t N, const float* obs, const void* act, const float* adv, const float* logp, const float* ret, float4* rec, hipStream_t s) {
     int blocks = (int)((N + 255) / 256); if (blocks > 8192) blocks = 8192;
-    if (kind == 0) pack_records_kernel<0><<<blocks, 256, 0, s>>>(N, obs, act, adv, logp, ret, rec);
-    else if (kind == 3) pack_records_kernel<3><<<blocks, 256, 0, s>>>(N, obs, act, adv, logp, ret, rec);
-    else if (kind == 4 || kind == 7) pack_records_kernel<4><<<blocks, 256, 0, s>>>(N, obs, act, adv, logp, ret, rec);
-    else if (kind == 6) pack_records_kernel<6><<<blocks, 256, 0, s>>>(N, obs, act, adv, logp, ret, rec);
-    else pack_records_kernel<1><<<blocks, 256, 0, s>>>(N, obs, act, adv, logp, ret, rec);
-    return hipGetLastError();
+    return with_env_kind<KindShare::Shape>(kind, [&](auto K) {
+        pack_records_kernel<decltype(K)::value><<<blocks, 256, 0, s>>>(N, obs, act, adv, logp, ret, rec);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_grad_reduce(const ReduceArgs& a, hipStream_t s) {
     grad_reduce_kernel<<<(a.P + 31) / 32, 1024, 0, s>>>(a);
@@ -1537,23 +1498,12 @@ hipError_t launch_explained_var(const float* val, const float* ret, int64_t N, d
     return hipGetLastError();
 }
 
-static void kind_dims(int kind, int& D, int& A, bool& disc) {
-    switch (kind) {
-        case 0: D = 4; A = 2; disc = true; break;
-        case 3: D = 2; A = 3; disc = true; break;
-        case 4: case 7: D = 2; A = 1; disc = false; break;
-        case 6: D = 6; A = 3; disc = true; break;
-        default: D = 3; A = 1; disc = false; break;
-    }
+int slab_size_actor(const EnvKindInfo& k, int hidden) {
+    const NetOff n = net_off(0, k.D, hidden, hidden, k.A);
+    return (n.end + (k.discrete ? 0 : k.A) + 8 + 3) / 4 * 4 + 0;
 }
-int slab_size_actor(int kind, int hidden) {
-    int D, A; bool disc; kind_dims(kind, D, A, disc);
-    const NetOff n = net_off(0, D, hidden, hidden, A);
-    return (n.end + (disc ? 0 : A) + 8 + 3) / 4 * 4 + 0;
-}
-int slab_size_critic(int kind, int hidden) {
-    int D, A_; bool disc_; kind_dims(kind, D, A_, disc_);
-    const NetOff n = net_off(0, D, hidden, hidden, 1);
+int slab_size_critic(const EnvKindInfo& k, int hidden) {
+    const NetOff n = net_off(0, k.D, hidden, hidden, 1);
     return (n.end + 8 + 3) / 4 * 4;
 }
 

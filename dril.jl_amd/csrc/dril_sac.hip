@@ -32,7 +32,7 @@
 #include "dril_sac_adapter.h"
 #include "dril_policy_internal.h"   // dril_policy_from_sac_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_sac_eval.h"
-#include "dril_env_module.h"
+#include "dril_env_side.h"     // DeviceEnvs: the envs this handle steps on the device (a built-in Box kind or a device env plug-in), shared with the PPO handle
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
 
 using namespace dril;
@@ -1245,12 +1245,11 @@ struct dril_sac_handle {
     float bt_actor[2], bt_critic[2], bt_ent[2]; int64_t grad_updates = 0; uint64_t update_counter = 0, aux_counter = 0;
     float target_entropy = 0, act_lo = -2.0f, act_hi = 2.0f; bool external = false;   // bounds of the agent-facing action space: Box(-2,2), Box(-1,1) under ScalingWrapperEnv
     float* act_bounds = nullptr;                     // device table [low[kMaxA] | high[kMaxA]] the sampling kernels read: the pair above in every entry, or a plug-in's bounds per dimension
-    // DRIL_ENV_MODULE: a device env plug-in (include/device/dril_env_plugin.h) loaded as a HIP module; its three kernels stand in for the env kernels of a built-in kind
-    bool module = false, fused_head_push = true; hipModule_t env_module = nullptr; hipFunction_t mod_reset = nullptr, mod_observe = nullptr, mod_step = nullptr; DrilEnvPluginDesc mod_desc{};
-    // env
-    float* state = nullptr; int32_t* step_count = nullptr; uint32_t *episode = nullptr, *gstep = nullptr; float* disc_returns = nullptr;
+    // env: the envs on the device — simulator state and counters, the seed, and for DRIL_ENV_MODULE the loaded plug-in (dril_env_side.h; SAC has no DiscreteAdapter and
+    // no fixed-length episodes: action_start 0, fixed_len 0)
+    DeviceEnvs env; bool fused_head_push = true;
     float *obs_cur = nullptr, *obs_nxt = nullptr, *e_rew = nullptr, *e_tobs = nullptr, *e_raw = nullptr, *e_envact = nullptr; uint8_t *e_term = nullptr, *e_trunc = nullptr;
-    uint64_t env_seed0 = 0; bool env_ready = false, obs_valid = false;
+    bool obs_valid = false;
     // replay ring
     long long cap = 0, size = 0, head = 0;
     float *rb_obs = nullptr, *rb_next = nullptr, *rb_act = nullptr, *rb_rew = nullptr; uint8_t *rb_term = nullptr, *rb_trunc = nullptr;
@@ -1479,18 +1478,10 @@ int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long*
     return DRIL_OK;
 }
 
-// the argument block of a plug-in's kernels: SAC has no DiscreteAdapter (action_start 0); the monitor pointers are filled by the collection step alone (monitor_row)
-DrilEnvPluginArgs module_args(dril_sac_handle* h) {
-    DrilEnvPluginArgs a{};
-    a.E = h->cfg.n_envs; a.episode_len = h->cfg.episode_len; a.seed0 = h->env_seed0;
-    a.state = h->state; a.step_count = h->step_count; a.episode = h->episode; a.gstep = h->gstep;
-    return a;
-}
 int ensure_obs(dril_sac_handle* h) {
-    if (!h->env_ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
+    if (!h->env.ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
     if (!h->obs_valid) {
-        if (h->module) { DrilEnvPluginArgs a = module_args(h); a.obs = h->obs_cur; SHIP(h, env_module_launch(h->mod_observe, a, h->stream)); }
-        else SHIP(h, launch_env_observe(h->cfg.env_kind, h->cfg.n_envs, h->state, h->obs_cur, h->stream));
+        SHIP(h, h->env.observe(h->obs_cur, h->stream));
         h->obs_valid = true;
     }
     return DRIL_OK;
@@ -1538,16 +1529,12 @@ int monitor_end(dril_sac_handle* h) {
 // so the ring is complete when the collection returns.
 int collect_step_module(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned long long* stamp, bool first, bool last) {
     const int E = h->cfg.n_envs;
-    DrilEnvPluginArgs st = module_args(h);
-    // `actions` is the env-space action of TanhScaleAdapter / rand(action_space), inside the Box by construction: the wrapper's ClampAdapter is a no-op on it
-    st.actions = h->e_envact; st.rewards = h->e_rew; st.terminated = h->e_term; st.truncated = h->e_trunc; st.terminal_obs = h->e_tobs; st.obs = h->obs_nxt;
-    if (h->mon_window) {                                                                             // MonitorWrapperEnv: the wrapper of dril_env_plugin.h keeps the sums and writes this step's row
-        const MonitorArgs mon = monitor_row(h); h->mon_row += 1;
-        st.mon_cur_ret = mon.cur_ret; st.mon_cur_len = mon.cur_len; st.ep_ret = mon.ep_ret; st.ep_len = mon.ep_len; st.flags = mon.flags_out;
-    }
+    // the step's actions are the env-space actions of TanhScaleAdapter / rand(action_space), inside the Box by construction: the wrapper's ClampAdapter is a no-op on them
+    const EnvStepOut out{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt};
+    const MonitorArgs mon = monitor_row(h); if (h->mon_window) h->mon_row += 1;                       // MonitorWrapperEnv: the wrapper of dril_env_plugin.h keeps the sums and writes this step's row
     if (!h->fused_head_push) {                                                                       // DRIL_SAC_NO_FUSED_HEAD_PUSH=1: three launches per step
         hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
-        SHIP(h, env_module_launch(h->mod_step, st, h->stream));
+        SHIP(h, h->env.step(h->e_envact, out, mon, h->stream));
         hipLaunchKernelGGL(sac_push_flat_kernel, dim3((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock), dim3(256), 0, h->stream, push_args(h, h->obs_cur, h->obs_nxt, stamp));
         SHIP(h, hipGetLastError());
         ring_advance(h); std::swap(h->obs_cur, h->obs_nxt);
@@ -1557,7 +1544,7 @@ int collect_step_module(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned 
     HeadPushArgs hp{ca, push_args(h, h->obs_nxt, h->obs_cur, nullptr)};
     if (first) hp.push.E = 0; else ring_advance(h);
     hipLaunchKernelGGL(sac_collect_head_push_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, hp);
-    SHIP(h, env_module_launch(h->mod_step, st, h->stream));                                          // (overwrites obs_nxt: its old rows went into the ring one launch earlier)
+    SHIP(h, h->env.step(h->e_envact, out, mon, h->stream));                                          // (overwrites obs_nxt: its old rows went into the ring one launch earlier)
     std::swap(h->obs_cur, h->obs_nxt);
     if (last) {
         hipLaunchKernelGGL(sac_push_flat_kernel, dim3((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock), dim3(256), 0, h->stream, push_args(h, h->obs_nxt, h->obs_cur, stamp));
@@ -1588,13 +1575,13 @@ int actor_hidden(dril_sac_handle* h, int use_random, const float* inj_noise, Col
         hipLaunchKernelGGL(sac_collect_l2_kernel, dim3((E + kL2TN - 1) / kL2TN, h->H2 / kL2TM), dim3(256), kL2LdsBytes, h->stream, l2);
         SHIP(h, hipGetLastError());
     } else if (!use_random) SDO(net_forward(h, h->params, h->actor, 0, D, A, h->obs_cur, D, 0, E, actor_bufs(h), 1, 1, mu_in_head));
-    *out = CollectHeadArgs{E, A, use_random, h->mu, h->params + h->log_std_off, inj_noise, h->gstep, h->env_seed0, h->act_bounds, h->act_bounds + kMaxA, h->e_raw, h->e_envact,
+    *out = CollectHeadArgs{E, A, use_random, h->mu, h->params + h->log_std_off, inj_noise, h->env.gstep, h->env.seed0, h->act_bounds, h->act_bounds + kMaxA, h->e_raw, h->e_envact,
                            mu_in_head ? h->ah2 : nullptr, h->params + h->actor.w3, h->params + h->actor.b3, h->H2, 0};
     return DRIL_OK;
 }
 // the env kernel's argument block of a built-in Box env (A = 1): head, push (collection only), the env arrays and the per-step results
 CollectEnvArgs env_kernel_args(dril_sac_handle* h, const CollectHeadArgs& ca, const PushArgs& pa, const MonitorArgs& mon) {
-    return CollectEnvArgs{ca, pa, h->env_seed0, h->cfg.episode_len, h->state, h->step_count, h->episode, h->gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt, mon};
+    return CollectEnvArgs{ca, pa, h->env.seed0, h->env.episode_len, h->env.state, h->env.step_count, h->env.episode, h->env.gstep, h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt, mon};
 }
 // ---- NormalizeWrapperEnv in a collection (kernels: dril_sac_norm.h) -----------------------------------------------------------------------------------------
 void normalize_free(dril_sac_handle* h) {
@@ -1605,10 +1592,9 @@ void normalize_free(dril_sac_handle* h) {
 }
 // the raw observation of the envs' present state in nz_old_obs (reset! :110-121 stores it; so does every observe)
 int nz_ensure_raw(dril_sac_handle* h) {
-    if (!h->env_ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
+    if (!h->env.ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
     if (h->nz_raw_valid) return DRIL_OK;
-    if (h->module) { DrilEnvPluginArgs a = module_args(h); a.obs = h->nz_old_obs; SHIP(h, env_module_launch(h->mod_observe, a, h->stream)); }
-    else SHIP(h, launch_env_observe(h->cfg.env_kind, h->cfg.n_envs, h->state, h->nz_old_obs, h->stream));
+    SHIP(h, h->env.observe(h->nz_old_obs, h->stream));
     h->nz_raw_valid = true;
     return DRIL_OK;
 }
@@ -1649,22 +1635,16 @@ int collect_step_norm(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned lo
     const bool upd_obs = h->nz.cfg.training && h->nz.cfg.norm_obs, upd_ret = h->nz.cfg.training && h->nz.cfg.norm_reward;
     int rows = 0;
     const MonitorArgs mon = monitor_row(h); if (h->mon_window) h->mon_row += 1;                     // MonitorWrapperEnv sits inside the normaliser: raw rewards
-    if (h->module) {
+    if (h->env.module) {
         hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
-        DrilEnvPluginArgs st = module_args(h);
-        st.actions = h->e_envact; st.rewards = h->e_rew; st.terminated = h->e_term; st.truncated = h->e_trunc; st.terminal_obs = h->e_tobs; st.obs = h->nz_old_obs;
-        if (h->mon_window) { st.mon_cur_ret = mon.cur_ret; st.mon_cur_len = mon.cur_len; st.ep_ret = mon.ep_ret; st.ep_len = mon.ep_len; st.flags = mon.flags_out; }
-        SHIP(h, env_module_launch(h->mod_step, st, h->stream));
+        SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->nz_old_obs}, mon, h->stream));
         if (upd_obs || upd_ret) SDO(nz_moments(h, upd_obs, upd_ret, &rows));
     } else {                                                                                         // every built-in Box env has A = 1
         CollectEnvArgs ce = env_kernel_args(h, ca, PushArgs{}, mon); ce.nobs = h->nz_old_obs;
         const NormEnvArgs ne{ce, h->nz_returns, upd_ret ? 1 : 0, h->nz.cfg.gamma, h->nz.partials};
         const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
         rows = (int)grid.x;
-        if (h->cfg.env_kind == DRIL_ENV_PENDULUM) hipLaunchKernelGGL(sac_norm_env_kernel<1>, grid, block, 0, h->stream, ne);
-        else if (h->cfg.env_kind == DRIL_ENV_PENDULUM_SCALED) hipLaunchKernelGGL(sac_norm_env_kernel<2>, grid, block, 0, h->stream, ne);
-        else if (h->cfg.env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) hipLaunchKernelGGL(sac_norm_env_kernel<7>, grid, block, 0, h->stream, ne);
-        else hipLaunchKernelGGL(sac_norm_env_kernel<4>, grid, block, 0, h->stream, ne);
+        SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_norm_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, ne); return hipGetLastError(); }));
     }
     NzApplyArgs a{}; a.w.raw = h->nz_old_obs; a.w.obs_out = h->obs_nxt;
     a.w.rew = h->e_rew; a.old_rew = h->nz_old_rew; a.w.returns = h->nz_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
@@ -1675,39 +1655,23 @@ int collect_step_norm(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned lo
 }
 // one step of collect_trajectories (off_policy_collection.jl:42-93) for all envs
 int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, unsigned long long* stamp = nullptr, bool first = true, bool last = true) {
-    const int E = h->cfg.n_envs, D = h->D, A = h->A;
+    const int E = h->cfg.n_envs, A = h->A;
     CollectHeadArgs ca; SDO(actor_hidden(h, use_random, inj_noise, &ca));
     if (h->nz.on) return collect_step_norm(h, ca, stamp);
-    if (h->module) return collect_step_module(h, ca, stamp, first, last);
+    if (h->env.module) return collect_step_module(h, ca, stamp, first, last);
     const MonitorArgs mon = monitor_row(h); if (h->mon_window) h->mon_row += 1;                                   // MonitorWrapperEnv: this step's row of the collection's block (null: off)
     if (A == 1 && !h->external && h->fused_collect) {                                                            // every device Box env: head + act! + observe + push! in one launch
-        const long long tail1 = (h->head + h->size) % h->cap;
-        PushArgs pa1{E, D, A, h->cap, tail1, h->obs_cur, h->e_raw, h->e_rew, h->e_tobs, h->obs_nxt, h->e_term, h->e_trunc,
-                     h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, stamp};
-        const CollectEnvArgs ce = env_kernel_args(h, ca, pa1, mon);
+        const CollectEnvArgs ce = env_kernel_args(h, ca, push_args(h, h->obs_cur, h->obs_nxt, stamp), mon);
         const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
-        if (h->cfg.env_kind == DRIL_ENV_PENDULUM) hipLaunchKernelGGL(sac_collect_env_kernel<1>, grid, block, 0, h->stream, ce);
-        else if (h->cfg.env_kind == DRIL_ENV_PENDULUM_SCALED) hipLaunchKernelGGL(sac_collect_env_kernel<2>, grid, block, 0, h->stream, ce);
-        else if (h->cfg.env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) hipLaunchKernelGGL(sac_collect_env_kernel<7>, grid, block, 0, h->stream, ce);
-        else hipLaunchKernelGGL(sac_collect_env_kernel<4>, grid, block, 0, h->stream, ce);
-        SHIP(h, hipGetLastError());
-        const long long over1 = h->size + E - h->cap;
-        if (over1 > 0) { h->head = (h->head + over1) % h->cap; h->size = h->cap; } else h->size += E;
-        std::swap(h->obs_cur, h->obs_nxt);
+        SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_collect_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, ce); return hipGetLastError(); }));
+        ring_advance(h); std::swap(h->obs_cur, h->obs_nxt);
         return DRIL_OK;
     }
     hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
-    SHIP(h, launch_env_step(h->cfg.env_kind, E, h->env_seed0, h->cfg.episode_len, 0, 0, h->e_envact, h->state, h->step_count, h->episode, h->gstep,
-                            h->e_rew, h->e_term, h->e_trunc, h->e_tobs, mon, h->stream));                                     // act! :60
-    SHIP(h, launch_env_observe(h->cfg.env_kind, E, h->state, h->obs_nxt, h->stream));                                         // observe :61
-    const long long tail = (h->head + h->size) % h->cap;
-    PushArgs pa{E, D, A, h->cap, tail, h->obs_cur, h->e_raw, h->e_rew, h->e_tobs, h->obs_nxt, h->e_term, h->e_trunc,
-                h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, stamp};
-    hipLaunchKernelGGL(sac_push_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, pa);
+    SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, mon, h->stream));   // act! :60, observe :61
+    hipLaunchKernelGGL(sac_push_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, push_args(h, h->obs_cur, h->obs_nxt, stamp));
     SHIP(h, hipGetLastError());
-    const long long over = h->size + E - h->cap;                                                  // CircularBuffer: overwrite the oldest
-    if (over > 0) { h->head = (h->head + over) % h->cap; h->size = h->cap; } else h->size += E;
-    std::swap(h->obs_cur, h->obs_nxt);
+    ring_advance(h); std::swap(h->obs_cur, h->obs_nxt);
     return DRIL_OK;
 }
 // cont: the steps continue the collection the previous call began (dril_sac_collect_continue) — under NormalizeWrapperEnv there is no second opening observe
@@ -1849,9 +1813,10 @@ int params_from_device(dril_sac_handle* h, float* host, const float* dev) {
 // exported entry points (include/dril_sac.h)
 // =================================================================================================================
 DRIL_EXPORT int32_t dril_sac_config_default(dril_sac_config* c, int32_t env_kind) {
-    if (!c || (env_kind != DRIL_ENV_PENDULUM && env_kind != DRIL_ENV_PENDULUM_SCALED && env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS && env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED && env_kind != DRIL_ENV_EXTERNAL && env_kind != DRIL_ENV_MODULE)) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "SAC needs a Box action space (sac.jl:74): env_kind must be DRIL_ENV_PENDULUM[_SCALED], DRIL_ENV_EXTERNAL or DRIL_ENV_MODULE");
+    const EnvKindInfo* k = env_kind_info(env_kind);
+    if (!c || (k ? !k->box : (env_kind != DRIL_ENV_EXTERNAL && env_kind != DRIL_ENV_MODULE))) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "SAC needs a Box action space (sac.jl:74): env_kind must be DRIL_ENV_PENDULUM[_SCALED], DRIL_ENV_EXTERNAL or DRIL_ENV_MODULE");
     memset(c, 0, sizeof(*c));
-    c->abi_version = DRIL_SAC_ABI_VERSION; c->env_kind = env_kind; c->n_envs = 1; c->episode_len = env_kind == DRIL_ENV_MODULE ? 0 /* the descriptor's */ : (env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 999 : 200;
+    c->abi_version = DRIL_SAC_ABI_VERSION; c->env_kind = env_kind; c->n_envs = 1; c->episode_len = k ? k->default_episode_len /* the Gymnasium time limit */ : env_kind == DRIL_ENV_MODULE ? 0 /* the descriptor's */ : 200;
     c->hidden1 = 512; c->hidden2 = 512; c->activation = 1;
     c->buffer_capacity = 1000000; c->start_steps = 100; c->batch_size = 256; c->tau = 0.005f; c->gamma = 0.99f;
     c->train_freq = 1; c->gradient_steps = 1; c->target_update_interval = 1;
@@ -1866,7 +1831,7 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->params, h->adam_m, h->adam_v, h->g_critic, h->g_actor, h->sc, h->sc_next, h->stats, h->stats_out, h->ssq_rows, h->counter, h->head_partials, h->head_counter,
-                    h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->obs_cur, h->obs_nxt, h->e_rew, h->e_tobs, h->e_raw, h->e_envact, h->e_term, h->e_trunc,
+                    h->obs_cur, h->obs_nxt, h->e_rew, h->e_tobs, h->e_raw, h->e_envact, h->e_term, h->e_trunc,
                     h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, h->xa, h->ah1, h->ah2, h->mu, h->xq, h->xq_pi,
                     h->qh1, h->qh2, h->q_cur, h->q_pi, h->dq, h->dz2, h->dz1, h->dxq, h->dmu, h->b_rew, h->b_ne, h->b_nn, h->b_np,
                     h->b_nlp, h->a_pi, h->g_pi, h->lp_pi, h->b_term, h->collect_noise, h->act_bounds, h->inj_idx, h->inj_ne, h->inj_nn, h->inj_np, h->s_in, h->s_act, h->s_noise, h->s_out, h->s_out2};
@@ -1881,7 +1846,7 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
     normalize_free(h);
     if (h->ev_counter_host) hipHostFree(h->ev_counter_host);
     if (h->stream) hipStreamDestroy(h->stream);
-    if (h->env_module) (void)hipModuleUnload(h->env_module);
+    h->env.release();
     delete h;
     return DRIL_OK;
 }
@@ -1916,8 +1881,8 @@ DRIL_EXPORT int32_t dril_sac_create_with_env_module(const dril_sac_config* cfg, 
 }
 DRIL_EXPORT int32_t dril_sac_env_module_info_of(const dril_sac_handle* h, dril_env_module_info* out) {
     if (!h || !out) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle / out");
-    if (!h->module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_info_of: the handle was not created with dril_sac_create_with_env_module");
-    fill_module_info(h->mod_desc, out);
+    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_info_of: the handle was not created with dril_sac_create_with_env_module");
+    fill_module_info(h->env.desc, out);
     return DRIL_OK;
 }
 
@@ -1927,7 +1892,8 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     if (cfg->abi_version != DRIL_SAC_ABI_VERSION) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_config.abi_version mismatch");
     const bool ext = cfg->env_kind == DRIL_ENV_EXTERNAL, is_module = cfg->env_kind == DRIL_ENV_MODULE;
     if (is_module && cfg->episode_len < 0) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_MODULE: episode_len must be > 0, or 0 for the plug-in's own time limit");
-    if (!ext && !is_module && cfg->env_kind != DRIL_ENV_PENDULUM && cfg->env_kind != DRIL_ENV_PENDULUM_SCALED && cfg->env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS && cfg->env_kind != DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC needs a Box action space (sac.jl:74): DRIL_ENV_PENDULUM[_SCALED] or DRIL_ENV_EXTERNAL");
+    const EnvKindInfo* kinfo = env_kind_info(cfg->env_kind);
+    if (!ext && !is_module && !(kinfo && kinfo->box)) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC needs a Box action space (sac.jl:74): DRIL_ENV_PENDULUM[_SCALED] or DRIL_ENV_EXTERNAL");
     if (ext && (cfg->ext_obs_dim < 1 || cfg->ext_obs_dim > 1024 || cfg->ext_action_dim < 1 || cfg->ext_action_dim > kMaxA || !(cfg->ext_action_low < cfg->ext_action_high)))
         return sfail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_EXTERNAL: ext_obs_dim 1..1024, ext_action_dim 1..16, ext_action_low < ext_action_high");
     if (cfg->n_envs <= 0 || (!ext && !is_module && cfg->episode_len <= 0) || cfg->batch_size <= 0 || cfg->buffer_capacity < cfg->n_envs || cfg->train_freq <= 0 || cfg->target_update_interval <= 0)
@@ -1937,34 +1903,33 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sfail(nullptr, DRIL_ERR_HIP, "no HIP device: libdril_hip has no CPU fallback");
     if (cfg->device < 0 || cfg->device >= ndev) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "device ordinal out of range");
-    hipModule_t mod = nullptr; DrilEnvPluginDesc desc{};
-    if (is_module) {                                                                     // the descriptor gives the spaces and the bounds: load it before anything is sized
-        std::string msg; int rcm = load_env_module(module_path, cfg->device, &mod, &desc, msg);
-        if (!rcm && (rcm = check_sac_plugin(desc, msg)) != DRIL_OK) { (void)hipModuleUnload(mod); (void)hipGetLastError(); }
-        if (rcm) return sfail(nullptr, rcm, "dril_sac_create_with_env_module: " + msg);
-    }
     dril_sac_handle* h = new dril_sac_handle(); h->cfg = *cfg;
-    if (is_module) { h->module = true; h->env_module = mod; h->mod_desc = desc; if (cfg->episode_len == 0) h->cfg.episode_len = desc.episode_len; }   // (dril_sac_destroy unloads it on every failing path below)
+    {   // a plug-in's descriptor gives the spaces and the bounds: it is loaded here, before anything is sized (dril_sac_destroy unloads it on every failing path below)
+        std::string msg; int rcm = h->env.open(cfg->env_kind, cfg->n_envs, cfg->episode_len, /*fixed_len=*/0, /*action_start=*/0, module_path, cfg->device, msg);
+        if (!rcm && is_module) rcm = check_sac_plugin(h->env.desc, msg);
+        if (rcm) { h->env.release(); delete h; return sfail(nullptr, rcm, "dril_sac_create_with_env_module: " + msg); }
+        h->cfg.episode_len = h->env.episode_len;
+    }
+    const DrilEnvPluginDesc& desc = h->env.desc;
 #define CHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(_e); dril_sac_destroy(h); return sfail(nullptr, DRIL_ERR_HIP, m); } } while (0)
     CHK(hipSetDevice(cfg->device));
     CHK(hipStreamCreate(&h->stream));
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->cfg.device) == hipSuccess && khz > 0) h->wall_hz = 1e3 * (double)khz; }   // wall_clock64 ticks per second (phase_stamp)
-    const int D = h->D = is_module ? desc.D : ext ? cfg->ext_obs_dim : ((cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 2 : 3), A = h->A = is_module ? desc.A : ext ? cfg->ext_action_dim : 1, S = h->S = is_module ? desc.S : ext ? 0 : 2, H1 = h->H1 = cfg->hidden1, H2 = h->H2 = cfg->hidden2, E = cfg->n_envs, B = cfg->batch_size, W = D + A;
+    const int D = h->D = is_module ? desc.D : ext ? cfg->ext_obs_dim : kinfo->D, A = h->A = is_module ? desc.A : ext ? cfg->ext_action_dim : kinfo->A, S = h->S = is_module ? desc.S : ext ? 0 : kinfo->S, H1 = h->H1 = cfg->hidden1, H2 = h->H2 = cfg->hidden2, E = cfg->n_envs, B = cfg->batch_size, W = D + A;
     h->Pa = D * H1 + H1 + H1 * H2 + H2 + H2 * A + A; h->Pq = W * H1 + H1 + H1 * H2 + H2 + H2 + 1; h->P = h->Pa + 2 * h->Pq + A;
     h->actor = net_off(0, D, H1, H2, A); h->Pqd = round4(h->Pq); h->q0 = net_off(round4(h->actor.end), W, H1, H2, 1);
     h->log_std_off = h->q0.w1 + 4 * h->Pqd; h->Pd = round4(h->log_std_off + A);      // device layout: actor | q1 | q2 | target q1 | target q2 | log_std
     h->nq = B; h->nmax = std::max(E, 2 * B);
     h->target_entropy = cfg->auto_target_entropy ? -(float)A : cfg->target_entropy;
-    h->act_hi = (cfg->env_kind == DRIL_ENV_PENDULUM_SCALED || cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS || cfg->env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) ? 1.0f : 2.0f; h->act_lo = -h->act_hi; h->external = ext;
+    h->external = ext;
     if (ext) { h->act_lo = cfg->ext_action_low; h->act_hi = cfg->ext_action_high; }
+    else if (kinfo) { h->act_lo = kinfo->act_lo; h->act_hi = kinfo->act_hi; }
     {   // the bounds table of the sampling kernels
         float tb[2 * kMaxA];
         for (int a = 0; a < kMaxA; ++a) { const bool own = is_module && a < A; tb[a] = own ? desc.action_low[a] : h->act_lo; tb[kMaxA + a] = own ? desc.action_high[a] : h->act_hi; }
         CHK(smalloc(&h->act_bounds, 2 * kMaxA)); CHK(hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
     }
     if (is_module) {
-        CHK(hipModuleGetFunction(&h->mod_reset, h->env_module, "dril_env_plugin_reset")); CHK(hipModuleGetFunction(&h->mod_observe, h->env_module, "dril_env_plugin_observe"));
-        CHK(hipModuleGetFunction(&h->mod_step, h->env_module, "dril_env_plugin_step"));
         h->fused_head_push = std::getenv("DRIL_SAC_NO_FUSED_HEAD_PUSH") == nullptr;           // A/B switch, latched here: head + plug-in step + push as three launches per env step
     }
     CHK(smalloc(&h->params, h->Pd)); CHK(smalloc(&h->adam_m, h->Pd)); CHK(smalloc(&h->adam_v, h->Pd));
@@ -1982,7 +1947,7 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     // past the step that completes the list.  No more than the time limit, after which every env has finished an episode.  DRIL_SAC_EVAL_POLL=<k> overrides; 1 is the step-by-step definition.
     h->eval_poll = std::max(1, std::min(h->cfg.episode_len, 32));
     if (const char* ep = std::getenv("DRIL_SAC_EVAL_POLL")) { const long k = std::strtol(ep, nullptr, 10); if (k >= 1) h->eval_poll = (int)std::min<long>(k, 1 << 20); }
-    CHK(smalloc(&h->state, (size_t)E * S)); CHK(smalloc(&h->step_count, E)); CHK(smalloc(&h->episode, E)); CHK(smalloc(&h->gstep, E)); CHK(smalloc(&h->disc_returns, E));
+    CHK(h->env.alloc(S));
     CHK(smalloc(&h->obs_cur, (size_t)E * D)); CHK(smalloc(&h->obs_nxt, (size_t)E * D)); CHK(smalloc(&h->e_rew, E)); CHK(smalloc(&h->e_tobs, (size_t)E * D));
     CHK(smalloc(&h->e_raw, (size_t)E * A)); CHK(smalloc(&h->e_envact, (size_t)E * A)); CHK(smalloc(&h->e_term, E)); CHK(smalloc(&h->e_trunc, E));
     h->cap = cfg->buffer_capacity;
@@ -2053,11 +2018,10 @@ DRIL_EXPORT int32_t dril_sac_reset_optimizer(dril_sac_handle* h) {
 
 DRIL_EXPORT int32_t dril_sac_env_reset(dril_sac_handle* h, uint64_t seed) {
     SNEED(h); S_NOT_EXTERNAL(h, "dril_sac_env_reset");
-    h->env_seed0 = seed;
-    if (h->module) SHIP(h, env_module_launch(h->mod_reset, module_args(h), h->stream));
-    else SHIP(h, launch_env_reset(h->cfg.env_kind, h->cfg.n_envs, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
+    h->env.seed0 = seed;
+    SHIP(h, h->env.reset(h->stream));
     if (h->mon_window) { SHIP(h, hipMemsetAsync(h->mon_cur_ret, 0, (size_t)h->cfg.n_envs * 4, h->stream)); SHIP(h, hipMemsetAsync(h->mon_cur_len, 0, (size_t)h->cfg.n_envs * 4, h->stream)); }   // MonitorWrapperEnv.reset!: the running sums restart, the window stays (monitorWrapperEnv.jl:36-42)
-    h->env_ready = true; h->obs_valid = false;
+    h->env.ready = true; h->obs_valid = false;
     if (h->nz.on) {                                                                   // NormalizeWrapperEnv.reset! (:110-121): old_obs = the raw observation, returns = 0, the statistics stay
         SHIP(h, hipMemsetAsync(h->nz_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream));
         h->nz_raw_valid = false; SDO(nz_ensure_raw(h));
@@ -2175,7 +2139,7 @@ DRIL_EXPORT int32_t dril_sac_collect_continue(dril_sac_handle* h, int32_t n_step
 DRIL_EXPORT int32_t dril_sac_ext_push(dril_sac_handle* h, const float* obs, const float* stored_actions, const float* rewards, const uint8_t* terminated,
                                       const uint8_t* truncated, const float* next_obs, const float* terminal_obs) {
     SNEED(h);
-    if (h->module) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the env of a device env plug-in (DRIL_ENV_MODULE) is on the device, not on the host: dril_sac_collect_rollout steps it");
+    if (h->env.module) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the env of a device env plug-in (DRIL_ENV_MODULE) is on the device, not on the host: dril_sac_collect_rollout steps it");
     if (!h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the handle was not created with DRIL_ENV_EXTERNAL");
     if (!obs || !stored_actions || !rewards || !terminated || !truncated || !next_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: null pointer");
     const size_t E = h->cfg.n_envs, D = h->D, A = h->A;
@@ -2305,7 +2269,7 @@ DRIL_EXPORT int32_t dril_sac_train(dril_sac_handle* h, int64_t max_steps, dril_s
 DRIL_EXPORT int32_t dril_sac_iterate(dril_sac_handle* h, int32_t iterations, dril_sac_stats* stats, int64_t stats_capacity, double* fps, int64_t fps_capacity) {
     SNEED(h); S_NOT_EXTERNAL(h, "dril_sac_iterate");
     if (iterations <= 0) return sfail(h, DRIL_ERR_INVALID_ARG, "iterations must be positive");
-    if (!h->env_ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
+    if (!h->env.ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
     const int64_t E = h->cfg.n_envs, tf = h->cfg.train_freq;
     const int64_t n_upd = h->cfg.gradient_steps == -1 ? tf * E : h->cfg.gradient_steps;
     int64_t done = 0;
@@ -2406,7 +2370,7 @@ DRIL_EXPORT int32_t dril_sac_normalize_enable(dril_sac_handle* h, const dril_sac
     SDO(ssync(h));
     normalize_free(h);
     const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
-    hipError_t e = h->nz.alloc((int)D, std::max<size_t>(kNzMaxRows, h->module ? 0 : (E + kEnvsPerBlock - 1) / kEnvsPerBlock));
+    hipError_t e = h->nz.alloc((int)D, std::max<size_t>(kNzMaxRows, h->env.module ? 0 : (E + kEnvsPerBlock - 1) / kEnvsPerBlock));
     if (e == hipSuccess) e = smalloc(&h->nz_returns, E);                               // (smalloc zeroes: returns and the cached originals start at 0)
     if (e == hipSuccess) e = smalloc(&h->nz_old_obs, E * D);
     if (e == hipSuccess) e = smalloc(&h->nz_old_rew, E);
@@ -2479,7 +2443,7 @@ int eval_buffers(dril_sac_handle* h, long long cap) {
 int eval_snapshot(dril_sac_handle* h, bool save) {
     const size_t E = (size_t)h->cfg.n_envs;
     auto cp = [&](void* snap, void* live, size_t bytes) { return save ? hipMemcpyAsync(snap, live, bytes, hipMemcpyDeviceToDevice, h->stream) : hipMemcpyAsync(live, snap, bytes, hipMemcpyDeviceToDevice, h->stream); };
-    SHIP(h, cp(h->ev_state, h->state, E * h->S * 4)); SHIP(h, cp(h->ev_sc, h->step_count, E * 4)); SHIP(h, cp(h->ev_ep, h->episode, E * 4)); SHIP(h, cp(h->ev_gs, h->gstep, E * 4));
+    SHIP(h, cp(h->ev_state, h->env.state, E * h->S * 4)); SHIP(h, cp(h->ev_sc, h->env.step_count, E * 4)); SHIP(h, cp(h->ev_ep, h->env.episode, E * 4)); SHIP(h, cp(h->ev_gs, h->env.gstep, E * 4));
     SHIP(h, cp(h->ev_obs, h->obs_cur, E * h->D * 4));                                 // (restore: into whichever of the two observation buffers is current now)
     if (h->mon_window) { SHIP(h, cp(h->ev_mon_ret, h->mon_cur_ret, E * 4)); SHIP(h, cp(h->ev_mon_len, h->mon_cur_len, E * 4)); }
     return DRIL_OK;
@@ -2492,11 +2456,9 @@ int eval_step(dril_sac_handle* h, int deterministic, int32_t step, unsigned int 
     const EvalAcctArgs acct{E, step, h->ev_cur_ret, h->ev_cur_len, h->ev_counter, h->ev_events, cap};
     // NormalizeWrapperEnv with training = false (set_training(eval_env, false) after sync_normalization_stats!, :299-309): the statistics in force, frozen
     const NzEvalArgs nz{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs};
-    if (h->module) {
+    if (h->env.module) {
         hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
-        DrilEnvPluginArgs st = module_args(h);                                         // (monitor pointers null: evaluation episodes do not feed the window)
-        st.actions = h->e_envact; st.rewards = h->e_rew; st.terminated = h->e_term; st.truncated = h->e_trunc; st.terminal_obs = h->e_tobs; st.obs = h->obs_nxt;
-        SHIP(h, env_module_launch(h->mod_step, st, h->stream));
+        SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, MonitorArgs{}, h->stream));   // (monitor pointers null: evaluation episodes do not feed the window)
         if (nz.st && nz.norm_obs) {                                                    // the accounting launch also normalises the observation the plug-in wrote, in place
             const long long nthr = std::max<long long>(E, std::min<long long>((long long)E * h->D, 256 * 1024));
             hipLaunchKernelGGL(sac_eval_account_norm_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, acct, h->e_rew, h->e_term, h->e_trunc, nz, h->D, h->obs_nxt);
@@ -2504,10 +2466,7 @@ int eval_step(dril_sac_handle* h, int deterministic, int32_t step, unsigned int 
     } else {                                                                           // every built-in Box env has A = 1
         const EvalEnvArgs ee{env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr}), acct, nz};
         const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
-        if (h->cfg.env_kind == DRIL_ENV_PENDULUM) hipLaunchKernelGGL(sac_eval_env_kernel<1>, grid, block, 0, h->stream, ee);
-        else if (h->cfg.env_kind == DRIL_ENV_PENDULUM_SCALED) hipLaunchKernelGGL(sac_eval_env_kernel<2>, grid, block, 0, h->stream, ee);
-        else if (h->cfg.env_kind == DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED) hipLaunchKernelGGL(sac_eval_env_kernel<7>, grid, block, 0, h->stream, ee);
-        else hipLaunchKernelGGL(sac_eval_env_kernel<4>, grid, block, 0, h->stream, ee);
+        SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_eval_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, ee); return hipGetLastError(); }));
     }
     SHIP(h, hipGetLastError());
     std::swap(h->obs_cur, h->obs_nxt);
@@ -2517,10 +2476,9 @@ int eval_step(dril_sac_handle* h, int deterministic, int32_t step, unsigned int 
 int eval_run(dril_sac_handle* h, int n_eval, int deterministic, uint64_t seed, std::vector<SacEvalEvent>& events) {
     const int E = h->cfg.n_envs;
     const long long cap = sac_eval_event_capacity(n_eval, E);
-    h->env_seed0 = seed;                                                               // env e seeded seed + e; its action noise is that env's stream from step 0
-    if (h->module) SHIP(h, env_module_launch(h->mod_reset, module_args(h), h->stream));
-    else SHIP(h, launch_env_reset(h->cfg.env_kind, E, seed, h->state, h->step_count, h->episode, h->gstep, h->disc_returns, h->stream));
-    h->env_ready = true; h->obs_valid = false;
+    h->env.seed0 = seed;                                                               // env e seeded seed + e; its action noise is that env's stream from step 0
+    SHIP(h, h->env.reset(h->stream));
+    h->env.ready = true; h->obs_valid = false;
     SDO(ensure_obs(h));                                                                // (the raw observation, into obs_cur: the wrapper's old_obs is not the evaluation's to write)
     if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }   // normalised in place, nothing updated
     SHIP(h, hipMemsetAsync(h->ev_cur_ret, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_cur_len, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
@@ -2545,12 +2503,12 @@ DRIL_EXPORT int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval, 
     if (n_eval < 1 || !out) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
     SDO(eval_buffers(h, sac_eval_event_capacity(n_eval, h->cfg.n_envs)));
     // evaluation runs on the handle's own envs: what a collection would continue from is set aside here and put back below, on every path
-    const uint64_t seed0 = h->env_seed0; const bool ready = h->env_ready, obs_valid = h->obs_valid;
+    const uint64_t seed0 = h->env.seed0; const bool ready = h->env.ready, obs_valid = h->obs_valid;
     SDO(eval_snapshot(h, true));
     std::vector<SacEvalEvent> events;
     const int rc = eval_run(h, n_eval, deterministic, seed, events);
     const std::string msg = h->err;
-    h->env_seed0 = seed0; h->env_ready = ready; h->obs_valid = obs_valid;
+    h->env.seed0 = seed0; h->env.ready = ready; h->obs_valid = obs_valid;
     int rr = eval_snapshot(h, false); if (rr == DRIL_OK) rr = ssync(h);
     if (rc != DRIL_OK) { h->err = msg; return rc; }
     if (rr != DRIL_OK) return rr;

@@ -51,6 +51,34 @@ def test_config_default_matches_reference_defaults(pkg):
     assert lib.dril_config_default(C.byref(c), 99) == pkg._capi.ERR_INVALID_ARG
 
 
+def test_default_time_limits_match_python_mirror_for_every_kind(pkg):
+    """the library's one table of built-in env kinds (csrc/dril_env_kinds.h) against its Python mirror: dril_config_default and, for the Box kinds,
+    dril_sac_config_default give the Gymnasium time limit _capi.default_config computes; kinds without a built-in simulator keep what the ABI documents"""
+    capi = pkg._capi
+    lib = capi.load_library()
+    builtin = (capi.ENV_CARTPOLE, capi.ENV_PENDULUM, capi.ENV_PENDULUM_SCALED, capi.ENV_MOUNTAINCAR, capi.ENV_MOUNTAINCAR_CONTINUOUS, capi.ENV_ACROBOT,
+               capi.ENV_MOUNTAINCAR_CONTINUOUS_SCALED)
+    box = (capi.ENV_PENDULUM, capi.ENV_PENDULUM_SCALED, capi.ENV_MOUNTAINCAR_CONTINUOUS, capi.ENV_MOUNTAINCAR_CONTINUOUS_SCALED)
+    assert sorted(builtin + (capi.ENV_EXTERNAL, capi.ENV_MODULE)) == list(range(9))
+    limits = {}
+    for kind in builtin + (capi.ENV_EXTERNAL, capi.ENV_MODULE):
+        c = capi.DrilConfig()
+        assert lib.dril_config_default(C.byref(c), kind) == 0
+        assert (c.env_kind, c.episode_len) == (kind, capi.default_config(kind).episode_len), kind
+        limits[kind] = c.episode_len
+    assert [limits[k] for k in builtin] == [500, 200, 200, 200, 999, 500, 999]
+    assert (limits[capi.ENV_EXTERNAL], limits[capi.ENV_MODULE]) == (200, 0)                          # host envs: a plain default; a plug-in: 0 = its descriptor's
+    assert lib.dril_config_default(C.byref(capi.DrilConfig()), 99) == capi.ERR_INVALID_ARG
+    for kind in builtin + (capi.ENV_EXTERNAL, capi.ENV_MODULE):
+        s = capi.DrilSacConfig()
+        rc = lib.dril_sac_config_default(C.byref(s), kind)
+        if kind in box + (capi.ENV_EXTERNAL, capi.ENV_MODULE):
+            assert rc == 0 and (s.env_kind, s.episode_len) == (kind, limits[kind]), kind
+        else:                                                                                        # Discrete kinds: SAC needs a Box (sac.jl:74)
+            assert rc == capi.ERR_INVALID_ARG and b"SAC needs a Box action space" in lib.dril_sac_last_error(None), kind
+    assert lib.dril_sac_config_default(C.byref(capi.DrilSacConfig()), 99) == capi.ERR_INVALID_ARG
+
+
 def test_null_and_bad_arguments_fail_loudly(pkg):
     """error convention: status codes + dril_last_error, never a crash, never a silent fallback"""
     lib = pkg._capi.load_library()
