@@ -158,6 +158,10 @@ _SIG = {
     "dril_create_with_env_module": (C.c_int32, [C.POINTER(DrilConfig), C.c_char_p, C.POINTER(_P)]),
     "dril_env_module_describe": (C.c_int32, [C.c_char_p, C.c_int32, C.POINTER(DrilEnvModuleInfo)]),
     "dril_env_module_info_of": (C.c_int32, [_P, C.POINTER(DrilEnvModuleInfo)]),
+    "dril_env_module_obs_space": (C.c_int32, [C.c_char_p, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
+    "dril_env_module_obs_space_of": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32)]),
+    "dril_scaling_enable": (C.c_int32, [_P, C.c_int32]),
+    "dril_agent_spaces": (C.c_int32, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     "dril_destroy": (C.c_int32, [_P]),
     "dril_last_error": (C.c_char_p, [_P]),
     "dril_synchronize": (C.c_int32, [_P]),
@@ -232,6 +236,9 @@ _SAC_SIG = {
     "create": (C.c_int32, [C.POINTER(DrilSacConfig), C.POINTER(_P)]),
     "create_with_env_module": (C.c_int32, [C.POINTER(DrilSacConfig), C.c_char_p, C.POINTER(_P)]),
     "env_module_info_of": (C.c_int32, [_P, C.POINTER(DrilEnvModuleInfo)]),
+    "env_module_obs_space_of": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32)]),
+    "scaling_enable": (C.c_int32, [_P, C.c_int32]),
+    "agent_spaces": (C.c_int32, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     "destroy": (C.c_int32, [_P]),
     "last_error": (C.c_char_p, [_P]),
     "obs_dim": (C.c_int32, [_P]),

@@ -622,6 +622,32 @@ DRIL_EXPORT int32_t dril_env_module_info_of(const dril_handle* h, dril_env_modul
     fill_module_info(h->env.desc, out);
     return DRIL_OK;
 }
+DRIL_EXPORT int32_t dril_env_module_obs_space(const char* code_object_path, int32_t device, float* low, float* high, int32_t* declared) {
+    std::string msg; const int rc = describe_module_obs_space(code_object_path, device, low, high, declared, msg);
+    return rc ? fail(nullptr, rc, "dril_env_module_obs_space: " + msg) : DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_env_module_obs_space_of(const dril_handle* h, float* low, float* high, int32_t* declared) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!h->env.module) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_env_module_obs_space_of: the handle was not created with dril_create_with_env_module");
+    const int D = h->env.desc.D;
+    if (low) std::memcpy(low, h->env.obs_low.data(), (size_t)D * 4);
+    if (high) std::memcpy(high, h->env.obs_high.data(), (size_t)D * 4);
+    if (declared) *declared = h->env.obs_declared ? 1 : 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_scaling_enable(dril_handle* h, int32_t on) {
+    NEED(h);
+    std::string msg; const int rc = h->env.set_scaling(on != 0, msg);
+    return rc ? fail(h, rc, "dril_scaling_enable: " + msg) : DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_agent_spaces(const dril_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!h->env.module) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_agent_spaces: the handle was not created with dril_create_with_env_module");
+    h->env.agent_obs_space(obs_low, obs_high);
+    if (!h->env.desc.discrete) h->env.agent_action_space(action_low, action_high);
+    if (scaling) *scaling = h->env.scaling ? 1 : 0;
+    return DRIL_OK;
+}
 
 namespace {
 int create_impl(const dril_config* cfg, const char* module_path, dril_handle** out) {

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "../../include/device/dril_philox.h"
+#include "../../include/device/dril_scaling.h"
 namespace dril {
 
 // Diagnostic / experiment switches (ablation bits, grid caps, the older form of a kernel for an A/B) are honoured only when DRIL_DEBUG=1 is set as well: a stray variable
@@ -291,9 +292,7 @@ template <> struct EnvSpec<3> { static constexpr int D = 2, S = 2, A = 3; static
 template <> struct EnvSpec<4> { static constexpr int D = 2, S = 2, A = 1; static constexpr bool discrete = false; };   // MountainCarContinuous-v0: Box(-1, 1)
 template <> struct EnvSpec<7> : EnvSpec<4> {};   // ScalingWrapperEnv(MountainCarContinuousEnv()): same simulator, affine maps at the boundary (observations Box((-1.2, -0.07), (0.6, 0.07)) -> Box(-1, 1))
 template <> struct EnvSpec<6> { static constexpr int D = 6, S = 4, A = 3; static constexpr bool discrete = true; };    // Acrobot-v1: (cos t1, sin t1, cos t2, sin t2, w1, w2), Discrete(3); fused at [64,64] / [128,128] / [256,256] through FirstLayer<6>, generic otherwise
-// ScalingWrapperEnv (scalingWrapperEnv.jl): scale! :71-74 `(x - low) * sf - 1`, unscale! :76-79 `(x + 1) / sf + low`, sf = 2 / (high - low) :36-44
-__host__ __device__ inline float scale_to_unit(float x, float low, float high) { const float sf = 2.0f / (high - low); return (x - low) * sf - 1.0f; }
-__host__ __device__ inline float unscale_from_unit(float x, float low, float high) { const float sf = 2.0f / (high - low); return (x + 1.0f) / sf + low; }
+// ScalingWrapperEnv (scalingWrapperEnv.jl): scale_to_unit / unscale_from_unit live in include/device/dril_scaling.h (shared with the device env plug-in header)
 // bound of the agent-facing action space (ClampAdapter / TanhScaleAdapter act on action_space(env)): Box(-2,2), Box(-1,1) under the wrapper
 template <int KIND> __host__ __device__ constexpr float act_bound() { return (KIND == 2 || KIND == 4 || KIND == 7) ? 1.0f : 2.0f; }
 

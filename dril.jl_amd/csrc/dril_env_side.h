@@ -4,9 +4,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/dril_hip.h"
 #include "../../include/device/dril_env_plugin.h"   // DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with
@@ -62,6 +65,40 @@ inline hipError_t env_module_launch(hipFunction_t f, DrilEnvPluginArgs a, hipStr
     void* params[] = {&a};
     return hipModuleLaunchKernel(f, (unsigned)((a.E + DRIL_ENV_PLUGIN_BLOCK - 1) / DRIL_ENV_PLUGIN_BLOCK), 1, 1, DRIL_ENV_PLUGIN_BLOCK, 1, 1, 0, stream, params, nullptr);
 }
+// the optional entry points of a plug-in (an env that declares obs_low / obs_high): absent ones are null, and asking for one leaves no HIP error behind
+inline hipFunction_t env_module_optional(hipModule_t mod, const char* name) {
+    hipFunction_t f = nullptr;
+    if (hipModuleGetFunction(&f, mod, name) != hipSuccess) { f = nullptr; (void)hipGetLastError(); }
+    return f;
+}
+// The declared observation space of a loaded, checked plug-in: dril_env_plugin_obs_space (one workgroup) writes low[D] | high[D] into a buffer sized from the
+// descriptor.  *declared = 0 and no launch when the code object has no such kernel (built before the observation space existed, or the env declares none).
+inline int read_module_obs_space(hipModule_t mod, const DrilEnvPluginDesc& d, std::vector<float>& low, std::vector<float>& high, bool* declared, std::string& msg) {
+    low.assign(d.D, -INFINITY); high.assign(d.D, INFINITY); *declared = false;
+    const hipFunction_t f = env_module_optional(mod, "dril_env_plugin_obs_space");
+    if (!f) return DRIL_OK;
+    float* buf = nullptr; std::vector<float> host(2 * (size_t)d.D);
+    hipError_t e = hipMalloc((void**)&buf, host.size() * sizeof(float));
+    if (e == hipSuccess) { DrilEnvPluginArgs a{}; a.E = 1; a.obs = buf; e = env_module_launch(f, a, nullptr); }
+    if (e == hipSuccess) e = hipMemcpy(host.data(), buf, host.size() * sizeof(float), hipMemcpyDeviceToHost);   // (the null stream: ordered after the launch)
+    if (buf) (void)hipFree(buf);
+    if (e != hipSuccess) { msg = std::string("reading the plug-in's observation space (dril_env_plugin_obs_space): ") + hipGetErrorString(e); return DRIL_ERR_HIP; }
+    std::copy(host.begin(), host.begin() + d.D, low.begin()); std::copy(host.begin() + d.D, host.end(), high.begin()); *declared = true;
+    return DRIL_OK;
+}
+// dril_env_module_obs_space: load, check, read the space, unload (the checks and statuses of dril_env_module_describe)
+inline int describe_module_obs_space(const char* path, int device, float* low, float* high, int32_t* declared, std::string& msg) {
+    hipModule_t mod = nullptr; DrilEnvPluginDesc d{};
+    int rc = load_env_module(path, device, &mod, &d, msg); if (rc) return rc;
+    std::vector<float> lo, hi; bool decl = false;
+    rc = read_module_obs_space(mod, d, lo, hi, &decl, msg);
+    (void)hipModuleUnload(mod);
+    if (rc) return rc;
+    if (low) std::memcpy(low, lo.data(), lo.size() * sizeof(float));
+    if (high) std::memcpy(high, hi.data(), hi.size() * sizeof(float));
+    if (declared) *declared = decl ? 1 : 0;
+    return DRIL_OK;
+}
 // ---- the envs of one handle ----
 // where one act! puts its results (device arrays of E entries, terminal_obs E x D); obs: null, or where the observation AFTER the step goes (a plug-in's step kernel
 // writes it in the same launch, a built-in kind's env_observe_kernel follows)
@@ -74,6 +111,10 @@ struct DeviceEnvs {
     float* state = nullptr; int32_t* step_count = nullptr; uint32_t *episode = nullptr, *gstep = nullptr; float* disc_returns = nullptr;   // E x S, E, E, E, E
     // DRIL_ENV_MODULE: the loaded plug-in (null: a built-in kind, or the host envs of DRIL_ENV_EXTERNAL); its three kernels stand in for env_reset / env_observe / env_step_kernel
     hipModule_t module = nullptr; hipFunction_t mod_reset = nullptr, mod_observe = nullptr, mod_step = nullptr; DrilEnvPluginDesc desc{};
+    // the plug-in's declared observation space (obs_declared false: the env declares none; the vectors then hold -inf / +inf) and ScalingWrapperEnv
+    // (scalingWrapperEnv.jl) around every env: `scaling` on = the plug-in's _scaled kernels stand where observe / step stood, agent-facing spaces Box(-1, 1)
+    std::vector<float> obs_low, obs_high; bool obs_declared = false, scaling = false;
+    hipFunction_t mod_observe_scaled = nullptr, mod_step_scaled = nullptr;
 
     // what the envs are; for DRIL_ENV_MODULE also the plug-in: loaded, its descriptor kept, episode_len 0 replaced by the descriptor's, its three kernels found.
     // Makes `device` current when it loads; on failure nothing is held and msg says why.
@@ -87,7 +128,35 @@ struct DeviceEnvs {
             const hipError_t e = hipModuleGetFunction(fns[i], module, names[i]);
             if (e != hipSuccess) { msg = std::string("hipModuleGetFunction(") + names[i] + "): " + hipGetErrorString(e); release(); return DRIL_ERR_HIP; }
         }
+        mod_observe_scaled = env_module_optional(module, "dril_env_plugin_observe_scaled"); mod_step_scaled = env_module_optional(module, "dril_env_plugin_step_scaled");
+        const int rs = read_module_obs_space(module, desc, obs_low, obs_high, &obs_declared, msg);
+        if (rs) release();
+        return rs;
+    }
+    // ScalingWrapperEnv on / off.  Legal on a plug-in handle whose envs have not been reset yet (between create and the first reset!): observations handed out
+    // before would change their meaning under the caller.  Every refusal says what to do instead.
+    int set_scaling(bool on, std::string& msg) {
+        if (!module) { msg = "ScalingWrapperEnv by this verb wraps a device env plug-in (DRIL_ENV_MODULE): a built-in env is scaled by its own kind (DRIL_ENV_PENDULUM_SCALED, DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED), a host env (DRIL_ENV_EXTERNAL) on the host"; return DRIL_ERR_UNSUPPORTED; }
+        if (ready) { msg = "ScalingWrapperEnv is chosen between create and the first env reset (observations already handed out would change their meaning): create a new handle"; return DRIL_ERR_INVALID_ARG; }
+        if (on) {
+            const std::string who = std::string("env plug-in \"") + desc.name + "\"";
+            if (desc.discrete) { msg = who + " has a Discrete action space: ScalingWrapperEnv needs Box observation and action spaces (scalingWrapperEnv.jl:22)"; return DRIL_ERR_UNSUPPORTED; }
+            if (!obs_declared) { msg = who + " declares no observation space: add static constexpr float obs_low[D], obs_high[D] to the env and rebuild the code object with this library's include/device/dril_env_plugin.h"; return DRIL_ERR_UNSUPPORTED; }
+            auto bad = [](float lo, float hi) { return !(std::isfinite(lo) && std::isfinite(hi) && lo < hi); };
+            for (int i = 0; i < desc.D; ++i) if (bad(obs_low[i], obs_high[i])) { msg = who + ": observation dim " + std::to_string(i) + " has bounds [" + std::to_string(obs_low[i]) + ", " + std::to_string(obs_high[i]) + "]: ScalingWrapperEnv needs finite bounds with low < high in every dimension; declare such bounds (or wrap without scaling)"; return DRIL_ERR_UNSUPPORTED; }
+            for (int i = 0; i < desc.A; ++i) if (bad(desc.action_low[i], desc.action_high[i])) { msg = who + ": action dim " + std::to_string(i) + " has bounds [" + std::to_string(desc.action_low[i]) + ", " + std::to_string(desc.action_high[i]) + "]: ScalingWrapperEnv needs finite bounds with low < high in every dimension"; return DRIL_ERR_UNSUPPORTED; }
+            if (!mod_observe_scaled || !mod_step_scaled) { msg = who + ": the code object has no dril_env_plugin_observe_scaled / dril_env_plugin_step_scaled kernels: rebuild it with this library's include/device/dril_env_plugin.h"; return DRIL_ERR_UNSUPPORTED; }
+        }
+        scaling = on;
         return DRIL_OK;
+    }
+    // the observation space the agent sees (low[D], high[D]; either may be null): Box(-1, 1) under ScalingWrapperEnv, the declared space otherwise
+    void agent_obs_space(float* low, float* high) const {
+        for (int i = 0; i < desc.D; ++i) { if (low) low[i] = scaling ? -1.0f : obs_low[i]; if (high) high[i] = scaling ? 1.0f : obs_high[i]; }
+    }
+    // the action space the agent's adapters act on (Box plug-ins): Box(-1, 1) under ScalingWrapperEnv, the env's own bounds otherwise
+    void agent_action_space(float* low, float* high) const {
+        for (int i = 0; i < desc.A; ++i) { if (low) low[i] = scaling ? -1.0f : desc.action_low[i]; if (high) high[i] = scaling ? 1.0f : desc.action_high[i]; }
     }
     // the per-env arrays, on the current device; S: floats of one env's simulator state
     hipError_t alloc(int S) {
@@ -119,7 +188,7 @@ struct DeviceEnvs {
         return launch_env_reset(kind, E, seed0, state, step_count, episode, gstep, disc_returns, s);
     }
     hipError_t observe(float* obs, hipStream_t s) const {
-        if (module) { DrilEnvPluginArgs a = args(); a.obs = obs; return env_module_launch(mod_observe, a, s); }
+        if (module) { DrilEnvPluginArgs a = args(); a.obs = obs; return env_module_launch(scaling ? mod_observe_scaled : mod_observe, a, s); }
         return launch_env_observe(kind, E, state, obs, s);
     }
     hipError_t step(const void* actions, const EnvStepOut& o, const MonitorArgs& mon, hipStream_t s) const {
@@ -127,7 +196,7 @@ struct DeviceEnvs {
             DrilEnvPluginArgs a = args();
             a.actions = actions; a.rewards = o.rewards; a.terminated = o.terminated; a.truncated = o.truncated; a.terminal_obs = o.terminal_obs; a.obs = o.obs;
             a.flags = mon.flags_out; a.mon_cur_ret = mon.cur_ret; a.mon_cur_len = mon.cur_len; a.ep_ret = mon.ep_ret; a.ep_len = mon.ep_len;
-            return env_module_launch(mod_step, a, s);
+            return env_module_launch(scaling ? mod_step_scaled : mod_step, a, s);
         }
         const hipError_t e = launch_env_step(kind, E, seed0, episode_len, fixed_len, action_start, actions, state, step_count, episode, gstep,
                                              o.rewards, o.terminated, o.truncated, o.terminal_obs, mon, s);

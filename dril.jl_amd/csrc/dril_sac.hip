@@ -1885,6 +1885,34 @@ DRIL_EXPORT int32_t dril_sac_env_module_info_of(const dril_sac_handle* h, dril_e
     fill_module_info(h->env.desc, out);
     return DRIL_OK;
 }
+DRIL_EXPORT int32_t dril_sac_env_module_obs_space_of(const dril_sac_handle* h, float* low, float* high, int32_t* declared) {
+    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_obs_space_of: the handle was not created with dril_sac_create_with_env_module");
+    const int D = h->env.desc.D;
+    if (low) std::memcpy(low, h->env.obs_low.data(), (size_t)D * 4);
+    if (high) std::memcpy(high, h->env.obs_high.data(), (size_t)D * 4);
+    if (declared) *declared = h->env.obs_declared ? 1 : 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_scaling_enable(dril_sac_handle* h, int32_t on) {
+    SNEED(h);
+    std::string msg; const int rc = h->env.set_scaling(on != 0, msg);
+    if (rc) return sfail(h, rc, "dril_sac_scaling_enable: " + msg);
+    // the adapters act on the wrapper's action space: the table the sampling kernels read (TanhScaleAdapter per dimension, rand(action_space) of the start phase).
+    // The envs have not been reset, so nothing that reads the table is in flight.
+    float tb[2 * kMaxA];
+    SHIP(h, hipMemcpy(tb, h->act_bounds, sizeof(tb), hipMemcpyDeviceToHost));
+    h->env.agent_action_space(tb, tb + kMaxA);
+    SHIP(h, hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_agent_spaces(const dril_sac_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling) {
+    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_agent_spaces: the handle was not created with dril_sac_create_with_env_module");
+    h->env.agent_obs_space(obs_low, obs_high); h->env.agent_action_space(action_low, action_high);
+    if (scaling) *scaling = h->env.scaling ? 1 : 0;
+    return DRIL_OK;
+}
 
 namespace {
 int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sac_handle** out) {

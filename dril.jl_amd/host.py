@@ -132,6 +132,15 @@ class ScalingWrapperEnv:
     [-1, 1]; on device the two affine maps are fused into the env kernels (env kinds DRIL_ENV_PENDULUM_SCALED, DRIL_ENV_MOUNTAINCAR_CONTINUOUS_SCALED)."""
     env: object
 
+    def __new__(cls, env=None):
+        """ScalingWrapperEnv(DeviceModuleEnv(path, n)): the wrapper around every env of a device env plug-in is a mode of the plug-in's own kernels
+        (dril_scaling_enable), so — like NormalizeWrapperEnv — this returns the parallel env with the wrapper switched on"""
+        if isinstance(env, DeviceParallelEnv):
+            if not isinstance(env, DeviceModuleEnv):
+                raise NotImplementedError("ScalingWrapperEnv wraps single envs (ScalingWrapperEnv(PendulumEnv()), then DeviceParallelEnv) or a DeviceModuleEnv")
+            return env._set_scaling(True)
+        return super().__new__(cls)
+
     def __post_init__(self):
         if not isinstance(self.env, (PendulumEnv, MountainCarContinuousEnv)):
             raise NotImplementedError("ScalingWrapperEnv needs Box observation and action spaces (scalingWrapperEnv.jl:22); the device envs with both are Pendulum-v1 and MountainCarContinuous-v0")
@@ -387,13 +396,27 @@ def _module_info_dict(info) -> dict:
 
 
 def describe_env_module(code_object_path, device: int = 0) -> dict:
-    """dril_env_module_describe: what a device env plug-in's code object says about itself (spaces, bounds, time limit, name)."""
+    """dril_env_module_describe + dril_env_module_obs_space: what a device env plug-in's code object says about itself (spaces, bounds, time limit, name;
+    `obs_low` / `obs_high` and `obs_declared`: the observation space the env declares, -inf / +inf and False when it declares none)."""
     lib = capi.load_library()
     info = capi.DrilEnvModuleInfo()
     rc = lib.dril_env_module_describe(os.fsencode(code_object_path), device, C.byref(info))
     if rc != capi.OK:
         raise DrilError(rc, (lib.dril_last_error(None) or b"").decode())
-    return _module_info_dict(info)
+    d = _module_info_dict(info)
+    lo, hi, decl = np.empty(info.obs_dim, np.float32), np.empty(info.obs_dim, np.float32), C.c_int32()
+    rc = lib.dril_env_module_obs_space(os.fsencode(code_object_path), device, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), C.byref(decl))
+    if rc != capi.OK:
+        raise DrilError(rc, (lib.dril_last_error(None) or b"").decode())
+    d.update(obs_low=lo, obs_high=hi, obs_declared=bool(decl.value))
+    return d
+
+
+def _agent_spaces(fn, h, D: int, A: int) -> dict:
+    """dril_agent_spaces / dril_sac_agent_spaces as a dict"""
+    ol, oh, al, ah, on = (np.empty(D, np.float32), np.empty(D, np.float32), np.full(A, np.nan, np.float32), np.full(A, np.nan, np.float32), C.c_int32())
+    rc = fn(h, *(a.ctypes.data_as(C.c_void_p) for a in (ol, oh, al, ah)), C.byref(on))
+    return rc, dict(obs_low=ol, obs_high=oh, action_low=al, action_high=ah, scaling=bool(on.value))
 
 
 @_normalize.normalize_verbs(lambda self, verb: getattr(self.lib, "dril_normalize_" + verb), "normalize_")
@@ -471,6 +494,22 @@ class Handle:
         info = capi.DrilEnvModuleInfo()
         self._chk(self.lib.dril_env_module_info_of(self._h, C.byref(info)))
         return _module_info_dict(info)
+
+    def env_module_obs_space(self) -> dict:
+        """dril_env_module_obs_space_of: the observation space the plug-in declares (the env's own, whether ScalingWrapperEnv is on or not)"""
+        lo, hi, decl = np.empty(self.D, np.float32), np.empty(self.D, np.float32), C.c_int32()
+        self._chk(self.lib.dril_env_module_obs_space_of(self._h, self._p(lo), self._p(hi), C.byref(decl)))
+        return dict(low=lo, high=hi, declared=bool(decl.value))
+
+    def scaling_enable(self, on: bool = True):
+        """dril_scaling_enable: ScalingWrapperEnv around every env of a plug-in handle; between create and the first env_reset"""
+        self._chk(self.lib.dril_scaling_enable(self._h, int(bool(on))))
+
+    def agent_spaces(self) -> dict:
+        """dril_agent_spaces: the spaces the agent sees (Box(-1, 1) throughout under ScalingWrapperEnv)"""
+        rc, d = _agent_spaces(self.lib.dril_agent_spaces, self._h, self.D, self.A)
+        self._chk(rc)
+        return d
 
     def env_reset(self, seed: int):
         self._chk(self.lib.dril_env_reset(self._h, seed))
@@ -830,15 +869,43 @@ class ModuleEnv:
     max_steps: int
     action_start: int = 1
     kind: int = capi.ENV_MODULE
+    scaling: bool = False            # ScalingWrapperEnv around the env (DeviceModuleEnv(..., scaling=True) / ScalingWrapperEnv(DeviceModuleEnv(...)))
 
-    def observation_space(self):
+    def declared_observation_space(self):
+        """the env's own observation space: the declared box, or Box(-inf, inf) when the plug-in declares none"""
         D = self.info["obs_dim"]
-        return Box((-math.inf,) * D, (math.inf,) * D)
+        if not self.info.get("obs_declared"):
+            return Box((-math.inf,) * D, (math.inf,) * D)
+        return Box(tuple(float(v) for v in self.info["obs_low"]), tuple(float(v) for v in self.info["obs_high"]))
 
-    def action_space(self):
+    def declared_action_space(self):
         if self.info["discrete"]:
             return Discrete(self.info["action_dim"], self.action_start)
         return Box(tuple(float(v) for v in self.info["action_low"]), tuple(float(v) for v in self.info["action_high"]))
+
+    def observation_space(self):
+        D = self.info["obs_dim"]
+        return Box((-1.0,) * D, (1.0,) * D) if self.scaling else self.declared_observation_space()
+
+    def action_space(self):
+        A = self.info["action_dim"]
+        return Box((-1.0,) * A, (1.0,) * A) if self.scaling else self.declared_action_space()
+
+    # scale! / unscale! (scalingWrapperEnv.jl:71-79) on host arrays, from the declared bounds
+    def _bounds(self, space):
+        return (np.asarray(v, np.float32) for v in (space.low, space.high))
+
+    def scale_observation(self, obs):
+        lo, hi = self._bounds(self.declared_observation_space())
+        return (np.asarray(obs, np.float32) - lo) * (np.float32(2) / (hi - lo)) - np.float32(1)
+
+    def unscale_observation(self, obs):
+        lo, hi = self._bounds(self.declared_observation_space())
+        return (np.asarray(obs, np.float32) + np.float32(1)) / (np.float32(2) / (hi - lo)) + lo
+
+    def unscale_action(self, act):
+        lo, hi = self._bounds(self.declared_action_space())
+        return (np.asarray(act, np.float32) + np.float32(1)) / (np.float32(2) / (hi - lo)) + lo
 
 
 class DeviceModuleEnv(DeviceParallelEnv):
@@ -852,12 +919,18 @@ class DeviceModuleEnv(DeviceParallelEnv):
     get_original_obs / get_original_rewards honour it.  The keyword takes part in bind's key.  The statistics live in the handle: a bind that has to re-create the
     handle (another alg or layer shape) starts a FRESH wrapper — a caller who wants to carry the statistics over saves them before
     (`env.handle.normalize_get_stats()`) and loads them after (`env.handle.normalize_set_stats(**st)`).
-    The function NormalizeWrapperEnv(DeviceModuleEnv(...)) stays refused: it works through cfg.norm_*, which size the built-in envs' tables (docs/external_envs.md)."""
+    The function NormalizeWrapperEnv(DeviceModuleEnv(...)) stays refused: it works through cfg.norm_*, which size the built-in envs' tables (docs/external_envs.md).
+
+    `scaling=True` (or ScalingWrapperEnv(DeviceModuleEnv(...))) puts ScalingWrapperEnv around every env: the plug-in's own _scaled kernels run where observe / step ran
+    (dril_scaling_enable, applied to a fresh handle before its first reset), `observation_space()` / `action_space()` become Box(-1, 1), and NormalizeWrapperEnv —
+    when both are asked for — sits outside it.  It needs a plug-in that declares finite obs_low / obs_high; the library's refusal says what is missing.  Part of
+    bind's key.  `scale_observation / unscale_observation / unscale_action` convert host arrays with the declared bounds."""
 
     def __init__(self, code_object_path, n_envs: int, *, seed: int = 42, device: int = 0, max_steps: Optional[int] = None, action_start: int = 1,
-                 fixed_length_episodes: bool = False, rank: int = 0, world_size: int = 1, profile_events: bool = False, normalize: Optional[dict] = None):
+                 fixed_length_episodes: bool = False, rank: int = 0, world_size: int = 1, profile_events: bool = False, normalize: Optional[dict] = None,
+                 scaling: bool = False):
         info = describe_env_module(code_object_path, device)
-        env = ModuleEnv(os.fspath(code_object_path), info, int(max_steps) if max_steps else info["episode_len"], action_start)
+        env = ModuleEnv(os.fspath(code_object_path), info, int(max_steps) if max_steps else info["episode_len"], action_start, scaling=bool(scaling))
         super().__init__(env, n_envs, seed=seed, fixed_length_episodes=fixed_length_episodes, device=device, rank=rank, world_size=world_size,
                          profile_events=profile_events)
         if normalize is not None:
@@ -868,11 +941,30 @@ class DeviceModuleEnv(DeviceParallelEnv):
         self.module_normalize = normalize
 
     def _bind_extra(self):
-        return None if self.module_normalize is None else tuple(sorted(self.module_normalize.items()))
+        return (None if self.module_normalize is None else tuple(sorted(self.module_normalize.items())), self.env.scaling)
 
     def _after_create(self, h: Handle):
+        if self.env.scaling:                      # inside NormalizeWrapperEnv: its statistics are those of scaled observations
+            h.scaling_enable(True)
         if self.module_normalize is not None:
             h.normalize_enable(**self.module_normalize)
+
+    def _set_scaling(self, on: bool):
+        self.env.scaling = bool(on)
+        if self.handle is not None:
+            self.handle.close(); self.handle = None
+        if on:                                    # fail here, with the library's message, rather than at the first bind
+            self._h()
+        return self
+
+    def scale_observation(self, obs):
+        return self.env.scale_observation(obs)
+
+    def unscale_observation(self, obs):
+        return self.env.unscale_observation(obs)
+
+    def unscale_action(self, act):
+        return self.env.unscale_action(act)
 
 
 class HostParallelEnv:

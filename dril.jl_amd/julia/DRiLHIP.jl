@@ -124,22 +124,26 @@ function describe_env_module(path::AbstractString, device::Integer = 0)
     i32 = reinterpret(Int32, buf[5:24]); A = Int(i32[3])
     low = collect(reinterpret(Float32, buf[25:280]))[1:A]; high = collect(reinterpret(Float32, buf[281:536]))[1:A]
     name = String(buf[537:(536 + something(findfirst(==(0x00), buf[537:end]), 65) - 1)])
-    return (path = String(path), state_dim = Int(i32[1]), obs_dim = Int(i32[2]), action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]), low = low, high = high, name = name)
+    D = Int(i32[2]); obs_low = zeros(Float32, D); obs_high = zeros(Float32, D); declared = Ref{Int32}(0)    # the observation space the env declares (-Inf / Inf and false: none)
+    check(ccall((:dril_env_module_obs_space, LIB[]), Int32, (Cstring, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}), path, Int32(device), obs_low, obs_high, declared))
+    return (path = String(path), state_dim = Int(i32[1]), obs_dim = D, action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]), low = low, high = high, name = name,
+        obs_low = obs_low, obs_high = obs_high, obs_declared = declared[] != 0, scaling = false)
 end
-"`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv, for PPO and SAC alike"
+"`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv, for PPO and SAC alike; `scaling = true` = ScalingWrapperEnv around every env (the plug-in's own _scaled kernels, spaces Box(-1, 1); inside NormalizeWrapperEnv)"
 function OnDeviceModule(path::AbstractString, n_envs::Integer; max_steps::Union{Nothing, Integer} = nothing, seed::Integer = 42, device::Integer = 0, monitor_window::Integer = 0,
-        normalize::Union{Nothing, NamedTuple} = nothing)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (dril_sac_normalize_enable) and by the PPO handle (dril_normalize_enable, applied in bind!)
+        normalize::Union{Nothing, NamedTuple} = nothing, scaling::Bool = false)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (dril_sac_normalize_enable) and by the PPO handle (dril_normalize_enable, applied in bind!)
     info = describe_env_module(path, device)
     env = DeviceParallelEnv(:Module, n_envs; max_steps = something(max_steps, info.episode_len), seed = seed, device = device, monitor_window = monitor_window, normalize = normalize)
-    MODULE_ENVS[env] = info
+    MODULE_ENVS[env] = merge(info, (scaling = scaling,))     # applied to every handle of this env right after create (dril_scaling_enable / dril_sac_scaling_enable), where the library refuses what it cannot scale
     return env
 end
 is_discrete(env) = env.kind === :Module ? MODULE_ENVS[env].discrete : env.kind === :CartPole || env.kind === :MountainCar || env.kind === :Acrobot
-observation_space(env::DeviceParallelEnv) = env.kind === :Module ? Box(fill(-Inf32, MODULE_ENVS[env].obs_dim), fill(Inf32, MODULE_ENVS[env].obs_dim)) : env.kind === :Acrobot ? Box(Float32[-1, -1, -1, -1, -4π, -9π], Float32[1, 1, 1, 1, 4π, 9π]) : (env.kind === :MountainCar || env.kind === :MountainCarContinuous) ? Box(Float32[-1.2, -0.07], Float32[0.6, 0.07]) : env.kind === :ScaledMountainCarContinuous ? Box(Float32[-1, -1], Float32[1, 1]) :
+module_box(n::Integer) = Box(fill(-1.0f0, n), fill(1.0f0, n))      # the agent-facing spaces of ScalingWrapperEnv
+observation_space(env::DeviceParallelEnv) = env.kind === :Module ? (MODULE_ENVS[env].scaling ? module_box(MODULE_ENVS[env].obs_dim) : Box(MODULE_ENVS[env].obs_low, MODULE_ENVS[env].obs_high)) : env.kind === :Acrobot ? Box(Float32[-1, -1, -1, -1, -4π, -9π], Float32[1, 1, 1, 1, 4π, 9π]) : (env.kind === :MountainCar || env.kind === :MountainCarContinuous) ? Box(Float32[-1.2, -0.07], Float32[0.6, 0.07]) : env.kind === :ScaledMountainCarContinuous ? Box(Float32[-1, -1], Float32[1, 1]) :
     env.kind === :CartPole ?
     Box(Float32[-4.8, -Inf, -0.41887903, -Inf], Float32[4.8, Inf, 0.41887903, Inf]) :
     env.kind === :ScaledPendulum ? Box(Float32[-1, -1, -1], Float32[1, 1, 1]) : Box(Float32[-1, -1, -8], Float32[1, 1, 8])
-action_space(env::DeviceParallelEnv) = env.kind === :Module ? (MODULE_ENVS[env].discrete ? Discrete(MODULE_ENVS[env].action_dim) : Box(MODULE_ENVS[env].low, MODULE_ENVS[env].high)) : env.kind === :CartPole ? Discrete(2) : (env.kind === :MountainCar || env.kind === :Acrobot) ? Discrete(3) :
+action_space(env::DeviceParallelEnv) = env.kind === :Module ? (MODULE_ENVS[env].discrete ? Discrete(MODULE_ENVS[env].action_dim) : MODULE_ENVS[env].scaling ? module_box(MODULE_ENVS[env].action_dim) : Box(MODULE_ENVS[env].low, MODULE_ENVS[env].high)) : env.kind === :CartPole ? Discrete(2) : (env.kind === :MountainCar || env.kind === :Acrobot) ? Discrete(3) :
     (env.kind === :ScaledPendulum || env.kind === :MountainCarContinuous || env.kind === :ScaledMountainCarContinuous) ? Box(Float32[-1], Float32[1]) : Box(Float32[-2], Float32[2])
 obs_dim(env::DeviceParallelEnv) = env.kind === :Module ? MODULE_ENVS[env].obs_dim : env.kind === :CartPole ? 4 : env.kind === :Acrobot ? 6 : (env.kind === :MountainCar || env.kind === :MountainCarContinuous || env.kind === :ScaledMountainCarContinuous) ? 2 : 3
 
@@ -210,6 +214,7 @@ function bind!(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int} = [64, 64],
         h = Ref{Ptr{Cvoid}}(C_NULL)
         if env.kind === :Module                                  # a device env plug-in: the library loads the code object itself
             check(ccall((:dril_create_with_env_module, LIB[]), Int32, (Ref{DrilConfig}, Cstring, Ref{Ptr{Cvoid}}), cfg, MODULE_ENVS[env].path, h))
+            MODULE_ENVS[env].scaling && check(ccall((:dril_scaling_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h[], Int32(1)), h[])   # ScalingWrapperEnv: before the first reset, inside NormalizeWrapperEnv
             env.normalize === nothing || normalize_enable!(h[], env.normalize)   # train!(agent, env, alg::PPO, ...) and evaluate_agent then run under the wrapper (evaluation: frozen, raw returns)
         else
             check(ccall((:dril_create, LIB[]), Int32, (Ref{DrilConfig}, Ref{Ptr{Cvoid}}), cfg, h))

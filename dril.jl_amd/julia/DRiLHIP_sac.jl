@@ -131,6 +131,10 @@ function sac_create(env::DeviceParallelEnv, alg::DRiL.SAC, agent)
         sac_check(ccall((:dril_sac_create, LIB[]), Int32, (Ref{DrilSacConfig}, Ref{Ptr{Cvoid}}), cfg, hp))
     end
     h = hp[]
+    if env.kind === :Module && MODULE_ENVS[env].scaling      # ScalingWrapperEnv: before the first reset, inside NormalizeWrapperEnv; the adapters then see Box(-1, 1)
+        rc = ccall((:dril_sac_scaling_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(1))
+        rc == 0 || (msg = unsafe_string(ccall((:dril_sac_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h)); ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h); error("libdril_hip (SAC) status $rc: " * msg))
+    end
     if env.monitor_window > 0
         rc = ccall((:dril_sac_monitor_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, env.monitor_window)
         rc == 0 || (msg = unsafe_string(ccall((:dril_sac_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h)); ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h); error("libdril_hip (SAC) status $rc: " * msg))

@@ -207,6 +207,23 @@ class SacHandle:
     def _f(self, name):
         return getattr(self.lib, self.prefix + name)
 
+    def env_module_obs_space(self) -> dict:
+        """dril_sac_env_module_obs_space_of: the observation space the plug-in declares"""
+        lo, hi, decl = np.empty(self.D, np.float32), np.empty(self.D, np.float32), C.c_int32()
+        self._chk(self._f("env_module_obs_space_of")(self._h, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), C.byref(decl)))
+        return dict(low=lo, high=hi, declared=bool(decl.value))
+
+    def scaling_enable(self, on: bool = True):
+        """dril_sac_scaling_enable: ScalingWrapperEnv around every env of a plug-in handle; between create and the first env_reset"""
+        self._chk(self._f("scaling_enable")(self._h, int(bool(on))))
+
+    def agent_spaces(self) -> dict:
+        """dril_sac_agent_spaces: the spaces the agent and its adapters see (Box(-1, 1) throughout under ScalingWrapperEnv)"""
+        from .host import _agent_spaces
+        rc, d = _agent_spaces(self._f("agent_spaces"), self._h, self.D, self.A)
+        self._chk(rc)
+        return d
+
     def env_module_info(self) -> dict:
         """dril_sac_env_module_info_of: spaces and bounds of the plug-in behind this handle"""
         from .host import _module_info_dict
@@ -472,6 +489,14 @@ def _monitor_from_env(h: SacHandle, env):
         h.monitor_enable(window)
 
 
+def _scaling_from_env(h: SacHandle, env):
+    """ScalingWrapperEnv around a DeviceModuleEnv (DeviceModuleEnv(..., scaling=True) / ScalingWrapperEnv(DeviceModuleEnv(...))): the same wrapper around the SAC
+    handle's envs, before their first reset and inside NormalizeWrapperEnv.  A handle that comes back with a replay buffer already has it."""
+    want = bool(getattr(getattr(env, "env", None), "scaling", False))
+    if getattr(getattr(env, "env", None), "kind", None) == capi.ENV_MODULE and h.agent_spaces()["scaling"] != want:
+        h.scaling_enable(want)
+
+
 def _normalize_kw(env, normalize: Optional[dict]) -> Optional[dict]:
     """the NormalizeWrapperEnv keywords of a run: the `normalize=` argument (the one way a DeviceModuleEnv gets the wrapper: host.NormalizeWrapperEnv probes the PPO
     handle, which refuses plug-ins) wins over what NormalizeWrapperEnv(DeviceParallelEnv(...)) recorded in the env's keywords; None: no wrapper"""
@@ -506,6 +531,7 @@ def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, determin
     h = SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     try:
         h.set_params(sac_flatten_params(agent.parameters))
+        _scaling_from_env(h, env)
         kw = _normalize_kw(env, normalize)
         if kw is not None:           # sync_normalization_stats! + set_training(eval_env, false) (normalizeWrapperEnv.jl:245-249,299-309): the training statistics, frozen
             h.normalize_enable(**{**kw, "training": False})
@@ -543,6 +569,7 @@ def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer:
     h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
     _monitor_from_env(h, env)
+    _scaling_from_env(h, env)
     _normalize_from_env(h, env, normalize)
     h.set_params(sac_flatten_params(agent.parameters))
     h.set_target_params(agent.q_target_parameters)
@@ -587,6 +614,7 @@ def _sac_train_callbacks(agent: SACAgent, env, alg: SAC, max_steps: int, replay_
     h = rb.handle if rb.handle is not None else SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
     rb.handle = h
     _monitor_from_env(h, env)
+    _scaling_from_env(h, env)
     _normalize_from_env(h, env, normalize)
     h.set_params(sac_flatten_params(agent.parameters)); h.set_target_params(agent.q_target_parameters); h.set_log_ent_coef(agent.log_ent_coef)
     h.env_reset(env.seed)

@@ -8,6 +8,9 @@ struct CartPolePlugin {
     static constexpr int S = 4, D = 4, A = 2;
     static constexpr bool discrete = true;
     static constexpr int episode_len = 500;
+    // Gymnasium's observation space: twice the termination thresholds for x and theta, unbounded velocities (so ScalingWrapperEnv cannot wrap it, and as a
+    // Discrete env it could not anyway)
+    static constexpr float obs_low[D] = {-4.8f, -INFINITY, -0.41887903f, -INFINITY}, obs_high[D] = {4.8f, INFINITY, 0.41887903f, INFINITY};
     static constexpr const char* name = "CartPole-v1 (plug-in)";
     DRIL_ENV_FN static void reset(const DrilEnvRng& rng, float* st) {                 // U(-0.05, 0.05)^4 from the four words of block 0
         const DrilEnvWords r = rng.words(0);

@@ -9,6 +9,7 @@ struct PendulumPlugin {
     static constexpr bool discrete = false;
     static constexpr int episode_len = 200;
     static constexpr float action_low[A] = {-2.0f}, action_high[A] = {2.0f};
+    static constexpr float obs_low[D] = {-1.0f, -1.0f, -8.0f}, obs_high[D] = {1.0f, 1.0f, 8.0f};   // Gymnasium's Box: (cos, sin, theta_dot clipped to max_speed)
     static constexpr const char* name = "Pendulum-v1 (plug-in)";
     DRIL_ENV_FN static void reset(const DrilEnvRng& rng, float* st) {                 // theta ~ U(-pi, pi), theta_dot ~ U(-1, 1)
         const DrilEnvWords r = rng.words(0);

@@ -13,6 +13,10 @@ struct Reacher3 {
     static constexpr bool discrete = false;
     static constexpr int episode_len = 100;
     static constexpr float action_low[A] = {-1.0f, -1.0f, -1.0f}, action_high[A] = {1.0f, 1.0f, 1.0f};
+    // observation space: |p_i| <= 2 + one move while the episode lasts (a step past 2 terminates; |move| <= dt |v|), |v_i| < dt damping / (1 - damping) = 1.9,
+    // |g_i| <= 1, |p_i - g_i| <= 3.2
+    static constexpr float obs_low[D] = {-2.2f, -2.2f, -2.2f, -2.0f, -2.0f, -2.0f, -1.0f, -1.0f, -1.0f, -3.2f, -3.2f, -3.2f};
+    static constexpr float obs_high[D] = {2.2f, 2.2f, 2.2f, 2.0f, 2.0f, 2.0f, 1.0f, 1.0f, 1.0f, 3.2f, 3.2f, 3.2f};
     static constexpr const char* name = "Reacher3";
     DRIL_ENV_FN static void reset(const DrilEnvRng& rng, float* st) {                 // p ~ U(-0.5, 0.5)^3 (block 0), v = 0, g ~ U(-1, 1)^3 (block 1)
         const DrilEnvWords r0 = rng.words(0), r1 = rng.words(1);

@@ -4,7 +4,9 @@ observation dims, a three-dimensional force Box) is compiled by the library's Ma
 (dril_sac_create_with_env_module) and steps it with its own kernels between the actor's forward and the replay ring.  No host env anywhere in the loop:
 off-policy collection, the ring and every gradient step stay on the device.  The PPO twin of this file is examples/ppo_device_plugin.py.
 
-usage: python examples/sac_device_plugin.py [--normalize] [n_envs=16] [max_steps=30000]
+usage: python examples/sac_device_plugin.py [--normalize] [--scaling] [n_envs=16] [max_steps=30000]
+--scaling trains under ScalingWrapperEnv (dril_sac_scaling_enable: the plug-in's own _scaled kernels; observations in the ring and the actions the adapters
+produce live in Box(-1, 1)).
 --normalize trains through NormalizeWrapperEnv on the device (sac_train_(..., normalize=dict()): running statistics of the 12 mixed-scale observation dims and of
 the discounted returns, normalised rows in the ring) and evaluates with the training statistics, frozen; the final statistics are printed."""
 import sys
@@ -14,14 +16,14 @@ sys.path.insert(0, str(ROOT))
 import __graft_entry__ as g
 
 pkg = g.load_package()
-args = [a for a in sys.argv[1:] if a != "--normalize"]
+args = [a for a in sys.argv[1:] if a not in ("--normalize", "--scaling")]
 normalize = dict() if "--normalize" in sys.argv[1:] else None                # the reference's keyword defaults (normalizeWrapperEnv.jl:71-80)
 n_envs = int(args[0]) if len(args) > 0 else 16
 max_steps = int(args[1]) if len(args) > 1 else 30000
 code_object = ROOT / "examples" / "envs" / "reacher3_plugin.hsaco"        # built by `make -C dril.jl_amd/csrc` (__graft_entry__.build())
 info = pkg.describe_env_module(code_object)
 print("env:", info)
-env = pkg.DeviceModuleEnv(code_object, n_envs, seed=0)
+env = pkg.DeviceModuleEnv(code_object, n_envs, seed=0, scaling="--scaling" in sys.argv[1:])
 alg = pkg.SAC(learning_rate=1e-3, buffer_capacity=100_000, start_steps=100 * n_envs, batch_size=256, gradient_steps=8)
 agent = pkg.SACAgent(pkg.SACLayer(env.observation_space(), env.action_space(), hidden_dims=(64, 64)), alg, seed=0)
 env = pkg.MonitorWrapperEnv(env, 100)                                     # sac_train_ switches MonitorWrapperEnv on around the handle's envs: ep_rew_mean of the training episodes

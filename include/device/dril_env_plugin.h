@@ -18,11 +18,20 @@
 //     };
 //     DRIL_ENV_PLUGIN(MyEnv)
 //
+// Optionally the env declares its OBSERVATION SPACE, the Box of observation_space(env) (interfaces/environments.jl):
+//         static constexpr float obs_low[D] = {...}, obs_high[D] = {...};                      // -INFINITY / INFINITY allowed per dimension
+// DRIL_ENV_PLUGIN then emits one more kernel, dril_env_plugin_obs_space (one thread writes low[D] | high[D]; the library runs it once at load time), and — when
+// in addition the env is continuous and every observation bound and every action bound is finite with low < high (dril_env_plugin_scalable) — the two kernels of
+// ScalingWrapperEnv (scalingWrapperEnv.jl), dril_env_plugin_observe_scaled and dril_env_plugin_step_scaled: the same transition with the agent-facing spaces
+// Box(-1, 1), the affine maps of device/dril_scaling.h applied inside the one launch.  An env without obs_low / obs_high emits exactly the descriptor and the three
+// kernels it always did; the descriptor, the argument block and DRIL_ENV_PLUGIN_ABI are unchanged by any of this.
+//
 // Everything else — action adapters, step counters, truncation at the time limit, the BUF_FLAGS byte, terminal observation, MonitorWrapperEnv's sums, auto-reset —
 // is the LIBRARY's transition (EnvCursor / env_advance / env_end_episode of dril_device.h) and is written once, here, in dril_env_plugin_step_one.
 //
 // With DRIL_ENV_PLUGIN_HOST defined the same file compiles with a plain C++17 compiler (no HIP headers): the qualifiers vanish, no kernels are emitted, and
-// dril_env_plugin_host_reset / _observe / _step run the same wrapper over the E envs in a serial loop — for gdb, host sanitizers and CPU tests.
+// dril_env_plugin_host_reset / _observe / _step (and _obs_space / _observe_scaled / _step_scaled under the same conditions as the kernels) run the same wrapper
+// over the E envs in a serial loop — for gdb, host sanitizers and CPU tests.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,6 +43,7 @@
 #define DRIL_ENV_FN __device__
 #endif
 #include "dril_philox.h"
+#include "dril_scaling.h"
 
 #ifndef DRIL_ENV_PLUGIN_ABI
 #define DRIL_ENV_PLUGIN_ABI 1u       // bumps whenever DrilEnvPluginDesc / DrilEnvPluginArgs or the meaning of a field changes
@@ -81,12 +91,30 @@ struct DrilEnvRng {
 template <class Env, class = void> struct DrilEnvHasBounds { static constexpr bool value = false; };
 template <class Env> struct DrilEnvHasBounds<Env, decltype((void)Env::action_low[0], (void)Env::action_high[0], void())> { static constexpr bool value = true; };
 
+// the optional observation space: static constexpr float obs_low[D], obs_high[D]
+template <class Env, class = void> struct DrilEnvHasObsSpace { static constexpr bool value = false; };
+template <class Env> struct DrilEnvHasObsSpace<Env, decltype((void)Env::obs_low[0], (void)Env::obs_high[0], void())> { static constexpr bool value = true; };
+constexpr bool dril_env_plugin_finite_interval(float low, float high) { return low >= -3.402823466e38f && high <= 3.402823466e38f && low < high; }   // (a NaN fails every comparison)
+// ScalingWrapperEnv needs Box / Box with finite, non-empty bounds in every dimension (scalingWrapperEnv.jl:22): a declared observation space and a continuous env
+template <class Env> constexpr bool dril_env_plugin_scalable() {
+    if constexpr (Env::discrete || !DrilEnvHasObsSpace<Env>::value || !DrilEnvHasBounds<Env>::value) return false;
+    else {
+        for (int i = 0; i < Env::D; ++i) if (!dril_env_plugin_finite_interval(Env::obs_low[i], Env::obs_high[i])) return false;
+        for (int i = 0; i < Env::A; ++i) if (!dril_env_plugin_finite_interval(Env::action_low[i], Env::action_high[i])) return false;
+        return true;
+    }
+}
+
 template <class Env> struct DrilEnvPluginCheck {
     static_assert(Env::S >= 1 && Env::S <= DRIL_ENV_PLUGIN_MAX_S, "DRIL_ENV_PLUGIN: S (state floats per env) must be 1..64");
     static_assert(Env::D >= 1 && Env::D <= DRIL_ENV_PLUGIN_MAX_D, "DRIL_ENV_PLUGIN: D (observation dims) must be 1..1024");
     static_assert(Env::A >= 1 && Env::A <= DRIL_ENV_PLUGIN_MAX_A, "DRIL_ENV_PLUGIN: A (action dims, or number of discrete actions) must be 1..64");
     static_assert(Env::episode_len >= 1, "DRIL_ENV_PLUGIN: episode_len (the default time limit) must be >= 1");
     static_assert(Env::discrete || DrilEnvHasBounds<Env>::value, "DRIL_ENV_PLUGIN: a continuous env (discrete = false) must define static constexpr float action_low[A] and action_high[A]");
+    template <class E2 = Env> static constexpr bool obs_space_sized() {
+        if constexpr (DrilEnvHasObsSpace<E2>::value) return sizeof(E2::obs_low) == sizeof(float) * E2::D && sizeof(E2::obs_high) == sizeof(float) * E2::D; else return true;
+    }
+    static_assert(obs_space_sized(), "DRIL_ENV_PLUGIN: obs_low and obs_high must be float[D]");
     static constexpr bool ok = true;
 };
 
@@ -107,14 +135,28 @@ template <class Env> DRIL_ENV_FN inline void dril_env_plugin_reset_one(const Dri
     for (int i = 0; i < Env::S; ++i) a.state[(size_t)e * Env::S + i] = st[i];
     a.step_count[e] = 0; a.episode[e] = 0; a.gstep[e] = 0;
 }
-template <class Env> DRIL_ENV_FN inline void dril_env_plugin_observe_one(const DrilEnvPluginArgs& a, int e) {
+// observe(env); scaled: observe(::ScalingWrapperEnv) (scalingWrapperEnv.jl:93-98) — the env's observation, then scale! per dimension
+template <class Env, bool scaled> DRIL_ENV_FN inline void dril_env_plugin_emit_obs(const float* st, float* obs) {
+    Env::observe(st, obs);
+    if constexpr (scaled) {
+#pragma unroll
+        for (int i = 0; i < Env::D; ++i) obs[i] = dril::scale_to_unit(obs[i], Env::obs_low[i], Env::obs_high[i]);
+    }
+}
+template <class Env, bool scaled = false> DRIL_ENV_FN inline void dril_env_plugin_observe_one(const DrilEnvPluginArgs& a, int e) {
     float st[Env::S];
 #pragma unroll
     for (int i = 0; i < Env::S; ++i) st[i] = a.state[(size_t)e * Env::S + i];
-    Env::observe(st, a.obs + (size_t)e * Env::D);
+    dril_env_plugin_emit_obs<Env, scaled>(st, a.obs + (size_t)e * Env::D);
+}
+// the declared observation space, low[D] | high[D], into a.obs (2 D floats): one env's worth of work, run once when the library loads the plug-in
+template <class Env> DRIL_ENV_FN inline void dril_env_plugin_obs_space_one(const DrilEnvPluginArgs& a) {
+    for (int i = 0; i < Env::D; ++i) { a.obs[i] = Env::obs_low[i]; a.obs[Env::D + i] = Env::obs_high[i]; }
 }
 // act! with auto-reset under MonitorWrapperEnv: the steps are those of env_step_kernel (load -> env_advance -> terminal observation -> env_end_episode -> store)
-template <class Env> DRIL_ENV_FN inline void dril_env_plugin_step_one(const DrilEnvPluginArgs& a, int e) {
+// scaled: act!(::ScalingWrapperEnv, action) (scalingWrapperEnv.jl:110-113) — the agent-facing action space is Box(-1, 1): ClampAdapter on it, then unscale! into the
+// env's own bounds; every observation that leaves goes through scale!; reward, flags, counters, monitor sums and auto-reset are the env's own
+template <class Env, bool scaled = false> DRIL_ENV_FN inline void dril_env_plugin_step_one(const DrilEnvPluginArgs& a, int e) {
     constexpr int S = Env::S, D = Env::D, A = Env::A;
     // 1. the cursor
     float st[S];
@@ -129,7 +171,8 @@ template <class Env> DRIL_ENV_FN inline void dril_env_plugin_step_one(const Dril
 #pragma unroll
         for (int i = 0; i < A; ++i) {
             float v = ((const float*)a.actions)[(size_t)e * A + i];
-            if (Env::action_low[i] < Env::action_high[i]) v = fminf(fmaxf(v, Env::action_low[i]), Env::action_high[i]);
+            if constexpr (scaled) v = dril::unscale_from_unit(fminf(fmaxf(v, -1.0f), 1.0f), Env::action_low[i], Env::action_high[i]);
+            else if (Env::action_low[i] < Env::action_high[i]) v = fminf(fmaxf(v, Env::action_low[i]), Env::action_high[i]);
             act_f[i] = v;
         }
     }
@@ -146,7 +189,7 @@ template <class Env> DRIL_ENV_FN inline void dril_env_plugin_step_one(const Dril
     if (a.truncated) a.truncated[e] = trunc;
     if (a.flags) a.flags[e] = (uint8_t)((term ? 1 : 0) | (trunc ? 2 : 0));
     // 5. terminal observation: of the state HERE, after the step and before the reset
-    if (trunc && a.terminal_obs) Env::observe(st, a.terminal_obs + (size_t)e * D);
+    if (trunc && a.terminal_obs) dril_env_plugin_emit_obs<Env, scaled>(st, a.terminal_obs + (size_t)e * D);
     // 6. the episode ends: monitor, next episode
     if (term || trunc) {
         if (a.mon_cur_ret && a.ep_ret) { a.ep_ret[e] = mon_ret; a.ep_len[e] = mon_len; }
@@ -158,8 +201,49 @@ template <class Env> DRIL_ENV_FN inline void dril_env_plugin_step_one(const Dril
     a.step_count[e] = sc; a.episode[e] = ep; a.gstep[e] = gs;
     if (a.mon_cur_ret) { a.mon_cur_ret[e] = mon_ret; a.mon_cur_len[e] = mon_len; }
     // 7. the next observation
-    if (a.obs) Env::observe(st, a.obs + (size_t)e * D);
+    if (a.obs) dril_env_plugin_emit_obs<Env, scaled>(st, a.obs + (size_t)e * D);
 }
+
+// ---- the optional entry points ----------------------------------------------------------------------------------------------------------------------
+// An extern "C" definition inside the macro cannot depend on a constexpr condition, so the optional entry points are declared here and DEFINED as friends of a
+// class template that DRIL_ENV_PLUGIN instantiates explicitly: the definitions exist in the specialisations that fit the env, and nowhere else.  A code object has
+// dril_env_plugin_obs_space iff the env declares obs_low / obs_high, and the two _scaled kernels iff dril_env_plugin_scalable<Env>().
+// (the friends' bodies are one call each: the work is in the function templates before them)
+#if defined(DRIL_ENV_PLUGIN_HOST)
+#define DRIL_ENV_PLUGIN_ENTRY(name) __attribute__((visibility("default"))) void dril_env_plugin_host_##name(const DrilEnvPluginArgs* a)
+#define DRIL_ENV_PLUGIN_ENTRY_NAME(name) dril_env_plugin_host_##name
+typedef const DrilEnvPluginArgs* DrilEnvPluginEntryArg;
+template <class Env> inline void dril_env_plugin_run_obs_space(DrilEnvPluginEntryArg a) { dril_env_plugin_obs_space_one<Env>(*a); }
+template <class Env> inline void dril_env_plugin_run_observe_scaled(DrilEnvPluginEntryArg a) { for (int e = 0; e < a->E; ++e) dril_env_plugin_observe_one<Env, true>(*a, e); }
+template <class Env> inline void dril_env_plugin_run_step_scaled(DrilEnvPluginEntryArg a) { for (int e = 0; e < a->E; ++e) dril_env_plugin_step_one<Env, true>(*a, e); }
+#else
+// one thread per env, 256 threads per workgroup; the library launches ceil(E / 256) workgroups
+#define DRIL_ENV_PLUGIN_BLOCK 256
+#define DRIL_ENV_PLUGIN_ENTRY(name) __global__ void __launch_bounds__(DRIL_ENV_PLUGIN_BLOCK) dril_env_plugin_##name(DrilEnvPluginArgs a)
+#define DRIL_ENV_PLUGIN_ENTRY_NAME(name) dril_env_plugin_##name
+typedef DrilEnvPluginArgs DrilEnvPluginEntryArg;
+template <class Env> __device__ inline void dril_env_plugin_run_obs_space(const DrilEnvPluginArgs& a) { if (blockIdx.x == 0 && threadIdx.x == 0) dril_env_plugin_obs_space_one<Env>(a); }
+template <class Env> __device__ inline void dril_env_plugin_run_observe_scaled(const DrilEnvPluginArgs& a) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x; if (e < a.E) dril_env_plugin_observe_one<Env, true>(a, e); }
+template <class Env> __device__ inline void dril_env_plugin_run_step_scaled(const DrilEnvPluginArgs& a) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x; if (e < a.E) dril_env_plugin_step_one<Env, true>(a, e); }
+#endif
+typedef void (*DrilEnvPluginEntry)(DrilEnvPluginEntryArg);
+extern "C" { DRIL_ENV_PLUGIN_ENTRY(obs_space); DRIL_ENV_PLUGIN_ENTRY(observe_scaled); DRIL_ENV_PLUGIN_ENTRY(step_scaled); }
+template <class Env, bool declared> struct DrilEnvPluginObsSpaceEntry {};
+template <class Env> struct DrilEnvPluginObsSpaceEntry<Env, true> {
+    friend DRIL_ENV_PLUGIN_ENTRY(obs_space) { dril_env_plugin_run_obs_space<Env>(a); }
+    static constexpr DrilEnvPluginEntry obs_space = &DRIL_ENV_PLUGIN_ENTRY_NAME(obs_space);     // (the use that makes the friend's definition exist)
+};
+template <class Env, bool scalable> struct DrilEnvPluginScaledEntries {};
+template <class Env> struct DrilEnvPluginScaledEntries<Env, true> {
+    friend DRIL_ENV_PLUGIN_ENTRY(observe_scaled) { dril_env_plugin_run_observe_scaled<Env>(a); }
+    friend DRIL_ENV_PLUGIN_ENTRY(step_scaled) { dril_env_plugin_run_step_scaled<Env>(a); }
+    static constexpr DrilEnvPluginEntry observe_scaled = &DRIL_ENV_PLUGIN_ENTRY_NAME(observe_scaled), step_scaled = &DRIL_ENV_PLUGIN_ENTRY_NAME(step_scaled);
+};
+#define DRIL_ENV_PLUGIN_EMIT_OPTIONAL(Env)                                        \
+    template struct DrilEnvPluginObsSpaceEntry<Env, DrilEnvHasObsSpace<Env>::value>; \
+    template struct DrilEnvPluginScaledEntries<Env, dril_env_plugin_scalable<Env>()>;
 
 #if defined(DRIL_ENV_PLUGIN_HOST)
 #define DRIL_ENV_PLUGIN(Env)                                                                                                              \
@@ -169,10 +253,9 @@ template <class Env> DRIL_ENV_FN inline void dril_env_plugin_step_one(const Dril
     void dril_env_plugin_host_reset(const DrilEnvPluginArgs* a) { for (int e = 0; e < a->E; ++e) dril_env_plugin_reset_one<Env>(*a, e); }   \
     void dril_env_plugin_host_observe(const DrilEnvPluginArgs* a) { for (int e = 0; e < a->E; ++e) dril_env_plugin_observe_one<Env>(*a, e); } \
     void dril_env_plugin_host_step(const DrilEnvPluginArgs* a) { for (int e = 0; e < a->E; ++e) dril_env_plugin_step_one<Env>(*a, e); }   \
-    }
+    }                                                                                                                                     \
+    DRIL_ENV_PLUGIN_EMIT_OPTIONAL(Env)
 #else
-// one thread per env, 256 threads per workgroup; the library launches ceil(E / 256) workgroups
-#define DRIL_ENV_PLUGIN_BLOCK 256
 #define DRIL_ENV_PLUGIN(Env)                                                                                                              \
     static_assert(DrilEnvPluginCheck<Env>::ok, "");                                                                                       \
     extern "C" {                                                                                                                          \
@@ -183,5 +266,6 @@ template <class Env> DRIL_ENV_FN inline void dril_env_plugin_step_one(const Dril
         const int e = blockIdx.x * blockDim.x + threadIdx.x; if (e < a.E) dril_env_plugin_observe_one<Env>(a, e); }                       \
     __global__ void __launch_bounds__(DRIL_ENV_PLUGIN_BLOCK) dril_env_plugin_step(DrilEnvPluginArgs a) {                                  \
         const int e = blockIdx.x * blockDim.x + threadIdx.x; if (e < a.E) dril_env_plugin_step_one<Env>(a, e); }                          \
-    }
+    }                                                                                                                                     \
+    DRIL_ENV_PLUGIN_EMIT_OPTIONAL(Env)
 #endif

@@ -208,6 +208,27 @@ typedef struct dril_env_module_info {
 int32_t dril_env_module_describe(const char* code_object_path, int32_t device, dril_env_module_info* out);
 /* the same record of a live handle (DRIL_ERR_UNSUPPORTED for a handle of another env kind) */
 int32_t dril_env_module_info_of(const dril_handle* h, dril_env_module_info* out);
+/* The OBSERVATION SPACE a plug-in declares (static constexpr float obs_low[D], obs_high[D] in the env; observation_space of interfaces/environments.jl): low / high
+ * take obs_dim floats each (either may be NULL), *declared = 1.  A code object that declares none (or was built before the space existed) gives *declared = 0 and
+ * -inf / +inf in every dimension.  The struct above is unchanged by this; the checks and statuses are those of dril_env_module_describe.  The _of form reports the
+ * env's own space of a live handle, whether ScalingWrapperEnv is on or not (DRIL_ERR_UNSUPPORTED for a handle of another env kind). */
+int32_t dril_env_module_obs_space(const char* code_object_path, int32_t device, float* low, float* high, int32_t* declared);
+int32_t dril_env_module_obs_space_of(const dril_handle* h, float* low, float* high, int32_t* declared);
+/* ScalingWrapperEnv(env) (scalingWrapperEnv.jl) around every env of a device env plug-in handle: on != 0 makes the env side launch the plug-in's
+ * dril_env_plugin_observe_scaled / dril_env_plugin_step_scaled kernels where it launched observe / step — no launch is added per env step.  The agent-facing
+ * spaces become Box(-1, 1): raw actions are clamped to [-1, 1] and unscaled into the env's own bounds, every observation the env side hands out (observe, the next
+ * observation, the terminal observation of a truncated env) is scaled from the declared space; rewards, flags, counters and the monitor's sums are the env's own.
+ * Every device-env verb honours it (dril_env_reset / _observe / _step, dril_collect_rollout, dril_train, dril_evaluate_agent); NormalizeWrapperEnv
+ * (dril_normalize_enable) sits OUTSIDE it, so its statistics are those of scaled observations.
+ * LEGAL between create and the first dril_env_reset of the handle only: afterwards it is DRIL_ERR_INVALID_ARG and nothing changes (observations already handed
+ * out would change their meaning).  DRIL_ERR_UNSUPPORTED, with a message that says what to do, for: a handle that is not a plug-in handle (the built-in scaled
+ * kinds stay the way to scale a built-in env; a host env is wrapped on the host), a Discrete plug-in, a plug-in that declares no observation space, an
+ * observation or action dimension whose bounds are not finite with low < high (the first such dimension is named), a code object without the two kernels.
+ * dril_env_module_info_of keeps reporting the env's own action bounds; dril_agent_spaces reports what the agent sees. */
+int32_t dril_scaling_enable(dril_handle* h, int32_t on);
+/* the spaces the agent of a plug-in handle sees: obs_low / obs_high (obs_dim floats) and action_low / action_high (action_dim floats; untouched for a Discrete
+ * plug-in), any of them NULL; *scaling = 1 and Box(-1, 1) throughout under ScalingWrapperEnv, else the declared observation space and the env's own action bounds */
+int32_t dril_agent_spaces(const dril_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling);
 int32_t dril_destroy(dril_handle* h);
 /* message of the last failing call on h (or of the last failing create when h == NULL) */
 const char* dril_last_error(const dril_handle* h);

@@ -100,6 +100,16 @@ int32_t dril_sac_create(const dril_sac_config* cfg, dril_sac_handle** out);
 int32_t dril_sac_create_with_env_module(const dril_sac_config* cfg, const char* code_object_path, dril_sac_handle** out);
 /* spaces and bounds of the plug-in behind a live handle (DRIL_ERR_UNSUPPORTED for a handle of dril_sac_create) */
 int32_t dril_sac_env_module_info_of(const dril_sac_handle* h, dril_env_module_info* out);
+/* the declared observation space of the plug-in behind a live handle: dril_env_module_obs_space_of (dril_hip.h) for a SAC handle */
+int32_t dril_sac_env_module_obs_space_of(const dril_sac_handle* h, float* low, float* high, int32_t* declared);
+/* ScalingWrapperEnv around every env of a plug-in handle: dril_scaling_enable (dril_hip.h) for a SAC handle — the same env side, the same rule (between create and
+ * the first dril_sac_env_reset, DRIL_ERR_INVALID_ARG afterwards), the same refusals.  While it is on the adapters see the WRAPPER's action space: the
+ * per-dimension TanhScaleAdapter table is [-1, 1] in every dimension, rand(action_space) of the start phase draws in [-1, 1], and the replay ring holds scaled
+ * observations.  Collection (dril_sac_collect_rollout / _continue), dril_sac_train, dril_sac_iterate, dril_sac_evaluate_agent, the monitor (raw rewards) and
+ * dril_sac_normalize_* (outside the wrapper: statistics of scaled observations) honour it with no code of their own. */
+int32_t dril_sac_scaling_enable(dril_sac_handle* h, int32_t on);
+/* dril_agent_spaces (dril_hip.h) for a SAC handle */
+int32_t dril_sac_agent_spaces(const dril_sac_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling);
 int32_t dril_sac_destroy(dril_sac_handle* h);
 const char* dril_sac_last_error(const dril_sac_handle* h);
 
