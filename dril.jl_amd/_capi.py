@@ -76,6 +76,12 @@ class DrilEnvModuleInfo(C.Structure):
                 ("episode_len", C.c_int32), ("action_low", C.c_float * 64), ("action_high", C.c_float * 64), ("name", C.c_char * 64)]
 
 
+class DrilFusedRolloutInfo(C.Structure):
+    """struct dril_fused_rollout_info, include/dril_hip.h"""
+    _fields_ = [("available", C.c_int32), ("enabled", C.c_int32), ("tile", C.c_int32), ("threads", C.c_int32), ("max_width", C.c_int32), ("reserved", C.c_int32),
+                ("last_collection_launches", C.c_int64), ("reason", C.c_char * 256)]
+
+
 class DrilSacConfig(C.Structure):
     """struct dril_sac_config, include/dril_sac.h"""
     _fields_ = [
@@ -162,6 +168,8 @@ _SIG = {
     "dril_env_module_obs_space_of": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32)]),
     "dril_scaling_enable": (C.c_int32, [_P, C.c_int32]),
     "dril_agent_spaces": (C.c_int32, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "dril_rollout_fused_enable": (C.c_int32, [_P, C.c_int32]),
+    "dril_rollout_fused_info": (C.c_int32, [_P, _P]),
     "dril_destroy": (C.c_int32, [_P]),
     "dril_last_error": (C.c_char_p, [_P]),
     "dril_synchronize": (C.c_int32, [_P]),

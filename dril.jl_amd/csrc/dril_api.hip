@@ -119,6 +119,7 @@ struct dril_handle {
     float lr = 0;
     unsigned long long* dbg = nullptr;
     bool force_allreduce = false, force_stepwise = false;
+    bool fused_rollout = false; int64_t rollout_launches = 0;   // dril_rollout_fused_enable; launch calls of the last plug-in collection (dril_rollout_fused_info)
     double *epoch_tables = nullptr, *epoch_stats = nullptr; int epoch_blocks = 2048, epoch_nb_cap = 0;   // per-epoch advantage moments
     float *w2a_actor = nullptr, *w2ta_actor = nullptr, *w2a_critic = nullptr, *w2ta_critic = nullptr; bool wide = false, wimg_dirty = true;   // wide nets (H > 64)
     void *w2pf_actor = nullptr, *w2pf_critic = nullptr;   // wide nets: the forward stream in the k-order of a register B operand (net_forward_wide_split)
@@ -282,6 +283,7 @@ hipError_t run_policy(dril_handle* h, const PolicyArgs& a) {
         b.obs_out = nullptr; b.boot_obs = nullptr; b.boot_where = nullptr; b.boot_out = nullptr; b.gstep = nullptr;
         hipError_t e = generic_policy(h->gd, b, h->gws, h->stream); if (e != hipSuccess) return e;
         e = generic_select(a.B, a.boot_where, h->gen_tmp, a.boot_out, h->stream); if (e != hipSuccess) return e;
+        h->gws.launches += 1;
     }
     PolicyArgs q = a; q.boot_obs = nullptr; q.boot_where = nullptr; q.boot_out = nullptr;
     return generic_policy(h->gd, q, h->gws, h->stream);
@@ -593,6 +595,7 @@ DRIL_EXPORT int32_t dril_config_default(dril_config* c, int32_t env_kind) {
 
 namespace {
 int create_impl(const dril_config* cfg, const char* module_path, dril_handle** out);
+std::string fused_rollout_unavailable(const dril_handle* h);
 }  // namespace
 
 DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
@@ -639,6 +642,26 @@ DRIL_EXPORT int32_t dril_scaling_enable(dril_handle* h, int32_t on) {
     NEED(h);
     std::string msg; const int rc = h->env.set_scaling(on != 0, msg);
     return rc ? fail(h, rc, "dril_scaling_enable: " + msg) : DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_rollout_fused_enable(dril_handle* h, int32_t on) {
+    NEED(h);
+    if (on) {
+        std::string why = fused_rollout_unavailable(h);
+        if (why.empty() && h->pn.on) why = "NormalizeWrapperEnv is on (dril_normalize_enable): its running statistics couple all envs at every step, which is what a workgroup per tile of envs gives up; collect step-granular, or switch the wrapper off with dril_normalize_enable(h, NULL) first";
+        if (!why.empty()) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_rollout_fused_enable: " + why);
+    }
+    h->fused_rollout = on != 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rollout_info* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_rollout_fused_info: null out pointer");
+    std::memset(out, 0, sizeof(*out));
+    const std::string why = fused_rollout_unavailable(h);
+    out->available = why.empty() ? 1 : 0; out->enabled = h->fused_rollout ? 1 : 0; out->last_collection_launches = h->rollout_launches;
+    if (h->env.module && h->env.rollout.has_desc) { out->tile = h->env.rollout.desc.tile; out->threads = h->env.rollout.desc.threads; out->max_width = h->env.rollout.desc.max_width; }
+    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
+    return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_agent_spaces(const dril_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling) {
     if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
@@ -953,6 +976,7 @@ DRIL_EXPORT int32_t dril_normalize_enable(dril_handle* h, const dril_normalize_c
         pn_free(h);
         return DRIL_OK;
     }
+    if (h->fused_rollout) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_normalize_enable: the fused rollout is on, and a workgroup per tile of envs cannot keep statistics that couple all envs at every step: switch it off with dril_rollout_fused_enable(h, 0) first");
     if (const NormErr err = norm_config_check(*cfg, h->D)) return fail(h, err.code, "dril_normalize_enable: " + err.msg);
     const dril_normalize_config c = norm_config_canonical(*cfg);
     if (h->pn.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart): its statistics and returns stay
@@ -1167,6 +1191,7 @@ int collect_rollout_stepwise(dril_handle* h) {
 int collect_rollout_module(dril_handle* h) {
     const int E = h->cfg.n_envs, T = h->cfg.n_steps, D = h->D, A = h->A;
     const size_t ab = act_bytes_per(h);
+    h->rollout_launches += 1 + T;                                                                 // the opening observe and T step kernels; run_policy counts its own
     HIPCHK(h, h->env.observe(h->e_obs, h->stream));                                               // new_obs = observe(env), trajectory.jl:32
     for (int t = 0; t < T; ++t) {
         const size_t k = (size_t)t * E;
@@ -1186,11 +1211,41 @@ int collect_rollout_module(dril_handle* h) {
 // the same loop under dril_normalize_enable: the plug-in's step kernel writes raw reward, terminal observation and raw next observation into the per-step arrays, then
 // norm_moments_kernel (dril_norm_wrap.h) + ppo_norm_apply_kernel (dril_ppo_norm.h) put the normalised reward into row t and the normalised next observation where the policy reads it:
 // two launches more per env step than collect_rollout_module, and two for the opening observe.  V(terminal_observation) is V of the normalised terminal observation
+// the fused collection (dril_rollout_fused_enable): ONE launch of the plug-in's own rollout kernel (include/device/dril_env_rollout.h) does what the loop of
+// collect_rollout_module does in 6+ launches per env step, and leaves env state, counters, monitor sums and the per-step arrays as that loop leaves them
+int collect_rollout_module_fused(dril_handle* h) {
+    DrilEnvRolloutArgs g{};
+    g.env = h->env.args();
+    g.env.terminated = h->e_term; g.env.truncated = h->e_trunc; g.env.terminal_obs = h->e_tobs; g.env.obs = h->e_obs;
+    g.env.mon_cur_ret = h->mon_cur_ret; g.env.mon_cur_len = h->mon_cur_len;
+    g.T = h->cfg.n_steps; g.n_hidden = h->gd.nh; g.activation = h->gd.act; g.n_params = h->P;
+    for (int l = 0; l < h->gd.nh; ++l) g.hidden[l] = h->gd.H[l];
+    g.actor_off = h->actor.w1; g.critic_off = h->critic.w1; g.log_std_off = h->log_std_off;
+    g.params = h->params; g.noise = h->noise_set ? h->noise_dev : nullptr;
+    g.obs = h->obs; g.act = h->act; g.rew = h->rew; g.logp = h->logp; g.val = h->val; g.boot = h->boot; g.flags = h->flags; g.last_values = h->last_values;
+    if (h->mon_cur_ret) { g.ep_ret = h->ep_ret; g.ep_len = h->ep_len; }
+    h->rollout_launches += 1;
+    HIPCHK(h, h->env.launch_rollout(g, h->stream));
+    return monitor_collect_rollout(h);
+}
+// "" when the handle's net fits the plug-in's fused rollout kernel, else why not
+std::string fused_rollout_unavailable(const dril_handle* h) {
+    if (!h->env.module) return "the fused rollout is the collection kernel of a device env plug-in (DRIL_ENV_MODULE): the built-in envs collect with the library's own rollout_kernel, host envs (DRIL_ENV_EXTERNAL) step on the host";
+    const EnvModuleRollout& r = h->env.rollout;
+    if (!r.reason.empty()) return std::string("env plug-in \"") + h->env.desc.name + "\": " + r.reason;
+    const int W = r.desc.max_width;
+    if (h->D > W) return "the observation has " + std::to_string(h->D) + " dims, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->D) + " or more";
+    for (int l = 0; l < h->gd.nh; ++l) if (h->gd.H[l] > W) return "hidden layer " + std::to_string(l + 1) + " is " + std::to_string(h->gd.H[l]) + " wide, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->gd.H[l]) + " or more";
+    if (h->env.scaling && !r.fn_scaled) return "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_rollout_scaled kernel: rebuild it with this library's include/device/dril_env_rollout.h";
+    return "";
+}
+
 int collect_rollout_module_norm(dril_handle* h) {
     const int E = h->cfg.n_envs, T = h->cfg.n_steps, D = h->D, A = h->A;
     const size_t ab = act_bytes_per(h);
     const bool upd_obs = h->pn.cfg.training && h->pn.cfg.norm_obs, upd_ret = h->pn.cfg.training && h->pn.cfg.norm_reward;
     int rc = pn_observe(h, true); if (rc) return rc;                                       // new_obs = observe(env), trajectory.jl:32
+    h->rollout_launches += 3 + (int64_t)T * (2 + ((upd_obs || upd_ret) ? 1 : 0));          // observe + its wrapper; per step: the step kernel, the apply kernel, the moments
     for (int t = 0; t < T; ++t) {
         const size_t k = (size_t)t * E;
         const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * (size_t)A)) : nullptr;
@@ -1218,7 +1273,10 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
         const auto t0s = std::chrono::steady_clock::now();
         if (fps) HIPCHK(h, hipStreamSynchronize(h->stream));
         prof_begin(h, DRIL_K_ROLLOUT);
-        int rcs = h->env.module ? (h->pn.on ? collect_rollout_module_norm(h) : collect_rollout_module(h)) : collect_rollout_stepwise(h);
+        h->rollout_launches = 0; h->gws.launches = 0;
+        if (h->fused_rollout) { const std::string why = fused_rollout_unavailable(h); if (!why.empty()) { prof_end(h); return fail(h, DRIL_ERR_UNSUPPORTED, "dril_collect_rollout with the fused rollout on: " + why); } }
+        int rcs = h->env.module ? (h->fused_rollout ? collect_rollout_module_fused(h) : h->pn.on ? collect_rollout_module_norm(h) : collect_rollout_module(h)) : collect_rollout_stepwise(h);
+        h->rollout_launches += h->gws.launches + (h->mon_cur_ret ? 1 : 0);
         prof_end(h);
         if (rcs) return rcs;
         if (fps) { HIPCHK(h, hipStreamSynchronize(h->stream)); const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0s).count(); *fps = (double)h->N / (dt > 0 ? dt : 1e-12); }

@@ -18,6 +18,7 @@
 
 #include "../../include/device/dril_philox.h"
 #include "../../include/device/dril_scaling.h"
+#include "../../include/device/dril_policy_head.h"
 namespace dril {
 
 // Diagnostic / experiment switches (ablation bits, grid caps, the older form of a kernel for an A/B) are honoured only when DRIL_DEBUG=1 is set as well: a stray variable
@@ -56,14 +57,7 @@ constexpr int kTS = 36;     // row stride of the transposed activation images (3
 //   3 + 16 i    call seed                 row (64 bit)        call counter         call_noise_*: dril_policy_forward on a host batch (no device envs), action component i
 //   4           SAC update key            update counter      sample               sac_gather_kernel / sac_gather_l1_kernel (dril_sac.hip): replay indices
 //   5 .. 8      SAC update / aux key      counter             4 sample + a / 2     sac_noise (dril_sac.hip): the update's three noise draws, sac_noise_fill_kernel
-__device__ __forceinline__ double env_noise_u01(uint64_t env_seed, uint32_t gstep) {                      // Categorical: the uniform of the inverse-CDF draw
-    uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gstep, 0, 1, 0, r);
-    return u01_f64(r[0], r[1]);
-}
-__device__ __forceinline__ float env_noise_randn(uint64_t env_seed, uint32_t gstep, int i) {              // DiagGaussian: the standard normal of action component i (two per block)
-    uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gstep, 0, 1, (uint32_t)(i / 2), r);
-    return (i & 1) ? randn_f32(r[2], r[3]) : randn_f32(r[0], r[1]);
-}
+// env_noise_u01 / env_noise_randn: include/device/dril_policy_head.h (shared with the fused rollout of a device env plug-in)
 __device__ __forceinline__ float env_noise_u01_f32(uint64_t env_seed, uint32_t gstep, int i) {            // SAC's random-action phase: a uniform from the block env_noise_randn(i) uses
     uint32_t r[4]; philox4x32_10((uint32_t)env_seed, (uint32_t)(env_seed >> 32), gstep, 0, 1, (uint32_t)(i / 2), r);
     return u01_f32((i & 1) ? r[2] : r[0]);

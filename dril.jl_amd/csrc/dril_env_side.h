@@ -13,6 +13,7 @@
 
 #include "../../include/dril_hip.h"
 #include "../../include/device/dril_env_plugin.h"   // DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with
+#include "../../include/device/dril_env_rollout.h"  // DrilEnvRolloutDesc / DrilEnvRolloutArgs: the fused rollout a plug-in may carry
 #include "dril_internal.h"
 
 namespace dril {
@@ -71,6 +72,26 @@ inline hipFunction_t env_module_optional(hipModule_t mod, const char* name) {
     if (hipModuleGetFunction(&f, mod, name) != hipSuccess) { f = nullptr; (void)hipGetLastError(); }
     return f;
 }
+// The fused rollout of a loaded, checked plug-in (DRIL_ENV_PLUGIN_ROLLOUT, include/device/dril_env_rollout.h): its two kernels and its descriptor, all optional.
+// `reason` is empty when the kernel can be launched; a code object without it, or with a descriptor of another ABI number / argument-block size, loads as before
+// and says here why the fused path is not available.  Nothing of the module is launched.
+struct EnvModuleRollout { hipFunction_t fn = nullptr, fn_scaled = nullptr; DrilEnvRolloutDesc desc{}; bool has_desc = false; std::string reason; };
+inline EnvModuleRollout find_module_rollout(hipModule_t mod) {
+    EnvModuleRollout r;
+    r.fn = env_module_optional(mod, "dril_env_plugin_rollout"); r.fn_scaled = env_module_optional(mod, "dril_env_plugin_rollout_scaled");
+    hipDeviceptr_t dptr = nullptr; size_t bytes = 0;
+    if (hipModuleGetGlobal(&dptr, &bytes, mod, "dril_env_plugin_rollout_desc") != hipSuccess) { (void)hipGetLastError(); dptr = nullptr; }
+    if (!r.fn || !dptr) { r.fn = r.fn_scaled = nullptr; r.reason = "the code object has no fused rollout kernel (dril_env_plugin_rollout): add #include \"device/dril_env_rollout.h\" and DRIL_ENV_PLUGIN_ROLLOUT(Env) to the plug-in's source and rebuild"; return r; }
+    if (bytes != sizeof(DrilEnvRolloutDesc) || hipMemcpy(&r.desc, dptr, sizeof(r.desc), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError(); r.fn = r.fn_scaled = nullptr;
+        r.reason = "dril_env_plugin_rollout_desc is " + std::to_string(bytes) + " bytes, this library reads " + std::to_string(sizeof(DrilEnvRolloutDesc)) + ": rebuild the plug-in against this library's include/device/dril_env_rollout.h"; return r; }
+    r.has_desc = true;
+    if (r.desc.abi_version != DRIL_ENV_ROLLOUT_ABI) r.reason = "fused rollout ABI " + std::to_string(r.desc.abi_version) + ", this library speaks " + std::to_string(DRIL_ENV_ROLLOUT_ABI) + ": rebuild the plug-in against this library's include/device/dril_env_rollout.h";
+    else if (r.desc.args_size != sizeof(DrilEnvRolloutArgs)) r.reason = "the fused rollout's argument block is " + std::to_string(r.desc.args_size) + " bytes, this library passes " + std::to_string(sizeof(DrilEnvRolloutArgs)) + ": rebuild the plug-in against this library's include/device/dril_env_rollout.h";
+    else if (r.desc.tile < 1 || r.desc.threads < r.desc.tile || r.desc.threads > 1024 || r.desc.max_width < 1) r.reason = "the fused rollout's descriptor is out of range (tile " + std::to_string(r.desc.tile) + ", threads " + std::to_string(r.desc.threads) + ", max width " + std::to_string(r.desc.max_width) + ")";
+    if (!r.reason.empty()) r.fn = r.fn_scaled = nullptr;
+    return r;
+}
 // The declared observation space of a loaded, checked plug-in: dril_env_plugin_obs_space (one workgroup) writes low[D] | high[D] into a buffer sized from the
 // descriptor.  *declared = 0 and no launch when the code object has no such kernel (built before the observation space existed, or the env declares none).
 inline int read_module_obs_space(hipModule_t mod, const DrilEnvPluginDesc& d, std::vector<float>& low, std::vector<float>& high, bool* declared, std::string& msg) {
@@ -115,6 +136,7 @@ struct DeviceEnvs {
     // (scalingWrapperEnv.jl) around every env: `scaling` on = the plug-in's _scaled kernels stand where observe / step stood, agent-facing spaces Box(-1, 1)
     std::vector<float> obs_low, obs_high; bool obs_declared = false, scaling = false;
     hipFunction_t mod_observe_scaled = nullptr, mod_step_scaled = nullptr;
+    EnvModuleRollout rollout;   // the plug-in's fused rollout, when its code object carries one (PPO handles: dril_rollout_fused_enable)
 
     // what the envs are; for DRIL_ENV_MODULE also the plug-in: loaded, its descriptor kept, episode_len 0 replaced by the descriptor's, its three kernels found.
     // Makes `device` current when it loads; on failure nothing is held and msg says why.
@@ -129,6 +151,7 @@ struct DeviceEnvs {
             if (e != hipSuccess) { msg = std::string("hipModuleGetFunction(") + names[i] + "): " + hipGetErrorString(e); release(); return DRIL_ERR_HIP; }
         }
         mod_observe_scaled = env_module_optional(module, "dril_env_plugin_observe_scaled"); mod_step_scaled = env_module_optional(module, "dril_env_plugin_step_scaled");
+        rollout = find_module_rollout(module);
         const int rs = read_module_obs_space(module, desc, obs_low, obs_high, &obs_declared, msg);
         if (rs) release();
         return rs;
@@ -190,6 +213,13 @@ struct DeviceEnvs {
     hipError_t observe(float* obs, hipStream_t s) const {
         if (module) { DrilEnvPluginArgs a = args(); a.obs = obs; return env_module_launch(scaling ? mod_observe_scaled : mod_observe, a, s); }
         return launch_env_observe(kind, E, state, obs, s);
+    }
+    // the fused collection: ceil(E / tile) workgroups, each takes its envs through all g.T steps.  g.env: args() plus the per-step arrays and the monitor's sums
+    hipError_t launch_rollout(DrilEnvRolloutArgs g, hipStream_t s) const {
+        const hipFunction_t f = scaling ? rollout.fn_scaled : rollout.fn;
+        if (!f) return hipErrorInvalidDeviceFunction;
+        void* params[] = {&g};
+        return hipModuleLaunchKernel(f, (unsigned)((E + rollout.desc.tile - 1) / rollout.desc.tile), 1, 1, (unsigned)rollout.desc.threads, 1, 1, 0, s, params, nullptr);
     }
     hipError_t step(const void* actions, const EnvStepOut& o, const MonitorArgs& mon, hipStream_t s) const {
         if (module) {

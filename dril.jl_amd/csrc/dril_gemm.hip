@@ -10,7 +10,7 @@
 
 #include "dril_device.h"
 #include "dril_gemm.h"
-#include "dril_activations.h"
+#include "../../include/device/dril_activations.h"
 
 namespace dril {
 

@@ -20,7 +20,6 @@ namespace {
 GemmArgs gargs() { GemmArgs g = gemm_args(); g.allow_split = 1; return g; }
 
 constexpr int kMaxOut = 64;
-constexpr float kLog2PiG = 1.8378770664093453f;
 
 hipError_t ws_reserve(GenericWs& ws, size_t floats) {
     if (floats <= ws.cap) return hipSuccess;
@@ -87,26 +86,8 @@ hipError_t mlp_forward_both(const GenericDims& d, const float* P, const NetLay& 
     return launch_gemm(c, 1, s);
 }
 
-// ---- per-sample distribution math (runtime action width) ------------------------------------------------------------------------
-// Lux.softmax statistics of one logit row: max and sum(exp(z - max)); p_i = exp(z_i - m) / s (layer_forward.jl:141-149)
-__device__ inline void softmax_stats(const float* z, int A, float& m, float& s) {
-    m = z[0]; for (int i = 1; i < A; ++i) m = fmaxf(m, z[i]);
-    s = 0.f; for (int i = 0; i < A; ++i) s += expf(z[i] - m);
-}
-__device__ inline float categorical_entropy_rt(const float* z, int A, float m, float s) {        // -sum(p log p), categorical.jl:38-40
-    float e = 0.f; for (int i = 0; i < A; ++i) { const float p = expf(z[i] - m) / s; e += p * logf(p); }
-    return -e;
-}
-__device__ inline float gauss_logpdf_rt(const float* x, const float* mu, const float* ls, int A) {   // diagGaussian.jl:25-36
-    float lss = 0.f, dss = 0.f;
-    for (int i = 0; i < A; ++i) { lss += ls[i]; const float d = x[i] - mu[i]; dss += d * d * expf(-2.0f * ls[i]); }
-    return -0.5f * (2.0f * lss + dss + (float)A * kLog2PiG);
-}
-__device__ inline float gauss_entropy_rt(const float* ls, int A) {                                 // diagGaussian.jl:38-43
-    float lss = 0.f; for (int i = 0; i < A; ++i) lss += ls[i];
-    return 0.5f * (float)A * (1.0f + kLog2PiG) + lss;
-}
-
+// ---- per-sample distribution math (runtime action width): softmax_stats, categorical_draw / _logp / _entropy_rt, gauss_draw / _logpdf_rt / _entropy_rt of
+// include/device/dril_policy_head.h (dril_device.h includes it) ----
 struct PolicyHeadArgs {
     PolicyArgs a; int A, discrete; int64_t r0, n;   // rows [r0, r0 + n) of the call's batch; out is chunk-local
     const float* out;
@@ -130,13 +111,12 @@ __global__ void generic_policy_head_kernel(PolicyHeadArgs g) {
                 if (a.noise) u = ((const double*)a.noise)[b];
                 else if (a.gstep) u = env_noise_u01(a.env_seed0 + (uint64_t)b, a.gstep[b]);   // device envs: the env-keyed stream of rollout_kernel
                 else u = call_noise_u01(a.seed, b, a.call_counter);
-                float cs = 0.f; act = A - 1;                                          // findfirst(cumsum(p) .>= u), categorical.jl:47-52
-                for (int k = 0; k < A; ++k) { cs += expf(z[k] - m) / s; if ((double)cs >= u) { act = k; break; } }
+                act = categorical_draw(z, A, m, s, u);                                 // findfirst(cumsum(p) .>= u), categorical.jl:47-52
             }
             ((int32_t*)a.actions)[b] = act + a.action_start;
         } else act = ((const int32_t*)a.actions)[b] - a.action_start;
         act = act < 0 ? 0 : (act >= A ? A - 1 : act);
-        a.logp[b] = logf(expf(z[act] - m) / s);
+        a.logp[b] = categorical_logp(z, act, m, s);
         if (a.mode == 1 && a.entropy) a.entropy[b] = categorical_entropy_rt(z, A, m, s);
     } else {
         const float* ls = a.params + a.log_std_off;
@@ -147,7 +127,7 @@ __global__ void generic_policy_head_kernel(PolicyHeadArgs g) {
                 if (a.noise) n01 = ((const float*)a.noise)[b * A + k];
                 else if (a.gstep) n01 = env_noise_randn(a.env_seed0 + (uint64_t)b, a.gstep[b], k);
                 else n01 = call_noise_randn(a.seed, b, k, a.call_counter);
-                x[k] = a.deterministic ? z[k] : z[k] + expf(ls[k]) * n01;                // diagGaussian.jl:13-17, mode(d) = mean :45-47
+                x[k] = a.deterministic ? z[k] : gauss_draw(z[k], ls[k], n01);                // diagGaussian.jl:13-17, mode(d) = mean :45-47
             }
         }
         a.logp[b] = gauss_logpdf_rt(x, z, ls, A);
@@ -350,11 +330,12 @@ hipError_t generic_policy(const GenericDims& d, const PolicyArgs& a, GenericWs& 
     for (int64_t r0 = 0; r0 < a.B; r0 += R) {
         const int64_t n = std::min<int64_t>(R, a.B - r0);
         const float* X = a.obs + r0 * d.D;
-        if (a.obs_out) { const int64_t cnt = n * d.D; generic_copy_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, s>>>(X, a.obs_out + r0 * d.D, cnt); }
-        if (a.values && a.mode != 2) { e = mlp_forward_both(d, a.params, La, Lc, X, (int)n, hb, out, a.values + r0, s); if (e != hipSuccess) return e; }
-        else if (a.values) { e = mlp_forward(d, a.params, Lc, X, (int)n, hb, a.values + r0, s); if (e != hipSuccess) return e; }
+        if (a.obs_out) { const int64_t cnt = n * d.D; generic_copy_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, s>>>(X, a.obs_out + r0 * d.D, cnt); ws.launches += 1; }
+        if (a.values && a.mode != 2) { e = mlp_forward_both(d, a.params, La, Lc, X, (int)n, hb, out, a.values + r0, s); if (e != hipSuccess) return e; ws.launches += d.nh + (n <= 8192 ? 1 : 2); }
+        else if (a.values) { e = mlp_forward(d, a.params, Lc, X, (int)n, hb, a.values + r0, s); if (e != hipSuccess) return e; ws.launches += d.nh + 1; }
         if (a.mode == 2) continue;
-        if (!a.values) { e = mlp_forward(d, a.params, La, X, (int)n, hb, out, s); if (e != hipSuccess) return e; }
+        if (!a.values) { e = mlp_forward(d, a.params, La, X, (int)n, hb, out, s); if (e != hipSuccess) return e; ws.launches += d.nh + 1; }
+        ws.launches += 1;
         PolicyHeadArgs hg{a, d.A, d.discrete, r0, n, out};
         generic_policy_head_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(hg);
         e = hipGetLastError(); if (e != hipSuccess) return e;

@@ -183,7 +183,7 @@ constexpr int kMaxHidden = 4;
 // dim(l) -> dim(l + 1) with dim(0) = D, dim(l) = H[l-1], dim(nh + 1) = out
 struct GenericDims { int D, A, nh, H[kMaxHidden], discrete, act; };
 int generic_net_size(const GenericDims& d, int out);   // parameters of one net {W_1 b_1 ... W_{nh+1} b_{nh+1}}
-struct GenericWs { float* p = nullptr; size_t cap = 0; };          // grow-only device workspace (floats), owned by the handle
+struct GenericWs { float* p = nullptr; size_t cap = 0; int64_t launches = 0; };   // grow-only device workspace (floats), owned by the handle; launches: launch calls generic_policy has enqueued (dril_rollout_fused_info)
 hipError_t generic_policy(const GenericDims& d, const PolicyArgs& a, GenericWs& ws, hipStream_t s);
 hipError_t generic_ppo_grad(const GenericDims& d, const GradArgs& a, GenericWs& ws, hipStream_t s);
 int generic_slab_size(const GenericDims& d, bool actor);

@@ -18,7 +18,7 @@
 
 #include "../../include/dril_policy.h"
 #include "../../include/device/dril_philox.h"
-#include "dril_activations.h"
+#include "../../include/device/dril_activations.h"
 #include "dril_gemm.h"
 #include "dril_policy_internal.h"
 #include "dril_sac_adapter.h"

@@ -501,6 +501,18 @@ class Handle:
         self._chk(self.lib.dril_env_module_obs_space_of(self._h, self._p(lo), self._p(hi), C.byref(decl)))
         return dict(low=lo, high=hi, declared=bool(decl.value))
 
+    def rollout_fused_enable(self, on: bool = True):
+        """dril_rollout_fused_enable: collections of a plug-in handle in ONE launch of the plug-in's own rollout kernel (a code object built with
+        DRIL_ENV_PLUGIN_ROLLOUT, include/device/dril_env_rollout.h); legal at any time between collections"""
+        self._chk(self.lib.dril_rollout_fused_enable(self._h, int(bool(on))))
+
+    def rollout_fused_info(self) -> dict:
+        """dril_rollout_fused_info: available / enabled / tile / threads / max_width / last_collection_launches / reason"""
+        info = capi.DrilFusedRolloutInfo()
+        self._chk(self.lib.dril_rollout_fused_info(self._h, C.byref(info)))
+        return dict(available=bool(info.available), enabled=bool(info.enabled), tile=info.tile, threads=info.threads, max_width=info.max_width,
+                    last_collection_launches=info.last_collection_launches, reason=info.reason.decode())
+
     def scaling_enable(self, on: bool = True):
         """dril_scaling_enable: ScalingWrapperEnv around every env of a plug-in handle; between create and the first env_reset"""
         self._chk(self.lib.dril_scaling_enable(self._h, int(bool(on))))
@@ -924,11 +936,14 @@ class DeviceModuleEnv(DeviceParallelEnv):
     `scaling=True` (or ScalingWrapperEnv(DeviceModuleEnv(...))) puts ScalingWrapperEnv around every env: the plug-in's own _scaled kernels run where observe / step ran
     (dril_scaling_enable, applied to a fresh handle before its first reset), `observation_space()` / `action_space()` become Box(-1, 1), and NormalizeWrapperEnv —
     when both are asked for — sits outside it.  It needs a plug-in that declares finite obs_low / obs_high; the library's refusal says what is missing.  Part of
-    bind's key.  `scale_observation / unscale_observation / unscale_action` convert host arrays with the declared bounds."""
+    bind's key.  `scale_observation / unscale_observation / unscale_action` convert host arrays with the declared bounds.
+
+    `fused_rollout=True` makes every PPO collection ONE launch of the plug-in's own rollout kernel (dril_rollout_fused_enable) — the code object must be built with
+    DRIL_ENV_PLUGIN_ROLLOUT (include/device/dril_env_rollout.h); not together with `normalize`.  The library's refusal says what is missing.  Part of bind's key."""
 
     def __init__(self, code_object_path, n_envs: int, *, seed: int = 42, device: int = 0, max_steps: Optional[int] = None, action_start: int = 1,
                  fixed_length_episodes: bool = False, rank: int = 0, world_size: int = 1, profile_events: bool = False, normalize: Optional[dict] = None,
-                 scaling: bool = False):
+                 scaling: bool = False, fused_rollout: bool = False):
         info = describe_env_module(code_object_path, device)
         env = ModuleEnv(os.fspath(code_object_path), info, int(max_steps) if max_steps else info["episode_len"], action_start, scaling=bool(scaling))
         super().__init__(env, n_envs, seed=seed, fixed_length_episodes=fixed_length_episodes, device=device, rank=rank, world_size=world_size,
@@ -939,13 +954,16 @@ class DeviceModuleEnv(DeviceParallelEnv):
                 raise TypeError(f"NormalizeWrapperEnv has no keyword {bad[0]!r}")
             normalize = {**_normalize.DEFAULTS, **normalize}
         self.module_normalize = normalize
+        self.fused_rollout = bool(fused_rollout)
 
     def _bind_extra(self):
-        return (None if self.module_normalize is None else tuple(sorted(self.module_normalize.items())), self.env.scaling)
+        return (None if self.module_normalize is None else tuple(sorted(self.module_normalize.items())), self.env.scaling, self.fused_rollout)
 
     def _after_create(self, h: Handle):
         if self.env.scaling:                      # inside NormalizeWrapperEnv: its statistics are those of scaled observations
             h.scaling_enable(True)
+        if self.fused_rollout:
+            h.rollout_fused_enable(True)
         if self.module_normalize is not None:
             h.normalize_enable(**self.module_normalize)
 

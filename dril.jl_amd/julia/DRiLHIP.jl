@@ -129,12 +129,12 @@ function describe_env_module(path::AbstractString, device::Integer = 0)
     return (path = String(path), state_dim = Int(i32[1]), obs_dim = D, action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]), low = low, high = high, name = name,
         obs_low = obs_low, obs_high = obs_high, obs_declared = declared[] != 0, scaling = false)
 end
-"`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv, for PPO and SAC alike; `scaling = true` = ScalingWrapperEnv around every env (the plug-in's own _scaled kernels, spaces Box(-1, 1); inside NormalizeWrapperEnv)"
+"`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv, for PPO and SAC alike; `scaling = true` = ScalingWrapperEnv around every env (the plug-in's own _scaled kernels, spaces Box(-1, 1); inside NormalizeWrapperEnv); `fused_rollout = true` = PPO collections in one launch of the plug-in's own rollout kernel (a code object built with DRIL_ENV_PLUGIN_ROLLOUT; dril_rollout_fused_enable; not together with `normalize`)"
 function OnDeviceModule(path::AbstractString, n_envs::Integer; max_steps::Union{Nothing, Integer} = nothing, seed::Integer = 42, device::Integer = 0, monitor_window::Integer = 0,
-        normalize::Union{Nothing, NamedTuple} = nothing, scaling::Bool = false)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (dril_sac_normalize_enable) and by the PPO handle (dril_normalize_enable, applied in bind!)
+        normalize::Union{Nothing, NamedTuple} = nothing, scaling::Bool = false, fused_rollout::Bool = false)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (dril_sac_normalize_enable) and by the PPO handle (dril_normalize_enable, applied in bind!)
     info = describe_env_module(path, device)
     env = DeviceParallelEnv(:Module, n_envs; max_steps = something(max_steps, info.episode_len), seed = seed, device = device, monitor_window = monitor_window, normalize = normalize)
-    MODULE_ENVS[env] = merge(info, (scaling = scaling,))     # applied to every handle of this env right after create (dril_scaling_enable / dril_sac_scaling_enable), where the library refuses what it cannot scale
+    MODULE_ENVS[env] = merge(info, (scaling = scaling, fused_rollout = fused_rollout))     # applied to every handle of this env right after create (dril_scaling_enable / dril_sac_scaling_enable), where the library refuses what it cannot scale
     return env
 end
 is_discrete(env) = env.kind === :Module ? MODULE_ENVS[env].discrete : env.kind === :CartPole || env.kind === :MountainCar || env.kind === :Acrobot
@@ -215,6 +215,7 @@ function bind!(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int} = [64, 64],
         if env.kind === :Module                                  # a device env plug-in: the library loads the code object itself
             check(ccall((:dril_create_with_env_module, LIB[]), Int32, (Ref{DrilConfig}, Cstring, Ref{Ptr{Cvoid}}), cfg, MODULE_ENVS[env].path, h))
             MODULE_ENVS[env].scaling && check(ccall((:dril_scaling_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h[], Int32(1)), h[])   # ScalingWrapperEnv: before the first reset, inside NormalizeWrapperEnv
+            MODULE_ENVS[env].fused_rollout && check(ccall((:dril_rollout_fused_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h[], Int32(1)), h[])   # collections in one launch of the plug-in's rollout kernel
             env.normalize === nothing || normalize_enable!(h[], env.normalize)   # train!(agent, env, alg::PPO, ...) and evaluate_agent then run under the wrapper (evaluation: frozen, raw returns)
         else
             check(ccall((:dril_create, LIB[]), Int32, (Ref{DrilConfig}, Ref{Ptr{Cvoid}}), cfg, h))
@@ -223,6 +224,14 @@ function bind!(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int} = [64, 64],
         check(ccall((:dril_env_reset, LIB[]), Int32, (Ptr{Cvoid}, UInt64), env.handle, env.seed), env.handle)
     end
     return env.handle
+end
+"dril_rollout_fused_info of the env's handle: (available, enabled, tile, threads, max_width, last_collection_launches, reason)"
+function rollout_fused_info(env::DeviceParallelEnv)
+    buf = zeros(UInt8, 288)                                      # dril_fused_rollout_info: 6 x Int32, Int64, char[256]
+    check(ccall((:dril_rollout_fused_info, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), handle(env), buf), handle(env))
+    i32 = reinterpret(Int32, buf[1:24])
+    return (available = i32[1] != 0, enabled = i32[2] != 0, tile = Int(i32[3]), threads = Int(i32[4]), max_width = Int(i32[5]),
+        last_collection_launches = Int(reinterpret(Int64, buf[25:32])[1]), reason = String(buf[33:(32 + something(findfirst(==(0x00), buf[33:end]), 257) - 1)]))
 end
 handle(env::DeviceParallelEnv) = env.handle == C_NULL ? bind!(env, PPO(; n_steps = 1, batch_size = env.n_envs)) : env.handle
 

@@ -3,8 +3,10 @@
 observation dims, 3 action dims — nothing the built-in kinds can express) is compiled by the library's Makefile into a gfx950 code object; the library loads
 it (DRIL_ENV_MODULE) and steps it with its own kernels.  No host env anywhere in the loop.
 
-usage: python examples/ppo_device_plugin.py [n_envs=256] [iterations=30] [--normalize] [--scaling]
+usage: python examples/ppo_device_plugin.py [n_envs=256] [iterations=30] [--normalize] [--scaling] [--fused]
 --scaling: ScalingWrapperEnv around every env (dril_scaling_enable: the plug-in's own _scaled kernels; the agent sees Box(-1, 1) observations and actions)
+--fused: every collection is ONE launch of the plug-in's own rollout kernel (examples/envs/reacher3_fused_plugin.hip = the same env + DRIL_ENV_PLUGIN_ROLLOUT;
+  dril_rollout_fused_enable) instead of six or more launches per env step; not together with --normalize
 --normalize: NormalizeWrapperEnv around the plug-in envs with the reference's default keywords (dril_normalize_enable: observation and reward statistics on the device)"""
 import sys
 from pathlib import Path
@@ -13,13 +15,13 @@ sys.path.insert(0, str(ROOT))
 import __graft_entry__ as g
 
 pkg = g.load_package()
-normalize, scaling = "--normalize" in sys.argv, "--scaling" in sys.argv
-args = [a for a in sys.argv[1:] if a not in ("--normalize", "--scaling")]
+normalize, scaling, fused = "--normalize" in sys.argv, "--scaling" in sys.argv, "--fused" in sys.argv
+args = [a for a in sys.argv[1:] if a not in ("--normalize", "--scaling", "--fused")]
 n_envs = int(args[0]) if len(args) > 0 else 256
 iters = int(args[1]) if len(args) > 1 else 30
-code_object = ROOT / "examples" / "envs" / "reacher3_plugin.hsaco"        # built by `make -C dril.jl_amd/csrc` (__graft_entry__.build())
+code_object = ROOT / "examples" / "envs" / ("reacher3_fused_plugin.hsaco" if fused else "reacher3_plugin.hsaco")        # built by `make -C dril.jl_amd/csrc` (__graft_entry__.build())
 print("env:", pkg.describe_env_module(code_object))
-env = pkg.MonitorWrapperEnv(pkg.DeviceModuleEnv(code_object, n_envs, seed=0, normalize={} if normalize else None, scaling=scaling), stats_window=n_envs)
+env = pkg.MonitorWrapperEnv(pkg.DeviceModuleEnv(code_object, n_envs, seed=0, normalize={} if normalize else None, scaling=scaling, fused_rollout=fused), stats_window=n_envs)
 alg = pkg.PPO(n_steps=100, batch_size=n_envs * 100 // 4, epochs=10, learning_rate=1e-3)
 agent = pkg.Agent(pkg.ActorCriticLayer(env.observation_space(), env.action_space()), alg, seed=0)
 

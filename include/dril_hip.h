@@ -229,6 +229,29 @@ int32_t dril_scaling_enable(dril_handle* h, int32_t on);
 /* the spaces the agent of a plug-in handle sees: obs_low / obs_high (obs_dim floats) and action_low / action_high (action_dim floats; untouched for a Discrete
  * plug-in), any of them NULL; *scaling = 1 and Box(-1, 1) throughout under ScalingWrapperEnv, else the declared observation space and the env's own action bounds */
 int32_t dril_agent_spaces(const dril_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling);
+/* The FUSED ROLLOUT of a device env plug-in (include/device/dril_env_rollout.h): a code object built with DRIL_ENV_PLUGIN_ROLLOUT(Env) holds a collection kernel
+ * with the env inlined — observe, critic and actor forward, the draw, the transition and the buffer rows of all n_steps steps in ONE launch, a workgroup per tile
+ * of envs, no grid barrier.  on != 0: from now on dril_collect_rollout and dril_train launch it (dril_env_plugin_rollout_scaled while dril_scaling_enable is on)
+ * where they issued the policy launches and the plug-in's step kernel per env step; GAE, the update, the env verbs and dril_evaluate_agent are unchanged and a
+ * collection of either kind may follow the other.  Legal at any time between collections; off is the default.
+ * Numerics: the fused forward is plain f32 FMA with k ascending, the step-granular one the bf16 x 3-piece MFMA contractions — two f32-equivalent arithmetics, so
+ * values, log-probabilities and Gaussian actions of the two paths agree like device and oracle do, not to the bit; noise words, flags for equal states, counters,
+ * monitor bookkeeping and the buffer layout are identical.  An env's rows do not depend on n_envs or on the env's position (batch invariance).
+ * Speed: the fused path removes the per-step launches; whether it also wins at very large n_envs is a measurement (docs/external_envs.md section 11).
+ * DRIL_ERR_UNSUPPORTED, each with a message that says what to do and the handle left as it was, for: a handle that is not a plug-in handle; a code object without
+ * the kernel; a rollout descriptor of another ABI number or argument-block size; a hidden layer or observation wider than the plug-in's compiled
+ * DRIL_ENV_ROLLOUT_MAX_WIDTH; a handle on which dril_normalize_enable is on (running statistics couple all envs at every step).  dril_normalize_enable on a
+ * handle whose fused path is on is refused likewise. */
+typedef struct dril_fused_rollout_info {
+    int32_t available;                 /* the code object has a usable rollout kernel for this handle's net */
+    int32_t enabled;
+    int32_t tile, threads, max_width;  /* of the plug-in's compile; 0 without a rollout descriptor */
+    int32_t reserved;
+    int64_t last_collection_launches;  /* launch calls the last dril_collect_rollout enqueued for collect_trajectories on this plug-in handle (either path; 0 before) */
+    char reason[256];                  /* why it is not available ("" when it is) */
+} dril_fused_rollout_info;
+int32_t dril_rollout_fused_enable(dril_handle* h, int32_t on);
+int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rollout_info* out);
 int32_t dril_destroy(dril_handle* h);
 /* message of the last failing call on h (or of the last failing create when h == NULL) */
 const char* dril_last_error(const dril_handle* h);
