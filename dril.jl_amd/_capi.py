@@ -70,6 +70,17 @@ class DrilEvalStats(C.Structure):
                 ("n_episodes", C.c_int32), ("n_steps", C.c_int32)]
 
 
+class DrilEvalOptions(C.Structure):
+    """struct dril_eval_options, include/dril_hip.h"""
+    _fields_ = [("n_eval_episodes", C.c_int32), ("deterministic", C.c_int32), ("seed", C.c_uint64), ("has_seed", C.c_int32), ("poll_steps", C.c_int32),
+                ("force_step_granular", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class DrilEvalInfo(C.Structure):
+    """struct dril_eval_info, include/dril_hip.h"""
+    _fields_ = [("path", C.c_int32), ("launches", C.c_int32), ("steps_enqueued", C.c_int32), ("events", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class DrilEnvModuleInfo(C.Structure):
     """struct dril_env_module_info, include/dril_hip.h"""
     _fields_ = [("plugin_abi", C.c_uint32), ("state_dim", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("discrete", C.c_int32),
@@ -221,6 +232,8 @@ _SIG = {
     "dril_ppo_loss_grad": (C.c_int32, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_float), _P, _P]),
     "dril_apply_gradients": (C.c_int32, [_P, _P, C.c_size_t, C.POINTER(C.c_float)]),
     "dril_evaluate_agent": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(DrilEvalStats), _P, _P]),
+    "dril_eval_options_default": (C.c_int32, [C.POINTER(DrilEvalOptions)]),
+    "dril_evaluate_agent_device": (C.c_int32, [_P, C.POINTER(DrilEvalOptions), C.POINTER(DrilEvalStats), _P, _P, C.POINTER(DrilEvalInfo)]),
     "dril_train": (C.c_int32, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     "dril_comm_unique_id": (C.c_int32, [_P]),
     "dril_comm_init": (C.c_int32, [_P, _P]),

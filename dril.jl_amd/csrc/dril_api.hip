@@ -155,6 +155,9 @@ struct dril_handle {
     bool no_persistent = false; unsigned long long* small_xchg = nullptr; uint64_t* epoch_keys = nullptr; int epoch_keys_cap = 0; int64_t small_chunk = 16384;   // ppo_update_small_kernel (batch_size <= 64): DRIL_NO_PERSISTENT_UPDATE; per-epoch DataLoader keys on the device
     std::vector<ProfEvent> prof_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
     double prof_ms[DRIL_K_COUNT] = {0}; int64_t prof_n[DRIL_K_COUNT] = {0}, prof_all[DRIL_K_COUNT] = {0}; bool prof_open = false;
+    // dril_evaluate_agent_device: where the env side is set aside for the call, the per-env running sums, the event list and its counter (pinned host word for the poll)
+    char* eval_snap = nullptr; size_t eval_snap_bytes = 0; float* eval_cur_ret = nullptr; int32_t* eval_cur_len = nullptr;
+    unsigned int *eval_counter = nullptr, *eval_counter_host = nullptr; SacEvalEvent* eval_events = nullptr; long long eval_events_cap = 0;
     std::string err;
 };
 
@@ -813,7 +816,8 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     generic_ws_free(h->gws); pn_free(h);
     h->env.release();
     if (h->ext_stage_rew) (void)hipHostFree(h->ext_stage_rew); if (h->ext_stage_flags) (void)hipHostFree(h->ext_stage_flags);
-    void* ptrs[] = {h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
+    if (h->eval_counter_host) (void)hipHostFree(h->eval_counter_host);
+    void* ptrs[] = {h->eval_snap, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
                     h->flags, h->last_values, h->noise_dev, h->perm_dev, h->epoch_index, h->epoch_keys, h->small_xchg, h->w2max_dev, h->gae_carry, h->gae_err, h->w2pf_actor, h->w2pf_critic, h->adv_partials, h->adv_stats, h->ev_partials, h->step_stats,
                     h->stop_flag, h->nan_flag, h->e_obs, h->e_rew, h->e_tobs, h->e_term, h->e_trunc, h->e_act, h->e_obs_raw, h->e_rew_n, h->obs_rms, h->ret_rms, h->rms_partials, h->rms_red, h->gen_tmp, h->dbg, h->rec, h->epoch_tables, h->epoch_stats, h->w2a_actor, h->w2ta_actor, h->w2a_critic, h->w2ta_critic, h->w2p_actor, h->w2tp_actor, h->w2p_critic, h->w2tp_critic, h->mon_cur_ret, h->ep_ret, h->mon_ring_ret, h->e_ep_ret, h->mon_cur_len, h->ep_len,
                     h->mon_ring_len, h->e_ep_len, h->mon_cnt, h->mon_meta, h->e_flags};
@@ -1817,6 +1821,157 @@ int evaluate_agent_loop(dril_handle* h, int32_t n_eval, int32_t deterministic, d
     return DRIL_OK;
 }
 }  // namespace
+
+// ---- evaluate_agent on the device, training state left untouched (docs/evaluation.md) --------------------------------------------------------
+// The loop of evaluate_agent_loop above with the host taken out of it: the episode accounting of dril_eval_account.h runs on the device, the host looks at ONE 4-byte
+// counter every K env steps, and what the loop writes of the env side is set aside before and put back after.  Two forms of the K steps between two looks:
+//   path 1  ONE launch of evaluate_kernel (dril_kernels.hip): built-in kinds on the fused shapes of width 64 / 128 / 256 with no normaliser
+//   path 0  per env step the launches run_policy / step_dev / observe_dev make, and eval_account_kernel over the step's reward and done arrays: everything else
+namespace {
+__global__ __launch_bounds__(256) void eval_account_kernel(EvalAcct a, int32_t step, const float* __restrict__ rew, const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.E) return;
+    eval_account_env(a, step, e, rew[e], (term[e] | trunc[e]) != 0);
+}
+// the default K of each path: UNMEASURED starting points (docs/evaluation.md, "Measured") — the SAC verb's min(time limit, 32) for the step-granular path, a guess for the
+// persistent one.  No more than the time limit, after which every env has finished an episode
+constexpr int kEvalPollStepwise = 32, kEvalPollPersistent = 64;
+constexpr long long kEvalMaxLaunchEvents = 1ll << 22;   // E K of one evaluate_kernel launch: 64 MB of event slots at the most
+bool eval_persistent_applies(const dril_handle* h) {
+    const int hd = h->cfg.hidden1;
+    return !h->generic && !h->env.module && !normalizing(h) && !h->force_stepwise && (hd == 64 || hd == 128 || hd == 256);   // (DRIL_FORCE_STEPWISE: the step-granular launches, as for the collection)
+}
+template <typename T> int eval_ensure(dril_handle* h, T** p, size_t n) { if (!*p) HIPCHK(h, dmalloc(p, n)); return DRIL_OK; }
+// what one evaluation sets aside: device arrays in a list (copied to / from one blob), the host-side words next to them
+struct EvalKeep {
+    std::vector<std::pair<void*, size_t>> arrays;
+    uint64_t seed0; bool ready; int obs_par, ret_par, norm_training, pn_training; float* mon_cur_ret; int64_t gws_launches;
+};
+void eval_keep_list(dril_handle* h, bool persistent, EvalKeep& k) {
+    const size_t E = (size_t)h->cfg.n_envs, ED = E * h->D * 4;
+    k.arrays = {{h->env.state, E * h->S * 4}, {h->env.step_count, E * 4}, {h->env.episode, E * 4}, {h->env.gstep, E * 4}, {h->env.disc_returns, E * 4}};
+    if (persistent) return;                                                        // evaluate_kernel writes the envs alone (reset! zeroes `returns`)
+    const std::pair<void*, size_t> step_arrays[] = {{h->e_obs, ED}, {h->e_rew, E * 4}, {h->e_tobs, ED}, {h->e_term, E}, {h->e_trunc, E}, {h->e_act, E * act_bytes_per(h)}};
+    k.arrays.insert(k.arrays.end(), std::begin(step_arrays), std::end(step_arrays));
+    if (normalizing(h) || h->pn.on) { k.arrays.push_back({h->e_obs_raw, ED}); k.arrays.push_back({h->e_rew_n, E * 4}); }
+    if (normalizing(h)) { k.arrays.push_back({h->obs_rms, 2 * sizeof(RmsState)}); k.arrays.push_back({h->ret_rms, 2 * sizeof(RmsState)}); }   // both halves: a frozen apply copies in -> out and flips the parity
+}
+int eval_keep_copy(dril_handle* h, const EvalKeep& k, bool save) {
+    size_t off = 0;
+    for (const auto& a : k.arrays) {
+        if (save) HIPCHK(h, hipMemcpyAsync(h->eval_snap + off, a.first, a.second, hipMemcpyDeviceToDevice, h->stream));
+        else HIPCHK(h, hipMemcpyAsync(a.first, h->eval_snap + off, a.second, hipMemcpyDeviceToDevice, h->stream));
+        off += (a.second + 15) & ~(size_t)15;
+    }
+    return DRIL_OK;
+}
+int eval_buffers(dril_handle* h, const EvalKeep& k, long long cap) {
+    const size_t E = (size_t)h->cfg.n_envs;
+    size_t bytes = 0; for (const auto& a : k.arrays) bytes += (a.second + 15) & ~(size_t)15;
+    if (bytes > h->eval_snap_bytes) { if (h->eval_snap) (void)hipFree(h->eval_snap); h->eval_snap = nullptr; h->eval_snap_bytes = 0; HIPCHK(h, dmalloc(&h->eval_snap, bytes)); h->eval_snap_bytes = bytes; }
+    { int rc = eval_ensure(h, &h->eval_cur_ret, E); if (rc) return rc; } { int rc = eval_ensure(h, &h->eval_cur_len, E); if (rc) return rc; } { int rc = eval_ensure(h, &h->eval_counter, 1); if (rc) return rc; }
+    if (!h->eval_counter_host) HIPCHK(h, hipHostMalloc((void**)&h->eval_counter_host, sizeof(unsigned int), hipHostMallocDefault));
+    if (cap > h->eval_events_cap) { if (h->eval_events) (void)hipFree(h->eval_events); h->eval_events = nullptr; h->eval_events_cap = 0; HIPCHK(h, dmalloc(&h->eval_events, (size_t)cap)); h->eval_events_cap = cap; }
+    return DRIL_OK;
+}
+// one env step of path 0, enqueued: predict_actions -> act! -> accounting -> observe.  raw: the accounting reads the raw rewards (dril_evaluate_agent's rule)
+int eval_step_granular(dril_handle* h, const EvalAcct& acct, int32_t step, int deterministic, bool raw, int32_t* launches) {
+    const int E = h->cfg.n_envs; const bool wrapped = normalizing(h) || h->pn.on; const int64_t g0 = h->gws.launches;
+    PolicyArgs p = policy_args(h, h->e_obs, E, nullptr, h->e_act, nullptr, h->e_rew /*log-probabilities are not needed: parked where act! writes next*/, nullptr, 0);
+    p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.deterministic = deterministic ? 1 : 0;
+    HIPCHK(h, run_policy(h, p));                                                   // predict_actions(agent, observations; deterministic), :92
+    const float* rew = h->e_rew;
+    if (wrapped) {                                                                 // act!(env, actions), :94: the wrapper's, its statistics frozen
+        float* delivered = (h->env.module && !h->pn.on) ? nullptr : h->e_rew_n;
+        int rc = step_dev(h, h->e_act, delivered, nullptr); if (rc) return rc;
+        if (!raw && delivered) rew = delivered;
+    } else { int rc = env_step_arrays(h, h->e_act); if (rc) return rc; }           // no wrapper: the raw step is the whole step (as dril_env_step)
+    hipLaunchKernelGGL(eval_account_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, step, rew, h->e_term, h->e_trunc);
+    HIPCHK(h, hipGetLastError());
+    if (wrapped) { int rc = observe_dev(h, true); if (rc) return rc; }             // observations = observe(env), :97
+    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
+    *launches += (h->generic ? (int32_t)(h->gws.launches - g0) : 1) + 2 + (wrapped ? (h->env.module ? 2 : 3) : 0);
+    return DRIL_OK;
+}
+// K: env steps between two looks at the counter.  The persistent kernel's launch length is also bounded by the list it may fill (eval_event_capacity, dril_eval_account.h)
+int eval_poll_steps(const dril_handle* h, const dril_eval_options* o, bool persistent) {
+    int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, persistent ? kEvalPollPersistent : kEvalPollStepwise));
+    if (persistent) K = (int)std::max<long long>(1, std::min<long long>(K, kEvalMaxLaunchEvents / std::max(1, h->cfg.n_envs)));
+    return K;
+}
+int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent, bool raw, int K, long long cap, std::vector<SacEvalEvent>& events, dril_eval_info* info) {
+    const int E = h->cfg.n_envs, n_eval = o->n_eval_episodes;
+    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
+    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :87
+    h->env.ready = true;
+    HIPCHK(h, hipMemsetAsync(h->eval_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_cur_len, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
+    const EvalAcct acct{E, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, (unsigned int)cap};
+    EvalKernelArgs g{};
+    if (persistent) {
+        RolloutArgs& a = g.r;
+        a.params = h->params; a.state = h->env.state; a.step_count = h->env.step_count; a.episode = h->env.episode; a.gstep = h->env.gstep;
+        a.E = E; a.T = K; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len; a.action_start = h->env.action_start; a.log_std_off = h->log_std_off;
+        a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic; a.exact_f32 = fwd_exact(h) ? 1 : 0;
+        a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = nullptr;
+        g.acct = acct; g.deterministic = (o->deterministic ? 1 : 0);
+    } else if (normalizing(h) || h->pn.on) { int rc = observe_dev(h, true); if (rc) return rc; }   // observations = observe(env), :88
+    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
+    // every env finishes an episode within the time limit, so n of them take at most ceil(n / E) time limits; one more, and the steps enqueued past a look
+    const long long max_steps = ((long long)(n_eval + E - 1) / E + 1) * (long long)h->env.episode_len + K;
+    long long steps = 0; unsigned int seen = 0; int32_t launches = 0;
+    while (seen < (unsigned int)n_eval) {
+        if (steps >= max_steps) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_evaluate_agent_device: no episode finishes");
+        if (persistent) { g.step0 = (int32_t)steps; HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream)); steps += K; launches += 1; }
+        else for (int k = 0; k < K; ++k) { int rc = eval_step_granular(h, acct, (int32_t)(++steps), (o->deterministic ? 1 : 0), raw, &launches); if (rc) return rc; }
+        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        seen = *h->eval_counter_host;
+    }
+    events.resize((size_t)std::min<long long>(seen, cap));
+    HIPCHK(h, hipMemcpyAsync(events.data(), h->eval_events, events.size() * sizeof(SacEvalEvent), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (info) { info->path = persistent ? 1 : 0; info->launches = launches; info->steps_enqueued = (int32_t)steps; info->events = (int32_t)seen; }
+    return DRIL_OK;
+}
+}  // namespace
+DRIL_EXPORT int32_t dril_eval_options_default(dril_eval_options* o) {
+    if (!o) return DRIL_ERR_INVALID_ARG;
+    std::memset(o, 0, sizeof(*o));
+    o->n_eval_episodes = 10; o->deterministic = 1;                                     // evaluation.jl:57-58
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths, dril_eval_info* info) {
+    NEED(h); NOT_EXTERNAL(h, "dril_evaluate_agent");
+    if (!o || !out || o->n_eval_episodes < 1 || o->poll_steps < 0) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent_device: options and out != NULL, n_eval_episodes >= 1, poll_steps >= 0");
+    if (info) std::memset(info, 0, sizeof(*info));
+    { int rc = ensure_wimg(h); if (rc) return rc; }
+    const bool persistent = !o->force_step_granular && eval_persistent_applies(h);
+    const bool raw = (h->env.module && h->pn.on) || h->mon_cur_ret != nullptr;         // dril_evaluate_agent's rule: raw returns under the monitor (and under a plug-in's normaliser)
+    EvalKeep keep; eval_keep_list(h, persistent, keep);
+    const int K = eval_poll_steps(h, o, persistent);
+    const long long cap = eval_event_capacity(o->n_eval_episodes, h->cfg.n_envs, persistent ? K : 1);   // (path 0: one launch per env step)
+    { int rc = eval_buffers(h, keep, cap); if (rc) return rc; }
+    // the evaluation runs on the handle's own envs: what training would continue from is set aside here and put back below, on every path
+    keep.seed0 = h->env.seed0; keep.ready = h->env.ready; keep.obs_par = h->obs_par; keep.ret_par = h->ret_par; keep.norm_training = h->cfg.norm_training;
+    keep.pn_training = h->pn.cfg.training; keep.mon_cur_ret = h->mon_cur_ret; keep.gws_launches = h->gws.launches;
+    { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
+    h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false): the statistics in force, frozen; `returns` stands still
+    h->mon_cur_ret = nullptr;                                                          // evaluation episodes do not enter the training env's MonitorWrapperEnv: its launches are not made
+    std::vector<SacEvalEvent> events;
+    const int rc = eval_device_run(h, o, persistent, raw, K, cap, events, info);
+    const std::string msg = h->err;
+    h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
+    h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
+    int rr = eval_keep_copy(h, keep, false);
+    if (rr == DRIL_OK) { const hipError_t e = hipStreamSynchronize(h->stream); if (e != hipSuccess) rr = fail(h, DRIL_ERR_HIP, std::string("dril_evaluate_agent_device: ") + hipGetErrorString(e)); }
+    if (rc != DRIL_OK) { h->err = msg; return rc; }
+    if (rr != DRIL_OK) return rr;
+    SacEvalSummary sum{};
+    sac_eval_reduce(events.data(), (int64_t)events.size(), o->n_eval_episodes, &sum, ep_rewards, ep_lengths);
+    out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
+    out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
+    return DRIL_OK;
+}
 
 // ---- train! ------------------------------------------------------------------------------------------
 DRIL_EXPORT int32_t dril_train(dril_handle* h, int64_t max_steps, dril_ppo_stats* stats, double* fps, int32_t* iterations_done) {

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "dril_device.h"
+#include "dril_eval_account.h"   // EvalAcct, eval_account: the episode accounting of an evaluation on the device
 #include "dril_env_kinds.h"   // the built-in env kinds: every launcher below that takes `kind` dispatches through with_env_kind
 
 // The forward of rollout_kernel / rollout_duo_kernel / policy_kernel puts ONE operand on f16 pieces: kTanhScale kWScale W2 (h1 = tanh is bounded, L1 and L3 are f32).
@@ -54,6 +55,12 @@ struct RolloutArgs {
     float* mon_cur_ret; int32_t* mon_cur_len; float* ep_ret; int32_t* ep_len;   // MonitorWrapperEnv (null = off)
     NetOff actor, critic;
 };
+
+// evaluate_kernel (dril_kernels.hip): r as the rollout's launcher fills it, of which the kernel reads the envs, the ACTOR (params, actor, w2a_actor, exact_f32,
+// log_std_off), the seeds and limits, and T = the env steps of this launch; noise, the buffer pointers, the critic and the monitor are unused (null).
+// step0: env steps of this evaluation already run by earlier launches
+struct EvalKernelArgs { RolloutArgs r; EvalAcct acct; int32_t step0; int deterministic; };
+hipError_t launch_evaluate(int kind, int hidden, const EvalKernelArgs& a, hipStream_t s);
 
 struct MomentsArgs {
     const float* adv; const int64_t* perm; int64_t pos0, count, N, idx_lo, n_local; uint64_t perm_key; int perm_bits;

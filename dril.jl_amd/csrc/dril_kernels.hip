@@ -540,6 +540,13 @@ __global__ void build_wimg_kernel(const float* __restrict__ P, NetOff off, int H
 // policy_kernel: host-batch / step-granular forward.  One wave = 32 samples.
 // mode 0: sample + logprob + value; 1: evaluate given actions (+entropy); 2: critic only
 // =============================================================================================
+// mode(d) of a Categorical = argmax(p), the first maximum (categorical.jl:42-44): the ONE definition of policy_kernel's deterministic path and evaluate_kernel's
+template <int A> __device__ __forceinline__ int categorical_mode(const float (&p)[A]) {
+    int act = 0; float best = p[0];
+#pragma unroll
+    for (int i = 1; i < A; ++i) if (p[i] > best) { best = p[i]; act = i; }
+    return act;
+}
 template <int KIND, int H, bool WIDE, bool SPLIT>
 __global__ __launch_bounds__(256, WIDE ? 1 : 2) void policy_kernel(PolicyArgs a) {
     constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
@@ -593,11 +600,8 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void policy_kernel(PolicyArgs a)
                 act = sample_categorical<A>(out, u, &logp);
             } else {
                 float p[A]; softmax_n<A>(out, p);
-                if (a.mode == 0) {                                       // mode(d) = argmax(p) (first maximum), categorical.jl:42-44
-                    act = 0; float best = p[0];
-#pragma unroll
-                    for (int i = 1; i < A; ++i) if (p[i] > best) { best = p[i]; act = i; }
-                } else act = ((const int32_t*)a.actions)[bb] - a.action_start;
+                if (a.mode == 0) act = categorical_mode<A>(p);
+                else act = ((const int32_t*)a.actions)[bb] - a.action_start;
                 logp = flog(pick<A>(p, act));
                 if (store && a.mode == 1 && a.entropy) a.entropy[b] = categorical_entropy<A>(p);
             }
@@ -847,6 +851,67 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
             if (t < a.T) lds_barrier();
         }
     }
+}
+
+// =============================================================================================
+// evaluate_kernel — the loop of evaluate_agent (evaluation.jl:90-122) for g.r.T env steps in one launch: predict_actions(deterministic) -> act! -> observe, and
+// the episode accounting of dril_eval_account.h.  rollout_kernel without what an evaluation does not need: the ACTOR's weights alone in LDS (no critic forward, no
+// V(terminal_observation), no last values), no buffer row, no monitor.  A wave owns 32 envs; EnvCursor is loaded once and stored at the end, the running return /
+// length of every env are registers between the two E-sized arrays of g.acct, and where an episode ends its lane appends one event.  The step is rollout_kernel's:
+// eval_net, rollout_sample on the env's stream at cur.gs (or the mode by policy_kernel's definition), env_advance / env_end_episode — so every action, reward and
+// flag is bit-identical to the step-granular launches (tests/test_gpu_eval_device.py).  Steps are numbered g.step0 + 1 .. g.step0 + T: launches continue each other.
+// =============================================================================================
+template <int KIND, int H, bool WIDE, bool SPLIT>
+__global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_kernel(EvalKernelArgs g) {
+    constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
+    const RolloutArgs& a = g.r;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* la = smem;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    stage_fwd<D, H, A, WIDE, SPLIT>(la, a.params, a.actor, tid, 256);
+    __syncthreads();
+    const int c = lane & 31, h = lane >> 5;
+    const int e_raw = (blockIdx.x * 4 + wave) * kTile + c;
+    if ((blockIdx.x * 4 + wave) * kTile >= a.E) return;  // whole wave out of range (wave-uniform)
+    const bool valid = e_raw < a.E;
+    const int e = valid ? e_raw : a.E - 1;
+    const bool writer = valid && h == 0;
+    const uint64_t env_seed = a.env_seed0 + (uint64_t)e;
+    const EnvArrays env{a.state, a.step_count, a.episode, a.gstep, nullptr, nullptr};
+
+    EnvCursor<KIND> cur; cur.load(env, e);
+    float obs[D];
+    // The observation is made opaque where env_obs hands it over: with the scaled kinds' affine map (x - low) sf - 1 in view, the optimiser sinks the "- 1" below
+    // pair_obs' select between the two halves of the wave and the map is then rounded twice (multiply, add) where env_observe_kernel / obs_partials_kernel contract
+    // it into one fma — a last-bit difference in the observation (kind 7), which the exact comparison with the step-granular launches does not allow
+    auto observe = [&] {
+        env_obs<KIND>(cur.st, obs);
+#pragma unroll
+        for (int i = 0; i < D; ++i) asm volatile("" : "+v"(obs[i]));
+    };
+    observe();
+    float lsr[4]; rollout_log_std<KIND>(a, lsr);
+    float ret = g.acct.cur_ret[e]; int32_t len = g.acct.cur_len[e];
+
+    for (int t = 0; t < a.T; ++t) {
+        int zoff = 0; asm volatile("" : "+v"(zoff));                          // keep the weights in LDS (see rollout_kernel)
+        const float* la_t = la + zoff;
+        float xk[FirstLayer<D>::KS];
+        pair_obs<D>(obs, h, xk);
+        float out[A];
+        eval_net<D, H, A, WIDE, SPLIT>(la_t, a.w2a_actor, xk, out, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        int act_env = 0; float actf_env = 0.f, logp;
+        if (g.deterministic) {
+            if (EnvSpec<KIND>::discrete) { float p[A]; softmax_n<A>(out, p); act_env = categorical_mode<A>(p); }
+            else actf_env = fminf(fmaxf(out[0], -act_bound<KIND>()), act_bound<KIND>());   // mode(d) = mean (diagGaussian.jl:45-47), then ClampAdapter
+        } else rollout_sample<KIND>(a, 0, env_seed, cur.gs, out, lsr, false, &act_env, &actf_env, &logp);
+        const StepOut so = env_advance<KIND>(cur, actf_env, act_env, a.episode_len, a.fixed_len != 0);
+        env_end_episode<KIND>(cur, env_seed, so, nullptr, nullptr);
+        if (writer) eval_account(g.acct, g.step0 + t + 1, e, so.rew, so.done(), ret, len);
+        observe();                                                            // observe(env), :97
+    }
+    if (writer) { cur.store(env, e); g.acct.cur_ret[e] = ret; g.acct.cur_len[e] = len; }
 }
 
 // =============================================================================================
@@ -1419,6 +1484,25 @@ hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_
 #define CALL(K, HH) { if constexpr (HH == 32) { CALLS(K, HH, false) } else { if (a.exact_f32) CALLS(K, HH, false) else CALLS(K, HH, true) } }
     return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
         DRIL_DISPATCH_H(decltype(K)::value, hidden, CALL)
+        return hipGetLastError();
+    });
+#undef CALL
+#undef CALLS
+}
+
+// evaluate_kernel: the fused shapes (two equal tanh layers of 64 / 128 / 256); the forward choice (a.r.exact_f32) and the kind dispatch are the rollout's
+hipError_t launch_evaluate(int kind, int hidden, const EvalKernelArgs& a, hipStream_t s) {
+    const int blocks = (a.r.E + 4 * kTile - 1) / (4 * kTile);
+#define CALLS(K, HH, SP)                                                                                      \
+    {                                                                                                         \
+        const size_t lds = sizeof(float) * FwdLds<EnvSpec<K>::D, HH, EnvSpec<K>::A, (HH > 64), SP>::SIZE;     \
+        { hipError_t e = set_max_dynamic_lds((const void*)evaluate_kernel<K, HH, (HH > 64), SP>, lds); if (e != hipSuccess) return e; } \
+        evaluate_kernel<K, HH, (HH > 64), SP><<<blocks, 256, lds, s>>>(a);                                    \
+    }
+#define CALL(K, HH) { if (a.r.exact_f32) CALLS(K, HH, false) else CALLS(K, HH, true) }
+    return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;
+        if (hidden == 64) CALL(KIND, 64) else if (hidden == 128) CALL(KIND, 128) else if (hidden == 256) CALL(KIND, 256) else return hipErrorInvalidValue;
         return hipGetLastError();
     });
 #undef CALL

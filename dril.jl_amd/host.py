@@ -724,6 +724,23 @@ class Handle:
         return dict(mean_reward=st.mean_reward, std_reward=st.std_reward, mean_length=st.mean_length, std_length=st.std_length,
                     n_steps=st.n_steps), er, el
 
+    def evaluate_agent_device(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None, poll_steps: int = 0,
+                              force_step_granular: bool = False):
+        """The same evaluation with the episode accounting on the device, leaving nothing behind on the handle (dril_evaluate_agent_device, docs/evaluation.md)
+        -> (stats dict, episode_rewards, episode_lengths, info dict).  seed None: the env seed in force; env e is reset with seed + its global index.
+        info: path (0 step-granular launches, 1 the persistent evaluate kernel), launches, steps_enqueued, events."""
+        o = capi.DrilEvalOptions()
+        self._chk(self.lib.dril_eval_options_default(C.byref(o)))
+        o.n_eval_episodes, o.deterministic, o.poll_steps, o.force_step_granular = int(n_eval_episodes), int(deterministic), int(poll_steps), int(force_step_granular)
+        if seed is not None:
+            o.seed, o.has_seed = int(seed), 1
+        st, info = capi.DrilEvalStats(), capi.DrilEvalInfo()
+        n = max(int(n_eval_episodes), 0)
+        er = np.empty(n, np.float32); el = np.empty(n, np.int32)
+        self._chk(self.lib.dril_evaluate_agent_device(self._h, C.byref(o), C.byref(st), self._p(er), self._p(el), C.byref(info)))
+        return (dict(mean_reward=st.mean_reward, std_reward=st.std_reward, mean_length=st.mean_length, std_length=st.std_length, n_steps=st.n_steps), er, el,
+                dict(path=info.path, launches=info.launches, steps_enqueued=info.steps_enqueued, events=info.events))
+
     def train(self, max_steps: int):
         per_iter = self.N * self.cfg.world_size
         iters = max_steps // per_iter
@@ -1326,10 +1343,14 @@ def _timer_sections(h: Handle, prof0, t_upd: float) -> dict:
 
 
 def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 10, deterministic: bool = True,
-                   reward_threshold: Optional[float] = None, return_stats: bool = True):
-    """evaluate_agent(agent, env; ...) (src/evaluation.jl:54-143)."""
+                   reward_threshold: Optional[float] = None, return_stats: bool = True, isolated: bool = False):
+    """evaluate_agent(agent, env; ...) (src/evaluation.jl:54-143).  isolated=True (device envs): the evaluation runs on the device and leaves the env as it was —
+    state, counters, the monitor's window, a normaliser's statistics (frozen for the call) — so it may sit between two training iterations
+    (Handle.evaluate_agent_device, docs/evaluation.md); the default resets the env and lets its episodes enter the monitor's window, as before."""
     h = env.bind(agent.alg, agent.layer)
     h.set_params(flatten_params(agent.train_state.parameters))
+    if isolated and isinstance(env, HostParallelEnv):
+        raise NotImplementedError("evaluate_agent(isolated=True): host envs (HostParallelEnv) live with the caller, who keeps a second set of envs for evaluation; the device verb steps device envs")
     if isinstance(env, HostParallelEnv):       # the reference loop on the caller's envs, predict_actions on the device (evaluation.jl:86-125)
         asp = env.action_space()
         er, el = [], []
@@ -1349,6 +1370,8 @@ def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 
         er, el = np.asarray(er, np.float32), np.asarray(el, np.int64)
         sd = lambda x: float(np.std(x, ddof=1)) if len(x) > 1 else float("nan")
         stats = {"mean_reward": float(er.mean()), "std_reward": sd(er), "mean_length": float(el.mean()), "std_length": sd(el)}
+    elif isolated:
+        stats, er, el, _ = h.evaluate_agent_device(n_eval_episodes, deterministic)
     else:
         stats, er, el = h.evaluate_agent(n_eval_episodes, deterministic)
     if reward_threshold is not None and stats["mean_reward"] < reward_threshold:

@@ -27,12 +27,32 @@ struct DrilEvalStats
     mean_reward::Float64; std_reward::Float64; mean_length::Float64; std_length::Float64
     n_episodes::Int32; n_steps::Int32
 end
+# dril_eval_options / dril_eval_info (include/dril_hip.h): the evaluation on the device that leaves the env side of the handle as it was (docs/evaluation.md)
+struct DrilEvalOptions
+    n_eval_episodes::Int32; deterministic::Int32
+    seed::UInt64; has_seed::Int32
+    poll_steps::Int32
+    force_step_granular::Int32
+    reserved::NTuple{3, Int32}
+end
+struct DrilEvalInfo
+    path::Int32
+    launches::Int32; steps_enqueued::Int32; events::Int32; reserved::NTuple{4, Int32}
+end
+# isolated = true: the episode accounting runs on the device and the env is left as it was — state, counters, the monitor's window, a normaliser's statistics (frozen
+# for the call) — so the call may sit between two training iterations on the training env.  The default keeps the reset env and the monitor's window as before.
 function DRiL.evaluate_agent(agent, env::DeviceParallelEnv; n_eval_episodes::Int = 10, deterministic::Bool = true,
-        reward_threshold::Union{Nothing, Real} = nothing, return_stats::Bool = true, warn::Bool = true, kwargs...)
+        reward_threshold::Union{Nothing, Real} = nothing, return_stats::Bool = true, warn::Bool = true, isolated::Bool = false, kwargs...)
     bind_agent!(env, agent, agent.algorithm); push_params!(env, agent)
     st = Ref{DrilEvalStats}(); er = Vector{Float32}(undef, n_eval_episodes); el = Vector{Int32}(undef, n_eval_episodes)
-    GC.@preserve er el check(ccall((:dril_evaluate_agent, LIB[]), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{DrilEvalStats}, Ptr{Float32}, Ptr{Int32}),
-        env.handle, n_eval_episodes, deterministic, st, er, el), env.handle)
+    if isolated
+        o = Ref(DrilEvalOptions(Int32(n_eval_episodes), Int32(deterministic), UInt64(0), Int32(0), Int32(0), Int32(0), (Int32(0), Int32(0), Int32(0))))
+        GC.@preserve er el check(ccall((:dril_evaluate_agent_device, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilEvalOptions}, Ref{DrilEvalStats}, Ptr{Float32}, Ptr{Int32}, Ptr{DrilEvalInfo}),
+            env.handle, o, st, er, el, C_NULL), env.handle)
+    else
+        GC.@preserve er el check(ccall((:dril_evaluate_agent, LIB[]), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{DrilEvalStats}, Ptr{Float32}, Ptr{Int32}),
+            env.handle, n_eval_episodes, deterministic, st, er, el), env.handle)
+    end
     s = st[]
     if reward_threshold !== nothing && s.mean_reward < reward_threshold
         error("Mean reward below threshold: $(round(s.mean_reward, digits = 2)) < $(reward_threshold)")            # evaluation.jl:131-135

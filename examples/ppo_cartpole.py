@@ -19,7 +19,8 @@ iters = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 env = pkg.MonitorWrapperEnv(pkg.DeviceParallelEnv(pkg.CartPoleEnv(max_steps=500), n_envs, seed=0), stats_window=100)
 alg = pkg.PPO(n_steps=128, batch_size=n_envs * 128 // 4, epochs=4, ent_coef=0.01, learning_rate=1e-3)
 agent = pkg.Agent(pkg.ActorCriticLayer(env.observation_space(), env.action_space()), alg, seed=0)
-print("before:", pkg.evaluate_agent(agent, env, n_eval_episodes=20))
+# isolated=True: the evaluation runs on the device (dril_evaluate_agent_device) and leaves the training env as it was (docs/evaluation.md)
+print("before:", pkg.evaluate_agent(agent, env, n_eval_episodes=20, isolated=True))
 stats, timer = pkg.train_(agent, env, alg, iters * alg.n_steps * n_envs)
 print(f"trained {iters} iterations in {timer['training_loop']:.2f} s; last loss {stats['losses'][-1]:.4f}, mean rollout fps {sum(stats['fps']) / len(stats['fps']):.3g}")
-print("after: ", pkg.evaluate_agent(agent, env, n_eval_episodes=20))
+print("after: ", pkg.evaluate_agent(agent, env, n_eval_episodes=20, isolated=True))

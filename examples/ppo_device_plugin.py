@@ -33,9 +33,11 @@ class PrintReturn:
         return True
 
 
+# isolated=True: evaluated on the device, the training envs, the monitor's window and (under --normalize) the statistics left as they were (docs/evaluation.md)
+print("evaluate_agent before:", pkg.evaluate_agent(agent, env, n_eval_episodes=20, isolated=True))
 stats, timer = pkg.train_(agent, env, alg, iters * alg.n_steps * n_envs, callbacks=[PrintReturn()])
 print(f"trained {iters} iterations in {timer['training_loop']:.2f} s; last loss {stats['losses'][-1]:.4f}")
-print("evaluate_agent:", pkg.evaluate_agent(agent, env, n_eval_episodes=20))        # under --normalize: the training statistics, frozen; raw episode returns
+print("evaluate_agent after: ", pkg.evaluate_agent(agent, env, n_eval_episodes=20, isolated=True))        # under --normalize: the training statistics, frozen; raw episode returns
 if normalize:
     st = env.handle.normalize_get_stats()
     print(f"obs_rms over {st['obs_count']} observations: mean {st['obs_mean'].round(3)}  var {st['obs_var'].round(3)};  ret_rms var {st['ret_var']:.4f} over {st['ret_count']}")

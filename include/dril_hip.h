@@ -441,6 +441,34 @@ typedef struct dril_eval_stats {
 int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval_episodes, int32_t deterministic, dril_eval_stats* out,
                             float* episode_rewards, int32_t* episode_lengths);
 
+/* The same evaluation ON THE DEVICE, and leaving nothing behind (docs/evaluation.md).  The episode accounting runs on the device: every env's thread adds its
+ * reward in float32 and in step order and appends {step, env, return, length} to one list where its episode ends; the host looks at the list's 4-byte counter
+ * once per K env steps, sorts the copied slots by (step, env) and takes n_eval_episodes — the numbers dril_evaluate_agent returns, whatever K is and whichever
+ * path ran.  Two paths: a persistent evaluate kernel (a wave keeps 32 envs in registers for K steps, the actor's weights in LDS) for the built-in kinds on the
+ * fused shapes without a normaliser, and step-granular launches with a small accounting launch for every other device-env handle (generic shapes, cfg.norm_*,
+ * plug-ins with or without dril_scaling_enable / dril_normalize_enable / the fused rollout).
+ * A normaliser is FROZEN for the call whatever its training flag (set_training(env, false), evaluation of a training env; docs/deviations.md).
+ * The call brings its own reset and puts back what it writes, on error paths too: env state, step counts, episode and noise-stream counters, the seed in force,
+ * `returns`, the E-sized per-step arrays, the statistics' buffers and parities, and whether the envs count as reset.  The monitor's sums / window / meta are not
+ * written at all (its launches are not made during the call), nor are the call counter of the policy noise, the rollout buffer, parameters, optimiser state, update
+ * and profile counters; no all-reduce is enqueued (every rank of a data-parallel job evaluates its own envs).
+ * DRIL_ERR_NOT_INITIALISED: null handle.  DRIL_ERR_INVALID_ARG: n_eval_episodes < 1, null o / out, poll_steps < 0.  DRIL_ERR_UNSUPPORTED: DRIL_ENV_EXTERNAL; no
+ * episode finishes within ceil(n / n_envs) + 1 time limits and one poll interval. */
+typedef struct dril_eval_options {
+    int32_t n_eval_episodes, deterministic;
+    uint64_t seed; int32_t has_seed;     /* 0: the handle's current env seed; env e is reset with seed + global env index */
+    int32_t poll_steps;                  /* 0: the library's default K; >= 1: look at the counter every poll_steps env steps */
+    int32_t force_step_granular;         /* 1: never take the persistent kernel (tests, A/B) */
+    int32_t reserved[3];
+} dril_eval_options;
+typedef struct dril_eval_info {
+    int32_t path;                        /* 0 step-granular launches + device accounting, 1 persistent evaluate kernel */
+    int32_t launches, steps_enqueued, events, reserved[4];   /* launch calls of the loop, env steps enqueued, events the device counted */
+} dril_eval_info;
+int32_t dril_eval_options_default(dril_eval_options* o);   /* 10 episodes, deterministic, evaluation.jl:57-58 */
+int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_options* o, dril_eval_stats* out,
+                                   float* episode_rewards, int32_t* episode_lengths, dril_eval_info* info /* may be NULL */);
+
 /* ---- train! ------------------------------------------------------------------ */
 /* iterations = max_steps / (T*E*world) of {set lr, collect_rollout!, ppo update}: ppo.jl:154-298.
  * stats / fps arrays need `iterations` entries (may be NULL) */

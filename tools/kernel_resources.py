@@ -28,8 +28,8 @@ for ln in r.stderr.splitlines():
     elif cur is not None and ":" in t: k, v = t.split(":", 1); cur[k.strip()] = v.strip()
 def dem(n):
     return subprocess.run(["/usr/bin/c++filt", n], capture_output=True, text=True).stdout.strip().replace("dril::", "").split("(")[0]
-print(f"{'kernel':70s} {'VGPR':>5s} {'AGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'occ':>3s} {'LDS':>7s} {'code B':>8s}")
+print(f"{'kernel':70s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'occ':>3s} {'LDS':>7s} {'code B':>8s}")
 for c in rows:
     n = dem(c["name"])
     if filt and filt not in n: continue
-    print(f"{n[:70]:70s} {c.get('VGPRs','?'):>5s} {c.get('AGPRs','?'):>5s} {c.get('VGPRs Spill','?'):>6s} {c.get('SGPRs Spill','?'):>6s} {c.get('ScratchSize [bytes/lane]','?'):>7s} {c.get('Occupancy [waves/SIMD]','?'):>3s} {c.get('LDS Size [bytes/block]','?'):>7s} {sizes.get(c['name'], 0):>8d}")
+    print(f"{n[:70]:70s} {c.get('VGPRs','?'):>5s} {c.get('AGPRs','?'):>5s} {c.get('TotalSGPRs','?'):>5s} {c.get('VGPRs Spill','?'):>6s} {c.get('SGPRs Spill','?'):>6s} {c.get('ScratchSize [bytes/lane]','?'):>7s} {c.get('Occupancy [waves/SIMD]','?'):>3s} {c.get('LDS Size [bytes/block]','?'):>7s} {sizes.get(c['name'], 0):>8d}")
