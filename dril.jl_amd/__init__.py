@@ -13,7 +13,7 @@ __graft_entry__.py / tests/conftest.py) under the module name `dril_jl_amd`.
 """
 from . import _capi  # noqa: F401
 from .host import (  # noqa: F401
-    AcrobotEnv, Agent, ActorCriticLayer, Box, CartPoleEnv, ContinuousActorCriticLayer, DeviceModuleEnv, DeviceParallelEnv, Discrete, HostParallelEnv,
+    AcrobotEnv, Agent, ActorCriticLayer, Box, CartPoleEnv, ContinuousActorCriticLayer, DeviceArrayParallelEnv, DeviceModuleEnv, DeviceParallelEnv, Discrete, HostParallelEnv,
     DiscreteActorCriticLayer, DrilError, Handle, MonitorWrapperEnv, MountainCarContinuousEnv, MountainCarEnv, NormalizeWrapperEnv, PendulumEnv, PPO, RolloutBuffer, ScalingWrapperEnv, collect_rollout_,
     describe_env_module, evaluate_agent, flatten_params, get_action_and_values, get_original_obs, get_original_rewards, make_config, predict_values, train_, unflatten_params,
     unnormalize_obs_, unnormalize_rewards_, TRAINING_START_LOCALS, ROLLOUT_START_LOCALS, TIMER_SECTIONS,

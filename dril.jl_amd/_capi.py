@@ -93,6 +93,12 @@ class DrilFusedRolloutInfo(C.Structure):
                 ("last_collection_launches", C.c_int64), ("reason", C.c_char * 256)]
 
 
+class DrilExtDeviceInfo(C.Structure):
+    """struct dril_ext_device_info, include/dril_hip.h"""
+    _fields_ = [("steps_device", C.c_int32), ("steps_host", C.c_int32), ("host_syncs", C.c_int32), ("per_dim_bounds", C.c_int32), ("launches", C.c_int64),
+                ("reserved", C.c_int32 * 4)]
+
+
 class DrilSacConfig(C.Structure):
     """struct dril_sac_config, include/dril_sac.h"""
     _fields_ = [
@@ -219,6 +225,12 @@ _SIG = {
     "dril_ext_record": (C.c_int32, [_P, _P, _P, _P, _P]),
     "dril_ext_finish": (C.c_int32, [_P, _P]),
     "dril_ext_steps": (C.c_int32, [_P]),
+    "dril_ext_act_device": (C.c_int32, [_P, _P, _P, _P, _P]),
+    "dril_ext_record_device": (C.c_int32, [_P, _P, _P, _P, _P, _P]),
+    "dril_ext_finish_device": (C.c_int32, [_P, _P, _P]),
+    "dril_predict_actions_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    "dril_ext_set_action_bounds": (C.c_int32, [_P, _P, _P]),
+    "dril_ext_device_info": (C.c_int32, [_P, C.POINTER(DrilExtDeviceInfo)]),
     "dril_collect_rollout": (C.c_int32, [_P, C.POINTER(C.c_double)]),
     "dril_debug_set_noise": (C.c_int32, [_P, _P, C.c_size_t]),
     "dril_buffer_copy_out": (C.c_int32, [_P, C.c_int32, _P, C.c_size_t]),

@@ -137,6 +137,12 @@ struct dril_handle {
     bool external = false; bool generic = false; float* gen_tmp = nullptr;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
     GenericDims gd{}; GenericWs gws; int ext_t = 0; bool ext_acted = false;   // DRIL_ENV_EXTERNAL: host envs, generic kernels
     float* ext_stage_rew = nullptr; uint8_t* ext_stage_flags = nullptr;   // pinned [T][E] staging: dril_ext_record returns without draining the stream
+    // the device-array verbs (dril_ext_*_device): the two ordering events (created once), the sticky error word and its pinned host copy, the ClampAdapter's
+    // per-dimension table (dril_ext_set_action_bounds), the counters of dril_ext_device_info, grow-only scratch of dril_predict_actions_device
+    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; int* ext_err = nullptr; int* ext_err_host = nullptr;
+    ExtBounds ext_bounds{}; bool ext_bounds_set = false;
+    int ext_steps_dev = 0, ext_steps_host = 0, ext_syncs = 0; int64_t ext_launches = 0;
+    void* ext_pred_act = nullptr; float* ext_pred_lp = nullptr; int64_t ext_pred_cap = 0;
     // NormalizeWrapperEnv around a plug-in env (dril_normalize_enable; kernels: dril_norm_wrap.h, dril_ppo_norm.h).  pn_red: the one row a data-parallel job all-reduces.
     // The wrapper's other arrays are the handle's own: disc_returns (`returns`), e_obs_raw / e_rew (old_obs / old_rewards: dril_normalize_get_original), e_rew_n (the
     // rewards dril_env_step delivers)
@@ -771,6 +777,10 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     if (!h->generic) CCHK(dmalloc(&h->rec, (size_t)(h->D <= 4 ? 2 : 3) * N));   // packed minibatch records: 2 (D <= 4) or 3 (D <= 8) float4 per sample
     if (h->generic) CCHK(dmalloc(&h->gen_tmp, E));
     if (ext) { CCHK(hipHostMalloc((void**)&h->ext_stage_rew, N * 4)); CCHK(hipHostMalloc((void**)&h->ext_stage_flags, N)); }
+    if (ext) {
+        CCHK(hipEventCreateWithFlags(&h->ext_ev_in, hipEventDisableTiming)); CCHK(hipEventCreateWithFlags(&h->ext_ev_out, hipEventDisableTiming));
+        CCHK(dmalloc(&h->ext_err, 1)); CCHK(hipMemsetAsync(h->ext_err, 0, 4, h->stream)); CCHK(hipHostMalloc((void**)&h->ext_err_host, 4)); *h->ext_err_host = 0;
+    }
     if (cfg->monitor_window > 0) {
         const size_t W = cfg->monitor_window;
         CCHK(dmalloc(&h->mon_cur_ret, E)); CCHK(dmalloc(&h->mon_cur_len, E)); CCHK(dmalloc(&h->ep_ret, N)); CCHK(dmalloc(&h->ep_len, N));
@@ -817,7 +827,9 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     h->env.release();
     if (h->ext_stage_rew) (void)hipHostFree(h->ext_stage_rew); if (h->ext_stage_flags) (void)hipHostFree(h->ext_stage_flags);
     if (h->eval_counter_host) (void)hipHostFree(h->eval_counter_host);
-    void* ptrs[] = {h->eval_snap, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
+    if (h->ext_err_host) (void)hipHostFree(h->ext_err_host);
+    if (h->ext_ev_in) (void)hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) (void)hipEventDestroy(h->ext_ev_out);
+    void* ptrs[] = {h->ext_err, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
                     h->flags, h->last_values, h->noise_dev, h->perm_dev, h->epoch_index, h->epoch_keys, h->small_xchg, h->w2max_dev, h->gae_carry, h->gae_err, h->w2pf_actor, h->w2pf_critic, h->adv_partials, h->adv_stats, h->ev_partials, h->step_stats,
                     h->stop_flag, h->nan_flag, h->e_obs, h->e_rew, h->e_tobs, h->e_term, h->e_trunc, h->e_act, h->e_obs_raw, h->e_rew_n, h->obs_rms, h->ret_rms, h->rms_partials, h->rms_red, h->gen_tmp, h->dbg, h->rec, h->epoch_tables, h->epoch_stats, h->w2a_actor, h->w2ta_actor, h->w2a_critic, h->w2ta_critic, h->w2p_actor, h->w2tp_actor, h->w2p_critic, h->w2tp_critic, h->mon_cur_ret, h->ep_ret, h->mon_ring_ret, h->e_ep_ret, h->mon_cur_len, h->ep_len,
                     h->mon_ring_len, h->e_ep_len, h->mon_cnt, h->mon_meta, h->e_flags};
@@ -1119,6 +1131,7 @@ DRIL_EXPORT int32_t dril_policy_from_handle(dril_handle* h, int32_t with_norm, d
     d.activation = h->cfg.activation; d.device = h->cfg.device;
     if (!h->discrete) for (int a = 0; a < h->A; ++a) {                                 // the Box the ClampAdapter clamps to (default_adapters.jl:4-11)
         if (h->env.module) { d.action_low[a] = h->env.desc.action_low[a]; d.action_high[a] = h->env.desc.action_high[a]; }
+        else if (h->external && h->ext_bounds_set) { d.action_low[a] = h->ext_bounds.lo[a]; d.action_high[a] = h->ext_bounds.hi[a]; }   // dril_ext_set_action_bounds
         else if (h->external) { d.action_low[a] = h->cfg.ext_action_low; d.action_high[a] = h->cfg.ext_action_high; }   // low >= high: per-dimension bounds the host env clamps to itself
         else { const EnvKindInfo* k = env_kind_info(h->env.kind); d.action_low[a] = k->act_lo; d.action_high[a] = k->act_hi; }   // a built-in Box: Pendulum's torque [-2, 2], every other [-1, 1]
     }
@@ -1313,6 +1326,52 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
     return do_sync ? sync(h) : DRIL_OK;
 }
 }  // namespace
+namespace {
+// dril_ext_device_info counts per rollout: the first act of a rollout starts the counters again
+void ext_count_begin(dril_handle* h) { if (h->ext_t == 0) { h->ext_steps_dev = h->ext_steps_host = h->ext_syncs = 0; h->ext_launches = 0; } }
+// the one drain of a rollout over external envs; the sticky error word of dril_ext_record_device comes back with it (a rollout may mix host and device verbs)
+int ext_finish_drain(dril_handle* h, const char* verb) {
+    HIPCHK(h, hipMemcpyAsync(h->ext_err_host, h->ext_err, 4, hipMemcpyDeviceToHost, h->stream));
+    int rc = sync(h); if (rc) return rc;
+    if (*h->ext_err_host) {
+        *h->ext_err_host = 0;
+        HIPCHK(h, hipMemsetAsync(h->ext_err, 0, 4, h->stream));
+        return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": dril_ext_record_device: truncated envs need terminal_obs (infos[i][\"terminal_observation\"], multithreadedParallelEnv.jl:64-66); the rollout is discarded");
+    }
+    return DRIL_OK;
+}
+// an argument of a device verb must be memory the handle's device can address, long enough for the array: a host pointer handed to a kernel is a GPU fault
+int ext_check_ptr(dril_handle* h, const char* verb, const char* name, const void* p, size_t bytes) {
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const bool ok = e == hipSuccess && ((at.type == hipMemoryTypeDevice && at.device == h->cfg.device) || at.type == hipMemoryTypeManaged || (at.type == hipMemoryTypeHost && at.devicePointer != nullptr));
+    if (!ok) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": " + name + " is not memory of device " + std::to_string(h->cfg.device) + " (the *_device verbs take device arrays; host arrays go to the verbs without the suffix)");
+    if (at.type == hipMemoryTypeDevice) {
+        hipDeviceptr_t base = nullptr; size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) (void)hipGetLastError();
+        else if ((const char*)p + bytes > (const char*)base + size) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": the allocation behind " + name + " ends before the " + std::to_string(bytes) + " bytes of the array");
+    }
+    return DRIL_OK;
+}
+// the handle's stream takes over from the caller's stream / hands back to it: two events per handle, no host wait
+int ext_stream_enter(dril_handle* h, void* caller_stream) {
+    HIPCHK(h, hipEventRecord(h->ext_ev_in, (hipStream_t)caller_stream)); HIPCHK(h, hipStreamWaitEvent(h->stream, h->ext_ev_in, 0));
+    return DRIL_OK;
+}
+int ext_stream_leave(dril_handle* h, void* caller_stream) {
+    HIPCHK(h, hipEventRecord(h->ext_ev_out, h->stream)); HIPCHK(h, hipStreamWaitEvent((hipStream_t)caller_stream, h->ext_ev_out, 0));
+    return DRIL_OK;
+}
+// the adapter's table of a Box handle as the actions-out kernel takes it (null: Discrete, or nothing to clamp)
+const ExtBounds* ext_bounds_for(dril_handle* h, ExtBounds& scalar) {
+    if (h->discrete) return nullptr;
+    if (h->ext_bounds_set) return &h->ext_bounds;
+    if (!(h->cfg.ext_action_low < h->cfg.ext_action_high)) return nullptr;
+    for (int a = 0; a < h->A; ++a) { scalar.lo[a] = h->cfg.ext_action_low; scalar.hi[a] = h->cfg.ext_action_high; }
+    return &scalar;
+}
+}  // namespace
 // ---- collect_trajectories over HOST envs (DRIL_ENV_EXTERNAL), trajectory.jl:22-78: the caller steps its envs, the device does the rest ----
 DRIL_EXPORT int32_t dril_ext_act(dril_handle* h, const float* obs, void* raw_actions, void* env_actions) {
     NEED(h);
@@ -1321,6 +1380,7 @@ DRIL_EXPORT int32_t dril_ext_act(dril_handle* h, const float* obs, void* raw_act
     if (h->ext_acted) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act: the previous step has no dril_ext_record yet");
     if (h->ext_t >= h->cfg.n_steps) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act: n_steps env steps are recorded; call dril_ext_finish");
     const size_t E = h->cfg.n_envs, D = h->D, A = h->A, ab = act_bytes_per(h), k = (size_t)h->ext_t * E;
+    ext_count_begin(h); const int64_t l0 = h->gws.launches;
     HIPCHK(h, hipMemcpyAsync(h->obs + k * D, obs, E * D * 4, hipMemcpyHostToDevice, h->stream));                          // observation -> buffer, :46-47
     const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * A)) : nullptr;
     PolicyArgs p = policy_args(h, h->obs + k * D, (int64_t)E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);     // get_action_and_values :41; raw action stored :48
@@ -1328,8 +1388,14 @@ DRIL_EXPORT int32_t dril_ext_act(dril_handle* h, const float* obs, void* raw_act
     h->policy_calls += 1;
     void* first = raw_actions ? raw_actions : env_actions;                             // one device-to-host copy; the second output is a host copy of it
     if (first) HIPCHK(h, hipMemcpyAsync(first, (char*)h->act + k * ab, E * ab, hipMemcpyDeviceToHost, h->stream));
+    h->ext_launches += h->gws.launches - l0;
     int rc = sync(h); if (rc) return rc;
+    h->ext_syncs += 1;
     if (raw_actions && env_actions) std::memcpy(env_actions, raw_actions, E * ab);
+    if (env_actions && !h->discrete && h->ext_bounds_set) {                                                               // the per-dimension table of dril_ext_set_action_bounds
+        float* a = (float*)env_actions;
+        for (size_t i = 0; i < E * A; ++i) { const float lo = h->ext_bounds.lo[i % A], hi = h->ext_bounds.hi[i % A]; if (lo < hi) a[i] = a[i] < lo ? lo : (a[i] > hi ? hi : a[i]); }
+    } else
     if (env_actions && !h->discrete && h->cfg.ext_action_low < h->cfg.ext_action_high) {                                  // to_env(ClampAdapter) :42, default_adapters.jl:4-11; E * A floats, on the host
         float* a = (float*)env_actions; const float lo = h->cfg.ext_action_low, hi = h->cfg.ext_action_high;
         for (size_t i = 0; i < E * A; ++i) a[i] = a[i] < lo ? lo : (a[i] > hi ? hi : a[i]);
@@ -1357,15 +1423,18 @@ DRIL_EXPORT int32_t dril_ext_record(dril_handle* h, const float* rewards, const 
         for (size_t j = 0; j < n; ++j) std::memcpy(&tobs[j * D], terminal_obs + (size_t)tr[j] * D, D * 4);
         HIPCHK(h, hipMemcpyAsync(h->e_tobs, tobs.data(), n * D * 4, hipMemcpyHostToDevice, h->stream));
         PolicyArgs p = policy_args(h, h->e_tobs, (int64_t)n, nullptr, nullptr, h->e_rew, nullptr, nullptr, 2);
+        const int64_t l0 = h->gws.launches;
         HIPCHK(h, run_policy(h, p));
+        h->ext_launches += h->gws.launches - l0;
         HIPCHK(h, hipMemcpyAsync(bv.data(), h->e_rew, n * 4, hipMemcpyDeviceToHost, h->stream));
         int rc = sync(h); if (rc) return rc;                                          // host temporaries: drain before they go out of scope
         for (size_t j = 0; j < n; ++j) row[tr[j]] = bv[j];
         HIPCHK(h, hipMemcpyAsync(h->boot + k, row.data(), E * 4, hipMemcpyHostToDevice, h->stream));
         rc = sync(h); if (rc) return rc;
+        h->ext_syncs += 2;
     }
     // no truncation: nothing to wait for — the copies read the pinned slot and complete behind the next dril_ext_act
-    h->ext_t += 1; h->ext_acted = false;
+    h->ext_t += 1; h->ext_acted = false; h->ext_steps_host += 1;
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_ext_finish(dril_handle* h, const float* last_obs) {
@@ -1376,12 +1445,126 @@ DRIL_EXPORT int32_t dril_ext_finish(dril_handle* h, const float* last_obs) {
     const size_t E = h->cfg.n_envs, D = h->D;
     HIPCHK(h, hipMemcpyAsync(h->e_obs, last_obs, E * D * 4, hipMemcpyHostToDevice, h->stream));
     PolicyArgs p = policy_args(h, h->e_obs, (int64_t)E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);          // V(new_obs) where the last step left the trajectory open, :65-70
+    const int64_t l0 = h->gws.launches;
     HIPCHK(h, run_policy(h, p));
+    h->ext_launches += h->gws.launches - l0 + 1;
     h->ext_t = 0; h->noise_set = false;
     int rc = compute_gae(h); if (rc) return rc;                                       // compute_advantages! + returns, rollout_buffer.jl:83-87
-    return sync(h);
+    return ext_finish_drain(h, "dril_ext_finish");
 }
 DRIL_EXPORT int32_t dril_ext_steps(const dril_handle* h) { return h ? h->ext_t : -1; }
+
+// ---- the same three verbs on DEVICE arrays: no copy across PCIe, no drain before dril_ext_finish_device (include/dril_hip.h) ----
+DRIL_EXPORT int32_t dril_ext_act_device(dril_handle* h, const float* d_obs, void* d_raw_actions, void* d_env_actions, void* caller_stream) {
+    NEED(h);
+    if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_act_device: the handle was not created with DRIL_ENV_EXTERNAL");
+    if (!d_obs) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act_device: null obs");
+    if (h->ext_acted) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act_device: the previous step has no dril_ext_record yet");
+    if (h->ext_t >= h->cfg.n_steps) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act_device: n_steps env steps are recorded; call dril_ext_finish");
+    const size_t E = h->cfg.n_envs, D = h->D, A = h->A, ab = act_bytes_per(h), k = (size_t)h->ext_t * E;
+    int rc = ext_check_ptr(h, "dril_ext_act_device", "d_obs", d_obs, E * D * 4); if (rc) return rc;
+    if (d_raw_actions) { rc = ext_check_ptr(h, "dril_ext_act_device", "d_raw_actions", d_raw_actions, E * ab); if (rc) return rc; }
+    if (d_env_actions) { rc = ext_check_ptr(h, "dril_ext_act_device", "d_env_actions", d_env_actions, E * ab); if (rc) return rc; }
+    ext_count_begin(h); const int64_t l0 = h->gws.launches;
+    rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->obs + k * D, d_obs, E * D * 4, hipMemcpyDefault, h->stream));                               // observation -> buffer, :46-47
+    const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * A)) : nullptr;
+    PolicyArgs p = policy_args(h, h->obs + k * D, (int64_t)E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);     // the host verb's forward: the same bits
+    HIPCHK(h, run_policy(h, p));
+    h->policy_calls += 1;
+    h->ext_launches += h->gws.launches - l0;
+    if (d_raw_actions || d_env_actions) {                                                                                   // to_env(ClampAdapter) :42 on the device
+        ExtBounds scalar; const ExtBounds* b = ext_bounds_for(h, scalar);
+        HIPCHK(h, launch_ext_actions_out((char*)h->act + k * ab, d_raw_actions, d_env_actions, (int64_t)E, (int)A, h->discrete ? 1 : 0, b, h->stream));
+        h->ext_launches += 1;
+    }
+    rc = ext_stream_leave(h, caller_stream); if (rc) return rc;
+    h->ext_acted = true;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_ext_record_device(dril_handle* h, const float* d_rewards, const uint8_t* d_terminated, const uint8_t* d_truncated, const float* d_terminal_obs, void* caller_stream) {
+    NEED(h);
+    if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_record_device: the handle was not created with DRIL_ENV_EXTERNAL");
+    if (!d_rewards || !d_terminated || !d_truncated) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_record_device: null rewards / terminated / truncated");
+    if (!h->ext_acted) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_record_device without a preceding dril_ext_act");
+    const size_t E = h->cfg.n_envs, D = h->D, k = (size_t)h->ext_t * E;
+    int rc = ext_check_ptr(h, "dril_ext_record_device", "d_rewards", d_rewards, E * 4); if (rc) return rc;
+    rc = ext_check_ptr(h, "dril_ext_record_device", "d_terminated", d_terminated, E); if (rc) return rc;
+    rc = ext_check_ptr(h, "dril_ext_record_device", "d_truncated", d_truncated, E); if (rc) return rc;
+    if (d_terminal_obs) { rc = ext_check_ptr(h, "dril_ext_record_device", "d_terminal_obs", d_terminal_obs, E * D * 4); if (rc) return rc; }
+    rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    if (d_terminal_obs) {                                                             // V(terminal_observation), trajectory.jl:57-61: the critic over all E columns, kept where truncated
+        const int64_t l0 = h->gws.launches;
+        PolicyArgs p = policy_args(h, d_terminal_obs, (int64_t)E, nullptr, nullptr, h->gen_tmp, nullptr, nullptr, 2);
+        HIPCHK(h, run_policy(h, p));
+        h->ext_launches += h->gws.launches - l0;
+    }
+    HIPCHK(h, launch_ext_record((int)E, d_rewards, d_terminated, d_truncated, d_terminal_obs ? h->gen_tmp : nullptr, h->rew + k, h->flags + k, h->boot + k, h->ext_err, h->stream));
+    h->ext_launches += 1;
+    rc = ext_stream_leave(h, caller_stream); if (rc) return rc;
+    h->ext_t += 1; h->ext_acted = false; h->ext_steps_dev += 1;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_ext_finish_device(dril_handle* h, const float* d_last_obs, void* caller_stream) {
+    NEED(h);
+    if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_finish_device: the handle was not created with DRIL_ENV_EXTERNAL");
+    if (!d_last_obs) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_finish_device: null last_obs");
+    if (h->ext_acted || h->ext_t != h->cfg.n_steps) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_finish_device: the rollout needs exactly n_steps act/record pairs");
+    const size_t E = h->cfg.n_envs, D = h->D;
+    int rc = ext_check_ptr(h, "dril_ext_finish_device", "d_last_obs", d_last_obs, E * D * 4); if (rc) return rc;
+    rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->e_obs, d_last_obs, E * D * 4, hipMemcpyDefault, h->stream));
+    PolicyArgs p = policy_args(h, h->e_obs, (int64_t)E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);          // V(new_obs) where the last step left the trajectory open, :65-70
+    const int64_t l0 = h->gws.launches;
+    HIPCHK(h, run_policy(h, p));
+    h->ext_launches += h->gws.launches - l0 + 1;
+    h->ext_t = 0; h->noise_set = false;
+    rc = compute_gae(h); if (rc) return rc;                                           // compute_advantages! + returns, rollout_buffer.jl:83-87
+    return ext_finish_drain(h, "dril_ext_finish_device");                             // the drain covers the read of d_last_obs: nothing for caller_stream to wait for
+}
+DRIL_EXPORT int32_t dril_predict_actions_device(dril_handle* h, const float* d_obs, int64_t batch, int32_t deterministic, void* d_raw_actions, void* d_env_actions, void* caller_stream) {
+    NEED(h);
+    if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_predict_actions_device: the handle was not created with DRIL_ENV_EXTERNAL");
+    if (!d_obs || batch < 1) return fail(h, DRIL_ERR_INVALID_ARG, "dril_predict_actions_device: null obs or batch < 1");
+    if (!d_raw_actions && !d_env_actions) return fail(h, DRIL_ERR_INVALID_ARG, "dril_predict_actions_device: null actions");
+    const size_t B = (size_t)batch, ab = act_bytes_per(h);
+    int rc = ext_check_ptr(h, "dril_predict_actions_device", "d_obs", d_obs, B * h->D * 4); if (rc) return rc;
+    if (d_raw_actions) { rc = ext_check_ptr(h, "dril_predict_actions_device", "d_raw_actions", d_raw_actions, B * ab); if (rc) return rc; }
+    if (d_env_actions) { rc = ext_check_ptr(h, "dril_predict_actions_device", "d_env_actions", d_env_actions, B * ab); if (rc) return rc; }
+    if (batch > h->ext_pred_cap) {                                                     // grow-only scratch: the head kernel's actions and log-probabilities (hipFree waits for the device)
+        if (h->ext_pred_act) HIPCHK(h, hipFree(h->ext_pred_act)); if (h->ext_pred_lp) HIPCHK(h, hipFree(h->ext_pred_lp));
+        h->ext_pred_act = nullptr; h->ext_pred_lp = nullptr; h->ext_pred_cap = 0;
+        HIPCHK(h, hipMalloc(&h->ext_pred_act, B * ab)); HIPCHK(h, dmalloc(&h->ext_pred_lp, B));
+        h->ext_pred_cap = batch;
+    }
+    rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    PolicyArgs a = policy_args(h, d_obs, batch, nullptr, h->ext_pred_act, nullptr, h->ext_pred_lp, nullptr, 0);
+    a.deterministic = deterministic ? 1 : 0;
+    HIPCHK(h, run_policy(h, a));
+    h->policy_calls += 1;
+    ExtBounds scalar; const ExtBounds* b = ext_bounds_for(h, scalar);
+    HIPCHK(h, launch_ext_actions_out(h->ext_pred_act, d_raw_actions, d_env_actions, batch, h->A, h->discrete ? 1 : 0, b, h->stream));
+    return ext_stream_leave(h, caller_stream);
+}
+DRIL_EXPORT int32_t dril_ext_set_action_bounds(dril_handle* h, const float* low, const float* high) {
+    NEED(h);
+    if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_set_action_bounds: the handle was not created with DRIL_ENV_EXTERNAL");
+    if (h->discrete) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_set_action_bounds: a Discrete action space has no bounds to clamp to");
+    if (!low && !high) { h->ext_bounds_set = false; return DRIL_OK; }
+    if (!low || !high) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_set_action_bounds: null low / high");
+    for (int a = 0; a < h->A; ++a) { h->ext_bounds.lo[a] = low[a]; h->ext_bounds.hi[a] = high[a]; }
+    h->ext_bounds_set = true;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_ext_device_info(const dril_handle* h, struct dril_ext_device_info* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return DRIL_ERR_INVALID_ARG;
+    if (!h->external) return DRIL_ERR_UNSUPPORTED;
+    std::memset(out, 0, sizeof(*out));
+    out->steps_device = h->ext_steps_dev; out->steps_host = h->ext_steps_host; out->host_syncs = h->ext_syncs; out->per_dim_bounds = h->ext_bounds_set ? 1 : 0;
+    out->launches = h->ext_launches;
+    return DRIL_OK;
+}
 
 DRIL_EXPORT int32_t dril_collect_rollout(dril_handle* h, double* fps) { NEED(h); NOT_EXTERNAL(h, "dril_collect_rollout"); return collect_rollout(h, fps, true); }
 DRIL_EXPORT int32_t dril_debug_set_noise(dril_handle* h, const void* noise, size_t count) {

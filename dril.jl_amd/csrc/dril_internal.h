@@ -198,4 +198,12 @@ int generic_pick_slabs(const GenericDims& d, int64_t count, int Gmax);   // slab
 void generic_ws_free(GenericWs& ws);
 hipError_t generic_select(int64_t n, const uint8_t* where, const float* src, float* dst, hipStream_t s);   // dst[i] = src[i] where where[i] != 0
 
+// device-array verbs of DRIL_ENV_EXTERNAL (dril_ext_device.hip).  ExtBounds: the ClampAdapter's table, one (low, high) per action dimension; low >= high = not clamped
+struct ExtBounds { float lo[64], hi[64]; };
+// act: E actions of the buffer row (i32 | f32 x A) -> raw (the same bits) and env (clamped for a Box when bounds != null); raw / env may be null
+hipError_t launch_ext_actions_out(const void* act, void* raw, void* env, int64_t E, int A, int discrete, const ExtBounds* bounds, hipStream_t s);
+// rew / flags / boot: row t of the buffer.  v_all: V(terminal_obs) of all E envs or null; a truncated env with v_all == null sets *err = 1
+hipError_t launch_ext_record(int E, const float* rewards, const uint8_t* terminated, const uint8_t* truncated, const float* v_all,
+                             float* rew, uint8_t* flags, float* boot, int* err, hipStream_t s);
+
 }  // namespace dril

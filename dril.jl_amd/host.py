@@ -419,6 +419,50 @@ def _agent_spaces(fn, h, D: int, A: int) -> dict:
     return rc, dict(obs_low=ol, obs_high=oh, action_low=al, action_high=ah, scaling=bool(on.value))
 
 
+_DEV_DTYPES = {"float32": (np.dtype(np.float32),), "int32": (np.dtype(np.int32),), "uint8": (np.dtype(np.uint8), np.dtype(np.bool_))}
+
+
+def _dev_ptr(name: str, a, shape: tuple, dtype: str, optional: bool = False):
+    """the device pointer behind `a`: an integer (a raw device pointer, taken as it is) or any object with `__cuda_array_interface__` (torch-ROCm tensors,
+    CuPy arrays), whose shape, dtype and C-contiguity are checked here — a ValueError names the argument before the library is called"""
+    if a is None:
+        if optional:
+            return None
+        raise ValueError(f"{name}: None, expected a device array of shape {shape} ({dtype})")
+    if isinstance(a, (int, np.integer)) and not isinstance(a, bool):
+        return C.c_void_p(int(a))
+    try:
+        cai = getattr(a, "__cuda_array_interface__", None)
+    except Exception:
+        cai = None
+    if cai is None:
+        raise ValueError(f"{name}: expected a device array (an object with __cuda_array_interface__) or an integer device pointer, got {type(a).__name__}; host arrays go to the verbs without `_device`")
+    got_shape, dt = tuple(int(x) for x in cai["shape"]), np.dtype(cai["typestr"])
+    if dt not in _DEV_DTYPES[dtype]:
+        raise ValueError(f"{name}: dtype {dt} where {dtype}{' / bool' if dtype == 'uint8' else ''} is expected")
+    if got_shape != tuple(shape):
+        hint = f": the layout is (n_envs, dim) = {tuple(shape)}, one row per env" if len(shape) == 2 and got_shape == tuple(shape)[::-1] and got_shape != tuple(shape) else ""
+        raise ValueError(f"{name}: shape {got_shape} where {tuple(shape)} is expected{hint}")
+    strides = cai.get("strides")
+    if strides is not None:
+        want, acc = [], dt.itemsize
+        for n in reversed(got_shape):
+            want.append(acc); acc *= n
+        if any(n > 1 and int(st) != w for n, st, w in zip(got_shape, strides, reversed(want))):
+            raise ValueError(f"{name}: not C-contiguous (strides {tuple(strides)}); pass a contiguous copy")
+    ptr = int(cai["data"][0])
+    if ptr == 0 and int(np.prod(got_shape)) > 0:
+        raise ValueError(f"{name}: null device pointer")
+    return C.c_void_p(ptr)
+
+
+def _stream_ptr(stream):
+    """a hipStream_t as an int, a callable returning one (`lambda: torch.cuda.current_stream().cuda_stream`), or None = the null stream"""
+    if callable(stream):
+        stream = stream()
+    return C.c_void_p(int(stream)) if stream else None
+
+
 @_normalize.normalize_verbs(lambda self, verb: getattr(self.lib, "dril_normalize_" + verb), "normalize_")
 class Handle:
     """Owns one dril_handle*; every method is a thin typed wrapper of one C entry point."""
@@ -640,6 +684,56 @@ class Handle:
 
     def ext_steps(self) -> int:
         return int(self.lib.dril_ext_steps(self._h))
+
+    # the same rollout over DEVICE arrays (dril_ext_*_device): integers (raw device pointers) or objects with __cuda_array_interface__; nothing is copied or allocated here
+    def _act_shape(self, n: int) -> tuple:
+        return (n,) if self.discrete else (n, self.A)
+
+    def ext_act_device(self, obs, raw_actions=None, env_actions=None, stream=None):
+        """obs (E, D) f32 on the device; raw_actions / env_actions: device OUTPUT arrays i32 (E,) | f32 (E, A), either may be None.  Enqueues and returns:
+        the outputs are ready for work enqueued on `stream` afterwards"""
+        at = "int32" if self.discrete else "float32"
+        args = (_dev_ptr("obs", obs, (self.E, self.D), "float32"), _dev_ptr("raw_actions", raw_actions, self._act_shape(self.E), at, True),
+                _dev_ptr("env_actions", env_actions, self._act_shape(self.E), at, True))
+        self._chk(self.lib.dril_ext_act_device(self._h, *args, _stream_ptr(stream)))
+
+    def ext_record_device(self, rewards, terminated, truncated, terminal_obs=None, stream=None):
+        """rewards f32 (E,), terminated / truncated u8 or bool (E,), terminal_obs f32 (E, D) or None = no env was truncated in this step"""
+        args = (_dev_ptr("rewards", rewards, (self.E,), "float32"), _dev_ptr("terminated", terminated, (self.E,), "uint8"), _dev_ptr("truncated", truncated, (self.E,), "uint8"),
+                _dev_ptr("terminal_obs", terminal_obs, (self.E, self.D), "float32", True))
+        self._chk(self.lib.dril_ext_record_device(self._h, *args, _stream_ptr(stream)))
+
+    def ext_finish_device(self, last_obs, stream=None):
+        o = _dev_ptr("last_obs", last_obs, (self.E, self.D), "float32")
+        self._chk(self.lib.dril_ext_finish_device(self._h, o, _stream_ptr(stream)))
+
+    def predict_actions_device(self, obs, deterministic: bool = False, raw_actions=None, env_actions=None, stream=None, batch: Optional[int] = None):
+        """dril_predict_actions on device arrays, the adapter applied in env_actions; `batch` is read from obs's shape (B, D) unless obs is a raw pointer"""
+        if batch is None:
+            cai = getattr(obs, "__cuda_array_interface__", None)
+            if cai is None or len(cai["shape"]) != 2:
+                raise ValueError("obs: expected a device array of shape (batch, obs_dim), or a raw pointer together with batch=")
+            batch = int(cai["shape"][0])
+        if raw_actions is None and env_actions is None:
+            raise ValueError("raw_actions / env_actions: at least one device output array is needed")
+        at = "int32" if self.discrete else "float32"
+        args = (_dev_ptr("obs", obs, (batch, self.D), "float32"), batch, int(deterministic), _dev_ptr("raw_actions", raw_actions, self._act_shape(batch), at, True),
+                _dev_ptr("env_actions", env_actions, self._act_shape(batch), at, True))
+        self._chk(self.lib.dril_predict_actions_device(self._h, *args, _stream_ptr(stream)))
+
+    def ext_set_action_bounds(self, low, high):
+        """the ClampAdapter's Box per action dimension (host arrays of A floats; both None: back to the config's scalar pair)"""
+        if low is None and high is None:
+            self._chk(self.lib.dril_ext_set_action_bounds(self._h, None, None)); return
+        lo, hi = np.ascontiguousarray(low, np.float32).ravel(), np.ascontiguousarray(high, np.float32).ravel()
+        if lo.size != self.A or hi.size != self.A:
+            raise ValueError(f"low / high: {lo.size} / {hi.size} values where action_dim = {self.A} are expected")
+        self._chk(self.lib.dril_ext_set_action_bounds(self._h, self._p(lo), self._p(hi)))
+
+    def ext_device_info(self) -> dict:
+        info = capi.DrilExtDeviceInfo()
+        self._chk(self.lib.dril_ext_device_info(self._h, C.byref(info)))
+        return dict(steps_device=info.steps_device, steps_host=info.steps_host, host_syncs=info.host_syncs, per_dim_bounds=bool(info.per_dim_bounds), launches=int(info.launches))
 
     def set_noise(self, noise: Optional[np.ndarray]):
         if noise is None:
@@ -1089,6 +1183,122 @@ def _host_rollout(h: Handle, env: HostParallelEnv, on_step=None):
     return h.N / max(time.perf_counter() - t0, 1e-12)
 
 
+def _default_empty(like):
+    """the `empty(shape, dtype)` factory of the array library `like` comes from: torch tensors and CuPy arrays are recognised"""
+    mod = type(like).__module__.split(".")[0]
+    if mod == "torch":
+        import torch
+        return lambda shape, dtype: torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
+    if mod == "cupy":
+        import cupy
+        return lambda shape, dtype: cupy.empty(tuple(shape), dtype=np.dtype(dtype))
+    raise ValueError(f"DeviceArrayParallelEnv: cannot allocate action arrays like {type(like).__name__}; pass empty=lambda shape, dtype: <a device array of your library>")
+
+
+def _to_host(a, stream) -> np.ndarray:
+    """a small device array (rewards, flags) as NumPy, for the episode accounting of evaluate_agent: the caller's stream is drained, then one blocking copy"""
+    cai = a.__cuda_array_interface__
+    out = np.empty(tuple(cai["shape"]), np.dtype(cai["typestr"]))
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamSynchronize.argtypes = [C.c_void_p]; hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    for rc in (hip.hipStreamSynchronize(_stream_ptr(stream)), hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(int(cai["data"][0])), out.nbytes, 2)):   # 2 = hipMemcpyDeviceToHost
+        if rc != 0:
+            raise DrilError(capi.ERR_HIP, f"copying a device array to the host failed with HIP status {rc}")
+    return out
+
+
+class DeviceArrayParallelEnv:
+    """The twin of HostParallelEnv for ONE batched env object whose arrays live on the DEVICE (a simulator in torch-ROCm / CuPy tensor ops, another HIP library):
+        n_envs, observation_space(), action_space(), reset_()
+        observe() -> (E, D) f32 device array
+        act_(actions) -> (rewards (E,) f32, terminated (E,), truncated (E,) u8 / bool, terminal_obs (E, D) f32 or None), all device arrays; finished envs reset inside
+                         act_ (as HostParallelEnv.act_ does), terminal_obs holds the pre-reset observation of the truncated envs (any other row may hold anything)
+    `actions` is the wrapper's own env-action array — i32 (E,) | f32 (E, A), the ClampAdapter applied on the device — allocated once through `empty(shape, dtype)`
+    (default: the library of the first observation).  `stream`: the hipStream_t the env's work runs on, an int or a callable returning one
+    (`lambda: torch.cuda.current_stream().cuda_stream`); None = the null stream.  collect_rollout_, train_ and evaluate_agent accept it; a rollout makes no host
+    wait before its last call (dril_ext_act_device / dril_ext_record_device / dril_ext_finish_device, docs/external_envs.md section 10)."""
+    kind = capi.ENV_EXTERNAL
+
+    def __init__(self, env, *, seed: int = 42, device: int = 0, stream=None, empty=None, profile_events: bool = False):
+        for name in ("n_envs", "observation_space", "action_space", "reset_", "observe", "act_"):
+            if not hasattr(env, name):
+                raise TypeError(f"DeviceArrayParallelEnv: the env has no `{name}`")
+        self.env, self.n_envs, self.seed, self.stream, self._empty = env, int(env.n_envs), seed, stream, empty
+        self._kw = dict(device=device, profile_events=profile_events)
+        self.handle: Optional[Handle] = None
+        self._bound_key = None
+        self._raw = self._env_actions = None
+        self._last_term = self._last_trunc = None
+
+    def bind(self, alg: PPO, layer: Optional[ActorCriticLayer] = None) -> Handle:
+        key = (tuple(sorted(asdict(alg).items())), None if layer is None else (tuple(layer.hidden_dims), layer.log_std_init, getattr(layer, "activation", "tanh")))
+        if self.handle is None or key != self._bound_key:
+            if self.handle is not None:
+                self.handle.close()
+            self.handle = h = Handle(make_config(self, self.n_envs, alg, layer, seed=self.seed, **self._kw))
+            asp = self.action_space()
+            if isinstance(asp, Box) and h.cfg.ext_action_low >= h.cfg.ext_action_high:   # per-dimension bounds: the ClampAdapter's table on the device
+                h.ext_set_action_bounds(np.asarray(asp.low, np.float32), np.asarray(asp.high, np.float32))
+            self._bound_key = key
+        return self.handle
+
+    def number_of_envs(self) -> int:
+        return self.n_envs
+
+    def observation_space(self):
+        return self.env.observation_space()
+
+    def action_space(self):
+        return self.env.action_space()
+
+    def reset_(self):
+        self.env.reset_()
+
+    def observe(self):
+        return self.env.observe()
+
+    def action_arrays(self, h: Handle, like):
+        """(raw, env) action arrays of the handle's action shape, allocated once"""
+        shape = (h.E,) if h.discrete else (h.E, h.A)
+        if self._raw is None or tuple(self._raw.__cuda_array_interface__["shape"]) != shape:
+            make = self._empty or _default_empty(like)
+            dt = np.int32 if h.discrete else np.float32
+            self._raw, self._env_actions = make(shape, dt), make(shape, dt)
+        return self._raw, self._env_actions
+
+    def act_(self, actions):
+        """-> (rewards, terminated, truncated, terminal_obs or None), device arrays, as the env's own act_ returns them"""
+        out = self.env.act_(actions)
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            n = len(out) if isinstance(out, (tuple, list)) else 1
+            raise ValueError(f"DeviceArrayParallelEnv: act_ must return (rewards, terminated, truncated, terminal_obs or None), got {n} value{'s' if n != 1 else ''}")
+        self._last_term, self._last_trunc = out[1], out[2]
+        return tuple(out)
+
+    def terminated(self):
+        return self._last_term
+
+    def truncated(self):
+        return self._last_trunc
+
+
+def _device_array_rollout(h: Handle, env: DeviceArrayParallelEnv, on_step=None):
+    """collect_trajectories (trajectory.jl:22-78) with env arrays and agent both on the device: every call enqueues and returns, the one host wait is
+    dril_ext_finish_device's.  -> fps, or None when an on_step callback stopped the collection"""
+    t0 = time.perf_counter()
+    new_obs = env.observe()                                                          # :32
+    raw, ea = env.action_arrays(h, new_obs)
+    for _ in range(h.T):
+        if on_step is not None and not on_step():
+            return None
+        h.ext_act_device(new_obs, raw, ea, env.stream)                               # get_action_and_values + to_env, :41-42
+        rew, term, trunc, tobs = env.act_(ea)                                        # :44
+        new_obs = env.observe()                                                      # :45
+        h.ext_record_device(rew, term, trunc, tobs, env.stream)                      # :46-61
+    h.ext_finish_device(new_obs, env.stream)                                         # :65-70 + compute_advantages! + returns
+    return h.N / max(time.perf_counter() - t0, 1e-12)
+
+
 
 def _stepwise_rollout(h: Handle, env, on_step=None):
     """collect_trajectories (trajectory.jl:22-78) over a DeviceParallelEnv through the step-granular env verbs — the path callbacks with an `on_step`
@@ -1217,7 +1427,7 @@ def collect_rollout_(buffer: RolloutBuffer, agent: Agent, alg: PPO, env: DeviceP
     """collect_rollout!(rollout_buffer, agent, alg, env) -> (fps, success), rollout_buffer.jl:46-90."""
     h = env.bind(alg, agent.layer)
     h.set_params(flatten_params(agent.train_state.parameters))
-    fps = _host_rollout(h, env) if isinstance(env, HostParallelEnv) else h.collect_rollout()
+    fps = _host_rollout(h, env) if isinstance(env, HostParallelEnv) else _device_array_rollout(h, env) if isinstance(env, DeviceArrayParallelEnv) else h.collect_rollout()
     buffer.observations = h.buffer(capi.BUF_OBSERVATIONS)
     acts = h.buffer(capi.BUF_ACTIONS)
     buffer.actions = acts.astype(np.int64) if h.discrete else acts  # eltype(Discrete{Int}) = Int64, spaces.jl:169
@@ -1276,6 +1486,8 @@ def train_(agent: Agent, env: DeviceParallelEnv, alg: PPO, max_steps: int, callb
             on_step = (lambda: all(c.on_step(loc) for c in step_hooks)) if step_hooks else None
             if isinstance(env, HostParallelEnv):
                 fps = _host_rollout(h, env, on_step)
+            elif isinstance(env, DeviceArrayParallelEnv):
+                fps = _device_array_rollout(h, env, on_step)
             else:
                 fps = _stepwise_rollout(h, env, on_step) if on_step else h.collect_rollout()  # ppo.jl:167; on_step hooks need the step-granular path
             if fps is None:
@@ -1349,7 +1561,7 @@ def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 
     (Handle.evaluate_agent_device, docs/evaluation.md); the default resets the env and lets its episodes enter the monitor's window, as before."""
     h = env.bind(agent.alg, agent.layer)
     h.set_params(flatten_params(agent.train_state.parameters))
-    if isolated and isinstance(env, HostParallelEnv):
+    if isolated and isinstance(env, (HostParallelEnv, DeviceArrayParallelEnv)):
         raise NotImplementedError("evaluate_agent(isolated=True): host envs (HostParallelEnv) live with the caller, who keeps a second set of envs for evaluation; the device verb steps device envs")
     if isinstance(env, HostParallelEnv):       # the reference loop on the caller's envs, predict_actions on the device (evaluation.jl:86-125)
         asp = env.action_space()
@@ -1364,6 +1576,25 @@ def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 
             cur_r += rew; cur_l += 1
             obs = np.stack(env.observe())
             for i in np.nonzero(term | trunc)[0]:
+                if len(er) < n_eval_episodes:
+                    er.append(float(cur_r[i])); el.append(int(cur_l[i]))
+                    cur_r[i] = 0; cur_l[i] = 0
+        er, el = np.asarray(er, np.float32), np.asarray(el, np.int64)
+        sd = lambda x: float(np.std(x, ddof=1)) if len(x) > 1 else float("nan")
+        stats = {"mean_reward": float(er.mean()), "std_reward": sd(er), "mean_length": float(el.mean()), "std_length": sd(el)}
+    elif isinstance(env, DeviceArrayParallelEnv):   # the same loop; observations and actions stay on the device, only rewards and flags (E values each) come to the host for the accounting
+        er, el = [], []
+        cur_r, cur_l = np.zeros(env.n_envs, np.float32), np.zeros(env.n_envs, np.int64)
+        env.reset_()
+        obs = env.observe()
+        _, ea = env.action_arrays(h, obs)
+        while len(er) < n_eval_episodes:
+            h.predict_actions_device(obs, deterministic, None, ea, env.stream)
+            rew, term, trunc, _ = env.act_(ea)
+            obs = env.observe()
+            rew, done = _to_host(rew, env.stream), _to_host(term, env.stream).astype(bool) | _to_host(trunc, env.stream).astype(bool)
+            cur_r += rew; cur_l += 1
+            for i in np.nonzero(done)[0]:
                 if len(er) < n_eval_episodes:
                     er.append(float(cur_r[i])); el.append(int(cur_l[i]))
                     cur_r[i] = 0; cur_l[i] = 0

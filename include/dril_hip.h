@@ -389,6 +389,45 @@ int32_t dril_ext_finish(dril_handle* h, const float* last_obs);
 /* env steps recorded since the last dril_ext_finish (0 .. n_steps) */
 int32_t dril_ext_steps(const dril_handle* h);
 
+/* ---- the same rollout over envs whose arrays already live on the DEVICE (a batched simulator in PyTorch-ROCm / CuPy, another HIP library of the process) ----
+ * The *_device verbs take DEVICE memory of the handle's device in the layouts of the host verbs: obs / terminal_obs / last_obs f32 (D x E) column-major,
+ * actions i32 (E) | f32 (A x E), rewards f32 (E), flags u8 (E).  They share the host verbs' state machine (a rollout may mix both, step by step) and fill the
+ * same buffer: observations, raw actions, values and log-probabilities of a step are the host verb's bits.
+ * caller_stream: the hipStream_t on which the caller produced the inputs and will consume the outputs (NULL = the null stream).  On entry the library records an
+ * event on it and makes the handle's stream wait; before returning it records an event on its own stream and makes caller_stream wait for that: the caller may
+ * enqueue its env step on the actions at once.  dril_ext_act_device and dril_ext_record_device never wait on the host — no stream, event or device
+ * synchronisation and no blocking copy, truncation steps included; dril_ext_finish_device enqueues V(last_obs) and GAE and drains ONCE: the one
+ * synchronisation of a rollout, and where deferred errors surface.
+ *   act:    d_raw_actions (pre-adapter, as stored) and d_env_actions (ClampAdapter applied on the device: per dimension after dril_ext_set_action_bounds, else
+ *           the scalar ext_action_low / ext_action_high; low >= high = not clamped; Discrete: equal to the raw actions); either may be NULL.
+ *   record: d_terminal_obs != NULL: V of ALL E columns is computed (one critic forward) and kept where the env was truncated; the other columns may hold
+ *           anything, finite or not, but must be readable memory of E x D floats.  d_terminal_obs == NULL states that no env was truncated in this step and
+ *           skips that forward; a truncated flag set all the same raises a sticky error on the device, which dril_ext_finish_device returns as
+ *           DRIL_ERR_INVALID_ARG after its drain — the rollout then counts as not collected (dril_ext_steps == 0).
+ * Statuses: those of the host verbs for null pointers and call order; DRIL_ERR_INVALID_ARG, before anything is enqueued, for a pointer that
+ * hipPointerGetAttributes does not report as accessible from the handle's device (or whose allocation is shorter than the array); DRIL_ERR_UNSUPPORTED on a
+ * handle that is not DRIL_ENV_EXTERNAL. */
+int32_t dril_ext_act_device(dril_handle* h, const float* d_obs, void* d_raw_actions, void* d_env_actions, void* caller_stream);
+int32_t dril_ext_record_device(dril_handle* h, const float* d_rewards, const uint8_t* d_terminated, const uint8_t* d_truncated, const float* d_terminal_obs, void* caller_stream);
+int32_t dril_ext_finish_device(dril_handle* h, const float* d_last_obs, void* caller_stream);
+/* dril_predict_actions on device arrays with the adapter applied (evaluate_agent over such an env): d_obs f32 (D x batch); noise from the handle's stream, as
+ * dril_predict_actions with noise == NULL; d_raw_actions / d_env_actions as in dril_ext_act_device (not both NULL).  Ordered on caller_stream like the verbs above;
+ * no host wait except when a larger batch than any before makes the library grow its scratch arrays. */
+int32_t dril_predict_actions_device(dril_handle* h, const float* d_obs, int64_t batch, int32_t deterministic, void* d_raw_actions, void* d_env_actions, void* caller_stream);
+/* the ClampAdapter's Box per dimension: low / high are HOST arrays of action_dim floats (both NULL: back to the scalar pair of the config).  Honoured by
+ * dril_ext_act as well from then on.  DRIL_ERR_INVALID_ARG for a Discrete action space or one NULL pointer, DRIL_ERR_UNSUPPORTED on a handle that is not external */
+int32_t dril_ext_set_action_bounds(dril_handle* h, const float* low, const float* high);
+/* what the current (or, between rollouts, the last) rollout of an external handle did.  A struct tag only: the verb below has the same name */
+struct dril_ext_device_info {
+    int32_t steps_device;      /* env steps recorded through dril_ext_record_device */
+    int32_t steps_host;        /* env steps recorded through dril_ext_record */
+    int32_t host_syncs;        /* host-side waits the library made inside act / record calls: 0 for the device verbs */
+    int32_t per_dim_bounds;    /* 1 after dril_ext_set_action_bounds */
+    int64_t launches;          /* kernel launches enqueued by act / record / finish calls */
+    int32_t reserved[4];
+};
+int32_t dril_ext_device_info(const dril_handle* h, struct dril_ext_device_info* out);
+
 /* ---- rollout --------------------------------------------------------------- */
 /* collect_rollout!(buffer, agent, alg, env): rollout_buffer.jl:46-90 =
  * collect_trajectories trajectory.jl:22-78 + compute_advantages! :80-102 + returns :87.
