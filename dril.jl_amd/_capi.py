@@ -120,6 +120,12 @@ class DrilSacStats(C.Structure):
                 ("entropy_coefficient", C.c_float), ("grad_norm", C.c_float), ("has_entropy_loss", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DrilSacExtDeviceInfo(C.Structure):
+    """struct dril_sac_ext_device_info, include/dril_sac.h"""
+    _fields_ = [("steps_device", C.c_int64), ("steps_host", C.c_int64), ("host_syncs", C.c_int64), ("flushes", C.c_int64), ("launches", C.c_int64),
+                ("pending_updates", C.c_int32), ("pending_capacity", C.c_int32), ("per_dim_bounds", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class DrilNormalizeConfig(C.Structure):
     """struct dril_normalize_config (include/dril_hip.h) and struct dril_sac_normalize_config (include/dril_sac.h): the keywords of NormalizeWrapperEnv,
     normalizeWrapperEnv.jl:71-80, in one layout for both verb families"""
@@ -140,6 +146,7 @@ class DrilPolicyDesc(C.Structure):
 POLICY_ABI_VERSION = 1
 POLICY_CATEGORICAL, POLICY_DIAG_GAUSSIAN, POLICY_SQUASHED_DIAG_GAUSSIAN = 0, 1, 2
 SAC_ABI_VERSION = 1
+SAC_PENDING_CAPACITY = 4096      # DRIL_SAC_PENDING_CAPACITY, include/dril_sac.h: statistics rows dril_sac_update_enqueue may leave pending
 (RB_OBSERVATIONS, RB_ACTIONS, RB_REWARDS, RB_TERMINATED, RB_TRUNCATED, RB_NEXT_OBSERVATIONS) = range(6)
 
 
@@ -293,6 +300,13 @@ _SAC_SIG = {
     "collect_rollout": (C.c_int32, [_P, C.c_int32, C.c_int32, _PD]),
     "collect_continue": (C.c_int32, [_P, C.c_int32, C.c_int32, _PD]),
     "ext_push": (C.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "ext_act_device": (C.c_int32, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    "ext_push_device": (C.c_int32, [_P, _P, _P, _P, _P, _P, _P]),
+    "predict_actions_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "update_enqueue": (C.c_int32, [_P, C.c_int32]),
+    "flush": (C.c_int32, [_P, _P, C.c_int64, _PI64]),
+    "ext_set_action_bounds": (C.c_int32, [_P, _P, _P]),
+    "ext_device_info": (C.c_int32, [_P, C.POINTER(DrilSacExtDeviceInfo)]),
     "debug_set_collect_noise": (C.c_int32, [_P, _P, C.c_size_t]),
     "replay_size": (C.c_int64, [_P]),
     "replay_capacity": (C.c_int64, [_P]),

@@ -20,6 +20,7 @@
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper on plug-ins shares with the SAC handle's (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_policy_internal.h"   // dril_policy_from_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in kind or a device env plug-in), shared with the SAC handle
+#include "dril_ext_stream.h"  // the pointer rule and the stream hand-over of the device-array verbs, shared with the SAC handle
 
 using namespace dril;
 
@@ -1342,27 +1343,12 @@ int ext_finish_drain(dril_handle* h, const char* verb) {
 }
 // an argument of a device verb must be memory the handle's device can address, long enough for the array: a host pointer handed to a kernel is a GPU fault
 int ext_check_ptr(dril_handle* h, const char* verb, const char* name, const void* p, size_t bytes) {
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    const bool ok = e == hipSuccess && ((at.type == hipMemoryTypeDevice && at.device == h->cfg.device) || at.type == hipMemoryTypeManaged || (at.type == hipMemoryTypeHost && at.devicePointer != nullptr));
-    if (!ok) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": " + name + " is not memory of device " + std::to_string(h->cfg.device) + " (the *_device verbs take device arrays; host arrays go to the verbs without the suffix)");
-    if (at.type == hipMemoryTypeDevice) {
-        hipDeviceptr_t base = nullptr; size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) (void)hipGetLastError();
-        else if ((const char*)p + bytes > (const char*)base + size) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": the allocation behind " + name + " ends before the " + std::to_string(bytes) + " bytes of the array");
-    }
-    return DRIL_OK;
+    const std::string msg = ext_ptr_problem(h->cfg.device, verb, name, p, bytes);         // dril_ext_stream.h: the rule the SAC handle's device verbs share
+    return msg.empty() ? DRIL_OK : fail(h, DRIL_ERR_INVALID_ARG, msg);
 }
 // the handle's stream takes over from the caller's stream / hands back to it: two events per handle, no host wait
-int ext_stream_enter(dril_handle* h, void* caller_stream) {
-    HIPCHK(h, hipEventRecord(h->ext_ev_in, (hipStream_t)caller_stream)); HIPCHK(h, hipStreamWaitEvent(h->stream, h->ext_ev_in, 0));
-    return DRIL_OK;
-}
-int ext_stream_leave(dril_handle* h, void* caller_stream) {
-    HIPCHK(h, hipEventRecord(h->ext_ev_out, h->stream)); HIPCHK(h, hipStreamWaitEvent((hipStream_t)caller_stream, h->ext_ev_out, 0));
-    return DRIL_OK;
-}
+int ext_stream_enter(dril_handle* h, void* caller_stream) { HIPCHK(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream)); return DRIL_OK; }
+int ext_stream_leave(dril_handle* h, void* caller_stream) { HIPCHK(h, ext_stream_give(h->stream, h->ext_ev_out, caller_stream)); return DRIL_OK; }
 // the adapter's table of a Box handle as the actions-out kernel takes it (null: Discrete, or nothing to clamp)
 const ExtBounds* ext_bounds_for(dril_handle* h, ExtBounds& scalar) {
     if (h->discrete) return nullptr;

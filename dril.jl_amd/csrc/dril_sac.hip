@@ -34,6 +34,7 @@
 #include "dril_sac_eval.h"
 #include "dril_env_side.h"     // DeviceEnvs: the envs this handle steps on the device (a built-in Box kind or a device env plug-in), shared with the PPO handle
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
+#include "dril_ext_stream.h"   // the pointer rule and the stream hand-over of the device-array verbs, shared with the PPO handle
 
 using namespace dril;
 
@@ -1223,6 +1224,69 @@ __global__ void sac_noise_fill_kernel(int n, int A, SacRng rng, float* out) {
     for (int a = 0; a < A; ++a) out[i * A + a] = sac_noise(rng, 8, i, a);
 }
 
+// ---- the device-array verbs of a DRIL_ENV_EXTERNAL handle (dril_sac_ext_act_device / dril_sac_predict_actions_device / dril_sac_ext_push_device) ------------
+// Head of the device act, one launch behind the actor forward: the noise draw (the words sac_noise_fill_kernel would have written to a buffer, computed in the
+// thread that uses them), the squashed sample (squashed_sample_logp: sac_squash_eval_kernel's own expression, so its bits), TanhScaleAdapter — or, mode 2, the
+// uniform branch rand(action_space) — and the writes into the caller's arrays and the handle's pending-action rows.  One thread per row: A <= kMaxA floats per
+// thread, n x A <= a few hundred KB in all; the launch is latency-bound, the point is that it is ONE launch and no copy.
+// rand(rng, Box) of one dimension as __fadd_rn(low, __fmul_rn(u, __fsub_rn(high, low))): three float32 operations, each rounded on its own, which NumPy float32
+// restates to the bit.  Spelled with plain operators under contract(off): this toolchain's __fmul_rn / __fadd_rn ARE plain operators compiled with contraction
+// allowed, and the pair became one v_fmac_f32 (a single rounding) when the intrinsics were used
+__device__ __forceinline__ float ext_rand_box_rn(float u, float lo, float hi) {
+#pragma clang fp contract(off)
+    const float w = hi - lo;
+    const float p = u * w;
+    return lo + p;
+}
+struct ExtHeadArgs {
+    int n, A, mode;                                   // mode 0: sample, 1: deterministic (tanh(mean)), 2: rand(action_space)
+    const float* mu; const float* log_std; const float* noise;   // noise null: the handle's stream (rng)
+    SacRng rng; const float* low; const float* high;
+    float* stored; float* envact; float* keep;        // the caller's arrays (either may be null) and the handle's e_raw (null: predict only)
+};
+__global__ __launch_bounds__(256) void sac_ext_head_kernel(ExtHeadArgs g) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.n) return;
+    const int A = g.A;
+    float nz[kMaxA], a_[kMaxA], ev[kMaxA];
+    if (g.mode == 2) {
+        for (int a = 0; a < A; ++a) {
+            float u;
+            if (g.noise) u = g.noise[(size_t)i * A + a];
+            else {                                                                                // the uniform of the word pair sac_noise(rng, 8, i, a) turns into a normal
+                uint32_t o[4];
+                philox4x32_10((uint32_t)g.rng.key, (uint32_t)(g.rng.key >> 32), (uint32_t)g.rng.u, (uint32_t)(g.rng.u >> 32), 8u, (uint32_t)(i * 4 + a / 2), o);
+                u = u01_f32((a & 1) ? o[2] : o[0]);
+            }
+            const float lo = g.low[a], hi = g.high[a];
+            a_[a] = ext_rand_box_rn(u, lo, hi);
+            ev[a] = a_[a];
+        }
+    } else {
+        float ls[kMaxA], gg[kMaxA];
+        for (int a = 0; a < A; ++a) { ls[a] = g.log_std[a]; nz[a] = g.mode == 1 ? 0.f : (g.noise ? g.noise[(size_t)i * A + a] : sac_noise(g.rng, 8, i, a)); }
+        (void)squashed_sample_logp(g.mu + (size_t)i * A, ls, nz, A, a_, gg);
+        for (int a = 0; a < A; ++a) ev[a] = sac_to_env(a_[a], g.low[a], g.high[a]);
+    }
+    for (int a = 0; a < A; ++a) {
+        const size_t k = (size_t)i * A + a;
+        if (g.keep) g.keep[k] = a_[a];
+        if (g.stored) g.stored[k] = a_[a];
+        if (g.envact) g.envact[k] = ev[a];
+    }
+}
+// push! of the pending step from the caller's arrays: sac_push_block's flat (env, dim) walk over kPushEnvsPerBlock envs per workgroup.  A null tobs states "no env
+// was truncated": the block then reads nobs in its place, and a truncated flag set all the same raises the sticky error word (a plain vector store of an int, as
+// ext_record_kernel's; dril_sac_flush reads it after its drain)
+__global__ __launch_bounds__(256) void sac_ext_push_kernel(PushArgs g, int* err) {
+    const int e0 = blockIdx.x * kPushEnvsPerBlock, n = min(kPushEnvsPerBlock, g.E - e0);            // grid = ceil(E / kPushEnvsPerBlock): n >= 1
+    if (!g.tobs) {
+        if ((int)threadIdx.x < n && g.trunc[e0 + threadIdx.x]) *err = 1;
+        g.tobs = g.nobs;
+    }
+    sac_push_block(g, e0, n);
+}
+
 }  // namespace
 
 // =================================================================================================================
@@ -1272,6 +1336,13 @@ struct dril_sac_handle {
     // observation of the envs' present state once nz_raw_valid
     NormWrap nz; bool nz_raw_valid = false;
     float *nz_returns = nullptr, *nz_old_obs = nullptr, *nz_old_rew = nullptr;
+    // device-array verbs of an external handle (dril_sac_ext_*_device, dril_sac_update_enqueue, dril_sac_flush): the two hand-over events, the sticky error word and
+    // its pinned host copy, the pending statistics table (DRIL_SAC_PENDING_CAPACITY rows, allocated at create) + its squared-gradient partials, what a flush has to free, and the counters of the info struct
+    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; int* ext_err = nullptr; int* ext_err_host = nullptr;
+    bool ext_acted = false, ext_bounds_set = false, in_device_verb = false;
+    int64_t fwd_launches = 0;                        // kernels enqueued through gemm / gemm_pair / the elementwise first layer since create: what `launches` of the info struct is counted from
+    float* pend_stats = nullptr; double* pend_ssq = nullptr; int pend_n = 0; std::vector<void*> pend_free;
+    int64_t ext_steps_dev = 0, ext_steps_host = 0, ext_syncs = 0, ext_flushes = 0, ext_launches = 0;
     // injected inputs (tests)
     float* collect_noise = nullptr; size_t collect_noise_count = 0;
     int inj_updates = 0; long long* inj_idx = nullptr; float *inj_ne = nullptr, *inj_nn = nullptr, *inj_np = nullptr;
@@ -1299,11 +1370,11 @@ template <typename T> hipError_t smalloc(T** p, size_t n) {
 }
 int round4(int x) { return (x + 3) & ~3; }
 int gemm_pair(dril_sac_handle* h, GemmArgs a, int Za, GemmArgs b, int Zb) {
-    SHIP(h, launch_gemm_pair(a, Za, b, Zb, h->stream));
+    SHIP(h, launch_gemm_pair(a, Za, b, Zb, h->stream)); h->fwd_launches += 1;
     return DRIL_OK;
 }
 int gemm(dril_sac_handle* h, GemmArgs g, int Z) {
-    SHIP(h, launch_gemm(g, Z, h->stream));
+    SHIP(h, launch_gemm(g, Z, h->stream)); h->fwd_launches += 1;
     return DRIL_OK;
 }
 
@@ -1317,7 +1388,7 @@ int net_forward(dril_sac_handle* h, const float* P, NetOff off, long long zP, in
     const bool elem_l1 = !first_done && h->fused_fwd && Z == 1 && in <= 4 && ldx == in && n >= 1024 && H1 % 2 == 0;
     if (elem_l1) {
         CollectL1Args l1{n, in, H1, h->cfg.activation ? 1 : 0, X, P + off.w1, P + off.b1, b.h1, nullptr, nullptr, 0, (n + 7) / 8, nullptr, 0, nullptr, nullptr, 0};
-        hipLaunchKernelGGL(sac_collect_l1_kernel, dim3((n + 7) / 8), dim3(256), 0, h->stream, l1);
+        hipLaunchKernelGGL(sac_collect_l1_kernel, dim3((n + 7) / 8), dim3(256), 0, h->stream, l1); h->fwd_launches += 1;
     }
     if (!first_done && !elem_l1) {
     g.A = P + off.w1; g.sAm = 1; g.sAk = H1; g.zA = zP; g.B = X; g.sBk = 1; g.sBn = ldx; g.zB = zX; g.zdivB = zdivX;
@@ -1367,7 +1438,7 @@ int net_backward(dril_sac_handle* h, const float* P, NetOff off, long long zP, i
 NetBufs actor_bufs(dril_sac_handle* h) { return NetBufs{h->ah1, h->ah2, h->mu, 0, 0, 0}; }
 NetBufs q_bufs(dril_sac_handle* h, float* h1, float* h2, float* out) { return NetBufs{h1, h2, out, (long long)h->nq * h->H1, (long long)h->nq, (long long)h->nq * h->H2}; }
 
-int ssync(dril_sac_handle* h) { SHIP(h, hipStreamSynchronize(h->stream)); return DRIL_OK; }
+int ssync(dril_sac_handle* h) { if (h->in_device_verb) h->ext_syncs += 1; SHIP(h, hipStreamSynchronize(h->stream)); return DRIL_OK; }   // (ext_syncs: dril_sac_ext_device_info.host_syncs — a wait inside a sync-free verb is a bug it would show)
 
 int adam_range(dril_sac_handle* h, int lo, int n, float* grads, const float* bt, double* ssq, int blocks, FirstLayerOpt fl = FirstLayerOpt{}) {
     AdamRangeArgs a{h->params + lo, h->adam_m + lo, h->adam_v + lo, grads ? grads + lo : nullptr, n, h->cfg.learning_rate, h->cfg.adam_beta1,
@@ -1378,8 +1449,8 @@ int adam_range(dril_sac_handle* h, int lo, int n, float* grads, const float* bt,
 }
 
 // one update!(agent, alg, batch): sac.jl:299-404.  `slot` = index into the injected batches (-1 = Philox), `out` = device stats row
-int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long* stamp = nullptr) {
-    double* ssq_row = h->ssq_rows + (size_t)((out - h->stats_out) / 8) * (h->adam_blocks_c + h->end_blocks);   // this update's squared-gradient partials: [critic Adam blocks | end blocks]
+int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long* stamp = nullptr, double* ssq_row_in = nullptr) {
+    double* ssq_row = ssq_row_in ? ssq_row_in : h->ssq_rows + (size_t)((out - h->stats_out) / 8) * (h->adam_blocks_c + h->end_blocks);   // this update's squared-gradient partials: [critic Adam blocks | end blocks] (ssq_row_in: a row of the pending table, dril_sac_update_enqueue)
     const int B = h->cfg.batch_size, D = h->D, A = h->A, W = D + A;
     const SacRng rng{h->cfg.seed ^ 0x5ac5ac5ac5ac5ac5ull, h->update_counter};
     GatherArgs ga{B, D, A, h->cap, h->head, h->size, h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term,
@@ -1712,12 +1783,12 @@ void fill_stats(const dril_sac_handle* h, const float* rows, int n, dril_sac_sta
     }
 }
 // the statistics rows of the last n gradient steps (stream drained): device rows + the squared-gradient partials summed here
-int fetch_stats(dril_sac_handle* h, int n, dril_sac_stats* out) {
+int fetch_stats(dril_sac_handle* h, int n, dril_sac_stats* out, const float* rows_dev = nullptr, const double* ssq_dev = nullptr) {   // (rows_dev / ssq_dev: the pending table of dril_sac_update_enqueue; null: the table of dril_sac_update)
     std::vector<float> rows((size_t)n * 8);
-    SHIP(h, hipMemcpy(rows.data(), h->stats_out, rows.size() * 4, hipMemcpyDeviceToHost));
+    SHIP(h, hipMemcpy(rows.data(), rows_dev ? rows_dev : h->stats_out, rows.size() * 4, hipMemcpyDeviceToHost));
     const int nb = h->adam_blocks_c + h->end_blocks;
     std::vector<double> ssq((size_t)n * nb);
-    SHIP(h, hipMemcpy(ssq.data(), h->ssq_rows, ssq.size() * 8, hipMemcpyDeviceToHost));
+    SHIP(h, hipMemcpy(ssq.data(), ssq_dev ? ssq_dev : h->ssq_rows, ssq.size() * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < n; ++k) { double t = 0; for (int b = 0; b < nb; ++b) t += ssq[(size_t)k * nb + b]; rows[(size_t)k * 8 + 5] = (float)sqrt(t); }   // grad_norm, sac.jl:393 (index order: deterministic)
     fill_stats(h, rows.data(), n, out);
     return DRIL_OK;
@@ -1845,6 +1916,10 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
     for (void* p : mon_eval) if (p) hipFree(p);
     normalize_free(h);
     if (h->ev_counter_host) hipHostFree(h->ev_counter_host);
+    for (void* p : h->pend_free) hipFree(p);
+    if (h->pend_stats) hipFree(h->pend_stats); if (h->pend_ssq) hipFree(h->pend_ssq); if (h->ext_err) hipFree(h->ext_err);
+    if (h->ext_err_host) hipHostFree(h->ext_err_host);
+    if (h->ext_ev_in) hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) hipEventDestroy(h->ext_ev_out);
     if (h->stream) hipStreamDestroy(h->stream);
     h->env.release();
     delete h;
@@ -1992,6 +2067,12 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     CHK(smalloc(&h->a_pi, nq * A)); CHK(smalloc(&h->g_pi, nq * A)); CHK(smalloc(&h->lp_pi, nq)); CHK(smalloc(&h->b_term, nq));
     CHK(smalloc(&h->s_in, nm * D)); CHK(smalloc(&h->s_act, nm * A)); CHK(smalloc(&h->s_noise, nm * A)); CHK(smalloc(&h->s_out, nm * A)); CHK(smalloc(&h->s_out2, nm * A));
     CHK(hipEventCreate(&h->ev_a)); CHK(hipEventCreate(&h->ev_b));
+    if (ext) {                                                                         // the device-array verbs: hand-over events and the sticky error word and the pending statistics table
+        CHK(hipEventCreateWithFlags(&h->ext_ev_in, hipEventDisableTiming)); CHK(hipEventCreateWithFlags(&h->ext_ev_out, hipEventDisableTiming));
+        CHK(smalloc(&h->ext_err, 1)); CHK(hipHostMalloc((void**)&h->ext_err_host, 4)); *h->ext_err_host = 0;
+        // the pending statistics table of dril_sac_update_enqueue: allocated HERE, not on first use — an allocation and its fill would be a host wait inside a sync-free verb
+        CHK(smalloc(&h->pend_stats, (size_t)DRIL_SAC_PENDING_CAPACITY * 8)); CHK(smalloc(&h->pend_ssq, (size_t)DRIL_SAC_PENDING_CAPACITY * (h->adam_blocks_c + h->end_blocks)));
+    }
 #undef CHK
     const SacScalars sc0{logf(cfg->ent_coef_init), 0.f, 0.f, cfg->ent_coef_init};                   // init_entropy_coefficient sac.jl:207-213
     if (hipMemcpy(h->sc, &sc0, sizeof(sc0), hipMemcpyHostToDevice) != hipSuccess) { dril_sac_destroy(h); return sfail(nullptr, DRIL_ERR_HIP, "hipMemcpy(log_ent_coef)"); }
@@ -2170,6 +2251,7 @@ DRIL_EXPORT int32_t dril_sac_ext_push(dril_sac_handle* h, const float* obs, cons
     if (h->env.module) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the env of a device env plug-in (DRIL_ENV_MODULE) is on the device, not on the host: dril_sac_collect_rollout steps it");
     if (!h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the handle was not created with DRIL_ENV_EXTERNAL");
     if (!obs || !stored_actions || !rewards || !terminated || !truncated || !next_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: null pointer");
+    if (h->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: a dril_sac_ext_act_device step is pending; dril_sac_ext_push_device completes it");
     const size_t E = h->cfg.n_envs, D = h->D, A = h->A;
     bool any_trunc = false; for (size_t e = 0; e < E; ++e) any_trunc = any_trunc || truncated[e] != 0;
     if (any_trunc && !terminal_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: truncated envs need terminal_obs");
@@ -2187,7 +2269,176 @@ DRIL_EXPORT int32_t dril_sac_ext_push(dril_sac_handle* h, const float* obs, cons
     SHIP(h, hipGetLastError());
     const long long over = h->size + (long long)E - h->cap;                                       // CircularBuffer: overwrite the oldest
     if (over > 0) { h->head = (h->head + over) % h->cap; h->size = h->cap; } else h->size += (long long)E;
+    h->ext_steps_host += 1;
     return ssync(h);                                                                              // the caller's arrays are pageable host memory: drain before returning
+}
+
+
+// ---- the same loop on DEVICE arrays: nothing below waits on the host except dril_sac_flush (include/dril_sac.h) --------------------------------------------
+namespace {
+constexpr int kPendingCap = DRIL_SAC_PENDING_CAPACITY;
+#define S_EXTERNAL_ONLY(h, verb) do { if (!(h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, verb ": the handle was not created with DRIL_ENV_EXTERNAL"); } while (0)
+// a wait inside the scope of one of these is counted (ssync): dril_sac_ext_device_info.host_syncs
+struct DeviceVerbScope { dril_sac_handle* h; explicit DeviceVerbScope(dril_sac_handle* h_) : h(h_) { h->in_device_verb = true; } ~DeviceVerbScope() { h->in_device_verb = false; } };
+// once the handle's stream has taken over from the caller's, EVERY way out of the verb hands it back: a step that fails half-way still leaves the caller's stream
+// ordered behind what was already enqueued.  give() is the successful path (its status is the verb's); the destructor covers the early returns
+struct StreamHandOver {
+    dril_sac_handle* h; void* caller; bool given = false;
+    StreamHandOver(dril_sac_handle* h_, void* caller_) : h(h_), caller(caller_) {}
+    hipError_t give() { given = true; return ext_stream_give(h->stream, h->ext_ev_out, caller); }
+    ~StreamHandOver() { if (!given && ext_stream_give(h->stream, h->ext_ev_out, caller) != hipSuccess) (void)hipGetLastError(); }
+};
+int sac_check_ptr(dril_sac_handle* h, const char* verb, const char* name, const void* p, size_t bytes) {
+    const std::string msg = ext_ptr_problem(h->cfg.device, verb, name, p, bytes);
+    return msg.empty() ? DRIL_OK : sfail(h, DRIL_ERR_INVALID_ARG, msg);
+}
+// actor means of n rows already in `x` (device), then the head: net_forward is the call dril_sac_predict_actions makes (actor_chunk), so the means are its bits
+int actor_device_rows(dril_sac_handle* h, const float* x, int n, int mode, const float* d_noise, float* stored, float* envact, float* keep) {
+    if (mode != 2) { const int64_t l0 = h->fwd_launches; SDO(net_forward(h, h->params, h->actor, 0, h->D, h->A, x, h->D, 0, n, actor_bufs(h), 1)); h->ext_launches += h->fwd_launches - l0; }
+    SacRng rng{0, 0};
+    if (mode != 1 && !d_noise) rng = SacRng{h->cfg.seed ^ 0x0b5e55edull, h->aux_counter++};       // the handle's stream: one counter per chunk, as actor_chunk (taken once the forward is enqueued: a failed call leaves the stream's position alone)
+    ExtHeadArgs g{n, h->A, mode, h->mu, h->params + h->log_std_off, d_noise, rng, h->act_bounds, h->act_bounds + kMaxA, stored, envact, keep};
+    hipLaunchKernelGGL(sac_ext_head_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, g);
+    SHIP(h, hipGetLastError());
+    h->ext_launches += 1;
+    return DRIL_OK;
+}
+}  // namespace
+DRIL_EXPORT int32_t dril_sac_ext_act_device(dril_sac_handle* h, const float* d_obs, int32_t use_random_actions, const float* d_noise, float* d_stored_actions,
+                                            float* d_env_actions, void* caller_stream) {
+    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_ext_act_device");
+    if (!d_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_act_device: null obs");
+    if (h->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_act_device: the previous step has no dril_sac_ext_push_device yet");
+    const size_t E = h->cfg.n_envs, D = h->D, A = h->A;
+    SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_obs", d_obs, E * D * 4));
+    if (d_noise) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_noise", d_noise, E * A * 4));
+    if (d_stored_actions) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_stored_actions", d_stored_actions, E * A * 4));
+    if (d_env_actions) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_env_actions", d_env_actions, E * A * 4));
+    DeviceVerbScope scope(h);
+    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
+    StreamHandOver back(h, caller_stream);
+    SHIP(h, hipMemcpyAsync(h->obs_cur, d_obs, E * D * 4, hipMemcpyDeviceToDevice, h->stream));     // the pending step's observation; the forward reads it from here
+    h->ext_launches += 1;
+    SDO(actor_device_rows(h, h->obs_cur, (int)E, use_random_actions ? 2 : 0, d_noise, d_stored_actions, d_env_actions, h->e_raw));
+    SHIP(h, back.give());
+    h->ext_acted = true;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_predict_actions_device(dril_sac_handle* h, const float* d_obs, int64_t batch, int32_t deterministic, const float* d_noise,
+                                                    float* d_raw_actions, float* d_env_actions, void* caller_stream) {
+    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_predict_actions_device");
+    if (!d_obs || batch < 1) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_predict_actions_device: null obs or batch < 1");
+    if (!d_raw_actions && !d_env_actions) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_predict_actions_device: null actions");
+    const size_t B = (size_t)batch, D = h->D, A = h->A;
+    SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_obs", d_obs, B * D * 4));
+    if (d_noise) SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_noise", d_noise, B * A * 4));
+    if (d_raw_actions) SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_raw_actions", d_raw_actions, B * A * 4));
+    if (d_env_actions) SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_env_actions", d_env_actions, B * A * 4));
+    DeviceVerbScope scope(h);
+    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
+    StreamHandOver back(h, caller_stream);
+    for (int64_t o = 0; o < batch; o += h->nmax) {                                                 // chunks of nmax rows, as the host verb: stream order keeps the scratch rows apart
+        const int n = (int)std::min<int64_t>(h->nmax, batch - o);
+        SHIP(h, hipMemcpyAsync(h->xa, d_obs + o * D, (size_t)n * D * 4, hipMemcpyDeviceToDevice, h->stream));
+        h->ext_launches += 1;
+        SDO(actor_device_rows(h, h->xa, n, deterministic ? 1 : 0, deterministic || !d_noise ? nullptr : d_noise + o * A,
+                              d_raw_actions ? d_raw_actions + o * A : nullptr, d_env_actions ? d_env_actions + o * A : nullptr, nullptr));
+    }
+    SHIP(h, back.give());
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_push_device(dril_sac_handle* h, const float* d_rewards, const uint8_t* d_terminated, const uint8_t* d_truncated,
+                                             const float* d_next_obs, const float* d_terminal_obs, void* caller_stream) {
+    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_ext_push_device");
+    if (!d_rewards || !d_terminated || !d_truncated || !d_next_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push_device: null rewards / terminated / truncated / next_obs");
+    if (!h->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push_device without a preceding dril_sac_ext_act_device");
+    const size_t E = h->cfg.n_envs, D = h->D;
+    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_rewards", d_rewards, E * 4));
+    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_terminated", d_terminated, E));
+    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_truncated", d_truncated, E));
+    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_next_obs", d_next_obs, E * D * 4));
+    if (d_terminal_obs) SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_terminal_obs", d_terminal_obs, E * D * 4));
+    DeviceVerbScope scope(h);
+    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
+    StreamHandOver back(h, caller_stream);
+    const long long tail = (h->head + h->size) % h->cap;
+    PushArgs pa{(int)E, (int)D, h->A, h->cap, tail, h->obs_cur, h->e_raw, d_rewards, d_terminal_obs, d_next_obs, d_terminated, d_truncated,
+                h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, nullptr};
+    hipLaunchKernelGGL(sac_ext_push_kernel, dim3((unsigned)((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock)), dim3(256), 0, h->stream, pa, h->ext_err);
+    SHIP(h, hipGetLastError());
+    h->ext_launches += 1;
+    ring_advance(h);                                                                              // head / size are host counters: nothing to wait for
+    SHIP(h, back.give());
+    h->ext_acted = false; h->ext_steps_dev += 1;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_update_enqueue(dril_sac_handle* h, int32_t n_updates) {
+    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_update_enqueue");
+    if (n_updates <= 0) return sfail(h, DRIL_ERR_INVALID_ARG, "n_updates must be positive");
+    if (h->inj_updates && h->inj_updates != n_updates) return sfail(h, DRIL_ERR_INVALID_ARG, "injected batches were set for a different n_updates");
+    if ((int64_t)h->pend_n + n_updates > kPendingCap)
+        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_update_enqueue: " + std::to_string(h->pend_n) + " pending + " + std::to_string(n_updates) + " new statistics rows exceed the pending table of " + std::to_string(kPendingCap) + ": flush first (dril_sac_flush)");
+    if (h->size <= 0) return sfail(h, DRIL_ERR_NOT_INITIALISED, "the replay buffer is empty");
+    const int nb = h->adam_blocks_c + h->end_blocks;
+    DeviceVerbScope scope(h);
+    const bool injected = h->inj_updates != 0;
+    int rc = DRIL_OK;
+    for (int k = 0; k < n_updates && rc == DRIL_OK; ++k) {
+        const size_t row = (size_t)h->pend_n;
+        rc = sac_one_update(h, injected ? k : -1, h->pend_stats + row * 8, nullptr, h->pend_ssq + row * nb);
+        if (rc == DRIL_OK) h->pend_n += 1;
+    }
+    // the injected batches are read by launches still in flight: hipFree would wait for the device, so they go with the next flush
+    for (void* p : {(void*)h->inj_idx, (void*)h->inj_ne, (void*)h->inj_nn, (void*)h->inj_np}) if (p) h->pend_free.push_back(p);
+    h->inj_idx = nullptr; h->inj_ne = h->inj_nn = h->inj_np = nullptr; h->inj_updates = 0;
+    return rc;
+}
+DRIL_EXPORT int32_t dril_sac_flush(dril_sac_handle* h, dril_sac_stats* stats, int64_t stats_capacity, int64_t* n_stats) {
+    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_flush");
+    SHIP(h, hipMemcpyAsync(h->ext_err_host, h->ext_err, 4, hipMemcpyDeviceToHost, h->stream));
+    SDO(ssync(h));
+    h->ext_flushes += 1;
+    for (void* p : h->pend_free) hipFree(p);
+    h->pend_free.clear();
+    const int n = h->pend_n;
+    if (n_stats) *n_stats = n;
+    if (n > 0 && stats && stats_capacity > 0) {
+        std::vector<dril_sac_stats> tmp((size_t)n);
+        SDO(fetch_stats(h, n, tmp.data(), h->pend_stats, h->pend_ssq));
+        for (int64_t k = 0; k < std::min<int64_t>(stats_capacity, n); ++k) stats[k] = tmp[(size_t)k];
+    }
+    h->pend_n = 0;
+    if (*h->ext_err_host) {
+        *h->ext_err_host = 0;
+        SHIP(h, hipMemsetAsync(h->ext_err, 0, 4, h->stream));
+        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_flush: a dril_sac_ext_push_device call had truncated envs and terminal_obs == NULL (infos[i][\"terminal_observation\"], off_policy_collection.jl:75-79); the rows of that push stay in the ring with next_obs in its place");
+    }
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_set_action_bounds(dril_sac_handle* h, const float* low, const float* high) {
+    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_ext_set_action_bounds");
+    if (!low || !high) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_set_action_bounds: null low / high");
+    float tb[2 * kMaxA];
+    for (int a = 0; a < kMaxA; ++a) { tb[a] = h->act_lo; tb[kMaxA + a] = h->act_hi; }
+    for (int a = 0; a < h->A; ++a) {
+        if (!std::isfinite(low[a]) || !std::isfinite(high[a]) || !(low[a] < high[a]))
+            return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_set_action_bounds: dimension " + std::to_string(a) + " needs finite bounds with low < high (TanhScaleAdapter, default_adapters.jl:13-21)");
+        tb[a] = low[a]; tb[kMaxA + a] = high[a];
+    }
+    SDO(ssync(h));                                                                                 // launches in flight read the table
+    SHIP(h, hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
+    h->ext_bounds_set = true;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_device_info(const dril_sac_handle* h, struct dril_sac_ext_device_info* out) {
+    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    dril_sac_handle* hm = const_cast<dril_sac_handle*>(h);                                         // (the message slot only)
+    if (!out) return sfail(hm, DRIL_ERR_INVALID_ARG, "dril_sac_ext_device_info: null out pointer");
+    if (!h->external) return sfail(hm, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_device_info: the handle was not created with DRIL_ENV_EXTERNAL");
+    std::memset(out, 0, sizeof(*out));
+    out->steps_device = h->ext_steps_dev; out->steps_host = h->ext_steps_host; out->host_syncs = h->ext_syncs; out->flushes = h->ext_flushes; out->launches = h->ext_launches;
+    out->pending_updates = h->pend_n; out->pending_capacity = kPendingCap; out->per_dim_bounds = h->ext_bounds_set ? 1 : 0;
+    return DRIL_OK;
 }
 
 DRIL_EXPORT int64_t dril_sac_replay_size(const dril_sac_handle* h) { return h ? h->size : 0; }

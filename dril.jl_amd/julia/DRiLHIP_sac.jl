@@ -354,3 +354,36 @@ function train!(agent::SACAgent, w::OnDevice, alg::DRiL.SAC, max_steps::Int; ad_
     end
 end
 
+# ---- the same loop on DEVICE arrays (DRIL_ENV_EXTERNAL; include/dril_sac.h, docs/sac.md last section) ------------------------------------------------------
+# Thin wrappers of the sync-free verbs for a simulator whose batched arrays already live on the GPU (AMDGPU.jl ROCArrays: pass `pointer(x)` converted to Ptr{Cvoid}).
+# `h` is a dril_sac_handle* of dril_sac_create with DRIL_ENV_EXTERNAL; `stream` a hipStream_t (C_NULL: the null stream).  None of act / push / predict / enqueue
+# waits on the host; sac_flush! is the one drain and returns the pending statistics rows.
+struct DrilSacExtDeviceInfo
+    steps_device::Int64; steps_host::Int64; host_syncs::Int64; flushes::Int64; launches::Int64
+    pending_updates::Int32; pending_capacity::Int32; per_dim_bounds::Int32
+    reserved::NTuple{5, Int32}
+end
+const SAC_PENDING_CAPACITY = 4096
+sac_ext_act_device!(h, d_obs, use_random::Bool, d_noise, d_stored, d_env_actions, stream = C_NULL) =
+    sac_check(ccall((:dril_sac_ext_act_device, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                    h, d_obs, Int32(use_random), d_noise, d_stored, d_env_actions, stream), h)
+sac_ext_push_device!(h, d_rewards, d_terminated, d_truncated, d_next_obs, d_terminal_obs = C_NULL, stream = C_NULL) =
+    sac_check(ccall((:dril_sac_ext_push_device, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                    h, d_rewards, d_terminated, d_truncated, d_next_obs, d_terminal_obs, stream), h)
+sac_predict_actions_device!(h, d_obs, batch::Integer, deterministic::Bool, d_noise, d_raw_actions, d_env_actions, stream = C_NULL) =
+    sac_check(ccall((:dril_sac_predict_actions_device, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                    h, d_obs, Int64(batch), Int32(deterministic), d_noise, d_raw_actions, d_env_actions, stream), h)
+sac_update_enqueue!(h, n_updates::Integer) = sac_check(ccall((:dril_sac_update_enqueue, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(n_updates)), h)
+function sac_flush!(h)
+    st = Vector{DrilSacStats}(undef, SAC_PENDING_CAPACITY); n = Ref{Int64}(0)
+    GC.@preserve st sac_check(ccall((:dril_sac_flush, LIB[]), Int32, (Ptr{Cvoid}, Ptr{DrilSacStats}, Int64, Ref{Int64}), h, st, Int64(length(st)), n), h)
+    return st[1:n[]]
+end
+function sac_ext_set_action_bounds!(h, low::Vector{Float32}, high::Vector{Float32})
+    GC.@preserve low high sac_check(ccall((:dril_sac_ext_set_action_bounds, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h, low, high), h)
+end
+function sac_ext_device_info(h)
+    info = Ref{DrilSacExtDeviceInfo}()
+    sac_check(ccall((:dril_sac_ext_device_info, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilSacExtDeviceInfo}), h, info), h)
+    return info[]
+end

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _capi as capi, _normalize
 from ._capi import DrilSacConfig, DrilSacStats
-from .host import Box, DrilError, PendulumEnv, ScalingWrapperEnv, _orthogonal
+from .host import Box, DeviceArrayParallelEnv, DrilError, PendulumEnv, ScalingWrapperEnv, _dev_ptr, _orthogonal, _stream_ptr, _to_host
 
 
 # --------------------------------------------------------------------------------------------
@@ -136,7 +136,7 @@ def sac_unflatten_params(flat: np.ndarray, like: dict) -> dict:
 
 
 def make_sac_config(env, n_envs: int, alg: SAC, layer: SACLayer, *, seed: int = 42, device: int = 0,
-                    profile_events: bool = False) -> DrilSacConfig:
+                    profile_events: bool = False, per_dim_bounds: bool = False) -> DrilSacConfig:
     """`env`: one env of a DeviceParallelEnv (`.env`), a HostParallelEnv, or a device env plug-in (a DeviceModuleEnv or its ModuleEnv: the spaces and the Box
     bounds per dimension are the code object's, the handle is made with SacHandle(cfg, env_module=path))"""
     if getattr(env, "kind", None) is None and getattr(getattr(env, "env", None), "kind", None) == capi.ENV_MODULE:
@@ -156,9 +156,10 @@ def make_sac_config(env, n_envs: int, alg: SAC, layer: SACLayer, *, seed: int = 
     if external:     # host envs: the spaces travel in the config (include/dril_sac.h)
         osp, asp = env.observation_space(), env.action_space()
         lo, hi = np.unique(np.asarray(asp.low, np.float32)), np.unique(np.asarray(asp.high, np.float32))
-        if lo.size != 1 or hi.size != 1:
+        if (lo.size != 1 or hi.size != 1) and not per_dim_bounds:
             raise NotImplementedError("DRIL_ENV_EXTERNAL SAC: one (low, high) pair for all action dimensions (wrap the env in a ScalingWrapperEnv-style Box(-1, 1))")
-        c.ext_obs_dim, c.ext_action_dim, c.ext_action_low, c.ext_action_high = len(osp.low), len(asp.low), float(lo[0]), float(hi[0])
+        # per_dim_bounds: the caller hands the Box per dimension to SacHandle.ext_set_action_bounds right after create; the config carries the enclosing pair
+        c.ext_obs_dim, c.ext_action_dim, c.ext_action_low, c.ext_action_high = len(osp.low), len(asp.low), float(lo[0]), float(hi[-1])
     c.hidden1, c.hidden2 = layer.hidden_dims
     c.activation = {"tanh": 0, "relu": 1}[layer.activation]
     c.buffer_capacity, c.start_steps, c.batch_size = alg.buffer_capacity, alg.start_steps, alg.batch_size
@@ -335,6 +336,69 @@ class SacHandle:
         te, tr = np.ascontiguousarray(terminated, np.uint8), np.ascontiguousarray(truncated, np.uint8)
         to = None if terminal_obs is None else self._f32(terminal_obs)
         self._chk(self._f("ext_push")(self._h, self._p(o), self._p(a), self._p(r), self._p(te), self._p(tr), self._p(n), self._p(to)))
+
+    # the same loop over DEVICE arrays (dril_sac_ext_*_device, docs/sac.md last section): integers (raw device pointers) or objects with __cuda_array_interface__
+    # (torch-ROCm tensors, CuPy arrays); nothing is copied or allocated here, and none of act / push / predict / update_enqueue waits on the host
+    discrete = False                                                                  # SAC needs a Box: what DeviceArrayParallelEnv.action_arrays asks of a handle
+
+    def ext_act_device(self, obs, use_random_actions: bool = False, noise=None, stored_actions=None, env_actions=None, stream=None):
+        """obs (E, D) f32 on the device; noise (E, A) f32 standard normals (uniforms in [0, 1) for random actions) or None = the handle's stream;
+        stored_actions / env_actions: device OUTPUT arrays (E, A) f32, either may be None.  The outputs are ready for work enqueued on `stream` afterwards"""
+        args = (_dev_ptr("obs", obs, (self.E, self.D), "float32"), int(bool(use_random_actions)), _dev_ptr("noise", noise, (self.E, self.A), "float32", True),
+                _dev_ptr("stored_actions", stored_actions, (self.E, self.A), "float32", True), _dev_ptr("env_actions", env_actions, (self.E, self.A), "float32", True))
+        self._chk(self._f("ext_act_device")(self._h, *args, _stream_ptr(stream)))
+
+    def ext_push_device(self, rewards, terminated, truncated, next_obs, terminal_obs=None, stream=None):
+        """rewards f32 (E,), terminated / truncated u8 or bool (E,), next_obs f32 (E, D), terminal_obs f32 (E, D) or None = no env was truncated in this step"""
+        args = (_dev_ptr("rewards", rewards, (self.E,), "float32"), _dev_ptr("terminated", terminated, (self.E,), "uint8"), _dev_ptr("truncated", truncated, (self.E,), "uint8"),
+                _dev_ptr("next_obs", next_obs, (self.E, self.D), "float32"), _dev_ptr("terminal_obs", terminal_obs, (self.E, self.D), "float32", True))
+        self._chk(self._f("ext_push_device")(self._h, *args, _stream_ptr(stream)))
+
+    def predict_actions_device(self, obs, deterministic: bool = False, noise=None, raw_actions=None, env_actions=None, stream=None, batch: Optional[int] = None):
+        """dril_sac_predict_actions on device arrays; `batch` is read from obs's shape (B, D) unless obs is a raw pointer"""
+        if batch is None:
+            cai = getattr(obs, "__cuda_array_interface__", None)
+            if cai is None or len(cai["shape"]) != 2:
+                raise ValueError("obs: expected a device array of shape (batch, obs_dim), or a raw pointer together with batch=")
+            batch = int(cai["shape"][0])
+        if raw_actions is None and env_actions is None:
+            raise ValueError("raw_actions / env_actions: at least one device output array is needed")
+        args = (_dev_ptr("obs", obs, (batch, self.D), "float32"), batch, int(bool(deterministic)), _dev_ptr("noise", noise, (batch, self.A), "float32", True),
+                _dev_ptr("raw_actions", raw_actions, (batch, self.A), "float32", True), _dev_ptr("env_actions", env_actions, (batch, self.A), "float32", True))
+        self._chk(self._f("predict_actions_device")(self._h, *args, _stream_ptr(stream)))
+
+    def update_enqueue(self, n_updates: int = 1):
+        """the launches of update(n_updates), no wait; the statistics rows wait in the pending table for flush()"""
+        self._chk(self._f("update_enqueue")(self._h, n_updates))
+
+    def flush(self) -> list:
+        """the one drain: -> the pending statistics rows in order.  The sticky error of ext_push_device (truncated envs without terminal_obs) is raised as a
+        DrilError whose `stats` attribute carries the rows this flush took out of the table: the library has emptied it, they would be lost otherwise"""
+        cap = capi.SAC_PENDING_CAPACITY
+        out, n = (DrilSacStats * cap)(), C.c_int64(0)
+        rc = self._f("flush")(self._h, C.cast(out, C.c_void_p), cap, C.byref(n))
+        rows = list(out[:n.value])
+        try:
+            self._chk(rc)
+        except DrilError as e:
+            e.stats = rows
+            raise
+        return rows
+
+    def ext_set_action_bounds(self, low, high):
+        """the Box per action dimension for TanhScaleAdapter and rand(action_space) on an external handle (host arrays of A floats)"""
+        if low is None or high is None:
+            raise ValueError("low / high: None, expected action_dim floats each")
+        lo, hi = np.ascontiguousarray(low, np.float32).ravel(), np.ascontiguousarray(high, np.float32).ravel()
+        if lo.size != self.A or hi.size != self.A:
+            raise ValueError(f"low / high: {lo.size} / {hi.size} values where action_dim = {self.A} are expected")
+        self._chk(self._f("ext_set_action_bounds")(self._h, self._p(lo), self._p(hi)))
+
+    def ext_device_info(self) -> dict:
+        info = capi.DrilSacExtDeviceInfo()
+        self._chk(self._f("ext_device_info")(self._h, C.byref(info)))
+        return dict(steps_device=int(info.steps_device), steps_host=int(info.steps_host), host_syncs=int(info.host_syncs), flushes=int(info.flushes), launches=int(info.launches),
+                    pending_updates=int(info.pending_updates), pending_capacity=int(info.pending_capacity), per_dim_bounds=bool(info.per_dim_bounds))
 
     def set_collect_noise(self, noise):
         self._noise = self._f32(noise)       # the oracle keeps the pointer until the next collect call
@@ -523,6 +587,8 @@ def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, determin
     NormalizeWrapperEnv (the env's own keywords, or `normalize=dict(...)`): the evaluation handle is a throw-away one, so the training statistics are loaded into it
     from `normalize_stats` — the training handle (`replay_buffer.handle`) or a norm_get_stats() dict — with training off; reported returns are raw.  Without
     them the evaluation would silently run under mean 0 / var 1: that is a RuntimeWarning unless `normalize_stats="fresh"` asks for it (an untrained agent)."""
+    if isinstance(env, DeviceArrayParallelEnv):
+        return _sac_evaluate_device_arrays(agent, env, n_eval_episodes, deterministic, reward_threshold, return_stats)
     if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
         raise NotImplementedError("sac_evaluate_agent: host envs (HostParallelEnv) are evaluated on the host; the device verb steps device envs")
     alg = agent.alg
@@ -552,6 +618,50 @@ def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, determin
     return {k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} if return_stats else (er, el.astype(np.int64))
 
 
+def _sac_ext_handle(agent: SACAgent, env, alg: SAC, rb_handle=None) -> "SacHandle":
+    """the DRIL_ENV_EXTERNAL handle of a DeviceArrayParallelEnv: a Box with per-dimension bounds goes through dril_sac_ext_set_action_bounds"""
+    if rb_handle is not None:
+        return rb_handle
+    asp = env.action_space()
+    cfg = make_sac_config(env, env.n_envs, alg, agent.layer, seed=env.seed, device=env._kw.get("device", 0), profile_events=env._kw.get("profile_events", False), per_dim_bounds=True)
+    h = SacHandle(cfg)
+    lo, hi = np.asarray(asp.low, np.float32).ravel(), np.asarray(asp.high, np.float32).ravel()
+    if np.unique(lo).size != 1 or np.unique(hi).size != 1:
+        h.ext_set_action_bounds(lo, hi)
+    return h
+
+
+def _sac_evaluate_device_arrays(agent: SACAgent, env: DeviceArrayParallelEnv, n_eval_episodes: int, deterministic: bool, reward_threshold: Optional[float], return_stats: bool):
+    """the reference loop (evaluation.jl:86-125) with observations and actions on the device: dril_sac_predict_actions_device per step.  Rewards and flags (E values
+    each) come to the host once per step for the episode accounting — that wait is the accounting's, not the library's"""
+    h = _sac_ext_handle(agent, env, replace(agent.alg, buffer_capacity=max(env.n_envs, 1)))   # an evaluation never touches the ring
+    try:
+        h.set_params(sac_flatten_params(agent.parameters))
+        er, el = [], []
+        cur_r, cur_l = np.zeros(env.n_envs, np.float32), np.zeros(env.n_envs, np.int64)
+        env.reset_()
+        obs = env.observe()
+        _, ea = env.action_arrays(h, obs)
+        while len(er) < n_eval_episodes:
+            h.predict_actions_device(obs, deterministic, None, None, ea, env.stream)
+            rew, term, trunc, _ = env.act_(ea)
+            obs = env.observe()
+            rew, done = _to_host(rew, env.stream), _to_host(term, env.stream).astype(bool) | _to_host(trunc, env.stream).astype(bool)
+            cur_r += rew; cur_l += 1
+            for i in np.nonzero(done)[0]:
+                if len(er) < n_eval_episodes:
+                    er.append(float(cur_r[i])); el.append(int(cur_l[i]))
+                    cur_r[i] = 0; cur_l[i] = 0
+    finally:
+        h.close()
+    er, el = np.asarray(er, np.float32), np.asarray(el, np.int64)
+    sd = lambda x: float(np.std(x, ddof=1)) if len(x) > 1 else float("nan")
+    stats = {"mean_reward": float(er.mean()), "std_reward": sd(er), "mean_length": float(el.mean()), "std_length": sd(el)}
+    if reward_threshold is not None and stats["mean_reward"] < reward_threshold:
+        raise RuntimeError(f"Mean reward below threshold: {stats['mean_reward']:.2f} < {reward_threshold}")   # evaluation.jl:131-135
+    return stats if return_stats else (er, el)
+
+
 def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer: Optional[ReplayBuffer] = None, callbacks=None, normalize: Optional[dict] = None):
     """train!(agent, env, alg::SAC, max_steps) sac.jl:406-549 -> (agent, replay_buffer, training_stats, timer); `env` is a
     DeviceParallelEnv over PendulumEnv / MountainCarContinuousEnv, a DeviceModuleEnv over a Box plug-in, or a HostParallelEnv.  training_stats carries the fields of SACTrainingStats (sac.jl:243-257).
@@ -560,6 +670,8 @@ def sac_train_(agent: SACAgent, env, alg: SAC, max_steps: int, *, replay_buffer:
     if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
         if normalize is not None:
             raise NotImplementedError("sac_train_: host envs (HostParallelEnv) are normalised on the host; normalize= wraps device envs")
+        if isinstance(env, DeviceArrayParallelEnv):
+            return _sac_train_device_arrays(agent, env, alg, max_steps, replay_buffer, list(callbacks or []))
         return _sac_train_host(agent, env, alg, max_steps, replay_buffer, list(callbacks or []))
     if callbacks:
         return _sac_train_callbacks(agent, env, alg, max_steps, replay_buffer, list(callbacks), normalize)
@@ -766,4 +878,118 @@ def _sac_train_host(agent: SACAgent, env, alg: SAC, max_steps: int, replay_buffe
             n_upd += n_updates
             loc.update(gradient_updates_performed=n_upd)
     hook("on_training_end", loc)                                                                    # (a failure here still returns the timer, sac.jl:548-550)
+    return leave(False)
+
+
+def _sac_train_device_arrays(agent: SACAgent, env: DeviceArrayParallelEnv, alg: SAC, max_steps: int, replay_buffer: Optional[ReplayBuffer] = None, cbs: Optional[list] = None):
+    """the loop of _sac_train_host for ONE batched env whose arrays live on the device (DeviceArrayParallelEnv): dril_sac_ext_act_device -> the env's own act_ ->
+    dril_sac_ext_push_device -> dril_sac_update_enqueue, none of which waits on the host or copies across PCIe; the random actions of the start phase are drawn on the
+    device.  dril_sac_flush — the one drain, which also brings the statistics rows — runs when the pending table would overflow, before a callback hook (it may read
+    the agent or the statistics) and at the end.  The timer dict gains "flushes" and "host_syncs" (waits inside the sync-free verbs: 0)."""
+    cbs = cbs or []
+    has_hook = lambda name: any(hasattr(c, name) for c in cbs)
+    step_hooks = [c for c in cbs if hasattr(c, "on_step")]
+    t0 = time.perf_counter()
+    E, asp = env.n_envs, env.action_space()
+    rb = replay_buffer or ReplayBuffer(env.observation_space(), asp, alg.buffer_capacity)
+    h = _sac_ext_handle(agent, env, alg, rb.handle)
+    rb.handle = h
+    h.set_params(sac_flatten_params(agent.parameters)); h.set_target_params(agent.q_target_parameters); h.set_log_ent_coef(agent.log_ent_coef)
+    total_start = alg.start_steps if alg.start_steps > 0 else alg.train_freq * E                    # sac.jl:456-458
+    adjusted = max(1, total_start // E) * E
+    n_steps = adjusted // E
+    iterations = int((max_steps - adjusted) / (alg.train_freq * E)) + 1                             # div truncates toward zero, :462
+    n_updates = get_gradient_steps(alg, alg.train_freq, E)
+    ts = {k: [] for k in _SAC_STAT_KEYS}
+    total = n_upd = 0
+    t_env = t_dev = 0.0
+    info0 = h.ext_device_info()
+    cap = info0["pending_capacity"]
+    pending = info0["pending_updates"]
+    obs = env.observe()
+    _, env_act = env.action_arrays(h, obs)
+    loc = dict(agent=agent, replay_buffer=rb, env=env, alg=alg, max_steps=max_steps, callbacks=cbs, n_envs=E, layer=agent.layer, training_stats=ts,
+               gradient_updates_performed=0, total_start_steps=total_start, adjusted_total_start_steps=adjusted, n_steps=n_steps, training_iteration=0,
+               iterations=iterations, total_steps=n_steps * E + alg.train_freq * E * (iterations - 1))
+
+    def flush():
+        nonlocal pending, t_dev
+        b = time.perf_counter()
+        try:
+            rows, err = h.flush(), None
+        except DrilError as e:                                                                      # the sticky error: the rows it took out of the table still count
+            rows, err = getattr(e, "stats", []), e
+        for s_ in rows:
+            ts["actor_losses"].append(s_.actor_loss); ts["critic_losses"].append(s_.critic_loss)
+            if s_.has_entropy_loss:
+                ts["entropy_losses"].append(s_.entropy_loss)
+            ts["entropy_coefficients"].append(s_.entropy_coefficient); ts["q_values"].append(s_.mean_q_values)
+            ts["learning_rates"].append(alg.learning_rate); ts["grad_norms"].append(s_.grad_norm)
+        pending = 0
+        t_dev += time.perf_counter() - b
+        if err is not None:
+            raise err
+
+    def hook(name):
+        if not has_hook(name):
+            return True
+        flush()                                                                                     # the hook may read the agent, the ring or the statistics
+        return all(getattr(c, name)(loc) for c in cbs if hasattr(c, name))
+
+    def leave(early):
+        try:
+            flush()
+        finally:
+            agent.steps_taken += total
+            agent.gradient_updates += n_upd
+            agent.parameters = sac_unflatten_params(h.get_params(), agent.parameters)
+            agent.q_target_parameters = h.get_target_params()
+            agent.log_ent_coef = h.get_log_ent_coef()
+        info = h.ext_device_info()
+        timer = {"training_loop": time.perf_counter() - t0, "iterations": max(iterations, 0), "collect_rollout": t_env, "device": t_dev,
+                 "flushes": info["flushes"] - info0["flushes"], "host_syncs": info["host_syncs"] - info0["host_syncs"]}
+        return (agent, rb, ts) if early else (agent, rb, ts, timer)
+
+    if not hook("on_training_start"):
+        return leave(True)
+    for it in range(max(iterations, 0)):
+        use_random = it == 0 and alg.start_steps > 0                                                # :487
+        loc.update(training_iteration=it + 1, n_steps=n_steps)
+        if not hook("on_rollout_start"):
+            return leave(True)
+        a = time.perf_counter()
+        for i_step in range(n_steps):                                                               # collect_trajectories, off_policy_collection.jl:28-96
+            if step_hooks:
+                loc.update(i=i_step + 1, use_random_actions=use_random)
+                if not hook("on_step"):
+                    return leave(True)
+            b = time.perf_counter()
+            h.ext_act_device(obs, use_random, None, None, env_act, env.stream)                      # rand(act_space) | predict_actions + to_env(TanhScaleAdapter), :50-58
+            t_dev += time.perf_counter() - b
+            rew, term, trunc, tobs = env.act_(env_act)                                              # :60
+            nobs = env.observe()                                                                    # :61
+            b = time.perf_counter()
+            h.ext_push_device(rew, term, trunc, nobs, tobs, env.stream)                             # push!(buffer, traj), replay_buffer.jl:98-114
+            t_dev += time.perf_counter() - b
+            obs = nobs
+        t_env += time.perf_counter() - a
+        fps = n_steps * E / max(time.perf_counter() - a, 1e-12)                                     # (enqueue rate: nothing waited for the device)
+        total += n_steps * E
+        loc.update(fps=fps, success=True)
+        if not hook("on_rollout_end"):
+            return leave(True)
+        ts["fps"].append(fps)
+        n_steps = alg.train_freq                                                                    # :520
+        left = n_updates
+        while left > 0:                                                                             # :523-538, in pieces the pending table holds
+            k = min(left, cap)
+            if pending + k > cap:
+                flush()
+            b = time.perf_counter()
+            h.update_enqueue(k)
+            t_dev += time.perf_counter() - b
+            pending += k; left -= k
+        n_upd += max(n_updates, 0)
+        loc.update(gradient_updates_performed=n_upd)
+    hook("on_training_end")                                                                         # (a failure here still returns the timer, sac.jl:548-550)
     return leave(False)

@@ -178,6 +178,66 @@ int32_t dril_sac_debug_set_collect_noise(dril_sac_handle* h, const float* noise,
 int32_t dril_sac_ext_push(dril_sac_handle* h, const float* obs, const float* stored_actions, const float* rewards, const uint8_t* terminated,
                           const uint8_t* truncated, const float* next_obs, const float* terminal_obs);
 
+/* ---- the same loop on DEVICE arrays (DRIL_ENV_EXTERNAL): envs whose batched arrays already live on the GPU (a simulator in torch-ROCm or CuPy, another HIP
+ * library of the process).  One env step is
+ *   dril_sac_ext_act_device(h, d_obs, use_random, d_noise, d_stored, d_env_actions, stream)       first half of collect_trajectories' step, :51-61
+ *   ... the caller's simulator steps on `stream` ...
+ *   dril_sac_ext_push_device(h, d_rewards, d_terminated, d_truncated, d_next_obs, d_terminal_obs, stream)   push! of the pending step, replay_buffer.jl:98-114
+ *   dril_sac_update_enqueue(h, gradient_steps)
+ * and NONE of the three waits on the host, copies across PCIe or calls a stream / event / device synchronisation; dril_sac_flush is the one drain.
+ * caller_stream (a hipStream_t; NULL = the null stream) follows the contract of dril_ext_act_device (dril_hip.h): on entry the handle's stream waits for an event
+ * recorded on caller_stream, before return caller_stream waits for an event recorded on the handle's stream.  Every device pointer must be memory the handle's
+ * device can address, in an allocation long enough for the array, else DRIL_ERR_INVALID_ARG before anything is enqueued.  Every verb of this block returns
+ * DRIL_ERR_UNSUPPORTED on a handle that was not created with DRIL_ENV_EXTERNAL.  A loop may mix these verbs with dril_sac_ext_push step by step: one ring, one set
+ * of counters.
+ *
+ * dril_sac_ext_act_device: d_obs f32 (D x E) is kept by the handle as the pending step's observation.  use_random_actions == 0: stored / env actions are exactly
+ * what dril_sac_predict_actions(h, obs, E, 0, noise, raw, env) returns for the same observations, parameters and noise; d_noise f32 (A x E) standard normals, or
+ * NULL = the handle's stream (the words dril_sac_predict_actions draws with noise == NULL at the same position of the stream).  use_random_actions != 0:
+ * stored = env = rand(action_space), per element low[a] + u * (high[a] - low[a]) with each operation rounded to float32 on its own; u from d_noise (uniforms in
+ * [0, 1)) or the handle's stream.  Either output pointer may be NULL; the stored action is kept by the handle in both cases.  DRIL_ERR_INVALID_ARG for null obs
+ * and for a second act before the push of the first. */
+int32_t dril_sac_ext_act_device(dril_sac_handle* h, const float* d_obs, int32_t use_random_actions, const float* d_noise, float* d_stored_actions,
+                                float* d_env_actions, void* caller_stream);
+/* the pending step into the ring, with the slots and rows of dril_sac_ext_push: a truncated env stores its d_terminal_obs column as next observation (columns of
+ * other envs may hold anything, NaN included, but must be readable).  d_terminal_obs == NULL states that no env was truncated in this step; a truncated flag set all
+ * the same raises a sticky error word on the device which dril_sac_flush returns as DRIL_ERR_INVALID_ARG — the rows of that push STAY in the ring and hold next_obs
+ * in place of the terminal observation (a ring cannot be rolled back), and the handle stays usable.  DRIL_ERR_INVALID_ARG for a push without a pending act and for
+ * null rewards / flags / next_obs. */
+int32_t dril_sac_ext_push_device(dril_sac_handle* h, const float* d_rewards, const uint8_t* d_terminated, const uint8_t* d_truncated, const float* d_next_obs,
+                                 const float* d_terminal_obs, void* caller_stream);
+/* dril_sac_predict_actions on device arrays, any batch >= 1 (chunked like the host verb); d_noise as above for deterministic == 0.  The two output pointers must
+ * not both be NULL.  Does not touch the pending step: the verb of evaluation. */
+int32_t dril_sac_predict_actions_device(dril_sac_handle* h, const float* d_obs, int64_t batch, int32_t deterministic, const float* d_noise, float* d_raw_actions,
+                                        float* d_env_actions, void* caller_stream);
+/* the launches of dril_sac_update(h, n_updates, ...) enqueued, no wait (legal on an external handle only).  Honours dril_sac_debug_set_batches like dril_sac_update.
+ * The statistics rows go to a pending table on the device of DRIL_SAC_PENDING_CAPACITY rows; a call that would overflow it returns DRIL_ERR_INVALID_ARG ("flush
+ * first") and enqueues nothing.  DRIL_ERR_NOT_INITIALISED on an empty ring.  k x update_enqueue(n) + flush leaves parameters, targets, optimiser state, entropy
+ * coefficient, update counters and statistics bit-identical to k x dril_sac_update(n). */
+#define DRIL_SAC_PENDING_CAPACITY 4096
+int32_t dril_sac_update_enqueue(dril_sac_handle* h, int32_t n_updates);
+/* the one drain: waits for the handle's stream, copies out the pending statistics rows in order (up to stats_capacity of them; *n_stats = rows pending; both may
+ * be NULL / 0), empties the table, and returns and clears the sticky error of dril_sac_ext_push_device (DRIL_ERR_INVALID_ARG, the message names terminal_obs).
+ * Legal with nothing pending. */
+int32_t dril_sac_flush(dril_sac_handle* h, dril_sac_stats* stats, int64_t stats_capacity, int64_t* n_stats);
+/* the Box per dimension for TanhScaleAdapter and rand(action_space) on an external handle: low / high are HOST arrays of action_dim floats.  Rewrites the table the
+ * sampling kernels read, so dril_sac_predict_actions and dril_policy_from_sac_handle honour it from then on.  DRIL_ERR_INVALID_ARG for a null pointer, a non-finite
+ * bound or low >= high in a dimension (the first such dimension is named). */
+int32_t dril_sac_ext_set_action_bounds(dril_sac_handle* h, const float* low, const float* high);
+/* counters of an external handle since create.  A struct tag only: the verb below has the same name */
+struct dril_sac_ext_device_info {
+    int64_t steps_device;      /* env steps pushed through dril_sac_ext_push_device */
+    int64_t steps_host;        /* env steps pushed through dril_sac_ext_push */
+    int64_t host_syncs;        /* host waits made INSIDE act_device / push_device / predict_actions_device / update_enqueue calls: stays 0 */
+    int64_t flushes;           /* dril_sac_flush calls */
+    int64_t launches;          /* kernels and device-to-device copies enqueued by act_device / push_device / predict_actions_device calls */
+    int32_t pending_updates;   /* statistics rows waiting for dril_sac_flush */
+    int32_t pending_capacity;  /* DRIL_SAC_PENDING_CAPACITY */
+    int32_t per_dim_bounds;    /* 1 after dril_sac_ext_set_action_bounds */
+    int32_t reserved[5];
+};
+int32_t dril_sac_ext_device_info(const dril_sac_handle* h, struct dril_sac_ext_device_info* out);
+
 /* ---- replay buffer ---------------------------------------------------------------------------------------------- */
 int64_t dril_sac_replay_size(const dril_sac_handle* h);       /* length(buffer) */
 int64_t dril_sac_replay_capacity(const dril_sac_handle* h);
