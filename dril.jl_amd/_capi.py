@@ -99,6 +99,12 @@ class DrilExtDeviceInfo(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class DrilExtWrapInfo(C.Structure):
+    """struct dril_ext_wrap_info, include/dril_hip.h"""
+    _fields_ = [("normalize_on", C.c_int32), ("monitor_on", C.c_int32), ("monitor_window", C.c_int32), ("reserved0", C.c_int32), ("launches_act", C.c_int64),
+                ("launches_record", C.c_int64), ("launches_finish", C.c_int64), ("allocations", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
 class DrilSacConfig(C.Structure):
     """struct dril_sac_config, include/dril_sac.h"""
     _fields_ = [
@@ -238,6 +244,17 @@ _SIG = {
     "dril_predict_actions_device": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     "dril_ext_set_action_bounds": (C.c_int32, [_P, _P, _P]),
     "dril_ext_device_info": (C.c_int32, [_P, C.POINTER(DrilExtDeviceInfo)]),
+    "dril_ext_normalize_enable": (C.c_int32, [_P, C.POINTER(DrilNormalizeConfig)]),
+    "dril_ext_normalize_get_config": (C.c_int32, [_P, C.POINTER(DrilNormalizeConfig)]),
+    "dril_ext_normalize_set_training": (C.c_int32, [_P, C.c_int32]),
+    "dril_ext_normalize_get_stats": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "dril_ext_normalize_set_stats": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64]),
+    "dril_ext_normalize_get_original": (C.c_int32, [_P, _P, _P]),
+    "dril_ext_normalize_get_returns": (C.c_int32, [_P, _P]),
+    "dril_ext_normalize_reset": (C.c_int32, [_P, _P]),
+    "dril_ext_monitor_enable": (C.c_int32, [_P, C.c_int32]),
+    "dril_ext_monitor_get_stats": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "dril_ext_wrap_info": (C.c_int32, [_P, C.POINTER(DrilExtWrapInfo)]),
     "dril_collect_rollout": (C.c_int32, [_P, C.POINTER(C.c_double)]),
     "dril_debug_set_noise": (C.c_int32, [_P, _P, C.c_size_t]),
     "dril_buffer_copy_out": (C.c_int32, [_P, C.c_int32, _P, C.c_size_t]),

@@ -1,5 +1,6 @@
 """NormalizeWrapperEnv (normalizeWrapperEnv.jl) on a handle, through either verb family of the library: dril_normalize_* (Handle: a PPO handle on a device env
-plug-in) and dril_sac_normalize_* (SacHandle).  The families have one shape, so the Python methods are defined once and installed on both classes."""
+plug-in), dril_ext_normalize_* (Handle: a PPO handle on device-resident external envs; the methods carry the prefix ext_) and dril_sac_normalize_* (SacHandle).
+The families have one shape, so the Python methods are defined once and installed per family."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,20 +15,21 @@ KEYS = tuple(DEFAULTS)
 _FLAGS = ("training", "norm_obs", "norm_reward")
 
 
-def normalize_verbs(fn, data_prefix: str):
+def normalize_verbs(fn, data_prefix: str, name_prefix: str = ""):
     """class decorator: normalize_enable / normalize_config / normalize_set_training and <data_prefix>get_stats / set_stats / get_original / get_returns on a handle
-    class with _h, _chk, _p, E and D; fn(self, verb) is the library function of the verb ("enable", "get_stats", ...)"""
+    class with _h, _chk, _p, E and D, every name behind name_prefix; fn(self, verb) is the library function of the verb ("enable", "get_stats", ...)"""
 
     def normalize_enable(self, enabled: bool = True, **kw):
         """NormalizeWrapperEnv(env; training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon) (normalizeWrapperEnv.jl:71-80) around the handle's envs:
         a fresh wrapper, or nothing when the handle already has this configuration (`training` apart, which is set); normalize_enable(False) switches it off"""
+        for k in kw:                                                     # before the library is called
+            if k not in KEYS:
+                raise TypeError(f"NormalizeWrapperEnv has no keyword {k!r}")
         if not enabled:
             self._chk(fn(self, "enable")(self._h, None)); return
         c = DrilNormalizeConfig()
         self._chk(fn(self, "config_default")(C.byref(c)))
         for k, v in kw.items():
-            if k not in KEYS:
-                raise TypeError(f"NormalizeWrapperEnv has no keyword {k!r}")
             setattr(c, k, int(v) if k in _FLAGS else float(v))
         self._chk(fn(self, "enable")(self._h, C.byref(c)))
 
@@ -68,8 +70,8 @@ def normalize_verbs(fn, data_prefix: str):
 
     def install(cls):
         for f in (normalize_enable, normalize_config, normalize_set_training):
-            setattr(cls, f.__name__, f)
+            setattr(cls, name_prefix + f.__name__, f)
         for f in (get_stats, set_stats, get_original, get_returns):
-            setattr(cls, data_prefix + f.__name__, f)
+            setattr(cls, name_prefix + data_prefix + f.__name__, f)
         return cls
     return install

@@ -148,6 +148,10 @@ struct dril_handle {
     // The wrapper's other arrays are the handle's own: disc_returns (`returns`), e_obs_raw / e_rew (old_obs / old_rewards: dril_normalize_get_original), e_rew_n (the
     // rewards dril_env_step delivers)
     NormWrap pn; int pn_rows_cap = 0; double* pn_red = nullptr;
+    // the same wrapper and MonitorWrapperEnv around the envs of a DRIL_ENV_EXTERNAL handle (dril_ext_normalize_enable / dril_ext_monitor_enable; kernels: dril_ext_norm.h): pn
+    // again, with e_tobs as the scratch of normalised terminal observations; ext_mon_window sizes the monitor arrays above (cfg.monitor_window stays 0).  xw_added: launches
+    // the wrappers added to the act / record / finish calls of the current rollout; xw_allocs: allocations inside those calls since enable (dril_ext_wrap_info)
+    int ext_mon_window = 0; int64_t xw_added[3] = {0, 0, 0}, xw_allocs = 0; float* ext_pred_obs = nullptr; int64_t ext_pred_obs_cap = 0;
     void* comm = nullptr;
     LoopGroup* loop = nullptr;   // debug loopback communicator (dril_debug_comm_loopback)
     int64_t allreduce_calls = 0;
@@ -830,7 +834,7 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     if (h->eval_counter_host) (void)hipHostFree(h->eval_counter_host);
     if (h->ext_err_host) (void)hipHostFree(h->ext_err_host);
     if (h->ext_ev_in) (void)hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) (void)hipEventDestroy(h->ext_ev_out);
-    void* ptrs[] = {h->ext_err, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
+    void* ptrs[] = {h->ext_err, h->ext_pred_obs, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
                     h->flags, h->last_values, h->noise_dev, h->perm_dev, h->epoch_index, h->epoch_keys, h->small_xchg, h->w2max_dev, h->gae_carry, h->gae_err, h->w2pf_actor, h->w2pf_critic, h->adv_partials, h->adv_stats, h->ev_partials, h->step_stats,
                     h->stop_flag, h->nan_flag, h->e_obs, h->e_rew, h->e_tobs, h->e_term, h->e_trunc, h->e_act, h->e_obs_raw, h->e_rew_n, h->obs_rms, h->ret_rms, h->rms_partials, h->rms_red, h->gen_tmp, h->dbg, h->rec, h->epoch_tables, h->epoch_stats, h->w2a_actor, h->w2ta_actor, h->w2a_critic, h->w2ta_critic, h->w2p_actor, h->w2tp_actor, h->w2p_critic, h->w2tp_critic, h->mon_cur_ret, h->ep_ret, h->mon_ring_ret, h->e_ep_ret, h->mon_cur_len, h->ep_len,
                     h->mon_ring_len, h->e_ep_len, h->mon_cnt, h->mon_meta, h->e_flags};
@@ -972,12 +976,44 @@ DRIL_EXPORT int32_t dril_norm_get_original(dril_handle* h, float* obs, float* re
 // ---- NormalizeWrapperEnv around a device env plug-in (rules and state: dril_norm_wrap.h) ------------------------------------------------------------------------------------
 namespace {
 int pn_kind_check(dril_handle* h, const char* what) {
-    if (h->external) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there");
+    if (h->external) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there (envs whose arrays live on the device: dril_ext_normalize_enable, honoured by the dril_ext_*_device verbs)");
     if (!h->env.module) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": this verb family wraps a device env plug-in (DRIL_ENV_MODULE); a built-in env is wrapped at create with cfg.norm_obs / cfg.norm_reward (dril_norm_get_stats / dril_norm_set_stats / dril_norm_get_original)");
     return DRIL_OK;
 }
 #define PN_ON(h, what) do { int _rc = pn_kind_check(h, what); if (_rc) return _rc; \
     if (!(h)->pn.on) return fail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_normalize_enable has not been called with a configuration)"); } while (0)
+// the bodies of the verbs that read or write a wrapper that is on: one definition for dril_normalize_* (plug-in handles) and dril_ext_normalize_* (external handles)
+int pn_get_config(dril_handle* h, const char* verb, dril_normalize_config* cfg) {
+    if (!cfg) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": null out pointer");
+    *cfg = h->pn.cfg;
+    return DRIL_OK;
+}
+int pn_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
+    std::vector<float> st(h->pn.stats_floats());
+    HIPCHK(h, hipMemcpyAsync(st.data(), h->pn.half(h->pn.cur), st.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    int rc = sync(h); if (rc) return rc;
+    h->pn.unpack(st, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+    return DRIL_OK;
+}
+int pn_set_stats(dril_handle* h, const char* verb, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
+    if (const NormErr err = norm_set_stats_check(obs_mean, obs_var, obs_count, ret_count)) return fail(h, err.code, std::string(verb) + ": " + err.msg);
+    const std::vector<float> st = h->pn.pack(obs_mean, obs_var, ret_mean, ret_var);
+    HIPCHK(h, hipMemcpyAsync(h->pn.half(h->pn.cur), st.data(), st.size() * 4, hipMemcpyHostToDevice, h->stream));
+    int rc = sync(h); if (rc) return rc;
+    h->pn.obs_count = obs_count; h->pn.ret_count = ret_count;
+    return DRIL_OK;
+}
+int pn_get_original(dril_handle* h, const char* verb, float* obs, float* rewards) {
+    if (!obs && !rewards) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": both out pointers are null");
+    if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->e_obs_raw, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
+    if (rewards) HIPCHK(h, hipMemcpyAsync(rewards, h->e_rew, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
+    return sync(h);
+}
+int pn_get_returns(dril_handle* h, const char* verb, float* returns) {
+    if (!returns) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": null out pointer");
+    HIPCHK(h, hipMemcpyAsync(returns, h->env.disc_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
+    return sync(h);
+}
 }  // namespace
 DRIL_EXPORT int32_t dril_normalize_config_default(dril_normalize_config* c) {
     if (!c) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_normalize_config_default: null configuration");
@@ -1020,45 +1056,33 @@ DRIL_EXPORT int32_t dril_normalize_set_training(dril_handle* h, int32_t training
 }
 DRIL_EXPORT int32_t dril_normalize_get_config(dril_handle* h, dril_normalize_config* cfg) {
     NEED(h); PN_ON(h, "dril_normalize_get_config");
-    if (!cfg) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_get_config: null out pointer");
-    *cfg = h->pn.cfg;
-    return DRIL_OK;
+    return pn_get_config(h, "dril_normalize_get_config", cfg);
 }
 DRIL_EXPORT int32_t dril_normalize_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
     NEED(h); PN_ON(h, "dril_normalize_get_stats");
-    std::vector<float> st(h->pn.stats_floats());
-    HIPCHK(h, hipMemcpyAsync(st.data(), h->pn.half(h->pn.cur), st.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    int rc = sync(h); if (rc) return rc;
-    h->pn.unpack(st, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-    return DRIL_OK;
+    return pn_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
 }
 DRIL_EXPORT int32_t dril_normalize_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
     NEED(h); PN_ON(h, "dril_normalize_set_stats");
-    if (const NormErr err = norm_set_stats_check(obs_mean, obs_var, obs_count, ret_count)) return fail(h, err.code, "dril_normalize_set_stats: " + err.msg);
-    const std::vector<float> st = h->pn.pack(obs_mean, obs_var, ret_mean, ret_var);
-    HIPCHK(h, hipMemcpyAsync(h->pn.half(h->pn.cur), st.data(), st.size() * 4, hipMemcpyHostToDevice, h->stream));
-    int rc = sync(h); if (rc) return rc;
-    h->pn.obs_count = obs_count; h->pn.ret_count = ret_count;
-    return DRIL_OK;
+    return pn_set_stats(h, "dril_normalize_set_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
 }
 DRIL_EXPORT int32_t dril_normalize_get_original(dril_handle* h, float* obs, float* rewards) {
     NEED(h); PN_ON(h, "dril_normalize_get_original");
-    if (!obs && !rewards) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_get_original: both out pointers are null");
-    if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->e_obs_raw, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
-    if (rewards) HIPCHK(h, hipMemcpyAsync(rewards, h->e_rew, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
-    return sync(h);
+    return pn_get_original(h, "dril_normalize_get_original", obs, rewards);
 }
 DRIL_EXPORT int32_t dril_normalize_get_returns(dril_handle* h, float* returns) {
     NEED(h); PN_ON(h, "dril_normalize_get_returns");
-    if (!returns) return fail(h, DRIL_ERR_INVALID_ARG, "dril_normalize_get_returns: null out pointer");
-    HIPCHK(h, hipMemcpyAsync(returns, h->env.disc_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
-    return sync(h);
+    return pn_get_returns(h, "dril_normalize_get_returns", returns);
 }
 
+namespace { int monitor_window_stats(dril_handle* h, int W, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes); }
 DRIL_EXPORT int32_t dril_monitor_get_stats(dril_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
     NEED(h);
-    if (!h->mon_cur_ret) return fail(h, DRIL_ERR_NOT_INITIALISED, "MonitorWrapperEnv is off (cfg.monitor_window == 0)");
-    const int W = h->cfg.monitor_window;
+    if (!h->mon_cur_ret || h->external) return fail(h, DRIL_ERR_NOT_INITIALISED, "MonitorWrapperEnv is off (cfg.monitor_window == 0)");   // (an external handle's monitor: dril_ext_monitor_get_stats)
+    return monitor_window_stats(h, h->cfg.monitor_window, ep_rew_mean, ep_len_mean, n_episodes);
+}
+namespace {
+int monitor_window_stats(dril_handle* h, int W, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
     std::vector<float> r(W); std::vector<int32_t> l(W); int meta[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(r.data(), h->mon_ring_ret, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(l.data(), h->mon_ring_len, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1071,6 +1095,7 @@ DRIL_EXPORT int32_t dril_monitor_get_stats(dril_handle* h, float* ep_rew_mean, f
     if (ep_len_mean) *ep_len_mean = meta[0] ? (float)(sl / meta[0]) : 0.f;
     return DRIL_OK;
 }
+}  // namespace
 
 // ---- policy on host batches ----------------------------------------------------------------------
 namespace {
@@ -1329,7 +1354,7 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
 }  // namespace
 namespace {
 // dril_ext_device_info counts per rollout: the first act of a rollout starts the counters again
-void ext_count_begin(dril_handle* h) { if (h->ext_t == 0) { h->ext_steps_dev = h->ext_steps_host = h->ext_syncs = 0; h->ext_launches = 0; } }
+void ext_count_begin(dril_handle* h) { if (h->ext_t == 0) { h->ext_steps_dev = h->ext_steps_host = h->ext_syncs = 0; h->ext_launches = 0; h->xw_added[0] = h->xw_added[1] = h->xw_added[2] = 0; } }
 // the one drain of a rollout over external envs; the sticky error word of dril_ext_record_device comes back with it (a rollout may mix host and device verbs)
 int ext_finish_drain(dril_handle* h, const char* verb) {
     HIPCHK(h, hipMemcpyAsync(h->ext_err_host, h->ext_err, 4, hipMemcpyDeviceToHost, h->stream));
@@ -1357,11 +1382,89 @@ const ExtBounds* ext_bounds_for(dril_handle* h, ExtBounds& scalar) {
     for (int a = 0; a < h->A; ++a) { scalar.lo[a] = h->cfg.ext_action_low; scalar.hi[a] = h->cfg.ext_action_high; }
     return &scalar;
 }
+
+// ---- NormalizeWrapperEnv / MonitorWrapperEnv around the envs of an external handle (dril_ext_normalize_enable / dril_ext_monitor_enable) ----
+#include "dril_ext_norm.h"
+bool xw_on(const dril_handle* h) { return h->pn.on || h->ext_mon_window > 0; }
+#define XW_HOST_REFUSED(h, what) do { if (xw_on(h)) return fail(h, DRIL_ERR_UNSUPPORTED, what ": wrapper on: use the device verbs, or wrap the host env on the host (dril_ext_normalize_enable / dril_ext_monitor_enable are honoured by dril_ext_act_device / _record_device / _finish_device only)"); } while (0)
+// the apply grid of both kernels: env ranges x column tiles, as ppo_norm_apply_kernel's
+dim3 xn_grid(int E, int D, int* epb) {
+    const int W = D > kPnTile ? kPnTile : D;
+    *epb = std::max(std::max(1, 4096 / W), (E + 255) / 256);
+    return dim3((E + *epb - 1) / *epb, pn_tiles(D));
+}
+// norm_moments_kernel over the caller's observations (raw) or the `returns` recursion over the caller's rewards (rew), n_envs rows; *rows: the rows of the table it writes
+int xn_moments(dril_handle* h, const float* raw, const float* rew, int* rows) {
+    const int E = h->cfg.n_envs, D = h->D;
+    *rows = pn_rows(E, D, h->pn_rows_cap);
+    const int R = (E + *rows - 1) / *rows;
+    *rows = (E + R - 1) / R;
+    const NormMomArgs m{E, D, R, raw, rew, h->env.disc_returns, h->pn.cfg.gamma, h->pn.partials};
+    hipLaunchKernelGGL(norm_moments_kernel<kPnTile>, dim3(*rows, raw ? pn_tiles(D) : 1), dim3(256), 0, h->stream, m);
+    HIPCHK(h, hipGetLastError());
+    return DRIL_OK;
+}
+// observe (:123-137) of B rows of the caller's array into obs_out.  rollout: a verb of the collection (B == n_envs) — statistics updated where training && norm_obs,
+// old_obs cached; else the read-only pass of dril_predict_actions_device.  *added: the launches enqueued
+int xn_observe(dril_handle* h, const float* raw, int64_t B, float* obs_out, bool rollout, int64_t* added) {
+    const bool upd = rollout && h->pn.cfg.training && h->pn.cfg.norm_obs;
+    int rows = 0;
+    if (upd) { int rc = xn_moments(h, raw, nullptr, &rows); if (rc) return rc; *added += 1; }
+    XnObserveArgs p{}; NormWrapArgs& a = p.w;
+    h->pn.fill(a, upd, false, (long long)B);
+    a.E = (int)B; a.rows = rows; a.raw = raw; a.obs_out = obs_out; p.old_obs = rollout ? h->e_obs_raw : nullptr;
+    const dim3 grid = xn_grid(a.E, h->D, &a.epb);
+    hipLaunchKernelGGL(ext_norm_observe_kernel, grid, dim3(256), 0, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    h->pn.commit(a); *added += 1;
+    return DRIL_OK;
+}
+// act! (:139-165) with the record's own work and the monitor's sums, row k / E of the buffer.  tobs_norm: where the critic must read the terminal observations
+// (the scratch, or the caller's array with norm_obs == 0; null without terminal_obs)
+int xn_record(dril_handle* h, size_t k, const float* d_rewards, const uint8_t* d_terminated, const uint8_t* d_truncated, const float* d_terminal_obs, const float** tobs_norm, int64_t* launches) {
+    const int E = h->cfg.n_envs;
+    const bool upd = h->pn.on && h->pn.cfg.training && h->pn.cfg.norm_reward;
+    int rows = 0;
+    if (upd) { int rc = xn_moments(h, nullptr, d_rewards, &rows); if (rc) return rc; *launches += 1; }
+    XnRecordArgs p{}; NormWrapArgs& a = p.w;
+    if (h->pn.on) h->pn.fill(a, false, upd, E);
+    a.D = h->D; a.E = E; a.rows = rows; a.rew = d_rewards; a.term = d_terminated; a.trunc = d_truncated; a.returns = h->env.disc_returns;
+    p.has_norm = h->pn.on ? 1 : 0;
+    p.tobs = d_terminal_obs; p.tobs_out = (d_terminal_obs && h->pn.on && h->pn.cfg.norm_obs) ? h->e_tobs : nullptr;
+    *tobs_norm = p.tobs_out ? p.tobs_out : d_terminal_obs;
+    p.old_rew = h->e_rew; p.rew_out = h->rew + k; p.flags = h->flags + k; p.boot = h->boot + k; p.err = h->ext_err;
+    if (h->ext_mon_window > 0) { p.mon_cur_ret = h->mon_cur_ret; p.mon_cur_len = h->mon_cur_len; p.ep_ret = h->ep_ret + k; p.ep_len = h->ep_len + k; }
+    dim3 grid = xn_grid(E, h->D, &a.epb);
+    if (!p.tobs_out && !a.st_out) grid.y = 1;                                            // no column work and no statistics to carry: the per-env pass alone
+    hipLaunchKernelGGL(ext_norm_record_kernel, grid, dim3(256), 0, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    if (h->pn.on) h->pn.commit(a);
+    *launches += 1;
+    return DRIL_OK;
+}
+// the monitor's arrays of an external handle (those of cfg.monitor_window on a device env, sized by ext_mon_window)
+void xm_free(dril_handle* h) {
+    void* ptrs[] = {h->mon_cur_ret, h->mon_cur_len, h->ep_ret, h->ep_len, h->mon_ring_ret, h->mon_ring_len, h->mon_cnt, h->mon_meta};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    h->mon_cur_ret = h->ep_ret = h->mon_ring_ret = nullptr; h->mon_cur_len = h->ep_len = h->mon_ring_len = nullptr; h->mon_cnt = h->mon_meta = nullptr;
+    h->ext_mon_window = 0;
+}
+int xw_kind_check(dril_handle* h, const char* what) {
+    if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": the handle was not created with DRIL_ENV_EXTERNAL; a built-in env is wrapped at create (cfg.norm_obs / cfg.norm_reward / cfg.monitor_window), a device env plug-in with dril_normalize_enable");
+    return DRIL_OK;
+}
+int xw_between_rollouts(dril_handle* h, const char* what) {
+    if (h->ext_t != 0 || h->ext_acted) return fail(h, DRIL_ERR_INVALID_ARG, std::string(what) + ": a rollout is under way (dril_ext_steps != 0, or an act without its record): switch the wrapper between rollouts, after dril_ext_finish_device");
+    return DRIL_OK;
+}
+#define XN_ON(h, what) do { int _rc = xw_kind_check(h, what); if (_rc) return _rc; \
+    if (!(h)->pn.on) return fail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_ext_normalize_enable has not been called with a configuration)"); } while (0)
 }  // namespace
 // ---- collect_trajectories over HOST envs (DRIL_ENV_EXTERNAL), trajectory.jl:22-78: the caller steps its envs, the device does the rest ----
 DRIL_EXPORT int32_t dril_ext_act(dril_handle* h, const float* obs, void* raw_actions, void* env_actions) {
     NEED(h);
     if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_act: the handle was not created with DRIL_ENV_EXTERNAL");
+    XW_HOST_REFUSED(h, "dril_ext_act");
     if (!obs) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act: null obs");
     if (h->ext_acted) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act: the previous step has no dril_ext_record yet");
     if (h->ext_t >= h->cfg.n_steps) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_act: n_steps env steps are recorded; call dril_ext_finish");
@@ -1392,6 +1495,7 @@ DRIL_EXPORT int32_t dril_ext_act(dril_handle* h, const float* obs, void* raw_act
 DRIL_EXPORT int32_t dril_ext_record(dril_handle* h, const float* rewards, const uint8_t* terminated, const uint8_t* truncated, const float* terminal_obs) {
     NEED(h);
     if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_record: the handle was not created with DRIL_ENV_EXTERNAL");
+    XW_HOST_REFUSED(h, "dril_ext_record");
     if (!rewards || !terminated || !truncated) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_record: null rewards / terminated / truncated");
     if (!h->ext_acted) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_record without a preceding dril_ext_act");
     const size_t E = h->cfg.n_envs, D = h->D, k = (size_t)h->ext_t * E;
@@ -1426,6 +1530,7 @@ DRIL_EXPORT int32_t dril_ext_record(dril_handle* h, const float* rewards, const 
 DRIL_EXPORT int32_t dril_ext_finish(dril_handle* h, const float* last_obs) {
     NEED(h);
     if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_finish: the handle was not created with DRIL_ENV_EXTERNAL");
+    XW_HOST_REFUSED(h, "dril_ext_finish");
     if (!last_obs) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_finish: null last_obs");
     if (h->ext_acted || h->ext_t != h->cfg.n_steps) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_finish: the rollout needs exactly n_steps act/record pairs");
     const size_t E = h->cfg.n_envs, D = h->D;
@@ -1453,6 +1558,11 @@ DRIL_EXPORT int32_t dril_ext_act_device(dril_handle* h, const float* d_obs, void
     if (d_env_actions) { rc = ext_check_ptr(h, "dril_ext_act_device", "d_env_actions", d_env_actions, E * ab); if (rc) return rc; }
     ext_count_begin(h); const int64_t l0 = h->gws.launches;
     rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    if (h->pn.on) {                                                                   // the wrapper's observe: raw -> old_obs and the normalised row in one pass (no copy)
+        int64_t added = 0;
+        rc = xn_observe(h, d_obs, (int64_t)E, h->obs + k * D, true, &added); if (rc) return rc;
+        h->ext_launches += added; h->xw_added[0] += added;
+    } else
     HIPCHK(h, hipMemcpyAsync(h->obs + k * D, d_obs, E * D * 4, hipMemcpyDefault, h->stream));                               // observation -> buffer, :46-47
     const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * A)) : nullptr;
     PolicyArgs p = policy_args(h, h->obs + k * D, (int64_t)E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);     // the host verb's forward: the same bits
@@ -1479,6 +1589,21 @@ DRIL_EXPORT int32_t dril_ext_record_device(dril_handle* h, const float* d_reward
     rc = ext_check_ptr(h, "dril_ext_record_device", "d_truncated", d_truncated, E); if (rc) return rc;
     if (d_terminal_obs) { rc = ext_check_ptr(h, "dril_ext_record_device", "d_terminal_obs", d_terminal_obs, E * D * 4); if (rc) return rc; }
     rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    if (xw_on(h)) {                                                                   // a wrapper on: act! of the wrapper and the record in one kernel, then V(normalised terminal_observation) selected into boot[t]
+        const float* tobs_norm = nullptr; int64_t own = 0;
+        rc = xn_record(h, k, d_rewards, d_terminated, d_truncated, d_terminal_obs, &tobs_norm, &own); if (rc) return rc;
+        const int64_t l0 = h->gws.launches;
+        if (tobs_norm) {
+            PolicyArgs p = policy_args(h, tobs_norm, (int64_t)E, nullptr, nullptr, h->gen_tmp, nullptr, nullptr, 2);
+            HIPCHK(h, run_policy(h, p));
+            HIPCHK(h, generic_select((int64_t)E, d_truncated, h->gen_tmp, h->boot + k, h->stream));
+            own += 1;
+        }
+        h->ext_launches += h->gws.launches - l0 + own; h->xw_added[1] += own - 1;      // (the unwrapped verb's one launch of its own is ext_record_kernel)
+        rc = ext_stream_leave(h, caller_stream); if (rc) return rc;
+        h->ext_t += 1; h->ext_acted = false; h->ext_steps_dev += 1;
+        return DRIL_OK;
+    }
     if (d_terminal_obs) {                                                             // V(terminal_observation), trajectory.jl:57-61: the critic over all E columns, kept where truncated
         const int64_t l0 = h->gws.launches;
         PolicyArgs p = policy_args(h, d_terminal_obs, (int64_t)E, nullptr, nullptr, h->gen_tmp, nullptr, nullptr, 2);
@@ -1499,6 +1624,11 @@ DRIL_EXPORT int32_t dril_ext_finish_device(dril_handle* h, const float* d_last_o
     const size_t E = h->cfg.n_envs, D = h->D;
     int rc = ext_check_ptr(h, "dril_ext_finish_device", "d_last_obs", d_last_obs, E * D * 4); if (rc) return rc;
     rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    if (h->pn.on) {                                                                   // one more observe of the wrapper
+        int64_t added = 0;
+        rc = xn_observe(h, d_last_obs, (int64_t)E, h->e_obs, true, &added); if (rc) return rc;
+        h->ext_launches += added; h->xw_added[2] += added;
+    } else
     HIPCHK(h, hipMemcpyAsync(h->e_obs, d_last_obs, E * D * 4, hipMemcpyDefault, h->stream));
     PolicyArgs p = policy_args(h, h->e_obs, (int64_t)E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);          // V(new_obs) where the last step left the trajectory open, :65-70
     const int64_t l0 = h->gws.launches;
@@ -1506,6 +1636,10 @@ DRIL_EXPORT int32_t dril_ext_finish_device(dril_handle* h, const float* d_last_o
     h->ext_launches += h->gws.launches - l0 + 1;
     h->ext_t = 0; h->noise_set = false;
     rc = compute_gae(h); if (rc) return rc;                                           // compute_advantages! + returns, rollout_buffer.jl:83-87
+    if (h->ext_mon_window > 0) {                                                      // MonitorWrapperEnv: this rollout's finished episodes enter the window in (step, env) order
+        HIPCHK(h, launch_monitor_collect(h->flags, h->ep_ret, h->ep_len, h->cfg.n_envs, h->cfg.n_steps, h->ext_mon_window, h->mon_cnt, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->stream));
+        h->ext_launches += 2; h->xw_added[2] += 2;                                    // (its count and its collect kernel)
+    }
     return ext_finish_drain(h, "dril_ext_finish_device");                             // the drain covers the read of d_last_obs: nothing for caller_stream to wait for
 }
 DRIL_EXPORT int32_t dril_predict_actions_device(dril_handle* h, const float* d_obs, int64_t batch, int32_t deterministic, void* d_raw_actions, void* d_env_actions, void* caller_stream) {
@@ -1523,7 +1657,19 @@ DRIL_EXPORT int32_t dril_predict_actions_device(dril_handle* h, const float* d_o
         HIPCHK(h, hipMalloc(&h->ext_pred_act, B * ab)); HIPCHK(h, dmalloc(&h->ext_pred_lp, B));
         h->ext_pred_cap = batch;
     }
+    const bool nz_eval = h->pn.on && h->pn.cfg.norm_obs;                               // evaluation under the wrapper: the statistics in force, never updated
+    if (nz_eval && batch > h->cfg.n_envs && batch > h->ext_pred_obs_cap) {             // (up to n_envs rows fit e_obs; more: grow-only scratch, counted by dril_ext_wrap_info)
+        if (h->ext_pred_obs) HIPCHK(h, hipFree(h->ext_pred_obs));
+        h->ext_pred_obs = nullptr; h->ext_pred_obs_cap = 0;
+        HIPCHK(h, dmalloc(&h->ext_pred_obs, B * h->D));
+        h->ext_pred_obs_cap = batch; h->xw_allocs += 1;
+    }
     rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    if (nz_eval) {
+        float* scratch = batch > h->cfg.n_envs ? h->ext_pred_obs : h->e_obs; int64_t added = 0;
+        rc = xn_observe(h, d_obs, batch, scratch, false, &added); if (rc) return rc;
+        d_obs = scratch;
+    }
     PolicyArgs a = policy_args(h, d_obs, batch, nullptr, h->ext_pred_act, nullptr, h->ext_pred_lp, nullptr, 0);
     a.deterministic = deterministic ? 1 : 0;
     HIPCHK(h, run_policy(h, a));
@@ -1549,6 +1695,106 @@ DRIL_EXPORT int32_t dril_ext_device_info(const dril_handle* h, struct dril_ext_d
     std::memset(out, 0, sizeof(*out));
     out->steps_device = h->ext_steps_dev; out->steps_host = h->ext_steps_host; out->host_syncs = h->ext_syncs; out->per_dim_bounds = h->ext_bounds_set ? 1 : 0;
     out->launches = h->ext_launches;
+    return DRIL_OK;
+}
+
+// ---- NormalizeWrapperEnv / MonitorWrapperEnv on an external handle (rules and state: dril_norm_wrap.h; kernels: dril_ext_norm.h) ----
+DRIL_EXPORT int32_t dril_ext_normalize_enable(dril_handle* h, const dril_normalize_config* cfg) {
+    NEED(h);
+    { int rc = xw_kind_check(h, "dril_ext_normalize_enable"); if (rc) return rc; }
+    if (h->cfg.world_size > 1) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_normalize_enable: world_size > 1: the batch moments of a data-parallel job need an all-reduce per env step, which is not free of host waits here; run a single rank, or normalise in the env's own arrays");
+    { int rc = xw_between_rollouts(h, "dril_ext_normalize_enable"); if (rc) return rc; }
+    if (!cfg) {                                                                        // the wrapper off: the handle enqueues the launches of a handle that never had it
+        if (!h->pn.on) return DRIL_OK;
+        int rc = sync(h); if (rc) return rc;
+        pn_free(h);
+        return DRIL_OK;
+    }
+    if (const NormErr err = norm_config_check(*cfg, h->D)) return fail(h, err.code, "dril_ext_normalize_enable: " + err.msg);
+    const dril_normalize_config c = norm_config_canonical(*cfg);
+    if (h->pn.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart): its statistics and returns stay
+    { int rc = sync(h); if (rc) return rc; }
+    pn_free(h);
+    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
+    h->pn_rows_cap = 0;
+    hipError_t e = h->pn.alloc((int)D, (size_t)pn_rows((int)E, (int)D, h->pn_rows_cap));   // every array of the wrapper that create did not size: statistics and the partial table
+    if (e == hipSuccess) e = hipMemset(h->env.disc_returns, 0, E * 4);                     // returns, and the cached originals, start at 0
+    if (e == hipSuccess) e = hipMemset(h->e_obs_raw, 0, E * D * 4);
+    if (e == hipSuccess) e = hipMemset(h->e_rew, 0, E * 4);
+    if (e != hipSuccess) { pn_free(h); return fail(h, DRIL_ERR_HIP, std::string("dril_ext_normalize_enable: ") + hipGetErrorString(e)); }
+    h->pn.cfg = c; h->pn.on = true; h->xw_allocs = 0;
+    return sync(h);
+}
+DRIL_EXPORT int32_t dril_ext_normalize_set_training(dril_handle* h, int32_t training) {
+    NEED(h); XN_ON(h, "dril_ext_normalize_set_training");
+    h->pn.cfg.training = training != 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_ext_normalize_get_config(dril_handle* h, dril_normalize_config* cfg) {
+    NEED(h); XN_ON(h, "dril_ext_normalize_get_config");
+    return pn_get_config(h, "dril_ext_normalize_get_config", cfg);
+}
+DRIL_EXPORT int32_t dril_ext_normalize_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
+    NEED(h); XN_ON(h, "dril_ext_normalize_get_stats");
+    return pn_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+}
+DRIL_EXPORT int32_t dril_ext_normalize_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
+    NEED(h); XN_ON(h, "dril_ext_normalize_set_stats");
+    return pn_set_stats(h, "dril_ext_normalize_set_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+}
+DRIL_EXPORT int32_t dril_ext_normalize_get_original(dril_handle* h, float* obs, float* rewards) {
+    NEED(h); XN_ON(h, "dril_ext_normalize_get_original");
+    return pn_get_original(h, "dril_ext_normalize_get_original", obs, rewards);
+}
+DRIL_EXPORT int32_t dril_ext_normalize_get_returns(dril_handle* h, float* returns) {
+    NEED(h); XN_ON(h, "dril_ext_normalize_get_returns");
+    return pn_get_returns(h, "dril_ext_normalize_get_returns", returns);
+}
+DRIL_EXPORT int32_t dril_ext_normalize_reset(dril_handle* h, void* caller_stream) {
+    NEED(h); XN_ON(h, "dril_ext_normalize_reset");
+    int rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->env.disc_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream));   // reset! :118; old_obs follows with the next observe
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_ext_monitor_enable(dril_handle* h, int32_t stats_window) {
+    NEED(h);
+    { int rc = xw_kind_check(h, "dril_ext_monitor_enable"); if (rc) return rc; }
+    if (stats_window < 0) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_monitor_enable: stats_window must be >= 0 (0: off)");
+    { int rc = xw_between_rollouts(h, "dril_ext_monitor_enable"); if (rc) return rc; }
+    if (stats_window == h->ext_mon_window) return DRIL_OK;                             // the window in force (or off while off): nothing changes
+    { int rc = sync(h); if (rc) return rc; }
+    xm_free(h);
+    if (stats_window == 0) return DRIL_OK;
+    const size_t E = (size_t)h->cfg.n_envs, N = (size_t)h->N, W = (size_t)stats_window;
+    hipError_t e = dmalloc(&h->mon_cur_ret, E);
+    if (e == hipSuccess) e = dmalloc(&h->mon_cur_len, E);
+    if (e == hipSuccess) e = dmalloc(&h->ep_ret, N);
+    if (e == hipSuccess) e = dmalloc(&h->ep_len, N);
+    if (e == hipSuccess) e = dmalloc(&h->mon_ring_ret, W);
+    if (e == hipSuccess) e = dmalloc(&h->mon_ring_len, W);
+    if (e == hipSuccess) e = dmalloc(&h->mon_cnt, (size_t)h->cfg.n_steps);
+    if (e == hipSuccess) e = dmalloc(&h->mon_meta, 2);
+    if (e == hipSuccess) e = hipMemset(h->mon_cur_ret, 0, E * 4);                      // fresh sums, an empty window
+    if (e == hipSuccess) e = hipMemset(h->mon_cur_len, 0, E * 4);
+    if (e == hipSuccess) e = hipMemset(h->mon_meta, 0, 8);
+    if (e != hipSuccess) { xm_free(h); return fail(h, DRIL_ERR_HIP, std::string("dril_ext_monitor_enable: ") + hipGetErrorString(e)); }
+    h->ext_mon_window = stats_window;
+    if (!h->pn.on) h->xw_allocs = 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_ext_monitor_get_stats(dril_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
+    NEED(h);
+    { int rc = xw_kind_check(h, "dril_ext_monitor_get_stats"); if (rc) return rc; }
+    if (h->ext_mon_window < 1) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_ext_monitor_get_stats: MonitorWrapperEnv is off (dril_ext_monitor_enable has not been called with a window)");
+    return monitor_window_stats(h, h->ext_mon_window, ep_rew_mean, ep_len_mean, n_episodes);
+}
+DRIL_EXPORT int32_t dril_ext_wrap_info(const dril_handle* h, struct dril_ext_wrap_info* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return DRIL_ERR_INVALID_ARG;
+    if (!h->external) return DRIL_ERR_UNSUPPORTED;
+    std::memset(out, 0, sizeof(*out));
+    out->normalize_on = h->pn.on ? 1 : 0; out->monitor_on = h->ext_mon_window > 0 ? 1 : 0; out->monitor_window = h->ext_mon_window;
+    out->launches_act = h->xw_added[0]; out->launches_record = h->xw_added[1]; out->launches_finish = h->xw_added[2]; out->allocations = h->xw_allocs;
     return DRIL_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include "dril_device.h"
 #include "dril_eval_account.h"   // EvalAcct, eval_account: the episode accounting of an evaluation on the device
+#include "dril_ext_record.h"     // xr_*: the per-env scalar rules of ext_norm_record_kernel (dril_ext_norm.h), host-compilable
 #include "dril_env_kinds.h"   // the built-in env kinds: every launcher below that takes `kind` dispatches through with_env_kind
 
 // The forward of rollout_kernel / rollout_duo_kernel / policy_kernel puts ONE operand on f16 pieces: kTanhScale kWScale W2 (h1 = tanh is bounded, L1 and L3 are f32).

@@ -17,7 +17,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi as capi
-from .host import ACTIVATIONS, Box, Discrete, DrilError, Handle, _normalize_kw
+from .host import ACTIVATIONS, Box, Discrete, DrilError, Handle, _norm_view, _normalize_kw
 
 KINDS = ("Categorical", "DiagGaussian", "SquashedDiagGaussian")
 
@@ -215,7 +215,8 @@ def _norm_of(norm_env):
     h = norm_env if hasattr(norm_env, "norm_get_stats") else getattr(norm_env, "handle", None)
     if h is None:
         raise ValueError("extract_policy(agent, norm_env): the env has no bound handle yet (its statistics live on the device: train or bind first)")
-    kw = _normalize_kw(norm_env) if hasattr(norm_env, "_kw") else None           # DeviceParallelEnv(normalize=...) / DeviceModuleEnv(..., normalize=...)
+    h = _norm_view(h)                                                           # an external handle's wrapper answers through dril_ext_normalize_*
+    kw = _normalize_kw(norm_env) if hasattr(norm_env, "_kw") else None           # DeviceParallelEnv(normalize=...) / DeviceModuleEnv(..., normalize=...) / a wrapped DeviceArrayParallelEnv
     if kw is None and hasattr(h, "normalize_config"):
         try:
             kw = h.normalize_config()                                           # the keywords as the handle holds them (normalize_enable verbs)

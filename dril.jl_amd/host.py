@@ -463,6 +463,7 @@ def _stream_ptr(stream):
     return C.c_void_p(int(stream)) if stream else None
 
 
+@_normalize.normalize_verbs(lambda self, verb: getattr(self.lib, ("dril_normalize_" if verb == "config_default" else "dril_ext_normalize_") + verb), "normalize_", "ext_")
 @_normalize.normalize_verbs(lambda self, verb: getattr(self.lib, "dril_normalize_" + verb), "normalize_")
 class Handle:
     """Owns one dril_handle*; every method is a thin typed wrapper of one C entry point."""
@@ -729,6 +730,29 @@ class Handle:
         if lo.size != self.A or hi.size != self.A:
             raise ValueError(f"low / high: {lo.size} / {hi.size} values where action_dim = {self.A} are expected")
         self._chk(self.lib.dril_ext_set_action_bounds(self._h, self._p(lo), self._p(hi)))
+
+    # NormalizeWrapperEnv / MonitorWrapperEnv around device-resident external envs (dril_ext_normalize_* / dril_ext_monitor_*, docs/external_envs.md section 10, "Wrappers on device-resident arrays"):
+    # ext_normalize_enable, ext_normalize_config, ext_normalize_set_training, ext_normalize_get_stats / _set_stats / _get_original / _get_returns come from
+    # _normalize.normalize_verbs
+    def ext_normalize_reset(self, stream=None):
+        """the wrapper's half of reset! (normalizeWrapperEnv.jl:111-121): returns <- 0, statistics kept; enqueued, no host wait"""
+        self._chk(self.lib.dril_ext_normalize_reset(self._h, _stream_ptr(stream)))
+
+    def ext_monitor_enable(self, stats_window: int):
+        """MonitorWrapperEnv(env, stats_window) around the external envs; 0 switches it off"""
+        self._chk(self.lib.dril_ext_monitor_enable(self._h, int(stats_window)))
+
+    def ext_monitor_stats(self):
+        """(ep_rew_mean, ep_len_mean, n_episodes) of the window: raw rewards, episodes in (step, env) order"""
+        r, l, n = C.c_float(), C.c_float(), C.c_int32()
+        self._chk(self.lib.dril_ext_monitor_get_stats(self._h, C.byref(r), C.byref(l), C.byref(n)))
+        return r.value, l.value, n.value
+
+    def ext_wrap_info(self) -> dict:
+        """which wrappers are on, the launches they added to the act / record / finish calls of the current (or last) rollout, allocations since enable"""
+        info = capi.DrilExtWrapInfo()
+        self._chk(self.lib.dril_ext_wrap_info(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k in ("normalize_on", "monitor_on", "monitor_window", "launches_act", "launches_record", "launches_finish", "allocations")}
 
     def ext_device_info(self) -> dict:
         info = capi.DrilExtDeviceInfo()
@@ -1229,6 +1253,8 @@ class DeviceArrayParallelEnv:
         self._bound_key = None
         self._raw = self._env_actions = None
         self._last_term = self._last_trunc = None
+        self.ext_normalize: Optional[dict] = None                                    # NormalizeWrapperEnv(env, ...) / MonitorWrapperEnv(env, window): the wrappers of the
+        self.ext_monitor_window = 0                                                  # handle (dril_ext_normalize_enable / dril_ext_monitor_enable), switched on by bind
 
     def bind(self, alg: PPO, layer: Optional[ActorCriticLayer] = None) -> Handle:
         key = (tuple(sorted(asdict(alg).items())), None if layer is None else (tuple(layer.hidden_dims), layer.log_std_init, getattr(layer, "activation", "tanh")))
@@ -1240,7 +1266,23 @@ class DeviceArrayParallelEnv:
             if isinstance(asp, Box) and h.cfg.ext_action_low >= h.cfg.ext_action_high:   # per-dimension bounds: the ClampAdapter's table on the device
                 h.ext_set_action_bounds(np.asarray(asp.low, np.float32), np.asarray(asp.high, np.float32))
             self._bound_key = key
+            self._apply_wrappers()
         return self.handle
+
+    def _apply_wrappers(self):
+        """the recorded wrappers on the bound handle (between rollouts): the same normaliser again keeps its statistics"""
+        h = self.handle
+        if h is None:
+            return
+        h.ext_monitor_enable(self.ext_monitor_window)
+        if self.ext_normalize is None:
+            h.ext_normalize_enable(False)
+        else:
+            h.ext_normalize_enable(**self.ext_normalize)
+
+    def monitor_stats(self):
+        """what log_stats logs (env/ep_rew_mean, env/ep_len_mean, episodes in the window), monitorWrapperEnv.jl:64-70"""
+        return self.handle.ext_monitor_stats()
 
     def number_of_envs(self) -> int:
         return self.n_envs
@@ -1253,6 +1295,8 @@ class DeviceArrayParallelEnv:
 
     def reset_(self):
         self.env.reset_()
+        if self.ext_normalize is not None and self.handle is not None:
+            self.handle.ext_normalize_reset(self.stream)                             # reset! of the wrapper: returns <- 0 (normalizeWrapperEnv.jl:111-121)
 
     def observe(self):
         return self.env.observe()
@@ -1330,6 +1374,12 @@ def _stepwise_rollout(h: Handle, env, on_step=None):
 def MonitorWrapperEnv(env: DeviceParallelEnv, stats_window: int = 100) -> DeviceParallelEnv:
     """MonitorWrapperEnv(env, stats_window) (monitorWrapperEnv.jl:15-24): episode return/length statistics from the device
     done flags; `env.handle.monitor_stats()` gives what `log_stats` logs (env/ep_rew_mean, env/ep_len_mean)."""
+    if isinstance(env, HostParallelEnv):
+        raise TypeError("MonitorWrapperEnv: the envs of a HostParallelEnv live on the host and are wrapped there, env by env; the device wrappers take a DeviceParallelEnv or a DeviceArrayParallelEnv")
+    if isinstance(env, DeviceArrayParallelEnv):                                      # the handle's own wrapper (dril_ext_monitor_enable): the same object, the wrapper recorded
+        env.ext_monitor_window = int(stats_window)
+        env._apply_wrappers()
+        return env
     env._kw["monitor_window"] = int(stats_window)
     if env.handle is not None:
         env.handle.close(); env.handle = None
@@ -1340,6 +1390,12 @@ def NormalizeWrapperEnv(env: DeviceParallelEnv, *, training: bool = True, norm_o
                         clip_obs: float = 10.0, clip_reward: float = 10.0, gamma: float = 0.99, epsilon: float = 1e-8) -> DeviceParallelEnv:
     """NormalizeWrapperEnv(env; kwargs...) (normalizeWrapperEnv.jl:71-107).  On device the wrapper is a mode of the same
     handle (running mean/std kernels fused around the env step), so this returns the env with the wrapper switched on."""
+    if isinstance(env, HostParallelEnv):
+        raise TypeError("NormalizeWrapperEnv: the envs of a HostParallelEnv live on the host and are wrapped there (the statistics couple all envs at every step); the device wrappers take a DeviceParallelEnv or a DeviceArrayParallelEnv")
+    if isinstance(env, DeviceArrayParallelEnv):                                      # the handle's own wrapper (dril_ext_normalize_enable): the same object, the wrapper recorded
+        env.ext_normalize = dict(training=training, norm_obs=norm_obs, norm_reward=norm_reward, clip_obs=clip_obs, clip_reward=clip_reward, gamma=gamma, epsilon=epsilon)
+        env._apply_wrappers()
+        return env
     env._kw["normalize"] = dict(training=training, norm_obs=norm_obs, norm_reward=norm_reward, clip_obs=clip_obs,
                                 clip_reward=clip_reward, gamma=gamma, epsilon=epsilon)
     if env.handle is not None:
@@ -1353,8 +1409,34 @@ def NormalizeWrapperEnv(env: DeviceParallelEnv, *, training: bool = True, norm_o
 
 
 def _normalize_kw(env: DeviceParallelEnv) -> Optional[dict]:
-    """the wrapper's keywords: cfg.norm_* of a built-in env, the `normalize` keyword of a DeviceModuleEnv"""
+    """the wrapper's keywords: cfg.norm_* of a built-in env, the `normalize` keyword of a DeviceModuleEnv, the recorded wrapper of a DeviceArrayParallelEnv"""
+    if isinstance(env, DeviceArrayParallelEnv):
+        return env.ext_normalize
     return env._kw["normalize"] if env._kw["normalize"] is not None else getattr(env, "module_normalize", None)
+
+
+class _ExtNormView:
+    """the normaliser of an external handle (dril_ext_normalize_*) under the names the wrapper helpers use for every other handle"""
+
+    def __init__(self, h: Handle):
+        self.h = h
+
+    def norm_get_stats(self) -> dict:
+        return self.h.ext_normalize_get_stats()
+
+    def norm_set_stats(self, *a, **kw):
+        return self.h.ext_normalize_set_stats(*a, **kw)
+
+    def norm_get_original(self):
+        return self.h.ext_normalize_get_original()
+
+    def normalize_config(self) -> dict:
+        return self.h.ext_normalize_config()
+
+
+def _norm_view(h):
+    """h, or the view of its dril_ext_normalize_* verbs when h is a PPO handle on external envs (Handle.norm_get_stats itself is unchanged there)"""
+    return _ExtNormView(h) if isinstance(h, Handle) and h.cfg.env_kind == capi.ENV_EXTERNAL else h
 
 
 def unnormalize_obs_(obs: np.ndarray, env: DeviceParallelEnv) -> np.ndarray:
@@ -1362,7 +1444,7 @@ def unnormalize_obs_(obs: np.ndarray, env: DeviceParallelEnv) -> np.ndarray:
     kw = _normalize_kw(env)
     if kw is None or not kw["norm_obs"]:
         return obs
-    st = env.handle.norm_get_stats()
+    st = _norm_view(env.handle).norm_get_stats()
     obs *= np.sqrt(st["obs_var"] + np.float32(kw["epsilon"])); obs += st["obs_mean"]
     return obs
 
@@ -1372,16 +1454,16 @@ def unnormalize_rewards_(rewards: np.ndarray, env: DeviceParallelEnv) -> np.ndar
     kw = _normalize_kw(env)
     if kw is None or not kw["norm_reward"]:
         return rewards
-    rewards *= np.sqrt(np.float32(env.handle.norm_get_stats()["ret_var"]) + np.float32(kw["epsilon"]))
+    rewards *= np.sqrt(np.float32(_norm_view(env.handle).norm_get_stats()["ret_var"]) + np.float32(kw["epsilon"]))
     return rewards
 
 
 def get_original_obs(env: DeviceParallelEnv) -> np.ndarray:
-    return env.handle.norm_get_original()[0]
+    return _norm_view(env.handle).norm_get_original()[0]
 
 
 def get_original_rewards(env: DeviceParallelEnv) -> np.ndarray:
-    return env.handle.norm_get_original()[1]
+    return _norm_view(env.handle).norm_get_original()[1]
 
 
 # --------------------------------------------------------------------------------------------
@@ -1466,6 +1548,7 @@ def train_(agent: Agent, env: DeviceParallelEnv, alg: PPO, max_steps: int, callb
     timer["setup"] = time.perf_counter() - t0
     learn_stats = {k: [] for k in _STAT_KEYS}
     env.last_f32_paths = []
+    env.last_monitor_stats = []
     loc = dict.fromkeys(TRAINING_START_LOCALS)                                                # the keys test/test_callbacks.jl:25-27 looks for in Base.@locals
     loc.update(agent=agent, env=env, alg=alg, iterations=iterations, total_steps=iterations * per_iter, max_steps=max_steps, n_steps=alg.n_steps,
                n_envs=env.n_envs, roll_buffer=None, total_fps=learn_stats["fps"], callbacks=cbs, learn_stats=learn_stats)
@@ -1511,6 +1594,8 @@ def train_(agent: Agent, env: DeviceParallelEnv, alg: PPO, max_steps: int, callb
             learn_stats["losses"].append(st.loss)
             learn_stats["explained_variances"].append(st.explained_variance)
             learn_stats["grad_norms"].append(st.grad_norm)
+            if isinstance(env, DeviceArrayParallelEnv) and env.ext_monitor_window:
+                env.last_monitor_stats.append(env.monitor_stats())                            # log_stats: env/ep_rew_mean, env/ep_len_mean per iteration (monitorWrapperEnv.jl:64-70)
             env.last_f32_paths.append(int(st.f32_path))                                       # per iteration: 0 default kernels, 1 redone on exact f32, 2 run directly on exact f32 (learn_stats keeps the reference's keys)
         timer["training_loop"] = time.perf_counter() - t1
         timer["collect_rollout"] = t_roll

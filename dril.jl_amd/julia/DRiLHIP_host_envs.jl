@@ -154,3 +154,64 @@ function train!(agent::PPOAgent, w::OnDevice, alg::PPO{T}, max_steps::Int; ad_ty
     end
 end
 
+
+# ---- NormalizeWrapperEnv / MonitorWrapperEnv around device-resident external envs (dril_ext_normalize_* / dril_ext_monitor_*, include/dril_hip.h): thin calls on a
+# handle created with DRIL_ENV_EXTERNAL whose rollout goes through the dril_ext_*_device verbs.  h: the dril_handle*; device arrays travel as Ptr{Cvoid} ----
+struct DrilExtNormalizeConfig                                            # struct dril_normalize_config
+    training::Int32; norm_obs::Int32; norm_reward::Int32
+    clip_obs::Float32; clip_reward::Float32
+    gamma::Float32; epsilon::Float32
+    reserved::Int32
+end
+struct DrilExtWrapInfo                                                   # struct dril_ext_wrap_info
+    normalize_on::Int32; monitor_on::Int32; monitor_window::Int32; reserved0::Int32
+    launches_act::Int64; launches_record::Int64; launches_finish::Int64; allocations::Int64
+    reserved::NTuple{2, Int64}
+end
+# nz: the wrapper's keywords as a NamedTuple (missing keys take the reference's defaults, normalizeWrapperEnv.jl:71-80); nothing switches the wrapper off
+function ext_normalize_enable!(h::Ptr{Cvoid}, nz::Union{Nothing, NamedTuple})
+    isnothing(nz) && return check(ccall((:dril_ext_normalize_enable, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, C_NULL), h)
+    g(k, d) = get(nz, k, d)
+    cfg = Ref(DrilExtNormalizeConfig(Int32(g(:training, true)), Int32(g(:norm_obs, true)), Int32(g(:norm_reward, true)),
+        Float32(g(:clip_obs, 10.0f0)), Float32(g(:clip_reward, 10.0f0)), Float32(g(:gamma, 0.99f0)), Float32(g(:epsilon, 1.0f-8)), Int32(0)))
+    return check(ccall((:dril_ext_normalize_enable, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilExtNormalizeConfig}), h, cfg), h)
+end
+function ext_normalize_config(h::Ptr{Cvoid})
+    cfg = Ref{DrilExtNormalizeConfig}()
+    check(ccall((:dril_ext_normalize_get_config, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilExtNormalizeConfig}), h, cfg), h)
+    return cfg[]
+end
+ext_normalize_set_training!(h::Ptr{Cvoid}, training::Bool) = check(ccall((:dril_ext_normalize_set_training, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(training)), h)
+function ext_normalize_get_stats(h::Ptr{Cvoid}, D::Integer)
+    om = Vector{Float32}(undef, D); ov = Vector{Float32}(undef, D); oc = Ref{Int64}(0); rc = Ref{Int64}(0); rm = Ref{Float32}(0); rv = Ref{Float32}(0)
+    GC.@preserve om ov check(ccall((:dril_ext_normalize_get_stats, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ref{Int64}, Ref{Float32}, Ref{Float32}, Ref{Int64}),
+        h, om, ov, oc, rm, rv, rc), h)
+    return (obs_mean = om, obs_var = ov, obs_count = oc[], ret_mean = rm[], ret_var = rv[], ret_count = rc[])
+end
+function ext_normalize_set_stats!(h::Ptr{Cvoid}, st)
+    om = Vector{Float32}(st.obs_mean); ov = Vector{Float32}(st.obs_var)
+    GC.@preserve om ov check(ccall((:dril_ext_normalize_set_stats, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int64, Float32, Float32, Int64),
+        h, om, ov, Int64(st.obs_count), Float32(st.ret_mean), Float32(st.ret_var), Int64(st.ret_count)), h)
+end
+function ext_normalize_get_original(h::Ptr{Cvoid}, D::Integer, E::Integer)
+    obs = Matrix{Float32}(undef, D, E); rew = Vector{Float32}(undef, E)
+    GC.@preserve obs rew check(ccall((:dril_ext_normalize_get_original, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h, obs, rew), h)
+    return obs, rew
+end
+function ext_normalize_get_returns(h::Ptr{Cvoid}, E::Integer)
+    r = Vector{Float32}(undef, E)
+    GC.@preserve r check(ccall((:dril_ext_normalize_get_returns, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}), h, r), h)
+    return r
+end
+ext_normalize_reset!(h::Ptr{Cvoid}, stream::Ptr{Cvoid} = C_NULL) = check(ccall((:dril_ext_normalize_reset, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, stream), h)
+ext_monitor_enable!(h::Ptr{Cvoid}, stats_window::Integer) = check(ccall((:dril_ext_monitor_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(stats_window)), h)
+function ext_monitor_stats(h::Ptr{Cvoid})
+    r = Ref{Float32}(0); l = Ref{Float32}(0); n = Ref{Int32}(0)
+    check(ccall((:dril_ext_monitor_get_stats, LIB[]), Int32, (Ptr{Cvoid}, Ref{Float32}, Ref{Float32}, Ref{Int32}), h, r, l, n), h)
+    return (ep_rew_mean = r[], ep_len_mean = l[], n_episodes = n[])
+end
+function ext_wrap_info(h::Ptr{Cvoid})
+    info = Ref{DrilExtWrapInfo}()
+    check(ccall((:dril_ext_wrap_info, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilExtWrapInfo}), h, info), h)
+    return info[]
+end

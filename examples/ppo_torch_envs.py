@@ -7,7 +7,11 @@
 The library takes the tensors through __cuda_array_interface__ (dril_ext_act_device / dril_ext_record_device / dril_ext_finish_device): every call of a
 rollout enqueues on the device and returns, the one host wait is the last call's (docs/external_envs.md section 10, "Device-resident arrays").
 
-usage: python examples/ppo_torch_envs.py [n_envs=1024] [iterations=30]"""
+--normalize / --monitor put NormalizeWrapperEnv / MonitorWrapperEnv around the env: the library's own wrappers on the device arrays (dril_ext_normalize_enable /
+dril_ext_monitor_enable, docs/external_envs.md section 10, "Wrappers on device-resident arrays") — running statistics, clipped normalised observations and rewards, episode statistics of the raw
+rewards — and the rollout still makes no host wait before its last call.
+
+usage: python examples/ppo_torch_envs.py [n_envs=1024] [iterations=30] [--normalize] [--monitor]"""
 import math
 import sys
 from pathlib import Path
@@ -64,10 +68,21 @@ def mean_return(agent, env, episodes):
     return pkg.evaluate_agent(agent, env, n_eval_episodes=episodes, deterministic=True)["mean_reward"]
 
 
+def make_env(n_envs, normalize=False, monitor=False, max_steps=200):
+    env = pkg.DeviceArrayParallelEnv(TorchPendulums(n_envs, max_steps=max_steps), stream=lambda: torch.cuda.current_stream().cuda_stream)
+    if monitor:
+        env = pkg.MonitorWrapperEnv(env, 100)                                        # inside the normaliser: raw returns
+    if normalize:
+        env = pkg.NormalizeWrapperEnv(env, gamma=0.95)
+    return env
+
+
 def main():
-    n_envs = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    iters = int(sys.argv[2]) if len(sys.argv) > 2 else 30
-    env = pkg.DeviceArrayParallelEnv(TorchPendulums(n_envs), stream=lambda: torch.cuda.current_stream().cuda_stream)
+    flags = {a for a in sys.argv[1:] if a.startswith("--")}
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    n_envs = int(args[0]) if len(args) > 0 else 1024
+    iters = int(args[1]) if len(args) > 1 else 30
+    env = make_env(n_envs, normalize="--normalize" in flags, monitor="--monitor" in flags)
     alg = pkg.PPO(n_steps=200, batch_size=n_envs * 200 // 8, epochs=8, learning_rate=1e-3, gamma=0.95)
     agent = pkg.Agent(pkg.ActorCriticLayer(env.observation_space(), env.action_space(), hidden_dims=(64, 64)), alg, seed=0)
     print(f"before: mean return {mean_return(agent, env, n_envs):9.1f}")
@@ -75,6 +90,11 @@ def main():
     info = env.handle.ext_device_info()
     print(f"after {iters} iterations ({timer['training_loop']:.1f} s, rollouts {timer['collect_rollout']:.1f} s, updates {timer['epoch loop']:.2f} s): mean return {mean_return(agent, env, n_envs):9.1f}; "
           f"last rollout: {info['steps_device']} steps through the device verbs, {info['host_syncs']} host waits before its last call, {info['launches']} launches")
+    if "--monitor" in flags:
+        print("monitor window: mean return %.1f, mean length %.1f over %d episodes" % env.monitor_stats())
+    if "--normalize" in flags:
+        st = env.handle.ext_normalize_get_stats()
+        print(f"normaliser: {st['obs_count']} observations, mean {st['obs_mean'].round(3)}, var {st['obs_var'].round(3)}; return variance {st['ret_var']:.3f}")
 
 
 if __name__ == "__main__":

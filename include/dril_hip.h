@@ -428,6 +428,62 @@ struct dril_ext_device_info {
 };
 int32_t dril_ext_device_info(const dril_handle* h, struct dril_ext_device_info* out);
 
+/* ---- NormalizeWrapperEnv / MonitorWrapperEnv around the envs of a DRIL_ENV_EXTERNAL handle, honoured by the DEVICE-ARRAY verbs (docs/external_envs.md section 10, "Wrappers on device-resident arrays").
+ * The env arrays stay the caller's; the wrappers are the library's and sit between them and the rollout buffer, so nothing leaves the device:
+ *   dril_ext_act_device(d_obs)      observe (normalizeWrapperEnv.jl:123-137): old_obs <- the raw observation; with training && norm_obs the observation statistics
+ *       are updated from the batch over the E envs; row t of DRIL_BUF_OBSERVATIONS holds the observation normalised with the NEW statistics and clipped (the raw bits
+ *       with norm_obs == 0), and the forward reads that row.
+ *   dril_ext_record_device(...)     act! (:139-165): old_rewards <- the raw rewards; with training && norm_reward returns = returns * gamma + reward and the return
+ *       statistics are updated; row t of DRIL_BUF_REWARDS holds reward / sqrt(ret_var + epsilon) clipped; `returns` of finished envs go to 0; the terminal
+ *       observation of a truncated env is normalised with the observation statistics in force (before the following observe) into an array of the handle's own —
+ *       d_terminal_obs is not written — and DRIL_BUF_BOOTSTRAP is V of that; rows of envs that were not truncated are never selected.
+ *   dril_ext_finish_device(d_last_obs)   one more observe; DRIL_BUF_LAST_VALUES = V(normalised last observation).  obs_count grows by n_envs * (n_steps + 1) per
+ *       rollout and ret_count by n_envs * n_steps.  A rollout that finish reports as discarded (the sticky terminal_obs error) keeps its statistics updates: they
+ *       were enqueued.
+ *   dril_predict_actions_device     evaluation: normalises with the statistics in force and never updates them, whatever `training` says; nothing else of the
+ *       wrapper is touched.
+ *   MonitorWrapperEnv sits inside the normaliser: per-env running return (float32, step order) and length of RAW rewards; an episode enters the window where
+ *       terminated | truncated, in (step, env) order, when dril_ext_finish_device collects the rollout's rows.
+ * With a wrapper on, act / record still make no host wait, no allocation and no memset (dril_ext_device_info.host_syncs stays 0): per verb at most two launches more
+ * than without (batch moments, then one apply kernel that also replaces the unwrapped verb's device-to-device copy of the observation); the monitor's window costs
+ * finish the two launches of its collector.  With both wrappers off a handle enqueues exactly what it did before these verbs existed.
+ * training == 0: statistics are frozen and `returns` changes only by the reset of finished envs.
+ * Refusals (the handle is left as it was): DRIL_ERR_UNSUPPORTED on a handle that is not DRIL_ENV_EXTERNAL (built-in envs: cfg.norm_* / cfg.monitor_window; plug-ins:
+ * dril_normalize_enable) and with world_size > 1 (single rank only); DRIL_ERR_INVALID_ARG for a negative or NaN clip / epsilon, and for an enable inside a rollout
+ * (dril_ext_steps != 0 or an act without its record).  While either wrapper is on, the HOST verbs dril_ext_act / dril_ext_record / dril_ext_finish return
+ * DRIL_ERR_UNSUPPORTED: a wrapped rollout is device verbs only.  dril_normalize_* and cfg.norm_* / cfg.monitor_window stay refused on an external handle. */
+/* a fresh wrapper (mean 0, var 1, counts 0, returns 0); the same configuration up to `training` keeps statistics and returns and sets `training`; NULL: off.
+ * Every array of the wrapper is allocated here */
+int32_t dril_ext_normalize_enable(dril_handle* h, const dril_normalize_config* cfg);
+/* as the dril_normalize_* verbs of the same names; DRIL_ERR_NOT_INITIALISED while the wrapper is off.  The getters drain the handle's stream */
+int32_t dril_ext_normalize_get_config(dril_handle* h, dril_normalize_config* cfg);
+int32_t dril_ext_normalize_set_training(dril_handle* h, int32_t training);
+int32_t dril_ext_normalize_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count);
+int32_t dril_ext_normalize_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count);
+int32_t dril_ext_normalize_get_original(dril_handle* h, float* obs, float* rewards);
+int32_t dril_ext_normalize_get_returns(dril_handle* h, float* returns);
+/* the wrapper's half of reset! (:111-121): returns <- 0, statistics kept.  Enqueued on the handle's stream behind everything it has enqueued; no host wait.
+ * caller_stream: as in the device verbs (the handle's stream waits for it first) */
+int32_t dril_ext_normalize_reset(dril_handle* h, void* caller_stream);
+/* MonitorWrapperEnv(env, stats_window): 0 switches it off; the window in force again keeps it.  Between rollouts only */
+int32_t dril_ext_monitor_enable(dril_handle* h, int32_t stats_window);
+/* what dril_monitor_get_stats reports for a device env; DRIL_ERR_NOT_INITIALISED while the monitor is off */
+int32_t dril_ext_monitor_get_stats(dril_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes);
+/* A struct tag only: the verb below has the same name */
+struct dril_ext_wrap_info {
+    int32_t normalize_on;      /* 1 while dril_ext_normalize_enable is in force */
+    int32_t monitor_on;        /* 1 while dril_ext_monitor_enable is in force */
+    int32_t monitor_window;
+    int32_t reserved0;
+    int64_t launches_act;      /* launches the wrappers ADDED to the act calls of the current (or last) rollout, against the same calls with the wrappers off */
+    int64_t launches_record;   /* ... to its record calls */
+    int64_t launches_finish;   /* ... to its finish call */
+    int64_t allocations;       /* device allocations a wrapper made inside act / record / finish / predict since the last enable: stays 0 over rollouts (a
+                                  dril_predict_actions_device batch larger than n_envs grows a scratch array once and is counted) */
+    int64_t reserved[2];
+};
+int32_t dril_ext_wrap_info(const dril_handle* h, struct dril_ext_wrap_info* out);
+
 /* ---- rollout --------------------------------------------------------------- */
 /* collect_rollout!(buffer, agent, alg, env): rollout_buffer.jl:46-90 =
  * collect_trajectories trajectory.jl:22-78 + compute_advantages! :80-102 + returns :87.
