@@ -132,6 +132,12 @@ class DrilSacExtDeviceInfo(C.Structure):
                 ("pending_updates", C.c_int32), ("pending_capacity", C.c_int32), ("per_dim_bounds", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class DrilSacExtWrapInfo(C.Structure):
+    """struct dril_sac_ext_wrap_info, include/dril_sac.h"""
+    _fields_ = [("normalize_on", C.c_int32), ("monitor_on", C.c_int32), ("monitor_window", C.c_int32), ("reserved0", C.c_int32), ("launches_act", C.c_int64),
+                ("launches_push", C.c_int64), ("allocations", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
 class DrilNormalizeConfig(C.Structure):
     """struct dril_normalize_config (include/dril_hip.h) and struct dril_sac_normalize_config (include/dril_sac.h): the keywords of NormalizeWrapperEnv,
     normalizeWrapperEnv.jl:71-80, in one layout for both verb families"""
@@ -347,6 +353,18 @@ _SAC_SIG = {
     "normalize_set_stats": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64]),
     "normalize_get_original": (C.c_int32, [_P, _P, _P]),
     "normalize_get_returns": (C.c_int32, [_P, _P]),
+    "ext_normalize_enable": (C.c_int32, [_P, C.POINTER(DrilSacNormalizeConfig)]),
+    "ext_normalize_get_config": (C.c_int32, [_P, C.POINTER(DrilSacNormalizeConfig)]),
+    "ext_normalize_set_training": (C.c_int32, [_P, C.c_int32]),
+    "ext_normalize_get_stats": (C.c_int32, [_P, _P, _P, _PI64, _PF, _PF, _PI64]),
+    "ext_normalize_set_stats": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64]),
+    "ext_normalize_get_original": (C.c_int32, [_P, _P, _P]),
+    "ext_normalize_get_returns": (C.c_int32, [_P, _P]),
+    "ext_normalize_reset": (C.c_int32, [_P, _P]),
+    "ext_collection_begin": (C.c_int32, [_P]),
+    "ext_monitor_enable": (C.c_int32, [_P, C.c_int32]),
+    "ext_monitor_get_stats": (C.c_int32, [_P, _PF, _PF, C.POINTER(C.c_int32)]),
+    "ext_wrap_info": (C.c_int32, [_P, C.POINTER(DrilSacExtWrapInfo)]),
 }
 _SIG.update({"dril_sac_" + k: v for k, v in _SAC_SIG.items()})
 # every symbol include/dril_policy.h declares

@@ -91,10 +91,10 @@ _NORM_KEYS = ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_co
 def _norm_handle_kw(env):
     """(the object with norm_get_stats / norm_set_stats, the wrapper's keywords or None): a DeviceParallelEnv with NormalizeWrapperEnv and a bound PPO handle, or a
     SacHandle with the wrapper on (dril_sac_normalize_enable) — `replay_buffer.handle` after sac_train_"""
-    from .host import _norm_view, _normalize_kw                           # an external handle's wrapper answers through dril_ext_normalize_*
+    from .host import _env_handle, _norm_view, _normalize_kw               # an external handle's wrapper answers through dril_ext_normalize_* / dril_sac_ext_normalize_*
     if hasattr(env, "norm_get_stats"):
         return _norm_view(env), None
-    return _norm_view(env.handle), _normalize_kw(env)
+    return _norm_view(_env_handle(env)), _normalize_kw(env)
 
 
 def save_normalization_stats(env, filepath, **keywords) -> str:

@@ -35,6 +35,7 @@
 #include "dril_env_side.h"     // DeviceEnvs: the envs this handle steps on the device (a built-in Box kind or a device env plug-in), shared with the PPO handle
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_ext_stream.h"   // the pointer rule and the stream hand-over of the device-array verbs, shared with the PPO handle
+#include "dril_ext_record.h"   // the per-env rules of a recorded step under the wrappers of an external handle (flags, sticky error, returns reset, the monitor's sums)
 
 using namespace dril;
 
@@ -1163,6 +1164,7 @@ __global__ __launch_bounds__(256) void sac_eval_account_kernel(EvalAcctArgs a, c
 // hundreds of steps; a SAC collection is train_freq steps, usually ONE, and a second dependent launch would add a launch gap to every env step — so the count is
 // the first pass of the same workgroup here, and a collection in which no episode ended (nearly all of them) leaves after it.
 constexpr int kMonBlock = 1024;
+constexpr int kXpPool = 4096;                       // HIP events of an external handle under cfg.profile_events: 1 024 env steps (act + push) between two flushes
 __global__ __launch_bounds__(kMonBlock) void sac_monitor_window_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ ep_ret, const int32_t* __restrict__ ep_len,
                                                                        int n, int W, float* ring_ret, int32_t* ring_len, int* meta) {
     __shared__ int wsum[kMonBlock / 64], s_total, s_base;
@@ -1286,6 +1288,7 @@ __global__ __launch_bounds__(256) void sac_ext_push_kernel(PushArgs g, int* err)
     }
     sac_push_block(g, e0, n);
 }
+#include "dril_sac_ext_norm.h"   // NormalizeWrapperEnv / MonitorWrapperEnv on such a handle (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable): the act and push apply kernels
 
 }  // namespace
 
@@ -1343,6 +1346,14 @@ struct dril_sac_handle {
     int64_t fwd_launches = 0;                        // kernels enqueued through gemm / gemm_pair / the elementwise first layer since create: what `launches` of the info struct is counted from
     float* pend_stats = nullptr; double* pend_ssq = nullptr; int pend_n = 0; std::vector<void*> pend_free;
     int64_t ext_steps_dev = 0, ext_steps_host = 0, ext_syncs = 0, ext_flushes = 0, ext_launches = 0;
+    // NormalizeWrapperEnv / MonitorWrapperEnv on an external handle (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable) live in nz / nz_* / mon_* above, which
+    // the built-in verbs never touch on such a handle.  xw_begin: the next act opens a collection (dril_sac_ext_collection_begin); xw_live: one is in progress (cleared
+    // by enable / set_stats / normalize_reset); the counters of dril_sac_ext_wrap_info
+    bool xw_begin = false, xw_live = false; int64_t xw_launches_act = 0, xw_launches_push = 0;
+    // cfg.profile_events on an external handle: HIP events around what act_device and push_device enqueue (a pair per call, recorded and never waited for); dril_sac_flush
+    // reads them after its drain into collect_ms / collect_steps (dril_sac_profile_get).  The pool is created at create (kXpPool events: nothing is created inside the
+    // sync-free verbs) and re-used after every flush; calls made while it is full are not timed
+    std::vector<hipEvent_t> xp_events; size_t xp_n = 0, xp_pairs = 0;
     // injected inputs (tests)
     float* collect_noise = nullptr; size_t collect_noise_count = 0;
     int inj_updates = 0; long long* inj_idx = nullptr; float *inj_ne = nullptr, *inj_nn = nullptr, *inj_np = nullptr;
@@ -1670,14 +1681,16 @@ int nz_ensure_raw(dril_sac_handle* h) {
     return DRIL_OK;
 }
 // norm_moments_kernel over nz_old_obs (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
-int nz_moments(dril_sac_handle* h, bool obs, bool ret, int* rows) {
+// (raw / rew: the arrays — the handle's own, or the caller's const ones on an external handle; null: that half is not summed)
+int nz_moments_over(dril_sac_handle* h, const float* raw, const float* rew, int* rows) {
     const int E = h->cfg.n_envs, D = h->D, R = std::max(kEnvsPerBlock, (E + kNzMaxRows - 1) / kNzMaxRows);
     *rows = (E + R - 1) / R;
-    const NormMomArgs m{E, D, R, obs ? h->nz_old_obs : nullptr, ret ? h->e_rew : nullptr, h->nz_returns, h->nz.cfg.gamma, h->nz.partials};
-    hipLaunchKernelGGL(norm_moments_kernel<kNzTile>, dim3(*rows, obs && D > 64 ? (D + kNzTile - 1) / kNzTile : 1), dim3(256), 0, h->stream, m);
+    const NormMomArgs m{E, D, R, raw, rew, h->nz_returns, h->nz.cfg.gamma, h->nz.partials};
+    hipLaunchKernelGGL(norm_moments_kernel<kNzTile>, dim3(*rows, raw && D > 64 ? (D + kNzTile - 1) / kNzTile : 1), dim3(256), 0, h->stream, m);
     SHIP(h, hipGetLastError());
     return DRIL_OK;
 }
+int nz_moments(dril_sac_handle* h, bool obs, bool ret, int* rows) { return nz_moments_over(h, obs ? h->nz_old_obs : nullptr, ret ? h->e_rew : nullptr, rows); }
 // sac_norm_apply_kernel over the table of `rows` rows the moments launch wrote
 int nz_apply(dril_sac_handle* h, NzApplyArgs p, int rows, bool upd_obs, bool upd_ret) {
     NormWrapArgs& a = p.w;
@@ -1909,6 +1922,7 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
     for (void* p : ptrs) if (p) hipFree(p);
     if (h->ev_a) hipEventDestroy(h->ev_a); if (h->ev_b) hipEventDestroy(h->ev_b);
     for (hipEvent_t e : h->it_events) hipEventDestroy(e);
+    for (hipEvent_t e : h->xp_events) hipEventDestroy(e);
     if (h->it_stamps) hipFree(h->it_stamps);
     if (h->col_h1p) hipFree(h->col_h1p); if (h->col_w2p) hipFree(h->col_w2p); if (h->col_flags) hipFree(h->col_flags);
     void* mon_eval[] = {h->mon_cur_ret, h->mon_cur_len, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->mon_ep_ret, h->mon_ep_len, h->mon_flags,
@@ -2070,6 +2084,7 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     if (ext) {                                                                         // the device-array verbs: hand-over events and the sticky error word and the pending statistics table
         CHK(hipEventCreateWithFlags(&h->ext_ev_in, hipEventDisableTiming)); CHK(hipEventCreateWithFlags(&h->ext_ev_out, hipEventDisableTiming));
         CHK(smalloc(&h->ext_err, 1)); CHK(hipHostMalloc((void**)&h->ext_err_host, 4)); *h->ext_err_host = 0;
+        if (cfg->profile_events) for (int i = 0; i < kXpPool; ++i) { hipEvent_t e = nullptr; CHK(hipEventCreate(&e)); h->xp_events.push_back(e); }   // (dril_sac_profile_get on this path: act / push pairs)
         // the pending statistics table of dril_sac_update_enqueue: allocated HERE, not on first use — an allocation and its fill would be a host wait inside a sync-free verb
         CHK(smalloc(&h->pend_stats, (size_t)DRIL_SAC_PENDING_CAPACITY * 8)); CHK(smalloc(&h->pend_ssq, (size_t)DRIL_SAC_PENDING_CAPACITY * (h->adam_blocks_c + h->end_blocks)));
     }
@@ -2204,7 +2219,7 @@ DRIL_EXPORT int32_t dril_policy_from_sac_handle(dril_sac_handle* h, int32_t with
     SHIP(h, hipMemcpy(tb, h->act_bounds, sizeof(tb), hipMemcpyDeviceToHost));
     for (int a = 0; a < h->A; ++a) { d.action_low[a] = tb[a]; d.action_high[a] = tb[kMaxA + a]; }
     if (with_norm) {
-        if (!h->nz.on) return refuse(DRIL_ERR_NOT_INITIALISED, "dril_policy_from_sac_handle: with_norm = 1, but the handle has no NormalizeWrapperEnv (dril_sac_normalize_enable)");
+        if (!h->nz.on) return refuse(DRIL_ERR_NOT_INITIALISED, "dril_policy_from_sac_handle: with_norm = 1, but the handle has no NormalizeWrapperEnv (dril_sac_normalize_enable; a DRIL_ENV_EXTERNAL handle: dril_sac_ext_normalize_enable)");
         d.has_norm = 1; d.clip_obs = h->nz.cfg.clip_obs; d.epsilon = h->nz.cfg.epsilon;
         s.obs_mean = h->nz.half(h->nz.cur); s.obs_var = s.obs_mean + h->D;
     }
@@ -2252,6 +2267,7 @@ DRIL_EXPORT int32_t dril_sac_ext_push(dril_sac_handle* h, const float* obs, cons
     if (!h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the handle was not created with DRIL_ENV_EXTERNAL");
     if (!obs || !stored_actions || !rewards || !terminated || !truncated || !next_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: null pointer");
     if (h->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: a dril_sac_ext_act_device step is pending; dril_sac_ext_push_device completes it");
+    if (h->nz.on || h->mon_window) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: wrapper on: use the device verbs, or wrap the host env on the host (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable are honoured by dril_sac_ext_act_device / _push_device only)");
     const size_t E = h->cfg.n_envs, D = h->D, A = h->A;
     bool any_trunc = false; for (size_t e = 0; e < E; ++e) any_trunc = any_trunc || truncated[e] != 0;
     if (any_trunc && !terminal_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: truncated envs need terminal_obs");
@@ -2288,6 +2304,15 @@ struct StreamHandOver {
     hipError_t give() { given = true; return ext_stream_give(h->stream, h->ext_ev_out, caller); }
     ~StreamHandOver() { if (!given && ext_stream_give(h->stream, h->ext_ev_out, caller) != hipSuccess) (void)hipGetLastError(); }
 };
+// cfg.profile_events: a pair of events of the handle's pool around what one act or push enqueues.  The scope takes the pair when the pool (created with the handle)
+// has one left — a call made while it is full is not timed, nothing is ever created here — and a verb that fails between its two marks gives the pair back, so the
+// pool always holds whole pairs
+struct XpScope {
+    dril_sac_handle* h; size_t n0; bool on, ok = false;
+    explicit XpScope(dril_sac_handle* h_) : h(h_), n0(h_->xp_n), on(h_->xp_n + 2 <= h_->xp_events.size()) {}
+    hipError_t mark() { if (!on) return hipSuccess; const hipError_t e = hipEventRecord(h->xp_events[h->xp_n], h->stream); if (e == hipSuccess) h->xp_n += 1; return e; }
+    ~XpScope() { if (!ok) h->xp_n = n0; }
+};
 int sac_check_ptr(dril_sac_handle* h, const char* verb, const char* name, const void* p, size_t bytes) {
     const std::string msg = ext_ptr_problem(h->cfg.device, verb, name, p, bytes);
     return msg.empty() ? DRIL_OK : sfail(h, DRIL_ERR_INVALID_ARG, msg);
@@ -2303,6 +2328,43 @@ int actor_device_rows(dril_sac_handle* h, const float* x, int n, int mode, const
     h->ext_launches += 1;
     return DRIL_OK;
 }
+// ---- the wrappers of an external handle inside the device verbs (kernels: dril_sac_ext_norm.h) ----
+int xs_epb(int n, int D) { return std::max(std::min(64, std::max(1, 2048 / D)), (n + 127) / 128); }   // (nz_apply's split: a block's share of the rows)
+// observe (:123-137) of n rows of the caller's array into `out`, in the place of the unwrapped verb's device-to-device copy.  opening: a collection's first act — the
+// one observe that updates the statistics (one more launch: the moments); cache: the wrapper's old_obs takes the rows (not for predict)
+int xw_observe(dril_sac_handle* h, const float* raw, int n, float* out, bool opening, bool cache) {
+    const bool upd = opening && h->nz.cfg.training && h->nz.cfg.norm_obs;
+    int rows = 0;
+    if (upd) { SDO(nz_moments_over(h, raw, nullptr, &rows)); h->ext_launches += 1; h->xw_launches_act += 1; }
+    XsActArgs p{}; NormWrapArgs& a = p.w;
+    h->nz.fill(a, upd, false, h->cfg.n_envs);
+    a.E = n; a.rows = rows; a.epb = xs_epb(n, h->D); a.raw = raw; a.obs_out = out; p.old_obs = cache ? h->nz_old_obs : nullptr;
+    hipLaunchKernelGGL(sac_ext_norm_act_kernel, dim3((n + a.epb - 1) / a.epb), dim3(256), nz_apply_lds(h->D), h->stream, p);
+    SHIP(h, hipGetLastError());
+    h->nz.commit(a); h->ext_launches += 1;
+    return DRIL_OK;
+}
+// act! + observe + push! of the pending step under a wrapper, in the place of sac_ext_push_kernel: the moments over the caller's next observations and rewards (ONE
+// launch, only where statistics are updated), then the apply-and-push kernel.  The monitor's block of buffered steps is collected first when it is full
+int xw_push(dril_sac_handle* h, const PushArgs& pa, const float* d_terminal_obs) {
+    const bool nzon = h->nz.on, upd_obs = nzon && h->nz.cfg.training && h->nz.cfg.norm_obs, upd_ret = nzon && h->nz.cfg.training && h->nz.cfg.norm_reward;
+    const int E = h->cfg.n_envs, D = h->D;
+    int rows = 0;
+    if (upd_obs || upd_ret) { SDO(nz_moments_over(h, upd_obs ? pa.nobs : nullptr, upd_ret ? pa.rew : nullptr, &rows)); h->ext_launches += 1; h->xw_launches_push += 1; }
+    if (h->mon_window && h->mon_row >= h->mon_rows_cap) { SDO(monitor_end(h)); h->ext_launches += 1; h->xw_launches_push += 1; }
+    XsPushArgs p{}; NormWrapArgs& a = p.w;
+    if (nzon) h->nz.fill(a, upd_obs, upd_ret, E); else a.D = D;
+    a.E = E; a.rows = rows; a.epb = xs_epb(E, D); a.raw = pa.nobs; a.rew = pa.rew; a.term = pa.term; a.trunc = pa.trunc; a.returns = h->nz_returns;
+    p.has_norm = nzon ? 1 : 0; p.tobs = d_terminal_obs; p.old_obs = h->nz_old_obs; p.old_rew = h->nz_old_rew; p.push = pa; p.err = h->ext_err;
+    const MonitorArgs m = monitor_row(h);
+    p.mon_cur_ret = m.cur_ret; p.mon_cur_len = m.cur_len; p.ep_ret = m.ep_ret; p.ep_len = m.ep_len; p.ep_flags = m.flags_out;
+    hipLaunchKernelGGL(sac_ext_norm_push_kernel, dim3((E + a.epb - 1) / a.epb), dim3(256), nzon ? xs_push_lds(D) : 0, h->stream, p);
+    SHIP(h, hipGetLastError());
+    if (nzon) h->nz.commit(a);
+    if (h->mon_window) h->mon_row += 1;
+    h->ext_launches += 1;
+    return DRIL_OK;
+}
 }  // namespace
 DRIL_EXPORT int32_t dril_sac_ext_act_device(dril_sac_handle* h, const float* d_obs, int32_t use_random_actions, const float* d_noise, float* d_stored_actions,
                                             float* d_env_actions, void* caller_stream) {
@@ -2314,12 +2376,21 @@ DRIL_EXPORT int32_t dril_sac_ext_act_device(dril_sac_handle* h, const float* d_o
     if (d_noise) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_noise", d_noise, E * A * 4));
     if (d_stored_actions) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_stored_actions", d_stored_actions, E * A * 4));
     if (d_env_actions) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_env_actions", d_env_actions, E * A * 4));
+    if (h->nz.on && !h->xw_begin && !h->xw_live)
+        return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_ext_act_device: no collection is in progress under NormalizeWrapperEnv (wrapper switched, statistics set or wrapper reset since the last step): dril_sac_ext_collection_begin marks the act that opens one");
     DeviceVerbScope scope(h);
     SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
     StreamHandOver back(h, caller_stream);
-    SHIP(h, hipMemcpyAsync(h->obs_cur, d_obs, E * D * 4, hipMemcpyDeviceToDevice, h->stream));     // the pending step's observation; the forward reads it from here
-    h->ext_launches += 1;
+    XpScope xp(h); SHIP(h, xp.mark());
+    if (h->nz.on) {                                                                                // observe through the wrapper: normalised into obs_cur, raw into old_obs, from one read
+        SDO(xw_observe(h, d_obs, (int)E, h->obs_cur, h->xw_begin, true));
+        h->xw_begin = false; h->xw_live = true;
+    } else {
+        SHIP(h, hipMemcpyAsync(h->obs_cur, d_obs, E * D * 4, hipMemcpyDeviceToDevice, h->stream)); // the pending step's observation; the forward reads it from here
+        h->ext_launches += 1;
+    }
     SDO(actor_device_rows(h, h->obs_cur, (int)E, use_random_actions ? 2 : 0, d_noise, d_stored_actions, d_env_actions, h->e_raw));
+    SHIP(h, xp.mark()); xp.ok = true;
     SHIP(h, back.give());
     h->ext_acted = true;
     return DRIL_OK;
@@ -2339,8 +2410,8 @@ DRIL_EXPORT int32_t dril_sac_predict_actions_device(dril_sac_handle* h, const fl
     StreamHandOver back(h, caller_stream);
     for (int64_t o = 0; o < batch; o += h->nmax) {                                                 // chunks of nmax rows, as the host verb: stream order keeps the scratch rows apart
         const int n = (int)std::min<int64_t>(h->nmax, batch - o);
-        SHIP(h, hipMemcpyAsync(h->xa, d_obs + o * D, (size_t)n * D * 4, hipMemcpyDeviceToDevice, h->stream));
-        h->ext_launches += 1;
+        if (h->nz.on && h->nz.cfg.norm_obs) SDO(xw_observe(h, d_obs + o * D, n, h->xa, false, false));   // the statistics in force; nothing of the wrapper is written
+        else { SHIP(h, hipMemcpyAsync(h->xa, d_obs + o * D, (size_t)n * D * 4, hipMemcpyDeviceToDevice, h->stream)); h->ext_launches += 1; }
         SDO(actor_device_rows(h, h->xa, n, deterministic ? 1 : 0, deterministic || !d_noise ? nullptr : d_noise + o * A,
                               d_raw_actions ? d_raw_actions + o * A : nullptr, d_env_actions ? d_env_actions + o * A : nullptr, nullptr));
     }
@@ -2361,13 +2432,18 @@ DRIL_EXPORT int32_t dril_sac_ext_push_device(dril_sac_handle* h, const float* d_
     DeviceVerbScope scope(h);
     SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
     StreamHandOver back(h, caller_stream);
+    XpScope xp(h); SHIP(h, xp.mark());
     const long long tail = (h->head + h->size) % h->cap;
     PushArgs pa{(int)E, (int)D, h->A, h->cap, tail, h->obs_cur, h->e_raw, d_rewards, d_terminal_obs, d_next_obs, d_terminated, d_truncated,
                 h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, nullptr};
-    hipLaunchKernelGGL(sac_ext_push_kernel, dim3((unsigned)((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock)), dim3(256), 0, h->stream, pa, h->ext_err);
-    SHIP(h, hipGetLastError());
-    h->ext_launches += 1;
+    if (h->nz.on || h->mon_window) SDO(xw_push(h, pa, d_terminal_obs));
+    else {
+        hipLaunchKernelGGL(sac_ext_push_kernel, dim3((unsigned)((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock)), dim3(256), 0, h->stream, pa, h->ext_err);
+        SHIP(h, hipGetLastError());
+        h->ext_launches += 1;
+    }
     ring_advance(h);                                                                              // head / size are host counters: nothing to wait for
+    SHIP(h, xp.mark()); xp.ok = true;
     SHIP(h, back.give());
     h->ext_acted = false; h->ext_steps_dev += 1;
     return DRIL_OK;
@@ -2395,9 +2471,12 @@ DRIL_EXPORT int32_t dril_sac_update_enqueue(dril_sac_handle* h, int32_t n_update
 }
 DRIL_EXPORT int32_t dril_sac_flush(dril_sac_handle* h, dril_sac_stats* stats, int64_t stats_capacity, int64_t* n_stats) {
     SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_flush");
+    SDO(monitor_end(h));                                                                           // MonitorWrapperEnv (dril_sac_ext_monitor_enable): the episodes of the steps since the last collection into the window
     SHIP(h, hipMemcpyAsync(h->ext_err_host, h->ext_err, 4, hipMemcpyDeviceToHost, h->stream));
     SDO(ssync(h));
     h->ext_flushes += 1;
+    for (size_t i = 0; i + 1 < h->xp_n; i += 2) { float ms = 0; if (hipEventElapsedTime(&ms, h->xp_events[i], h->xp_events[i + 1]) == hipSuccess) h->collect_ms += ms; }   // cfg.profile_events: an act and a push per env step
+    h->collect_steps += (int64_t)(h->xp_n / 4); h->xp_n = 0;                                       // (a step = an act and a push: four events)
     for (void* p : h->pend_free) hipFree(p);
     h->pend_free.clear();
     const int n = h->pend_n;
@@ -2576,6 +2655,23 @@ void monitor_free(dril_sac_handle* h) {
     h->mon_cur_ret = h->mon_ring_ret = h->mon_ep_ret = nullptr; h->mon_cur_len = h->mon_ring_len = h->mon_ep_len = nullptr; h->mon_meta = nullptr; h->mon_flags = nullptr;
     h->mon_window = 0; h->mon_rows_cap = 0; h->mon_row = 0;
 }
+// log_stats over the window as it stands on the device, after a drain: one body for dril_sac_monitor_get_stats and dril_sac_ext_monitor_get_stats
+int monitor_read(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
+    const int W = h->mon_window;
+    std::vector<float> r(W); std::vector<int32_t> l(W); int meta[2] = {0, 0};
+    SHIP(h, hipMemcpyAsync(r.data(), h->mon_ring_ret, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
+    SHIP(h, hipMemcpyAsync(l.data(), h->mon_ring_len, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
+    SHIP(h, hipMemcpyAsync(meta, h->mon_meta, 8, hipMemcpyDeviceToHost, h->stream));
+    SDO(ssync(h));
+    double sr = 0, sl = 0;
+    for (int i = 0; i < meta[0]; ++i) { sr += r[i]; sl += l[i]; }
+    if (n_episodes) *n_episodes = meta[0];
+    if (meta[0] > 0) {                                                                // log_stats: mean over the CircularBuffer, monitorWrapperEnv.jl:64-70; nothing to log for an empty one
+        if (ep_rew_mean) *ep_rew_mean = (float)(sr / meta[0]);
+        if (ep_len_mean) *ep_len_mean = (float)(sl / meta[0]);
+    }
+    return DRIL_OK;
+}
 }  // namespace
 DRIL_EXPORT int32_t dril_sac_monitor_enable(dril_sac_handle* h, int32_t window) {
     SNEED(h);
@@ -2602,22 +2698,26 @@ DRIL_EXPORT int32_t dril_sac_monitor_get_stats(dril_sac_handle* h, float* ep_rew
     SNEED(h);
     if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_monitor_get_stats: the envs of DRIL_ENV_EXTERNAL live on the host: MonitorWrapperEnv wraps them there");
     if (!h->mon_window) return sfail(h, DRIL_ERR_NOT_INITIALISED, "MonitorWrapperEnv is off (dril_sac_monitor_enable has not been called with a window >= 1)");
-    const int W = h->mon_window;
-    std::vector<float> r(W); std::vector<int32_t> l(W); int meta[2] = {0, 0};
-    SHIP(h, hipMemcpyAsync(r.data(), h->mon_ring_ret, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
-    SHIP(h, hipMemcpyAsync(l.data(), h->mon_ring_len, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
-    SHIP(h, hipMemcpyAsync(meta, h->mon_meta, 8, hipMemcpyDeviceToHost, h->stream));
-    SDO(ssync(h));
-    double sr = 0, sl = 0;
-    for (int i = 0; i < meta[0]; ++i) { sr += r[i]; sl += l[i]; }
-    if (n_episodes) *n_episodes = meta[0];
-    if (meta[0] > 0) {                                                                // log_stats: mean over the CircularBuffer, monitorWrapperEnv.jl:64-70; nothing to log for an empty one
-        if (ep_rew_mean) *ep_rew_mean = (float)(sr / meta[0]);
-        if (ep_len_mean) *ep_len_mean = (float)(sl / meta[0]);
-    }
+    return monitor_read(h, ep_rew_mean, ep_len_mean, n_episodes);
+}
+// the same for the device-resident envs of an external handle (dril_sac_ext_monitor_enable): the episodes of the steps pushed since the last collection enter the window first
+DRIL_EXPORT int32_t dril_sac_ext_monitor_get_stats(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
+    SNEED(h);
+    if (!h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_monitor_get_stats: the handle was not created with DRIL_ENV_EXTERNAL: the wrapper around device envs is dril_sac_monitor_enable / dril_sac_monitor_get_stats");
+    if (!h->mon_window) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_ext_monitor_get_stats: MonitorWrapperEnv is off (dril_sac_ext_monitor_enable has not been called with a window >= 1)");
+    SDO(monitor_end(h));
+    return monitor_read(h, ep_rew_mean, ep_len_mean, n_episodes);
+}
+DRIL_EXPORT int32_t dril_sac_ext_wrap_info(const dril_sac_handle* h, struct dril_sac_ext_wrap_info* out) {
+    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    dril_sac_handle* hm = const_cast<dril_sac_handle*>(h);                            // (the message slot only)
+    if (!out) return sfail(hm, DRIL_ERR_INVALID_ARG, "dril_sac_ext_wrap_info: null out pointer");
+    if (!h->external) return sfail(hm, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_wrap_info: the handle was not created with DRIL_ENV_EXTERNAL");
+    std::memset(out, 0, sizeof(*out));
+    out->normalize_on = h->nz.on ? 1 : 0; out->monitor_on = h->mon_window > 0 ? 1 : 0; out->monitor_window = h->mon_window;
+    out->launches_act = h->xw_launches_act; out->launches_push = h->xw_launches_push; out->allocations = 0;   // (structural: see the header)
     return DRIL_OK;
 }
-
 // ---- NormalizeWrapperEnv around the handle's device envs (normalizeWrapperEnv.jl; rules and state: dril_norm_wrap.h) ------------------------------------------------------
 namespace {
 #define S_NORMALIZE_ON(h, what) do { if ((h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, what ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there"); \
@@ -2657,6 +2757,37 @@ DRIL_EXPORT int32_t dril_sac_normalize_enable(dril_sac_handle* h, const dril_sac
     h->nz.cfg = c; h->nz.on = true; h->obs_valid = false;                              // the next collection observes through the wrapper
     return DRIL_OK;
 }
+// the bodies of the verbs that read or write a wrapper that is on: one definition for dril_sac_normalize_* (device envs) and dril_sac_ext_normalize_* (external handles)
+namespace {
+int nzv_get_config(dril_sac_handle* h, const std::string& verb, dril_sac_normalize_config* cfg) {
+    if (!cfg) return sfail(h, DRIL_ERR_INVALID_ARG, verb + ": null out pointer");
+    memcpy(cfg, &h->nz.cfg, sizeof(*cfg));
+    return DRIL_OK;
+}
+int nzv_get_stats(dril_sac_handle* h, const std::string& verb, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
+    if (!obs_mean || !obs_var || !obs_count || !ret_mean || !ret_var || !ret_count) return sfail(h, DRIL_ERR_INVALID_ARG, verb + ": null out pointer");
+    SDO(ssync(h));
+    std::vector<float> st(h->nz.stats_floats());
+    SHIP(h, hipMemcpy(st.data(), h->nz.half(h->nz.cur), st.size() * 4, hipMemcpyDeviceToHost));
+    h->nz.unpack(st, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+    return DRIL_OK;
+}
+int nzv_set_stats(dril_sac_handle* h, const std::string& verb, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
+    if (const NormErr err = norm_set_stats_check(obs_mean, obs_var, obs_count, ret_count)) return sfail(h, err.code, verb + ": " + err.msg);
+    SDO(ssync(h));
+    const std::vector<float> st = h->nz.pack(obs_mean, obs_var, ret_mean, ret_var);
+    SHIP(h, hipMemcpy(h->nz.half(h->nz.cur), st.data(), st.size() * 4, hipMemcpyHostToDevice));
+    h->nz.obs_count = obs_count; h->nz.ret_count = ret_count;
+    h->obs_valid = false; h->xw_begin = h->xw_live = false;                           // (the current normalised observation was made with other statistics)
+    return DRIL_OK;
+}
+int nzv_get_returns(dril_sac_handle* h, const std::string& verb, float* returns) {
+    if (!returns) return sfail(h, DRIL_ERR_INVALID_ARG, verb + ": null out pointer");
+    SDO(ssync(h));
+    SHIP(h, hipMemcpy(returns, h->nz_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost));
+    return DRIL_OK;
+}
+}  // namespace
 DRIL_EXPORT int32_t dril_sac_normalize_set_training(dril_sac_handle* h, int32_t training) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_set_training");
     h->nz.cfg.training = training != 0;
@@ -2664,27 +2795,15 @@ DRIL_EXPORT int32_t dril_sac_normalize_set_training(dril_sac_handle* h, int32_t 
 }
 DRIL_EXPORT int32_t dril_sac_normalize_get_config(dril_sac_handle* h, dril_sac_normalize_config* cfg) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_get_config");
-    if (!cfg) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_get_config: null out pointer");
-    memcpy(cfg, &h->nz.cfg, sizeof(*cfg));
-    return DRIL_OK;
+    return nzv_get_config(h, "dril_sac_normalize_get_config", cfg);
 }
 DRIL_EXPORT int32_t dril_sac_normalize_get_stats(dril_sac_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_get_stats");
-    if (!obs_mean || !obs_var || !obs_count || !ret_mean || !ret_var || !ret_count) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_get_stats: null out pointer");
-    SDO(ssync(h));
-    std::vector<float> st(h->nz.stats_floats());
-    SHIP(h, hipMemcpy(st.data(), h->nz.half(h->nz.cur), st.size() * 4, hipMemcpyDeviceToHost));
-    h->nz.unpack(st, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-    return DRIL_OK;
+    return nzv_get_stats(h, "dril_sac_normalize_get_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
 }
 DRIL_EXPORT int32_t dril_sac_normalize_set_stats(dril_sac_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_set_stats");
-    if (const NormErr err = norm_set_stats_check(obs_mean, obs_var, obs_count, ret_count)) return sfail(h, err.code, "dril_sac_normalize_set_stats: " + err.msg);
-    SDO(ssync(h));
-    const std::vector<float> st = h->nz.pack(obs_mean, obs_var, ret_mean, ret_var);
-    SHIP(h, hipMemcpy(h->nz.half(h->nz.cur), st.data(), st.size() * 4, hipMemcpyHostToDevice));
-    h->nz.obs_count = obs_count; h->nz.ret_count = ret_count; h->obs_valid = false;   // (the current normalised observation was made with other statistics)
-    return DRIL_OK;
+    return nzv_set_stats(h, "dril_sac_normalize_set_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
 }
 DRIL_EXPORT int32_t dril_sac_normalize_get_original(dril_sac_handle* h, float* obs, float* rewards) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_get_original");
@@ -2696,9 +2815,108 @@ DRIL_EXPORT int32_t dril_sac_normalize_get_original(dril_sac_handle* h, float* o
 }
 DRIL_EXPORT int32_t dril_sac_normalize_get_returns(dril_sac_handle* h, float* returns) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_get_returns");
-    if (!returns) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_normalize_get_returns: null out pointer");
+    return nzv_get_returns(h, "dril_sac_normalize_get_returns", returns);
+}
+
+// ---- NormalizeWrapperEnv / MonitorWrapperEnv around the device-resident envs of an external handle (include/dril_sac.h; the device verbs honour them: xw_observe / xw_push) ----
+namespace {
+#define XW_KIND(h, verb, twin) do { if (!(h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, verb ": the handle was not created with DRIL_ENV_EXTERNAL: the wrapper around device envs is " twin); } while (0)
+#define XN_ON(h, verb) do { XW_KIND(h, verb, "dril_sac_normalize_enable"); \
+    if (!(h)->nz.on) return sfail(h, DRIL_ERR_NOT_INITIALISED, verb ": NormalizeWrapperEnv is off (dril_sac_ext_normalize_enable has not been called with a configuration)"); } while (0)
+#define XW_NO_PENDING_ACT(h, verb) do { if ((h)->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, verb ": a dril_sac_ext_act_device step is pending: switch wrappers between env steps (after dril_sac_ext_push_device)"); } while (0)
+}  // namespace
+DRIL_EXPORT int32_t dril_sac_ext_normalize_enable(dril_sac_handle* h, const dril_sac_normalize_config* cfg) {
+    SNEED(h); XW_KIND(h, "dril_sac_ext_normalize_enable", "dril_sac_normalize_enable");
+    dril_normalize_config c{};
+    if (cfg) {
+        memcpy(&c, cfg, sizeof(c));
+        if (const NormErr err = norm_config_check(c, h->D)) return sfail(h, err.code, "dril_sac_ext_normalize_enable: " + err.msg);
+        c = norm_config_canonical(c);
+    }
+    XW_NO_PENDING_ACT(h, "dril_sac_ext_normalize_enable");
+    if (!cfg) {
+        if (!h->nz.on) return DRIL_OK;
+        SDO(ssync(h)); normalize_free(h); h->xw_begin = h->xw_live = false;
+        return DRIL_OK;
+    }
+    if (h->nz.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart, which is set): its statistics, returns and collection stay
     SDO(ssync(h));
-    SHIP(h, hipMemcpy(returns, h->nz_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost));
+    normalize_free(h);
+    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
+    hipError_t e = h->nz.alloc((int)D, kNzMaxRows);
+    if (e == hipSuccess) e = smalloc(&h->nz_returns, E);                               // (smalloc zeroes: returns and the cached originals start at 0)
+    if (e == hipSuccess) e = smalloc(&h->nz_old_obs, E * D);
+    if (e == hipSuccess) e = smalloc(&h->nz_old_rew, E);
+    if (e != hipSuccess) { normalize_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_ext_normalize_enable: ") + hipGetErrorString(e)); }
+    h->nz.cfg = c; h->nz.on = true; h->xw_begin = h->xw_live = false;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_normalize_set_training(dril_sac_handle* h, int32_t training) {
+    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_set_training");
+    h->nz.cfg.training = training != 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_normalize_get_config(dril_sac_handle* h, dril_sac_normalize_config* cfg) {
+    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_config");
+    return nzv_get_config(h, "dril_sac_ext_normalize_get_config", cfg);
+}
+DRIL_EXPORT int32_t dril_sac_ext_normalize_get_stats(dril_sac_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
+    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_stats");
+    return nzv_get_stats(h, "dril_sac_ext_normalize_get_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+}
+DRIL_EXPORT int32_t dril_sac_ext_normalize_set_stats(dril_sac_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
+    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_set_stats");
+    XW_NO_PENDING_ACT(h, "dril_sac_ext_normalize_set_stats");                          // (the pending observation was normalised under the statistics in force)
+    return nzv_set_stats(h, "dril_sac_ext_normalize_set_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
+}
+DRIL_EXPORT int32_t dril_sac_ext_normalize_get_original(dril_sac_handle* h, float* obs, float* rewards) {
+    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_original");
+    if (!obs && !rewards) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_normalize_get_original: both out pointers are null");
+    SDO(ssync(h));
+    if (obs) SHIP(h, hipMemcpy(obs, h->nz_old_obs, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost));
+    if (rewards) SHIP(h, hipMemcpy(rewards, h->nz_old_rew, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost));
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_normalize_get_returns(dril_sac_handle* h, float* returns) {
+    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_returns");
+    return nzv_get_returns(h, "dril_sac_ext_normalize_get_returns", returns);
+}
+DRIL_EXPORT int32_t dril_sac_ext_normalize_reset(dril_sac_handle* h, void* caller_stream) {
+    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_reset");
+    XW_NO_PENDING_ACT(h, "dril_sac_ext_normalize_reset");
+    DeviceVerbScope scope(h);
+    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
+    StreamHandOver back(h, caller_stream);
+    SHIP(h, hipMemsetAsync(h->nz_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream));   // reset! :110-121: returns <- 0; the env's own reset gives the next observation
+    SHIP(h, back.give());
+    h->xw_begin = h->xw_live = false;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_collection_begin(dril_sac_handle* h) {
+    SNEED(h); XW_KIND(h, "dril_sac_ext_collection_begin", "driven by dril_sac_collect_rollout");
+    if (h->nz.on) h->xw_begin = true;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_ext_monitor_enable(dril_sac_handle* h, int32_t window) {
+    SNEED(h); XW_KIND(h, "dril_sac_ext_monitor_enable", "dril_sac_monitor_enable");
+    if (window < 0) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_monitor_enable: window must be >= 1 (MonitorWrapperEnv's stats_window), or 0 to switch the monitor off");
+    XW_NO_PENDING_ACT(h, "dril_sac_ext_monitor_enable");
+    if (window == h->mon_window) return DRIL_OK;                                      // the same wrapper again: its window and running sums stay
+    SDO(ssync(h));
+    monitor_free(h);
+    if (window == 0) return DRIL_OK;
+    // the block of buffered steps: a row per push until dril_sac_flush / dril_sac_ext_monitor_get_stats (or a full block) collects it; about a million entries, 4 .. 256 rows
+    const size_t E = (size_t)h->cfg.n_envs, rows = std::max<size_t>(4, std::min<size_t>(256, ((size_t)1 << 20) / E));
+    hipError_t e = smalloc(&h->mon_cur_ret, E);                                       // (smalloc zeroes: fresh sums, an empty window)
+    if (e == hipSuccess) e = smalloc(&h->mon_cur_len, E);
+    if (e == hipSuccess) e = smalloc(&h->mon_ring_ret, (size_t)window);
+    if (e == hipSuccess) e = smalloc(&h->mon_ring_len, (size_t)window);
+    if (e == hipSuccess) e = smalloc(&h->mon_meta, 2);
+    if (e == hipSuccess) e = smalloc(&h->mon_ep_ret, rows * E);
+    if (e == hipSuccess) e = smalloc(&h->mon_ep_len, rows * E);
+    if (e == hipSuccess) e = smalloc(&h->mon_flags, rows * E);
+    if (e != hipSuccess) { monitor_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_ext_monitor_enable: ") + hipGetErrorString(e)); }
+    h->mon_window = window; h->mon_rows_cap = (int)rows;
     return DRIL_OK;
 }
 

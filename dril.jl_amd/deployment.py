@@ -17,7 +17,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi as capi
-from .host import ACTIVATIONS, Box, Discrete, DrilError, Handle, _norm_view, _normalize_kw
+from .host import ACTIVATIONS, Box, Discrete, DrilError, Handle, _env_handle, _norm_view, _normalize_kw
 
 KINDS = ("Categorical", "DiagGaussian", "SquashedDiagGaussian")
 
@@ -212,7 +212,7 @@ def _layer_policy_desc(layer, *, clip_obs=None, epsilon=1e-8, device=0) -> capi.
 def _norm_of(norm_env):
     """(obs_mean, obs_var, epsilon, clip_obs) of a NormalizeWrapperEnv: a DeviceParallelEnv / DeviceModuleEnv with normalize= and a bound handle, a Handle wrapped by
     normalize_enable, or a SacHandle with its wrapper on"""
-    h = norm_env if hasattr(norm_env, "norm_get_stats") else getattr(norm_env, "handle", None)
+    h = norm_env if hasattr(norm_env, "norm_get_stats") else _env_handle(norm_env) if hasattr(norm_env, "handle") else None
     if h is None:
         raise ValueError("extract_policy(agent, norm_env): the env has no bound handle yet (its statistics live on the device: train or bind first)")
     h = _norm_view(h)                                                           # an external handle's wrapper answers through dril_ext_normalize_*

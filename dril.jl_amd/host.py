@@ -1250,6 +1250,7 @@ class DeviceArrayParallelEnv:
         self.env, self.n_envs, self.seed, self.stream, self._empty = env, int(env.n_envs), seed, stream, empty
         self._kw = dict(device=device, profile_events=profile_events)
         self.handle: Optional[Handle] = None
+        self.sac_handle = None                                                       # the SAC handle sac_train_ drives this env with (bind_sac); owned by its ReplayBuffer
         self._bound_key = None
         self._raw = self._env_actions = None
         self._last_term = self._last_trunc = None
@@ -1258,6 +1259,7 @@ class DeviceArrayParallelEnv:
 
     def bind(self, alg: PPO, layer: Optional[ActorCriticLayer] = None) -> Handle:
         key = (tuple(sorted(asdict(alg).items())), None if layer is None else (tuple(layer.hidden_dims), layer.log_std_init, getattr(layer, "activation", "tanh")))
+        self.sac_handle = None                                                       # PPO drives the env from here on
         if self.handle is None or key != self._bound_key:
             if self.handle is not None:
                 self.handle.close()
@@ -1269,9 +1271,23 @@ class DeviceArrayParallelEnv:
             self._apply_wrappers()
         return self.handle
 
+    def bind_sac(self, h):
+        """the DRIL_ENV_EXTERNAL SacHandle that sac_train_ drives this env with: it takes the recorded wrappers (dril_sac_ext_normalize_enable /
+        dril_sac_ext_monitor_enable), and monitor_stats, reset_ and the normalisation helpers answer from it until a PPO bind"""
+        self.sac_handle = h
+        self._apply_wrappers()
+        return h
+
+    def wrapper_handle(self):
+        """the handle that holds the env's wrappers: the SAC handle of the latest sac_train_, else the bound PPO handle (None: neither yet)"""
+        if self.sac_handle is not None and not getattr(self.sac_handle, "_h", True):                   # closed by its owner (replay_buffer.handle.close()): the env lets go of it
+            self.sac_handle = None
+        return self.sac_handle if self.sac_handle is not None else self.handle
+
     def _apply_wrappers(self):
-        """the recorded wrappers on the bound handle (between rollouts): the same normaliser again keeps its statistics"""
-        h = self.handle
+        """the recorded wrappers on the bound handle (between rollouts / env steps): the same normaliser again keeps its statistics.  Handle and SacHandle carry the
+        same ext_* method names"""
+        h = self.wrapper_handle()
         if h is None:
             return
         h.ext_monitor_enable(self.ext_monitor_window)
@@ -1282,7 +1298,7 @@ class DeviceArrayParallelEnv:
 
     def monitor_stats(self):
         """what log_stats logs (env/ep_rew_mean, env/ep_len_mean, episodes in the window), monitorWrapperEnv.jl:64-70"""
-        return self.handle.ext_monitor_stats()
+        return self.wrapper_handle().ext_monitor_stats()
 
     def number_of_envs(self) -> int:
         return self.n_envs
@@ -1295,8 +1311,8 @@ class DeviceArrayParallelEnv:
 
     def reset_(self):
         self.env.reset_()
-        if self.ext_normalize is not None and self.handle is not None:
-            self.handle.ext_normalize_reset(self.stream)                             # reset! of the wrapper: returns <- 0 (normalizeWrapperEnv.jl:111-121)
+        if self.ext_normalize is not None and self.wrapper_handle() is not None:
+            self.wrapper_handle().ext_normalize_reset(self.stream)                             # reset! of the wrapper: returns <- 0 (normalizeWrapperEnv.jl:111-121)
 
     def observe(self):
         return self.env.observe()
@@ -1435,8 +1451,15 @@ class _ExtNormView:
 
 
 def _norm_view(h):
-    """h, or the view of its dril_ext_normalize_* verbs when h is a PPO handle on external envs (Handle.norm_get_stats itself is unchanged there)"""
-    return _ExtNormView(h) if isinstance(h, Handle) and h.cfg.env_kind == capi.ENV_EXTERNAL else h
+    """h, or the view of its dril_ext_normalize_* / dril_sac_ext_normalize_* verbs when h is a PPO or SAC handle on external envs (norm_get_stats itself is
+    unchanged there)"""
+    ext = getattr(getattr(h, "cfg", None), "env_kind", None) == capi.ENV_EXTERNAL and hasattr(h, "ext_normalize_get_stats")
+    return _ExtNormView(h) if ext else h
+
+
+def _env_handle(env):
+    """the handle behind an env's wrappers: a DeviceArrayParallelEnv may be driven by a SAC handle (bind_sac)"""
+    return env.wrapper_handle() if isinstance(env, DeviceArrayParallelEnv) else env.handle
 
 
 def unnormalize_obs_(obs: np.ndarray, env: DeviceParallelEnv) -> np.ndarray:
@@ -1444,7 +1467,7 @@ def unnormalize_obs_(obs: np.ndarray, env: DeviceParallelEnv) -> np.ndarray:
     kw = _normalize_kw(env)
     if kw is None or not kw["norm_obs"]:
         return obs
-    st = _norm_view(env.handle).norm_get_stats()
+    st = _norm_view(_env_handle(env)).norm_get_stats()
     obs *= np.sqrt(st["obs_var"] + np.float32(kw["epsilon"])); obs += st["obs_mean"]
     return obs
 
@@ -1454,16 +1477,16 @@ def unnormalize_rewards_(rewards: np.ndarray, env: DeviceParallelEnv) -> np.ndar
     kw = _normalize_kw(env)
     if kw is None or not kw["norm_reward"]:
         return rewards
-    rewards *= np.sqrt(np.float32(_norm_view(env.handle).norm_get_stats()["ret_var"]) + np.float32(kw["epsilon"]))
+    rewards *= np.sqrt(np.float32(_norm_view(_env_handle(env)).norm_get_stats()["ret_var"]) + np.float32(kw["epsilon"]))
     return rewards
 
 
 def get_original_obs(env: DeviceParallelEnv) -> np.ndarray:
-    return _norm_view(env.handle).norm_get_original()[0]
+    return _norm_view(_env_handle(env)).norm_get_original()[0]
 
 
 def get_original_rewards(env: DeviceParallelEnv) -> np.ndarray:
-    return _norm_view(env.handle).norm_get_original()[1]
+    return _norm_view(_env_handle(env)).norm_get_original()[1]
 
 
 # --------------------------------------------------------------------------------------------

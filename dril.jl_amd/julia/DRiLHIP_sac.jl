@@ -387,3 +387,60 @@ function sac_ext_device_info(h)
     sac_check(ccall((:dril_sac_ext_device_info, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilSacExtDeviceInfo}), h, info), h)
     return info[]
 end
+
+# ---- NormalizeWrapperEnv / MonitorWrapperEnv around such envs (dril_sac_ext_normalize_* / dril_sac_ext_monitor_*, include/dril_sac.h) ----------------------------
+# The device verbs above honour them and stay free of host waits.  sac_ext_collection_begin! marks the next sac_ext_act_device! as the opening observe(env) of a
+# collect_trajectories call (off_policy_collection.jl:43): call it before every collection while the normaliser is on.
+struct DrilSacExtWrapInfo                                                # struct dril_sac_ext_wrap_info
+    normalize_on::Int32; monitor_on::Int32; monitor_window::Int32; reserved0::Int32
+    launches_act::Int64; launches_push::Int64; allocations::Int64
+    reserved::NTuple{3, Int64}
+end
+function sac_ext_normalize_enable!(h::Ptr{Cvoid}, nz::Union{Nothing, NamedTuple})
+    isnothing(nz) && return sac_check(ccall((:dril_sac_ext_normalize_enable, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, C_NULL), h)
+    g(k, d) = get(nz, k, d)
+    cfg = Ref(DrilSacNormalizeConfig(Int32(g(:training, true)), Int32(g(:norm_obs, true)), Int32(g(:norm_reward, true)),
+        Float32(g(:clip_obs, 10.0f0)), Float32(g(:clip_reward, 10.0f0)), Float32(g(:gamma, 0.99f0)), Float32(g(:epsilon, 1.0f-8)), Int32(0)))
+    return sac_check(ccall((:dril_sac_ext_normalize_enable, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilSacNormalizeConfig}), h, cfg), h)
+end
+function sac_ext_normalize_config(h::Ptr{Cvoid})
+    cfg = Ref{DrilSacNormalizeConfig}()
+    sac_check(ccall((:dril_sac_ext_normalize_get_config, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilSacNormalizeConfig}), h, cfg), h)
+    return cfg[]
+end
+sac_ext_normalize_set_training!(h::Ptr{Cvoid}, training::Bool) =
+    sac_check(ccall((:dril_sac_ext_normalize_set_training, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(training)), h)
+function sac_ext_normalize_get_stats(h::Ptr{Cvoid}, D::Integer)
+    om = Vector{Float32}(undef, D); ov = Vector{Float32}(undef, D); oc = Ref{Int64}(0); rc = Ref{Int64}(0); rm = Ref{Float32}(0); rv = Ref{Float32}(0)
+    GC.@preserve om ov sac_check(ccall((:dril_sac_ext_normalize_get_stats, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ref{Int64}, Ref{Float32}, Ref{Float32}, Ref{Int64}),
+                                       h, om, ov, oc, rm, rv, rc), h)
+    return (obs_mean = om, obs_var = ov, obs_count = oc[], ret_mean = rm[], ret_var = rv[], ret_count = rc[])
+end
+function sac_ext_normalize_set_stats!(h::Ptr{Cvoid}, st)
+    om = Vector{Float32}(st.obs_mean); ov = Vector{Float32}(st.obs_var)
+    GC.@preserve om ov sac_check(ccall((:dril_sac_ext_normalize_set_stats, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int64, Float32, Float32, Int64),
+                                       h, om, ov, Int64(st.obs_count), Float32(st.ret_mean), Float32(st.ret_var), Int64(st.ret_count)), h)
+end
+function sac_ext_normalize_get_original(h::Ptr{Cvoid}, E::Integer, D::Integer)
+    obs = Matrix{Float32}(undef, D, E); rew = Vector{Float32}(undef, E)
+    GC.@preserve obs rew sac_check(ccall((:dril_sac_ext_normalize_get_original, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h, obs, rew), h)
+    return obs, rew
+end
+function sac_ext_normalize_get_returns(h::Ptr{Cvoid}, E::Integer)
+    r = Vector{Float32}(undef, E)
+    GC.@preserve r sac_check(ccall((:dril_sac_ext_normalize_get_returns, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float32}), h, r), h)
+    return r
+end
+sac_ext_normalize_reset!(h::Ptr{Cvoid}, stream = C_NULL) = sac_check(ccall((:dril_sac_ext_normalize_reset, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, stream), h)
+sac_ext_collection_begin!(h::Ptr{Cvoid}) = sac_check(ccall((:dril_sac_ext_collection_begin, LIB[]), Int32, (Ptr{Cvoid},), h), h)
+sac_ext_monitor_enable!(h::Ptr{Cvoid}, window::Integer) = sac_check(ccall((:dril_sac_ext_monitor_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h, Int32(window)), h)
+function sac_ext_monitor_stats(h::Ptr{Cvoid})
+    r = Ref{Float32}(NaN32); l = Ref{Float32}(NaN32); n = Ref{Int32}(0)
+    sac_check(ccall((:dril_sac_ext_monitor_get_stats, LIB[]), Int32, (Ptr{Cvoid}, Ref{Float32}, Ref{Float32}, Ref{Int32}), h, r, l, n), h)
+    return (ep_rew_mean = r[], ep_len_mean = l[], n_episodes = n[])
+end
+function sac_ext_wrap_info(h::Ptr{Cvoid})
+    info = Ref{DrilSacExtWrapInfo}()
+    sac_check(ccall((:dril_sac_ext_wrap_info, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilSacExtWrapInfo}), h, info), h)
+    return info[]
+end

@@ -179,6 +179,7 @@ def make_sac_config(env, n_envs: int, alg: SAC, layer: SACLayer, *, seed: int = 
 # --------------------------------------------------------------------------------------------
 # typed wrapper of one dril_sac_handle*
 # --------------------------------------------------------------------------------------------
+@_normalize.normalize_verbs(lambda self, verb: self._f(("normalize_" if verb == "config_default" else "ext_normalize_") + verb), "normalize_", "ext_")
 @_normalize.normalize_verbs(lambda self, verb: self._f("normalize_" + verb), "norm_")
 class SacHandle:
     """typed wrapper of one dril_sac_handle* of libdril_hip.so (there is no other backend: the CPU oracle is driven by a subclass that lives under tests/)"""
@@ -400,6 +401,33 @@ class SacHandle:
         return dict(steps_device=int(info.steps_device), steps_host=int(info.steps_host), host_syncs=int(info.host_syncs), flushes=int(info.flushes), launches=int(info.launches),
                     pending_updates=int(info.pending_updates), pending_capacity=int(info.pending_capacity), per_dim_bounds=bool(info.per_dim_bounds))
 
+    # NormalizeWrapperEnv / MonitorWrapperEnv around device-resident external envs (dril_sac_ext_normalize_* / dril_sac_ext_monitor_*, docs/sac.md last section), under
+    # the names of the PPO handle: ext_normalize_enable, ext_normalize_config, ext_normalize_set_training, ext_normalize_get_stats / _set_stats / _get_original /
+    # _get_returns come from _normalize.normalize_verbs
+    def ext_normalize_reset(self, stream=None):
+        """the wrapper's half of reset!: returns <- 0, statistics kept; enqueued, no host wait"""
+        self._chk(self._f("ext_normalize_reset")(self._h, _stream_ptr(stream)))
+
+    def ext_collection_begin(self):
+        """the next ext_act_device is the opening observe(env) of a collect_trajectories call (a host flag; a no-op while the normaliser is off)"""
+        self._chk(self._f("ext_collection_begin")(self._h))
+
+    def ext_monitor_enable(self, stats_window: int):
+        """MonitorWrapperEnv(env, stats_window) around the handle's device-resident envs; 0 switches it off"""
+        self._chk(self._f("ext_monitor_enable")(self._h, int(stats_window)))
+
+    def ext_monitor_stats(self):
+        """(ep_rew_mean, ep_len_mean, n_episodes) of the window (log_stats, monitorWrapperEnv.jl:64-70); the means are nan while it is empty.  Drains the stream"""
+        r, l, n = C.c_float(float("nan")), C.c_float(float("nan")), C.c_int32()
+        self._chk(self._f("ext_monitor_get_stats")(self._h, C.byref(r), C.byref(l), C.byref(n)))
+        return r.value, l.value, n.value
+
+    def ext_wrap_info(self) -> dict:
+        info = capi.DrilSacExtWrapInfo()
+        self._chk(self._f("ext_wrap_info")(self._h, C.byref(info)))
+        return dict(normalize_on=int(info.normalize_on), monitor_on=int(info.monitor_on), monitor_window=int(info.monitor_window), launches_act=int(info.launches_act),
+                    launches_push=int(info.launches_push), allocations=int(info.allocations))
+
     def set_collect_noise(self, noise):
         self._noise = self._f32(noise)       # the oracle keeps the pointer until the next collect call
         self._chk(self._f("debug_set_collect_noise")(self._h, self._p(self._noise), 0 if noise is None else self._noise.size))
@@ -588,7 +616,7 @@ def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, determin
     from `normalize_stats` — the training handle (`replay_buffer.handle`) or a norm_get_stats() dict — with training off; reported returns are raw.  Without
     them the evaluation would silently run under mean 0 / var 1: that is a RuntimeWarning unless `normalize_stats="fresh"` asks for it (an untrained agent)."""
     if isinstance(env, DeviceArrayParallelEnv):
-        return _sac_evaluate_device_arrays(agent, env, n_eval_episodes, deterministic, reward_threshold, return_stats)
+        return _sac_evaluate_device_arrays(agent, env, n_eval_episodes, deterministic, reward_threshold, return_stats, normalize_stats)
     if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
         raise NotImplementedError("sac_evaluate_agent: host envs (HostParallelEnv) are evaluated on the host; the device verb steps device envs")
     alg = agent.alg
@@ -631,12 +659,35 @@ def _sac_ext_handle(agent: SACAgent, env, alg: SAC, rb_handle=None) -> "SacHandl
     return h
 
 
-def _sac_evaluate_device_arrays(agent: SACAgent, env: DeviceArrayParallelEnv, n_eval_episodes: int, deterministic: bool, reward_threshold: Optional[float], return_stats: bool):
+def _eval_normalize_stats(normalize_stats):
+    """normalize_stats of sac_evaluate_agent -> a statistics dict, or None for "fresh": the training handle, a norm_get_stats() dict, or the word"""
+    from .host import _norm_view
+    if isinstance(normalize_stats, str):
+        if normalize_stats != "fresh":
+            raise ValueError("normalize_stats: a handle, a norm_get_stats() dict, or \"fresh\"")
+        return None
+    if normalize_stats is None:
+        warnings.warn("sac_evaluate_agent: the env is normalised but no normalize_stats were given: the evaluation runs with fresh statistics (mean 0, var 1), "
+                      "not those the agent was trained under; pass the training handle (replay_buffer.handle), a norm_get_stats() dict, or \"fresh\" to say so",
+                      RuntimeWarning, stacklevel=4)
+        return None
+    return _norm_view(normalize_stats).norm_get_stats() if hasattr(normalize_stats, "norm_get_stats") else normalize_stats
+
+
+def _sac_evaluate_device_arrays(agent: SACAgent, env: DeviceArrayParallelEnv, n_eval_episodes: int, deterministic: bool, reward_threshold: Optional[float], return_stats: bool,
+                                normalize_stats=None):
     """the reference loop (evaluation.jl:86-125) with observations and actions on the device: dril_sac_predict_actions_device per step.  Rewards and flags (E values
-    each) come to the host once per step for the episode accounting — that wait is the accounting's, not the library's"""
+    each) come to the host once per step for the episode accounting — that wait is the accounting's, not the library's.  A wrapped env (NormalizeWrapperEnv(env)):
+    the throw-away handle takes the wrapper with training off and the statistics of `normalize_stats`; dril_sac_predict_actions_device normalises under them and
+    updates nothing; the rewards come from the env itself, so the reported returns are raw"""
     h = _sac_ext_handle(agent, env, replace(agent.alg, buffer_capacity=max(env.n_envs, 1)))   # an evaluation never touches the ring
     try:
         h.set_params(sac_flatten_params(agent.parameters))
+        if env.ext_normalize is not None:       # sync_normalization_stats! + set_training(eval_env, false) (normalizeWrapperEnv.jl:245-249,299-309)
+            h.ext_normalize_enable(**{**env.ext_normalize, "training": False})
+            st = _eval_normalize_stats(normalize_stats)
+            if st is not None:
+                h.ext_normalize_set_stats(*(st[k] for k in ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")))
         er, el = [], []
         cur_r, cur_l = np.zeros(env.n_envs, np.float32), np.zeros(env.n_envs, np.int64)
         env.reset_()
@@ -885,7 +936,10 @@ def _sac_train_device_arrays(agent: SACAgent, env: DeviceArrayParallelEnv, alg: 
     """the loop of _sac_train_host for ONE batched env whose arrays live on the device (DeviceArrayParallelEnv): dril_sac_ext_act_device -> the env's own act_ ->
     dril_sac_ext_push_device -> dril_sac_update_enqueue, none of which waits on the host or copies across PCIe; the random actions of the start phase are drawn on the
     device.  dril_sac_flush — the one drain, which also brings the statistics rows — runs when the pending table would overflow, before a callback hook (it may read
-    the agent or the statistics) and at the end.  The timer dict gains "flushes" and "host_syncs" (waits inside the sync-free verbs: 0)."""
+    the agent or the statistics) and at the end.  The timer dict gains "flushes" and "host_syncs" (waits inside the sync-free verbs: 0).
+    NormalizeWrapperEnv(env) / MonitorWrapperEnv(env, window) around the DeviceArrayParallelEnv are the handle's own wrappers (dril_sac_ext_normalize_enable /
+    dril_sac_ext_monitor_enable): the loop stays as it is, plus dril_sac_ext_collection_begin before every collection; `replay_buffer.handle.ext_monitor_stats()`
+    and `.ext_normalize_get_stats()` read them, and env.reset_() resets the wrapper with the env."""
     cbs = cbs or []
     has_hook = lambda name: any(hasattr(c, name) for c in cbs)
     step_hooks = [c for c in cbs if hasattr(c, "on_step")]
@@ -894,6 +948,7 @@ def _sac_train_device_arrays(agent: SACAgent, env: DeviceArrayParallelEnv, alg: 
     rb = replay_buffer or ReplayBuffer(env.observation_space(), asp, alg.buffer_capacity)
     h = _sac_ext_handle(agent, env, alg, rb.handle)
     rb.handle = h
+    env.bind_sac(h)                                                                                 # NormalizeWrapperEnv(env) / MonitorWrapperEnv(env, window) as recorded on the env: the handle's own wrappers (a handle that comes back keeps its statistics)
     h.set_params(sac_flatten_params(agent.parameters)); h.set_target_params(agent.q_target_parameters); h.set_log_ent_coef(agent.log_ent_coef)
     total_start = alg.start_steps if alg.start_steps > 0 else alg.train_freq * E                    # sac.jl:456-458
     adjusted = max(1, total_start // E) * E
@@ -958,6 +1013,7 @@ def _sac_train_device_arrays(agent: SACAgent, env: DeviceArrayParallelEnv, alg: 
         if not hook("on_rollout_start"):
             return leave(True)
         a = time.perf_counter()
+        h.ext_collection_begin()                                                                    # the next act is the opening observe(env), :43 (a host flag)
         for i_step in range(n_steps):                                                               # collect_trajectories, off_policy_collection.jl:28-96
             if step_hooks:
                 loc.update(i=i_step + 1, use_random_actions=use_random)

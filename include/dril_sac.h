@@ -331,6 +331,60 @@ int32_t dril_sac_normalize_get_original(dril_sac_handle* h, float* obs, float* r
 /* env.returns (E): the discounted running return per env behind ret_rms */
 int32_t dril_sac_normalize_get_returns(dril_sac_handle* h, float* returns);
 
+/* ---- NormalizeWrapperEnv / MonitorWrapperEnv around the envs of a DRIL_ENV_EXTERNAL handle whose arrays live on the device: honoured by dril_sac_ext_act_device,
+ * dril_sac_ext_push_device and dril_sac_predict_actions_device, which stay free of host waits, copies across PCIe, allocations and memsets (docs/sac.md last section).
+ * The dril_sac_normalize_* / dril_sac_monitor_* verbs above keep returning DRIL_ERR_UNSUPPORTED on such a handle; every verb of this block returns
+ * DRIL_ERR_UNSUPPORTED on a handle that was NOT created with DRIL_ENV_EXTERNAL (use dril_sac_normalize_enable / dril_sac_monitor_enable there).
+ *
+ * The caller drives collect_trajectories (off_policy_collection.jl:28-96) step by step, so it also says where one begins: dril_sac_ext_collection_begin marks the next
+ * dril_sac_ext_act_device as the opening observe(env) (:43).  With the normaliser on
+ *   first act after collection_begin   observe (normalizeWrapperEnv.jl:123-137): old_obs <- d_obs; with training && norm_obs the observation statistics are updated from
+ *                                      the batch over the n_envs envs; the actor reads d_obs normalised with the NEW statistics and clipped (norm_obs == 0: the raw
+ *                                      bits).  d_obs itself is never written
+ *   any later act of the collection    no update: d_obs normalised with the statistics in force — for the same raw array what the preceding push stored as next observation
+ *   an act with no collection begun since enable / set_stats / normalize_reset      DRIL_ERR_NOT_INITIALISED, the message names dril_sac_ext_collection_begin
+ *   push                               act! (:139-165) then observe: old_rewards <- d_rewards; returns = returns * gamma + r, the return statistics updated, r /
+ *                                      sqrt(ret_var + epsilon) clipped; returns of finished envs to 0; the terminal observation of a truncated env normalised with the
+ *                                      observation statistics in force BEFORE this push's observe; d_next_obs updates the observation statistics and is normalised
+ *                                      with the NEW ones; old_obs <- d_next_obs.  Ring row: normalised pending observation, stored action as kept, normalised reward,
+ *                                      flags, normalised terminal | next observation.  Rows of d_terminal_obs of envs that were not truncated are never read into the
+ *                                      ring or a sum.  d_terminal_obs == NULL with a truncated flag: the sticky error of dril_sac_flush as without the wrapper, the
+ *                                      row holds the normalised d_next_obs, the statistics updates are kept
+ *   dril_sac_predict_actions_device    normalises with the statistics in force and never updates them, whatever `training` says; touches nothing else of the wrapper
+ * obs_count grows by n_envs per opening act and per push, ret_count by n_envs per push: n_envs * (n + 1) and n_envs * n per collection of n steps.  training == 0
+ * freezes both statistics; `returns` then changes only by the reset of finished envs.  MonitorWrapperEnv sits inside the normaliser: running return (float32, step
+ * order) and length of RAW rewards per env; finished episodes enter the window in (step, env) order — the window is brought up to date by dril_sac_flush and
+ * dril_sac_ext_monitor_get_stats before they drain (and, inside a push, once per block of buffered steps).  With both wrappers off the handle enqueues exactly what
+ * it did before these verbs existed.  While a wrapper is on the host verb dril_sac_ext_push returns DRIL_ERR_UNSUPPORTED. */
+/* a fresh wrapper (mean 0, var 1, counts 0, returns 0); the same configuration up to `training` keeps statistics and returns and sets `training`; NULL switches the
+ * wrapper off.  Every array of the wrapper is allocated here.  DRIL_ERR_INVALID_ARG for a negative or NaN clip / epsilon and while an act is pending */
+int32_t dril_sac_ext_normalize_enable(dril_sac_handle* h, const dril_sac_normalize_config* cfg);
+/* the contracts of the dril_sac_normalize_* verbs of the same names; DRIL_ERR_NOT_INITIALISED while the wrapper is off; the getters drain the handle's stream */
+int32_t dril_sac_ext_normalize_get_config(dril_sac_handle* h, dril_sac_normalize_config* cfg);
+int32_t dril_sac_ext_normalize_set_training(dril_sac_handle* h, int32_t training);
+int32_t dril_sac_ext_normalize_get_stats(dril_sac_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count);
+int32_t dril_sac_ext_normalize_set_stats(dril_sac_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count);
+int32_t dril_sac_ext_normalize_get_original(dril_sac_handle* h, float* obs, float* rewards);
+int32_t dril_sac_ext_normalize_get_returns(dril_sac_handle* h, float* returns);
+/* the wrapper's half of reset! (:110-121): returns <- 0, statistics kept; enqueued behind caller_stream (as in the device verbs), no host wait */
+int32_t dril_sac_ext_normalize_reset(dril_sac_handle* h, void* caller_stream);
+/* the next dril_sac_ext_act_device opens a collect_trajectories call.  A host flag: launches nothing; a no-op while the normaliser is off */
+int32_t dril_sac_ext_collection_begin(dril_sac_handle* h);
+/* MonitorWrapperEnv(env, window): the window in force again is a no-op, 0 switches it off; DRIL_ERR_INVALID_ARG for window < 0 and while an act is pending */
+int32_t dril_sac_ext_monitor_enable(dril_sac_handle* h, int32_t window);
+/* dril_sac_monitor_get_stats for such a handle: collects what is outstanding, then drains; DRIL_ERR_NOT_INITIALISED while the monitor is off */
+int32_t dril_sac_ext_monitor_get_stats(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes);
+/* A struct tag only: the verb below has the same name */
+struct dril_sac_ext_wrap_info {
+    int32_t normalize_on, monitor_on, monitor_window, reserved0;
+    int64_t launches_act;      /* launches the wrappers ADDED to dril_sac_ext_act_device calls since create, against the same calls with the wrappers off */
+    int64_t launches_push;     /* ... to dril_sac_ext_push_device calls */
+    int64_t allocations;       /* always 0, by construction: no path of act / push / predict allocates (every array of a wrapper is made by its enable verb), so
+                                  nothing counts here; the field keeps the struct the shape of dril_ext_wrap_info, whose handle has a path that grows a scratch array */
+    int64_t reserved[3];
+};
+int32_t dril_sac_ext_wrap_info(const dril_sac_handle* h, struct dril_sac_ext_wrap_info* out);
+
 /* ---- evaluate_agent(agent, env; n_eval_episodes, deterministic) (src/evaluation.jl:54-143) with the handle's actor on the handle's envs --------------------
  * reset (env e seeded seed + e), then predict_actions(; deterministic) -> act! -> observe until the first n_eval_episodes episodes have finished, taken in
  * (step, env) order.  deterministic: mode(d) = tanh(mean) (squashedDiagGaussian.jl:48-50) through TanhScaleAdapter; otherwise a sample, its noise from env e's
