@@ -81,6 +81,21 @@ class DrilEvalInfo(C.Structure):
     _fields_ = [("path", C.c_int32), ("launches", C.c_int32), ("steps_enqueued", C.c_int32), ("events", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class DrilTrajOptions(C.Structure):
+    """struct dril_traj_options, include/dril_hip.h"""
+    _fields_ = [("n_trajectories", C.c_int32), ("max_steps", C.c_int32), ("deterministic", C.c_int32), ("has_seed", C.c_int32), ("seed", C.c_uint64),
+                ("poll_steps", C.c_int32), ("final_original", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class DrilTrajInfo(C.Structure):
+    """struct dril_traj_info, include/dril_hip.h"""
+    _fields_ = [("capacity", C.c_int32), ("steps_enqueued", C.c_int32), ("launches", C.c_int32), ("longest", C.c_int32), ("cut_by_max_steps", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+TRAJ_TERMINATED, TRAJ_TRUNCATED, TRAJ_MAX_STEPS = 1, 2, 4   # dril_collect_trajectory_device: end_flags bits
+
+
 class DrilEnvModuleInfo(C.Structure):
     """struct dril_env_module_info, include/dril_hip.h"""
     _fields_ = [("plugin_abi", C.c_uint32), ("state_dim", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("discrete", C.c_int32),
@@ -276,6 +291,9 @@ _SIG = {
     "dril_evaluate_agent": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(DrilEvalStats), _P, _P]),
     "dril_eval_options_default": (C.c_int32, [C.POINTER(DrilEvalOptions)]),
     "dril_evaluate_agent_device": (C.c_int32, [_P, C.POINTER(DrilEvalOptions), C.POINTER(DrilEvalStats), _P, _P, C.POINTER(DrilEvalInfo)]),
+    "dril_traj_options_default": (C.c_int32, [C.POINTER(DrilTrajOptions)]),
+    "dril_trajectory_capacity": (C.c_int32, [_P, C.POINTER(DrilTrajOptions), C.POINTER(C.c_int32)]),
+    "dril_collect_trajectory_device": (C.c_int32, [_P, C.POINTER(DrilTrajOptions), _P, _P, _P, _P, _P, C.POINTER(DrilTrajInfo)]),
     "dril_train": (C.c_int32, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     "dril_comm_unique_id": (C.c_int32, [_P]),
     "dril_comm_init": (C.c_int32, [_P, _P]),

@@ -20,6 +20,7 @@
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper on plug-ins shares with the SAC handle's (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_policy_internal.h"   // dril_policy_from_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in kind or a device env plug-in), shared with the SAC handle
+#include "dril_traj_record.h"  // collect_trajectory on the device: the per-env recording traj_record_kernel runs (host-compilable)
 #include "dril_ext_stream.h"  // the pointer rule and the stream hand-over of the device-array verbs, shared with the SAC handle
 
 using namespace dril;
@@ -169,6 +170,8 @@ struct dril_handle {
     // dril_evaluate_agent_device: where the env side is set aside for the call, the per-env running sums, the event list and its counter (pinned host word for the poll)
     char* eval_snap = nullptr; size_t eval_snap_bytes = 0; float* eval_cur_ret = nullptr; int32_t* eval_cur_len = nullptr;
     unsigned int *eval_counter = nullptr, *eval_counter_host = nullptr; SacEvalEvent* eval_events = nullptr; long long eval_events_cap = 0;
+    // dril_collect_trajectory_device: ONE grow-only blob for the step-major recording, the shadow envs' arrays and the table of bounds (the counter and its pinned word are the evaluation's)
+    char* traj_blob = nullptr; size_t traj_blob_bytes = 0;
     std::string err;
 };
 
@@ -834,7 +837,7 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     if (h->eval_counter_host) (void)hipHostFree(h->eval_counter_host);
     if (h->ext_err_host) (void)hipHostFree(h->ext_err_host);
     if (h->ext_ev_in) (void)hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) (void)hipEventDestroy(h->ext_ev_out);
-    void* ptrs[] = {h->ext_err, h->ext_pred_obs, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
+    void* ptrs[] = {h->ext_err, h->ext_pred_obs, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->traj_blob, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
                     h->flags, h->last_values, h->noise_dev, h->perm_dev, h->epoch_index, h->epoch_keys, h->small_xchg, h->w2max_dev, h->gae_carry, h->gae_err, h->w2pf_actor, h->w2pf_critic, h->adv_partials, h->adv_stats, h->ev_partials, h->step_stats,
                     h->stop_flag, h->nan_flag, h->e_obs, h->e_rew, h->e_tobs, h->e_term, h->e_trunc, h->e_act, h->e_obs_raw, h->e_rew_n, h->obs_rms, h->ret_rms, h->rms_partials, h->rms_red, h->gen_tmp, h->dbg, h->rec, h->epoch_tables, h->epoch_stats, h->w2a_actor, h->w2ta_actor, h->w2a_critic, h->w2ta_critic, h->w2p_actor, h->w2tp_actor, h->w2p_critic, h->w2tp_critic, h->mon_cur_ret, h->ep_ret, h->mon_ring_ret, h->e_ep_ret, h->mon_cur_len, h->ep_len,
                     h->mon_ring_len, h->e_ep_len, h->mon_cnt, h->mon_meta, h->e_flags};
@@ -2386,6 +2389,170 @@ DRIL_EXPORT int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_o
     out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
     out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
     return DRIL_OK;
+}
+
+// ---- collect_trajectory on the device, training state left untouched (trajectory_utils.jl:3-49; docs/evaluation.md, "Trajectories") ------------------------------
+// The step-granular launches of the evaluation above, with the episode accounting replaced by a recording of envs 0..M-1.  What no existing kernel produces is the
+// observation after the last step of a TERMINATED episode (the step kernels write terminal_obs where truncated, then auto-reset), so M SHADOW envs take every step
+// a second time: a DeviceEnvs view of the same kind / plug-in with its own arrays, fixed_len = 1 (masks the terminated flag, nothing else) and an unreachable time
+// limit, so it never resets.  Per env step it is given the live envs' pre-step state, takes the step with the same actions, and its observe is the post-step,
+// pre-reset observation of every recorded env — the very float operations the live step ran before its auto-reset.  No kernel, argument block or code object changes.
+namespace dril {   // (a named namespace: tools/kernel_resources.py lists the kernel by its name)
+__global__ __launch_bounds__(256) void traj_record_kernel(TrajRec r, TrajMaps x, TrajStep s, int32_t t) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t lanes = r.D > r.W ? r.D : r.W;                                   // a thread per (env, word): one step's rows are contiguous in the step-major recording
+    if (i >= (int64_t)r.M * lanes) return;
+    traj_record_lane(r, x, s, t, (int32_t)(i / lanes), (int32_t)(i % lanes));
+}
+}  // namespace dril
+namespace {
+constexpr int64_t kTrajMaxBytes = 1ll << 30;
+struct TrajRun {
+    TrajRec rec; TrajMaps maps; DeviceEnvs shadow;
+    float *sh_rew, *sh_tobs, *sh_obs; uint8_t *sh_term, *sh_trunc;
+};
+// carves the handle's blob (grown when the call needs more) and fills the table of bounds
+int traj_prepare(dril_handle* h, const dril_traj_options* o, int32_t Tcap, TrajRun& r) {
+    const size_t M = (size_t)o->n_trajectories, D = (size_t)h->D, W = h->discrete ? 1 : (size_t)h->A, S = (size_t)h->S, T = (size_t)Tcap;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_obs = take((T + 1) * M * D * 4), o_act = take(T * M * W * 4), o_rew = take(T * M * 4), o_len = take(M * 4), o_flg = take(M);
+    const size_t o_st = take(M * S * 4), o_sc = take(M * 4), o_ep = take(M * 4), o_gs = take(M * 4);
+    const size_t o_srew = take(M * 4), o_sterm = take(M), o_strunc = take(M), o_stobs = take(M * D * 4), o_sobs = take(M * D * 4), o_tab = take((2 * D + 4 * W) * 4);
+    if (off > h->traj_blob_bytes) { if (h->traj_blob) (void)hipFree(h->traj_blob); h->traj_blob = nullptr; h->traj_blob_bytes = 0; HIPCHK(h, dmalloc(&h->traj_blob, off)); h->traj_blob_bytes = off; }
+    char* b = h->traj_blob;
+    r.rec = TrajRec{(int32_t)M, (int32_t)D, (int32_t)W, Tcap, (float*)(b + o_obs), (uint32_t*)(b + o_act), (float*)(b + o_rew), (int32_t*)(b + o_len), (uint8_t*)(b + o_flg), h->eval_counter};
+    r.shadow = h->env;                                                             // the kind / the plug-in's kernels, scaling, action_start
+    r.shadow.E = (int)M; r.shadow.fixed_len = 1; r.shadow.episode_len = INT32_MAX; r.shadow.disc_returns = nullptr;
+    r.shadow.state = (float*)(b + o_st); r.shadow.step_count = (int32_t*)(b + o_sc); r.shadow.episode = (uint32_t*)(b + o_ep); r.shadow.gstep = (uint32_t*)(b + o_gs);
+    r.sh_rew = (float*)(b + o_srew); r.sh_term = (uint8_t*)(b + o_sterm); r.sh_trunc = (uint8_t*)(b + o_strunc); r.sh_tobs = (float*)(b + o_stobs); r.sh_obs = (float*)(b + o_sobs);
+    // the table: obs_low | obs_high (D each), clamp_low | clamp_high | act_low | act_high (W each)
+    std::vector<float> tab(2 * D + 4 * W, 0.f);
+    float *ol = tab.data(), *oh = ol + D, *cl = oh + D, *ch = cl + W, *al = ch + W, *ah = al + W;
+    bool scaled = false;
+    if (h->env.module) {
+        scaled = h->env.scaling;
+        if (scaled) for (size_t i = 0; i < D; ++i) { ol[i] = h->env.obs_low[i]; oh[i] = h->env.obs_high[i]; }
+        if (!h->discrete) for (size_t i = 0; i < W; ++i) { al[i] = h->env.desc.action_low[i]; ah[i] = h->env.desc.action_high[i]; cl[i] = scaled ? -1.0f : al[i]; ch[i] = scaled ? 1.0f : ah[i]; }
+    } else {
+        const EnvKindInfo* ki = env_kind_info(h->env.kind);
+        if (!ki) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_collect_trajectory_device: no device env on this handle");
+        if (ki->box) { cl[0] = ki->act_lo; ch[0] = ki->act_hi; }                   // ClampAdapter on the agent-facing Box (Box(-1, 1) under the wrapper)
+        if (h->env.kind == 2) { scaled = true; ol[0] = -1.0f; oh[0] = 1.0f; ol[1] = -1.0f; oh[1] = 1.0f; ol[2] = -8.0f; oh[2] = 8.0f; al[0] = -2.0f; ah[0] = 2.0f; }   // the bounds env_obs<2> / env_step<2> use (dril_device.h)
+        if (h->env.kind == 7) { scaled = true; ol[0] = -1.2f; oh[0] = 0.6f; ol[1] = -0.07f; oh[1] = 0.07f; al[0] = -1.0f; ah[0] = 1.0f; }                             // env_obs<7> / env_step<7>
+    }
+    HIPCHK(h, hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (the table is a local)
+    const float* dt = (const float*)(b + o_tab);
+    r.maps = TrajMaps{scaled ? dt : nullptr, scaled ? dt + D : nullptr, h->discrete ? nullptr : dt + 2 * D, h->discrete ? nullptr : dt + 2 * D + W,
+                      (scaled && !h->discrete) ? dt + 2 * D + 2 * W : nullptr, (scaled && !h->discrete) ? dt + 2 * D + 3 * W : nullptr, h->discrete ? 1 : 0, o->final_original ? 1 : 0};
+    return DRIL_OK;
+}
+int traj_record_launch(dril_handle* h, const TrajRun& r, const TrajStep& s, int32_t t) {
+    const int64_t n = (int64_t)r.rec.M * std::max(r.rec.D, r.rec.W);
+    hipLaunchKernelGGL(traj_record_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.rec, r.maps, s, t);
+    HIPCHK(h, hipGetLastError());
+    return DRIL_OK;
+}
+// one env step, enqueued: the launches of eval_step_granular, and over the M recorded envs only a state copy, the shadow step, the shadow observe and the recording
+int traj_step(dril_handle* h, const TrajRun& r, int32_t t, int deterministic, int32_t* launches) {
+    const int E = h->cfg.n_envs; const bool wrapped = normalizing(h) || h->pn.on; const int64_t g0 = h->gws.launches;
+    HIPCHK(h, hipMemcpyAsync(r.shadow.state, h->env.state, (size_t)r.rec.M * h->S * 4, hipMemcpyDeviceToDevice, h->stream));   // the pre-step state of envs 0..M-1 (env-major prefix)
+    PolicyArgs p = policy_args(h, h->e_obs, E, nullptr, h->e_act, nullptr, h->e_rew /*log-probabilities are not needed: parked where act! writes next*/, nullptr, 0);
+    p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.deterministic = deterministic ? 1 : 0;
+    HIPCHK(h, run_policy(h, p));                                                   // predict_actions(agent, [obs_to_agent]; deterministic), :28
+    HIPCHK(h, r.shadow.step(h->e_act, EnvStepOut{r.sh_rew, r.sh_term, r.sh_trunc, r.sh_tobs, nullptr}, MonitorArgs{}, h->stream));   // the same step, with no reset after it
+    HIPCHK(h, r.shadow.observe(r.sh_obs, h->stream));                              // observe(env) of the env that did not auto-reset
+    if (wrapped) { int rc = step_dev(h, h->e_act, (h->env.module && !h->pn.on) ? nullptr : h->e_rew_n, nullptr); if (rc) return rc; }   // act!(env, action), :35: the wrapper's, its statistics frozen; raw rewards stay in e_rew
+    else { int rc = env_step_arrays(h, h->e_act); if (rc) return rc; }
+    { int rc = traj_record_launch(h, r, TrajStep{h->e_act, h->e_rew, h->e_term, h->e_trunc, r.sh_obs}, t); if (rc) return rc; }
+    if (wrapped) { int rc = observe_dev(h, true); if (rc) return rc; }             // the next obs_to_agent (normalize_obs!, :24-26)
+    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
+    *launches += (h->generic ? (int32_t)(h->gws.launches - g0) : 1) + 2 + (wrapped ? (h->env.module ? 2 : 3) : 0) + 4 + (h->env.module ? 0 : 1);   // (a built-in shadow step + observe: env_step_kernel, env_observe_kernel)
+    return DRIL_OK;
+}
+int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, float* observations, void* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
+    const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap; const size_t D = (size_t)r.rec.D, W = (size_t)r.rec.W;
+    const bool wrapped = normalizing(h) || h->pn.on;
+    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
+    r.shadow.seed0 = h->env.seed0;
+    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :10
+    h->env.ready = true;
+    HIPCHK(h, hipMemsetAsync(r.shadow.step_count, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(r.shadow.episode, 0, (size_t)M * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(r.shadow.gstep, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
+    if (wrapped) { int rc = observe_dev(h, true); if (rc) return rc; }             // observation = observe(env), :17
+    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
+    { int rc = traj_record_launch(h, r, TrajStep{nullptr, nullptr, nullptr, nullptr, wrapped ? h->e_obs_raw : h->e_obs}, 0); if (rc) return rc; }   // row 0: the original observation
+    const int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, kEvalPollStepwise));
+    int32_t steps = 0, launches = 0; unsigned int seen = 0;
+    while (seen < (unsigned int)M) {
+        if (steps >= Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
+        for (int k = 0; k < K && steps < Tcap; ++k) { int rc = traj_step(h, r, ++steps, (o->deterministic ? 1 : 0), &launches); if (rc) return rc; }
+        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        seen = *h->eval_counter_host;
+    }
+    // copy-out: lengths first, then rows 0..longest only, reordered into the caller's per-trajectory layout on the host
+    HIPCHK(h, hipMemcpyAsync(lengths, r.rec.length, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(end_flags, r.rec.end_flags, (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int32_t longest = 0, cuts = 0;
+    for (int m = 0; m < M; ++m) {
+        if (lengths[m] < 1 || lengths[m] > Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: trajectory " + std::to_string(m) + " has length " + std::to_string(lengths[m]) + " (internal)");
+        longest = std::max(longest, lengths[m]); cuts += (end_flags[m] & kTrajCut) ? 1 : 0;
+    }
+    std::vector<float> obs_tm((size_t)(longest + 1) * M * D), rew_tm((size_t)longest * M); std::vector<uint32_t> act_tm((size_t)longest * M * W);
+    HIPCHK(h, hipMemcpyAsync(obs_tm.data(), r.rec.obs, obs_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(act_tm.data(), r.rec.act, act_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(rew_tm.data(), r.rec.rew, rew_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    traj_reorder(M, (int64_t)D, (int64_t)W, Tcap, lengths, obs_tm.data(), act_tm.data(), rew_tm.data(), observations, (uint32_t*)actions, rewards);
+    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; }
+    return DRIL_OK;
+}
+}  // namespace
+DRIL_EXPORT int32_t dril_traj_options_default(dril_traj_options* o) {
+    if (!o) return DRIL_ERR_INVALID_ARG;
+    std::memset(o, 0, sizeof(*o));
+    o->n_trajectories = 1; o->deterministic = 1;                                       // trajectory_utils.jl:6-8
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_trajectory_capacity(const dril_handle* h, const dril_traj_options* o, int32_t* capacity) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!o || !capacity || o->max_steps < 0) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_trajectory_capacity: options and capacity != NULL, max_steps >= 0");
+    if (h->external) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_trajectory_capacity: the envs of DRIL_ENV_EXTERNAL live on the host, with the caller");
+    *capacity = traj_capacity(o->max_steps, h->env.episode_len);
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_traj_options* o, float* observations, void* actions, float* rewards, int32_t* lengths,
+                                                   uint8_t* end_flags, dril_traj_info* info) {
+    NEED(h); NOT_EXTERNAL(h, "dril_collect_trajectory_device");
+    if (!o || !observations || !actions || !rewards || !lengths || !end_flags || o->n_trajectories < 1 || o->n_trajectories > h->cfg.n_envs || o->max_steps < 0 || o->poll_steps < 0)
+        return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: options and the five output arrays != NULL, 1 <= n_trajectories <= n_envs, max_steps >= 0, poll_steps >= 0");
+    if (info) std::memset(info, 0, sizeof(*info));
+    const int32_t Tcap = traj_capacity(o->max_steps, h->env.episode_len);
+    const int64_t bytes = traj_bytes(o->n_trajectories, Tcap, h->D, h->discrete ? 1 : h->A);
+    if (bytes > kTrajMaxBytes)
+        return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: the recording needs " + std::to_string(bytes) + " bytes on the device (M = " + std::to_string(o->n_trajectories) + ", Tcap = " + std::to_string(Tcap) + "), more than 1 GiB: record fewer envs or set max_steps");
+    { int rc = ensure_wimg(h); if (rc) return rc; }
+    EvalKeep keep; eval_keep_list(h, false, keep);
+    { int rc = eval_buffers(h, keep, 0); if (rc) return rc; }
+    TrajRun run{};
+    { int rc = traj_prepare(h, o, Tcap, run); if (rc) return rc; }
+    // as dril_evaluate_agent_device: what training would continue from is set aside here and put back below, on every path
+    keep.seed0 = h->env.seed0; keep.ready = h->env.ready; keep.obs_par = h->obs_par; keep.ret_par = h->ret_par; keep.norm_training = h->cfg.norm_training;
+    keep.pn_training = h->pn.cfg.training; keep.mon_cur_ret = h->mon_cur_ret; keep.gws_launches = h->gws.launches;
+    { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
+    h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false), :12
+    h->mon_cur_ret = nullptr;                                                          // the recorded episodes do not enter the training env's MonitorWrapperEnv
+    const int rc = traj_device_run(h, o, run, observations, actions, rewards, lengths, end_flags, info);
+    const std::string msg = h->err;
+    h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
+    h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
+    int rr = eval_keep_copy(h, keep, false);
+    if (rr == DRIL_OK) { const hipError_t e = hipStreamSynchronize(h->stream); if (e != hipSuccess) rr = fail(h, DRIL_ERR_HIP, std::string("dril_collect_trajectory_device: ") + hipGetErrorString(e)); }
+    if (rc != DRIL_OK) { h->err = msg; return rc; }
+    return rr;
 }
 
 // ---- train! ------------------------------------------------------------------------------------------

@@ -1,0 +1,105 @@
+// dril_traj_record.h — the per-env recording of a device-resident collect_trajectory (trajectory_utils.jl:3-49) on a PPO handle: what the lanes of env m do with the
+// action, the reward, the done flags and the observation of its step — the active test, what is written where, finalisation, and the precedence of the episode's end
+// over the max_steps cut.  No HIP dependency, in the manner of dril_eval_account.h: dril_api.hip (traj_record_kernel, over the E-sized per-step arrays and the shadow
+// envs' observation) includes it, and tests/test_traj_device.py drives the same lines with g++ against a restatement of the reference's loop.
+//
+// The recording is step-major on the device, [t][m][.], so one step's writes are contiguous M-sized rows; traj_reorder puts it into the caller's per-trajectory layout.
+// Every index is 64-bit.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/device/dril_scaling.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define DRIL_TRAJ_HD __host__ __device__ __forceinline__
+#else
+#define DRIL_TRAJ_HD inline
+#endif
+
+namespace dril {
+constexpr int32_t kTrajOpen = 0x7f7f7f7f;                       // length[m] of a trajectory still recording (larger than any capacity)
+enum : uint8_t { kTrajTerminated = 1, kTrajTruncated = 2, kTrajCut = 4 };   // end_flags bits; kTrajCut: the reference's "Max steps reached" (:38-41)
+
+// Tcap: the rows a trajectory can need — the env's time limit ends every episode, max_steps (> 0) may end it sooner
+DRIL_TRAJ_HD int32_t traj_capacity(int32_t max_steps, int32_t episode_len) { return (max_steps > 0 && max_steps < episode_len) ? max_steps : episode_len; }
+// bytes of the device recording of M trajectories of capacity Tcap (observations | actions | rewards | lengths | end flags)
+DRIL_TRAJ_HD int64_t traj_bytes(int64_t M, int64_t Tcap, int64_t D, int64_t W) { return 4 * M * ((Tcap + 1) * D + Tcap * W + Tcap) + 5 * M; }
+
+// the recording of one call.  W: 4-byte words of one action (1 for a Discrete space, A for a Box).  length[m] is kTrajOpen until trajectory m is finalised: the ONE
+// word the active test reads, so the lanes of an env need no ordering among themselves (its lane 0 writes t in the launch of step t, and both values mean "record t")
+struct TrajRec {
+    int32_t M, D, W, Tcap;
+    float* obs; uint32_t* act; float* rew;                      // [(Tcap + 1)][M][D], [Tcap][M][W], [Tcap][M]
+    int32_t* length; uint8_t* end_flags; unsigned int* finished;   // [M], [M], ONE counter
+};
+// what happens to the values on their way into the recording.  Observations (obs_low != null: ScalingWrapperEnv) go through unscale_from_unit — rows below the final
+// one always (:19-21), the final row only with final_original (:44 does not unscale).  Box actions: ClampAdapter on the agent-facing Box where clamp_low[a] <
+// clamp_high[a] (to_env), then unscale! under the wrapper (act_low != null, :30-32)
+struct TrajMaps {
+    const float *obs_low, *obs_high, *clamp_low, *clamp_high, *act_low, *act_high;
+    int32_t discrete, final_original;
+};
+// one env step's arrays, E-sized, env-major (the handle's per-step arrays; obs is the shadow envs' post-step, pre-reset observation)
+struct TrajStep { const void* act; const float* rew; const uint8_t* term; const uint8_t* trunc; const float* obs; };
+
+DRIL_TRAJ_HD bool traj_active(const TrajRec& r, int32_t t, int32_t m) { return t == 0 || r.length[m] >= t; }
+DRIL_TRAJ_HD void traj_count_finished(unsigned int* counter) {
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__CUDA_ARCH__)
+    atomicAdd(counter, 1u);
+#else
+    (*counter)++;
+#endif
+}
+DRIL_TRAJ_HD uint32_t traj_f2u(float f) { union { float f; uint32_t u; } v; v.f = f; return v.u; }
+DRIL_TRAJ_HD float traj_u2f(uint32_t u) { union { float f; uint32_t u; } v; v.u = u; return v.f; }
+// the env action of word j (:28-34): predict_actions' to_env, then unscale! under ScalingWrapperEnv
+DRIL_TRAJ_HD uint32_t traj_env_action(const TrajMaps& x, int32_t j, uint32_t raw) {
+    if (x.discrete) return raw;
+    float v = traj_u2f(raw);
+    if (x.clamp_low && x.clamp_low[j] < x.clamp_high[j]) v = fminf(fmaxf(v, x.clamp_low[j]), x.clamp_high[j]);
+    if (x.act_low) v = unscale_from_unit(v, x.act_low[j], x.act_high[j]);
+    return traj_f2u(v);
+}
+// Lane j of env m after env step t (1-based; t = 0: after the initial observe, s.obs the raw observation, nothing else read).  j < D writes observation row t,
+// j < W action row t - 1, lane 0 the reward of row t - 1 and, where the trajectory ends here, its length, its flags and the finished-counter.  The episode's end
+// takes precedence over the cut when both fall on step Tcap.  Steps after the trajectory ended (a second episode of a fast env, steps enqueued past the last finish)
+// write nothing.
+DRIL_TRAJ_HD void traj_record_lane(const TrajRec& r, const TrajMaps& x, const TrajStep& s, int32_t t, int32_t m, int32_t j) {
+    if (t == 0) {
+        if (j < r.D) { const float o = s.obs[(int64_t)m * r.D + j]; r.obs[(int64_t)m * r.D + j] = x.obs_low ? unscale_from_unit(o, x.obs_low[j], x.obs_high[j]) : o; }
+        if (j == 0) { r.length[m] = kTrajOpen; r.end_flags[m] = 0; }
+        return;
+    }
+    if (t > r.Tcap || !traj_active(r, t, m)) return;
+    const bool term = s.term[m] != 0, trunc = s.trunc[m] != 0, done = term || trunc, cut = !done && t >= r.Tcap, last = done || cut;
+    const int64_t row = (int64_t)t * r.M + m, prev = row - r.M;
+    if (j < r.D) {
+        const float o = s.obs[(int64_t)m * r.D + j];
+        r.obs[row * r.D + j] = (x.obs_low && (!last || x.final_original)) ? unscale_from_unit(o, x.obs_low[j], x.obs_high[j]) : o;
+    }
+    if (j < r.W) r.act[prev * r.W + j] = traj_env_action(x, j, ((const uint32_t*)s.act)[(int64_t)m * r.W + j]);
+    if (j == 0) {
+        r.rew[prev] = s.rew[m];
+        if (last) {
+            r.length[m] = t;
+            r.end_flags[m] = (uint8_t)((term ? kTrajTerminated : 0) | (trunc ? kTrajTruncated : 0) | (cut ? kTrajCut : 0));
+            traj_count_finished(r.finished);
+        }
+    }
+}
+// the caller's layout from rows 0..longest of the step-major recording (host side): observations (D, Tcap + 1, M), actions (W, Tcap, M), rewards (Tcap, M), all
+// column-major; rows past a trajectory's own length are zero
+inline void traj_reorder(int64_t M, int64_t D, int64_t W, int64_t Tcap, const int32_t* length, const float* obs_tm, const uint32_t* act_tm, const float* rew_tm,
+                         float* obs, uint32_t* act, float* rew) {
+    for (int64_t m = 0; m < M; ++m) {
+        const int64_t L = length[m];
+        for (int64_t t = 0; t <= Tcap; ++t)
+            for (int64_t d = 0; d < D; ++d) obs[(m * (Tcap + 1) + t) * D + d] = t <= L ? obs_tm[(t * M + m) * D + d] : 0.f;
+        for (int64_t t = 0; t < Tcap; ++t) {
+            for (int64_t a = 0; a < W; ++a) act[(m * Tcap + t) * W + a] = t < L ? act_tm[(t * M + m) * W + a] : 0u;
+            rew[m * Tcap + t] = t < L ? rew_tm[t * M + m] : 0.f;
+        }
+    }
+}
+}  // namespace dril

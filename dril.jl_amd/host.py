@@ -24,6 +24,7 @@ import math
 import os
 import sys
 import time
+import warnings
 from dataclasses import dataclass, field, asdict
 from typing import Optional, Sequence
 
@@ -858,6 +859,32 @@ class Handle:
         self._chk(self.lib.dril_evaluate_agent_device(self._h, C.byref(o), C.byref(st), self._p(er), self._p(el), C.byref(info)))
         return (dict(mean_reward=st.mean_reward, std_reward=st.std_reward, mean_length=st.mean_length, std_length=st.std_length, n_steps=st.n_steps), er, el,
                 dict(path=info.path, launches=info.launches, steps_enqueued=info.steps_enqueued, events=info.events))
+
+    def collect_trajectory_device(self, n_trajectories: int = 1, max_steps: Optional[int] = None, deterministic: bool = True, seed: Optional[int] = None,
+                                  poll_steps: int = 0, final_original: bool = False):
+        """collect_trajectory on the device, leaving nothing behind on the handle (dril_collect_trajectory_device, docs/evaluation.md): envs 0..n_trajectories-1 record
+        their first episode after the call's own reset -> (trajectories, lengths, end_flags, info dict).  trajectories[m] = (observations (L+1, D), actions (L,) | (L, A),
+        rewards (L,)): original observations (rows 0..L-1 unscaled under ScalingWrapperEnv, never normalised), the actions the env's physics received, raw rewards;
+        the last observation is the terminal state as the wrapper delivers it (final_original: unscaled too).  end_flags: capi.TRAJ_TERMINATED | TRAJ_TRUNCATED |
+        TRAJ_MAX_STEPS.  info: capacity, steps_enqueued, launches, longest, cut_by_max_steps."""
+        o = capi.DrilTrajOptions()
+        self._chk(self.lib.dril_traj_options_default(C.byref(o)))
+        o.n_trajectories, o.max_steps, o.deterministic = int(n_trajectories), 0 if max_steps is None else int(max_steps), int(deterministic)
+        o.poll_steps, o.final_original = int(poll_steps), int(bool(final_original))
+        if max_steps is not None and int(max_steps) < 1:
+            raise ValueError("max_steps is None or >= 1")
+        if seed is not None:
+            o.seed, o.has_seed = int(seed), 1
+        cap, info = C.c_int32(), capi.DrilTrajInfo()
+        self._chk(self.lib.dril_trajectory_capacity(self._h, C.byref(o), C.byref(cap)))
+        M, T = max(int(n_trajectories), 1), cap.value
+        obs = np.empty((M, T + 1, self.D), np.float32)
+        act = np.empty((M, T), np.int32) if self.discrete else np.empty((M, T, self.A), np.float32)
+        rew = np.empty((M, T), np.float32); lengths = np.empty(M, np.int32); flags = np.empty(M, np.uint8)
+        self._chk(self.lib.dril_collect_trajectory_device(self._h, C.byref(o), self._p(obs), self._p(act), self._p(rew), self._p(lengths), self._p(flags), C.byref(info)))
+        trajs = [(obs[m, :L + 1].copy(), act[m, :L].copy(), rew[m, :L].copy()) for m, L in enumerate(lengths)]
+        return trajs, lengths, flags, dict(capacity=info.capacity, steps_enqueued=info.steps_enqueued, launches=info.launches, longest=info.longest,
+                                           cut_by_max_steps=info.cut_by_max_steps)
 
     def train(self, max_steps: int):
         per_iter = self.N * self.cfg.world_size
@@ -1716,6 +1743,24 @@ def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 
     if reward_threshold is not None and stats["mean_reward"] < reward_threshold:
         raise RuntimeError(f"Mean reward below threshold: {stats['mean_reward']:.2f} < {reward_threshold}")   # evaluation.jl:131-135
     return {k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} if return_stats else (er, el)
+
+
+def collect_trajectory(agent: Agent, env: DeviceParallelEnv, max_steps: Optional[int] = None, norm_env=None, deterministic: bool = True,
+                       n_trajectories: int = 1, seed: Optional[int] = None):
+    """collect_trajectory(agent, env; max_steps, norm_env, deterministic) (src/utils/trajectory_utils.jl:3-49) -> (observations, actions, rewards): the original
+    observations (L + 1 of them, the last one the terminal state), the env actions and the raw rewards of one episode; n_trajectories > 1: a list of such triples,
+    envs 0..n-1 of the parallel env, each its first episode after the reset.  Runs on the device and leaves the env as it was (Handle.collect_trajectory_device,
+    docs/evaluation.md).  norm_env: None, or `env` itself — a NormalizeWrapperEnv around the device env is a mode of its handle, found there and applied frozen."""
+    if isinstance(env, (HostParallelEnv, DeviceArrayParallelEnv)):
+        raise NotImplementedError("collect_trajectory: host envs (HostParallelEnv, DeviceArrayParallelEnv) live with the caller; the device verb steps device envs")
+    if norm_env is not None and norm_env is not env:
+        raise NotImplementedError("collect_trajectory: norm_env is None or the env itself (NormalizeWrapperEnv around a device env is a mode of the env's handle and is applied frozen)")
+    h = env.bind(agent.alg, agent.layer)
+    h.set_params(flatten_params(agent.train_state.parameters))
+    trajs, _, flags, _ = h.collect_trajectory_device(n_trajectories, max_steps, deterministic, seed)
+    if (flags & capi.TRAJ_MAX_STEPS).any():
+        warnings.warn("Max steps reached")                                           # trajectory_utils.jl:39
+    return trajs[0] if n_trajectories == 1 else trajs
 
 
 def get_action_and_values(agent: Agent, env: DeviceParallelEnv, observations):

@@ -62,6 +62,41 @@ function DRiL.evaluate_agent(agent, env::DeviceParallelEnv; n_eval_episodes::Int
 end
 
 
+# ---- collect_trajectory(agent, env::DeviceParallelEnv; ...)  (src/utils/trajectory_utils.jl:3-49) ----
+# dril_traj_options / dril_traj_info (include/dril_hip.h): the reference loop on the device, once per recorded env, leaving the env as it was (docs/evaluation.md)
+struct DrilTrajOptions
+    n_trajectories::Int32; max_steps::Int32; deterministic::Int32
+    has_seed::Int32; seed::UInt64
+    poll_steps::Int32; final_original::Int32
+    reserved::NTuple{5, Int32}
+end
+struct DrilTrajInfo
+    capacity::Int32; steps_enqueued::Int32; launches::Int32; longest::Int32; cut_by_max_steps::Int32; reserved::NTuple{3, Int32}
+end
+# -> (observations, actions, rewards) as the reference returns them (L + 1 original observations, L env actions, L raw rewards); n_trajectories > 1: a vector of such
+# tuples, envs 1..n of the parallel env, each its first episode after the reset.  A NormalizeWrapperEnv around the device env is a mode of its handle: applied frozen.
+function DRiL.collect_trajectory(agent, env::DeviceParallelEnv; max_steps::Union{Int, Nothing} = nothing, deterministic::Bool = true, n_trajectories::Int = 1, kwargs...)
+    bind_agent!(env, agent, agent.algorithm); push_params!(env, agent)
+    h = env.handle
+    o = Ref(DrilTrajOptions(Int32(n_trajectories), Int32(max_steps === nothing ? 0 : max_steps), Int32(deterministic), Int32(0), UInt64(0), Int32(0), Int32(0),
+        (Int32(0), Int32(0), Int32(0), Int32(0), Int32(0))))
+    cap = Ref{Int32}(0)
+    check(ccall((:dril_trajectory_capacity, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilTrajOptions}, Ref{Int32}), h, o, cap), h)
+    D = obs_dim(env); T = Int(cap[]); M = n_trajectories; disc = is_discrete(env)
+    A = disc ? 1 : Int(ccall((:dril_action_dim, LIB[]), Int32, (Ptr{Cvoid},), h))
+    obs = Array{Float32}(undef, D, T + 1, M); rew = Matrix{Float32}(undef, T, M); len = Vector{Int32}(undef, M); flags = Vector{UInt8}(undef, M)
+    act = disc ? Array{Int32}(undef, 1, T, M) : Array{Float32}(undef, A, T, M)
+    GC.@preserve obs act rew len flags check(ccall((:dril_collect_trajectory_device, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilTrajOptions}, Ptr{Float32}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}, Ptr{UInt8}, Ptr{DrilTrajInfo}),
+        h, o, obs, act, rew, len, flags, C_NULL), h)
+    any(f -> f & 0x04 != 0, flags) && @warn "Max steps reached"                                                    # trajectory_utils.jl:39
+    trajs = map(1:M) do m
+        L = Int(len[m])
+        ([obs[:, t, m] for t in 1:(L + 1)], disc ? [Int(act[1, t, m]) for t in 1:L] : [act[:, t, m] for t in 1:L], [rew[t, m] for t in 1:L])
+    end
+    return M == 1 ? trajs[1] : trajs
+end
+
+
 # ---- deployment policies on the device (include/dril_policy.h): the device twin of extract_policy (src/deployment/deployment_policy.jl) ----
 # DRiL.extract_policy(agent[, norm_env]) keeps working on the host parameters train! writes back; a DevicePolicy is the same thing as one light device object
 # (actor + adapter + frozen observation statistics) that answers in one kernel launch.  Calls on one DevicePolicy must not overlap.

@@ -564,6 +564,41 @@ int32_t dril_eval_options_default(dril_eval_options* o);   /* 10 episodes, deter
 int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_options* o, dril_eval_stats* out,
                                    float* episode_rewards, int32_t* episode_lengths, dril_eval_info* info /* may be NULL */);
 
+/* ---- collect_trajectory on the device (src/utils/trajectory_utils.jl:3-49; docs/evaluation.md, "Trajectories") ---- */
+/* The reference loop, once per recorded env and independently of the others: envs 0..M-1 of this handle record their FIRST episode after the call's own reset.
+ * Row t < L of a trajectory is the ORIGINAL observation before step t + 1 (never normalised; mapped back with unscale_from_unit under ScalingWrapperEnv), action row t
+ * what predict_actions returns after to_env (and after unscale! under ScalingWrapperEnv: the value the env's physics receives), reward row t the env's own raw reward.
+ * The agent sees the wrapper's observation: scaled, and normalised with the statistics in force, FROZEN for the call (every normaliser of the handle, as in
+ * dril_evaluate_agent_device).  Row L is observe(env) of the env that did not auto-reset — the terminal state, in the wrapper's scale unless final_original.
+ * The episode ends at its first terminated || truncated, or after max_steps steps; the episode's end takes precedence when both coincide.  With deterministic = 0 the
+ * draws are those of dril_evaluate_agent_device on the same seed.  The trajectory of env m does not depend on M, on poll_steps or on the other envs.
+ * The call leaves nothing behind: everything dril_evaluate_agent_device sets aside and puts back is set aside and put back here, on error paths too; the monitor's
+ * launches are not made and no all-reduce is enqueued (each rank of a data-parallel job records its own envs).
+ * DRIL_ERR_NOT_INITIALISED: null handle.  DRIL_ERR_INVALID_ARG: null options or output array, n_trajectories outside 1..n_envs, negative max_steps or poll_steps, a
+ * recording whose device arrays exceed 1 GiB.  DRIL_ERR_UNSUPPORTED: DRIL_ENV_EXTERNAL (the envs live with the caller). */
+typedef struct dril_traj_options {
+    int32_t n_trajectories;              /* M: envs 0..M-1 record; 1 <= M <= n_envs */
+    int32_t max_steps;                   /* trajectory_utils.jl:6,38-41; 0 = nothing (the env's time limit ends every episode) */
+    int32_t deterministic;               /* :8, default 1 */
+    int32_t has_seed; uint64_t seed;     /* as dril_eval_options: 0 = the env seed in force; else env e resets with seed + global env index */
+    int32_t poll_steps;                  /* env steps between two looks at the finished-counter; 0 = the library's default */
+    int32_t final_original;              /* 0 (reference): the last observation as ScalingWrapperEnv delivers it (:44); 1: unscaled like rows 0..L-1 */
+    int32_t reserved[5];
+} dril_traj_options;
+typedef struct dril_traj_info {
+    int32_t capacity, steps_enqueued, launches, longest, cut_by_max_steps, reserved[3];   /* Tcap, env steps enqueued, launch calls of the loop, max L, trajectories with bit 2 */
+} dril_traj_info;
+int32_t dril_traj_options_default(dril_traj_options* o);   /* M = 1, deterministic, the rest 0 */
+/* Tcap = max_steps > 0 ? min(max_steps, episode_len) : episode_len: the rows the output arrays are sized with */
+int32_t dril_trajectory_capacity(const dril_handle* h, const dril_traj_options* o, int32_t* capacity);
+int32_t dril_collect_trajectory_device(dril_handle* h, const dril_traj_options* o,
+                                       float* observations,  /* (D, Tcap+1, M) column-major: trajectory m, row t at ((m*(Tcap+1)+t)*D); rows > lengths[m] are 0 */
+                                       void* actions,        /* i32 (Tcap, M) | f32 (A, Tcap, M); rows >= lengths[m] are 0 */
+                                       float* rewards,       /* (Tcap, M) */
+                                       int32_t* lengths,     /* (M): steps taken */
+                                       uint8_t* end_flags,   /* (M): bit0 terminated, bit1 truncated, bit2 stopped by max_steps ("Max steps reached") */
+                                       dril_traj_info* info  /* may be NULL; the five arrays may not */);
+
 /* ---- train! ------------------------------------------------------------------ */
 /* iterations = max_steps / (T*E*world) of {set lr, collect_rollout!, ppo update}: ppo.jl:154-298.
  * stats / fps arrays need `iterations` entries (may be NULL) */
