@@ -37,6 +37,47 @@ inline int epi_of_activation(int act) { return act == 1 ? EPI_RELU : act == 2 ? 
 inline int mask_epi_of_activation(int act) { return act == 1 ? EPI_MASK_RELU : act == 2 ? EPI_MASK_SIGMOID : act == 3 ? EPI_MASK_ELU : act == 4 ? EPI_MASK_LEAKY : act == 5 ? EPI_MASK_SOFTPLUS : act == 6 ? EPI_MASK_GELU : act == 7 ? EPI_MASK_SWISH : EPI_MASK_TANH; }
 
 GemmArgs gemm_args();
+
+// The kernels launch_gemm picks between, in ONE table: X(id, name, grid shape, kernel).  launch_gemm switches on gemm_select() and launches the kernel of the
+// selected row, gemm_target_name() prints the name of the same row (tests/gemm_check.hip --plan, tests/test_gemm_plan.py), so neither can drift from the other.
+// Grid shapes (dril_gemm.hip gemm_grid): TILE one workgroup per 32 x 32 tile (its 8 waves split K), ROW8 one per 32 x 256 block (a tile per wave),
+// SPLIT2 one per 64 x 256 block (two m-tiles per wave); LDS = TILE with the 66 KB dynamic LDS block.
+// lds_<A><B>: access pattern of the staged operand, 0 k-contiguous float4, 1 row-contiguous float4 (GemmArgs.ldsA / ldsB: one kernel, four bodies).
+// big / split <am|ak>_<bk|bn>: A m- or k-contiguous, B k- or n-contiguous; split = the bf16 three-piece operand split, mb = m-tiles per wave.
+#define DRIL_GEMM_TARGETS(X) \
+    X(GEMM_DIRECT_SPLITK, "direct_splitk", GEMM_GRID_TILE, (sac_gemm_kernel<true>)) \
+    X(GEMM_DIRECT_TILES, "direct_tiles", GEMM_GRID_ROW8, (sac_gemm_kernel<false>)) \
+    X(GEMM_LDS_00, "lds_00", GEMM_GRID_LDS, (sac_gemm_lds_kernel)) \
+    X(GEMM_LDS_01, "lds_01", GEMM_GRID_LDS, (sac_gemm_lds_kernel)) \
+    X(GEMM_LDS_10, "lds_10", GEMM_GRID_LDS, (sac_gemm_lds_kernel)) \
+    X(GEMM_LDS_11, "lds_11", GEMM_GRID_LDS, (sac_gemm_lds_kernel)) \
+    X(GEMM_BIG_AM_BK, "big_am_bk", GEMM_GRID_ROW8, (sac_gemm_big_kernel<false, false>)) \
+    X(GEMM_BIG_AK_BK, "big_ak_bk", GEMM_GRID_ROW8, (sac_gemm_big_kernel<true, false>)) \
+    X(GEMM_BIG_AM_BN, "big_am_bn", GEMM_GRID_ROW8, (sac_gemm_big_kernel<false, true>)) \
+    X(GEMM_BIG_AK_BN, "big_ak_bn", GEMM_GRID_ROW8, (sac_gemm_big_kernel<true, true>)) \
+    X(GEMM_SPLIT_AM_BK_MB1, "split_am_bk_mb1", GEMM_GRID_ROW8, (sac_gemm_split_kernel<false, false, 1, 1>)) \
+    X(GEMM_SPLIT_AK_BK_MB1, "split_ak_bk_mb1", GEMM_GRID_ROW8, (sac_gemm_split_kernel<true, false, 1, 1>)) \
+    X(GEMM_SPLIT_AM_BN_MB1, "split_am_bn_mb1", GEMM_GRID_ROW8, (sac_gemm_split_kernel<false, true, 1, 1>)) \
+    X(GEMM_SPLIT_AK_BN_MB1, "split_ak_bn_mb1", GEMM_GRID_ROW8, (sac_gemm_split_kernel<true, true, 1, 1>)) \
+    X(GEMM_SPLIT_AM_BK_MB2, "split_am_bk_mb2", GEMM_GRID_SPLIT2, (sac_gemm_split_kernel<false, false, 2, 1>)) \
+    X(GEMM_SPLIT_AK_BK_MB2, "split_ak_bk_mb2", GEMM_GRID_SPLIT2, (sac_gemm_split_kernel<true, false, 2, 1>)) \
+    X(GEMM_SPLIT_AM_BN_MB2, "split_am_bn_mb2", GEMM_GRID_SPLIT2, (sac_gemm_split_kernel<false, true, 2, 1>)) \
+    X(GEMM_SPLIT_AK_BN_MB2, "split_ak_bn_mb2", GEMM_GRID_SPLIT2, (sac_gemm_split_kernel<true, true, 2, 1>))
+enum GemmTarget {
+#define DRIL_GEMM_TARGET_ID(id, name, grid, kernel) id,
+    DRIL_GEMM_TARGETS(DRIL_GEMM_TARGET_ID)
+#undef DRIL_GEMM_TARGET_ID
+    GEMM_TARGET_COUNT
+};
+enum GemmGrid { GEMM_GRID_TILE, GEMM_GRID_LDS, GEMM_GRID_ROW8, GEMM_GRID_SPLIT2 };
+// fills the derived fields (vecA / vecB / vecBn, use_lds, ldsA / ldsB, dbg) from shape, strides and pointer alignment; false: an empty contraction
+bool gemm_prepare(GemmArgs& g);
+// the split-K body a PREPARED contraction runs on: GEMM_LDS_<ldsA><ldsB> with use_lds, else GEMM_DIRECT_SPLITK.  launch_gemm below its tile-count threshold,
+// and launch_gemm_pair / launch_gemm_multi for each of their contractions on its own (gemm_body_any)
+inline GemmTarget gemm_splitk_body(const GemmArgs& g) { return g.use_lds ? (GemmTarget)(GEMM_LDS_00 + 2 * g.ldsA + g.ldsB) : GEMM_DIRECT_SPLITK; }
+// the kernel launch_gemm runs for a PREPARED contraction of Z batches (a host function of the arguments alone: no device call)
+GemmTarget gemm_select(const GemmArgs& g, int Z);
+const char* gemm_target_name(GemmTarget t);
 // one contraction, Z batches (blockIdx.z); picks the split-K / tile-parallel / LDS-tiled shape from the tile count
 hipError_t launch_gemm(GemmArgs g, int Z, hipStream_t s);
 // two independent contractions in one launch (a layer's [dW | db] and its dz): blockIdx.z < Za runs `a`

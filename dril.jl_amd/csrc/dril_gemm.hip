@@ -505,8 +505,10 @@ __global__ __launch_bounds__(64 * kGemmWaves, 4) void sac_gemm_split_kernel(Gemm
                 const bf16x8 Ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&Ap[ao]));
                 const bf16x8 Am = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&Ap[kSplitAImg + ao]));
                 const bf16x8 Al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&Ap[2 * kSplitAImg + ao]));
+#ifndef DRIL_DEBUG_DROP_LO                                                                   // NEGATIVE CONTROL (tests/test_gpu_gemm.py compiles tests/gemm_check.hip with it, never the library): four of six products, 2^-16 relative
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc[t], 0, 0, 0);   // small terms first
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc[t], 0, 0, 0);
+#endif
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc[t], 0, 0, 0);
@@ -553,6 +555,9 @@ __global__ __launch_bounds__(64 * kGemmWaves, 4) void sac_gemm_multi_kernel(Gemm
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+}  // namespace
+
 bool gemm_prepare(GemmArgs& g) {
     g.vecA = g.sAk == 1 && g.sAm % 4 == 0 && g.K % 4 == 0 && aligned16(g.A) && g.zA % 4 == 0;
     g.vecB = !g.ones_n && g.sBk == 1 && g.sBn % 4 == 0 && g.K % 4 == 0 && aligned16(g.B) && g.zB % 4 == 0;
@@ -566,8 +571,6 @@ bool gemm_prepare(GemmArgs& g) {
     static const int dbg_bits = debug_env("DRIL_GEMM_DBG") ? std::atoi(debug_env("DRIL_GEMM_DBG")) : 0; g.dbg = dbg_bits;   // diagnostic ablations (results wrong on purpose)
     return g.M > 0 && g.N > 0 && g.K > 0;
 }
-
-}  // namespace
 
 // kernels that take the 66 KB dynamic LDS block: raise the limit once per kernel and device context
 static hipError_t lds_attr(const void* fn) {
@@ -605,15 +608,13 @@ hipError_t launch_gemm_multi(const GemmArgs* gs, const int* Zs, int n, hipStream
     hipLaunchKernelGGL(sac_gemm_multi_kernel, dim3((unsigned)total), dim3(64 * kGemmWaves), kLdsBytes, s, p);
     return hipGetLastError();
 }
-hipError_t launch_gemm(GemmArgs g, int Z, hipStream_t s) {
-    if (!gemm_prepare(g)) return hipErrorInvalidValue;
+// the ONE definition of launch_gemm's choice (dril_gemm.h DRIL_GEMM_TARGETS); g is prepared
+GemmTarget gemm_select(const GemmArgs& g, int Z) {
     const int tm = (g.M + 31) / 32, tn = (g.N + 31) / 32;
-    if ((tn + kGemmWaves - 1) / kGemmWaves > 65535 || Z > 65535) return hipErrorInvalidValue;
     constexpr long long many_tiles = 2048;                                                                 // tile count from which the LDS-tiled throughput shapes take over from split-K (measured both ways at 2 048 tiles: 31 vs 43 us)
     const bool many = (long long)tm * tn * Z >= many_tiles && g.K >= kBigKc;
     const bool a_m = g.sAm == 1, a_k = !a_m && g.sAk == 1;                                             // A m-contiguous / k-contiguous
     const bool b_k = g.sBk == 1 && g.vecB && !g.ones_n, b_n = !b_k && g.sBn == 1 && g.sBk != 1;        // B k-contiguous (float4 rows) / n-contiguous
-    const dim3 bgrid(tm, (tn + kGemmWaves - 1) / kGemmWaves, Z), bblock(64 * kGemmWaves);
     static const bool split_all = debug_env("DRIL_GEMM_SPLIT") != nullptr;                                // A/B: also for callers that did not ask (SAC)
     const bool split = many && (g.allow_split || split_all) && g.K >= 64;
     if (split && (a_m || a_k) && (b_k || b_n)) {
@@ -625,27 +626,47 @@ hipError_t launch_gemm(GemmArgs g, int Z, hipStream_t s) {
         // inside one workgroup (staging of chunk i + 1 interleaved with the MFMAs of chunk i, loads two chunks ahead; built, parity-green) was slower still (55):
         // the split form reads 0.75 ds_read_b128 per MFMA (9 reads per 12 MFMAs of 32 cycles), ~2000 LDS cycles per chunk against 1536 MFMA cycles per SIMD —
         // the kernel is LDS-read-bound, and the next step is 2 x 2 register tiling per wave (0.5 reads per MFMA), not more overlap.
-        constexpr int mb_cap = 2;                                                                           // (1, 2, 4 are built; 4 measured slower, comment above)
-        int MB = 1;
         const long long tn256 = (g.N + 255) / 256;
-        for (int cand = 4; cand > 1; cand >>= 1) if (cand <= mb_cap && g.M >= 32 * cand && (long long)((g.M + 32 * cand - 1) / (32 * cand)) * tn256 * Z >= 512) { MB = cand; break; }
-        const dim3 sgrid((g.M + 32 * MB - 1) / (32 * MB), bgrid.y, Z);
-#define DRIL_SPLIT_LAUNCH(AKv, BNv) { if (MB == 4) hipLaunchKernelGGL((sac_gemm_split_kernel<AKv, BNv, 4, 1>), sgrid, bblock, 0, s, g); \
-                                      else if (MB == 2) hipLaunchKernelGGL((sac_gemm_split_kernel<AKv, BNv, 2, 1>), sgrid, bblock, 0, s, g); \
-                                      else hipLaunchKernelGGL((sac_gemm_split_kernel<AKv, BNv, 1, 1>), sgrid, bblock, 0, s, g); }
-        if (a_m && b_k) DRIL_SPLIT_LAUNCH(false, false) else if (a_k && b_k) DRIL_SPLIT_LAUNCH(true, false) else if (a_m && b_n) DRIL_SPLIT_LAUNCH(false, true) else DRIL_SPLIT_LAUNCH(true, true)
-#undef DRIL_SPLIT_LAUNCH
+        const bool mb2 = g.M >= 64 && (long long)((g.M + 63) / 64) * tn256 * Z >= 512;
+        const int layout = (a_k ? 1 : 0) + (b_k ? 0 : 2);
+        return (GemmTarget)((mb2 ? GEMM_SPLIT_AM_BK_MB2 : GEMM_SPLIT_AM_BK_MB1) + layout);
     }
-    else if (many && a_m && b_k) hipLaunchKernelGGL((sac_gemm_big_kernel<false, false>), bgrid, bblock, 0, s, g);
-    else if (many && a_k && b_k) hipLaunchKernelGGL((sac_gemm_big_kernel<true, false>), bgrid, bblock, 0, s, g);
-    else if (many && a_m && b_n) hipLaunchKernelGGL((sac_gemm_big_kernel<false, true>), bgrid, bblock, 0, s, g);
-    else if (many && a_k && b_n) hipLaunchKernelGGL((sac_gemm_big_kernel<true, true>), bgrid, bblock, 0, s, g);
-    else if ((long long)tm * tn * Z >= many_tiles) hipLaunchKernelGGL(sac_gemm_kernel<false>, dim3(tm, (tn + kGemmWaves - 1) / kGemmWaves, Z), dim3(64 * kGemmWaves), 0, s, g);
-    else if (g.use_lds) {
-        hipError_t e = lds_attr((const void*)sac_gemm_lds_kernel); if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(sac_gemm_lds_kernel, dim3(tm, tn, Z), dim3(64 * kGemmWaves), kLdsBytes, s, g);
+    if (many && (a_m || a_k) && (b_k || b_n)) return (GemmTarget)(GEMM_BIG_AM_BK + (a_k ? 1 : 0) + (b_k ? 0 : 2));
+    if ((long long)tm * tn * Z >= many_tiles) return GEMM_DIRECT_TILES;
+    return gemm_splitk_body(g);
+}
+static_assert(GEMM_BIG_AK_BK == GEMM_BIG_AM_BK + 1 && GEMM_BIG_AM_BN == GEMM_BIG_AM_BK + 2 && GEMM_BIG_AK_BN == GEMM_BIG_AM_BK + 3, "gemm_select: layout offset");
+static_assert(GEMM_SPLIT_AK_BK_MB1 == GEMM_SPLIT_AM_BK_MB1 + 1 && GEMM_SPLIT_AM_BN_MB1 == GEMM_SPLIT_AM_BK_MB1 + 2 && GEMM_SPLIT_AK_BN_MB1 == GEMM_SPLIT_AM_BK_MB1 + 3, "gemm_select: layout offset");
+static_assert(GEMM_SPLIT_AK_BK_MB2 == GEMM_SPLIT_AM_BK_MB2 + 1 && GEMM_SPLIT_AM_BN_MB2 == GEMM_SPLIT_AM_BK_MB2 + 2 && GEMM_SPLIT_AK_BN_MB2 == GEMM_SPLIT_AM_BK_MB2 + 3, "gemm_select: layout offset");
+static_assert(GEMM_LDS_01 == GEMM_LDS_00 + 1 && GEMM_LDS_10 == GEMM_LDS_00 + 2 && GEMM_LDS_11 == GEMM_LDS_00 + 3, "gemm_splitk_body: pattern offset");
+const char* gemm_target_name(GemmTarget t) {
+    switch (t) {
+#define DRIL_GEMM_TARGET_NAME(id, name, grid, kernel) case id: return name;
+        DRIL_GEMM_TARGETS(DRIL_GEMM_TARGET_NAME)
+#undef DRIL_GEMM_TARGET_NAME
+        default: return "?";
     }
-    else hipLaunchKernelGGL(sac_gemm_kernel<true>, dim3(tm, tn, Z), dim3(64 * kGemmWaves), 0, s, g);
+}
+static dim3 gemm_grid(GemmGrid shape, const GemmArgs& g, int Z) {
+    const int tm = (g.M + 31) / 32, tn = (g.N + 31) / 32;
+    if (shape == GEMM_GRID_TILE || shape == GEMM_GRID_LDS) return dim3(tm, tn, Z);
+    return dim3(shape == GEMM_GRID_SPLIT2 ? (g.M + 63) / 64 : tm, (tn + kGemmWaves - 1) / kGemmWaves, Z);
+}
+hipError_t launch_gemm(GemmArgs g, int Z, hipStream_t s) {
+    if (!gemm_prepare(g)) return hipErrorInvalidValue;
+    const int tn = (g.N + 31) / 32;
+    if ((tn + kGemmWaves - 1) / kGemmWaves > 65535 || Z > 65535) return hipErrorInvalidValue;
+    switch (gemm_select(g, Z)) {
+#define DRIL_GEMM_TARGET_LAUNCH(id, name, grid, kernel) \
+        case id: { \
+            if (grid == GEMM_GRID_LDS) { const hipError_t e = lds_attr((const void*)kernel); if (e != hipSuccess) return e; } \
+            hipLaunchKernelGGL(kernel, gemm_grid(grid, g, Z), dim3(64 * kGemmWaves), grid == GEMM_GRID_LDS ? kLdsBytes : 0, s, g); \
+            break; \
+        }
+        DRIL_GEMM_TARGETS(DRIL_GEMM_TARGET_LAUNCH)
+#undef DRIL_GEMM_TARGET_LAUNCH
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
