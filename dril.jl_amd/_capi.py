@@ -94,6 +94,8 @@ class DrilTrajInfo(C.Structure):
 
 
 TRAJ_TERMINATED, TRAJ_TRUNCATED, TRAJ_MAX_STEPS = 1, 2, 4   # dril_collect_trajectory_device: end_flags bits
+# documented slots of the reserved words (dril_hip.h): the opt-in request for the persistent evaluate kernel in both option structs, and the path dril_traj_info reports
+EVAL_OPT_PERSISTENT, TRAJ_OPT_PERSISTENT, TRAJ_INFO_PATH = 0, 0, 0
 
 
 class DrilEnvModuleInfo(C.Structure):

@@ -2243,7 +2243,8 @@ int evaluate_agent_loop(dril_handle* h, int32_t n_eval, int32_t deterministic, d
 // ---- evaluate_agent on the device, training state left untouched (docs/evaluation.md) --------------------------------------------------------
 // The loop of evaluate_agent_loop above with the host taken out of it: the episode accounting of dril_eval_account.h runs on the device, the host looks at ONE 4-byte
 // counter every K env steps, and what the loop writes of the env side is set aside before and put back after.  Two forms of the K steps between two looks:
-//   path 1  ONE launch of evaluate_kernel (dril_kernels.hip): built-in kinds on the fused shapes of width 64 / 128 / 256 with no normaliser
+//   path 1  ONE launch of evaluate_kernel (dril_kernels.hip): built-in kinds on the fused shapes of width 64 / 128 / 256 with no normaliser — and, where the
+//           options ask for it (DRIL_EVAL_OPT_PERSISTENT), under cfg.norm_* too: evaluate_modes_kernel reads the frozen statistics as an argument
 //   path 0  per env step the launches run_policy / step_dev / observe_dev make, and eval_account_kernel over the step's reward and done arrays: everything else
 namespace {
 __global__ __launch_bounds__(256) void eval_account_kernel(EvalAcct a, int32_t step, const float* __restrict__ rew, const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc) {
@@ -2255,9 +2256,25 @@ __global__ __launch_bounds__(256) void eval_account_kernel(EvalAcct a, int32_t s
 // persistent one.  No more than the time limit, after which every env has finished an episode
 constexpr int kEvalPollStepwise = 32, kEvalPollPersistent = 64;
 constexpr long long kEvalMaxLaunchEvents = 1ll << 22;   // E K of one evaluate_kernel launch: 64 MB of event slots at the most
-bool eval_persistent_applies(const dril_handle* h) {
+// requested: the caller's opt-in (DRIL_EVAL_OPT_PERSISTENT / DRIL_TRAJ_OPT_PERSISTENT), which admits a normalised handle; without it, the rule every caller has had
+bool eval_persistent_applies(const dril_handle* h, bool requested = false) {
     const int hd = h->cfg.hidden1;
-    return !h->generic && !h->env.module && !normalizing(h) && !h->force_stepwise && (hd == 64 || hd == 128 || hd == 256);   // (DRIL_FORCE_STEPWISE: the step-granular launches, as for the collection)
+    return !h->generic && !h->env.module && (!normalizing(h) || requested) && !h->force_stepwise && (hd == 64 || hd == 128 || hd == 256);   // (DRIL_FORCE_STEPWISE: the step-granular launches, as for the collection)
+}
+// evaluate_kernel's arguments from the handle (the rollout launcher's choices: fwd_exact, action_start, fixed_length_episodes); T and step0 are set per launch
+void eval_kernel_args(const dril_handle* h, EvalKernelArgs& g, int deterministic) {
+    RolloutArgs& a = g.r;
+    a.params = h->params; a.state = h->env.state; a.step_count = h->env.step_count; a.episode = h->env.episode; a.gstep = h->env.gstep;
+    a.E = h->cfg.n_envs; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len; a.action_start = h->env.action_start; a.log_std_off = h->log_std_off;
+    a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic; a.exact_f32 = fwd_exact(h) ? 1 : 0;
+    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = nullptr;
+    g.deterministic = deterministic ? 1 : 0;
+}
+// the frozen NormalizeWrapperEnv as evaluate_modes_kernel takes it: the halves of the statistics in force, read only.  raw: the accounting counts raw rewards
+void eval_mode_norm(const dril_handle* h, EvalModeArgs& x, bool raw) {
+    x.obs_stats = h->obs_rms + h->obs_par; x.ret_stats = h->ret_rms + h->ret_par;
+    x.norm_obs = h->cfg.norm_obs ? 1 : 0; x.norm_reward = h->cfg.norm_reward ? 1 : 0; x.count_raw = raw ? 1 : 0;
+    x.clip_obs = h->cfg.clip_obs; x.clip_reward = h->cfg.clip_reward; x.eps = h->cfg.norm_epsilon;
 }
 template <typename T> int eval_ensure(dril_handle* h, T** p, size_t n) { if (!*p) HIPCHK(h, dmalloc(p, n)); return DRIL_OK; }
 // what one evaluation sets aside: device arrays in a list (copied to / from one blob), the host-side words next to them
@@ -2324,14 +2341,11 @@ int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent,
     h->env.ready = true;
     HIPCHK(h, hipMemsetAsync(h->eval_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_cur_len, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
     const EvalAcct acct{E, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, (unsigned int)cap};
-    EvalKernelArgs g{};
+    EvalKernelArgs g{}; EvalModeArgs x{};
+    const bool modes = persistent && normalizing(h);                              // a frozen normaliser: evaluate_modes_kernel; otherwise evaluate_kernel as ever
     if (persistent) {
-        RolloutArgs& a = g.r;
-        a.params = h->params; a.state = h->env.state; a.step_count = h->env.step_count; a.episode = h->env.episode; a.gstep = h->env.gstep;
-        a.E = E; a.T = K; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len; a.action_start = h->env.action_start; a.log_std_off = h->log_std_off;
-        a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic; a.exact_f32 = fwd_exact(h) ? 1 : 0;
-        a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = nullptr;
-        g.acct = acct; g.deterministic = (o->deterministic ? 1 : 0);
+        eval_kernel_args(h, g, o->deterministic); g.r.T = K; g.acct = acct;       // (after the seed above: env_seed0 is the one the reset used)
+        if (modes) eval_mode_norm(h, x, raw);
     } else if (normalizing(h) || h->pn.on) { int rc = observe_dev(h, true); if (rc) return rc; }   // observations = observe(env), :88
     else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
     // every env finishes an episode within the time limit, so n of them take at most ceil(n / E) time limits; one more, and the steps enqueued past a look
@@ -2339,7 +2353,7 @@ int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent,
     long long steps = 0; unsigned int seen = 0; int32_t launches = 0;
     while (seen < (unsigned int)n_eval) {
         if (steps >= max_steps) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_evaluate_agent_device: no episode finishes");
-        if (persistent) { g.step0 = (int32_t)steps; HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream)); steps += K; launches += 1; }
+        if (persistent) { g.step0 = (int32_t)steps; HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream, modes ? &x : nullptr)); steps += K; launches += 1; }
         else for (int k = 0; k < K; ++k) { int rc = eval_step_granular(h, acct, (int32_t)(++steps), (o->deterministic ? 1 : 0), raw, &launches); if (rc) return rc; }
         HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2363,7 +2377,7 @@ DRIL_EXPORT int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_o
     if (!o || !out || o->n_eval_episodes < 1 || o->poll_steps < 0) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent_device: options and out != NULL, n_eval_episodes >= 1, poll_steps >= 0");
     if (info) std::memset(info, 0, sizeof(*info));
     { int rc = ensure_wimg(h); if (rc) return rc; }
-    const bool persistent = !o->force_step_granular && eval_persistent_applies(h);
+    const bool persistent = !o->force_step_granular && eval_persistent_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);
     const bool raw = (h->env.module && h->pn.on) || h->mon_cur_ret != nullptr;         // dril_evaluate_agent's rule: raw returns under the monitor (and under a plug-in's normaliser)
     EvalKeep keep; eval_keep_list(h, persistent, keep);
     const int K = eval_poll_steps(h, o, persistent);
@@ -2471,8 +2485,34 @@ int traj_step(dril_handle* h, const TrajRun& r, int32_t t, int deterministic, in
     *launches += (h->generic ? (int32_t)(h->gws.launches - g0) : 1) + 2 + (wrapped ? (h->env.module ? 2 : 3) : 0) + 4 + (h->env.module ? 0 : 1);   // (a built-in shadow step + observe: env_step_kernel, env_observe_kernel)
     return DRIL_OK;
 }
-int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, float* observations, void* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
-    const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap; const size_t D = (size_t)r.rec.D, W = (size_t)r.rec.W;
+// the persistent form: evaluate_modes_kernel in its recording mode, K env steps per launch.  No shadow envs, no state copies, none of the per-step arrays: the lane
+// that holds env m < M records it from its registers.  The last launch is shortened so that no step past Tcap is ever enqueued
+int traj_persistent_run(dril_handle* h, const dril_traj_options* o, const TrajRun& r, int32_t* steps_out, int32_t* launches_out) {
+    const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap;
+    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
+    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :10
+    h->env.ready = true;
+    HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
+    EvalKernelArgs g{}; EvalModeArgs x{};
+    eval_kernel_args(h, g, o->deterministic);
+    if (normalizing(h)) eval_mode_norm(h, x, true);                                // (no accounting while recording: the reward row is the raw reward)
+    x.record = 1; x.rec = r.rec; x.maps = r.maps;
+    const int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, kEvalPollPersistent));
+    int32_t steps = 0, launches = 0; unsigned int seen = 0;
+    while (seen < (unsigned int)M) {
+        if (steps >= Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
+        g.step0 = steps; g.r.T = std::min(K, Tcap - steps);
+        HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream, &x)); steps += g.r.T; launches += 1;
+        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        seen = *h->eval_counter_host;
+    }
+    *steps_out = steps; *launches_out = launches;
+    return DRIL_OK;
+}
+// the step-granular form: traj_step per env step, a look at the finished-counter every K steps
+int traj_stepwise_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int32_t* steps_out, int32_t* launches_out) {
+    const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap;
     const bool wrapped = normalizing(h) || h->pn.on;
     if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
     r.shadow.seed0 = h->env.seed0;
@@ -2492,6 +2532,13 @@ int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, floa
         HIPCHK(h, hipStreamSynchronize(h->stream));
         seen = *h->eval_counter_host;
     }
+    *steps_out = steps; *launches_out = launches;
+    return DRIL_OK;
+}
+int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, bool persistent, float* observations, void* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
+    const int M = r.rec.M, Tcap = r.rec.Tcap; const size_t D = (size_t)r.rec.D, W = (size_t)r.rec.W;
+    int32_t steps = 0, launches = 0;
+    { int rc = persistent ? traj_persistent_run(h, o, r, &steps, &launches) : traj_stepwise_run(h, o, r, &steps, &launches); if (rc) return rc; }
     // copy-out: lengths first, then rows 0..longest only, reordered into the caller's per-trajectory layout on the host
     HIPCHK(h, hipMemcpyAsync(lengths, r.rec.length, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(end_flags, r.rec.end_flags, (size_t)M, hipMemcpyDeviceToHost, h->stream));
@@ -2507,7 +2554,7 @@ int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, floa
     HIPCHK(h, hipMemcpyAsync(rew_tm.data(), r.rec.rew, rew_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     traj_reorder(M, (int64_t)D, (int64_t)W, Tcap, lengths, obs_tm.data(), act_tm.data(), rew_tm.data(), observations, (uint32_t*)actions, rewards);
-    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; }
+    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = persistent ? 1 : 0; }
     return DRIL_OK;
 }
 }  // namespace
@@ -2535,7 +2582,9 @@ DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_tr
     if (bytes > kTrajMaxBytes)
         return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: the recording needs " + std::to_string(bytes) + " bytes on the device (M = " + std::to_string(o->n_trajectories) + ", Tcap = " + std::to_string(Tcap) + "), more than 1 GiB: record fewer envs or set max_steps");
     { int rc = ensure_wimg(h); if (rc) return rc; }
-    EvalKeep keep; eval_keep_list(h, false, keep);
+    // the opt-in one-launch form where evaluate_modes_kernel applies; elsewhere (generic shapes, plug-ins, DRIL_FORCE_STEPWISE) the request falls back silently
+    const bool persistent = o->reserved[DRIL_TRAJ_OPT_PERSISTENT] != 0 && eval_persistent_applies(h, true);
+    EvalKeep keep; eval_keep_list(h, persistent, keep);
     { int rc = eval_buffers(h, keep, 0); if (rc) return rc; }
     TrajRun run{};
     { int rc = traj_prepare(h, o, Tcap, run); if (rc) return rc; }
@@ -2545,7 +2594,7 @@ DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_tr
     { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
     h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false), :12
     h->mon_cur_ret = nullptr;                                                          // the recorded episodes do not enter the training env's MonitorWrapperEnv
-    const int rc = traj_device_run(h, o, run, observations, actions, rewards, lengths, end_flags, info);
+    const int rc = traj_device_run(h, o, run, persistent, observations, actions, rewards, lengths, end_flags, info);
     const std::string msg = h->err;
     h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
     h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;

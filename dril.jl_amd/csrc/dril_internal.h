@@ -6,6 +6,7 @@
 
 #include "dril_device.h"
 #include "dril_eval_account.h"   // EvalAcct, eval_account: the episode accounting of an evaluation on the device
+#include "dril_traj_record.h"    // TrajRec, TrajMaps, traj_record_env: the per-env recording of collect_trajectory (evaluate_modes_kernel's recording mode)
 #include "dril_ext_record.h"     // xr_*: the per-env scalar rules of ext_norm_record_kernel (dril_ext_norm.h), host-compilable
 #include "dril_env_kinds.h"   // the built-in env kinds: every launcher below that takes `kind` dispatches through with_env_kind
 
@@ -61,7 +62,17 @@ struct RolloutArgs {
 // log_std_off), the seeds and limits, and T = the env steps of this launch; noise, the buffer pointers, the critic and the monitor are unused (null).
 // step0: env steps of this evaluation already run by earlier launches
 struct EvalKernelArgs { RolloutArgs r; EvalAcct acct; int32_t step0; int deterministic; };
-hipError_t launch_evaluate(int kind, int hidden, const EvalKernelArgs& a, hipStream_t s);
+// evaluate_modes_kernel: evaluate_kernel's loop with two opt-in modes, both wave-uniform runtime branches of one extra instantiation per (kind, width, forward).
+//   frozen NormalizeWrapperEnv: obs_stats / ret_stats are the halves in force (h->obs_rms + h->obs_par, h->ret_rms + h->ret_par), READ only.  The actor sees
+//     nz_obs of the env's observation where norm_obs; the accounting counts the raw reward where count_raw (the monitor is on), else nz_reward of it where norm_reward
+//   record: envs 0..rec.M-1 record their first episode through traj_record_env (dril_traj_record.h) and the episode accounting is off (rec.finished is its counter)
+struct EvalModeArgs {
+    const RmsState* obs_stats; const RmsState* ret_stats;
+    int norm_obs, norm_reward, count_raw; float clip_obs, clip_reward, eps;
+    int record; TrajRec rec; TrajMaps maps;
+};
+// x == nullptr: evaluate_kernel, exactly as before the modes existed
+hipError_t launch_evaluate(int kind, int hidden, const EvalKernelArgs& a, hipStream_t s, const EvalModeArgs* x = nullptr);
 
 struct MomentsArgs {
     const float* adv; const int64_t* perm; int64_t pos0, count, N, idx_lo, n_local; uint64_t perm_key; int perm_bits;

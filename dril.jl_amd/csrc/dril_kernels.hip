@@ -861,14 +861,34 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
 // eval_net, rollout_sample on the env's stream at cur.gs (or the mode by policy_kernel's definition), env_advance / env_end_episode — so every action, reward and
 // flag is bit-identical to the step-granular launches (tests/test_gpu_eval_device.py).  Steps are numbered g.step0 + 1 .. g.step0 + T: launches continue each other.
 // =============================================================================================
-template <int KIND, int H, bool WIDE, bool SPLIT>
-__global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_kernel(EvalKernelArgs g) {
+// EXT = false is evaluate_kernel; EXT = true (evaluate_modes_kernel) adds the two opt-in modes of EvalModeArgs, each a wave-uniform runtime branch:
+//   a frozen NormalizeWrapperEnv — the statistics in force are wave-uniform: read once per launch into a few LDS words behind the weights (EvalModeLds; in scalar
+//     registers they, the recording's pointers and the env's constants together overflow the scalar file) and never written; what the actor
+//     sees after env_obs and its pin is norm_obs_apply_kernel's expression (nz_obs: subtract, correctly rounded divide and sqrtf, clamp); the simulator state is never
+//     normalised; the reward that enters the accounting is eval_step_granular's (raw under the monitor, else nz_reward where norm_reward);
+//   recording — the lane that holds env m < rec.M writes what traj_record_kernel writes (traj_record_env, dril_traj_record.h): row 0 at step0 == 0, then per step the
+//     action the physics receives, the raw reward and env_obs of the cursor AFTER env_advance and BEFORE env_end_episode — the state no separate launch can see, so
+//     no shadow envs.  The episode accounting is off while recording (rec.finished is its counter).
+// what the modes read in every step, staged once per launch behind the actor's weights: per dimension the mean and sqrtf(var + eps) of the observation statistics,
+// the returns' variance, and the recording's two argument blocks
+struct EvalModeLds { float mean[8], den[8], rvar; int32_t pad[3]; TrajRec rec; TrajMaps maps; };
+template <int KIND, int H, bool WIDE, bool SPLIT> constexpr int eval_mode_lds_off() { return (FwdLds<EnvSpec<KIND>::D, H, EnvSpec<KIND>::A, WIDE, SPLIT>::SIZE + 3) & ~3; }   // floats
+template <int KIND, int H, bool WIDE, bool SPLIT, bool EXT>
+__device__ __forceinline__ void evaluate_body(const EvalKernelArgs& g, const EvalModeArgs& x) {
     constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
+    static_assert(EnvSpec<KIND>::discrete || A == 1, "the recording takes one action word per env");
     const RolloutArgs& a = g.r;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* la = smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     stage_fwd<D, H, A, WIDE, SPLIT>(la, a.params, a.actor, tid, 256);
+    constexpr int MOFF = eval_mode_lds_off<KIND, H, WIDE, SPLIT>();
+    if constexpr (EXT) {
+        EvalModeLds* m = reinterpret_cast<EvalModeLds*>(la + MOFF);
+        if (tid < 8) { m->mean[tid] = x.norm_obs ? x.obs_stats->mean[tid] : 0.f; m->den[tid] = x.norm_obs ? sqrtf(x.obs_stats->var[tid] + x.eps) : 1.f; }   // (RmsState holds 8 dims)
+        if (tid == 8) m->rvar = x.norm_reward ? x.ret_stats->var[0] : 1.f;
+        if (tid == 9) { m->rec = x.rec; m->maps = x.maps; }
+    }
     __syncthreads();
     const int c = lane & 31, h = lane >> 5;
     const int e_raw = (blockIdx.x * 4 + wave) * kTile + c;
@@ -878,20 +898,43 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_kernel(EvalKernelA
     const bool writer = valid && h == 0;
     const uint64_t env_seed = a.env_seed0 + (uint64_t)e;
     const EnvArrays env{a.state, a.step_count, a.episode, a.gstep, nullptr, nullptr};
+    const bool recording = EXT && x.record != 0;                               // wave-uniform
+    const bool rec_lane = recording && writer && e < x.rec.M;
+    int32_t rec_len = 0;                                                       // the trajectory's length word: kTrajOpen while it records
 
     EnvCursor<KIND> cur; cur.load(env, e);
     float obs[D];
     // The observation is made opaque where env_obs hands it over: with the scaled kinds' affine map (x - low) sf - 1 in view, the optimiser sinks the "- 1" below
     // pair_obs' select between the two halves of the wave and the map is then rounded twice (multiply, add) where env_observe_kernel / obs_partials_kernel contract
     // it into one fma — a last-bit difference in the observation (kind 7), which the exact comparison with the step-granular launches does not allow
-    auto observe = [&] {
-        env_obs<KIND>(cur.st, obs);
+    auto observe_env = [&](float (&o)[D]) {
+        env_obs<KIND>(cur.st, o);
 #pragma unroll
-        for (int i = 0; i < D; ++i) asm volatile("" : "+v"(obs[i]));
+        for (int i = 0; i < D; ++i) asm volatile("" : "+v"(o[i]));
     };
-    observe();
+    // normalize_obs! with the frozen statistics: norm_obs_apply_kernel's expression, on the observation alone (cur.st is the simulator's)
+    auto normalise = [&](const float* lds) {
+        if constexpr (EXT) {
+            if (x.norm_obs) {
+                const EvalModeLds* m = reinterpret_cast<const EvalModeLds*>(lds + MOFF);
+#pragma unroll
+                for (int i = 0; i < D; ++i) { float v = (obs[i] - m->mean[i]) / m->den[i]; obs[i] = fminf(fmaxf(v, -x.clip_obs), x.clip_obs); }
+            }
+        }
+    };
+    observe_env(obs);
+    if constexpr (EXT) {
+        if (rec_lane) {
+            const uint32_t none[1] = {0u};
+            const EvalModeLds* m = reinterpret_cast<const EvalModeLds*>(la + MOFF);
+            if (g.step0 == 0) traj_record_env<D, 1>(m->rec, m->maps, 0, e, none, 0.f, false, false, obs, rec_len);   // row 0: the original observation
+            else rec_len = x.rec.length[e];
+        }
+    }
+    normalise(la);
     float lsr[4]; rollout_log_std<KIND>(a, lsr);
-    float ret = g.acct.cur_ret[e]; int32_t len = g.acct.cur_len[e];
+    float ret = 0.f; int32_t len = 0;
+    if (!recording) { ret = g.acct.cur_ret[e]; len = g.acct.cur_len[e]; }
 
     for (int t = 0; t < a.T; ++t) {
         int zoff = 0; asm volatile("" : "+v"(zoff));                          // keep the weights in LDS (see rollout_kernel)
@@ -907,12 +950,27 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_kernel(EvalKernelA
             else actf_env = fminf(fmaxf(out[0], -act_bound<KIND>()), act_bound<KIND>());   // mode(d) = mean (diagGaussian.jl:45-47), then ClampAdapter
         } else rollout_sample<KIND>(a, 0, env_seed, cur.gs, out, lsr, false, &act_env, &actf_env, &logp);
         const StepOut so = env_advance<KIND>(cur, actf_env, act_env, a.episode_len, a.fixed_len != 0);
+        if constexpr (EXT) {
+            if (rec_lane && rec_len == kTrajOpen) {                           // observe(env) of the env that has not auto-reset: the terminal state where the episode ends here
+                float tobs[D]; observe_env(tobs);
+                const uint32_t aw[1] = {EnvSpec<KIND>::discrete ? (uint32_t)(act_env + a.action_start) : __float_as_uint(actf_env)};
+                const EvalModeLds* m = reinterpret_cast<const EvalModeLds*>(la_t + MOFF);
+                traj_record_env<D, 1>(m->rec, m->maps, g.step0 + t + 1, e, aw, so.rew, so.term != 0, so.trunc != 0, tobs, rec_len);
+            }
+        }
         env_end_episode<KIND>(cur, env_seed, so, nullptr, nullptr);
-        if (writer) eval_account(g.acct, g.step0 + t + 1, e, so.rew, so.done(), ret, len);
-        observe();                                                            // observe(env), :97
+        float rew = so.rew;
+        if constexpr (EXT) { if (x.norm_reward && !x.count_raw) rew = nz_reward(so.rew, reinterpret_cast<const EvalModeLds*>(la_t + MOFF)->rvar, x.eps, x.clip_reward); }
+        if (writer && !recording) eval_account(g.acct, g.step0 + t + 1, e, rew, so.done(), ret, len);
+        observe_env(obs);                                                     // observe(env), :97
+        normalise(la_t);
     }
-    if (writer) { cur.store(env, e); g.acct.cur_ret[e] = ret; g.acct.cur_len[e] = len; }
+    if (writer) { cur.store(env, e); if (!recording) { g.acct.cur_ret[e] = ret; g.acct.cur_len[e] = len; } }
 }
+template <int KIND, int H, bool WIDE, bool SPLIT>
+__global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_kernel(EvalKernelArgs g) { evaluate_body<KIND, H, WIDE, SPLIT, false>(g, EvalModeArgs{}); }
+template <int KIND, int H, bool WIDE, bool SPLIT>
+__global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_modes_kernel(EvalKernelArgs g, EvalModeArgs x) { evaluate_body<KIND, H, WIDE, SPLIT, true>(g, x); }
 
 // =============================================================================================
 // gae_scan_kernel — compute_advantages! (trajectory.jl:80-102) + returns = advantages + values (rollout_buffer.jl:87) over the time-major buffer.
@@ -1491,13 +1549,19 @@ hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_
 }
 
 // evaluate_kernel: the fused shapes (two equal tanh layers of 64 / 128 / 256); the forward choice (a.r.exact_f32) and the kind dispatch are the rollout's
-hipError_t launch_evaluate(int kind, int hidden, const EvalKernelArgs& a, hipStream_t s) {
+hipError_t launch_evaluate(int kind, int hidden, const EvalKernelArgs& a, hipStream_t s, const EvalModeArgs* x) {
     const int blocks = (a.r.E + 4 * kTile - 1) / (4 * kTile);
 #define CALLS(K, HH, SP)                                                                                      \
     {                                                                                                         \
         const size_t lds = sizeof(float) * FwdLds<EnvSpec<K>::D, HH, EnvSpec<K>::A, (HH > 64), SP>::SIZE;     \
-        { hipError_t e = set_max_dynamic_lds((const void*)evaluate_kernel<K, HH, (HH > 64), SP>, lds); if (e != hipSuccess) return e; } \
-        evaluate_kernel<K, HH, (HH > 64), SP><<<blocks, 256, lds, s>>>(a);                                    \
+        if (x) {                                                                                              \
+            const size_t ldx = sizeof(float) * eval_mode_lds_off<K, HH, (HH > 64), SP>() + sizeof(EvalModeLds);   \
+            { hipError_t e = set_max_dynamic_lds((const void*)evaluate_modes_kernel<K, HH, (HH > 64), SP>, ldx); if (e != hipSuccess) return e; } \
+            evaluate_modes_kernel<K, HH, (HH > 64), SP><<<blocks, 256, ldx, s>>>(a, *x);                      \
+        } else {                                                                                              \
+            { hipError_t e = set_max_dynamic_lds((const void*)evaluate_kernel<K, HH, (HH > 64), SP>, lds); if (e != hipSuccess) return e; } \
+            evaluate_kernel<K, HH, (HH > 64), SP><<<blocks, 256, lds, s>>>(a);                                \
+        }                                                                                                     \
     }
 #define CALL(K, HH) { if (a.r.exact_f32) CALLS(K, HH, false) else CALLS(K, HH, true) }
     return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {

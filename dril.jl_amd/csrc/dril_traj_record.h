@@ -88,6 +88,40 @@ DRIL_TRAJ_HD void traj_record_lane(const TrajRec& r, const TrajMaps& x, const Tr
         }
     }
 }
+// The same rule with ONE lane holding env m, for a kernel that keeps the env in registers over the steps of a launch (evaluate_modes_kernel, dril_kernels.hip): the lane
+// has the env's values themselves — its W action words as the agent returns them, its raw reward and flags, and obs = the D original observations of the env AFTER
+// the step and BEFORE its auto-reset (t = 0: after the initial observe) — and the trajectory's open / closed state in `length`, a register across the steps of a
+// launch and r.length[m] across launches (the caller loads it where t0 > 0; t = 0 sets both).  Writes, lane for lane, what traj_record_lane writes for the same step
+// stream (tests/test_eval_persistent_modes.py).  D and W are template parameters so that obs / act stay registers.
+template <int D, int W>
+DRIL_TRAJ_HD void traj_record_env(const TrajRec& r, const TrajMaps& x, int32_t t, int32_t m, const uint32_t (&act)[W], float rew, bool term, bool trunc,
+                                  const float (&obs)[D], int32_t& length) {
+    if (t == 0) {
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < D; ++j) r.obs[(int64_t)m * D + j] = x.obs_low ? unscale_from_unit(obs[j], x.obs_low[j], x.obs_high[j]) : obs[j];
+        length = kTrajOpen; r.length[m] = kTrajOpen; r.end_flags[m] = 0;
+        return;
+    }
+    if (t > r.Tcap || length != kTrajOpen) return;
+    const bool done = term || trunc, cut = !done && t >= r.Tcap, last = done || cut;
+    const int64_t row = (int64_t)t * r.M + m, prev = row - r.M;
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < D; ++j) r.obs[row * D + j] = (x.obs_low && (!last || x.final_original)) ? unscale_from_unit(obs[j], x.obs_low[j], x.obs_high[j]) : obs[j];
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < W; ++j) r.act[prev * W + j] = traj_env_action(x, j, act[j]);
+    r.rew[prev] = rew;
+    if (last) {
+        length = t; r.length[m] = t;
+        r.end_flags[m] = (uint8_t)((term ? kTrajTerminated : 0) | (trunc ? kTrajTruncated : 0) | (cut ? kTrajCut : 0));
+        traj_count_finished(r.finished);
+    }
+}
 // the caller's layout from rows 0..longest of the step-major recording (host side): observations (D, Tcap + 1, M), actions (W, Tcap, M), rewards (Tcap, M), all
 // column-major; rows past a trajectory's own length are zero
 inline void traj_reorder(int64_t M, int64_t D, int64_t W, int64_t Tcap, const int32_t* length, const float* obs_tm, const uint32_t* act_tm, const float* rew_tm,

@@ -20,6 +20,7 @@ fallback (loading fails loudly when the library is missing).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 import sys
@@ -464,6 +465,19 @@ def _stream_ptr(stream):
     return C.c_void_p(int(stream)) if stream else None
 
 
+def _opt_in_persistent(impl):
+    """The positional signatures of evaluate_agent_device / collect_trajectory_device / collect_trajectory are a fixed interface (callers and tests rely on them
+    as inspect.signature reports them).  The opt-in `persistent` is therefore a keyword-only option added in front of the verb: the decorated function states the
+    fixed interface (and is what inspect.signature reports), `impl` — the same parameters plus `persistent` — does the work."""
+    def decorate(public):
+        @functools.wraps(public)
+        def verb(*args, persistent: bool = False, **kwargs):
+            return impl(*args, persistent=persistent, **kwargs)
+        verb.__doc__ = (impl.__doc__ or "") + "\n\n" + (public.__doc__ or "")
+        return verb
+    return decorate
+
+
 @_normalize.normalize_verbs(lambda self, verb: getattr(self.lib, ("dril_normalize_" if verb == "config_default" else "dril_ext_normalize_") + verb), "normalize_", "ext_")
 @_normalize.normalize_verbs(lambda self, verb: getattr(self.lib, "dril_normalize_" + verb), "normalize_")
 class Handle:
@@ -843,14 +857,17 @@ class Handle:
         return dict(mean_reward=st.mean_reward, std_reward=st.std_reward, mean_length=st.mean_length, std_length=st.std_length,
                     n_steps=st.n_steps), er, el
 
-    def evaluate_agent_device(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None, poll_steps: int = 0,
-                              force_step_granular: bool = False):
+    def _evaluate_agent_device(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None, poll_steps: int = 0,
+                               force_step_granular: bool = False, persistent: bool = False):
         """The same evaluation with the episode accounting on the device, leaving nothing behind on the handle (dril_evaluate_agent_device, docs/evaluation.md)
         -> (stats dict, episode_rewards, episode_lengths, info dict).  seed None: the env seed in force; env e is reset with seed + its global index.
-        info: path (0 step-granular launches, 1 the persistent evaluate kernel), launches, steps_enqueued, events."""
+        persistent=True asks for the persistent evaluate kernel wherever it can run, cfg.norm_* handles included (the frozen statistics are an argument of the
+        kernel); the default keeps such handles on the step-granular launches.  force_step_granular wins.
+        info: path (what ran: 0 step-granular launches, 1 the persistent evaluate kernel), launches, steps_enqueued, events."""
         o = capi.DrilEvalOptions()
         self._chk(self.lib.dril_eval_options_default(C.byref(o)))
         o.n_eval_episodes, o.deterministic, o.poll_steps, o.force_step_granular = int(n_eval_episodes), int(deterministic), int(poll_steps), int(force_step_granular)
+        o.reserved[capi.EVAL_OPT_PERSISTENT] = int(bool(persistent))
         if seed is not None:
             o.seed, o.has_seed = int(seed), 1
         st, info = capi.DrilEvalStats(), capi.DrilEvalInfo()
@@ -860,17 +877,25 @@ class Handle:
         return (dict(mean_reward=st.mean_reward, std_reward=st.std_reward, mean_length=st.mean_length, std_length=st.std_length, n_steps=st.n_steps), er, el,
                 dict(path=info.path, launches=info.launches, steps_enqueued=info.steps_enqueued, events=info.events))
 
-    def collect_trajectory_device(self, n_trajectories: int = 1, max_steps: Optional[int] = None, deterministic: bool = True, seed: Optional[int] = None,
-                                  poll_steps: int = 0, final_original: bool = False):
+    @_opt_in_persistent(_evaluate_agent_device)
+    def evaluate_agent_device(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None, poll_steps: int = 0,
+                              force_step_granular: bool = False):
+        """Handle._evaluate_agent_device with the keyword-only option `persistent` (default False): evaluate_agent_device(..., persistent=True)."""
+
+    def _collect_trajectory_device(self, n_trajectories: int = 1, max_steps: Optional[int] = None, deterministic: bool = True, seed: Optional[int] = None,
+                                   poll_steps: int = 0, final_original: bool = False, persistent: bool = False):
         """collect_trajectory on the device, leaving nothing behind on the handle (dril_collect_trajectory_device, docs/evaluation.md): envs 0..n_trajectories-1 record
         their first episode after the call's own reset -> (trajectories, lengths, end_flags, info dict).  trajectories[m] = (observations (L+1, D), actions (L,) | (L, A),
         rewards (L,)): original observations (rows 0..L-1 unscaled under ScalingWrapperEnv, never normalised), the actions the env's physics received, raw rewards;
         the last observation is the terminal state as the wrapper delivers it (final_original: unscaled too).  end_flags: capi.TRAJ_TERMINATED | TRAJ_TRUNCATED |
-        TRAJ_MAX_STEPS.  info: capacity, steps_enqueued, launches, longest, cut_by_max_steps."""
+        TRAJ_MAX_STEPS.  persistent=True asks for the one-launch form (the recording inside the persistent evaluate kernel, K steps per launch, no shadow envs)
+        where that kernel can run; elsewhere the request falls back silently.  The recording is the same, bit for bit.
+        info: capacity, steps_enqueued, launches, longest, cut_by_max_steps, path (what ran: 0 step-granular launches, 1 the persistent kernel)."""
         o = capi.DrilTrajOptions()
         self._chk(self.lib.dril_traj_options_default(C.byref(o)))
         o.n_trajectories, o.max_steps, o.deterministic = int(n_trajectories), 0 if max_steps is None else int(max_steps), int(deterministic)
         o.poll_steps, o.final_original = int(poll_steps), int(bool(final_original))
+        o.reserved[capi.TRAJ_OPT_PERSISTENT] = int(bool(persistent))
         if max_steps is not None and int(max_steps) < 1:
             raise ValueError("max_steps is None or >= 1")
         if seed is not None:
@@ -884,7 +909,12 @@ class Handle:
         self._chk(self.lib.dril_collect_trajectory_device(self._h, C.byref(o), self._p(obs), self._p(act), self._p(rew), self._p(lengths), self._p(flags), C.byref(info)))
         trajs = [(obs[m, :L + 1].copy(), act[m, :L].copy(), rew[m, :L].copy()) for m, L in enumerate(lengths)]
         return trajs, lengths, flags, dict(capacity=info.capacity, steps_enqueued=info.steps_enqueued, launches=info.launches, longest=info.longest,
-                                           cut_by_max_steps=info.cut_by_max_steps)
+                                           cut_by_max_steps=info.cut_by_max_steps, path=info.reserved[capi.TRAJ_INFO_PATH])
+
+    @_opt_in_persistent(_collect_trajectory_device)
+    def collect_trajectory_device(self, n_trajectories: int = 1, max_steps: Optional[int] = None, deterministic: bool = True, seed: Optional[int] = None,
+                                  poll_steps: int = 0, final_original: bool = False):
+        """Handle._collect_trajectory_device with the keyword-only option `persistent` (default False): collect_trajectory_device(..., persistent=True)."""
 
     def train(self, max_steps: int):
         per_iter = self.N * self.cfg.world_size
@@ -1690,10 +1720,11 @@ def _timer_sections(h: Handle, prof0, t_upd: float) -> dict:
 
 
 def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 10, deterministic: bool = True,
-                   reward_threshold: Optional[float] = None, return_stats: bool = True, isolated: bool = False):
+                   reward_threshold: Optional[float] = None, return_stats: bool = True, isolated: bool = False, persistent: bool = False):
     """evaluate_agent(agent, env; ...) (src/evaluation.jl:54-143).  isolated=True (device envs): the evaluation runs on the device and leaves the env as it was —
     state, counters, the monitor's window, a normaliser's statistics (frozen for the call) — so it may sit between two training iterations
-    (Handle.evaluate_agent_device, docs/evaluation.md); the default resets the env and lets its episodes enter the monitor's window, as before."""
+    (Handle.evaluate_agent_device, docs/evaluation.md); the default resets the env and lets its episodes enter the monitor's window, as before.
+    persistent=True (with isolated=True) asks for the persistent evaluate kernel wherever it can run, normalised envs included; the numbers are the same."""
     h = env.bind(agent.alg, agent.layer)
     h.set_params(flatten_params(agent.train_state.parameters))
     if isolated and isinstance(env, (HostParallelEnv, DeviceArrayParallelEnv)):
@@ -1737,7 +1768,7 @@ def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 
         sd = lambda x: float(np.std(x, ddof=1)) if len(x) > 1 else float("nan")
         stats = {"mean_reward": float(er.mean()), "std_reward": sd(er), "mean_length": float(el.mean()), "std_length": sd(el)}
     elif isolated:
-        stats, er, el, _ = h.evaluate_agent_device(n_eval_episodes, deterministic)
+        stats, er, el, _ = h.evaluate_agent_device(n_eval_episodes, deterministic, persistent=persistent)
     else:
         stats, er, el = h.evaluate_agent(n_eval_episodes, deterministic)
     if reward_threshold is not None and stats["mean_reward"] < reward_threshold:
@@ -1745,22 +1776,28 @@ def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 
     return {k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} if return_stats else (er, el)
 
 
-def collect_trajectory(agent: Agent, env: DeviceParallelEnv, max_steps: Optional[int] = None, norm_env=None, deterministic: bool = True,
-                       n_trajectories: int = 1, seed: Optional[int] = None):
+def _collect_trajectory(agent: Agent, env: DeviceParallelEnv, max_steps: Optional[int] = None, norm_env=None, deterministic: bool = True,
+                        n_trajectories: int = 1, seed: Optional[int] = None, persistent: bool = False):
     """collect_trajectory(agent, env; max_steps, norm_env, deterministic) (src/utils/trajectory_utils.jl:3-49) -> (observations, actions, rewards): the original
     observations (L + 1 of them, the last one the terminal state), the env actions and the raw rewards of one episode; n_trajectories > 1: a list of such triples,
     envs 0..n-1 of the parallel env, each its first episode after the reset.  Runs on the device and leaves the env as it was (Handle.collect_trajectory_device,
-    docs/evaluation.md).  norm_env: None, or `env` itself — a NormalizeWrapperEnv around the device env is a mode of its handle, found there and applied frozen."""
+    docs/evaluation.md); persistent=True asks for its one-launch form where the persistent evaluate kernel can run.  norm_env: None, or `env` itself — a NormalizeWrapperEnv around the device env is a mode of its handle, found there and applied frozen."""
     if isinstance(env, (HostParallelEnv, DeviceArrayParallelEnv)):
         raise NotImplementedError("collect_trajectory: host envs (HostParallelEnv, DeviceArrayParallelEnv) live with the caller; the device verb steps device envs")
     if norm_env is not None and norm_env is not env:
         raise NotImplementedError("collect_trajectory: norm_env is None or the env itself (NormalizeWrapperEnv around a device env is a mode of the env's handle and is applied frozen)")
     h = env.bind(agent.alg, agent.layer)
     h.set_params(flatten_params(agent.train_state.parameters))
-    trajs, _, flags, _ = h.collect_trajectory_device(n_trajectories, max_steps, deterministic, seed)
+    trajs, _, flags, _ = h.collect_trajectory_device(n_trajectories, max_steps, deterministic, seed, persistent=persistent)
     if (flags & capi.TRAJ_MAX_STEPS).any():
         warnings.warn("Max steps reached")                                           # trajectory_utils.jl:39
     return trajs[0] if n_trajectories == 1 else trajs
+
+
+@_opt_in_persistent(_collect_trajectory)
+def collect_trajectory(agent: Agent, env: DeviceParallelEnv, max_steps: Optional[int] = None, norm_env=None, deterministic: bool = True,
+                       n_trajectories: int = 1, seed: Optional[int] = None):
+    """_collect_trajectory with the keyword-only option `persistent` (default False): collect_trajectory(agent, env, ..., persistent=True)."""
 
 
 def get_action_and_values(agent: Agent, env: DeviceParallelEnv, observations):

@@ -41,12 +41,13 @@ struct DrilEvalInfo
 end
 # isolated = true: the episode accounting runs on the device and the env is left as it was — state, counters, the monitor's window, a normaliser's statistics (frozen
 # for the call) — so the call may sit between two training iterations on the training env.  The default keeps the reset env and the monitor's window as before.
+# persistent = true (with isolated): reserved[DRIL_EVAL_OPT_PERSISTENT = 0] — the persistent evaluate kernel wherever it can run, normalised envs included; same numbers.
 function DRiL.evaluate_agent(agent, env::DeviceParallelEnv; n_eval_episodes::Int = 10, deterministic::Bool = true,
-        reward_threshold::Union{Nothing, Real} = nothing, return_stats::Bool = true, warn::Bool = true, isolated::Bool = false, kwargs...)
+        reward_threshold::Union{Nothing, Real} = nothing, return_stats::Bool = true, warn::Bool = true, isolated::Bool = false, persistent::Bool = false, kwargs...)
     bind_agent!(env, agent, agent.algorithm); push_params!(env, agent)
     st = Ref{DrilEvalStats}(); er = Vector{Float32}(undef, n_eval_episodes); el = Vector{Int32}(undef, n_eval_episodes)
     if isolated
-        o = Ref(DrilEvalOptions(Int32(n_eval_episodes), Int32(deterministic), UInt64(0), Int32(0), Int32(0), Int32(0), (Int32(0), Int32(0), Int32(0))))
+        o = Ref(DrilEvalOptions(Int32(n_eval_episodes), Int32(deterministic), UInt64(0), Int32(0), Int32(0), Int32(0), (Int32(persistent), Int32(0), Int32(0))))
         GC.@preserve er el check(ccall((:dril_evaluate_agent_device, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilEvalOptions}, Ref{DrilEvalStats}, Ptr{Float32}, Ptr{Int32}, Ptr{DrilEvalInfo}),
             env.handle, o, st, er, el, C_NULL), env.handle)
     else
@@ -75,11 +76,12 @@ struct DrilTrajInfo
 end
 # -> (observations, actions, rewards) as the reference returns them (L + 1 original observations, L env actions, L raw rewards); n_trajectories > 1: a vector of such
 # tuples, envs 1..n of the parallel env, each its first episode after the reset.  A NormalizeWrapperEnv around the device env is a mode of its handle: applied frozen.
-function DRiL.collect_trajectory(agent, env::DeviceParallelEnv; max_steps::Union{Int, Nothing} = nothing, deterministic::Bool = true, n_trajectories::Int = 1, kwargs...)
+# persistent = true: reserved[DRIL_TRAJ_OPT_PERSISTENT = 0] — the recording inside the persistent evaluate kernel where it can run (silent fall-back elsewhere); same recording.
+function DRiL.collect_trajectory(agent, env::DeviceParallelEnv; max_steps::Union{Int, Nothing} = nothing, deterministic::Bool = true, n_trajectories::Int = 1, persistent::Bool = false, kwargs...)
     bind_agent!(env, agent, agent.algorithm); push_params!(env, agent)
     h = env.handle
     o = Ref(DrilTrajOptions(Int32(n_trajectories), Int32(max_steps === nothing ? 0 : max_steps), Int32(deterministic), Int32(0), UInt64(0), Int32(0), Int32(0),
-        (Int32(0), Int32(0), Int32(0), Int32(0), Int32(0))))
+        (Int32(persistent), Int32(0), Int32(0), Int32(0), Int32(0))))
     cap = Ref{Int32}(0)
     check(ccall((:dril_trajectory_capacity, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilTrajOptions}, Ref{Int32}), h, o, cap), h)
     D = obs_dim(env); T = Int(cap[]); M = n_trajectories; disc = is_discrete(env)

@@ -541,7 +541,8 @@ int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval_episodes, int32_t det
  * once per K env steps, sorts the copied slots by (step, env) and takes n_eval_episodes — the numbers dril_evaluate_agent returns, whatever K is and whichever
  * path ran.  Two paths: a persistent evaluate kernel (a wave keeps 32 envs in registers for K steps, the actor's weights in LDS) for the built-in kinds on the
  * fused shapes without a normaliser, and step-granular launches with a small accounting launch for every other device-env handle (generic shapes, cfg.norm_*,
- * plug-ins with or without dril_scaling_enable / dril_normalize_enable / the fused rollout).
+ * plug-ins with or without dril_scaling_enable / dril_normalize_enable / the fused rollout).  On request (reserved[DRIL_EVAL_OPT_PERSISTENT] = 1) a cfg.norm_*
+ * handle on a fused shape takes the persistent kernel too: it reads the frozen statistics as an argument and returns the same numbers.
  * A normaliser is FROZEN for the call whatever its training flag (set_training(env, false), evaluation of a training env; docs/deviations.md).
  * The call brings its own reset and puts back what it writes, on error paths too: env state, step counts, episode and noise-stream counters, the seed in force,
  * `returns`, the E-sized per-step arrays, the statistics' buffers and parities, and whether the envs count as reset.  The monitor's sums / window / meta are not
@@ -553,11 +554,15 @@ typedef struct dril_eval_options {
     int32_t n_eval_episodes, deterministic;
     uint64_t seed; int32_t has_seed;     /* 0: the handle's current env seed; env e is reset with seed + global env index */
     int32_t poll_steps;                  /* 0: the library's default K; >= 1: look at the counter every poll_steps env steps */
-    int32_t force_step_granular;         /* 1: never take the persistent kernel (tests, A/B) */
-    int32_t reserved[3];
+    int32_t force_step_granular;         /* 1: never take the persistent kernel (tests, A/B); wins over the request below, as DRIL_FORCE_STEPWISE=1 at create does */
+    int32_t reserved[3];                 /* reserved[DRIL_EVAL_OPT_PERSISTENT]: the opt-in request for the persistent kernel.  0 (default): today's rule — the kernel
+                                          * where no normaliser is on.  1: the kernel wherever it can run, cfg.norm_obs / cfg.norm_reward handles included: the FROZEN
+                                          * statistics in force are passed to it as an argument and only read.  Same numbers on either path.  Generic shapes, plug-ins and
+                                          * DRIL_ENV_EXTERNAL keep their answers (path 0, or the refusal), never an error because of the request.  The other words: 0 */
 } dril_eval_options;
+#define DRIL_EVAL_OPT_PERSISTENT 0       /* index into dril_eval_options.reserved */
 typedef struct dril_eval_info {
-    int32_t path;                        /* 0 step-granular launches + device accounting, 1 persistent evaluate kernel */
+    int32_t path;                        /* what ran: 0 step-granular launches + device accounting, 1 persistent evaluate kernel */
     int32_t launches, steps_enqueued, events, reserved[4];   /* launch calls of the loop, env steps enqueued, events the device counted */
 } dril_eval_info;
 int32_t dril_eval_options_default(dril_eval_options* o);   /* 10 episodes, deterministic, evaluation.jl:57-58 */
@@ -574,6 +579,8 @@ int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_options* o, d
  * draws are those of dril_evaluate_agent_device on the same seed.  The trajectory of env m does not depend on M, on poll_steps or on the other envs.
  * The call leaves nothing behind: everything dril_evaluate_agent_device sets aside and puts back is set aside and put back here, on error paths too; the monitor's
  * launches are not made and no all-reduce is enqueued (each rank of a data-parallel job records its own envs).
+ * Two forms, the same recording bit for bit: step-granular launches with shadow envs (default), and on request (reserved[DRIL_TRAJ_OPT_PERSISTENT] = 1) the
+ * recording inside the persistent evaluate kernel, one launch per K env steps, for the built-in kinds on the fused shapes of width 64 / 128 / 256.
  * DRIL_ERR_NOT_INITIALISED: null handle.  DRIL_ERR_INVALID_ARG: null options or output array, n_trajectories outside 1..n_envs, negative max_steps or poll_steps, a
  * recording whose device arrays exceed 1 GiB.  DRIL_ERR_UNSUPPORTED: DRIL_ENV_EXTERNAL (the envs live with the caller). */
 typedef struct dril_traj_options {
@@ -583,11 +590,17 @@ typedef struct dril_traj_options {
     int32_t has_seed; uint64_t seed;     /* as dril_eval_options: 0 = the env seed in force; else env e resets with seed + global env index */
     int32_t poll_steps;                  /* env steps between two looks at the finished-counter; 0 = the library's default */
     int32_t final_original;              /* 0 (reference): the last observation as ScalingWrapperEnv delivers it (:44); 1: unscaled like rows 0..L-1 */
-    int32_t reserved[5];
+    int32_t reserved[5];                 /* reserved[DRIL_TRAJ_OPT_PERSISTENT]: the opt-in request for the one-launch form.  0 (default): the step-granular launches with
+                                          * shadow envs.  1: where the persistent evaluate kernel can run (built-in kinds on the fused shapes of width 64 / 128 / 256, with
+                                          * or without cfg.norm_*), envs 0..M-1 are recorded inside it, K env steps per launch, no shadow envs — the same recording, bit
+                                          * for bit.  Elsewhere (generic shapes, plug-ins, DRIL_FORCE_STEPWISE) the request falls back silently.  The other words: 0 */
 } dril_traj_options;
+#define DRIL_TRAJ_OPT_PERSISTENT 0       /* index into dril_traj_options.reserved */
 typedef struct dril_traj_info {
-    int32_t capacity, steps_enqueued, launches, longest, cut_by_max_steps, reserved[3];   /* Tcap, env steps enqueued, launch calls of the loop, max L, trajectories with bit 2 */
+    int32_t capacity, steps_enqueued, launches, longest, cut_by_max_steps, reserved[3];   /* Tcap, env steps enqueued, launch calls of the loop, max L, trajectories with bit 2;
+                                          * reserved[DRIL_TRAJ_INFO_PATH]: what ran — 0 the step-granular launches, 1 the persistent kernel's recording mode */
 } dril_traj_info;
+#define DRIL_TRAJ_INFO_PATH 0            /* index into dril_traj_info.reserved */
 int32_t dril_traj_options_default(dril_traj_options* o);   /* M = 1, deterministic, the rest 0 */
 /* Tcap = max_steps > 0 ? min(max_steps, episode_len) : episode_len: the rows the output arrays are sized with */
 int32_t dril_trajectory_capacity(const dril_handle* h, const dril_traj_options* o, int32_t* capacity);

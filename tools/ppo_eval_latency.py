@@ -3,12 +3,14 @@
 on its two paths and at several poll intervals K, next to a collection step of the same handle.
   CartPole  (time limit 500, real episodes: poles fall)   built-in kind, hidden [64,64]: both paths
   Pendulum  (time limit 200)                              built-in kind, hidden [64,64]: both paths
+  Pendulum under cfg.norm_obs / cfg.norm_reward           the same, wrapped: step-granular by default (six launches per env step), the persistent kernel on request
+                                                          (persistent = True: the frozen statistics are an argument of the kernel)
   reacher3 plug-in (time limit 100)                       step-granular path only
 E = 64 / 1 024 / 16 384, one process, n_eval = E (for Pendulum / reacher3 exactly one time limit of env steps).  The wall time of the whole call — reset, every
 enqueued step (those past the last counted episode included), the polls, the event copy, the restore of the training envs — is divided by the counted steps
 (stats.n_steps).  The calls are synchronous, so the wall time contains the device time.  Median (min .. max) over the calls after warm-up.
 The collection figure: wall time of dril_collect_rollout (n_steps = 32, drained) / 32.
-usage: python tools/ppo_eval_latency.py [evaluations=20] [env ...]      env: cartpole pendulum reacher3"""
+usage: python tools/ppo_eval_latency.py [evaluations=20] [env ...]      env: cartpole pendulum pendulum_norm reacher3"""
 import sys, time
 from pathlib import Path
 import numpy as np
@@ -19,10 +21,10 @@ import __graft_entry__ as g
 pkg = g.load_package()
 capi = pkg._capi
 R = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-ENVS = sys.argv[2:] or ["cartpole", "pendulum", "reacher3"]
+ENVS = sys.argv[2:] or ["cartpole", "pendulum", "pendulum_norm", "reacher3"]
 WARM, T = 3, 32
 REACHER = ROOT / "examples" / "envs" / "reacher3_plugin.hsaco"
-KIND = {"cartpole": (capi.ENV_CARTPOLE, None), "pendulum": (capi.ENV_PENDULUM, None), "reacher3": (capi.ENV_MODULE, REACHER)}
+KIND = {"cartpole": (capi.ENV_CARTPOLE, None), "pendulum": (capi.ENV_PENDULUM, None), "pendulum_norm": (capi.ENV_PENDULUM, None), "reacher3": (capi.ENV_MODULE, REACHER)}
 K_PERSISTENT = (8, 32, 64, 128, 0)          # candidates of the persistent path (0 = the library's default)
 
 
@@ -30,9 +32,13 @@ def handle_for(name, E):
     kind, module = KIND[name]
     cfg = capi.default_config(kind)
     cfg.n_envs, cfg.n_steps, cfg.batch_size, cfg.epochs = E, T, min(E * T, 4096), 1
+    if name == "pendulum_norm":
+        cfg.norm_obs = cfg.norm_reward = cfg.norm_training = 1
     h = pkg.Handle(cfg, env_module=module)
     h.set_params((np.random.default_rng(0).standard_normal(h.P) * 0.3).astype(np.float32))
     h.env_reset(1)
+    if name == "pendulum_norm":
+        h.collect_rollout()                      # statistics that are not the initial ones
     return h
 
 
@@ -58,7 +64,7 @@ def measure(name, E):
         assert info["path"] == 0
     if KIND[name][1] is None:
         for K in K_PERSISTENT:
-            s, steps, info = timed(lambda: h.evaluate_agent_device(E, True, poll_steps=K))
+            s, steps, info = timed(lambda: h.evaluate_agent_device(E, True, poll_steps=K, persistent=name == "pendulum_norm"))
             print(f"   device, persistent     K = {'default' if not K else K:>7}          {s} us / env step over {steps} steps, {info['steps_enqueued']} enqueued, {info['launches']} launches", flush=True)
             assert info["path"] == 1
     h.env_reset(1)
