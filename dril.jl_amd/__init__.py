@@ -20,7 +20,7 @@ from .host import (  # noqa: F401
 )
 from .sac import (  # noqa: F401
     SAC, AutoEntropyCoefficient, FixedEntropyCoefficient, ReplayBuffer, SACAgent, SACLayer, SacHandle, get_gradient_steps, make_sac_config,
-    sac_evaluate_agent, sac_flatten_params, sac_train_, sac_unflatten_params,
+    sac_collect_trajectory, sac_evaluate_agent, sac_flatten_params, sac_train_, sac_unflatten_params,
 )
 from .checkpoint import load_normalization_stats_, load_policy, load_policy_params_and_state_, save_normalization_stats, save_policy, save_policy_params_and_state  # noqa: F401
 from .deployment import ConstantPolicy, NeuralPolicy, NormWrapperPolicy, RandomPolicy, extract_policy  # noqa: F401

@@ -365,6 +365,8 @@ _SAC_SIG = {
     "monitor_enable": (C.c_int32, [_P, C.c_int32]),
     "monitor_get_stats": (C.c_int32, [_P, _PF, _PF, C.POINTER(C.c_int32)]),
     "evaluate_agent": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(DrilEvalStats), _P, _P]),
+    "trajectory_capacity": (C.c_int32, [_P, C.POINTER(DrilTrajOptions), C.POINTER(C.c_int32)]),
+    "collect_trajectory": (C.c_int32, [_P, C.POINTER(DrilTrajOptions), _P, _P, _P, _P, _P, C.POINTER(DrilTrajInfo)]),
     "normalize_config_default": (C.c_int32, [C.POINTER(DrilSacNormalizeConfig)]),
     "normalize_enable": (C.c_int32, [_P, C.POINTER(DrilSacNormalizeConfig)]),
     "normalize_get_config": (C.c_int32, [_P, C.POINTER(DrilSacNormalizeConfig)]),

@@ -32,6 +32,7 @@
 #include "dril_sac_adapter.h"
 #include "dril_policy_internal.h"   // dril_policy_from_sac_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_sac_eval.h"
+#include "dril_traj_record.h"  // collect_trajectory on the device: the per-env recording sac_traj_env_kernel / sac_traj_record_kernel run (host-compilable)
 #include "dril_env_side.h"     // DeviceEnvs: the envs this handle steps on the device (a built-in Box kind or a device env plug-in), shared with the PPO handle
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_ext_stream.h"   // the pointer rule and the stream hand-over of the device-array verbs, shared with the PPO handle
@@ -1150,6 +1151,40 @@ __global__ __launch_bounds__(256) void sac_eval_env_kernel(EvalEnvArgs c) {
     }
     sac_eval_account(c.acct, e, so.rew, so.done());
 }
+// ---- collect_trajectory on the device (trajectory_utils.jl:3-49; dril_traj_record.h) -----------------------------------------------------------------
+// built-in Box envs: the twin of sac_eval_env_kernel with the recording of envs 0..M-1 where that kernel has the accounting.  After the step the env's thread holds
+// a whole row in registers: `to` is env_obs of the cursor after env_advance and before env_end_episode — the terminal state where the episode ended, and where it did
+// not, env_end_episode returns at once and `no` is the same expression over the same state, the same floats — so `to` is the row's observation throughout; the env
+// action is the word sac_env_thread_step stored for this env; reward and flags are the step's own.  One step per launch: the open / closed state of trajectory e is
+// rec.length[e], loaded before the step.  Threads of envs >= M and of closed trajectories step like an evaluation and write nothing to the recording.
+struct TrajEnvArgs { CollectEnvArgs env; NzEvalArgs nz; TrajRec rec; TrajMaps maps; int32_t t; };
+template <int KIND>
+__global__ __launch_bounds__(256) void sac_traj_env_kernel(TrajEnvArgs c) {
+    constexpr int D = EnvSpec<KIND>::D;
+    __shared__ float mu_s[kEnvsPerBlock];
+    int e; float mu_e;
+    if (!sac_env_thread_mu(c.env.head, mu_s, &e, &mu_e)) return;
+    const bool recorded = e < c.rec.M;
+    int32_t length = recorded ? c.rec.length[e] : 0;
+    float r, to[D], no[D];
+    const StepOut so = sac_env_thread_step<KIND>(c.env, e, mu_e, &r, to, no);
+    if (c.nz.st && c.nz.norm_obs) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) c.env.nobs[(size_t)e * D + i] = nz_obs(no[i], c.nz.st[i], c.nz.st[D + i], c.nz.eps, c.nz.clip);
+    }
+    if (recorded) {
+        const uint32_t act[1] = {traj_f2u(c.env.head.envact[e])};                       // (written by this thread in sac_env_thread_step)
+        traj_record_env<D, 1>(c.rec, c.maps, c.t, e, act, so.rew, so.term, so.trunc, to, length);
+    }
+}
+// a thread per (env, word) over M x max(D, W) lanes: row 0 of either path (t = 0, after the initial observe) and, on plug-ins, every step's row from the per-step
+// arrays and the shadow envs' observation.  The rule itself is traj_record_lane
+__global__ __launch_bounds__(256) void sac_traj_record_kernel(TrajRec r, TrajMaps x, TrajStep s, int32_t t) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t lanes = r.D > r.W ? r.D : r.W;
+    if (i >= (int64_t)r.M * lanes) return;
+    traj_record_lane(r, x, s, t, (int32_t)(i / lanes), (int32_t)(i % lanes));
+}
 // plug-ins: after the plug-in's step kernel, over its per-step arrays.  One thread per env, flat index.
 __global__ __launch_bounds__(256) void sac_eval_account_kernel(EvalAcctArgs a, const float* __restrict__ rew, const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1335,6 +1370,8 @@ struct dril_sac_handle {
     // evaluate_agent (dril_sac_evaluate_agent): the env-side snapshot, the per-env running sums, the event list and its counter (pinned host word for the poll)
     int eval_poll = 0; float *ev_state = nullptr, *ev_obs = nullptr, *ev_mon_ret = nullptr, *ev_cur_ret = nullptr; int32_t *ev_sc = nullptr, *ev_mon_len = nullptr, *ev_cur_len = nullptr; uint32_t *ev_ep = nullptr, *ev_gs = nullptr;
     unsigned int *ev_counter = nullptr, *ev_counter_host = nullptr; SacEvalEvent* ev_events = nullptr; long long ev_events_cap = 0;
+    // dril_sac_collect_trajectory: ONE grow-only blob for the step-major recording, the shadow envs' arrays (plug-ins) and the table of bounds (the counter and its pinned word are the evaluation's)
+    char* traj_blob = nullptr; size_t traj_blob_bytes = 0;
     // NormalizeWrapperEnv (dril_sac_normalize_enable; nz.on false: every pointer null; kernels: dril_norm_wrap.h, dril_sac_norm.h).  nz_old_obs (E x D) is the raw
     // observation of the envs' present state once nz_raw_valid
     NormWrap nz; bool nz_raw_valid = false;
@@ -1930,6 +1967,7 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
     for (void* p : mon_eval) if (p) hipFree(p);
     normalize_free(h);
     if (h->ev_counter_host) hipHostFree(h->ev_counter_host);
+    if (h->traj_blob) hipFree(h->traj_blob);
     for (void* p : h->pend_free) hipFree(p);
     if (h->pend_stats) hipFree(h->pend_stats); if (h->pend_ssq) hipFree(h->pend_ssq); if (h->ext_err) hipFree(h->ext_err);
     if (h->ext_err_host) hipHostFree(h->ext_err_host);
@@ -3014,4 +3052,172 @@ DRIL_EXPORT int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval, 
     out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
     out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
     return DRIL_OK;
+}
+
+// ---- collect_trajectory (src/utils/trajectory_utils.jl:3-49) with the handle's actor on the handle's envs; docs/sac.md, "Trajectories" ---------------------------
+// The evaluation's launches with the episode accounting replaced by a recording of envs 0..M-1.  Built-in Box kinds: one env launch per step (sac_traj_env_kernel),
+// the env's own thread records from its registers.  Plug-ins: their code objects write terminal_obs where truncated only, so M SHADOW envs — a DeviceEnvs view of
+// the same plug-in with its own arrays, fixed_len = 1 and an unreachable time limit, which never resets — take every step a second time from the live envs' pre-step
+// state with the same env actions, and their observe is the post-step, pre-reset observation sac_traj_record_kernel records (the construction of
+// dril_collect_trajectory_device).
+namespace {
+constexpr int64_t kTrajMaxBytes = 1ll << 30;
+struct SacTrajRun {
+    TrajRec rec; TrajMaps maps; DeviceEnvs shadow;
+    float *sh_rew, *sh_tobs, *sh_obs; uint8_t *sh_term, *sh_trunc;
+};
+// carves the handle's blob (grown when the call needs more) and fills the table of bounds
+int traj_prepare(dril_sac_handle* h, const dril_traj_options* o, int32_t Tcap, SacTrajRun& r) {
+    const size_t M = (size_t)o->n_trajectories, D = (size_t)h->D, W = (size_t)h->A, S = (size_t)h->S, T = (size_t)Tcap;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_obs = take((T + 1) * M * D * 4), o_act = take(T * M * W * 4), o_rew = take(T * M * 4), o_len = take(M * 4), o_flg = take(M);
+    const size_t o_st = take(M * S * 4), o_sc = take(M * 4), o_ep = take(M * 4), o_gs = take(M * 4);
+    const size_t o_srew = take(M * 4), o_sterm = take(M), o_strunc = take(M), o_stobs = take(M * D * 4), o_sobs = take(M * D * 4), o_tab = take((2 * D + 2 * W) * 4);
+    if (off > h->traj_blob_bytes) {
+        SDO(ssync(h));
+        if (h->traj_blob) (void)hipFree(h->traj_blob);
+        h->traj_blob = nullptr; h->traj_blob_bytes = 0;
+        SHIP(h, hipMalloc((void**)&h->traj_blob, off)); h->traj_blob_bytes = off;
+    }
+    char* b = h->traj_blob;
+    r.rec = TrajRec{(int32_t)M, (int32_t)D, (int32_t)W, Tcap, (float*)(b + o_obs), (uint32_t*)(b + o_act), (float*)(b + o_rew), (int32_t*)(b + o_len), (uint8_t*)(b + o_flg), h->ev_counter};
+    r.shadow = h->env;                                                             // the plug-in's kernels, scaling
+    r.shadow.E = (int)M; r.shadow.fixed_len = 1; r.shadow.episode_len = INT32_MAX; r.shadow.disc_returns = nullptr;
+    r.shadow.state = (float*)(b + o_st); r.shadow.step_count = (int32_t*)(b + o_sc); r.shadow.episode = (uint32_t*)(b + o_ep); r.shadow.gstep = (uint32_t*)(b + o_gs);
+    r.sh_rew = (float*)(b + o_srew); r.sh_term = (uint8_t*)(b + o_sterm); r.sh_trunc = (uint8_t*)(b + o_strunc); r.sh_tobs = (float*)(b + o_stobs); r.sh_obs = (float*)(b + o_sobs);
+    // the table: obs_low | obs_high (D each), act_low | act_high (W each).  No ClampAdapter: TanhScaleAdapter's actions are inside the Box by construction
+    std::vector<float> tab(2 * D + 2 * W, 0.f);
+    float *ol = tab.data(), *oh = ol + D, *al = oh + D, *ah = al + W;
+    bool scaled = false;
+    if (h->env.module) {
+        scaled = h->env.scaling;
+        if (scaled) {
+            for (size_t i = 0; i < D; ++i) { ol[i] = h->env.obs_low[i]; oh[i] = h->env.obs_high[i]; }
+            for (size_t i = 0; i < W; ++i) { al[i] = h->env.desc.action_low[i]; ah[i] = h->env.desc.action_high[i]; }
+        }
+    } else {
+        if (h->env.kind == 2) { scaled = true; ol[0] = -1.0f; oh[0] = 1.0f; ol[1] = -1.0f; oh[1] = 1.0f; ol[2] = -8.0f; oh[2] = 8.0f; al[0] = -2.0f; ah[0] = 2.0f; }   // the bounds env_obs<2> / env_step<2> use (dril_device.h)
+        if (h->env.kind == 7) { scaled = true; ol[0] = -1.2f; oh[0] = 0.6f; ol[1] = -0.07f; oh[1] = 0.07f; al[0] = -1.0f; ah[0] = 1.0f; }                             // env_obs<7> / env_step<7>
+    }
+    SHIP(h, hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
+    SDO(ssync(h));                                                                 // (the table is a local)
+    const float* dt = (const float*)(b + o_tab);
+    r.maps = TrajMaps{scaled ? dt : nullptr, scaled ? dt + D : nullptr, nullptr, nullptr, scaled ? dt + 2 * D : nullptr, scaled ? dt + 2 * D + W : nullptr, 0, o->final_original ? 1 : 0};
+    return DRIL_OK;
+}
+int traj_record_launch(dril_sac_handle* h, const SacTrajRun& r, const TrajStep& s, int32_t t) {
+    const int64_t n = (int64_t)r.rec.M * std::max(r.rec.D, r.rec.W);
+    hipLaunchKernelGGL(sac_traj_record_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.rec, r.maps, s, t);
+    SHIP(h, hipGetLastError());
+    return DRIL_OK;
+}
+// one env step, enqueued: the launches of eval_step without the accounting, and the recording of envs 0..M-1
+int traj_step(dril_sac_handle* h, const SacTrajRun& r, int32_t t, int deterministic, int32_t* launches) {
+    const int E = h->cfg.n_envs;
+    const int64_t f0 = h->fwd_launches; const int tag0 = h->col_tag;
+    const NzEvalArgs nz{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs};
+    if (h->env.module) SHIP(h, hipMemcpyAsync(r.shadow.state, h->env.state, (size_t)r.rec.M * h->S * 4, hipMemcpyDeviceToDevice, h->stream));   // the pre-step state of envs 0..M-1 (env-major prefix)
+    CollectHeadArgs ca; SDO(actor_hidden(h, 0, nullptr, &ca));
+    ca.deterministic = deterministic ? 1 : 0;
+    *launches += (int32_t)(h->fwd_launches - f0) + (h->col_tag != tag0 ? 2 : 0);   // (the f16-piece form of the hidden layers: sac_collect_l1_kernel + sac_collect_l2_kernel)
+    if (h->env.module) {
+        hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
+        SHIP(h, r.shadow.step(h->e_envact, EnvStepOut{r.sh_rew, r.sh_term, r.sh_trunc, r.sh_tobs, nullptr}, MonitorArgs{}, h->stream));   // the same step with the same actions' prefix, with no reset after it
+        SHIP(h, r.shadow.observe(r.sh_obs, h->stream));                            // observe(env) of the env that did not auto-reset
+        SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, MonitorArgs{}, h->stream));   // act!(env, action), :35 (monitor pointers null)
+        SDO(traj_record_launch(h, r, TrajStep{h->e_envact, h->e_rew, h->e_term, h->e_trunc, r.sh_obs}, t));
+        *launches += 6;                                                             // state copy, head, shadow step, shadow observe, live step, recording
+        if (nz.st && nz.norm_obs) { NzApplyArgs a{}; a.w.raw = h->obs_nxt; a.w.obs_out = h->obs_nxt; SDO(nz_apply(h, a, 0, false, false)); *launches += 1; }   // the next observation under the frozen statistics, in place
+    } else {                                                                       // every built-in Box env has A = 1
+        const TrajEnvArgs te{env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr}), nz, r.rec, r.maps, t};
+        const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
+        SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_traj_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, te); return hipGetLastError(); }));
+        *launches += 1;
+    }
+    SHIP(h, hipGetLastError());
+    std::swap(h->obs_cur, h->obs_nxt);
+    return DRIL_OK;
+}
+// reset!(env) .. the loop of trajectory_utils.jl:16-45 on the device; the host looks at the finished-counter once per K steps and never enqueues a step past Tcap
+int traj_run(dril_sac_handle* h, const dril_traj_options* o, SacTrajRun& r, int32_t* steps_out, int32_t* launches_out) {
+    const int M = r.rec.M, Tcap = r.rec.Tcap;
+    if (o->has_seed) h->env.seed0 = o->seed;                                       // env e seeded seed + e; its action noise is that env's stream from step 0
+    r.shadow.seed0 = h->env.seed0;
+    SHIP(h, h->env.reset(h->stream));                                              // reset!(env), :10
+    h->env.ready = true; h->obs_valid = false;
+    if (h->env.module) {
+        SHIP(h, hipMemsetAsync(r.shadow.step_count, 0, (size_t)M * 4, h->stream)); SHIP(h, hipMemsetAsync(r.shadow.episode, 0, (size_t)M * 4, h->stream));
+        SHIP(h, hipMemsetAsync(r.shadow.gstep, 0, (size_t)M * 4, h->stream));
+    }
+    SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
+    SDO(ensure_obs(h));                                                            // observation = observe(env), :17 (raw, into obs_cur: the wrapper's old_obs is not this call's to write)
+    SDO(traj_record_launch(h, r, TrajStep{nullptr, nullptr, nullptr, nullptr, h->obs_cur}, 0));   // row 0: the original observation, before the agent's copy is normalised
+    if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }   // normalised in place, nothing updated
+    const int K = o->poll_steps > 0 ? o->poll_steps : h->eval_poll;
+    int32_t steps = 0, launches = 0; unsigned int seen = 0;
+    while (seen < (unsigned int)M) {
+        if (steps >= Tcap) return sfail(h, DRIL_ERR_HIP, "dril_sac_collect_trajectory: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
+        for (int k = 0; k < K && steps < Tcap; ++k) SDO(traj_step(h, r, ++steps, o->deterministic ? 1 : 0, &launches));
+        SHIP(h, hipMemcpyAsync(h->ev_counter_host, h->ev_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        SDO(ssync(h));
+        seen = *h->ev_counter_host;
+    }
+    *steps_out = steps; *launches_out = launches;
+    return DRIL_OK;
+}
+int traj_run_and_copy(dril_sac_handle* h, const dril_traj_options* o, SacTrajRun& r, float* observations, float* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
+    const int M = r.rec.M, Tcap = r.rec.Tcap; const size_t D = (size_t)r.rec.D, W = (size_t)r.rec.W;
+    int32_t steps = 0, launches = 0;
+    SDO(traj_run(h, o, r, &steps, &launches));
+    // copy-out: lengths first, then rows 0..longest only, reordered into the caller's per-trajectory layout on the host
+    SHIP(h, hipMemcpyAsync(lengths, r.rec.length, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
+    SHIP(h, hipMemcpyAsync(end_flags, r.rec.end_flags, (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    SDO(ssync(h));
+    int32_t longest = 0, cuts = 0;
+    for (int m = 0; m < M; ++m) {
+        if (lengths[m] < 1 || lengths[m] > Tcap) return sfail(h, DRIL_ERR_HIP, "dril_sac_collect_trajectory: trajectory " + std::to_string(m) + " has length " + std::to_string(lengths[m]) + " (internal)");
+        longest = std::max(longest, lengths[m]); cuts += (end_flags[m] & kTrajCut) ? 1 : 0;
+    }
+    std::vector<float> obs_tm((size_t)(longest + 1) * M * D), rew_tm((size_t)longest * M); std::vector<uint32_t> act_tm((size_t)longest * M * W);
+    SHIP(h, hipMemcpyAsync(obs_tm.data(), r.rec.obs, obs_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    SHIP(h, hipMemcpyAsync(act_tm.data(), r.rec.act, act_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    SHIP(h, hipMemcpyAsync(rew_tm.data(), r.rec.rew, rew_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    SDO(ssync(h));
+    traj_reorder(M, (int64_t)D, (int64_t)W, Tcap, lengths, obs_tm.data(), act_tm.data(), rew_tm.data(), observations, (uint32_t*)actions, rewards);
+    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = 0; }
+    return DRIL_OK;
+}
+}  // namespace
+DRIL_EXPORT int32_t dril_sac_trajectory_capacity(const dril_sac_handle* h, const dril_traj_options* o, int32_t* capacity) {
+    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    dril_sac_handle* hh = const_cast<dril_sac_handle*>(h);
+    if (!o || !capacity || o->max_steps < 0) return sfail(hh, DRIL_ERR_INVALID_ARG, "dril_sac_trajectory_capacity: options and capacity != NULL, max_steps >= 0");
+    if (h->external) return sfail(hh, DRIL_ERR_UNSUPPORTED, "dril_sac_trajectory_capacity: the envs of DRIL_ENV_EXTERNAL live on the host, with the caller");
+    *capacity = traj_capacity(o->max_steps, h->env.episode_len);
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_collect_trajectory(dril_sac_handle* h, const dril_traj_options* o, float* observations, float* actions, float* rewards, int32_t* lengths,
+                                                uint8_t* end_flags, dril_traj_info* info) {
+    SNEED(h);
+    if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_collect_trajectory: the envs of DRIL_ENV_EXTERNAL live on the host: record there, in a loop over dril_sac_predict_actions");
+    if (!o || !observations || !actions || !rewards || !lengths || !end_flags || o->n_trajectories < 1 || o->n_trajectories > h->cfg.n_envs || o->max_steps < 0 || o->poll_steps < 0)
+        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_collect_trajectory: options and the five output arrays != NULL, 1 <= n_trajectories <= n_envs, max_steps >= 0, poll_steps >= 0");
+    if (info) std::memset(info, 0, sizeof(*info));
+    const int32_t Tcap = traj_capacity(o->max_steps, h->env.episode_len);
+    const int64_t bytes = traj_bytes(o->n_trajectories, Tcap, h->D, h->A);
+    if (bytes > kTrajMaxBytes)
+        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_collect_trajectory: the recording needs " + std::to_string(bytes) + " bytes on the device (M = " + std::to_string(o->n_trajectories) + ", Tcap = " + std::to_string(Tcap) + "), more than 1 GiB: record fewer envs or set max_steps");
+    SDO(eval_buffers(h, 0));
+    SacTrajRun run{};
+    SDO(traj_prepare(h, o, Tcap, run));
+    // as dril_sac_evaluate_agent: what a collection would continue from is set aside here and put back below, on every path
+    const uint64_t seed0 = h->env.seed0; const bool ready = h->env.ready, obs_valid = h->obs_valid;
+    SDO(eval_snapshot(h, true));
+    const int rc = traj_run_and_copy(h, o, run, observations, actions, rewards, lengths, end_flags, info);
+    const std::string msg = h->err;
+    h->env.seed0 = seed0; h->env.ready = ready; h->obs_valid = obs_valid;
+    int rr = eval_snapshot(h, false); if (rr == DRIL_OK) rr = ssync(h);
+    if (rc != DRIL_OK) { h->err = msg; return rc; }
+    return rr;
 }

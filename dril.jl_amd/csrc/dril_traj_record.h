@@ -2,6 +2,8 @@
 // action, the reward, the done flags and the observation of its step — the active test, what is written where, finalisation, and the precedence of the episode's end
 // over the max_steps cut.  No HIP dependency, in the manner of dril_eval_account.h: dril_api.hip (traj_record_kernel, over the E-sized per-step arrays and the shadow
 // envs' observation) includes it, and tests/test_traj_device.py drives the same lines with g++ against a restatement of the reference's loop.
+// The SAC handle's verb runs the same rule (dril_sac.hip: sac_traj_env_kernel through traj_record_env, sac_traj_record_kernel through traj_record_lane, both with null
+// clamp pointers; tests/test_sac_traj.py).
 //
 // The recording is step-major on the device, [t][m][.], so one step's writes are contiguous M-sized rows; traj_reorder puts it into the caller's per-trajectory layout.
 // Every index is 64-bit.

@@ -201,6 +201,45 @@ function DRiL.evaluate_agent(agent::SACAgent, env::DeviceParallelEnv; n_eval_epi
 end
 
 """
+    collect_trajectory(agent::SACAgent, env::DeviceParallelEnv; max_steps = nothing, deterministic = true, n_trajectories = 1, ...)
+
+`collect_trajectory` (src/utils/trajectory_utils.jl:3-49) of a SAC agent on a device env (built-in Box kind or `OnDeviceModule`), on a throw-away handle built as
+`evaluate_agent` builds its own (dril_sac_collect_trajectory): `(observations, actions, rewards)` as the reference returns them (L + 1 original observations, L env
+actions, L raw rewards); `n_trajectories > 1`: a vector of such tuples, envs 1..n of the parallel env, each its first episode after the reset.  An env with
+`normalize` keywords runs under NormalizeWrapperEnv with training off and `normalize_stats`; the recording is raw.
+"""
+function DRiL.collect_trajectory(agent::SACAgent, env::DeviceParallelEnv; max_steps::Union{Int, Nothing} = nothing, deterministic::Bool = true, n_trajectories::Int = 1,
+        normalize_stats = nothing, kwargs...)
+    h = sac_create(env, agent.algorithm, agent)
+    try
+        sac_push_agent!(h, agent)
+        if env.normalize !== nothing
+            sac_normalize_set_training!(h, false)
+            normalize_stats === nothing || sac_set_norm_stats!(h, normalize_stats)
+        end
+        o = Ref(DrilTrajOptions(Int32(n_trajectories), Int32(max_steps === nothing ? 0 : max_steps), Int32(deterministic), Int32(1), UInt64(env.seed), Int32(0), Int32(0),
+            (Int32(0), Int32(0), Int32(0), Int32(0), Int32(0))))
+        cap = Ref{Int32}(0)
+        sac_check(ccall((:dril_sac_trajectory_capacity, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilTrajOptions}, Ref{Int32}), h, o, cap), h)
+        D = Int(ccall((:dril_sac_obs_dim, LIB[]), Int32, (Ptr{Cvoid},), h)); A = Int(ccall((:dril_sac_action_dim, LIB[]), Int32, (Ptr{Cvoid},), h))
+        T = Int(cap[]); M = n_trajectories
+        obs = Array{Float32}(undef, D, T + 1, M); act = Array{Float32}(undef, A, T, M); rew = Matrix{Float32}(undef, T, M)
+        len = Vector{Int32}(undef, M); flags = Vector{UInt8}(undef, M)
+        GC.@preserve obs act rew len flags sac_check(ccall((:dril_sac_collect_trajectory, LIB[]), Int32,
+            (Ptr{Cvoid}, Ref{DrilTrajOptions}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{UInt8}, Ptr{DrilTrajInfo}),
+            h, o, obs, act, rew, len, flags, C_NULL), h)
+        any(f -> f & 0x04 != 0, flags) && @warn "Max steps reached"                                                # trajectory_utils.jl:39
+        trajs = map(1:M) do m
+            L = Int(len[m])
+            ([obs[:, t, m] for t in 1:(L + 1)], [act[:, t, m] for t in 1:L], [rew[t, m] for t in 1:L])
+        end
+        return M == 1 ? trajs[1] : trajs
+    finally
+        ccall((:dril_sac_destroy, LIB[]), Int32, (Ptr{Cvoid},), h)
+    end
+end
+
+"""
     train!(agent, env::DeviceParallelEnv, alg::SAC, max_steps) -> (agent, nothing, training_stats, to)
 
 Same contract as `train!(agent, replay_buffer, env, alg::SAC, max_steps)` (sac.jl:414-549) with the ReplayBuffer resident on the device

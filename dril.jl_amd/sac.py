@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _capi as capi, _normalize
 from ._capi import DrilSacConfig, DrilSacStats
-from .host import Box, DeviceArrayParallelEnv, DrilError, PendulumEnv, ScalingWrapperEnv, _dev_ptr, _orthogonal, _stream_ptr, _to_host
+from .host import Box, DeviceArrayParallelEnv, DrilError, HostParallelEnv, PendulumEnv, ScalingWrapperEnv, _dev_ptr, _orthogonal, _stream_ptr, _to_host
 
 
 # --------------------------------------------------------------------------------------------
@@ -510,6 +510,30 @@ class SacHandle:
         return dict(mean_reward=st.mean_reward, std_reward=st.std_reward, mean_length=st.mean_length, std_length=st.std_length,
                     n_steps=st.n_steps), er, el
 
+    def collect_trajectory(self, n_trajectories: int = 1, max_steps: Optional[int] = None, deterministic: bool = True, seed: Optional[int] = None,
+                           poll_steps: int = 0, final_original: bool = False):
+        """collect_trajectory on the device, leaving nothing behind on the handle (dril_sac_collect_trajectory, docs/sac.md "Trajectories"): envs 0..n_trajectories-1
+        record their first episode after the call's own reset -> (trajectories, lengths, end_flags, info dict), in the shapes of Handle.collect_trajectory_device.
+        trajectories[m] = (observations (L+1, D), actions (L, A), rewards (L,)): original observations (rows 0..L-1 unscaled under ScalingWrapperEnv, never normalised),
+        the actions the env's physics received, raw rewards; the last observation is the terminal state as the wrapper delivers it (final_original: unscaled too).
+        end_flags: capi.TRAJ_TERMINATED | TRAJ_TRUNCATED | TRAJ_MAX_STEPS.  info: capacity, steps_enqueued, launches, longest, cut_by_max_steps, path (0)."""
+        if max_steps is not None and int(max_steps) < 1:
+            raise ValueError("max_steps is None or >= 1")
+        o = capi.DrilTrajOptions()
+        o.n_trajectories, o.max_steps, o.deterministic = int(n_trajectories), 0 if max_steps is None else int(max_steps), int(deterministic)
+        o.poll_steps, o.final_original = int(poll_steps), int(bool(final_original))
+        if seed is not None:
+            o.seed, o.has_seed = int(seed), 1
+        cap, info = C.c_int32(), capi.DrilTrajInfo()
+        self._chk(self._f("trajectory_capacity")(self._h, C.byref(o), C.byref(cap)))
+        M, T = max(int(n_trajectories), 1), cap.value
+        obs = np.empty((M, T + 1, self.D), np.float32); act = np.empty((M, T, self.A), np.float32)
+        rew = np.empty((M, T), np.float32); lengths = np.empty(M, np.int32); flags = np.empty(M, np.uint8)
+        self._chk(self._f("collect_trajectory")(self._h, C.byref(o), self._p(obs), self._p(act), self._p(rew), self._p(lengths), self._p(flags), C.byref(info)))
+        trajs = [(obs[m, :L + 1].copy(), act[m, :L].copy(), rew[m, :L].copy()) for m, L in enumerate(lengths)]
+        return trajs, lengths, flags, dict(capacity=info.capacity, steps_enqueued=info.steps_enqueued, launches=info.launches, longest=info.longest,
+                                           cut_by_max_steps=info.cut_by_max_steps, path=info.reserved[capi.TRAJ_INFO_PATH])
+
     def profile(self) -> dict:
         cm, um, cs, us = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self._f("profile_get")(self._h, C.byref(cm), C.byref(cs), C.byref(um), C.byref(us)))
@@ -607,6 +631,34 @@ def _normalize_from_env(h: SacHandle, env, normalize: Optional[dict]):
         h.normalize_enable(**kw)
 
 
+def _sac_throwaway_handle(agent: "SACAgent", env, normalize: Optional[dict], normalize_stats, who: str, what: str) -> "SacHandle":
+    """the throw-away handle of sac_evaluate_agent / sac_collect_trajectory over a DeviceParallelEnv or a DeviceModuleEnv: the agent's parameters, ScalingWrapperEnv as
+    the env carries it, NormalizeWrapperEnv (the env's own keywords, or `normalize`) with training off and the statistics of `normalize_stats` — the training handle, a
+    norm_get_stats() dict, or "fresh"; without them a RuntimeWarning says that the run is under mean 0 / var 1.  The caller closes it."""
+    small = replace(agent.alg, buffer_capacity=max(env.n_envs, 1))        # neither verb touches the ring: the smallest one the library accepts
+    cfg = make_sac_config(env.env, env.n_envs, small, agent.layer, seed=env.seed, device=env._kw.get("device", 0))
+    h = SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
+    try:
+        h.set_params(sac_flatten_params(agent.parameters))
+        _scaling_from_env(h, env)
+        kw = _normalize_kw(env, normalize)
+        if kw is not None:           # sync_normalization_stats! + set_training(eval_env, false) (normalizeWrapperEnv.jl:245-249,299-309): the training statistics, frozen
+            h.normalize_enable(**{**kw, "training": False})
+            if normalize_stats is None:
+                warnings.warn(f"{who}: the env is normalised but no normalize_stats were given: the {what} runs with fresh statistics (mean 0, var 1), "
+                              "not those the agent was trained under; pass the training handle (replay_buffer.handle), a norm_get_stats() dict, or \"fresh\" to say so",
+                              RuntimeWarning, stacklevel=3)
+            st = None if isinstance(normalize_stats, str) else normalize_stats.norm_get_stats() if hasattr(normalize_stats, "norm_get_stats") else normalize_stats
+            if isinstance(normalize_stats, str) and normalize_stats != "fresh":
+                raise ValueError("normalize_stats: a handle, a norm_get_stats() dict, or \"fresh\"")
+            if st is not None:
+                h.norm_set_stats(*(st[k] for k in ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")))
+    except BaseException:
+        h.close()
+        raise
+    return h
+
+
 def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, deterministic: bool = True, reward_threshold: Optional[float] = None,
                        return_stats: bool = True, *, normalize: Optional[dict] = None, normalize_stats=None):
     """evaluate_agent(agent, env; ...) (src/evaluation.jl:54-143) of a SAC agent on a DeviceParallelEnv over a Box env or a DeviceModuleEnv over a Box plug-in:
@@ -619,31 +671,38 @@ def sac_evaluate_agent(agent: SACAgent, env, n_eval_episodes: int = 10, determin
         return _sac_evaluate_device_arrays(agent, env, n_eval_episodes, deterministic, reward_threshold, return_stats, normalize_stats)
     if getattr(env, "kind", None) == capi.ENV_EXTERNAL:
         raise NotImplementedError("sac_evaluate_agent: host envs (HostParallelEnv) are evaluated on the host; the device verb steps device envs")
-    alg = agent.alg
-    small = replace(alg, buffer_capacity=max(env.n_envs, 1))        # an evaluation never touches the ring: the smallest one the library accepts
-    cfg = make_sac_config(env.env, env.n_envs, small, agent.layer, seed=env.seed, device=env._kw.get("device", 0))
-    h = SacHandle(cfg, env_module=getattr(env.env, "code_object_path", None))
+    h = _sac_throwaway_handle(agent, env, normalize, normalize_stats, "sac_evaluate_agent", "evaluation")
     try:
-        h.set_params(sac_flatten_params(agent.parameters))
-        _scaling_from_env(h, env)
-        kw = _normalize_kw(env, normalize)
-        if kw is not None:           # sync_normalization_stats! + set_training(eval_env, false) (normalizeWrapperEnv.jl:245-249,299-309): the training statistics, frozen
-            h.normalize_enable(**{**kw, "training": False})
-            if normalize_stats is None:
-                warnings.warn("sac_evaluate_agent: the env is normalised but no normalize_stats were given: the evaluation runs with fresh statistics (mean 0, var 1), "
-                              "not those the agent was trained under; pass the training handle (replay_buffer.handle), a norm_get_stats() dict, or \"fresh\" to say so",
-                              RuntimeWarning, stacklevel=2)
-            st = None if isinstance(normalize_stats, str) else normalize_stats.norm_get_stats() if hasattr(normalize_stats, "norm_get_stats") else normalize_stats
-            if isinstance(normalize_stats, str) and normalize_stats != "fresh":
-                raise ValueError("normalize_stats: a handle, a norm_get_stats() dict, or \"fresh\"")
-            if st is not None:
-                h.norm_set_stats(*(st[k] for k in ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")))
         stats, er, el = h.evaluate_agent(n_eval_episodes, deterministic, seed=env.seed)
     finally:
         h.close()
     if reward_threshold is not None and stats["mean_reward"] < reward_threshold:
         raise RuntimeError(f"Mean reward below threshold: {stats['mean_reward']:.2f} < {reward_threshold}")   # evaluation.jl:131-135
     return {k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} if return_stats else (er, el.astype(np.int64))
+
+
+def sac_collect_trajectory(agent: SACAgent, env, max_steps: Optional[int] = None, norm_env=None, deterministic: bool = True, n_trajectories: int = 1,
+                           seed: Optional[int] = None, *, normalize: Optional[dict] = None, normalize_stats=None):
+    """collect_trajectory(agent, env; max_steps, norm_env, deterministic) (src/utils/trajectory_utils.jl:3-49) of a SAC agent on a DeviceParallelEnv over a Box env or a
+    DeviceModuleEnv over a Box plug-in -> (observations, actions, rewards): the original observations (L + 1 of them, the last one the terminal state), the env actions
+    and the raw rewards of one episode; n_trajectories > 1: a list of such triples, envs 0..n-1 of the parallel env, each its first episode after the reset (seed:
+    env.seed by default).  Runs on a throw-away handle built as sac_evaluate_agent builds its own (dril_sac_collect_trajectory, docs/sac.md "Trajectories"):
+    NormalizeWrapperEnv frozen, under `normalize_stats`; the recording is raw.  norm_env: None, or `env` itself — the normaliser around a device env is a mode of the
+    handle, found in the env's keywords (or `normalize=`)."""
+    if isinstance(env, (HostParallelEnv, DeviceArrayParallelEnv)) or getattr(env, "kind", None) == capi.ENV_EXTERNAL:
+        raise NotImplementedError("sac_collect_trajectory: host envs (HostParallelEnv, DeviceArrayParallelEnv) live with the caller; the device verb steps device envs "
+                                  "(record there, in a loop over predict_actions)")
+    if norm_env is not None and norm_env is not env:
+        raise NotImplementedError("sac_collect_trajectory: norm_env is None or the env itself (NormalizeWrapperEnv around a device env is a mode of the handle: it is "
+                                  "taken from the env's keywords or `normalize=` and applied frozen, with the statistics of `normalize_stats`)")
+    h = _sac_throwaway_handle(agent, env, normalize, normalize_stats, "sac_collect_trajectory", "recording")
+    try:
+        trajs, _, flags, _ = h.collect_trajectory(n_trajectories, max_steps, deterministic, env.seed if seed is None else seed)
+    finally:
+        h.close()
+    if (flags & capi.TRAJ_MAX_STEPS).any():
+        warnings.warn("Max steps reached")                                           # trajectory_utils.jl:39
+    return trajs[0] if n_trajectories == 1 else trajs
 
 
 def _sac_ext_handle(agent: SACAgent, env, alg: SAC, rb_handle=None) -> "SacHandle":

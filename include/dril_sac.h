@@ -400,6 +400,32 @@ int32_t dril_sac_ext_wrap_info(const dril_sac_handle* h, struct dril_sac_ext_wra
 int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval_episodes, int32_t deterministic, uint64_t seed,
                                 dril_eval_stats* out, float* episode_rewards, int32_t* episode_lengths);
 
+/* ---- collect_trajectory(agent, env; max_steps, deterministic) (src/utils/trajectory_utils.jl:3-49) with the handle's actor on the handle's envs ----------------
+ * The SAC form of dril_collect_trajectory_device (dril_hip.h; docs/sac.md "Trajectories"): dril_traj_options, dril_traj_info, dril_traj_options_default, the layouts
+ * of the five output arrays and the end-flag bits are those of that verb.  Envs 0..M-1 record their FIRST episode after the call's own reset (has_seed ? seed : the
+ * seed in force; env e gets seed + e).  Row t < L is the ORIGINAL observation before step t + 1: never normalised, and under ScalingWrapperEnv (the scaled kinds,
+ * or dril_sac_scaling_enable on a plug-in) mapped back with unscale_from_unit.  The agent sees the wrapper's observation: scaled, and normalised with the statistics
+ * of dril_sac_normalize_enable FROZEN for the call whatever its training flag.  Action row t is mode(d) = tanh(mean) (deterministic) or a sample, through
+ * to_env(TanhScaleAdapter), then unscale! under ScalingWrapperEnv: the value the env's physics receives.  Reward row t is the env's raw reward.  The episode ends at
+ * its first terminated || truncated or after max_steps steps, the episode's end taking precedence; row L is observe(env) of the env that did not auto-reset, in the
+ * wrapper's scale unless final_original.  With deterministic = 0 the draws are those of dril_sac_evaluate_agent on the same seed, which are those of a collection
+ * after dril_sac_env_reset(seed).  The trajectory of env m does not depend on M, on poll_steps or on the other envs.
+ * The call leaves nothing behind: it never writes the replay ring, parameters, targets, optimiser state, update counters, the monitor's window or the normaliser's
+ * statistics / returns / old_obs, and it sets aside and puts back what dril_sac_evaluate_agent sets aside and puts back, on error paths too.
+ * poll_steps = 0: K of dril_sac_evaluate_agent (DRIL_SAC_EVAL_POLL honoured).  reserved[DRIL_TRAJ_OPT_PERSISTENT] is accepted and ignored (there is one form);
+ * info.reserved[DRIL_TRAJ_INFO_PATH] is 0.
+ * DRIL_ERR_NOT_INITIALISED: null handle.  DRIL_ERR_INVALID_ARG: null options or output array, n_trajectories outside 1..n_envs, negative max_steps or poll_steps, a
+ * recording whose device arrays exceed 1 GiB.  DRIL_ERR_UNSUPPORTED: DRIL_ENV_EXTERNAL (the envs live with the caller: loop there over dril_sac_predict_actions).
+ * All of them are decided before anything is enqueued. */
+int32_t dril_sac_trajectory_capacity(const dril_sac_handle* h, const dril_traj_options* o, int32_t* capacity);
+int32_t dril_sac_collect_trajectory(dril_sac_handle* h, const dril_traj_options* o,
+                                    float* observations,  /* (D, Tcap+1, M) column-major, as dril_collect_trajectory_device */
+                                    float* actions,       /* f32 (A, Tcap, M); rows >= lengths[m] are 0 */
+                                    float* rewards,       /* (Tcap, M) */
+                                    int32_t* lengths,     /* (M): steps taken */
+                                    uint8_t* end_flags,   /* (M): bit0 terminated, bit1 truncated, bit2 stopped by max_steps */
+                                    dril_traj_info* info  /* may be NULL; the five arrays may not */);
+
 /* ---- measurement: accumulated HIP-event milliseconds since the last reset --------------------------------------------- */
 int32_t dril_sac_profile_get(dril_sac_handle* h, double* collect_ms, int64_t* collect_steps, double* update_ms,
                              int64_t* updates);

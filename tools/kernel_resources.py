@@ -27,7 +27,7 @@ for ln in r.stderr.splitlines():
     if t.startswith("Function Name:"): cur = {"name": t.split(":", 1)[1].strip()}; rows.append(cur)
     elif cur is not None and ":" in t: k, v = t.split(":", 1); cur[k.strip()] = v.strip()
 def dem(n):
-    return subprocess.run(["/usr/bin/c++filt", n], capture_output=True, text=True).stdout.strip().replace("dril::", "").split("(")[0]
+    return subprocess.run(["/usr/bin/c++filt", n], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").replace("dril::", "").split("(")[0]
 print(f"{'kernel':70s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'occ':>3s} {'LDS':>7s} {'code B':>8s}")
 for c in rows:
     n = dem(c["name"])
