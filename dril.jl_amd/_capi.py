@@ -110,6 +110,11 @@ class DrilFusedRolloutInfo(C.Structure):
                 ("last_collection_launches", C.c_int64), ("reason", C.c_char * 256)]
 
 
+class DrilFusedEvaluateInfo(C.Structure):
+    """struct dril_fused_evaluate_info, include/dril_hip.h"""
+    _fields_ = [("available", C.c_int32), ("tile", C.c_int32), ("threads", C.c_int32), ("max_width", C.c_int32), ("reason", C.c_char * 256)]
+
+
 class DrilExtDeviceInfo(C.Structure):
     """struct dril_ext_device_info, include/dril_hip.h"""
     _fields_ = [("steps_device", C.c_int32), ("steps_host", C.c_int32), ("host_syncs", C.c_int32), ("per_dim_bounds", C.c_int32), ("launches", C.c_int64),
@@ -223,6 +228,7 @@ _SIG = {
     "dril_agent_spaces": (C.c_int32, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     "dril_rollout_fused_enable": (C.c_int32, [_P, C.c_int32]),
     "dril_rollout_fused_info": (C.c_int32, [_P, _P]),
+    "dril_evaluate_fused_info": (C.c_int32, [_P, _P]),
     "dril_destroy": (C.c_int32, [_P]),
     "dril_last_error": (C.c_char_p, [_P]),
     "dril_synchronize": (C.c_int32, [_P]),

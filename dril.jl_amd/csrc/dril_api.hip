@@ -172,6 +172,9 @@ struct dril_handle {
     unsigned int *eval_counter = nullptr, *eval_counter_host = nullptr; SacEvalEvent* eval_events = nullptr; long long eval_events_cap = 0;
     // dril_collect_trajectory_device: ONE grow-only blob for the step-major recording, the shadow envs' arrays and the table of bounds (the counter and its pinned word are the evaluation's)
     char* traj_blob = nullptr; size_t traj_blob_bytes = 0;
+    // path 2 of both verbs (a plug-in's fused evaluation kernel): ONE grow-only blob for the observation and action scratch, the K rows of rewards and flag bytes and,
+    // when recording, the rows of raw actions and post-step observations
+    char* evalf_blob = nullptr; size_t evalf_blob_bytes = 0;
     std::string err;
 };
 
@@ -613,6 +616,7 @@ DRIL_EXPORT int32_t dril_config_default(dril_config* c, int32_t env_kind) {
 namespace {
 int create_impl(const dril_config* cfg, const char* module_path, dril_handle** out);
 std::string fused_rollout_unavailable(const dril_handle* h);
+std::string fused_evaluate_unavailable(const dril_handle* h);
 }  // namespace
 
 DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
@@ -677,6 +681,16 @@ DRIL_EXPORT int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rol
     const std::string why = fused_rollout_unavailable(h);
     out->available = why.empty() ? 1 : 0; out->enabled = h->fused_rollout ? 1 : 0; out->last_collection_launches = h->rollout_launches;
     if (h->env.module && h->env.rollout.has_desc) { out->tile = h->env.rollout.desc.tile; out->threads = h->env.rollout.desc.threads; out->max_width = h->env.rollout.desc.max_width; }
+    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_evaluate_fused_info(const dril_handle* h, dril_fused_evaluate_info* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_evaluate_fused_info: null out pointer");
+    std::memset(out, 0, sizeof(*out));
+    const std::string why = fused_evaluate_unavailable(h);
+    out->available = why.empty() ? 1 : 0;
+    if (h->env.module && h->env.evaluate.has_desc) { out->tile = h->env.evaluate.desc.tile; out->threads = h->env.evaluate.desc.threads; out->max_width = h->env.evaluate.desc.max_width; }
     std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
     return DRIL_OK;
 }
@@ -837,7 +851,7 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     if (h->eval_counter_host) (void)hipHostFree(h->eval_counter_host);
     if (h->ext_err_host) (void)hipHostFree(h->ext_err_host);
     if (h->ext_ev_in) (void)hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) (void)hipEventDestroy(h->ext_ev_out);
-    void* ptrs[] = {h->ext_err, h->ext_pred_obs, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->traj_blob, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
+    void* ptrs[] = {h->ext_err, h->ext_pred_obs, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->traj_blob, h->evalf_blob, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
                     h->flags, h->last_values, h->noise_dev, h->perm_dev, h->epoch_index, h->epoch_keys, h->small_xchg, h->w2max_dev, h->gae_carry, h->gae_err, h->w2pf_actor, h->w2pf_critic, h->adv_partials, h->adv_stats, h->ev_partials, h->step_stats,
                     h->stop_flag, h->nan_flag, h->e_obs, h->e_rew, h->e_tobs, h->e_term, h->e_trunc, h->e_act, h->e_obs_raw, h->e_rew_n, h->obs_rms, h->ret_rms, h->rms_partials, h->rms_red, h->gen_tmp, h->dbg, h->rec, h->epoch_tables, h->epoch_stats, h->w2a_actor, h->w2ta_actor, h->w2a_critic, h->w2ta_critic, h->w2p_actor, h->w2tp_actor, h->w2p_critic, h->w2tp_critic, h->mon_cur_ret, h->ep_ret, h->mon_ring_ret, h->e_ep_ret, h->mon_cur_len, h->ep_len,
                     h->mon_ring_len, h->e_ep_len, h->mon_cnt, h->mon_meta, h->e_flags};
@@ -1283,6 +1297,18 @@ std::string fused_rollout_unavailable(const dril_handle* h) {
     if (h->D > W) return "the observation has " + std::to_string(h->D) + " dims, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->D) + " or more";
     for (int l = 0; l < h->gd.nh; ++l) if (h->gd.H[l] > W) return "hidden layer " + std::to_string(l + 1) + " is " + std::to_string(h->gd.H[l]) + " wide, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->gd.H[l]) + " or more";
     if (h->env.scaling && !r.fn_scaled) return "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_rollout_scaled kernel: rebuild it with this library's include/device/dril_env_rollout.h";
+    return "";
+}
+
+// "" when the handle's net fits the plug-in's fused evaluation kernel (path 2 of the evaluation / trajectory verbs), else why not
+std::string fused_evaluate_unavailable(const dril_handle* h) {
+    if (!h->env.module) return "the fused evaluation is a kernel of a device env plug-in (DRIL_ENV_MODULE): the built-in envs evaluate with the library's own evaluate_kernel, host envs (DRIL_ENV_EXTERNAL) step on the host";
+    const EnvModuleEvaluate& r = h->env.evaluate;
+    if (!r.reason.empty()) return std::string("env plug-in \"") + h->env.desc.name + "\": " + r.reason;
+    const int W = r.desc.max_width;
+    if (h->D > W) return "the observation has " + std::to_string(h->D) + " dims, the plug-in's fused evaluation was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->D) + " or more";
+    for (int l = 0; l < h->gd.nh; ++l) if (h->gd.H[l] > W) return "hidden layer " + std::to_string(l + 1) + " is " + std::to_string(h->gd.H[l]) + " wide, the plug-in's fused evaluation was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->gd.H[l]) + " or more";
+    if (h->env.scaling && !r.fn_scaled) return "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_evaluate_scaled kernel: rebuild it with this library's include/device/dril_env_evaluate.h";
     return "";
 }
 
@@ -2246,6 +2272,25 @@ int evaluate_agent_loop(dril_handle* h, int32_t n_eval, int32_t deterministic, d
 //   path 1  ONE launch of evaluate_kernel (dril_kernels.hip): built-in kinds on the fused shapes of width 64 / 128 / 256 with no normaliser — and, where the
 //           options ask for it (DRIL_EVAL_OPT_PERSISTENT), under cfg.norm_* too: evaluate_modes_kernel reads the frozen statistics as an argument
 //   path 0  per env step the launches run_policy / step_dev / observe_dev make, and eval_account_kernel over the step's reward and done arrays: everything else
+//   path 2  on request, a plug-in handle whose code object carries a usable evaluation kernel (include/device/dril_env_evaluate.h): ONE launch of that kernel leaves the K
+//           rows of raw rewards and flag bytes, ONE launch of eval_account_rows_kernel walks them: 2 launches per K env steps
+namespace dril {   // (a named namespace: tools/kernel_resources.py lists the kernels by their names)
+// path 2: a thread per env walks its K rows in step order.  Inside the launch events are unordered, as on path 1: the list has eval_event_capacity(n, E, K) slots
+__global__ __launch_bounds__(256) void eval_account_rows_kernel(EvalAcct a, int32_t step0, int32_t K, const float* __restrict__ rew, const uint8_t* __restrict__ flags) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.E) return;
+    float ret = a.cur_ret[e]; int32_t len = a.cur_len[e];
+    for (int32_t k = 0; k < K; ++k) { const size_t i = (size_t)k * a.E + e; eval_account(a, step0 + k + 1, e, rew[i], flags[i] != 0, ret, len); }
+    a.cur_ret[e] = ret; a.cur_len[e] = len;
+}
+// path 2, recording: the per-trajectory rule over the K rows, a thread per (env, word) as traj_record_kernel
+__global__ __launch_bounds__(256) void traj_record_rows_kernel(TrajRec r, TrajMaps x, TrajRows s, int32_t t0) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t lanes = r.D > r.W ? r.D : r.W;
+    if (i >= (int64_t)r.M * lanes) return;
+    traj_record_lane_rows(r, x, s, t0, (int32_t)(i / lanes), (int32_t)(i % lanes));
+}
+}  // namespace dril
 namespace {
 __global__ __launch_bounds__(256) void eval_account_kernel(EvalAcct a, int32_t step, const float* __restrict__ rew, const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2275,6 +2320,31 @@ void eval_mode_norm(const dril_handle* h, EvalModeArgs& x, bool raw) {
     x.obs_stats = h->obs_rms + h->obs_par; x.ret_stats = h->ret_rms + h->ret_par;
     x.norm_obs = h->cfg.norm_obs ? 1 : 0; x.norm_reward = h->cfg.norm_reward ? 1 : 0; x.count_raw = raw ? 1 : 0;
     x.clip_obs = h->cfg.clip_obs; x.clip_reward = h->cfg.clip_reward; x.eps = h->cfg.norm_epsilon;
+}
+// path 2 applies: the request, a plug-in handle, a usable kernel for this net; DRIL_FORCE_STEPWISE wins, as everywhere
+bool eval_fused_applies(const dril_handle* h, bool requested) {
+    return requested && h->env.module && !h->force_stepwise && fused_evaluate_unavailable(h).empty();
+}
+// the argument block of a plug-in's evaluation kernel for launches of up to K steps, M recorded envs (shadow: their never-resetting twins; null when M == 0); the
+// handle's blob is grown to hold the scratch.  The frozen statistics of dril_normalize_enable travel as pointers into the half in force and are only read
+int eval_fused_args(dril_handle* h, DrilEnvEvaluateArgs& g, int deterministic, int K, int M, const DeviceEnvs* shadow) {
+    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D, W = h->discrete ? 1 : (size_t)h->A, Ks = (size_t)K, Ms = (size_t)M;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_obs = take(E * D * 4), o_act = take(E * W * 4), o_rew = take(Ks * E * 4), o_flg = take(Ks * E);
+    const size_t o_obs0 = take(Ms * D * 4), o_ract = take(Ks * Ms * W * 4), o_robs = take(Ks * Ms * D * 4);
+    if (off > h->evalf_blob_bytes) { if (h->evalf_blob) (void)hipFree(h->evalf_blob); h->evalf_blob = nullptr; h->evalf_blob_bytes = 0; HIPCHK(h, dmalloc(&h->evalf_blob, off)); h->evalf_blob_bytes = off; }
+    char* b = h->evalf_blob;
+    g = DrilEnvEvaluateArgs{};
+    g.r.env = h->env.args(); g.r.env.obs = (float*)(b + o_obs);                       // (after the call's seed is in force: seed0 is the one the reset used)
+    g.r.T = K; g.r.n_hidden = h->gd.nh; g.r.activation = h->gd.act; g.r.n_params = h->P;
+    for (int l = 0; l < h->gd.nh; ++l) g.r.hidden[l] = h->gd.H[l];
+    g.r.actor_off = h->actor.w1; g.r.log_std_off = h->log_std_off; g.r.params = h->params;
+    g.r.act = b + o_act; g.r.rew = (float*)(b + o_rew); g.r.flags = (uint8_t*)(b + o_flg);
+    g.deterministic = deterministic ? 1 : 0; g.n_record = M;
+    if (h->pn.on && h->pn.cfg.norm_obs) { g.norm_mean = h->pn.half(h->pn.cur); g.norm_var = g.norm_mean + h->pn.D; g.norm_eps = h->pn.cfg.epsilon; g.norm_clip = h->pn.cfg.clip_obs; }
+    if (M > 0) { g.shadow = shadow->args(); g.rec_obs0 = (float*)(b + o_obs0); g.rec_act = b + o_ract; g.rec_obs = (float*)(b + o_robs); }
+    return DRIL_OK;
 }
 template <typename T> int eval_ensure(dril_handle* h, T** p, size_t n) { if (!*p) HIPCHK(h, dmalloc(p, n)); return DRIL_OK; }
 // what one evaluation sets aside: device arrays in a list (copied to / from one blob), the host-side words next to them
@@ -2334,16 +2404,17 @@ int eval_poll_steps(const dril_handle* h, const dril_eval_options* o, bool persi
     if (persistent) K = (int)std::max<long long>(1, std::min<long long>(K, kEvalMaxLaunchEvents / std::max(1, h->cfg.n_envs)));
     return K;
 }
-int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent, bool raw, int K, long long cap, std::vector<SacEvalEvent>& events, dril_eval_info* info) {
+int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent, bool fused, bool raw, int K, long long cap, std::vector<SacEvalEvent>& events, dril_eval_info* info) {
     const int E = h->cfg.n_envs, n_eval = o->n_eval_episodes;
     if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
     HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :87
     h->env.ready = true;
     HIPCHK(h, hipMemsetAsync(h->eval_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_cur_len, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
     const EvalAcct acct{E, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, (unsigned int)cap};
-    EvalKernelArgs g{}; EvalModeArgs x{};
+    EvalKernelArgs g{}; EvalModeArgs x{}; DrilEnvEvaluateArgs gf{};
     const bool modes = persistent && normalizing(h);                              // a frozen normaliser: evaluate_modes_kernel; otherwise evaluate_kernel as ever
-    if (persistent) {
+    if (fused) { int rc = eval_fused_args(h, gf, o->deterministic, K, 0, nullptr); if (rc) return rc; }   // (the kernel opens every launch with its own observe)
+    else if (persistent) {
         eval_kernel_args(h, g, o->deterministic); g.r.T = K; g.acct = acct;       // (after the seed above: env_seed0 is the one the reset used)
         if (modes) eval_mode_norm(h, x, raw);
     } else if (normalizing(h) || h->pn.on) { int rc = observe_dev(h, true); if (rc) return rc; }   // observations = observe(env), :88
@@ -2353,7 +2424,13 @@ int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent,
     long long steps = 0; unsigned int seen = 0; int32_t launches = 0;
     while (seen < (unsigned int)n_eval) {
         if (steps >= max_steps) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_evaluate_agent_device: no episode finishes");
-        if (persistent) { g.step0 = (int32_t)steps; HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream, modes ? &x : nullptr)); steps += K; launches += 1; }
+        if (fused) {
+            HIPCHK(h, h->env.launch_evaluate(gf, h->stream));
+            hipLaunchKernelGGL(eval_account_rows_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, (int32_t)steps, (int32_t)K, gf.r.rew, gf.r.flags);
+            HIPCHK(h, hipGetLastError());
+            steps += K; launches += 2;
+        }
+        else if (persistent) { g.step0 = (int32_t)steps; HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream, modes ? &x : nullptr)); steps += K; launches += 1; }
         else for (int k = 0; k < K; ++k) { int rc = eval_step_granular(h, acct, (int32_t)(++steps), (o->deterministic ? 1 : 0), raw, &launches); if (rc) return rc; }
         HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2362,7 +2439,7 @@ int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent,
     events.resize((size_t)std::min<long long>(seen, cap));
     HIPCHK(h, hipMemcpyAsync(events.data(), h->eval_events, events.size() * sizeof(SacEvalEvent), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (info) { info->path = persistent ? 1 : 0; info->launches = launches; info->steps_enqueued = (int32_t)steps; info->events = (int32_t)seen; }
+    if (info) { info->path = fused ? 2 : persistent ? 1 : 0; info->launches = launches; info->steps_enqueued = (int32_t)steps; info->events = (int32_t)seen; }
     return DRIL_OK;
 }
 }  // namespace
@@ -2378,10 +2455,11 @@ DRIL_EXPORT int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_o
     if (info) std::memset(info, 0, sizeof(*info));
     { int rc = ensure_wimg(h); if (rc) return rc; }
     const bool persistent = !o->force_step_granular && eval_persistent_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);
+    const bool fused = !o->force_step_granular && eval_fused_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);   // path 2: a plug-in's own evaluation kernel (never both)
     const bool raw = (h->env.module && h->pn.on) || h->mon_cur_ret != nullptr;         // dril_evaluate_agent's rule: raw returns under the monitor (and under a plug-in's normaliser)
-    EvalKeep keep; eval_keep_list(h, persistent, keep);
-    const int K = eval_poll_steps(h, o, persistent);
-    const long long cap = eval_event_capacity(o->n_eval_episodes, h->cfg.n_envs, persistent ? K : 1);   // (path 0: one launch per env step)
+    EvalKeep keep; eval_keep_list(h, persistent || fused, keep);                       // (path 2 writes the envs and scratch of its own: the per-step arrays are not touched)
+    const int K = eval_poll_steps(h, o, persistent || fused);
+    const long long cap = eval_event_capacity(o->n_eval_episodes, h->cfg.n_envs, (persistent || fused) ? K : 1);   // (path 0: one launch per env step)
     { int rc = eval_buffers(h, keep, cap); if (rc) return rc; }
     // the evaluation runs on the handle's own envs: what training would continue from is set aside here and put back below, on every path
     keep.seed0 = h->env.seed0; keep.ready = h->env.ready; keep.obs_par = h->obs_par; keep.ret_par = h->ret_par; keep.norm_training = h->cfg.norm_training;
@@ -2390,7 +2468,7 @@ DRIL_EXPORT int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_o
     h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false): the statistics in force, frozen; `returns` stands still
     h->mon_cur_ret = nullptr;                                                          // evaluation episodes do not enter the training env's MonitorWrapperEnv: its launches are not made
     std::vector<SacEvalEvent> events;
-    const int rc = eval_device_run(h, o, persistent, raw, K, cap, events, info);
+    const int rc = eval_device_run(h, o, persistent, fused, raw, K, cap, events, info);
     const std::string msg = h->err;
     h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
     h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
@@ -2510,6 +2588,37 @@ int traj_persistent_run(dril_handle* h, const dril_traj_options* o, const TrajRu
     *steps_out = steps; *launches_out = launches;
     return DRIL_OK;
 }
+// path 2: a plug-in's evaluation kernel in its recording mode, K env steps per launch, and ONE launch of the per-trajectory rule over the rows it leaves.  The shadow
+// envs are those of the step-granular form, stepped inside the kernel by the recorded env's own lane.  The last launch is shortened: no step past Tcap is ever enqueued
+int traj_fused_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int32_t* steps_out, int32_t* launches_out) {
+    const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap;
+    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
+    r.shadow.seed0 = h->env.seed0;
+    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :10
+    h->env.ready = true;
+    HIPCHK(h, hipMemsetAsync(r.shadow.step_count, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(r.shadow.episode, 0, (size_t)M * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(r.shadow.gstep, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
+    int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, kEvalPollPersistent));
+    K = (int)std::max<long long>(1, std::min<long long>(std::min(K, Tcap), kEvalMaxLaunchEvents / std::max(1, E)));
+    DrilEnvEvaluateArgs g{};
+    { int rc = eval_fused_args(h, g, o->deterministic, K, M, &r.shadow); if (rc) return rc; }
+    const int64_t n = (int64_t)M * std::max(r.rec.D, r.rec.W);
+    int32_t steps = 0, launches = 0; unsigned int seen = 0;
+    while (seen < (unsigned int)M) {
+        if (steps >= Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
+        g.r.T = std::min(K, Tcap - steps);
+        HIPCHK(h, h->env.launch_evaluate(g, h->stream));
+        const TrajRows rows{g.r.T, E, g.r.rew, g.r.flags, g.rec_obs0, (const uint32_t*)g.rec_act, g.rec_obs};
+        hipLaunchKernelGGL(traj_record_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.rec, r.maps, rows, steps);
+        HIPCHK(h, hipGetLastError());
+        steps += g.r.T; launches += 2;
+        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        seen = *h->eval_counter_host;
+    }
+    *steps_out = steps; *launches_out = launches;
+    return DRIL_OK;
+}
 // the step-granular form: traj_step per env step, a look at the finished-counter every K steps
 int traj_stepwise_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int32_t* steps_out, int32_t* launches_out) {
     const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap;
@@ -2535,10 +2644,10 @@ int traj_stepwise_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, in
     *steps_out = steps; *launches_out = launches;
     return DRIL_OK;
 }
-int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, bool persistent, float* observations, void* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
+int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int path, float* observations, void* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
     const int M = r.rec.M, Tcap = r.rec.Tcap; const size_t D = (size_t)r.rec.D, W = (size_t)r.rec.W;
     int32_t steps = 0, launches = 0;
-    { int rc = persistent ? traj_persistent_run(h, o, r, &steps, &launches) : traj_stepwise_run(h, o, r, &steps, &launches); if (rc) return rc; }
+    { int rc = path == 2 ? traj_fused_run(h, o, r, &steps, &launches) : path == 1 ? traj_persistent_run(h, o, r, &steps, &launches) : traj_stepwise_run(h, o, r, &steps, &launches); if (rc) return rc; }
     // copy-out: lengths first, then rows 0..longest only, reordered into the caller's per-trajectory layout on the host
     HIPCHK(h, hipMemcpyAsync(lengths, r.rec.length, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(end_flags, r.rec.end_flags, (size_t)M, hipMemcpyDeviceToHost, h->stream));
@@ -2554,7 +2663,7 @@ int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, bool
     HIPCHK(h, hipMemcpyAsync(rew_tm.data(), r.rec.rew, rew_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     traj_reorder(M, (int64_t)D, (int64_t)W, Tcap, lengths, obs_tm.data(), act_tm.data(), rew_tm.data(), observations, (uint32_t*)actions, rewards);
-    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = persistent ? 1 : 0; }
+    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = path; }
     return DRIL_OK;
 }
 }  // namespace
@@ -2584,7 +2693,8 @@ DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_tr
     { int rc = ensure_wimg(h); if (rc) return rc; }
     // the opt-in one-launch form where evaluate_modes_kernel applies; elsewhere (generic shapes, plug-ins, DRIL_FORCE_STEPWISE) the request falls back silently
     const bool persistent = o->reserved[DRIL_TRAJ_OPT_PERSISTENT] != 0 && eval_persistent_applies(h, true);
-    EvalKeep keep; eval_keep_list(h, persistent, keep);
+    const bool fused = eval_fused_applies(h, o->reserved[DRIL_TRAJ_OPT_PERSISTENT] != 0);   // path 2: the recording mode of a plug-in's own evaluation kernel (never both)
+    EvalKeep keep; eval_keep_list(h, persistent || fused, keep);
     { int rc = eval_buffers(h, keep, 0); if (rc) return rc; }
     TrajRun run{};
     { int rc = traj_prepare(h, o, Tcap, run); if (rc) return rc; }
@@ -2594,7 +2704,7 @@ DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_tr
     { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
     h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false), :12
     h->mon_cur_ret = nullptr;                                                          // the recorded episodes do not enter the training env's MonitorWrapperEnv
-    const int rc = traj_device_run(h, o, run, persistent, observations, actions, rewards, lengths, end_flags, info);
+    const int rc = traj_device_run(h, o, run, fused ? 2 : persistent ? 1 : 0, observations, actions, rewards, lengths, end_flags, info);
     const std::string msg = h->err;
     h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
     h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;

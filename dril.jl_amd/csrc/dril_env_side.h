@@ -14,6 +14,7 @@
 #include "../../include/dril_hip.h"
 #include "../../include/device/dril_env_plugin.h"   // DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with
 #include "../../include/device/dril_env_rollout.h"  // DrilEnvRolloutDesc / DrilEnvRolloutArgs: the fused rollout a plug-in may carry
+#include "../../include/device/dril_env_evaluate.h" // DrilEnvEvaluateDesc / DrilEnvEvaluateArgs: the fused evaluation a plug-in may carry
 #include "dril_internal.h"
 
 namespace dril {
@@ -92,6 +93,27 @@ inline EnvModuleRollout find_module_rollout(hipModule_t mod) {
     if (!r.reason.empty()) r.fn = r.fn_scaled = nullptr;
     return r;
 }
+// The fused evaluation of a loaded, checked plug-in (DRIL_ENV_PLUGIN_EVALUATE, include/device/dril_env_evaluate.h), looked up like the rollout: two kernels and a
+// descriptor, all optional; `reason` is empty when the kernel can be launched.  Nothing of the module is launched.
+struct EnvModuleEvaluate { hipFunction_t fn = nullptr, fn_scaled = nullptr; DrilEnvEvaluateDesc desc{}; bool has_desc = false; std::string reason; };
+inline EnvModuleEvaluate find_module_evaluate(hipModule_t mod) {
+    EnvModuleEvaluate r;
+    r.fn = env_module_optional(mod, "dril_env_plugin_evaluate"); r.fn_scaled = env_module_optional(mod, "dril_env_plugin_evaluate_scaled");
+    hipDeviceptr_t dptr = nullptr; size_t bytes = 0;
+    if (hipModuleGetGlobal(&dptr, &bytes, mod, "dril_env_plugin_evaluate_desc") != hipSuccess) { (void)hipGetLastError(); dptr = nullptr; }
+    const std::string rebuild = ": rebuild the plug-in against this library's include/device/dril_env_evaluate.h";
+    if (!r.fn || !dptr) { r.fn = r.fn_scaled = nullptr; r.reason = "the code object has no fused evaluation kernel (dril_env_plugin_evaluate): add #include \"device/dril_env_evaluate.h\" and DRIL_ENV_PLUGIN_EVALUATE(Env) to the plug-in's source and rebuild"; return r; }
+    if (bytes != sizeof(DrilEnvEvaluateDesc) || hipMemcpy(&r.desc, dptr, sizeof(r.desc), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError(); r.fn = r.fn_scaled = nullptr;
+        r.reason = "dril_env_plugin_evaluate_desc is " + std::to_string(bytes) + " bytes, this library reads " + std::to_string(sizeof(DrilEnvEvaluateDesc)) + rebuild; return r; }
+    r.has_desc = true;
+    if (r.desc.abi_version != DRIL_ENV_EVALUATE_ABI) r.reason = "fused evaluation ABI " + std::to_string(r.desc.abi_version) + ", this library speaks " + std::to_string(DRIL_ENV_EVALUATE_ABI) + rebuild;
+    else if (r.desc.args_size != sizeof(DrilEnvEvaluateArgs)) r.reason = "the fused evaluation's argument block is " + std::to_string(r.desc.args_size) + " bytes, this library passes " + std::to_string(sizeof(DrilEnvEvaluateArgs)) + rebuild;
+    else if (r.desc.tile < 1 || r.desc.threads < r.desc.tile || r.desc.threads > 1024 || r.desc.max_width < 1) r.reason = "the fused evaluation's descriptor is out of range (tile " + std::to_string(r.desc.tile) + ", threads " + std::to_string(r.desc.threads) + ", max width " + std::to_string(r.desc.max_width) + ")";
+    else if ((r.desc.has_scaled != 0) != (r.fn_scaled != nullptr)) r.reason = std::string("the fused evaluation's descriptor says has_scaled = ") + std::to_string(r.desc.has_scaled) + ", but dril_env_plugin_evaluate_scaled is " + (r.fn_scaled ? "present" : "absent");
+    if (!r.reason.empty()) r.fn = r.fn_scaled = nullptr;
+    return r;
+}
 // The declared observation space of a loaded, checked plug-in: dril_env_plugin_obs_space (one workgroup) writes low[D] | high[D] into a buffer sized from the
 // descriptor.  *declared = 0 and no launch when the code object has no such kernel (built before the observation space existed, or the env declares none).
 inline int read_module_obs_space(hipModule_t mod, const DrilEnvPluginDesc& d, std::vector<float>& low, std::vector<float>& high, bool* declared, std::string& msg) {
@@ -137,6 +159,7 @@ struct DeviceEnvs {
     std::vector<float> obs_low, obs_high; bool obs_declared = false, scaling = false;
     hipFunction_t mod_observe_scaled = nullptr, mod_step_scaled = nullptr;
     EnvModuleRollout rollout;   // the plug-in's fused rollout, when its code object carries one (PPO handles: dril_rollout_fused_enable)
+    EnvModuleEvaluate evaluate; // the plug-in's fused evaluation, when its code object carries one (PPO handles: path 2 of the evaluation / trajectory verbs)
 
     // what the envs are; for DRIL_ENV_MODULE also the plug-in: loaded, its descriptor kept, episode_len 0 replaced by the descriptor's, its three kernels found.
     // Makes `device` current when it loads; on failure nothing is held and msg says why.
@@ -151,7 +174,7 @@ struct DeviceEnvs {
             if (e != hipSuccess) { msg = std::string("hipModuleGetFunction(") + names[i] + "): " + hipGetErrorString(e); release(); return DRIL_ERR_HIP; }
         }
         mod_observe_scaled = env_module_optional(module, "dril_env_plugin_observe_scaled"); mod_step_scaled = env_module_optional(module, "dril_env_plugin_step_scaled");
-        rollout = find_module_rollout(module);
+        rollout = find_module_rollout(module); evaluate = find_module_evaluate(module);
         const int rs = read_module_obs_space(module, desc, obs_low, obs_high, &obs_declared, msg);
         if (rs) release();
         return rs;
@@ -220,6 +243,13 @@ struct DeviceEnvs {
         if (!f) return hipErrorInvalidDeviceFunction;
         void* params[] = {&g};
         return hipModuleLaunchKernel(f, (unsigned)((E + rollout.desc.tile - 1) / rollout.desc.tile), 1, 1, (unsigned)rollout.desc.threads, 1, 1, 0, s, params, nullptr);
+    }
+    // the fused evaluation: ceil(E / tile) workgroups, each takes its envs through the g.r.T steps of the launch
+    hipError_t launch_evaluate(DrilEnvEvaluateArgs g, hipStream_t s) const {
+        const hipFunction_t f = scaling ? evaluate.fn_scaled : evaluate.fn;
+        if (!f) return hipErrorInvalidDeviceFunction;
+        void* params[] = {&g};
+        return hipModuleLaunchKernel(f, (unsigned)((E + evaluate.desc.tile - 1) / evaluate.desc.tile), 1, 1, (unsigned)evaluate.desc.threads, 1, 1, 0, s, params, nullptr);
     }
     hipError_t step(const void* actions, const EnvStepOut& o, const MonitorArgs& mon, hipStream_t s) const {
         if (module) {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/dril_hip.h"              // dril_normalize_config (the one configuration type in here), the DRIL_ERR_* codes
+#include "../../include/device/dril_normalize.h" // normalize_obs: the one definition, shared with the evaluation kernel of a device env plug-in
 
 namespace {
 
@@ -40,10 +41,7 @@ __device__ __forceinline__ void nz_merge_sums(float& mean, float& var, long long
     nz_merge(mean, var, count, (float)bm, (float)bv, n);
 }
 // normalize_obs! (:174-179)
-__device__ __forceinline__ float nz_obs(float v, float mean, float var, float eps, float clip) {
-    v = (v - mean) / sqrtf(var + eps);
-    return fminf(fmaxf(v, -clip), clip);
-}
+__device__ __forceinline__ float nz_obs(float v, float mean, float var, float eps, float clip) { return dril::normalize_obs(v, mean, var, eps, clip); }
 // normalize_rewards! (:188-197): no mean subtraction
 __device__ __forceinline__ float nz_reward(float r, float var, float eps, float clip) {
     r = r / sqrtf(var + eps);

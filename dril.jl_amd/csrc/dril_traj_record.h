@@ -67,27 +67,51 @@ DRIL_TRAJ_HD uint32_t traj_env_action(const TrajMaps& x, int32_t j, uint32_t raw
 // j < W action row t - 1, lane 0 the reward of row t - 1 and, where the trajectory ends here, its length, its flags and the finished-counter.  The episode's end
 // takes precedence over the cut when both fall on step Tcap.  Steps after the trajectory ended (a second episode of a fast env, steps enqueued past the last finish)
 // write nothing.
-DRIL_TRAJ_HD void traj_record_lane(const TrajRec& r, const TrajMaps& x, const TrajStep& s, int32_t t, int32_t m, int32_t j) {
-    if (t == 0) {
-        if (j < r.D) { const float o = s.obs[(int64_t)m * r.D + j]; r.obs[(int64_t)m * r.D + j] = x.obs_low ? unscale_from_unit(o, x.obs_low[j], x.obs_high[j]) : o; }
-        if (j == 0) { r.length[m] = kTrajOpen; r.end_flags[m] = 0; }
-        return;
-    }
-    if (t > r.Tcap || !traj_active(r, t, m)) return;
-    const bool term = s.term[m] != 0, trunc = s.trunc[m] != 0, done = term || trunc, cut = !done && t >= r.Tcap, last = done || cut;
+// `length`: the trajectory's open / closed state as this lane holds it — kTrajOpen while it records.  obs_m / act_m: env m's D observations / W action words of this step.
+DRIL_TRAJ_HD void traj_record_lane_step(const TrajRec& r, const TrajMaps& x, int32_t t, int32_t m, int32_t j, const float* obs_m, const uint32_t* act_m, float rew,
+                                        bool term, bool trunc, int32_t& length) {
+    if (t > r.Tcap || length != kTrajOpen) return;
+    const bool done = term || trunc, cut = !done && t >= r.Tcap, last = done || cut;
     const int64_t row = (int64_t)t * r.M + m, prev = row - r.M;
     if (j < r.D) {
-        const float o = s.obs[(int64_t)m * r.D + j];
+        const float o = obs_m[j];
         r.obs[row * r.D + j] = (x.obs_low && (!last || x.final_original)) ? unscale_from_unit(o, x.obs_low[j], x.obs_high[j]) : o;
     }
-    if (j < r.W) r.act[prev * r.W + j] = traj_env_action(x, j, ((const uint32_t*)s.act)[(int64_t)m * r.W + j]);
+    if (j < r.W) r.act[prev * r.W + j] = traj_env_action(x, j, act_m[j]);
+    if (last) length = t;
     if (j == 0) {
-        r.rew[prev] = s.rew[m];
+        r.rew[prev] = rew;
         if (last) {
             r.length[m] = t;
             r.end_flags[m] = (uint8_t)((term ? kTrajTerminated : 0) | (trunc ? kTrajTruncated : 0) | (cut ? kTrajCut : 0));
             traj_count_finished(r.finished);
         }
+    }
+}
+// row 0: the original observation after the initial observe, and the trajectory opened
+DRIL_TRAJ_HD void traj_record_lane_open(const TrajRec& r, const TrajMaps& x, int32_t m, int32_t j, const float* obs_m) {
+    if (j < r.D) r.obs[(int64_t)m * r.D + j] = x.obs_low ? unscale_from_unit(obs_m[j], x.obs_low[j], x.obs_high[j]) : obs_m[j];
+    if (j == 0) { r.length[m] = kTrajOpen; r.end_flags[m] = 0; }
+}
+// one launch per env step: the open / closed state is r.length[m], read once per lane
+DRIL_TRAJ_HD void traj_record_lane(const TrajRec& r, const TrajMaps& x, const TrajStep& s, int32_t t, int32_t m, int32_t j) {
+    if (t == 0) { traj_record_lane_open(r, x, m, j, s.obs + (int64_t)m * r.D); return; }
+    if (t > r.Tcap || !traj_active(r, t, m)) return;
+    int32_t length = kTrajOpen;
+    traj_record_lane_step(r, x, t, m, j, s.obs + (int64_t)m * r.D, (const uint32_t*)s.act + (int64_t)m * r.W, s.rew[m], s.term[m] != 0, s.trunc[m] != 0, length);
+}
+// K env steps in ONE launch (the evaluation kernel of a device env plug-in leaves K rows: device/dril_env_evaluate.h): every lane of env m walks the rows in step order
+// with the open / closed state in a register of its own, loaded from r.length[m] as the launch before left it — inside the launch the lanes of an env have no order
+// among themselves, so none of them depends on what lane 0 writes meanwhile.  rew / flags: rows of n_envs entries (flag byte: bit0 terminated, bit1 truncated); obs0: (M x D) the
+// observation before the launch's first step (read where t0 == 0: row 0); act (K x M x W) and obs (K x M x D): the raw actions and the post-step, pre-reset observations
+struct TrajRows { int32_t K, n_envs; const float* rew; const uint8_t* flags; const float* obs0; const uint32_t* act; const float* obs; };
+DRIL_TRAJ_HD void traj_record_lane_rows(const TrajRec& r, const TrajMaps& x, const TrajRows& s, int32_t t0, int32_t m, int32_t j) {
+    int32_t length = kTrajOpen;
+    if (t0 == 0) traj_record_lane_open(r, x, m, j, s.obs0 + (int64_t)m * r.D);
+    else if (r.length[m] <= t0) length = r.length[m];                              // closed before this launch; a value > t0 is "open", or lane 0's finalisation in THIS launch, which this lane reaches by itself
+    for (int32_t k = 0; k < s.K; ++k) {
+        const int64_t e = (int64_t)k * s.n_envs + m, i = (int64_t)k * r.M + m;
+        traj_record_lane_step(r, x, t0 + k + 1, m, j, s.obs + i * r.D, s.act + i * r.W, s.rew[e], (s.flags[e] & 1) != 0, (s.flags[e] & 2) != 0, length);
     }
 }
 // The same rule with ONE lane holding env m, for a kernel that keeps the env in registers over the steps of a launch (evaluate_modes_kernel, dril_kernels.hip): the lane

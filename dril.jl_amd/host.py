@@ -573,6 +573,13 @@ class Handle:
         return dict(available=bool(info.available), enabled=bool(info.enabled), tile=info.tile, threads=info.threads, max_width=info.max_width,
                     last_collection_launches=info.last_collection_launches, reason=info.reason.decode())
 
+    def evaluate_fused_info(self) -> dict:
+        """dril_evaluate_fused_info: available / tile / threads / max_width / reason — whether persistent=True of the evaluation and trajectory verbs would run the
+        plug-in's own evaluation kernel (path 2; a code object built with DRIL_ENV_PLUGIN_EVALUATE, include/device/dril_env_evaluate.h) on this handle"""
+        info = capi.DrilFusedEvaluateInfo()
+        self._chk(self.lib.dril_evaluate_fused_info(self._h, C.byref(info)))
+        return dict(available=bool(info.available), tile=info.tile, threads=info.threads, max_width=info.max_width, reason=info.reason.decode())
+
     def scaling_enable(self, on: bool = True):
         """dril_scaling_enable: ScalingWrapperEnv around every env of a plug-in handle; between create and the first env_reset"""
         self._chk(self.lib.dril_scaling_enable(self._h, int(bool(on))))
@@ -863,7 +870,8 @@ class Handle:
         -> (stats dict, episode_rewards, episode_lengths, info dict).  seed None: the env seed in force; env e is reset with seed + its global index.
         persistent=True asks for the persistent evaluate kernel wherever it can run, cfg.norm_* handles included (the frozen statistics are an argument of the
         kernel); the default keeps such handles on the step-granular launches.  force_step_granular wins.
-        info: path (what ran: 0 step-granular launches, 1 the persistent evaluate kernel), launches, steps_enqueued, events."""
+        info: path (what ran: 0 step-granular launches, 1 the persistent evaluate kernel, 2 a plug-in's fused evaluation kernel — persistent=True on a plug-in handle
+        whose code object carries one, evaluate_fused_info), launches, steps_enqueued, events."""
         o = capi.DrilEvalOptions()
         self._chk(self.lib.dril_eval_options_default(C.byref(o)))
         o.n_eval_episodes, o.deterministic, o.poll_steps, o.force_step_granular = int(n_eval_episodes), int(deterministic), int(poll_steps), int(force_step_granular)
@@ -890,7 +898,8 @@ class Handle:
         the last observation is the terminal state as the wrapper delivers it (final_original: unscaled too).  end_flags: capi.TRAJ_TERMINATED | TRAJ_TRUNCATED |
         TRAJ_MAX_STEPS.  persistent=True asks for the one-launch form (the recording inside the persistent evaluate kernel, K steps per launch, no shadow envs)
         where that kernel can run; elsewhere the request falls back silently.  The recording is the same, bit for bit.
-        info: capacity, steps_enqueued, launches, longest, cut_by_max_steps, path (what ran: 0 step-granular launches, 1 the persistent kernel)."""
+        info: capacity, steps_enqueued, launches, longest, cut_by_max_steps, path (what ran: 0 step-granular launches, 1 the persistent kernel, 2 the recording mode
+        of a plug-in's fused evaluation kernel)."""
         o = capi.DrilTrajOptions()
         self._chk(self.lib.dril_traj_options_default(C.byref(o)))
         o.n_trajectories, o.max_steps, o.deterministic = int(n_trajectories), 0 if max_steps is None else int(max_steps), int(deterministic)

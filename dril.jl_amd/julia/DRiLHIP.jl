@@ -233,6 +233,14 @@ function rollout_fused_info(env::DeviceParallelEnv)
     return (available = i32[1] != 0, enabled = i32[2] != 0, tile = Int(i32[3]), threads = Int(i32[4]), max_width = Int(i32[5]),
         last_collection_launches = Int(reinterpret(Int64, buf[25:32])[1]), reason = String(buf[33:(32 + something(findfirst(==(0x00), buf[33:end]), 257) - 1)]))
 end
+"dril_evaluate_fused_info of the env's handle: (available, tile, threads, max_width, reason) — whether `persistent = true` of evaluate_agent / collect_trajectory would run the plug-in's own evaluation kernel (path 2)"
+function evaluate_fused_info(env::DeviceParallelEnv)
+    buf = zeros(UInt8, 272)                                      # dril_fused_evaluate_info: 4 x Int32, char[256]
+    check(ccall((:dril_evaluate_fused_info, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), handle(env), buf), handle(env))
+    i32 = reinterpret(Int32, buf[1:16])
+    return (available = i32[1] != 0, tile = Int(i32[2]), threads = Int(i32[3]), max_width = Int(i32[4]),
+        reason = String(buf[17:(16 + something(findfirst(==(0x00), buf[17:end]), 257) - 1)]))
+end
 handle(env::DeviceParallelEnv) = env.handle == C_NULL ? bind!(env, PPO(; n_steps = 1, batch_size = env.n_envs)) : env.handle
 
 # ---- env verbs with host copy-out: generic DRiL callers (evaluate_agent, check_env, wrappers) keep working ----

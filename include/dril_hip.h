@@ -252,6 +252,19 @@ typedef struct dril_fused_rollout_info {
 } dril_fused_rollout_info;
 int32_t dril_rollout_fused_enable(dril_handle* h, int32_t on);
 int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rollout_info* out);
+/* The FUSED EVALUATION of a device env plug-in (include/device/dril_env_evaluate.h): a code object built with DRIL_ENV_PLUGIN_EVALUATE(Env) holds a second, optional
+ * kernel with the env inlined — K env steps of observe, (frozen) normalisation, actor forward, mode or draw and the transition in ONE launch, a workgroup per tile
+ * of envs, no grid barrier — with a descriptor and an ABI number of its own (the rollout's are untouched).  It is path 2 of dril_evaluate_agent_device and
+ * dril_collect_trajectory_device, taken where the options ask for the persistent form (reserved[DRIL_EVAL_OPT_PERSISTENT] / reserved[DRIL_TRAJ_OPT_PERSISTENT] = 1);
+ * nothing switches a handle to it.  This verb says whether such a request would be served on this handle, and why not: a handle that is not a plug-in handle; a code
+ * object without the kernel; an evaluation descriptor of another ABI number or argument-block size; a hidden layer or observation wider than the plug-in's compiled
+ * DRIL_ENV_ROLLOUT_MAX_WIDTH; dril_scaling_enable on without the _scaled kernel.  A request on a handle where it is not available runs path 0, never an error. */
+typedef struct dril_fused_evaluate_info {
+    int32_t available;                 /* the code object has a usable evaluation kernel for this handle's net */
+    int32_t tile, threads, max_width;  /* of the plug-in's compile; 0 without an evaluation descriptor */
+    char reason[256];                  /* why it is not available ("" when it is) */
+} dril_fused_evaluate_info;
+int32_t dril_evaluate_fused_info(const dril_handle* h, dril_fused_evaluate_info* out);
 int32_t dril_destroy(dril_handle* h);
 /* message of the last failing call on h (or of the last failing create when h == NULL) */
 const char* dril_last_error(const dril_handle* h);
@@ -542,7 +555,11 @@ int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval_episodes, int32_t det
  * path ran.  Two paths: a persistent evaluate kernel (a wave keeps 32 envs in registers for K steps, the actor's weights in LDS) for the built-in kinds on the
  * fused shapes without a normaliser, and step-granular launches with a small accounting launch for every other device-env handle (generic shapes, cfg.norm_*,
  * plug-ins with or without dril_scaling_enable / dril_normalize_enable / the fused rollout).  On request (reserved[DRIL_EVAL_OPT_PERSISTENT] = 1) a cfg.norm_*
- * handle on a fused shape takes the persistent kernel too: it reads the frozen statistics as an argument and returns the same numbers.
+ * handle on a fused shape takes the persistent kernel too: it reads the frozen statistics as an argument and returns the same numbers.  On the same request a
+ * plug-in handle whose code object carries a usable evaluation kernel (dril_evaluate_fused_info) takes PATH 2: that kernel, K env steps per launch, and one
+ * accounting launch of the library over the K rows of raw rewards and flag bytes it leaves — 2 launches per K env steps, with dril_scaling_enable, with
+ * dril_normalize_enable (frozen statistics read as an argument; raw returns, the rule for plug-ins) and with the monitor on.  Its forward is the fused rollout's plain
+ * f32 FMA chain, path 0's the bf16 x 3-piece contractions: two f32-equivalent arithmetics, so paths 0 and 2 agree like device and oracle do, not to the bit.
  * A normaliser is FROZEN for the call whatever its training flag (set_training(env, false), evaluation of a training env; docs/deviations.md).
  * The call brings its own reset and puts back what it writes, on error paths too: env state, step counts, episode and noise-stream counters, the seed in force,
  * `returns`, the E-sized per-step arrays, the statistics' buffers and parities, and whether the envs count as reset.  The monitor's sums / window / meta are not
@@ -557,12 +574,13 @@ typedef struct dril_eval_options {
     int32_t force_step_granular;         /* 1: never take the persistent kernel (tests, A/B); wins over the request below, as DRIL_FORCE_STEPWISE=1 at create does */
     int32_t reserved[3];                 /* reserved[DRIL_EVAL_OPT_PERSISTENT]: the opt-in request for the persistent kernel.  0 (default): today's rule — the kernel
                                           * where no normaliser is on.  1: the kernel wherever it can run, cfg.norm_obs / cfg.norm_reward handles included: the FROZEN
-                                          * statistics in force are passed to it as an argument and only read.  Same numbers on either path.  Generic shapes, plug-ins and
-                                          * DRIL_ENV_EXTERNAL keep their answers (path 0, or the refusal), never an error because of the request.  The other words: 0 */
+                                          * statistics in force are passed to it as an argument and only read.  Same numbers on either path.  A plug-in handle with a
+                                          * usable evaluation kernel (dril_evaluate_fused_info) takes path 2.  Generic shapes, other plug-ins and DRIL_ENV_EXTERNAL keep
+                                          * their answers (path 0, or the refusal), never an error because of the request.  The other words: 0 */
 } dril_eval_options;
 #define DRIL_EVAL_OPT_PERSISTENT 0       /* index into dril_eval_options.reserved */
 typedef struct dril_eval_info {
-    int32_t path;                        /* what ran: 0 step-granular launches + device accounting, 1 persistent evaluate kernel */
+    int32_t path;                        /* what ran: 0 step-granular launches + device accounting, 1 persistent evaluate kernel, 2 a plug-in's fused evaluation kernel */
     int32_t launches, steps_enqueued, events, reserved[4];   /* launch calls of the loop, env steps enqueued, events the device counted */
 } dril_eval_info;
 int32_t dril_eval_options_default(dril_eval_options* o);   /* 10 episodes, deterministic, evaluation.jl:57-58 */
@@ -580,7 +598,10 @@ int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_options* o, d
  * The call leaves nothing behind: everything dril_evaluate_agent_device sets aside and puts back is set aside and put back here, on error paths too; the monitor's
  * launches are not made and no all-reduce is enqueued (each rank of a data-parallel job records its own envs).
  * Two forms, the same recording bit for bit: step-granular launches with shadow envs (default), and on request (reserved[DRIL_TRAJ_OPT_PERSISTENT] = 1) the
- * recording inside the persistent evaluate kernel, one launch per K env steps, for the built-in kinds on the fused shapes of width 64 / 128 / 256.
+ * recording inside the persistent evaluate kernel, one launch per K env steps, for the built-in kinds on the fused shapes of width 64 / 128 / 256.  A third form
+ * (path 2) serves the same request on a plug-in handle whose code object carries a usable evaluation kernel (dril_evaluate_fused_info): the kernel's recording mode —
+ * the lane of a recorded env takes each step a second time on a shadow env that never resets — and one launch of the library's per-trajectory rule over the K rows:
+ * 2 launches per K env steps, no step past Tcap enqueued.  Against path 0 it agrees as two f32-equivalent arithmetics do (see dril_evaluate_agent_device).
  * DRIL_ERR_NOT_INITIALISED: null handle.  DRIL_ERR_INVALID_ARG: null options or output array, n_trajectories outside 1..n_envs, negative max_steps or poll_steps, a
  * recording whose device arrays exceed 1 GiB.  DRIL_ERR_UNSUPPORTED: DRIL_ENV_EXTERNAL (the envs live with the caller). */
 typedef struct dril_traj_options {
@@ -593,12 +614,14 @@ typedef struct dril_traj_options {
     int32_t reserved[5];                 /* reserved[DRIL_TRAJ_OPT_PERSISTENT]: the opt-in request for the one-launch form.  0 (default): the step-granular launches with
                                           * shadow envs.  1: where the persistent evaluate kernel can run (built-in kinds on the fused shapes of width 64 / 128 / 256, with
                                           * or without cfg.norm_*), envs 0..M-1 are recorded inside it, K env steps per launch, no shadow envs — the same recording, bit
-                                          * for bit.  Elsewhere (generic shapes, plug-ins, DRIL_FORCE_STEPWISE) the request falls back silently.  The other words: 0 */
+                                          * for bit.  A plug-in handle with a usable evaluation kernel records through it (path 2).  Elsewhere (generic shapes, other
+                                          * plug-ins, DRIL_FORCE_STEPWISE) the request falls back silently.  The other words: 0 */
 } dril_traj_options;
 #define DRIL_TRAJ_OPT_PERSISTENT 0       /* index into dril_traj_options.reserved */
 typedef struct dril_traj_info {
     int32_t capacity, steps_enqueued, launches, longest, cut_by_max_steps, reserved[3];   /* Tcap, env steps enqueued, launch calls of the loop, max L, trajectories with bit 2;
-                                          * reserved[DRIL_TRAJ_INFO_PATH]: what ran — 0 the step-granular launches, 1 the persistent kernel's recording mode */
+                                          * reserved[DRIL_TRAJ_INFO_PATH]: what ran — 0 the step-granular launches, 1 the persistent kernel's recording mode, 2 the
+                                          * recording mode of a plug-in's fused evaluation kernel */
 } dril_traj_info;
 #define DRIL_TRAJ_INFO_PATH 0            /* index into dril_traj_info.reserved */
 int32_t dril_traj_options_default(dril_traj_options* o);   /* M = 1, deterministic, the rest 0 */

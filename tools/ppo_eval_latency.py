@@ -6,11 +6,12 @@ on its two paths and at several poll intervals K, next to a collection step of t
   Pendulum under cfg.norm_obs / cfg.norm_reward           the same, wrapped: step-granular by default (six launches per env step), the persistent kernel on request
                                                           (persistent = True: the frozen statistics are an argument of the kernel)
   reacher3 plug-in (time limit 100)                       step-granular path only
+  reacher3_eval: the same env with DRIL_ENV_PLUGIN_EVALUATE  path 0 against path 2 (the plug-in's own evaluation kernel) on the same handle in the same process
 E = 64 / 1 024 / 16 384, one process, n_eval = E (for Pendulum / reacher3 exactly one time limit of env steps).  The wall time of the whole call — reset, every
 enqueued step (those past the last counted episode included), the polls, the event copy, the restore of the training envs — is divided by the counted steps
 (stats.n_steps).  The calls are synchronous, so the wall time contains the device time.  Median (min .. max) over the calls after warm-up.
 The collection figure: wall time of dril_collect_rollout (n_steps = 32, drained) / 32.
-usage: python tools/ppo_eval_latency.py [evaluations=20] [env ...]      env: cartpole pendulum pendulum_norm reacher3"""
+usage: python tools/ppo_eval_latency.py [evaluations=20] [env ...]      env: cartpole pendulum pendulum_norm reacher3 reacher3_eval"""
 import sys, time
 from pathlib import Path
 import numpy as np
@@ -21,10 +22,11 @@ import __graft_entry__ as g
 pkg = g.load_package()
 capi = pkg._capi
 R = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-ENVS = sys.argv[2:] or ["cartpole", "pendulum", "pendulum_norm", "reacher3"]
+ENVS = sys.argv[2:] or ["cartpole", "pendulum", "pendulum_norm", "reacher3", "reacher3_eval"]
 WARM, T = 3, 32
 REACHER = ROOT / "examples" / "envs" / "reacher3_plugin.hsaco"
-KIND = {"cartpole": (capi.ENV_CARTPOLE, None), "pendulum": (capi.ENV_PENDULUM, None), "pendulum_norm": (capi.ENV_PENDULUM, None), "reacher3": (capi.ENV_MODULE, REACHER)}
+KIND = {"cartpole": (capi.ENV_CARTPOLE, None), "pendulum": (capi.ENV_PENDULUM, None), "pendulum_norm": (capi.ENV_PENDULUM, None), "reacher3": (capi.ENV_MODULE, REACHER),
+        "reacher3_eval": (capi.ENV_MODULE, REACHER.with_name("reacher3_eval_plugin.hsaco"))}
 K_PERSISTENT = (8, 32, 64, 128, 0)          # candidates of the persistent path (0 = the library's default)
 
 
@@ -67,6 +69,11 @@ def measure(name, E):
             s, steps, info = timed(lambda: h.evaluate_agent_device(E, True, poll_steps=K, persistent=name == "pendulum_norm"))
             print(f"   device, persistent     K = {'default' if not K else K:>7}          {s} us / env step over {steps} steps, {info['steps_enqueued']} enqueued, {info['launches']} launches", flush=True)
             assert info["path"] == 1
+    if name == "reacher3_eval":
+        for K in (8, 32, 0):
+            s, steps, info = timed(lambda: h.evaluate_agent_device(E, True, poll_steps=K, persistent=True))
+            print(f"   device, path 2         K = {'default' if not K else K:>7}          {s} us / env step over {steps} steps, {info['steps_enqueued']} enqueued, {info['launches']} launches", flush=True)
+            assert info["path"] == 2
     h.env_reset(1)
     col = []
     for r in range(5 + WARM):

@@ -7,10 +7,11 @@ write before (dril_env_observe / dril_predict_actions / dril_env_step per step, 
   Pendulum  (time limit 200)                              built-in kind, hidden [64,64]
   Pendulum under cfg.norm_obs / cfg.norm_reward           the same, wrapped (statistics frozen for the call)
   reacher3 plug-in (time limit 100)                       generic kernels; no persistent form (the request falls back)
+  reacher3_eval: the same env with DRIL_ENV_PLUGIN_EVALUATE  path 0 against path 2 (the recording mode of the plug-in's own evaluation kernel) on the same handle
 The wall time of the whole call — reset, every enqueued step, the looks at the counter, the copy-out and reorder, the restore of the training envs — is divided by the
 steps that count: the longest recorded trajectory (the verb), stats.n_steps (the evaluation), the steps taken (the host loop).  Median (min .. max) over the calls
 after warm-up; the host loop is timed over fewer calls (a fifth), it is the slow one.
-usage: python tools/traj_latency.py [calls=20] [env ...]      env: cartpole pendulum pendulum_norm reacher3"""
+usage: python tools/traj_latency.py [calls=20] [env ...]      env: cartpole pendulum pendulum_norm reacher3 reacher3_eval"""
 import sys, time
 from pathlib import Path
 import numpy as np
@@ -21,10 +22,11 @@ import __graft_entry__ as g
 pkg = g.load_package()
 capi = pkg._capi
 R = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-ENVS = sys.argv[2:] or ["cartpole", "pendulum", "pendulum_norm", "reacher3"]
+ENVS = sys.argv[2:] or ["cartpole", "pendulum", "pendulum_norm", "reacher3", "reacher3_eval"]
 WARM, SIZES, E_BASELINES = 3, (64, 1024, 16384), 1024
 REACHER = ROOT / "examples" / "envs" / "reacher3_plugin.hsaco"
-KIND = {"cartpole": (capi.ENV_CARTPOLE, None), "pendulum": (capi.ENV_PENDULUM, None), "pendulum_norm": (capi.ENV_PENDULUM, None), "reacher3": (capi.ENV_MODULE, REACHER)}
+KIND = {"cartpole": (capi.ENV_CARTPOLE, None), "pendulum": (capi.ENV_PENDULUM, None), "pendulum_norm": (capi.ENV_PENDULUM, None), "reacher3": (capi.ENV_MODULE, REACHER),
+        "reacher3_eval": (capi.ENV_MODULE, REACHER.with_name("reacher3_eval_plugin.hsaco"))}
 
 
 def handle_for(name, E):
@@ -72,7 +74,7 @@ def measure(name, E):
                 _, lengths, _, info = h.collect_trajectory_device(M, persistent=persistent)
                 return int(lengths.max()), info
             s, info = timed(verb, R)
-            form = "persistent   " if info["path"] == 1 else "step-granular"
+            form = {0: "step-granular", 1: "persistent   ", 2: "path 2       "}[info["path"]]
             print(f"   dril_collect_trajectory_device  M = {M:5d}  {form}  {s} us / env step over {info['longest']} steps, {info['steps_enqueued']} enqueued, {info['launches']} launches", flush=True)
             if persistent and info["path"] == 0:
                 print("      (no persistent form on this handle: the request fell back)", flush=True)
