@@ -224,6 +224,8 @@ _SIG = {
     "dril_env_module_info_of": (C.c_int32, [_P, C.POINTER(DrilEnvModuleInfo)]),
     "dril_env_module_obs_space": (C.c_int32, [C.c_char_p, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "dril_env_module_obs_space_of": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32)]),
+    "dril_env_module_agents": (C.c_int32, [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "dril_env_module_agents_of": (C.c_int32, [_P, C.POINTER(C.c_int32)]),
     "dril_scaling_enable": (C.c_int32, [_P, C.c_int32]),
     "dril_agent_spaces": (C.c_int32, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     "dril_rollout_fused_enable": (C.c_int32, [_P, C.c_int32]),

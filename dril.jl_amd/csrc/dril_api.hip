@@ -659,6 +659,21 @@ DRIL_EXPORT int32_t dril_env_module_obs_space_of(const dril_handle* h, float* lo
     if (declared) *declared = h->env.obs_declared ? 1 : 0;
     return DRIL_OK;
 }
+DRIL_EXPORT int32_t dril_env_module_agents(const char* code_object_path, int32_t device, int32_t* agents) {
+    if (!agents) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_env_module_agents: null agents");
+    hipModule_t mod = nullptr; DrilEnvPluginDesc d{}; std::string msg;
+    const int rc = load_env_module(code_object_path, device, &mod, &d, msg);
+    if (rc) return fail(nullptr, rc, "dril_env_module_agents: " + msg);
+    (void)hipModuleUnload(mod);
+    *agents = d.agents ? d.agents : 1;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_env_module_agents_of(const dril_handle* h, int32_t* agents) {
+    if (!h || !agents) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle / agents");
+    if (!h->env.module) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_env_module_agents_of: the handle was not created with dril_create_with_env_module");
+    *agents = h->env.agents();
+    return DRIL_OK;
+}
 DRIL_EXPORT int32_t dril_scaling_enable(dril_handle* h, int32_t on) {
     NEED(h);
     std::string msg; const int rc = h->env.set_scaling(on != 0, msg);
@@ -945,13 +960,19 @@ DRIL_EXPORT int32_t dril_env_step(dril_handle* h, const void* actions, float* re
 }
 DRIL_EXPORT int32_t dril_env_get_state(dril_handle* h, float* state, int32_t* step_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_get_state"); if (!state) return fail(h, DRIL_ERR_INVALID_ARG, "null state");
-    HIPCHK(h, hipMemcpyAsync(state, h->env.state, (size_t)h->cfg.n_envs * h->S * 4, hipMemcpyDeviceToHost, h->stream));
+    // a world handle moves its W = n_envs / N states (S floats each, world w at float offset w S); the counters are per row for every handle
+    HIPCHK(h, hipMemcpyAsync(state, h->env.state, (size_t)h->env.n_worlds() * h->S * 4, hipMemcpyDeviceToHost, h->stream));
     if (step_count) HIPCHK(h, hipMemcpyAsync(step_count, h->env.step_count, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
 DRIL_EXPORT int32_t dril_env_set_state(dril_handle* h, const float* state, const int32_t* step_count) {
     NEED(h); NOT_EXTERNAL(h, "dril_env_set_state"); if (!state) return fail(h, DRIL_ERR_INVALID_ARG, "null state");
-    HIPCHK(h, hipMemcpyAsync(h->env.state, state, (size_t)h->cfg.n_envs * h->S * 4, hipMemcpyHostToDevice, h->stream));
+    if (step_count && h->env.is_world()) {                                             // the N rows of a world count the same steps: unequal values are refused, nothing is written
+        const int N = h->env.agents();
+        for (int e = 0; e < h->cfg.n_envs; ++e) if (step_count[e] != step_count[e - e % N])
+            return fail(h, DRIL_ERR_INVALID_ARG, "dril_env_set_state: rows " + std::to_string(e - e % N) + " and " + std::to_string(e) + " belong to one world of " + std::to_string(N) + " agents but are given step counts " + std::to_string(step_count[e - e % N]) + " and " + std::to_string(step_count[e]) + ": the rows of a world share the world's step count");
+    }
+    HIPCHK(h, hipMemcpyAsync(h->env.state, state, (size_t)h->env.n_worlds() * h->S * 4, hipMemcpyHostToDevice, h->stream));
     if (step_count) HIPCHK(h, hipMemcpyAsync(h->env.step_count, step_count, (size_t)h->cfg.n_envs * 4, hipMemcpyHostToDevice, h->stream));
     return sync(h);
 }
@@ -1291,6 +1312,7 @@ int collect_rollout_module_fused(dril_handle* h) {
 // "" when the handle's net fits the plug-in's fused rollout kernel, else why not
 std::string fused_rollout_unavailable(const dril_handle* h) {
     if (!h->env.module) return "the fused rollout is the collection kernel of a device env plug-in (DRIL_ENV_MODULE): the built-in envs collect with the library's own rollout_kernel, host envs (DRIL_ENV_EXTERNAL) step on the host";
+    if (h->env.is_world()) return std::string("env plug-in \"") + h->env.desc.name + "\" is a world of " + std::to_string(h->env.agents()) + " agents: worlds have no fused rollout yet (DRIL_ENV_PLUGIN_ROLLOUT refuses a world at compile time); collect step-granular, which is the default";
     const EnvModuleRollout& r = h->env.rollout;
     if (!r.reason.empty()) return std::string("env plug-in \"") + h->env.desc.name + "\": " + r.reason;
     const int W = r.desc.max_width;
@@ -1303,6 +1325,7 @@ std::string fused_rollout_unavailable(const dril_handle* h) {
 // "" when the handle's net fits the plug-in's fused evaluation kernel (path 2 of the evaluation / trajectory verbs), else why not
 std::string fused_evaluate_unavailable(const dril_handle* h) {
     if (!h->env.module) return "the fused evaluation is a kernel of a device env plug-in (DRIL_ENV_MODULE): the built-in envs evaluate with the library's own evaluate_kernel, host envs (DRIL_ENV_EXTERNAL) step on the host";
+    if (h->env.is_world()) return std::string("env plug-in \"") + h->env.desc.name + "\" is a world of " + std::to_string(h->env.agents()) + " agents: worlds have no fused evaluation yet (DRIL_ENV_PLUGIN_EVALUATE refuses a world at compile time); the evaluation and trajectory verbs run step-granular (path 0)";
     const EnvModuleEvaluate& r = h->env.evaluate;
     if (!r.reason.empty()) return std::string("env plug-in \"") + h->env.desc.name + "\": " + r.reason;
     const int W = r.desc.max_width;
@@ -2685,6 +2708,8 @@ DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_tr
     NEED(h); NOT_EXTERNAL(h, "dril_collect_trajectory_device");
     if (!o || !observations || !actions || !rewards || !lengths || !end_flags || o->n_trajectories < 1 || o->n_trajectories > h->cfg.n_envs || o->max_steps < 0 || o->poll_steps < 0)
         return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: options and the five output arrays != NULL, 1 <= n_trajectories <= n_envs, max_steps >= 0, poll_steps >= 0");
+    if (h->env.is_world() && o->n_trajectories % h->env.agents() != 0)
+        return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: the env is a world of " + std::to_string(h->env.agents()) + " agents and whole worlds are recorded: n_trajectories " + std::to_string(o->n_trajectories) + " is not a multiple of " + std::to_string(h->env.agents()));
     if (info) std::memset(info, 0, sizeof(*info));
     const int32_t Tcap = traj_capacity(o->max_steps, h->env.episode_len);
     const int64_t bytes = traj_bytes(o->n_trajectories, Tcap, h->D, h->discrete ? 1 : h->A);

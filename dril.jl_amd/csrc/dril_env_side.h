@@ -13,6 +13,7 @@
 
 #include "../../include/dril_hip.h"
 #include "../../include/device/dril_env_plugin.h"   // DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with
+#include "../../include/device/dril_env_world.h"    // the limits of a world (N agents per state): descriptor word `agents`
 #include "../../include/device/dril_env_rollout.h"  // DrilEnvRolloutDesc / DrilEnvRolloutArgs: the fused rollout a plug-in may carry
 #include "../../include/device/dril_env_evaluate.h" // DrilEnvEvaluateDesc / DrilEnvEvaluateArgs: the fused evaluation a plug-in may carry
 #include "dril_internal.h"
@@ -32,8 +33,12 @@ inline int check_code_object_path(const char* path, std::string& msg) {
 inline int check_plugin_desc(const DrilEnvPluginDesc& d, std::string& msg) {
     if (d.abi_version != DRIL_ENV_PLUGIN_ABI) { msg = "env plug-in ABI " + std::to_string(d.abi_version) + ", this library speaks " + std::to_string(DRIL_ENV_PLUGIN_ABI) + ": recompile the plug-in against this library's include/device/dril_env_plugin.h"; return DRIL_ERR_UNSUPPORTED; }
     if (d.args_size != sizeof(DrilEnvPluginArgs)) { msg = "env plug-in kernel argument block is " + std::to_string(d.args_size) + " bytes, this library passes " + std::to_string(sizeof(DrilEnvPluginArgs)) + ": recompile the plug-in against this library's include/device/dril_env_plugin.h"; return DRIL_ERR_UNSUPPORTED; }
-    if (d.S < 1 || d.S > DRIL_ENV_PLUGIN_MAX_S || d.D < 1 || d.D > DRIL_ENV_PLUGIN_MAX_D || d.A < 1 || d.A > DRIL_ENV_PLUGIN_MAX_A || d.episode_len < 1) {
-        msg = "env plug-in descriptor out of range: S " + std::to_string(d.S) + " (1..64), D " + std::to_string(d.D) + " (1..1024), A " + std::to_string(d.A) + " (1..64), episode_len " + std::to_string(d.episode_len) + " (>= 1)"; return DRIL_ERR_UNSUPPORTED; }
+    // agents: 0 = one env per row (DRIL_ENV_PLUGIN), 2..16 = a world of that many agents per state (DRIL_ENV_PLUGIN_WORLD); a world's S is per world, up to 256
+    const bool world = d.agents != 0;
+    if (world && (d.agents < DRIL_ENV_WORLD_MIN_N || d.agents > DRIL_ENV_WORLD_MAX_N)) { msg = "env plug-in descriptor out of range: agents " + std::to_string(d.agents) + " (0 for an env, 2..16 for a world)"; return DRIL_ERR_UNSUPPORTED; }
+    const int max_s = world ? DRIL_ENV_WORLD_MAX_S : DRIL_ENV_PLUGIN_MAX_S;
+    if (d.S < 1 || d.S > max_s || d.D < 1 || d.D > DRIL_ENV_PLUGIN_MAX_D || d.A < 1 || d.A > DRIL_ENV_PLUGIN_MAX_A || d.episode_len < 1) {
+        msg = "env plug-in descriptor out of range: S " + std::to_string(d.S) + (world ? " (1..256 per world)" : " (1..64)") + ", D " + std::to_string(d.D) + " (1..1024), A " + std::to_string(d.A) + " (1..64), episode_len " + std::to_string(d.episode_len) + " (>= 1)"; return DRIL_ERR_UNSUPPORTED; }
     return DRIL_OK;
 }
 // path checks -> hipModuleLoad -> descriptor out and checked; on success the caller owns *mod (nothing of the module has been launched)
@@ -162,11 +167,16 @@ struct DeviceEnvs {
     EnvModuleEvaluate evaluate; // the plug-in's fused evaluation, when its code object carries one (PPO handles: path 2 of the evaluation / trajectory verbs)
 
     // what the envs are; for DRIL_ENV_MODULE also the plug-in: loaded, its descriptor kept, episode_len 0 replaced by the descriptor's, its three kernels found.
-    // Makes `device` current when it loads; on failure nothing is held and msg says why.
-    int open(int kind_, int n_envs, int episode_len_, int fixed_len_, int action_start_, const char* module_path, int device, std::string& msg) {
+    // Makes `device` current when it loads; on failure nothing is held and msg says why.  no_worlds: null, or why this kind of handle takes no world (then a world is
+    // refused with DRIL_ERR_UNSUPPORTED before its row count is looked at).
+    int open(int kind_, int n_envs, int episode_len_, int fixed_len_, int action_start_, const char* module_path, int device, std::string& msg, const char* no_worlds = nullptr) {
         kind = kind_; E = n_envs; episode_len = episode_len_; fixed_len = fixed_len_; action_start = action_start_;
         if (kind != DRIL_ENV_MODULE) return DRIL_OK;
         const int rc = load_env_module(module_path, device, &module, &desc, msg); if (rc) return rc;
+        if (desc.agents && no_worlds) { msg = std::string("env plug-in \"") + desc.name + "\" is a world of " + std::to_string(desc.agents) + " agents: " + no_worlds; release(); return DRIL_ERR_UNSUPPORTED; }
+        if (desc.agents && E % desc.agents != 0) {
+            msg = std::string("env plug-in \"") + desc.name + "\" is a world of " + std::to_string(desc.agents) + " agents (one row each): n_envs " + std::to_string(E) + " is not a multiple of " + std::to_string(desc.agents) + " (per rank, under data parallelism)";
+            release(); return DRIL_ERR_INVALID_ARG; }
         if (episode_len == 0) episode_len = desc.episode_len;
         const char* names[3] = {"dril_env_plugin_reset", "dril_env_plugin_observe", "dril_env_plugin_step"}; hipFunction_t* fns[3] = {&mod_reset, &mod_observe, &mod_step};
         for (int i = 0; i < 3; ++i) {
@@ -179,6 +189,12 @@ struct DeviceEnvs {
         if (rs) release();
         return rs;
     }
+    // a world (dril_env_world.h): `agents()` rows share one state of desc.S floats; a classic plug-in and a built-in kind have one agent per env.  The state array stays
+    // E x S floats for either (N times what a world needs): world w lies at float offset w S, and every snapshot / restore / prefix copy of E x S (or M x S for the
+    // first M rows) floats holds the worlds it has to hold
+    int agents() const { return (module && desc.agents) ? desc.agents : 1; }
+    bool is_world() const { return module && desc.agents != 0; }
+    int n_worlds() const { return E / agents(); }
     // ScalingWrapperEnv on / off.  Legal on a plug-in handle whose envs have not been reset yet (between create and the first reset!): observations handed out
     // before would change their meaning under the caller.  Every refusal says what to do instead.
     int set_scaling(bool on, std::string& msg) {
@@ -186,6 +202,7 @@ struct DeviceEnvs {
         if (ready) { msg = "ScalingWrapperEnv is chosen between create and the first env reset (observations already handed out would change their meaning): create a new handle"; return DRIL_ERR_INVALID_ARG; }
         if (on) {
             const std::string who = std::string("env plug-in \"") + desc.name + "\"";
+            if (desc.agents) { msg = who + " is a world of " + std::to_string(desc.agents) + " agents: a world declares no observation space and carries no _scaled kernels (ScalingWrapperEnv on worlds is not built yet); scale observations and actions inside the world's own observe / step"; return DRIL_ERR_UNSUPPORTED; }
             if (desc.discrete) { msg = who + " has a Discrete action space: ScalingWrapperEnv needs Box observation and action spaces (scalingWrapperEnv.jl:22)"; return DRIL_ERR_UNSUPPORTED; }
             if (!obs_declared) { msg = who + " declares no observation space: add static constexpr float obs_low[D], obs_high[D] to the env and rebuild the code object with this library's include/device/dril_env_plugin.h"; return DRIL_ERR_UNSUPPORTED; }
             auto bad = [](float lo, float hi) { return !(std::isfinite(lo) && std::isfinite(hi) && lo < hi); };

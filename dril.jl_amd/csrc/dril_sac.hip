@@ -2060,7 +2060,8 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     if (cfg->device < 0 || cfg->device >= ndev) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "device ordinal out of range");
     dril_sac_handle* h = new dril_sac_handle(); h->cfg = *cfg;
     {   // a plug-in's descriptor gives the spaces and the bounds: it is loaded here, before anything is sized (dril_sac_destroy unloads it on every failing path below)
-        std::string msg; int rcm = h->env.open(cfg->env_kind, cfg->n_envs, cfg->episode_len, /*fixed_len=*/0, /*action_start=*/0, module_path, cfg->device, msg);
+        std::string msg; int rcm = h->env.open(cfg->env_kind, cfg->n_envs, cfg->episode_len, /*fixed_len=*/0, /*action_start=*/0, module_path, cfg->device, msg,
+                                          "SAC steps one env per row; a world trains with PPO (dril_create_with_env_module)");
         if (!rcm && is_module) rcm = check_sac_plugin(h->env.desc, msg);
         if (rcm) { h->env.release(); delete h; return sfail(nullptr, rcm, "dril_sac_create_with_env_module: " + msg); }
         h->cfg.episode_len = h->env.episode_len;

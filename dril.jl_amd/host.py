@@ -398,8 +398,9 @@ def _module_info_dict(info) -> dict:
 
 
 def describe_env_module(code_object_path, device: int = 0) -> dict:
-    """dril_env_module_describe + dril_env_module_obs_space: what a device env plug-in's code object says about itself (spaces, bounds, time limit, name;
-    `obs_low` / `obs_high` and `obs_declared`: the observation space the env declares, -inf / +inf and False when it declares none)."""
+    """dril_env_module_describe + dril_env_module_obs_space + dril_env_module_agents: what a device env plug-in's code object says about itself (spaces, bounds, time
+    limit, name; `obs_low` / `obs_high` and `obs_declared`: the observation space the env declares, -inf / +inf and False when it declares none; `agents`: agents per
+    world, 1 for a classic plug-in)."""
     lib = capi.load_library()
     info = capi.DrilEnvModuleInfo()
     rc = lib.dril_env_module_describe(os.fsencode(code_object_path), device, C.byref(info))
@@ -411,6 +412,11 @@ def describe_env_module(code_object_path, device: int = 0) -> dict:
     if rc != capi.OK:
         raise DrilError(rc, (lib.dril_last_error(None) or b"").decode())
     d.update(obs_low=lo, obs_high=hi, obs_declared=bool(decl.value))
+    agents = C.c_int32()
+    rc = lib.dril_env_module_agents(os.fsencode(code_object_path), device, C.byref(agents))
+    if rc != capi.OK:
+        raise DrilError(rc, (lib.dril_last_error(None) or b"").decode())
+    d.update(agents=agents.value)               # N for a world (include/device/dril_env_world.h: N agents share a state, one row each), 1 for a classic plug-in
     return d
 
 
@@ -561,6 +567,12 @@ class Handle:
         self._chk(self.lib.dril_env_module_obs_space_of(self._h, self._p(lo), self._p(hi), C.byref(decl)))
         return dict(low=lo, high=hi, declared=bool(decl.value))
 
+    def env_module_agents(self) -> int:
+        """dril_env_module_agents_of: agents per world of a plug-in handle (rows w N .. w N + N - 1 are world w); 1 for a classic plug-in"""
+        n = C.c_int32()
+        self._chk(self.lib.dril_env_module_agents_of(self._h, C.byref(n)))
+        return n.value
+
     def rollout_fused_enable(self, on: bool = True):
         """dril_rollout_fused_enable: collections of a plug-in handle in ONE launch of the plug-in's own rollout kernel (a code object built with
         DRIL_ENV_PLUGIN_ROLLOUT, include/device/dril_env_rollout.h); legal at any time between collections"""
@@ -609,7 +621,8 @@ class Handle:
 
     def env_get_state(self):
         S = self.env_module_info()["state_dim"] if self.cfg.env_kind == capi.ENV_MODULE else 4 if self.cfg.env_kind in (capi.ENV_CARTPOLE, capi.ENV_ACROBOT) else 2      # CartPole / Acrobot (theta1, theta2, dtheta1, dtheta2); (x, x_dot, theta, theta_dot); Pendulum (theta, theta_dot); MountainCar (position, velocity)
-        st = np.empty((self.E, S), np.float32)
+        W = self.E // self.env_module_agents() if self.cfg.env_kind == capi.ENV_MODULE else self.E     # a world handle: one state per world, (W, S); counters per row
+        st = np.empty((W, S), np.float32)
         sc = np.empty(self.E, np.int32)
         self._chk(self.lib.dril_env_get_state(self._h, self._p(st), self._p(sc)))
         return st, sc
@@ -617,6 +630,10 @@ class Handle:
     def env_set_state(self, st: np.ndarray, sc: Optional[np.ndarray] = None):
         st = np.ascontiguousarray(st, np.float32)
         sc = None if sc is None else np.ascontiguousarray(sc, np.int32)
+        if self.cfg.env_kind == capi.ENV_MODULE:                       # (W, S) for a world handle, (E, S) otherwise; step counts per row
+            W = self.E // self.env_module_agents()
+            if st.size != W * self.env_module_info()["state_dim"] or (sc is not None and sc.size != self.E):
+                raise ValueError(f"env_set_state: state of {st.size} floats / {0 if sc is None else sc.size} step counts for {W} states and {self.E} rows")
         self._chk(self.lib.dril_env_set_state(self._h, self._p(st), self._p(sc)))
 
     def monitor_stats(self):
@@ -1140,12 +1157,22 @@ class DeviceModuleEnv(DeviceParallelEnv):
     bind's key.  `scale_observation / unscale_observation / unscale_action` convert host arrays with the declared bounds.
 
     `fused_rollout=True` makes every PPO collection ONE launch of the plug-in's own rollout kernel (dril_rollout_fused_enable) — the code object must be built with
-    DRIL_ENV_PLUGIN_ROLLOUT (include/device/dril_env_rollout.h); not together with `normalize`.  The library's refusal says what is missing.  Part of bind's key."""
+    DRIL_ENV_PLUGIN_ROLLOUT (include/device/dril_env_rollout.h); not together with `normalize`.  The library's refusal says what is missing.  Part of bind's key.
+
+    A code object built with DRIL_ENV_PLUGIN_WORLD (include/device/dril_env_world.h) holds a multi-agent WORLD, the device form of MultiAgentParallelEnv: `n_envs` counts
+    rows, `agents_per_world` of them share one state and one joint step (row w N + i is agent i of world w), `n_worlds = n_envs / agents_per_world`; for a classic
+    plug-in the two numbers are 1 and n_envs.  One shared policy acts for every row; `scaling` and `fused_rollout` are refused by the library for a world, and
+    collect_trajectory records whole worlds (n_trajectories a multiple of agents_per_world)."""
 
     def __init__(self, code_object_path, n_envs: int, *, seed: int = 42, device: int = 0, max_steps: Optional[int] = None, action_start: int = 1,
                  fixed_length_episodes: bool = False, rank: int = 0, world_size: int = 1, profile_events: bool = False, normalize: Optional[dict] = None,
                  scaling: bool = False, fused_rollout: bool = False):
         info = describe_env_module(code_object_path, device)
+        # a world (include/device/dril_env_world.h): agents_per_world rows share one state and one joint step; row w N + i is agent i of world w
+        self.agents_per_world = int(info["agents"])
+        if int(n_envs) % self.agents_per_world != 0:
+            raise ValueError(f"{info['name']} is a world of {self.agents_per_world} agents (one row each): n_envs {n_envs} is not a multiple of {self.agents_per_world}")
+        self.n_worlds = int(n_envs) // self.agents_per_world
         env = ModuleEnv(os.fspath(code_object_path), info, int(max_steps) if max_steps else info["episode_len"], action_start, scaling=bool(scaling))
         super().__init__(env, n_envs, seed=seed, fixed_length_episodes=fixed_length_episodes, device=device, rank=rank, world_size=world_size,
                          profile_events=profile_events)

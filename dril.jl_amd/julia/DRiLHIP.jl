@@ -126,16 +126,29 @@ function describe_env_module(path::AbstractString, device::Integer = 0)
     name = String(buf[537:(536 + something(findfirst(==(0x00), buf[537:end]), 65) - 1)])
     D = Int(i32[2]); obs_low = zeros(Float32, D); obs_high = zeros(Float32, D); declared = Ref{Int32}(0)    # the observation space the env declares (-Inf / Inf and false: none)
     check(ccall((:dril_env_module_obs_space, LIB[]), Int32, (Cstring, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}), path, Int32(device), obs_low, obs_high, declared))
+    agents = Ref{Int32}(1)                                                                                  # a world (include/device/dril_env_world.h): agents per state; 1 for a classic plug-in
+    check(ccall((:dril_env_module_agents, LIB[]), Int32, (Cstring, Int32, Ref{Int32}), path, Int32(device), agents))
     return (path = String(path), state_dim = Int(i32[1]), obs_dim = D, action_dim = A, discrete = i32[4] != 0, episode_len = Int(i32[5]), low = low, high = high, name = name,
-        obs_low = obs_low, obs_high = obs_high, obs_declared = declared[] != 0, scaling = false)
+        obs_low = obs_low, obs_high = obs_high, obs_declared = declared[] != 0, scaling = false, agents_per_world = Int(agents[]))
 end
 "`OnDeviceModule(path, n_envs; normalize = nothing, ...)`: n_envs copies of the env in the code object `path`, stepped on the device by the env's own kernels (no host env in the loop); `normalize = (; ...)` = NormalizeWrapperEnv, for PPO and SAC alike; `scaling = true` = ScalingWrapperEnv around every env (the plug-in's own _scaled kernels, spaces Box(-1, 1); inside NormalizeWrapperEnv); `fused_rollout = true` = PPO collections in one launch of the plug-in's own rollout kernel (a code object built with DRIL_ENV_PLUGIN_ROLLOUT; dril_rollout_fused_enable; not together with `normalize`)"
 function OnDeviceModule(path::AbstractString, n_envs::Integer; max_steps::Union{Nothing, Integer} = nothing, seed::Integer = 42, device::Integer = 0, monitor_window::Integer = 0,
         normalize::Union{Nothing, NamedTuple} = nothing, scaling::Bool = false, fused_rollout::Bool = false)      # NormalizeWrapperEnv keywords: honoured by the SAC handle (dril_sac_normalize_enable) and by the PPO handle (dril_normalize_enable, applied in bind!)
     info = describe_env_module(path, device)
+    n_envs % info.agents_per_world == 0 || error("$(info.name) is a world of $(info.agents_per_world) agents (one row each): n_envs $n_envs is not a multiple of $(info.agents_per_world)")
     env = DeviceParallelEnv(:Module, n_envs; max_steps = something(max_steps, info.episode_len), seed = seed, device = device, monitor_window = monitor_window, normalize = normalize)
     MODULE_ENVS[env] = merge(info, (scaling = scaling, fused_rollout = fused_rollout))     # applied to every handle of this env right after create (dril_scaling_enable / dril_sac_scaling_enable), where the library refuses what it cannot scale
     return env
+end
+"agents per world of a device env plug-in (a code object built with DRIL_ENV_PLUGIN_WORLD: row w N + i is agent i of world w); 1 for every other env"
+agents_per_world(env::DeviceParallelEnv) = env.kind === :Module ? MODULE_ENVS[env].agents_per_world : 1
+"worlds of a device env: number_of_envs(env) / agents_per_world(env)"
+n_worlds(env::DeviceParallelEnv) = env.n_envs ÷ agents_per_world(env)
+"dril_env_module_agents_of: agents per world as the bound handle reports them"
+function agents_per_world_of_handle(env::DeviceParallelEnv)
+    n = Ref{Int32}(1)
+    check(ccall((:dril_env_module_agents_of, LIB[]), Int32, (Ptr{Cvoid}, Ref{Int32}), env.handle, n), env.handle)
+    return Int(n[])
 end
 is_discrete(env) = env.kind === :Module ? MODULE_ENVS[env].discrete : env.kind === :CartPole || env.kind === :MountainCar || env.kind === :Acrobot
 module_box(n::Integer) = Box(fill(-1.0f0, n), fill(1.0f0, n))      # the agent-facing spaces of ScalingWrapperEnv
@@ -567,7 +580,7 @@ include("DRiLHIP_host_envs.jl")     # OnDevice(env::AbstractParallelEnv): host e
 include("DRiLHIP_extras.jl")        # normalisation statistics, evaluate_agent
 include("DRiLHIP_sac.jl")           # SAC
 
-export DeviceParallelEnv, OnDevice, OnDeviceModule, describe_env_module
+export DeviceParallelEnv, OnDevice, OnDeviceModule, describe_env_module, agents_per_world, n_worlds
 export DevicePolicy, extract_device_policy, extract_device_policy_sac
 
 end # module

@@ -127,7 +127,8 @@ template <class Env, bool scaled> inline void dril_env_evaluate_host(const DrilE
     }
 }
 #define DRIL_ENV_EVALUATE_ENTRY(name) __attribute__((visibility("default"))) void dril_env_plugin_host_##name(const DrilEnvEvaluateArgs* g)
-#define DRIL_ENV_EVALUATE_RUN(Env, scaled) dril_env_evaluate_host<Env, scaled>(*g)
+#define DRIL_ENV_EVALUATE_IMPL dril_env_evaluate_host
+#define DRIL_ENV_EVALUATE_RUN(Env, scaled) DrilEnvEvaluateBody<Env, scaled>::run(*g)
 #else
 // ---- the kernel ----------------------------------------------------------------------------------------------------------------------------------------------
 // the K steps of the workgroup's tile; P: the parameter vector the forward reads — global memory, or its copy in LDS
@@ -168,8 +169,13 @@ template <class Env, bool scaled> __device__ inline void dril_env_evaluate_run(c
     } else dril_env_evaluate_steps<Env, scaled>(g, g.r.params, p0, p1);
 }
 #define DRIL_ENV_EVALUATE_ENTRY(name) __global__ void __launch_bounds__(DRIL_ENV_ROLLOUT_THREADS) dril_env_plugin_##name(DrilEnvEvaluateArgs g)
-#define DRIL_ENV_EVALUATE_RUN(Env, scaled) dril_env_evaluate_run<Env, scaled>(g)
+#define DRIL_ENV_EVALUATE_IMPL dril_env_evaluate_run
+#define DRIL_ENV_EVALUATE_RUN(Env, scaled) DrilEnvEvaluateBody<Env, scaled>::run(g)
 #endif
+
+// the body of an entry point; empty for a world (DrilEnvRolloutBody)
+template <class Env, bool scaled, bool world = DrilEnvIsWorld<Env>::value> struct DrilEnvEvaluateBody { DRIL_ENV_FN static void run(const DrilEnvEvaluateArgs& g) { DRIL_ENV_EVALUATE_IMPL<Env, scaled>(g); } };
+template <class Env, bool scaled> struct DrilEnvEvaluateBody<Env, scaled, true> { DRIL_ENV_FN static void run(const DrilEnvEvaluateArgs&) {} };
 
 // the optional _scaled entry point: declared here, DEFINED as a friend of the specialisation that fits the env (the mechanism of DrilEnvRolloutScaledEntry)
 #if defined(DRIL_ENV_PLUGIN_HOST)

@@ -26,6 +26,9 @@
 // Box(-1, 1), the affine maps of device/dril_scaling.h applied inside the one launch.  An env without obs_low / obs_high emits exactly the descriptor and the three
 // kernels it always did; the descriptor, the argument block and DRIL_ENV_PLUGIN_ABI are unchanged by any of this.
 //
+// Agents that share ONE state (they collide, cooperate or compete) do not fit "one env, one thread": device/dril_env_world.h is the second, optional form for them —
+// a WORLD of N agents with one joint step, compiled into the same symbols and seen by the library as N rows per world (DRIL_ENV_PLUGIN_WORLD).
+//
 // Everything else — action adapters, step counters, truncation at the time limit, the BUF_FLAGS byte, terminal observation, MonitorWrapperEnv's sums, auto-reset —
 // is the LIBRARY's transition (EnvCursor / env_advance / env_end_episode of dril_device.h) and is written once, here, in dril_env_plugin_step_one.
 //
@@ -56,7 +59,9 @@
 struct DrilEnvPluginDesc {
     uint32_t abi_version;            // DRIL_ENV_PLUGIN_ABI the plug-in was compiled against
     uint32_t args_size;              // sizeof(DrilEnvPluginArgs) the plug-in was compiled against
-    int32_t S, D, A, discrete, episode_len, reserved;
+    int32_t S, D, A, discrete, episode_len;
+    int32_t agents;                  // 0: one env per row (DRIL_ENV_PLUGIN); N in 2..16: a WORLD of N agents per state (DRIL_ENV_PLUGIN_WORLD, dril_env_world.h).  The word was
+                                     // `reserved` and is 0 in every code object built before worlds existed, which keeps its meaning: DRIL_ENV_PLUGIN_ABI stays 1
     float action_low[DRIL_ENV_PLUGIN_MAX_A], action_high[DRIL_ENV_PLUGIN_MAX_A];   // entries 0..A-1 (continuous); low >= high in a dimension = no clamp there
     char name[64];
 };

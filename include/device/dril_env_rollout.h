@@ -71,7 +71,12 @@ struct DrilEnvRolloutArgs {
     float* ep_ret; int32_t* ep_len;      // (T x E): MonitorWrapperEnv's finished episodes (null = no monitor)
 };
 
+// a world (device/dril_env_world.h: N agents per state) is told from an env by its N
+template <class Env, class = void> struct DrilEnvIsWorld { static constexpr bool value = false; };
+template <class Env> struct DrilEnvIsWorld<Env, decltype((void)Env::N, void())> { static constexpr bool value = true; };
+
 template <class Env> struct DrilEnvRolloutCheck {
+    static_assert(!DrilEnvIsWorld<Env>::value, "DRIL_ENV_PLUGIN_ROLLOUT / DRIL_ENV_PLUGIN_EVALUATE: a world (DRIL_ENV_PLUGIN_WORLD) has no fused rollout or evaluation yet: leave the macro out, the library collects and evaluates a world step-granular");
     static_assert(DRIL_ENV_ROLLOUT_TILE >= 4 && DRIL_ENV_ROLLOUT_TILE % 4 == 0 && DRIL_ENV_ROLLOUT_TILE <= DRIL_ENV_ROLLOUT_THREADS, "DRIL_ENV_PLUGIN_ROLLOUT: DRIL_ENV_ROLLOUT_TILE must be a multiple of 4 in 4..256");
     static_assert(Env::D <= DRIL_ENV_ROLLOUT_MAX_WIDTH && Env::A <= DRIL_ENV_ROLLOUT_MAX_WIDTH, "DRIL_ENV_PLUGIN_ROLLOUT: D and A must fit DRIL_ENV_ROLLOUT_MAX_WIDTH");
     static_assert(8 * DRIL_ENV_ROLLOUT_MAX_WIDTH * DRIL_ENV_ROLLOUT_TILE + 4 * DRIL_ENV_ROLLOUT_STAGE_FLOATS + 1024 <= 160 * 1024, "DRIL_ENV_PLUGIN_ROLLOUT: the two activation panels (8 x DRIL_ENV_ROLLOUT_MAX_WIDTH x DRIL_ENV_ROLLOUT_TILE bytes) and the staged parameters (4 x DRIL_ENV_ROLLOUT_STAGE_FLOATS bytes) must fit the 160 KB of LDS of a gfx950 CU");
@@ -189,7 +194,8 @@ template <class Env, bool scaled> inline void dril_env_rollout_host(const DrilEn
     }
 }
 #define DRIL_ENV_ROLLOUT_ENTRY(name) __attribute__((visibility("default"))) void dril_env_plugin_host_##name(const DrilEnvRolloutArgs* g)
-#define DRIL_ENV_ROLLOUT_RUN(Env, scaled) dril_env_rollout_host<Env, scaled>(*g)
+#define DRIL_ENV_ROLLOUT_IMPL dril_env_rollout_host
+#define DRIL_ENV_ROLLOUT_RUN(Env, scaled) DrilEnvRolloutBody<Env, scaled>::run(*g)
 #define DRIL_ENV_ROLLOUT_DESC_QUAL
 #else
 // ---- the kernel ----------------------------------------------------------------------------------------------------------------------------------------------
@@ -307,9 +313,14 @@ template <class Env, bool scaled> __device__ inline void dril_env_rollout_run(co
     } else dril_env_rollout_steps<Env, scaled>(g, g.params, p0, p1, values, &any_truncated);
 }
 #define DRIL_ENV_ROLLOUT_ENTRY(name) __global__ void __launch_bounds__(DRIL_ENV_ROLLOUT_THREADS) dril_env_plugin_##name(DrilEnvRolloutArgs g)
-#define DRIL_ENV_ROLLOUT_RUN(Env, scaled) dril_env_rollout_run<Env, scaled>(g)
+#define DRIL_ENV_ROLLOUT_IMPL dril_env_rollout_run
+#define DRIL_ENV_ROLLOUT_RUN(Env, scaled) DrilEnvRolloutBody<Env, scaled>::run(g)
 #define DRIL_ENV_ROLLOUT_DESC_QUAL __device__
 #endif
+
+// the body of an entry point; for a world it is empty, so that DrilEnvRolloutCheck's static_assert is the one error of such a compile
+template <class Env, bool scaled, bool world = DrilEnvIsWorld<Env>::value> struct DrilEnvRolloutBody { DRIL_ENV_FN static void run(const DrilEnvRolloutArgs& g) { DRIL_ENV_ROLLOUT_IMPL<Env, scaled>(g); } };
+template <class Env, bool scaled> struct DrilEnvRolloutBody<Env, scaled, true> { DRIL_ENV_FN static void run(const DrilEnvRolloutArgs&) {} };
 
 // the optional _scaled entry point: declared here, DEFINED as a friend of the specialisation that fits the env (the mechanism of DrilEnvPluginScaledEntries)
 #if defined(DRIL_ENV_PLUGIN_HOST)

@@ -192,7 +192,7 @@ int32_t dril_config_default(dril_config* cfg, int32_t env_kind);
 int32_t dril_create(const dril_config* cfg, dril_handle** out);
 /* the same for cfg->env_kind == DRIL_ENV_MODULE: code_object_path names a gfx950 code object built from include/device/dril_env_plugin.h (a plain ELF or a
  * clang-offload-bundle).  A null path, an unreadable file and a file that is neither are DRIL_ERR_INVALID_ARG before any HIP call; then the module is loaded, its
- * descriptor copied out and checked (plug-in ABI number, size of the kernel argument block, S 1..64, D 1..1024, A 1..64, time limit) and its three kernels looked
+ * descriptor copied out and checked (plug-in ABI number, size of the kernel argument block, S 1..64 (a world: agents 2..16, S 1..256), D 1..1024, A 1..64, time limit) and its three kernels looked
  * up: a mismatch is DRIL_ERR_UNSUPPORTED with a message, before anything of the module is launched.  cfg->episode_len == 0 takes the descriptor's time limit;
  * Box bounds per dimension come from the descriptor (ClampAdapter).  The module is unloaded by dril_destroy and on every failing path of this call. */
 int32_t dril_create_with_env_module(const dril_config* cfg, const char* code_object_path, dril_handle** out);
@@ -214,6 +214,19 @@ int32_t dril_env_module_info_of(const dril_handle* h, dril_env_module_info* out)
  * env's own space of a live handle, whether ScalingWrapperEnv is on or not (DRIL_ERR_UNSUPPORTED for a handle of another env kind). */
 int32_t dril_env_module_obs_space(const char* code_object_path, int32_t device, float* low, float* high, int32_t* declared);
 int32_t dril_env_module_obs_space_of(const dril_handle* h, float* low, float* high, int32_t* declared);
+/* WORLDS (include/device/dril_env_world.h, DRIL_ENV_PLUGIN_WORLD): a code object whose descriptor says agents = N in 2..16 holds a multi-agent world — N agents, one
+ * shared state of state_dim floats (up to 256) and one joint step; the device form of MultiAgentParallelEnv (multiAgentParallelEnv.jl).  The library sees agent i of
+ * world w as ROW w N + i, and every verb works per row as for a classic plug-in: n_envs counts rows and must be a multiple of N (per rank), else
+ * dril_create_with_env_module returns DRIL_ERR_INVALID_ARG.  World w is seeded seed0 + w N (the global row index of its agent 0); action noise stays keyed by row.
+ * *agents is N for a world and 1 for a classic plug-in; dril_env_module_info keeps its layout (state_dim is the world's, obs_dim / action_dim are per agent).
+ * On a world handle: the env state array stays n_envs x state_dim floats on the device (N times what the worlds need), world w at float offset w state_dim;
+ * dril_env_get_state / dril_env_set_state move the W = n_envs / N world states (W x state_dim floats) and the per-row step counts, and dril_env_set_state refuses
+ * step counts that differ between the rows of one world (DRIL_ERR_INVALID_ARG).  dril_collect_trajectory_device records whole worlds: n_trajectories must be a multiple
+ * of N.  DRIL_ERR_UNSUPPORTED with a message, before anything is launched: dril_scaling_enable, dril_rollout_fused_enable, dril_sac_create_with_env_module;
+ * dril_evaluate_fused_info answers available = 0 (evaluation and trajectories run on path 0).  The checks and statuses of the path form are those of
+ * dril_env_module_describe; the _of form is DRIL_ERR_UNSUPPORTED for a handle of another env kind. */
+int32_t dril_env_module_agents(const char* code_object_path, int32_t device, int32_t* agents);
+int32_t dril_env_module_agents_of(const dril_handle* h, int32_t* agents);
 /* ScalingWrapperEnv(env) (scalingWrapperEnv.jl) around every env of a device env plug-in handle: on != 0 makes the env side launch the plug-in's
  * dril_env_plugin_observe_scaled / dril_env_plugin_step_scaled kernels where it launched observe / step — no launch is added per env step.  The agent-facing
  * spaces become Box(-1, 1): raw actions are clamped to [-1, 1] and unscaled into the env's own bounds, every observation the env side hands out (observe, the next
@@ -223,7 +236,8 @@ int32_t dril_env_module_obs_space_of(const dril_handle* h, float* low, float* hi
  * LEGAL between create and the first dril_env_reset of the handle only: afterwards it is DRIL_ERR_INVALID_ARG and nothing changes (observations already handed
  * out would change their meaning).  DRIL_ERR_UNSUPPORTED, with a message that says what to do, for: a handle that is not a plug-in handle (the built-in scaled
  * kinds stay the way to scale a built-in env; a host env is wrapped on the host), a Discrete plug-in, a plug-in that declares no observation space, an
- * observation or action dimension whose bounds are not finite with low < high (the first such dimension is named), a code object without the two kernels.
+ * observation or action dimension whose bounds are not finite with low < high (the first such dimension is named), a code object without the two kernels,
+ * a world.
  * dril_env_module_info_of keeps reporting the env's own action bounds; dril_agent_spaces reports what the agent sees. */
 int32_t dril_scaling_enable(dril_handle* h, int32_t on);
 /* the spaces the agent of a plug-in handle sees: obs_low / obs_high (obs_dim floats) and action_low / action_high (action_dim floats; untouched for a Discrete
@@ -305,7 +319,7 @@ int32_t dril_env_observe(dril_handle* h, float* host_obs, int32_t update_stats);
 int32_t dril_env_step(dril_handle* h, const void* host_actions, float* rewards, uint8_t* terminated,
                       uint8_t* truncated, float* terminal_obs);
 /* raw simulator state: CartPole (x, x_dot, theta, theta_dot), Pendulum (theta, theta_dot), + step counter */
-int32_t dril_env_get_state(dril_handle* h, float* state /* S x E */, int32_t* step_count /* E */);
+int32_t dril_env_get_state(dril_handle* h, float* state /* S x E; a world handle: S x W, W = E / agents */, int32_t* step_count /* E */);
 int32_t dril_env_set_state(dril_handle* h, const float* state, const int32_t* step_count);
 /* RunningMeanStd fields, normalizeWrapperEnv.jl:8-19 (save/load :261-297) */
 int32_t dril_norm_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count,
