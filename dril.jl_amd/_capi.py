@@ -64,6 +64,14 @@ class DrilF32Fallback(C.Structure):
                 ("latch_updates_left", C.c_int32), ("forward_exact_f32", C.c_int32), ("max_abs_w2", C.c_float), ("reserved", C.c_int32)]
 
 
+class DrilPopulationInfo(C.Structure):
+    """struct dril_population_info (include/dril_hip.h)"""
+    _fields_ = [("members", C.c_int32), ("cap", C.c_int32), ("last_rollout_launches", C.c_int32), ("last_update_launches", C.c_int32),
+                ("last_solo_rollouts", C.c_int32), ("last_solo_updates", C.c_int32),
+                ("total_rollout_launches", C.c_int64), ("total_update_launches", C.c_int64), ("total_solo_rollouts", C.c_int64), ("total_solo_updates", C.c_int64),
+                ("last_launches_per_iteration", C.c_double), ("last_rollout_ms", C.c_double), ("last_update_ms", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
 class DrilEvalStats(C.Structure):
     """struct dril_eval_stats, include/dril_hip.h"""
     _fields_ = [("mean_reward", C.c_double), ("std_reward", C.c_double), ("mean_length", C.c_double), ("std_length", C.c_double),
@@ -305,6 +313,13 @@ _SIG = {
     "dril_trajectory_capacity": (C.c_int32, [_P, C.POINTER(DrilTrajOptions), C.POINTER(C.c_int32)]),
     "dril_collect_trajectory_device": (C.c_int32, [_P, C.POINTER(DrilTrajOptions), _P, _P, _P, _P, _P, C.POINTER(DrilTrajInfo)]),
     "dril_train": (C.c_int32, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
+    "dril_population_join": (C.c_int32, [C.POINTER(_P), C.c_int32, C.POINTER(_P)]),
+    "dril_population_destroy": (C.c_int32, [_P]),
+    "dril_population_last_error": (C.c_char_p, [_P]),
+    "dril_population_collect_rollout": (C.c_int32, [_P, _P]),
+    "dril_population_ppo_update": (C.c_int32, [_P, _P]),
+    "dril_population_train": (C.c_int32, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
+    "dril_population_info": (C.c_int32, [_P, C.POINTER(DrilPopulationInfo)]),
     "dril_comm_unique_id": (C.c_int32, [_P]),
     "dril_comm_init": (C.c_int32, [_P, _P]),
     "dril_comm_ranks": (C.c_int32, [_P]),

@@ -155,6 +155,7 @@ struct dril_handle {
     int ext_mon_window = 0; int64_t xw_added[3] = {0, 0, 0}, xw_allocs = 0; float* ext_pred_obs = nullptr; int64_t ext_pred_obs_cap = 0;
     void* comm = nullptr;
     LoopGroup* loop = nullptr;   // debug loopback communicator (dril_debug_comm_loopback)
+    dril_population* pop = nullptr;   // the population the handle is a member of (dril_population_join): dril_destroy waits for dril_population_destroy
     int64_t allreduce_calls = 0;
     float* retry_snap = nullptr; bool no_f32_retry = false; int64_t f32_retries = 0;   // ppo_update: state before the update (for the exact-f32 redo of an update that left f16's range); DRIL_NO_F32_RETRY; how often it happened
     // the redo's bookkeeping (dril_f32_fallback_info): used_f16 = an f16-piece kernel ran in the current update (sticky over its optimiser steps — the LAST step's kernel says nothing
@@ -852,6 +853,7 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
 DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     if (h) (void)hipSetDevice(h->cfg.device);
     if (!h) return DRIL_OK;
+    if (h->pop) { h->err = "dril_destroy: the handle is a member of a population: dril_population_destroy first (the members stay alive and usable)"; return DRIL_ERR_INVALID_ARG; }
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     if (h->loop) {                                                   // the last handle to leave frees the group
@@ -1361,10 +1363,25 @@ int collect_rollout_module_norm(dril_handle* h) {
     return monitor_collect_rollout(h);
 }
 
+// a collection that is ONE launch of the fused rollout kernel of a built-in kind (generic nets have no fused rollout kernel, wrapped envs step through the wrapper's kernels)
+bool rollout_fused_applies(const dril_handle* h) { return !(normalizing(h) || h->force_stepwise || h->generic); }
+// the argument block of that launch, read from the handle as it stands (collect_rollout, and a population for each of its members)
+RolloutArgs rollout_args(const dril_handle* h) {
+    RolloutArgs a{};
+    a.params = h->params; a.state = h->env.state; a.step_count = h->env.step_count; a.episode = h->env.episode; a.gstep = h->env.gstep;
+    a.obs = h->obs; a.act = h->act; a.rew = h->rew; a.logp = h->logp; a.val = h->val; a.boot = h->boot; a.flags = h->flags; a.last_values = h->last_values;
+    a.noise = h->noise_set ? h->noise_dev : nullptr;
+    a.E = h->env.E; a.T = h->cfg.n_steps; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len;
+    a.action_start = h->env.action_start; a.log_std_off = h->log_std_off; a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic;
+    a.exact_f32 = fwd_exact(h) ? 1 : 0;
+    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = a.exact_f32 ? h->w2a_critic : (const float*)h->w2pf_critic;
+    a.mon_cur_ret = h->mon_cur_ret; a.mon_cur_len = h->mon_cur_len; a.ep_ret = h->ep_ret; a.ep_len = h->ep_len;
+    return a;
+}
 int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
     if (!h->env.ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset");
     { int rcw = ensure_wimg(h); if (rcw) return rcw; }
-    if (normalizing(h) || h->force_stepwise || h->generic) {            // generic nets have no fused rollout kernel: step-granular launches
+    if (!rollout_fused_applies(h)) {                                    // step-granular launches
         const auto t0s = std::chrono::steady_clock::now();
         if (fps) HIPCHK(h, hipStreamSynchronize(h->stream));
         prof_begin(h, DRIL_K_ROLLOUT);
@@ -1379,15 +1396,7 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
         rcs = compute_gae(h); if (rcs) return rcs;
         return do_sync ? sync(h) : DRIL_OK;
     }
-    RolloutArgs a{};
-    a.params = h->params; a.state = h->env.state; a.step_count = h->env.step_count; a.episode = h->env.episode; a.gstep = h->env.gstep;
-    a.obs = h->obs; a.act = h->act; a.rew = h->rew; a.logp = h->logp; a.val = h->val; a.boot = h->boot; a.flags = h->flags; a.last_values = h->last_values;
-    a.noise = h->noise_set ? h->noise_dev : nullptr;
-    a.E = h->env.E; a.T = h->cfg.n_steps; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len;
-    a.action_start = h->env.action_start; a.log_std_off = h->log_std_off; a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic;
-    a.exact_f32 = fwd_exact(h) ? 1 : 0;
-    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = a.exact_f32 ? h->w2a_critic : (const float*)h->w2pf_critic;
-    a.mon_cur_ret = h->mon_cur_ret; a.mon_cur_len = h->mon_cur_len; a.ep_ret = h->ep_ret; a.ep_len = h->ep_len;
+    const RolloutArgs a = rollout_args(h);
     const auto t0 = std::chrono::steady_clock::now();
     if (fps) HIPCHK(h, hipStreamSynchronize(h->stream));
     prof_begin(h, DRIL_K_ROLLOUT);
@@ -1918,13 +1927,30 @@ DRIL_EXPORT int32_t dril_debug_set_permutation(dril_handle* h, const int64_t* pe
 }
 
 namespace {
-int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
-    const int world = comm_ready(h) ? h->cfg.world_size : 1;
-    if (h->cfg.world_size > 1 && !comm_ready(h)) return fail(h, DRIL_ERR_NOT_INITIALISED, "world_size > 1 but dril_comm_init was not called");
-    const int64_t N = h->N, B = h->cfg.batch_size / h->cfg.world_size;
-    const int64_t nb = (N + B - 1) / B;                       // partial last batch kept (MLUtils partial=true)
-    const int64_t total_steps = nb * h->cfg.epochs;
-    const uint64_t adam_steps0 = h->adam_steps;
+// One update in the pieces that ppo_update_once runs in order, and that a population (dril_population_ppo_update) runs member by member around ONE batched launch:
+//   update_begin (sizes, memsets, packed records) -> [small_update_args + the persistent kernel | the per-step kernels] -> update_enqueue_home (explained variance,
+//   max |W2|, the copies home) -> the stream drained -> update_finish (the statistics, the handle's counters, the status)
+struct UpdatePlan { int world = 1; int64_t N = 0, B = 0, nb = 0, total_steps = 0; uint64_t adam_steps0 = 0; int bits = 0; };
+// where an update's results land on the host: st [total_steps][16], ev [4 ev_blocks], scal = {nan flag, gae give-up flag, max |W2| bits}, keys [epochs].  Storage is the
+// caller's and must not move before update_finish: vectors for a solo update, one pinned block per member in a population
+struct UpdateHome { float* st = nullptr; double* ev = nullptr; int* scal = nullptr; uint64_t* keys = nullptr; };
+UpdatePlan update_plan(const dril_handle* h) {
+    UpdatePlan p;
+    p.world = comm_ready(h) ? h->cfg.world_size : 1;
+    p.N = h->N; p.B = h->cfg.batch_size / h->cfg.world_size;
+    p.nb = (p.N + p.B - 1) / p.B;                             // partial last batch kept (MLUtils partial=true)
+    p.total_steps = p.nb * h->cfg.epochs;
+    p.adam_steps0 = h->adam_steps; p.bits = perm_bits(p.N);
+    return p;
+}
+// the reference's default PPO() (batch_size = 64) on hidden [64,64]: every optimiser step of the iteration inside ONE launch of two persistent workgroups, one per net (dril_update_small.hip);
+// single-rank only (a data-parallel run all-reduces between the gradient and the step)
+bool small_persistent_applies(const dril_handle* h, const UpdatePlan& p) {
+    return !h->wide && !h->generic && h->cfg.hidden1 == 64 && h->D <= 8 && p.world == 1 && !(comm_ready(h) && h->force_allreduce) && h->rec && p.B >= 2 && p.B <= 64 && h->P <= 2 * 256 * 19 &&
+           !h->no_persistent && !h->no_small_path && h->grad_variant < 0 && p.total_steps > 0;   // (DRIL_GRAD_VARIANT pins one of the per-step kernels)
+}
+int update_begin(dril_handle* h, const UpdatePlan& p) {
+    const int64_t total_steps = p.total_steps;
     h->used_f16 = false; h->spin_timeout = false;
     if (total_steps > h->step_stats_cap) {
         if (h->step_stats) hipFree(h->step_stats);
@@ -1932,41 +1958,60 @@ int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
     }
     if (total_steps > 0) HIPCHK(h, hipMemsetAsync(h->step_stats, 0, (size_t)total_steps * 16 * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(h->stop_flag, 0, 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->nan_flag, 0, 4, h->stream));
-    const int bits = perm_bits(N);
-    if (h->rec) { prof_begin(h, DRIL_K_PACK_RECORDS); HIPCHK(h, launch_pack_records(h->cfg.env_kind, N, h->obs, h->act, h->adv, h->logp, h->ret, h->rec, h->stream)); prof_end(h); }
+    if (h->rec) { prof_begin(h, DRIL_K_PACK_RECORDS); HIPCHK(h, launch_pack_records(h->cfg.env_kind, p.N, h->obs, h->act, h->adv, h->logp, h->ret, h->rec, h->stream)); prof_end(h); }
+    return DRIL_OK;
+}
+// the persistent kernel's argument block (step0 / nsteps / step_parity / xchg are the launch's: the caller sets them); keys[epochs] goes to the device on the handle's
+// stream and must stay alive until that copy has run
+int small_update_args(dril_handle* h, const UpdatePlan& p, uint64_t* keys, SmallUpdateArgs& u) {
+    if (h->cfg.epochs > h->epoch_keys_cap) {
+        if (h->epoch_keys) hipFree(h->epoch_keys);
+        h->epoch_keys = nullptr; HIPCHK(h, dmalloc(&h->epoch_keys, (size_t)h->cfg.epochs)); h->epoch_keys_cap = h->cfg.epochs;
+    }
+    for (int ep = 0; ep < h->cfg.epochs; ++ep) keys[ep] = perm_key(h->cfg.seed + (uint64_t)h->cfg.rank, h->update_counter, ep);
+    HIPCHK(h, hipMemcpyAsync(h->epoch_keys, keys, (size_t)h->cfg.epochs * 8, hipMemcpyHostToDevice, h->stream));
+    u = SmallUpdateArgs{};
+    u.params = h->params; u.adam_m = h->adam_m; u.adam_v = h->adam_v; u.bt = h->bt; u.step_parity = (int)(h->adam_steps & 1);
+    u.rec = h->rec; u.val_old = h->val; u.perm = h->perm_count ? h->perm_dev : nullptr; u.keys = h->epoch_keys; u.perm_bits = p.bits;
+    u.N = p.N; u.B = p.B; u.nb = (int)p.nb; u.step_stats = h->step_stats; u.norm_out = h->norm_out; u.nan_flag = h->nan_flag; u.stop_flag = h->stop_flag;
+    u.lr = h->lr; u.beta1 = h->cfg.adam_beta1; u.beta2 = h->cfg.adam_beta2; u.eps = h->cfg.adam_eps; u.max_grad_norm = h->cfg.max_grad_norm;
+    u.target_kl = h->cfg.target_kl; u.ent_coef = h->cfg.ent_coef; u.vf_coef = h->cfg.vf_coef; u.clip_range = h->cfg.clip_range; u.clip_range_vf = h->cfg.clip_range_vf;
+    u.has_max_grad_norm = h->cfg.has_max_grad_norm; u.has_target_kl = h->cfg.has_target_kl; u.has_clip_vf = h->cfg.has_clip_range_vf;
+    u.normalize_adv = h->cfg.normalize_advantage; u.action_start = h->cfg.action_start; u.P = h->P; u.Pa = h->Pa; u.Pc = h->Pc; u.dbg = h->dbg;
+    return DRIL_OK;
+}
+// the launch that starts at step s0 of the chunked sequence: at most chunk (h->small_chunk) optimiser steps per launch (16 384: a bound on one kernel's run time, ~0.2 s)
+void small_update_chunk(const UpdatePlan& p, int64_t chunk, int64_t s0, SmallUpdateArgs& u) {
+    u.step0 = (int)s0; u.nsteps = (int)(p.total_steps - s0 < chunk ? p.total_steps - s0 : chunk);
+    u.step_parity = s0 == 0 ? (int)(p.adam_steps0 & 1) : 0;                           // (the kernel leaves both ping-pong slots of the beta powers equal)
+}
+// what the persistent kernel's launches leave on the host side of the handle
+void small_update_done(dril_handle* h, const UpdatePlan& p) { h->adam_steps += p.total_steps; h->wimg_dirty = true; h->last_variant = 6; h->used_f16 = true; }
+int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home);
+int update_finish(dril_handle* h, const UpdatePlan& p, const UpdateHome& home, dril_ppo_stats* out);
+int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
+    if (h->cfg.world_size > 1 && !comm_ready(h)) return fail(h, DRIL_ERR_NOT_INITIALISED, "world_size > 1 but dril_comm_init was not called");
+    const UpdatePlan plan = update_plan(h);
+    const int world = plan.world;
+    const int64_t N = plan.N, B = plan.B, nb = plan.nb, total_steps = plan.total_steps;
+    { int rcb = update_begin(h, plan); if (rcb) return rcb; }
+    const int bits = plan.bits;
     int64_t step = 0;
-    // the reference's default PPO() (batch_size = 64) on hidden [64,64]: every optimiser step of the iteration inside ONE launch of two persistent workgroups, one per net (dril_update_small.hip);
-    // single-rank only (a data-parallel run all-reduces between the gradient and the step)
-    const bool persistent = !h->wide && !h->generic && h->cfg.hidden1 == 64 && h->D <= 8 && world == 1 && !(comm_ready(h) && h->force_allreduce) && h->rec && B >= 2 && B <= 64 && h->P <= 2 * 256 * 19 &&
-                            !h->no_persistent && !h->no_small_path && h->grad_variant < 0 && total_steps > 0;   // (DRIL_GRAD_VARIANT pins one of the per-step kernels)
+    const bool persistent = small_persistent_applies(h, plan);
     if (persistent) {
-        if (h->cfg.epochs > h->epoch_keys_cap) {
-            if (h->epoch_keys) hipFree(h->epoch_keys);
-            h->epoch_keys = nullptr; HIPCHK(h, dmalloc(&h->epoch_keys, (size_t)h->cfg.epochs)); h->epoch_keys_cap = h->cfg.epochs;
-        }
         std::vector<uint64_t> keys((size_t)h->cfg.epochs);
-        for (int ep = 0; ep < h->cfg.epochs; ++ep) keys[ep] = perm_key(h->cfg.seed + (uint64_t)h->cfg.rank, h->update_counter, ep);
-        HIPCHK(h, hipMemcpyAsync(h->epoch_keys, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (keys is a stack-lifetime host buffer)
         SmallUpdateArgs u{};
-        u.params = h->params; u.adam_m = h->adam_m; u.adam_v = h->adam_v; u.bt = h->bt; u.step_parity = (int)(h->adam_steps & 1);
-        u.rec = h->rec; u.val_old = h->val; u.perm = h->perm_count ? h->perm_dev : nullptr; u.keys = h->epoch_keys; u.perm_bits = bits;
-        u.N = N; u.B = B; u.nb = (int)nb; u.step_stats = h->step_stats; u.norm_out = h->norm_out; u.nan_flag = h->nan_flag; u.stop_flag = h->stop_flag;
-        u.lr = h->lr; u.beta1 = h->cfg.adam_beta1; u.beta2 = h->cfg.adam_beta2; u.eps = h->cfg.adam_eps; u.max_grad_norm = h->cfg.max_grad_norm;
-        u.target_kl = h->cfg.target_kl; u.ent_coef = h->cfg.ent_coef; u.vf_coef = h->cfg.vf_coef; u.clip_range = h->cfg.clip_range; u.clip_range_vf = h->cfg.clip_range_vf;
-        u.has_max_grad_norm = h->cfg.has_max_grad_norm; u.has_target_kl = h->cfg.has_target_kl; u.has_clip_vf = h->cfg.has_clip_range_vf;
-        u.normalize_adv = h->cfg.normalize_advantage; u.action_start = h->cfg.action_start; u.P = h->P; u.Pa = h->Pa; u.Pc = h->Pc; u.dbg = h->dbg;
+        { int rca = small_update_args(h, plan, keys.data(), u); if (rca) return rca; }
+        HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (keys is a stack-lifetime host buffer)
         if (!h->small_xchg) HIPCHK(h, dmalloc(&h->small_xchg, (size_t)kSmallXchgWords));
         u.xchg = h->small_xchg; u.debug_solo = std::getenv("DRIL_SMALL_DEBUG_SOLO") != nullptr;
-        const int64_t chunk = h->small_chunk;                                          // optimiser steps per launch (16 384: a bound on one kernel's run time, ~0.2 s)
-        for (int64_t s0 = 0; s0 < total_steps; s0 += chunk) {
-            u.step0 = (int)s0; u.nsteps = (int)(total_steps - s0 < chunk ? total_steps - s0 : chunk);
-            u.step_parity = s0 == 0 ? (int)(h->adam_steps & 1) : 0;                  // (the kernel leaves both ping-pong slots of the beta powers equal)
+        for (int64_t s0 = 0; s0 < total_steps; s0 += h->small_chunk) {
+            small_update_chunk(plan, h->small_chunk, s0, u);
             prof_begin(h, DRIL_K_PPO_GRAD);
             HIPCHK(h, launch_ppo_update_small(h->cfg.env_kind, u, h->stream));
             prof_end(h);
         }
-        h->adam_steps += total_steps; h->wimg_dirty = true; h->last_variant = 6; h->used_f16 = true;
+        small_update_done(h, plan);
 #ifdef DRIL_STAMPS
         {   // per-phase s_memtime ticks of the last launch, per wave
             hipStreamSynchronize(h->stream);
@@ -2018,20 +2063,34 @@ int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
             if (rc) return rc;
         }
     }
+    std::vector<float> st((size_t)total_steps * 16); std::vector<double> ev(4 * (size_t)h->ev_blocks); int scal[3] = {0, 0, 0};
+    const UpdateHome home{st.data(), ev.data(), scal, nullptr};
+    { int rce = update_enqueue_home(h, plan, home); if (rce) return rce; }
+    int rc = sync(h); if (rc) return rc;
+    return update_finish(h, plan, home, out);
+}
+int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home) {
     h->update_counter += 1;
     prof_begin(h, DRIL_K_EXPLAINED_VAR);
-    HIPCHK(h, launch_explained_var(h->val, h->ret, N, h->ev_partials, h->ev_blocks, h->stream));
+    HIPCHK(h, launch_explained_var(h->val, h->ret, p.N, h->ev_partials, h->ev_blocks, h->stream));
     prof_end(h);
-    std::vector<float> st((size_t)total_steps * 16); std::vector<double> ev(4 * (size_t)h->ev_blocks); int nan = 0; unsigned w2bits = 0;
+    home.scal[0] = 0; home.scal[1] = 0; home.scal[2] = 0;
     if (!h->generic) {    // max |W2| of the parameters this update leaves behind rides home with its statistics (fwd_exact: the next rollout's arithmetic)
         HIPCHK(h, launch_w2_absmax(h->params, h->actor, h->critic, h->cfg.hidden1, h->w2max_dev, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&w2bits, h->w2max_dev, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&home.scal[2], h->w2max_dev, 4, hipMemcpyDeviceToHost, h->stream));
     }
-    if (total_steps > 0) HIPCHK(h, hipMemcpyAsync(st.data(), h->step_stats, st.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ev.data(), h->ev_partials, ev.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&nan, h->nan_flag, 4, hipMemcpyDeviceToHost, h->stream));
-    int gae_gave_up = 0; HIPCHK(h, hipMemcpyAsync(&gae_gave_up, h->gae_err, 4, hipMemcpyDeviceToHost, h->stream));
-    int rc = sync(h); if (rc) return rc;
+    if (p.total_steps > 0) HIPCHK(h, hipMemcpyAsync(home.st, h->step_stats, (size_t)p.total_steps * 16 * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(home.ev, h->ev_partials, 4 * (size_t)h->ev_blocks * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&home.scal[0], h->nan_flag, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&home.scal[1], h->gae_err, 4, hipMemcpyDeviceToHost, h->stream));
+    return DRIL_OK;
+}
+// the stream is drained: the statistics of the update, the handle's counters and the status
+int update_finish(dril_handle* h, const UpdatePlan& p, const UpdateHome& home, dril_ppo_stats* out) {
+    const int world = p.world; const int64_t N = p.N, total_steps = p.total_steps; const uint64_t adam_steps0 = p.adam_steps0;
+    const float* st = home.st; const double* ev = home.ev;
+    const int nan = home.scal[0], gae_gave_up = home.scal[1]; unsigned w2bits; std::memcpy(&w2bits, &home.scal[2], 4);
+    int rc = DRIL_OK;
     // (a rank-local early return here would leave the other ranks of a data-parallel job alone in the collectives that follow — they saw this rank's NaN advantages in the
     // all-reduced gradient and start the exact-f32 redo: the flag is folded into the explained-variance all-reduce below, and every rank returns the same code at the same point)
     if (gae_gave_up && world == 1) { (void)hipMemsetAsync(h->gae_err, 0, 4, h->stream); return fail(h, DRIL_ERR_HIP, "gae_scan_kernel: a chunk's predecessor did not publish its carry within the spin limit (advantages of this rollout are NaN)"); }
@@ -2099,47 +2158,55 @@ int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
 // 65 504 / SG overflows a hi piece, and the step that meets it reports a non-finite gradient without touching the parameters.  Range is not something the reference
 // asks of its user, so such an update is taken back (parameters, Adam moments, beta powers and the counters as they were before it) and redone on the exact-f32
 // kernels; only a gradient that is non-finite there as well is an error (ppo.jl:213-214).  Costs three small device copies per update.
-int ppo_update(dril_handle* h, dril_ppo_stats* out) {
-    const bool may_retry = !h->generic && h->grad_variant < 0 && !h->no_f32_retry;
-    // (a) known in advance that f16 cannot hold this update: a W2 entry out of range, or the latch (kRetryLatchAfter consecutive redone updates: the workload lives outside
-    //     f16's range, so the next kRetryLatchUpdates run the exact-f32 kernels at once instead of paying an f16 pass + snapshot + redo each) — no wasted pass, no snapshot
-    if (may_retry && (h->f32_latch_left > 0 || !(h->w2max < kFwdSplitMaxW))) {
-        if (h->f32_latch_left > 0) h->f32_latch_left -= 1;
-        const int gv = h->grad_variant; h->grad_variant = 0;
-        const int rc = ppo_update_once(h, out);
-        h->grad_variant = gv; h->f32_direct_updates += 1;
-        if (out) out->f32_path = 2;
-        return rc;
-    }
-    const uint64_t adam_steps0 = h->adam_steps; const uint64_t counter0 = h->update_counter;
+// ppo_update in the pieces a population shares with it: the decision (a), the snapshot, and what follows the first pass (b), (c)
+struct UpdateTry { bool may_retry = false; uint64_t adam_steps0 = 0, counter0 = 0; };
+bool update_may_retry(const dril_handle* h) { return !h->generic && h->grad_variant < 0 && !h->no_f32_retry; }
+// (a) known in advance that f16 cannot hold this update: a W2 entry out of range, or the latch (kRetryLatchAfter consecutive redone updates: the workload lives outside
+//     f16's range, so the next kRetryLatchUpdates run the exact-f32 kernels at once instead of paying an f16 pass + snapshot + redo each) — no wasted pass, no snapshot
+bool update_direct_f32(const dril_handle* h) { return update_may_retry(h) && (h->f32_latch_left > 0 || !(h->w2max < kFwdSplitMaxW)); }
+int update_run_direct_f32(dril_handle* h, dril_ppo_stats* out) {
+    if (h->f32_latch_left > 0) h->f32_latch_left -= 1;
+    const int gv = h->grad_variant; h->grad_variant = 0;
+    const int rc = ppo_update_once(h, out);
+    h->grad_variant = gv; h->f32_direct_updates += 1;
+    if (out) out->f32_path = 2;
+    return rc;
+}
+int update_snapshot(dril_handle* h, UpdateTry& t) {
+    t.may_retry = update_may_retry(h); t.adam_steps0 = h->adam_steps; t.counter0 = h->update_counter;
     const size_t P = (size_t)h->P;
-    if (may_retry) {
+    if (t.may_retry) {
         if (!h->retry_snap) HIPCHK(h, dmalloc(&h->retry_snap, 3 * P + 4));
         HIPCHK(h, hipMemcpyAsync(h->retry_snap, h->params, P * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->retry_snap + P, h->adam_m, P * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->retry_snap + 2 * P, h->adam_v, P * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->retry_snap + 3 * P, h->bt, 4 * 4, hipMemcpyDeviceToDevice, h->stream));
     }
-    auto restore = [&]() -> int {
-        HIPCHK(h, hipMemcpyAsync(h->params, h->retry_snap, P * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->adam_m, h->retry_snap + P, P * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->adam_v, h->retry_snap + 2 * P, P * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->bt, h->retry_snap + 3 * P, 4 * 4, hipMemcpyDeviceToDevice, h->stream));
-        h->adam_steps = adam_steps0; h->update_counter = counter0; h->wimg_dirty = true;
-        return DRIL_OK;
-    };
-    int rc = ppo_update_once(h, out);
+    return DRIL_OK;
+}
+int update_restore(dril_handle* h, const UpdateTry& t) {
+    const size_t P = (size_t)h->P;
+    HIPCHK(h, hipMemcpyAsync(h->params, h->retry_snap, P * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->adam_m, h->retry_snap + P, P * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->adam_v, h->retry_snap + 2 * P, P * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->bt, h->retry_snap + 3 * P, 4 * 4, hipMemcpyDeviceToDevice, h->stream));
+    h->adam_steps = t.adam_steps0; h->update_counter = t.counter0; h->wimg_dirty = true;
+    return DRIL_OK;
+}
+// rc: what the first pass over the default kernels returned (ppo_update_once, or a population's batched launch followed by update_finish)
+int update_resolve(dril_handle* h, const UpdateTry& t, int rc, dril_ppo_stats* out) {
+    const bool may_retry = t.may_retry;
     // (b) the persistent two-workgroup kernel gave up waiting for its partner (the GPU is shared with another stream / process and the two workgroups were not resident
     //     together): nothing is lost — the state of before the update is in the snapshot and the per-step kernels need no co-residency.  Redone once; the handle stays on them.
     if (rc == DRIL_ERR_HIP && h->spin_timeout && may_retry) {
-        { const int rr = restore(); if (rr) return rr; }
+        { const int rr = update_restore(h, t); if (rr) return rr; }
         h->no_persistent = true; h->persistent_fallbacks += 1;
         rc = ppo_update_once(h, out);
         if (rc == DRIL_OK) h->err.clear();
     }
     // (c) an f16-piece kernel ran somewhere in this update (sticky flag, not the last step's kernel) and a step met a non-finite gradient: redo on the exact-f32 kernels
     if (rc == DRIL_ERR_NAN_IN_GRADS && may_retry && h->used_f16) {
-        { const int rr = restore(); if (rr) return rr; }
+        { const int rr = update_restore(h, t); if (rr) return rr; }
         const int gv = h->grad_variant; h->grad_variant = 0;                            // the exact-f32 kernels for this update (the persistent small kernel is f16 as well: per-step path)
         rc = ppo_update_once(h, out);
         h->grad_variant = gv; h->f32_retries += 1;
@@ -2148,6 +2215,12 @@ int ppo_update(dril_handle* h, dril_ppo_stats* out) {
         if (rc == DRIL_OK && ++h->f32_streak >= kRetryLatchAfter) h->f32_latch_left = kRetryLatchUpdates;   // (a gradient that is non-finite on exact f32 too is not a range problem: it arms nothing)
     } else if (rc == DRIL_OK && h->used_f16) h->f32_streak = 0;                         // an update inside f16's range: the streak (and with it the latch's re-arming) ends
     return rc;
+}
+int ppo_update(dril_handle* h, dril_ppo_stats* out) {
+    if (update_direct_f32(h)) return update_run_direct_f32(h, out);
+    UpdateTry t;
+    { const int rs = update_snapshot(h, t); if (rs) return rs; }
+    return update_resolve(h, t, ppo_update_once(h, out), out);
 }
 }  // namespace
 DRIL_EXPORT int32_t dril_ppo_update(dril_handle* h, dril_ppo_stats* out) { NEED(h); return ppo_update(h, out); }
@@ -2756,6 +2829,302 @@ DRIL_EXPORT int32_t dril_train(dril_handle* h, int64_t max_steps, dril_ppo_stats
     }
     if (iterations_done) *iterations_done = done;
     return DRIL_OK;
+}
+
+// ---- populations: many small PPO agents per launch (docs/population.md) ------------------------------------------------------------------
+// A population joins ordinary PPO handles for batched launches: one rollout_duo_pop_kernel and one ppo_update_small_pop_kernel where P solo iterations launch
+// rollout_duo_kernel and ppo_update_small_kernel P times.  It keeps no copy of member state: every verb reads each handle with the solo path's own functions
+// (rollout_args, update_begin, small_update_args, update_enqueue_home, update_finish, update_resolve), so a member's result is that of its handle driven alone, bit for bit.
+// While joined, the members share the population's stream: whatever a member's own verbs enqueue between population calls is ordered with the batched launches.
+struct dril_population {
+    std::vector<dril_handle*> members; std::vector<hipStream_t> own_streams;
+    hipStream_t stream = nullptr; int device = 0, cap = 1; int64_t chunk = 16384, total_steps = 0; int n_chunks = 1;
+    RolloutArgs *h_rargs = nullptr, *d_rargs = nullptr; SmallUpdateArgs *h_uargs = nullptr, *d_uargs = nullptr;   // pinned / device: [n] and [n_chunks][n]
+    unsigned long long* xchg = nullptr;                          // n x kSmallXchgWords
+    std::vector<char*> home_blocks; std::vector<UpdateHome> homes;   // one pinned block per member: where its update's results land
+    std::vector<int> failed;                                     // status of a member that failed in the current call (it sits out the rest of the iteration)
+    struct dril_population_info info{};
+    struct Ev { int kind; hipEvent_t a, b; }; std::vector<Ev> ev_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::string err;
+};
+namespace {
+int pop_fail(dril_population* p, int code, const std::string& msg) { p->err = msg; return code; }
+// "" when the handle can be a member, else why not (the shape on which a solo iteration is one rollout_duo_kernel launch and one ppo_update_small_kernel launch)
+std::string pop_ineligible(const dril_handle* h, int& code) {
+    code = DRIL_ERR_UNSUPPORTED;
+    if (h->external) return "an external handle (DRIL_ENV_EXTERNAL): its envs live with the caller";
+    if (h->env.is_world()) return "a world of a device env plug-in";
+    if (h->env.module || !env_kind_info(h->cfg.env_kind)) return "a device env plug-in handle (DRIL_ENV_MODULE): populations take the built-in env kinds";
+    if (normalizing(h) || h->pn.on) return "a normalising handle (NormalizeWrapperEnv collects step by step)";
+    if (h->cfg.world_size > 1 || comm_ready(h)) return "world_size > 1: members are single-rank handles";
+    if (h->generic || h->wide || h->cfg.hidden1 != 64) return "a generic or wide net: members have hidden_dims [64,64] with tanh";
+    const UpdatePlan plan = update_plan(h);
+    if (plan.B > 64) return "batch_size " + std::to_string((long long)plan.B) + " > 64: the persistent update kernel takes minibatches of 2..64 samples";
+    if (h->force_stepwise || !rollout_fused_applies(h) || !rollout_duo_applies(h->cfg.hidden1, h->cfg.n_envs)) return "its collection is not one launch of rollout_duo_kernel (n_envs <= 16384, not step-granular)";
+    if (h->grad_variant >= 0 || h->no_persistent || h->no_small_path || !small_persistent_applies(h, plan)) return "its update is not one launch of ppo_update_small_kernel (2 <= batch_size <= 64, default gradient variant, persistent update on)";
+    return "";
+}
+// what fixes the kernel instance and the grid must be equal across members
+std::string pop_mismatch(const dril_handle* a, const dril_handle* b, int& code) {
+    const dril_config &x = a->cfg, &y = b->cfg;
+    code = DRIL_ERR_INVALID_ARG;
+    if (x.device != y.device) return "mixed devices (device " + std::to_string(y.device) + " against member 0's " + std::to_string(x.device) + ")";
+    if (x.env_kind != y.env_kind) return "mixed env kinds (" + std::to_string(y.env_kind) + " against member 0's " + std::to_string(x.env_kind) + ")";
+    if (x.n_envs != y.n_envs || x.n_steps != y.n_steps || x.batch_size != y.batch_size || x.epochs != y.epochs) return "mixed shapes (n_envs, n_steps, batch_size and epochs must equal member 0's)";
+    if (x.hidden1 != y.hidden1 || x.hidden2 != y.hidden2 || x.n_hidden != y.n_hidden || x.activation != y.activation) return "mixed shapes (hidden dims and activation must equal member 0's)";
+    if (x.normalize_advantage != y.normalize_advantage) return "mixed shapes (normalize_advantage must equal member 0's)";
+    return "";
+}
+void pop_release(dril_population* p) {
+    (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    for (size_t m = 0; m < p->members.size(); ++m) { dril_handle* h = p->members[m]; if (h->pop == p) { h->stream = p->own_streams[m]; h->pop = nullptr; } }
+    for (char* b : p->home_blocks) if (b) (void)hipHostFree(b);
+    if (p->h_rargs) (void)hipHostFree(p->h_rargs); if (p->h_uargs) (void)hipHostFree(p->h_uargs);
+    if (p->d_rargs) (void)hipFree(p->d_rargs); if (p->d_uargs) (void)hipFree(p->d_uargs); if (p->xchg) (void)hipFree(p->xchg);
+    for (auto& e : p->ev_pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
+    for (auto& e : p->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
+    if (p->stream) (void)hipStreamDestroy(p->stream);
+    delete p;
+}
+#define POPCHK(p, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return pop_fail(p, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
+// HIP-event brackets of the batched kernels (member 0's cfg.profile_events), resolved when the stream is drained
+void pop_ev_begin(dril_population* p, int kind) {
+    if (!p->members[0]->cfg.profile_events) return;
+    std::pair<hipEvent_t, hipEvent_t> ev;
+    if (!p->ev_pool.empty()) { ev = p->ev_pool.back(); p->ev_pool.pop_back(); } else { hipEventCreate(&ev.first); hipEventCreate(&ev.second); }
+    hipEventRecord(ev.first, p->stream);
+    p->ev_pending.push_back({kind, ev.first, ev.second});
+}
+void pop_ev_end(dril_population* p) { if (p->members[0]->cfg.profile_events && !p->ev_pending.empty()) hipEventRecord(p->ev_pending.back().b, p->stream); }
+int pop_sync(dril_population* p) {
+    POPCHK(p, hipStreamSynchronize(p->stream));
+    for (auto& e : p->ev_pending) {
+        float ms = 0; if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) (e.kind == 0 ? p->info.last_rollout_ms : p->info.last_update_ms) += ms;
+        p->ev_pool.push_back({e.a, e.b});
+    }
+    p->ev_pending.clear();
+    for (dril_handle* h : p->members) prof_resolve(h);
+    return DRIL_OK;
+}
+void pop_member_failed(dril_population* p, int m, int rc, const char* verb, int& first) {
+    p->failed[m] = rc;
+    if (first == DRIL_OK) { first = rc; p->err = std::string(verb) + ": member " + std::to_string(m) + ": " + p->members[m]->err; }
+}
+void pop_call_begin(dril_population* p) {
+    (void)hipSetDevice(p->device);
+    std::fill(p->failed.begin(), p->failed.end(), DRIL_OK);
+    struct dril_population_info& i = p->info;
+    i.last_rollout_launches = i.last_update_launches = i.last_solo_rollouts = i.last_solo_updates = 0; i.last_launches_per_iteration = 0; i.last_rollout_ms = i.last_update_ms = 0;
+}
+// collect_rollout of every member that has not failed in this call: ONE rollout_duo_pop_kernel launch for the members whose collection is that kernel's solo twin on the
+// f16-piece forward, collect_rollout itself for the others; then per member what follows the launch in collect_rollout (monitor window, GAE)
+int pop_collect(dril_population* p, double* fps, bool do_sync, int& first) {
+    const int n = (int)p->members.size();
+    std::vector<int> batched, solo;
+    for (int m = 0; m < n; ++m) {
+        dril_handle* h = p->members[m];
+        if (p->failed[m]) continue;
+        if (fps) fps[m] = 0;
+        if (!h->env.ready) { pop_member_failed(p, m, fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset"), "dril_population_collect_rollout", first); continue; }
+        { const int rcw = ensure_wimg(h); if (rcw) { pop_member_failed(p, m, rcw, "dril_population_collect_rollout", first); continue; } }
+        if (rollout_fused_applies(h) && h->cfg.hidden1 == 64 && rollout_duo_applies(h->cfg.hidden1, h->env.E) && !fwd_exact(h)) batched.push_back(m); else solo.push_back(m);
+    }
+    if (!batched.empty()) {
+        const int nbat = (int)batched.size();
+        for (int k = 0; k < nbat; ++k) p->h_rargs[k] = rollout_args(p->members[batched[k]]);
+        hipError_t e = hipMemcpyAsync(p->d_rargs, p->h_rargs, sizeof(RolloutArgs) * (size_t)nbat, hipMemcpyHostToDevice, p->stream);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (fps && e == hipSuccess) e = hipStreamSynchronize(p->stream);
+        pop_ev_begin(p, 0);
+        if (e == hipSuccess) e = launch_rollout_pop(p->members[0]->cfg.env_kind, p->d_rargs, nbat, p->members[0]->env.E, p->stream);
+        pop_ev_end(p);
+        double f = 0;
+        if (fps && e == hipSuccess) {   // fps = steps / wall time of collect_trajectories (rollout_buffer.jl:60-64): every member of the launch waited for the whole launch
+            e = hipStreamSynchronize(p->stream);
+            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            f = (double)p->members[0]->N / (dt > 0 ? dt : 1e-12);
+        }
+        p->info.last_rollout_launches += 1; p->info.total_rollout_launches += 1;
+        for (int k = 0; k < nbat; ++k) {
+            const int m = batched[k]; dril_handle* h = p->members[m];
+            int rc = e == hipSuccess ? DRIL_OK : fail(h, DRIL_ERR_HIP, std::string("rollout_duo_pop_kernel: ") + hipGetErrorString(e));
+            if (!rc) { if (fps) fps[m] = f; h->noise_set = false; rc = monitor_collect_rollout(h); }
+            if (!rc) rc = compute_gae(h);
+            if (rc) pop_member_failed(p, m, rc, "dril_population_collect_rollout", first);
+        }
+    }
+    for (int m : solo) {
+        double f = 0; const int rc = collect_rollout(p->members[m], fps ? &f : nullptr, false);
+        if (fps) fps[m] = f;
+        p->info.last_solo_rollouts += 1; p->info.total_solo_rollouts += 1;
+        if (rc) pop_member_failed(p, m, rc, "dril_population_collect_rollout", first);
+    }
+    if (do_sync) { const int rc = pop_sync(p); if (rc) return rc; }
+    return DRIL_OK;
+}
+// ppo_update of every member that has not failed in this call: the members whose update is one run of the persistent kernel go through ppo_update_small_pop_kernel
+// (at most cap members per launch: a pair of workgroups needs both resident at once), the others through ppo_update; ONE drain of the stream, then per member
+// update_finish and what ppo_update does after its first pass (the redo of a pair that never met, or of an update that left f16's range: alone, on the solo kernels)
+int pop_update(dril_population* p, dril_ppo_stats* out, int& first) {
+    const int n = (int)p->members.size();
+    struct Run { int m; UpdatePlan plan; UpdateTry t; };
+    std::vector<Run> batched; std::vector<int> solo;
+    for (int m = 0; m < n; ++m) {
+        dril_handle* h = p->members[m];
+        if (p->failed[m]) continue;
+        if (out) std::memset(&out[m], 0, sizeof(dril_ppo_stats));
+        const UpdatePlan plan = update_plan(h);
+        if (!small_persistent_applies(h, plan) || update_direct_f32(h) || plan.total_steps != p->total_steps) { solo.push_back(m); continue; }
+        Run r{m, plan, UpdateTry{}};
+        SmallUpdateArgs u{};
+        int rc = update_snapshot(h, r.t);
+        if (!rc) rc = update_begin(h, plan);
+        if (!rc) rc = small_update_args(h, plan, p->homes[m].keys, u);
+        if (rc) { pop_member_failed(p, m, rc, "dril_population_ppo_update", first); continue; }
+        p->h_uargs[(size_t)p->n_chunks * n + batched.size()] = u;                       // behind the launch table: the member's block, copied into every launch's row below
+        batched.push_back(r);
+    }
+    const int nbat = (int)batched.size();
+    hipError_t e = hipSuccess;
+    if (nbat > 0) {
+        int c = 0;
+        for (int64_t s0 = 0; s0 < p->total_steps; s0 += p->chunk, ++c)
+            for (int k = 0; k < nbat; ++k) {
+                SmallUpdateArgs& u = p->h_uargs[(size_t)c * nbat + k];
+                u = p->h_uargs[(size_t)p->n_chunks * n + k];                              // the member's block as small_update_args filled it (kept behind the launch table)
+                u.xchg = p->xchg + (size_t)k * kSmallXchgWords; u.debug_solo = 0;
+                small_update_chunk(batched[k].plan, p->chunk, s0, u);
+            }
+        e = hipMemcpyAsync(p->d_uargs, p->h_uargs, sizeof(SmallUpdateArgs) * (size_t)p->n_chunks * nbat, hipMemcpyHostToDevice, p->stream);
+        pop_ev_begin(p, 1);
+        for (c = 0; c < p->n_chunks && e == hipSuccess; ++c)
+            for (int g0 = 0; g0 < nbat && e == hipSuccess; g0 += p->cap) {
+                const int cnt = nbat - g0 < p->cap ? nbat - g0 : p->cap;
+                e = launch_ppo_update_small_pop(p->members[0]->cfg.env_kind, p->d_uargs + (size_t)c * nbat + g0, cnt, p->xchg + (size_t)g0 * kSmallXchgWords, (size_t)cnt * kSmallXchgWords, p->stream);
+                p->info.last_update_launches += 1; p->info.total_update_launches += 1;
+            }
+        pop_ev_end(p);
+    }
+    std::vector<char> enq((size_t)nbat, 0);
+    for (int k = 0; k < nbat; ++k) {
+        const int m = batched[k].m; dril_handle* h = p->members[m];
+        int rc = e == hipSuccess ? DRIL_OK : fail(h, DRIL_ERR_HIP, std::string("ppo_update_small_pop_kernel: ") + hipGetErrorString(e));
+        if (!rc) { small_update_done(h, batched[k].plan); rc = update_enqueue_home(h, batched[k].plan, p->homes[m]); }
+        if (rc) pop_member_failed(p, m, rc, "dril_population_ppo_update", first); else enq[k] = 1;
+    }
+    if (nbat > 0) { const int rc = pop_sync(p); if (rc) return rc; }                       // ONE drain for the whole population
+    for (int k = 0; k < nbat; ++k) {
+        if (!enq[k]) continue;
+        const int m = batched[k].m; dril_handle* h = p->members[m];
+        const int64_t redo0 = h->persistent_fallbacks + h->f32_retries;
+        int rc = update_finish(h, batched[k].plan, p->homes[m], out ? &out[m] : nullptr);
+        rc = update_resolve(h, batched[k].t, rc, out ? &out[m] : nullptr);
+        if (h->persistent_fallbacks + h->f32_retries != redo0) { p->info.last_solo_updates += 1; p->info.total_solo_updates += 1; }   // redone alone, on the solo kernels
+        if (rc) pop_member_failed(p, m, rc, "dril_population_ppo_update", first);
+    }
+    for (int m : solo) {
+        const int rc = ppo_update(p->members[m], out ? &out[m] : nullptr);
+        p->info.last_solo_updates += 1; p->info.total_solo_updates += 1;
+        if (rc) pop_member_failed(p, m, rc, "dril_population_ppo_update", first);
+    }
+    return DRIL_OK;
+}
+}  // namespace
+
+DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_population** out) {
+    if (!out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_population_join: null out");
+    *out = nullptr;
+    if (!members || n < 1 || n > DRIL_POPULATION_MAX) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_population_join: 1.." + std::to_string(DRIL_POPULATION_MAX) + " members");
+    for (int m = 0; m < n; ++m) {
+        const dril_handle* h = members[m];
+        const std::string who = "dril_population_join: member " + std::to_string(m) + ": ";
+        if (!h) return fail(nullptr, DRIL_ERR_INVALID_ARG, who + "null handle");
+        for (int q = 0; q < m; ++q) if (members[q] == h) return fail(nullptr, DRIL_ERR_INVALID_ARG, who + "the same handle as member " + std::to_string(q));
+        if (h->pop) return fail(nullptr, DRIL_ERR_INVALID_ARG, who + "the handle is already a member of a population");
+        int code = DRIL_OK;
+        std::string why = pop_ineligible(h, code);
+        if (why.empty() && m > 0) why = pop_mismatch(members[0], h, code);
+        if (!why.empty()) return fail(nullptr, code, who + why);
+    }
+    dril_handle* h0 = members[0];
+    (void)hipSetDevice(h0->cfg.device);
+    dril_population* p = new dril_population();
+    p->device = h0->cfg.device;
+    p->cap = h0->num_cus / 4 > 0 ? h0->num_cus / 4 : 1;                               // two workgroups per member, at most half the CUs per launch
+    if (const char* e = debug_env("DRIL_POP_CAP")) { const int c = std::atoi(e); if (c > 0 && c < p->cap) p->cap = c; }   // tests: more than one launch per verb
+    p->chunk = h0->small_chunk;
+    for (int m = 0; m < n; ++m) if (members[m]->small_chunk < p->chunk) p->chunk = members[m]->small_chunk;
+    p->total_steps = update_plan(h0).total_steps;
+    p->n_chunks = (int)((p->total_steps + p->chunk - 1) / p->chunk);
+#define JCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { const std::string msg = std::string("dril_population_join: " #expr ": ") + hipGetErrorString(_e); pop_release(p); return fail(nullptr, DRIL_ERR_HIP, msg); } } while (0)
+    JCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    JCHK(hipHostMalloc((void**)&p->h_rargs, sizeof(RolloutArgs) * (size_t)n, hipHostMallocDefault));
+    JCHK(hipHostMalloc((void**)&p->h_uargs, sizeof(SmallUpdateArgs) * ((size_t)p->n_chunks + 1) * n, hipHostMallocDefault));   // the launch table, and behind it one block per member
+    JCHK(hipMalloc((void**)&p->d_rargs, sizeof(RolloutArgs) * (size_t)n));
+    JCHK(hipMalloc((void**)&p->d_uargs, sizeof(SmallUpdateArgs) * (size_t)p->n_chunks * n));
+    JCHK(dmalloc(&p->xchg, (size_t)n * kSmallXchgWords));
+    p->home_blocks.assign((size_t)n, nullptr); p->homes.assign((size_t)n, UpdateHome{}); p->failed.assign((size_t)n, DRIL_OK);
+    for (int m = 0; m < n; ++m) {
+        const dril_handle* h = members[m];
+        const size_t st = ((size_t)p->total_steps * 16 * 4 + 15) & ~(size_t)15, ev = 4 * (size_t)h->ev_blocks * 8, keys = (size_t)h->cfg.epochs * 8;
+        JCHK(hipHostMalloc((void**)&p->home_blocks[m], st + ev + keys + 16, hipHostMallocDefault));
+        char* b = p->home_blocks[m];
+        p->homes[m] = UpdateHome{(float*)b, (double*)(b + st), (int*)(b + st + ev + keys), (uint64_t*)(b + st + ev)};
+    }
+#undef JCHK
+    for (int m = 0; m < n; ++m) {                                                      // from here on nothing fails: the members move onto the population's stream
+        dril_handle* h = members[m];
+        (void)hipStreamSynchronize(h->stream);
+        p->members.push_back(h); p->own_streams.push_back(h->stream);
+        h->stream = p->stream; h->pop = p;
+    }
+    p->info.members = n; p->info.cap = p->cap;
+    *out = p;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_population_destroy(dril_population* p) { if (p) pop_release(p); return DRIL_OK; }
+DRIL_EXPORT const char* dril_population_last_error(const dril_population* p) { return p ? p->err.c_str() : g_create_error.c_str(); }
+DRIL_EXPORT int32_t dril_population_info(const dril_population* p, struct dril_population_info* out) {
+    if (!p || !out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_population_info: null argument");
+    *out = p->info;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_population_collect_rollout(dril_population* p, double* fps) {
+    if (!p) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null population");
+    pop_call_begin(p);
+    int first = DRIL_OK;
+    const int rc = pop_collect(p, fps, true, first);
+    p->info.last_launches_per_iteration = p->info.last_rollout_launches;
+    return rc ? rc : first;
+}
+DRIL_EXPORT int32_t dril_population_ppo_update(dril_population* p, dril_ppo_stats* out) {
+    if (!p) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null population");
+    pop_call_begin(p);
+    int first = DRIL_OK;
+    const int rc = pop_update(p, out, first);
+    p->info.last_launches_per_iteration = p->info.last_update_launches;
+    return rc ? rc : first;
+}
+DRIL_EXPORT int32_t dril_population_train(dril_population* p, int64_t max_steps, dril_ppo_stats* stats, double* fps, int32_t* iterations_done) {
+    if (!p) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null population");
+    pop_call_begin(p);
+    const int n = (int)p->members.size();
+    const dril_handle* h0 = p->members[0];
+    const int64_t per_iter = (int64_t)h0->cfg.n_steps * h0->cfg.n_envs * h0->cfg.world_size;
+    const int64_t iterations = max_steps / per_iter;                                   // ppo.jl:117
+    int32_t done = 0; int first = DRIL_OK, rc = DRIL_OK;
+    for (int64_t i = 0; i < iterations && rc == DRIL_OK && first == DRIL_OK; ++i) {
+        for (dril_handle* h : p->members) h->lr = h->cfg.learning_rate;                // ppo.jl:155-156
+        rc = pop_collect(p, fps ? fps + i * n : nullptr, false, first);                // ppo.jl:167
+        if (rc == DRIL_OK) rc = pop_update(p, stats ? stats + i * n : nullptr, first); // ppo.jl:188-264; a member that failed sits out, the others finish the iteration
+        if (rc == DRIL_OK && first == DRIL_OK) ++done;
+    }
+    if (rc != DRIL_OK || first != DRIL_OK) (void)hipStreamSynchronize(p->stream);
+    const int64_t ran = done + ((rc || first) ? 1 : 0);
+    p->info.last_launches_per_iteration = ran > 0 ? (double)(p->info.last_rollout_launches + p->info.last_update_launches) / (double)ran : 0.0;
+    if (iterations_done) *iterations_done = done;
+    return rc ? rc : first;
 }
 
 // ---- multi-GPU ------------------------------------------------------------------------------------------

@@ -117,6 +117,8 @@ struct SmallUpdateArgs {
 };
 constexpr int kSmallXchgWords = 4 * 16;
 hipError_t launch_ppo_update_small(int kind, const SmallUpdateArgs& a, hipStream_t s);
+// n members of a population in one launch (ppo_update_small_pop_kernel): d_members on the device, every block's xchg inside [xchg, xchg + xchg_words)
+hipError_t launch_ppo_update_small_pop(int kind, const SmallUpdateArgs* d_members, int n, unsigned long long* xchg, size_t xchg_words, hipStream_t s);
 hipError_t launch_epoch_index(int64_t N, uint64_t key, int bits, int32_t* out, hipStream_t s);   // N < 2^31
 
 struct ReduceArgs {
@@ -170,6 +172,8 @@ hipError_t launch_norm_obs_apply(const NormObsArgs& a, hipStream_t s);
 hipError_t launch_rew_partials(int E, const float* rew_raw, float* disc_returns, float gamma, int update, double* partials, int nblocks, hipStream_t s);
 hipError_t launch_norm_rew_apply(const NormRewArgs& a, hipStream_t s);
 hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_t s);
+bool rollout_duo_applies(int hidden, int E);   // launch_rollout runs rollout_duo_kernel (one launch, tiles of 32 envs on two waves) rather than rollout_kernel
+hipError_t launch_rollout_pop(int kind, const RolloutArgs* d_members, int n, int E, hipStream_t s);   // rollout_duo_pop_kernel: n members of a population, grid (tiles, n)
 // carry: gae_chunks(T) x E 64-bit words {tag | f32}, zero at allocation; tag: a non-zero number no earlier launch on this carry buffer used; err: device int, set to 1 if a
 // workgroup gave up waiting for its predecessor (the advantages it wrote are NaN)
 int gae_chunks(int T);

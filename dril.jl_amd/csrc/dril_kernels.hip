@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "dril_internal.h"
+#include "dril_pop_map.h"
 #include "dril_norm_wrap.h"     // nz_merge, nz_reward: the scalars the built-in wrapper (RmsState, 8 dims) shares with the general-width one
 #include "dril_grad_common.h"
 #include "dril_split_pieces.h"
@@ -756,7 +757,7 @@ __global__ __launch_bounds__(256, WIDE ? 1 : 2) void rollout_kernel(RolloutArgs 
 // one-wave kernel (tests/test_gpu_parity.py, test_stepwise_path_equals_persistent_kernel).
 // =============================================================================================
 template <int KIND, int H, bool SPLIT>
-__global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
+__device__ __forceinline__ void rollout_duo_body(const RolloutArgs& a, int tile) {
     constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
     constexpr int LA = FwdLds<D, H, A, false, SPLIT>::SIZE, LC = FwdLds<D, H, 1, false, SPLIT>::SIZE;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -768,7 +769,7 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
     stage_fwd<D, H, A, false, SPLIT>(la, a.params, a.actor, tid, 128);
     stage_fwd<D, H, 1, false, SPLIT>(lc, a.params, a.critic, tid, 128);
     const int c = lane & 31, h = lane >> 5;
-    const int e_raw = blockIdx.x * kTile + c;
+    const int e_raw = tile * kTile + c;
     const bool valid = e_raw < a.E;
     const int e = valid ? e_raw : a.E - 1;
     const bool writer = valid && h == 0;
@@ -851,6 +852,19 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) {
             if (t < a.T) lds_barrier();
         }
     }
+}
+template <int KIND, int H, bool SPLIT>
+__global__ __launch_bounds__(128, 2) void rollout_duo_kernel(RolloutArgs a) { rollout_duo_body<KIND, H, SPLIT>(a, (int)blockIdx.x); }
+// n members of a population (dril_population_*, docs/population.md) in one launch: grid (tiles of 32 envs, members); a workgroup copies its member's argument block
+// (uniform loads) and runs the body above on it — tiles share nothing, so a member's every bit is that of its handle collected alone
+template <int KIND, int H, bool SPLIT>
+__global__ __launch_bounds__(128, 2) void rollout_duo_pop_kernel(const RolloutArgs* __restrict__ members) {
+    RolloutArgs a = members[blockIdx.y];
+    a.params = pop_global(a.params); a.state = pop_global(a.state); a.step_count = pop_global(a.step_count); a.episode = pop_global(a.episode); a.gstep = pop_global(a.gstep);
+    a.obs = pop_global(a.obs); a.act = pop_global(a.act); a.rew = pop_global(a.rew); a.logp = pop_global(a.logp); a.val = pop_global(a.val); a.boot = pop_global(a.boot);
+    a.flags = pop_global(a.flags); a.last_values = pop_global(a.last_values); a.noise = pop_global(a.noise); a.w2a_actor = pop_global(a.w2a_actor); a.w2a_critic = pop_global(a.w2a_critic);
+    a.mon_cur_ret = pop_global(a.mon_cur_ret); a.mon_cur_len = pop_global(a.mon_cur_len); a.ep_ret = pop_global(a.ep_ret); a.ep_len = pop_global(a.ep_len);
+    rollout_duo_body<KIND, H, SPLIT>(a, (int)blockIdx.x);
 }
 
 // =============================================================================================
@@ -1518,9 +1532,24 @@ template <int KIND, int H, bool SPLIT> static size_t duo_lds_bytes() {
     constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
     return sizeof(float) * (FwdLds<D, H, A, false, SPLIT>::SIZE + FwdLds<D, H, 1, false, SPLIT>::SIZE + 2 * (2 * D + 1) * 32);
 }
-hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_t s) {
+bool rollout_duo_applies(int hidden, int E) {
     static const bool no_duo = debug_env("DRIL_NO_ROLLOUT_DUO") != nullptr;             // A/B (DRIL_DEBUG=1)
-    if ((hidden == 64 || hidden == 32) && a.E <= 16384 && !no_duo) {                                      // env counts that leave SIMDs idle: two waves per tile of 32 envs
+    return (hidden == 64 || hidden == 32) && E <= 16384 && !no_duo;                     // env counts that leave SIMDs idle: two waves per tile of 32 envs
+}
+// hidden 64 on the f16-piece forward only (what a population's members run); every member with the E of the first
+hipError_t launch_rollout_pop(int kind, const RolloutArgs* d_members, int n, int E, hipStream_t s) {
+    if (!d_members || n < 1 || n > 65535 || !rollout_duo_applies(64, E)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((E + kTile - 1) / kTile), (unsigned)n);
+    return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;
+        const size_t lds = duo_lds_bytes<KIND, 64, true>();
+        { hipError_t e = set_max_dynamic_lds((const void*)rollout_duo_pop_kernel<KIND, 64, true>, lds); if (e != hipSuccess) return e; }
+        rollout_duo_pop_kernel<KIND, 64, true><<<grid, 128, lds, s>>>(d_members);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_t s) {
+    if (rollout_duo_applies(hidden, a.E)) {
         const int blocks = (a.E + kTile - 1) / kTile;
 #define CALLDS(K, HH, SP) { const size_t lds = duo_lds_bytes<K, HH, SP>(); \
             { hipError_t e = set_max_dynamic_lds((const void*)rollout_duo_kernel<K, HH, SP>, lds); if (e != hipSuccess) return e; } \

@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "dril_grad_common.h"
+#include "dril_pop_map.h"
 #include "dril_split_pieces.h"
 
 namespace dril {
@@ -562,6 +563,29 @@ __global__ __launch_bounds__(256, 1) void ppo_update_small_kernel(SmallUpdateArg
     else small_net_loop<KIND, 1, HEAD_VALUE, 1>(a, smem, shx, xin, mom);
 }
 
+// ppo_update_small_pop_kernel — n members of a population (dril_population_*, docs/population.md) in one launch: every member is the pair of workgroups above, on its own
+// argument block, placed by dril_pop_map.h.  A block copies its member's block out of the array (uniform loads) and runs small_net_loop as the solo kernel does: the same
+// device code on the same arguments, so a member's every bit is that of its handle updated alone.  A pair needs both its workgroups resident at once and a workgroup takes
+// a CU (launch bounds, LDS): the host never puts more than num_cus / 4 members into a launch.
+template <int KIND>
+__global__ __launch_bounds__(256, 1) void ppo_update_small_pop_kernel(const SmallUpdateArgs* __restrict__ members, int n) {
+    constexpr int A = EnvSpec<KIND>::A;
+    constexpr int AHEAD = EnvSpec<KIND>::discrete ? HEAD_CATEGORICAL : HEAD_GAUSSIAN;
+    extern __shared__ __attribute__((aligned(1024))) float smem[];
+    __shared__ float shx[kMsgWords];
+    __shared__ float xin[kMsgWords + 1];
+    __shared__ float mom[2];
+    const int m = pop_block_member((int)blockIdx.x);
+    if (m >= n) return;
+    SmallUpdateArgs a = members[m];
+    a.params = pop_global(a.params); a.adam_m = pop_global(a.adam_m); a.adam_v = pop_global(a.adam_v); a.bt = pop_global(a.bt); a.rec = pop_global(a.rec);
+    a.val_old = pop_global(a.val_old); a.perm = pop_global(a.perm); a.keys = pop_global(a.keys); a.step_stats = pop_global(a.step_stats); a.norm_out = pop_global(a.norm_out);
+    a.nan_flag = pop_global(a.nan_flag); a.stop_flag = pop_global(a.stop_flag); a.dbg = pop_global(a.dbg); a.xchg = pop_global(a.xchg);
+    if (*a.stop_flag) return;
+    if (pop_block_role((int)blockIdx.x) == 0) small_net_loop<KIND, A, AHEAD, 0>(a, smem, shx, xin, mom);
+    else small_net_loop<KIND, 1, HEAD_VALUE, 1>(a, smem, shx, xin, mom);
+}
+
 template <int KIND> static size_t update_small_lds_bytes() {
     constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
     constexpr int wa = SmallNet<D, A>::END + 2 * SmallPair<D, A>::SIZE, wc = SmallNet<D, 1>::END + 2 * SmallPair<D, 1>::SIZE;
@@ -580,6 +604,19 @@ hipError_t launch_ppo_update_small(int kind, const SmallUpdateArgs& a, hipStream
         return hipGetLastError();
     });
 #undef CALLU
+}
+
+// d_members: n argument blocks on the device, each with its own xchg words inside [xchg, xchg + xchg_words): ONE memset clears them all
+hipError_t launch_ppo_update_small_pop(int kind, const SmallUpdateArgs* d_members, int n, unsigned long long* xchg, size_t xchg_words, hipStream_t s) {
+    if (!d_members || !xchg || n < 1) return hipErrorInvalidValue;
+    { hipError_t e = hipMemsetAsync(xchg, 0, sizeof(unsigned long long) * xchg_words, s); if (e != hipSuccess) return e; }
+    return with_env_kind<KindShare::Shape>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;
+        const size_t lds = update_small_lds_bytes<KIND>();
+        { hipError_t e = set_max_dynamic_lds((const void*)ppo_update_small_pop_kernel<KIND>, lds); if (e != hipSuccess) return e; }
+        ppo_update_small_pop_kernel<KIND><<<pop_grid(n), 256, lds, s>>>(d_members, n);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace dril

@@ -508,7 +508,7 @@ class Handle:
 
     def close(self):
         if self._h:
-            self.lib.dril_destroy(self._h)
+            self._chk(self.lib.dril_destroy(self._h))      # refused while the handle is a member of a Population: close the population first
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -1013,6 +1013,76 @@ class Handle:
 # --------------------------------------------------------------------------------------------
 # DeviceParallelEnv <: AbstractParallelEnv (interfaces/environments.jl:21-39)
 # --------------------------------------------------------------------------------------------
+class Population:
+    """Owns one dril_population*: ordinary PPO handles joined for batched launches (include/dril_hip.h, docs/population.md).  Every member is bit-identical to the
+    same handle driven alone; the handles stay the caller's and every Handle method works on a member between population calls.  close() (or leaving the `with`
+    block) releases the population, never the members; a member cannot be closed while it is joined."""
+
+    def __init__(self, handles: Sequence[Handle]):
+        handles = list(handles)
+        if not handles:
+            raise ValueError("Population: at least one handle")
+        self.handles = handles
+        self.lib = handles[0].lib
+        self._p = C.c_void_p()
+        arr = (C.c_void_p * len(handles))(*[h._h for h in handles])
+        rc = self.lib.dril_population_join(arr, len(handles), C.byref(self._p))
+        if rc != capi.OK:
+            raise DrilError(rc, (self.lib.dril_population_last_error(None) or b"").decode())
+
+    def __len__(self):
+        return len(self.handles)
+
+    def close(self):
+        if self._p:
+            self.lib.dril_population_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc: int):
+        if rc != capi.OK:
+            raise DrilError(rc, (self.lib.dril_population_last_error(self._p) or b"").decode())
+
+    def collect_rollout(self) -> list:
+        """dril_collect_rollout of every member in one launch; returns the members' fps"""
+        fps = (C.c_double * len(self))()
+        self._chk(self.lib.dril_population_collect_rollout(self._p, fps))
+        return list(fps)
+
+    def ppo_update(self) -> list:
+        """dril_ppo_update of every member in one launch per `cap` members; returns the members' DrilPPOStats"""
+        st = (DrilPPOStats * len(self))()
+        self._chk(self.lib.dril_population_ppo_update(self._p, st))
+        return list(st)
+
+    def train(self, max_steps: int):
+        """dril_train of every member: (stats[iteration][member], fps[iteration][member]) of the iterations that completed"""
+        n = len(self)
+        iters = max_steps // self.handles[0].N
+        stats = (DrilPPOStats * (max(iters, 1) * n))()
+        fps = (C.c_double * (max(iters, 1) * n))()
+        done = C.c_int32()
+        self._chk(self.lib.dril_population_train(self._p, max_steps, stats, fps, C.byref(done)))
+        return ([[stats[i * n + m] for m in range(n)] for i in range(done.value)], [[fps[i * n + m] for m in range(n)] for i in range(done.value)])
+
+    def info(self) -> dict:
+        i = capi.DrilPopulationInfo()
+        self._chk(self.lib.dril_population_info(self._p, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in i._fields_ if k != "reserved"}
+
+
 class DeviceParallelEnv:
     """Device-resident batched simulator standing in for
     `MultiThreadedParallelEnv([CartPoleEnv() for _ in 1:n_envs])`.  The env verbs keep the reference's
@@ -1733,6 +1803,80 @@ def train_(agent: Agent, env: DeviceParallelEnv, alg: PPO, max_steps: int, callb
         except DrilError:
             if primary is None:
                 raise
+
+
+def train_population_(agents: Sequence[Agent], envs: Sequence[DeviceParallelEnv], algs: Sequence[PPO], max_steps: int):
+    """The list form of train_: train_population_(agents, envs, algs, max_steps) -> [(learn_stats, timer), ...], one pair per agent, each equal to what
+    train_(agents[i], envs[i], algs[i], max_steps) returns and leaves behind (parameters and optimiser state are copied back on every exit path) — but every
+    iteration of all agents is one batched rollout launch and one batched update launch (Population, docs/population.md).  The envs are DeviceParallelEnv of one
+    built-in kind and shape; the algs may differ in everything the kernels take at run time (learning rate, gamma, clip ranges, coefficients, target_kl, ...).
+    Callbacks are out of scope here: hooks observe and steer one agent's loop step by step, so per-member train_ remains the way to use them.  `timer` holds the
+    wall seconds of the whole population (the members share every launch)."""
+    agents, envs, algs = list(agents), list(envs), list(algs)
+    if not agents:
+        raise ValueError("train_population_: empty population")
+    if not (len(agents) == len(envs) == len(algs)):
+        raise ValueError(f"train_population_: {len(agents)} agents, {len(envs)} envs and {len(algs)} algs: one of each per member")
+    for e in envs:
+        if type(e) is not DeviceParallelEnv:
+            raise TypeError("train_population_: members train on DeviceParallelEnv of a built-in kind (plug-in, host and device-array envs: train_ per member)")
+    t0 = time.perf_counter()
+    handles = []
+    for agent, env, alg in zip(agents, envs, algs):
+        h = env.bind(alg, agent.layer)
+        h.set_params(flatten_params(agent.train_state.parameters))
+        h.set_optimizer_state(agent.train_state.optimizer_state)
+        handles.append(h)
+    per_iter = algs[0].n_steps * envs[0].n_envs
+    results = [({k: [] for k in _STAT_KEYS}, {}) for _ in agents]
+    for env in envs:
+        env.last_f32_paths = []
+        env.last_monitor_stats = []
+    primary = None
+    try:
+        with Population(handles) as pop:
+            t_setup = time.perf_counter() - t0
+            t1 = time.perf_counter()
+            t_roll = t_upd = 0.0
+            for _ in range(max_steps // per_iter):  # ppo.jl:117
+                for h, alg, (ls, _t) in zip(handles, algs, results):
+                    h.set_learning_rate(alg.learning_rate)  # Optimisers.adjust!, ppo.jl:155-156
+                    ls["learning_rates"].append(alg.learning_rate)
+                a = time.perf_counter()
+                fps = pop.collect_rollout()  # ppo.jl:167
+                b = time.perf_counter()
+                sts = pop.ppo_update()  # ppo.jl:188-264
+                c = time.perf_counter()
+                t_roll += b - a
+                t_upd += c - b
+                for agent, env, f, st, (ls, _t) in zip(agents, envs, fps, sts, results):
+                    agent.steps_taken += per_iter
+                    agent.gradient_updates += st.n_updates
+                    ls["fps"].append(f)
+                    ls["entropy_losses"].append(st.entropy_loss)
+                    ls["policy_losses"].append(st.policy_loss)
+                    ls["value_losses"].append(st.value_loss)
+                    ls["approx_kl_divs"].append(st.approx_kl_div)
+                    ls["clip_fractions"].append(st.clip_fraction)
+                    ls["losses"].append(st.loss)
+                    ls["explained_variances"].append(st.explained_variance)
+                    ls["grad_norms"].append(st.grad_norm)
+                    env.last_f32_paths.append(int(st.f32_path))
+            for _ls, timer in results:
+                timer.update({"setup": t_setup, "training_loop": time.perf_counter() - t1, "collect_rollout": t_roll, "epoch loop": t_upd,
+                              "batch loop": t_upd, "compute_gradients": float("nan"), "apply_gradients": float("nan")})
+        return results
+    except BaseException as e:
+        primary = e
+        raise
+    finally:
+        for agent, h in zip(agents, handles):   # as train_: every exit path copies the device parameters back
+            try:
+                agent.train_state.parameters = unflatten_params(h.get_params(), agent.train_state.parameters)
+                agent.train_state.optimizer_state = h.get_optimizer_state()
+            except DrilError:
+                if primary is None:
+                    raise
 
 
 # keys of Base.@locals the reference's callback test reads (test/test_callbacks.jl:25-27 at training start, :36-39 at rollout start);

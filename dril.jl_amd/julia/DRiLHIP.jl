@@ -576,6 +576,74 @@ function train!(agent::PPOAgent, env::DeviceParallelEnv, alg::PPO{T}, max_steps:
 end
 
 
+# ---- populations: train!(agents::Vector, envs::Vector{<:DeviceParallelEnv}, algs::Vector{<:PPO}, max_steps)  (no reference counterpart: defined as P calls of train!) ----
+# struct dril_population_info (include/dril_hip.h)
+struct DrilPopulationInfo
+    members::Int32; cap::Int32; last_rollout_launches::Int32; last_update_launches::Int32; last_solo_rollouts::Int32; last_solo_updates::Int32
+    total_rollout_launches::Int64; total_update_launches::Int64; total_solo_rollouts::Int64; total_solo_updates::Int64
+    last_launches_per_iteration::Float64; last_rollout_ms::Float64; last_update_ms::Float64
+    reserved::NTuple{4, Int64}
+end
+population_error(p) = unsafe_string(ccall((:dril_population_last_error, LIB[]), Cstring, (Ptr{Cvoid},), p))
+check_population(rc::Int32, p = C_NULL) = rc == 0 ? nothing : error("libdril_hip status $rc: $(population_error(p))")
+"batched-launch counters of a population (dril_population_info)"
+function population_info(p::Ptr{Cvoid})
+    out = Ref{DrilPopulationInfo}()
+    check_population(ccall((:dril_population_info, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilPopulationInfo}), p, out), p)
+    return out[]
+end
+"""
+The list form of `train!`: P agents, each on its own DeviceParallelEnv of one built-in kind and shape, trained as one population — every iteration is one batched
+rollout launch and one batched update launch (docs/population.md), and every agent ends bit-identical to `train!(agents[i], envs[i], algs[i], max_steps)`.
+Returns a vector of `(learn_stats, to)`; the TimerOutput is the population's (the members share every launch).  Callbacks are out of scope: per-member `train!`
+remains the way to use hooks.  Static-checked only, as everything in this file (tools/check_shim.py).
+"""
+function train!(agents::Vector, envs::Vector{<:DeviceParallelEnv}, algs::Vector{<:PPO}, max_steps::Int)
+    P = length(agents)
+    (P >= 1 && length(envs) == P && length(algs) == P) || throw(ArgumentError("train!: $(length(agents)) agents, $(length(envs)) envs and $(length(algs)) algs: one of each per member, at least one"))
+    to = TimerOutput()
+    n_steps = algs[1].n_steps; n_envs = envs[1].n_envs
+    pop = Ref{Ptr{Cvoid}}(C_NULL)
+    stats = [NamedTuple{(:entropy_losses, :policy_losses, :value_losses, :approx_kl_divs, :clip_fractions, :losses,
+        :explained_variances, :fps, :grad_norms, :learning_rates)}(ntuple(_ -> Float32[], 10)) for _ in 1:P]
+    try
+        @timeit to "setup" begin
+            for m in 1:P
+                bind_agent!(envs[m], agents[m], algs[m]); push_params!(envs[m], agents[m])
+                if !push_optimizer_state!(envs[m], agents[m]) && envs[m].optimizer_owner !== agents[m].train_state
+                    check(ccall((:dril_reset_optimizer, LIB[]), Int32, (Ptr{Cvoid},), envs[m].handle), envs[m].handle)
+                end
+                envs[m].optimizer_owner = agents[m].train_state
+            end
+            handles = Ptr{Cvoid}[e.handle for e in envs]
+            GC.@preserve handles check_population(ccall((:dril_population_join, LIB[]), Int32, (Ptr{Ptr{Cvoid}}, Int32, Ref{Ptr{Cvoid}}), handles, Int32(P), pop))
+        end
+        iterations = max_steps ÷ (n_steps * n_envs)                    # ppo.jl:117
+        fps = Vector{Float64}(undef, P); st = Vector{DrilPPOStats}(undef, P)
+        @timeit to "training_loop" for it in 1:iterations
+            for m in 1:P
+                check(ccall((:dril_set_learning_rate, LIB[]), Int32, (Ptr{Cvoid}, Float32), envs[m].handle, algs[m].learning_rate), envs[m].handle)  # ppo.jl:155-156
+                push!(stats[m].learning_rates, algs[m].learning_rate)
+            end
+            @timeit to "collect_rollout" GC.@preserve fps check_population(ccall((:dril_population_collect_rollout, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Float64}), pop[], fps), pop[])
+            @timeit to "epoch loop" GC.@preserve st check_population(ccall((:dril_population_ppo_update, LIB[]), Int32, (Ptr{Cvoid}, Ptr{DrilPPOStats}), pop[], st), pop[])
+            for m in 1:P
+                s = st[m]; ls = stats[m]
+                push!(ls.fps, fps[m]); DRiL.add_step!(agents[m], n_steps * n_envs); DRiL.add_gradient_update!(agents[m], Int(s.n_updates))
+                push!(ls.entropy_losses, s.entropy_loss); push!(ls.policy_losses, s.policy_loss); push!(ls.value_losses, s.value_loss)
+                push!(ls.approx_kl_divs, s.approx_kl_div); push!(ls.clip_fractions, s.clip_fraction); push!(ls.losses, s.loss)
+                push!(ls.explained_variances, s.explained_variance); push!(ls.grad_norms, s.grad_norm)
+            end
+        end
+        return [(stats[m], to) for m in 1:P]
+    finally
+        pop[] != C_NULL && ccall((:dril_population_destroy, LIB[]), Int32, (Ptr{Cvoid},), pop[])
+        for m in 1:P                                                       # as train!: every exit leaves the agents with the weights trained so far
+            envs[m].handle != C_NULL && (pull_params!(envs[m], agents[m]); pull_optimizer_state!(envs[m], agents[m]))
+        end
+    end
+end
+
 include("DRiLHIP_host_envs.jl")     # OnDevice(env::AbstractParallelEnv): host envs, generic kernels
 include("DRiLHIP_extras.jl")        # normalisation statistics, evaluate_agent
 include("DRiLHIP_sac.jl")           # SAC

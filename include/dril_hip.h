@@ -654,6 +654,48 @@ int32_t dril_collect_trajectory_device(dril_handle* h, const dril_traj_options* 
  * stats / fps arrays need `iterations` entries (may be NULL) */
 int32_t dril_train(dril_handle* h, int64_t max_steps, dril_ppo_stats* stats, double* fps, int32_t* iterations_done);
 
+/* ---- populations: many small PPO agents per launch (new; the reference has no counterpart: defined as P calls of train!, docs/population.md) ---------------- */
+/* A population is a set of ordinary PPO handles joined for batched launches: where P solo iterations launch rollout_duo_kernel and ppo_update_small_kernel P times,
+ * a population launches rollout_duo_pop_kernel once and ppo_update_small_pop_kernel once per `cap` members (dril_population_info).  The per-member device code and
+ * arguments are those of the solo kernels, so every member is BIT-IDENTICAL to the same handle driven alone with dril_collect_rollout / dril_ppo_update / dril_train.
+ * Ownership: the members stay the caller's.  Between population calls every verb works on a member (dril_get_params, dril_evaluate_agent_device,
+ * dril_policy_from_handle, dril_set_learning_rate, dril_debug_set_noise / _set_permutation, ...); the population keeps no copy of member state and reads each handle
+ * when it builds the member's argument block.  dril_destroy of a joined member is refused (DRIL_ERR_INVALID_ARG): dril_population_destroy first.  A population and
+ * its members are driven from one host thread.
+ * Equal across members (they fix the kernel instance and the grid): env_kind (built-in kinds), n_envs, n_steps, batch_size, epochs, hidden dims, activation, device,
+ * normalize_advantage.  Free per member: seed, learning rate, gamma, gae_lambda, clip_range, clip_range_vf, ent_coef, vf_coef, max_grad_norm, target_kl (and their
+ * has_ flags), Adam betas / eps, monitor_window, parameters, optimiser state.
+ * dril_population_join refuses, naming the member index and the reason in dril_population_last_error(NULL), and leaves every handle as it was:
+ *   DRIL_ERR_UNSUPPORTED  an external handle, a device env plug-in handle or a world; a normalising handle; a generic or wide net; batch_size > 64; world_size > 1;
+ *                         a handle whose iteration is not one rollout_duo_kernel launch + one ppo_update_small_kernel launch (DRIL_GRAD_VARIANT, DRIL_FORCE_STEPWISE, ...)
+ *   DRIL_ERR_INVALID_ARG  n < 1 or n > DRIL_POPULATION_MAX, a null entry, the same handle twice, a handle already in a population, mixed kinds / shapes / devices
+ * A member that cannot take the batched launch in one iteration (a latched or out-of-range exact-f32 forward / update, a redo after a non-finite f16 step, a
+ * pair of workgroups that was not co-resident) runs ALONE through the solo code after the batched launches and is counted in dril_population_info.
+ * Errors: a member's error (DRIL_ERR_NAN_IN_GRADS, ...) does not stop the other members' iteration; the call returns the first failing member's status,
+ * dril_population_last_error names the member, the member's own dril_last_error says what a solo call would have said.  dril_population_train stops after the
+ * iteration in which a member failed. */
+#define DRIL_POPULATION_MAX 4096   /* members of one population; a verb runs ceil(n / cap) update launches */
+typedef struct dril_population dril_population;
+struct dril_population_info {     /* (a struct tag: dril_population_info is also the verb that fills it) */
+    int32_t members;
+    int32_t cap;                       /* members per ppo_update_small_pop_kernel launch: num_cus / 4 (two workgroups per member, one per CU, at most half the chip) */
+    int32_t last_rollout_launches, last_update_launches;   /* batched kernel launches of the last population call (an update of S optimiser steps: ceil(S / DRIL_SMALL_CHUNK) x ceil(n / cap)) */
+    int32_t last_solo_rollouts, last_solo_updates;         /* members run alone through the solo code in the last call */
+    int64_t total_rollout_launches, total_update_launches, total_solo_rollouts, total_solo_updates;   /* the same since join */
+    double last_launches_per_iteration;                    /* batched launches of the last call / the iterations it ran (collect_rollout and ppo_update count as one) */
+    double last_rollout_ms, last_update_ms;                /* HIP-event time of the batched kernels of the last call (member 0's cfg.profile_events != 0, else 0) */
+    int64_t reserved[4];
+};
+int32_t dril_population_join(dril_handle** members, int32_t n, dril_population** out);
+int32_t dril_population_destroy(dril_population* p);            /* members stay alive and usable */
+const char* dril_population_last_error(const dril_population* p);   /* NULL: the last refusal of dril_population_join on this thread */
+/* dril_collect_rollout / dril_ppo_update of every member; fps / out: n entries, may be NULL */
+int32_t dril_population_collect_rollout(dril_population* p, double* fps);
+int32_t dril_population_ppo_update(dril_population* p, dril_ppo_stats* out);
+/* dril_train of every member: iterations = max_steps / (T*E) of {set lr, collect, update}; stats / fps: [iteration][member], iterations x n entries (may be NULL) */
+int32_t dril_population_train(dril_population* p, int64_t max_steps, dril_ppo_stats* stats, double* fps, int32_t* iterations_done);
+int32_t dril_population_info(const dril_population* p, struct dril_population_info* out);
+
 /* ---- multi-GPU (new; the reference is single-process) ------------------------- */
 /* 128-byte ncclUniqueId from rank 0, distributed to the other ranks by the host */
 int32_t dril_comm_unique_id(uint8_t id[128]);
