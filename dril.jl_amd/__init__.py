@@ -15,7 +15,7 @@ from . import _capi  # noqa: F401
 from .host import (  # noqa: F401
     AcrobotEnv, Agent, ActorCriticLayer, Box, CartPoleEnv, ContinuousActorCriticLayer, DeviceArrayParallelEnv, DeviceModuleEnv, DeviceParallelEnv, Discrete, HostParallelEnv,
     DiscreteActorCriticLayer, DrilError, Handle, MonitorWrapperEnv, MountainCarContinuousEnv, MountainCarEnv, NormalizeWrapperEnv, PendulumEnv, Population, PPO, RolloutBuffer, ScalingWrapperEnv, collect_rollout_,
-    collect_trajectory, describe_env_module, evaluate_agent, flatten_params, get_action_and_values, get_original_obs, get_original_rewards, make_config, predict_values, train_, train_population_, unflatten_params,
+    collect_trajectory, describe_env_module, evaluate_agent, evaluate_population, flatten_params, get_action_and_values, get_original_obs, get_original_rewards, make_config, predict_values, train_, train_population_, unflatten_params,
     unnormalize_obs_, unnormalize_rewards_, TRAINING_START_LOCALS, ROLLOUT_START_LOCALS, TIMER_SECTIONS,
 )
 from .sac import (  # noqa: F401

@@ -89,6 +89,12 @@ class DrilEvalInfo(C.Structure):
     _fields_ = [("path", C.c_int32), ("launches", C.c_int32), ("steps_enqueued", C.c_int32), ("events", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class DrilPopulationEvalInfo(C.Structure):
+    """struct dril_population_eval_info, include/dril_hip.h"""
+    _fields_ = [("launches", C.c_int32), ("looks", C.c_int32), ("batched_members", C.c_int32), ("solo_members", C.c_int32), ("kernel_ms", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+
 class DrilTrajOptions(C.Structure):
     """struct dril_traj_options, include/dril_hip.h"""
     _fields_ = [("n_trajectories", C.c_int32), ("max_steps", C.c_int32), ("deterministic", C.c_int32), ("has_seed", C.c_int32), ("seed", C.c_uint64),
@@ -320,6 +326,8 @@ _SIG = {
     "dril_population_ppo_update": (C.c_int32, [_P, _P]),
     "dril_population_train": (C.c_int32, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     "dril_population_info": (C.c_int32, [_P, C.POINTER(DrilPopulationInfo)]),
+    "dril_population_evaluate_device": (C.c_int32, [_P, C.POINTER(DrilEvalOptions), C.POINTER(DrilEvalStats), _P, _P, C.POINTER(DrilEvalInfo),
+                                                    C.POINTER(DrilPopulationEvalInfo)]),
     "dril_comm_unique_id": (C.c_int32, [_P]),
     "dril_comm_init": (C.c_int32, [_P, _P]),
     "dril_comm_ranks": (C.c_int32, [_P]),

@@ -2500,23 +2500,75 @@ int eval_poll_steps(const dril_handle* h, const dril_eval_options* o, bool persi
     if (persistent) K = (int)std::max<long long>(1, std::min<long long>(K, kEvalMaxLaunchEvents / std::max(1, h->cfg.n_envs)));
     return K;
 }
-int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent, bool fused, bool raw, int K, long long cap, std::vector<SacEvalEvent>& events, dril_eval_info* info) {
-    const int E = h->cfg.n_envs, n_eval = o->n_eval_episodes;
+// ---- the pieces of dril_evaluate_agent_device, in the order it runs them: prepare, set-aside, reset, enqueue, put-back, reduce.  dril_population_evaluate_device
+// calls the same pieces per member (as pop_collect / pop_update call rollout_args / update_begin), so a member's evaluation is that of its handle alone ----
+struct EvalPlan { bool persistent, fused, raw; int K; long long cap; EvalKeep keep; };
+// prepare: which path runs, K, the list's capacity, what the call will set aside, the buffers
+int eval_prepare(dril_handle* h, const dril_eval_options* o, EvalPlan& pl) {
+    { int rc = ensure_wimg(h); if (rc) return rc; }
+    pl.persistent = !o->force_step_granular && eval_persistent_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);
+    pl.fused = !o->force_step_granular && eval_fused_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);   // path 2: a plug-in's own evaluation kernel (never both)
+    pl.raw = (h->env.module && h->pn.on) || h->mon_cur_ret != nullptr;                  // dril_evaluate_agent's rule: raw returns under the monitor (and under a plug-in's normaliser)
+    eval_keep_list(h, pl.persistent || pl.fused, pl.keep);                             // (path 2 writes the envs and scratch of its own: the per-step arrays are not touched)
+    pl.K = eval_poll_steps(h, o, pl.persistent || pl.fused);
+    pl.cap = eval_event_capacity(o->n_eval_episodes, h->cfg.n_envs, (pl.persistent || pl.fused) ? pl.K : 1);   // (path 0: one launch per env step)
+    return eval_buffers(h, pl.keep, pl.cap);
+}
+// set-aside: the evaluation runs on the handle's own envs — what training would continue from is kept here and put back by eval_put_back, on every path
+int eval_set_aside(dril_handle* h, EvalKeep& keep) {
+    keep.seed0 = h->env.seed0; keep.ready = h->env.ready; keep.obs_par = h->obs_par; keep.ret_par = h->ret_par; keep.norm_training = h->cfg.norm_training;
+    keep.pn_training = h->pn.cfg.training; keep.mon_cur_ret = h->mon_cur_ret; keep.gws_launches = h->gws.launches;
+    { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
+    h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false): the statistics in force, frozen; `returns` stands still
+    h->mon_cur_ret = nullptr;                                                          // evaluation episodes do not enter the training env's MonitorWrapperEnv: its launches are not made
+    return DRIL_OK;
+}
+// reset: the call's seed, reset!(env) (:87), zeroed accounting.  counter: the device word the kernels count in (the handle's own, or its word of a population's array)
+int eval_reset(dril_handle* h, const dril_eval_options* o, unsigned int* counter, long long cap, EvalAcct& acct) {
+    const int E = h->cfg.n_envs;
     if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
     HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :87
     h->env.ready = true;
-    HIPCHK(h, hipMemsetAsync(h->eval_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_cur_len, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
-    const EvalAcct acct{E, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, (unsigned int)cap};
+    HIPCHK(h, hipMemsetAsync(h->eval_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_cur_len, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(counter, 0, 4, h->stream));
+    acct = EvalAcct{E, h->eval_cur_ret, h->eval_cur_len, counter, h->eval_events, (unsigned int)cap};
+    return DRIL_OK;
+}
+// every env finishes an episode within the time limit, so n of them take at most ceil(n / E) time limits; one more, and the steps enqueued past a look
+long long eval_max_steps(const dril_handle* h, int n_eval, int K) {
+    const int E = h->cfg.n_envs;
+    return ((long long)(n_eval + E - 1) / E + 1) * (long long)h->env.episode_len + K;
+}
+// enqueue (path 1): the argument block of the launches of K steps; step0 is set per launch
+void eval_persistent_args(const dril_handle* h, const dril_eval_options* o, int K, const EvalAcct& acct, EvalKernelArgs& g) {
+    eval_kernel_args(h, g, o->deterministic); g.r.T = K; g.acct = acct;           // (after the seed of eval_reset: env_seed0 is the one the reset used)
+}
+// put-back: the host-side words, and the copies home enqueued (the caller drains the stream)
+int eval_put_back(dril_handle* h, const EvalKeep& keep) {
+    h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
+    h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
+    return eval_keep_copy(h, keep, false);
+}
+// reduce: the first n_eval_episodes events in (step, env) order
+void eval_reduce(SacEvalEvent* events, int64_t n_events, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) {
+    SacEvalSummary sum{};
+    sac_eval_reduce(events, n_events, o->n_eval_episodes, &sum, ep_rewards, ep_lengths);
+    out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
+    out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
+}
+int eval_device_run(dril_handle* h, const dril_eval_options* o, const EvalPlan& pl, std::vector<SacEvalEvent>& events, dril_eval_info* info) {
+    const bool persistent = pl.persistent, fused = pl.fused, raw = pl.raw; const int K = pl.K; const long long cap = pl.cap;
+    const int E = h->cfg.n_envs, n_eval = o->n_eval_episodes;
+    EvalAcct acct{};
+    { int rc = eval_reset(h, o, h->eval_counter, cap, acct); if (rc) return rc; }
     EvalKernelArgs g{}; EvalModeArgs x{}; DrilEnvEvaluateArgs gf{};
     const bool modes = persistent && normalizing(h);                              // a frozen normaliser: evaluate_modes_kernel; otherwise evaluate_kernel as ever
     if (fused) { int rc = eval_fused_args(h, gf, o->deterministic, K, 0, nullptr); if (rc) return rc; }   // (the kernel opens every launch with its own observe)
     else if (persistent) {
-        eval_kernel_args(h, g, o->deterministic); g.r.T = K; g.acct = acct;       // (after the seed above: env_seed0 is the one the reset used)
+        eval_persistent_args(h, o, K, acct, g);
         if (modes) eval_mode_norm(h, x, raw);
     } else if (normalizing(h) || h->pn.on) { int rc = observe_dev(h, true); if (rc) return rc; }   // observations = observe(env), :88
     else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
-    // every env finishes an episode within the time limit, so n of them take at most ceil(n / E) time limits; one more, and the steps enqueued past a look
-    const long long max_steps = ((long long)(n_eval + E - 1) / E + 1) * (long long)h->env.episode_len + K;
+    const long long max_steps = eval_max_steps(h, n_eval, K);
     long long steps = 0; unsigned int seen = 0; int32_t launches = 0;
     while (seen < (unsigned int)n_eval) {
         if (steps >= max_steps) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_evaluate_agent_device: no episode finishes");
@@ -2538,6 +2590,7 @@ int eval_device_run(dril_handle* h, const dril_eval_options* o, bool persistent,
     if (info) { info->path = fused ? 2 : persistent ? 1 : 0; info->launches = launches; info->steps_enqueued = (int32_t)steps; info->events = (int32_t)seen; }
     return DRIL_OK;
 }
+const char* const kEvalArgMsg = "dril_evaluate_agent_device: options and out != NULL, n_eval_episodes >= 1, poll_steps >= 0";
 }  // namespace
 DRIL_EXPORT int32_t dril_eval_options_default(dril_eval_options* o) {
     if (!o) return DRIL_ERR_INVALID_ARG;
@@ -2547,35 +2600,19 @@ DRIL_EXPORT int32_t dril_eval_options_default(dril_eval_options* o) {
 }
 DRIL_EXPORT int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths, dril_eval_info* info) {
     NEED(h); NOT_EXTERNAL(h, "dril_evaluate_agent");
-    if (!o || !out || o->n_eval_episodes < 1 || o->poll_steps < 0) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent_device: options and out != NULL, n_eval_episodes >= 1, poll_steps >= 0");
+    if (!o || !out || o->n_eval_episodes < 1 || o->poll_steps < 0) return fail(h, DRIL_ERR_INVALID_ARG, kEvalArgMsg);
     if (info) std::memset(info, 0, sizeof(*info));
-    { int rc = ensure_wimg(h); if (rc) return rc; }
-    const bool persistent = !o->force_step_granular && eval_persistent_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);
-    const bool fused = !o->force_step_granular && eval_fused_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);   // path 2: a plug-in's own evaluation kernel (never both)
-    const bool raw = (h->env.module && h->pn.on) || h->mon_cur_ret != nullptr;         // dril_evaluate_agent's rule: raw returns under the monitor (and under a plug-in's normaliser)
-    EvalKeep keep; eval_keep_list(h, persistent || fused, keep);                       // (path 2 writes the envs and scratch of its own: the per-step arrays are not touched)
-    const int K = eval_poll_steps(h, o, persistent || fused);
-    const long long cap = eval_event_capacity(o->n_eval_episodes, h->cfg.n_envs, (persistent || fused) ? K : 1);   // (path 0: one launch per env step)
-    { int rc = eval_buffers(h, keep, cap); if (rc) return rc; }
-    // the evaluation runs on the handle's own envs: what training would continue from is set aside here and put back below, on every path
-    keep.seed0 = h->env.seed0; keep.ready = h->env.ready; keep.obs_par = h->obs_par; keep.ret_par = h->ret_par; keep.norm_training = h->cfg.norm_training;
-    keep.pn_training = h->pn.cfg.training; keep.mon_cur_ret = h->mon_cur_ret; keep.gws_launches = h->gws.launches;
-    { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
-    h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false): the statistics in force, frozen; `returns` stands still
-    h->mon_cur_ret = nullptr;                                                          // evaluation episodes do not enter the training env's MonitorWrapperEnv: its launches are not made
+    EvalPlan pl;
+    { int rc = eval_prepare(h, o, pl); if (rc) return rc; }
+    { int rc = eval_set_aside(h, pl.keep); if (rc) return rc; }
     std::vector<SacEvalEvent> events;
-    const int rc = eval_device_run(h, o, persistent, fused, raw, K, cap, events, info);
+    const int rc = eval_device_run(h, o, pl, events, info);
     const std::string msg = h->err;
-    h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
-    h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
-    int rr = eval_keep_copy(h, keep, false);
+    int rr = eval_put_back(h, pl.keep);
     if (rr == DRIL_OK) { const hipError_t e = hipStreamSynchronize(h->stream); if (e != hipSuccess) rr = fail(h, DRIL_ERR_HIP, std::string("dril_evaluate_agent_device: ") + hipGetErrorString(e)); }
     if (rc != DRIL_OK) { h->err = msg; return rc; }
     if (rr != DRIL_OK) return rr;
-    SacEvalSummary sum{};
-    sac_eval_reduce(events.data(), (int64_t)events.size(), o->n_eval_episodes, &sum, ep_rewards, ep_lengths);
-    out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
-    out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
+    eval_reduce(events.data(), (int64_t)events.size(), o, out, ep_rewards, ep_lengths);
     return DRIL_OK;
 }
 
@@ -2844,6 +2881,10 @@ struct dril_population {
     std::vector<char*> home_blocks; std::vector<UpdateHome> homes;   // one pinned block per member: where its update's results land
     std::vector<int> failed;                                     // status of a member that failed in the current call (it sits out the rest of the iteration)
     struct dril_population_info info{};
+    EvalKernelArgs *h_eargs = nullptr, *d_eargs = nullptr;       // dril_population_evaluate_device: pinned / device [n]
+    unsigned int *eval_counters = nullptr, *h_eval_counters = nullptr;   // device / pinned [n]: member m's EvalAcct.counter is word m, looked at with ONE copy per K env steps
+    SacEvalEvent* h_eval_events = nullptr; size_t h_eval_events_cap = 0;   // pinned, grow-only: where the members' event lists land
+    double eval_ms = 0;                                          // HIP-event time of the evaluate_pop_kernel launches of the last evaluation
     struct Ev { int kind; hipEvent_t a, b; }; std::vector<Ev> ev_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     std::string err;
 };
@@ -2882,6 +2923,8 @@ void pop_release(dril_population* p) {
     for (char* b : p->home_blocks) if (b) (void)hipHostFree(b);
     if (p->h_rargs) (void)hipHostFree(p->h_rargs); if (p->h_uargs) (void)hipHostFree(p->h_uargs);
     if (p->d_rargs) (void)hipFree(p->d_rargs); if (p->d_uargs) (void)hipFree(p->d_uargs); if (p->xchg) (void)hipFree(p->xchg);
+    if (p->h_eargs) (void)hipHostFree(p->h_eargs); if (p->h_eval_counters) (void)hipHostFree(p->h_eval_counters); if (p->h_eval_events) (void)hipHostFree(p->h_eval_events);
+    if (p->d_eargs) (void)hipFree(p->d_eargs); if (p->eval_counters) (void)hipFree(p->eval_counters);
     for (auto& e : p->ev_pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
     for (auto& e : p->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -2900,7 +2943,7 @@ void pop_ev_end(dril_population* p) { if (p->members[0]->cfg.profile_events && !
 int pop_sync(dril_population* p) {
     POPCHK(p, hipStreamSynchronize(p->stream));
     for (auto& e : p->ev_pending) {
-        float ms = 0; if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) (e.kind == 0 ? p->info.last_rollout_ms : p->info.last_update_ms) += ms;
+        float ms = 0; if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) (e.kind == 0 ? p->info.last_rollout_ms : e.kind == 1 ? p->info.last_update_ms : p->eval_ms) += ms;
         p->ev_pool.push_back({e.a, e.b});
     }
     p->ev_pending.clear();
@@ -3030,6 +3073,95 @@ int pop_update(dril_population* p, dril_ppo_stats* out, int& first) {
     }
     return DRIL_OK;
 }
+// dril_evaluate_agent_device of every member, with the pieces of the solo verb (eval_prepare .. eval_reduce).  The members whose evaluation is evaluate_kernel on the
+// f16-piece forward share ONE evaluate_pop_kernel launch and ONE look at the n counters per K env steps; a member that has its episodes sits out the later launches
+// (T = 0).  The others (exact-f32 forward, force_step_granular, DRIL_FORCE_STEPWISE) run the solo verb after the batched loop
+int pop_evaluate(dril_population* p, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths, dril_eval_info* member_info,
+                 dril_population_eval_info* info, int& first) {
+    const char* verb = "dril_population_evaluate_device";
+    const int n = (int)p->members.size(), n_eval = o->n_eval_episodes;
+    struct Run { int m; EvalPlan pl; EvalKernelArgs g; long long steps, max_steps; unsigned int seen; int32_t launches; bool done; size_t ev_off, ev_n; };
+    std::vector<Run> batched; std::vector<int> solo;
+    for (int m = 0; m < n; ++m) {
+        dril_handle* h = p->members[m];
+        std::memset(&out[m], 0, sizeof(dril_eval_stats));
+        if (member_info) std::memset(&member_info[m], 0, sizeof(dril_eval_info));
+        Run r{}; r.m = m;
+        int rc = eval_prepare(h, o, r.pl);
+        if (rc) { pop_member_failed(p, m, rc, verb, first); continue; }
+        if (!r.pl.persistent || r.pl.fused || normalizing(h) || fwd_exact(h) || h->cfg.hidden1 != 64) { solo.push_back(m); continue; }   // not evaluate_kernel<K, 64, false, true>: alone, below
+        rc = eval_set_aside(h, r.pl.keep);
+        if (rc) { pop_member_failed(p, m, rc, verb, first); continue; }
+        EvalAcct acct{};
+        rc = eval_reset(h, o, p->eval_counters + batched.size(), r.pl.cap, acct);
+        if (!rc) { eval_persistent_args(h, o, r.pl.K, acct, r.g); r.max_steps = eval_max_steps(h, n_eval, r.pl.K); }
+        else { pop_member_failed(p, m, rc, verb, first); r.done = true; }              // (set aside already: it is put back with the others, and takes no launch)
+        batched.push_back(std::move(r));
+    }
+    const int nbat = (int)batched.size();
+    hipError_t e = hipSuccess;
+    // per round: the blocks built in pinned memory (a member that has its episodes, or ran into its bound, gets T = 0), ONE copy to the device, ONE launch, ONE copy
+    // of the counters home, ONE synchronise
+    for (;;) {
+        int active = 0;
+        for (int k = 0; k < nbat; ++k) {
+            Run& r = batched[k]; dril_handle* h = p->members[r.m];
+            if (!r.done && r.seen >= (unsigned int)n_eval) r.done = true;
+            if (!r.done && r.steps >= r.max_steps) { r.done = true; pop_member_failed(p, r.m, fail(h, DRIL_ERR_UNSUPPORTED, "dril_evaluate_agent_device: no episode finishes"), verb, first); }
+            EvalKernelArgs& g = p->h_eargs[k];
+            g = r.g; g.r.T = r.done ? 0 : r.pl.K; g.step0 = (int32_t)r.steps;
+            if (!r.done) { ++active; r.steps += r.pl.K; r.launches += 1; }
+        }
+        if (active == 0) break;
+        e = hipMemcpyAsync(p->d_eargs, p->h_eargs, sizeof(EvalKernelArgs) * (size_t)nbat, hipMemcpyHostToDevice, p->stream);
+        pop_ev_begin(p, 2);
+        if (e == hipSuccess) e = launch_evaluate_pop(p->members[0]->cfg.env_kind, p->d_eargs, nbat, p->members[0]->cfg.n_envs, p->stream);
+        pop_ev_end(p);
+        if (e == hipSuccess) e = hipMemcpyAsync(p->h_eval_counters, p->eval_counters, sizeof(unsigned int) * (size_t)nbat, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+        if (info) { info->launches += 1; info->looks += 1; }
+        if (e != hipSuccess) break;
+        for (int k = 0; k < nbat; ++k) if (!batched[k].done) batched[k].seen = p->h_eval_counters[k];
+    }
+    if (e != hipSuccess)
+        for (Run& r : batched) if (!p->failed[r.m]) pop_member_failed(p, r.m, fail(p->members[r.m], DRIL_ERR_HIP, std::string("evaluate_pop_kernel: ") + hipGetErrorString(e)), verb, first);
+    // the event lists home (one pinned area for all members), then every member's state put back; ONE drain
+    size_t total = 0;
+    for (Run& r : batched) { r.ev_off = total; r.ev_n = p->failed[r.m] ? 0 : (size_t)std::min<long long>(r.seen, r.pl.cap); total += r.ev_n; }
+    if (total > p->h_eval_events_cap) {
+        if (p->h_eval_events) (void)hipHostFree(p->h_eval_events);
+        p->h_eval_events = nullptr; p->h_eval_events_cap = 0;
+        if (hipHostMalloc((void**)&p->h_eval_events, total * sizeof(SacEvalEvent), hipHostMallocDefault) == hipSuccess) p->h_eval_events_cap = total;
+    }
+    for (Run& r : batched) {
+        dril_handle* h = p->members[r.m];
+        const std::string msg = h->err;
+        int rc = DRIL_OK;
+        if (r.ev_n > 0) {
+            if (!p->h_eval_events) rc = fail(h, DRIL_ERR_HIP, "dril_population_evaluate_device: no pinned memory for the event lists");
+            else { const hipError_t ce = hipMemcpyAsync(p->h_eval_events + r.ev_off, h->eval_events, r.ev_n * sizeof(SacEvalEvent), hipMemcpyDeviceToHost, p->stream);
+                   if (ce != hipSuccess) rc = fail(h, DRIL_ERR_HIP, std::string("dril_population_evaluate_device: ") + hipGetErrorString(ce)); }
+        }
+        const int rr = eval_put_back(h, r.pl.keep);
+        if (p->failed[r.m]) h->err = msg;                                               // what the solo call would have said
+        else if (rc || rr) pop_member_failed(p, r.m, rc ? rc : rr, verb, first);
+    }
+    if (nbat > 0) { const int rc = pop_sync(p); if (rc) { for (Run& r : batched) if (!p->failed[r.m]) p->failed[r.m] = rc; if (first == DRIL_OK) first = rc; } }
+    for (Run& r : batched) {
+        if (p->failed[r.m]) continue;
+        eval_reduce(p->h_eval_events + r.ev_off, (int64_t)r.ev_n, o, &out[r.m], ep_rewards ? ep_rewards + (size_t)r.m * n_eval : nullptr, ep_lengths ? ep_lengths + (size_t)r.m * n_eval : nullptr);
+        if (member_info) { dril_eval_info& mi = member_info[r.m]; mi.path = 1; mi.launches = r.launches; mi.steps_enqueued = (int32_t)r.steps; mi.events = (int32_t)r.seen; }
+        if (info) info->batched_members += 1;
+    }
+    for (int m : solo) {
+        const int rc = dril_evaluate_agent_device(p->members[m], o, &out[m], ep_rewards ? ep_rewards + (size_t)m * n_eval : nullptr, ep_lengths ? ep_lengths + (size_t)m * n_eval : nullptr,
+                                                  member_info ? &member_info[m] : nullptr);
+        if (info) info->solo_members += 1;
+        if (rc) pop_member_failed(p, m, rc, verb, first);
+    }
+    if (info) info->kernel_ms = p->eval_ms;
+    return DRIL_OK;
+}
 }  // namespace
 
 DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_population** out) {
@@ -3064,6 +3196,10 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
     JCHK(hipMalloc((void**)&p->d_rargs, sizeof(RolloutArgs) * (size_t)n));
     JCHK(hipMalloc((void**)&p->d_uargs, sizeof(SmallUpdateArgs) * (size_t)p->n_chunks * n));
     JCHK(dmalloc(&p->xchg, (size_t)n * kSmallXchgWords));
+    JCHK(hipHostMalloc((void**)&p->h_eargs, sizeof(EvalKernelArgs) * (size_t)n, hipHostMallocDefault));
+    JCHK(hipMalloc((void**)&p->d_eargs, sizeof(EvalKernelArgs) * (size_t)n));
+    JCHK(hipHostMalloc((void**)&p->h_eval_counters, sizeof(unsigned int) * (size_t)n, hipHostMallocDefault));
+    JCHK(dmalloc(&p->eval_counters, (size_t)n));
     p->home_blocks.assign((size_t)n, nullptr); p->homes.assign((size_t)n, UpdateHome{}); p->failed.assign((size_t)n, DRIL_OK);
     for (int m = 0; m < n; ++m) {
         const dril_handle* h = members[m];
@@ -3124,6 +3260,18 @@ DRIL_EXPORT int32_t dril_population_train(dril_population* p, int64_t max_steps,
     const int64_t ran = done + ((rc || first) ? 1 : 0);
     p->info.last_launches_per_iteration = ran > 0 ? (double)(p->info.last_rollout_launches + p->info.last_update_launches) / (double)ran : 0.0;
     if (iterations_done) *iterations_done = done;
+    return rc ? rc : first;
+}
+DRIL_EXPORT int32_t dril_population_evaluate_device(dril_population* p, const dril_eval_options* o, dril_eval_stats* out, float* episode_rewards, int32_t* episode_lengths,
+                                                    dril_eval_info* member_info, dril_population_eval_info* info) {
+    if (!p) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_population_evaluate_device: null population");
+    if (!o || !out || o->n_eval_episodes < 1 || o->poll_steps < 0) return pop_fail(p, DRIL_ERR_INVALID_ARG, "dril_population_evaluate_device: options and out != NULL, n_eval_episodes >= 1, poll_steps >= 0");
+    (void)hipSetDevice(p->device);
+    std::fill(p->failed.begin(), p->failed.end(), DRIL_OK);
+    p->eval_ms = 0;
+    if (info) std::memset(info, 0, sizeof(*info));
+    int first = DRIL_OK;
+    const int rc = pop_evaluate(p, o, out, episode_rewards, episode_lengths, member_info, info, first);
     return rc ? rc : first;
 }
 

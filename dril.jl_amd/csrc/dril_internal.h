@@ -174,6 +174,7 @@ hipError_t launch_norm_rew_apply(const NormRewArgs& a, hipStream_t s);
 hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_t s);
 bool rollout_duo_applies(int hidden, int E);   // launch_rollout runs rollout_duo_kernel (one launch, tiles of 32 envs on two waves) rather than rollout_kernel
 hipError_t launch_rollout_pop(int kind, const RolloutArgs* d_members, int n, int E, hipStream_t s);   // rollout_duo_pop_kernel: n members of a population, grid (tiles, n)
+hipError_t launch_evaluate_pop(int kind, const EvalKernelArgs* d_members, int n, int E, hipStream_t s);   // evaluate_pop_kernel: n members of a population, grid (blocks of 128 envs, n); a member with r.T <= 0 sits out
 // carry: gae_chunks(T) x E 64-bit words {tag | f32}, zero at allocation; tag: a non-zero number no earlier launch on this carry buffer used; err: device int, set to 1 if a
 // workgroup gave up waiting for its predecessor (the advantages it wrote are NaN)
 int gae_chunks(int T);

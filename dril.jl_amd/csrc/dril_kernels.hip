@@ -985,6 +985,20 @@ template <int KIND, int H, bool WIDE, bool SPLIT>
 __global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_kernel(EvalKernelArgs g) { evaluate_body<KIND, H, WIDE, SPLIT, false>(g, EvalModeArgs{}); }
 template <int KIND, int H, bool WIDE, bool SPLIT>
 __global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_modes_kernel(EvalKernelArgs g, EvalModeArgs x) { evaluate_body<KIND, H, WIDE, SPLIT, true>(g, x); }
+// n members of a population in one launch (dril_population_evaluate_device, docs/population.md): grid (blocks of 128 envs, members); a workgroup copies its member's
+// argument block (uniform loads), takes what it dereferences through the global address space once (pop_global) and runs the body above on it.  Blocks share nothing:
+// every member's event list, counter word and env arrays are its own, so each member's launch is evaluate_kernel on its handle alone.  A member whose block says
+// T <= 0 has its episodes (or failed): its workgroups leave before anything is staged or stored
+template <int KIND, int H, bool WIDE, bool SPLIT>
+__global__ __launch_bounds__(256, WIDE ? 1 : 2) void evaluate_pop_kernel(const EvalKernelArgs* __restrict__ members) {
+    EvalKernelArgs g = members[blockIdx.y];
+    if (g.r.T <= 0) return;
+    RolloutArgs& a = g.r;
+    a.params = pop_global(a.params); a.state = pop_global(a.state); a.step_count = pop_global(a.step_count); a.episode = pop_global(a.episode); a.gstep = pop_global(a.gstep);
+    a.noise = pop_global(a.noise); a.w2a_actor = pop_global(a.w2a_actor);
+    g.acct.cur_ret = pop_global(g.acct.cur_ret); g.acct.cur_len = pop_global(g.acct.cur_len); g.acct.counter = pop_global(g.acct.counter); g.acct.events = pop_global(g.acct.events);
+    evaluate_body<KIND, H, WIDE, SPLIT, false>(g, EvalModeArgs{});
+}
 
 // =============================================================================================
 // gae_scan_kernel — compute_advantages! (trajectory.jl:80-102) + returns = advantages + values (rollout_buffer.jl:87) over the time-major buffer.
@@ -1600,6 +1614,18 @@ hipError_t launch_evaluate(int kind, int hidden, const EvalKernelArgs& a, hipStr
     });
 #undef CALL
 #undef CALLS
+}
+// evaluate_pop_kernel: hidden 64 on the f16-piece forward only (what a population's members run); every member with the same E; LDS as the solo launcher's
+hipError_t launch_evaluate_pop(int kind, const EvalKernelArgs* d_members, int n, int E, hipStream_t s) {
+    if (!d_members || n < 1 || n > 65535 || E < 1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((E + 4 * kTile - 1) / (4 * kTile)), (unsigned)n);
+    return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;
+        const size_t lds = sizeof(float) * FwdLds<EnvSpec<KIND>::D, 64, EnvSpec<KIND>::A, false, true>::SIZE;
+        { hipError_t e = set_max_dynamic_lds((const void*)evaluate_pop_kernel<KIND, 64, false, true>, lds); if (e != hipSuccess) return e; }
+        evaluate_pop_kernel<KIND, 64, false, true><<<grid, 256, lds, s>>>(d_members);
+        return hipGetLastError();
+    });
 }
 
 int gae_chunks(int T) { return (T + kGaeRows - 1) / kGaeRows; }

@@ -1082,6 +1082,28 @@ class Population:
         self._chk(self.lib.dril_population_info(self._p, C.byref(i)))
         return {k: getattr(i, k) for k, _ in i._fields_ if k != "reserved"}
 
+    def evaluate(self, n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None, poll_steps: int = 0, force_step_granular: bool = False) -> list:
+        """Handle.evaluate_agent_device of every member, with one evaluate_pop_kernel launch and one look at the members' counters per K env steps
+        (dril_population_evaluate_device, docs/population.md "Evaluation") -> [(stats dict, episode_rewards, episode_lengths, info dict), ...] per member, each byte
+        for byte what the member's own evaluate_agent_device returns; nothing is left behind on any member.  seed=None: every member's own env seed in force;
+        a seed: the same for all members (common random numbers).  self.last_eval_info: launches, looks, batched_members, solo_members, kernel_ms."""
+        n = len(self)
+        o = capi.DrilEvalOptions()
+        rc = self.lib.dril_eval_options_default(C.byref(o))
+        if rc != capi.OK:
+            raise DrilError(rc, "dril_eval_options_default")
+        o.n_eval_episodes, o.deterministic, o.poll_steps, o.force_step_granular = int(n_eval_episodes), int(deterministic), int(poll_steps), int(bool(force_step_granular))
+        if seed is not None:
+            o.seed, o.has_seed = int(seed), 1
+        ne = max(int(n_eval_episodes), 1)
+        st = (capi.DrilEvalStats * n)(); mi = (capi.DrilEvalInfo * n)(); pi = capi.DrilPopulationEvalInfo()
+        er = np.empty((n, ne), np.float32); el = np.empty((n, ne), np.int32)
+        self.last_eval_info = None
+        self._chk(self.lib.dril_population_evaluate_device(self._p, C.byref(o), st, er.ctypes.data_as(C.c_void_p), el.ctypes.data_as(C.c_void_p), mi, C.byref(pi)))
+        self.last_eval_info = {k: getattr(pi, k) for k, _ in pi._fields_ if k != "reserved"}
+        return [(dict(mean_reward=s.mean_reward, std_reward=s.std_reward, mean_length=s.mean_length, std_length=s.std_length, n_steps=s.n_steps), er[m].copy(), el[m].copy(),
+                 dict(path=i.path, launches=i.launches, steps_enqueued=i.steps_enqueued, events=i.events)) for m, (s, i) in enumerate(zip(st, mi))]
+
 
 class DeviceParallelEnv:
     """Device-resident batched simulator standing in for
@@ -1954,6 +1976,35 @@ def evaluate_agent(agent: Agent, env: DeviceParallelEnv, n_eval_episodes: int = 
     if reward_threshold is not None and stats["mean_reward"] < reward_threshold:
         raise RuntimeError(f"Mean reward below threshold: {stats['mean_reward']:.2f} < {reward_threshold}")   # evaluation.jl:131-135
     return {k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} if return_stats else (er, el)
+
+
+def evaluate_population(agents: Sequence[Agent], envs: Sequence[DeviceParallelEnv], n_eval_episodes: int = 10, deterministic: bool = True, seed: Optional[int] = None,
+                        population: Optional[Population] = None) -> list:
+    """The list form of evaluate_agent(agent, env, isolated=True): one stats dict per agent (the keys of evaluate_agent(..., return_stats=True)), each equal to what
+    the per-agent call returns, with one batched launch and one look per K env steps for all of them (Population.evaluate, docs/population.md "Evaluation"); the
+    envs are left as they were.  Each env is bound as train_population_ binds it.  The handles are joined into a population for the call; handles that already are
+    joined are evaluated through the population the caller passes as `population=` (its members, in the order of `agents`).  seed=None: every env's own seed."""
+    agents, envs = list(agents), list(envs)
+    if not agents:
+        raise ValueError("evaluate_population: empty population")
+    if len(agents) != len(envs):
+        raise ValueError(f"evaluate_population: {len(agents)} agents and {len(envs)} envs: one of each per member")
+    for e in envs:
+        if type(e) is not DeviceParallelEnv:
+            raise TypeError("evaluate_population: members are DeviceParallelEnv of a built-in kind (plug-in, host and device-array envs: evaluate_agent per member)")
+    handles = []
+    for agent, env in zip(agents, envs):
+        h = env.bind(agent.alg, agent.layer)
+        h.set_params(flatten_params(agent.train_state.parameters))
+        handles.append(h)
+    if population is not None:
+        if len(population.handles) != len(handles) or any(a is not b for a, b in zip(population.handles, handles)):
+            raise ValueError("evaluate_population: population= must hold exactly the handles of `envs`, in the same order")
+        res = population.evaluate(n_eval_episodes, deterministic, seed)
+    else:
+        with Population(handles) as pop:
+            res = pop.evaluate(n_eval_episodes, deterministic, seed)
+    return [{k: stats[k] for k in ("mean_reward", "std_reward", "mean_length", "std_length")} for stats, _er, _el, _info in res]
 
 
 def _collect_trajectory(agent: Agent, env: DeviceParallelEnv, max_steps: Optional[int] = None, norm_env=None, deterministic: bool = True,

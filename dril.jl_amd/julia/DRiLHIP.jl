@@ -648,6 +648,39 @@ include("DRiLHIP_host_envs.jl")     # OnDevice(env::AbstractParallelEnv): host e
 include("DRiLHIP_extras.jl")        # normalisation statistics, evaluate_agent
 include("DRiLHIP_sac.jl")           # SAC
 
+# ---- populations: evaluate_agent(agents::Vector, envs::Vector{<:DeviceParallelEnv}; ...)  (behind the includes: the evaluation structs are DRiLHIP_extras.jl's) ----
+# struct dril_population_eval_info (include/dril_hip.h)
+struct DrilPopulationEvalInfo
+    launches::Int32; looks::Int32; batched_members::Int32; solo_members::Int32
+    kernel_ms::Float64
+    reserved::NTuple{4, Int64}
+end
+"""
+The list form of `evaluate_agent(agent, env; isolated = true)`: the agents are joined into a population for the call and evaluated with one batched launch and one
+look at their counters per K env steps (dril_population_evaluate_device, docs/population.md "Evaluation").  Returns a vector of the reference's named tuples, each
+what the per-agent call returns; the envs are left as they were.  `seed = nothing`: every env's own seed; a seed: the same for every member.  Static-checked only.
+"""
+function DRiL.evaluate_agent(agents::Vector, envs::Vector{<:DeviceParallelEnv}; n_eval_episodes::Int = 10, deterministic::Bool = true, seed::Union{Nothing, Integer} = nothing)
+    P = length(agents)
+    (P >= 1 && length(envs) == P) || throw(ArgumentError("evaluate_agent: $(length(agents)) agents and $(length(envs)) envs: one of each per member, at least one"))
+    for m in 1:P
+        bind_agent!(envs[m], agents[m], agents[m].algorithm); push_params!(envs[m], agents[m])
+    end
+    pop = Ref{Ptr{Cvoid}}(C_NULL)
+    st = Vector{DrilEvalStats}(undef, P)
+    o = Ref(DrilEvalOptions(Int32(n_eval_episodes), Int32(deterministic), seed === nothing ? UInt64(0) : UInt64(seed), Int32(seed !== nothing), Int32(0), Int32(0), (Int32(0), Int32(0), Int32(0))))
+    try
+        handles = Ptr{Cvoid}[e.handle for e in envs]
+        GC.@preserve handles check_population(ccall((:dril_population_join, LIB[]), Int32, (Ptr{Ptr{Cvoid}}, Int32, Ref{Ptr{Cvoid}}), handles, Int32(P), pop))
+        GC.@preserve st check_population(ccall((:dril_population_evaluate_device, LIB[]), Int32,
+            (Ptr{Cvoid}, Ref{DrilEvalOptions}, Ptr{DrilEvalStats}, Ptr{Float32}, Ptr{Int32}, Ptr{DrilEvalInfo}, Ptr{DrilPopulationEvalInfo}),
+            pop[], o, st, C_NULL, C_NULL, C_NULL, C_NULL), pop[])
+    finally
+        pop[] != C_NULL && ccall((:dril_population_destroy, LIB[]), Int32, (Ptr{Cvoid},), pop[])
+    end
+    return [(; mean_reward = s.mean_reward, std_reward = s.std_reward, mean_length = s.mean_length, std_length = s.std_length) for s in st]
+end
+
 export DeviceParallelEnv, OnDevice, OnDeviceModule, describe_env_module, agents_per_world, n_worlds
 export DevicePolicy, extract_device_policy, extract_device_policy_sac
 

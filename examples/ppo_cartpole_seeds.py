@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """The reference README quick-start (4 envs, `PPO()` defaults: 2048 steps, batch 64, 10 epochs) for ten seeds as ONE population: every iteration of all ten
-agents is one batched rollout launch and one batched update launch (docs/population.md), and every agent ends bit-identical to its own `train_` call.
+agents is one batched rollout launch and one batched update launch (docs/population.md), and every agent ends bit-identical to its own `train_` call.  The seeds are then judged with `evaluate_population`: one batched
+launch and one look at the counters per K env steps for all of them.
 
-usage: python examples/ppo_cartpole_seeds.py [iterations=30] [seeds=10] [--serial]      (--serial: also time the same agents trained one after the other)"""
+usage: python examples/ppo_cartpole_seeds.py [iterations=30] [seeds=10] [--serial]      (--serial: also time the same agents trained and evaluated one after the other)"""
 import sys
 import time
 from pathlib import Path
@@ -28,9 +29,17 @@ t0 = time.perf_counter()
 results = pkg.train_population_(agents, envs, [alg] * seeds, max_steps)
 t_pop = time.perf_counter() - t0
 print(f"population of {seeds} seeds, {iters} iterations: {t_pop:.2f} s wall ({results[0][1]['training_loop']:.2f} s in the training loop)")
-for s, (agent, env) in enumerate(zip(agents, envs)):
-    ev = pkg.evaluate_agent(agent, env, n_eval_episodes=10)
+t0 = time.perf_counter()
+evs = pkg.evaluate_population(agents, envs, n_eval_episodes=10)   # all seeds in one batched launch per K env steps (docs/population.md, "Evaluation")
+t_eval = time.perf_counter() - t0
+print(f"evaluation of the {seeds} seeds as one population: {1e3 * t_eval:.1f} ms wall")
+for s, ev in enumerate(evs):
     print(f"  seed {s}: mean reward {ev['mean_reward']:.1f} +- {ev['std_reward']:.1f}, last loss {results[s][0]['losses'][-1]:.4f}")
+if "--serial" in sys.argv:
+    t0 = time.perf_counter()
+    each = [pkg.evaluate_agent(agent, env, n_eval_episodes=10, isolated=True) for agent, env in zip(agents, envs)]
+    t_each = time.perf_counter() - t0
+    print(f"the same evaluation, one evaluate_agent(isolated=True) per seed: {1e3 * t_each:.1f} ms wall ({t_each / t_eval:.2f} x the population); results equal: {each == evs}")
 if "--serial" in sys.argv:
     agents2, envs2 = fresh()
     t0 = time.perf_counter()

@@ -658,8 +658,9 @@ int32_t dril_train(dril_handle* h, int64_t max_steps, dril_ppo_stats* stats, dou
 /* A population is a set of ordinary PPO handles joined for batched launches: where P solo iterations launch rollout_duo_kernel and ppo_update_small_kernel P times,
  * a population launches rollout_duo_pop_kernel once and ppo_update_small_pop_kernel once per `cap` members (dril_population_info).  The per-member device code and
  * arguments are those of the solo kernels, so every member is BIT-IDENTICAL to the same handle driven alone with dril_collect_rollout / dril_ppo_update / dril_train.
- * Ownership: the members stay the caller's.  Between population calls every verb works on a member (dril_get_params, dril_evaluate_agent_device,
- * dril_policy_from_handle, dril_set_learning_rate, dril_debug_set_noise / _set_permutation, ...); the population keeps no copy of member state and reads each handle
+ * Ownership: the members stay the caller's.  Between population calls every verb works on a member (dril_get_params, dril_policy_from_handle,
+ * dril_set_learning_rate, dril_debug_set_noise / _set_permutation, ...; dril_evaluate_agent_device too, though the whole population is evaluated by one call of
+ * dril_population_evaluate_device below); the population keeps no copy of member state and reads each handle
  * when it builds the member's argument block.  dril_destroy of a joined member is refused (DRIL_ERR_INVALID_ARG): dril_population_destroy first.  A population and
  * its members are driven from one host thread.
  * Equal across members (they fix the kernel instance and the grid): env_kind (built-in kinds), n_envs, n_steps, batch_size, epochs, hidden dims, activation, device,
@@ -695,6 +696,33 @@ int32_t dril_population_ppo_update(dril_population* p, dril_ppo_stats* out);
 /* dril_train of every member: iterations = max_steps / (T*E) of {set lr, collect, update}; stats / fps: [iteration][member], iterations x n entries (may be NULL) */
 int32_t dril_population_train(dril_population* p, int64_t max_steps, dril_ppo_stats* stats, double* fps, int32_t* iterations_done);
 int32_t dril_population_info(const dril_population* p, struct dril_population_info* out);
+/* dril_evaluate_agent_device of every member, in ONE evaluate_pop_kernel launch and ONE look at the members' counters per K env steps (docs/population.md, "Evaluation").
+ * Equal to solo: out[m], member m's episode rewards / lengths and member_info[m] (path, launches, steps_enqueued, events) are byte for byte what
+ *   dril_evaluate_agent_device(member m, o, ...) returns for that handle alone.  One options struct serves all members: has_seed = 0 uses each member's own env seed
+ *   in force, has_seed = 1 gives every member the same seed (common random numbers across members); poll_steps, deterministic and n_eval_episodes are the solo
+ *   verb's.  K is the solo verb's, and equal for all members (n_envs and the env kind are).
+ * Leaves nothing behind, per member: the solo verb's set-aside and put-back (the same functions), on error paths too.  A population that evaluates between two
+ *   iterations continues bit-identically to one that does not.
+ * One look per K steps for the whole population: the members' counters are one population-owned device array (EvalAcct.counter of member m points at word m; the
+ *   other accounting buffers are the handle's own).  Per round: the argument blocks built in pinned memory (T = 0 for a member that has seen n_eval_episodes events,
+ *   else T = K and its own step0), one copy to the device, one launch, one copy of the n counters home, one synchronise.  Then every member's event list is copied
+ *   home, its state put back, one more synchronise, and the host's reduction per member.  The bound on an evaluation that never ends is the solo verb's, per member.
+ * Who runs solo (dril_evaluate_agent_device alone, after the batched loop; counted in solo_members): a member on the exact-f32 forward (max |W2| >= 350, or the
+ *   latch); every member under o->force_step_granular or DRIL_FORCE_STEPWISE.  reserved[DRIL_EVAL_OPT_PERSISTENT] is accepted and changes nothing (members never normalise).
+ * Errors: as the other population verbs — a failing member does not stop the others and its state is put back; the call returns the first failing member's status,
+ *   dril_population_last_error names the member, its own dril_last_error says what the solo call would have said.  DRIL_ERR_INVALID_ARG, no member touched: null p, o
+ *   or out, n_eval_episodes < 1, poll_steps < 0. */
+typedef struct dril_population_eval_info {
+    int32_t launches;        /* evaluate_pop_kernel launches of the call */
+    int32_t looks;           /* counter copies + synchronises (== launches) */
+    int32_t batched_members, solo_members;
+    double  kernel_ms;       /* HIP-event time of the batched launches; 0 unless member 0 has profile_events */
+    int64_t reserved[4];
+} dril_population_eval_info;
+/* out: n entries; episode_rewards / episode_lengths: [member][n_eval_episodes], may be NULL; member_info: n entries, may be NULL; info may be NULL */
+int32_t dril_population_evaluate_device(dril_population* p, const dril_eval_options* o, dril_eval_stats* out,
+                                        float* episode_rewards, int32_t* episode_lengths,
+                                        dril_eval_info* member_info, dril_population_eval_info* info);
 
 /* ---- multi-GPU (new; the reference is single-process) ------------------------- */
 /* 128-byte ncclUniqueId from rank 0, distributed to the other ranks by the host */

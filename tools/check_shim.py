@@ -256,7 +256,7 @@ def check_abi() -> list[str]:
     print(f"abi: {len(used)} distinct ccall symbols, all declared" if not (used - declared) else f"abi: undeclared {sorted(used - declared)}")
     for cname, jname in (("dril_config", "DrilConfig"), ("dril_ppo_stats", "DrilPPOStats"), ("dril_sac_config", "DrilSacConfig"), ("dril_sac_stats", "DrilSacStats"), ("dril_eval_stats", "DrilEvalStats"),
                          ("dril_sac_normalize_config", "DrilSacNormalizeConfig"), ("dril_eval_options", "DrilEvalOptions"), ("dril_eval_info", "DrilEvalInfo"),
-                         ("dril_traj_options", "DrilTrajOptions"), ("dril_traj_info", "DrilTrajInfo")):
+                         ("dril_traj_options", "DrilTrajOptions"), ("dril_traj_info", "DrilTrajInfo"), ("dril_population_eval_info", "DrilPopulationEvalInfo")):
         cm = re.search(r"typedef struct " + cname + r"\s*\{(.*?)\}\s*" + cname + ";", headers, re.S)
         jm = re.search(r"struct " + jname + r"\n(.*?)\nend", shim, re.S)
         if not cm or not jm:
