@@ -2475,30 +2475,43 @@ int eval_buffers(dril_handle* h, const EvalKeep& k, long long cap) {
     if (cap > h->eval_events_cap) { if (h->eval_events) (void)hipFree(h->eval_events); h->eval_events = nullptr; h->eval_events_cap = 0; HIPCHK(h, dmalloc(&h->eval_events, (size_t)cap)); h->eval_events_cap = cap; }
     return DRIL_OK;
 }
-// one env step of path 0, enqueued: predict_actions -> act! -> accounting -> observe.  raw: the accounting reads the raw rewards (dril_evaluate_agent's rule)
-int eval_step_granular(dril_handle* h, const EvalAcct& acct, int32_t step, int deterministic, bool raw, int32_t* launches) {
-    const int E = h->cfg.n_envs; const bool wrapped = normalizing(h) || h->pn.on; const int64_t g0 = h->gws.launches;
-    PolicyArgs p = policy_args(h, h->e_obs, E, nullptr, h->e_act, nullptr, h->e_rew /*log-probabilities are not needed: parked where act! writes next*/, nullptr, 0);
+// The pieces of one step-granular env step that the evaluation (eval_step_granular) and the recording (traj_step) share; what differs sits between them.
+// wrapped: a NormalizeWrapperEnv (cfg.norm_* or dril_normalize_enable) is around the envs, its statistics frozen for the call
+bool eval_wrapped(const dril_handle* h) { return normalizing(h) || h->pn.on; }
+// predict_actions(agent, observations; deterministic), evaluation.jl:92 / trajectory_utils.jl:28
+int eval_step_policy(dril_handle* h, int deterministic) {
+    PolicyArgs p = policy_args(h, h->e_obs, h->cfg.n_envs, nullptr, h->e_act, nullptr, h->e_rew /*log-probabilities are not needed: parked where act! writes next*/, nullptr, 0);
     p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.deterministic = deterministic ? 1 : 0;
-    HIPCHK(h, run_policy(h, p));                                                   // predict_actions(agent, observations; deterministic), :92
-    const float* rew = h->e_rew;
-    if (wrapped) {                                                                 // act!(env, actions), :94: the wrapper's, its statistics frozen
-        float* delivered = (h->env.module && !h->pn.on) ? nullptr : h->e_rew_n;
-        int rc = step_dev(h, h->e_act, delivered, nullptr); if (rc) return rc;
-        if (!raw && delivered) rew = delivered;
-    } else { int rc = env_step_arrays(h, h->e_act); if (rc) return rc; }           // no wrapper: the raw step is the whole step (as dril_env_step)
-    hipLaunchKernelGGL(eval_account_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, step, rew, h->e_term, h->e_trunc);
-    HIPCHK(h, hipGetLastError());
-    if (wrapped) { int rc = observe_dev(h, true); if (rc) return rc; }             // observations = observe(env), :97
-    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
-    *launches += (h->generic ? (int32_t)(h->gws.launches - g0) : 1) + 2 + (wrapped ? (h->env.module ? 2 : 3) : 0);
+    HIPCHK(h, run_policy(h, p));
     return DRIL_OK;
 }
-// K: env steps between two looks at the counter.  The persistent kernel's launch length is also bounded by the list it may fill (eval_event_capacity, dril_eval_account.h)
-int eval_poll_steps(const dril_handle* h, const dril_eval_options* o, bool persistent) {
-    int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, persistent ? kEvalPollPersistent : kEvalPollStepwise));
-    if (persistent) K = (int)std::max<long long>(1, std::min<long long>(K, kEvalMaxLaunchEvents / std::max(1, h->cfg.n_envs)));
-    return K;
+// act!(env, actions), :94 / :35.  *rew: the rewards an accounting reads — raw (dril_evaluate_agent's rule; they stay in e_rew), else what the wrapper delivers
+int eval_step_env(dril_handle* h, bool raw, const float** rew) {
+    float* delivered = (h->env.module && !h->pn.on) ? nullptr : h->e_rew_n;
+    *rew = (eval_wrapped(h) && !raw && delivered) ? delivered : h->e_rew;
+    return eval_wrapped(h) ? step_dev(h, h->e_act, delivered, nullptr) : env_step_arrays(h, h->e_act);   // no wrapper: the raw step is the whole step (as dril_env_step)
+}
+// observations = observe(env), :88, :97 / :17, :24-26
+int eval_step_observe(dril_handle* h) { if (eval_wrapped(h)) return observe_dev(h, true); HIPCHK(h, h->env.observe(h->e_obs, h->stream)); return DRIL_OK; }
+// the launches of the three above.  g0: gws.launches before the policy (a generic shape's forward is several launches)
+int32_t eval_step_launches(const dril_handle* h, int64_t g0) { return (h->generic ? (int32_t)(h->gws.launches - g0) : 1) + 2 + (eval_wrapped(h) ? (h->env.module ? 2 : 3) : 0); }
+// one env step of path 0, enqueued: predict_actions -> act! -> accounting -> observe.  raw: the accounting reads the raw rewards (dril_evaluate_agent's rule)
+int eval_step_granular(dril_handle* h, const EvalAcct& acct, int32_t step, int deterministic, bool raw, int32_t* launches) {
+    const int E = h->cfg.n_envs; const int64_t g0 = h->gws.launches; const float* rew = nullptr;
+    { int rc = eval_step_policy(h, deterministic); if (rc) return rc; }
+    { int rc = eval_step_env(h, raw, &rew); if (rc) return rc; }
+    hipLaunchKernelGGL(eval_account_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, step, rew, h->e_term, h->e_trunc);
+    HIPCHK(h, hipGetLastError());
+    { int rc = eval_step_observe(h); if (rc) return rc; }
+    *launches += eval_step_launches(h, g0);
+    return DRIL_OK;
+}
+// K: env steps between two looks at the counter — the ONE rule of both verbs on every path (the table of callers: docs/evaluation.md, "K").  poll_steps > 0 replaces
+// the default and takes the same caps.  persistent: one launch runs the K steps (paths 1 and 2).  cap_events: E K of a launch is bounded by kEvalMaxLaunchEvents
+// (the list it may fill: eval_event_capacity, dril_eval_account.h); the recording on path 1 does not ask for it.  cap_steps: Tcap, for the recording on path 2 alone
+int eval_poll_steps(const dril_handle* h, int32_t poll_steps, bool persistent, bool cap_events, int cap_steps = INT32_MAX) {
+    const int K = std::min(poll_steps > 0 ? poll_steps : std::max(1, std::min(h->env.episode_len, persistent ? kEvalPollPersistent : kEvalPollStepwise)), cap_steps);
+    return cap_events ? (int)std::max<long long>(1, std::min<long long>(K, kEvalMaxLaunchEvents / std::max(1, h->cfg.n_envs))) : K;
 }
 // ---- the pieces of dril_evaluate_agent_device, in the order it runs them: prepare, set-aside, reset, enqueue, put-back, reduce.  dril_population_evaluate_device
 // calls the same pieces per member (as pop_collect / pop_update call rollout_args / update_begin), so a member's evaluation is that of its handle alone ----
@@ -2510,7 +2523,7 @@ int eval_prepare(dril_handle* h, const dril_eval_options* o, EvalPlan& pl) {
     pl.fused = !o->force_step_granular && eval_fused_applies(h, o->reserved[DRIL_EVAL_OPT_PERSISTENT] != 0);   // path 2: a plug-in's own evaluation kernel (never both)
     pl.raw = (h->env.module && h->pn.on) || h->mon_cur_ret != nullptr;                  // dril_evaluate_agent's rule: raw returns under the monitor (and under a plug-in's normaliser)
     eval_keep_list(h, pl.persistent || pl.fused, pl.keep);                             // (path 2 writes the envs and scratch of its own: the per-step arrays are not touched)
-    pl.K = eval_poll_steps(h, o, pl.persistent || pl.fused);
+    pl.K = eval_poll_steps(h, o->poll_steps, pl.persistent || pl.fused, /*cap_events=*/pl.persistent || pl.fused);
     pl.cap = eval_event_capacity(o->n_eval_episodes, h->cfg.n_envs, (pl.persistent || pl.fused) ? pl.K : 1);   // (path 0: one launch per env step)
     return eval_buffers(h, pl.keep, pl.cap);
 }
@@ -2523,13 +2536,21 @@ int eval_set_aside(dril_handle* h, EvalKeep& keep) {
     h->mon_cur_ret = nullptr;                                                          // evaluation episodes do not enter the training env's MonitorWrapperEnv: its launches are not made
     return DRIL_OK;
 }
-// reset: the call's seed, reset!(env) (:87), zeroed accounting.  counter: the device word the kernels count in (the handle's own, or its word of a population's array)
+// open the episode, for both verbs: the call's seed (env e of rank r: seed + r E + e), reset!(env) (evaluation.jl:87 / trajectory_utils.jl:10), the counter zeroed — the
+// device word the kernels count in (the handle's own, or its word of a population's array).  shadow (null: none): a recording's twins of envs 0..M-1, seeded alike
+int eval_open_episode(dril_handle* h, bool has_seed, uint64_t seed, unsigned int* counter, DeviceEnvs* shadow = nullptr) {
+    if (has_seed) h->env.seed0 = seed + (uint64_t)h->cfg.rank * (uint64_t)h->cfg.n_envs;
+    HIPCHK(h, h->env.reset(h->stream));
+    h->env.ready = true;
+    if (shadow) shadow->seed0 = h->env.seed0;
+    if (shadow) for (void* p : {(void*)shadow->step_count, (void*)shadow->episode, (void*)shadow->gstep}) HIPCHK(h, hipMemsetAsync(p, 0, (size_t)shadow->E * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(counter, 0, 4, h->stream));
+    return DRIL_OK;
+}
 int eval_reset(dril_handle* h, const dril_eval_options* o, unsigned int* counter, long long cap, EvalAcct& acct) {
     const int E = h->cfg.n_envs;
-    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
-    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :87
-    h->env.ready = true;
-    HIPCHK(h, hipMemsetAsync(h->eval_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_cur_len, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(counter, 0, 4, h->stream));
+    { int rc = eval_open_episode(h, o->has_seed != 0, o->seed, counter); if (rc) return rc; }
+    HIPCHK(h, hipMemsetAsync(h->eval_cur_ret, 0, (size_t)E * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_cur_len, 0, (size_t)E * 4, h->stream));
     acct = EvalAcct{E, h->eval_cur_ret, h->eval_cur_len, counter, h->eval_events, (unsigned int)cap};
     return DRIL_OK;
 }
@@ -2547,6 +2568,28 @@ int eval_put_back(dril_handle* h, const EvalKeep& keep) {
     h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
     h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
     return eval_keep_copy(h, keep, false);
+}
+// the end of either verb, after eval_set_aside: the state is put back and the stream drained whatever the run returned (rc), and the run's error is the one reported
+int eval_finish(dril_handle* h, const EvalKeep& keep, const char* verb, int rc) {
+    const std::string msg = h->err;
+    int rr = eval_put_back(h, keep);
+    if (rr == DRIL_OK) { const hipError_t e = hipStreamSynchronize(h->stream); if (e != hipSuccess) rr = fail(h, DRIL_ERR_HIP, std::string(verb) + ": " + hipGetErrorString(e)); }
+    if (rc != DRIL_OK) { h->err = msg; return rc; }
+    return rr;
+}
+// the loop of either verb on every path: until `want` episodes / trajectories are counted, enqueue a chunk of env steps, copy the 4-byte counter home, drain, read it.
+// enqueue(steps, launches) -> status advances both by what it put into the stream.  A chunk that would start at or past `bound` steps fails with (code, bound_msg)
+struct EvalPoll { unsigned int seen = 0; long long steps = 0; int32_t launches = 0; };
+template <class Enqueue> int eval_poll_loop(dril_handle* h, int want, long long bound, int code, const char* bound_msg, EvalPoll& p, Enqueue&& enqueue) {
+    p = EvalPoll{};
+    while (p.seen < (unsigned int)want) {
+        if (p.steps >= bound) return fail(h, code, bound_msg);
+        { int rc = enqueue(p.steps, p.launches); if (rc) return rc; }
+        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        p.seen = *h->eval_counter_host;
+    }
+    return DRIL_OK;
 }
 // reduce: the first n_eval_episodes events in (step, env) order
 void eval_reduce(SacEvalEvent* events, int64_t n_events, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) {
@@ -2566,12 +2609,9 @@ int eval_device_run(dril_handle* h, const dril_eval_options* o, const EvalPlan& 
     else if (persistent) {
         eval_persistent_args(h, o, K, acct, g);
         if (modes) eval_mode_norm(h, x, raw);
-    } else if (normalizing(h) || h->pn.on) { int rc = observe_dev(h, true); if (rc) return rc; }   // observations = observe(env), :88
-    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
-    const long long max_steps = eval_max_steps(h, n_eval, K);
-    long long steps = 0; unsigned int seen = 0; int32_t launches = 0;
-    while (seen < (unsigned int)n_eval) {
-        if (steps >= max_steps) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_evaluate_agent_device: no episode finishes");
+    } else { int rc = eval_step_observe(h); if (rc) return rc; }                  // observations = observe(env), :88
+    EvalPoll p;
+    const int rc = eval_poll_loop(h, n_eval, eval_max_steps(h, n_eval, K), DRIL_ERR_UNSUPPORTED, "dril_evaluate_agent_device: no episode finishes", p, [&](long long& steps, int32_t& launches) -> int {
         if (fused) {
             HIPCHK(h, h->env.launch_evaluate(gf, h->stream));
             hipLaunchKernelGGL(eval_account_rows_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, (int32_t)steps, (int32_t)K, gf.r.rew, gf.r.flags);
@@ -2580,14 +2620,13 @@ int eval_device_run(dril_handle* h, const dril_eval_options* o, const EvalPlan& 
         }
         else if (persistent) { g.step0 = (int32_t)steps; HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream, modes ? &x : nullptr)); steps += K; launches += 1; }
         else for (int k = 0; k < K; ++k) { int rc = eval_step_granular(h, acct, (int32_t)(++steps), (o->deterministic ? 1 : 0), raw, &launches); if (rc) return rc; }
-        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        seen = *h->eval_counter_host;
-    }
-    events.resize((size_t)std::min<long long>(seen, cap));
+        return DRIL_OK;
+    });
+    if (rc) return rc;
+    events.resize((size_t)std::min<long long>(p.seen, cap));
     HIPCHK(h, hipMemcpyAsync(events.data(), h->eval_events, events.size() * sizeof(SacEvalEvent), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (info) { info->path = fused ? 2 : persistent ? 1 : 0; info->launches = launches; info->steps_enqueued = (int32_t)steps; info->events = (int32_t)seen; }
+    if (info) { info->path = fused ? 2 : persistent ? 1 : 0; info->launches = p.launches; info->steps_enqueued = (int32_t)p.steps; info->events = (int32_t)p.seen; }
     return DRIL_OK;
 }
 const char* const kEvalArgMsg = "dril_evaluate_agent_device: options and out != NULL, n_eval_episodes >= 1, poll_steps >= 0";
@@ -2606,12 +2645,7 @@ DRIL_EXPORT int32_t dril_evaluate_agent_device(dril_handle* h, const dril_eval_o
     { int rc = eval_prepare(h, o, pl); if (rc) return rc; }
     { int rc = eval_set_aside(h, pl.keep); if (rc) return rc; }
     std::vector<SacEvalEvent> events;
-    const int rc = eval_device_run(h, o, pl, events, info);
-    const std::string msg = h->err;
-    int rr = eval_put_back(h, pl.keep);
-    if (rr == DRIL_OK) { const hipError_t e = hipStreamSynchronize(h->stream); if (e != hipSuccess) rr = fail(h, DRIL_ERR_HIP, std::string("dril_evaluate_agent_device: ") + hipGetErrorString(e)); }
-    if (rc != DRIL_OK) { h->err = msg; return rc; }
-    if (rr != DRIL_OK) return rr;
+    { int rc = eval_finish(h, pl.keep, "dril_evaluate_agent_device", eval_device_run(h, o, pl, events, info)); if (rc) return rc; }
     eval_reduce(events.data(), (int64_t)events.size(), o, out, ep_rewards, ep_lengths);
     return DRIL_OK;
 }
@@ -2663,8 +2697,10 @@ int traj_prepare(dril_handle* h, const dril_traj_options* o, int32_t Tcap, TrajR
         const EnvKindInfo* ki = env_kind_info(h->env.kind);
         if (!ki) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_collect_trajectory_device: no device env on this handle");
         if (ki->box) { cl[0] = ki->act_lo; ch[0] = ki->act_hi; }                   // ClampAdapter on the agent-facing Box (Box(-1, 1) under the wrapper)
-        if (h->env.kind == 2) { scaled = true; ol[0] = -1.0f; oh[0] = 1.0f; ol[1] = -1.0f; oh[1] = 1.0f; ol[2] = -8.0f; oh[2] = 8.0f; al[0] = -2.0f; ah[0] = 2.0f; }   // the bounds env_obs<2> / env_step<2> use (dril_device.h)
-        if (h->env.kind == 7) { scaled = true; ol[0] = -1.2f; oh[0] = 0.6f; ol[1] = -0.07f; oh[1] = 0.07f; al[0] = -1.0f; ah[0] = 1.0f; }                             // env_obs<7> / env_step<7>
+        if (const ScaledKindBoxes* sb = scaled_kind_boxes(h->env.kind)) {          // a built-in ScalingWrapperEnv: the boxes its kernels map from
+            scaled = true; al[0] = sb->act_low; ah[0] = sb->act_high;
+            for (int i = 0; i < sb->D; ++i) { ol[i] = sb->obs_low[i]; oh[i] = sb->obs_high[i]; }
+        }
     }
     HIPCHK(h, hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (the table is a local)
@@ -2681,122 +2717,70 @@ int traj_record_launch(dril_handle* h, const TrajRun& r, const TrajStep& s, int3
 }
 // one env step, enqueued: the launches of eval_step_granular, and over the M recorded envs only a state copy, the shadow step, the shadow observe and the recording
 int traj_step(dril_handle* h, const TrajRun& r, int32_t t, int deterministic, int32_t* launches) {
-    const int E = h->cfg.n_envs; const bool wrapped = normalizing(h) || h->pn.on; const int64_t g0 = h->gws.launches;
+    const int64_t g0 = h->gws.launches; const float* raw_rew = nullptr;
     HIPCHK(h, hipMemcpyAsync(r.shadow.state, h->env.state, (size_t)r.rec.M * h->S * 4, hipMemcpyDeviceToDevice, h->stream));   // the pre-step state of envs 0..M-1 (env-major prefix)
-    PolicyArgs p = policy_args(h, h->e_obs, E, nullptr, h->e_act, nullptr, h->e_rew /*log-probabilities are not needed: parked where act! writes next*/, nullptr, 0);
-    p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.deterministic = deterministic ? 1 : 0;
-    HIPCHK(h, run_policy(h, p));                                                   // predict_actions(agent, [obs_to_agent]; deterministic), :28
+    { int rc = eval_step_policy(h, deterministic); if (rc) return rc; }
     HIPCHK(h, r.shadow.step(h->e_act, EnvStepOut{r.sh_rew, r.sh_term, r.sh_trunc, r.sh_tobs, nullptr}, MonitorArgs{}, h->stream));   // the same step, with no reset after it
     HIPCHK(h, r.shadow.observe(r.sh_obs, h->stream));                              // observe(env) of the env that did not auto-reset
-    if (wrapped) { int rc = step_dev(h, h->e_act, (h->env.module && !h->pn.on) ? nullptr : h->e_rew_n, nullptr); if (rc) return rc; }   // act!(env, action), :35: the wrapper's, its statistics frozen; raw rewards stay in e_rew
-    else { int rc = env_step_arrays(h, h->e_act); if (rc) return rc; }
-    { int rc = traj_record_launch(h, r, TrajStep{h->e_act, h->e_rew, h->e_term, h->e_trunc, r.sh_obs}, t); if (rc) return rc; }
-    if (wrapped) { int rc = observe_dev(h, true); if (rc) return rc; }             // the next obs_to_agent (normalize_obs!, :24-26)
-    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
-    *launches += (h->generic ? (int32_t)(h->gws.launches - g0) : 1) + 2 + (wrapped ? (h->env.module ? 2 : 3) : 0) + 4 + (h->env.module ? 0 : 1);   // (a built-in shadow step + observe: env_step_kernel, env_observe_kernel)
+    { int rc = eval_step_env(h, /*raw=*/true, &raw_rew); if (rc) return rc; }      // (the wrapper's statistics frozen; the recording takes the raw rewards)
+    { int rc = traj_record_launch(h, r, TrajStep{h->e_act, raw_rew, h->e_term, h->e_trunc, r.sh_obs}, t); if (rc) return rc; }
+    { int rc = eval_step_observe(h); if (rc) return rc; }                          // the next obs_to_agent (normalize_obs!, :24-26)
+    *launches += eval_step_launches(h, g0) + 4 + (h->env.module ? 0 : 1);          // (a built-in shadow step + observe: env_step_kernel, env_observe_kernel)
     return DRIL_OK;
 }
+const char* const kTrajStillOpenMsg = "dril_collect_trajectory_device: a trajectory is still open after its capacity (internal)";   // (step Tcap finalises every open one)
 // the persistent form: evaluate_modes_kernel in its recording mode, K env steps per launch.  No shadow envs, no state copies, none of the per-step arrays: the lane
 // that holds env m < M records it from its registers.  The last launch is shortened so that no step past Tcap is ever enqueued
-int traj_persistent_run(dril_handle* h, const dril_traj_options* o, const TrajRun& r, int32_t* steps_out, int32_t* launches_out) {
-    const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap;
-    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
-    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :10
-    h->env.ready = true;
-    HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
+int traj_persistent_run(dril_handle* h, const dril_traj_options* o, const TrajRun& r, EvalPoll& p) {
+    { int rc = eval_open_episode(h, o->has_seed != 0, o->seed, h->eval_counter); if (rc) return rc; }
     EvalKernelArgs g{}; EvalModeArgs x{};
-    eval_kernel_args(h, g, o->deterministic);
+    eval_kernel_args(h, g, o->deterministic);                                      // (after the call's seed is in force)
     if (normalizing(h)) eval_mode_norm(h, x, true);                                // (no accounting while recording: the reward row is the raw reward)
     x.record = 1; x.rec = r.rec; x.maps = r.maps;
-    const int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, kEvalPollPersistent));
-    int32_t steps = 0, launches = 0; unsigned int seen = 0;
-    while (seen < (unsigned int)M) {
-        if (steps >= Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
-        g.step0 = steps; g.r.T = std::min(K, Tcap - steps);
+    const int K = eval_poll_steps(h, o->poll_steps, /*persistent=*/true, /*cap_events=*/false);
+    return eval_poll_loop(h, r.rec.M, r.rec.Tcap, DRIL_ERR_HIP, kTrajStillOpenMsg, p, [&](long long& steps, int32_t& launches) -> int {
+        g.step0 = (int32_t)steps; g.r.T = std::min(K, r.rec.Tcap - (int)steps);
         HIPCHK(h, launch_evaluate(h->env.kind, h->cfg.hidden1, g, h->stream, &x)); steps += g.r.T; launches += 1;
-        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        seen = *h->eval_counter_host;
-    }
-    *steps_out = steps; *launches_out = launches;
-    return DRIL_OK;
+        return DRIL_OK;
+    });
 }
 // path 2: a plug-in's evaluation kernel in its recording mode, K env steps per launch, and ONE launch of the per-trajectory rule over the rows it leaves.  The shadow
 // envs are those of the step-granular form, stepped inside the kernel by the recorded env's own lane.  The last launch is shortened: no step past Tcap is ever enqueued
-int traj_fused_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int32_t* steps_out, int32_t* launches_out) {
+int traj_fused_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, EvalPoll& p) {
     const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap;
-    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
-    r.shadow.seed0 = h->env.seed0;
-    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :10
-    h->env.ready = true;
-    HIPCHK(h, hipMemsetAsync(r.shadow.step_count, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(r.shadow.episode, 0, (size_t)M * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(r.shadow.gstep, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
-    int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, kEvalPollPersistent));
-    K = (int)std::max<long long>(1, std::min<long long>(std::min(K, Tcap), kEvalMaxLaunchEvents / std::max(1, E)));
+    { int rc = eval_open_episode(h, o->has_seed != 0, o->seed, h->eval_counter, &r.shadow); if (rc) return rc; }
+    const int K = eval_poll_steps(h, o->poll_steps, /*persistent=*/true, /*cap_events=*/true, /*cap_steps=*/Tcap);
     DrilEnvEvaluateArgs g{};
     { int rc = eval_fused_args(h, g, o->deterministic, K, M, &r.shadow); if (rc) return rc; }
     const int64_t n = (int64_t)M * std::max(r.rec.D, r.rec.W);
-    int32_t steps = 0, launches = 0; unsigned int seen = 0;
-    while (seen < (unsigned int)M) {
-        if (steps >= Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
-        g.r.T = std::min(K, Tcap - steps);
+    return eval_poll_loop(h, M, Tcap, DRIL_ERR_HIP, kTrajStillOpenMsg, p, [&](long long& steps, int32_t& launches) -> int {
+        g.r.T = std::min(K, Tcap - (int)steps);
         HIPCHK(h, h->env.launch_evaluate(g, h->stream));
         const TrajRows rows{g.r.T, E, g.r.rew, g.r.flags, g.rec_obs0, (const uint32_t*)g.rec_act, g.rec_obs};
-        hipLaunchKernelGGL(traj_record_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.rec, r.maps, rows, steps);
+        hipLaunchKernelGGL(traj_record_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.rec, r.maps, rows, (int32_t)steps);
         HIPCHK(h, hipGetLastError());
         steps += g.r.T; launches += 2;
-        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        seen = *h->eval_counter_host;
-    }
-    *steps_out = steps; *launches_out = launches;
-    return DRIL_OK;
+        return DRIL_OK;
+    });
 }
 // the step-granular form: traj_step per env step, a look at the finished-counter every K steps
-int traj_stepwise_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int32_t* steps_out, int32_t* launches_out) {
-    const int E = h->cfg.n_envs, M = r.rec.M, Tcap = r.rec.Tcap;
-    const bool wrapped = normalizing(h) || h->pn.on;
-    if (o->has_seed) h->env.seed0 = o->seed + (uint64_t)h->cfg.rank * (uint64_t)E;
-    r.shadow.seed0 = h->env.seed0;
-    HIPCHK(h, h->env.reset(h->stream));                                            // reset!(env), :10
-    h->env.ready = true;
-    HIPCHK(h, hipMemsetAsync(r.shadow.step_count, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(r.shadow.episode, 0, (size_t)M * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(r.shadow.gstep, 0, (size_t)M * 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->eval_counter, 0, 4, h->stream));
-    if (wrapped) { int rc = observe_dev(h, true); if (rc) return rc; }             // observation = observe(env), :17
-    else HIPCHK(h, h->env.observe(h->e_obs, h->stream));
-    { int rc = traj_record_launch(h, r, TrajStep{nullptr, nullptr, nullptr, nullptr, wrapped ? h->e_obs_raw : h->e_obs}, 0); if (rc) return rc; }   // row 0: the original observation
-    const int K = o->poll_steps > 0 ? o->poll_steps : std::max(1, std::min(h->env.episode_len, kEvalPollStepwise));
-    int32_t steps = 0, launches = 0; unsigned int seen = 0;
-    while (seen < (unsigned int)M) {
-        if (steps >= Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
-        for (int k = 0; k < K && steps < Tcap; ++k) { int rc = traj_step(h, r, ++steps, (o->deterministic ? 1 : 0), &launches); if (rc) return rc; }
-        HIPCHK(h, hipMemcpyAsync(h->eval_counter_host, h->eval_counter, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        seen = *h->eval_counter_host;
-    }
-    *steps_out = steps; *launches_out = launches;
-    return DRIL_OK;
+int traj_stepwise_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, EvalPoll& p) {
+    { int rc = eval_open_episode(h, o->has_seed != 0, o->seed, h->eval_counter, &r.shadow); if (rc) return rc; }
+    { int rc = eval_step_observe(h); if (rc) return rc; }                          // observation = observe(env), :17
+    { int rc = traj_record_launch(h, r, TrajStep{nullptr, nullptr, nullptr, nullptr, eval_wrapped(h) ? h->e_obs_raw : h->e_obs}, 0); if (rc) return rc; }   // row 0: the original observation
+    const int K = eval_poll_steps(h, o->poll_steps, /*persistent=*/false, /*cap_events=*/false);
+    return eval_poll_loop(h, r.rec.M, r.rec.Tcap, DRIL_ERR_HIP, kTrajStillOpenMsg, p, [&](long long& steps, int32_t& launches) -> int {
+        for (int k = 0; k < K && steps < r.rec.Tcap; ++k) { int rc = traj_step(h, r, (int32_t)(++steps), (o->deterministic ? 1 : 0), &launches); if (rc) return rc; }
+        return DRIL_OK;
+    });
 }
 int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int path, float* observations, void* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
-    const int M = r.rec.M, Tcap = r.rec.Tcap; const size_t D = (size_t)r.rec.D, W = (size_t)r.rec.W;
-    int32_t steps = 0, launches = 0;
-    { int rc = path == 2 ? traj_fused_run(h, o, r, &steps, &launches) : path == 1 ? traj_persistent_run(h, o, r, &steps, &launches) : traj_stepwise_run(h, o, r, &steps, &launches); if (rc) return rc; }
-    // copy-out: lengths first, then rows 0..longest only, reordered into the caller's per-trajectory layout on the host
-    HIPCHK(h, hipMemcpyAsync(lengths, r.rec.length, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(end_flags, r.rec.end_flags, (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    int32_t longest = 0, cuts = 0;
-    for (int m = 0; m < M; ++m) {
-        if (lengths[m] < 1 || lengths[m] > Tcap) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: trajectory " + std::to_string(m) + " has length " + std::to_string(lengths[m]) + " (internal)");
-        longest = std::max(longest, lengths[m]); cuts += (end_flags[m] & kTrajCut) ? 1 : 0;
-    }
-    std::vector<float> obs_tm((size_t)(longest + 1) * M * D), rew_tm((size_t)longest * M); std::vector<uint32_t> act_tm((size_t)longest * M * W);
-    HIPCHK(h, hipMemcpyAsync(obs_tm.data(), r.rec.obs, obs_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(act_tm.data(), r.rec.act, act_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(rew_tm.data(), r.rec.rew, rew_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    traj_reorder(M, (int64_t)D, (int64_t)W, Tcap, lengths, obs_tm.data(), act_tm.data(), rew_tm.data(), observations, (uint32_t*)actions, rewards);
-    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = path; }
+    EvalPoll p;
+    { int rc = path == 2 ? traj_fused_run(h, o, r, p) : path == 1 ? traj_persistent_run(h, o, r, p) : traj_stepwise_run(h, o, r, p); if (rc) return rc; }
+    const TrajCopyOut c = traj_copy_out(h->stream, r.rec, observations, (uint32_t*)actions, rewards, lengths, end_flags);
+    if (c.err != hipSuccess) return fail(h, DRIL_ERR_HIP, std::string("dril_collect_trajectory_device: copy-out: ") + hipGetErrorString(c.err));
+    if (c.bad >= 0) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: trajectory " + std::to_string(c.bad) + " has length " + std::to_string(c.bad_length) + " (internal)");
+    if (info) { info->capacity = r.rec.Tcap; info->steps_enqueued = (int32_t)p.steps; info->launches = p.launches; info->longest = c.longest; info->cut_by_max_steps = c.cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = path; }
     return DRIL_OK;
 }
 }  // namespace
@@ -2833,20 +2817,9 @@ DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_tr
     { int rc = eval_buffers(h, keep, 0); if (rc) return rc; }
     TrajRun run{};
     { int rc = traj_prepare(h, o, Tcap, run); if (rc) return rc; }
-    // as dril_evaluate_agent_device: what training would continue from is set aside here and put back below, on every path
-    keep.seed0 = h->env.seed0; keep.ready = h->env.ready; keep.obs_par = h->obs_par; keep.ret_par = h->ret_par; keep.norm_training = h->cfg.norm_training;
-    keep.pn_training = h->pn.cfg.training; keep.mon_cur_ret = h->mon_cur_ret; keep.gws_launches = h->gws.launches;
-    { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
-    h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false), :12
-    h->mon_cur_ret = nullptr;                                                          // the recorded episodes do not enter the training env's MonitorWrapperEnv
-    const int rc = traj_device_run(h, o, run, fused ? 2 : persistent ? 1 : 0, observations, actions, rewards, lengths, end_flags, info);
-    const std::string msg = h->err;
-    h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
-    h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
-    int rr = eval_keep_copy(h, keep, false);
-    if (rr == DRIL_OK) { const hipError_t e = hipStreamSynchronize(h->stream); if (e != hipSuccess) rr = fail(h, DRIL_ERR_HIP, std::string("dril_collect_trajectory_device: ") + hipGetErrorString(e)); }
-    if (rc != DRIL_OK) { h->err = msg; return rc; }
-    return rr;
+    // as dril_evaluate_agent_device: what training would continue from is set aside here and put back by eval_finish, on every path (set_training(env, false), :12)
+    { int rc = eval_set_aside(h, keep); if (rc) return rc; }
+    return eval_finish(h, keep, "dril_collect_trajectory_device", traj_device_run(h, o, run, fused ? 2 : persistent ? 1 : 0, observations, actions, rewards, lengths, end_flags, info));
 }
 
 // ---- train! ------------------------------------------------------------------------------------------

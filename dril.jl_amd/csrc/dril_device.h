@@ -344,6 +344,7 @@ template <int KIND> __device__ inline void env_reset(uint64_t env_seed, uint32_t
         st[1] = u01_f32(r[1]) * 2.0f - 1.0f;
     }
 }
+// (the boxes of the scaled kinds 2 and 7 below and in env_step are stated once more for the host: scaled_kind_boxes, dril_env_kinds.h — the two change together)
 template <int KIND> __device__ inline void env_obs(const float* st, float* obs) {
     if (KIND == 0) {
 #pragma unroll

@@ -2,7 +2,8 @@
 // (derived from EnvSpec<KIND> / act_bound<KIND>(), the kernels' truth in dril_device.h), which kinds may share a kernel instantiation, and the one dispatcher
 // from a run-time env_kind to a compile-time KIND.  DRIL_ENV_EXTERNAL (host envs) and DRIL_ENV_MODULE (device env plug-ins, dril_env_side.h) are not in the list:
 // they have no EnvSpec, no simulator and no per-kind kernel.
-// No launcher and no create function names a kind; adding one: DESIGN.md §5, "Env kinds on the host".
+// No launcher, no create function and no verb names a kind: what is particular to one (its time limit, which kinds share a kernel, the boxes of the scaled ones) is
+// stated here; adding one: DESIGN.md §5, "Env kinds on the host".
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +33,16 @@ template <int... K> const EnvKindInfo* find_kind_info(int kind, KindList<K...>) 
 }
 // null: a kind with no built-in simulator (DRIL_ENV_EXTERNAL, DRIL_ENV_MODULE, any number out of range)
 inline const EnvKindInfo* env_kind_info(int kind) { return find_kind_info(kind, BuiltinKinds{}); }
+// The built-ins that are a ScalingWrapperEnv (kinds 2 and 7) and the boxes of the env they wrap — its observation space (D entries) and its action space (A = 1) — as
+// the trajectory recordings need them to undo the maps.  The host's copy of the literals in env_obs<2 / 7> and env_step<2 / 7> (dril_device.h): the two change together
+struct ScaledKindBoxes { int kind, D; float obs_low[3], obs_high[3], act_low, act_high; };
+inline const ScaledKindBoxes* scaled_kind_boxes(int kind) {   // null: not a ScalingWrapperEnv
+    static constexpr ScaledKindBoxes table[] = {{2, EnvSpec<2>::D, {-1.0f, -1.0f, -8.0f}, {1.0f, 1.0f, 8.0f}, -2.0f, 2.0f},
+                                                {7, EnvSpec<7>::D, {-1.2f, -0.07f}, {0.6f, 0.07f}, -1.0f, 1.0f}};
+    static_assert(EnvSpec<2>::D == 3 && EnvSpec<7>::D == 2 && EnvSpec<2>::A == 1 && EnvSpec<7>::A == 1, "the boxes above are written for these shapes");
+    for (const ScaledKindBoxes& b : table) if (b.kind == kind) return &b;
+    return nullptr;
+}
 
 // Which kinds may run the same instantiation of a kernel depends on what the kernel touches of the simulator.  canonical(kind) is the kind whose instantiation runs:
 //

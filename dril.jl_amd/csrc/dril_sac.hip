@@ -3097,9 +3097,9 @@ int traj_prepare(dril_sac_handle* h, const dril_traj_options* o, int32_t Tcap, S
             for (size_t i = 0; i < D; ++i) { ol[i] = h->env.obs_low[i]; oh[i] = h->env.obs_high[i]; }
             for (size_t i = 0; i < W; ++i) { al[i] = h->env.desc.action_low[i]; ah[i] = h->env.desc.action_high[i]; }
         }
-    } else {
-        if (h->env.kind == 2) { scaled = true; ol[0] = -1.0f; oh[0] = 1.0f; ol[1] = -1.0f; oh[1] = 1.0f; ol[2] = -8.0f; oh[2] = 8.0f; al[0] = -2.0f; ah[0] = 2.0f; }   // the bounds env_obs<2> / env_step<2> use (dril_device.h)
-        if (h->env.kind == 7) { scaled = true; ol[0] = -1.2f; oh[0] = 0.6f; ol[1] = -0.07f; oh[1] = 0.07f; al[0] = -1.0f; ah[0] = 1.0f; }                             // env_obs<7> / env_step<7>
+    } else if (const ScaledKindBoxes* sb = scaled_kind_boxes(h->env.kind)) {      // a built-in ScalingWrapperEnv: the boxes its kernels map from
+        scaled = true; al[0] = sb->act_low; ah[0] = sb->act_high;
+        for (int i = 0; i < sb->D; ++i) { ol[i] = sb->obs_low[i]; oh[i] = sb->obs_high[i]; }
     }
     SHIP(h, hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
     SDO(ssync(h));                                                                 // (the table is a local)
@@ -3168,25 +3168,12 @@ int traj_run(dril_sac_handle* h, const dril_traj_options* o, SacTrajRun& r, int3
     return DRIL_OK;
 }
 int traj_run_and_copy(dril_sac_handle* h, const dril_traj_options* o, SacTrajRun& r, float* observations, float* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
-    const int M = r.rec.M, Tcap = r.rec.Tcap; const size_t D = (size_t)r.rec.D, W = (size_t)r.rec.W;
     int32_t steps = 0, launches = 0;
     SDO(traj_run(h, o, r, &steps, &launches));
-    // copy-out: lengths first, then rows 0..longest only, reordered into the caller's per-trajectory layout on the host
-    SHIP(h, hipMemcpyAsync(lengths, r.rec.length, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
-    SHIP(h, hipMemcpyAsync(end_flags, r.rec.end_flags, (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    SDO(ssync(h));
-    int32_t longest = 0, cuts = 0;
-    for (int m = 0; m < M; ++m) {
-        if (lengths[m] < 1 || lengths[m] > Tcap) return sfail(h, DRIL_ERR_HIP, "dril_sac_collect_trajectory: trajectory " + std::to_string(m) + " has length " + std::to_string(lengths[m]) + " (internal)");
-        longest = std::max(longest, lengths[m]); cuts += (end_flags[m] & kTrajCut) ? 1 : 0;
-    }
-    std::vector<float> obs_tm((size_t)(longest + 1) * M * D), rew_tm((size_t)longest * M); std::vector<uint32_t> act_tm((size_t)longest * M * W);
-    SHIP(h, hipMemcpyAsync(obs_tm.data(), r.rec.obs, obs_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    SHIP(h, hipMemcpyAsync(act_tm.data(), r.rec.act, act_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    SHIP(h, hipMemcpyAsync(rew_tm.data(), r.rec.rew, rew_tm.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    SDO(ssync(h));
-    traj_reorder(M, (int64_t)D, (int64_t)W, Tcap, lengths, obs_tm.data(), act_tm.data(), rew_tm.data(), observations, (uint32_t*)actions, rewards);
-    if (info) { info->capacity = Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = longest; info->cut_by_max_steps = cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = 0; }
+    const TrajCopyOut c = traj_copy_out(h->stream, r.rec, observations, (uint32_t*)actions, rewards, lengths, end_flags);
+    if (c.err != hipSuccess) return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_collect_trajectory: copy-out: ") + hipGetErrorString(c.err));
+    if (c.bad >= 0) return sfail(h, DRIL_ERR_HIP, "dril_sac_collect_trajectory: trajectory " + std::to_string(c.bad) + " has length " + std::to_string(c.bad_length) + " (internal)");
+    if (info) { info->capacity = r.rec.Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = c.longest; info->cut_by_max_steps = c.cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = 0; }
     return DRIL_OK;
 }
 }  // namespace

@@ -1,6 +1,6 @@
 // dril_traj_record.h — the per-env recording of a device-resident collect_trajectory (trajectory_utils.jl:3-49) on a PPO handle: what the lanes of env m do with the
 // action, the reward, the done flags and the observation of its step — the active test, what is written where, finalisation, and the precedence of the episode's end
-// over the max_steps cut.  No HIP dependency, in the manner of dril_eval_account.h: dril_api.hip (traj_record_kernel, over the E-sized per-step arrays and the shadow
+// over the max_steps cut.  No HIP dependency (traj_copy_out apart: HIP compiles only), in the manner of dril_eval_account.h: dril_api.hip (traj_record_kernel, over the E-sized per-step arrays and the shadow
 // envs' observation) includes it, and tests/test_traj_device.py drives the same lines with g++ against a restatement of the reference's loop.
 // The SAC handle's verb runs the same rule (dril_sac.hip: sac_traj_env_kernel through traj_record_env, sac_traj_record_kernel through traj_record_lane, both with null
 // clamp pointers; tests/test_sac_traj.py).
@@ -14,6 +14,9 @@
 #include "../../include/device/dril_scaling.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <vector>
 #define DRIL_TRAJ_HD __host__ __device__ __forceinline__
 #else
 #define DRIL_TRAJ_HD inline
@@ -162,4 +165,27 @@ inline void traj_reorder(int64_t M, int64_t D, int64_t W, int64_t Tcap, const in
         }
     }
 }
+#if defined(__HIPCC__) || defined(__CUDACC__)
+// the copy-out of a finished recording, for the PPO and the SAC handle's verb alike (host side): lengths and end flags first, then rows 0..longest only, reordered into
+// the caller's five arrays.  err: the first HIP error; bad >= 0: trajectory `bad` has the impossible length bad_length and nothing further was copied; else
+// longest / cuts (trajectories ended by max_steps) for dril_traj_info.  The caller words its own error
+struct TrajCopyOut { hipError_t err; int32_t bad, bad_length, longest, cuts; };
+inline TrajCopyOut traj_copy_out(hipStream_t stream, const TrajRec& r, float* observations, uint32_t* actions, float* rewards, int32_t* lengths, uint8_t* end_flags) {
+    TrajCopyOut c{hipSuccess, -1, 0, 0, 0};
+    const size_t M = (size_t)r.M, D = (size_t)r.D, W = (size_t)r.W;
+    auto home = [&](void* dst, const void* src, size_t bytes) { if (c.err == hipSuccess) c.err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream); };
+    auto drained = [&] { if (c.err == hipSuccess) c.err = hipStreamSynchronize(stream); return c.err == hipSuccess; };
+    home(lengths, r.length, M * 4); home(end_flags, r.end_flags, M);
+    if (!drained()) return c;
+    for (int32_t m = 0; m < r.M; ++m) {
+        if (lengths[m] < 1 || lengths[m] > r.Tcap) { c.bad = m; c.bad_length = lengths[m]; return c; }
+        c.longest = std::max(c.longest, lengths[m]); c.cuts += (end_flags[m] & kTrajCut) ? 1 : 0;
+    }
+    std::vector<float> obs_tm((size_t)(c.longest + 1) * M * D), rew_tm((size_t)c.longest * M); std::vector<uint32_t> act_tm((size_t)c.longest * M * W);
+    home(obs_tm.data(), r.obs, obs_tm.size() * 4); home(act_tm.data(), r.act, act_tm.size() * 4); home(rew_tm.data(), r.rew, rew_tm.size() * 4);
+    if (!drained()) return c;
+    traj_reorder(r.M, r.D, r.W, r.Tcap, lengths, obs_tm.data(), act_tm.data(), rew_tm.data(), observations, actions, rewards);
+    return c;
+}
+#endif
 }  // namespace dril
