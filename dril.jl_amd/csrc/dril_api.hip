@@ -21,6 +21,7 @@
 #include "dril_policy_internal.h"   // dril_policy_from_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in kind or a device env plug-in), shared with the SAC handle
 #include "dril_traj_record.h"  // collect_trajectory on the device: the per-env recording traj_record_kernel runs (host-compilable)
+#include "dril_traj_run.h"    // ... and its setup (blob layout, table of bounds, shadow envs, messages), shared with the SAC handle
 #include "dril_ext_stream.h"  // the pointer rule and the stream hand-over of the device-array verbs, shared with the SAC handle
 
 using namespace dril;
@@ -2592,12 +2593,7 @@ template <class Enqueue> int eval_poll_loop(dril_handle* h, int want, long long 
     return DRIL_OK;
 }
 // reduce: the first n_eval_episodes events in (step, env) order
-void eval_reduce(SacEvalEvent* events, int64_t n_events, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) {
-    SacEvalSummary sum{};
-    sac_eval_reduce(events, n_events, o->n_eval_episodes, &sum, ep_rewards, ep_lengths);
-    out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
-    out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
-}
+void eval_reduce(SacEvalEvent* events, int64_t n_events, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) { sac_eval_stats(events, n_events, o->n_eval_episodes, out, ep_rewards, ep_lengths); }
 int eval_device_run(dril_handle* h, const dril_eval_options* o, const EvalPlan& pl, std::vector<SacEvalEvent>& events, dril_eval_info* info) {
     const bool persistent = pl.persistent, fused = pl.fused, raw = pl.raw; const int K = pl.K; const long long cap = pl.cap;
     const int E = h->cfg.n_envs, n_eval = o->n_eval_episodes;
@@ -2665,54 +2661,17 @@ __global__ __launch_bounds__(256) void traj_record_kernel(TrajRec r, TrajMaps x,
 }
 }  // namespace dril
 namespace {
-constexpr int64_t kTrajMaxBytes = 1ll << 30;
-struct TrajRun {
-    TrajRec rec; TrajMaps maps; DeviceEnvs shadow;
-    float *sh_rew, *sh_tobs, *sh_obs; uint8_t *sh_term, *sh_trunc;
-};
-// carves the handle's blob (grown when the call needs more) and fills the table of bounds
+// the setup shared with the SAC handle (dril_traj_run.h) with what this handle alone knows: `discrete`, and ClampAdapter on the agent-facing Box (Box(-1, 1) under ScalingWrapperEnv)
 int traj_prepare(dril_handle* h, const dril_traj_options* o, int32_t Tcap, TrajRun& r) {
-    const size_t M = (size_t)o->n_trajectories, D = (size_t)h->D, W = h->discrete ? 1 : (size_t)h->A, S = (size_t)h->S, T = (size_t)Tcap;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_obs = take((T + 1) * M * D * 4), o_act = take(T * M * W * 4), o_rew = take(T * M * 4), o_len = take(M * 4), o_flg = take(M);
-    const size_t o_st = take(M * S * 4), o_sc = take(M * 4), o_ep = take(M * 4), o_gs = take(M * 4);
-    const size_t o_srew = take(M * 4), o_sterm = take(M), o_strunc = take(M), o_stobs = take(M * D * 4), o_sobs = take(M * D * 4), o_tab = take((2 * D + 4 * W) * 4);
-    if (off > h->traj_blob_bytes) { if (h->traj_blob) (void)hipFree(h->traj_blob); h->traj_blob = nullptr; h->traj_blob_bytes = 0; HIPCHK(h, dmalloc(&h->traj_blob, off)); h->traj_blob_bytes = off; }
-    char* b = h->traj_blob;
-    r.rec = TrajRec{(int32_t)M, (int32_t)D, (int32_t)W, Tcap, (float*)(b + o_obs), (uint32_t*)(b + o_act), (float*)(b + o_rew), (int32_t*)(b + o_len), (uint8_t*)(b + o_flg), h->eval_counter};
-    r.shadow = h->env;                                                             // the kind / the plug-in's kernels, scaling, action_start
-    r.shadow.E = (int)M; r.shadow.fixed_len = 1; r.shadow.episode_len = INT32_MAX; r.shadow.disc_returns = nullptr;
-    r.shadow.state = (float*)(b + o_st); r.shadow.step_count = (int32_t*)(b + o_sc); r.shadow.episode = (uint32_t*)(b + o_ep); r.shadow.gstep = (uint32_t*)(b + o_gs);
-    r.sh_rew = (float*)(b + o_srew); r.sh_term = (uint8_t*)(b + o_sterm); r.sh_trunc = (uint8_t*)(b + o_strunc); r.sh_tobs = (float*)(b + o_stobs); r.sh_obs = (float*)(b + o_sobs);
-    // the table: obs_low | obs_high (D each), clamp_low | clamp_high | act_low | act_high (W each)
-    std::vector<float> tab(2 * D + 4 * W, 0.f);
-    float *ol = tab.data(), *oh = ol + D, *cl = oh + D, *ch = cl + W, *al = ch + W, *ah = al + W;
-    bool scaled = false;
-    if (h->env.module) {
-        scaled = h->env.scaling;
-        if (scaled) for (size_t i = 0; i < D; ++i) { ol[i] = h->env.obs_low[i]; oh[i] = h->env.obs_high[i]; }
-        if (!h->discrete) for (size_t i = 0; i < W; ++i) { al[i] = h->env.desc.action_low[i]; ah[i] = h->env.desc.action_high[i]; cl[i] = scaled ? -1.0f : al[i]; ch[i] = scaled ? 1.0f : ah[i]; }
-    } else {
-        const EnvKindInfo* ki = env_kind_info(h->env.kind);
-        if (!ki) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_collect_trajectory_device: no device env on this handle");
-        if (ki->box) { cl[0] = ki->act_lo; ch[0] = ki->act_hi; }                   // ClampAdapter on the agent-facing Box (Box(-1, 1) under the wrapper)
-        if (const ScaledKindBoxes* sb = scaled_kind_boxes(h->env.kind)) {          // a built-in ScalingWrapperEnv: the boxes its kernels map from
-            scaled = true; al[0] = sb->act_low; ah[0] = sb->act_high;
-            for (int i = 0; i < sb->D; ++i) { ol[i] = sb->obs_low[i]; oh[i] = sb->obs_high[i]; }
-        }
-    }
-    HIPCHK(h, hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (the table is a local)
-    const float* dt = (const float*)(b + o_tab);
-    r.maps = TrajMaps{scaled ? dt : nullptr, scaled ? dt + D : nullptr, h->discrete ? nullptr : dt + 2 * D, h->discrete ? nullptr : dt + 2 * D + W,
-                      (scaled && !h->discrete) ? dt + 2 * D + 2 * W : nullptr, (scaled && !h->discrete) ? dt + 2 * D + 3 * W : nullptr, h->discrete ? 1 : 0, o->final_original ? 1 : 0};
-    return DRIL_OK;
-}
-int traj_record_launch(dril_handle* h, const TrajRun& r, const TrajStep& s, int32_t t) {
-    const int64_t n = (int64_t)r.rec.M * std::max(r.rec.D, r.rec.W);
-    hipLaunchKernelGGL(traj_record_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.rec, r.maps, s, t);
-    HIPCHK(h, hipGetLastError());
+    const size_t W = h->discrete ? 1 : (size_t)h->A;
+    std::vector<float> clamp_low(W, 0.f), clamp_high(W, 0.f);
+    TrajBoxes boxes = traj_env_boxes(h->env); boxes.discrete = h->discrete; boxes.clamp_low = clamp_low.data(); boxes.clamp_high = clamp_high.data();
+    const EnvKindInfo* ki = env_kind_info(h->env.kind);
+    if (!h->env.module && !ki) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_collect_trajectory_device: no device env on this handle");
+    if (h->env.module) { if (!h->discrete) h->env.agent_action_space(clamp_low.data(), clamp_high.data()); }
+    else if (ki->box) { clamp_low[0] = ki->act_lo; clamp_high[0] = ki->act_hi; }
+    const TrajLayout L = traj_layout((size_t)o->n_trajectories, (size_t)h->D, W, (size_t)h->S, (size_t)Tcap);
+    HIPCHK(h, traj_setup(h->env, h->stream, &h->traj_blob, &h->traj_blob_bytes, h->eval_counter, L, boxes, o->final_original != 0, /*drain_before_free=*/false, r));
     return DRIL_OK;
 }
 // one env step, enqueued: the launches of eval_step_granular, and over the M recorded envs only a state copy, the shadow step, the shadow observe and the recording
@@ -2723,7 +2682,7 @@ int traj_step(dril_handle* h, const TrajRun& r, int32_t t, int deterministic, in
     HIPCHK(h, r.shadow.step(h->e_act, EnvStepOut{r.sh_rew, r.sh_term, r.sh_trunc, r.sh_tobs, nullptr}, MonitorArgs{}, h->stream));   // the same step, with no reset after it
     HIPCHK(h, r.shadow.observe(r.sh_obs, h->stream));                              // observe(env) of the env that did not auto-reset
     { int rc = eval_step_env(h, /*raw=*/true, &raw_rew); if (rc) return rc; }      // (the wrapper's statistics frozen; the recording takes the raw rewards)
-    { int rc = traj_record_launch(h, r, TrajStep{h->e_act, raw_rew, h->e_term, h->e_trunc, r.sh_obs}, t); if (rc) return rc; }
+    HIPCHK(h, traj_record_launch(traj_record_kernel, h->stream, r, TrajStep{h->e_act, raw_rew, h->e_term, h->e_trunc, r.sh_obs}, t));
     { int rc = eval_step_observe(h); if (rc) return rc; }                          // the next obs_to_agent (normalize_obs!, :24-26)
     *launches += eval_step_launches(h, g0) + 4 + (h->env.module ? 0 : 1);          // (a built-in shadow step + observe: env_step_kernel, env_observe_kernel)
     return DRIL_OK;
@@ -2767,7 +2726,7 @@ int traj_fused_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, EvalP
 int traj_stepwise_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, EvalPoll& p) {
     { int rc = eval_open_episode(h, o->has_seed != 0, o->seed, h->eval_counter, &r.shadow); if (rc) return rc; }
     { int rc = eval_step_observe(h); if (rc) return rc; }                          // observation = observe(env), :17
-    { int rc = traj_record_launch(h, r, TrajStep{nullptr, nullptr, nullptr, nullptr, eval_wrapped(h) ? h->e_obs_raw : h->e_obs}, 0); if (rc) return rc; }   // row 0: the original observation
+    HIPCHK(h, traj_record_launch(traj_record_kernel, h->stream, r, TrajStep{nullptr, nullptr, nullptr, nullptr, eval_wrapped(h) ? h->e_obs_raw : h->e_obs}, 0));   // row 0: the original observation
     const int K = eval_poll_steps(h, o->poll_steps, /*persistent=*/false, /*cap_events=*/false);
     return eval_poll_loop(h, r.rec.M, r.rec.Tcap, DRIL_ERR_HIP, kTrajStillOpenMsg, p, [&](long long& steps, int32_t& launches) -> int {
         for (int k = 0; k < K && steps < r.rec.Tcap; ++k) { int rc = traj_step(h, r, (int32_t)(++steps), (o->deterministic ? 1 : 0), &launches); if (rc) return rc; }
@@ -2778,9 +2737,7 @@ int traj_device_run(dril_handle* h, const dril_traj_options* o, TrajRun& r, int 
     EvalPoll p;
     { int rc = path == 2 ? traj_fused_run(h, o, r, p) : path == 1 ? traj_persistent_run(h, o, r, p) : traj_stepwise_run(h, o, r, p); if (rc) return rc; }
     const TrajCopyOut c = traj_copy_out(h->stream, r.rec, observations, (uint32_t*)actions, rewards, lengths, end_flags);
-    if (c.err != hipSuccess) return fail(h, DRIL_ERR_HIP, std::string("dril_collect_trajectory_device: copy-out: ") + hipGetErrorString(c.err));
-    if (c.bad >= 0) return fail(h, DRIL_ERR_HIP, "dril_collect_trajectory_device: trajectory " + std::to_string(c.bad) + " has length " + std::to_string(c.bad_length) + " (internal)");
-    if (info) { info->capacity = r.rec.Tcap; info->steps_enqueued = (int32_t)p.steps; info->launches = p.launches; info->longest = c.longest; info->cut_by_max_steps = c.cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = path; }
+    if (const std::string msg = traj_report("dril_collect_trajectory_device", c, r.rec.Tcap, (int32_t)p.steps, p.launches, path, info); !msg.empty()) return fail(h, DRIL_ERR_HIP, msg);
     return DRIL_OK;
 }
 }  // namespace
@@ -2800,15 +2757,11 @@ DRIL_EXPORT int32_t dril_trajectory_capacity(const dril_handle* h, const dril_tr
 DRIL_EXPORT int32_t dril_collect_trajectory_device(dril_handle* h, const dril_traj_options* o, float* observations, void* actions, float* rewards, int32_t* lengths,
                                                    uint8_t* end_flags, dril_traj_info* info) {
     NEED(h); NOT_EXTERNAL(h, "dril_collect_trajectory_device");
-    if (!o || !observations || !actions || !rewards || !lengths || !end_flags || o->n_trajectories < 1 || o->n_trajectories > h->cfg.n_envs || o->max_steps < 0 || o->poll_steps < 0)
-        return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: options and the five output arrays != NULL, 1 <= n_trajectories <= n_envs, max_steps >= 0, poll_steps >= 0");
+    if (const std::string msg = traj_options_error("dril_collect_trajectory_device", o, observations && actions && rewards && lengths && end_flags, h->cfg.n_envs); !msg.empty()) return fail(h, DRIL_ERR_INVALID_ARG, msg);
     if (h->env.is_world() && o->n_trajectories % h->env.agents() != 0)
         return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: the env is a world of " + std::to_string(h->env.agents()) + " agents and whole worlds are recorded: n_trajectories " + std::to_string(o->n_trajectories) + " is not a multiple of " + std::to_string(h->env.agents()));
-    if (info) std::memset(info, 0, sizeof(*info));
-    const int32_t Tcap = traj_capacity(o->max_steps, h->env.episode_len);
-    const int64_t bytes = traj_bytes(o->n_trajectories, Tcap, h->D, h->discrete ? 1 : h->A);
-    if (bytes > kTrajMaxBytes)
-        return fail(h, DRIL_ERR_INVALID_ARG, "dril_collect_trajectory_device: the recording needs " + std::to_string(bytes) + " bytes on the device (M = " + std::to_string(o->n_trajectories) + ", Tcap = " + std::to_string(Tcap) + "), more than 1 GiB: record fewer envs or set max_steps");
+    int32_t Tcap = 0;
+    if (const std::string msg = traj_size_error("dril_collect_trajectory_device", o, h->env.episode_len, h->D, h->discrete ? 1 : h->A, info, &Tcap); !msg.empty()) return fail(h, DRIL_ERR_INVALID_ARG, msg);
     { int rc = ensure_wimg(h); if (rc) return rc; }
     // the opt-in one-launch form where evaluate_modes_kernel applies; elsewhere (generic shapes, plug-ins, DRIL_FORCE_STEPWISE) the request falls back silently
     const bool persistent = o->reserved[DRIL_TRAJ_OPT_PERSISTENT] != 0 && eval_persistent_applies(h, true);

@@ -33,7 +33,8 @@
 #include "dril_policy_internal.h"   // dril_policy_from_sac_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_sac_eval.h"
 #include "dril_traj_record.h"  // collect_trajectory on the device: the per-env recording sac_traj_env_kernel / sac_traj_record_kernel run (host-compilable)
-#include "dril_env_side.h"     // DeviceEnvs: the envs this handle steps on the device (a built-in Box kind or a device env plug-in), shared with the PPO handle
+#include "dril_traj_run.h"     // ... and its setup (blob layout, table of bounds, shadow envs, messages), shared with the PPO handle
+#include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in Box kind or a device env plug-in), shared with the PPO handle
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_ext_stream.h"   // the pointer rule and the stream hand-over of the device-array verbs, shared with the PPO handle
 #include "dril_ext_record.h"   // the per-env rules of a recorded step under the wrappers of an external handle (flags, sticky error, returns reset, the monitor's sums)
@@ -2984,51 +2985,90 @@ int eval_snapshot(dril_sac_handle* h, bool save) {
     if (h->mon_window) { SHIP(h, cp(h->ev_mon_ret, h->mon_cur_ret, E * 4)); SHIP(h, cp(h->ev_mon_len, h->mon_cur_len, E * 4)); }
     return DRIL_OK;
 }
+// ---- the pieces both verbs run: the PPO handle's (dril_api.hip, under the same names; docs/sac.md "Layout of the host code") over this handle's state ----
+// set-aside: the verbs run on the handle's own envs — what a collection would continue from is kept here and put back by eval_finish, on every path
+struct EvalKeep { uint64_t seed0; bool ready, obs_valid; };
+int eval_set_aside(dril_sac_handle* h, EvalKeep& keep) { keep = EvalKeep{h->env.seed0, h->env.ready, h->obs_valid}; return eval_snapshot(h, true); }
+int eval_put_back(dril_sac_handle* h, const EvalKeep& keep) { h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_valid = keep.obs_valid; return eval_snapshot(h, false); }
+// the end of either verb: the state is put back and the stream drained whatever the run returned (rc), and the run's error is the one reported
+int eval_finish(dril_sac_handle* h, const EvalKeep& keep, int rc) {
+    const std::string msg = h->err;
+    int rr = eval_put_back(h, keep); if (rr == DRIL_OK) rr = ssync(h);
+    if (rc != DRIL_OK) h->err = msg;
+    return rc != DRIL_OK ? rc : rr;
+}
+// open the episode: the call's seed (env e seeded seed + e; its action noise is that env's stream from step 0), reset!(env), the counter zeroed, the first observation
+// — raw, into obs_cur: the wrapper's old_obs is not these verbs' to write — handed to row0() (the recording's row 0 is the original observation), then normalised in
+// place with the frozen statistics, nothing updated.  shadow (null: none): a plug-in recording's twins of envs 0..M-1, seeded alike
+template <class Row0> int eval_open_episode(dril_sac_handle* h, bool has_seed, uint64_t seed, Row0&& row0, DeviceEnvs* shadow = nullptr) {
+    if (has_seed) h->env.seed0 = seed;
+    SHIP(h, h->env.reset(h->stream));
+    h->env.ready = true; h->obs_valid = false;
+    if (shadow) { shadow->seed0 = h->env.seed0; for (void* p : {(void*)shadow->step_count, (void*)shadow->episode, (void*)shadow->gstep}) SHIP(h, hipMemsetAsync(p, 0, (size_t)shadow->E * 4, h->stream)); }
+    SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
+    SDO(ensure_obs(h)); SDO(row0());
+    if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }
+    return DRIL_OK;
+}
+// the loop of either verb (eval_poll_loop of dril_api.hip): enqueue(steps, launches) advances both; a chunk that would start at or past `bound` fails with (code, bound_msg)
+struct EvalPoll { unsigned int seen = 0; long long steps = 0; int32_t launches = 0; };
+template <class Enqueue> int eval_poll_loop(dril_sac_handle* h, int want, long long bound, int code, const char* bound_msg, EvalPoll& p, Enqueue&& enqueue) {
+    for (p = EvalPoll{}; p.seen < (unsigned int)want; p.seen = *h->ev_counter_host) {
+        if (p.steps >= bound) return sfail(h, code, bound_msg);
+        SDO(enqueue(p.steps, p.launches));
+        SHIP(h, hipMemcpyAsync(h->ev_counter_host, h->ev_counter, 4, hipMemcpyDeviceToHost, h->stream));
+        SDO(ssync(h));
+    }
+    return DRIL_OK;
+}
+// The pieces of one env step that eval_step and traj_step share; what differs — the accounting, or shadow step, shadow observe and recording — sits between them.
+// predict_actions(agent, observations; deterministic): the collection step's hidden layers; the output layer runs in the launch that takes `ca`
+int eval_step_actor(dril_sac_handle* h, int deterministic, CollectHeadArgs& ca) { SDO(actor_hidden(h, 0, nullptr, &ca)); ca.deterministic = deterministic ? 1 : 0; return DRIL_OK; }
+// NormalizeWrapperEnv with training = false (set_training(eval_env, false) after sync_normalization_stats!, :299-309): the statistics in force, frozen
+NzEvalArgs eval_step_nz(const dril_sac_handle* h) { return NzEvalArgs{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs}; }
+// a plug-in: the action head into e_envact, and act!(env, action) of the live envs (monitor pointers null: these episodes do not feed the window)
+void eval_step_head(dril_sac_handle* h, const CollectHeadArgs& ca) { hipLaunchKernelGGL(sac_collect_head_kernel, dim3((h->cfg.n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca); }
+int eval_step_env(dril_sac_handle* h) { SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, MonitorArgs{}, h->stream)); return DRIL_OK; }
+// a built-in Box kind (A = 1): head, act! and observe are ONE launch, launch(K, env, grid, block), of the caller's env kernel over the collection's block without push and monitor
+template <class Launch> int eval_step_builtin(dril_sac_handle* h, const CollectHeadArgs& ca, Launch&& launch) {
+    const CollectEnvArgs env = env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr});
+    const dim3 grid((h->cfg.n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
+    SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { launch(K, env, grid, block); return hipGetLastError(); }));
+    return DRIL_OK;
+}
+int eval_step_end(dril_sac_handle* h) { SHIP(h, hipGetLastError()); std::swap(h->obs_cur, h->obs_nxt); return DRIL_OK; }
+// ---- the evaluation itself ----
 // one env step of the evaluation, enqueued: the collection step's hidden layers, then head + act! + observe + accounting
 int eval_step(dril_sac_handle* h, int deterministic, int32_t step, unsigned int cap) {
     const int E = h->cfg.n_envs;
-    CollectHeadArgs ca; SDO(actor_hidden(h, 0, nullptr, &ca));
-    ca.deterministic = deterministic ? 1 : 0;
-    const EvalAcctArgs acct{E, step, h->ev_cur_ret, h->ev_cur_len, h->ev_counter, h->ev_events, cap};
-    // NormalizeWrapperEnv with training = false (set_training(eval_env, false) after sync_normalization_stats!, :299-309): the statistics in force, frozen
-    const NzEvalArgs nz{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs};
+    CollectHeadArgs ca; SDO(eval_step_actor(h, deterministic, ca));
+    const EvalAcctArgs acct{E, step, h->ev_cur_ret, h->ev_cur_len, h->ev_counter, h->ev_events, cap}; const NzEvalArgs nz = eval_step_nz(h);
     if (h->env.module) {
-        hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
-        SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, MonitorArgs{}, h->stream));   // (monitor pointers null: evaluation episodes do not feed the window)
+        eval_step_head(h, ca); SDO(eval_step_env(h));
         if (nz.st && nz.norm_obs) {                                                    // the accounting launch also normalises the observation the plug-in wrote, in place
             const long long nthr = std::max<long long>(E, std::min<long long>((long long)E * h->D, 256 * 1024));
             hipLaunchKernelGGL(sac_eval_account_norm_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, acct, h->e_rew, h->e_term, h->e_trunc, nz, h->D, h->obs_nxt);
         } else hipLaunchKernelGGL(sac_eval_account_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, h->e_rew, h->e_term, h->e_trunc);
-    } else {                                                                           // every built-in Box env has A = 1
-        const EvalEnvArgs ee{env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr}), acct, nz};
-        const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
-        SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_eval_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, ee); return hipGetLastError(); }));
+    } else {
+        SDO(eval_step_builtin(h, ca, [&](auto K, const CollectEnvArgs& env, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL(sac_eval_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, EvalEnvArgs{env, acct, nz});
+        }));
     }
-    SHIP(h, hipGetLastError());
-    std::swap(h->obs_cur, h->obs_nxt);
-    return DRIL_OK;
+    return eval_step_end(h);
 }
 // reset!(env) .. the loop of evaluation.jl:90-122 on the device; the host looks at the event counter once per eval_poll steps
 int eval_run(dril_sac_handle* h, int n_eval, int deterministic, uint64_t seed, std::vector<SacEvalEvent>& events) {
-    const int E = h->cfg.n_envs;
-    const long long cap = sac_eval_event_capacity(n_eval, E);
-    h->env.seed0 = seed;                                                               // env e seeded seed + e; its action noise is that env's stream from step 0
-    SHIP(h, h->env.reset(h->stream));
-    h->env.ready = true; h->obs_valid = false;
-    SDO(ensure_obs(h));                                                                // (the raw observation, into obs_cur: the wrapper's old_obs is not the evaluation's to write)
-    if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }   // normalised in place, nothing updated
-    SHIP(h, hipMemsetAsync(h->ev_cur_ret, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_cur_len, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
+    const int E = h->cfg.n_envs; const long long cap = sac_eval_event_capacity(n_eval, E);
+    SDO(eval_open_episode(h, true, seed, [] { return DRIL_OK; }));
+    SHIP(h, hipMemsetAsync(h->ev_cur_ret, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_cur_len, 0, (size_t)E * 4, h->stream));
     // every env finishes an episode within the time limit, so n_eval of them take at most ceil(n_eval / E) time limits; one more, and the steps enqueued past a look
     const long long max_steps = ((long long)(n_eval + E - 1) / E + 1) * (long long)h->cfg.episode_len + h->eval_poll;
-    long long steps = 0; unsigned int seen = 0;
-    while (seen < (unsigned int)n_eval) {
-        if (steps >= max_steps) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_evaluate_agent: no episode finishes");
+    EvalPoll p;
+    SDO(eval_poll_loop(h, n_eval, max_steps, DRIL_ERR_UNSUPPORTED, "dril_sac_evaluate_agent: no episode finishes", p, [&](long long& steps, int32_t&) -> int {
         for (int k = 0; k < h->eval_poll; ++k) SDO(eval_step(h, deterministic, (int32_t)(++steps), (unsigned int)cap));
-        SHIP(h, hipMemcpyAsync(h->ev_counter_host, h->ev_counter, 4, hipMemcpyDeviceToHost, h->stream));
-        SDO(ssync(h));
-        seen = *h->ev_counter_host;
-    }
-    events.resize((size_t)std::min<long long>(seen, cap));
+        return DRIL_OK;
+    }));
+    events.resize((size_t)std::min<long long>(p.seen, cap));
     SHIP(h, hipMemcpy(events.data(), h->ev_events, events.size() * sizeof(SacEvalEvent), hipMemcpyDeviceToHost));
     return DRIL_OK;
 }
@@ -3038,142 +3078,62 @@ DRIL_EXPORT int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval, 
     if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_evaluate_agent: the envs of DRIL_ENV_EXTERNAL live on the host: evaluate there with dril_sac_predict_actions");
     if (n_eval < 1 || !out) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
     SDO(eval_buffers(h, sac_eval_event_capacity(n_eval, h->cfg.n_envs)));
-    // evaluation runs on the handle's own envs: what a collection would continue from is set aside here and put back below, on every path
-    const uint64_t seed0 = h->env.seed0; const bool ready = h->env.ready, obs_valid = h->obs_valid;
-    SDO(eval_snapshot(h, true));
+    EvalKeep keep; SDO(eval_set_aside(h, keep));
     std::vector<SacEvalEvent> events;
-    const int rc = eval_run(h, n_eval, deterministic, seed, events);
-    const std::string msg = h->err;
-    h->env.seed0 = seed0; h->env.ready = ready; h->obs_valid = obs_valid;
-    int rr = eval_snapshot(h, false); if (rr == DRIL_OK) rr = ssync(h);
-    if (rc != DRIL_OK) { h->err = msg; return rc; }
-    if (rr != DRIL_OK) return rr;
-    SacEvalSummary sum{};
-    sac_eval_reduce(events.data(), (int64_t)events.size(), n_eval, &sum, ep_rewards, ep_lengths);
-    out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length;
-    out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
+    SDO(eval_finish(h, keep, eval_run(h, n_eval, deterministic, seed, events)));
+    sac_eval_stats(events.data(), (int64_t)events.size(), n_eval, out, ep_rewards, ep_lengths);
     return DRIL_OK;
 }
 
 // ---- collect_trajectory (src/utils/trajectory_utils.jl:3-49) with the handle's actor on the handle's envs; docs/sac.md, "Trajectories" ---------------------------
 // The evaluation's launches with the episode accounting replaced by a recording of envs 0..M-1.  Built-in Box kinds: one env launch per step (sac_traj_env_kernel),
-// the env's own thread records from its registers.  Plug-ins: their code objects write terminal_obs where truncated only, so M SHADOW envs — a DeviceEnvs view of
-// the same plug-in with its own arrays, fixed_len = 1 and an unreachable time limit, which never resets — take every step a second time from the live envs' pre-step
-// state with the same env actions, and their observe is the post-step, pre-reset observation sac_traj_record_kernel records (the construction of
-// dril_collect_trajectory_device).
+// the env's own thread records from its registers.  Plug-ins: their code objects write terminal_obs where truncated only, so the M SHADOW envs of
+// dril_collect_trajectory_device (its comment in dril_api.hip; built by traj_setup, dril_traj_run.h) take every step a second time, with the same env actions, and
+// their observe is the post-step, pre-reset observation sac_traj_record_kernel records.
 namespace {
-constexpr int64_t kTrajMaxBytes = 1ll << 30;
-struct SacTrajRun {
-    TrajRec rec; TrajMaps maps; DeviceEnvs shadow;
-    float *sh_rew, *sh_tobs, *sh_obs; uint8_t *sh_term, *sh_trunc;
-};
-// carves the handle's blob (grown when the call needs more) and fills the table of bounds
-int traj_prepare(dril_sac_handle* h, const dril_traj_options* o, int32_t Tcap, SacTrajRun& r) {
-    const size_t M = (size_t)o->n_trajectories, D = (size_t)h->D, W = (size_t)h->A, S = (size_t)h->S, T = (size_t)Tcap;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_obs = take((T + 1) * M * D * 4), o_act = take(T * M * W * 4), o_rew = take(T * M * 4), o_len = take(M * 4), o_flg = take(M);
-    const size_t o_st = take(M * S * 4), o_sc = take(M * 4), o_ep = take(M * 4), o_gs = take(M * 4);
-    const size_t o_srew = take(M * 4), o_sterm = take(M), o_strunc = take(M), o_stobs = take(M * D * 4), o_sobs = take(M * D * 4), o_tab = take((2 * D + 2 * W) * 4);
-    if (off > h->traj_blob_bytes) {
-        SDO(ssync(h));
-        if (h->traj_blob) (void)hipFree(h->traj_blob);
-        h->traj_blob = nullptr; h->traj_blob_bytes = 0;
-        SHIP(h, hipMalloc((void**)&h->traj_blob, off)); h->traj_blob_bytes = off;
-    }
-    char* b = h->traj_blob;
-    r.rec = TrajRec{(int32_t)M, (int32_t)D, (int32_t)W, Tcap, (float*)(b + o_obs), (uint32_t*)(b + o_act), (float*)(b + o_rew), (int32_t*)(b + o_len), (uint8_t*)(b + o_flg), h->ev_counter};
-    r.shadow = h->env;                                                             // the plug-in's kernels, scaling
-    r.shadow.E = (int)M; r.shadow.fixed_len = 1; r.shadow.episode_len = INT32_MAX; r.shadow.disc_returns = nullptr;
-    r.shadow.state = (float*)(b + o_st); r.shadow.step_count = (int32_t*)(b + o_sc); r.shadow.episode = (uint32_t*)(b + o_ep); r.shadow.gstep = (uint32_t*)(b + o_gs);
-    r.sh_rew = (float*)(b + o_srew); r.sh_term = (uint8_t*)(b + o_sterm); r.sh_trunc = (uint8_t*)(b + o_strunc); r.sh_tobs = (float*)(b + o_stobs); r.sh_obs = (float*)(b + o_sobs);
-    // the table: obs_low | obs_high (D each), act_low | act_high (W each).  No ClampAdapter: TanhScaleAdapter's actions are inside the Box by construction
-    std::vector<float> tab(2 * D + 2 * W, 0.f);
-    float *ol = tab.data(), *oh = ol + D, *al = oh + D, *ah = al + W;
-    bool scaled = false;
-    if (h->env.module) {
-        scaled = h->env.scaling;
-        if (scaled) {
-            for (size_t i = 0; i < D; ++i) { ol[i] = h->env.obs_low[i]; oh[i] = h->env.obs_high[i]; }
-            for (size_t i = 0; i < W; ++i) { al[i] = h->env.desc.action_low[i]; ah[i] = h->env.desc.action_high[i]; }
-        }
-    } else if (const ScaledKindBoxes* sb = scaled_kind_boxes(h->env.kind)) {      // a built-in ScalingWrapperEnv: the boxes its kernels map from
-        scaled = true; al[0] = sb->act_low; ah[0] = sb->act_high;
-        for (int i = 0; i < sb->D; ++i) { ol[i] = sb->obs_low[i]; oh[i] = sb->obs_high[i]; }
-    }
-    SHIP(h, hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, h->stream));
-    SDO(ssync(h));                                                                 // (the table is a local)
-    const float* dt = (const float*)(b + o_tab);
-    r.maps = TrajMaps{scaled ? dt : nullptr, scaled ? dt + D : nullptr, nullptr, nullptr, scaled ? dt + 2 * D : nullptr, scaled ? dt + 2 * D + W : nullptr, 0, o->final_original ? 1 : 0};
-    return DRIL_OK;
-}
-int traj_record_launch(dril_sac_handle* h, const SacTrajRun& r, const TrajStep& s, int32_t t) {
-    const int64_t n = (int64_t)r.rec.M * std::max(r.rec.D, r.rec.W);
-    hipLaunchKernelGGL(sac_traj_record_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.rec, r.maps, s, t);
-    SHIP(h, hipGetLastError());
+// the recording of one call.  No ClampAdapter (the boxes' clamp_* stay null): TanhScaleAdapter's actions are inside the Box by construction
+int traj_prepare(dril_sac_handle* h, const dril_traj_options* o, int32_t Tcap, TrajRun& r) {
+    const TrajLayout L = traj_layout((size_t)o->n_trajectories, (size_t)h->D, (size_t)h->A, (size_t)h->S, (size_t)Tcap);
+    SHIP(h, traj_setup(h->env, h->stream, &h->traj_blob, &h->traj_blob_bytes, h->ev_counter, L, traj_env_boxes(h->env), o->final_original != 0, /*drain_before_free=*/true, r));
     return DRIL_OK;
 }
 // one env step, enqueued: the launches of eval_step without the accounting, and the recording of envs 0..M-1
-int traj_step(dril_sac_handle* h, const SacTrajRun& r, int32_t t, int deterministic, int32_t* launches) {
-    const int E = h->cfg.n_envs;
-    const int64_t f0 = h->fwd_launches; const int tag0 = h->col_tag;
-    const NzEvalArgs nz{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs};
+int traj_step(dril_sac_handle* h, const TrajRun& r, int32_t t, int deterministic, int32_t* launches) {
+    const int64_t f0 = h->fwd_launches; const int tag0 = h->col_tag; const NzEvalArgs nz = eval_step_nz(h);
     if (h->env.module) SHIP(h, hipMemcpyAsync(r.shadow.state, h->env.state, (size_t)r.rec.M * h->S * 4, hipMemcpyDeviceToDevice, h->stream));   // the pre-step state of envs 0..M-1 (env-major prefix)
-    CollectHeadArgs ca; SDO(actor_hidden(h, 0, nullptr, &ca));
-    ca.deterministic = deterministic ? 1 : 0;
+    CollectHeadArgs ca; SDO(eval_step_actor(h, deterministic, ca));
     *launches += (int32_t)(h->fwd_launches - f0) + (h->col_tag != tag0 ? 2 : 0);   // (the f16-piece form of the hidden layers: sac_collect_l1_kernel + sac_collect_l2_kernel)
     if (h->env.module) {
-        hipLaunchKernelGGL(sac_collect_head_kernel, dim3((E + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca);
+        eval_step_head(h, ca);
         SHIP(h, r.shadow.step(h->e_envact, EnvStepOut{r.sh_rew, r.sh_term, r.sh_trunc, r.sh_tobs, nullptr}, MonitorArgs{}, h->stream));   // the same step with the same actions' prefix, with no reset after it
         SHIP(h, r.shadow.observe(r.sh_obs, h->stream));                            // observe(env) of the env that did not auto-reset
-        SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, MonitorArgs{}, h->stream));   // act!(env, action), :35 (monitor pointers null)
-        SDO(traj_record_launch(h, r, TrajStep{h->e_envact, h->e_rew, h->e_term, h->e_trunc, r.sh_obs}, t));
+        SDO(eval_step_env(h));                                                     // act!(env, action), :35
+        SHIP(h, traj_record_launch(sac_traj_record_kernel, h->stream, r, TrajStep{h->e_envact, h->e_rew, h->e_term, h->e_trunc, r.sh_obs}, t));
         *launches += 6;                                                             // state copy, head, shadow step, shadow observe, live step, recording
         if (nz.st && nz.norm_obs) { NzApplyArgs a{}; a.w.raw = h->obs_nxt; a.w.obs_out = h->obs_nxt; SDO(nz_apply(h, a, 0, false, false)); *launches += 1; }   // the next observation under the frozen statistics, in place
-    } else {                                                                       // every built-in Box env has A = 1
-        const TrajEnvArgs te{env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr}), nz, r.rec, r.maps, t};
-        const dim3 grid((E + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
-        SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_traj_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, te); return hipGetLastError(); }));
+    } else {
+        SDO(eval_step_builtin(h, ca, [&](auto K, const CollectEnvArgs& env, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL(sac_traj_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, TrajEnvArgs{env, nz, r.rec, r.maps, t});
+        }));
         *launches += 1;
     }
-    SHIP(h, hipGetLastError());
-    std::swap(h->obs_cur, h->obs_nxt);
-    return DRIL_OK;
+    return eval_step_end(h);
 }
 // reset!(env) .. the loop of trajectory_utils.jl:16-45 on the device; the host looks at the finished-counter once per K steps and never enqueues a step past Tcap
-int traj_run(dril_sac_handle* h, const dril_traj_options* o, SacTrajRun& r, int32_t* steps_out, int32_t* launches_out) {
-    const int M = r.rec.M, Tcap = r.rec.Tcap;
-    if (o->has_seed) h->env.seed0 = o->seed;                                       // env e seeded seed + e; its action noise is that env's stream from step 0
-    r.shadow.seed0 = h->env.seed0;
-    SHIP(h, h->env.reset(h->stream));                                              // reset!(env), :10
-    h->env.ready = true; h->obs_valid = false;
-    if (h->env.module) {
-        SHIP(h, hipMemsetAsync(r.shadow.step_count, 0, (size_t)M * 4, h->stream)); SHIP(h, hipMemsetAsync(r.shadow.episode, 0, (size_t)M * 4, h->stream));
-        SHIP(h, hipMemsetAsync(r.shadow.gstep, 0, (size_t)M * 4, h->stream));
-    }
-    SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
-    SDO(ensure_obs(h));                                                            // observation = observe(env), :17 (raw, into obs_cur: the wrapper's old_obs is not this call's to write)
-    SDO(traj_record_launch(h, r, TrajStep{nullptr, nullptr, nullptr, nullptr, h->obs_cur}, 0));   // row 0: the original observation, before the agent's copy is normalised
-    if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }   // normalised in place, nothing updated
-    const int K = o->poll_steps > 0 ? o->poll_steps : h->eval_poll;
-    int32_t steps = 0, launches = 0; unsigned int seen = 0;
-    while (seen < (unsigned int)M) {
-        if (steps >= Tcap) return sfail(h, DRIL_ERR_HIP, "dril_sac_collect_trajectory: a trajectory is still open after its capacity (internal)");   // step Tcap finalises every open one
-        for (int k = 0; k < K && steps < Tcap; ++k) SDO(traj_step(h, r, ++steps, o->deterministic ? 1 : 0, &launches));
-        SHIP(h, hipMemcpyAsync(h->ev_counter_host, h->ev_counter, 4, hipMemcpyDeviceToHost, h->stream));
-        SDO(ssync(h));
-        seen = *h->ev_counter_host;
-    }
-    *steps_out = steps; *launches_out = launches;
-    return DRIL_OK;
-}
-int traj_run_and_copy(dril_sac_handle* h, const dril_traj_options* o, SacTrajRun& r, float* observations, float* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
-    int32_t steps = 0, launches = 0;
-    SDO(traj_run(h, o, r, &steps, &launches));
+int traj_run(dril_sac_handle* h, const dril_traj_options* o, TrajRun& r, float* observations, float* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
+    const int Tcap = r.rec.Tcap, K = o->poll_steps > 0 ? o->poll_steps : h->eval_poll;
+    const auto row0 = [&]() -> int {                                               // the original observation, before the agent's copy is normalised
+        SHIP(h, traj_record_launch(sac_traj_record_kernel, h->stream, r, TrajStep{nullptr, nullptr, nullptr, nullptr, h->obs_cur}, 0));
+        return DRIL_OK;
+    };
+    SDO(eval_open_episode(h, o->has_seed != 0, o->seed, row0, h->env.module ? &r.shadow : nullptr));
+    EvalPoll p;
+    SDO(eval_poll_loop(h, r.rec.M, Tcap, DRIL_ERR_HIP, "dril_sac_collect_trajectory: a trajectory is still open after its capacity (internal)", p, [&](long long& steps, int32_t& launches) -> int {   // (step Tcap finalises every open one)
+        for (int k = 0; k < K && steps < Tcap; ++k) SDO(traj_step(h, r, (int32_t)(++steps), o->deterministic ? 1 : 0, &launches));
+        return DRIL_OK;
+    }));
     const TrajCopyOut c = traj_copy_out(h->stream, r.rec, observations, (uint32_t*)actions, rewards, lengths, end_flags);
-    if (c.err != hipSuccess) return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_collect_trajectory: copy-out: ") + hipGetErrorString(c.err));
-    if (c.bad >= 0) return sfail(h, DRIL_ERR_HIP, "dril_sac_collect_trajectory: trajectory " + std::to_string(c.bad) + " has length " + std::to_string(c.bad_length) + " (internal)");
-    if (info) { info->capacity = r.rec.Tcap; info->steps_enqueued = steps; info->launches = launches; info->longest = c.longest; info->cut_by_max_steps = c.cuts; info->reserved[DRIL_TRAJ_INFO_PATH] = 0; }
+    if (const std::string msg = traj_report("dril_sac_collect_trajectory", c, Tcap, (int32_t)p.steps, p.launches, 0, info); !msg.empty()) return sfail(h, DRIL_ERR_HIP, msg);
     return DRIL_OK;
 }
 }  // namespace
@@ -3189,23 +3149,12 @@ DRIL_EXPORT int32_t dril_sac_collect_trajectory(dril_sac_handle* h, const dril_t
                                                 uint8_t* end_flags, dril_traj_info* info) {
     SNEED(h);
     if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_collect_trajectory: the envs of DRIL_ENV_EXTERNAL live on the host: record there, in a loop over dril_sac_predict_actions");
-    if (!o || !observations || !actions || !rewards || !lengths || !end_flags || o->n_trajectories < 1 || o->n_trajectories > h->cfg.n_envs || o->max_steps < 0 || o->poll_steps < 0)
-        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_collect_trajectory: options and the five output arrays != NULL, 1 <= n_trajectories <= n_envs, max_steps >= 0, poll_steps >= 0");
-    if (info) std::memset(info, 0, sizeof(*info));
-    const int32_t Tcap = traj_capacity(o->max_steps, h->env.episode_len);
-    const int64_t bytes = traj_bytes(o->n_trajectories, Tcap, h->D, h->A);
-    if (bytes > kTrajMaxBytes)
-        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_collect_trajectory: the recording needs " + std::to_string(bytes) + " bytes on the device (M = " + std::to_string(o->n_trajectories) + ", Tcap = " + std::to_string(Tcap) + "), more than 1 GiB: record fewer envs or set max_steps");
+    if (const std::string msg = traj_options_error("dril_sac_collect_trajectory", o, observations && actions && rewards && lengths && end_flags, h->cfg.n_envs); !msg.empty()) return sfail(h, DRIL_ERR_INVALID_ARG, msg);
+    int32_t Tcap = 0;
+    if (const std::string msg = traj_size_error("dril_sac_collect_trajectory", o, h->env.episode_len, h->D, h->A, info, &Tcap); !msg.empty()) return sfail(h, DRIL_ERR_INVALID_ARG, msg);
     SDO(eval_buffers(h, 0));
-    SacTrajRun run{};
-    SDO(traj_prepare(h, o, Tcap, run));
-    // as dril_sac_evaluate_agent: what a collection would continue from is set aside here and put back below, on every path
-    const uint64_t seed0 = h->env.seed0; const bool ready = h->env.ready, obs_valid = h->obs_valid;
-    SDO(eval_snapshot(h, true));
-    const int rc = traj_run_and_copy(h, o, run, observations, actions, rewards, lengths, end_flags, info);
-    const std::string msg = h->err;
-    h->env.seed0 = seed0; h->env.ready = ready; h->obs_valid = obs_valid;
-    int rr = eval_snapshot(h, false); if (rr == DRIL_OK) rr = ssync(h);
-    if (rc != DRIL_OK) { h->err = msg; return rc; }
-    return rr;
+    TrajRun run{}; SDO(traj_prepare(h, o, Tcap, run));
+    // as dril_sac_evaluate_agent: what a collection would continue from is set aside here and put back by eval_finish, on every path
+    EvalKeep keep; SDO(eval_set_aside(h, keep));
+    return eval_finish(h, keep, traj_run(h, o, run, observations, actions, rewards, lengths, end_flags, info));
 }

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include "../../include/dril_hip.h"   // dril_eval_stats
 
 namespace dril {
 struct SacEvalEvent { int32_t step, env; float ret; int32_t len; };   // step: 1-based env step of the evaluation in which the episode ended
@@ -38,5 +39,10 @@ inline int32_t sac_eval_reduce(SacEvalEvent* events, int64_t n_events, int32_t n
     out->n_episodes = n; out->n_steps = n > 0 ? events[n - 1].step : 0;
     for (int32_t i = 0; i < n; ++i) { if (episode_rewards) episode_rewards[i] = events[i].ret; if (episode_lengths) episode_lengths[i] = events[i].len; }
     return n;
+}
+// the same into the struct both handles' verbs return (dril_sac_evaluate_agent, dril_evaluate_agent_device)
+inline void sac_eval_stats(SacEvalEvent* events, int64_t n_events, int32_t n_eval, dril_eval_stats* out, float* episode_rewards, int32_t* episode_lengths) {
+    SacEvalSummary sum{}; sac_eval_reduce(events, n_events, n_eval, &sum, episode_rewards, episode_lengths);
+    out->mean_reward = sum.mean_reward; out->std_reward = sum.std_reward; out->mean_length = sum.mean_length; out->std_length = sum.std_length; out->n_episodes = sum.n_episodes; out->n_steps = sum.n_steps;
 }
 }  // namespace dril
