@@ -135,6 +135,7 @@ struct dril_handle {
     double* rms_partials = nullptr; int rms_blocks = 256; float* e_obs_raw = nullptr; float* e_rew_n = nullptr;   // e_obs_raw / e_rew: get_original_obs / get_original_rewards; e_rew_n: rewards as the wrapper delivers them
     double* rms_red = nullptr;   // data-parallel: this step's partial sums folded to one row and summed over ranks
     int grad_actor_pct = 0;   // ppo_grad_pair_kernel: share (per mille) of the pairs given to the actor; 0 = by head (env DRIL_GRAD_ACTOR_PERMILLE)
+    int last_G = 0, last_Gc = 0; mutable char grad_info[640] = {0};   // the grid of that step (slabs of the actor / of the critic; ppo_grad_pair_kernel: pairs) and the text dril_grad_kernel_info returns
     int last_variant = -1;  // which gradient kernel the last optimiser step ran: 0 ppo_grad_kernel, 2 ppo_grad_wide_kernel, 3 generic path, 4 ppo_grad_wide_split_kernel, 5 ppo_grad_pair_kernel (dril_grad_kernel_info)
     int grad_variant = -1;  // env DRIL_GRAD_VARIANT: 0 = the exact-f32 kernels (ppo_grad_kernel / ppo_grad_wide_kernel), 1 = the bf16-split kernels (ppo_grad_pair_kernel at hidden 64, ppo_grad_wide_split_kernel at 128 / 256) for every minibatch size, -1 = default: wide nets split, hidden 64 by minibatch size
     bool external = false; bool generic = false; float* gen_tmp = nullptr;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
@@ -489,6 +490,7 @@ int ppo_step(dril_handle* h, const float* obs, const void* actions, const float*
     { int rcw = ensure_wimg(h); if (rcw) return rcw; }
     h->last_variant = h->generic ? 3 : h->wide ? (variant ? 4 : 2) : (variant == 2 ? 5 : variant);
     if (h->last_variant == 4 || h->last_variant == 5) h->used_f16 = true;
+    h->last_G = G; h->last_Gc = Gc;
     const double* adv_stats = h->adv_stats;
     // launch-bound regime (the reference's default batch_size = 64): the advantage moments are computed inside the grad kernel and
     // reduce + norm + Adam run as one workgroup: 2 dependent launches per optimiser step instead of 6
@@ -3274,9 +3276,8 @@ DRIL_EXPORT const char* dril_kernel_name(int32_t kid) {
     return (kid >= 0 && kid < DRIL_K_COUNT) ? names[kid] : "?";
 }
 DRIL_EXPORT int32_t dril_kernel_count(void) { return DRIL_K_COUNT; }
-DRIL_EXPORT const char* dril_grad_kernel_info(const dril_handle* h) {
-    if (!h) return "?";
-    switch (h->last_variant) {
+static const char* grad_kernel_base(int variant) {
+    switch (variant) {
         case 0: return "ppo_grad_kernel: f32 (v_mfma_f32_32x32x2_f32)";
         case 2: return "ppo_grad_wide_kernel: f32 (v_mfma_f32_32x32x2_f32)";
         case 6: return "ppo_update_small_kernel: f32 (f16x2 split, f32 accumulate; v_mfma_f32_32x32x16_f16 x 3 per k16 step on two-piece f16 operands = 2^-24 relative, input layer on v_mfma_f32_32x32x2_f32; two persistent workgroups (actor | critic), all optimiser steps of the iteration in one launch)";
@@ -3285,5 +3286,12 @@ DRIL_EXPORT const char* dril_grad_kernel_info(const dril_handle* h) {
         case 3: return "generic path: f32 contractions (sac_gemm_*; large ones bf16x3 split, f32 accumulate)";
         default: return "none yet";
     }
+}
+DRIL_EXPORT const char* dril_grad_kernel_info(const dril_handle* h) {
+    if (!h) return "?";
+    const char* base = grad_kernel_base(h->last_variant);
+    if (h->last_variant < 0 || h->last_variant == 6) return base;              // no step yet; ppo_update_small_kernel has no slab grid
+    std::snprintf(h->grad_info, sizeof(h->grad_info), "%s; grid G=%d Gc=%d", base, h->last_G, h->last_Gc);   // what ppo_step launched: slabs (ppo_grad_pair_kernel: pairs) of the actor, of the critic
+    return h->grad_info;
 }
 DRIL_EXPORT const char* dril_version(void) { return "dril_hip 0.2 (gfx950, abi 2)"; }

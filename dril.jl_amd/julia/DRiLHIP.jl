@@ -471,7 +471,7 @@ function f32_fallback_info(env::DeviceParallelEnv)
     check(ccall((:dril_f32_fallback_info, LIB[]), Int32, (Ptr{Cvoid}, Ref{DrilF32Fallback}), env.handle, out), env.handle)
     return out[]
 end
-"which gradient kernel the last optimiser step ran and the arithmetic it computes in, e.g. \"ppo_grad_pair_kernel: f32 (f16x2 split, f32 accumulate; ...)\" (dril_grad_kernel_info)"
+"which gradient kernel the last optimiser step ran and the arithmetic it computes in, e.g. \"ppo_grad_pair_kernel: f32 (f16x2 split, f32 accumulate; ...); grid G=460 Gc=564\" (dril_grad_kernel_info; the grid is the slabs — pair kernel: pairs — of the actor and of the critic)"
 grad_kernel_info(env::DeviceParallelEnv) = unsafe_string(ccall((:dril_grad_kernel_info, LIB[]), Cstring, (Ptr{Cvoid},), env.handle))
 "which device the handle lives on: ordinal, name, PCI bus id, visibility masks (dril_device_info) — the line every rank of a multi-GPU job should print before `comm_init`"
 device_info(env::DeviceParallelEnv) = unsafe_string(ccall((:dril_device_info, LIB[]), Cstring, (Ptr{Cvoid},), env.handle))
