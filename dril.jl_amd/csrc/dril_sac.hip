@@ -1345,6 +1345,7 @@ struct dril_sac_handle {
     SacScalars* sc_next = nullptr;   // ping-pong partner of `sc` (fused heads: the entropy step writes the new state here, then the two are swapped)
     double* head_partials = nullptr; unsigned int* head_counter = nullptr; unsigned* col_h1p = nullptr; unsigned* col_w2p = nullptr; int* col_flags = nullptr; int col_tag = 0, col_w2tag = 0; bool col_w2_dirty = true, f16_fwd = true, l2_attr_set = false;   // the f16-piece collection forward (sac_collect_l2_kernel)
     unsigned long long* it_stamps = nullptr; int it_stamps_cap = 0; double wall_hz = 1e8; bool fused_heads = true; bool fused_dw1 = false; int fl_c = 0, fl_a = 0; bool fused_collect = true; bool fused_fwd = true; bool trace_enqueue = false; std::vector<hipEvent_t> it_events; int iter_chunk = 64;   // fused output-layer + head kernels (DRIL_SAC_NO_FUSED_HEADS=1: the round-1 launch sequence, A/B)
+    int upd_route[3] = {-1, 0, 0}; mutable char upd_info[160] = {0};   // what the last sac_one_update enqueued: {first layers in the gather, PRE head, launched yet} (dril_sac_update_info)
     float bt_actor[2], bt_critic[2], bt_ent[2]; int64_t grad_updates = 0; uint64_t update_counter = 0, aux_counter = 0;
     float target_entropy = 0, act_lo = -2.0f, act_hi = 2.0f; bool external = false;   // bounds of the agent-facing action space: Box(-2,2), Box(-1,1) under ScalingWrapperEnv
     float* act_bounds = nullptr;                     // device table [low[kMaxA] | high[kMaxA]] the sampling kernels read: the pair above in every entry, or a plug-in's bounds per dimension
@@ -1508,6 +1509,7 @@ int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long*
                   rng, h->xa, h->xq, h->b_rew, h->b_ne, h->b_nn, h->b_np, h->b_term};
     const int relu_ = h->cfg.activation ? 1 : 0;
     const bool l1 = h->fused_heads && W <= kFusedL1MaxIn;      // narrow inputs: first layers inside the gather / head kernels (two launches less)
+    h->upd_route[0] = l1 ? 1 : 0; h->upd_route[1] = 0; h->upd_route[2] = 1;
     if (l1) {
         GatherL1Args gl{ga, h->H1, relu_, h->params + h->actor.w1, h->params + h->actor.b1, h->ah1, h->params, h->q0.w1, h->q0.b1, h->Pqd, (long long)h->nq * h->H1, h->qh1};
         hipLaunchKernelGGL(sac_gather_l1_kernel, dim3(B), dim3(256), 0, h->stream, gl);
@@ -1524,7 +1526,9 @@ int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long*
         double* hp_critic = h->head_partials; double* hp_actor = hp_critic + 2 * (size_t)hb; double* hp_ls = hp_actor + 2 * (size_t)hb; double* hp_ent = hp_ls + (size_t)kMaxA * hb;   // one region per head kernel
         ActorHeadFusedArgs af{en, h->ah2, h->H2, h->params + h->actor.w3, h->params + h->actor.b3, h->mu, hp_ent, h->head_counter,
                               l1 ? 1 : 0, h->H1, relu, h->params, h->q0.w1, h->q0.b1, h->Pqd, (long long)h->nq * h->H1, h->qh1};
-        if (W <= kL1PreMaxIn && (!l1 || h->H1 <= kL1PreMaxH)) hipLaunchKernelGGL(sac_actor_out_ent_kernel<true>, dim3(hb), dim3(256), 0, h->stream, af);
+        const bool pre = W <= kL1PreMaxIn && (!l1 || h->H1 <= kL1PreMaxH);
+        h->upd_route[1] = pre ? 1 : 0;
+        if (pre) hipLaunchKernelGGL(sac_actor_out_ent_kernel<true>, dim3(hb), dim3(256), 0, h->stream, af);
         else hipLaunchKernelGGL(sac_actor_out_ent_kernel<false>, dim3(hb), dim3(256), 0, h->stream, af);
         if (h->cfg.auto_ent_coef) { h->bt_ent[0] *= h->cfg.adam_beta1; h->bt_ent[1] *= h->cfg.adam_beta2; }
         // critic: all four Q nets' hidden layers in one pass (z = 0,1 the critics on (obs, action), z = 2,3 the targets on (next obs, next action)), then output
@@ -2617,6 +2621,17 @@ DRIL_EXPORT int32_t dril_sac_update(dril_sac_handle* h, int32_t n_updates, dril_
     const int rc = run_updates(h, n_updates, h->inj_updates != 0, out);
     clear_injected(h);
     return rc;
+}
+// which launches the last sac_one_update enqueued, from what that function decided (no launch, no device read): the route of tests/sac_update_cases.py
+DRIL_EXPORT const char* dril_sac_update_info(const dril_sac_handle* h) {
+    if (!h) return "";
+    if (!h->upd_route[2]) return "none";
+    const int B = h->cfg.batch_size, hb = (B + kHeadSamplesPerBlock - 1) / kHeadSamplesPerBlock;
+    const bool l1 = h->upd_route[0] != 0, pre = h->upd_route[1] != 0, fl = h->fused_heads && h->fused_dw1;
+    std::snprintf(h->upd_info, sizeof(h->upd_info), "gather=%s head=%s dw1=%s l1pre=%d hb=%d adam_blocks=%d end_blocks=%d fl_blocks=%d",
+                  l1 ? "l1" : "plain", !h->fused_heads ? "unfused" : pre ? "fused,pre" : "fused,nopre", fl ? "fused" : "launch", l1 && pre ? 1 : 0,
+                  h->fused_heads ? hb : 1, h->adam_blocks_c, h->end_blocks, fl ? h->fl_c + h->fl_a : 0);
+    return h->upd_info;
 }
 DRIL_EXPORT int32_t dril_sac_get_last_grads(dril_sac_handle* h, float* gc, float* ga, size_t n) {
     SNEED(h); if (n != (size_t)h->P) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_get_last_grads: n must equal dril_sac_param_count");

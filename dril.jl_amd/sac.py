@@ -468,6 +468,10 @@ class SacHandle:
         self._chk(self._f("get_last_grads")(self._h, self._p(gc), self._p(ga), self.P))
         return gc, ga
 
+    def update_info(self) -> str:
+        """dril_sac_update_info: the launches the last gradient step enqueued ("gather=l1 head=fused,pre dw1=fused ...")"""
+        return self._f("update_info")(self._h).decode()
+
     def train(self, max_steps: int, stats_capacity: int = 1 << 16, fps_capacity: int = 1 << 16):
         stats = (DrilSacStats * stats_capacity)()
         fps = np.zeros(fps_capacity, np.float64)

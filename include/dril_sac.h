@@ -262,6 +262,10 @@ int32_t dril_sac_debug_set_batches(dril_sac_handle* h, int32_t n_updates, const 
 /* gradients of the LAST gradient step in the parameter layout (n = param_count): critic_grad = d critic_loss (non-zero
  * only in the two Q nets), actor_grad = d actor_loss after zero_critic_grads! (non-zero in actor_head and log_std) */
 int32_t dril_sac_get_last_grads(dril_sac_handle* h, float* critic_grad, float* actor_grad, size_t n);
+/* the launches the LAST gradient step enqueued, as text: "gather=l1|plain head=fused,pre|fused,nopre|unfused dw1=fused|launch
+ * l1pre=<0|1> hb=<head blocks> adam_blocks=<n> end_blocks=<n> fl_blocks=<first-layer blocks among them>" ("none" before the first
+ * step).  Host state only: no launch, no device read.  The pointer stays valid until the next call on this handle */
+const char* dril_sac_update_info(const dril_sac_handle* h);
 
 /* ---- train!(agent, env, alg::SAC, max_steps) sac.jl:406-549 ----------------------------------------------------------
  * first collection of max(1, start_steps / E) steps with random actions (:438-440,485-489), then `iterations` rounds of
