@@ -334,6 +334,7 @@ _SIG = {
     "dril_comm_allreduce_calls": (C.c_int64, [_P]),
     "dril_device_info": (C.c_char_p, [_P]),
     "dril_debug_comm_loopback": (C.c_int32, [C.POINTER(_P), C.c_int32]),
+    "dril_debug_device_bytes_live": (C.c_int64, []),
     "dril_profile_get": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "dril_profile_launches": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "dril_profile_reset": (C.c_int32, [_P]),

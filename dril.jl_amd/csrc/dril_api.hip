@@ -17,6 +17,7 @@
 
 #include "../../include/dril_hip.h"
 #include "dril_internal.h"
+#include "dril_devmem.h"     // DevBuf / PinnedBuf: every allocation a handle or a population holds; a raw pointer member is not owned
 #include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper on plug-ins shares with the SAC handle's (NormWrap, norm_moments_kernel, nz_*)
 #include "dril_policy_internal.h"   // dril_policy_from_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
 #include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in kind or a device env plug-in), shared with the SAC handle
@@ -105,79 +106,79 @@ struct dril_handle {
     hipStream_t stream = nullptr;
     int num_cus = 256;
     std::string device_info;   // "device <ordinal> of <visible>: <name> <arch>, PCI <bus id>, HIP_VISIBLE_DEVICES=.. ROCR_VISIBLE_DEVICES=.." (dril_device_info; part of every RCCL failure message)
-    float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *bt = nullptr, *flat = nullptr, *norm_out = nullptr;
-    double* norm_partials = nullptr; int n_norm_partials = 0;
-    float *slabs_a = nullptr, *slabs_c = nullptr; int slab_a = 0, slab_c = 0, Gmax = 0;
+    DevBuf<float> params, adam_m, adam_v, bt, flat, norm_out;
+    DevBuf<double> norm_partials; int n_norm_partials = 0;
+    DevBuf<float> slabs_a, slabs_c; int slab_a = 0, slab_c = 0, Gmax = 0;
     DeviceEnvs env;   // the envs on the device: simulator state and counters, the seed, and for DRIL_ENV_MODULE the loaded plug-in (dril_env_side.h)
-    float *obs = nullptr, *rew = nullptr, *adv = nullptr, *ret = nullptr, *logp = nullptr, *val = nullptr, *boot = nullptr, *last_values = nullptr;
-    void* act = nullptr; uint8_t* flags = nullptr;
-    void* noise_dev = nullptr; bool noise_set = false;
-    int64_t* perm_dev = nullptr; size_t perm_count = 0;
-    int32_t* epoch_index = nullptr; bool no_epoch_index = false;   // the device DataLoader order of the current epoch, written out (large minibatches; DRIL_NO_EPOCH_INDEX)
-    double *adv_partials = nullptr, *adv_stats = nullptr, *ev_partials = nullptr; int adv_blocks = 0, ev_blocks = 0;
-    float* step_stats = nullptr; int step_stats_cap = 0;
-    int *stop_flag = nullptr, *nan_flag = nullptr;
-    float *e_obs = nullptr, *e_rew = nullptr, *e_tobs = nullptr; uint8_t *e_term = nullptr, *e_trunc = nullptr; void* e_act = nullptr;
+    DevBuf<float> obs, rew, adv, ret, logp, val, boot, last_values;
+    DevBuf<char> act; DevBuf<uint8_t> flags;
+    DevBuf<char> noise_dev; bool noise_set = false;
+    DevBuf<int64_t> perm_dev; size_t perm_count = 0;
+    DevBuf<int32_t> epoch_index; bool no_epoch_index = false;   // the device DataLoader order of the current epoch, written out (large minibatches; DRIL_NO_EPOCH_INDEX)
+    DevBuf<double> adv_partials, adv_stats, ev_partials; int adv_blocks = 0, ev_blocks = 0;
+    DevBuf<float> step_stats;
+    DevBuf<int> stop_flag, nan_flag;
+    DevBuf<float> e_obs, e_rew, e_tobs; DevBuf<uint8_t> e_term, e_trunc; DevBuf<char> e_act;
     uint64_t adam_steps = 0, update_counter = 0; uint32_t policy_calls = 0;
     float lr = 0;
-    unsigned long long* dbg = nullptr;
+    DevBuf<unsigned long long> dbg;
     bool force_allreduce = false, force_stepwise = false;
     bool fused_rollout = false; int64_t rollout_launches = 0;   // dril_rollout_fused_enable; launch calls of the last plug-in collection (dril_rollout_fused_info)
-    double *epoch_tables = nullptr, *epoch_stats = nullptr; int epoch_blocks = 2048, epoch_nb_cap = 0;   // per-epoch advantage moments
-    float *w2a_actor = nullptr, *w2ta_actor = nullptr, *w2a_critic = nullptr, *w2ta_critic = nullptr; bool wide = false, wimg_dirty = true;   // wide nets (H > 64)
-    void *w2pf_actor = nullptr, *w2pf_critic = nullptr;   // wide nets: the forward stream in the k-order of a register B operand (net_forward_wide_split)
-    void *w2p_actor = nullptr, *w2tp_actor = nullptr, *w2p_critic = nullptr, *w2tp_critic = nullptr;   // wide nets: pre-split bf16 fragment streams of W2 / W2' (ppo_grad_wide_split_kernel)
+    DevBuf<double> epoch_tables, epoch_stats; int epoch_blocks = 2048;   // per-epoch advantage moments
+    DevBuf<float> w2a_actor, w2ta_actor, w2a_critic, w2ta_critic; bool wide = false, wimg_dirty = true;   // wide nets (H > 64)
+    DevBuf<char> w2pf_actor, w2pf_critic;   // wide nets: the forward stream in the k-order of a register B operand (net_forward_wide_split)
+    DevBuf<char> w2p_actor, w2tp_actor, w2p_critic, w2tp_critic;   // wide nets: pre-split bf16 fragment streams of W2 / W2' (ppo_grad_wide_split_kernel)
     // MonitorWrapperEnv (cfg.monitor_window > 0)
-    float *mon_cur_ret = nullptr, *ep_ret = nullptr, *mon_ring_ret = nullptr, *e_ep_ret = nullptr; int32_t *mon_cur_len = nullptr, *ep_len = nullptr, *mon_ring_len = nullptr, *e_ep_len = nullptr;
-    int *mon_cnt = nullptr, *mon_meta = nullptr; uint8_t* e_flags = nullptr;
-    float4* rec = nullptr;   // packed minibatch records (see pack_records_kernel)
-    RmsState *obs_rms = nullptr, *ret_rms = nullptr; int obs_par = 0, ret_par = 0;   // ping-pong RunningMeanStd pairs
-    double* rms_partials = nullptr; int rms_blocks = 256; float* e_obs_raw = nullptr; float* e_rew_n = nullptr;   // e_obs_raw / e_rew: get_original_obs / get_original_rewards; e_rew_n: rewards as the wrapper delivers them
-    double* rms_red = nullptr;   // data-parallel: this step's partial sums folded to one row and summed over ranks
+    DevBuf<float> mon_cur_ret, ep_ret, mon_ring_ret, e_ep_ret; DevBuf<int32_t> mon_cur_len, ep_len, mon_ring_len, e_ep_len;
+    DevBuf<int> mon_cnt, mon_meta; DevBuf<uint8_t> e_flags;
+    DevBuf<float4> rec;   // packed minibatch records (see pack_records_kernel)
+    DevBuf<RmsState> obs_rms, ret_rms; int obs_par = 0, ret_par = 0;   // ping-pong RunningMeanStd pairs
+    DevBuf<double> rms_partials; int rms_blocks = 256; DevBuf<float> e_obs_raw; DevBuf<float> e_rew_n;   // e_obs_raw / e_rew: get_original_obs / get_original_rewards; e_rew_n: rewards as the wrapper delivers them
+    DevBuf<double> rms_red;   // data-parallel: this step's partial sums folded to one row and summed over ranks
     int grad_actor_pct = 0;   // ppo_grad_pair_kernel: share (per mille) of the pairs given to the actor; 0 = by head (env DRIL_GRAD_ACTOR_PERMILLE)
     int last_G = 0, last_Gc = 0; mutable char grad_info[640] = {0};   // the grid of that step (slabs of the actor / of the critic; ppo_grad_pair_kernel: pairs) and the text dril_grad_kernel_info returns
     int last_variant = -1;  // which gradient kernel the last optimiser step ran: 0 ppo_grad_kernel, 2 ppo_grad_wide_kernel, 3 generic path, 4 ppo_grad_wide_split_kernel, 5 ppo_grad_pair_kernel (dril_grad_kernel_info)
     int grad_variant = -1;  // env DRIL_GRAD_VARIANT: 0 = the exact-f32 kernels (ppo_grad_kernel / ppo_grad_wide_kernel), 1 = the bf16-split kernels (ppo_grad_pair_kernel at hidden 64, ppo_grad_wide_split_kernel at 128 / 256) for every minibatch size, -1 = default: wide nets split, hidden 64 by minibatch size
-    bool external = false; bool generic = false; float* gen_tmp = nullptr;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
+    bool external = false; bool generic = false; DevBuf<float> gen_tmp;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
     GenericDims gd{}; GenericWs gws; int ext_t = 0; bool ext_acted = false;   // DRIL_ENV_EXTERNAL: host envs, generic kernels
-    float* ext_stage_rew = nullptr; uint8_t* ext_stage_flags = nullptr;   // pinned [T][E] staging: dril_ext_record returns without draining the stream
+    PinnedBuf<float> ext_stage_rew; PinnedBuf<uint8_t> ext_stage_flags;   // pinned [T][E] staging: dril_ext_record returns without draining the stream
     // the device-array verbs (dril_ext_*_device): the two ordering events (created once), the sticky error word and its pinned host copy, the ClampAdapter's
     // per-dimension table (dril_ext_set_action_bounds), the counters of dril_ext_device_info, grow-only scratch of dril_predict_actions_device
-    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; int* ext_err = nullptr; int* ext_err_host = nullptr;
+    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; DevBuf<int> ext_err; PinnedBuf<int> ext_err_host;
     ExtBounds ext_bounds{}; bool ext_bounds_set = false;
     int ext_steps_dev = 0, ext_steps_host = 0, ext_syncs = 0; int64_t ext_launches = 0;
-    void* ext_pred_act = nullptr; float* ext_pred_lp = nullptr; int64_t ext_pred_cap = 0;
+    DevBuf<char> ext_pred_act; DevBuf<float> ext_pred_lp;
     // NormalizeWrapperEnv around a plug-in env (dril_normalize_enable; kernels: dril_norm_wrap.h, dril_ppo_norm.h).  pn_red: the one row a data-parallel job all-reduces.
     // The wrapper's other arrays are the handle's own: disc_returns (`returns`), e_obs_raw / e_rew (old_obs / old_rewards: dril_normalize_get_original), e_rew_n (the
     // rewards dril_env_step delivers)
-    NormWrap pn; int pn_rows_cap = 0; double* pn_red = nullptr;
+    NormWrap pn; int pn_rows_cap = 0; DevBuf<double> pn_red;
     // the same wrapper and MonitorWrapperEnv around the envs of a DRIL_ENV_EXTERNAL handle (dril_ext_normalize_enable / dril_ext_monitor_enable; kernels: dril_ext_norm.h): pn
     // again, with e_tobs as the scratch of normalised terminal observations; ext_mon_window sizes the monitor arrays above (cfg.monitor_window stays 0).  xw_added: launches
     // the wrappers added to the act / record / finish calls of the current rollout; xw_allocs: allocations inside those calls since enable (dril_ext_wrap_info)
-    int ext_mon_window = 0; int64_t xw_added[3] = {0, 0, 0}, xw_allocs = 0; float* ext_pred_obs = nullptr; int64_t ext_pred_obs_cap = 0;
+    int ext_mon_window = 0; int64_t xw_added[3] = {0, 0, 0}, xw_allocs = 0; DevBuf<float> ext_pred_obs;
     void* comm = nullptr;
     LoopGroup* loop = nullptr;   // debug loopback communicator (dril_debug_comm_loopback)
     dril_population* pop = nullptr;   // the population the handle is a member of (dril_population_join): dril_destroy waits for dril_population_destroy
     int64_t allreduce_calls = 0;
-    float* retry_snap = nullptr; bool no_f32_retry = false; int64_t f32_retries = 0;   // ppo_update: state before the update (for the exact-f32 redo of an update that left f16's range); DRIL_NO_F32_RETRY; how often it happened
+    DevBuf<float> retry_snap; bool no_f32_retry = false; int64_t f32_retries = 0;   // ppo_update: state before the update (for the exact-f32 redo of an update that left f16's range); DRIL_NO_F32_RETRY; how often it happened
     // the redo's bookkeeping (dril_f32_fallback_info): used_f16 = an f16-piece kernel ran in the current update (sticky over its optimiser steps — the LAST step's kernel says nothing
     // about a ragged tail); streak = consecutive redone updates; after kRetryLatchAfter of them the next kRetryLatchUpdates updates run the exact-f32 kernels directly (no wasted f16
     // pass, no snapshot), then ONE update probes f16 again; direct = updates run that way (latched, or max |W2| out of f16's range)
     bool used_f16 = false, spin_timeout = false; int f32_streak = 0, f32_latch_left = 0; int64_t f32_direct_updates = 0, persistent_fallbacks = 0;
-    unsigned long long* gae_carry = nullptr; unsigned gae_tag = 0; int* gae_err = nullptr;   // gae_scan_kernel: the chunk-to-chunk carry words, the launch tag that validates them, its give-up flag
-    unsigned* w2max_dev = nullptr; float w2max = 0.f;   // max |W2| over both nets (fused kernels): host copy refreshed by dril_set_params and with every optimiser run's statistics
+    DevBuf<unsigned long long> gae_carry; unsigned gae_tag = 0; DevBuf<int> gae_err;   // gae_scan_kernel: the chunk-to-chunk carry words, the launch tag that validates them, its give-up flag
+    DevBuf<unsigned> w2max_dev; float w2max = 0.f;   // max |W2| over both nets (fused kernels): host copy refreshed by dril_set_params and with every optimiser run's statistics
     bool no_small_path = false;   // DRIL_NO_SMALL_PATH (with DRIL_DEBUG=1), latched in dril_create
-    bool no_persistent = false; unsigned long long* small_xchg = nullptr; uint64_t* epoch_keys = nullptr; int epoch_keys_cap = 0; int64_t small_chunk = 16384;   // ppo_update_small_kernel (batch_size <= 64): DRIL_NO_PERSISTENT_UPDATE; per-epoch DataLoader keys on the device
+    bool no_persistent = false; DevBuf<unsigned long long> small_xchg; DevBuf<uint64_t> epoch_keys; int64_t small_chunk = 16384;   // ppo_update_small_kernel (batch_size <= 64): DRIL_NO_PERSISTENT_UPDATE; per-epoch DataLoader keys on the device
     std::vector<ProfEvent> prof_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
     double prof_ms[DRIL_K_COUNT] = {0}; int64_t prof_n[DRIL_K_COUNT] = {0}, prof_all[DRIL_K_COUNT] = {0}; bool prof_open = false;
     // dril_evaluate_agent_device: where the env side is set aside for the call, the per-env running sums, the event list and its counter (pinned host word for the poll)
-    char* eval_snap = nullptr; size_t eval_snap_bytes = 0; float* eval_cur_ret = nullptr; int32_t* eval_cur_len = nullptr;
-    unsigned int *eval_counter = nullptr, *eval_counter_host = nullptr; SacEvalEvent* eval_events = nullptr; long long eval_events_cap = 0;
+    DevBuf<char> eval_snap; DevBuf<float> eval_cur_ret; DevBuf<int32_t> eval_cur_len;
+    DevBuf<unsigned int> eval_counter; PinnedBuf<unsigned int> eval_counter_host; DevBuf<SacEvalEvent> eval_events;
     // dril_collect_trajectory_device: ONE grow-only blob for the step-major recording, the shadow envs' arrays and the table of bounds (the counter and its pinned word are the evaluation's)
-    char* traj_blob = nullptr; size_t traj_blob_bytes = 0;
+    DevBuf<char> traj_blob;
     // path 2 of both verbs (a plug-in's fused evaluation kernel): ONE grow-only blob for the observation and action scratch, the K rows of rewards and flag bytes and,
     // when recording, the rows of raw actions and post-step observations
-    char* evalf_blob = nullptr; size_t evalf_blob_bytes = 0;
+    DevBuf<char> evalf_blob;
     std::string err;
 };
 
@@ -190,7 +191,6 @@ int fail(dril_handle* h, int code, const std::string& msg) { if (h) h->err = msg
 // every entry point makes the handle's device current first: a process may hold handles on several devices
 #define NEED(h) do { if (!(h)) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle"); (void)hipSetDevice((h)->cfg.device); } while (0)
 
-template <typename T> hipError_t dmalloc(T** p, size_t n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
 
 // cfg.profile_events = k >= 1: the per-iteration classes (rollout, GAE, pack, moments, explained variance) are bracketed at every launch; the classes launched once per
 // OPTIMISER STEP (gradient, reduce, Adam, all-reduce) at every k-th launch — a hipEventRecord costs the stream ~3.5 us and an iteration of configs[1] holds 960 such launches
@@ -320,7 +320,7 @@ PolicyArgs policy_args(dril_handle* h, const float* obs, int64_t B, const void* 
     a.mode = mode; a.action_start = h->cfg.action_start; a.log_std_off = h->log_std_off; a.seed = h->cfg.seed; a.call_counter = h->policy_calls;
     a.actor = h->actor; a.critic = h->critic;
     a.exact_f32 = fwd_exact(h) ? 1 : 0;
-    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = a.exact_f32 ? h->w2a_critic : (const float*)h->w2pf_critic;   // wide nets: W2 operand of the forward
+    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor.get(); a.w2a_critic = a.exact_f32 ? h->w2a_critic : (const float*)h->w2pf_critic.get();   // wide nets: W2 operand of the forward
     return a;
 }
 
@@ -366,7 +366,7 @@ int global_partials(dril_handle* h, bool update, const double*& partials, int& n
 
 // ---- NormalizeWrapperEnv around a device env plug-in (dril_normalize_enable) ----
 #include "dril_ppo_norm.h"
-void pn_free(dril_handle* h) { h->pn.release(); if (h->pn_red) hipFree(h->pn_red); h->pn_red = nullptr; }
+void pn_free(dril_handle* h) { h->pn.release(); h->pn_red.release(); }
 // norm_moments_kernel over e_obs_raw (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
 int pn_moments(dril_handle* h, bool obs, bool ret, int* rows) {
     const int E = h->cfg.n_envs, D = h->D;
@@ -510,7 +510,7 @@ int ppo_step(dril_handle* h, const float* obs, const void* actions, const float*
     GradArgs g{};
     g.params = h->params; g.obs = obs; g.actions = actions; g.adv = adv; g.ret = ret; g.logp_old = logp_old; g.val_old = val_old;
     g.perm = perm; g.perm32 = perm32; g.pos0 = pos0; g.count = count; g.N = N; g.idx_lo = 0; g.n_local = N; g.perm_key = key; g.perm_bits = bits;
-    g.w2p_actor = (const u32x4*)h->w2p_actor; g.w2tp_actor = (const u32x4*)h->w2tp_actor; g.w2p_critic = (const u32x4*)h->w2p_critic; g.w2tp_critic = (const u32x4*)h->w2tp_critic;
+    g.w2p_actor = (const u32x4*)h->w2p_actor.get(); g.w2tp_actor = (const u32x4*)h->w2tp_actor.get(); g.w2p_critic = (const u32x4*)h->w2p_critic.get(); g.w2tp_critic = (const u32x4*)h->w2tp_critic.get();
     g.rec = rec; g.w2a_actor = h->w2a_actor; g.w2ta_actor = h->w2ta_actor; g.w2a_critic = h->w2a_critic; g.w2ta_critic = h->w2ta_critic;
     g.adv_stats = adv_stats; g.inline_moments = (h->cfg.normalize_advantage && adv_stats == nullptr) ? 1 : 0; g.invB = 1.0f / (float)(count * world);
     g.clip_range = h->cfg.clip_range; g.ent_coef = h->cfg.ent_coef; g.vf_coef = h->cfg.vf_coef; g.clip_range_vf = h->cfg.clip_range_vf;
@@ -795,11 +795,11 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     }
     CCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     const size_t E = cfg->n_envs, N = (size_t)h->N, P = h->P;
-    CCHK(dmalloc(&h->params, P)); CCHK(dmalloc(&h->adam_m, P)); CCHK(dmalloc(&h->adam_v, P)); CCHK(dmalloc(&h->bt, 4));
-    CCHK(dmalloc(&h->flat, P + 8)); CCHK(dmalloc(&h->norm_out, 1)); CCHK(dmalloc(&h->w2max_dev, 1));
-    { const size_t words = (size_t)gae_chunks(cfg->n_steps) * cfg->n_envs; CCHK(dmalloc(&h->gae_carry, words)); CCHK(hipMemsetAsync(h->gae_carry, 0, words * 8, h->stream));
-      CCHK(dmalloc(&h->gae_err, 1)); CCHK(hipMemsetAsync(h->gae_err, 0, 4, h->stream)); }
-    h->n_norm_partials = (int)((P + 31) / 32); CCHK(dmalloc(&h->norm_partials, h->n_norm_partials));
+    CCHK(h->params.alloc(P)); CCHK(h->adam_m.alloc(P)); CCHK(h->adam_v.alloc(P)); CCHK(h->bt.alloc(4));
+    CCHK(h->flat.alloc(P + 8)); CCHK(h->norm_out.alloc(1)); CCHK(h->w2max_dev.alloc(1));
+    { const size_t words = (size_t)gae_chunks(cfg->n_steps) * cfg->n_envs; CCHK(h->gae_carry.alloc(words)); CCHK(hipMemsetAsync(h->gae_carry, 0, words * 8, h->stream));
+      CCHK(h->gae_err.alloc(1)); CCHK(hipMemsetAsync(h->gae_err, 0, 4, h->stream)); }
+    h->n_norm_partials = (int)((P + 31) / 32); CCHK(h->norm_partials.alloc(h->n_norm_partials));
     if (h->generic) { h->slab_a = generic_slab_size(h->gd, true); h->slab_c = generic_slab_size(h->gd, false); }
     else { h->slab_a = slab_size_actor(*kinfo, hd[0]); h->slab_c = slab_size_critic(*kinfo, hd[0]); }
     h->wide = !h->generic && hd[0] > 64;
@@ -807,37 +807,37 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     if (h->generic) h->Gmax = 64;                                                                                                                                                                                             // generic path: one slab per row chunk of the minibatch
     if (const char* e = debug_env("DRIL_GRAD_GMAX")) { const int g = std::atoi(e); if (g > 0 && g < h->Gmax) h->Gmax = g; }   // diagnostic: fewer workgroups per net
     if (h->wide) { const size_t pb = (size_t)hd[0] * hd[0] * 6;    // three bf16 pieces per element
-        CCHK(hipMalloc(&h->w2p_actor, pb)); CCHK(hipMalloc(&h->w2tp_actor, pb)); CCHK(hipMalloc(&h->w2p_critic, pb)); CCHK(hipMalloc(&h->w2tp_critic, pb));
-        CCHK(hipMalloc(&h->w2pf_actor, pb)); CCHK(hipMalloc(&h->w2pf_critic, pb)); }
-    if (h->wide) { const size_t hh = (size_t)hd[0] * hd[0]; CCHK(dmalloc(&h->w2a_actor, hh)); CCHK(dmalloc(&h->w2ta_actor, hh)); CCHK(dmalloc(&h->w2a_critic, hh)); CCHK(dmalloc(&h->w2ta_critic, hh)); }
-    CCHK(dmalloc(&h->slabs_a, (size_t)h->Gmax * h->slab_a)); CCHK(dmalloc(&h->slabs_c, (size_t)h->Gmax * h->slab_c));
+        CCHK(h->w2p_actor.alloc(pb)); CCHK(h->w2tp_actor.alloc(pb)); CCHK(h->w2p_critic.alloc(pb)); CCHK(h->w2tp_critic.alloc(pb));
+        CCHK(h->w2pf_actor.alloc(pb)); CCHK(h->w2pf_critic.alloc(pb)); }
+    if (h->wide) { const size_t hh = (size_t)hd[0] * hd[0]; CCHK(h->w2a_actor.alloc(hh)); CCHK(h->w2ta_actor.alloc(hh)); CCHK(h->w2a_critic.alloc(hh)); CCHK(h->w2ta_critic.alloc(hh)); }
+    CCHK(h->slabs_a.alloc((size_t)h->Gmax * h->slab_a)); CCHK(h->slabs_c.alloc((size_t)h->Gmax * h->slab_c));
     CCHK(h->env.alloc(h->S));
-    CCHK(dmalloc(&h->obs, N * h->D)); CCHK(hipMalloc(&h->act, N * act_bytes_per(h))); CCHK(dmalloc(&h->rew, N)); CCHK(dmalloc(&h->adv, N));
-    CCHK(dmalloc(&h->ret, N)); CCHK(dmalloc(&h->logp, N)); CCHK(dmalloc(&h->val, N)); CCHK(dmalloc(&h->boot, N)); CCHK(dmalloc(&h->flags, N));
-    CCHK(dmalloc(&h->last_values, E));
-    if (!h->generic) CCHK(dmalloc(&h->rec, (size_t)(h->D <= 4 ? 2 : 3) * N));   // packed minibatch records: 2 (D <= 4) or 3 (D <= 8) float4 per sample
-    if (h->generic) CCHK(dmalloc(&h->gen_tmp, E));
-    if (ext) { CCHK(hipHostMalloc((void**)&h->ext_stage_rew, N * 4)); CCHK(hipHostMalloc((void**)&h->ext_stage_flags, N)); }
+    CCHK(h->obs.alloc(N * h->D)); CCHK(h->act.alloc(N * act_bytes_per(h))); CCHK(h->rew.alloc(N)); CCHK(h->adv.alloc(N));
+    CCHK(h->ret.alloc(N)); CCHK(h->logp.alloc(N)); CCHK(h->val.alloc(N)); CCHK(h->boot.alloc(N)); CCHK(h->flags.alloc(N));
+    CCHK(h->last_values.alloc(E));
+    if (!h->generic) CCHK(h->rec.alloc((size_t)(h->D <= 4 ? 2 : 3) * N));   // packed minibatch records: 2 (D <= 4) or 3 (D <= 8) float4 per sample
+    if (h->generic) CCHK(h->gen_tmp.alloc(E));
+    if (ext) { CCHK(h->ext_stage_rew.alloc(N)); CCHK(h->ext_stage_flags.alloc(N)); }
     if (ext) {
         CCHK(hipEventCreateWithFlags(&h->ext_ev_in, hipEventDisableTiming)); CCHK(hipEventCreateWithFlags(&h->ext_ev_out, hipEventDisableTiming));
-        CCHK(dmalloc(&h->ext_err, 1)); CCHK(hipMemsetAsync(h->ext_err, 0, 4, h->stream)); CCHK(hipHostMalloc((void**)&h->ext_err_host, 4)); *h->ext_err_host = 0;
+        CCHK(h->ext_err.alloc(1)); CCHK(hipMemsetAsync(h->ext_err, 0, 4, h->stream)); CCHK(h->ext_err_host.alloc(1)); *h->ext_err_host = 0;
     }
     if (cfg->monitor_window > 0) {
         const size_t W = cfg->monitor_window;
-        CCHK(dmalloc(&h->mon_cur_ret, E)); CCHK(dmalloc(&h->mon_cur_len, E)); CCHK(dmalloc(&h->ep_ret, N)); CCHK(dmalloc(&h->ep_len, N));
-        CCHK(dmalloc(&h->mon_ring_ret, W)); CCHK(dmalloc(&h->mon_ring_len, W)); CCHK(dmalloc(&h->e_ep_ret, E)); CCHK(dmalloc(&h->e_ep_len, E));
-        CCHK(dmalloc(&h->mon_cnt, (size_t)cfg->n_steps)); CCHK(dmalloc(&h->mon_meta, 2)); CCHK(dmalloc(&h->e_flags, E));
+        CCHK(h->mon_cur_ret.alloc(E)); CCHK(h->mon_cur_len.alloc(E)); CCHK(h->ep_ret.alloc(N)); CCHK(h->ep_len.alloc(N));
+        CCHK(h->mon_ring_ret.alloc(W)); CCHK(h->mon_ring_len.alloc(W)); CCHK(h->e_ep_ret.alloc(E)); CCHK(h->e_ep_len.alloc(E));
+        CCHK(h->mon_cnt.alloc((size_t)cfg->n_steps)); CCHK(h->mon_meta.alloc(2)); CCHK(h->e_flags.alloc(E));
         CCHK(hipMemset(h->mon_cur_ret, 0, E * 4)); CCHK(hipMemset(h->mon_cur_len, 0, E * 4)); CCHK(hipMemset(h->mon_meta, 0, 8));
     }
-    h->adv_blocks = 1024; CCHK(dmalloc(&h->adv_partials, 2 * (size_t)h->adv_blocks)); CCHK(dmalloc(&h->adv_stats, 4));
-    h->ev_blocks = 1024; CCHK(dmalloc(&h->ev_partials, 4 * (size_t)h->ev_blocks));
-    CCHK(dmalloc(&h->stop_flag, 1)); CCHK(dmalloc(&h->nan_flag, 1));
+    h->adv_blocks = 1024; CCHK(h->adv_partials.alloc(2 * (size_t)h->adv_blocks)); CCHK(h->adv_stats.alloc(4));
+    h->ev_blocks = 1024; CCHK(h->ev_partials.alloc(4 * (size_t)h->ev_blocks));
+    CCHK(h->stop_flag.alloc(1)); CCHK(h->nan_flag.alloc(1));
 #ifdef DRIL_STAMPS
-    CCHK(dmalloc(&h->dbg, (size_t)2 * h->Gmax * 4 * 12)); CCHK(hipMemset(h->dbg, 0, (size_t)2 * h->Gmax * 4 * 12 * 8));
+    CCHK(h->dbg.alloc((size_t)2 * h->Gmax * 4 * 12)); CCHK(hipMemset(h->dbg, 0, (size_t)2 * h->Gmax * 4 * 12 * 8));
 #endif
-    CCHK(dmalloc(&h->e_obs, E * h->D)); CCHK(dmalloc(&h->e_rew, E)); CCHK(dmalloc(&h->e_tobs, E * h->D)); CCHK(dmalloc(&h->e_term, E));
-    CCHK(dmalloc(&h->e_trunc, E)); CCHK(hipMalloc(&h->e_act, E * act_bytes_per(h)));
-    CCHK(dmalloc(&h->e_obs_raw, E * h->D)); CCHK(dmalloc(&h->e_rew_n, E)); CCHK(dmalloc(&h->obs_rms, 2)); CCHK(dmalloc(&h->ret_rms, 2)); CCHK(dmalloc(&h->rms_partials, (size_t)h->rms_blocks * 16)); CCHK(dmalloc(&h->rms_red, 16));
+    CCHK(h->e_obs.alloc(E * h->D)); CCHK(h->e_rew.alloc(E)); CCHK(h->e_tobs.alloc(E * h->D)); CCHK(h->e_term.alloc(E));
+    CCHK(h->e_trunc.alloc(E)); CCHK(h->e_act.alloc(E * act_bytes_per(h)));
+    CCHK(h->e_obs_raw.alloc(E * h->D)); CCHK(h->e_rew_n.alloc(E)); CCHK(h->obs_rms.alloc(2)); CCHK(h->ret_rms.alloc(2)); CCHK(h->rms_partials.alloc((size_t)h->rms_blocks * 16)); CCHK(h->rms_red.alloc(16));
     { RmsState init[2]; for (auto& r : init) { for (int d = 0; d < 8; ++d) { r.mean[d] = 0.f; r.var[d] = 1.f; } r.count = 0; }   // RunningMeanStd{T}(shape): zeros, ones, 0 (normalizeWrapperEnv.jl:14-16)
       CCHK(hipMemcpy(h->obs_rms, init, sizeof(init), hipMemcpyHostToDevice)); CCHK(hipMemcpy(h->ret_rms, init, sizeof(init), hipMemcpyHostToDevice)); }
     CCHK(hipMemsetAsync(h->params, 0, P * 4, h->stream)); CCHK(hipMemsetAsync(h->boot, 0, N * 4, h->stream));
@@ -865,17 +865,8 @@ DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
         if (last) { for (int q = 0; q < g->n; ++q) if (g->ready[q]) hipEventDestroy(g->ready[q]); if (g->done) hipEventDestroy(g->done); delete g; }
         h->loop = nullptr;
     }
-    generic_ws_free(h->gws); pn_free(h);
     h->env.release();
-    if (h->ext_stage_rew) (void)hipHostFree(h->ext_stage_rew); if (h->ext_stage_flags) (void)hipHostFree(h->ext_stage_flags);
-    if (h->eval_counter_host) (void)hipHostFree(h->eval_counter_host);
-    if (h->ext_err_host) (void)hipHostFree(h->ext_err_host);
     if (h->ext_ev_in) (void)hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) (void)hipEventDestroy(h->ext_ev_out);
-    void* ptrs[] = {h->ext_err, h->ext_pred_obs, h->ext_pred_act, h->ext_pred_lp, h->eval_snap, h->traj_blob, h->evalf_blob, h->eval_cur_ret, h->eval_cur_len, h->eval_counter, h->eval_events, h->params, h->adam_m, h->adam_v, h->bt, h->flat, h->norm_out, h->norm_partials, h->retry_snap, h->slabs_a, h->slabs_c, h->obs, h->act, h->rew, h->adv, h->ret, h->logp, h->val, h->boot,
-                    h->flags, h->last_values, h->noise_dev, h->perm_dev, h->epoch_index, h->epoch_keys, h->small_xchg, h->w2max_dev, h->gae_carry, h->gae_err, h->w2pf_actor, h->w2pf_critic, h->adv_partials, h->adv_stats, h->ev_partials, h->step_stats,
-                    h->stop_flag, h->nan_flag, h->e_obs, h->e_rew, h->e_tobs, h->e_term, h->e_trunc, h->e_act, h->e_obs_raw, h->e_rew_n, h->obs_rms, h->ret_rms, h->rms_partials, h->rms_red, h->gen_tmp, h->dbg, h->rec, h->epoch_tables, h->epoch_stats, h->w2a_actor, h->w2ta_actor, h->w2a_critic, h->w2ta_critic, h->w2p_actor, h->w2tp_actor, h->w2p_critic, h->w2tp_critic, h->mon_cur_ret, h->ep_ret, h->mon_ring_ret, h->e_ep_ret, h->mon_cur_len, h->ep_len,
-                    h->mon_ring_len, h->e_ep_len, h->mon_cnt, h->mon_meta, h->e_flags};
-    for (void* p : ptrs) if (p) hipFree(p);
     for (auto& p : h->prof_pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& p : h->prof_pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1082,7 +1073,7 @@ DRIL_EXPORT int32_t dril_normalize_enable(dril_handle* h, const dril_normalize_c
     h->pn_rows_cap = 0;
     if (const char* e = debug_env("DRIL_NORM_ROWS")) { const int r = std::atoi(e); if (r > 0) h->pn_rows_cap = r; }   // measurements: fewer rows in the partial table
     hipError_t e = h->pn.alloc((int)D, (size_t)pn_rows((int)E, (int)D, h->pn_rows_cap));
-    if (e == hipSuccess) e = dmalloc(&h->pn_red, Cn);
+    if (e == hipSuccess) e = h->pn_red.alloc(Cn);
     if (e == hipSuccess) e = hipMemset(h->pn_red, 0, Cn * 8);
     if (e == hipSuccess) e = hipMemset(h->env.disc_returns, 0, E * 4);                     // returns, and the cached originals, start at 0
     if (e == hipSuccess) e = hipMemset(h->e_obs_raw, 0, E * D * 4);
@@ -1145,29 +1136,23 @@ namespace {
 int policy_host(dril_handle* h, const float* obs, int64_t B, const void* noise, void* actions, bool actions_in, float* values, float* logp,
                 float* entropy, int mode, int deterministic = 0) {
     if (!obs || B < 1) return fail(h, DRIL_ERR_INVALID_ARG, "policy: null obs or batch < 1");
-    float *d_obs = nullptr, *d_val = nullptr, *d_lp = nullptr, *d_ent = nullptr; void *d_noise = nullptr, *d_act = nullptr;
+    DevBuf<float> d_obs, d_val, d_lp, d_ent; DevBuf<char> d_noise, d_act;                       // freed on every return
     const size_t ab = (size_t)B * act_bytes_per(h), nb = (size_t)B * (h->discrete ? 8 : 4 * (size_t)h->A);
-    int rc = DRIL_OK;
-    auto cleanup = [&]() { hipFree(d_obs); hipFree(d_val); hipFree(d_lp); hipFree(d_ent); hipFree(d_noise); hipFree(d_act); };
-#define PCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return fail(h, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } } while (0)
-    PCHK(dmalloc(&d_obs, (size_t)B * h->D)); PCHK(dmalloc(&d_val, (size_t)B)); PCHK(dmalloc(&d_lp, (size_t)B)); PCHK(dmalloc(&d_ent, (size_t)B));
-    PCHK(hipMalloc(&d_act, ab));
-    PCHK(hipMemcpyAsync(d_obs, obs, (size_t)B * h->D * 4, hipMemcpyHostToDevice, h->stream));
-    if (noise) { PCHK(hipMalloc(&d_noise, nb)); PCHK(hipMemcpyAsync(d_noise, noise, nb, hipMemcpyHostToDevice, h->stream)); }
-    if (actions_in) PCHK(hipMemcpyAsync(d_act, actions, ab, hipMemcpyHostToDevice, h->stream));
-    { int rcw = ensure_wimg(h); if (rcw) { cleanup(); return rcw; } }
+    HIPCHK(h, d_obs.alloc((size_t)B * h->D)); HIPCHK(h, d_val.alloc((size_t)B)); HIPCHK(h, d_lp.alloc((size_t)B)); HIPCHK(h, d_ent.alloc((size_t)B));
+    HIPCHK(h, d_act.alloc(ab));
+    HIPCHK(h, hipMemcpyAsync(d_obs, obs, (size_t)B * h->D * 4, hipMemcpyHostToDevice, h->stream));
+    if (noise) { HIPCHK(h, d_noise.alloc(nb)); HIPCHK(h, hipMemcpyAsync(d_noise, noise, nb, hipMemcpyHostToDevice, h->stream)); }
+    if (actions_in) HIPCHK(h, hipMemcpyAsync(d_act, actions, ab, hipMemcpyHostToDevice, h->stream));
+    { int rcw = ensure_wimg(h); if (rcw) return rcw; }
     PolicyArgs a = policy_args(h, d_obs, B, d_noise, d_act, d_val, d_lp, d_ent, mode);
     a.deterministic = deterministic;
-    PCHK(run_policy(h, a));
+    HIPCHK(h, run_policy(h, a));
     h->policy_calls += 1;
-    if (values) PCHK(hipMemcpyAsync(values, d_val, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    if (logp && mode != 2) PCHK(hipMemcpyAsync(logp, d_lp, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    if (entropy && mode == 1) PCHK(hipMemcpyAsync(entropy, d_ent, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    if (actions && mode == 0) PCHK(hipMemcpyAsync(actions, d_act, ab, hipMemcpyDeviceToHost, h->stream));
-    rc = sync(h);
-#undef PCHK
-    cleanup();
-    return rc;
+    if (values) HIPCHK(h, hipMemcpyAsync(values, d_val, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (logp && mode != 2) HIPCHK(h, hipMemcpyAsync(logp, d_lp, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (entropy && mode == 1) HIPCHK(h, hipMemcpyAsync(entropy, d_ent, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (actions && mode == 0) HIPCHK(h, hipMemcpyAsync(actions, d_act, ab, hipMemcpyDeviceToHost, h->stream));
+    return sync(h);
 }
 }  // namespace
 DRIL_EXPORT int32_t dril_policy_forward(dril_handle* h, const float* obs, int64_t batch, const void* noise, void* actions, float* values, float* logprobs) {
@@ -1377,7 +1362,7 @@ RolloutArgs rollout_args(const dril_handle* h) {
     a.E = h->env.E; a.T = h->cfg.n_steps; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len;
     a.action_start = h->env.action_start; a.log_std_off = h->log_std_off; a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic;
     a.exact_f32 = fwd_exact(h) ? 1 : 0;
-    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = a.exact_f32 ? h->w2a_critic : (const float*)h->w2pf_critic;
+    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor.get(); a.w2a_critic = a.exact_f32 ? h->w2a_critic : (const float*)h->w2pf_critic.get();
     a.mon_cur_ret = h->mon_cur_ret; a.mon_cur_len = h->mon_cur_len; a.ep_ret = h->ep_ret; a.ep_len = h->ep_len;
     return a;
 }
@@ -1508,9 +1493,8 @@ int xn_record(dril_handle* h, size_t k, const float* d_rewards, const uint8_t* d
 }
 // the monitor's arrays of an external handle (those of cfg.monitor_window on a device env, sized by ext_mon_window)
 void xm_free(dril_handle* h) {
-    void* ptrs[] = {h->mon_cur_ret, h->mon_cur_len, h->ep_ret, h->ep_len, h->mon_ring_ret, h->mon_ring_len, h->mon_cnt, h->mon_meta};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->mon_cur_ret = h->ep_ret = h->mon_ring_ret = nullptr; h->mon_cur_len = h->ep_len = h->mon_ring_len = nullptr; h->mon_cnt = h->mon_meta = nullptr;
+    h->mon_cur_ret.release(); h->mon_cur_len.release(); h->ep_ret.release(); h->ep_len.release();
+    h->mon_ring_ret.release(); h->mon_ring_len.release(); h->mon_cnt.release(); h->mon_meta.release();
     h->ext_mon_window = 0;
 }
 int xw_kind_check(dril_handle* h, const char* what) {
@@ -1715,18 +1699,11 @@ DRIL_EXPORT int32_t dril_predict_actions_device(dril_handle* h, const float* d_o
     int rc = ext_check_ptr(h, "dril_predict_actions_device", "d_obs", d_obs, B * h->D * 4); if (rc) return rc;
     if (d_raw_actions) { rc = ext_check_ptr(h, "dril_predict_actions_device", "d_raw_actions", d_raw_actions, B * ab); if (rc) return rc; }
     if (d_env_actions) { rc = ext_check_ptr(h, "dril_predict_actions_device", "d_env_actions", d_env_actions, B * ab); if (rc) return rc; }
-    if (batch > h->ext_pred_cap) {                                                     // grow-only scratch: the head kernel's actions and log-probabilities (hipFree waits for the device)
-        if (h->ext_pred_act) HIPCHK(h, hipFree(h->ext_pred_act)); if (h->ext_pred_lp) HIPCHK(h, hipFree(h->ext_pred_lp));
-        h->ext_pred_act = nullptr; h->ext_pred_lp = nullptr; h->ext_pred_cap = 0;
-        HIPCHK(h, hipMalloc(&h->ext_pred_act, B * ab)); HIPCHK(h, dmalloc(&h->ext_pred_lp, B));
-        h->ext_pred_cap = batch;
-    }
+    HIPCHK(h, h->ext_pred_act.grow(B * ab)); HIPCHK(h, h->ext_pred_lp.grow(B));           // grow-only scratch: the head kernel's actions and log-probabilities (a free waits for the device)
     const bool nz_eval = h->pn.on && h->pn.cfg.norm_obs;                               // evaluation under the wrapper: the statistics in force, never updated
-    if (nz_eval && batch > h->cfg.n_envs && batch > h->ext_pred_obs_cap) {             // (up to n_envs rows fit e_obs; more: grow-only scratch, counted by dril_ext_wrap_info)
-        if (h->ext_pred_obs) HIPCHK(h, hipFree(h->ext_pred_obs));
-        h->ext_pred_obs = nullptr; h->ext_pred_obs_cap = 0;
-        HIPCHK(h, dmalloc(&h->ext_pred_obs, B * h->D));
-        h->ext_pred_obs_cap = batch; h->xw_allocs += 1;
+    if (nz_eval && batch > h->cfg.n_envs) {                                            // (up to n_envs rows fit e_obs; more: grow-only scratch, counted by dril_ext_wrap_info)
+        bool grew; HIPCHK(h, h->ext_pred_obs.grow(B * h->D, &grew));
+        if (grew) h->xw_allocs += 1;
     }
     rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
     if (nz_eval) {
@@ -1830,14 +1807,14 @@ DRIL_EXPORT int32_t dril_ext_monitor_enable(dril_handle* h, int32_t stats_window
     xm_free(h);
     if (stats_window == 0) return DRIL_OK;
     const size_t E = (size_t)h->cfg.n_envs, N = (size_t)h->N, W = (size_t)stats_window;
-    hipError_t e = dmalloc(&h->mon_cur_ret, E);
-    if (e == hipSuccess) e = dmalloc(&h->mon_cur_len, E);
-    if (e == hipSuccess) e = dmalloc(&h->ep_ret, N);
-    if (e == hipSuccess) e = dmalloc(&h->ep_len, N);
-    if (e == hipSuccess) e = dmalloc(&h->mon_ring_ret, W);
-    if (e == hipSuccess) e = dmalloc(&h->mon_ring_len, W);
-    if (e == hipSuccess) e = dmalloc(&h->mon_cnt, (size_t)h->cfg.n_steps);
-    if (e == hipSuccess) e = dmalloc(&h->mon_meta, 2);
+    hipError_t e = h->mon_cur_ret.alloc(E);
+    if (e == hipSuccess) e = h->mon_cur_len.alloc(E);
+    if (e == hipSuccess) e = h->ep_ret.alloc(N);
+    if (e == hipSuccess) e = h->ep_len.alloc(N);
+    if (e == hipSuccess) e = h->mon_ring_ret.alloc(W);
+    if (e == hipSuccess) e = h->mon_ring_len.alloc(W);
+    if (e == hipSuccess) e = h->mon_cnt.alloc((size_t)h->cfg.n_steps);
+    if (e == hipSuccess) e = h->mon_meta.alloc(2);
     if (e == hipSuccess) e = hipMemset(h->mon_cur_ret, 0, E * 4);                      // fresh sums, an empty window
     if (e == hipSuccess) e = hipMemset(h->mon_cur_len, 0, E * 4);
     if (e == hipSuccess) e = hipMemset(h->mon_meta, 0, 8);
@@ -1869,7 +1846,7 @@ DRIL_EXPORT int32_t dril_debug_set_noise(dril_handle* h, const void* noise, size
     const size_t need = (size_t)h->N * (h->discrete ? 1 : (size_t)h->A);
     if (count != need) return fail(h, DRIL_ERR_INVALID_ARG, "dril_debug_set_noise: count must be n_envs*n_steps (*action_dim)");
     const size_t bytes = need * (h->discrete ? 8 : 4);
-    if (!h->noise_dev) HIPCHK(h, hipMalloc(&h->noise_dev, bytes));
+    if (!h->noise_dev) HIPCHK(h, h->noise_dev.alloc(bytes));
     HIPCHK(h, hipMemcpyAsync(h->noise_dev, noise, bytes, hipMemcpyHostToDevice, h->stream));
     h->noise_set = true;
     return sync(h);
@@ -1897,22 +1874,18 @@ DRIL_EXPORT int32_t dril_gae(int32_t E, int32_t T, float gamma, float lam, const
     if (E < 1 || T < 1 || !rewards || !values || !flags || !bootstrap || !last_values || !advantages || !returns)
         return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_gae: bad argument");
     const size_t N = (size_t)E * T;
-    float *d_r = nullptr, *d_v = nullptr, *d_b = nullptr, *d_l = nullptr, *d_a = nullptr, *d_ret = nullptr; uint8_t* d_f = nullptr; unsigned long long* d_c = nullptr; int* d_e = nullptr;
-    auto cleanup = [&]() { hipFree(d_r); hipFree(d_v); hipFree(d_b); hipFree(d_l); hipFree(d_a); hipFree(d_ret); hipFree(d_f); hipFree(d_c); hipFree(d_e); };
-#define GCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return fail(nullptr, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } } while (0)
-    GCHK(dmalloc(&d_r, N)); GCHK(dmalloc(&d_v, N)); GCHK(dmalloc(&d_b, N)); GCHK(dmalloc(&d_l, (size_t)E)); GCHK(dmalloc(&d_a, N)); GCHK(dmalloc(&d_ret, N)); GCHK(dmalloc(&d_f, N));
-    GCHK(hipMemcpy(d_r, rewards, N * 4, hipMemcpyHostToDevice)); GCHK(hipMemcpy(d_v, values, N * 4, hipMemcpyHostToDevice));
-    GCHK(hipMemcpy(d_b, bootstrap, N * 4, hipMemcpyHostToDevice)); GCHK(hipMemcpy(d_l, last_values, (size_t)E * 4, hipMemcpyHostToDevice));
-    GCHK(hipMemcpy(d_f, flags, N, hipMemcpyHostToDevice));
+    DevBuf<float> d_r, d_v, d_b, d_l, d_a, d_ret; DevBuf<uint8_t> d_f; DevBuf<unsigned long long> d_c; DevBuf<int> d_e;
+    HIPCHK(nullptr, d_r.alloc(N)); HIPCHK(nullptr, d_v.alloc(N)); HIPCHK(nullptr, d_b.alloc(N)); HIPCHK(nullptr, d_l.alloc((size_t)E)); HIPCHK(nullptr, d_a.alloc(N)); HIPCHK(nullptr, d_ret.alloc(N)); HIPCHK(nullptr, d_f.alloc(N));
+    HIPCHK(nullptr, hipMemcpy(d_r, rewards, N * 4, hipMemcpyHostToDevice)); HIPCHK(nullptr, hipMemcpy(d_v, values, N * 4, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_b, bootstrap, N * 4, hipMemcpyHostToDevice)); HIPCHK(nullptr, hipMemcpy(d_l, last_values, (size_t)E * 4, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_f, flags, N, hipMemcpyHostToDevice));
     const size_t words = (size_t)gae_chunks(T) * E; int gave_up = 0;
-    GCHK(dmalloc(&d_c, words)); GCHK(hipMemset(d_c, 0, words * 8)); GCHK(dmalloc(&d_e, 1)); GCHK(hipMemset(d_e, 0, 4));
-    GCHK(launch_gae(E, T, gamma, lam, d_r, d_v, d_f, d_b, d_l, d_a, d_ret, d_c, 1u, d_e, nullptr));
-    GCHK(hipDeviceSynchronize());
-    GCHK(hipMemcpy(&gave_up, d_e, 4, hipMemcpyDeviceToHost));
-    if (gave_up) { cleanup(); return fail(nullptr, DRIL_ERR_HIP, "gae_scan_kernel: a chunk's predecessor did not publish its carry within the spin limit"); }
-    GCHK(hipMemcpy(advantages, d_a, N * 4, hipMemcpyDeviceToHost)); GCHK(hipMemcpy(returns, d_ret, N * 4, hipMemcpyDeviceToHost));
-#undef GCHK
-    cleanup();
+    HIPCHK(nullptr, d_c.alloc(words)); HIPCHK(nullptr, hipMemset(d_c, 0, words * 8)); HIPCHK(nullptr, d_e.alloc(1)); HIPCHK(nullptr, hipMemset(d_e, 0, 4));
+    HIPCHK(nullptr, launch_gae(E, T, gamma, lam, d_r, d_v, d_f, d_b, d_l, d_a, d_ret, d_c, 1u, d_e, nullptr));
+    HIPCHK(nullptr, hipDeviceSynchronize());
+    HIPCHK(nullptr, hipMemcpy(&gave_up, d_e, 4, hipMemcpyDeviceToHost));
+    if (gave_up) return fail(nullptr, DRIL_ERR_HIP, "gae_scan_kernel: a chunk's predecessor did not publish its carry within the spin limit");
+    HIPCHK(nullptr, hipMemcpy(advantages, d_a, N * 4, hipMemcpyDeviceToHost)); HIPCHK(nullptr, hipMemcpy(returns, d_ret, N * 4, hipMemcpyDeviceToHost));
     return DRIL_OK;
 }
 
@@ -1923,7 +1896,7 @@ DRIL_EXPORT int32_t dril_debug_set_permutation(dril_handle* h, const int64_t* pe
     const size_t need = (size_t)h->cfg.epochs * (size_t)h->N;
     if (count != need) return fail(h, DRIL_ERR_INVALID_ARG, "dril_debug_set_permutation: count must be epochs * n_envs * n_steps");
     for (size_t i = 0; i < count; ++i) if (perm[i] < 0 || perm[i] >= h->N) return fail(h, DRIL_ERR_INVALID_ARG, "dril_debug_set_permutation: index out of range");
-    if (!h->perm_dev) HIPCHK(h, dmalloc(&h->perm_dev, need));
+    if (!h->perm_dev) HIPCHK(h, h->perm_dev.alloc(need));
     HIPCHK(h, hipMemcpyAsync(h->perm_dev, perm, need * 8, hipMemcpyHostToDevice, h->stream));
     h->perm_count = need;
     return sync(h);
@@ -1955,10 +1928,7 @@ bool small_persistent_applies(const dril_handle* h, const UpdatePlan& p) {
 int update_begin(dril_handle* h, const UpdatePlan& p) {
     const int64_t total_steps = p.total_steps;
     h->used_f16 = false; h->spin_timeout = false;
-    if (total_steps > h->step_stats_cap) {
-        if (h->step_stats) hipFree(h->step_stats);
-        h->step_stats = nullptr; HIPCHK(h, dmalloc(&h->step_stats, (size_t)total_steps * 16)); h->step_stats_cap = (int)total_steps;
-    }
+    if (total_steps > 0) HIPCHK(h, h->step_stats.grow((size_t)total_steps * 16));
     if (total_steps > 0) HIPCHK(h, hipMemsetAsync(h->step_stats, 0, (size_t)total_steps * 16 * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(h->stop_flag, 0, 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->nan_flag, 0, 4, h->stream));
     if (h->rec) { prof_begin(h, DRIL_K_PACK_RECORDS); HIPCHK(h, launch_pack_records(h->cfg.env_kind, p.N, h->obs, h->act, h->adv, h->logp, h->ret, h->rec, h->stream)); prof_end(h); }
@@ -1967,10 +1937,7 @@ int update_begin(dril_handle* h, const UpdatePlan& p) {
 // the persistent kernel's argument block (step0 / nsteps / step_parity / xchg are the launch's: the caller sets them); keys[epochs] goes to the device on the handle's
 // stream and must stay alive until that copy has run
 int small_update_args(dril_handle* h, const UpdatePlan& p, uint64_t* keys, SmallUpdateArgs& u) {
-    if (h->cfg.epochs > h->epoch_keys_cap) {
-        if (h->epoch_keys) hipFree(h->epoch_keys);
-        h->epoch_keys = nullptr; HIPCHK(h, dmalloc(&h->epoch_keys, (size_t)h->cfg.epochs)); h->epoch_keys_cap = h->cfg.epochs;
-    }
+    if (h->cfg.epochs > 0) HIPCHK(h, h->epoch_keys.grow((size_t)h->cfg.epochs));
     for (int ep = 0; ep < h->cfg.epochs; ++ep) keys[ep] = perm_key(h->cfg.seed + (uint64_t)h->cfg.rank, h->update_counter, ep);
     HIPCHK(h, hipMemcpyAsync(h->epoch_keys, keys, (size_t)h->cfg.epochs * 8, hipMemcpyHostToDevice, h->stream));
     u = SmallUpdateArgs{};
@@ -2006,7 +1973,7 @@ int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
         SmallUpdateArgs u{};
         { int rca = small_update_args(h, plan, keys.data(), u); if (rca) return rca; }
         HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (keys is a stack-lifetime host buffer)
-        if (!h->small_xchg) HIPCHK(h, dmalloc(&h->small_xchg, (size_t)kSmallXchgWords));
+        if (!h->small_xchg) HIPCHK(h, h->small_xchg.alloc((size_t)kSmallXchgWords));
         u.xchg = h->small_xchg; u.debug_solo = std::getenv("DRIL_SMALL_DEBUG_SOLO") != nullptr;
         for (int64_t s0 = 0; s0 < total_steps; s0 += h->small_chunk) {
             small_update_chunk(plan, h->small_chunk, s0, u);
@@ -2039,18 +2006,13 @@ int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
         // keyed bijection per lane, wave, net and tile)
         const bool index_array = !perm && !h->generic && !h->no_epoch_index && N < (1ll << 31) && (B + kTile - 1) / kTile >= kPairTilesPerCu * (int64_t)h->num_cus;
         if (index_array) {
-            if (!h->epoch_index) HIPCHK(h, dmalloc(&h->epoch_index, (size_t)N));
+            if (!h->epoch_index) HIPCHK(h, h->epoch_index.alloc((size_t)N));
             prof_begin(h, DRIL_K_ADV_MOMENTS);
             HIPCHK(h, launch_epoch_index(N, key, bits, h->epoch_index, h->stream));
             prof_end(h);
         }
         if (epoch_moments) {
-            if (nb > h->epoch_nb_cap) {
-                if (h->epoch_tables) hipFree(h->epoch_tables); if (h->epoch_stats) hipFree(h->epoch_stats);
-                h->epoch_tables = nullptr; h->epoch_stats = nullptr;
-                HIPCHK(h, dmalloc(&h->epoch_tables, (size_t)h->epoch_blocks * 2 * nb)); HIPCHK(h, dmalloc(&h->epoch_stats, (size_t)3 * nb));
-                h->epoch_nb_cap = (int)nb;
-            }
+            if (nb > 0) { HIPCHK(h, h->epoch_tables.grow((size_t)h->epoch_blocks * 2 * nb)); HIPCHK(h, h->epoch_stats.grow((size_t)3 * nb)); }
             prof_begin(h, DRIL_K_ADV_MOMENTS);
             const int eb = (int)std::min<int64_t>(h->epoch_blocks, std::max<int64_t>(64, N / 8192));       // eight waves per SIMD at chip-filling sizes: the pass is one dependent chain per sample
             HIPCHK(h, launch_epoch_moments(h->adv, N, B, (int)nb, key, bits, h->epoch_tables, eb, h->epoch_stats, h->stop_flag, h->stream));
@@ -2179,7 +2141,7 @@ int update_snapshot(dril_handle* h, UpdateTry& t) {
     t.may_retry = update_may_retry(h); t.adam_steps0 = h->adam_steps; t.counter0 = h->update_counter;
     const size_t P = (size_t)h->P;
     if (t.may_retry) {
-        if (!h->retry_snap) HIPCHK(h, dmalloc(&h->retry_snap, 3 * P + 4));
+        if (!h->retry_snap) HIPCHK(h, h->retry_snap.alloc(3 * P + 4));
         HIPCHK(h, hipMemcpyAsync(h->retry_snap, h->params, P * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->retry_snap + P, h->adam_m, P * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->retry_snap + 2 * P, h->adam_v, P * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -2242,23 +2204,19 @@ DRIL_EXPORT int32_t dril_ppo_loss_grad(dril_handle* h, const float* obs, const v
     if (!obs || !actions || !advantages || !returns || !old_logprobs || !old_values || batch < 1) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ppo_loss_grad: bad argument");
     if (h->cfg.world_size > 1) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ppo_loss_grad is a single-rank parity entry point");
     const size_t B = (size_t)batch;
-    float *d_obs = nullptr, *d_adv = nullptr, *d_ret = nullptr, *d_lp = nullptr, *d_val = nullptr; void* d_act = nullptr; float4* d_rec = nullptr;
-    auto cleanup = [&]() { hipFree(d_obs); hipFree(d_adv); hipFree(d_ret); hipFree(d_lp); hipFree(d_val); hipFree(d_act); hipFree(d_rec); };
-#define LCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return fail(h, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } } while (0)
-    LCHK(dmalloc(&d_obs, B * h->D)); LCHK(dmalloc(&d_adv, B)); LCHK(dmalloc(&d_ret, B)); LCHK(dmalloc(&d_lp, B)); LCHK(dmalloc(&d_val, B)); LCHK(hipMalloc(&d_act, B * act_bytes_per(h)));
-    LCHK(hipMemcpyAsync(d_obs, obs, B * h->D * 4, hipMemcpyHostToDevice, h->stream)); LCHK(hipMemcpyAsync(d_adv, advantages, B * 4, hipMemcpyHostToDevice, h->stream));
-    LCHK(hipMemcpyAsync(d_ret, returns, B * 4, hipMemcpyHostToDevice, h->stream)); LCHK(hipMemcpyAsync(d_lp, old_logprobs, B * 4, hipMemcpyHostToDevice, h->stream));
-    LCHK(hipMemcpyAsync(d_val, old_values, B * 4, hipMemcpyHostToDevice, h->stream)); LCHK(hipMemcpyAsync(d_act, actions, B * act_bytes_per(h), hipMemcpyHostToDevice, h->stream));
-    LCHK(hipMemsetAsync(h->stop_flag, 0, 4, h->stream));
+    DevBuf<float> d_obs, d_adv, d_ret, d_lp, d_val; DevBuf<char> d_act; DevBuf<float4> d_rec;     // freed on every return
+    HIPCHK(h, d_obs.alloc(B * h->D)); HIPCHK(h, d_adv.alloc(B)); HIPCHK(h, d_ret.alloc(B)); HIPCHK(h, d_lp.alloc(B)); HIPCHK(h, d_val.alloc(B)); HIPCHK(h, d_act.alloc(B * act_bytes_per(h)));
+    HIPCHK(h, hipMemcpyAsync(d_obs, obs, B * h->D * 4, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipMemcpyAsync(d_adv, advantages, B * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_ret, returns, B * 4, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipMemcpyAsync(d_lp, old_logprobs, B * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_val, old_values, B * 4, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipMemcpyAsync(d_act, actions, B * act_bytes_per(h), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->stop_flag, 0, 4, h->stream));
     // the same packed records dril_ppo_update builds, so that this parity entry point runs the kernel the size rule picks for `batch` in production
     // (the pair / wide split kernels read records only)
-    if (h->rec) { LCHK(dmalloc(&d_rec, (size_t)(h->D <= 4 ? 2 : 3) * B)); LCHK(launch_pack_records(h->cfg.env_kind, batch, d_obs, d_act, d_adv, d_lp, d_ret, d_rec, h->stream)); }
-#undef LCHK
+    if (h->rec) { HIPCHK(h, d_rec.alloc((size_t)(h->D <= 4 ? 2 : 3) * B)); HIPCHK(h, launch_pack_records(h->cfg.env_kind, batch, d_obs, d_act, d_adv, d_lp, d_ret, d_rec, h->stream)); }
     int rc = ppo_step(h, d_obs, d_act, d_adv, d_ret, d_lp, d_val, nullptr, 0, batch, batch, 0, /*bits=0: identity order*/ 0, nullptr, false, d_rec);
     std::vector<float> flat((size_t)h->P + 8);
     if (!rc) { hipError_t e = hipMemcpyAsync(flat.data(), h->flat, flat.size() * 4, hipMemcpyDeviceToHost, h->stream); if (e != hipSuccess) rc = fail(h, DRIL_ERR_HIP, hipGetErrorString(e)); }
     if (!rc) rc = sync(h);
-    cleanup();
     if (rc) return rc;
     const float* s = flat.data() + h->P; const float n = s[6];
     const float pl = s[0] / n, ent = s[1] / n, vl = s[5] / n;
@@ -2303,7 +2261,7 @@ DRIL_EXPORT int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval, int32_t 
     int rc = ensure_wimg(h); if (rc) return rc;
     if (h->env.module && h->pn.on) {                                                 // a plug-in env under dril_normalize_enable: the statistics in force, frozen; nothing of the wrapper moves
         const size_t ED = (size_t)E * h->D;
-        float* keep = nullptr; HIPCHK(h, dmalloc(&keep, ED + 2 * (size_t)E));    // returns | old_rewards | old_obs
+        DevBuf<float> keep; HIPCHK(h, keep.alloc(ED + 2 * (size_t)E));    // returns | old_rewards | old_obs
         const int training = h->pn.cfg.training;
         hipError_t e = hipMemcpyAsync(keep, h->env.disc_returns, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(keep + E, h->e_rew, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
@@ -2317,7 +2275,7 @@ DRIL_EXPORT int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval, int32_t 
             if (e == hipSuccess) e = hipMemcpyAsync(h->e_obs_raw, keep + 2 * (size_t)E, ED * 4, hipMemcpyDeviceToDevice, h->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         }
-        (void)hipFree(keep);
+        keep.release();
         if (rc) return rc;
         HIPCHK(h, e);
         return DRIL_OK;
@@ -2411,7 +2369,7 @@ void eval_kernel_args(const dril_handle* h, EvalKernelArgs& g, int deterministic
     a.params = h->params; a.state = h->env.state; a.step_count = h->env.step_count; a.episode = h->env.episode; a.gstep = h->env.gstep;
     a.E = h->cfg.n_envs; a.episode_len = h->env.episode_len; a.fixed_len = h->env.fixed_len; a.action_start = h->env.action_start; a.log_std_off = h->log_std_off;
     a.env_seed0 = h->env.seed0; a.actor = h->actor; a.critic = h->critic; a.exact_f32 = fwd_exact(h) ? 1 : 0;
-    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor; a.w2a_critic = nullptr;
+    a.w2a_actor = a.exact_f32 ? h->w2a_actor : (const float*)h->w2pf_actor.get(); a.w2a_critic = nullptr;
     g.deterministic = deterministic ? 1 : 0;
 }
 // the frozen NormalizeWrapperEnv as evaluate_modes_kernel takes it: the halves of the statistics in force, read only.  raw: the accounting counts raw rewards
@@ -2432,7 +2390,7 @@ int eval_fused_args(dril_handle* h, DrilEnvEvaluateArgs& g, int deterministic, i
     auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_obs = take(E * D * 4), o_act = take(E * W * 4), o_rew = take(Ks * E * 4), o_flg = take(Ks * E);
     const size_t o_obs0 = take(Ms * D * 4), o_ract = take(Ks * Ms * W * 4), o_robs = take(Ks * Ms * D * 4);
-    if (off > h->evalf_blob_bytes) { if (h->evalf_blob) (void)hipFree(h->evalf_blob); h->evalf_blob = nullptr; h->evalf_blob_bytes = 0; HIPCHK(h, dmalloc(&h->evalf_blob, off)); h->evalf_blob_bytes = off; }
+    if (off > 0) HIPCHK(h, h->evalf_blob.grow(off));
     char* b = h->evalf_blob;
     g = DrilEnvEvaluateArgs{};
     g.r.env = h->env.args(); g.r.env.obs = (float*)(b + o_obs);                       // (after the call's seed is in force: seed0 is the one the reset used)
@@ -2445,11 +2403,10 @@ int eval_fused_args(dril_handle* h, DrilEnvEvaluateArgs& g, int deterministic, i
     if (M > 0) { g.shadow = shadow->args(); g.rec_obs0 = (float*)(b + o_obs0); g.rec_act = b + o_ract; g.rec_obs = (float*)(b + o_robs); }
     return DRIL_OK;
 }
-template <typename T> int eval_ensure(dril_handle* h, T** p, size_t n) { if (!*p) HIPCHK(h, dmalloc(p, n)); return DRIL_OK; }
 // what one evaluation sets aside: device arrays in a list (copied to / from one blob), the host-side words next to them
 struct EvalKeep {
     std::vector<std::pair<void*, size_t>> arrays;
-    uint64_t seed0; bool ready; int obs_par, ret_par, norm_training, pn_training; float* mon_cur_ret; int64_t gws_launches;
+    uint64_t seed0; bool ready; int obs_par, ret_par, norm_training, pn_training; DevBuf<float> mon_cur_ret; int64_t gws_launches;
 };
 void eval_keep_list(dril_handle* h, bool persistent, EvalKeep& k) {
     const size_t E = (size_t)h->cfg.n_envs, ED = E * h->D * 4;
@@ -2472,10 +2429,10 @@ int eval_keep_copy(dril_handle* h, const EvalKeep& k, bool save) {
 int eval_buffers(dril_handle* h, const EvalKeep& k, long long cap) {
     const size_t E = (size_t)h->cfg.n_envs;
     size_t bytes = 0; for (const auto& a : k.arrays) bytes += (a.second + 15) & ~(size_t)15;
-    if (bytes > h->eval_snap_bytes) { if (h->eval_snap) (void)hipFree(h->eval_snap); h->eval_snap = nullptr; h->eval_snap_bytes = 0; HIPCHK(h, dmalloc(&h->eval_snap, bytes)); h->eval_snap_bytes = bytes; }
-    { int rc = eval_ensure(h, &h->eval_cur_ret, E); if (rc) return rc; } { int rc = eval_ensure(h, &h->eval_cur_len, E); if (rc) return rc; } { int rc = eval_ensure(h, &h->eval_counter, 1); if (rc) return rc; }
-    if (!h->eval_counter_host) HIPCHK(h, hipHostMalloc((void**)&h->eval_counter_host, sizeof(unsigned int), hipHostMallocDefault));
-    if (cap > h->eval_events_cap) { if (h->eval_events) (void)hipFree(h->eval_events); h->eval_events = nullptr; h->eval_events_cap = 0; HIPCHK(h, dmalloc(&h->eval_events, (size_t)cap)); h->eval_events_cap = cap; }
+    if (bytes > 0) HIPCHK(h, h->eval_snap.grow(bytes));
+    if (!h->eval_cur_ret) HIPCHK(h, h->eval_cur_ret.alloc(E)); if (!h->eval_cur_len) HIPCHK(h, h->eval_cur_len.alloc(E)); if (!h->eval_counter) HIPCHK(h, h->eval_counter.alloc(1));
+    if (!h->eval_counter_host) HIPCHK(h, h->eval_counter_host.alloc(1));
+    if (cap > 0) HIPCHK(h, h->eval_events.grow((size_t)cap));
     return DRIL_OK;
 }
 // The pieces of one step-granular env step that the evaluation (eval_step_granular) and the recording (traj_step) share; what differs sits between them.
@@ -2533,10 +2490,10 @@ int eval_prepare(dril_handle* h, const dril_eval_options* o, EvalPlan& pl) {
 // set-aside: the evaluation runs on the handle's own envs — what training would continue from is kept here and put back by eval_put_back, on every path
 int eval_set_aside(dril_handle* h, EvalKeep& keep) {
     keep.seed0 = h->env.seed0; keep.ready = h->env.ready; keep.obs_par = h->obs_par; keep.ret_par = h->ret_par; keep.norm_training = h->cfg.norm_training;
-    keep.pn_training = h->pn.cfg.training; keep.mon_cur_ret = h->mon_cur_ret; keep.gws_launches = h->gws.launches;
+    keep.pn_training = h->pn.cfg.training; keep.gws_launches = h->gws.launches;
     { int rc = eval_keep_copy(h, keep, true); if (rc) return rc; }
     h->cfg.norm_training = 0; h->pn.cfg.training = 0;                                  // set_training(env, false): the statistics in force, frozen; `returns` stands still
-    h->mon_cur_ret = nullptr;                                                          // evaluation episodes do not enter the training env's MonitorWrapperEnv: its launches are not made
+    keep.mon_cur_ret = std::move(h->mon_cur_ret);                                      // evaluation episodes do not enter the training env's MonitorWrapperEnv: its launches are not made
     return DRIL_OK;
 }
 // open the episode, for both verbs: the call's seed (env e of rank r: seed + r E + e), reset!(env) (evaluation.jl:87 / trajectory_utils.jl:10), the counter zeroed — the
@@ -2567,13 +2524,13 @@ void eval_persistent_args(const dril_handle* h, const dril_eval_options* o, int 
     eval_kernel_args(h, g, o->deterministic); g.r.T = K; g.acct = acct;           // (after the seed of eval_reset: env_seed0 is the one the reset used)
 }
 // put-back: the host-side words, and the copies home enqueued (the caller drains the stream)
-int eval_put_back(dril_handle* h, const EvalKeep& keep) {
+int eval_put_back(dril_handle* h, EvalKeep& keep) {
     h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_par = keep.obs_par; h->ret_par = keep.ret_par; h->cfg.norm_training = keep.norm_training;
-    h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = keep.mon_cur_ret; h->gws.launches = keep.gws_launches;
+    h->pn.cfg.training = keep.pn_training; h->mon_cur_ret = std::move(keep.mon_cur_ret); h->gws.launches = keep.gws_launches;
     return eval_keep_copy(h, keep, false);
 }
 // the end of either verb, after eval_set_aside: the state is put back and the stream drained whatever the run returned (rc), and the run's error is the one reported
-int eval_finish(dril_handle* h, const EvalKeep& keep, const char* verb, int rc) {
+int eval_finish(dril_handle* h, EvalKeep& keep, const char* verb, int rc) {
     const std::string msg = h->err;
     int rr = eval_put_back(h, keep);
     if (rr == DRIL_OK) { const hipError_t e = hipStreamSynchronize(h->stream); if (e != hipSuccess) rr = fail(h, DRIL_ERR_HIP, std::string(verb) + ": " + hipGetErrorString(e)); }
@@ -2673,7 +2630,7 @@ int traj_prepare(dril_handle* h, const dril_traj_options* o, int32_t Tcap, TrajR
     if (h->env.module) { if (!h->discrete) h->env.agent_action_space(clamp_low.data(), clamp_high.data()); }
     else if (ki->box) { clamp_low[0] = ki->act_lo; clamp_high[0] = ki->act_hi; }
     const TrajLayout L = traj_layout((size_t)o->n_trajectories, (size_t)h->D, W, (size_t)h->S, (size_t)Tcap);
-    HIPCHK(h, traj_setup(h->env, h->stream, &h->traj_blob, &h->traj_blob_bytes, h->eval_counter, L, boxes, o->final_original != 0, /*drain_before_free=*/false, r));
+    HIPCHK(h, traj_setup(h->env, h->stream, h->traj_blob, h->eval_counter, L, boxes, o->final_original != 0, /*drain_before_free=*/false, r));
     return DRIL_OK;
 }
 // one env step, enqueued: the launches of eval_step_granular, and over the M recorded envs only a state copy, the shadow step, the shadow observe and the recording
@@ -2804,14 +2761,14 @@ DRIL_EXPORT int32_t dril_train(dril_handle* h, int64_t max_steps, dril_ppo_stats
 struct dril_population {
     std::vector<dril_handle*> members; std::vector<hipStream_t> own_streams;
     hipStream_t stream = nullptr; int device = 0, cap = 1; int64_t chunk = 16384, total_steps = 0; int n_chunks = 1;
-    RolloutArgs *h_rargs = nullptr, *d_rargs = nullptr; SmallUpdateArgs *h_uargs = nullptr, *d_uargs = nullptr;   // pinned / device: [n] and [n_chunks][n]
-    unsigned long long* xchg = nullptr;                          // n x kSmallXchgWords
-    std::vector<char*> home_blocks; std::vector<UpdateHome> homes;   // one pinned block per member: where its update's results land
+    PinnedBuf<RolloutArgs> h_rargs; DevBuf<RolloutArgs> d_rargs; PinnedBuf<SmallUpdateArgs> h_uargs; DevBuf<SmallUpdateArgs> d_uargs;   // pinned / device: [n] and [n_chunks][n]
+    DevBuf<unsigned long long> xchg;                             // n x kSmallXchgWords
+    std::vector<PinnedBuf<char>> home_blocks; std::vector<UpdateHome> homes;   // one pinned block per member: where its update's results land
     std::vector<int> failed;                                     // status of a member that failed in the current call (it sits out the rest of the iteration)
     struct dril_population_info info{};
-    EvalKernelArgs *h_eargs = nullptr, *d_eargs = nullptr;       // dril_population_evaluate_device: pinned / device [n]
-    unsigned int *eval_counters = nullptr, *h_eval_counters = nullptr;   // device / pinned [n]: member m's EvalAcct.counter is word m, looked at with ONE copy per K env steps
-    SacEvalEvent* h_eval_events = nullptr; size_t h_eval_events_cap = 0;   // pinned, grow-only: where the members' event lists land
+    PinnedBuf<EvalKernelArgs> h_eargs; DevBuf<EvalKernelArgs> d_eargs; // dril_population_evaluate_device: pinned / device [n]
+    DevBuf<unsigned int> eval_counters; PinnedBuf<unsigned int> h_eval_counters;   // device / pinned [n]: member m's EvalAcct.counter is word m, looked at with ONE copy per K env steps
+    PinnedBuf<SacEvalEvent> h_eval_events;   // pinned, grow-only: where the members' event lists land
     double eval_ms = 0;                                          // HIP-event time of the evaluate_pop_kernel launches of the last evaluation
     struct Ev { int kind; hipEvent_t a, b; }; std::vector<Ev> ev_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     std::string err;
@@ -2848,11 +2805,6 @@ void pop_release(dril_population* p) {
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (size_t m = 0; m < p->members.size(); ++m) { dril_handle* h = p->members[m]; if (h->pop == p) { h->stream = p->own_streams[m]; h->pop = nullptr; } }
-    for (char* b : p->home_blocks) if (b) (void)hipHostFree(b);
-    if (p->h_rargs) (void)hipHostFree(p->h_rargs); if (p->h_uargs) (void)hipHostFree(p->h_uargs);
-    if (p->d_rargs) (void)hipFree(p->d_rargs); if (p->d_uargs) (void)hipFree(p->d_uargs); if (p->xchg) (void)hipFree(p->xchg);
-    if (p->h_eargs) (void)hipHostFree(p->h_eargs); if (p->h_eval_counters) (void)hipHostFree(p->h_eval_counters); if (p->h_eval_events) (void)hipHostFree(p->h_eval_events);
-    if (p->d_eargs) (void)hipFree(p->d_eargs); if (p->eval_counters) (void)hipFree(p->eval_counters);
     for (auto& e : p->ev_pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
     for (auto& e : p->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -3056,11 +3008,7 @@ int pop_evaluate(dril_population* p, const dril_eval_options* o, dril_eval_stats
     // the event lists home (one pinned area for all members), then every member's state put back; ONE drain
     size_t total = 0;
     for (Run& r : batched) { r.ev_off = total; r.ev_n = p->failed[r.m] ? 0 : (size_t)std::min<long long>(r.seen, r.pl.cap); total += r.ev_n; }
-    if (total > p->h_eval_events_cap) {
-        if (p->h_eval_events) (void)hipHostFree(p->h_eval_events);
-        p->h_eval_events = nullptr; p->h_eval_events_cap = 0;
-        if (hipHostMalloc((void**)&p->h_eval_events, total * sizeof(SacEvalEvent), hipHostMallocDefault) == hipSuccess) p->h_eval_events_cap = total;
-    }
+    if (total > 0) (void)p->h_eval_events.grow(total);                                 // (a failure leaves it empty: the copies below report it)
     for (Run& r : batched) {
         dril_handle* h = p->members[r.m];
         const std::string msg = h->err;
@@ -3119,20 +3067,20 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
     p->n_chunks = (int)((p->total_steps + p->chunk - 1) / p->chunk);
 #define JCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { const std::string msg = std::string("dril_population_join: " #expr ": ") + hipGetErrorString(_e); pop_release(p); return fail(nullptr, DRIL_ERR_HIP, msg); } } while (0)
     JCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    JCHK(hipHostMalloc((void**)&p->h_rargs, sizeof(RolloutArgs) * (size_t)n, hipHostMallocDefault));
-    JCHK(hipHostMalloc((void**)&p->h_uargs, sizeof(SmallUpdateArgs) * ((size_t)p->n_chunks + 1) * n, hipHostMallocDefault));   // the launch table, and behind it one block per member
-    JCHK(hipMalloc((void**)&p->d_rargs, sizeof(RolloutArgs) * (size_t)n));
-    JCHK(hipMalloc((void**)&p->d_uargs, sizeof(SmallUpdateArgs) * (size_t)p->n_chunks * n));
-    JCHK(dmalloc(&p->xchg, (size_t)n * kSmallXchgWords));
-    JCHK(hipHostMalloc((void**)&p->h_eargs, sizeof(EvalKernelArgs) * (size_t)n, hipHostMallocDefault));
-    JCHK(hipMalloc((void**)&p->d_eargs, sizeof(EvalKernelArgs) * (size_t)n));
-    JCHK(hipHostMalloc((void**)&p->h_eval_counters, sizeof(unsigned int) * (size_t)n, hipHostMallocDefault));
-    JCHK(dmalloc(&p->eval_counters, (size_t)n));
-    p->home_blocks.assign((size_t)n, nullptr); p->homes.assign((size_t)n, UpdateHome{}); p->failed.assign((size_t)n, DRIL_OK);
+    JCHK(p->h_rargs.alloc((size_t)n));
+    JCHK(p->h_uargs.alloc(((size_t)p->n_chunks + 1) * n));   // the launch table, and behind it one block per member
+    JCHK(p->d_rargs.alloc((size_t)n));
+    JCHK(p->d_uargs.alloc((size_t)p->n_chunks * n));
+    JCHK(p->xchg.alloc((size_t)n * kSmallXchgWords));
+    JCHK(p->h_eargs.alloc((size_t)n));
+    JCHK(p->d_eargs.alloc((size_t)n));
+    JCHK(p->h_eval_counters.alloc((size_t)n));
+    JCHK(p->eval_counters.alloc((size_t)n));
+    p->home_blocks.resize((size_t)n); p->homes.assign((size_t)n, UpdateHome{}); p->failed.assign((size_t)n, DRIL_OK);
     for (int m = 0; m < n; ++m) {
         const dril_handle* h = members[m];
         const size_t st = ((size_t)p->total_steps * 16 * 4 + 15) & ~(size_t)15, ev = 4 * (size_t)h->ev_blocks * 8, keys = (size_t)h->cfg.epochs * 8;
-        JCHK(hipHostMalloc((void**)&p->home_blocks[m], st + ev + keys + 16, hipHostMallocDefault));
+        JCHK(p->home_blocks[m].alloc(st + ev + keys + 16));
         char* b = p->home_blocks[m];
         p->homes[m] = UpdateHome{(float*)b, (double*)(b + st), (int*)(b + st + ev + keys), (uint64_t*)(b + st + ev)};
     }
@@ -3225,6 +3173,7 @@ DRIL_EXPORT int32_t dril_comm_init(dril_handle* h, const uint8_t id[128]) {
     return DRIL_OK;
 }
 
+DRIL_EXPORT int64_t dril_debug_device_bytes_live(void) { return g_devmem_live_bytes.load(); }
 DRIL_EXPORT int32_t dril_debug_comm_loopback(dril_handle** hs, int32_t n) {
     if (!hs || n < 1 || n > kLoopMax) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_debug_comm_loopback: 1..8 handles");
     std::vector<bool> seen((size_t)n, false);

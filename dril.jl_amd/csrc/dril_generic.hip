@@ -22,13 +22,8 @@ GemmArgs gargs() { GemmArgs g = gemm_args(); g.allow_split = 1; return g; }
 constexpr int kMaxOut = 64;
 
 hipError_t ws_reserve(GenericWs& ws, size_t floats) {
-    if (floats <= ws.cap) return hipSuccess;
-    if (ws.p) { hipError_t e = hipFree(ws.p); ws.p = nullptr; ws.cap = 0; if (e != hipSuccess) return e; }   // hipFree drains the device first
-    const size_t want = floats + floats / 4;
-    hipError_t e = hipMalloc((void**)&ws.p, want * sizeof(float));
-    if (e != hipSuccess) return e;
-    ws.cap = want;
-    return hipSuccess;
+    if (floats <= ws.p.size()) return hipSuccess;
+    return ws.p.alloc(floats + floats / 4);                                   // (the free of the smaller one drains the device first)
 }
 struct Carver { float* p; size_t used = 0; float* take(size_t n) { float* r = p + used; used += (n + 3) & ~(size_t)3; return r; } };   // 16-byte aligned pieces
 
@@ -296,7 +291,6 @@ hipError_t generic_select(int64_t n, const uint8_t* where, const float* src, flo
     return hipGetLastError();
 }
 
-void generic_ws_free(GenericWs& ws) { if (ws.p) (void)hipFree(ws.p); ws.p = nullptr; ws.cap = 0; }
 
 int generic_net_size(const GenericDims& d, int out) { return net_lay(d, 0, out).end; }
 int generic_slab_size(const GenericDims& d, bool actor) {

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "dril_device.h"
+#include "dril_devmem.h"         // DevBuf: GenericWs owns its workspace
 #include "dril_eval_account.h"   // EvalAcct, eval_account: the episode accounting of an evaluation on the device
 #include "dril_traj_record.h"    // TrajRec, TrajMaps, traj_record_env: the per-env recording of collect_trajectory (evaluate_modes_kernel's recording mode)
 #include "dril_ext_record.h"     // xr_*: the per-env scalar rules of ext_norm_record_kernel (dril_ext_norm.h), host-compilable
@@ -207,12 +208,11 @@ constexpr int kMaxHidden = 4;
 // dim(l) -> dim(l + 1) with dim(0) = D, dim(l) = H[l-1], dim(nh + 1) = out
 struct GenericDims { int D, A, nh, H[kMaxHidden], discrete, act; };
 int generic_net_size(const GenericDims& d, int out);   // parameters of one net {W_1 b_1 ... W_{nh+1} b_{nh+1}}
-struct GenericWs { float* p = nullptr; size_t cap = 0; int64_t launches = 0; };   // grow-only device workspace (floats), owned by the handle; launches: launch calls generic_policy has enqueued (dril_rollout_fused_info)
+struct GenericWs { DevBuf<float> p; int64_t launches = 0; };   // grow-only device workspace (floats), owned by the handle; launches: launch calls generic_policy has enqueued (dril_rollout_fused_info)
 hipError_t generic_policy(const GenericDims& d, const PolicyArgs& a, GenericWs& ws, hipStream_t s);
 hipError_t generic_ppo_grad(const GenericDims& d, const GradArgs& a, GenericWs& ws, hipStream_t s);
 int generic_slab_size(const GenericDims& d, bool actor);
 int generic_pick_slabs(const GenericDims& d, int64_t count, int Gmax);   // slabs (row chunks) for a minibatch of `count` rows; < 1: does not fit
-void generic_ws_free(GenericWs& ws);
 hipError_t generic_select(int64_t n, const uint8_t* where, const float* src, float* dst, hipStream_t s);   // dst[i] = src[i] where where[i] != 0
 
 // device-array verbs of DRIL_ENV_EXTERNAL (dril_ext_device.hip).  ExtBounds: the ClampAdapter's table, one (low, high) per action dimension; low >= high = not clamped

@@ -19,6 +19,7 @@
 
 #include "../../include/dril_hip.h"              // dril_normalize_config (the one configuration type in here), the DRIL_ERR_* codes
 #include "../../include/device/dril_normalize.h" // normalize_obs: the one definition, shared with the evaluation kernel of a device env plug-in
+#include "dril_devmem.h"                         // DevBuf: the wrapper owns its statistics and its table
 
 namespace {
 
@@ -184,22 +185,20 @@ inline NormErr norm_set_stats_check(const float* obs_mean, const float* obs_var,
 
 struct NormWrap {
     bool on = false; dril_normalize_config cfg{}; int D = 0, cur = 0; int64_t obs_count = 0, ret_count = 0;
-    float* stats = nullptr; double* partials = nullptr;
+    dril::DevBuf<float> stats; dril::DevBuf<double> partials;
 
     float* half(int i) const { return stats + (size_t)i * (2 * D + 2); }
     size_t stats_floats() const { return 2 * (size_t)D + 2; }
     void release() {
-        if (stats) hipFree(stats); if (partials) hipFree(partials);
-        stats = nullptr; partials = nullptr; on = false; cur = 0; obs_count = ret_count = 0;
+        stats.release(); partials.release(); on = false; cur = 0; obs_count = ret_count = 0;
     }
     // a fresh wrapper over observations of width D_: RunningMeanStd() — mean 0, var 1, count 0 (:12-16) — in both halves, a zeroed table of `rows` rows.  `on` is the caller's
     // to set once its own arrays stand too
     hipError_t alloc(int D_, size_t rows) {
         release(); D = D_;
         const size_t C = stats_floats();
-        hipError_t e = hipMalloc((void**)&stats, 2 * C * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&partials, rows * C * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(partials, 0, rows * C * sizeof(double));
+        hipError_t e = stats.alloc(2 * C);
+        if (e == hipSuccess) e = partials.alloc_zero(rows * C);
         if (e == hipSuccess) {
             std::vector<float> st(2 * C, 0.f);
             for (size_t hf = 0; hf < 2; ++hf) { for (int d = 0; d < D; ++d) st[hf * C + D + d] = 1.0f; st[hf * C + 2 * D + 1] = 1.0f; }

@@ -1338,52 +1338,53 @@ struct dril_sac_handle {
     int Pd = 0, Pqd = 0, log_std_off = 0;            // DEVICE layout: every net starts on a 16-byte boundary (float4 operand loads); pads stay zero
     NetOff actor{}, q0{};                            // device offsets
     hipStream_t stream = nullptr;
-    float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *target = nullptr, *g_critic = nullptr, *g_actor = nullptr;
-    SacScalars* sc = nullptr; float* stats = nullptr; float* stats_out = nullptr; int stats_cap = 0;
-    double* ssq_rows = nullptr;   // [stats_cap][adam_blocks_c + end_blocks] squared-gradient partials per update, summed on the host (grad_norm statistic)
-    unsigned int* counter = nullptr; int adam_blocks_c = 0, end_blocks = 0;
-    SacScalars* sc_next = nullptr;   // ping-pong partner of `sc` (fused heads: the entropy step writes the new state here, then the two are swapped)
-    double* head_partials = nullptr; unsigned int* head_counter = nullptr; unsigned* col_h1p = nullptr; unsigned* col_w2p = nullptr; int* col_flags = nullptr; int col_tag = 0, col_w2tag = 0; bool col_w2_dirty = true, f16_fwd = true, l2_attr_set = false;   // the f16-piece collection forward (sac_collect_l2_kernel)
-    unsigned long long* it_stamps = nullptr; int it_stamps_cap = 0; double wall_hz = 1e8; bool fused_heads = true; bool fused_dw1 = false; int fl_c = 0, fl_a = 0; bool fused_collect = true; bool fused_fwd = true; bool trace_enqueue = false; std::vector<hipEvent_t> it_events; int iter_chunk = 64;   // fused output-layer + head kernels (DRIL_SAC_NO_FUSED_HEADS=1: the round-1 launch sequence, A/B)
+    DevBuf<float> params, adam_m, adam_v, g_critic, g_actor;
+    float* target = nullptr;                         // alias: the target critics inside params
+    DevBuf<SacScalars> sc; DevBuf<float> stats; DevBuf<float> stats_out;
+    DevBuf<double> ssq_rows;   // [updates stats_out holds][adam_blocks_c + end_blocks] squared-gradient partials per update, summed on the host (grad_norm statistic)
+    DevBuf<unsigned int> counter; int adam_blocks_c = 0, end_blocks = 0;
+    DevBuf<SacScalars> sc_next;   // ping-pong partner of `sc` (fused heads: the entropy step writes the new state here, then the two are swapped)
+    DevBuf<double> head_partials; DevBuf<unsigned int> head_counter; DevBuf<unsigned> col_h1p; DevBuf<unsigned> col_w2p; DevBuf<int> col_flags; int col_tag = 0, col_w2tag = 0; bool col_w2_dirty = true, f16_fwd = true, l2_attr_set = false;   // the f16-piece collection forward (sac_collect_l2_kernel)
+    DevBuf<unsigned long long> it_stamps; double wall_hz = 1e8; bool fused_heads = true; bool fused_dw1 = false; int fl_c = 0, fl_a = 0; bool fused_collect = true; bool fused_fwd = true; bool trace_enqueue = false; std::vector<hipEvent_t> it_events; int iter_chunk = 64;   // fused output-layer + head kernels (DRIL_SAC_NO_FUSED_HEADS=1: the round-1 launch sequence, A/B)
     int upd_route[3] = {-1, 0, 0}; mutable char upd_info[160] = {0};   // what the last sac_one_update enqueued: {first layers in the gather, PRE head, launched yet} (dril_sac_update_info)
     float bt_actor[2], bt_critic[2], bt_ent[2]; int64_t grad_updates = 0; uint64_t update_counter = 0, aux_counter = 0;
     float target_entropy = 0, act_lo = -2.0f, act_hi = 2.0f; bool external = false;   // bounds of the agent-facing action space: Box(-2,2), Box(-1,1) under ScalingWrapperEnv
-    float* act_bounds = nullptr;                     // device table [low[kMaxA] | high[kMaxA]] the sampling kernels read: the pair above in every entry, or a plug-in's bounds per dimension
+    DevBuf<float> act_bounds;                     // device table [low[kMaxA] | high[kMaxA]] the sampling kernels read: the pair above in every entry, or a plug-in's bounds per dimension
     // env: the envs on the device — simulator state and counters, the seed, and for DRIL_ENV_MODULE the loaded plug-in (dril_env_side.h; SAC has no DiscreteAdapter and
     // no fixed-length episodes: action_start 0, fixed_len 0)
     DeviceEnvs env; bool fused_head_push = true;
-    float *obs_cur = nullptr, *obs_nxt = nullptr, *e_rew = nullptr, *e_tobs = nullptr, *e_raw = nullptr, *e_envact = nullptr; uint8_t *e_term = nullptr, *e_trunc = nullptr;
+    DevBuf<float> obs_cur, obs_nxt, e_rew, e_tobs, e_raw, e_envact; DevBuf<uint8_t> e_term, e_trunc;
     bool obs_valid = false;
     // replay ring
     long long cap = 0, size = 0, head = 0;
-    float *rb_obs = nullptr, *rb_next = nullptr, *rb_act = nullptr, *rb_rew = nullptr; uint8_t *rb_term = nullptr, *rb_trunc = nullptr;
+    DevBuf<float> rb_obs, rb_next, rb_act, rb_rew; DevBuf<uint8_t> rb_term, rb_trunc;
     // batch + activations
-    float *xa = nullptr, *ah1 = nullptr, *ah2 = nullptr, *mu = nullptr;               // actor: [nmax][D], [nmax][H], [nmax][A]
-    float *xq = nullptr, *xq_next = nullptr, *xq_pi = nullptr;                       // [B][D+A]
-    float *qh1 = nullptr, *qh2 = nullptr, *th1 = nullptr, *th2 = nullptr;            // [2][nq][H]
-    float *q_cur = nullptr, *q_next = nullptr, *q_pi = nullptr, *dq = nullptr;       // [2][nq]
-    float *dz2 = nullptr, *dz1 = nullptr, *dxq = nullptr, *dmu = nullptr;            // [2][nq][H], [2][nq][D+A], [B][A]
-    float *b_rew = nullptr, *b_ne = nullptr, *b_nn = nullptr, *b_np = nullptr, *b_nlp = nullptr, *a_pi = nullptr, *g_pi = nullptr, *lp_pi = nullptr; uint8_t* b_term = nullptr;
+    DevBuf<float> xa, ah1, ah2, mu;               // actor: [nmax][D], [nmax][H], [nmax][A]
+    DevBuf<float> xq, xq_pi; float* xq_next = nullptr;                 // [B][D+A]; xq_next: alias (second half of xq)
+    DevBuf<float> qh1, qh2; float *th1 = nullptr, *th2 = nullptr;      // [2][nq][H]; th1 / th2: aliases (z = 2,3 of qh1 / qh2)
+    DevBuf<float> q_cur, q_pi, dq; float* q_next = nullptr; // [2][nq]; q_next: alias (second half of q_cur)
+    DevBuf<float> dz2, dz1, dxq, dmu;            // [2][nq][H], [2][nq][D+A], [B][A]
+    DevBuf<float> b_rew, b_ne, b_nn, b_np, b_nlp, a_pi, g_pi, lp_pi; DevBuf<uint8_t> b_term;
     int nq = 0;
     // MonitorWrapperEnv (dril_sac_monitor_enable; mon_window == 0: off, every pointer null): running sums per env, the ring of the last mon_window finished episodes
     // with meta = {count, head}, and the finished-episode block [mon_rows_cap][E] of the collection in flight (mon_row: its next row)
-    int mon_window = 0, mon_rows_cap = 0, mon_row = 0; float *mon_cur_ret = nullptr, *mon_ring_ret = nullptr, *mon_ep_ret = nullptr; int32_t *mon_cur_len = nullptr, *mon_ring_len = nullptr, *mon_ep_len = nullptr;
-    int* mon_meta = nullptr; uint8_t* mon_flags = nullptr;
+    int mon_window = 0, mon_rows_cap = 0, mon_row = 0; DevBuf<float> mon_cur_ret, mon_ring_ret, mon_ep_ret; DevBuf<int32_t> mon_cur_len, mon_ring_len, mon_ep_len;
+    DevBuf<int> mon_meta; DevBuf<uint8_t> mon_flags;
     // evaluate_agent (dril_sac_evaluate_agent): the env-side snapshot, the per-env running sums, the event list and its counter (pinned host word for the poll)
-    int eval_poll = 0; float *ev_state = nullptr, *ev_obs = nullptr, *ev_mon_ret = nullptr, *ev_cur_ret = nullptr; int32_t *ev_sc = nullptr, *ev_mon_len = nullptr, *ev_cur_len = nullptr; uint32_t *ev_ep = nullptr, *ev_gs = nullptr;
-    unsigned int *ev_counter = nullptr, *ev_counter_host = nullptr; SacEvalEvent* ev_events = nullptr; long long ev_events_cap = 0;
+    int eval_poll = 0; DevBuf<float> ev_state, ev_obs, ev_mon_ret, ev_cur_ret; DevBuf<int32_t> ev_sc, ev_mon_len, ev_cur_len; DevBuf<uint32_t> ev_ep, ev_gs;
+    DevBuf<unsigned int> ev_counter; PinnedBuf<unsigned int> ev_counter_host; DevBuf<SacEvalEvent> ev_events;
     // dril_sac_collect_trajectory: ONE grow-only blob for the step-major recording, the shadow envs' arrays (plug-ins) and the table of bounds (the counter and its pinned word are the evaluation's)
-    char* traj_blob = nullptr; size_t traj_blob_bytes = 0;
+    DevBuf<char> traj_blob;
     // NormalizeWrapperEnv (dril_sac_normalize_enable; nz.on false: every pointer null; kernels: dril_norm_wrap.h, dril_sac_norm.h).  nz_old_obs (E x D) is the raw
     // observation of the envs' present state once nz_raw_valid
     NormWrap nz; bool nz_raw_valid = false;
-    float *nz_returns = nullptr, *nz_old_obs = nullptr, *nz_old_rew = nullptr;
+    DevBuf<float> nz_returns, nz_old_obs, nz_old_rew;
     // device-array verbs of an external handle (dril_sac_ext_*_device, dril_sac_update_enqueue, dril_sac_flush): the two hand-over events, the sticky error word and
     // its pinned host copy, the pending statistics table (DRIL_SAC_PENDING_CAPACITY rows, allocated at create) + its squared-gradient partials, what a flush has to free, and the counters of the info struct
-    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; int* ext_err = nullptr; int* ext_err_host = nullptr;
+    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; DevBuf<int> ext_err; PinnedBuf<int> ext_err_host;
     bool ext_acted = false, ext_bounds_set = false, in_device_verb = false;
     int64_t fwd_launches = 0;                        // kernels enqueued through gemm / gemm_pair / the elementwise first layer since create: what `launches` of the info struct is counted from
-    float* pend_stats = nullptr; double* pend_ssq = nullptr; int pend_n = 0; std::vector<void*> pend_free;
+    DevBuf<float> pend_stats; DevBuf<double> pend_ssq; int pend_n = 0; struct InjectedBatches { DevBuf<long long> idx; DevBuf<float> ne, nn, np; }; std::vector<InjectedBatches> pend_free;
     int64_t ext_steps_dev = 0, ext_steps_host = 0, ext_syncs = 0, ext_flushes = 0, ext_launches = 0;
     // NormalizeWrapperEnv / MonitorWrapperEnv on an external handle (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable) live in nz / nz_* / mon_* above, which
     // the built-in verbs never touch on such a handle.  xw_begin: the next act opens a collection (dril_sac_ext_collection_begin); xw_live: one is in progress (cleared
@@ -1394,10 +1395,10 @@ struct dril_sac_handle {
     // sync-free verbs) and re-used after every flush; calls made while it is full are not timed
     std::vector<hipEvent_t> xp_events; size_t xp_n = 0, xp_pairs = 0;
     // injected inputs (tests)
-    float* collect_noise = nullptr; size_t collect_noise_count = 0;
-    int inj_updates = 0; long long* inj_idx = nullptr; float *inj_ne = nullptr, *inj_nn = nullptr, *inj_np = nullptr;
+    DevBuf<float> collect_noise; size_t collect_noise_count = 0;
+    int inj_updates = 0; DevBuf<long long> inj_idx; DevBuf<float> inj_ne, inj_nn, inj_np;
     // host-batch scratch
-    float *s_in = nullptr, *s_act = nullptr, *s_noise = nullptr, *s_out = nullptr, *s_out2 = nullptr;
+    DevBuf<float> s_in, s_act, s_noise, s_out, s_out2;
     // timing
     hipEvent_t ev_a = nullptr, ev_b = nullptr; double collect_ms = 0, update_ms = 0; int64_t collect_steps = 0, updates = 0;
     std::string err;
@@ -1413,11 +1414,6 @@ int sfail(dril_sac_handle* h, int code, const std::string& msg) { if (h) h->err 
 #define SDO(expr) do { int _rc = (expr); if (_rc != DRIL_OK) return _rc; } while (0)
 #define S_NOT_EXTERNAL(h, what) do { if ((h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, what ": the envs of DRIL_ENV_EXTERNAL live on the host (dril_sac_predict_actions + dril_sac_ext_push)"); } while (0)
 
-template <typename T> hipError_t smalloc(T** p, size_t n) {
-    hipError_t e = hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
-    if (e == hipSuccess) e = hipMemset(*p, 0, (n ? n : 1) * sizeof(T));
-    return e;
-}
 int round4(int x) { return (x + 3) & ~3; }
 int gemm_pair(dril_sac_handle* h, GemmArgs a, int Za, GemmArgs b, int Zb) {
     SHIP(h, launch_gemm_pair(a, Za, b, Zb, h->stream)); h->fwd_launches += 1;
@@ -1633,10 +1629,9 @@ int monitor_begin(dril_sac_handle* h, int n_steps) {
     h->mon_row = 0;
     if (n_steps <= h->mon_rows_cap) return DRIL_OK;
     SDO(ssync(h));                                                                                 // (the previous collection's window launch reads the old rows)
-    if (h->mon_ep_ret) hipFree(h->mon_ep_ret); if (h->mon_ep_len) hipFree(h->mon_ep_len); if (h->mon_flags) hipFree(h->mon_flags);
-    h->mon_ep_ret = nullptr; h->mon_ep_len = nullptr; h->mon_flags = nullptr; h->mon_rows_cap = 0;
+    h->mon_rows_cap = 0;
     const size_t n = (size_t)n_steps * h->cfg.n_envs;
-    SHIP(h, smalloc(&h->mon_ep_ret, n)); SHIP(h, smalloc(&h->mon_ep_len, n)); SHIP(h, smalloc(&h->mon_flags, n)); h->mon_rows_cap = n_steps;
+    SHIP(h, h->mon_ep_ret.alloc_zero(n)); SHIP(h, h->mon_ep_len.alloc_zero(n)); SHIP(h, h->mon_flags.alloc_zero(n)); h->mon_rows_cap = n_steps;
     return DRIL_OK;
 }
 // after its last step: the finished episodes of the whole collection into the window, one launch (sac_monitor_window_kernel)
@@ -1710,9 +1705,16 @@ CollectEnvArgs env_kernel_args(dril_sac_handle* h, const CollectHeadArgs& ca, co
 // ---- NormalizeWrapperEnv in a collection (kernels: dril_sac_norm.h) -----------------------------------------------------------------------------------------
 void normalize_free(dril_sac_handle* h) {
     h->nz.release();
-    void* ptrs[] = {h->nz_returns, h->nz_old_obs, h->nz_old_rew};
-    for (void* p : ptrs) if (p) hipFree(p);
-    h->nz_returns = h->nz_old_obs = h->nz_old_rew = nullptr; h->nz_raw_valid = false;
+    h->nz_returns.release(); h->nz_old_obs.release(); h->nz_old_rew.release(); h->nz_raw_valid = false;
+}
+// a fresh wrapper with a table of `rows` rows, and the handle's arrays next to it, zeroed: returns and the cached originals start at 0
+hipError_t normalize_alloc(dril_sac_handle* h, size_t rows) {
+    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
+    hipError_t e = h->nz.alloc((int)D, rows);
+    if (e == hipSuccess) e = h->nz_returns.alloc_zero(E);
+    if (e == hipSuccess) e = h->nz_old_obs.alloc_zero(E * D);
+    if (e == hipSuccess) e = h->nz_old_rew.alloc_zero(E);
+    return e;
 }
 // the raw observation of the envs' present state in nz_old_obs (reset! :110-121 stores it; so does every observe)
 int nz_ensure_raw(dril_sac_handle* h) {
@@ -1819,15 +1821,12 @@ int collect(dril_sac_handle* h, int n_steps, int use_random, double* fps, bool c
     if (h->cfg.profile_events) { float ms = 0; if (hipEventElapsedTime(&ms, h->ev_a, h->ev_b) == hipSuccess) { h->collect_ms += ms; h->collect_steps += n_steps; } }
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (fps) *fps = (double)n_steps * h->cfg.n_envs / (dt > 0 ? dt : 1e-9);                      // :126-128
-    if (h->collect_noise) { hipFree(h->collect_noise); h->collect_noise = nullptr; h->collect_noise_count = 0; }
+    h->collect_noise.release(); h->collect_noise_count = 0;
     return DRIL_OK;
 }
 int ensure_stats(dril_sac_handle* h, int n) {
-    if (n <= h->stats_cap) return DRIL_OK;
-    if (h->stats_out) hipFree(h->stats_out);
-    if (h->ssq_rows) hipFree(h->ssq_rows);
-    h->stats_out = nullptr; h->ssq_rows = nullptr;
-    SHIP(h, smalloc(&h->stats_out, (size_t)n * 8)); SHIP(h, smalloc(&h->ssq_rows, (size_t)n * (h->adam_blocks_c + h->end_blocks))); h->stats_cap = n;
+    if (n <= 0) return DRIL_OK;
+    SHIP(h, h->stats_out.grow_zero((size_t)n * 8)); SHIP(h, h->ssq_rows.grow_zero((size_t)n * (h->adam_blocks_c + h->end_blocks)));
     return DRIL_OK;
 }
 void fill_stats(const dril_sac_handle* h, const float* rows, int n, dril_sac_stats* out) {
@@ -1878,7 +1877,7 @@ int run_iterations(dril_sac_handle* h, int count, int tf, int n_upd, dril_sac_st
     const bool timed = h->cfg.profile_events || fps;
     const int n_st = 1 + 2 * count;                                                        // [loop start | per iteration: collection end, update end] (phase_stamp)
     if (timed) {
-        if (n_st > h->it_stamps_cap) { if (h->it_stamps) hipFree(h->it_stamps); h->it_stamps = nullptr; SHIP(h, smalloc(&h->it_stamps, (size_t)n_st)); h->it_stamps_cap = n_st; }
+        SHIP(h, h->it_stamps.grow_zero((size_t)n_st));
         SHIP(h, hipMemsetAsync(h->it_stamps, 0, sizeof(unsigned long long) * n_st, h->stream));
         hipLaunchKernelGGL(sac_stamp_kernel, dim3(1), dim3(64), 0, h->stream, h->it_stamps);
     }
@@ -1909,8 +1908,7 @@ int run_iterations(dril_sac_handle* h, int count, int tf, int n_upd, dril_sac_st
     return DRIL_OK;
 }
 void clear_injected(dril_sac_handle* h) {
-    if (h->inj_idx) hipFree(h->inj_idx); if (h->inj_ne) hipFree(h->inj_ne); if (h->inj_nn) hipFree(h->inj_nn); if (h->inj_np) hipFree(h->inj_np);
-    h->inj_idx = nullptr; h->inj_ne = h->inj_nn = h->inj_np = nullptr; h->inj_updates = 0;
+    h->inj_idx.release(); h->inj_ne.release(); h->inj_nn.release(); h->inj_np.release(); h->inj_updates = 0;
 }
 void reset_optimizer(dril_sac_handle* h) {
     h->bt_actor[0] = h->bt_critic[0] = h->bt_ent[0] = h->cfg.adam_beta1; h->bt_actor[1] = h->bt_critic[1] = h->bt_ent[1] = h->cfg.adam_beta2;
@@ -1956,26 +1954,9 @@ DRIL_EXPORT int32_t dril_sac_destroy(dril_sac_handle* h) {
     if (!h) return DRIL_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    void* ptrs[] = {h->params, h->adam_m, h->adam_v, h->g_critic, h->g_actor, h->sc, h->sc_next, h->stats, h->stats_out, h->ssq_rows, h->counter, h->head_partials, h->head_counter,
-                    h->obs_cur, h->obs_nxt, h->e_rew, h->e_tobs, h->e_raw, h->e_envact, h->e_term, h->e_trunc,
-                    h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, h->xa, h->ah1, h->ah2, h->mu, h->xq, h->xq_pi,
-                    h->qh1, h->qh2, h->q_cur, h->q_pi, h->dq, h->dz2, h->dz1, h->dxq, h->dmu, h->b_rew, h->b_ne, h->b_nn, h->b_np,
-                    h->b_nlp, h->a_pi, h->g_pi, h->lp_pi, h->b_term, h->collect_noise, h->act_bounds, h->inj_idx, h->inj_ne, h->inj_nn, h->inj_np, h->s_in, h->s_act, h->s_noise, h->s_out, h->s_out2};
-    for (void* p : ptrs) if (p) hipFree(p);
     if (h->ev_a) hipEventDestroy(h->ev_a); if (h->ev_b) hipEventDestroy(h->ev_b);
     for (hipEvent_t e : h->it_events) hipEventDestroy(e);
     for (hipEvent_t e : h->xp_events) hipEventDestroy(e);
-    if (h->it_stamps) hipFree(h->it_stamps);
-    if (h->col_h1p) hipFree(h->col_h1p); if (h->col_w2p) hipFree(h->col_w2p); if (h->col_flags) hipFree(h->col_flags);
-    void* mon_eval[] = {h->mon_cur_ret, h->mon_cur_len, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->mon_ep_ret, h->mon_ep_len, h->mon_flags,
-                        h->ev_state, h->ev_obs, h->ev_mon_ret, h->ev_cur_ret, h->ev_sc, h->ev_mon_len, h->ev_cur_len, h->ev_ep, h->ev_gs, h->ev_counter, h->ev_events};
-    for (void* p : mon_eval) if (p) hipFree(p);
-    normalize_free(h);
-    if (h->ev_counter_host) hipHostFree(h->ev_counter_host);
-    if (h->traj_blob) hipFree(h->traj_blob);
-    for (void* p : h->pend_free) hipFree(p);
-    if (h->pend_stats) hipFree(h->pend_stats); if (h->pend_ssq) hipFree(h->pend_ssq); if (h->ext_err) hipFree(h->ext_err);
-    if (h->ext_err_host) hipHostFree(h->ext_err_host);
     if (h->ext_ev_in) hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) hipEventDestroy(h->ext_ev_out);
     if (h->stream) hipStreamDestroy(h->stream);
     h->env.release();
@@ -2088,20 +2069,20 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     {   // the bounds table of the sampling kernels
         float tb[2 * kMaxA];
         for (int a = 0; a < kMaxA; ++a) { const bool own = is_module && a < A; tb[a] = own ? desc.action_low[a] : h->act_lo; tb[kMaxA + a] = own ? desc.action_high[a] : h->act_hi; }
-        CHK(smalloc(&h->act_bounds, 2 * kMaxA)); CHK(hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
+        CHK(h->act_bounds.alloc_zero(2 * kMaxA)); CHK(hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
     }
     if (is_module) {
         h->fused_head_push = std::getenv("DRIL_SAC_NO_FUSED_HEAD_PUSH") == nullptr;           // A/B switch, latched here: head + plug-in step + push as three launches per env step
     }
-    CHK(smalloc(&h->params, h->Pd)); CHK(smalloc(&h->adam_m, h->Pd)); CHK(smalloc(&h->adam_v, h->Pd));
+    CHK(h->params.alloc_zero(h->Pd)); CHK(h->adam_m.alloc_zero(h->Pd)); CHK(h->adam_v.alloc_zero(h->Pd));
     h->target = h->params + h->q0.w1 + 2 * h->Pqd;   // the targets sit right behind the critics so that one launch runs all four Q nets (blockIdx.z stride Pqd)
-    CHK(smalloc(&h->g_critic, h->Pd)); CHK(smalloc(&h->g_actor, h->Pd)); CHK(smalloc(&h->sc, 1)); CHK(smalloc(&h->sc_next, 1)); CHK(smalloc(&h->stats, 8));
+    CHK(h->g_critic.alloc_zero(h->Pd)); CHK(h->g_actor.alloc_zero(h->Pd)); CHK(h->sc.alloc_zero(1)); CHK(h->sc_next.alloc_zero(1)); CHK(h->stats.alloc_zero(8));
     h->adam_blocks_c = std::min(kSacAdamBlocks, (2 * h->Pqd + 255) / 256); h->end_blocks = std::min(kSacAdamBlocks, ((h->actor.end + 3) / 4 + 2 * h->Pqd / 4 + 255) / 256);   // elementwise optimiser kernels: up to 1 024 blocks (no grid-wide fold is left in them; 256 -> 1 024: update! 0.174 -> 0.168 ms)
     // narrow first layers: their gradient, step and (critics) re-evaluation inside the optimiser kernels (first_layer_opt_block; DRIL_SAC_NO_FUSED_DW1=1: launches of their own)
     h->fused_dw1 = std::getenv("DRIL_SAC_NO_FUSED_HEADS") == nullptr && std::getenv("DRIL_SAC_NO_FUSED_DW1") == nullptr && W <= kOptL1MaxIn && H1 % 4 == 0 && B <= kOptL1MaxB;
     if (h->fused_dw1) { h->fl_a = (H1 + kOptL1Units - 1) / kOptL1Units; h->fl_c = 2 * h->fl_a; h->adam_blocks_c += h->fl_c; h->end_blocks += h->fl_a; }
-    CHK(smalloc(&h->counter, 1));
-    CHK(smalloc(&h->head_partials, (size_t)(2 * kMaxA + 8) * ((B + kHeadSamplesPerBlock - 1) / kHeadSamplesPerBlock + 1))); CHK(smalloc(&h->head_counter, kMaxA + 1));   // doubles: [critic 2 | actor 2 | log_std kMaxA | entropy 2] x blocks
+    CHK(h->counter.alloc_zero(1));
+    CHK(h->head_partials.alloc_zero((size_t)(2 * kMaxA + 8) * ((B + kHeadSamplesPerBlock - 1) / kHeadSamplesPerBlock + 1))); CHK(h->head_counter.alloc_zero(kMaxA + 1));   // doubles: [critic 2 | actor 2 | log_std kMaxA | entropy 2] x blocks
     h->fused_heads = std::getenv("DRIL_SAC_NO_FUSED_HEADS") == nullptr; h->fused_collect = std::getenv("DRIL_SAC_NO_FUSED_COLLECT") == nullptr; h->fused_fwd = std::getenv("DRIL_SAC_NO_FUSED_FWD") == nullptr; h->f16_fwd = std::getenv("DRIL_SAC_NO_F16_FWD") == nullptr; h->trace_enqueue = false;   // latched here: no getenv on the update path
     // evaluate_agent: env steps enqueued between two looks of the host at the event counter.  A look is one 4-byte copy and a stream drain (measured: 9 - 10 us per look on
     // built-in Pendulum, half an env step; docs/sac.md); 32 steps per look put it under half a microsecond per step, and at most 31 steps (under a millisecond) run
@@ -2109,28 +2090,28 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     h->eval_poll = std::max(1, std::min(h->cfg.episode_len, 32));
     if (const char* ep = std::getenv("DRIL_SAC_EVAL_POLL")) { const long k = std::strtol(ep, nullptr, 10); if (k >= 1) h->eval_poll = (int)std::min<long>(k, 1 << 20); }
     CHK(h->env.alloc(S));
-    CHK(smalloc(&h->obs_cur, (size_t)E * D)); CHK(smalloc(&h->obs_nxt, (size_t)E * D)); CHK(smalloc(&h->e_rew, E)); CHK(smalloc(&h->e_tobs, (size_t)E * D));
-    CHK(smalloc(&h->e_raw, (size_t)E * A)); CHK(smalloc(&h->e_envact, (size_t)E * A)); CHK(smalloc(&h->e_term, E)); CHK(smalloc(&h->e_trunc, E));
+    CHK(h->obs_cur.alloc_zero((size_t)E * D)); CHK(h->obs_nxt.alloc_zero((size_t)E * D)); CHK(h->e_rew.alloc_zero(E)); CHK(h->e_tobs.alloc_zero((size_t)E * D));
+    CHK(h->e_raw.alloc_zero((size_t)E * A)); CHK(h->e_envact.alloc_zero((size_t)E * A)); CHK(h->e_term.alloc_zero(E)); CHK(h->e_trunc.alloc_zero(E));
     h->cap = cfg->buffer_capacity;
-    CHK(smalloc(&h->rb_obs, (size_t)h->cap * D)); CHK(smalloc(&h->rb_next, (size_t)h->cap * D)); CHK(smalloc(&h->rb_act, (size_t)h->cap * A));
-    CHK(smalloc(&h->rb_rew, (size_t)h->cap)); CHK(smalloc(&h->rb_term, (size_t)h->cap)); CHK(smalloc(&h->rb_trunc, (size_t)h->cap));
+    CHK(h->rb_obs.alloc_zero((size_t)h->cap * D)); CHK(h->rb_next.alloc_zero((size_t)h->cap * D)); CHK(h->rb_act.alloc_zero((size_t)h->cap * A));
+    CHK(h->rb_rew.alloc_zero((size_t)h->cap)); CHK(h->rb_term.alloc_zero((size_t)h->cap)); CHK(h->rb_trunc.alloc_zero((size_t)h->cap));
     const size_t nm = h->nmax, nq = h->nq;
-    if (H1 % 2 == 0) { CHK(smalloc(&h->col_h1p, (size_t)2 * nm * (H1 / 2))); CHK(smalloc(&h->col_w2p, (size_t)2 * H2 * (H1 / 2))); CHK(smalloc(&h->col_flags, 2)); }   // f16 planes of h1 [2][nm][H1/2] and of the actor's W2 [2][H2][H1/2]; their range flags
-    CHK(smalloc(&h->xa, nm * D)); CHK(smalloc(&h->ah1, nm * H1)); CHK(smalloc(&h->ah2, nm * H2)); CHK(smalloc(&h->mu, nm * A));
-    CHK(smalloc(&h->xq, 2 * nq * W)); h->xq_next = h->xq + nq * W; CHK(smalloc(&h->xq_pi, nq * W));       // [xq | xq_next]: one input buffer, batch index z / 2
-    CHK(smalloc(&h->qh1, 4 * nq * H1)); CHK(smalloc(&h->qh2, 4 * nq * H2)); h->th1 = h->qh1 + 2 * nq * H1; h->th2 = h->qh2 + 2 * nq * H2;   // z = 0,1 critics (kept for the reverse pass), 2,3 targets
-    CHK(smalloc(&h->q_cur, 4 * nq)); h->q_next = h->q_cur + 2 * nq; CHK(smalloc(&h->q_pi, 2 * nq)); CHK(smalloc(&h->dq, 2 * nq));
-    CHK(smalloc(&h->dz2, 2 * nq * H2)); CHK(smalloc(&h->dz1, 2 * nq * H1)); CHK(smalloc(&h->dxq, 2 * nq * W)); CHK(smalloc(&h->dmu, nq * A));
-    CHK(smalloc(&h->b_rew, nq)); CHK(smalloc(&h->b_ne, nq * A)); CHK(smalloc(&h->b_nn, nq * A)); CHK(smalloc(&h->b_np, nq * A)); CHK(smalloc(&h->b_nlp, nq));
-    CHK(smalloc(&h->a_pi, nq * A)); CHK(smalloc(&h->g_pi, nq * A)); CHK(smalloc(&h->lp_pi, nq)); CHK(smalloc(&h->b_term, nq));
-    CHK(smalloc(&h->s_in, nm * D)); CHK(smalloc(&h->s_act, nm * A)); CHK(smalloc(&h->s_noise, nm * A)); CHK(smalloc(&h->s_out, nm * A)); CHK(smalloc(&h->s_out2, nm * A));
+    if (H1 % 2 == 0) { CHK(h->col_h1p.alloc_zero((size_t)2 * nm * (H1 / 2))); CHK(h->col_w2p.alloc_zero((size_t)2 * H2 * (H1 / 2))); CHK(h->col_flags.alloc_zero(2)); }   // f16 planes of h1 [2][nm][H1/2] and of the actor's W2 [2][H2][H1/2]; their range flags
+    CHK(h->xa.alloc_zero(nm * D)); CHK(h->ah1.alloc_zero(nm * H1)); CHK(h->ah2.alloc_zero(nm * H2)); CHK(h->mu.alloc_zero(nm * A));
+    CHK(h->xq.alloc_zero(2 * nq * W)); h->xq_next = h->xq + nq * W; CHK(h->xq_pi.alloc_zero(nq * W));       // [xq | xq_next]: one input buffer, batch index z / 2
+    CHK(h->qh1.alloc_zero(4 * nq * H1)); CHK(h->qh2.alloc_zero(4 * nq * H2)); h->th1 = h->qh1 + 2 * nq * H1; h->th2 = h->qh2 + 2 * nq * H2;   // z = 0,1 critics (kept for the reverse pass), 2,3 targets
+    CHK(h->q_cur.alloc_zero(4 * nq)); h->q_next = h->q_cur + 2 * nq; CHK(h->q_pi.alloc_zero(2 * nq)); CHK(h->dq.alloc_zero(2 * nq));
+    CHK(h->dz2.alloc_zero(2 * nq * H2)); CHK(h->dz1.alloc_zero(2 * nq * H1)); CHK(h->dxq.alloc_zero(2 * nq * W)); CHK(h->dmu.alloc_zero(nq * A));
+    CHK(h->b_rew.alloc_zero(nq)); CHK(h->b_ne.alloc_zero(nq * A)); CHK(h->b_nn.alloc_zero(nq * A)); CHK(h->b_np.alloc_zero(nq * A)); CHK(h->b_nlp.alloc_zero(nq));
+    CHK(h->a_pi.alloc_zero(nq * A)); CHK(h->g_pi.alloc_zero(nq * A)); CHK(h->lp_pi.alloc_zero(nq)); CHK(h->b_term.alloc_zero(nq));
+    CHK(h->s_in.alloc_zero(nm * D)); CHK(h->s_act.alloc_zero(nm * A)); CHK(h->s_noise.alloc_zero(nm * A)); CHK(h->s_out.alloc_zero(nm * A)); CHK(h->s_out2.alloc_zero(nm * A));
     CHK(hipEventCreate(&h->ev_a)); CHK(hipEventCreate(&h->ev_b));
     if (ext) {                                                                         // the device-array verbs: hand-over events and the sticky error word and the pending statistics table
         CHK(hipEventCreateWithFlags(&h->ext_ev_in, hipEventDisableTiming)); CHK(hipEventCreateWithFlags(&h->ext_ev_out, hipEventDisableTiming));
-        CHK(smalloc(&h->ext_err, 1)); CHK(hipHostMalloc((void**)&h->ext_err_host, 4)); *h->ext_err_host = 0;
+        CHK(h->ext_err.alloc_zero(1)); CHK(h->ext_err_host.alloc(1)); *h->ext_err_host = 0;
         if (cfg->profile_events) for (int i = 0; i < kXpPool; ++i) { hipEvent_t e = nullptr; CHK(hipEventCreate(&e)); h->xp_events.push_back(e); }   // (dril_sac_profile_get on this path: act / push pairs)
         // the pending statistics table of dril_sac_update_enqueue: allocated HERE, not on first use — an allocation and its fill would be a host wait inside a sync-free verb
-        CHK(smalloc(&h->pend_stats, (size_t)DRIL_SAC_PENDING_CAPACITY * 8)); CHK(smalloc(&h->pend_ssq, (size_t)DRIL_SAC_PENDING_CAPACITY * (h->adam_blocks_c + h->end_blocks)));
+        CHK(h->pend_stats.alloc_zero((size_t)DRIL_SAC_PENDING_CAPACITY * 8)); CHK(h->pend_ssq.alloc_zero((size_t)DRIL_SAC_PENDING_CAPACITY * (h->adam_blocks_c + h->end_blocks)));
     }
 #undef CHK
     const SacScalars sc0{logf(cfg->ent_coef_init), 0.f, 0.f, cfg->ent_coef_init};                   // init_entropy_coefficient sac.jl:207-213
@@ -2292,9 +2273,9 @@ DRIL_EXPORT int32_t dril_sac_predict_q(dril_sac_handle* h, const float* obs, con
 
 DRIL_EXPORT int32_t dril_sac_debug_set_collect_noise(dril_sac_handle* h, const float* noise, size_t count) {
     SNEED(h); SDO(ssync(h));
-    if (h->collect_noise) { hipFree(h->collect_noise); h->collect_noise = nullptr; h->collect_noise_count = 0; }
+    h->collect_noise.release(); h->collect_noise_count = 0;
     if (!noise || !count) return DRIL_OK;
-    SHIP(h, smalloc(&h->collect_noise, count)); SHIP(h, hipMemcpy(h->collect_noise, noise, count * 4, hipMemcpyHostToDevice)); h->collect_noise_count = count;
+    SHIP(h, h->collect_noise.alloc_zero(count)); SHIP(h, hipMemcpy(h->collect_noise, noise, count * 4, hipMemcpyHostToDevice)); h->collect_noise_count = count;
     return DRIL_OK;
 }
 DRIL_EXPORT int32_t dril_sac_collect_rollout(dril_sac_handle* h, int32_t n_steps, int32_t use_random_actions, double* fps) {
@@ -2508,9 +2489,9 @@ DRIL_EXPORT int32_t dril_sac_update_enqueue(dril_sac_handle* h, int32_t n_update
         rc = sac_one_update(h, injected ? k : -1, h->pend_stats + row * 8, nullptr, h->pend_ssq + row * nb);
         if (rc == DRIL_OK) h->pend_n += 1;
     }
-    // the injected batches are read by launches still in flight: hipFree would wait for the device, so they go with the next flush
-    for (void* p : {(void*)h->inj_idx, (void*)h->inj_ne, (void*)h->inj_nn, (void*)h->inj_np}) if (p) h->pend_free.push_back(p);
-    h->inj_idx = nullptr; h->inj_ne = h->inj_nn = h->inj_np = nullptr; h->inj_updates = 0;
+    // the injected batches are read by launches still in flight: freeing them would wait for the device, so they go with the next flush
+    if (h->inj_idx || h->inj_ne || h->inj_nn || h->inj_np) h->pend_free.push_back(dril_sac_handle::InjectedBatches{std::move(h->inj_idx), std::move(h->inj_ne), std::move(h->inj_nn), std::move(h->inj_np)});
+    h->inj_updates = 0;
     return rc;
 }
 DRIL_EXPORT int32_t dril_sac_flush(dril_sac_handle* h, dril_sac_stats* stats, int64_t stats_capacity, int64_t* n_stats) {
@@ -2521,7 +2502,6 @@ DRIL_EXPORT int32_t dril_sac_flush(dril_sac_handle* h, dril_sac_stats* stats, in
     h->ext_flushes += 1;
     for (size_t i = 0; i + 1 < h->xp_n; i += 2) { float ms = 0; if (hipEventElapsedTime(&ms, h->xp_events[i], h->xp_events[i + 1]) == hipSuccess) h->collect_ms += ms; }   // cfg.profile_events: an act and a push per env step
     h->collect_steps += (int64_t)(h->xp_n / 4); h->xp_n = 0;                                       // (a step = an act and a push: four events)
-    for (void* p : h->pend_free) hipFree(p);
     h->pend_free.clear();
     const int n = h->pend_n;
     if (n_stats) *n_stats = n;
@@ -2570,12 +2550,12 @@ DRIL_EXPORT int32_t dril_sac_replay_copy_out(dril_sac_handle* h, int32_t which, 
     SNEED(h);
     size_t w; const char* src;
     switch (which) {
-        case DRIL_RB_OBSERVATIONS: w = (size_t)h->D * 4; src = (const char*)h->rb_obs; break;
-        case DRIL_RB_NEXT_OBSERVATIONS: w = (size_t)h->D * 4; src = (const char*)h->rb_next; break;
-        case DRIL_RB_ACTIONS: w = (size_t)h->A * 4; src = (const char*)h->rb_act; break;
-        case DRIL_RB_REWARDS: w = 4; src = (const char*)h->rb_rew; break;
-        case DRIL_RB_TERMINATED: w = 1; src = (const char*)h->rb_term; break;
-        case DRIL_RB_TRUNCATED: w = 1; src = (const char*)h->rb_trunc; break;
+        case DRIL_RB_OBSERVATIONS: w = (size_t)h->D * 4; src = (const char*)h->rb_obs.get(); break;
+        case DRIL_RB_NEXT_OBSERVATIONS: w = (size_t)h->D * 4; src = (const char*)h->rb_next.get(); break;
+        case DRIL_RB_ACTIONS: w = (size_t)h->A * 4; src = (const char*)h->rb_act.get(); break;
+        case DRIL_RB_REWARDS: w = 4; src = (const char*)h->rb_rew.get(); break;
+        case DRIL_RB_TERMINATED: w = 1; src = (const char*)h->rb_term.get(); break;
+        case DRIL_RB_TRUNCATED: w = 1; src = (const char*)h->rb_trunc.get(); break;
         default: return sfail(h, DRIL_ERR_INVALID_ARG, "unknown replay field");
     }
     if (!host || bytes != w * (size_t)h->size) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_replay_copy_out: bytes must equal replay_size * element size");
@@ -2607,11 +2587,11 @@ DRIL_EXPORT int32_t dril_sac_debug_set_batches(dril_sac_handle* h, int32_t n_upd
     const size_t nb = (size_t)n_updates * h->cfg.batch_size, na = nb * h->A;
     if (idx) {
         for (size_t i = 0; i < nb; ++i) if (idx[i] < 0 || idx[i] >= h->size) return sfail(h, DRIL_ERR_INVALID_ARG, "injected replay index out of range");
-        SHIP(h, smalloc(&h->inj_idx, nb)); SHIP(h, hipMemcpy(h->inj_idx, idx, nb * 8, hipMemcpyHostToDevice));
+        SHIP(h, h->inj_idx.alloc_zero(nb)); SHIP(h, hipMemcpy(h->inj_idx, idx, nb * 8, hipMemcpyHostToDevice));
     }
-    if (ne) { SHIP(h, smalloc(&h->inj_ne, na)); SHIP(h, hipMemcpy(h->inj_ne, ne, na * 4, hipMemcpyHostToDevice)); }
-    if (nn) { SHIP(h, smalloc(&h->inj_nn, na)); SHIP(h, hipMemcpy(h->inj_nn, nn, na * 4, hipMemcpyHostToDevice)); }
-    if (np) { SHIP(h, smalloc(&h->inj_np, na)); SHIP(h, hipMemcpy(h->inj_np, np, na * 4, hipMemcpyHostToDevice)); }
+    if (ne) { SHIP(h, h->inj_ne.alloc_zero(na)); SHIP(h, hipMemcpy(h->inj_ne, ne, na * 4, hipMemcpyHostToDevice)); }
+    if (nn) { SHIP(h, h->inj_nn.alloc_zero(na)); SHIP(h, hipMemcpy(h->inj_nn, nn, na * 4, hipMemcpyHostToDevice)); }
+    if (np) { SHIP(h, h->inj_np.alloc_zero(na)); SHIP(h, hipMemcpy(h->inj_np, np, na * 4, hipMemcpyHostToDevice)); }
     h->inj_updates = n_updates;
     return DRIL_OK;
 }
@@ -2705,10 +2685,22 @@ DRIL_EXPORT int32_t dril_sac_profile_reset(dril_sac_handle* h) { SNEED(h); h->co
 // ---- MonitorWrapperEnv around the handle's device envs (monitorWrapperEnv.jl) ----------------------------------------------------------------------------
 namespace {
 void monitor_free(dril_sac_handle* h) {
-    void* ptrs[] = {h->mon_cur_ret, h->mon_cur_len, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->mon_ep_ret, h->mon_ep_len, h->mon_flags};
-    for (void* p : ptrs) if (p) hipFree(p);
-    h->mon_cur_ret = h->mon_ring_ret = h->mon_ep_ret = nullptr; h->mon_cur_len = h->mon_ring_len = h->mon_ep_len = nullptr; h->mon_meta = nullptr; h->mon_flags = nullptr;
+    h->mon_cur_ret.release(); h->mon_cur_len.release(); h->mon_ring_ret.release(); h->mon_ring_len.release();
+    h->mon_meta.release(); h->mon_ep_ret.release(); h->mon_ep_len.release(); h->mon_flags.release();
     h->mon_window = 0; h->mon_rows_cap = 0; h->mon_row = 0;
+}
+// the arrays of a monitor with this window and a block of `rows` buffered steps, zeroed: fresh sums, an empty window
+hipError_t monitor_alloc(dril_sac_handle* h, int32_t window, size_t rows) {
+    const size_t E = (size_t)h->cfg.n_envs;
+    hipError_t e = h->mon_cur_ret.alloc_zero(E);
+    if (e == hipSuccess) e = h->mon_cur_len.alloc_zero(E);
+    if (e == hipSuccess) e = h->mon_ring_ret.alloc_zero((size_t)window);
+    if (e == hipSuccess) e = h->mon_ring_len.alloc_zero((size_t)window);
+    if (e == hipSuccess) e = h->mon_meta.alloc_zero(2);
+    if (e == hipSuccess) e = h->mon_ep_ret.alloc_zero(rows * E);
+    if (e == hipSuccess) e = h->mon_ep_len.alloc_zero(rows * E);
+    if (e == hipSuccess) e = h->mon_flags.alloc_zero(rows * E);
+    return e;
 }
 // log_stats over the window as it stands on the device, after a drain: one body for dril_sac_monitor_get_stats and dril_sac_ext_monitor_get_stats
 int monitor_read(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
@@ -2737,14 +2729,7 @@ DRIL_EXPORT int32_t dril_sac_monitor_enable(dril_sac_handle* h, int32_t window) 
     monitor_free(h);
     if (window == 0) return DRIL_OK;
     const size_t E = (size_t)h->cfg.n_envs, rows = (size_t)std::max(1, h->cfg.train_freq);
-    hipError_t e = smalloc(&h->mon_cur_ret, E);                                       // (smalloc zeroes: fresh sums, an empty window)
-    if (e == hipSuccess) e = smalloc(&h->mon_cur_len, E);
-    if (e == hipSuccess) e = smalloc(&h->mon_ring_ret, (size_t)window);
-    if (e == hipSuccess) e = smalloc(&h->mon_ring_len, (size_t)window);
-    if (e == hipSuccess) e = smalloc(&h->mon_meta, 2);
-    if (e == hipSuccess) e = smalloc(&h->mon_ep_ret, rows * E);
-    if (e == hipSuccess) e = smalloc(&h->mon_ep_len, rows * E);
-    if (e == hipSuccess) e = smalloc(&h->mon_flags, rows * E);
+    const hipError_t e = monitor_alloc(h, window, rows);
     if (e != hipSuccess) { monitor_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_monitor_enable: ") + hipGetErrorString(e)); }
     h->mon_window = window; h->mon_rows_cap = (int)rows;
     return DRIL_OK;
@@ -2803,11 +2788,8 @@ DRIL_EXPORT int32_t dril_sac_normalize_enable(dril_sac_handle* h, const dril_sac
     if (h->nz.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart: that is set_training's to change): its statistics and returns stay
     SDO(ssync(h));
     normalize_free(h);
-    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
-    hipError_t e = h->nz.alloc((int)D, std::max<size_t>(kNzMaxRows, h->env.module ? 0 : (E + kEnvsPerBlock - 1) / kEnvsPerBlock));
-    if (e == hipSuccess) e = smalloc(&h->nz_returns, E);                               // (smalloc zeroes: returns and the cached originals start at 0)
-    if (e == hipSuccess) e = smalloc(&h->nz_old_obs, E * D);
-    if (e == hipSuccess) e = smalloc(&h->nz_old_rew, E);
+    const size_t E = (size_t)h->cfg.n_envs;
+    const hipError_t e = normalize_alloc(h, std::max<size_t>(kNzMaxRows, h->env.module ? 0 : (E + kEnvsPerBlock - 1) / kEnvsPerBlock));
     if (e != hipSuccess) { normalize_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_normalize_enable: ") + hipGetErrorString(e)); }
     h->nz.cfg = c; h->nz.on = true; h->obs_valid = false;                              // the next collection observes through the wrapper
     return DRIL_OK;
@@ -2897,11 +2879,7 @@ DRIL_EXPORT int32_t dril_sac_ext_normalize_enable(dril_sac_handle* h, const dril
     if (h->nz.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart, which is set): its statistics, returns and collection stay
     SDO(ssync(h));
     normalize_free(h);
-    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
-    hipError_t e = h->nz.alloc((int)D, kNzMaxRows);
-    if (e == hipSuccess) e = smalloc(&h->nz_returns, E);                               // (smalloc zeroes: returns and the cached originals start at 0)
-    if (e == hipSuccess) e = smalloc(&h->nz_old_obs, E * D);
-    if (e == hipSuccess) e = smalloc(&h->nz_old_rew, E);
+    const hipError_t e = normalize_alloc(h, kNzMaxRows);
     if (e != hipSuccess) { normalize_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_ext_normalize_enable: ") + hipGetErrorString(e)); }
     h->nz.cfg = c; h->nz.on = true; h->xw_begin = h->xw_live = false;
     return DRIL_OK;
@@ -2962,14 +2940,7 @@ DRIL_EXPORT int32_t dril_sac_ext_monitor_enable(dril_sac_handle* h, int32_t wind
     if (window == 0) return DRIL_OK;
     // the block of buffered steps: a row per push until dril_sac_flush / dril_sac_ext_monitor_get_stats (or a full block) collects it; about a million entries, 4 .. 256 rows
     const size_t E = (size_t)h->cfg.n_envs, rows = std::max<size_t>(4, std::min<size_t>(256, ((size_t)1 << 20) / E));
-    hipError_t e = smalloc(&h->mon_cur_ret, E);                                       // (smalloc zeroes: fresh sums, an empty window)
-    if (e == hipSuccess) e = smalloc(&h->mon_cur_len, E);
-    if (e == hipSuccess) e = smalloc(&h->mon_ring_ret, (size_t)window);
-    if (e == hipSuccess) e = smalloc(&h->mon_ring_len, (size_t)window);
-    if (e == hipSuccess) e = smalloc(&h->mon_meta, 2);
-    if (e == hipSuccess) e = smalloc(&h->mon_ep_ret, rows * E);
-    if (e == hipSuccess) e = smalloc(&h->mon_ep_len, rows * E);
-    if (e == hipSuccess) e = smalloc(&h->mon_flags, rows * E);
+    const hipError_t e = monitor_alloc(h, window, rows);
     if (e != hipSuccess) { monitor_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_ext_monitor_enable: ") + hipGetErrorString(e)); }
     h->mon_window = window; h->mon_rows_cap = (int)rows;
     return DRIL_OK;
@@ -2977,18 +2948,14 @@ DRIL_EXPORT int32_t dril_sac_ext_monitor_enable(dril_sac_handle* h, int32_t wind
 
 // ---- evaluate_agent (src/evaluation.jl:54-143) with the handle's actor on the handle's envs -------------------------------------------------------------------
 namespace {
-template <typename T> int ensure_buf(dril_sac_handle* h, T** p, size_t n) { if (!*p) SHIP(h, smalloc(p, n)); return DRIL_OK; }
+template <typename T> int ensure_buf(dril_sac_handle* h, DevBuf<T>& p, size_t n) { if (!p) SHIP(h, p.alloc_zero(n)); return DRIL_OK; }
 // the buffers of an evaluation: allocated by the first one, kept; the event list grows with n_eval
 int eval_buffers(dril_sac_handle* h, long long cap) {
     const size_t E = (size_t)h->cfg.n_envs;
-    SDO(ensure_buf(h, &h->ev_state, E * h->S)); SDO(ensure_buf(h, &h->ev_obs, E * h->D)); SDO(ensure_buf(h, &h->ev_sc, E)); SDO(ensure_buf(h, &h->ev_ep, E)); SDO(ensure_buf(h, &h->ev_gs, E));
-    SDO(ensure_buf(h, &h->ev_mon_ret, E)); SDO(ensure_buf(h, &h->ev_mon_len, E)); SDO(ensure_buf(h, &h->ev_cur_ret, E)); SDO(ensure_buf(h, &h->ev_cur_len, E)); SDO(ensure_buf(h, &h->ev_counter, 1));
-    if (!h->ev_counter_host) SHIP(h, hipHostMalloc((void**)&h->ev_counter_host, sizeof(unsigned int), hipHostMallocDefault));
-    if (cap > h->ev_events_cap) {
-        if (h->ev_events) hipFree(h->ev_events);
-        h->ev_events = nullptr; h->ev_events_cap = 0;
-        SHIP(h, smalloc(&h->ev_events, (size_t)cap)); h->ev_events_cap = cap;
-    }
+    SDO(ensure_buf(h, h->ev_state, E * h->S)); SDO(ensure_buf(h, h->ev_obs, E * h->D)); SDO(ensure_buf(h, h->ev_sc, E)); SDO(ensure_buf(h, h->ev_ep, E)); SDO(ensure_buf(h, h->ev_gs, E));
+    SDO(ensure_buf(h, h->ev_mon_ret, E)); SDO(ensure_buf(h, h->ev_mon_len, E)); SDO(ensure_buf(h, h->ev_cur_ret, E)); SDO(ensure_buf(h, h->ev_cur_len, E)); SDO(ensure_buf(h, h->ev_counter, 1));
+    if (!h->ev_counter_host) SHIP(h, h->ev_counter_host.alloc(1));
+    if (cap > 0) SHIP(h, h->ev_events.grow_zero((size_t)cap));
     return DRIL_OK;
 }
 // the env side of the handle, out (save) or back in (restore): simulator state, counters, the noise stream's position, the current observation, the monitor's sums
@@ -3109,7 +3076,7 @@ namespace {
 // the recording of one call.  No ClampAdapter (the boxes' clamp_* stay null): TanhScaleAdapter's actions are inside the Box by construction
 int traj_prepare(dril_sac_handle* h, const dril_traj_options* o, int32_t Tcap, TrajRun& r) {
     const TrajLayout L = traj_layout((size_t)o->n_trajectories, (size_t)h->D, (size_t)h->A, (size_t)h->S, (size_t)Tcap);
-    SHIP(h, traj_setup(h->env, h->stream, &h->traj_blob, &h->traj_blob_bytes, h->ev_counter, L, traj_env_boxes(h->env), o->final_original != 0, /*drain_before_free=*/true, r));
+    SHIP(h, traj_setup(h->env, h->stream, h->traj_blob, h->ev_counter, L, traj_env_boxes(h->env), o->final_original != 0, /*drain_before_free=*/true, r));
     return DRIL_OK;
 }
 // one env step, enqueued: the launches of eval_step without the accounting, and the recording of envs 0..M-1

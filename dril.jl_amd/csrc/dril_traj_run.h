@@ -1,6 +1,6 @@
 // dril_traj_run.h — the recording setup of a device-resident collect_trajectory, for the PPO handle (dril_api.hip) and the SAC handle (dril_sac.hip) alike: the layout
 // of the handle's private blob, the table of bounds behind TrajMaps, the shadow envs, and the refusals and reports in which only the verb's name differs.  Nothing
-// here knows a handle: envs, stream, the blob's two words, a counter and sizes are plain arguments, and an error comes back as a hipError_t or as a message (empty:
+// here knows a handle: envs, stream, the blob's owner, a counter and sizes are plain arguments, and an error comes back as a hipError_t or as a message (empty:
 // none) for the caller's own fail / sfail.  No HIP dependency above the #if (tests/test_traj_run.py drives traj_layout and traj_bounds_table with g++).
 #pragma once
 #include <string>
@@ -10,6 +10,7 @@
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #include <algorithm>
 #include <vector>
+#include "dril_devmem.h"     // DevBuf: the blob
 #include "dril_env_side.h"   // DeviceEnvs; scaled_kind_boxes (dril_env_kinds.h) through dril_internal.h
 #endif
 
@@ -86,16 +87,13 @@ inline TrajBoxes traj_env_boxes(const DeviceEnvs& env) {
 }
 // Grows the blob where L needs more (drain_before_free: the handle does not free under a running stream), carves it, builds r and puts the table on the device.
 // Returns with `stream` drained: the table's host copy is a local
-inline hipError_t traj_setup(const DeviceEnvs& env, hipStream_t stream, char** blob, size_t* blob_bytes, unsigned int* counter, const TrajLayout& L, const TrajBoxes& boxes,
+inline hipError_t traj_setup(const DeviceEnvs& env, hipStream_t stream, DevBuf<char>& blob, unsigned int* counter, const TrajLayout& L, const TrajBoxes& boxes,
                              bool final_original, bool drain_before_free, TrajRun& r) {
-    if (L.total > *blob_bytes) {
+    if (L.total > blob.size()) {
         if (drain_before_free) { if (const hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e; }
-        if (*blob) (void)hipFree(*blob);
-        *blob = nullptr; *blob_bytes = 0;
-        if (const hipError_t e = hipMalloc((void**)blob, L.total); e != hipSuccess) return e;
-        *blob_bytes = L.total;
+        if (const hipError_t e = blob.alloc(L.total); e != hipSuccess) return e;
     }
-    char* b = *blob;
+    char* b = blob;
     r.rec = TrajRec{(int32_t)L.M, (int32_t)L.D, (int32_t)L.W, (int32_t)L.Tcap, (float*)(b + L.obs.at), (uint32_t*)(b + L.act.at), (float*)(b + L.rew.at), (int32_t*)(b + L.len.at),
                     (uint8_t*)(b + L.flg.at), counter};
     r.shadow = env;                                                                // the kind / the plug-in's kernels, scaling, action_start

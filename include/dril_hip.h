@@ -746,6 +746,10 @@ const char* dril_device_info(const dril_handle* h);
  * all of them.  Each handle must then be driven from its own host thread, all making the same sequence of calls; a rank that waits
  * 120 s for the others fails with DRIL_ERR_RCCL.  (new: the reference has no distributed code) */
 int32_t dril_debug_comm_loopback(dril_handle** handles, int32_t n);
+/* DEBUG / TEST: bytes of device and pinned host memory that the handles, populations and running calls of this process hold through the library's owning buffers
+ * (csrc/dril_devmem.h), process-wide.  Back at its earlier value once whatever was created since is destroyed; unlike hipMemGetInfo it does not see other tenants
+ * of the card.  (The envs' own arrays and a deployment policy are not counted.) */
+int64_t dril_debug_device_bytes_live(void);
 
 /* ---- measurement ---------------------------------------------------------------- */
 /* accumulated HIP-event time and count of the BRACKETED launches of one kernel class since the last reset (total_ms / launches = average launch);

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""create / use / destroy every handle type in a loop and watch free device memory (hipMemGetInfo): leaks show up as a drift"""
+"""create / use / destroy every handle type in a loop and watch free device memory (hipMemGetInfo): leaks show up as a drift.  Next to it the library's own count of
+bytes its owning buffers hold (dril_debug_device_bytes_live), which must be back at its start after the loop, exactly"""
 import ctypes as C, sys
 from pathlib import Path
 import numpy as np
@@ -24,12 +25,14 @@ def sac():
     env = pkg.PendulumEnv(); alg = pkg.SAC(batch_size=64, buffer_capacity=4096, start_steps=64)
     layer = pkg.SACLayer(env.observation_space(), env.action_space(), hidden_dims=(64, 64))
     h = pkg.SacHandle(pkg.make_sac_config(env, 16, alg, layer)); h.env_reset(0); h.train(400); h.close()
-base = None
+live = capi.load_library().dril_debug_device_bytes_live
+base, live0 = None, live()
 for rep in range(6):
     for _ in range(10):
         ppo(capi.ENV_CARTPOLE); ppo(capi.ENV_PENDULUM, hidden1=256, hidden2=256, norm_obs=1, norm_reward=1, norm_training=1, monitor_window=10)
         ppo(capi.ENV_EXTERNAL, ext_obs_dim=20, ext_action_dim=5, ext_discrete=0, hidden1=96, hidden2=48); sac()
     f = free_mb(); base = base or f
-    print(f"after {10 * (rep + 1):3d} rounds of 4 handles: free {f:10.1f} MiB (drift {f - base:+.1f})")
+    print(f"after {10 * (rep + 1):3d} rounds of 4 handles: free {f:10.1f} MiB (drift {f - base:+.1f}), live bytes of the owners {live() - live0:+d}")
 assert abs(free_mb() - base) < 64, "device memory drifts"
+assert live() == live0, f"the owners still hold {live() - live0} bytes"
 print("no leak")
