@@ -1,201 +1,69 @@
 // dril_api.hip — the C ABI of libdril_hip.so (include/dril_hip.h): handle, device memory, launch sequencing.
 // One HIP stream per handle; kernels of one PPO iteration are enqueued back-to-back with no host sync
 // (KL early-stop and NaN detection are device flags the later kernels test), RCCL all-reduces ride the
-// same stream.  RCCL is dlopen'ed lazily so single-GPU users never load it.
-#include <dlfcn.h>
-
+// same stream.  The handle itself, and what this file shares with dril_comm.hip (RCCL) and dril_wrap.hip (NormalizeWrapperEnv on plug-in and external handles): dril_handle.h.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
-#include "../../include/dril_hip.h"
-#include "dril_internal.h"
-#include "dril_devmem.h"     // DevBuf / PinnedBuf: every allocation a handle or a population holds; a raw pointer member is not owned
-#include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper on plug-ins shares with the SAC handle's (NormWrap, norm_moments_kernel, nz_*)
+#include "dril_handle.h"
+
 #include "dril_policy_internal.h"   // dril_policy_from_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
-#include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in kind or a device env plug-in), shared with the SAC handle
 #include "dril_traj_record.h"  // collect_trajectory on the device: the per-env recording traj_record_kernel runs (host-compilable)
 #include "dril_traj_run.h"    // ... and its setup (blob layout, table of bounds, shadow envs, messages), shared with the SAC handle
 #include "dril_ext_stream.h"  // the pointer rule and the stream hand-over of the device-array verbs, shared with the SAC handle
 
 using namespace dril;
-
-#define DRIL_EXPORT extern "C" __attribute__((visibility("default")))
-
-namespace {
-
-thread_local std::string g_create_error;
-
-// ---- minimal RCCL surface, resolved at run time ------------------------------------------------
-struct RcclApi {
-    void* lib = nullptr;
-    int (*GetUniqueId)(void*) = nullptr;
-    int (*CommInitRank)(void**, int, const void*, int) = nullptr;   // ncclUniqueId passed by value = 128-byte struct
-    int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*CommDestroy)(void*) = nullptr;
-    int (*CommCount)(void*, int*) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-    const char* (*GetLastError)(void*) = nullptr;       // ncclGetLastError(comm): the human-readable cause behind a status code (which rank / device / transport)
-};
-struct NcclId { char bytes[128]; };
-typedef int (*nccl_init_rank_fn)(void**, int, NcclId, int);
-RcclApi g_rccl;
-bool load_rccl(std::string& err) {
-    if (g_rccl.lib) return true;
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    for (const char* n : names) { g_rccl.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL); if (g_rccl.lib) break; }
-    if (!g_rccl.lib) { err = std::string("dlopen(librccl) failed: ") + dlerror(); return false; }
-    g_rccl.GetUniqueId = (int (*)(void*))dlsym(g_rccl.lib, "ncclGetUniqueId");
-    g_rccl.CommInitRank = (int (*)(void**, int, const void*, int))dlsym(g_rccl.lib, "ncclCommInitRank");
-    g_rccl.AllReduce = (int (*)(const void*, void*, size_t, int, int, void*, hipStream_t))dlsym(g_rccl.lib, "ncclAllReduce");
-    g_rccl.CommDestroy = (int (*)(void*))dlsym(g_rccl.lib, "ncclCommDestroy");
-    g_rccl.GetErrorString = (const char* (*)(int))dlsym(g_rccl.lib, "ncclGetErrorString");
-    g_rccl.CommCount = (int (*)(void*, int*))dlsym(g_rccl.lib, "ncclCommCount");
-    g_rccl.GetLastError = (const char* (*)(void*))dlsym(g_rccl.lib, "ncclGetLastError");
-    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllReduce) { err = "librccl lacks ncclGetUniqueId/ncclCommInitRank/ncclAllReduce"; return false; }
-    return true;
-}
-constexpr int kNcclFloat32 = 7, kNcclFloat64 = 8, kNcclSum = 0;
-// "<call>: <ncclGetErrorString(rc)> [<ncclGetLastError(comm)>]": a failing first contact with a multi-GPU node must name its cause in dril_last_error
-std::string rccl_error(const char* call, int rc, void* comm) {
-    std::string m = std::string(call) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error") + " (status " + std::to_string(rc) + ")";
-    if (g_rccl.GetLastError) { const char* le = g_rccl.GetLastError(comm); if (le && *le) m += std::string(" [ncclGetLastError: ") + le + "]"; }
-    return m;
-}
-
-// ---- debug loopback communicator -----------------------------------------------------------------
-// RCCL refuses two ranks on one device, so the data-parallel code of this file (every `reduce` branch below) could only be
-// executed on a multi-GPU node.  A loopback group joins n handles of ONE process on ONE device as ranks 0..n-1: the all-reduce
-// call sites, counts and dtypes are unchanged, only the transport differs — the ranks' host threads rendezvous, the last arriver
-// makes its stream wait for every rank's buffer, one kernel sums the n device buffers element-wise in rank order and writes the
-// sum back to all of them (every rank ends with bit-identical values, as after a ring all-reduce), and the other ranks' streams
-// wait for that kernel.  Each handle must be driven from its own host thread (dril_debug_comm_loopback, include/dril_hip.h).
-constexpr int kLoopMax = 8;
-struct LoopPtrs { void* p[kLoopMax]; };
-struct LoopGroup {
-    std::mutex mu; std::condition_variable cv;
-    int n = 0, arrived = 0, refs = 0; uint64_t gen = 0; int64_t calls = 0;
-    LoopPtrs bufs{}; hipEvent_t ready[kLoopMax] = {nullptr}; hipEvent_t done = nullptr;
-    size_t count = 0; int dtype = 0; bool mismatch = false, failed = false;
-};
-template <typename T> __global__ void loop_allreduce_kernel(LoopPtrs bufs, int n, size_t count) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    T s = ((const T*)bufs.p[0])[i];
-    for (int r = 1; r < n; ++r) s += ((const T*)bufs.p[r])[i];      // fixed rank order: deterministic
-    for (int r = 0; r < n; ++r) ((T*)bufs.p[r])[i] = s;             // this thread has read element i of every rank before it writes any
-}
-
-struct ProfEvent { int kid; hipEvent_t a, b; };
-
-}  // namespace
-
-struct dril_handle {
-    dril_config cfg;
-    int D = 0, A = 0, S = 0, P = 0, Pa = 0, Pc = 0, log_std_off = 0;
-    bool discrete = true;
-    NetOff actor{}, critic{};
-    int64_t N = 0;
-    hipStream_t stream = nullptr;
-    int num_cus = 256;
-    std::string device_info;   // "device <ordinal> of <visible>: <name> <arch>, PCI <bus id>, HIP_VISIBLE_DEVICES=.. ROCR_VISIBLE_DEVICES=.." (dril_device_info; part of every RCCL failure message)
-    DevBuf<float> params, adam_m, adam_v, bt, flat, norm_out;
-    DevBuf<double> norm_partials; int n_norm_partials = 0;
-    DevBuf<float> slabs_a, slabs_c; int slab_a = 0, slab_c = 0, Gmax = 0;
-    DeviceEnvs env;   // the envs on the device: simulator state and counters, the seed, and for DRIL_ENV_MODULE the loaded plug-in (dril_env_side.h)
-    DevBuf<float> obs, rew, adv, ret, logp, val, boot, last_values;
-    DevBuf<char> act; DevBuf<uint8_t> flags;
-    DevBuf<char> noise_dev; bool noise_set = false;
-    DevBuf<int64_t> perm_dev; size_t perm_count = 0;
-    DevBuf<int32_t> epoch_index; bool no_epoch_index = false;   // the device DataLoader order of the current epoch, written out (large minibatches; DRIL_NO_EPOCH_INDEX)
-    DevBuf<double> adv_partials, adv_stats, ev_partials; int adv_blocks = 0, ev_blocks = 0;
-    DevBuf<float> step_stats;
-    DevBuf<int> stop_flag, nan_flag;
-    DevBuf<float> e_obs, e_rew, e_tobs; DevBuf<uint8_t> e_term, e_trunc; DevBuf<char> e_act;
-    uint64_t adam_steps = 0, update_counter = 0; uint32_t policy_calls = 0;
-    float lr = 0;
-    DevBuf<unsigned long long> dbg;
-    bool force_allreduce = false, force_stepwise = false;
-    bool fused_rollout = false; int64_t rollout_launches = 0;   // dril_rollout_fused_enable; launch calls of the last plug-in collection (dril_rollout_fused_info)
-    DevBuf<double> epoch_tables, epoch_stats; int epoch_blocks = 2048;   // per-epoch advantage moments
-    DevBuf<float> w2a_actor, w2ta_actor, w2a_critic, w2ta_critic; bool wide = false, wimg_dirty = true;   // wide nets (H > 64)
-    DevBuf<char> w2pf_actor, w2pf_critic;   // wide nets: the forward stream in the k-order of a register B operand (net_forward_wide_split)
-    DevBuf<char> w2p_actor, w2tp_actor, w2p_critic, w2tp_critic;   // wide nets: pre-split bf16 fragment streams of W2 / W2' (ppo_grad_wide_split_kernel)
-    // MonitorWrapperEnv (cfg.monitor_window > 0)
-    DevBuf<float> mon_cur_ret, ep_ret, mon_ring_ret, e_ep_ret; DevBuf<int32_t> mon_cur_len, ep_len, mon_ring_len, e_ep_len;
-    DevBuf<int> mon_cnt, mon_meta; DevBuf<uint8_t> e_flags;
-    DevBuf<float4> rec;   // packed minibatch records (see pack_records_kernel)
-    DevBuf<RmsState> obs_rms, ret_rms; int obs_par = 0, ret_par = 0;   // ping-pong RunningMeanStd pairs
-    DevBuf<double> rms_partials; int rms_blocks = 256; DevBuf<float> e_obs_raw; DevBuf<float> e_rew_n;   // e_obs_raw / e_rew: get_original_obs / get_original_rewards; e_rew_n: rewards as the wrapper delivers them
-    DevBuf<double> rms_red;   // data-parallel: this step's partial sums folded to one row and summed over ranks
-    int grad_actor_pct = 0;   // ppo_grad_pair_kernel: share (per mille) of the pairs given to the actor; 0 = by head (env DRIL_GRAD_ACTOR_PERMILLE)
-    int last_G = 0, last_Gc = 0; mutable char grad_info[640] = {0};   // the grid of that step (slabs of the actor / of the critic; ppo_grad_pair_kernel: pairs) and the text dril_grad_kernel_info returns
-    int last_variant = -1;  // which gradient kernel the last optimiser step ran: 0 ppo_grad_kernel, 2 ppo_grad_wide_kernel, 3 generic path, 4 ppo_grad_wide_split_kernel, 5 ppo_grad_pair_kernel (dril_grad_kernel_info)
-    int grad_variant = -1;  // env DRIL_GRAD_VARIANT: 0 = the exact-f32 kernels (ppo_grad_kernel / ppo_grad_wide_kernel), 1 = the bf16-split kernels (ppo_grad_pair_kernel at hidden 64, ppo_grad_wide_split_kernel at 128 / 256) for every minibatch size, -1 = default: wide nets split, hidden 64 by minibatch size
-    bool external = false; bool generic = false; DevBuf<float> gen_tmp;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
-    GenericDims gd{}; GenericWs gws; int ext_t = 0; bool ext_acted = false;   // DRIL_ENV_EXTERNAL: host envs, generic kernels
-    PinnedBuf<float> ext_stage_rew; PinnedBuf<uint8_t> ext_stage_flags;   // pinned [T][E] staging: dril_ext_record returns without draining the stream
-    // the device-array verbs (dril_ext_*_device): the two ordering events (created once), the sticky error word and its pinned host copy, the ClampAdapter's
-    // per-dimension table (dril_ext_set_action_bounds), the counters of dril_ext_device_info, grow-only scratch of dril_predict_actions_device
-    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; DevBuf<int> ext_err; PinnedBuf<int> ext_err_host;
-    ExtBounds ext_bounds{}; bool ext_bounds_set = false;
-    int ext_steps_dev = 0, ext_steps_host = 0, ext_syncs = 0; int64_t ext_launches = 0;
-    DevBuf<char> ext_pred_act; DevBuf<float> ext_pred_lp;
-    // NormalizeWrapperEnv around a plug-in env (dril_normalize_enable; kernels: dril_norm_wrap.h, dril_ppo_norm.h).  pn_red: the one row a data-parallel job all-reduces.
-    // The wrapper's other arrays are the handle's own: disc_returns (`returns`), e_obs_raw / e_rew (old_obs / old_rewards: dril_normalize_get_original), e_rew_n (the
-    // rewards dril_env_step delivers)
-    NormWrap pn; int pn_rows_cap = 0; DevBuf<double> pn_red;
-    // the same wrapper and MonitorWrapperEnv around the envs of a DRIL_ENV_EXTERNAL handle (dril_ext_normalize_enable / dril_ext_monitor_enable; kernels: dril_ext_norm.h): pn
-    // again, with e_tobs as the scratch of normalised terminal observations; ext_mon_window sizes the monitor arrays above (cfg.monitor_window stays 0).  xw_added: launches
-    // the wrappers added to the act / record / finish calls of the current rollout; xw_allocs: allocations inside those calls since enable (dril_ext_wrap_info)
-    int ext_mon_window = 0; int64_t xw_added[3] = {0, 0, 0}, xw_allocs = 0; DevBuf<float> ext_pred_obs;
-    void* comm = nullptr;
-    LoopGroup* loop = nullptr;   // debug loopback communicator (dril_debug_comm_loopback)
-    dril_population* pop = nullptr;   // the population the handle is a member of (dril_population_join): dril_destroy waits for dril_population_destroy
-    int64_t allreduce_calls = 0;
-    DevBuf<float> retry_snap; bool no_f32_retry = false; int64_t f32_retries = 0;   // ppo_update: state before the update (for the exact-f32 redo of an update that left f16's range); DRIL_NO_F32_RETRY; how often it happened
-    // the redo's bookkeeping (dril_f32_fallback_info): used_f16 = an f16-piece kernel ran in the current update (sticky over its optimiser steps — the LAST step's kernel says nothing
-    // about a ragged tail); streak = consecutive redone updates; after kRetryLatchAfter of them the next kRetryLatchUpdates updates run the exact-f32 kernels directly (no wasted f16
-    // pass, no snapshot), then ONE update probes f16 again; direct = updates run that way (latched, or max |W2| out of f16's range)
-    bool used_f16 = false, spin_timeout = false; int f32_streak = 0, f32_latch_left = 0; int64_t f32_direct_updates = 0, persistent_fallbacks = 0;
-    DevBuf<unsigned long long> gae_carry; unsigned gae_tag = 0; DevBuf<int> gae_err;   // gae_scan_kernel: the chunk-to-chunk carry words, the launch tag that validates them, its give-up flag
-    DevBuf<unsigned> w2max_dev; float w2max = 0.f;   // max |W2| over both nets (fused kernels): host copy refreshed by dril_set_params and with every optimiser run's statistics
-    bool no_small_path = false;   // DRIL_NO_SMALL_PATH (with DRIL_DEBUG=1), latched in dril_create
-    bool no_persistent = false; DevBuf<unsigned long long> small_xchg; DevBuf<uint64_t> epoch_keys; int64_t small_chunk = 16384;   // ppo_update_small_kernel (batch_size <= 64): DRIL_NO_PERSISTENT_UPDATE; per-epoch DataLoader keys on the device
-    std::vector<ProfEvent> prof_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
-    double prof_ms[DRIL_K_COUNT] = {0}; int64_t prof_n[DRIL_K_COUNT] = {0}, prof_all[DRIL_K_COUNT] = {0}; bool prof_open = false;
-    // dril_evaluate_agent_device: where the env side is set aside for the call, the per-env running sums, the event list and its counter (pinned host word for the poll)
-    DevBuf<char> eval_snap; DevBuf<float> eval_cur_ret; DevBuf<int32_t> eval_cur_len;
-    DevBuf<unsigned int> eval_counter; PinnedBuf<unsigned int> eval_counter_host; DevBuf<SacEvalEvent> eval_events;
-    // dril_collect_trajectory_device: ONE grow-only blob for the step-major recording, the shadow envs' arrays and the table of bounds (the counter and its pinned word are the evaluation's)
-    DevBuf<char> traj_blob;
-    // path 2 of both verbs (a plug-in's fused evaluation kernel): ONE grow-only blob for the observation and action scratch, the K rows of rewards and flag bytes and,
-    // when recording, the rows of raw actions and post-step observations
-    DevBuf<char> evalf_blob;
-    std::string err;
-};
+using namespace dril::ppo;
 
 namespace {
-
-int fail(dril_handle* h, int code, const std::string& msg) { if (h) h->err = msg; else g_create_error = msg; return code; }
-#define HIPCHK(h, expr)                                                                                      \
-    do { hipError_t _e = (expr); if (_e != hipSuccess)                                                       \
-        return fail(h, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
-// every entry point makes the handle's device current first: a process may hold handles on several devices
-#define NEED(h) do { if (!(h)) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle"); (void)hipSetDevice((h)->cfg.device); } while (0)
-
 
 // cfg.profile_events = k >= 1: the per-iteration classes (rollout, GAE, pack, moments, explained variance) are bracketed at every launch; the classes launched once per
 // OPTIMISER STEP (gradient, reduce, Adam, all-reduce) at every k-th launch — a hipEventRecord costs the stream ~3.5 us and an iteration of configs[1] holds 960 such launches
 // (measured round 4, same box: 350.4 / 346.9 ms with all of them bracketed, 343.7 / 343.3 with none / every 8th; hipEventDisableSystemFence changes nothing)
 bool prof_per_step(int kid) { return kid == DRIL_K_PPO_GRAD || kid == DRIL_K_GRAD_REDUCE || kid == DRIL_K_ADAM || kid == DRIL_K_ALLREDUCE; }
+void prof_resolve(dril_handle* h) {   // stream must be drained
+    for (auto& p : h->prof_pending) {
+        float ms = 0; if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { h->prof_ms[p.kid] += ms; h->prof_n[p.kid] += 1; }
+        h->prof_pool.push_back({p.a, p.b});
+    }
+    h->prof_pending.clear();
+}
+
+// wide nets: (re)build the pre-tiled W2 / W2' images after every parameter change (enqueued on the handle's stream)
+int ensure_wimg(dril_handle* h) {
+    if (!h->wide || !h->wimg_dirty) return DRIL_OK;
+    HIPCHK(h, launch_build_wimg(h->params, h->actor, h->cfg.hidden1, h->w2a_actor, h->w2ta_actor, h->stream));
+    HIPCHK(h, launch_build_wimg(h->params, h->critic, h->cfg.hidden1, h->w2a_critic, h->w2ta_critic, h->stream));
+    {                                             // the pre-split f16 fragment streams: ppo_grad_wide_split_kernel, and the forward of rollout / policy kernels
+        HIPCHK(h, launch_build_wimg_split(h->params, h->actor, h->cfg.hidden1, h->w2p_actor, h->w2tp_actor, h->w2pf_actor, h->stream));
+        HIPCHK(h, launch_build_wimg_split(h->params, h->critic, h->cfg.hidden1, h->w2p_critic, h->w2tp_critic, h->w2pf_critic, h->stream));
+    }
+    h->wimg_dirty = false;
+    return DRIL_OK;
+}
+
+// ---- MonitorWrapperEnv helpers ----
+MonitorArgs monitor_step_args(dril_handle* h) {   // one env step: finished episodes land in the E-sized step arrays
+    MonitorArgs m{}; if (h->mon_cur_ret) { m.cur_ret = h->mon_cur_ret; m.cur_len = h->mon_cur_len; m.ep_ret = h->e_ep_ret; m.ep_len = h->e_ep_len; m.flags_out = h->e_flags; }
+    return m;
+}
+int monitor_collect_step(dril_handle* h) {
+    if (!h->mon_cur_ret) return DRIL_OK;
+    HIPCHK(h, launch_monitor_collect(h->e_flags, h->e_ep_ret, h->e_ep_len, h->cfg.n_envs, 1, h->cfg.monitor_window, h->mon_cnt, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->stream));
+    return DRIL_OK;
+}
+}  // namespace
+
+namespace dril::ppo {
+// ---- what dril_comm.hip and dril_wrap.hip call (dril_handle.h) ----
+thread_local std::string g_create_error;
+
 void prof_begin(dril_handle* h, int kid) {
     h->prof_open = false;
     if (!h->cfg.profile_events) return;
@@ -213,90 +81,7 @@ void prof_end(dril_handle* h) {
     hipEventRecord(h->prof_pending.back().b, h->stream);
     h->prof_open = false;
 }
-void prof_resolve(dril_handle* h) {   // stream must be drained
-    for (auto& p : h->prof_pending) {
-        float ms = 0; if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { h->prof_ms[p.kid] += ms; h->prof_n[p.kid] += 1; }
-        h->prof_pool.push_back({p.a, p.b});
-    }
-    h->prof_pending.clear();
-}
 int sync(dril_handle* h) { HIPCHK(h, hipStreamSynchronize(h->stream)); prof_resolve(h); return DRIL_OK; }
-
-bool comm_ready(const dril_handle* h) { return h->comm != nullptr || h->loop != nullptr; }
-
-// the loopback transport of one all-reduce (see LoopGroup): called by every rank's host thread with the same count / dtype
-int loop_allreduce(dril_handle* h, void* buf, size_t count, int dtype) {
-    LoopGroup* g = h->loop; const int r = h->cfg.rank;
-    HIPCHK(h, hipEventRecord(g->ready[r], h->stream));                 // this rank's contribution is complete behind this event
-    std::unique_lock<std::mutex> lk(g->mu);
-    if (g->failed) return fail(h, DRIL_ERR_RCCL, "loopback communicator: an earlier all-reduce failed");
-    const uint64_t my_gen = g->gen;
-    if (g->arrived == 0) { g->count = count; g->dtype = dtype; g->mismatch = false; }
-    else if (g->count != count || g->dtype != dtype) g->mismatch = true;
-    g->bufs.p[r] = buf;
-    if (++g->arrived == g->n) {
-        hipError_t e = hipSuccess;
-        for (int q = 0; q < g->n && e == hipSuccess; ++q) e = hipStreamWaitEvent(h->stream, g->ready[q], 0);
-        if (e == hipSuccess && !g->mismatch) {
-            const unsigned nb = (unsigned)((count + 255) / 256);
-            if (dtype == kNcclFloat64) loop_allreduce_kernel<double><<<nb, 256, 0, h->stream>>>(g->bufs, g->n, count);
-            else loop_allreduce_kernel<float><<<nb, 256, 0, h->stream>>>(g->bufs, g->n, count);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(g->done, h->stream);
-        if (e != hipSuccess || g->mismatch) g->failed = true;
-        g->arrived = 0; g->gen += 1; g->calls += 1;
-        g->cv.notify_all();
-        if (e != hipSuccess) return fail(h, DRIL_ERR_HIP, std::string("loopback all-reduce: ") + hipGetErrorString(e));
-    } else {
-        if (!g->cv.wait_for(lk, std::chrono::seconds(120), [&] { return g->gen != my_gen; })) {
-            g->failed = true; g->arrived = 0; g->gen += 1; g->cv.notify_all();
-            return fail(h, DRIL_ERR_RCCL, "loopback all-reduce: the other ranks did not arrive within 120 s (every handle of the group needs its own host thread making the same calls)");
-        }
-        if (!g->failed) HIPCHK(h, hipStreamWaitEvent(h->stream, g->done, 0));
-    }
-    if (g->failed) return fail(h, DRIL_ERR_RCCL, g->mismatch ? "loopback all-reduce: the ranks disagree on count / dtype (they are not making the same calls)" : "loopback all-reduce failed on another rank");
-    return DRIL_OK;
-}
-
-int rccl_allreduce(dril_handle* h, void* buf, size_t count, int dtype) {
-    if (!comm_ready(h)) return DRIL_OK;
-    h->allreduce_calls += 1;
-    prof_begin(h, DRIL_K_ALLREDUCE);
-    int rc = 0;
-    if (h->loop) { const int lrc = loop_allreduce(h, buf, count, dtype); prof_end(h); return lrc; }
-    rc = g_rccl.AllReduce(buf, buf, count, dtype, kNcclSum, h->comm, h->stream);
-    prof_end(h);
-    if (rc != 0) return fail(h, DRIL_ERR_RCCL, rccl_error("ncclAllReduce", rc, h->comm) + "; " + h->device_info);
-    return DRIL_OK;
-}
-
-bool normalizing(const dril_handle* h) { return h->cfg.norm_obs || h->cfg.norm_reward; }
-size_t act_bytes_per(const dril_handle* h) { return h->discrete ? 4 : 4 * (size_t)h->A; }
-
-// wide nets: (re)build the pre-tiled W2 / W2' images after every parameter change (enqueued on the handle's stream)
-// wide nets: 1 = ppo_grad_wide_split_kernel (bf16 matrix cores), 0 = the f32-MFMA ppo_grad_wide_kernel (DRIL_GRAD_VARIANT; records are needed by the split form)
-// default by measurement (profiles/r02_wide_split.md): the split form for both wide widths (hidden 256: 176-183 vs 118 TFLOP/s; hidden 128: 151 vs 113.5)
-int wide_variant(const dril_handle* h) { return (h->wide && h->rec && (h->grad_variant < 0 ? 1 : h->grad_variant)) ? 1 : 0; }
-// hidden [64,64]: may ppo_grad_pair_kernel run at all (it reads packed records; DRIL_GRAD_VARIANT=0 pins the exact-f32 kernel)
-// minibatches of at least this many 32-sample tiles per CU run ppo_grad_pair_kernel (measured on the f16 arithmetic, 256 CUs: 65 536 samples 50.7 us against 64.8 us on the
-// exact-f32 kernel, 16 384 samples 42.2 against 39.0; with the bf16 x 3 arithmetic of rounds 2 - 3 the crossover was at 16 tiles per CU)
-constexpr int kPairTilesPerCu = 8;
-bool pair_variant(const dril_handle* h) { return !h->wide && !h->generic && h->cfg.hidden1 == 64 && h->grad_variant != 0 && h->rec && h->D <= 8; }   // (D > 4, Acrobot: dW1 / db1 through a third piece image on the matrix cores — 16 (D + 1) per-lane accumulators would not fit)
-// the forward of the fused rollout / policy kernels: f16 two-piece W2 while every W2 entry is inside f16's range, else (or with DRIL_GRAD_VARIANT=0: "exact f32 everywhere") the f32-MFMA instantiations
-bool fwd_exact(const dril_handle* h) { return h->grad_variant == 0 || h->cfg.hidden1 == 32 || !(h->w2max < kFwdSplitMaxW); }   // (hidden 32 has no f16-piece instantiation)
-constexpr int kRetryLatchAfter = 2, kRetryLatchUpdates = 16;
-int ensure_wimg(dril_handle* h) {
-    if (!h->wide || !h->wimg_dirty) return DRIL_OK;
-    HIPCHK(h, launch_build_wimg(h->params, h->actor, h->cfg.hidden1, h->w2a_actor, h->w2ta_actor, h->stream));
-    HIPCHK(h, launch_build_wimg(h->params, h->critic, h->cfg.hidden1, h->w2a_critic, h->w2ta_critic, h->stream));
-    {                                             // the pre-split f16 fragment streams: ppo_grad_wide_split_kernel, and the forward of rollout / policy kernels
-        HIPCHK(h, launch_build_wimg_split(h->params, h->actor, h->cfg.hidden1, h->w2p_actor, h->w2tp_actor, h->w2pf_actor, h->stream));
-        HIPCHK(h, launch_build_wimg_split(h->params, h->critic, h->cfg.hidden1, h->w2p_critic, h->w2tp_critic, h->w2pf_critic, h->stream));
-    }
-    h->wimg_dirty = false;
-    return DRIL_OK;
-}
 
 // fused per-kind kernels for the device envs, the layer-by-layer generic path for DRIL_ENV_EXTERNAL
 hipError_t run_policy(dril_handle* h, const PolicyArgs& a) {
@@ -311,7 +96,6 @@ hipError_t run_policy(dril_handle* h, const PolicyArgs& a) {
     PolicyArgs q = a; q.boot_obs = nullptr; q.boot_where = nullptr; q.boot_out = nullptr;
     return generic_policy(h->gd, q, h->gws, h->stream);
 }
-#define NOT_EXTERNAL(h, what) do { if ((h)->external) return fail(h, DRIL_ERR_UNSUPPORTED, what ": the envs of DRIL_ENV_EXTERNAL live on the host (use dril_ext_act / dril_ext_record / dril_ext_finish)"); } while (0)
 
 PolicyArgs policy_args(dril_handle* h, const float* obs, int64_t B, const void* noise, void* actions, float* values, float* logp,
                        float* entropy, int mode) {
@@ -324,19 +108,9 @@ PolicyArgs policy_args(dril_handle* h, const float* obs, int64_t B, const void* 
     return a;
 }
 
-// ---- MonitorWrapperEnv helpers ----
-MonitorArgs monitor_step_args(dril_handle* h) {   // one env step: finished episodes land in the E-sized step arrays
-    MonitorArgs m{}; if (h->mon_cur_ret) { m.cur_ret = h->mon_cur_ret; m.cur_len = h->mon_cur_len; m.ep_ret = h->e_ep_ret; m.ep_len = h->e_ep_len; m.flags_out = h->e_flags; }
-    return m;
-}
 MonitorArgs monitor_rollout_args(dril_handle* h, size_t k) {   // row k / E of a step-granular rollout over a plug-in: the BUF_FLAGS byte always, finished episodes with the monitor on
     MonitorArgs m{}; m.flags_out = h->flags + k; if (h->mon_cur_ret) { m.cur_ret = h->mon_cur_ret; m.cur_len = h->mon_cur_len; m.ep_ret = h->ep_ret + k; m.ep_len = h->ep_len + k; }
     return m;
-}
-int monitor_collect_step(dril_handle* h) {
-    if (!h->mon_cur_ret) return DRIL_OK;
-    HIPCHK(h, launch_monitor_collect(h->e_flags, h->e_ep_ret, h->e_ep_len, h->cfg.n_envs, 1, h->cfg.monitor_window, h->mon_cnt, h->mon_ring_ret, h->mon_ring_len, h->mon_meta, h->stream));
-    return DRIL_OK;
 }
 int monitor_collect_rollout(dril_handle* h) {
     if (!h->mon_cur_ret) return DRIL_OK;
@@ -349,8 +123,9 @@ int env_step_arrays(dril_handle* h, const void* actions) {
     HIPCHK(h, h->env.step(actions, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, nullptr}, monitor_step_args(h), h->stream));
     return monitor_collect_step(h);
 }
-#define NOT_MODULE(h, what) do { if ((h)->env.module) return fail(h, DRIL_ERR_UNSUPPORTED, what ": NormalizeWrapperEnv is off on this device env plug-in handle (DRIL_ENV_MODULE): switch it on with dril_normalize_enable, then this verb forwards to dril_normalize_*"); } while (0)
+}  // namespace dril::ppo
 
+namespace {
 // data-parallel runs: NormalizeWrapperEnv's batch moments cover every env of the job (the reference has ONE vector env, normalizeWrapperEnv.jl:21-26):
 // this rank's partial table is folded to one row, RCCL sums the rows, and the apply kernels merge that row with n_stats = world * E.  One 128-byte
 // all-reduce per env step; every rank applies the identical update, so the running statistics stay bit-identical across ranks
@@ -362,61 +137,6 @@ int global_partials(dril_handle* h, bool update, const double*& partials, int& n
     int rc = rccl_allreduce(h, h->rms_red, 16, kNcclFloat64); if (rc) return rc;
     partials = h->rms_red; nb = 1; n_stats = (long long)h->cfg.n_envs * world;
     return DRIL_OK;
-}
-
-// ---- NormalizeWrapperEnv around a device env plug-in (dril_normalize_enable) ----
-#include "dril_ppo_norm.h"
-void pn_free(dril_handle* h) { h->pn.release(); h->pn_red.release(); }
-// norm_moments_kernel over e_obs_raw (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
-int pn_moments(dril_handle* h, bool obs, bool ret, int* rows) {
-    const int E = h->cfg.n_envs, D = h->D;
-    *rows = pn_rows(E, D, h->pn_rows_cap);
-    const int R = (E + *rows - 1) / *rows;
-    *rows = (E + R - 1) / R;
-    const NormMomArgs m{E, D, R, obs ? h->e_obs_raw : nullptr, ret ? h->e_rew : nullptr, h->env.disc_returns, h->pn.cfg.gamma, h->pn.partials};
-    hipLaunchKernelGGL(norm_moments_kernel<kPnTile>, dim3(*rows, obs ? pn_tiles(D) : 1), dim3(256), 0, h->stream, m);
-    HIPCHK(h, hipGetLastError());
-    return DRIL_OK;
-}
-// ppo_norm_apply_kernel.  Data-parallel jobs: the batch moments cover every env of the job (global_partials does the same for the built-in envs' 16 columns) — this
-// rank's table folded to one row of 2 D + 2 doubles, ONE all-reduce of that row, and every rank applies the identical merge with n = world * E, so the statistics
-// stay bit-identical across ranks
-int pn_apply(dril_handle* h, PnApplyArgs p, int rows, bool upd_obs, bool upd_ret) {
-    NormWrapArgs& a = p.w;
-    const int E = h->cfg.n_envs, D = h->D, C = 2 * D + 2;
-    const int world = comm_ready(h) ? h->cfg.world_size : 1;
-    h->pn.fill(a, upd_obs, upd_ret, E);
-    a.E = E; a.rows = rows;
-    if ((upd_obs || upd_ret) && (world > 1 || (comm_ready(h) && h->force_allreduce))) {
-        hipLaunchKernelGGL(ppo_norm_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, h->stream, h->pn.partials, rows, C, h->pn_red);
-        HIPCHK(h, hipGetLastError());
-        int rc = rccl_allreduce(h, h->pn_red, (size_t)C, kNcclFloat64); if (rc) return rc;
-        a.partials = h->pn_red; a.rows = 1; a.n = (long long)E * world;
-    }
-    const int W = D > kPnTile ? kPnTile : D;
-    a.epb = std::max(std::max(1, 4096 / W), (E + 255) / 256);
-    hipLaunchKernelGGL(ppo_norm_apply_kernel, dim3((E + a.epb - 1) / a.epb, pn_tiles(D)), dim3(256), 0, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    h->pn.commit(a);
-    return DRIL_OK;
-}
-// observe(env) of the wrapper (:123-137): the plug-in's observe kernel into e_obs_raw, then moments + apply into e_obs
-int pn_observe(dril_handle* h, bool update_stats) {
-    HIPCHK(h, h->env.observe(h->e_obs_raw, h->stream));
-    const bool upd = update_stats && h->pn.cfg.training && h->pn.cfg.norm_obs;
-    int rows = 0;
-    if (upd) { int rc = pn_moments(h, true, false, &rows); if (rc) return rc; }
-    PnApplyArgs a{}; a.w.raw = h->e_obs_raw; a.w.obs_out = h->e_obs;
-    return pn_apply(h, a, rows, upd, false);
-}
-// act!(env, actions) of the wrapper (:139-165) through the E-sized per-step arrays: raw rewards stay in e_rew, the delivered ones go to rew_out
-int pn_step(dril_handle* h, const void* actions, float* rew_out) {
-    { int rcs = env_step_arrays(h, actions); if (rcs) return rcs; }                // (MonitorWrapperEnv sits inside: raw rewards)
-    const bool upd = h->pn.cfg.training && h->pn.cfg.norm_reward;
-    int rows = 0;
-    if (upd) { int rc = pn_moments(h, false, true, &rows); if (rc) return rc; }
-    PnApplyArgs a{}; a.w.rew = h->e_rew; a.rew_out = rew_out; a.w.returns = h->env.disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
-    return pn_apply(h, a, rows, false, upd);
 }
 
 // ---- step-granular env verbs on device (NormalizeWrapperEnv.observe / act!, normalizeWrapperEnv.jl:123-165) ----
@@ -617,24 +337,6 @@ DRIL_EXPORT int32_t dril_config_default(dril_config* c, int32_t env_kind) {
     return DRIL_OK;
 }
 
-namespace {
-int create_impl(const dril_config* cfg, const char* module_path, dril_handle** out);
-std::string fused_rollout_unavailable(const dril_handle* h);
-std::string fused_evaluate_unavailable(const dril_handle* h);
-}  // namespace
-
-DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
-    if (cfg && cfg->abi_version == DRIL_ABI_VERSION && cfg->env_kind == DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_MODULE needs a code object: use dril_create_with_env_module(cfg, code_object_path, out)");
-    return create_impl(cfg, nullptr, out);
-}
-DRIL_EXPORT int32_t dril_create_with_env_module(const dril_config* cfg, const char* code_object_path, dril_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "null cfg/out");
-    if (cfg->abi_version != DRIL_ABI_VERSION) return fail(nullptr, DRIL_ERR_INVALID_ARG, "abi_version mismatch");
-    if (cfg->env_kind != DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_create_with_env_module: cfg->env_kind must be DRIL_ENV_MODULE");
-    std::string msg; const int rc = check_code_object_path(code_object_path, msg);
-    if (rc) return fail(nullptr, rc, "dril_create_with_env_module: " + msg);
-    return create_impl(cfg, code_object_path, out);
-}
 DRIL_EXPORT int32_t dril_env_module_describe(const char* code_object_path, int32_t device, dril_env_module_info* out) {
     if (!out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_env_module_describe: null out");
     hipModule_t mod = nullptr; DrilEnvPluginDesc d{}; std::string msg;
@@ -683,36 +385,6 @@ DRIL_EXPORT int32_t dril_scaling_enable(dril_handle* h, int32_t on) {
     std::string msg; const int rc = h->env.set_scaling(on != 0, msg);
     return rc ? fail(h, rc, "dril_scaling_enable: " + msg) : DRIL_OK;
 }
-DRIL_EXPORT int32_t dril_rollout_fused_enable(dril_handle* h, int32_t on) {
-    NEED(h);
-    if (on) {
-        std::string why = fused_rollout_unavailable(h);
-        if (why.empty() && h->pn.on) why = "NormalizeWrapperEnv is on (dril_normalize_enable): its running statistics couple all envs at every step, which is what a workgroup per tile of envs gives up; collect step-granular, or switch the wrapper off with dril_normalize_enable(h, NULL) first";
-        if (!why.empty()) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_rollout_fused_enable: " + why);
-    }
-    h->fused_rollout = on != 0;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rollout_info* out) {
-    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_rollout_fused_info: null out pointer");
-    std::memset(out, 0, sizeof(*out));
-    const std::string why = fused_rollout_unavailable(h);
-    out->available = why.empty() ? 1 : 0; out->enabled = h->fused_rollout ? 1 : 0; out->last_collection_launches = h->rollout_launches;
-    if (h->env.module && h->env.rollout.has_desc) { out->tile = h->env.rollout.desc.tile; out->threads = h->env.rollout.desc.threads; out->max_width = h->env.rollout.desc.max_width; }
-    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_evaluate_fused_info(const dril_handle* h, dril_fused_evaluate_info* out) {
-    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_evaluate_fused_info: null out pointer");
-    std::memset(out, 0, sizeof(*out));
-    const std::string why = fused_evaluate_unavailable(h);
-    out->available = why.empty() ? 1 : 0;
-    if (h->env.module && h->env.evaluate.has_desc) { out->tile = h->env.evaluate.desc.tile; out->threads = h->env.evaluate.desc.threads; out->max_width = h->env.evaluate.desc.max_width; }
-    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
-    return DRIL_OK;
-}
 DRIL_EXPORT int32_t dril_agent_spaces(const dril_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling) {
     if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
     if (!h->env.module) return fail(const_cast<dril_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_agent_spaces: the handle was not created with dril_create_with_env_module");
@@ -723,6 +395,7 @@ DRIL_EXPORT int32_t dril_agent_spaces(const dril_handle* h, float* obs_low, floa
 }
 
 namespace {
+#define CCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(_e); dril_destroy(h); return fail(nullptr, DRIL_ERR_HIP, m); } } while (0)
 int create_impl(const dril_config* cfg, const char* module_path, dril_handle** out) {
     if (!cfg || !out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "null cfg/out");
     if (cfg->abi_version != DRIL_ABI_VERSION) return fail(nullptr, DRIL_ERR_INVALID_ARG, "abi_version mismatch");
@@ -782,7 +455,6 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     if (const char* e = debug_env("DRIL_SMALL_CHUNK")) { const long c = std::atol(e); if (c > 0) h->small_chunk = c; }   // optimiser steps per launch of ppo_update_small_kernel (tests: launch boundaries)
     h->no_small_path = debug_env("DRIL_NO_SMALL_PATH") != nullptr;
     h->no_f32_retry = std::getenv("DRIL_NO_F32_RETRY") != nullptr;
-#define CCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(_e); dril_destroy(h); return fail(nullptr, DRIL_ERR_HIP, m); } } while (0)
     CCHK(hipSetDevice(cfg->device));
     hipDeviceProp_t prop; CCHK(hipGetDeviceProperties(&prop, cfg->device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) { std::string m = std::string("libdril_hip targets gfx950 (MI355X) only; device is ") + prop.gcnArchName; dril_destroy(h); return fail(nullptr, DRIL_ERR_UNSUPPORTED, m); }
@@ -845,26 +517,32 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     CCHK(hipMemsetAsync(h->stop_flag, 0, 4, h->stream)); CCHK(hipMemsetAsync(h->nan_flag, 0, 4, h->stream));
     CCHK(hipMemsetAsync(h->e_tobs, 0, E * h->D * 4, h->stream));
     if (!h->discrete) { std::vector<float> ls(h->A, cfg->log_std_init); CCHK(hipMemcpyAsync(h->params + h->log_std_off, ls.data(), 4 * h->A, hipMemcpyHostToDevice, h->stream)); CCHK(hipStreamSynchronize(h->stream)); }
-#undef CCHK
     int rc = reset_optimizer(h);
     if (rc) { std::string m = h->err; dril_destroy(h); return fail(nullptr, rc, m); }
     *out = h;
     return DRIL_OK;
 }
+#undef CCHK
 }  // namespace
+DRIL_EXPORT int32_t dril_create(const dril_config* cfg, dril_handle** out) {
+    if (cfg && cfg->abi_version == DRIL_ABI_VERSION && cfg->env_kind == DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "DRIL_ENV_MODULE needs a code object: use dril_create_with_env_module(cfg, code_object_path, out)");
+    return create_impl(cfg, nullptr, out);
+}
+DRIL_EXPORT int32_t dril_create_with_env_module(const dril_config* cfg, const char* code_object_path, dril_handle** out) {
+    if (!cfg || !out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "null cfg/out");
+    if (cfg->abi_version != DRIL_ABI_VERSION) return fail(nullptr, DRIL_ERR_INVALID_ARG, "abi_version mismatch");
+    if (cfg->env_kind != DRIL_ENV_MODULE) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_create_with_env_module: cfg->env_kind must be DRIL_ENV_MODULE");
+    std::string msg; const int rc = check_code_object_path(code_object_path, msg);
+    if (rc) return fail(nullptr, rc, "dril_create_with_env_module: " + msg);
+    return create_impl(cfg, code_object_path, out);
+}
 
 DRIL_EXPORT int32_t dril_destroy(dril_handle* h) {
     if (h) (void)hipSetDevice(h->cfg.device);
     if (!h) return DRIL_OK;
     if (h->pop) { h->err = "dril_destroy: the handle is a member of a population: dril_population_destroy first (the members stay alive and usable)"; return DRIL_ERR_INVALID_ARG; }
     if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-    if (h->loop) {                                                   // the last handle to leave frees the group
-        LoopGroup* g = h->loop; bool last;
-        { std::lock_guard<std::mutex> lk(g->mu); last = --g->refs == 0; }
-        if (last) { for (int q = 0; q < g->n; ++q) if (g->ready[q]) hipEventDestroy(g->ready[q]); if (g->done) hipEventDestroy(g->done); delete g; }
-        h->loop = nullptr;
-    }
+    comm_release(h);
     h->env.release();
     if (h->ext_ev_in) (void)hipEventDestroy(h->ext_ev_in); if (h->ext_ev_out) (void)hipEventDestroy(h->ext_ev_out);
     for (auto& p : h->prof_pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -1007,129 +685,6 @@ DRIL_EXPORT int32_t dril_norm_get_original(dril_handle* h, float* obs, float* re
     return sync(h);
 }
 
-// ---- NormalizeWrapperEnv around a device env plug-in (rules and state: dril_norm_wrap.h) ------------------------------------------------------------------------------------
-namespace {
-int pn_kind_check(dril_handle* h, const char* what) {
-    if (h->external) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there (envs whose arrays live on the device: dril_ext_normalize_enable, honoured by the dril_ext_*_device verbs)");
-    if (!h->env.module) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": this verb family wraps a device env plug-in (DRIL_ENV_MODULE); a built-in env is wrapped at create with cfg.norm_obs / cfg.norm_reward (dril_norm_get_stats / dril_norm_set_stats / dril_norm_get_original)");
-    return DRIL_OK;
-}
-#define PN_ON(h, what) do { int _rc = pn_kind_check(h, what); if (_rc) return _rc; \
-    if (!(h)->pn.on) return fail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_normalize_enable has not been called with a configuration)"); } while (0)
-// the bodies of the verbs that read or write a wrapper that is on: one definition for dril_normalize_* (plug-in handles) and dril_ext_normalize_* (external handles)
-int pn_get_config(dril_handle* h, const char* verb, dril_normalize_config* cfg) {
-    if (!cfg) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": null out pointer");
-    *cfg = h->pn.cfg;
-    return DRIL_OK;
-}
-int pn_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
-    std::vector<float> st(h->pn.stats_floats());
-    HIPCHK(h, hipMemcpyAsync(st.data(), h->pn.half(h->pn.cur), st.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    int rc = sync(h); if (rc) return rc;
-    h->pn.unpack(st, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-    return DRIL_OK;
-}
-int pn_set_stats(dril_handle* h, const char* verb, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
-    if (const NormErr err = norm_set_stats_check(obs_mean, obs_var, obs_count, ret_count)) return fail(h, err.code, std::string(verb) + ": " + err.msg);
-    const std::vector<float> st = h->pn.pack(obs_mean, obs_var, ret_mean, ret_var);
-    HIPCHK(h, hipMemcpyAsync(h->pn.half(h->pn.cur), st.data(), st.size() * 4, hipMemcpyHostToDevice, h->stream));
-    int rc = sync(h); if (rc) return rc;
-    h->pn.obs_count = obs_count; h->pn.ret_count = ret_count;
-    return DRIL_OK;
-}
-int pn_get_original(dril_handle* h, const char* verb, float* obs, float* rewards) {
-    if (!obs && !rewards) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": both out pointers are null");
-    if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->e_obs_raw, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost, h->stream));
-    if (rewards) HIPCHK(h, hipMemcpyAsync(rewards, h->e_rew, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
-    return sync(h);
-}
-int pn_get_returns(dril_handle* h, const char* verb, float* returns) {
-    if (!returns) return fail(h, DRIL_ERR_INVALID_ARG, std::string(verb) + ": null out pointer");
-    HIPCHK(h, hipMemcpyAsync(returns, h->env.disc_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost, h->stream));
-    return sync(h);
-}
-}  // namespace
-DRIL_EXPORT int32_t dril_normalize_config_default(dril_normalize_config* c) {
-    if (!c) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_normalize_config_default: null configuration");
-    norm_config_default(c);
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_normalize_enable(dril_handle* h, const dril_normalize_config* cfg) {
-    NEED(h);
-    { int rc = pn_kind_check(h, "dril_normalize_enable"); if (rc) return rc; }
-    if (!cfg) {                                                                        // the wrapper off: the handle enqueues the launches of a handle that never had it
-        if (!h->pn.on) return DRIL_OK;
-        int rc = sync(h); if (rc) return rc;
-        pn_free(h);
-        return DRIL_OK;
-    }
-    if (h->fused_rollout) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_normalize_enable: the fused rollout is on, and a workgroup per tile of envs cannot keep statistics that couple all envs at every step: switch it off with dril_rollout_fused_enable(h, 0) first");
-    if (const NormErr err = norm_config_check(*cfg, h->D)) return fail(h, err.code, "dril_normalize_enable: " + err.msg);
-    const dril_normalize_config c = norm_config_canonical(*cfg);
-    if (h->pn.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart): its statistics and returns stay
-    { int rc = sync(h); if (rc) return rc; }
-    pn_free(h);
-    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D, Cn = 2 * D + 2;
-    h->pn_rows_cap = 0;
-    if (const char* e = debug_env("DRIL_NORM_ROWS")) { const int r = std::atoi(e); if (r > 0) h->pn_rows_cap = r; }   // measurements: fewer rows in the partial table
-    hipError_t e = h->pn.alloc((int)D, (size_t)pn_rows((int)E, (int)D, h->pn_rows_cap));
-    if (e == hipSuccess) e = h->pn_red.alloc(Cn);
-    if (e == hipSuccess) e = hipMemset(h->pn_red, 0, Cn * 8);
-    if (e == hipSuccess) e = hipMemset(h->env.disc_returns, 0, E * 4);                     // returns, and the cached originals, start at 0
-    if (e == hipSuccess) e = hipMemset(h->e_obs_raw, 0, E * D * 4);
-    if (e == hipSuccess) e = hipMemset(h->e_rew, 0, E * 4);
-    if (e != hipSuccess) { pn_free(h); return fail(h, DRIL_ERR_HIP, std::string("dril_normalize_enable: ") + hipGetErrorString(e)); }
-    h->pn.cfg = c; h->pn.on = true;
-    if (h->env.ready) HIPCHK(h, h->env.observe(h->e_obs_raw, h->stream));                    // old_obs of the envs' present state, as reset! would have stored it
-    return sync(h);
-}
-DRIL_EXPORT int32_t dril_normalize_set_training(dril_handle* h, int32_t training) {
-    NEED(h); PN_ON(h, "dril_normalize_set_training");
-    h->pn.cfg.training = training != 0;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_normalize_get_config(dril_handle* h, dril_normalize_config* cfg) {
-    NEED(h); PN_ON(h, "dril_normalize_get_config");
-    return pn_get_config(h, "dril_normalize_get_config", cfg);
-}
-DRIL_EXPORT int32_t dril_normalize_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
-    NEED(h); PN_ON(h, "dril_normalize_get_stats");
-    return pn_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-}
-DRIL_EXPORT int32_t dril_normalize_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
-    NEED(h); PN_ON(h, "dril_normalize_set_stats");
-    return pn_set_stats(h, "dril_normalize_set_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-}
-DRIL_EXPORT int32_t dril_normalize_get_original(dril_handle* h, float* obs, float* rewards) {
-    NEED(h); PN_ON(h, "dril_normalize_get_original");
-    return pn_get_original(h, "dril_normalize_get_original", obs, rewards);
-}
-DRIL_EXPORT int32_t dril_normalize_get_returns(dril_handle* h, float* returns) {
-    NEED(h); PN_ON(h, "dril_normalize_get_returns");
-    return pn_get_returns(h, "dril_normalize_get_returns", returns);
-}
-
-namespace { int monitor_window_stats(dril_handle* h, int W, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes); }
-DRIL_EXPORT int32_t dril_monitor_get_stats(dril_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
-    NEED(h);
-    if (!h->mon_cur_ret || h->external) return fail(h, DRIL_ERR_NOT_INITIALISED, "MonitorWrapperEnv is off (cfg.monitor_window == 0)");   // (an external handle's monitor: dril_ext_monitor_get_stats)
-    return monitor_window_stats(h, h->cfg.monitor_window, ep_rew_mean, ep_len_mean, n_episodes);
-}
-namespace {
-int monitor_window_stats(dril_handle* h, int W, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
-    std::vector<float> r(W); std::vector<int32_t> l(W); int meta[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(r.data(), h->mon_ring_ret, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(l.data(), h->mon_ring_len, (size_t)W * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(meta, h->mon_meta, 8, hipMemcpyDeviceToHost, h->stream));
-    int rc = sync(h); if (rc) return rc;
-    double sr = 0, sl = 0;
-    for (int i = 0; i < meta[0]; ++i) { sr += r[i]; sl += l[i]; }
-    if (n_episodes) *n_episodes = meta[0];
-    if (ep_rew_mean) *ep_rew_mean = meta[0] ? (float)(sr / meta[0]) : 0.f;      // log_stats: mean over the CircularBuffer, monitorWrapperEnv.jl:64-70
-    if (ep_len_mean) *ep_len_mean = meta[0] ? (float)(sl / meta[0]) : 0.f;
-    return DRIL_OK;
-}
-}  // namespace
 
 // ---- policy on host batches ----------------------------------------------------------------------
 namespace {
@@ -1279,9 +834,6 @@ int collect_rollout_module(dril_handle* h) {
     return monitor_collect_rollout(h);
 }
 
-// the same loop under dril_normalize_enable: the plug-in's step kernel writes raw reward, terminal observation and raw next observation into the per-step arrays, then
-// norm_moments_kernel (dril_norm_wrap.h) + ppo_norm_apply_kernel (dril_ppo_norm.h) put the normalised reward into row t and the normalised next observation where the policy reads it:
-// two launches more per env step than collect_rollout_module, and two for the opening observe.  V(terminal_observation) is V of the normalised terminal observation
 // the fused collection (dril_rollout_fused_enable): ONE launch of the plug-in's own rollout kernel (include/device/dril_env_rollout.h) does what the loop of
 // collect_rollout_module does in 6+ launches per env step, and leaves env state, counters, monitor sums and the per-step arrays as that loop leaves them
 int collect_rollout_module_fused(dril_handle* h) {
@@ -1323,32 +875,6 @@ std::string fused_evaluate_unavailable(const dril_handle* h) {
     for (int l = 0; l < h->gd.nh; ++l) if (h->gd.H[l] > W) return "hidden layer " + std::to_string(l + 1) + " is " + std::to_string(h->gd.H[l]) + " wide, the plug-in's fused evaluation was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->gd.H[l]) + " or more";
     if (h->env.scaling && !r.fn_scaled) return "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_evaluate_scaled kernel: rebuild it with this library's include/device/dril_env_evaluate.h";
     return "";
-}
-
-int collect_rollout_module_norm(dril_handle* h) {
-    const int E = h->cfg.n_envs, T = h->cfg.n_steps, D = h->D, A = h->A;
-    const size_t ab = act_bytes_per(h);
-    const bool upd_obs = h->pn.cfg.training && h->pn.cfg.norm_obs, upd_ret = h->pn.cfg.training && h->pn.cfg.norm_reward;
-    int rc = pn_observe(h, true); if (rc) return rc;                                       // new_obs = observe(env), trajectory.jl:32
-    h->rollout_launches += 3 + (int64_t)T * (2 + ((upd_obs || upd_ret) ? 1 : 0));          // observe + its wrapper; per step: the step kernel, the apply kernel, the moments
-    for (int t = 0; t < T; ++t) {
-        const size_t k = (size_t)t * E;
-        const void* nz = h->noise_set ? (const void*)((const char*)h->noise_dev + k * (h->discrete ? 8 : 4 * (size_t)A)) : nullptr;
-        PolicyArgs p = policy_args(h, h->e_obs, E, nz, (char*)h->act + k * ab, h->val + k, h->logp + k, nullptr, 0);
-        p.gstep = h->env.gstep; p.env_seed0 = h->env.seed0; p.obs_out = h->obs + k * D;
-        if (t > 0) { p.boot_obs = h->e_tobs; p.boot_where = h->e_trunc; p.boot_out = h->boot + (k - E); }   // :57-61 for step t-1
-        HIPCHK(h, run_policy(h, p));                                                       // get_action_and_values, :41
-        HIPCHK(h, h->env.step((const char*)h->act + k * ab, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->e_obs_raw}, monitor_rollout_args(h, k), h->stream));   // to_env + the env's own act! + raw observe
-        int rows = 0;
-        if (upd_obs || upd_ret) { rc = pn_moments(h, upd_obs, upd_ret, &rows); if (rc) return rc; }
-        PnApplyArgs a{}; a.w.raw = h->e_obs_raw; a.w.obs_out = h->e_obs;
-        a.w.rew = h->e_rew; a.rew_out = h->rew + k; a.w.returns = h->env.disc_returns; a.w.term = h->e_term; a.w.trunc = h->e_trunc; a.tobs = h->e_tobs;
-        rc = pn_apply(h, a, rows, upd_obs, upd_ret); if (rc) return rc;                    // the wrapper's act! :139-165 and observe :123-137
-    }
-    PolicyArgs l = policy_args(h, h->e_obs, E, nullptr, nullptr, h->last_values, nullptr, nullptr, 2);
-    l.boot_obs = h->e_tobs; l.boot_where = h->e_trunc; l.boot_out = h->boot + (size_t)(T - 1) * E;
-    HIPCHK(h, run_policy(h, l));                                                           // V(new_obs) for rollout-limited tails, :65-70
-    return monitor_collect_rollout(h);
 }
 
 // a collection that is ONE launch of the fused rollout kernel of a built-in kind (generic nets have no fused rollout kernel, wrapped envs step through the wrapper's kernels)
@@ -1401,6 +927,36 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
     return do_sync ? sync(h) : DRIL_OK;
 }
 }  // namespace
+DRIL_EXPORT int32_t dril_rollout_fused_enable(dril_handle* h, int32_t on) {
+    NEED(h);
+    if (on) {
+        std::string why = fused_rollout_unavailable(h);
+        if (why.empty() && h->pn.on) why = "NormalizeWrapperEnv is on (dril_normalize_enable): its running statistics couple all envs at every step, which is what a workgroup per tile of envs gives up; collect step-granular, or switch the wrapper off with dril_normalize_enable(h, NULL) first";
+        if (!why.empty()) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_rollout_fused_enable: " + why);
+    }
+    h->fused_rollout = on != 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rollout_info* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_rollout_fused_info: null out pointer");
+    std::memset(out, 0, sizeof(*out));
+    const std::string why = fused_rollout_unavailable(h);
+    out->available = why.empty() ? 1 : 0; out->enabled = h->fused_rollout ? 1 : 0; out->last_collection_launches = h->rollout_launches;
+    if (h->env.module && h->env.rollout.has_desc) { out->tile = h->env.rollout.desc.tile; out->threads = h->env.rollout.desc.threads; out->max_width = h->env.rollout.desc.max_width; }
+    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_evaluate_fused_info(const dril_handle* h, dril_fused_evaluate_info* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_evaluate_fused_info: null out pointer");
+    std::memset(out, 0, sizeof(*out));
+    const std::string why = fused_evaluate_unavailable(h);
+    out->available = why.empty() ? 1 : 0;
+    if (h->env.module && h->env.evaluate.has_desc) { out->tile = h->env.evaluate.desc.tile; out->threads = h->env.evaluate.desc.threads; out->max_width = h->env.evaluate.desc.max_width; }
+    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
+    return DRIL_OK;
+}
 namespace {
 // dril_ext_device_info counts per rollout: the first act of a rollout starts the counters again
 void ext_count_begin(dril_handle* h) { if (h->ext_t == 0) { h->ext_steps_dev = h->ext_steps_host = h->ext_syncs = 0; h->ext_launches = 0; h->xw_added[0] = h->xw_added[1] = h->xw_added[2] = 0; } }
@@ -1420,9 +976,13 @@ int ext_check_ptr(dril_handle* h, const char* verb, const char* name, const void
     const std::string msg = ext_ptr_problem(h->cfg.device, verb, name, p, bytes);         // dril_ext_stream.h: the rule the SAC handle's device verbs share
     return msg.empty() ? DRIL_OK : fail(h, DRIL_ERR_INVALID_ARG, msg);
 }
+}  // namespace
+namespace dril::ppo {
 // the handle's stream takes over from the caller's stream / hands back to it: two events per handle, no host wait
 int ext_stream_enter(dril_handle* h, void* caller_stream) { HIPCHK(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream)); return DRIL_OK; }
 int ext_stream_leave(dril_handle* h, void* caller_stream) { HIPCHK(h, ext_stream_give(h->stream, h->ext_ev_out, caller_stream)); return DRIL_OK; }
+}  // namespace dril::ppo
+namespace {
 // the adapter's table of a Box handle as the actions-out kernel takes it (null: Discrete, or nothing to clamp)
 const ExtBounds* ext_bounds_for(dril_handle* h, ExtBounds& scalar) {
     if (h->discrete) return nullptr;
@@ -1432,81 +992,9 @@ const ExtBounds* ext_bounds_for(dril_handle* h, ExtBounds& scalar) {
     return &scalar;
 }
 
-// ---- NormalizeWrapperEnv / MonitorWrapperEnv around the envs of an external handle (dril_ext_normalize_enable / dril_ext_monitor_enable) ----
-#include "dril_ext_norm.h"
+// a wrapper of dril_ext_normalize_enable / dril_ext_monitor_enable is on (dril_wrap.hip): the device verbs honour it, the host verbs refuse
 bool xw_on(const dril_handle* h) { return h->pn.on || h->ext_mon_window > 0; }
 #define XW_HOST_REFUSED(h, what) do { if (xw_on(h)) return fail(h, DRIL_ERR_UNSUPPORTED, what ": wrapper on: use the device verbs, or wrap the host env on the host (dril_ext_normalize_enable / dril_ext_monitor_enable are honoured by dril_ext_act_device / _record_device / _finish_device only)"); } while (0)
-// the apply grid of both kernels: env ranges x column tiles, as ppo_norm_apply_kernel's
-dim3 xn_grid(int E, int D, int* epb) {
-    const int W = D > kPnTile ? kPnTile : D;
-    *epb = std::max(std::max(1, 4096 / W), (E + 255) / 256);
-    return dim3((E + *epb - 1) / *epb, pn_tiles(D));
-}
-// norm_moments_kernel over the caller's observations (raw) or the `returns` recursion over the caller's rewards (rew), n_envs rows; *rows: the rows of the table it writes
-int xn_moments(dril_handle* h, const float* raw, const float* rew, int* rows) {
-    const int E = h->cfg.n_envs, D = h->D;
-    *rows = pn_rows(E, D, h->pn_rows_cap);
-    const int R = (E + *rows - 1) / *rows;
-    *rows = (E + R - 1) / R;
-    const NormMomArgs m{E, D, R, raw, rew, h->env.disc_returns, h->pn.cfg.gamma, h->pn.partials};
-    hipLaunchKernelGGL(norm_moments_kernel<kPnTile>, dim3(*rows, raw ? pn_tiles(D) : 1), dim3(256), 0, h->stream, m);
-    HIPCHK(h, hipGetLastError());
-    return DRIL_OK;
-}
-// observe (:123-137) of B rows of the caller's array into obs_out.  rollout: a verb of the collection (B == n_envs) — statistics updated where training && norm_obs,
-// old_obs cached; else the read-only pass of dril_predict_actions_device.  *added: the launches enqueued
-int xn_observe(dril_handle* h, const float* raw, int64_t B, float* obs_out, bool rollout, int64_t* added) {
-    const bool upd = rollout && h->pn.cfg.training && h->pn.cfg.norm_obs;
-    int rows = 0;
-    if (upd) { int rc = xn_moments(h, raw, nullptr, &rows); if (rc) return rc; *added += 1; }
-    XnObserveArgs p{}; NormWrapArgs& a = p.w;
-    h->pn.fill(a, upd, false, (long long)B);
-    a.E = (int)B; a.rows = rows; a.raw = raw; a.obs_out = obs_out; p.old_obs = rollout ? h->e_obs_raw : nullptr;
-    const dim3 grid = xn_grid(a.E, h->D, &a.epb);
-    hipLaunchKernelGGL(ext_norm_observe_kernel, grid, dim3(256), 0, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    h->pn.commit(a); *added += 1;
-    return DRIL_OK;
-}
-// act! (:139-165) with the record's own work and the monitor's sums, row k / E of the buffer.  tobs_norm: where the critic must read the terminal observations
-// (the scratch, or the caller's array with norm_obs == 0; null without terminal_obs)
-int xn_record(dril_handle* h, size_t k, const float* d_rewards, const uint8_t* d_terminated, const uint8_t* d_truncated, const float* d_terminal_obs, const float** tobs_norm, int64_t* launches) {
-    const int E = h->cfg.n_envs;
-    const bool upd = h->pn.on && h->pn.cfg.training && h->pn.cfg.norm_reward;
-    int rows = 0;
-    if (upd) { int rc = xn_moments(h, nullptr, d_rewards, &rows); if (rc) return rc; *launches += 1; }
-    XnRecordArgs p{}; NormWrapArgs& a = p.w;
-    if (h->pn.on) h->pn.fill(a, false, upd, E);
-    a.D = h->D; a.E = E; a.rows = rows; a.rew = d_rewards; a.term = d_terminated; a.trunc = d_truncated; a.returns = h->env.disc_returns;
-    p.has_norm = h->pn.on ? 1 : 0;
-    p.tobs = d_terminal_obs; p.tobs_out = (d_terminal_obs && h->pn.on && h->pn.cfg.norm_obs) ? h->e_tobs : nullptr;
-    *tobs_norm = p.tobs_out ? p.tobs_out : d_terminal_obs;
-    p.old_rew = h->e_rew; p.rew_out = h->rew + k; p.flags = h->flags + k; p.boot = h->boot + k; p.err = h->ext_err;
-    if (h->ext_mon_window > 0) { p.mon_cur_ret = h->mon_cur_ret; p.mon_cur_len = h->mon_cur_len; p.ep_ret = h->ep_ret + k; p.ep_len = h->ep_len + k; }
-    dim3 grid = xn_grid(E, h->D, &a.epb);
-    if (!p.tobs_out && !a.st_out) grid.y = 1;                                            // no column work and no statistics to carry: the per-env pass alone
-    hipLaunchKernelGGL(ext_norm_record_kernel, grid, dim3(256), 0, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    if (h->pn.on) h->pn.commit(a);
-    *launches += 1;
-    return DRIL_OK;
-}
-// the monitor's arrays of an external handle (those of cfg.monitor_window on a device env, sized by ext_mon_window)
-void xm_free(dril_handle* h) {
-    h->mon_cur_ret.release(); h->mon_cur_len.release(); h->ep_ret.release(); h->ep_len.release();
-    h->mon_ring_ret.release(); h->mon_ring_len.release(); h->mon_cnt.release(); h->mon_meta.release();
-    h->ext_mon_window = 0;
-}
-int xw_kind_check(dril_handle* h, const char* what) {
-    if (!h->external) return fail(h, DRIL_ERR_UNSUPPORTED, std::string(what) + ": the handle was not created with DRIL_ENV_EXTERNAL; a built-in env is wrapped at create (cfg.norm_obs / cfg.norm_reward / cfg.monitor_window), a device env plug-in with dril_normalize_enable");
-    return DRIL_OK;
-}
-int xw_between_rollouts(dril_handle* h, const char* what) {
-    if (h->ext_t != 0 || h->ext_acted) return fail(h, DRIL_ERR_INVALID_ARG, std::string(what) + ": a rollout is under way (dril_ext_steps != 0, or an act without its record): switch the wrapper between rollouts, after dril_ext_finish_device");
-    return DRIL_OK;
-}
-#define XN_ON(h, what) do { int _rc = xw_kind_check(h, what); if (_rc) return _rc; \
-    if (!(h)->pn.on) return fail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_ext_normalize_enable has not been called with a configuration)"); } while (0)
 }  // namespace
 // ---- collect_trajectories over HOST envs (DRIL_ENV_EXTERNAL), trajectory.jl:22-78: the caller steps its envs, the device does the rest ----
 DRIL_EXPORT int32_t dril_ext_act(dril_handle* h, const float* obs, void* raw_actions, void* env_actions) {
@@ -1739,106 +1227,6 @@ DRIL_EXPORT int32_t dril_ext_device_info(const dril_handle* h, struct dril_ext_d
     return DRIL_OK;
 }
 
-// ---- NormalizeWrapperEnv / MonitorWrapperEnv on an external handle (rules and state: dril_norm_wrap.h; kernels: dril_ext_norm.h) ----
-DRIL_EXPORT int32_t dril_ext_normalize_enable(dril_handle* h, const dril_normalize_config* cfg) {
-    NEED(h);
-    { int rc = xw_kind_check(h, "dril_ext_normalize_enable"); if (rc) return rc; }
-    if (h->cfg.world_size > 1) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_ext_normalize_enable: world_size > 1: the batch moments of a data-parallel job need an all-reduce per env step, which is not free of host waits here; run a single rank, or normalise in the env's own arrays");
-    { int rc = xw_between_rollouts(h, "dril_ext_normalize_enable"); if (rc) return rc; }
-    if (!cfg) {                                                                        // the wrapper off: the handle enqueues the launches of a handle that never had it
-        if (!h->pn.on) return DRIL_OK;
-        int rc = sync(h); if (rc) return rc;
-        pn_free(h);
-        return DRIL_OK;
-    }
-    if (const NormErr err = norm_config_check(*cfg, h->D)) return fail(h, err.code, "dril_ext_normalize_enable: " + err.msg);
-    const dril_normalize_config c = norm_config_canonical(*cfg);
-    if (h->pn.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart): its statistics and returns stay
-    { int rc = sync(h); if (rc) return rc; }
-    pn_free(h);
-    const size_t E = (size_t)h->cfg.n_envs, D = (size_t)h->D;
-    h->pn_rows_cap = 0;
-    hipError_t e = h->pn.alloc((int)D, (size_t)pn_rows((int)E, (int)D, h->pn_rows_cap));   // every array of the wrapper that create did not size: statistics and the partial table
-    if (e == hipSuccess) e = hipMemset(h->env.disc_returns, 0, E * 4);                     // returns, and the cached originals, start at 0
-    if (e == hipSuccess) e = hipMemset(h->e_obs_raw, 0, E * D * 4);
-    if (e == hipSuccess) e = hipMemset(h->e_rew, 0, E * 4);
-    if (e != hipSuccess) { pn_free(h); return fail(h, DRIL_ERR_HIP, std::string("dril_ext_normalize_enable: ") + hipGetErrorString(e)); }
-    h->pn.cfg = c; h->pn.on = true; h->xw_allocs = 0;
-    return sync(h);
-}
-DRIL_EXPORT int32_t dril_ext_normalize_set_training(dril_handle* h, int32_t training) {
-    NEED(h); XN_ON(h, "dril_ext_normalize_set_training");
-    h->pn.cfg.training = training != 0;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_ext_normalize_get_config(dril_handle* h, dril_normalize_config* cfg) {
-    NEED(h); XN_ON(h, "dril_ext_normalize_get_config");
-    return pn_get_config(h, "dril_ext_normalize_get_config", cfg);
-}
-DRIL_EXPORT int32_t dril_ext_normalize_get_stats(dril_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
-    NEED(h); XN_ON(h, "dril_ext_normalize_get_stats");
-    return pn_get_stats(h, obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-}
-DRIL_EXPORT int32_t dril_ext_normalize_set_stats(dril_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
-    NEED(h); XN_ON(h, "dril_ext_normalize_set_stats");
-    return pn_set_stats(h, "dril_ext_normalize_set_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-}
-DRIL_EXPORT int32_t dril_ext_normalize_get_original(dril_handle* h, float* obs, float* rewards) {
-    NEED(h); XN_ON(h, "dril_ext_normalize_get_original");
-    return pn_get_original(h, "dril_ext_normalize_get_original", obs, rewards);
-}
-DRIL_EXPORT int32_t dril_ext_normalize_get_returns(dril_handle* h, float* returns) {
-    NEED(h); XN_ON(h, "dril_ext_normalize_get_returns");
-    return pn_get_returns(h, "dril_ext_normalize_get_returns", returns);
-}
-DRIL_EXPORT int32_t dril_ext_normalize_reset(dril_handle* h, void* caller_stream) {
-    NEED(h); XN_ON(h, "dril_ext_normalize_reset");
-    int rc = ext_stream_enter(h, caller_stream); if (rc) return rc;
-    HIPCHK(h, hipMemsetAsync(h->env.disc_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream));   // reset! :118; old_obs follows with the next observe
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_ext_monitor_enable(dril_handle* h, int32_t stats_window) {
-    NEED(h);
-    { int rc = xw_kind_check(h, "dril_ext_monitor_enable"); if (rc) return rc; }
-    if (stats_window < 0) return fail(h, DRIL_ERR_INVALID_ARG, "dril_ext_monitor_enable: stats_window must be >= 0 (0: off)");
-    { int rc = xw_between_rollouts(h, "dril_ext_monitor_enable"); if (rc) return rc; }
-    if (stats_window == h->ext_mon_window) return DRIL_OK;                             // the window in force (or off while off): nothing changes
-    { int rc = sync(h); if (rc) return rc; }
-    xm_free(h);
-    if (stats_window == 0) return DRIL_OK;
-    const size_t E = (size_t)h->cfg.n_envs, N = (size_t)h->N, W = (size_t)stats_window;
-    hipError_t e = h->mon_cur_ret.alloc(E);
-    if (e == hipSuccess) e = h->mon_cur_len.alloc(E);
-    if (e == hipSuccess) e = h->ep_ret.alloc(N);
-    if (e == hipSuccess) e = h->ep_len.alloc(N);
-    if (e == hipSuccess) e = h->mon_ring_ret.alloc(W);
-    if (e == hipSuccess) e = h->mon_ring_len.alloc(W);
-    if (e == hipSuccess) e = h->mon_cnt.alloc((size_t)h->cfg.n_steps);
-    if (e == hipSuccess) e = h->mon_meta.alloc(2);
-    if (e == hipSuccess) e = hipMemset(h->mon_cur_ret, 0, E * 4);                      // fresh sums, an empty window
-    if (e == hipSuccess) e = hipMemset(h->mon_cur_len, 0, E * 4);
-    if (e == hipSuccess) e = hipMemset(h->mon_meta, 0, 8);
-    if (e != hipSuccess) { xm_free(h); return fail(h, DRIL_ERR_HIP, std::string("dril_ext_monitor_enable: ") + hipGetErrorString(e)); }
-    h->ext_mon_window = stats_window;
-    if (!h->pn.on) h->xw_allocs = 0;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_ext_monitor_get_stats(dril_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
-    NEED(h);
-    { int rc = xw_kind_check(h, "dril_ext_monitor_get_stats"); if (rc) return rc; }
-    if (h->ext_mon_window < 1) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_ext_monitor_get_stats: MonitorWrapperEnv is off (dril_ext_monitor_enable has not been called with a window)");
-    return monitor_window_stats(h, h->ext_mon_window, ep_rew_mean, ep_len_mean, n_episodes);
-}
-DRIL_EXPORT int32_t dril_ext_wrap_info(const dril_handle* h, struct dril_ext_wrap_info* out) {
-    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    if (!out) return DRIL_ERR_INVALID_ARG;
-    if (!h->external) return DRIL_ERR_UNSUPPORTED;
-    std::memset(out, 0, sizeof(*out));
-    out->normalize_on = h->pn.on ? 1 : 0; out->monitor_on = h->ext_mon_window > 0 ? 1 : 0; out->monitor_window = h->ext_mon_window;
-    out->launches_act = h->xw_added[0]; out->launches_record = h->xw_added[1]; out->launches_finish = h->xw_added[2]; out->allocations = h->xw_allocs;
-    return DRIL_OK;
-}
-
 DRIL_EXPORT int32_t dril_collect_rollout(dril_handle* h, double* fps) { NEED(h); NOT_EXTERNAL(h, "dril_collect_rollout"); return collect_rollout(h, fps, true); }
 DRIL_EXPORT int32_t dril_debug_set_noise(dril_handle* h, const void* noise, size_t count) {
     NEED(h);
@@ -1957,83 +1345,6 @@ void small_update_chunk(const UpdatePlan& p, int64_t chunk, int64_t s0, SmallUpd
 }
 // what the persistent kernel's launches leave on the host side of the handle
 void small_update_done(dril_handle* h, const UpdatePlan& p) { h->adam_steps += p.total_steps; h->wimg_dirty = true; h->last_variant = 6; h->used_f16 = true; }
-int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home);
-int update_finish(dril_handle* h, const UpdatePlan& p, const UpdateHome& home, dril_ppo_stats* out);
-int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
-    if (h->cfg.world_size > 1 && !comm_ready(h)) return fail(h, DRIL_ERR_NOT_INITIALISED, "world_size > 1 but dril_comm_init was not called");
-    const UpdatePlan plan = update_plan(h);
-    const int world = plan.world;
-    const int64_t N = plan.N, B = plan.B, nb = plan.nb, total_steps = plan.total_steps;
-    { int rcb = update_begin(h, plan); if (rcb) return rcb; }
-    const int bits = plan.bits;
-    int64_t step = 0;
-    const bool persistent = small_persistent_applies(h, plan);
-    if (persistent) {
-        std::vector<uint64_t> keys((size_t)h->cfg.epochs);
-        SmallUpdateArgs u{};
-        { int rca = small_update_args(h, plan, keys.data(), u); if (rca) return rca; }
-        HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (keys is a stack-lifetime host buffer)
-        if (!h->small_xchg) HIPCHK(h, h->small_xchg.alloc((size_t)kSmallXchgWords));
-        u.xchg = h->small_xchg; u.debug_solo = std::getenv("DRIL_SMALL_DEBUG_SOLO") != nullptr;
-        for (int64_t s0 = 0; s0 < total_steps; s0 += h->small_chunk) {
-            small_update_chunk(plan, h->small_chunk, s0, u);
-            prof_begin(h, DRIL_K_PPO_GRAD);
-            HIPCHK(h, launch_ppo_update_small(h->cfg.env_kind, u, h->stream));
-            prof_end(h);
-        }
-        small_update_done(h, plan);
-#ifdef DRIL_STAMPS
-        {   // per-phase s_memtime ticks of the last launch, per wave
-            hipStreamSynchronize(h->stream);
-            std::vector<unsigned long long> d(8 * 16);
-            hipMemcpy(d.data(), h->dbg, d.size() * 8, hipMemcpyDeviceToHost);
-            const char* nm[16] = {"top: moments + barrier", "L1 + tanh + h1 pieces", "wait B1", "L2 + tanh + out partial", "wait B2", "head + dW3 + dz2 + pieces", "wait B3", "dh1 + dW1 + dW2", "wait B4",
-                                  "dW2 overlay", "wait B5", "g + norm", "stats + Adam + images", "-", "-", "-"};
-            for (int wv = 0; wv < 8; wv += 4) {
-                double tot = 0; for (int k = 0; k < 15; ++k) tot += (double)d[wv * 16 + k];
-                fprintf(stderr, "[small stamps] wave %d: %.0f ticks per step (100 MHz: %.2f us)\n", wv, tot / (double)total_steps, tot / (double)total_steps / 100.0);
-                for (int k = 0; k < 15; ++k) fprintf(stderr, "   %-28s %8.0f ticks/step  %5.1f %%\n", nm[k], (double)d[wv * 16 + k] / (double)total_steps, 100.0 * (double)d[wv * 16 + k] / tot);
-            }
-        }
-#endif
-        step = total_steps;
-    }
-    for (int ep = 0; ep < h->cfg.epochs && !persistent; ++ep) {
-        const uint64_t key = perm_key(h->cfg.seed + (uint64_t)h->cfg.rank, h->update_counter, ep);
-        const int64_t* perm = h->perm_count ? h->perm_dev + (size_t)ep * N : nullptr;
-        const bool epoch_moments = h->cfg.normalize_advantage && !perm && nb >= 2 && nb <= 2048;
-        // chip-filling minibatches of the fused kernels: the epoch's order as an index array (the update kernels then read 8 bytes per sample instead of evaluating the
-        // keyed bijection per lane, wave, net and tile)
-        const bool index_array = !perm && !h->generic && !h->no_epoch_index && N < (1ll << 31) && (B + kTile - 1) / kTile >= kPairTilesPerCu * (int64_t)h->num_cus;
-        if (index_array) {
-            if (!h->epoch_index) HIPCHK(h, h->epoch_index.alloc((size_t)N));
-            prof_begin(h, DRIL_K_ADV_MOMENTS);
-            HIPCHK(h, launch_epoch_index(N, key, bits, h->epoch_index, h->stream));
-            prof_end(h);
-        }
-        if (epoch_moments) {
-            if (nb > 0) { HIPCHK(h, h->epoch_tables.grow((size_t)h->epoch_blocks * 2 * nb)); HIPCHK(h, h->epoch_stats.grow((size_t)3 * nb)); }
-            prof_begin(h, DRIL_K_ADV_MOMENTS);
-            const int eb = (int)std::min<int64_t>(h->epoch_blocks, std::max<int64_t>(64, N / 8192));       // eight waves per SIMD at chip-filling sizes: the pass is one dependent chain per sample
-            HIPCHK(h, launch_epoch_moments(h->adv, N, B, (int)nb, key, bits, h->epoch_tables, eb, h->epoch_stats, h->stop_flag, h->stream));
-            prof_end(h);
-            if (world > 1 || (comm_ready(h) && h->force_allreduce)) {     // ONE all-reduce per epoch for the advantage moments of all its minibatches
-                int rca = rccl_allreduce(h, h->epoch_stats, (size_t)3 * nb, kNcclFloat64); if (rca) return rca;
-            }
-        }
-        for (int64_t k = 0; k < nb; ++k, ++step) {
-            const int64_t pos0 = k * B, count = (pos0 + B <= N) ? B : N - pos0;
-            int rc = ppo_step(h, h->obs, h->act, h->adv, h->ret, h->logp, h->val, perm, pos0, count, N, key, bits, h->step_stats + step * 16, true, h->rec,
-                              epoch_moments ? h->epoch_stats + 3 * k : nullptr, index_array ? h->epoch_index : nullptr);
-            if (rc) return rc;
-        }
-    }
-    std::vector<float> st((size_t)total_steps * 16); std::vector<double> ev(4 * (size_t)h->ev_blocks); int scal[3] = {0, 0, 0};
-    const UpdateHome home{st.data(), ev.data(), scal, nullptr};
-    { int rce = update_enqueue_home(h, plan, home); if (rce) return rce; }
-    int rc = sync(h); if (rc) return rc;
-    return update_finish(h, plan, home, out);
-}
 int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home) {
     h->update_counter += 1;
     prof_begin(h, DRIL_K_EXPLAINED_VAR);
@@ -2118,6 +1429,81 @@ int update_finish(dril_handle* h, const UpdatePlan& p, const UpdateHome& home, d
     if (nan == 2) { h->spin_timeout = true; return fail(h, DRIL_ERR_HIP, "ppo_update_small_kernel: the partner workgroup did not answer within the spin limit (its two workgroups must be resident together); DRIL_NO_PERSISTENT_UPDATE=1 selects the per-step kernels"); }
     if (nan) return fail(h, DRIL_ERR_NAN_IN_GRADS, "gradient contains nan or is not finite (ppo.jl:213-214)");
     return DRIL_OK;
+}
+int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
+    if (h->cfg.world_size > 1 && !comm_ready(h)) return fail(h, DRIL_ERR_NOT_INITIALISED, "world_size > 1 but dril_comm_init was not called");
+    const UpdatePlan plan = update_plan(h);
+    const int world = plan.world;
+    const int64_t N = plan.N, B = plan.B, nb = plan.nb, total_steps = plan.total_steps;
+    { int rcb = update_begin(h, plan); if (rcb) return rcb; }
+    const int bits = plan.bits;
+    int64_t step = 0;
+    const bool persistent = small_persistent_applies(h, plan);
+    if (persistent) {
+        std::vector<uint64_t> keys((size_t)h->cfg.epochs);
+        SmallUpdateArgs u{};
+        { int rca = small_update_args(h, plan, keys.data(), u); if (rca) return rca; }
+        HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (keys is a stack-lifetime host buffer)
+        if (!h->small_xchg) HIPCHK(h, h->small_xchg.alloc((size_t)kSmallXchgWords));
+        u.xchg = h->small_xchg; u.debug_solo = std::getenv("DRIL_SMALL_DEBUG_SOLO") != nullptr;
+        for (int64_t s0 = 0; s0 < total_steps; s0 += h->small_chunk) {
+            small_update_chunk(plan, h->small_chunk, s0, u);
+            prof_begin(h, DRIL_K_PPO_GRAD);
+            HIPCHK(h, launch_ppo_update_small(h->cfg.env_kind, u, h->stream));
+            prof_end(h);
+        }
+        small_update_done(h, plan);
+#ifdef DRIL_STAMPS
+        {   // per-phase s_memtime ticks of the last launch, per wave
+            hipStreamSynchronize(h->stream);
+            std::vector<unsigned long long> d(8 * 16);
+            hipMemcpy(d.data(), h->dbg, d.size() * 8, hipMemcpyDeviceToHost);
+            const char* nm[16] = {"top: moments + barrier", "L1 + tanh + h1 pieces", "wait B1", "L2 + tanh + out partial", "wait B2", "head + dW3 + dz2 + pieces", "wait B3", "dh1 + dW1 + dW2", "wait B4",
+                                  "dW2 overlay", "wait B5", "g + norm", "stats + Adam + images", "-", "-", "-"};
+            for (int wv = 0; wv < 8; wv += 4) {
+                double tot = 0; for (int k = 0; k < 15; ++k) tot += (double)d[wv * 16 + k];
+                fprintf(stderr, "[small stamps] wave %d: %.0f ticks per step (100 MHz: %.2f us)\n", wv, tot / (double)total_steps, tot / (double)total_steps / 100.0);
+                for (int k = 0; k < 15; ++k) fprintf(stderr, "   %-28s %8.0f ticks/step  %5.1f %%\n", nm[k], (double)d[wv * 16 + k] / (double)total_steps, 100.0 * (double)d[wv * 16 + k] / tot);
+            }
+        }
+#endif
+        step = total_steps;
+    }
+    for (int ep = 0; ep < h->cfg.epochs && !persistent; ++ep) {
+        const uint64_t key = perm_key(h->cfg.seed + (uint64_t)h->cfg.rank, h->update_counter, ep);
+        const int64_t* perm = h->perm_count ? h->perm_dev + (size_t)ep * N : nullptr;
+        const bool epoch_moments = h->cfg.normalize_advantage && !perm && nb >= 2 && nb <= 2048;
+        // chip-filling minibatches of the fused kernels: the epoch's order as an index array (the update kernels then read 8 bytes per sample instead of evaluating the
+        // keyed bijection per lane, wave, net and tile)
+        const bool index_array = !perm && !h->generic && !h->no_epoch_index && N < (1ll << 31) && (B + kTile - 1) / kTile >= kPairTilesPerCu * (int64_t)h->num_cus;
+        if (index_array) {
+            if (!h->epoch_index) HIPCHK(h, h->epoch_index.alloc((size_t)N));
+            prof_begin(h, DRIL_K_ADV_MOMENTS);
+            HIPCHK(h, launch_epoch_index(N, key, bits, h->epoch_index, h->stream));
+            prof_end(h);
+        }
+        if (epoch_moments) {
+            if (nb > 0) { HIPCHK(h, h->epoch_tables.grow((size_t)h->epoch_blocks * 2 * nb)); HIPCHK(h, h->epoch_stats.grow((size_t)3 * nb)); }
+            prof_begin(h, DRIL_K_ADV_MOMENTS);
+            const int eb = (int)std::min<int64_t>(h->epoch_blocks, std::max<int64_t>(64, N / 8192));       // eight waves per SIMD at chip-filling sizes: the pass is one dependent chain per sample
+            HIPCHK(h, launch_epoch_moments(h->adv, N, B, (int)nb, key, bits, h->epoch_tables, eb, h->epoch_stats, h->stop_flag, h->stream));
+            prof_end(h);
+            if (world > 1 || (comm_ready(h) && h->force_allreduce)) {     // ONE all-reduce per epoch for the advantage moments of all its minibatches
+                int rca = rccl_allreduce(h, h->epoch_stats, (size_t)3 * nb, kNcclFloat64); if (rca) return rca;
+            }
+        }
+        for (int64_t k = 0; k < nb; ++k, ++step) {
+            const int64_t pos0 = k * B, count = (pos0 + B <= N) ? B : N - pos0;
+            int rc = ppo_step(h, h->obs, h->act, h->adv, h->ret, h->logp, h->val, perm, pos0, count, N, key, bits, h->step_stats + step * 16, true, h->rec,
+                              epoch_moments ? h->epoch_stats + 3 * k : nullptr, index_array ? h->epoch_index : nullptr);
+            if (rc) return rc;
+        }
+    }
+    std::vector<float> st((size_t)total_steps * 16); std::vector<double> ev(4 * (size_t)h->ev_blocks); int scal[3] = {0, 0, 0};
+    const UpdateHome home{st.data(), ev.data(), scal, nullptr};
+    { int rce = update_enqueue_home(h, plan, home); if (rce) return rce; }
+    int rc = sync(h); if (rc) return rc;
+    return update_finish(h, plan, home, out);
 }
 // The f16-piece kernels (the default of the fused path) compute fp32-equivalent products inside f16's RANGE: a staged weight beyond ~ 350 or a gradient tile beyond
 // 65 504 / SG overflows a hi piece, and the step that meets it reports a non-finite gradient without touching the parameters.  Range is not something the reference
@@ -2253,35 +1639,6 @@ DRIL_EXPORT int32_t dril_apply_gradients(dril_handle* h, const float* grads, siz
 }
 
 // ---- evaluate_agent (src/evaluation.jl:54-143) ------------------------------------------------------------
-namespace { int evaluate_agent_loop(dril_handle* h, int32_t n_eval, int32_t deterministic, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths, bool raw); }
-DRIL_EXPORT int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval, int32_t deterministic, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) {
-    NEED(h); NOT_EXTERNAL(h, "dril_evaluate_agent");
-    if (n_eval < 1 || !out) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
-    const int E = h->cfg.n_envs;
-    int rc = ensure_wimg(h); if (rc) return rc;
-    if (h->env.module && h->pn.on) {                                                 // a plug-in env under dril_normalize_enable: the statistics in force, frozen; nothing of the wrapper moves
-        const size_t ED = (size_t)E * h->D;
-        DevBuf<float> keep; HIPCHK(h, keep.alloc(ED + 2 * (size_t)E));    // returns | old_rewards | old_obs
-        const int training = h->pn.cfg.training;
-        hipError_t e = hipMemcpyAsync(keep, h->env.disc_returns, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(keep + E, h->e_rew, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(keep + 2 * (size_t)E, h->e_obs_raw, ED * 4, hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) {
-            h->pn.cfg.training = 0;                                              // set_training(eval_env, false): neither statistics nor `returns` are updated
-            rc = evaluate_agent_loop(h, n_eval, deterministic, out, ep_rewards, ep_lengths, /*raw_rewards=*/true);
-            h->pn.cfg.training = training;
-            e = hipMemcpyAsync(h->env.disc_returns, keep, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(h->e_rew, keep + E, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(h->e_obs_raw, keep + 2 * (size_t)E, ED * 4, hipMemcpyDeviceToDevice, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
-        keep.release();
-        if (rc) return rc;
-        HIPCHK(h, e);
-        return DRIL_OK;
-    }
-    return evaluate_agent_loop(h, n_eval, deterministic, out, ep_rewards, ep_lengths, h->mon_cur_ret != nullptr);   // monitored: infos[i]["episode"]["r"] is the raw return
-}
 namespace {
 int evaluate_agent_loop(dril_handle* h, int32_t n_eval, int32_t deterministic, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths, bool raw) {
     const int E = h->cfg.n_envs;
@@ -2322,6 +1679,34 @@ int evaluate_agent_loop(dril_handle* h, int32_t n_eval, int32_t deterministic, d
     return DRIL_OK;
 }
 }  // namespace
+DRIL_EXPORT int32_t dril_evaluate_agent(dril_handle* h, int32_t n_eval, int32_t deterministic, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) {
+    NEED(h); NOT_EXTERNAL(h, "dril_evaluate_agent");
+    if (n_eval < 1 || !out) return fail(h, DRIL_ERR_INVALID_ARG, "dril_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
+    const int E = h->cfg.n_envs;
+    int rc = ensure_wimg(h); if (rc) return rc;
+    if (h->env.module && h->pn.on) {                                                 // a plug-in env under dril_normalize_enable: the statistics in force, frozen; nothing of the wrapper moves
+        const size_t ED = (size_t)E * h->D;
+        DevBuf<float> keep; HIPCHK(h, keep.alloc(ED + 2 * (size_t)E));    // returns | old_rewards | old_obs
+        const int training = h->pn.cfg.training;
+        hipError_t e = hipMemcpyAsync(keep, h->env.disc_returns, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(keep + E, h->e_rew, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(keep + 2 * (size_t)E, h->e_obs_raw, ED * 4, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) {
+            h->pn.cfg.training = 0;                                              // set_training(eval_env, false): neither statistics nor `returns` are updated
+            rc = evaluate_agent_loop(h, n_eval, deterministic, out, ep_rewards, ep_lengths, /*raw_rewards=*/true);
+            h->pn.cfg.training = training;
+            e = hipMemcpyAsync(h->env.disc_returns, keep, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(h->e_rew, keep + E, (size_t)E * 4, hipMemcpyDeviceToDevice, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(h->e_obs_raw, keep + 2 * (size_t)E, ED * 4, hipMemcpyDeviceToDevice, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        }
+        keep.release();
+        if (rc) return rc;
+        HIPCHK(h, e);
+        return DRIL_OK;
+    }
+    return evaluate_agent_loop(h, n_eval, deterministic, out, ep_rewards, ep_lengths, h->mon_cur_ret != nullptr);   // monitored: infos[i]["episode"]["r"] is the raw return
+}
 
 // ---- evaluate_agent on the device, training state left untouched (docs/evaluation.md) --------------------------------------------------------
 // The loop of evaluate_agent_loop above with the host taken out of it: the episode accounting of dril_eval_account.h runs on the device, the host looks at ONE 4-byte
@@ -2775,6 +2160,7 @@ struct dril_population {
 };
 namespace {
 int pop_fail(dril_population* p, int code, const std::string& msg) { p->err = msg; return code; }
+#define POPCHK(p, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return pop_fail(p, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
 // "" when the handle can be a member, else why not (the shape on which a solo iteration is one rollout_duo_kernel launch and one ppo_update_small_kernel launch)
 std::string pop_ineligible(const dril_handle* h, int& code) {
     code = DRIL_ERR_UNSUPPORTED;
@@ -2810,7 +2196,6 @@ void pop_release(dril_population* p) {
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
-#define POPCHK(p, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return pop_fail(p, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
 // HIP-event brackets of the batched kernels (member 0's cfg.profile_events), resolved when the stream is drained
 void pop_ev_begin(dril_population* p, int kind) {
     if (!p->members[0]->cfg.profile_events) return;
@@ -3040,6 +2425,7 @@ int pop_evaluate(dril_population* p, const dril_eval_options* o, dril_eval_stats
 }
 }  // namespace
 
+#define JCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { const std::string msg = std::string("dril_population_join: " #expr ": ") + hipGetErrorString(_e); pop_release(p); return fail(nullptr, DRIL_ERR_HIP, msg); } } while (0)
 DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_population** out) {
     if (!out) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_population_join: null out");
     *out = nullptr;
@@ -3065,7 +2451,6 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
     for (int m = 0; m < n; ++m) if (members[m]->small_chunk < p->chunk) p->chunk = members[m]->small_chunk;
     p->total_steps = update_plan(h0).total_steps;
     p->n_chunks = (int)((p->total_steps + p->chunk - 1) / p->chunk);
-#define JCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { const std::string msg = std::string("dril_population_join: " #expr ": ") + hipGetErrorString(_e); pop_release(p); return fail(nullptr, DRIL_ERR_HIP, msg); } } while (0)
     JCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     JCHK(p->h_rargs.alloc((size_t)n));
     JCHK(p->h_uargs.alloc(((size_t)p->n_chunks + 1) * n));   // the launch table, and behind it one block per member
@@ -3084,7 +2469,6 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
         char* b = p->home_blocks[m];
         p->homes[m] = UpdateHome{(float*)b, (double*)(b + st), (int*)(b + st + ev + keys), (uint64_t*)(b + st + ev)};
     }
-#undef JCHK
     for (int m = 0; m < n; ++m) {                                                      // from here on nothing fails: the members move onto the population's stream
         dril_handle* h = members[m];
         (void)hipStreamSynchronize(h->stream);
@@ -3095,6 +2479,7 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
     *out = p;
     return DRIL_OK;
 }
+#undef JCHK
 DRIL_EXPORT int32_t dril_population_destroy(dril_population* p) { if (p) pop_release(p); return DRIL_OK; }
 DRIL_EXPORT const char* dril_population_last_error(const dril_population* p) { return p ? p->err.c_str() : g_create_error.c_str(); }
 DRIL_EXPORT int32_t dril_population_info(const dril_population* p, struct dril_population_info* out) {
@@ -3151,55 +2536,7 @@ DRIL_EXPORT int32_t dril_population_evaluate_device(dril_population* p, const dr
     return rc ? rc : first;
 }
 
-// ---- multi-GPU ------------------------------------------------------------------------------------------
-DRIL_EXPORT int32_t dril_comm_unique_id(uint8_t id[128]) {
-    std::string err;
-    if (!id) return fail(nullptr, DRIL_ERR_INVALID_ARG, "null id");
-    if (!load_rccl(err)) return fail(nullptr, DRIL_ERR_RCCL, err);
-    NcclId nid; std::memset(&nid, 0, sizeof(nid));
-    const int rc = g_rccl.GetUniqueId(&nid);
-    if (rc != 0) return fail(nullptr, DRIL_ERR_RCCL, rccl_error("ncclGetUniqueId", rc, nullptr));
-    std::memcpy(id, nid.bytes, 128);
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_comm_init(dril_handle* h, const uint8_t id[128]) {
-    NEED(h); std::string err;
-    if (!id) return fail(h, DRIL_ERR_INVALID_ARG, "null id");
-    if (!load_rccl(err)) return fail(h, DRIL_ERR_RCCL, err);
-    NcclId nid; std::memcpy(nid.bytes, id, 128);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int rc = ((nccl_init_rank_fn)(void*)g_rccl.CommInitRank)(&h->comm, h->cfg.world_size, nid, h->cfg.rank);
-    if (rc != 0) { const std::string m = rccl_error("ncclCommInitRank", rc, nullptr) + "; rank " + std::to_string(h->cfg.rank) + " of " + std::to_string(h->cfg.world_size) + " on " + h->device_info; h->comm = nullptr; return fail(h, DRIL_ERR_RCCL, m); }
-    return DRIL_OK;
-}
-
 DRIL_EXPORT int64_t dril_debug_device_bytes_live(void) { return g_devmem_live_bytes.load(); }
-DRIL_EXPORT int32_t dril_debug_comm_loopback(dril_handle** hs, int32_t n) {
-    if (!hs || n < 1 || n > kLoopMax) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_debug_comm_loopback: 1..8 handles");
-    std::vector<bool> seen((size_t)n, false);
-    for (int i = 0; i < n; ++i) {
-        dril_handle* h = hs[i];
-        if (!h) return fail(nullptr, DRIL_ERR_INVALID_ARG, "dril_debug_comm_loopback: null handle");
-        if (comm_ready(h)) return fail(h, DRIL_ERR_INVALID_ARG, "dril_debug_comm_loopback: the handle already has a communicator");
-        if (h->cfg.world_size != n || h->cfg.rank < 0 || h->cfg.rank >= n || seen[h->cfg.rank]) return fail(h, DRIL_ERR_INVALID_ARG, "dril_debug_comm_loopback: the handles must be ranks 0..n-1 of world_size n, one each");
-        if (h->cfg.device != hs[0]->cfg.device) return fail(h, DRIL_ERR_INVALID_ARG, "dril_debug_comm_loopback: all handles must live on one device");
-        seen[h->cfg.rank] = true;
-    }
-    (void)hipSetDevice(hs[0]->cfg.device);
-    LoopGroup* g = new LoopGroup(); g->n = n; g->refs = n;
-    hipError_t e = hipEventCreateWithFlags(&g->done, hipEventDisableTiming);
-    for (int q = 0; q < n && e == hipSuccess; ++q) e = hipEventCreateWithFlags(&g->ready[q], hipEventDisableTiming);
-    if (e != hipSuccess) { for (int q = 0; q < n; ++q) if (g->ready[q]) hipEventDestroy(g->ready[q]); if (g->done) hipEventDestroy(g->done); delete g; return fail(hs[0], DRIL_ERR_HIP, hipGetErrorString(e)); }
-    for (int i = 0; i < n; ++i) hs[i]->loop = g;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_comm_ranks(dril_handle* h) {
-    if (!h) return -1;
-    if (h->loop) return h->loop->n;
-    if (h->comm) { int c = -1; if (g_rccl.CommCount && g_rccl.CommCount(h->comm, &c) == 0) return c; return -1; }
-    return 1;
-}
-DRIL_EXPORT int64_t dril_comm_allreduce_calls(const dril_handle* h) { return h ? h->allreduce_calls : -1; }
 DRIL_EXPORT const char* dril_device_info(const dril_handle* h) { return h ? h->device_info.c_str() : ""; }
 
 // ---- measurement ----------------------------------------------------------------------------------------

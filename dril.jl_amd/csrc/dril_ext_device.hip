@@ -4,7 +4,7 @@
 //   ext_record_kernel        the caller's rewards / terminated / truncated -> rew[t], flags[t], boot[t] (trajectory.jl:52-61)
 // Both are one element per thread and bound by launch latency (E x A <= a few MB); the policy forward between them is generic_policy.
 // With NormalizeWrapperEnv / MonitorWrapperEnv on the handle (dril_ext_normalize_enable / dril_ext_monitor_enable) ext_norm_record_kernel stands where ext_record_kernel
-// stands here: dril_ext_norm.h, compiled into dril_api.hip next to the normaliser core it shares with the plug-in wrapper.
+// stands here: dril_ext_norm.h, compiled into dril_wrap.hip next to the normaliser core it shares with the plug-in wrapper.
 #include "dril_internal.h"
 
 namespace dril {

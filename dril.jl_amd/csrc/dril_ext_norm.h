@@ -1,8 +1,7 @@
 // dril_ext_norm.h — what is the DRIL_ENV_EXTERNAL handle's own of NormalizeWrapperEnv / MonitorWrapperEnv around the caller's device-resident envs
 // (dril_ext_normalize_enable / dril_ext_monitor_enable, include/dril_hip.h; honoured by dril_ext_act_device / _record_device / _finish_device and
 // dril_predict_actions_device).  Scalars, the moments kernel, the head of an apply kernel and the host state are dril_norm_wrap.h; the table shape (pn_rows, pn_tiles,
-// column tiles of 64) is dril_ppo_norm.h's: like a plug-in rollout, an external one has many envs per step.  Included by dril_api.hip after both, inside its
-// anonymous namespace.
+// column tiles of 64) is dril_ppo_norm.h's: like a plug-in rollout, an external one has many envs per step.  The launches are dril_wrap.hip's.
 //
 // One env step has one grid-wide dependency per half (all envs' sums -> the merged statistics -> every env's normalised value), so each half is
 //   moments   norm_moments_kernel<kPnTile> over the CALLER's array (d_obs, or `returns` advanced by d_rewards)
@@ -12,6 +11,14 @@
 // monitor's sums fused in, and the caller's terminal observations — a const array — normalised into a scratch array of the handle.
 // No atomics: the launch shape fixes the order of every sum.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dril_norm_wrap.h"    // NormWrapArgs, nz_fold, nz_statistics, nz_obs, nz_reward
+#include "dril_ppo_norm.h"     // kPnTile
+#include "dril_ext_record.h"   // xr_*: the per-env scalar rules of the record
+
+namespace {
 
 // ---- observe (normalizeWrapperEnv.jl:123-137) -------------------------------------------------------------------------------------------------------------------------
 // grid (env ranges, tiles): block (b, y) owns the envs [b epb, b epb + epb) and the columns [c0, c0 + W) of tile y (D <= 64: all of them).
@@ -96,3 +103,5 @@ __global__ __launch_bounds__(256) void ext_norm_record_kernel(XnRecordArgs p) {
         }
     }
 }
+
+}  // namespace

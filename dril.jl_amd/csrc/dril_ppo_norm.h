@@ -1,8 +1,7 @@
 // dril_ppo_norm.h — what is the PPO handle's own of NormalizeWrapperEnv (src/environment_wrappers/normalizeWrapperEnv.jl) around its device env plug-in
 // (dril_normalize_enable, include/dril_hip.h), for every observation width a plug-in may have (1 .. 1024).  Everything it shares with the SAC handle's wrapper —
-// scalars, the moments kernel, the head of the apply kernel, the host state — is dril_norm_wrap.h, which dril_api.hip includes first; this file is included inside its
-// anonymous namespace.  Built-in envs keep their own wrapper (cfg.norm_*: RmsState with 8 dims, the fused norm_step_kernel / norm_apply_kernel of dril_kernels.hip);
-// this file is never launched for them.
+// scalars, the moments kernel, the head of the apply kernel, the host state — is dril_norm_wrap.h; the launches are dril_wrap.hip's.  Built-in envs keep their own
+// wrapper (cfg.norm_*: RmsState with 8 dims, the fused norm_step_kernel / norm_apply_kernel of dril_kernels.hip); this file is never launched for them.
 //
 // After the plug-in's own step kernel (raw reward, flags, terminal observation and next observation into the per-step arrays) two launches follow:
 //   moments   norm_moments_kernel<kPnTile> over the E x D raw observations and the E rewards
@@ -16,8 +15,13 @@
 //     block folds only its tile's 2 x 64 (+ 2) columns instead of all 2 D + 2;
 //   * the table may have up to 256 rows for narrow observations: kPnFoldDoubles bounds what one apply block re-reads (rows x folded columns), not a fixed row count.
 #pragma once
+#include <hip/hip_runtime.h>
 
-constexpr int kPnTile = 64;            // columns per tile when D > 64: a wave reads 64 consecutive floats of an env's row
+#include "dril_norm_wrap.h"   // NormWrapArgs, nz_fold, nz_statistics, nz_obs, nz_reward
+
+namespace {
+
+constexpr int kPnTile = 64;           // columns per tile when D > 64: a wave reads 64 consecutive floats of an env's row
 constexpr int kPnMaxRows = 256;        // rows of the partial table (= workgroup rows of the moments kernel), and
 constexpr int kPnFoldDoubles = 8192;   // rows x columns an apply block folds, at most: 64 KB from L2 per block, 32 loads per thread
 constexpr int kPnMinEnvsPerRow = 16;
@@ -86,3 +90,5 @@ __global__ __launch_bounds__(256) void ppo_norm_apply_kernel(PnApplyArgs p) {
         }
     }
 }
+
+}  // namespace

@@ -24,6 +24,18 @@ def test_library_exports_every_declared_symbol(pkg):
     assert lib.dril_kernel_name(pkg._capi.K_PPO_GRAD) == b"ppo_grad_kernel"
 
 
+def test_library_exports_nothing_but_the_declared_symbols(pkg):
+    """The functions of the dynamic symbol table (type T) are exactly the ctypes table: a helper that crosses two units of the host code has external linkage, and
+    only -fvisibility=hidden keeps it out of the ABI — a leaked one shows here, a missing one too."""
+    so = ROOT / "dril.jl_amd" / "csrc" / "libdril_hip.so"
+    assert so.exists(), "build with __graft_entry__.build()"
+    out = subprocess.run(["nm", "-D", "--defined-only", str(so)], capture_output=True, text=True, check=True).stdout
+    exported = [ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"]
+    assert len(exported) == len(set(exported))
+    assert set(exported) == set(pkg._capi.EXPORTED_SYMBOLS)
+    assert all(name.startswith("dril_") for name in exported)
+
+
 def test_config_struct_layout_matches_c(pkg, tmp_path):
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dril_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu\\n", sizeof(dril_config),'

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the LIBRARY's world_size > 1 code (every `reduce` branch of dril_api.hip: per-step advantage moments, the
+"""GPU (-m gpu): the LIBRARY's world_size > 1 code (every `reduce` branch of dril_api.hip and dril_wrap.hip: per-step advantage moments, the
 [grads || 8 sums] all-reduce + grad-norm, the per-epoch moment table, NormalizeWrapperEnv's global batch moments, the
 explained-variance sums, dril_train's iteration arithmetic) executed on ONE device.
 
