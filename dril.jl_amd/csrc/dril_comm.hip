@@ -53,7 +53,7 @@ std::string rccl_error(const char* call, int rc, void* comm) {
 }
 
 // ---- debug loopback communicator -----------------------------------------------------------------
-// RCCL refuses two ranks on one device, so the data-parallel code of the handle (every `reduce` branch of dril_api.hip and dril_wrap.hip) could only be
+// RCCL refuses two ranks on one device, so the data-parallel code of the handle (every `reduce` branch of dril_update.hip, dril_api.hip and dril_wrap.hip) could only be
 // executed on a multi-GPU node.  A loopback group joins n handles of ONE process on ONE device as ranks 0..n-1: the all-reduce
 // call sites, counts and dtypes are unchanged, only the transport differs — the ranks' host threads rendezvous, the last arriver
 // makes its stream wait for every rank's buffer, one kernel sums the n device buffers element-wise in rank order and writes the

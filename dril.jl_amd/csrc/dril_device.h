@@ -53,7 +53,7 @@ constexpr int kTS = 36;     // row stride of the transposed activation images (3
 //   0           env seed (seed0 + e)      episode, 0          0                    env_reset<KIND>: the initial state of an episode
 //   1           env seed                  gstep, 0            component / 2        env_noise_*: the action noise of a device env at its global step — the same draw on
 //                                                                                  every collection path (policy_kernel / generic head with device envs, both rollout kernels, SAC)
-//   2           handle seed               update counter      epoch                perm_key (dril_api.hip): key of the epoch's index bijection
+//   2           handle seed               update counter      epoch                perm_key (dril_update.hip): key of the epoch's index bijection
 //   3 + 16 i    call seed                 row (64 bit)        call counter         call_noise_*: dril_policy_forward on a host batch (no device envs), action component i
 //   4           SAC update key            update counter      sample               sac_gather_kernel / sac_gather_l1_kernel (dril_sac.hip): replay indices
 //   5 .. 8      SAC update / aux key      counter             4 sample + a / 2     sac_noise (dril_sac.hip): the update's three noise draws, sac_noise_fill_kernel

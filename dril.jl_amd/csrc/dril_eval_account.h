@@ -1,6 +1,6 @@
 // dril_eval_account.h — the per-env episode accounting of a device-resident evaluate_agent (evaluation.jl:95-121) on a PPO handle: what env e's thread does with the
 // reward and the done flag of its step.  The record it appends and the host's reduction of the copied list are dril_sac_eval.h's (SacEvalEvent, sac_eval_event_capacity,
-// sac_eval_reduce); the list's ordering argument is written there.  No HIP dependency: dril_api.hip (eval_account_kernel, over the E-sized per-step arrays) and
+// sac_eval_reduce); the list's ordering argument is written there.  No HIP dependency: dril_eval.hip (eval_account_kernel, over the E-sized per-step arrays) and
 // dril_kernels.hip (evaluate_kernel, the sums in registers) include it, and tests/test_eval_device.py drives the same lines with g++ against a restatement of the
 // reference's loop.
 #pragma once

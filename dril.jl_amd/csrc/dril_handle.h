@@ -1,8 +1,13 @@
 // dril_handle.h — the PPO handle (include/dril_hip.h: dril_handle) and what the units of its host code share: the struct itself, the error and entry macros, the one-line
 // predicates several units read, and the prototypes of the functions that cross a unit boundary, under the name of the unit that defines them.  The units:
-//   dril_api.hip    create / destroy, the env, policy, rollout, external-env, update, evaluation and population verbs, profiling and info
-//   dril_comm.hip   RCCL, the loopback communicator, the all-reduce
-//   dril_wrap.hip   NormalizeWrapperEnv on plug-in and external handles, the monitor's statistics
+//   dril_api.hip      create / destroy, the parameter, optimiser-state, env and policy verbs, dril_train, profiling and info
+//   dril_rollout.hip  collect_rollout on every path, GAE, the rollout buffer's verbs
+//   dril_ext.hip      the DRIL_ENV_EXTERNAL verbs on host and device arrays
+//   dril_update.hip   ppo_step, the PPO update and its exact-f32 redo, dril_ppo_loss_grad / dril_apply_gradients
+//   dril_eval.hip     evaluate_agent (host loop and on the device), collect_trajectory on the device, their four kernels
+//   dril_pop.hip      populations: struct dril_population and the dril_population_* verbs
+//   dril_comm.hip     RCCL, the loopback communicator, the all-reduce
+//   dril_wrap.hip     NormalizeWrapperEnv on plug-in and external handles, the monitor's statistics
 // The library is built with -fvisibility=hidden: what is declared here has external linkage inside libdril_hip.so and is not exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -142,7 +147,10 @@ constexpr int kRetryLatchAfter = 2, kRetryLatchUpdates = 16;
 // HIP-event brackets of the kernel classes (cfg.profile_events)
 void prof_begin(dril_handle* h, int kid);
 void prof_end(dril_handle* h);
+void prof_resolve(dril_handle* h);   // stream must be drained
 int sync(dril_handle* h);
+// wide nets: (re)build the pre-tiled W2 / W2' images after every parameter change (enqueued on the handle's stream)
+int ensure_wimg(dril_handle* h);
 // fused per-kind kernels for the device envs, the layer-by-layer generic path for DRIL_ENV_EXTERNAL
 hipError_t run_policy(dril_handle* h, const PolicyArgs& a);
 PolicyArgs policy_args(dril_handle* h, const float* obs, int64_t B, const void* noise, void* actions, float* values, float* logp, float* entropy, int mode);
@@ -150,9 +158,61 @@ MonitorArgs monitor_rollout_args(dril_handle* h, size_t k);   // row k / E of a 
 int monitor_collect_rollout(dril_handle* h);
 // act!(env, actions) through the E-sized per-step arrays (dril_env_step, dril_evaluate_agent, the step-granular verbs), and MonitorWrapperEnv's window after it
 int env_step_arrays(dril_handle* h, const void* actions);
+// data-parallel runs: this rank's partial table of NormalizeWrapperEnv's batch moments folded to one row and summed over the ranks
+int global_partials(dril_handle* h, bool update, const double*& partials, int& nb, long long& n_stats);
+// the step-granular env verbs on device (NormalizeWrapperEnv.observe / act!).  actions: device pointer; rew_out / flags_out: device destinations
+int observe_dev(dril_handle* h, bool update_stats);
+int step_dev(dril_handle* h, const void* actions, float* rew_out, uint8_t* flags_out);
+
+// ---- dril_rollout.hip ----
+int compute_gae(dril_handle* h);
+// "" when the handle's net fits the plug-in's fused evaluation kernel (path 2 of the evaluation / trajectory verbs), else why not
+std::string fused_evaluate_unavailable(const dril_handle* h);
+// a collection that is ONE launch of the fused rollout kernel of a built-in kind, and the argument block of that launch, read from the handle as it stands
+bool rollout_fused_applies(const dril_handle* h);
+RolloutArgs rollout_args(const dril_handle* h);
+int collect_rollout(dril_handle* h, double* fps, bool do_sync);
+
+// ---- dril_ext.hip ----
 // the handle's stream takes over from the caller's stream / hands back to it: two events per handle, no host wait
 int ext_stream_enter(dril_handle* h, void* caller_stream);
 int ext_stream_leave(dril_handle* h, void* caller_stream);
+
+// ---- dril_update.hip ----
+// One update in the pieces that ppo_update runs in order, and that a population runs member by member around ONE batched launch (the order: dril_update.hip)
+struct UpdatePlan { int world = 1; int64_t N = 0, B = 0, nb = 0, total_steps = 0; uint64_t adam_steps0 = 0; int bits = 0; };
+// where an update's results land on the host: st [total_steps][16], ev [4 ev_blocks], scal = {nan flag, gae give-up flag, max |W2| bits}, keys [epochs].  Storage is the
+// caller's and must not move before update_finish: vectors for a solo update, one pinned block per member in a population
+struct UpdateHome { float* st = nullptr; double* ev = nullptr; int* scal = nullptr; uint64_t* keys = nullptr; };
+struct UpdateTry { bool may_retry = false; uint64_t adam_steps0 = 0, counter0 = 0; };
+UpdatePlan update_plan(const dril_handle* h);
+bool small_persistent_applies(const dril_handle* h, const UpdatePlan& p);
+int update_begin(dril_handle* h, const UpdatePlan& p);
+int small_update_args(dril_handle* h, const UpdatePlan& p, uint64_t* keys, SmallUpdateArgs& u);
+void small_update_chunk(const UpdatePlan& p, int64_t chunk, int64_t s0, SmallUpdateArgs& u);
+void small_update_done(dril_handle* h, const UpdatePlan& p);
+int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home);
+int update_finish(dril_handle* h, const UpdatePlan& p, const UpdateHome& home, dril_ppo_stats* out);
+bool update_direct_f32(const dril_handle* h);
+int update_snapshot(dril_handle* h, UpdateTry& t);
+int update_resolve(dril_handle* h, const UpdateTry& t, int rc, dril_ppo_stats* out);
+int ppo_update(dril_handle* h, dril_ppo_stats* out);
+
+// ---- dril_eval.hip ----
+// what one evaluation sets aside: device arrays in a list (copied to / from one blob), the host-side words next to them
+struct EvalKeep {
+    std::vector<std::pair<void*, size_t>> arrays;
+    uint64_t seed0; bool ready; int obs_par, ret_par, norm_training, pn_training; DevBuf<float> mon_cur_ret; int64_t gws_launches;
+};
+struct EvalPlan { bool persistent, fused, raw; int K; long long cap; EvalKeep keep; };
+// the pieces of dril_evaluate_agent_device, in the order it runs them: prepare, set-aside, reset, enqueue, put-back, reduce
+int eval_prepare(dril_handle* h, const dril_eval_options* o, EvalPlan& pl);
+int eval_set_aside(dril_handle* h, EvalKeep& keep);
+int eval_reset(dril_handle* h, const dril_eval_options* o, unsigned int* counter, long long cap, EvalAcct& acct);
+long long eval_max_steps(const dril_handle* h, int n_eval, int K);
+void eval_persistent_args(const dril_handle* h, const dril_eval_options* o, int K, const EvalAcct& acct, EvalKernelArgs& g);
+int eval_put_back(dril_handle* h, EvalKeep& keep);
+void eval_reduce(SacEvalEvent* events, int64_t n_events, const dril_eval_options* o, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths);
 
 // ---- dril_comm.hip ----
 int rccl_allreduce(dril_handle* h, void* buf, size_t count, int dtype);

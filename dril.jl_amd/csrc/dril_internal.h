@@ -1,4 +1,4 @@
-// dril_internal.h — kernel argument blocks and launcher prototypes shared by dril_kernels.hip and dril_api.hip
+// dril_internal.h — kernel argument blocks and launcher prototypes shared by dril_kernels.hip and the host units of the PPO handle (dril_handle.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

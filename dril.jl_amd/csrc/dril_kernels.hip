@@ -1643,7 +1643,7 @@ hipError_t launch_adv_moments(const MomentsArgs& a, int nblocks, hipStream_t s) 
 hipError_t launch_epoch_moments(const float* adv, int64_t N, int64_t B, int nb, uint64_t key, int bits, double* block_tables, int nblocks,
                                 double* table3, const int* stop_flag, hipStream_t s) {
     int R = 16;
-    while (R > 1 && (size_t)R * 2 * (nb + 1) * sizeof(double) > 32768) R >>= 1;          // nb <= 2048 (dril_api.hip): one copy is at most 32 KB
+    while (R > 1 && (size_t)R * 2 * (nb + 1) * sizeof(double) > 32768) R >>= 1;          // nb <= 2048 (dril_update.hip): one copy is at most 32 KB
     const size_t lds = (size_t)R * 2 * (nb + 1) * sizeof(double);
     if (bits <= 31) epoch_moments_kernel<true><<<nblocks, 256, lds, s>>>(adv, N, B, 1.0 / (double)B, nb, R, key, bits, block_tables, stop_flag);
     else epoch_moments_kernel<false><<<nblocks, 256, lds, s>>>(adv, N, B, 0.0, nb, R, key, bits, block_tables, stop_flag);

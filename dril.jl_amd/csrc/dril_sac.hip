@@ -2967,7 +2967,7 @@ int eval_snapshot(dril_sac_handle* h, bool save) {
     if (h->mon_window) { SHIP(h, cp(h->ev_mon_ret, h->mon_cur_ret, E * 4)); SHIP(h, cp(h->ev_mon_len, h->mon_cur_len, E * 4)); }
     return DRIL_OK;
 }
-// ---- the pieces both verbs run: the PPO handle's (dril_api.hip, under the same names; docs/sac.md "Layout of the host code") over this handle's state ----
+// ---- the pieces both verbs run: the PPO handle's (dril_eval.hip, under the same names; docs/sac.md "Layout of the host code") over this handle's state ----
 // set-aside: the verbs run on the handle's own envs — what a collection would continue from is kept here and put back by eval_finish, on every path
 struct EvalKeep { uint64_t seed0; bool ready, obs_valid; };
 int eval_set_aside(dril_sac_handle* h, EvalKeep& keep) { keep = EvalKeep{h->env.seed0, h->env.ready, h->obs_valid}; return eval_snapshot(h, true); }
@@ -2992,7 +2992,7 @@ template <class Row0> int eval_open_episode(dril_sac_handle* h, bool has_seed, u
     if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }
     return DRIL_OK;
 }
-// the loop of either verb (eval_poll_loop of dril_api.hip): enqueue(steps, launches) advances both; a chunk that would start at or past `bound` fails with (code, bound_msg)
+// the loop of either verb (eval_poll_loop of dril_eval.hip): enqueue(steps, launches) advances both; a chunk that would start at or past `bound` fails with (code, bound_msg)
 struct EvalPoll { unsigned int seen = 0; long long steps = 0; int32_t launches = 0; };
 template <class Enqueue> int eval_poll_loop(dril_sac_handle* h, int want, long long bound, int code, const char* bound_msg, EvalPoll& p, Enqueue&& enqueue) {
     for (p = EvalPoll{}; p.seen < (unsigned int)want; p.seen = *h->ev_counter_host) {
@@ -3070,7 +3070,7 @@ DRIL_EXPORT int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval, 
 // ---- collect_trajectory (src/utils/trajectory_utils.jl:3-49) with the handle's actor on the handle's envs; docs/sac.md, "Trajectories" ---------------------------
 // The evaluation's launches with the episode accounting replaced by a recording of envs 0..M-1.  Built-in Box kinds: one env launch per step (sac_traj_env_kernel),
 // the env's own thread records from its registers.  Plug-ins: their code objects write terminal_obs where truncated only, so the M SHADOW envs of
-// dril_collect_trajectory_device (its comment in dril_api.hip; built by traj_setup, dril_traj_run.h) take every step a second time, with the same env actions, and
+// dril_collect_trajectory_device (its comment in dril_eval.hip; built by traj_setup, dril_traj_run.h) take every step a second time, with the same env actions, and
 // their observe is the post-step, pre-reset observation sac_traj_record_kernel records.
 namespace {
 // the recording of one call.  No ClampAdapter (the boxes' clamp_* stay null): TanhScaleAdapter's actions are inside the Box by construction

@@ -77,7 +77,7 @@ int pn_step(dril_handle* h, const void* actions, float* rew_out) {
     return pn_apply(h, a, rows, false, upd);
 }
 
-// the loop of collect_rollout_module (dril_api.hip) under dril_normalize_enable: the plug-in's step kernel writes raw reward, terminal observation and raw next observation into the per-step arrays, then
+// the loop of collect_rollout_module (dril_rollout.hip) under dril_normalize_enable: the plug-in's step kernel writes raw reward, terminal observation and raw next observation into the per-step arrays, then
 // norm_moments_kernel (dril_norm_wrap.h) + ppo_norm_apply_kernel (dril_ppo_norm.h) put the normalised reward into row t and the normalised next observation where the policy reads it:
 // two launches more per env step than collect_rollout_module, and two for the opening observe.  V(terminal_observation) is V of the normalised terminal observation
 int collect_rollout_module_norm(dril_handle* h) {

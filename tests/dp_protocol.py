@@ -2,7 +2,7 @@
 
 Data-parallel protocol of the PPO update, stated on the host.
 
-libdril_hip.so runs this protocol in C++ on its own stream (dril_api.hip: ppo_step) with RCCL all-reduces; this
+libdril_hip.so runs this protocol in C++ on its own stream (dril_update.hip: ppo_step) with RCCL all-reduces; this
 module states the same protocol over a pluggable `allreduce(np.ndarray) -> np.ndarray` (sum over ranks) so that the
 sharding maths can be exercised with torch.distributed/gloo on CPU (tests/test_distributed_gloo.py) and so that hosts
 (bench.py, the Julia shim) share one definition of who owns what.

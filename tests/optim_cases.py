@@ -2,7 +2,7 @@
 float64 reference of ONE step, the error bounds, a numpy float32 emulation of the kernels' own expressions and the assertion functions (test infrastructure of
 tests/test_optim_cases.py and tests/test_gpu_optim.py; the driver is tests/optim_check.hip).
 
-Routes (ppo_step / dril_apply_gradients in dril_api.hip pick one):
+Routes (ppo_step / dril_apply_gradients in dril_update.hip pick one):
   A  grad_reduce_kernel -> adam_kernel (norm from norm_partials)        B  ppo_finish_small_kernel (one workgroup, P <= 16384)
   C  flat given -> grad_norm_kernel -> adam_kernel                      D  flat given -> adam_kernel with norm_from_flat = 1
 A case is a layout, slab counts (G, Gc), a route and a sequence of steps.  Routes A and B of the same layout / slab counts read the SAME slab images, routes C and D

@@ -1,5 +1,5 @@
-"""CPU, world_size 2, gloo: the data-parallel protocol of the PPO update (tests/dp_protocol.py — a host statement of what dril_api.hip does in C++; the LIBRARY's own world_size > 1 code is executed by tests/test_gpu_dataparallel.py; mirrored in C++ by
-dril_api.hip: ppo_step) reproduces the single-process result.  The compute backend here is the CPU oracle (the checker);
+"""CPU, world_size 2, gloo: the data-parallel protocol of the PPO update (tests/dp_protocol.py — a host statement of what dril_update.hip does in C++; the LIBRARY's own world_size > 1 code is executed by tests/test_gpu_dataparallel.py; mirrored in C++ by
+dril_update.hip: ppo_step) reproduces the single-process result.  The compute backend here is the CPU oracle (the checker);
 the all-reduce is torch.distributed over gloo on 127.0.0.1."""
 import os
 import sys

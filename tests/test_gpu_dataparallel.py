@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the LIBRARY's world_size > 1 code (every `reduce` branch of dril_api.hip and dril_wrap.hip: per-step advantage moments, the
+"""GPU (-m gpu): the LIBRARY's world_size > 1 code (every `reduce` branch of dril_update.hip, dril_api.hip and dril_wrap.hip: per-step advantage moments, the
 [grads || 8 sums] all-reduce + grad-norm, the per-epoch moment table, NormalizeWrapperEnv's global batch moments, the
 explained-variance sums, dril_train's iteration arithmetic) executed on ONE device.
 
@@ -95,7 +95,7 @@ def _same_stats(a, b):
 ])
 def test_two_ranks_equal_one_handle_over_the_union(pkg, oracle_mod, kind, E, T, B, world, kw):
     """rollout (no communication) + update with an injected DataLoader order: per-step advantage-moment all-reduce (3 doubles),
-    [grads || 8 sums] all-reduce + grad norm, explained-variance reduce (dril_api.hip ppo_step / ppo_update)"""
+    [grads || 8 sums] all-reduce + grad norm, explained-variance reduce (dril_update.hip ppo_step / ppo_update)"""
     capi = pkg._capi
     common = dict(n_steps=T, batch_size=B, epochs=3, episode_len=11, **kw)
     one = pkg.Handle(_cfg(pkg, kind, n_envs=E, **common))
@@ -143,7 +143,7 @@ def test_two_ranks_equal_one_handle_over_the_union(pkg, oracle_mod, kind, E, T, 
 
 def test_keyed_order_and_epoch_moment_table(pkg, oracle_mod):
     """no injected order: every rank draws its shard-local keyed bijection (key = f(seed + rank, update, epoch)) and the advantage
-    moments of ALL minibatches of an epoch go through ONE all-reduce of the (3 x nb) table (dril_api.hip ppo_update).  The union handle
+    moments of ALL minibatches of an epoch go through ONE all-reduce of the (3 x nb) table (dril_update.hip ppo_update).  The union handle
     gets the same order injected (computed with the oracle's statement of the bijection), which sends it down the per-step moments path:
     two different routes to the same minibatch statistics"""
     capi = pkg._capi

@@ -18,7 +18,7 @@ from test_gpu_eval_device import assert_bitwise, snapshot, stats_equal
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-K_DEFAULT = 64                                                                 # kEvalPollPersistent (dril_api.hip)
+K_DEFAULT = 64                                                                 # kEvalPollPersistent (dril_eval.hip)
 
 
 def _make(pkg, name, E, L, scaling=False, hidden=None, **kw):

@@ -100,7 +100,7 @@ def test_f16_pieces_across_the_operand_range(pkg, oracle_mod, kind, H, scale):
 def test_an_update_outside_the_f16_range_is_redone_on_the_exact_f32_kernels(pkg, oracle_mod, monkeypatch):
     """what f32 has and the f16 pieces do not is range: a staged weight beyond ~ 350 overflows its hi piece, and the step that meets it reports a non-finite
     gradient without touching the parameters.  dril_ppo_update then takes the update back (parameters, Adam moments, beta powers, counters) and redoes it on the
-    exact-f32 kernels (dril_api.hip ppo_update): the result is the one DRIL_GRAD_VARIANT=0 gives from the same state, bit for bit, and equals the oracle's; with
+    exact-f32 kernels (dril_update.hip ppo_update): the result is the one DRIL_GRAD_VARIANT=0 gives from the same state, bit for bit, and equals the oracle's; with
     DRIL_NO_F32_RETRY=1 the non-finite gradient surfaces as the reference's error (ppo.jl:213-214) — never a silently wrong update"""
     capi = pkg._capi
     cfg = _cfg(pkg, 0, n_envs=4096, n_steps=64, batch_size=4096 * 64 // 2, epochs=2, episode_len=25)
