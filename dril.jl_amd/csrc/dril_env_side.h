@@ -1,4 +1,4 @@
-// dril_env_side.h — the env side of a handle: the envs a PPO handle (dril_handle.h) or a SAC handle (dril_sac.hip) steps on the device, whichever they are — a built-in
+// dril_env_side.h — the env side of a handle: the envs a PPO handle (dril_handle.h) or a SAC handle (dril_sac_handle.h) steps on the device, whichever they are — a built-in
 // kind (dril_env_kinds.h; the env kernels of dril_kernels.hip) or a device env plug-in (include/device/dril_env_plugin.h; a HIP module loaded at create).  The ONE
 // definition of loading a plug-in (path checks, descriptor checks, load order), of the argument block its kernels take, and of reset! / observe / act! over either.
 #pragma once

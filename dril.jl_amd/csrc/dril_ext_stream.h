@@ -1,5 +1,5 @@
 // dril_ext_stream.h — what the device-array verbs of a DRIL_ENV_EXTERNAL handle share between the PPO handle (dril_ext.hip: dril_ext_*_device) and the SAC handle
-// (dril_sac.hip: dril_sac_ext_*_device): the rule a caller's device pointer must meet, and the hand-over between the caller's stream and the handle's stream.
+// (dril_sac_ext.hip: dril_sac_ext_*_device): the rule a caller's device pointer must meet, and the hand-over between the caller's stream and the handle's stream.
 // Host code only; each handle wraps these with its own error reporting.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
-// dril_sac.hip — the off-policy (SAC) path of libdril_hip.so: kernels + the C ABI of include/dril_sac.h.
+// dril_sac.hip — the off-policy (SAC) path of libdril_hip.so: kernels + the C ABI of include/dril_sac.h.  The external-env verbs (dril_sac_ext.hip) and the
+// evaluation (dril_sac_eval.hip) are units of their own around dril_sac_handle.h; what their kernels share with this file's is dril_sac_device.h.
 //
 // Reference: src/algorithms/sac.jl (losses :93-150, update! :299-404, train! :406-549), src/buffers/replay_buffer.jl,
 // src/buffers/off_policy_collection.jl, src/DRiLDistributions/squashedDiagGaussian.jl.  BASELINE.json configs[4]:
@@ -26,47 +27,15 @@
 #include <string>
 #include <vector>
 
-#include "../../include/dril_sac.h"
-#include "dril_internal.h"
-#include "dril_gemm.h"
-#include "dril_sac_adapter.h"
+#include "dril_sac_handle.h"
 #include "dril_policy_internal.h"   // dril_policy_from_sac_handle: the snapshot this handle gives a deployment policy (dril_policy.hip)
-#include "dril_sac_eval.h"
-#include "dril_traj_record.h"  // collect_trajectory on the device: the per-env recording sac_traj_env_kernel / sac_traj_record_kernel run (host-compilable)
-#include "dril_traj_run.h"     // ... and its setup (blob layout, table of bounds, shadow envs, messages), shared with the PPO handle
-#include "dril_env_side.h"    // DeviceEnvs: the envs this handle steps on the device (a built-in Box kind or a device env plug-in), shared with the PPO handle
-#include "dril_norm_wrap.h"    // NormalizeWrapperEnv for any observation width: what this handle's wrapper shares with the PPO handle's on plug-ins (NormWrap, norm_moments_kernel, nz_*)
-#include "dril_ext_stream.h"   // the pointer rule and the stream hand-over of the device-array verbs, shared with the PPO handle
-#include "dril_ext_record.h"   // the per-env rules of a recorded step under the wrappers of an external handle (flags, sticky error, returns reset, the monitor's sums)
 
 using namespace dril;
-
-#define DRIL_EXPORT extern "C" __attribute__((visibility("default")))
+using namespace dril::sac;
 
 namespace {
 
 thread_local std::string g_sac_create_error;
-
-
-// =================================================================================================================
-// SquashedDiagGaussian (squashedDiagGaussian.jl:24-46) — per-sample scalar math, accurate libm
-// =================================================================================================================
-constexpr int kMaxA = 16;
-constexpr float kLog2Pi = 1.8378770664093453f;
-__device__ inline float softplus_f(float x) { return log1pf(expf(-fabsf(x))) + (x > 0.f ? x : 0.f); }   // Lux.softplus
-// a = tanh(mu + exp(ls) * noise); returns logpdf(d, a) (:36-46), g = atanh(clamp(a))
-__device__ inline float squashed_sample_logp(const float* mu, const float* ls, const float* noise, int A, float* a, float* g) {
-    const float eps = 1.0e-6f, lo = -1.0f + eps, hi = 1.0f - eps;
-    float lss = 0.f, dss = 0.f, corr = 0.f;
-    for (int i = 0; i < A; ++i) {
-        a[i] = tanhf(mu[i] + expf(ls[i]) * noise[i]);
-        const float xc = a[i] < lo ? lo : (a[i] > hi ? hi : a[i]);
-        g[i] = atanhf(xc);
-        corr += 2.0f * (logf(2.0f) - g[i] - softplus_f(-2.0f * g[i]));
-        lss += ls[i]; const float d = g[i] - mu[i]; dss += d * d * expf(-2.0f * ls[i]);
-    }
-    return -0.5f * (2.0f * lss + dss + (float)A * kLog2Pi) - corr;       // diagGaussian.jl:25-36 minus the correction
-}
 
 // deterministic block reduction (blockDim.x == 256): pairwise tree in shared memory
 __device__ inline double block_sum(double v, double* sh) {
@@ -75,13 +44,6 @@ __device__ inline double block_sum(double v, double* sh) {
     for (int s = 128; s > 0; s >>= 1) { if (t < s) sh[t] += sh[t + s]; __syncthreads(); }
     const double r = sh[0]; __syncthreads();
     return r;
-}
-
-struct SacRng { uint64_t key; uint64_t u; };
-__device__ inline float sac_noise(SacRng r, int stream, int i, int a) {
-    uint32_t o[4];
-    philox4x32_10((uint32_t)r.key, (uint32_t)(r.key >> 32), (uint32_t)r.u, (uint32_t)(r.u >> 32), (uint32_t)stream, (uint32_t)(i * 4 + a / 2), o);
-    return (a & 1) ? randn_f32(o[2], o[3]) : randn_f32(o[0], o[1]);
 }
 
 // ---- get_data_loader (replay_buffer.jl:116-157): gather one batch + its three noise draws -------------------------------
@@ -363,17 +325,8 @@ __global__ __launch_bounds__(256) void sac_gather_l1_kernel(GatherL1Args f) {
 #pragma unroll
     for (int z = 0; z < 2; ++z) first_layer_row(f.P + f.qw1 + z * f.zP, f.P + f.qb1 + z * f.zP, xqs, W, f.H1, f.relu, f.qh1 + z * f.zh + (size_t)i * f.H1);
 }
-
-// In-stream time stamps of dril_sac_iterate: the fps of every iteration's collection (off_policy_collection.jl:126-128) and the update / collection split of the
-// profile need the time at the phase boundaries.  A HIP event per boundary costs the stream ~5 us each (three per iteration: 16 us of a 205 us iteration, seen as
-// gaps in the rocprofv3 trace); instead the LAST kernel of a phase stores the constant-rate wall clock (s_memrealtime) when its highest-numbered workgroup is done —
-// one store, no atomics, nothing waits.  Kernels of one stream run back to back, so a phase lasts from the previous phase's stamp to its own.
-__device__ __forceinline__ void phase_stamp(unsigned long long* stamp) {
-    if (stamp && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *stamp = wall_clock64();
-}
+// the loop-start stamp of dril_sac_iterate (phase_stamp, dril_sac_device.h: the later stamps are written by the last kernel of each phase)
 __global__ void sac_stamp_kernel(unsigned long long* stamp) { phase_stamp(stamp); }
-// device scalars shared by the kernels of one gradient step
-struct SacScalars { float log_ent, ent_m, ent_v, alpha; };
 
 // ---- entropy-coefficient step (sac.jl:313-343) + next actions for the critic target (:131) ----------------------------------
 struct EntNextArgs {
@@ -920,102 +873,10 @@ __global__ __launch_bounds__(256) void sac_step_end_kernel(StepEndArgs a) {
     if (threadIdx.x == 0) { a.out[0] = a.stats[0]; a.out[1] = a.stats[1]; a.out[2] = a.stats[2]; a.out[3] = a.stats[3]; a.out[4] = a.stats[4]; a.out[5] = 0.f; }
 }
 
-// ---- collection (off_policy_collection.jl:28-96) ---------------------------------------------------------------------------
-struct CollectHeadArgs {
-    int E, A, use_random; float* mu; const float* log_std; const float* inj_noise; const uint32_t* gstep; uint64_t seed0;
-    const float* low; const float* high;                              // Box bounds per action dimension, device table [A] each (built-in and external envs: their one pair in every entry)
-    float* raw; float* envact;
-    const float* h2; const float* w3; const float* b3; int H2;     // h2 != null: the actor's output layer mu = W3 h2 + b3 is evaluated HERE (sac_mu_rows) instead of in a launch of its own
-    int deterministic;                                             // evaluation only (a collection leaves it 0): mode(d) = tanh(mean), squashedDiagGaussian.jl:48-50 — the sample with zero noise
-};
-// mu[e][a] = W3[a, :] . h2[e, :] + b3[a] for the kEnvsPerBlock envs of a 256-thread block (4096 envs = 256 blocks: every CU takes part in what is a latency-bound
-// pass): each of the four waves takes kMuRows envs, the wave across the features — per 256-feature slice all rows' loads (one coalesced 1 KB line run each) are in
-// flight together, then one butterfly sum per row (every lane ends with the total; fixed order => deterministic).  Result in mu_s[] (shared), valid after the
-// caller's barrier.  Every thread of the block takes part whatever E is.
-constexpr int kEnvsPerBlock = 16, kMuRows = kEnvsPerBlock / 4;
-__device__ __forceinline__ void sac_mu_block(const CollectHeadArgs& g, int a, int e_block0, float* mu_s) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, e0 = e_block0 + kMuRows * wave;
-    const float* __restrict__ w = g.w3 + a;                          // W3 column-major (A x H2): W3[a + k A]
-    float acc[kMuRows];
-#pragma unroll
-    for (int r = 0; r < kMuRows; ++r) acc[r] = 0.f;
-    for (int k0 = 0; k0 < g.H2; k0 += 256) {                         // H2 % 4 == 0 (host-checked): a lane's four features are inside the row or all outside
-        const int k = k0 + 4 * lane;
-        const bool in = k < g.H2;
-        const int kk = in ? k : 0;                                    // out-of-range lanes re-read the row's start and multiply by zero weights: no branch around the loads
-        float wk[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { const float x = w[(size_t)(kk + t) * g.A]; wk[t] = in ? x : 0.f; }
-        float4 v[kMuRows];
-#pragma unroll
-        for (int r = 0; r < kMuRows; ++r) {
-            const int e = e0 + r < g.E ? e0 + r : g.E - 1;           // rows past E re-read the last one (in bounds, unused)
-            v[r] = *reinterpret_cast<const float4*>(g.h2 + (size_t)e * g.H2 + kk);
-        }
-#pragma unroll
-        for (int r = 0; r < kMuRows; ++r) { acc[r] = fmaf(v[r].x, wk[0], acc[r]); acc[r] = fmaf(v[r].y, wk[1], acc[r]); acc[r] = fmaf(v[r].z, wk[2], acc[r]); acc[r] = fmaf(v[r].w, wk[3], acc[r]); }
-    }
-    const float b = g.b3[a];
-#pragma unroll
-    for (int r = 0; r < kMuRows; ++r) {
-        float s2 = acc[r];
-#pragma unroll
-        for (int o = 32; o; o >>= 1) s2 += __shfl_xor(s2, o);
-        if (lane == r) mu_s[kMuRows * wave + r] = s2 + b;
-    }
-}
-// action component a of env e in the collection step: the noise (injected, or the env's stream at its global step: dril_device.h) -> the raw action the replay stores ->
-// the action the env receives (*envact); the caller stores them
-__device__ __forceinline__ void sac_collect_action(const CollectHeadArgs& g, int e, uint32_t gstep, int a, float mu, float* raw, float* envact) {
-    float z, r, ev;
-    if (g.deterministic) z = 0.f;                                                                // mode(d): the same expression as sac_squash_eval_kernel's deterministic branch
-    else if (g.inj_noise) z = g.inj_noise[e * g.A + a];
-    else z = g.use_random ? env_noise_u01_f32(g.seed0 + (uint64_t)e, gstep, a) : env_noise_randn(g.seed0 + (uint64_t)e, gstep, a);
-    const float lo = g.low[a], hi = g.high[a];
-    if (g.use_random) { r = sac_rand_box(z, lo, hi); ev = r; }                                   // rand(rng, act_space) per dimension: already env space, :50-53
-    else {
-        r = tanhf(mu + expf(g.log_std[a]) * z);                                                  // rand(SquashedDiagGaussian) squashedDiagGaussian.jl:24-27
-        ev = sac_to_env(r, lo, hi);                                                              // to_env(TanhScaleAdapter) default_adapters.jl:13-21
-    }
-    *raw = r; *envact = ev;
-}
-// the head of the kEnvsPerBlock envs of a 256-thread block: the output layer by all four waves (g.h2 set), then one thread per env
-__device__ __forceinline__ void sac_head_block(const CollectHeadArgs& g, float* mu_s) {
-    const int e = blockIdx.x * kEnvsPerBlock + threadIdx.x;
-    if (g.h2 && !g.use_random) {                                     // the output layer first (whole block: no early return before it)
-        for (int a = 0; a < g.A; ++a) {
-            sac_mu_block(g, a, blockIdx.x * kEnvsPerBlock, mu_s);
-            __syncthreads();
-            if (threadIdx.x < kEnvsPerBlock && e < g.E) g.mu[(size_t)e * g.A + a] = mu_s[threadIdx.x];
-            __syncthreads();
-        }
-    }
-    if (threadIdx.x >= kEnvsPerBlock || e >= g.E) return;
-    const uint32_t gs = g.gstep[e];
-    for (int a = 0; a < g.A; ++a) {
-        float r, ev;
-        sac_collect_action(g, e, gs, a, g.use_random ? 0.f : g.mu[(size_t)e * g.A + a], &r, &ev);
-        g.raw[e * g.A + a] = r; g.envact[e * g.A + a] = ev;
-    }
-}
+// ---- collection (off_policy_collection.jl:28-96): the head, push and env-step kernels; their pieces are dril_sac_device.h ------------------------------------
 __global__ __launch_bounds__(256) void sac_collect_head_kernel(CollectHeadArgs g) {
     __shared__ float mu_s[kEnvsPerBlock];
     sac_head_block(g, mu_s);
-}
-struct PushArgs {
-    int E, D, A; long long cap, tail; const float *obs, *raw, *rew, *tobs, *nobs; const uint8_t *term, *trunc;
-    float *rb_obs, *rb_next, *rb_act, *rb_rew; uint8_t *rb_term, *rb_trunc;
-    unsigned long long* stamp;   // phase_stamp (null: none)
-};
-// push! of env e's transition into its ring slot: D / A the row widths, tobs / nobs / raw the env's rows (memory or registers)
-__device__ __forceinline__ void sac_push_row(const PushArgs& g, int e, int D, int A, const float* tobs, const float* nobs, const float* raw, float rew, bool term, bool trunc) {
-    const long long slot = (g.tail + e) % g.cap;
-    for (int d = 0; d < D; ++d) {
-        g.rb_obs[slot * D + d] = g.obs[(size_t)e * D + d];
-        g.rb_next[slot * D + d] = trunc ? tobs[d] : nobs[d];                                    // truncated_observation | next observation
-    }
-    for (int a = 0; a < A; ++a) g.rb_act[slot * A + a] = raw[a];                                // unprocessed action, :72
-    g.rb_rew[slot] = rew; g.rb_term[slot] = term; g.rb_trunc[slot] = trunc;
 }
 __global__ void sac_push_kernel(PushArgs g) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1023,28 +884,6 @@ __global__ void sac_push_kernel(PushArgs g) {
     if (e >= g.E) return;
     sac_push_row(g, e, g.D, g.A, g.tobs + (size_t)e * g.D, g.nobs + (size_t)e * g.D, g.raw + e * g.A, g.rew[e], g.term[e] != 0, g.trunc[e] != 0);
 }
-// push! of the n envs [e0, e0 + n) by a whole workgroup, memory to memory: the threads walk the flat (env, dim) index of each field, so a wave's stores into rb_obs /
-// rb_next / rb_act are one contiguous run for any D / A (consecutive envs take consecutive ring slots; the run breaks once, where the ring wraps) instead of one lane
-// per env with a D-float stride.  Same rows, same slots as sac_push_row.
-__device__ __forceinline__ void sac_push_block(const PushArgs& g, int e0, int n) {
-    const int D = g.D, A = g.A;
-    for (int i = threadIdx.x; i < n * D; i += blockDim.x) {
-        const int e = e0 + i / D, d = i % D;
-        const long long slot = (g.tail + e) % g.cap;
-        g.rb_obs[slot * D + d] = g.obs[(size_t)e * D + d];
-        g.rb_next[slot * D + d] = g.trunc[e] ? g.tobs[(size_t)e * D + d] : g.nobs[(size_t)e * D + d];   // truncated_observation | next observation
-    }
-    for (int i = threadIdx.x; i < n * A; i += blockDim.x) {
-        const int e = e0 + i / A, a = i % A;
-        g.rb_act[((g.tail + e) % g.cap) * A + a] = g.raw[(size_t)e * A + a];                        // unprocessed action, :72
-    }
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int e = e0 + i;
-        const long long slot = (g.tail + e) % g.cap;
-        g.rb_rew[slot] = g.rew[e]; g.rb_term[slot] = g.term[e] != 0; g.rb_trunc[slot] = g.trunc[e] != 0;
-    }
-}
-constexpr int kPushEnvsPerBlock = 64;
 __global__ __launch_bounds__(256) void sac_push_flat_kernel(PushArgs g) {
     const int e0 = blockIdx.x * kPushEnvsPerBlock;
     phase_stamp(g.stamp);
@@ -1065,48 +904,6 @@ __global__ __launch_bounds__(256) void sac_collect_head_push_kernel(HeadPushArgs
 // on data of that env only (four dependent launches of 4 - 5 us and their boundaries per collected step).  The same four definitions in the same order — sac_collect_action,
 // the EnvCursor transition (env_advance / env_end_episode, dril_device.h), env_obs, sac_push_row — and every intermediate buffer (e_raw, e_envact, e_rew, e_term, e_trunc,
 // e_tobs, obs_nxt) still written: bit-identical to the four-launch sequence (A = 1: every device Box env).
-struct CollectEnvArgs { CollectHeadArgs head; PushArgs push; uint64_t seed0; int episode_len; float* state; int32_t* step_count; uint32_t* episode; uint32_t* gstep;
-                        float* rew; uint8_t* term; uint8_t* trunc; float* tobs; float* nobs;
-                        MonitorArgs mon; };   // MonitorWrapperEnv (dril_sac_monitor_enable): running sums, and row t of the collection's finished-episode block; all null = off
-// the actor's output layer for the kEnvsPerBlock envs of the block (A = 1), then this thread's env: false = the thread owns no env
-__device__ __forceinline__ bool sac_env_thread_mu(const CollectHeadArgs& g, float* mu_s, int* e_out, float* mu_out) {
-    const int e = blockIdx.x * kEnvsPerBlock + threadIdx.x;          // 256 threads per kEnvsPerBlock envs: all four waves on the output layer, then one thread per env
-    if (!g.use_random && g.h2) { sac_mu_block(g, 0, blockIdx.x * kEnvsPerBlock, mu_s); __syncthreads(); }   // same device function as the head kernel
-    if (threadIdx.x >= kEnvsPerBlock || e >= g.E) return false;
-    float mu_e = 0.f;
-    if (!g.use_random) { if (g.h2) { mu_e = mu_s[threadIdx.x]; g.mu[e] = mu_e; } else mu_e = g.mu[e]; }
-    *e_out = e; *mu_out = mu_e;
-    return true;
-}
-// predict_actions -> act! with auto-reset -> observe of env e by its thread: what the collection and the evaluation of a built-in Box env share.  *raw the action the
-// replay stores, to / no the terminal and the next observation (also written to c.tobs where truncated / c.nobs)
-template <int KIND>
-__device__ __forceinline__ StepOut sac_env_thread_step(const CollectEnvArgs& c, int e, float mu_e, float* raw, float* to, float* no) {
-    constexpr int D = EnvSpec<KIND>::D;
-    const CollectHeadArgs& g = c.head;
-    const EnvArrays env{c.state, c.step_count, c.episode, c.gstep, c.mon.cur_ret, c.mon.cur_len};
-    EnvCursor<KIND> cur; cur.load(env, e);
-    // ---- the action (sac_collect_head_kernel, A = 1) ----
-    float r, ev;
-    sac_collect_action(g, e, cur.gs, 0, mu_e, &r, &ev);
-    g.raw[e] = r; g.envact[e] = ev; *raw = r;
-    // ---- act! with auto-reset (env_step_kernel) ----
-    const StepOut so = env_advance<KIND>(cur, ev, 0, c.episode_len, false);
-    c.rew[e] = so.rew; c.term[e] = so.term; c.trunc[e] = so.trunc;
-    if (c.mon.cur_ret) c.mon.flags_out[e] = so.flags();
-    env_obs<KIND>(cur.st, to);                                                          // terminal_observation (stored where truncated)
-    if (so.trunc) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) c.tobs[(size_t)e * D + i] = to[i];
-    }
-    env_end_episode<KIND>(cur, c.seed0 + (uint64_t)e, so, c.mon.cur_ret ? c.mon.ep_ret + e : nullptr, c.mon.ep_len + e);
-    cur.store(env, e);
-    // ---- observe (env_observe_kernel) ----
-    env_obs<KIND>(cur.st, no);
-#pragma unroll
-    for (int i = 0; i < D; ++i) c.nobs[(size_t)e * D + i] = no[i];
-    return so;
-}
 template <int KIND>
 __global__ __launch_bounds__(256) void sac_collect_env_kernel(CollectEnvArgs c) {
     constexpr int D = EnvSpec<KIND>::D;
@@ -1120,24 +917,13 @@ __global__ __launch_bounds__(256) void sac_collect_env_kernel(CollectEnvArgs c) 
     phase_stamp(c.push.stamp);                                               // thread 0 of the last workgroup owns a live env (grid = ceil(E / kEnvsPerBlock)): the end of its work ~ the end of the phase
 }
 
-// ---- evaluate_agent on the device (evaluation.jl:90-124; the event list: dril_sac_eval.h) ----------------------------------------------------------
-// The episode accounting of env e after its step, by the env's own thread: current_rewards[e] += reward in float32 and in step order, as the reference's host loop
-// adds them; where the episode ended, one event through the list's counter (slots past the capacity are only counted) and the two sums restart.
-struct EvalAcctArgs { int E; int32_t step; float* cur_ret; int32_t* cur_len; unsigned int* counter; SacEvalEvent* events; unsigned int cap; };
-__device__ __forceinline__ void sac_eval_account(const EvalAcctArgs& a, int e, float rew, bool done) {
-    float r = a.cur_ret[e] + rew; int32_t l = a.cur_len[e] + 1;
-    if (done) {
-        const unsigned int i = atomicAdd(a.counter, 1u);
-        if (i < a.cap) a.events[i] = SacEvalEvent{a.step, e, r, l};
-        r = 0.f; l = 0;
-    }
-    a.cur_ret[e] = r; a.cur_len[e] = l;
-}
-#include "dril_sac_norm.h"   // NormalizeWrapperEnv on the SAC handle (dril_sac_normalize_enable): the env-step moments and apply + push kernels, the evaluation's frozen statistics
+// ---- the twins of sac_collect_env_kernel that an evaluation and a trajectory recording enqueue (launch_eval_env / launch_traj_env below; the host code: -----------
+// dril_sac_eval.hip).  They stand in this unit because all four kernels over sac_env_thread_step must be compiled together: how the compiler inlines the env's noise
+// draw (Philox under env_noise_*) into one of them depends on which others of the unit call it, and apart these two come out ~450 code bytes longer, with Philox
+// rounds computed twice (profiles/sac_units_resources.md)
 // built-in Box envs: the twin of sac_collect_env_kernel with the accounting where that one has the push (the monitor pointers of `env` are null: an evaluation does
 // not feed the training env's MonitorWrapperEnv).  nz.st != null: NormalizeWrapperEnv with training = false — the next observation normalised with the frozen
 // statistics by the env's own thread, in place of the raw row
-struct EvalEnvArgs { CollectEnvArgs env; EvalAcctArgs acct; NzEvalArgs nz; };
 template <int KIND>
 __global__ __launch_bounds__(256) void sac_eval_env_kernel(EvalEnvArgs c) {
     constexpr int D = EnvSpec<KIND>::D;
@@ -1158,7 +944,6 @@ __global__ __launch_bounds__(256) void sac_eval_env_kernel(EvalEnvArgs c) {
 // not, env_end_episode returns at once and `no` is the same expression over the same state, the same floats — so `to` is the row's observation throughout; the env
 // action is the word sac_env_thread_step stored for this env; reward and flags are the step's own.  One step per launch: the open / closed state of trajectory e is
 // rec.length[e], loaded before the step.  Threads of envs >= M and of closed trajectories step like an evaluation and write nothing to the recording.
-struct TrajEnvArgs { CollectEnvArgs env; NzEvalArgs nz; TrajRec rec; TrajMaps maps; int32_t t; };
 template <int KIND>
 __global__ __launch_bounds__(256) void sac_traj_env_kernel(TrajEnvArgs c) {
     constexpr int D = EnvSpec<KIND>::D;
@@ -1178,19 +963,92 @@ __global__ __launch_bounds__(256) void sac_traj_env_kernel(TrajEnvArgs c) {
         traj_record_env<D, 1>(c.rec, c.maps, c.t, e, act, so.rew, so.term, so.trunc, to, length);
     }
 }
-// a thread per (env, word) over M x max(D, W) lanes: row 0 of either path (t = 0, after the initial observe) and, on plug-ins, every step's row from the per-step
-// arrays and the shadow envs' observation.  The rule itself is traj_record_lane
-__global__ __launch_bounds__(256) void sac_traj_record_kernel(TrajRec r, TrajMaps x, TrajStep s, int32_t t) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t lanes = r.D > r.W ? r.D : r.W;
-    if (i >= (int64_t)r.M * lanes) return;
-    traj_record_lane(r, x, s, t, (int32_t)(i / lanes), (int32_t)(i % lanes));
+
+// ---- NormalizeWrapperEnv in a collection (argument blocks and the table shape: dril_sac_norm.h) -----------------------------------------------------------------
+// ---- moments, built-in Box envs (A = 1) -----------------------------------------------------------------------------------------------------------------
+// The twin of sac_collect_env_kernel without the push: the 16 env threads of a block sit in lanes 0 - 15 of wave 0, so the block's 2 D + 2 sums are four xor
+// steps each and one row of the table per block (rows = ceil(E / kEnvsPerBlock)).  env.nobs points at the wrapper's old_obs: the raw next observation.
+template <int KIND>
+__global__ __launch_bounds__(256) void sac_norm_env_kernel(NormEnvArgs c) {
+    constexpr int D = EnvSpec<KIND>::D, C = 2 * D + 2;
+    __shared__ float mu_s[kEnvsPerBlock];
+    int e = 0; float mu_e = 0.f;
+    const bool own = sac_env_thread_mu(c.env.head, mu_s, &e, &mu_e);
+    if (threadIdx.x >= 64) return;                                                       // (no barrier below: the other three waves only served the output layer)
+    double acc[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) acc[i] = 0;
+    if (own) {
+        float r, to[D], no[D];
+        const StepOut so = sac_env_thread_step<KIND>(c.env, e, mu_e, &r, to, no);
+        if (c.upd_ret) {                                                                 // update_reward_stats! :167-171 (done envs go back to zero in the apply kernel)
+            const float ret = c.returns[e] * c.gamma + so.rew;
+            c.returns[e] = ret; acc[2 * D] = ret; acc[2 * D + 1] = (double)ret * ret;
+        }
+#pragma unroll
+        for (int d = 0; d < D; ++d) { acc[d] = no[d]; acc[D + d] = (double)no[d] * no[d]; }
+    }
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        double v = acc[i];
+#pragma unroll
+        for (int o = kEnvsPerBlock / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (threadIdx.x == 0) c.partials[(size_t)blockIdx.x * C + i] = v;
+    }
 }
-// plug-ins: after the plug-in's step kernel, over its per-step arrays.  One thread per env, flat index.
-__global__ __launch_bounds__(256) void sac_eval_account_kernel(EvalAcctArgs a, const float* __restrict__ rew, const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.E) return;
-    sac_eval_account(a, e, rew[e], (term[e] | trunc[e]) != 0);
+
+// ---- apply + push -----------------------------------------------------------------------------------------------------------------------------------------
+// Block b owns the envs [b epb, b epb + epb) and keeps the statistics of all D columns in (dynamic) LDS.  Head (dril_norm_wrap.h): the column sums of the table, 256
+// columns at a time, the merge, the new statistics in LDS; block 0 stores them to st_out.  Body: flat (env, dim) loops, so a wave's loads and its stores into obs_out
+// and the ring are contiguous runs for any D.
+__global__ __launch_bounds__(256) void sac_norm_apply_kernel(NzApplyArgs p) {
+    extern __shared__ double nz_sh[];
+    const NormWrapArgs& a = p.w;
+    const int t = threadIdx.x, D = a.D, C = 2 * D + 2;
+    double* s_part = nz_sh; double* s_col = nz_sh + 256;
+    float* s_mean = reinterpret_cast<float*>(s_col + C); float* s_var = s_mean + D; float* s_rvar = s_var + D;
+    const bool upd_obs = a.partials && a.upd_obs, upd_ret = a.partials && a.upd_ret && a.rew;
+    if (upd_obs || upd_ret)
+        for (int c0 = 0; c0 < C; c0 += 256) nz_fold(a.partials, a.rows, C, min(256, C - c0), [=](int j) { return c0 + j; }, s_part, s_col + c0);
+    nz_statistics(a, upd_obs, upd_ret, 0, D, true, 0, blockIdx.x == 0, s_col, s_mean, s_var, s_rvar);
+    const int e0 = blockIdx.x * a.epb, n = min(a.epb, a.E - e0);
+    const bool push = p.push.E > 0;
+    for (int i = t; i < n * D; i += 256) {
+        const int e = e0 + i / D, d = i % D; const size_t j = (size_t)e * D + d;
+        float v = a.raw[j];
+        if (a.norm_obs) v = nz_obs(v, s_mean[d], s_var[d], a.eps, a.clip_obs);           // observe :123-137: the NEW statistics
+        a.obs_out[j] = v;
+        if (push) {
+            const long long slot = (p.push.tail + e) % p.push.cap;
+            p.push.rb_obs[slot * D + d] = p.push.obs[j];
+            if (a.trunc[e]) {                                                            // terminal_observation, :157-163: the statistics as they are before this observe
+                v = p.tobs[j];
+                if (a.norm_obs) v = nz_obs(v, a.st_in[d], a.st_in[D + d], a.eps, a.clip_obs);
+            }
+            p.push.rb_next[slot * D + d] = v;                                            // truncated_observation | next observation
+        }
+    }
+    if (a.rew) {
+        const float rvar = *s_rvar;
+        for (int i = t; i < n; i += 256) {
+            const int e = e0 + i;
+            const float r = a.rew[e];
+            p.old_rew[e] = r;
+            float rn = r;
+            if (a.norm_reward) rn = nz_reward(r, rvar, a.eps, a.clip_reward);
+            const bool term = a.term[e] != 0, trunc = a.trunc[e] != 0;
+            if (term || trunc) a.returns[e] = 0.f;                                       // :152-155
+            if (push) { const long long slot = (p.push.tail + e) % p.push.cap; p.push.rb_rew[slot] = rn; p.push.rb_term[slot] = term; p.push.rb_trunc[slot] = trunc; }
+        }
+    }
+    if (push) {
+        const int A = p.push.A;
+        for (int i = t; i < n * A; i += 256) {
+            const int e = e0 + i / A, k = i % A;
+            p.push.rb_act[((p.push.tail + e) % p.push.cap) * A + k] = p.push.raw[(size_t)e * A + k];   // unprocessed action, off_policy_collection.jl:72
+        }
+    }
+    phase_stamp(p.push.stamp);
 }
 
 // ---- MonitorWrapperEnv's window (monitorWrapperEnv.jl:1-7,53-58) after a collection, in ONE launch ---------------------------------------------------
@@ -1262,172 +1120,26 @@ __global__ void sac_noise_fill_kernel(int n, int A, SacRng rng, float* out) {
     for (int a = 0; a < A; ++a) out[i * A + a] = sac_noise(rng, 8, i, a);
 }
 
-// ---- the device-array verbs of a DRIL_ENV_EXTERNAL handle (dril_sac_ext_act_device / dril_sac_predict_actions_device / dril_sac_ext_push_device) ------------
-// Head of the device act, one launch behind the actor forward: the noise draw (the words sac_noise_fill_kernel would have written to a buffer, computed in the
-// thread that uses them), the squashed sample (squashed_sample_logp: sac_squash_eval_kernel's own expression, so its bits), TanhScaleAdapter — or, mode 2, the
-// uniform branch rand(action_space) — and the writes into the caller's arrays and the handle's pending-action rows.  One thread per row: A <= kMaxA floats per
-// thread, n x A <= a few hundred KB in all; the launch is latency-bound, the point is that it is ONE launch and no copy.
-// rand(rng, Box) of one dimension as __fadd_rn(low, __fmul_rn(u, __fsub_rn(high, low))): three float32 operations, each rounded on its own, which NumPy float32
-// restates to the bit.  Spelled with plain operators under contract(off): this toolchain's __fmul_rn / __fadd_rn ARE plain operators compiled with contraction
-// allowed, and the pair became one v_fmac_f32 (a single rounding) when the intrinsics were used
-__device__ __forceinline__ float ext_rand_box_rn(float u, float lo, float hi) {
-#pragma clang fp contract(off)
-    const float w = hi - lo;
-    const float p = u * w;
-    return lo + p;
-}
-struct ExtHeadArgs {
-    int n, A, mode;                                   // mode 0: sample, 1: deterministic (tanh(mean)), 2: rand(action_space)
-    const float* mu; const float* log_std; const float* noise;   // noise null: the handle's stream (rng)
-    SacRng rng; const float* low; const float* high;
-    float* stored; float* envact; float* keep;        // the caller's arrays (either may be null) and the handle's e_raw (null: predict only)
-};
-__global__ __launch_bounds__(256) void sac_ext_head_kernel(ExtHeadArgs g) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= g.n) return;
-    const int A = g.A;
-    float nz[kMaxA], a_[kMaxA], ev[kMaxA];
-    if (g.mode == 2) {
-        for (int a = 0; a < A; ++a) {
-            float u;
-            if (g.noise) u = g.noise[(size_t)i * A + a];
-            else {                                                                                // the uniform of the word pair sac_noise(rng, 8, i, a) turns into a normal
-                uint32_t o[4];
-                philox4x32_10((uint32_t)g.rng.key, (uint32_t)(g.rng.key >> 32), (uint32_t)g.rng.u, (uint32_t)(g.rng.u >> 32), 8u, (uint32_t)(i * 4 + a / 2), o);
-                u = u01_f32((a & 1) ? o[2] : o[0]);
-            }
-            const float lo = g.low[a], hi = g.high[a];
-            a_[a] = ext_rand_box_rn(u, lo, hi);
-            ev[a] = a_[a];
-        }
-    } else {
-        float ls[kMaxA], gg[kMaxA];
-        for (int a = 0; a < A; ++a) { ls[a] = g.log_std[a]; nz[a] = g.mode == 1 ? 0.f : (g.noise ? g.noise[(size_t)i * A + a] : sac_noise(g.rng, 8, i, a)); }
-        (void)squashed_sample_logp(g.mu + (size_t)i * A, ls, nz, A, a_, gg);
-        for (int a = 0; a < A; ++a) ev[a] = sac_to_env(a_[a], g.low[a], g.high[a]);
-    }
-    for (int a = 0; a < A; ++a) {
-        const size_t k = (size_t)i * A + a;
-        if (g.keep) g.keep[k] = a_[a];
-        if (g.stored) g.stored[k] = a_[a];
-        if (g.envact) g.envact[k] = ev[a];
-    }
-}
-// push! of the pending step from the caller's arrays: sac_push_block's flat (env, dim) walk over kPushEnvsPerBlock envs per workgroup.  A null tobs states "no env
-// was truncated": the block then reads nobs in its place, and a truncated flag set all the same raises the sticky error word (a plain vector store of an int, as
-// ext_record_kernel's; dril_sac_flush reads it after its drain)
-__global__ __launch_bounds__(256) void sac_ext_push_kernel(PushArgs g, int* err) {
-    const int e0 = blockIdx.x * kPushEnvsPerBlock, n = min(kPushEnvsPerBlock, g.E - e0);            // grid = ceil(E / kPushEnvsPerBlock): n >= 1
-    if (!g.tobs) {
-        if ((int)threadIdx.x < n && g.trunc[e0 + threadIdx.x]) *err = 1;
-        g.tobs = g.nobs;
-    }
-    sac_push_block(g, e0, n);
-}
-#include "dril_sac_ext_norm.h"   // NormalizeWrapperEnv / MonitorWrapperEnv on such a handle (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable): the act and push apply kernels
-
 }  // namespace
 
-// =================================================================================================================
-// handle
-// =================================================================================================================
-struct dril_sac_handle {
-    dril_sac_config cfg;
-    int D = 0, A = 0, S = 0, H1 = 0, H2 = 0, nmax = 0;
-    int P = 0, Pa = 0, Pq = 0;                       // host (ABI) layout: actor | q1 | q2 | log_std
-    int Pd = 0, Pqd = 0, log_std_off = 0;            // DEVICE layout: every net starts on a 16-byte boundary (float4 operand loads); pads stay zero
-    NetOff actor{}, q0{};                            // device offsets
-    hipStream_t stream = nullptr;
-    DevBuf<float> params, adam_m, adam_v, g_critic, g_actor;
-    float* target = nullptr;                         // alias: the target critics inside params
-    DevBuf<SacScalars> sc; DevBuf<float> stats; DevBuf<float> stats_out;
-    DevBuf<double> ssq_rows;   // [updates stats_out holds][adam_blocks_c + end_blocks] squared-gradient partials per update, summed on the host (grad_norm statistic)
-    DevBuf<unsigned int> counter; int adam_blocks_c = 0, end_blocks = 0;
-    DevBuf<SacScalars> sc_next;   // ping-pong partner of `sc` (fused heads: the entropy step writes the new state here, then the two are swapped)
-    DevBuf<double> head_partials; DevBuf<unsigned int> head_counter; DevBuf<unsigned> col_h1p; DevBuf<unsigned> col_w2p; DevBuf<int> col_flags; int col_tag = 0, col_w2tag = 0; bool col_w2_dirty = true, f16_fwd = true, l2_attr_set = false;   // the f16-piece collection forward (sac_collect_l2_kernel)
-    DevBuf<unsigned long long> it_stamps; double wall_hz = 1e8; bool fused_heads = true; bool fused_dw1 = false; int fl_c = 0, fl_a = 0; bool fused_collect = true; bool fused_fwd = true; bool trace_enqueue = false; std::vector<hipEvent_t> it_events; int iter_chunk = 64;   // fused output-layer + head kernels (DRIL_SAC_NO_FUSED_HEADS=1: the round-1 launch sequence, A/B)
-    int upd_route[3] = {-1, 0, 0}; mutable char upd_info[160] = {0};   // what the last sac_one_update enqueued: {first layers in the gather, PRE head, launched yet} (dril_sac_update_info)
-    float bt_actor[2], bt_critic[2], bt_ent[2]; int64_t grad_updates = 0; uint64_t update_counter = 0, aux_counter = 0;
-    float target_entropy = 0, act_lo = -2.0f, act_hi = 2.0f; bool external = false;   // bounds of the agent-facing action space: Box(-2,2), Box(-1,1) under ScalingWrapperEnv
-    DevBuf<float> act_bounds;                     // device table [low[kMaxA] | high[kMaxA]] the sampling kernels read: the pair above in every entry, or a plug-in's bounds per dimension
-    // env: the envs on the device — simulator state and counters, the seed, and for DRIL_ENV_MODULE the loaded plug-in (dril_env_side.h; SAC has no DiscreteAdapter and
-    // no fixed-length episodes: action_start 0, fixed_len 0)
-    DeviceEnvs env; bool fused_head_push = true;
-    DevBuf<float> obs_cur, obs_nxt, e_rew, e_tobs, e_raw, e_envact; DevBuf<uint8_t> e_term, e_trunc;
-    bool obs_valid = false;
-    // replay ring
-    long long cap = 0, size = 0, head = 0;
-    DevBuf<float> rb_obs, rb_next, rb_act, rb_rew; DevBuf<uint8_t> rb_term, rb_trunc;
-    // batch + activations
-    DevBuf<float> xa, ah1, ah2, mu;               // actor: [nmax][D], [nmax][H], [nmax][A]
-    DevBuf<float> xq, xq_pi; float* xq_next = nullptr;                 // [B][D+A]; xq_next: alias (second half of xq)
-    DevBuf<float> qh1, qh2; float *th1 = nullptr, *th2 = nullptr;      // [2][nq][H]; th1 / th2: aliases (z = 2,3 of qh1 / qh2)
-    DevBuf<float> q_cur, q_pi, dq; float* q_next = nullptr; // [2][nq]; q_next: alias (second half of q_cur)
-    DevBuf<float> dz2, dz1, dxq, dmu;            // [2][nq][H], [2][nq][D+A], [B][A]
-    DevBuf<float> b_rew, b_ne, b_nn, b_np, b_nlp, a_pi, g_pi, lp_pi; DevBuf<uint8_t> b_term;
-    int nq = 0;
-    // MonitorWrapperEnv (dril_sac_monitor_enable; mon_window == 0: off, every pointer null): running sums per env, the ring of the last mon_window finished episodes
-    // with meta = {count, head}, and the finished-episode block [mon_rows_cap][E] of the collection in flight (mon_row: its next row)
-    int mon_window = 0, mon_rows_cap = 0, mon_row = 0; DevBuf<float> mon_cur_ret, mon_ring_ret, mon_ep_ret; DevBuf<int32_t> mon_cur_len, mon_ring_len, mon_ep_len;
-    DevBuf<int> mon_meta; DevBuf<uint8_t> mon_flags;
-    // evaluate_agent (dril_sac_evaluate_agent): the env-side snapshot, the per-env running sums, the event list and its counter (pinned host word for the poll)
-    int eval_poll = 0; DevBuf<float> ev_state, ev_obs, ev_mon_ret, ev_cur_ret; DevBuf<int32_t> ev_sc, ev_mon_len, ev_cur_len; DevBuf<uint32_t> ev_ep, ev_gs;
-    DevBuf<unsigned int> ev_counter; PinnedBuf<unsigned int> ev_counter_host; DevBuf<SacEvalEvent> ev_events;
-    // dril_sac_collect_trajectory: ONE grow-only blob for the step-major recording, the shadow envs' arrays (plug-ins) and the table of bounds (the counter and its pinned word are the evaluation's)
-    DevBuf<char> traj_blob;
-    // NormalizeWrapperEnv (dril_sac_normalize_enable; nz.on false: every pointer null; kernels: dril_norm_wrap.h, dril_sac_norm.h).  nz_old_obs (E x D) is the raw
-    // observation of the envs' present state once nz_raw_valid
-    NormWrap nz; bool nz_raw_valid = false;
-    DevBuf<float> nz_returns, nz_old_obs, nz_old_rew;
-    // device-array verbs of an external handle (dril_sac_ext_*_device, dril_sac_update_enqueue, dril_sac_flush): the two hand-over events, the sticky error word and
-    // its pinned host copy, the pending statistics table (DRIL_SAC_PENDING_CAPACITY rows, allocated at create) + its squared-gradient partials, what a flush has to free, and the counters of the info struct
-    hipEvent_t ext_ev_in = nullptr, ext_ev_out = nullptr; DevBuf<int> ext_err; PinnedBuf<int> ext_err_host;
-    bool ext_acted = false, ext_bounds_set = false, in_device_verb = false;
-    int64_t fwd_launches = 0;                        // kernels enqueued through gemm / gemm_pair / the elementwise first layer since create: what `launches` of the info struct is counted from
-    DevBuf<float> pend_stats; DevBuf<double> pend_ssq; int pend_n = 0; struct InjectedBatches { DevBuf<long long> idx; DevBuf<float> ne, nn, np; }; std::vector<InjectedBatches> pend_free;
-    int64_t ext_steps_dev = 0, ext_steps_host = 0, ext_syncs = 0, ext_flushes = 0, ext_launches = 0;
-    // NormalizeWrapperEnv / MonitorWrapperEnv on an external handle (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable) live in nz / nz_* / mon_* above, which
-    // the built-in verbs never touch on such a handle.  xw_begin: the next act opens a collection (dril_sac_ext_collection_begin); xw_live: one is in progress (cleared
-    // by enable / set_stats / normalize_reset); the counters of dril_sac_ext_wrap_info
-    bool xw_begin = false, xw_live = false; int64_t xw_launches_act = 0, xw_launches_push = 0;
-    // cfg.profile_events on an external handle: HIP events around what act_device and push_device enqueue (a pair per call, recorded and never waited for); dril_sac_flush
-    // reads them after its drain into collect_ms / collect_steps (dril_sac_profile_get).  The pool is created at create (kXpPool events: nothing is created inside the
-    // sync-free verbs) and re-used after every flush; calls made while it is full are not timed
-    std::vector<hipEvent_t> xp_events; size_t xp_n = 0, xp_pairs = 0;
-    // injected inputs (tests)
-    DevBuf<float> collect_noise; size_t collect_noise_count = 0;
-    int inj_updates = 0; DevBuf<long long> inj_idx; DevBuf<float> inj_ne, inj_nn, inj_np;
-    // host-batch scratch
-    DevBuf<float> s_in, s_act, s_noise, s_out, s_out2;
-    // timing
-    hipEvent_t ev_a = nullptr, ev_b = nullptr; double collect_ms = 0, update_ms = 0; int64_t collect_steps = 0, updates = 0;
-    std::string err;
-};
-
-namespace {
-
+namespace dril::sac {
 int sfail(dril_sac_handle* h, int code, const std::string& msg) { if (h) h->err = msg; else g_sac_create_error = msg; return code; }
-#define SHIP(h, expr)                                                                                        \
-    do { hipError_t _e = (expr); if (_e != hipSuccess)                                                       \
-        return sfail(h, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
-#define SNEED(h) do { if (!(h)) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle"); (void)hipSetDevice((h)->cfg.device); } while (0)
-#define SDO(expr) do { int _rc = (expr); if (_rc != DRIL_OK) return _rc; } while (0)
-#define S_NOT_EXTERNAL(h, what) do { if ((h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, what ": the envs of DRIL_ENV_EXTERNAL live on the host (dril_sac_predict_actions + dril_sac_ext_push)"); } while (0)
-
-int round4(int x) { return (x + 3) & ~3; }
+}  // namespace dril::sac
+namespace {
 int gemm_pair(dril_sac_handle* h, GemmArgs a, int Za, GemmArgs b, int Zb) {
     SHIP(h, launch_gemm_pair(a, Za, b, Zb, h->stream)); h->fwd_launches += 1;
     return DRIL_OK;
 }
+}  // namespace
+namespace dril::sac {
 int gemm(dril_sac_handle* h, GemmArgs g, int Z) {
     SHIP(h, launch_gemm(g, Z, h->stream)); h->fwd_launches += 1;
     return DRIL_OK;
 }
 
-// One net = {W1 b1 W2 b2 W3 b3} at `P + off` (+ z * zP for the second critic); activations are (features x n) column-major
-struct NetBufs { float* h1; float* h2; float* out; long long zh, zo, zh2; };   // [Z][n][H1], [Z][n][O], [Z][n][H2]: batch strides of h1 / out / h2 (zh2 == 0: H1 == H2 shapes, use zh)
+// One net = {W1 b1 W2 b2 W3 b3} at `P + off` (+ z * zP for the second critic); activations are (features x n) column-major (NetBufs: dril_sac_handle.h)
 int net_forward(dril_sac_handle* h, const float* P, NetOff off, long long zP, int in, int O, const float* X, int ldx, long long zX, int n,
-                NetBufs b, int Z, int zdivX = 1, bool hidden_only = false, bool first_done = false) {
+                NetBufs b, int Z, int zdivX, bool hidden_only, bool first_done) {
     const int H1 = h->H1, H2 = h->H2, act = h->cfg.activation ? EPI_RELU : EPI_TANH;
     GemmArgs g = gemm_args();                                                       // h1 = act(W1 x + b1)
     // a narrow input (Pendulum: 3 features) over many rows (the collection forward): an elementwise pass instead of a K = 3 contraction
@@ -1454,7 +1166,7 @@ int net_forward(dril_sac_handle* h, const float* P, NetOff off, long long zP, in
 // reverse pass given dOut [Z][n][O]: parameter gradients into G (same layout as P; null = skip) and/or dX [Z][n][in] (null = skip)
 // have_dz2: the fused head kernel already wrote dz2 = (W3' dOut) .* act'(h2); then [dW3|db3], [dW2|db2] and dz1 share ONE launch (three independent contractions)
 int net_backward(dril_sac_handle* h, const float* P, NetOff off, long long zP, int in, int O, const float* X, int ldx, long long zX, int n,
-                 NetBufs b, const float* dOut, float* G, float* dX, int Z, bool have_dz2 = false, bool skip_w1 = false) {
+                 NetBufs b, const float* dOut, float* G, float* dX, int Z, bool have_dz2, bool skip_w1) {
     const int H1 = h->H1, H2 = h->H2, mask = h->cfg.activation ? EPI_MASK_RELU : EPI_MASK_TANH;
     const long long zd = (long long)h->nq * H1;   // dz buffers are [2][nq][H] (H1 == H2 layouts are separate buffers)
     const bool big = (long long)((H2 + 31) / 32) * ((n + 31) / 32) * Z >= 2048;          // large batches: one launch per contraction (the pair kernel is the split-K shape)
@@ -1481,11 +1193,10 @@ int net_backward(dril_sac_handle* h, const float* P, NetOff off, long long zP, i
     if (G && dX && !big) SDO(gemm_pair(h, w, Z, g, Z)); else { if (G) SDO(gemm(h, w, Z)); if (dX) SDO(gemm(h, g, Z)); }
     return DRIL_OK;
 }
-NetBufs actor_bufs(dril_sac_handle* h) { return NetBufs{h->ah1, h->ah2, h->mu, 0, 0, 0}; }
-NetBufs q_bufs(dril_sac_handle* h, float* h1, float* h2, float* out) { return NetBufs{h1, h2, out, (long long)h->nq * h->H1, (long long)h->nq, (long long)h->nq * h->H2}; }
 
 int ssync(dril_sac_handle* h) { if (h->in_device_verb) h->ext_syncs += 1; SHIP(h, hipStreamSynchronize(h->stream)); return DRIL_OK; }   // (ext_syncs: dril_sac_ext_device_info.host_syncs — a wait inside a sync-free verb is a bug it would show)
-
+}  // namespace dril::sac
+namespace {
 int adam_range(dril_sac_handle* h, int lo, int n, float* grads, const float* bt, double* ssq, int blocks, FirstLayerOpt fl = FirstLayerOpt{}) {
     AdamRangeArgs a{h->params + lo, h->adam_m + lo, h->adam_v + lo, grads ? grads + lo : nullptr, n, h->cfg.learning_rate, h->cfg.adam_beta1,
                     h->cfg.adam_beta2, h->cfg.adam_eps, bt[0], bt[1], ssq, fl};
@@ -1494,8 +1205,10 @@ int adam_range(dril_sac_handle* h, int lo, int n, float* grads, const float* bt,
     return DRIL_OK;
 }
 
+}  // namespace
+namespace dril::sac {
 // one update!(agent, alg, batch): sac.jl:299-404.  `slot` = index into the injected batches (-1 = Philox), `out` = device stats row
-int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long* stamp = nullptr, double* ssq_row_in = nullptr) {
+int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long* stamp, double* ssq_row_in) {
     double* ssq_row = ssq_row_in ? ssq_row_in : h->ssq_rows + (size_t)((out - h->stats_out) / 8) * (h->adam_blocks_c + h->end_blocks);   // this update's squared-gradient partials: [critic Adam blocks | end blocks] (ssq_row_in: a row of the pending table, dril_sac_update_enqueue)
     const int B = h->cfg.batch_size, D = h->D, A = h->A, W = D + A;
     const SacRng rng{h->cfg.seed ^ 0x5ac5ac5ac5ac5ac5ull, h->update_counter};
@@ -1606,11 +1319,15 @@ int ensure_obs(dril_sac_handle* h) {
     }
     return DRIL_OK;
 }
+}  // namespace dril::sac
+namespace {
 PushArgs push_args(dril_sac_handle* h, const float* obs, const float* nobs, unsigned long long* stamp) {
     const long long tail = (h->head + h->size) % h->cap;
     return PushArgs{h->cfg.n_envs, h->D, h->A, h->cap, tail, obs, h->e_raw, h->e_rew, h->e_tobs, nobs, h->e_term, h->e_trunc,
                     h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, stamp};
 }
+}  // namespace
+namespace dril::sac {
 void ring_advance(dril_sac_handle* h) {                                                            // CircularBuffer: n_envs rows in, overwrite the oldest
     const long long over = h->size + h->cfg.n_envs - h->cap;
     if (over > 0) { h->head = (h->head + over) % h->cap; h->size = h->cap; } else h->size += h->cfg.n_envs;
@@ -1623,6 +1340,8 @@ MonitorArgs monitor_row(dril_sac_handle* h) {
     m.cur_ret = h->mon_cur_ret; m.cur_len = h->mon_cur_len; m.ep_ret = h->mon_ep_ret + o; m.ep_len = h->mon_ep_len + o; m.flags_out = h->mon_flags + o;
     return m;
 }
+}  // namespace dril::sac
+namespace {
 // before a collection of n_steps: its block has n_steps rows (grown on demand: the start phase is the one long collection of a run)
 int monitor_begin(dril_sac_handle* h, int n_steps) {
     if (!h->mon_window) return DRIL_OK;
@@ -1634,6 +1353,8 @@ int monitor_begin(dril_sac_handle* h, int n_steps) {
     SHIP(h, h->mon_ep_ret.alloc_zero(n)); SHIP(h, h->mon_ep_len.alloc_zero(n)); SHIP(h, h->mon_flags.alloc_zero(n)); h->mon_rows_cap = n_steps;
     return DRIL_OK;
 }
+}  // namespace
+namespace dril::sac {
 // after its last step: the finished episodes of the whole collection into the window, one launch (sac_monitor_window_kernel)
 int monitor_end(dril_sac_handle* h) {
     if (!h->mon_window || h->mon_row == 0) return DRIL_OK;
@@ -1643,6 +1364,20 @@ int monitor_end(dril_sac_handle* h) {
     h->mon_row = 0;
     return DRIL_OK;
 }
+// the launches another unit enqueues: the action head of all envs (a plug-in's evaluation step), the ring write of one env step (dril_sac_ext_push), and for a
+// built-in Box kind (A = 1) the ONE launch of an evaluation / a trajectory step over the collection's grid
+void launch_collect_head(dril_sac_handle* h, const CollectHeadArgs& ca) { hipLaunchKernelGGL(sac_collect_head_kernel, dim3((h->cfg.n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca); }
+void launch_push(dril_sac_handle* h, const PushArgs& pa) { hipLaunchKernelGGL(sac_push_kernel, dim3((pa.E + 255) / 256), dim3(256), 0, h->stream, pa); }
+hipError_t launch_eval_env(dril_sac_handle* h, const EvalEnvArgs& a) {
+    const dim3 grid((h->cfg.n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
+    return with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_eval_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, a); return hipGetLastError(); });
+}
+hipError_t launch_traj_env(dril_sac_handle* h, const TrajEnvArgs& a) {
+    const dim3 grid((h->cfg.n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
+    return with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { hipLaunchKernelGGL(sac_traj_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, a); return hipGetLastError(); });
+}
+}  // namespace dril::sac
+namespace {
 // head -> act! + observe -> push! of one collection step over a device env plug-in (the actor's hidden layers are already enqueued).  `first` / `last`: the step's
 // place in its collection — the fused form pushes step t's rows in the launch that computes the head of step t + 1, the last step's rows in a launch of their own,
 // so the ring is complete when the collection returns.
@@ -1672,6 +1407,8 @@ int collect_step_module(dril_sac_handle* h, const CollectHeadArgs& ca, unsigned 
     SHIP(h, hipGetLastError());
     return DRIL_OK;
 }
+}  // namespace
+namespace dril::sac {
 // predict_actions_raw (off_policy_collection.jl:55, evaluation.jl:94) up to the output layer, for the envs' current observations: the hidden layers as contractions
 // (the first one inside the second's staging when the input is narrow); the output layer inside the head / env kernel that follows (fused_fwd;
 // DRIL_SAC_NO_FUSED_FWD=1: three contractions and mu through memory, the round 1 - 3 form).  Returns the head's argument block; a collection step and an
@@ -1716,6 +1453,8 @@ hipError_t normalize_alloc(dril_sac_handle* h, size_t rows) {
     if (e == hipSuccess) e = h->nz_old_rew.alloc_zero(E);
     return e;
 }
+}  // namespace dril::sac
+namespace {
 // the raw observation of the envs' present state in nz_old_obs (reset! :110-121 stores it; so does every observe)
 int nz_ensure_raw(dril_sac_handle* h) {
     if (!h->env.ready) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_env_reset has not been called");
@@ -1724,6 +1463,8 @@ int nz_ensure_raw(dril_sac_handle* h) {
     h->nz_raw_valid = true;
     return DRIL_OK;
 }
+}  // namespace
+namespace dril::sac {
 // norm_moments_kernel over nz_old_obs (obs) and / or the `returns` recursion over e_rew (ret); *rows: the rows of the table it writes
 // (raw / rew: the arrays — the handle's own, or the caller's const ones on an external handle; null: that half is not summed)
 int nz_moments_over(dril_sac_handle* h, const float* raw, const float* rew, int* rows) {
@@ -1734,7 +1475,11 @@ int nz_moments_over(dril_sac_handle* h, const float* raw, const float* rew, int*
     SHIP(h, hipGetLastError());
     return DRIL_OK;
 }
+}  // namespace dril::sac
+namespace {
 int nz_moments(dril_sac_handle* h, bool obs, bool ret, int* rows) { return nz_moments_over(h, obs ? h->nz_old_obs : nullptr, ret ? h->e_rew : nullptr, rows); }
+}  // namespace
+namespace dril::sac {
 // sac_norm_apply_kernel over the table of `rows` rows the moments launch wrote
 int nz_apply(dril_sac_handle* h, NzApplyArgs p, int rows, bool upd_obs, bool upd_ret) {
     NormWrapArgs& a = p.w;
@@ -1746,6 +1491,8 @@ int nz_apply(dril_sac_handle* h, NzApplyArgs p, int rows, bool upd_obs, bool upd
     h->nz.commit(a);
     return DRIL_OK;
 }
+}  // namespace dril::sac
+namespace {
 // observe(env) of the wrapper (:123-137) over the envs' present state into `out`; update = false: a read-only peek
 int nz_observe(dril_sac_handle* h, bool update, float* out) {
     SDO(nz_ensure_raw(h));
@@ -1836,8 +1583,10 @@ void fill_stats(const dril_sac_handle* h, const float* rows, int n, dril_sac_sta
         s.entropy_coefficient = r[4]; s.grad_norm = r[5]; s.has_entropy_loss = h->cfg.auto_ent_coef ? 1 : 0;
     }
 }
+}  // namespace
+namespace dril::sac {
 // the statistics rows of the last n gradient steps (stream drained): device rows + the squared-gradient partials summed here
-int fetch_stats(dril_sac_handle* h, int n, dril_sac_stats* out, const float* rows_dev = nullptr, const double* ssq_dev = nullptr) {   // (rows_dev / ssq_dev: the pending table of dril_sac_update_enqueue; null: the table of dril_sac_update)
+int fetch_stats(dril_sac_handle* h, int n, dril_sac_stats* out, const float* rows_dev, const double* ssq_dev) {
     std::vector<float> rows((size_t)n * 8);
     SHIP(h, hipMemcpy(rows.data(), rows_dev ? rows_dev : h->stats_out, rows.size() * 4, hipMemcpyDeviceToHost));
     const int nb = h->adam_blocks_c + h->end_blocks;
@@ -1847,6 +1596,8 @@ int fetch_stats(dril_sac_handle* h, int n, dril_sac_stats* out, const float* row
     fill_stats(h, rows.data(), n, out);
     return DRIL_OK;
 }
+}  // namespace dril::sac
+namespace {
 int run_updates(dril_sac_handle* h, int n_updates, bool injected, dril_sac_stats* out) {
     if (h->size <= 0) return sfail(h, DRIL_ERR_NOT_INITIALISED, "the replay buffer is empty");
     SDO(ensure_stats(h, n_updates));
@@ -1977,57 +1728,6 @@ int check_sac_plugin(const DrilEnvPluginDesc& d, std::string& msg) {
         }
     return DRIL_OK;
 }
-int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sac_handle** out);
-}  // namespace
-
-DRIL_EXPORT int32_t dril_sac_create(const dril_sac_config* cfg, dril_sac_handle** out) {
-    if (cfg && cfg->abi_version == DRIL_SAC_ABI_VERSION && cfg->env_kind == DRIL_ENV_MODULE) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC on a device env plug-in (DRIL_ENV_MODULE) needs the plug-in's code object: use dril_sac_create_with_env_module(cfg, code_object_path, out)");
-    return sac_create_impl(cfg, nullptr, out);
-}
-DRIL_EXPORT int32_t dril_sac_create_with_env_module(const dril_sac_config* cfg, const char* code_object_path, dril_sac_handle** out) {
-    if (!cfg || !out) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "null config / out pointer");
-    if (cfg->abi_version != DRIL_SAC_ABI_VERSION) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_config.abi_version mismatch");
-    if (cfg->env_kind != DRIL_ENV_MODULE) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_create_with_env_module: cfg->env_kind must be DRIL_ENV_MODULE");
-    std::string msg; const int rc = check_code_object_path(code_object_path, msg);
-    if (rc) return sfail(nullptr, rc, "dril_sac_create_with_env_module: " + msg);
-    return sac_create_impl(cfg, code_object_path, out);
-}
-DRIL_EXPORT int32_t dril_sac_env_module_info_of(const dril_sac_handle* h, dril_env_module_info* out) {
-    if (!h || !out) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle / out");
-    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_info_of: the handle was not created with dril_sac_create_with_env_module");
-    fill_module_info(h->env.desc, out);
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_env_module_obs_space_of(const dril_sac_handle* h, float* low, float* high, int32_t* declared) {
-    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_obs_space_of: the handle was not created with dril_sac_create_with_env_module");
-    const int D = h->env.desc.D;
-    if (low) std::memcpy(low, h->env.obs_low.data(), (size_t)D * 4);
-    if (high) std::memcpy(high, h->env.obs_high.data(), (size_t)D * 4);
-    if (declared) *declared = h->env.obs_declared ? 1 : 0;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_scaling_enable(dril_sac_handle* h, int32_t on) {
-    SNEED(h);
-    std::string msg; const int rc = h->env.set_scaling(on != 0, msg);
-    if (rc) return sfail(h, rc, "dril_sac_scaling_enable: " + msg);
-    // the adapters act on the wrapper's action space: the table the sampling kernels read (TanhScaleAdapter per dimension, rand(action_space) of the start phase).
-    // The envs have not been reset, so nothing that reads the table is in flight.
-    float tb[2 * kMaxA];
-    SHIP(h, hipMemcpy(tb, h->act_bounds, sizeof(tb), hipMemcpyDeviceToHost));
-    h->env.agent_action_space(tb, tb + kMaxA);
-    SHIP(h, hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_agent_spaces(const dril_sac_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling) {
-    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_agent_spaces: the handle was not created with dril_sac_create_with_env_module");
-    h->env.agent_obs_space(obs_low, obs_high); h->env.agent_action_space(action_low, action_high);
-    if (scaling) *scaling = h->env.scaling ? 1 : 0;
-    return DRIL_OK;
-}
-
-namespace {
 int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sac_handle** out) {
     if (!cfg || !out) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "null config / out pointer");
     if (cfg->abi_version != DRIL_SAC_ABI_VERSION) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_config.abi_version mismatch");
@@ -2121,6 +1821,54 @@ int sac_create_impl(const dril_sac_config* cfg, const char* module_path, dril_sa
     return DRIL_OK;
 }
 }  // namespace
+
+DRIL_EXPORT int32_t dril_sac_create(const dril_sac_config* cfg, dril_sac_handle** out) {
+    if (cfg && cfg->abi_version == DRIL_SAC_ABI_VERSION && cfg->env_kind == DRIL_ENV_MODULE) return sfail(nullptr, DRIL_ERR_UNSUPPORTED, "SAC on a device env plug-in (DRIL_ENV_MODULE) needs the plug-in's code object: use dril_sac_create_with_env_module(cfg, code_object_path, out)");
+    return sac_create_impl(cfg, nullptr, out);
+}
+DRIL_EXPORT int32_t dril_sac_create_with_env_module(const dril_sac_config* cfg, const char* code_object_path, dril_sac_handle** out) {
+    if (!cfg || !out) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "null config / out pointer");
+    if (cfg->abi_version != DRIL_SAC_ABI_VERSION) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_config.abi_version mismatch");
+    if (cfg->env_kind != DRIL_ENV_MODULE) return sfail(nullptr, DRIL_ERR_INVALID_ARG, "dril_sac_create_with_env_module: cfg->env_kind must be DRIL_ENV_MODULE");
+    std::string msg; const int rc = check_code_object_path(code_object_path, msg);
+    if (rc) return sfail(nullptr, rc, "dril_sac_create_with_env_module: " + msg);
+    return sac_create_impl(cfg, code_object_path, out);
+}
+DRIL_EXPORT int32_t dril_sac_env_module_info_of(const dril_sac_handle* h, dril_env_module_info* out) {
+    if (!h || !out) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle / out");
+    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_info_of: the handle was not created with dril_sac_create_with_env_module");
+    fill_module_info(h->env.desc, out);
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_env_module_obs_space_of(const dril_sac_handle* h, float* low, float* high, int32_t* declared) {
+    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_env_module_obs_space_of: the handle was not created with dril_sac_create_with_env_module");
+    const int D = h->env.desc.D;
+    if (low) std::memcpy(low, h->env.obs_low.data(), (size_t)D * 4);
+    if (high) std::memcpy(high, h->env.obs_high.data(), (size_t)D * 4);
+    if (declared) *declared = h->env.obs_declared ? 1 : 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_scaling_enable(dril_sac_handle* h, int32_t on) {
+    SNEED(h);
+    std::string msg; const int rc = h->env.set_scaling(on != 0, msg);
+    if (rc) return sfail(h, rc, "dril_sac_scaling_enable: " + msg);
+    // the adapters act on the wrapper's action space: the table the sampling kernels read (TanhScaleAdapter per dimension, rand(action_space) of the start phase).
+    // The envs have not been reset, so nothing that reads the table is in flight.
+    float tb[2 * kMaxA];
+    SHIP(h, hipMemcpy(tb, h->act_bounds, sizeof(tb), hipMemcpyDeviceToHost));
+    h->env.agent_action_space(tb, tb + kMaxA);
+    SHIP(h, hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_sac_agent_spaces(const dril_sac_handle* h, float* obs_low, float* obs_high, float* action_low, float* action_high, int32_t* scaling) {
+    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!h->env.module) return sfail(const_cast<dril_sac_handle*>(h), DRIL_ERR_UNSUPPORTED, "dril_sac_agent_spaces: the handle was not created with dril_sac_create_with_env_module");
+    h->env.agent_obs_space(obs_low, obs_high); h->env.agent_action_space(action_low, action_high);
+    if (scaling) *scaling = h->env.scaling ? 1 : 0;
+    return DRIL_OK;
+}
+
 DRIL_EXPORT const char* dril_sac_last_error(const dril_sac_handle* h) { return h ? h->err.c_str() : g_sac_create_error.c_str(); }
 DRIL_EXPORT int32_t dril_sac_obs_dim(const dril_sac_handle* h) { return h ? h->D : 0; }
 DRIL_EXPORT int32_t dril_sac_action_dim(const dril_sac_handle* h) { return h ? h->A : 0; }
@@ -2284,265 +2032,6 @@ DRIL_EXPORT int32_t dril_sac_collect_rollout(dril_sac_handle* h, int32_t n_steps
 DRIL_EXPORT int32_t dril_sac_collect_continue(dril_sac_handle* h, int32_t n_steps, int32_t use_random_actions, double* fps) {
     SNEED(h); S_NOT_EXTERNAL(h, "dril_sac_collect_continue"); return collect(h, n_steps, use_random_actions != 0, fps, true);
 }
-// one env step of the caller's host envs into the ring: the same push kernel as the device collection (truncated envs store their terminal observation)
-DRIL_EXPORT int32_t dril_sac_ext_push(dril_sac_handle* h, const float* obs, const float* stored_actions, const float* rewards, const uint8_t* terminated,
-                                      const uint8_t* truncated, const float* next_obs, const float* terminal_obs) {
-    SNEED(h);
-    if (h->env.module) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the env of a device env plug-in (DRIL_ENV_MODULE) is on the device, not on the host: dril_sac_collect_rollout steps it");
-    if (!h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: the handle was not created with DRIL_ENV_EXTERNAL");
-    if (!obs || !stored_actions || !rewards || !terminated || !truncated || !next_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: null pointer");
-    if (h->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: a dril_sac_ext_act_device step is pending; dril_sac_ext_push_device completes it");
-    if (h->nz.on || h->mon_window) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_push: wrapper on: use the device verbs, or wrap the host env on the host (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable are honoured by dril_sac_ext_act_device / _push_device only)");
-    const size_t E = h->cfg.n_envs, D = h->D, A = h->A;
-    bool any_trunc = false; for (size_t e = 0; e < E; ++e) any_trunc = any_trunc || truncated[e] != 0;
-    if (any_trunc && !terminal_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push: truncated envs need terminal_obs");
-    SHIP(h, hipMemcpyAsync(h->obs_cur, obs, E * D * 4, hipMemcpyHostToDevice, h->stream));
-    SHIP(h, hipMemcpyAsync(h->obs_nxt, next_obs, E * D * 4, hipMemcpyHostToDevice, h->stream));
-    SHIP(h, hipMemcpyAsync(h->e_raw, stored_actions, E * A * 4, hipMemcpyHostToDevice, h->stream));
-    SHIP(h, hipMemcpyAsync(h->e_rew, rewards, E * 4, hipMemcpyHostToDevice, h->stream));
-    SHIP(h, hipMemcpyAsync(h->e_term, terminated, E, hipMemcpyHostToDevice, h->stream));
-    SHIP(h, hipMemcpyAsync(h->e_trunc, truncated, E, hipMemcpyHostToDevice, h->stream));
-    if (any_trunc) SHIP(h, hipMemcpyAsync(h->e_tobs, terminal_obs, E * D * 4, hipMemcpyHostToDevice, h->stream));
-    const long long tail = (h->head + h->size) % h->cap;
-    PushArgs pa{(int)E, (int)D, (int)A, h->cap, tail, h->obs_cur, h->e_raw, h->e_rew, h->e_tobs, h->obs_nxt, h->e_term, h->e_trunc,
-                h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc};
-    hipLaunchKernelGGL(sac_push_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, h->stream, pa);
-    SHIP(h, hipGetLastError());
-    const long long over = h->size + (long long)E - h->cap;                                       // CircularBuffer: overwrite the oldest
-    if (over > 0) { h->head = (h->head + over) % h->cap; h->size = h->cap; } else h->size += (long long)E;
-    h->ext_steps_host += 1;
-    return ssync(h);                                                                              // the caller's arrays are pageable host memory: drain before returning
-}
-
-
-// ---- the same loop on DEVICE arrays: nothing below waits on the host except dril_sac_flush (include/dril_sac.h) --------------------------------------------
-namespace {
-constexpr int kPendingCap = DRIL_SAC_PENDING_CAPACITY;
-#define S_EXTERNAL_ONLY(h, verb) do { if (!(h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, verb ": the handle was not created with DRIL_ENV_EXTERNAL"); } while (0)
-// a wait inside the scope of one of these is counted (ssync): dril_sac_ext_device_info.host_syncs
-struct DeviceVerbScope { dril_sac_handle* h; explicit DeviceVerbScope(dril_sac_handle* h_) : h(h_) { h->in_device_verb = true; } ~DeviceVerbScope() { h->in_device_verb = false; } };
-// once the handle's stream has taken over from the caller's, EVERY way out of the verb hands it back: a step that fails half-way still leaves the caller's stream
-// ordered behind what was already enqueued.  give() is the successful path (its status is the verb's); the destructor covers the early returns
-struct StreamHandOver {
-    dril_sac_handle* h; void* caller; bool given = false;
-    StreamHandOver(dril_sac_handle* h_, void* caller_) : h(h_), caller(caller_) {}
-    hipError_t give() { given = true; return ext_stream_give(h->stream, h->ext_ev_out, caller); }
-    ~StreamHandOver() { if (!given && ext_stream_give(h->stream, h->ext_ev_out, caller) != hipSuccess) (void)hipGetLastError(); }
-};
-// cfg.profile_events: a pair of events of the handle's pool around what one act or push enqueues.  The scope takes the pair when the pool (created with the handle)
-// has one left — a call made while it is full is not timed, nothing is ever created here — and a verb that fails between its two marks gives the pair back, so the
-// pool always holds whole pairs
-struct XpScope {
-    dril_sac_handle* h; size_t n0; bool on, ok = false;
-    explicit XpScope(dril_sac_handle* h_) : h(h_), n0(h_->xp_n), on(h_->xp_n + 2 <= h_->xp_events.size()) {}
-    hipError_t mark() { if (!on) return hipSuccess; const hipError_t e = hipEventRecord(h->xp_events[h->xp_n], h->stream); if (e == hipSuccess) h->xp_n += 1; return e; }
-    ~XpScope() { if (!ok) h->xp_n = n0; }
-};
-int sac_check_ptr(dril_sac_handle* h, const char* verb, const char* name, const void* p, size_t bytes) {
-    const std::string msg = ext_ptr_problem(h->cfg.device, verb, name, p, bytes);
-    return msg.empty() ? DRIL_OK : sfail(h, DRIL_ERR_INVALID_ARG, msg);
-}
-// actor means of n rows already in `x` (device), then the head: net_forward is the call dril_sac_predict_actions makes (actor_chunk), so the means are its bits
-int actor_device_rows(dril_sac_handle* h, const float* x, int n, int mode, const float* d_noise, float* stored, float* envact, float* keep) {
-    if (mode != 2) { const int64_t l0 = h->fwd_launches; SDO(net_forward(h, h->params, h->actor, 0, h->D, h->A, x, h->D, 0, n, actor_bufs(h), 1)); h->ext_launches += h->fwd_launches - l0; }
-    SacRng rng{0, 0};
-    if (mode != 1 && !d_noise) rng = SacRng{h->cfg.seed ^ 0x0b5e55edull, h->aux_counter++};       // the handle's stream: one counter per chunk, as actor_chunk (taken once the forward is enqueued: a failed call leaves the stream's position alone)
-    ExtHeadArgs g{n, h->A, mode, h->mu, h->params + h->log_std_off, d_noise, rng, h->act_bounds, h->act_bounds + kMaxA, stored, envact, keep};
-    hipLaunchKernelGGL(sac_ext_head_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, g);
-    SHIP(h, hipGetLastError());
-    h->ext_launches += 1;
-    return DRIL_OK;
-}
-// ---- the wrappers of an external handle inside the device verbs (kernels: dril_sac_ext_norm.h) ----
-int xs_epb(int n, int D) { return std::max(std::min(64, std::max(1, 2048 / D)), (n + 127) / 128); }   // (nz_apply's split: a block's share of the rows)
-// observe (:123-137) of n rows of the caller's array into `out`, in the place of the unwrapped verb's device-to-device copy.  opening: a collection's first act — the
-// one observe that updates the statistics (one more launch: the moments); cache: the wrapper's old_obs takes the rows (not for predict)
-int xw_observe(dril_sac_handle* h, const float* raw, int n, float* out, bool opening, bool cache) {
-    const bool upd = opening && h->nz.cfg.training && h->nz.cfg.norm_obs;
-    int rows = 0;
-    if (upd) { SDO(nz_moments_over(h, raw, nullptr, &rows)); h->ext_launches += 1; h->xw_launches_act += 1; }
-    XsActArgs p{}; NormWrapArgs& a = p.w;
-    h->nz.fill(a, upd, false, h->cfg.n_envs);
-    a.E = n; a.rows = rows; a.epb = xs_epb(n, h->D); a.raw = raw; a.obs_out = out; p.old_obs = cache ? h->nz_old_obs : nullptr;
-    hipLaunchKernelGGL(sac_ext_norm_act_kernel, dim3((n + a.epb - 1) / a.epb), dim3(256), nz_apply_lds(h->D), h->stream, p);
-    SHIP(h, hipGetLastError());
-    h->nz.commit(a); h->ext_launches += 1;
-    return DRIL_OK;
-}
-// act! + observe + push! of the pending step under a wrapper, in the place of sac_ext_push_kernel: the moments over the caller's next observations and rewards (ONE
-// launch, only where statistics are updated), then the apply-and-push kernel.  The monitor's block of buffered steps is collected first when it is full
-int xw_push(dril_sac_handle* h, const PushArgs& pa, const float* d_terminal_obs) {
-    const bool nzon = h->nz.on, upd_obs = nzon && h->nz.cfg.training && h->nz.cfg.norm_obs, upd_ret = nzon && h->nz.cfg.training && h->nz.cfg.norm_reward;
-    const int E = h->cfg.n_envs, D = h->D;
-    int rows = 0;
-    if (upd_obs || upd_ret) { SDO(nz_moments_over(h, upd_obs ? pa.nobs : nullptr, upd_ret ? pa.rew : nullptr, &rows)); h->ext_launches += 1; h->xw_launches_push += 1; }
-    if (h->mon_window && h->mon_row >= h->mon_rows_cap) { SDO(monitor_end(h)); h->ext_launches += 1; h->xw_launches_push += 1; }
-    XsPushArgs p{}; NormWrapArgs& a = p.w;
-    if (nzon) h->nz.fill(a, upd_obs, upd_ret, E); else a.D = D;
-    a.E = E; a.rows = rows; a.epb = xs_epb(E, D); a.raw = pa.nobs; a.rew = pa.rew; a.term = pa.term; a.trunc = pa.trunc; a.returns = h->nz_returns;
-    p.has_norm = nzon ? 1 : 0; p.tobs = d_terminal_obs; p.old_obs = h->nz_old_obs; p.old_rew = h->nz_old_rew; p.push = pa; p.err = h->ext_err;
-    const MonitorArgs m = monitor_row(h);
-    p.mon_cur_ret = m.cur_ret; p.mon_cur_len = m.cur_len; p.ep_ret = m.ep_ret; p.ep_len = m.ep_len; p.ep_flags = m.flags_out;
-    hipLaunchKernelGGL(sac_ext_norm_push_kernel, dim3((E + a.epb - 1) / a.epb), dim3(256), nzon ? xs_push_lds(D) : 0, h->stream, p);
-    SHIP(h, hipGetLastError());
-    if (nzon) h->nz.commit(a);
-    if (h->mon_window) h->mon_row += 1;
-    h->ext_launches += 1;
-    return DRIL_OK;
-}
-}  // namespace
-DRIL_EXPORT int32_t dril_sac_ext_act_device(dril_sac_handle* h, const float* d_obs, int32_t use_random_actions, const float* d_noise, float* d_stored_actions,
-                                            float* d_env_actions, void* caller_stream) {
-    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_ext_act_device");
-    if (!d_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_act_device: null obs");
-    if (h->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_act_device: the previous step has no dril_sac_ext_push_device yet");
-    const size_t E = h->cfg.n_envs, D = h->D, A = h->A;
-    SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_obs", d_obs, E * D * 4));
-    if (d_noise) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_noise", d_noise, E * A * 4));
-    if (d_stored_actions) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_stored_actions", d_stored_actions, E * A * 4));
-    if (d_env_actions) SDO(sac_check_ptr(h, "dril_sac_ext_act_device", "d_env_actions", d_env_actions, E * A * 4));
-    if (h->nz.on && !h->xw_begin && !h->xw_live)
-        return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_ext_act_device: no collection is in progress under NormalizeWrapperEnv (wrapper switched, statistics set or wrapper reset since the last step): dril_sac_ext_collection_begin marks the act that opens one");
-    DeviceVerbScope scope(h);
-    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
-    StreamHandOver back(h, caller_stream);
-    XpScope xp(h); SHIP(h, xp.mark());
-    if (h->nz.on) {                                                                                // observe through the wrapper: normalised into obs_cur, raw into old_obs, from one read
-        SDO(xw_observe(h, d_obs, (int)E, h->obs_cur, h->xw_begin, true));
-        h->xw_begin = false; h->xw_live = true;
-    } else {
-        SHIP(h, hipMemcpyAsync(h->obs_cur, d_obs, E * D * 4, hipMemcpyDeviceToDevice, h->stream)); // the pending step's observation; the forward reads it from here
-        h->ext_launches += 1;
-    }
-    SDO(actor_device_rows(h, h->obs_cur, (int)E, use_random_actions ? 2 : 0, d_noise, d_stored_actions, d_env_actions, h->e_raw));
-    SHIP(h, xp.mark()); xp.ok = true;
-    SHIP(h, back.give());
-    h->ext_acted = true;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_predict_actions_device(dril_sac_handle* h, const float* d_obs, int64_t batch, int32_t deterministic, const float* d_noise,
-                                                    float* d_raw_actions, float* d_env_actions, void* caller_stream) {
-    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_predict_actions_device");
-    if (!d_obs || batch < 1) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_predict_actions_device: null obs or batch < 1");
-    if (!d_raw_actions && !d_env_actions) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_predict_actions_device: null actions");
-    const size_t B = (size_t)batch, D = h->D, A = h->A;
-    SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_obs", d_obs, B * D * 4));
-    if (d_noise) SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_noise", d_noise, B * A * 4));
-    if (d_raw_actions) SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_raw_actions", d_raw_actions, B * A * 4));
-    if (d_env_actions) SDO(sac_check_ptr(h, "dril_sac_predict_actions_device", "d_env_actions", d_env_actions, B * A * 4));
-    DeviceVerbScope scope(h);
-    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
-    StreamHandOver back(h, caller_stream);
-    for (int64_t o = 0; o < batch; o += h->nmax) {                                                 // chunks of nmax rows, as the host verb: stream order keeps the scratch rows apart
-        const int n = (int)std::min<int64_t>(h->nmax, batch - o);
-        if (h->nz.on && h->nz.cfg.norm_obs) SDO(xw_observe(h, d_obs + o * D, n, h->xa, false, false));   // the statistics in force; nothing of the wrapper is written
-        else { SHIP(h, hipMemcpyAsync(h->xa, d_obs + o * D, (size_t)n * D * 4, hipMemcpyDeviceToDevice, h->stream)); h->ext_launches += 1; }
-        SDO(actor_device_rows(h, h->xa, n, deterministic ? 1 : 0, deterministic || !d_noise ? nullptr : d_noise + o * A,
-                              d_raw_actions ? d_raw_actions + o * A : nullptr, d_env_actions ? d_env_actions + o * A : nullptr, nullptr));
-    }
-    SHIP(h, back.give());
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_push_device(dril_sac_handle* h, const float* d_rewards, const uint8_t* d_terminated, const uint8_t* d_truncated,
-                                             const float* d_next_obs, const float* d_terminal_obs, void* caller_stream) {
-    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_ext_push_device");
-    if (!d_rewards || !d_terminated || !d_truncated || !d_next_obs) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push_device: null rewards / terminated / truncated / next_obs");
-    if (!h->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_push_device without a preceding dril_sac_ext_act_device");
-    const size_t E = h->cfg.n_envs, D = h->D;
-    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_rewards", d_rewards, E * 4));
-    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_terminated", d_terminated, E));
-    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_truncated", d_truncated, E));
-    SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_next_obs", d_next_obs, E * D * 4));
-    if (d_terminal_obs) SDO(sac_check_ptr(h, "dril_sac_ext_push_device", "d_terminal_obs", d_terminal_obs, E * D * 4));
-    DeviceVerbScope scope(h);
-    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
-    StreamHandOver back(h, caller_stream);
-    XpScope xp(h); SHIP(h, xp.mark());
-    const long long tail = (h->head + h->size) % h->cap;
-    PushArgs pa{(int)E, (int)D, h->A, h->cap, tail, h->obs_cur, h->e_raw, d_rewards, d_terminal_obs, d_next_obs, d_terminated, d_truncated,
-                h->rb_obs, h->rb_next, h->rb_act, h->rb_rew, h->rb_term, h->rb_trunc, nullptr};
-    if (h->nz.on || h->mon_window) SDO(xw_push(h, pa, d_terminal_obs));
-    else {
-        hipLaunchKernelGGL(sac_ext_push_kernel, dim3((unsigned)((E + kPushEnvsPerBlock - 1) / kPushEnvsPerBlock)), dim3(256), 0, h->stream, pa, h->ext_err);
-        SHIP(h, hipGetLastError());
-        h->ext_launches += 1;
-    }
-    ring_advance(h);                                                                              // head / size are host counters: nothing to wait for
-    SHIP(h, xp.mark()); xp.ok = true;
-    SHIP(h, back.give());
-    h->ext_acted = false; h->ext_steps_dev += 1;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_update_enqueue(dril_sac_handle* h, int32_t n_updates) {
-    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_update_enqueue");
-    if (n_updates <= 0) return sfail(h, DRIL_ERR_INVALID_ARG, "n_updates must be positive");
-    if (h->inj_updates && h->inj_updates != n_updates) return sfail(h, DRIL_ERR_INVALID_ARG, "injected batches were set for a different n_updates");
-    if ((int64_t)h->pend_n + n_updates > kPendingCap)
-        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_update_enqueue: " + std::to_string(h->pend_n) + " pending + " + std::to_string(n_updates) + " new statistics rows exceed the pending table of " + std::to_string(kPendingCap) + ": flush first (dril_sac_flush)");
-    if (h->size <= 0) return sfail(h, DRIL_ERR_NOT_INITIALISED, "the replay buffer is empty");
-    const int nb = h->adam_blocks_c + h->end_blocks;
-    DeviceVerbScope scope(h);
-    const bool injected = h->inj_updates != 0;
-    int rc = DRIL_OK;
-    for (int k = 0; k < n_updates && rc == DRIL_OK; ++k) {
-        const size_t row = (size_t)h->pend_n;
-        rc = sac_one_update(h, injected ? k : -1, h->pend_stats + row * 8, nullptr, h->pend_ssq + row * nb);
-        if (rc == DRIL_OK) h->pend_n += 1;
-    }
-    // the injected batches are read by launches still in flight: freeing them would wait for the device, so they go with the next flush
-    if (h->inj_idx || h->inj_ne || h->inj_nn || h->inj_np) h->pend_free.push_back(dril_sac_handle::InjectedBatches{std::move(h->inj_idx), std::move(h->inj_ne), std::move(h->inj_nn), std::move(h->inj_np)});
-    h->inj_updates = 0;
-    return rc;
-}
-DRIL_EXPORT int32_t dril_sac_flush(dril_sac_handle* h, dril_sac_stats* stats, int64_t stats_capacity, int64_t* n_stats) {
-    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_flush");
-    SDO(monitor_end(h));                                                                           // MonitorWrapperEnv (dril_sac_ext_monitor_enable): the episodes of the steps since the last collection into the window
-    SHIP(h, hipMemcpyAsync(h->ext_err_host, h->ext_err, 4, hipMemcpyDeviceToHost, h->stream));
-    SDO(ssync(h));
-    h->ext_flushes += 1;
-    for (size_t i = 0; i + 1 < h->xp_n; i += 2) { float ms = 0; if (hipEventElapsedTime(&ms, h->xp_events[i], h->xp_events[i + 1]) == hipSuccess) h->collect_ms += ms; }   // cfg.profile_events: an act and a push per env step
-    h->collect_steps += (int64_t)(h->xp_n / 4); h->xp_n = 0;                                       // (a step = an act and a push: four events)
-    h->pend_free.clear();
-    const int n = h->pend_n;
-    if (n_stats) *n_stats = n;
-    if (n > 0 && stats && stats_capacity > 0) {
-        std::vector<dril_sac_stats> tmp((size_t)n);
-        SDO(fetch_stats(h, n, tmp.data(), h->pend_stats, h->pend_ssq));
-        for (int64_t k = 0; k < std::min<int64_t>(stats_capacity, n); ++k) stats[k] = tmp[(size_t)k];
-    }
-    h->pend_n = 0;
-    if (*h->ext_err_host) {
-        *h->ext_err_host = 0;
-        SHIP(h, hipMemsetAsync(h->ext_err, 0, 4, h->stream));
-        return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_flush: a dril_sac_ext_push_device call had truncated envs and terminal_obs == NULL (infos[i][\"terminal_observation\"], off_policy_collection.jl:75-79); the rows of that push stay in the ring with next_obs in its place");
-    }
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_set_action_bounds(dril_sac_handle* h, const float* low, const float* high) {
-    SNEED(h); S_EXTERNAL_ONLY(h, "dril_sac_ext_set_action_bounds");
-    if (!low || !high) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_set_action_bounds: null low / high");
-    float tb[2 * kMaxA];
-    for (int a = 0; a < kMaxA; ++a) { tb[a] = h->act_lo; tb[kMaxA + a] = h->act_hi; }
-    for (int a = 0; a < h->A; ++a) {
-        if (!std::isfinite(low[a]) || !std::isfinite(high[a]) || !(low[a] < high[a]))
-            return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_set_action_bounds: dimension " + std::to_string(a) + " needs finite bounds with low < high (TanhScaleAdapter, default_adapters.jl:13-21)");
-        tb[a] = low[a]; tb[kMaxA + a] = high[a];
-    }
-    SDO(ssync(h));                                                                                 // launches in flight read the table
-    SHIP(h, hipMemcpy(h->act_bounds, tb, sizeof(tb), hipMemcpyHostToDevice));
-    h->ext_bounds_set = true;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_device_info(const dril_sac_handle* h, struct dril_sac_ext_device_info* out) {
-    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    dril_sac_handle* hm = const_cast<dril_sac_handle*>(h);                                         // (the message slot only)
-    if (!out) return sfail(hm, DRIL_ERR_INVALID_ARG, "dril_sac_ext_device_info: null out pointer");
-    if (!h->external) return sfail(hm, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_device_info: the handle was not created with DRIL_ENV_EXTERNAL");
-    std::memset(out, 0, sizeof(*out));
-    out->steps_device = h->ext_steps_dev; out->steps_host = h->ext_steps_host; out->host_syncs = h->ext_syncs; out->flushes = h->ext_flushes; out->launches = h->ext_launches;
-    out->pending_updates = h->pend_n; out->pending_capacity = kPendingCap; out->per_dim_bounds = h->ext_bounds_set ? 1 : 0;
-    return DRIL_OK;
-}
 
 DRIL_EXPORT int64_t dril_sac_replay_size(const dril_sac_handle* h) { return h ? h->size : 0; }
 DRIL_EXPORT int64_t dril_sac_replay_capacity(const dril_sac_handle* h) { return h ? h->cap : 0; }
@@ -2683,7 +2172,7 @@ DRIL_EXPORT int32_t dril_sac_profile_get(dril_sac_handle* h, double* collect_ms,
 DRIL_EXPORT int32_t dril_sac_profile_reset(dril_sac_handle* h) { SNEED(h); h->collect_ms = h->update_ms = 0; h->collect_steps = h->updates = 0; return DRIL_OK; }
 
 // ---- MonitorWrapperEnv around the handle's device envs (monitorWrapperEnv.jl) ----------------------------------------------------------------------------
-namespace {
+namespace dril::sac {
 void monitor_free(dril_sac_handle* h) {
     h->mon_cur_ret.release(); h->mon_cur_len.release(); h->mon_ring_ret.release(); h->mon_ring_len.release();
     h->mon_meta.release(); h->mon_ep_ret.release(); h->mon_ep_len.release(); h->mon_flags.release();
@@ -2719,7 +2208,7 @@ int monitor_read(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int
     }
     return DRIL_OK;
 }
-}  // namespace
+}  // namespace dril::sac
 DRIL_EXPORT int32_t dril_sac_monitor_enable(dril_sac_handle* h, int32_t window) {
     SNEED(h);
     if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_monitor_enable: the envs of DRIL_ENV_EXTERNAL live on the host: MonitorWrapperEnv wraps them there");
@@ -2740,29 +2229,9 @@ DRIL_EXPORT int32_t dril_sac_monitor_get_stats(dril_sac_handle* h, float* ep_rew
     if (!h->mon_window) return sfail(h, DRIL_ERR_NOT_INITIALISED, "MonitorWrapperEnv is off (dril_sac_monitor_enable has not been called with a window >= 1)");
     return monitor_read(h, ep_rew_mean, ep_len_mean, n_episodes);
 }
-// the same for the device-resident envs of an external handle (dril_sac_ext_monitor_enable): the episodes of the steps pushed since the last collection enter the window first
-DRIL_EXPORT int32_t dril_sac_ext_monitor_get_stats(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes) {
-    SNEED(h);
-    if (!h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_monitor_get_stats: the handle was not created with DRIL_ENV_EXTERNAL: the wrapper around device envs is dril_sac_monitor_enable / dril_sac_monitor_get_stats");
-    if (!h->mon_window) return sfail(h, DRIL_ERR_NOT_INITIALISED, "dril_sac_ext_monitor_get_stats: MonitorWrapperEnv is off (dril_sac_ext_monitor_enable has not been called with a window >= 1)");
-    SDO(monitor_end(h));
-    return monitor_read(h, ep_rew_mean, ep_len_mean, n_episodes);
-}
-DRIL_EXPORT int32_t dril_sac_ext_wrap_info(const dril_sac_handle* h, struct dril_sac_ext_wrap_info* out) {
-    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    dril_sac_handle* hm = const_cast<dril_sac_handle*>(h);                            // (the message slot only)
-    if (!out) return sfail(hm, DRIL_ERR_INVALID_ARG, "dril_sac_ext_wrap_info: null out pointer");
-    if (!h->external) return sfail(hm, DRIL_ERR_UNSUPPORTED, "dril_sac_ext_wrap_info: the handle was not created with DRIL_ENV_EXTERNAL");
-    std::memset(out, 0, sizeof(*out));
-    out->normalize_on = h->nz.on ? 1 : 0; out->monitor_on = h->mon_window > 0 ? 1 : 0; out->monitor_window = h->mon_window;
-    out->launches_act = h->xw_launches_act; out->launches_push = h->xw_launches_push; out->allocations = 0;   // (structural: see the header)
-    return DRIL_OK;
-}
 // ---- NormalizeWrapperEnv around the handle's device envs (normalizeWrapperEnv.jl; rules and state: dril_norm_wrap.h) ------------------------------------------------------
-namespace {
 #define S_NORMALIZE_ON(h, what) do { if ((h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, what ": the envs of DRIL_ENV_EXTERNAL live on the host: NormalizeWrapperEnv wraps them there"); \
     if (!(h)->nz.on) return sfail(h, DRIL_ERR_NOT_INITIALISED, what ": NormalizeWrapperEnv is off (dril_sac_normalize_enable has not been called with a configuration)"); } while (0)
-}  // namespace
 // the two public configuration structs are one layout; inside the library it is dril_normalize_config
 static_assert(sizeof(dril_sac_normalize_config) == sizeof(dril_normalize_config) && offsetof(dril_sac_normalize_config, training) == offsetof(dril_normalize_config, training) &&
               offsetof(dril_sac_normalize_config, norm_obs) == offsetof(dril_normalize_config, norm_obs) && offsetof(dril_sac_normalize_config, norm_reward) == offsetof(dril_normalize_config, norm_reward) &&
@@ -2795,7 +2264,7 @@ DRIL_EXPORT int32_t dril_sac_normalize_enable(dril_sac_handle* h, const dril_sac
     return DRIL_OK;
 }
 // the bodies of the verbs that read or write a wrapper that is on: one definition for dril_sac_normalize_* (device envs) and dril_sac_ext_normalize_* (external handles)
-namespace {
+namespace dril::sac {
 int nzv_get_config(dril_sac_handle* h, const std::string& verb, dril_sac_normalize_config* cfg) {
     if (!cfg) return sfail(h, DRIL_ERR_INVALID_ARG, verb + ": null out pointer");
     memcpy(cfg, &h->nz.cfg, sizeof(*cfg));
@@ -2824,7 +2293,7 @@ int nzv_get_returns(dril_sac_handle* h, const std::string& verb, float* returns)
     SHIP(h, hipMemcpy(returns, h->nz_returns, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost));
     return DRIL_OK;
 }
-}  // namespace
+}  // namespace dril::sac
 DRIL_EXPORT int32_t dril_sac_normalize_set_training(dril_sac_handle* h, int32_t training) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_set_training");
     h->nz.cfg.training = training != 0;
@@ -2853,290 +2322,4 @@ DRIL_EXPORT int32_t dril_sac_normalize_get_original(dril_sac_handle* h, float* o
 DRIL_EXPORT int32_t dril_sac_normalize_get_returns(dril_sac_handle* h, float* returns) {
     SNEED(h); S_NORMALIZE_ON(h, "dril_sac_normalize_get_returns");
     return nzv_get_returns(h, "dril_sac_normalize_get_returns", returns);
-}
-
-// ---- NormalizeWrapperEnv / MonitorWrapperEnv around the device-resident envs of an external handle (include/dril_sac.h; the device verbs honour them: xw_observe / xw_push) ----
-namespace {
-#define XW_KIND(h, verb, twin) do { if (!(h)->external) return sfail(h, DRIL_ERR_UNSUPPORTED, verb ": the handle was not created with DRIL_ENV_EXTERNAL: the wrapper around device envs is " twin); } while (0)
-#define XN_ON(h, verb) do { XW_KIND(h, verb, "dril_sac_normalize_enable"); \
-    if (!(h)->nz.on) return sfail(h, DRIL_ERR_NOT_INITIALISED, verb ": NormalizeWrapperEnv is off (dril_sac_ext_normalize_enable has not been called with a configuration)"); } while (0)
-#define XW_NO_PENDING_ACT(h, verb) do { if ((h)->ext_acted) return sfail(h, DRIL_ERR_INVALID_ARG, verb ": a dril_sac_ext_act_device step is pending: switch wrappers between env steps (after dril_sac_ext_push_device)"); } while (0)
-}  // namespace
-DRIL_EXPORT int32_t dril_sac_ext_normalize_enable(dril_sac_handle* h, const dril_sac_normalize_config* cfg) {
-    SNEED(h); XW_KIND(h, "dril_sac_ext_normalize_enable", "dril_sac_normalize_enable");
-    dril_normalize_config c{};
-    if (cfg) {
-        memcpy(&c, cfg, sizeof(c));
-        if (const NormErr err = norm_config_check(c, h->D)) return sfail(h, err.code, "dril_sac_ext_normalize_enable: " + err.msg);
-        c = norm_config_canonical(c);
-    }
-    XW_NO_PENDING_ACT(h, "dril_sac_ext_normalize_enable");
-    if (!cfg) {
-        if (!h->nz.on) return DRIL_OK;
-        SDO(ssync(h)); normalize_free(h); h->xw_begin = h->xw_live = false;
-        return DRIL_OK;
-    }
-    if (h->nz.keeps(c)) return DRIL_OK;                                                // the same wrapper again (training apart, which is set): its statistics, returns and collection stay
-    SDO(ssync(h));
-    normalize_free(h);
-    const hipError_t e = normalize_alloc(h, kNzMaxRows);
-    if (e != hipSuccess) { normalize_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_ext_normalize_enable: ") + hipGetErrorString(e)); }
-    h->nz.cfg = c; h->nz.on = true; h->xw_begin = h->xw_live = false;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_normalize_set_training(dril_sac_handle* h, int32_t training) {
-    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_set_training");
-    h->nz.cfg.training = training != 0;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_normalize_get_config(dril_sac_handle* h, dril_sac_normalize_config* cfg) {
-    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_config");
-    return nzv_get_config(h, "dril_sac_ext_normalize_get_config", cfg);
-}
-DRIL_EXPORT int32_t dril_sac_ext_normalize_get_stats(dril_sac_handle* h, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count) {
-    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_stats");
-    return nzv_get_stats(h, "dril_sac_ext_normalize_get_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-}
-DRIL_EXPORT int32_t dril_sac_ext_normalize_set_stats(dril_sac_handle* h, const float* obs_mean, const float* obs_var, int64_t obs_count, float ret_mean, float ret_var, int64_t ret_count) {
-    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_set_stats");
-    XW_NO_PENDING_ACT(h, "dril_sac_ext_normalize_set_stats");                          // (the pending observation was normalised under the statistics in force)
-    return nzv_set_stats(h, "dril_sac_ext_normalize_set_stats", obs_mean, obs_var, obs_count, ret_mean, ret_var, ret_count);
-}
-DRIL_EXPORT int32_t dril_sac_ext_normalize_get_original(dril_sac_handle* h, float* obs, float* rewards) {
-    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_original");
-    if (!obs && !rewards) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_normalize_get_original: both out pointers are null");
-    SDO(ssync(h));
-    if (obs) SHIP(h, hipMemcpy(obs, h->nz_old_obs, (size_t)h->cfg.n_envs * h->D * 4, hipMemcpyDeviceToHost));
-    if (rewards) SHIP(h, hipMemcpy(rewards, h->nz_old_rew, (size_t)h->cfg.n_envs * 4, hipMemcpyDeviceToHost));
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_normalize_get_returns(dril_sac_handle* h, float* returns) {
-    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_get_returns");
-    return nzv_get_returns(h, "dril_sac_ext_normalize_get_returns", returns);
-}
-DRIL_EXPORT int32_t dril_sac_ext_normalize_reset(dril_sac_handle* h, void* caller_stream) {
-    SNEED(h); XN_ON(h, "dril_sac_ext_normalize_reset");
-    XW_NO_PENDING_ACT(h, "dril_sac_ext_normalize_reset");
-    DeviceVerbScope scope(h);
-    SHIP(h, ext_stream_take(h->stream, h->ext_ev_in, caller_stream));
-    StreamHandOver back(h, caller_stream);
-    SHIP(h, hipMemsetAsync(h->nz_returns, 0, (size_t)h->cfg.n_envs * 4, h->stream));   // reset! :110-121: returns <- 0; the env's own reset gives the next observation
-    SHIP(h, back.give());
-    h->xw_begin = h->xw_live = false;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_collection_begin(dril_sac_handle* h) {
-    SNEED(h); XW_KIND(h, "dril_sac_ext_collection_begin", "driven by dril_sac_collect_rollout");
-    if (h->nz.on) h->xw_begin = true;
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_ext_monitor_enable(dril_sac_handle* h, int32_t window) {
-    SNEED(h); XW_KIND(h, "dril_sac_ext_monitor_enable", "dril_sac_monitor_enable");
-    if (window < 0) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_ext_monitor_enable: window must be >= 1 (MonitorWrapperEnv's stats_window), or 0 to switch the monitor off");
-    XW_NO_PENDING_ACT(h, "dril_sac_ext_monitor_enable");
-    if (window == h->mon_window) return DRIL_OK;                                      // the same wrapper again: its window and running sums stay
-    SDO(ssync(h));
-    monitor_free(h);
-    if (window == 0) return DRIL_OK;
-    // the block of buffered steps: a row per push until dril_sac_flush / dril_sac_ext_monitor_get_stats (or a full block) collects it; about a million entries, 4 .. 256 rows
-    const size_t E = (size_t)h->cfg.n_envs, rows = std::max<size_t>(4, std::min<size_t>(256, ((size_t)1 << 20) / E));
-    const hipError_t e = monitor_alloc(h, window, rows);
-    if (e != hipSuccess) { monitor_free(h); return sfail(h, DRIL_ERR_HIP, std::string("dril_sac_ext_monitor_enable: ") + hipGetErrorString(e)); }
-    h->mon_window = window; h->mon_rows_cap = (int)rows;
-    return DRIL_OK;
-}
-
-// ---- evaluate_agent (src/evaluation.jl:54-143) with the handle's actor on the handle's envs -------------------------------------------------------------------
-namespace {
-template <typename T> int ensure_buf(dril_sac_handle* h, DevBuf<T>& p, size_t n) { if (!p) SHIP(h, p.alloc_zero(n)); return DRIL_OK; }
-// the buffers of an evaluation: allocated by the first one, kept; the event list grows with n_eval
-int eval_buffers(dril_sac_handle* h, long long cap) {
-    const size_t E = (size_t)h->cfg.n_envs;
-    SDO(ensure_buf(h, h->ev_state, E * h->S)); SDO(ensure_buf(h, h->ev_obs, E * h->D)); SDO(ensure_buf(h, h->ev_sc, E)); SDO(ensure_buf(h, h->ev_ep, E)); SDO(ensure_buf(h, h->ev_gs, E));
-    SDO(ensure_buf(h, h->ev_mon_ret, E)); SDO(ensure_buf(h, h->ev_mon_len, E)); SDO(ensure_buf(h, h->ev_cur_ret, E)); SDO(ensure_buf(h, h->ev_cur_len, E)); SDO(ensure_buf(h, h->ev_counter, 1));
-    if (!h->ev_counter_host) SHIP(h, h->ev_counter_host.alloc(1));
-    if (cap > 0) SHIP(h, h->ev_events.grow_zero((size_t)cap));
-    return DRIL_OK;
-}
-// the env side of the handle, out (save) or back in (restore): simulator state, counters, the noise stream's position, the current observation, the monitor's sums
-int eval_snapshot(dril_sac_handle* h, bool save) {
-    const size_t E = (size_t)h->cfg.n_envs;
-    auto cp = [&](void* snap, void* live, size_t bytes) { return save ? hipMemcpyAsync(snap, live, bytes, hipMemcpyDeviceToDevice, h->stream) : hipMemcpyAsync(live, snap, bytes, hipMemcpyDeviceToDevice, h->stream); };
-    SHIP(h, cp(h->ev_state, h->env.state, E * h->S * 4)); SHIP(h, cp(h->ev_sc, h->env.step_count, E * 4)); SHIP(h, cp(h->ev_ep, h->env.episode, E * 4)); SHIP(h, cp(h->ev_gs, h->env.gstep, E * 4));
-    SHIP(h, cp(h->ev_obs, h->obs_cur, E * h->D * 4));                                 // (restore: into whichever of the two observation buffers is current now)
-    if (h->mon_window) { SHIP(h, cp(h->ev_mon_ret, h->mon_cur_ret, E * 4)); SHIP(h, cp(h->ev_mon_len, h->mon_cur_len, E * 4)); }
-    return DRIL_OK;
-}
-// ---- the pieces both verbs run: the PPO handle's (dril_eval.hip, under the same names; docs/sac.md "Layout of the host code") over this handle's state ----
-// set-aside: the verbs run on the handle's own envs — what a collection would continue from is kept here and put back by eval_finish, on every path
-struct EvalKeep { uint64_t seed0; bool ready, obs_valid; };
-int eval_set_aside(dril_sac_handle* h, EvalKeep& keep) { keep = EvalKeep{h->env.seed0, h->env.ready, h->obs_valid}; return eval_snapshot(h, true); }
-int eval_put_back(dril_sac_handle* h, const EvalKeep& keep) { h->env.seed0 = keep.seed0; h->env.ready = keep.ready; h->obs_valid = keep.obs_valid; return eval_snapshot(h, false); }
-// the end of either verb: the state is put back and the stream drained whatever the run returned (rc), and the run's error is the one reported
-int eval_finish(dril_sac_handle* h, const EvalKeep& keep, int rc) {
-    const std::string msg = h->err;
-    int rr = eval_put_back(h, keep); if (rr == DRIL_OK) rr = ssync(h);
-    if (rc != DRIL_OK) h->err = msg;
-    return rc != DRIL_OK ? rc : rr;
-}
-// open the episode: the call's seed (env e seeded seed + e; its action noise is that env's stream from step 0), reset!(env), the counter zeroed, the first observation
-// — raw, into obs_cur: the wrapper's old_obs is not these verbs' to write — handed to row0() (the recording's row 0 is the original observation), then normalised in
-// place with the frozen statistics, nothing updated.  shadow (null: none): a plug-in recording's twins of envs 0..M-1, seeded alike
-template <class Row0> int eval_open_episode(dril_sac_handle* h, bool has_seed, uint64_t seed, Row0&& row0, DeviceEnvs* shadow = nullptr) {
-    if (has_seed) h->env.seed0 = seed;
-    SHIP(h, h->env.reset(h->stream));
-    h->env.ready = true; h->obs_valid = false;
-    if (shadow) { shadow->seed0 = h->env.seed0; for (void* p : {(void*)shadow->step_count, (void*)shadow->episode, (void*)shadow->gstep}) SHIP(h, hipMemsetAsync(p, 0, (size_t)shadow->E * 4, h->stream)); }
-    SHIP(h, hipMemsetAsync(h->ev_counter, 0, 4, h->stream));
-    SDO(ensure_obs(h)); SDO(row0());
-    if (h->nz.on) { NzApplyArgs a{}; a.w.raw = h->obs_cur; a.w.obs_out = h->obs_cur; SDO(nz_apply(h, a, 0, false, false)); }
-    return DRIL_OK;
-}
-// the loop of either verb (eval_poll_loop of dril_eval.hip): enqueue(steps, launches) advances both; a chunk that would start at or past `bound` fails with (code, bound_msg)
-struct EvalPoll { unsigned int seen = 0; long long steps = 0; int32_t launches = 0; };
-template <class Enqueue> int eval_poll_loop(dril_sac_handle* h, int want, long long bound, int code, const char* bound_msg, EvalPoll& p, Enqueue&& enqueue) {
-    for (p = EvalPoll{}; p.seen < (unsigned int)want; p.seen = *h->ev_counter_host) {
-        if (p.steps >= bound) return sfail(h, code, bound_msg);
-        SDO(enqueue(p.steps, p.launches));
-        SHIP(h, hipMemcpyAsync(h->ev_counter_host, h->ev_counter, 4, hipMemcpyDeviceToHost, h->stream));
-        SDO(ssync(h));
-    }
-    return DRIL_OK;
-}
-// The pieces of one env step that eval_step and traj_step share; what differs — the accounting, or shadow step, shadow observe and recording — sits between them.
-// predict_actions(agent, observations; deterministic): the collection step's hidden layers; the output layer runs in the launch that takes `ca`
-int eval_step_actor(dril_sac_handle* h, int deterministic, CollectHeadArgs& ca) { SDO(actor_hidden(h, 0, nullptr, &ca)); ca.deterministic = deterministic ? 1 : 0; return DRIL_OK; }
-// NormalizeWrapperEnv with training = false (set_training(eval_env, false) after sync_normalization_stats!, :299-309): the statistics in force, frozen
-NzEvalArgs eval_step_nz(const dril_sac_handle* h) { return NzEvalArgs{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs}; }
-// a plug-in: the action head into e_envact, and act!(env, action) of the live envs (monitor pointers null: these episodes do not feed the window)
-void eval_step_head(dril_sac_handle* h, const CollectHeadArgs& ca) { hipLaunchKernelGGL(sac_collect_head_kernel, dim3((h->cfg.n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), dim3(256), 0, h->stream, ca); }
-int eval_step_env(dril_sac_handle* h) { SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, MonitorArgs{}, h->stream)); return DRIL_OK; }
-// a built-in Box kind (A = 1): head, act! and observe are ONE launch, launch(K, env, grid, block), of the caller's env kernel over the collection's block without push and monitor
-template <class Launch> int eval_step_builtin(dril_sac_handle* h, const CollectHeadArgs& ca, Launch&& launch) {
-    const CollectEnvArgs env = env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr});
-    const dim3 grid((h->cfg.n_envs + kEnvsPerBlock - 1) / kEnvsPerBlock), block(256);
-    SHIP(h, with_env_kind<KindShare::None>(BoxKinds{}, h->env.kind, [&](auto K) { launch(K, env, grid, block); return hipGetLastError(); }));
-    return DRIL_OK;
-}
-int eval_step_end(dril_sac_handle* h) { SHIP(h, hipGetLastError()); std::swap(h->obs_cur, h->obs_nxt); return DRIL_OK; }
-// ---- the evaluation itself ----
-// one env step of the evaluation, enqueued: the collection step's hidden layers, then head + act! + observe + accounting
-int eval_step(dril_sac_handle* h, int deterministic, int32_t step, unsigned int cap) {
-    const int E = h->cfg.n_envs;
-    CollectHeadArgs ca; SDO(eval_step_actor(h, deterministic, ca));
-    const EvalAcctArgs acct{E, step, h->ev_cur_ret, h->ev_cur_len, h->ev_counter, h->ev_events, cap}; const NzEvalArgs nz = eval_step_nz(h);
-    if (h->env.module) {
-        eval_step_head(h, ca); SDO(eval_step_env(h));
-        if (nz.st && nz.norm_obs) {                                                    // the accounting launch also normalises the observation the plug-in wrote, in place
-            const long long nthr = std::max<long long>(E, std::min<long long>((long long)E * h->D, 256 * 1024));
-            hipLaunchKernelGGL(sac_eval_account_norm_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, acct, h->e_rew, h->e_term, h->e_trunc, nz, h->D, h->obs_nxt);
-        } else hipLaunchKernelGGL(sac_eval_account_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, acct, h->e_rew, h->e_term, h->e_trunc);
-    } else {
-        SDO(eval_step_builtin(h, ca, [&](auto K, const CollectEnvArgs& env, dim3 grid, dim3 block) {
-            hipLaunchKernelGGL(sac_eval_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, EvalEnvArgs{env, acct, nz});
-        }));
-    }
-    return eval_step_end(h);
-}
-// reset!(env) .. the loop of evaluation.jl:90-122 on the device; the host looks at the event counter once per eval_poll steps
-int eval_run(dril_sac_handle* h, int n_eval, int deterministic, uint64_t seed, std::vector<SacEvalEvent>& events) {
-    const int E = h->cfg.n_envs; const long long cap = sac_eval_event_capacity(n_eval, E);
-    SDO(eval_open_episode(h, true, seed, [] { return DRIL_OK; }));
-    SHIP(h, hipMemsetAsync(h->ev_cur_ret, 0, (size_t)E * 4, h->stream)); SHIP(h, hipMemsetAsync(h->ev_cur_len, 0, (size_t)E * 4, h->stream));
-    // every env finishes an episode within the time limit, so n_eval of them take at most ceil(n_eval / E) time limits; one more, and the steps enqueued past a look
-    const long long max_steps = ((long long)(n_eval + E - 1) / E + 1) * (long long)h->cfg.episode_len + h->eval_poll;
-    EvalPoll p;
-    SDO(eval_poll_loop(h, n_eval, max_steps, DRIL_ERR_UNSUPPORTED, "dril_sac_evaluate_agent: no episode finishes", p, [&](long long& steps, int32_t&) -> int {
-        for (int k = 0; k < h->eval_poll; ++k) SDO(eval_step(h, deterministic, (int32_t)(++steps), (unsigned int)cap));
-        return DRIL_OK;
-    }));
-    events.resize((size_t)std::min<long long>(p.seen, cap));
-    SHIP(h, hipMemcpy(events.data(), h->ev_events, events.size() * sizeof(SacEvalEvent), hipMemcpyDeviceToHost));
-    return DRIL_OK;
-}
-}  // namespace
-DRIL_EXPORT int32_t dril_sac_evaluate_agent(dril_sac_handle* h, int32_t n_eval, int32_t deterministic, uint64_t seed, dril_eval_stats* out, float* ep_rewards, int32_t* ep_lengths) {
-    SNEED(h);
-    if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_evaluate_agent: the envs of DRIL_ENV_EXTERNAL live on the host: evaluate there with dril_sac_predict_actions");
-    if (n_eval < 1 || !out) return sfail(h, DRIL_ERR_INVALID_ARG, "dril_sac_evaluate_agent: n_eval_episodes >= 1 and out != NULL");
-    SDO(eval_buffers(h, sac_eval_event_capacity(n_eval, h->cfg.n_envs)));
-    EvalKeep keep; SDO(eval_set_aside(h, keep));
-    std::vector<SacEvalEvent> events;
-    SDO(eval_finish(h, keep, eval_run(h, n_eval, deterministic, seed, events)));
-    sac_eval_stats(events.data(), (int64_t)events.size(), n_eval, out, ep_rewards, ep_lengths);
-    return DRIL_OK;
-}
-
-// ---- collect_trajectory (src/utils/trajectory_utils.jl:3-49) with the handle's actor on the handle's envs; docs/sac.md, "Trajectories" ---------------------------
-// The evaluation's launches with the episode accounting replaced by a recording of envs 0..M-1.  Built-in Box kinds: one env launch per step (sac_traj_env_kernel),
-// the env's own thread records from its registers.  Plug-ins: their code objects write terminal_obs where truncated only, so the M SHADOW envs of
-// dril_collect_trajectory_device (its comment in dril_eval.hip; built by traj_setup, dril_traj_run.h) take every step a second time, with the same env actions, and
-// their observe is the post-step, pre-reset observation sac_traj_record_kernel records.
-namespace {
-// the recording of one call.  No ClampAdapter (the boxes' clamp_* stay null): TanhScaleAdapter's actions are inside the Box by construction
-int traj_prepare(dril_sac_handle* h, const dril_traj_options* o, int32_t Tcap, TrajRun& r) {
-    const TrajLayout L = traj_layout((size_t)o->n_trajectories, (size_t)h->D, (size_t)h->A, (size_t)h->S, (size_t)Tcap);
-    SHIP(h, traj_setup(h->env, h->stream, h->traj_blob, h->ev_counter, L, traj_env_boxes(h->env), o->final_original != 0, /*drain_before_free=*/true, r));
-    return DRIL_OK;
-}
-// one env step, enqueued: the launches of eval_step without the accounting, and the recording of envs 0..M-1
-int traj_step(dril_sac_handle* h, const TrajRun& r, int32_t t, int deterministic, int32_t* launches) {
-    const int64_t f0 = h->fwd_launches; const int tag0 = h->col_tag; const NzEvalArgs nz = eval_step_nz(h);
-    if (h->env.module) SHIP(h, hipMemcpyAsync(r.shadow.state, h->env.state, (size_t)r.rec.M * h->S * 4, hipMemcpyDeviceToDevice, h->stream));   // the pre-step state of envs 0..M-1 (env-major prefix)
-    CollectHeadArgs ca; SDO(eval_step_actor(h, deterministic, ca));
-    *launches += (int32_t)(h->fwd_launches - f0) + (h->col_tag != tag0 ? 2 : 0);   // (the f16-piece form of the hidden layers: sac_collect_l1_kernel + sac_collect_l2_kernel)
-    if (h->env.module) {
-        eval_step_head(h, ca);
-        SHIP(h, r.shadow.step(h->e_envact, EnvStepOut{r.sh_rew, r.sh_term, r.sh_trunc, r.sh_tobs, nullptr}, MonitorArgs{}, h->stream));   // the same step with the same actions' prefix, with no reset after it
-        SHIP(h, r.shadow.observe(r.sh_obs, h->stream));                            // observe(env) of the env that did not auto-reset
-        SDO(eval_step_env(h));                                                     // act!(env, action), :35
-        SHIP(h, traj_record_launch(sac_traj_record_kernel, h->stream, r, TrajStep{h->e_envact, h->e_rew, h->e_term, h->e_trunc, r.sh_obs}, t));
-        *launches += 6;                                                             // state copy, head, shadow step, shadow observe, live step, recording
-        if (nz.st && nz.norm_obs) { NzApplyArgs a{}; a.w.raw = h->obs_nxt; a.w.obs_out = h->obs_nxt; SDO(nz_apply(h, a, 0, false, false)); *launches += 1; }   // the next observation under the frozen statistics, in place
-    } else {
-        SDO(eval_step_builtin(h, ca, [&](auto K, const CollectEnvArgs& env, dim3 grid, dim3 block) {
-            hipLaunchKernelGGL(sac_traj_env_kernel<decltype(K)::value>, grid, block, 0, h->stream, TrajEnvArgs{env, nz, r.rec, r.maps, t});
-        }));
-        *launches += 1;
-    }
-    return eval_step_end(h);
-}
-// reset!(env) .. the loop of trajectory_utils.jl:16-45 on the device; the host looks at the finished-counter once per K steps and never enqueues a step past Tcap
-int traj_run(dril_sac_handle* h, const dril_traj_options* o, TrajRun& r, float* observations, float* actions, float* rewards, int32_t* lengths, uint8_t* end_flags, dril_traj_info* info) {
-    const int Tcap = r.rec.Tcap, K = o->poll_steps > 0 ? o->poll_steps : h->eval_poll;
-    const auto row0 = [&]() -> int {                                               // the original observation, before the agent's copy is normalised
-        SHIP(h, traj_record_launch(sac_traj_record_kernel, h->stream, r, TrajStep{nullptr, nullptr, nullptr, nullptr, h->obs_cur}, 0));
-        return DRIL_OK;
-    };
-    SDO(eval_open_episode(h, o->has_seed != 0, o->seed, row0, h->env.module ? &r.shadow : nullptr));
-    EvalPoll p;
-    SDO(eval_poll_loop(h, r.rec.M, Tcap, DRIL_ERR_HIP, "dril_sac_collect_trajectory: a trajectory is still open after its capacity (internal)", p, [&](long long& steps, int32_t& launches) -> int {   // (step Tcap finalises every open one)
-        for (int k = 0; k < K && steps < Tcap; ++k) SDO(traj_step(h, r, (int32_t)(++steps), o->deterministic ? 1 : 0, &launches));
-        return DRIL_OK;
-    }));
-    const TrajCopyOut c = traj_copy_out(h->stream, r.rec, observations, (uint32_t*)actions, rewards, lengths, end_flags);
-    if (const std::string msg = traj_report("dril_sac_collect_trajectory", c, Tcap, (int32_t)p.steps, p.launches, 0, info); !msg.empty()) return sfail(h, DRIL_ERR_HIP, msg);
-    return DRIL_OK;
-}
-}  // namespace
-DRIL_EXPORT int32_t dril_sac_trajectory_capacity(const dril_sac_handle* h, const dril_traj_options* o, int32_t* capacity) {
-    if (!h) return sfail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
-    dril_sac_handle* hh = const_cast<dril_sac_handle*>(h);
-    if (!o || !capacity || o->max_steps < 0) return sfail(hh, DRIL_ERR_INVALID_ARG, "dril_sac_trajectory_capacity: options and capacity != NULL, max_steps >= 0");
-    if (h->external) return sfail(hh, DRIL_ERR_UNSUPPORTED, "dril_sac_trajectory_capacity: the envs of DRIL_ENV_EXTERNAL live on the host, with the caller");
-    *capacity = traj_capacity(o->max_steps, h->env.episode_len);
-    return DRIL_OK;
-}
-DRIL_EXPORT int32_t dril_sac_collect_trajectory(dril_sac_handle* h, const dril_traj_options* o, float* observations, float* actions, float* rewards, int32_t* lengths,
-                                                uint8_t* end_flags, dril_traj_info* info) {
-    SNEED(h);
-    if (h->external) return sfail(h, DRIL_ERR_UNSUPPORTED, "dril_sac_collect_trajectory: the envs of DRIL_ENV_EXTERNAL live on the host: record there, in a loop over dril_sac_predict_actions");
-    if (const std::string msg = traj_options_error("dril_sac_collect_trajectory", o, observations && actions && rewards && lengths && end_flags, h->cfg.n_envs); !msg.empty()) return sfail(h, DRIL_ERR_INVALID_ARG, msg);
-    int32_t Tcap = 0;
-    if (const std::string msg = traj_size_error("dril_sac_collect_trajectory", o, h->env.episode_len, h->D, h->A, info, &Tcap); !msg.empty()) return sfail(h, DRIL_ERR_INVALID_ARG, msg);
-    SDO(eval_buffers(h, 0));
-    TrajRun run{}; SDO(traj_prepare(h, o, Tcap, run));
-    // as dril_sac_evaluate_agent: what a collection would continue from is set aside here and put back by eval_finish, on every path
-    EvalKeep keep; SDO(eval_set_aside(h, keep));
-    return eval_finish(h, keep, traj_run(h, o, run, observations, actions, rewards, lengths, end_flags, info));
 }

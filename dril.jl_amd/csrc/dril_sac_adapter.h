@@ -1,5 +1,5 @@
 // dril_sac_adapter.h — TanhScaleAdapter on a Box with per-dimension bounds (default_adapters.jl:13-30) and rand(action_space): the ONE definition behind
-// sac_collect_action and sac_squash_eval_kernel (dril_sac.hip).  Plain float arithmetic with no HIP dependency, so the same lines compile with a host C++
+// sac_collect_action (dril_sac_device.h) and sac_squash_eval_kernel (dril_sac.hip).  Plain float arithmetic with no HIP dependency, so the same lines compile with a host C++
 // compiler (tests/test_sac_env_plugin.py builds them with g++ and follows them with NumPy).
 #pragma once
 #include <math.h>

@@ -1,8 +1,8 @@
 // dril_sac_ext_norm.h — what is the DRIL_ENV_EXTERNAL SAC handle's own of NormalizeWrapperEnv / MonitorWrapperEnv around the caller's device-resident envs
 // (dril_sac_ext_normalize_enable / dril_sac_ext_monitor_enable, include/dril_sac.h; honoured by dril_sac_ext_act_device / _push_device and
 // dril_sac_predict_actions_device).  Scalars, the moments kernel, the head of an apply kernel and the host state are dril_norm_wrap.h; the table shape (at most
-// kNzMaxRows rows, column tiles of kNzTile) and the LDS layout are dril_sac_norm.h's; the per-env rules of a recorded step are dril_ext_record.h's.  Included by
-// dril_sac.hip inside its anonymous namespace, after PushArgs and dril_sac_norm.h.
+// kNzMaxRows rows, column tiles of kNzTile) and the LDS layout are dril_sac_norm.h's; the per-env rules of a recorded step are dril_ext_record.h's.  The launches are
+// dril_sac_ext.hip's, the one unit that includes this header.
 //
 // One verb has one grid-wide dependency (all envs' sums -> the merged statistics -> every env's normalised row), so a verb is
 //   moments   norm_moments_kernel<kNzTile> over the CALLER's arrays (act: d_obs, opening act only; push: d_next_obs and `returns` advanced by d_rewards, ONE launch)
@@ -13,6 +13,16 @@
 // under the same statistics, which gives the same bits).
 // No atomics: the launch shape fixes the order of every sum.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dril_norm_wrap.h"     // NormWrapArgs, nz_fold, nz_statistics, nz_obs, nz_reward
+#include "dril_sac_device.h"    // PushArgs
+#include "dril_sac_norm.h"      // nz_apply_lds: the LDS layout this one extends
+#include "dril_ext_record.h"    // xr_*: the per-env scalar rules of the push
+
+namespace dril::sac {
+namespace {
 
 // the dynamic LDS of both kernels: sac_norm_apply_kernel's layout, then (push) the observation statistics as they were before the launch
 static_assert(sizeof(double) * (256 + 2 * (size_t)kNzMaxD + 2) + sizeof(float) * (4 * (size_t)kNzMaxD + 2) <= 48 * 1024, "sac_ext_norm_push_kernel's dynamic LDS at the widest observation");
@@ -115,3 +125,6 @@ __global__ __launch_bounds__(256) void sac_ext_norm_push_kernel(XsPushArgs p) {
         g.rb_act[((g.tail + e) % g.cap) * A + k] = g.raw[(size_t)e * A + k];             // unprocessed action, off_policy_collection.jl:72
     }
 }
+
+}  // namespace
+}  // namespace dril::sac

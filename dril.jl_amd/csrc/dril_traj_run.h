@@ -1,4 +1,4 @@
-// dril_traj_run.h — the recording setup of a device-resident collect_trajectory, for the PPO handle (dril_eval.hip) and the SAC handle (dril_sac.hip) alike: the layout
+// dril_traj_run.h — the recording setup of a device-resident collect_trajectory, for the PPO handle (dril_eval.hip) and the SAC handle (dril_sac_eval.hip) alike: the layout
 // of the handle's private blob, the table of bounds behind TrajMaps, the shadow envs, and the refusals and reports in which only the verb's name differs.  Nothing
 // here knows a handle: envs, stream, the blob's owner, a counter and sizes are plain arguments, and an error comes back as a hipError_t or as a message (empty:
 // none) for the caller's own fail / sfail.  No HIP dependency above the #if (tests/test_traj_run.py drives traj_layout and traj_bounds_table with g++).

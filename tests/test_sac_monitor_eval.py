@@ -2,7 +2,7 @@
 
   * the library exports the three new entry points; include/dril_sac.h, dril.jl_amd/_capi.py and the Julia shim agree on them (arity and widths);
   * a null handle and bad arguments return their status before any HIP call;
-  * the host arithmetic of the device-resident evaluation (dril.jl_amd/csrc/dril_sac_eval.h, the lines dril_sac.hip compiles) built with g++ against a
+  * the host arithmetic of the device-resident evaluation (dril.jl_amd/csrc/dril_sac_eval.h, the lines dril_sac_eval.hip compiles) built with g++ against a
     restatement of the reference's loop (evaluation.jl:100-124)."""
 import ctypes as C
 import math
