@@ -124,6 +124,12 @@ class DrilFusedRolloutInfo(C.Structure):
                 ("last_collection_launches", C.c_int64), ("reason", C.c_char * 256)]
 
 
+class DrilNormRolloutInfo(C.Structure):
+    """struct dril_norm_rollout_report, include/dril_hip.h (what dril_norm_rollout_info fills)"""
+    _fields_ = [("available", C.c_int32), ("enabled", C.c_int32), ("max_envs", C.c_int32), ("last_collection_path", C.c_int32),
+                ("last_collection_launches", C.c_int64), ("total_stepwise_fallbacks", C.c_int64), ("reason", C.c_char * 256)]
+
+
 class DrilFusedEvaluateInfo(C.Structure):
     """struct dril_fused_evaluate_info, include/dril_hip.h"""
     _fields_ = [("available", C.c_int32), ("tile", C.c_int32), ("threads", C.c_int32), ("max_width", C.c_int32), ("reason", C.c_char * 256)]
@@ -244,6 +250,8 @@ _SIG = {
     "dril_agent_spaces": (C.c_int32, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     "dril_rollout_fused_enable": (C.c_int32, [_P, C.c_int32]),
     "dril_rollout_fused_info": (C.c_int32, [_P, _P]),
+    "dril_norm_rollout_enable": (C.c_int32, [_P, C.c_int32]),
+    "dril_norm_rollout_info": (C.c_int32, [_P, C.POINTER(DrilNormRolloutInfo)]),
     "dril_evaluate_fused_info": (C.c_int32, [_P, _P]),
     "dril_destroy": (C.c_int32, [_P]),
     "dril_last_error": (C.c_char_p, [_P]),

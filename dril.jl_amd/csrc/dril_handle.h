@@ -58,6 +58,9 @@ struct dril_handle {
     dril::DevBuf<unsigned long long> dbg;
     bool force_allreduce = false, force_stepwise = false;
     bool fused_rollout = false; int64_t rollout_launches = 0;   // dril_rollout_fused_enable; launch calls of the last plug-in collection (dril_rollout_fused_info)
+    // dril_norm_rollout_enable: the opt-in, the launches and the path (1 = rollout_norm_kernel, 0 = step-granular) of the last normalised collection, and how often
+    // an enabled handle collected step-granular because its forward was the exact-f32 one (dril_norm_rollout_info)
+    bool norm_rollout = false; int norm_rollout_path = 0; int64_t norm_rollout_launches = 0, norm_rollout_fallbacks = 0;
     dril::DevBuf<double> epoch_tables, epoch_stats; int epoch_blocks = 2048;   // per-epoch advantage moments
     dril::DevBuf<float> w2a_actor, w2ta_actor, w2a_critic, w2ta_critic; bool wide = false, wimg_dirty = true;   // wide nets (H > 64)
     dril::DevBuf<char> w2pf_actor, w2pf_critic;   // wide nets: the forward stream in the k-order of a register B operand (net_forward_wide_split)
@@ -171,6 +174,12 @@ std::string fused_evaluate_unavailable(const dril_handle* h);
 // a collection that is ONE launch of the fused rollout kernel of a built-in kind, and the argument block of that launch, read from the handle as it stands
 bool rollout_fused_applies(const dril_handle* h);
 RolloutArgs rollout_args(const dril_handle* h);
+// the one-launch collection of a normalising built-in handle (dril_norm_rollout_enable): "" when the handle may take it, else why not; whether this collection takes
+// it (enabled, available, on the f16-piece forward); its argument block, read from the handle AFTER the opening observe; the host's bookkeeping after the launch
+std::string norm_rollout_unavailable(const dril_handle* h);
+bool norm_rollout_applies(const dril_handle* h);
+NormRolloutArgs norm_rollout_args(const dril_handle* h);
+void norm_rollout_done(dril_handle* h);
 int collect_rollout(dril_handle* h, double* fps, bool do_sync);
 
 // ---- dril_ext.hip ----

@@ -165,6 +165,20 @@ struct NormApplyArgs {
     float clip_obs, clip_reward, eps;
     long long n_stats;
 };
+// rollout_norm_kernel (dril_kernels.hip): collect_trajectories under NormalizeWrapperEnv for E <= kNormRolloutMaxEnvs envs in ONE workgroup — r as the rollout's
+// launcher fills it, and what collect_rollout_stepwise hands norm_step_kernel / norm_apply_kernel step by step.  obs_rms / ret_rms: the ping-pong PAIRS, obs_par /
+// ret_par the halves in force at launch (the kernel flips once per env step, as the host does around norm_apply_kernel); the e_* arrays hold the opening observation
+// on entry (observe_dev) and the last step's on exit
+constexpr int kNormRolloutMaxEnvs = 128;
+struct NormRolloutArgs {
+    RolloutArgs r;
+    float* disc_returns; RmsState* obs_rms; RmsState* ret_rms; int obs_par, ret_par;
+    int update_obs, update_ret, norm_obs, norm_reward;
+    float gamma, clip_obs, clip_reward, eps;
+    float* e_obs; float* e_obs_raw; float* e_rew; uint8_t* e_term; uint8_t* e_trunc; float* e_tobs;
+};
+hipError_t launch_rollout_norm(int kind, const NormRolloutArgs& a, hipStream_t s);                             // hidden [64,64] on the f16-piece forward
+hipError_t launch_rollout_norm_pop(int kind, const NormRolloutArgs* d_members, int n, int E, hipStream_t s);   // rollout_norm_pop_kernel: grid (1, n); every member with the same E
 hipError_t launch_fold_partials(const double* partials, int nblocks, double* out16, hipStream_t s);
 hipError_t launch_norm_step(int kind, const NormStepArgs& a, int nblocks, hipStream_t s);
 hipError_t launch_norm_apply(const NormApplyArgs& a, hipStream_t s);

@@ -868,6 +868,216 @@ __global__ __launch_bounds__(128, 2) void rollout_duo_pop_kernel(const RolloutAr
 }
 
 // =============================================================================================
+// rollout_norm_kernel — collect_trajectories under NormalizeWrapperEnv(MonitorWrapperEnv(env)) for E <= kNormRolloutMaxEnvs envs: ONE workgroup runs all T steps, where
+// collect_rollout_stepwise launches policy_kernel -> norm_step_kernel -> norm_apply_kernel per env step.  ceil(E / 32) tiles of rollout_duo_body's two waves (wave
+// i: actor + sampler + simulator + wrapper of tile i, wave tiles + i: its critic), one staged copy of both nets for all of them.  The running statistics couple all
+// envs at every step; here they meet in LDS:
+//   actor wave, step t   forward, sample, act! (env_advance / env_end_episode), the discounted return, the raw next observation — norm_step_kernel's loop body;
+//                        its 1 + D float columns go to mom[t & 1][column][env]                                                       -> barrier B_t
+//                        EVERY actor wave then sums all columns by norm_step_kernel's own tree and merges (norm_apply_kernel's head): the same bits in every
+//                        wave, so no second barrier.  Lane 0 keeps the return statistics, lanes 1 .. D those of observation dim lane - 1; tile 0 stores them to
+//                        the half of the ping-pong pair that the host's loop would have in force after this step.  Then norm_apply_kernel's per-env part,
+//                        and slot[(t + 1) & 1] for the critic
+//   critic wave          V(obs_t) and V(terminal_observation of step t - 1) from slot[t & 1] between B_t and B_{t+1}: a step behind rollout_duo_body's critic, because
+//                        the slot is written after the barrier that publishes the columns
+// The sums are bit-equal to the step-granular path by construction.  There norm_step_kernel runs one block of 256 (E <= 256): env e is lane e % 64 of wave e / 64,
+// block_sum_f64 is the xor butterfly d = 32 .. 1 inside a wave and then 0 + w0 + w1 + w2 + w3, fold_partials16 over one block adds zeros.  Here a wave reads the columns back
+// as v[lane + 64 w], w = 0, 1 (0 beyond E), runs the same butterfly per w and adds the two results in the same order.
+// =============================================================================================
+__device__ __forceinline__ double wave_tree_f64(double v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);       // block_sum_f64's first stage
+    return v;
+}
+__device__ __forceinline__ float lane_bcast(float v, int src) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src)); }
+template <int D> struct NormRolloutLds {
+    static constexpr int SLOT = (2 * D + 1) * 32, TILES = kNormRolloutMaxEnvs / kTile, MOMS = kNormRolloutMaxEnvs + 1;   // column stride: odd, so the lanes of a column's reader spread over the banks
+    static constexpr int SLOTS = TILES * 2 * SLOT, MOM = 2 * (1 + D) * MOMS, SIZE = SLOTS + MOM;                         // floats, after the two nets
+};
+template <int KIND, int H, bool SPLIT>
+__device__ __forceinline__ void rollout_norm_body(const NormRolloutArgs& g) {
+    const RolloutArgs& a = g.r;
+    constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
+    constexpr int LA = FwdLds<D, H, A, false, SPLIT>::SIZE, LC = FwdLds<D, H, 1, false, SPLIT>::SIZE;
+    using NL = NormRolloutLds<D>;
+    constexpr int SLOT = NL::SLOT, MOMS = NL::MOMS;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* la = smem; float* lc = smem + LA;
+    const int tid = threadIdx.x, lane = tid & 63;
+    // waves 0 .. tiles - 1 are the actors, the next `tiles` waves their critics: a workgroup's waves go round the four SIMDs, so with four tiles every SIMD holds one
+    // actor wave (the longer chain of a step) and one critic wave rather than two actors
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), tiles = (int)blockDim.x >> 7;
+    const int role = wave >= tiles ? 1 : 0, tile = role ? wave - tiles : wave;
+    float* slot = smem + LA + LC + tile * 2 * SLOT;                    // this tile's [2 parities][obs D x 32 | terminal obs D x 32 | truncated flag 32]
+    float* mom = smem + LA + LC + NL::SLOTS;                            // [2 parities][discounted return | raw observation D][MOMS]
+    stage_fwd<D, H, A, false, SPLIT>(la, a.params, a.actor, tid, (int)blockDim.x);
+    stage_fwd<D, H, 1, false, SPLIT>(lc, a.params, a.critic, tid, (int)blockDim.x);
+    const int c = lane & 31, h = lane >> 5;
+    const int e_raw = tile * kTile + c;
+    const bool valid = e_raw < a.E;
+    const int e = valid ? e_raw : a.E - 1;
+    const bool writer = valid && h == 0;
+    if (role == 0) {
+        // ================= actor + simulator + wrapper =================
+        const uint64_t env_seed = a.env_seed0 + (uint64_t)e;
+        const EnvArrays env{a.state, a.step_count, a.episode, a.gstep, a.mon_cur_ret, a.mon_cur_len};
+        EnvCursor<KIND> cur; cur.load(env, e);
+        float obs[D];                                                   // what the policy reads: the opening observe(env) left it in e_obs
+#pragma unroll
+        for (int i = 0; i < D; ++i) obs[i] = g.e_obs[(size_t)e * D + i];
+        float disc = g.disc_returns[e];
+        // the statistics in force, one column per lane: lane 0 the discounted returns, lanes 1 .. D the observation dims
+        const int sd = lane == 0 ? 0 : (lane <= D ? lane - 1 : 0);
+        const RmsState* st_in = lane == 0 ? g.ret_rms + g.ret_par : g.obs_rms + g.obs_par;
+        float s_mean = st_in->mean[sd], s_var = st_in->var[sd]; long long s_count = st_in->count;
+        int obs_par = g.obs_par, ret_par = g.ret_par;
+        if (h == 0) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) slot[i * 32 + c] = obs[i];     // parity 0: the observation of step 0
+        }
+        float lsr[4]; rollout_log_std<KIND>(a, lsr);
+        __syncthreads();                                                // weights staged, slot 0 published
+        for (int t = 0; t < a.T; ++t) {
+            const size_t k = (size_t)t * a.E + e;
+            int zoff = 0; asm volatile("" : "+v"(zoff));
+            const float* la_t = la + zoff;
+            float xk[FirstLayer<D>::KS];
+            pair_obs<D>(obs, h, xk);
+            float out[A];
+            eval_net<D, H, A, false, SPLIT>(la_t, a.w2a_actor, xk, out, lane);
+            int act_env = 0; float actf_env = 0.f, logp;
+            rollout_sample<KIND>(a, k, env_seed, cur.gs, out, lsr, writer, &act_env, &actf_env, &logp);
+            if (writer) {
+                if (D == 4) *reinterpret_cast<float4*>(a.obs + k * 4) = make_float4(obs[0], obs[1], obs[2], obs[3]);
+                else {
+#pragma unroll
+                    for (int i = 0; i < D; ++i) a.obs[k * D + i] = obs[i];
+                }
+                a.logp[k] = logp;
+            }
+            // ---- norm_step_kernel's loop body ----
+            const StepOut so = env_advance<KIND>(cur, actf_env, act_env, a.episode_len, a.fixed_len != 0);
+            if (g.update_ret) { disc = disc * g.gamma + so.rew; }       // update_reward_stats! :167-171
+            float tobs[D]; env_obs<KIND>(cur.st, tobs);                 // terminal_observation (only used where truncated)
+            env_end_episode<KIND>(cur, env_seed, so, writer && a.ep_ret ? a.ep_ret + k : nullptr, a.ep_len + k);
+            float raw[D]; env_obs<KIND>(cur.st, raw);
+            float* mm = mom + (t & 1) * (1 + D) * MOMS;
+            if (writer) {
+                a.flags[k] = so.flags();
+                mm[e] = disc;
+#pragma unroll
+                for (int d = 0; d < D; ++d) mm[(1 + d) * MOMS + e] = raw[d];
+            }
+            lds_barrier();                                              // B_t: every env's columns of step t are published
+            // ---- the batch moments over all E envs (norm_step_kernel's tail; fold_partials16 over its one block adds zeros) ----
+            double bs = 0, bq = 0;                                      // this lane's column: sum and sum of squares
+#pragma unroll
+            for (int i = 0; i <= D; ++i) {
+                double s = 0, q = 0;
+#pragma unroll
+                for (int w = 0; w < kNormRolloutMaxEnvs / 64; ++w) {
+                    if (w > 0 && a.E <= 64 * w) break;                  // (uniform) a wave of zeros adds zero
+                    const int j = lane + 64 * w;
+                    double as = 0, aq = 0;                              // a thread of norm_step_kernel: acc = 0, then += its env's
+                    if (j < a.E) { const float x = mm[i * MOMS + j]; as += x; aq += (double)x * x; }
+                    s += wave_tree_f64(as); q += wave_tree_f64(aq);
+                }
+                if (lane == i) { bs = s; bq = q; }
+            }
+            // ---- norm_apply_kernel's head: lane 0 merges the returns, lanes 1 .. D the observation dims ----
+            const long long nb_ = a.E;
+            const float mean_old = s_mean, var_old = s_var;
+            const int upd = lane == 0 ? g.update_ret : g.update_obs;
+            if (upd) {
+                const double s = bs, q = bq;
+                const double bm = s / nb_; double bv = q / nb_ - bm * bm; if (bv < 0) bv = 0;
+                nz_merge(s_mean, s_var, s_count, (float)bm, (float)bv, nb_);
+                s_count += nb_;
+            }
+            obs_par ^= 1; ret_par ^= 1;
+            if (tile == 0 && lane <= D) {                               // the other half of the pair, which is then in force
+                RmsState* st_out = lane == 0 ? g.ret_rms + ret_par : g.obs_rms + obs_par;
+                st_out->mean[sd] = s_mean; st_out->var[sd] = s_var; if (lane <= 1) st_out->count = s_count;
+            }
+            // ---- norm_apply_kernel's per-env part ----
+            float r = so.rew;
+            const float rvar = lane_bcast(s_var, 0);                    // the NEW return variance
+            if (g.norm_reward) r = nz_reward(r, rvar, g.eps, g.clip_reward);
+            if (so.term || so.trunc) disc = 0.f;
+            float* sl = slot + ((t + 1) & 1) * SLOT;                    // what the critic reads between B_{t+1} and B_{t+2}
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const float m_new = lane_bcast(s_mean, 1 + d), v_new = lane_bcast(s_var, 1 + d), m_old = lane_bcast(mean_old, 1 + d), v_old = lane_bcast(var_old, 1 + d);
+                float v = raw[d];
+                if (g.norm_obs) { v = (v - m_new) / sqrtf(v_new + g.eps); v = fminf(fmaxf(v, -g.clip_obs), g.clip_obs); }   // NEW statistics
+                obs[d] = v;
+                if (g.norm_obs && so.trunc) {                           // terminal_observation: OLD statistics, :157-163
+                    float tv = (tobs[d] - m_old) / sqrtf(v_old + g.eps);
+                    tobs[d] = fminf(fmaxf(tv, -g.clip_obs), g.clip_obs);
+                }
+                if (h == 0) { sl[d * 32 + c] = v; sl[(D + d) * 32 + c] = tobs[d]; }
+                if (writer && so.trunc) g.e_tobs[(size_t)e * D + d] = tobs[d];
+            }
+            if (h == 0) sl[2 * D * 32 + c] = (so.trunc && valid) ? 1.0f : 0.0f;
+            if (writer) {
+                a.rew[k] = r;
+                if (t == a.T - 1) {                                     // the per-step arrays as the loop's last step leaves them
+                    g.e_rew[e] = so.rew; g.e_term[e] = so.term; g.e_trunc[e] = so.trunc;
+#pragma unroll
+                    for (int d = 0; d < D; ++d) { g.e_obs_raw[(size_t)e * D + d] = raw[d]; g.e_obs[(size_t)e * D + d] = obs[d]; }
+                }
+            }
+        }
+        lds_barrier();                                                  // B_T: slot T published
+        if (writer) { cur.store(env, e); g.disc_returns[e] = disc; }
+    } else {
+        // ================= critic: V(obs_t), V(terminal_observation) of step t - 1, the last values =================
+        __syncthreads();
+        for (int t = 0; t <= a.T; ++t) {
+            lds_barrier();                                              // B_t
+            const float* sl = slot + (t & 1) * SLOT;
+            int zoff = 0; asm volatile("" : "+v"(zoff));
+            const float* lc_t = lc + zoff;
+            float obs[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) obs[i] = sl[i * 32 + c];
+            float xk[FirstLayer<D>::KS], v[1];
+            pair_obs<D>(obs, h, xk);
+            eval_net<D, H, 1, false, SPLIT>(lc_t, a.w2a_critic, xk, v, lane);
+            if (t < a.T) { if (writer) a.val[(size_t)t * a.E + e] = v[0]; }
+            else if (writer) a.last_values[e] = v[0];                  // V(new_obs) for rollout-limited trajectories, trajectory.jl:65-70
+            if (t > 0) {
+                const bool trunc = sl[2 * D * 32 + c] != 0.0f;          // of step t - 1
+                if (__any(trunc)) {                                     // V(terminal_observation), trajectory.jl:57-61
+                    float tobs[D];
+#pragma unroll
+                    for (int i = 0; i < D; ++i) tobs[i] = sl[(D + i) * 32 + c];
+                    float tk[FirstLayer<D>::KS], bv[1];
+                    pair_obs<D>(tobs, h, tk);
+                    eval_net<D, H, 1, false, SPLIT>(lc_t, a.w2a_critic, tk, bv, lane);
+                    if (writer && trunc) a.boot[(size_t)(t - 1) * a.E + e] = bv[0];
+                }
+            }
+        }
+    }
+}
+template <int KIND, int H, bool SPLIT>
+__global__ __launch_bounds__(4 * kNormRolloutMaxEnvs, 2) void rollout_norm_kernel(NormRolloutArgs g) { rollout_norm_body<KIND, H, SPLIT>(g); }
+// n members of a population in one launch, grid (1, n): as rollout_duo_pop_kernel, a workgroup copies its member's argument block and runs the body above on it
+template <int KIND, int H, bool SPLIT>
+__global__ __launch_bounds__(4 * kNormRolloutMaxEnvs, 2) void rollout_norm_pop_kernel(const NormRolloutArgs* __restrict__ members) {
+    NormRolloutArgs g = members[blockIdx.y];
+    RolloutArgs& a = g.r;
+    a.params = pop_global(a.params); a.state = pop_global(a.state); a.step_count = pop_global(a.step_count); a.episode = pop_global(a.episode); a.gstep = pop_global(a.gstep);
+    a.obs = pop_global(a.obs); a.act = pop_global(a.act); a.rew = pop_global(a.rew); a.logp = pop_global(a.logp); a.val = pop_global(a.val); a.boot = pop_global(a.boot);
+    a.flags = pop_global(a.flags); a.last_values = pop_global(a.last_values); a.noise = pop_global(a.noise); a.w2a_actor = pop_global(a.w2a_actor); a.w2a_critic = pop_global(a.w2a_critic);
+    a.mon_cur_ret = pop_global(a.mon_cur_ret); a.mon_cur_len = pop_global(a.mon_cur_len); a.ep_ret = pop_global(a.ep_ret); a.ep_len = pop_global(a.ep_len);
+    g.disc_returns = pop_global(g.disc_returns); g.obs_rms = pop_global(g.obs_rms); g.ret_rms = pop_global(g.ret_rms);
+    g.e_obs = pop_global(g.e_obs); g.e_obs_raw = pop_global(g.e_obs_raw); g.e_rew = pop_global(g.e_rew); g.e_term = pop_global(g.e_term); g.e_trunc = pop_global(g.e_trunc); g.e_tobs = pop_global(g.e_tobs);
+    rollout_norm_body<KIND, H, SPLIT>(g);
+}
+
+// =============================================================================================
 // evaluate_kernel — the loop of evaluate_agent (evaluation.jl:90-122) for g.r.T env steps in one launch: predict_actions(deterministic) -> act! -> observe, and
 // the episode accounting of dril_eval_account.h.  rollout_kernel without what an evaluation does not need: the ACTOR's weights alone in LDS (no critic forward, no
 // V(terminal_observation), no last values), no buffer row, no monitor.  A wave owns 32 envs; EnvCursor is loaded once and stored at the end, the running return /
@@ -1589,6 +1799,34 @@ hipError_t launch_rollout(int kind, int hidden, const RolloutArgs& a, hipStream_
     });
 #undef CALL
 #undef CALLS
+}
+
+// rollout_norm_kernel: ONE workgroup of two waves per tile of 32 envs, so that every wave launched reaches every barrier; hidden [64,64] on the f16-piece forward only
+template <int KIND> static size_t norm_rollout_lds_bytes() {
+    constexpr int D = EnvSpec<KIND>::D, A = EnvSpec<KIND>::A;
+    return sizeof(float) * (FwdLds<D, 64, A, false, true>::SIZE + FwdLds<D, 64, 1, false, true>::SIZE + NormRolloutLds<D>::SIZE);
+}
+hipError_t launch_rollout_norm(int kind, const NormRolloutArgs& a, hipStream_t s) {
+    if (a.r.E < 1 || a.r.E > kNormRolloutMaxEnvs || a.r.exact_f32) return hipErrorInvalidValue;
+    const int tiles = (a.r.E + kTile - 1) / kTile;
+    return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;
+        const size_t lds = norm_rollout_lds_bytes<KIND>();
+        { hipError_t e = set_max_dynamic_lds((const void*)rollout_norm_kernel<KIND, 64, true>, lds); if (e != hipSuccess) return e; }
+        rollout_norm_kernel<KIND, 64, true><<<1, 128 * tiles, lds, s>>>(a);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_rollout_norm_pop(int kind, const NormRolloutArgs* d_members, int n, int E, hipStream_t s) {
+    if (!d_members || n < 1 || n > 65535 || E < 1 || E > kNormRolloutMaxEnvs) return hipErrorInvalidValue;
+    const int tiles = (E + kTile - 1) / kTile;
+    return with_env_kind<KindShare::None>(kind, [&](auto K) -> hipError_t {
+        constexpr int KIND = decltype(K)::value;
+        const size_t lds = norm_rollout_lds_bytes<KIND>();
+        { hipError_t e = set_max_dynamic_lds((const void*)rollout_norm_pop_kernel<KIND, 64, true>, lds); if (e != hipSuccess) return e; }
+        rollout_norm_pop_kernel<KIND, 64, true><<<dim3(1, (unsigned)n), 128 * tiles, lds, s>>>(d_members);
+        return hipGetLastError();
+    });
 }
 
 // evaluate_kernel: the fused shapes (two equal tanh layers of 64 / 128 / 256); the forward choice (a.r.exact_f32) and the kind dispatch are the rollout's

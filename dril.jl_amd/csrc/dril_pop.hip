@@ -14,12 +14,14 @@ using namespace dril::ppo;
 
 // ---- populations: many small PPO agents per launch (docs/population.md) ------------------------------------------------------------------
 // A population joins ordinary PPO handles for batched launches: one rollout_duo_pop_kernel and one ppo_update_small_pop_kernel where P solo iterations launch
-// rollout_duo_kernel and ppo_update_small_kernel P times.  It keeps no copy of member state: every verb reads each handle with the solo path's own functions
+// rollout_duo_kernel and ppo_update_small_kernel P times.  Normalising members (NormalizeWrapperEnv with dril_norm_rollout_enable on) collect through one
+// rollout_norm_pop_kernel launch, after each member's opening observe.  It keeps no copy of member state: every verb reads each handle with the solo path's own functions
 // (rollout_args, update_begin, small_update_args, update_enqueue_home, update_finish, update_resolve), so a member's result is that of its handle driven alone, bit for bit.
 // While joined, the members share the population's stream: whatever a member's own verbs enqueue between population calls is ordered with the batched launches.
 struct dril_population {
     std::vector<dril_handle*> members; std::vector<hipStream_t> own_streams;
     hipStream_t stream = nullptr; int device = 0, cap = 1; int64_t chunk = 16384, total_steps = 0; int n_chunks = 1;
+    PinnedBuf<NormRolloutArgs> h_nargs; DevBuf<NormRolloutArgs> d_nargs;   // normalising members: the blocks of rollout_norm_pop_kernel, pinned / device [n]
     PinnedBuf<RolloutArgs> h_rargs; DevBuf<RolloutArgs> d_rargs; PinnedBuf<SmallUpdateArgs> h_uargs; DevBuf<SmallUpdateArgs> d_uargs;   // pinned / device: [n] and [n_chunks][n]
     DevBuf<unsigned long long> xchg;                             // n x kSmallXchgWords
     std::vector<PinnedBuf<char>> home_blocks; std::vector<UpdateHome> homes;   // one pinned block per member: where its update's results land
@@ -41,12 +43,13 @@ std::string pop_ineligible(const dril_handle* h, int& code) {
     if (h->external) return "an external handle (DRIL_ENV_EXTERNAL): its envs live with the caller";
     if (h->env.is_world()) return "a world of a device env plug-in";
     if (h->env.module || !env_kind_info(h->cfg.env_kind)) return "a device env plug-in handle (DRIL_ENV_MODULE): populations take the built-in env kinds";
-    if (normalizing(h) || h->pn.on) return "a normalising handle (NormalizeWrapperEnv collects step by step)";
+    if (h->pn.on || (normalizing(h) && !h->norm_rollout)) return "a normalising handle (NormalizeWrapperEnv collects step by step): a built-in handle becomes eligible with the one-launch collection, dril_norm_rollout_enable(h, 1)";
+    if (normalizing(h)) { const std::string why = norm_rollout_unavailable(h); if (!why.empty()) return "a normalising handle whose one-launch collection is not available: " + why; }
     if (h->cfg.world_size > 1 || comm_ready(h)) return "world_size > 1: members are single-rank handles";
     if (h->generic || h->wide || h->cfg.hidden1 != 64) return "a generic or wide net: members have hidden_dims [64,64] with tanh";
     const UpdatePlan plan = update_plan(h);
     if (plan.B > 64) return "batch_size " + std::to_string((long long)plan.B) + " > 64: the persistent update kernel takes minibatches of 2..64 samples";
-    if (h->force_stepwise || !rollout_fused_applies(h) || !rollout_duo_applies(h->cfg.hidden1, h->cfg.n_envs)) return "its collection is not one launch of rollout_duo_kernel (n_envs <= 16384, not step-granular)";
+    if (!normalizing(h) && (h->force_stepwise || !rollout_fused_applies(h) || !rollout_duo_applies(h->cfg.hidden1, h->cfg.n_envs))) return "its collection is not one launch of rollout_duo_kernel (n_envs <= 16384, not step-granular)";
     if (h->grad_variant >= 0 || h->no_persistent || h->no_small_path || !small_persistent_applies(h, plan)) return "its update is not one launch of ppo_update_small_kernel (2 <= batch_size <= 64, default gradient variant, persistent update on)";
     return "";
 }
@@ -59,6 +62,8 @@ std::string pop_mismatch(const dril_handle* a, const dril_handle* b, int& code) 
     if (x.n_envs != y.n_envs || x.n_steps != y.n_steps || x.batch_size != y.batch_size || x.epochs != y.epochs) return "mixed shapes (n_envs, n_steps, batch_size and epochs must equal member 0's)";
     if (x.hidden1 != y.hidden1 || x.hidden2 != y.hidden2 || x.n_hidden != y.n_hidden || x.activation != y.activation) return "mixed shapes (hidden dims and activation must equal member 0's)";
     if (x.normalize_advantage != y.normalize_advantage) return "mixed shapes (normalize_advantage must equal member 0's)";
+    if ((x.norm_obs != 0) != (y.norm_obs != 0) || (x.norm_reward != 0) != (y.norm_reward != 0) || (x.norm_training != 0) != (y.norm_training != 0) || a->norm_rollout != b->norm_rollout)
+        return "mixed NormalizeWrapperEnv (norm_obs, norm_reward, norm_training and dril_norm_rollout_enable must equal member 0's; clips, epsilon, norm_gamma and the statistics are free)";
     return "";
 }
 void pop_release(dril_population* p) {
@@ -103,14 +108,47 @@ void pop_call_begin(dril_population* p) {
 // f16-piece forward, collect_rollout itself for the others; then per member what follows the launch in collect_rollout (monitor window, GAE)
 int pop_collect(dril_population* p, double* fps, bool do_sync, int& first) {
     const int n = (int)p->members.size();
-    std::vector<int> batched, solo;
+    std::vector<int> batched, nbatched, solo;                     // one rollout_duo_pop_kernel launch; one rollout_norm_pop_kernel launch; alone
     for (int m = 0; m < n; ++m) {
         dril_handle* h = p->members[m];
         if (p->failed[m]) continue;
         if (fps) fps[m] = 0;
         if (!h->env.ready) { pop_member_failed(p, m, fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset"), "dril_population_collect_rollout", first); continue; }
         { const int rcw = ensure_wimg(h); if (rcw) { pop_member_failed(p, m, rcw, "dril_population_collect_rollout", first); continue; } }
-        if (rollout_fused_applies(h) && h->cfg.hidden1 == 64 && rollout_duo_applies(h->cfg.hidden1, h->env.E) && !fwd_exact(h)) batched.push_back(m); else solo.push_back(m);
+        if (rollout_fused_applies(h) && h->cfg.hidden1 == 64 && rollout_duo_applies(h->cfg.hidden1, h->env.E) && !fwd_exact(h)) batched.push_back(m);
+        else if (norm_rollout_applies(h)) nbatched.push_back(m);
+        else solo.push_back(m);
+    }
+    if (!nbatched.empty()) {                                      // collect_rollout's one-launch route, member by member around ONE launch
+        const int nbat = (int)nbatched.size();
+        hipError_t e = hipSuccess;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (fps) e = hipStreamSynchronize(p->stream);
+        pop_ev_begin(p, 0);
+        std::vector<int> orc((size_t)nbat, DRIL_OK);
+        for (int k = 0; k < nbat; ++k) {
+            dril_handle* h = p->members[nbatched[k]];
+            orc[k] = observe_dev(h, true);                          // new_obs = observe(env), trajectory.jl:32 (two launches per member)
+            p->h_nargs[k] = norm_rollout_args(h);                   // (a member whose observe failed keeps its block: the launch is skipped below)
+            if (orc[k]) e = hipErrorUnknown;
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(p->d_nargs, p->h_nargs, sizeof(NormRolloutArgs) * (size_t)nbat, hipMemcpyHostToDevice, p->stream);
+        if (e == hipSuccess) e = launch_rollout_norm_pop(p->members[0]->cfg.env_kind, p->d_nargs, nbat, p->members[0]->env.E, p->stream);
+        pop_ev_end(p);
+        double f = 0;
+        if (fps && e == hipSuccess) {
+            e = hipStreamSynchronize(p->stream);
+            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            f = (double)p->members[0]->N / (dt > 0 ? dt : 1e-12);
+        }
+        p->info.last_rollout_launches += 1 + 2 * nbat; p->info.total_rollout_launches += 1 + 2 * nbat;
+        for (int k = 0; k < nbat; ++k) {
+            const int m = nbatched[k]; dril_handle* h = p->members[m];
+            int rc = orc[k] ? orc[k] : e == hipSuccess ? DRIL_OK : fail(h, DRIL_ERR_HIP, std::string("rollout_norm_pop_kernel: ") + hipGetErrorString(e));
+            if (!rc) { if (fps) fps[m] = f; norm_rollout_done(h); h->noise_set = false; rc = monitor_collect_rollout(h); }
+            if (!rc) rc = compute_gae(h);
+            if (rc) pop_member_failed(p, m, rc, "dril_population_collect_rollout", first);
+        }
     }
     if (!batched.empty()) {
         const int nbat = (int)batched.size();
@@ -329,6 +367,8 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
     JCHK(p->h_rargs.alloc((size_t)n));
     JCHK(p->h_uargs.alloc(((size_t)p->n_chunks + 1) * n));   // the launch table, and behind it one block per member
     JCHK(p->d_rargs.alloc((size_t)n));
+    JCHK(p->h_nargs.alloc((size_t)n));
+    JCHK(p->d_nargs.alloc((size_t)n));
     JCHK(p->d_uargs.alloc((size_t)p->n_chunks * n));
     JCHK(p->xchg.alloc((size_t)n * kSmallXchgWords));
     JCHK(p->h_eargs.alloc((size_t)n));

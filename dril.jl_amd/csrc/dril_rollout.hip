@@ -52,6 +52,16 @@ int collect_rollout_stepwise(dril_handle* h) {
     return monitor_collect_rollout(h);
 }
 
+// the same collection in ONE launch of rollout_norm_kernel (dril_norm_rollout_enable), after the opening observe(env) that the loop above starts with: it leaves env state,
+// counters, disc_returns, the statistics' half in force, the per-step arrays, last_values and the monitor's sums as that loop leaves them
+int collect_rollout_norm(dril_handle* h) {
+    int rc = observe_dev(h, true); if (rc) return rc;                                      // new_obs = observe(env), trajectory.jl:32
+    const NormRolloutArgs g = norm_rollout_args(h);
+    HIPCHK(h, launch_rollout_norm(h->env.kind, g, h->stream));
+    norm_rollout_done(h);
+    return monitor_collect_rollout(h);
+}
+
 // step-granular collect_trajectories for a device env plug-in: two launch groups per env step,
 //   policy (generic forward + sampling head, + V(terminal_observation) of the previous step) -> the plug-in's step kernel
 // which writes reward and BUF_FLAGS byte straight into row t, the terminal observation and the next observation into the per-step arrays (one env launch where
@@ -160,6 +170,33 @@ RolloutArgs rollout_args(const dril_handle* h) {
     a.mon_cur_ret = h->mon_cur_ret; a.mon_cur_len = h->mon_cur_len; a.ep_ret = h->ep_ret; a.ep_len = h->ep_len;
     return a;
 }
+std::string norm_rollout_unavailable(const dril_handle* h) {
+    if (h->env.module) return "the handle steps a device env plug-in (DRIL_ENV_MODULE): its NormalizeWrapperEnv is dril_normalize_enable and its one-launch collection dril_rollout_fused_enable; this verb is for the built-in env kinds";
+    if (h->external) return "the envs of a DRIL_ENV_EXTERNAL handle are the caller's: its NormalizeWrapperEnv is dril_ext_normalize_enable and its collection the dril_ext_* verbs; this verb is for the built-in env kinds";
+    if (!normalizing(h)) return "the handle has no NormalizeWrapperEnv (cfg.norm_obs = cfg.norm_reward = 0): its collection already is one launch of the rollout kernel; create it with norm_obs and / or norm_reward";
+    if (h->generic) return "the handle runs the generic layer-by-layer kernels (hidden_dims other than two equal tanh layers of 32 / 64 / 128 / 256, or DRIL_FORCE_GENERIC): rollout_norm_kernel is built for hidden_dims [64,64]; collect step-granular, which is the default";
+    if (h->wide || h->cfg.hidden1 != 64) return "hidden_dims [" + std::to_string(h->cfg.hidden1) + "," + std::to_string(h->cfg.hidden2) + "]: rollout_norm_kernel is built for hidden_dims [64,64] alone; collect step-granular, which is the default";
+    if (h->cfg.n_envs > kNormRolloutMaxEnvs) return "n_envs = " + std::to_string(h->cfg.n_envs) + ": one workgroup couples at most " + std::to_string(kNormRolloutMaxEnvs) + " envs through LDS; use n_envs <= " + std::to_string(kNormRolloutMaxEnvs) + ", or collect step-granular, which is the default";
+    if (h->cfg.world_size > 1 || comm_ready(h)) return "the handle is part of a data-parallel job (world_size > 1 or a ready communicator): its batch moments are an all-reduce per env step, which one launch cannot hold; collect step-granular, which is the default";
+    if (h->force_stepwise) return "DRIL_FORCE_STEPWISE is set: every collection of this handle runs the step-granular launches; unset it and create the handle again";
+    return "";
+}
+bool norm_rollout_applies(const dril_handle* h) { return h->norm_rollout && !fwd_exact(h) && norm_rollout_unavailable(h).empty(); }
+NormRolloutArgs norm_rollout_args(const dril_handle* h) {
+    NormRolloutArgs g{};
+    g.r = rollout_args(h);
+    g.disc_returns = h->env.disc_returns; g.obs_rms = h->obs_rms; g.ret_rms = h->ret_rms; g.obs_par = h->obs_par; g.ret_par = h->ret_par;
+    g.update_obs = (h->cfg.norm_obs && h->cfg.norm_training) ? 1 : 0; g.update_ret = (h->cfg.norm_reward && h->cfg.norm_training) ? 1 : 0;
+    g.norm_obs = h->cfg.norm_obs; g.norm_reward = h->cfg.norm_reward;
+    g.gamma = h->cfg.norm_gamma; g.clip_obs = h->cfg.clip_obs; g.clip_reward = h->cfg.clip_reward; g.eps = h->cfg.norm_epsilon;
+    g.e_obs = h->e_obs; g.e_obs_raw = h->e_obs_raw; g.e_rew = h->e_rew; g.e_term = h->e_term; g.e_trunc = h->e_trunc; g.e_tobs = h->e_tobs;
+    return g;
+}
+// the kernel flipped both ping-pong pairs once per env step, as the loop's host does
+void norm_rollout_done(dril_handle* h) {
+    h->obs_par ^= h->cfg.n_steps & 1; h->ret_par ^= h->cfg.n_steps & 1;
+    h->norm_rollout_path = 1; h->norm_rollout_launches = 3 + (h->mon_cur_ret ? 2 : 0);     // observe (2), the kernel, the monitor's window (2)
+}
 int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
     if (!h->env.ready) return fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset");
     { int rcw = ensure_wimg(h); if (rcw) return rcw; }
@@ -169,8 +206,15 @@ int collect_rollout(dril_handle* h, double* fps, bool do_sync) {
         prof_begin(h, DRIL_K_ROLLOUT);
         h->rollout_launches = 0; h->gws.launches = 0;
         if (h->fused_rollout) { const std::string why = fused_rollout_unavailable(h); if (!why.empty()) { prof_end(h); return fail(h, DRIL_ERR_UNSUPPORTED, "dril_collect_rollout with the fused rollout on: " + why); } }
-        int rcs = h->env.module ? (h->fused_rollout ? collect_rollout_module_fused(h) : h->pn.on ? collect_rollout_module_norm(h) : collect_rollout_module(h)) : collect_rollout_stepwise(h);
+        const bool one_launch = !h->env.module && norm_rollout_applies(h);
+        int rcs = h->env.module ? (h->fused_rollout ? collect_rollout_module_fused(h) : h->pn.on ? collect_rollout_module_norm(h) : collect_rollout_module(h))
+                                : one_launch ? collect_rollout_norm(h) : collect_rollout_stepwise(h);
         h->rollout_launches += h->gws.launches + (h->mon_cur_ret ? 1 : 0);
+        if (!h->env.module && !h->generic && normalizing(h)) {           // what dril_norm_rollout_info reports: observe (2), the kernel or 3 per env step + the last values, the monitor's window (2)
+            h->norm_rollout_path = one_launch ? 1 : 0;
+            h->norm_rollout_launches = 2 + (one_launch ? 1 : 3 * (int64_t)h->cfg.n_steps + 1) + (h->mon_cur_ret ? 2 : 0);
+            if (h->norm_rollout && !one_launch && fwd_exact(h)) h->norm_rollout_fallbacks += 1;
+        }
         prof_end(h);
         if (rcs) return rcs;
         if (fps) { HIPCHK(h, hipStreamSynchronize(h->stream)); const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0s).count(); *fps = (double)h->N / (dt > 0 ? dt : 1e-12); }
@@ -212,6 +256,22 @@ DRIL_EXPORT int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rol
     const std::string why = fused_rollout_unavailable(h);
     out->available = why.empty() ? 1 : 0; out->enabled = h->fused_rollout ? 1 : 0; out->last_collection_launches = h->rollout_launches;
     if (h->env.module && h->env.rollout.has_desc) { out->tile = h->env.rollout.desc.tile; out->threads = h->env.rollout.desc.threads; out->max_width = h->env.rollout.desc.max_width; }
+    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_norm_rollout_enable(dril_handle* h, int32_t on) {
+    NEED(h);
+    if (on) { const std::string why = norm_rollout_unavailable(h); if (!why.empty()) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_norm_rollout_enable: " + why); }
+    h->norm_rollout = on != 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_norm_rollout_info(const dril_handle* h, dril_norm_rollout_report* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_norm_rollout_info: null out pointer");
+    std::memset(out, 0, sizeof(*out));
+    const std::string why = norm_rollout_unavailable(h);
+    out->available = why.empty() ? 1 : 0; out->enabled = h->norm_rollout ? 1 : 0; out->max_envs = kNormRolloutMaxEnvs;
+    out->last_collection_path = h->norm_rollout_path; out->last_collection_launches = h->norm_rollout_launches; out->total_stepwise_fallbacks = h->norm_rollout_fallbacks;
     std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
     return DRIL_OK;
 }

@@ -585,6 +585,19 @@ class Handle:
         return dict(available=bool(info.available), enabled=bool(info.enabled), tile=info.tile, threads=info.threads, max_width=info.max_width,
                     last_collection_launches=info.last_collection_launches, reason=info.reason.decode())
 
+    def norm_rollout_enable(self, on: bool = True):
+        """dril_norm_rollout_enable: collections of a normalising built-in handle (n_envs <= 128, hidden_dims [64,64]) as the opening observe and ONE launch of
+        rollout_norm_kernel instead of three launches per env step (docs/normalized_rollout.md); legal at any time between collections"""
+        self._chk(self.lib.dril_norm_rollout_enable(self._h, int(bool(on))))
+
+    def norm_rollout_info(self) -> dict:
+        """dril_norm_rollout_info: available / enabled / max_envs / last_collection_launches / last_collection_path (1 = the kernel, 0 = step-granular) /
+        total_stepwise_fallbacks / reason"""
+        info = capi.DrilNormRolloutInfo()
+        self._chk(self.lib.dril_norm_rollout_info(self._h, C.byref(info)))
+        return dict(available=bool(info.available), enabled=bool(info.enabled), max_envs=info.max_envs, last_collection_launches=info.last_collection_launches,
+                    last_collection_path=info.last_collection_path, total_stepwise_fallbacks=info.total_stepwise_fallbacks, reason=info.reason.decode())
+
     def evaluate_fused_info(self) -> dict:
         """dril_evaluate_fused_info: available / tile / threads / max_width / reason — whether persistent=True of the evaluation and trajectory verbs would run the
         plug-in's own evaluation kernel (path 2; a code object built with DRIL_ENV_PLUGIN_EVALUATE, include/device/dril_env_evaluate.h) on this handle"""
@@ -1122,6 +1135,7 @@ class DeviceParallelEnv:
         self._last_term = np.zeros(n_envs, bool)
         self._last_trunc = np.zeros(n_envs, bool)
         self.last_f32_paths: list = []      # dril_ppo_stats.f32_path of every iteration of the last train_ (0 = the default kernels throughout)
+        self.norm_fused_rollout = False     # NormalizeWrapperEnv(env, fused_rollout=True): dril_norm_rollout_enable on every handle bound to this env
 
     def f32_fallback_info(self) -> dict:
         """how often this env's handle left the f16-piece arithmetic (dril_f32_fallback_info); all zeros for a healthy run on normalised data"""
@@ -1142,11 +1156,13 @@ class DeviceParallelEnv:
         return self.handle
 
     def _bind_extra(self):
-        """what a subclass adds to bind's key"""
-        return None
+        """what bind's key holds beyond the config: here the one-launch normalised collection; a subclass states its own"""
+        return self.norm_fused_rollout
 
     def _after_create(self, h: Handle):
-        """verbs a subclass applies to a freshly created handle, before its first reset"""
+        """verbs applied to a freshly created handle, before its first reset: here the one-launch normalised collection; a subclass states its own"""
+        if self.norm_fused_rollout:
+            h.norm_rollout_enable(True)
 
     def _h(self) -> Handle:
         return self.handle or self.bind(PPO(n_steps=1, batch_size=self.n_envs * max(1, self._kw["world_size"])))
@@ -1588,9 +1604,15 @@ def MonitorWrapperEnv(env: DeviceParallelEnv, stats_window: int = 100) -> Device
 
 
 def NormalizeWrapperEnv(env: DeviceParallelEnv, *, training: bool = True, norm_obs: bool = True, norm_reward: bool = True,
-                        clip_obs: float = 10.0, clip_reward: float = 10.0, gamma: float = 0.99, epsilon: float = 1e-8) -> DeviceParallelEnv:
+                        clip_obs: float = 10.0, clip_reward: float = 10.0, gamma: float = 0.99, epsilon: float = 1e-8,
+                        fused_rollout: bool = False) -> DeviceParallelEnv:
     """NormalizeWrapperEnv(env; kwargs...) (normalizeWrapperEnv.jl:71-107).  On device the wrapper is a mode of the same
-    handle (running mean/std kernels fused around the env step), so this returns the env with the wrapper switched on."""
+    handle (running mean/std kernels fused around the env step), so this returns the env with the wrapper switched on.
+    `fused_rollout=True` (built-in envs, n_envs <= 128, hidden_dims [64,64]) asks every handle bound to the env to collect in ONE launch of rollout_norm_kernel
+    (dril_norm_rollout_enable, docs/normalized_rollout.md) — through `train_` and `train_population_` alike; the library refuses, with what to do, where it cannot."""
+    if fused_rollout and (isinstance(env, (HostParallelEnv, DeviceArrayParallelEnv, DeviceModuleEnv)) or not (norm_obs or norm_reward)):
+        raise TypeError("NormalizeWrapperEnv(fused_rollout=True) is the one-launch collection of a normalising built-in env (norm_obs and / or norm_reward): a device env "
+                        "plug-in has DeviceModuleEnv(path, n, fused_rollout=True), host and device-array envs step outside the library")
     if isinstance(env, HostParallelEnv):
         raise TypeError("NormalizeWrapperEnv: the envs of a HostParallelEnv live on the host and are wrapped there (the statistics couple all envs at every step); the device wrappers take a DeviceParallelEnv or a DeviceArrayParallelEnv")
     if isinstance(env, DeviceArrayParallelEnv):                                      # the handle's own wrapper (dril_ext_normalize_enable): the same object, the wrapper recorded
@@ -1599,6 +1621,7 @@ def NormalizeWrapperEnv(env: DeviceParallelEnv, *, training: bool = True, norm_o
         return env
     env._kw["normalize"] = dict(training=training, norm_obs=norm_obs, norm_reward=norm_reward, clip_obs=clip_obs,
                                 clip_reward=clip_reward, gamma=gamma, epsilon=epsilon)
+    env.norm_fused_rollout = bool(fused_rollout)
     if env.handle is not None:
         env.handle.close(); env.handle = None
     if isinstance(env, DeviceModuleEnv) and (norm_obs or norm_reward):   # cfg.norm_* are the built-in envs': fail here, with the library's message and the way that works

@@ -104,13 +104,15 @@ end
 
 function DeviceParallelEnv(kind::Symbol, n_envs::Integer; max_steps::Integer = (kind === :CartPole || kind === :Acrobot) ? 500 : (kind === :MountainCarContinuous || kind === :ScaledMountainCarContinuous) ? 999 : 200,
         seed::Integer = 42, fixed_length_episodes::Bool = false, device::Integer = 0, monitor_window::Integer = 0,
-        normalize::Union{Nothing, NamedTuple} = nothing)
+        normalize::Union{Nothing, NamedTuple} = nothing, fused_rollout::Bool = false)      # fused_rollout: with `normalize` on a built-in env (n_envs <= 128, hidden_dims [64,64]), collections in ONE launch of rollout_norm_kernel (dril_norm_rollout_enable, applied in bind!)
     haskey(ENV_KINDS, kind) || error("unknown device env $kind")
     env = DeviceParallelEnv(kind, n_envs, max_steps, UInt64(seed), fixed_length_episodes, device, monitor_window, normalize,
         C_NULL, nothing, fill(false, n_envs), fill(false, n_envs), nothing, Dict{String, Float64}())
     finalizer(e -> (e.handle != C_NULL && ccall((:dril_destroy, LIB[]), Int32, (Ptr{Cvoid},), e.handle); nothing), env)
+    fused_rollout && kind !== :Module && (NORM_FUSED_ROLLOUT[env] = true)
     return env
 end
+const NORM_FUSED_ROLLOUT = IdDict{Any, Bool}()            # env => the one-launch normalised collection was asked for (DeviceParallelEnv(...; normalize, fused_rollout = true))
 
 number_of_envs(env::DeviceParallelEnv) = env.n_envs
 
@@ -232,6 +234,7 @@ function bind!(env::DeviceParallelEnv, alg::PPO, hidden::Vector{Int} = [64, 64],
             env.normalize === nothing || normalize_enable!(h[], env.normalize)   # train!(agent, env, alg::PPO, ...) and evaluate_agent then run under the wrapper (evaluation: frozen, raw returns)
         else
             check(ccall((:dril_create, LIB[]), Int32, (Ref{DrilConfig}, Ref{Ptr{Cvoid}}), cfg, h))
+            get(NORM_FUSED_ROLLOUT, env, false) && check(ccall((:dril_norm_rollout_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), h[], Int32(1)), h[])   # NormalizeWrapperEnv's collections in one launch; the library refuses, with what to do, where it cannot
         end
         env.handle = h[]; env.bound = key; env.optimizer_owner = nothing
         check(ccall((:dril_env_reset, LIB[]), Int32, (Ptr{Cvoid}, UInt64), env.handle, env.seed), env.handle)
@@ -245,6 +248,14 @@ function rollout_fused_info(env::DeviceParallelEnv)
     i32 = reinterpret(Int32, buf[1:24])
     return (available = i32[1] != 0, enabled = i32[2] != 0, tile = Int(i32[3]), threads = Int(i32[4]), max_width = Int(i32[5]),
         last_collection_launches = Int(reinterpret(Int64, buf[25:32])[1]), reason = String(buf[33:(32 + something(findfirst(==(0x00), buf[33:end]), 257) - 1)]))
+end
+"dril_norm_rollout_info of the env's handle: (available, enabled, max_envs, last_collection_path, last_collection_launches, total_stepwise_fallbacks, reason) — path 1 = rollout_norm_kernel, 0 = step-granular"
+function norm_rollout_info(env::DeviceParallelEnv)
+    buf = zeros(UInt8, 288)                                      # dril_norm_rollout_report: 4 x Int32, 2 x Int64, char[256]
+    check(ccall((:dril_norm_rollout_info, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), handle(env), buf), handle(env))
+    i32 = reinterpret(Int32, buf[1:16]); i64 = reinterpret(Int64, buf[17:32])
+    return (available = i32[1] != 0, enabled = i32[2] != 0, max_envs = Int(i32[3]), last_collection_path = Int(i32[4]), last_collection_launches = Int(i64[1]),
+        total_stepwise_fallbacks = Int(i64[2]), reason = String(buf[33:(32 + something(findfirst(==(0x00), buf[33:end]), 257) - 1)]))
 end
 "dril_evaluate_fused_info of the env's handle: (available, tile, threads, max_width, reason) — whether `persistent = true` of evaluate_agent / collect_trajectory would run the plug-in's own evaluation kernel (path 2)"
 function evaluate_fused_info(env::DeviceParallelEnv)

@@ -266,6 +266,29 @@ typedef struct dril_fused_rollout_info {
 } dril_fused_rollout_info;
 int32_t dril_rollout_fused_enable(dril_handle* h, int32_t on);
 int32_t dril_rollout_fused_info(const dril_handle* h, dril_fused_rollout_info* out);
+/* The ONE-LAUNCH COLLECTION of a normalising built-in handle (cfg.norm_obs / cfg.norm_reward on a built-in env kind, docs/normalized_rollout.md).  By default such a
+ * handle collects step-granular: three launches per env step, because NormalizeWrapperEnv's running statistics couple all envs at every step.  Up to max_envs = 128
+ * envs fit in one workgroup, which couples them through LDS: on != 0 makes dril_collect_rollout and dril_train run collect_trajectories as the opening observe and
+ * ONE launch of rollout_norm_kernel, whatever n_steps is.  Opt-in, off by default, legal at any time between collections; the step verbs, the dril_norm_* verbs, the
+ * evaluation and trajectory verbs are untouched and may run between two such collections, and a collection of either kind may follow the other.
+ * Equality: observations, actions, rewards, log-probabilities, flags, the running statistics and their counts, env state and the monitor's figures are bit-equal to
+ * the step-granular collection of the same handle (the batch moments are summed by the same tree); values, last values and bootstrap values agree to 1e-6 (the
+ * critic's two forward forms, as between the step-granular launches and rollout_duo_kernel).
+ * A collection while the forward is the exact-f32 one (max |W2| >= 350, dril_f32_fallback_info) runs step-granular for that call and is counted.
+ * DRIL_ERR_UNSUPPORTED, each with a message that says what to do and the handle left as it was, for: a handle that is not a normalising built-in handle (plug-ins have
+ * dril_normalize_enable, external handles dril_ext_normalize_enable); a generic or wide net, hidden 32; n_envs > max_envs; world_size > 1 or a ready communicator
+ * (the batch moments are an all-reduce per env step); DRIL_FORCE_STEPWISE / DRIL_FORCE_GENERIC. */
+typedef struct dril_norm_rollout_report {
+    int32_t available;                 /* dril_norm_rollout_enable(h, 1) would be accepted */
+    int32_t enabled;
+    int32_t max_envs;                  /* the envs one workgroup couples: 128 */
+    int32_t last_collection_path;      /* of the last collection of a normalising built-in handle: 1 = rollout_norm_kernel, 0 = step-granular */
+    int64_t last_collection_launches;  /* launch calls that collection enqueued for collect_trajectories (the opening observe and the monitor's window included, GAE not) */
+    int64_t total_stepwise_fallbacks;  /* collections of an enabled handle that ran step-granular because the forward was the exact-f32 one */
+    char reason[256];                  /* why it is not available ("" when it is) */
+} dril_norm_rollout_report;
+int32_t dril_norm_rollout_enable(dril_handle* h, int32_t on);
+int32_t dril_norm_rollout_info(const dril_handle* h, dril_norm_rollout_report* out);
 /* The FUSED EVALUATION of a device env plug-in (include/device/dril_env_evaluate.h): a code object built with DRIL_ENV_PLUGIN_EVALUATE(Env) holds a second, optional
  * kernel with the env inlined — K env steps of observe, (frozen) normalisation, actor forward, mode or draw and the transition in ONE launch, a workgroup per tile
  * of envs, no grid barrier — with a descriptor and an ABI number of its own (the rollout's are untouched).  It is path 2 of dril_evaluate_agent_device and
