@@ -130,6 +130,13 @@ class DrilNormRolloutInfo(C.Structure):
                 ("last_collection_launches", C.c_int64), ("total_stepwise_fallbacks", C.c_int64), ("reason", C.c_char * 256)]
 
 
+class DrilUpdateFusedInfo(C.Structure):
+    """struct dril_update_fused_report, include/dril_hip.h (what dril_update_fused_info fills)"""
+    _fields_ = [("available", C.c_int32), ("enabled", C.c_int32), ("max_width", C.c_int32), ("max_obs_dim", C.c_int32), ("max_action_dim", C.c_int32),
+                ("max_params", C.c_int32), ("max_hidden_layers", C.c_int32), ("min_batch", C.c_int32), ("max_batch", C.c_int32), ("faster_up_to_batch", C.c_int32), ("reserved", C.c_int32), ("last_update_path", C.c_int32),
+                ("last_update_launches", C.c_int64), ("steps_per_launch", C.c_int64), ("reason", C.c_char * 256)]
+
+
 class DrilFusedEvaluateInfo(C.Structure):
     """struct dril_fused_evaluate_info, include/dril_hip.h"""
     _fields_ = [("available", C.c_int32), ("tile", C.c_int32), ("threads", C.c_int32), ("max_width", C.c_int32), ("reason", C.c_char * 256)]
@@ -252,6 +259,8 @@ _SIG = {
     "dril_rollout_fused_info": (C.c_int32, [_P, _P]),
     "dril_norm_rollout_enable": (C.c_int32, [_P, C.c_int32]),
     "dril_norm_rollout_info": (C.c_int32, [_P, C.POINTER(DrilNormRolloutInfo)]),
+    "dril_update_fused_enable": (C.c_int32, [_P, C.c_int32]),
+    "dril_update_fused_info": (C.c_int32, [_P, C.POINTER(DrilUpdateFusedInfo)]),
     "dril_evaluate_fused_info": (C.c_int32, [_P, _P]),
     "dril_destroy": (C.c_int32, [_P]),
     "dril_last_error": (C.c_char_p, [_P]),
@@ -318,6 +327,7 @@ _SIG = {
     "dril_f32_retries": (C.c_int64, [_P]),
     "dril_f32_fallback_info": (C.c_int32, [_P, C.POINTER(DrilF32Fallback)]),
     "dril_debug_set_permutation": (C.c_int32, [_P, _P, C.c_size_t]),
+    "dril_debug_get_step_stats": (C.c_int32, [_P, _P, C.c_size_t]),
     "dril_ppo_loss_grad": (C.c_int32, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_float), _P, _P]),
     "dril_apply_gradients": (C.c_int32, [_P, _P, C.c_size_t, C.POINTER(C.c_float)]),
     "dril_evaluate_agent": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(DrilEvalStats), _P, _P]),

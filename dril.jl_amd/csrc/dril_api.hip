@@ -315,7 +315,7 @@ int create_impl(const dril_config* cfg, const char* module_path, dril_handle** o
     if (const char* e = std::getenv("DRIL_GRAD_ACTOR_PERMILLE")) { h->grad_actor_pct = std::atoi(e); if (h->grad_actor_pct < 100 || h->grad_actor_pct > 900) h->grad_actor_pct = 0; }
     if (const char* e = std::getenv("DRIL_GRAD_VARIANT")) { h->grad_variant = std::atoi(e); if (h->grad_variant < -1 || h->grad_variant > 2) h->grad_variant = -1; if (h->grad_variant == 2) h->grad_variant = 1; }
     h->no_persistent = std::getenv("DRIL_NO_PERSISTENT_UPDATE") != nullptr; { const char* e = std::getenv("DRIL_NO_EPOCH_INDEX"); h->no_epoch_index = e && std::atoi(e) != 0; }
-    if (const char* e = debug_env("DRIL_SMALL_CHUNK")) { const long c = std::atol(e); if (c > 0) h->small_chunk = c; }   // optimiser steps per launch of ppo_update_small_kernel (tests: launch boundaries)
+    if (const char* e = debug_env("DRIL_SMALL_CHUNK")) { const long c = std::atol(e); if (c > 0) { h->small_chunk = c; h->update_fused_chunk = c; } }   // optimiser steps per launch of ppo_update_small_kernel and of ppo_update_generic_small_kernel (tests: launch boundaries)
     h->no_small_path = debug_env("DRIL_NO_SMALL_PATH") != nullptr;
     h->no_f32_retry = std::getenv("DRIL_NO_F32_RETRY") != nullptr;
     CCHK(hipSetDevice(cfg->device));
@@ -675,6 +675,7 @@ static const char* grad_kernel_base(int variant) {
         case 6: return "ppo_update_small_kernel: f32 (f16x2 split, f32 accumulate; v_mfma_f32_32x32x16_f16 x 3 per k16 step on two-piece f16 operands = 2^-24 relative, input layer on v_mfma_f32_32x32x2_f32; two persistent workgroups (actor | critic), all optimiser steps of the iteration in one launch)";
         case 5: return "ppo_grad_pair_kernel: f32 (f16x2 split, f32 accumulate; v_mfma_f32_32x32x16_f16 x 3 per k16 step on two-piece f16 operands = 2^-24 relative, input layer on v_mfma_f32_32x32x2_f32)";
         case 4: return "ppo_grad_wide_split_kernel: f32 (f16x2 split, f32 accumulate; v_mfma_f32_32x32x16_f16 x 3 per k16 step on two-piece f16 operands = 2^-24 relative, input layer on f32 MFMAs, dW1 / dW3 in f32 on the vector ALU)";
+        case 7: return "ppo_update_generic_small_kernel: f32 (v_fma_f32 on the vector ALU, f32 accumulate; one workgroup, parameters and gradients in LDS, all optimiser steps of the update in one launch)";
         case 3: return "generic path: f32 contractions (sac_gemm_*; large ones bf16x3 split, f32 accumulate)";
         default: return "none yet";
     }
@@ -682,7 +683,7 @@ static const char* grad_kernel_base(int variant) {
 DRIL_EXPORT const char* dril_grad_kernel_info(const dril_handle* h) {
     if (!h) return "?";
     const char* base = grad_kernel_base(h->last_variant);
-    if (h->last_variant < 0 || h->last_variant == 6) return base;              // no step yet; ppo_update_small_kernel has no slab grid
+    if (h->last_variant < 0 || h->last_variant == 6 || h->last_variant == 7) return base;              // no step yet; the persistent update kernels have no slab grid
     std::snprintf(h->grad_info, sizeof(h->grad_info), "%s; grid G=%d Gc=%d", base, h->last_G, h->last_Gc);   // what ppo_step launched: slabs (ppo_grad_pair_kernel: pairs) of the actor, of the critic
     return h->grad_info;
 }

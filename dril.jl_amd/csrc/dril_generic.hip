@@ -11,6 +11,7 @@
 
 #include "dril_gemm.h"
 #include "dril_internal.h"
+#include "dril_ppo_head.h"
 
 namespace dril {
 
@@ -186,37 +187,13 @@ __global__ __launch_bounds__(256) void generic_loss_head_kernel(LossHeadArgs g) 
     for (int64_t i = (int64_t)z * g.Cr + tid; i < (int64_t)(z + 1) * g.Cr; i += blockDim.x) {
         const bool valid = g.valid[i] != 0.f;
         const float* o = g.out + i * A; float* d_o = g.dout + i * A;
-        // value head
-        const float R = g.ret[i], ov = g.vold[i], val = g.v[i];
-        const float dcl = val - ov;
-        const bool vpass = !a.has_clip_vf || (dcl >= -a.clip_range_vf && dcl <= a.clip_range_vf);                  // clip_range, ppo.jl:344-346,378
-        const float value = a.has_clip_vf ? ov + fminf(fmaxf(dcl, -a.clip_range_vf), a.clip_range_vf) : val;
-        const float ve = value - R;
-        g.dv[i] = (valid && vpass) ? a.invB * a.vf_coef * 2.0f * ve : 0.f;
-        // policy head
+        // value and policy head of the sample (dril_ppo_head.h)
+        float ve2, ps[5];
+        g.dv[i] = ppo_value_sample(a, valid, g.ret[i], g.vold[i], g.v[i], ve2);
         const float advn = (g.adv[i] - adv_mean) * adv_inv;
-        float logp, ent, m = 0.f, s = 1.f; int act = 0;
-        if (g.discrete) {
-            softmax_stats(o, A, m, s);
-            act = reinterpret_cast<const int32_t*>(g.act)[i] - a.action_start; act = act < 0 ? 0 : (act >= A ? A - 1 : act);
-            logp = logf(expf(o[act] - m) / s); ent = categorical_entropy_rt(o, A, m, s);
-        } else { logp = gauss_logpdf_rt(g.act + i * A, o, ls, A); ent = gauss_entropy_rt(ls, A); }
-        const float lr = logp - g.lpo[i];
-        const float r = expf(lr);                                                     // :380
-        const float lo = 1.0f - a.clip_range, hi = 1.0f + a.clip_range;
-        const float rc = fminf(fmaxf(r, lo), hi);                                     // :381
-        const float t1 = r * advn, t2 = rc * advn;
-        const float mn = t2 < t1 ? t2 : t1;                                           // :382
-        const float dm_dr = (t2 < t1) ? ((r >= lo && r <= hi) ? advn : 0.f) : advn;
-        const float dlogp = valid ? -a.invB * dm_dr * r : 0.f;
-        const float dent = valid ? -a.invB * a.ent_coef : 0.f;                        // ent_loss = -mean(entropy), :383,:386
-        g.dlp[i] = dlogp;
-        if (g.discrete) {
-            for (int k = 0; k < A; ++k) { const float p = expf(o[k] - m) / s; d_o[k] = dlogp * ((k == act ? 1.0f : 0.0f) - p) + dent * (-p * (logf(p) + ent)); }
-        } else {
-            for (int k = 0; k < A; ++k) { const float iv = expf(-2.0f * ls[k]), d = g.act[i * A + k] - o[k]; d_o[k] = dlogp * d * iv; }
-        }
-        if (valid) { st[0] += -mn; st[1] += ent; st[2] += (r != rc) ? 1.0 : 0.0; st[3] += (double)((r - 1.0f) - lr); st[4] += r; st[5] += (double)(ve * ve); }   // :382,:383,:390,:393,:402,:385
+        const int act_i = g.discrete ? reinterpret_cast<const int32_t*>(g.act)[i] : 0;
+        ppo_policy_sample(a, A, g.discrete, valid, o, 1, act_i, g.act + i * A, 1, advn, g.lpo[i], ls, d_o, 1, g.dlp[i], ps);
+        if (valid) { st[0] += ps[0]; st[1] += ps[1]; st[2] += ps[2]; st[3] += (double)ps[3]; st[4] += ps[4]; st[5] += (double)ve2; }   // :382,:383,:390,:393,:402,:385
     }
     float* slab_a = a.slabs_actor + (size_t)(g.slab0 + z) * a.slab_a; float* slab_c = a.slabs_critic + (size_t)(g.slab0 + z) * a.slab_c;
     for (int k = 0; k < 6; ++k) {
@@ -234,9 +211,7 @@ __global__ __launch_bounds__(256) void generic_loss_head_kernel(LossHeadArgs g) 
             double acc = 0;
             for (int64_t i = (int64_t)z * g.Cr + tid; i < (int64_t)(z + 1) * g.Cr; i += blockDim.x) {
                 if (g.valid[i] == 0.f) continue;
-                const float d = g.act[i * A + k] - g.out[i * A + k];
-                const float dlogp = g.dlp[i], dent = -a.invB * a.ent_coef;
-                acc += (double)(dlogp * (d * d * iv - 1.0f) + dent);
+                acc += (double)ppo_log_std_term(a, g.dlp[i], g.act[i * A + k], g.out[i * A + k], iv);
             }
             sh[tid] = acc; __syncthreads();
             for (int w = 128; w > 0; w >>= 1) { if (tid < w) sh[tid] += sh[tid + w]; __syncthreads(); }

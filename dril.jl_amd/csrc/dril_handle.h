@@ -74,7 +74,7 @@ struct dril_handle {
     dril::DevBuf<double> rms_red;   // data-parallel: this step's partial sums folded to one row and summed over ranks
     int grad_actor_pct = 0;   // ppo_grad_pair_kernel: share (per mille) of the pairs given to the actor; 0 = by head (env DRIL_GRAD_ACTOR_PERMILLE)
     int last_G = 0, last_Gc = 0; mutable char grad_info[640] = {0};   // the grid of that step (slabs of the actor / of the critic; ppo_grad_pair_kernel: pairs) and the text dril_grad_kernel_info returns
-    int last_variant = -1;  // which gradient kernel the last optimiser step ran: 0 ppo_grad_kernel, 2 ppo_grad_wide_kernel, 3 generic path, 4 ppo_grad_wide_split_kernel, 5 ppo_grad_pair_kernel (dril_grad_kernel_info)
+    int last_variant = -1;  // which gradient kernel the last optimiser step ran: 0 ppo_grad_kernel, 2 ppo_grad_wide_kernel, 3 generic path, 4 ppo_grad_wide_split_kernel, 5 ppo_grad_pair_kernel, 6 ppo_update_small_kernel, 7 ppo_update_generic_small_kernel (dril_grad_kernel_info)
     int grad_variant = -1;  // env DRIL_GRAD_VARIANT: 0 = the exact-f32 kernels (ppo_grad_kernel / ppo_grad_wide_kernel), 1 = the bf16-split kernels (ppo_grad_pair_kernel at hidden 64, ppo_grad_wide_split_kernel at 128 / 256) for every minibatch size, -1 = default: wide nets split, hidden 64 by minibatch size
     bool external = false; bool generic = false; dril::DevBuf<float> gen_tmp;   // generic: layer-by-layer kernels (host envs, or a device env whose hidden_dims the fused kernels are not built for)
     dril::GenericDims gd{}; dril::GenericWs gws; int ext_t = 0; bool ext_acted = false;   // DRIL_ENV_EXTERNAL: host envs, generic kernels
@@ -106,6 +106,10 @@ struct dril_handle {
     dril::DevBuf<unsigned> w2max_dev; float w2max = 0.f;   // max |W2| over both nets (fused kernels): host copy refreshed by dril_set_params and with every optimiser run's statistics
     bool no_small_path = false;   // DRIL_NO_SMALL_PATH (with DRIL_DEBUG=1), latched in dril_create
     bool no_persistent = false; dril::DevBuf<unsigned long long> small_xchg; dril::DevBuf<uint64_t> epoch_keys; int64_t small_chunk = 16384;   // ppo_update_small_kernel (batch_size <= 64): DRIL_NO_PERSISTENT_UPDATE; per-epoch DataLoader keys on the device
+    // dril_update_fused_enable: the opt-in of a generic handle, the path (1 = ppo_update_generic_small_kernel, 0 = per step) and the kernel launches of the last update,
+    // the optimiser steps per launch (kGuChunk; DRIL_SMALL_CHUNK with DRIL_DEBUG=1)
+    bool update_fused = false; int update_fused_path = 0; int64_t update_fused_launches = 0, update_fused_chunk = dril::kGuChunk;
+    int64_t last_update_steps = 0;   // epochs x minibatches of the last update: the rows of step_stats that are its own (dril_debug_get_step_stats)
     std::vector<dril::ppo::ProfEvent> prof_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
     double prof_ms[DRIL_K_COUNT] = {0}; int64_t prof_n[DRIL_K_COUNT] = {0}, prof_all[DRIL_K_COUNT] = {0}; bool prof_open = false;
     // dril_evaluate_agent_device: where the env side is set aside for the call, the per-env running sums, the event list and its counter (pinned host word for the poll)
@@ -200,6 +204,11 @@ int update_begin(dril_handle* h, const UpdatePlan& p);
 int small_update_args(dril_handle* h, const UpdatePlan& p, uint64_t* keys, SmallUpdateArgs& u);
 void small_update_chunk(const UpdatePlan& p, int64_t chunk, int64_t s0, SmallUpdateArgs& u);
 void small_update_done(dril_handle* h, const UpdatePlan& p);
+// the one-launch update of a generic handle (dril_update_fused_enable): "" when the handle may take it, else why not and what to do; whether this update takes it;
+// what its launches leave on the host side of the handle
+std::string update_fused_unavailable(const dril_handle* h);
+bool update_fused_applies(const dril_handle* h, const UpdatePlan& p);
+void update_fused_done(dril_handle* h, const UpdatePlan& p, int64_t launches);
 int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home);
 int update_finish(dril_handle* h, const UpdatePlan& p, const UpdateHome& home, dril_ppo_stats* out);
 bool update_direct_f32(const dril_handle* h);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdlib>
+#include <string>
 
 #include "dril_device.h"
 #include "dril_devmem.h"         // DevBuf: GenericWs owns its workspace
@@ -228,6 +229,27 @@ hipError_t generic_ppo_grad(const GenericDims& d, const GradArgs& a, GenericWs& 
 int generic_slab_size(const GenericDims& d, bool actor);
 int generic_pick_slabs(const GenericDims& d, int64_t count, int Gmax);   // slabs (row chunks) for a minibatch of `count` rows; < 1: does not fit
 hipError_t generic_select(int64_t n, const uint8_t* where, const float* src, float* dst, hipStream_t s);   // dst[i] = src[i] where where[i] != 0
+
+// ppo_update_generic_small_kernel (dril_update_generic_small.hip): a run of optimiser steps of a generic handle's update in one launch of ONE workgroup, every net shape a
+// run-time argument.  The caps below are the kernel's LDS plan (parameters and gradients, padded, plus the activation panels of a 32- or 16-sample tile in one CU's
+// 160 KB) and what dril_update_fused_info reports.
+constexpr int kGuMaxWidth = 64, kGuMaxObs = 16, kGuMaxAct = 8, kGuMaxParams = 11264, kGuMinBatch = 2, kGuMaxBatch = 64;
+constexpr int kGuFasterBatch = 32;   // the largest batch_size at which the route measured faster than the per-step route on every admitted shape (profiles/generic_update_scaling.json)
+constexpr int64_t kGuChunk = 1536;   // optimiser steps per launch: a bound on one kernel's run time (measured 34 - 133 us per step over the shapes of profiles/generic_update_scaling.json: 0.05 - 0.2 s); the README shape's 1 280 steps are one launch
+// where a net's pieces sit in LDS (float offsets): layer l of net n (0 actor, 1 critic) is (in[l] + 1) rows of op[n][l] = roundup(out[n][l], 4) floats at lw[n][l] and
+// out[n][l] * (in[l] + 1) floats at fw[n][l] of the flat parameter vector; log_std at ls; PP floats in all.  The panels (x, hb, zb, dz, outb, dout, actb, sc) are
+// offsets behind the parameter and gradient blocks, `total` floats in all
+struct GuLayout { int nl, in[kMaxHidden + 1], out[2][kMaxHidden + 1], op[2][kMaxHidden + 1], lw[2][kMaxHidden + 1], fw[2][kMaxHidden + 1], ls, PP;
+                  int x, hb[kMaxHidden], zb[kMaxHidden], dz[2], outb, dout, actb, sc, total; };
+// u: as small_update_args fills it (rec unused); the rollout buffer's arrays; lay, D .. need_z are the launcher's
+struct GenericUpdateArgs {
+    SmallUpdateArgs u; GuLayout lay;
+    const float* obs; const void* actions; const float* adv; const float* ret; const float* logp;
+    int D, A, discrete, act_code, need_z;
+};
+std::string generic_update_unfit(const GenericDims& d, int P);   // "" when the net is inside the kernel's caps, else which cap it misses and what to do
+int generic_update_tile(const GenericDims& d);                   // samples per tile the launcher picks (32 or 16; 0: does not fit)
+hipError_t launch_ppo_update_generic_small(const GenericDims& d, GenericUpdateArgs a, hipStream_t s);
 
 // device-array verbs of DRIL_ENV_EXTERNAL (dril_ext_device.hip).  ExtBounds: the ClampAdapter's table, one (low, high) per action dimension; low >= high = not clamped
 struct ExtBounds { float lo[64], hi[64]; };

@@ -142,6 +142,13 @@ DRIL_EXPORT int32_t dril_debug_set_permutation(dril_handle* h, const int64_t* pe
     return sync(h);
 }
 
+DRIL_EXPORT int32_t dril_debug_get_step_stats(dril_handle* h, float* out, size_t rows) {
+    NEED(h);
+    if (!out || (int64_t)rows > h->last_update_steps || rows * 16 > h->step_stats.size()) return fail(h, DRIL_ERR_INVALID_ARG, "dril_debug_get_step_stats: null pointer, or more rows than the last update had optimiser steps");
+    HIPCHK(h, hipMemcpyAsync(out, h->step_stats, rows * 16 * 4, hipMemcpyDeviceToHost, h->stream));
+    return sync(h);
+}
+
 namespace dril::ppo {
 // One update in the pieces that ppo_update_once runs in order, and that a population (dril_population_ppo_update) runs member by member around ONE batched launch:
 //   update_begin (sizes, memsets, packed records) -> [small_update_args + the persistent kernel | the per-step kernels] -> update_enqueue_home (explained variance,
@@ -163,7 +170,7 @@ bool small_persistent_applies(const dril_handle* h, const UpdatePlan& p) {
 }
 int update_begin(dril_handle* h, const UpdatePlan& p) {
     const int64_t total_steps = p.total_steps;
-    h->used_f16 = false; h->spin_timeout = false;
+    h->used_f16 = false; h->spin_timeout = false; h->last_update_steps = total_steps;
     if (total_steps > 0) HIPCHK(h, h->step_stats.grow((size_t)total_steps * 16));
     if (total_steps > 0) HIPCHK(h, hipMemsetAsync(h->step_stats, 0, (size_t)total_steps * 16 * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(h->stop_flag, 0, 4, h->stream)); HIPCHK(h, hipMemsetAsync(h->nan_flag, 0, 4, h->stream));
@@ -193,6 +200,25 @@ void small_update_chunk(const UpdatePlan& p, int64_t chunk, int64_t s0, SmallUpd
 }
 // what the persistent kernel's launches leave on the host side of the handle
 void small_update_done(dril_handle* h, const UpdatePlan& p) { h->adam_steps += p.total_steps; h->wimg_dirty = true; h->last_variant = 6; h->used_f16 = true; }
+// the one-launch update of a generic handle (dril_update_fused_enable, dril_update_generic_small.hip).  Eligibility is the handle's own and does not change between
+// updates: generic, single rank, 2 <= batch_size <= 64, no pinned route, a net inside the kernel's caps
+std::string update_fused_unavailable(const dril_handle* h) {
+    if (!h->generic) return "the handle runs the fused kernels of a built-in env kind (two equal tanh layers of 32 / 64 / 128 / 256): at batch_size <= 64 on hidden_dims [64,64] its update already is one launch of ppo_update_small_kernel, and larger minibatches fill the chip per step; nothing to enable";
+    if (h->cfg.world_size > 1 || comm_ready(h) || h->force_allreduce) return "the handle is part of a data-parallel job (world_size > 1, a ready communicator or DRIL_FORCE_ALLREDUCE): its optimiser step all-reduces between the gradient and Adam, which one launch cannot hold; keep the per-step route, which is the default";
+    const int64_t B = h->cfg.batch_size;
+    if (B < kGuMinBatch || B > kGuMaxBatch) return "batch_size = " + std::to_string(B) + ": the kernel holds a minibatch of " + std::to_string(kGuMinBatch) + " to " + std::to_string(kGuMaxBatch) + " samples in one workgroup; larger minibatches are not launch-bound: keep the per-step route, which is the default";
+    if (h->no_persistent) return "DRIL_NO_PERSISTENT_UPDATE is set: every update of this handle runs the per-step kernels; unset it and create the handle again";
+    if (h->grad_variant >= 0) return "DRIL_GRAD_VARIANT is set: it pins the per-step kernels; unset it and create the handle again";
+    const std::string why = generic_update_unfit(h->gd, h->P);
+    if (!why.empty()) return why;
+    return "";
+}
+bool update_fused_applies(const dril_handle* h, const UpdatePlan& p) { return h->update_fused && p.total_steps > 0 && update_fused_unavailable(h).empty(); }
+// the arithmetic is f32: no range redo follows
+void update_fused_done(dril_handle* h, const UpdatePlan& p, int64_t launches) {
+    h->adam_steps += p.total_steps; h->wimg_dirty = true; h->last_variant = 7; h->used_f16 = false;
+    h->update_fused_path = 1; h->update_fused_launches = launches;
+}
 int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home) {
     h->update_counter += 1;
     prof_begin(h, DRIL_K_EXPLAINED_VAR);
@@ -319,7 +345,25 @@ int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
 #endif
         step = total_steps;
     }
-    for (int ep = 0; ep < h->cfg.epochs && !persistent; ++ep) {
+    const bool fused = !persistent && update_fused_applies(h, plan);
+    h->update_fused_path = 0; h->update_fused_launches = 0;
+    if (fused) {
+        std::vector<uint64_t> keys((size_t)h->cfg.epochs);
+        GenericUpdateArgs g{};
+        { int rca = small_update_args(h, plan, keys.data(), g.u); if (rca) return rca; }
+        HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (keys is a stack-lifetime host buffer)
+        g.obs = h->obs; g.actions = h->act; g.adv = h->adv; g.ret = h->ret; g.logp = h->logp;
+        int64_t launches = 0;
+        for (int64_t s0 = 0; s0 < total_steps; s0 += h->update_fused_chunk, ++launches) {
+            small_update_chunk(plan, h->update_fused_chunk, s0, g.u);
+            prof_begin(h, DRIL_K_PPO_GRAD);
+            HIPCHK(h, launch_ppo_update_generic_small(h->gd, g, h->stream));
+            prof_end(h);
+        }
+        update_fused_done(h, plan, launches);
+        step = total_steps;
+    }
+    for (int ep = 0; ep < h->cfg.epochs && !persistent && !fused; ++ep) {
         const uint64_t key = perm_key(h->cfg.seed + (uint64_t)h->cfg.rank, h->update_counter, ep);
         const int64_t* perm = h->perm_count ? h->perm_dev + (size_t)ep * N : nullptr;
         const bool epoch_moments = h->cfg.normalize_advantage && !perm && nb >= 2 && nb <= 2048;
@@ -426,6 +470,24 @@ int ppo_update(dril_handle* h, dril_ppo_stats* out) {
 }
 }  // namespace dril::ppo
 DRIL_EXPORT int32_t dril_ppo_update(dril_handle* h, dril_ppo_stats* out) { NEED(h); return ppo_update(h, out); }
+DRIL_EXPORT int32_t dril_update_fused_enable(dril_handle* h, int32_t on) {
+    NEED(h);
+    if (on) { const std::string why = update_fused_unavailable(h); if (!why.empty()) return fail(h, DRIL_ERR_UNSUPPORTED, "dril_update_fused_enable: " + why); }
+    h->update_fused = on != 0;
+    return DRIL_OK;
+}
+DRIL_EXPORT int32_t dril_update_fused_info(const dril_handle* h, dril_update_fused_report* out) {
+    if (!h) return fail(nullptr, DRIL_ERR_NOT_INITIALISED, "null handle");
+    if (!out) return fail(const_cast<dril_handle*>(h), DRIL_ERR_INVALID_ARG, "dril_update_fused_info: null out pointer");
+    std::memset(out, 0, sizeof(*out));
+    const std::string why = update_fused_unavailable(h);
+    out->available = why.empty() ? 1 : 0; out->enabled = h->update_fused ? 1 : 0;
+    out->max_width = kGuMaxWidth; out->max_obs_dim = kGuMaxObs; out->max_action_dim = kGuMaxAct; out->max_params = kGuMaxParams; out->max_hidden_layers = kMaxHidden;
+    out->min_batch = kGuMinBatch; out->max_batch = kGuMaxBatch; out->faster_up_to_batch = kGuFasterBatch;
+    out->last_update_path = h->update_fused_path; out->last_update_launches = h->update_fused_launches; out->steps_per_launch = h->update_fused_chunk;
+    std::snprintf(out->reason, sizeof(out->reason), "%s", why.c_str());
+    return DRIL_OK;
+}
 // how often the f16-piece arithmetic had to be left (include/dril_hip.h): nothing here is an error — every number delivered came from kernels that could hold it
 DRIL_EXPORT int64_t dril_f32_retries(const dril_handle* h) { return h ? h->f32_retries : -1; }
 DRIL_EXPORT int32_t dril_f32_fallback_info(const dril_handle* h, dril_f32_fallback* out) {

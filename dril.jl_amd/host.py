@@ -598,6 +598,23 @@ class Handle:
         return dict(available=bool(info.available), enabled=bool(info.enabled), max_envs=info.max_envs, last_collection_launches=info.last_collection_launches,
                     last_collection_path=info.last_collection_path, total_stepwise_fallbacks=info.total_stepwise_fallbacks, reason=info.reason.decode())
 
+    def update_fused_enable(self, on: bool = True):
+        """dril_update_fused_enable: every optimiser step of dril_ppo_update on a generic handle (a plug-in, external envs, a built-in with other hidden_dims or
+        activation) at batch_size <= 64 inside ONE launch of ppo_update_generic_small_kernel instead of 3 nh + 6 launches per step (docs/generic_update.md); legal at
+        any time between updates.  A handle that cannot take it raises the library's message and stays as it was"""
+        self._chk(self.lib.dril_update_fused_enable(self._h, int(bool(on))))
+
+    def update_fused_info(self) -> dict:
+        """dril_update_fused_info: available / enabled / the kernel's caps / last_update_path (1 = the kernel, 0 = per step) / last_update_launches /
+        steps_per_launch / reason; faster_up_to_batch = the largest batch_size at which the route measured faster than the per-step
+        route (it is accepted up to max_batch)"""
+        info = capi.DrilUpdateFusedInfo()
+        self._chk(self.lib.dril_update_fused_info(self._h, C.byref(info)))
+        return dict(available=bool(info.available), enabled=bool(info.enabled), max_width=info.max_width, max_obs_dim=info.max_obs_dim,
+                    max_action_dim=info.max_action_dim, max_params=info.max_params, max_hidden_layers=info.max_hidden_layers, min_batch=info.min_batch,
+                    max_batch=info.max_batch, faster_up_to_batch=info.faster_up_to_batch, last_update_path=info.last_update_path, last_update_launches=info.last_update_launches,
+                    steps_per_launch=info.steps_per_launch, reason=info.reason.decode())
+
     def evaluate_fused_info(self) -> dict:
         """dril_evaluate_fused_info: available / tile / threads / max_width / reason — whether persistent=True of the evaluation and trajectory verbs would run the
         plug-in's own evaluation kernel (path 2; a code object built with DRIL_ENV_PLUGIN_EVALUATE, include/device/dril_env_evaluate.h) on this handle"""
@@ -861,6 +878,13 @@ class Handle:
         fb = capi.DrilF32Fallback()
         self._chk(self.lib.dril_f32_fallback_info(self._h, C.byref(fb)))
         return {k: getattr(fb, k) for k, _ in fb._fields_ if k != "reserved"}
+
+    def step_stats(self, rows: int) -> np.ndarray:
+        """dril_debug_get_step_stats: the (rows, 16) per-optimiser-step rows of the last ppo_update as the device wrote them"""
+        out = np.zeros((int(rows), 16), np.float32)
+        if rows:
+            self._chk(self.lib.dril_debug_get_step_stats(self._h, self._p(out), int(rows)))
+        return out
 
     def set_permutation(self, perm: Optional[np.ndarray]):
         if perm is None:
@@ -1760,18 +1784,21 @@ _STAT_KEYS = ("entropy_losses", "policy_losses", "value_losses", "approx_kl_divs
               "explained_variances", "fps", "grad_norms", "learning_rates")
 
 
-def train_(agent: Agent, env: DeviceParallelEnv, alg: PPO, max_steps: int, callbacks=None):
+def train_(agent: Agent, env: DeviceParallelEnv, alg: PPO, max_steps: int, callbacks=None, fused_update: bool = False):
     """train!(agent, env, alg, max_steps) -> (learn_stats, timer).  learn_stats has the reference's keys
     (ppo.jl:301-312); `timer` holds the TimerOutputs section names (ppo.jl:109,154,167,205-207,239) with
     wall seconds.  `callbacks`: objects with any of on_training_start / on_rollout_start / on_step / on_rollout_end / on_training_end(locals) -> bool;
     a false return stops the training and train_ returns None (ppo.jl:145-152).  An `on_step` hook routes the rollout through the step-granular
-    env verbs instead of the fused kernel."""
+    env verbs instead of the fused kernel.  `fused_update=True` switches the bound handle to the one-launch update of the generic path
+    (dril_update_fused_enable, docs/generic_update.md); where the handle cannot take it the library's message is raised."""
     cbs = list(callbacks or [])
     hook = lambda name, loc: all(getattr(c, name)(loc) for c in cbs if hasattr(c, name))   # a callback returning false stops the training (ppo.jl:145-152)
     step_hooks = [c for c in cbs if hasattr(c, "on_step")]
     timer = {}
     t0 = time.perf_counter()
     h = env.bind(alg, agent.layer)
+    if fused_update:
+        h.update_fused_enable(True)
     h.set_params(flatten_params(agent.train_state.parameters))
     h.set_optimizer_state(agent.train_state.optimizer_state)                                   # the TrainState owns the Adam moments (ppo.jl:52-53), not the env's handle
     per_iter = alg.n_steps * env.n_envs * h.cfg.world_size

@@ -257,6 +257,15 @@ function norm_rollout_info(env::DeviceParallelEnv)
     return (available = i32[1] != 0, enabled = i32[2] != 0, max_envs = Int(i32[3]), last_collection_path = Int(i32[4]), last_collection_launches = Int(i64[1]),
         total_stepwise_fallbacks = Int(i64[2]), reason = String(buf[33:(32 + something(findfirst(==(0x00), buf[33:end]), 257) - 1)]))
 end
+"dril_update_fused_info of the env's handle: (available, enabled, max_width, max_obs_dim, max_action_dim, max_params, max_hidden_layers, min_batch, max_batch, faster_up_to_batch, last_update_path, last_update_launches, steps_per_launch, reason) — path 1 = ppo_update_generic_small_kernel, 0 = per step"
+function update_fused_info(env::DeviceParallelEnv)
+    buf = zeros(UInt8, 320)                                      # dril_update_fused_report: 12 x Int32, 2 x Int64, char[256]
+    check(ccall((:dril_update_fused_info, LIB[]), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), handle(env), buf), handle(env))
+    i32 = reinterpret(Int32, buf[1:48]); i64 = reinterpret(Int64, buf[49:64])
+    return (available = i32[1] != 0, enabled = i32[2] != 0, max_width = Int(i32[3]), max_obs_dim = Int(i32[4]), max_action_dim = Int(i32[5]), max_params = Int(i32[6]),
+        max_hidden_layers = Int(i32[7]), min_batch = Int(i32[8]), max_batch = Int(i32[9]), faster_up_to_batch = Int(i32[10]), last_update_path = Int(i32[12]), last_update_launches = Int(i64[1]),
+        steps_per_launch = Int(i64[2]), reason = String(buf[65:(64 + something(findfirst(==(0x00), buf[65:end]), 257) - 1)]))
+end
 "dril_evaluate_fused_info of the env's handle: (available, tile, threads, max_width, reason) — whether `persistent = true` of evaluate_agent / collect_trajectory would run the plug-in's own evaluation kernel (path 2)"
 function evaluate_fused_info(env::DeviceParallelEnv)
     buf = zeros(UInt8, 272)                                      # dril_fused_evaluate_info: 4 x Int32, char[256]
@@ -511,7 +520,7 @@ function add_device_sections!(to::TimerOutput, secs::Dict{String, Float64}, nste
     return (; compute_gradients = grad, apply_gradients = apply)
 end
 
-function train!(agent::PPOAgent, env::DeviceParallelEnv, alg::PPO{T}, max_steps::Int; ad_type = nothing, callbacks = nothing) where {T}
+function train!(agent::PPOAgent, env::DeviceParallelEnv, alg::PPO{T}, max_steps::Int; ad_type = nothing, callbacks = nothing, fused_update::Bool = false) where {T}   # fused_update: the one-launch update of a generic handle (dril_update_fused_enable, docs/generic_update.md); the library refuses, with what to do, where it cannot
     if has_step_hooks(callbacks)
         # on_step hooks fire once per env step inside the rollout (trajectory.jl:34-39; test/test_callbacks.jl:91-99 expects a stop at exactly 512 steps):
         # run the REFERENCE's own train! over this env's step-granular verbs (observe / act! above) — slow path, semantics preserved (SURVEY.md §8b)
@@ -523,6 +532,7 @@ function train!(agent::PPOAgent, env::DeviceParallelEnv, alg::PPO{T}, max_steps:
     local iterations, total_steps
     @timeit to "setup" begin
         bind_agent!(env, agent, alg); push_params!(env, agent)
+        fused_update && check(ccall((:dril_update_fused_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), handle(env), Int32(1)), handle(env))
         # the handle's Adam moments belong to ONE TrainState (Lux.Training.TrainState carries optimizer_state, ppo.jl:52-53): a different one — another agent, or
         # the TrainState load_policy_params_and_state! rebuilds (ppo.jl:77-94) — starts from a fresh optimiser; repeated train! calls on the same one continue
         # The Adam moments belong to the TrainState (Lux.Training.TrainState carries optimizer_state, ppo.jl:52-53,239): they are pushed into the handle here and

@@ -37,4 +37,24 @@ DRIL_DEVICE_FN float activation_forward(int act, float v) {
     }
 }
 
+// the derivatives the reverse pass multiplies with, by the same codes.  tanh, relu, sigmoid, elu, leakyrelu and softplus are functions of the activation's OUTPUT y;
+// gelu and swish need the pre-activation x (activation_grad_reads_preactivation): `u` is whichever of the two the activation asks for.  The formulas are those of the
+// masked epilogues of dril_gemm.hip.
+DRIL_DEVICE_FN bool activation_grad_reads_preactivation(int act) { return act == 6 || act == 7; }
+DRIL_DEVICE_FN float activation_grad(int act, float u) {
+    switch (act) {
+        case 1: return u > 0.f ? 1.0f : 0.f;
+        case 2: return u * (1.0f - u);
+        case 3: return u > 0.f ? 1.0f : u + 1.0f;                                    // alpha e^x = elu(x) + alpha
+        case 4: return u > 0.f ? 1.0f : 0.01f;
+        case 5: return -expm1f(-u);                                                  // sigmoid(x) = 1 - e^(-softplus(x))
+        case 6: {
+            const float w = 0.7978845608028654f * (u + 0.044715f * u * u * u), t = tanhf(w);
+            return 0.5f * (1.0f + t) + 0.5f * u * (1.0f - t * t) * 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * u * u);
+        }
+        case 7: { const float sg = 1.0f / (1.0f + expf(-u)); return sg * (1.0f + u * (1.0f - sg)); }
+        default: return 1.0f - u * u;
+    }
+}
+
 }  // namespace dril

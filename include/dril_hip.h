@@ -289,6 +289,33 @@ typedef struct dril_norm_rollout_report {
 } dril_norm_rollout_report;
 int32_t dril_norm_rollout_enable(dril_handle* h, int32_t on);
 int32_t dril_norm_rollout_info(const dril_handle* h, dril_norm_rollout_report* out);
+/* The ONE-LAUNCH UPDATE of a generic handle (docs/generic_update.md).  A handle on the layer-by-layer kernels — a device env plug-in, DRIL_ENV_EXTERNAL, a built-in env
+ * with hidden_dims / an activation the fused kernels are not built for, DRIL_FORCE_GENERIC — runs every optimiser step of dril_ppo_update as a chain of 3 nh + 6
+ * dependent launches (nh hidden layers).  on != 0 makes dril_ppo_update and dril_train run the whole
+ * epoch x minibatch loop inside ppo_update_generic_small_kernel, one workgroup, steps_per_launch optimiser steps per launch.  Opt-in, off by default, legal at any time
+ * between updates; enable(h, 0) returns to the per-step route exactly, and an update of either route may follow the other.
+ * Measured (docs/generic_update.md): 1.26 - 1.51 x the per-step route's speed at batch_size <= 32, 0.75 - 0.92 x (slower) at 64, where a minibatch is two sample
+ * tiles; the report says so in faster_up_to_batch.
+ * Arithmetic: f32 throughout, every sum in an order fixed by the launch shape — two runs give the same bits, however the steps are cut into launches.  The route
+ * agrees with the per-step route like the device agrees with the oracle (f32 rounding in another order), not to the bit.
+ * DRIL_ERR_UNSUPPORTED, each with a message that says what to do and the handle left as it was, for: a fused-shape handle (its update already is one launch);
+ * world_size > 1, a ready communicator or DRIL_FORCE_ALLREDUCE; batch_size outside min_batch .. max_batch; DRIL_NO_PERSISTENT_UPDATE or DRIL_GRAD_VARIANT set; a net
+ * beyond the caps below (the kernel keeps parameters, gradients and a sample tile's activations in one CU's LDS). */
+typedef struct dril_update_fused_report {
+    int32_t available;                 /* dril_update_fused_enable(h, 1) would be accepted */
+    int32_t enabled;
+    int32_t max_width, max_obs_dim, max_action_dim, max_params, max_hidden_layers;   /* the kernel's caps: 64, 16, 8, 11 264, 4 */
+    int32_t min_batch, max_batch;      /* 2, 64: what the kernel holds and the verb accepts */
+    int32_t faster_up_to_batch;        /* 32: the largest batch_size at which the route measured faster than the per-step route on every admitted shape
+                                          (docs/generic_update.md, "Measured"); from 33 to max_batch it is accepted and measured SLOWER */
+    int32_t reserved;
+    int32_t last_update_path;          /* of the last dril_ppo_update: 1 = ppo_update_generic_small_kernel, 0 = per step */
+    int64_t last_update_launches;      /* launches of the update kernel in that update (path 1), else 0 */
+    int64_t steps_per_launch;          /* optimiser steps one launch runs at most */
+    char reason[256];                  /* why it is not available ("" when it is) */
+} dril_update_fused_report;
+int32_t dril_update_fused_enable(dril_handle* h, int32_t on);
+int32_t dril_update_fused_info(const dril_handle* h, dril_update_fused_report* out);
 /* The FUSED EVALUATION of a device env plug-in (include/device/dril_env_evaluate.h): a code object built with DRIL_ENV_PLUGIN_EVALUATE(Env) holds a second, optional
  * kernel with the env inlined — K env steps of observe, (frozen) normalisation, actor forward, mode or draw and the transition in ONE launch, a workgroup per tile
  * of envs, no grid barrier — with a descriptor and an ABI number of its own (the rollout's are untouched).  It is path 2 of dril_evaluate_agent_device and
@@ -562,6 +589,9 @@ int32_t dril_f32_fallback_info(const dril_handle* h, dril_f32_fallback* out);
 /* injected DataLoader order: perm[e*N + p] = 0-based buffer index at position p of epoch e
  * (ppo.jl:188-195); NULL = device-generated pseudo-random bijection per epoch */
 int32_t dril_debug_set_permutation(dril_handle* h, const int64_t* perm, size_t count);
+/* DEBUG / TEST: the per-optimiser-step rows of the last dril_ppo_update, as the device wrote them: rows x 16 floats, row s = {policy loss, value loss, entropy loss,
+ * clip fraction, approx KL, entropy, mean ratio, loss, gradient norm, applied, non-finite, KL stop, 4 unused}; rows must not exceed that update's epochs x minibatches. */
+int32_t dril_debug_get_step_stats(dril_handle* h, float* out, size_t rows);
 /* (alg::PPO)(layer, ps, st, batch) ppo.jl:365-407 and its gradient (Lux.Training.compute_gradients,
  * ppo.jl:207) on a caller minibatch; stats7 = policy_loss, value_loss, entropy_loss, clip_fraction,
  * approx_kl_div, entropy, ratio; grads has dril_param_count entries, same layout as the params.
