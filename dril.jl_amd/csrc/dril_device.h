@@ -55,7 +55,7 @@ constexpr int kTS = 36;     // row stride of the transposed activation images (3
 //                                                                                  every collection path (policy_kernel / generic head with device envs, both rollout kernels, SAC)
 //   2           handle seed               update counter      epoch                perm_key (dril_update.hip): key of the epoch's index bijection
 //   3 + 16 i    call seed                 row (64 bit)        call counter         call_noise_*: dril_policy_forward on a host batch (no device envs), action component i
-//   4           SAC update key            update counter      sample               sac_gather_kernel / sac_gather_l1_kernel (dril_sac.hip): replay indices
+//   4           SAC update key            update counter      sample               sac_gather_kernel / sac_gather_l1_kernel (dril_sac_update.hip): replay indices
 //   5 .. 8      SAC update / aux key      counter             4 sample + a / 2     sac_noise (dril_sac_device.h): the update's three noise draws, sac_noise_fill_kernel
 // env_noise_u01 / env_noise_randn: include/device/dril_policy_head.h (shared with the fused rollout of a device env plug-in)
 __device__ __forceinline__ float env_noise_u01_f32(uint64_t env_seed, uint32_t gstep, int i) {            // SAC's random-action phase: a uniform from the block env_noise_randn(i) uses

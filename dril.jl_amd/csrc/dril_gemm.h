@@ -1,4 +1,4 @@
-// dril_gemm.h — the generic strided fp32-MFMA contraction shared by the SAC path (dril_sac.hip) and the generic
+// dril_gemm.h — the generic strided fp32-MFMA contraction shared by the SAC path (dril_sac_net.hip) and the generic
 // (any obs / action / hidden width) on-policy path (dril_generic.hip).  Kernels in dril_gemm.hip.
 #pragma once
 #include <hip/hip_runtime.h>

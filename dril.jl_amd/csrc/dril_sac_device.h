@@ -1,7 +1,7 @@
 // dril_sac_device.h — what the kernels of more than one unit of the SAC host code share (the units: dril_sac_handle.h): __device__ inline functions and the argument
-// structs they take, no __global__ definition.  The SquashedDiagGaussian sample, the handle's Philox streams, the phase stamp, and the four pieces of a collected env step
-// — head, push, the built-in Box envs' own thread, the evaluation's episode accounting — that the collection (dril_sac.hip), the device-array verbs
-// (dril_sac_ext.hip) and the evaluation (dril_sac_eval.hip) assemble into their kernels.
+// structs they take, no __global__ definition.  The SquashedDiagGaussian sample, the handle's Philox streams, the phase stamp, the grid constants of the gradient
+// step that creation sizes buffers by, and the four pieces of a collected env step — head, push, the built-in Box envs' own thread, the evaluation's episode
+// accounting — that the collection (dril_sac_collect.hip), the device-array verbs (dril_sac_ext.hip) and the evaluation (dril_sac_eval.hip) assemble into their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +46,14 @@ __device__ inline float sac_noise(SacRng r, int stream, int i, int a) {
 __device__ __forceinline__ void phase_stamp(unsigned long long* stamp) {
     if (stamp && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *stamp = wall_clock64();
 }
+
+// ---- grid shapes of the gradient step's kernels (dril_sac_update.hip) that dril_sac_create sizes the handle's buffers by --------------------------------
+#ifndef DRIL_SAC_ADAM_BLOCKS
+#define DRIL_SAC_ADAM_BLOCKS 1024
+#endif
+constexpr int kSacAdamBlocks = DRIL_SAC_ADAM_BLOCKS;   // grid cap of the two elementwise optimiser kernels (-DDRIL_SAC_ADAM_BLOCKS=<n>: a tuning switch; 256 -> 1 024 was measured)
+constexpr int kHeadSamplesPerBlock = 1;   // fused head kernels: one workgroup per sample — the dot products of a sample run on separate waves, so a head is ~3 dependent memory round trips
+constexpr int kOptL1MaxIn = 4, kOptL1Units = 16, kOptL1Groups = 16, kOptL1MaxB = 1024;      // first_layer_opt_block: a block owns kOptL1Units hidden units (2 B in floats of dynamic LDS: 32 KB at the cap)
 
 // ---- collection (off_policy_collection.jl:28-96) ---------------------------------------------------------------------------
 struct CollectHeadArgs {

@@ -1,5 +1,5 @@
 // dril_sac_eval.h — the host arithmetic of a device-resident evaluate_agent (evaluation.jl:90-124): the event record the evaluation kernels append, and the reduction
-// of a copied event list to what evaluate_agent returns.  No HIP dependency: dril_sac.hip includes it, and tests/test_sac_monitor_eval.py builds the same lines with
+// of a copied event list to what evaluate_agent returns.  No HIP dependency: dril_sac_handle.h includes it, and tests/test_sac_monitor_eval.py builds the same lines with
 // g++.  Written against the record alone, so another handle's evaluation appends the same events and reuses it: the PPO verb dril_evaluate_agent_device does (dril_eval_account.h, dril_eval.hip).
 //
 // The list.  Every env keeps its running return / length on the device; where an episode ends the env's thread appends {step, env, return, length} through ONE

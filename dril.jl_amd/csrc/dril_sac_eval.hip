@@ -1,7 +1,7 @@
 // dril_sac_eval.hip — evaluate_agent (src/evaluation.jl:54-143) and collect_trajectory (src/utils/trajectory_utils.jl:3-49) with the handle's actor on the handle's
 // envs, on the device, training state left untouched: dril_sac_evaluate_agent, dril_sac_trajectory_capacity, dril_sac_collect_trajectory and their kernels.  The hidden
-// layers of a step are the collection's (actor_hidden), a plug-in's action head is the collection's launch (launch_collect_head), both in
-// dril_sac.hip.  The units: dril_sac_handle.h.
+// layers of a step are the collection's (actor_hidden, dril_sac_net.hip), a plug-in's action head is the collection's launch (launch_collect_head,
+// dril_sac_collect.hip).  The units: dril_sac_handle.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,9 +103,9 @@ template <class Enqueue> int eval_poll_loop(dril_sac_handle* h, int want, long l
 int eval_step_actor(dril_sac_handle* h, int deterministic, CollectHeadArgs& ca) { SDO(actor_hidden(h, 0, nullptr, &ca)); ca.deterministic = deterministic ? 1 : 0; return DRIL_OK; }
 // NormalizeWrapperEnv with training = false (set_training(eval_env, false) after sync_normalization_stats!, :299-309): the statistics in force, frozen
 NzEvalArgs eval_step_nz(const dril_sac_handle* h) { return NzEvalArgs{h->nz.on ? h->nz.half(h->nz.cur) : nullptr, h->nz.on ? h->nz.cfg.norm_obs : 0, h->nz.cfg.epsilon, h->nz.cfg.clip_obs}; }
-// a plug-in: the action head into e_envact is launch_collect_head (dril_sac.hip); act!(env, action) of the live envs (monitor pointers null: these episodes do not feed the window)
+// a plug-in: the action head into e_envact is launch_collect_head (dril_sac_collect.hip); act!(env, action) of the live envs (monitor pointers null: these episodes do not feed the window)
 int eval_step_env(dril_sac_handle* h) { SHIP(h, h->env.step(h->e_envact, EnvStepOut{h->e_rew, h->e_term, h->e_trunc, h->e_tobs, h->obs_nxt}, MonitorArgs{}, h->stream)); return DRIL_OK; }
-// a built-in Box kind (A = 1): head, act! and observe are ONE launch (launch_eval_env / launch_traj_env, dril_sac.hip) over the collection's block without push and monitor
+// a built-in Box kind (A = 1): head, act! and observe are ONE launch (launch_eval_env / launch_traj_env, dril_sac_collect.hip) over the collection's block without push and monitor
 CollectEnvArgs eval_env_args(dril_sac_handle* h, const CollectHeadArgs& ca) { return env_kernel_args(h, ca, PushArgs{}, MonitorArgs{nullptr, nullptr, nullptr, nullptr, nullptr}); }
 int eval_step_end(dril_sac_handle* h) { SHIP(h, hipGetLastError()); std::swap(h->obs_cur, h->obs_nxt); return DRIL_OK; }
 // ---- the evaluation itself ----

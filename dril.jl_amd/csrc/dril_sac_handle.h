@@ -1,9 +1,11 @@
 // dril_sac_handle.h — the SAC handle (include/dril_sac.h: dril_sac_handle) and what the units of its host code share: the struct itself, the types of its members, the
 // error and entry macros, and the prototypes of the functions that cross a unit boundary, under the name
 // of the unit that defines them.  The units:
-//   dril_sac.hip          create / destroy, the parameter, env and prediction verbs, the replay ring, dril_sac_train / dril_sac_iterate, profiling; and, not cut out
-//                         yet: the contractions of one net (net_forward, net_backward, actor_hidden), one gradient step (sac_one_update) with its kernels, and the
-//                         collection with MonitorWrapperEnv / NormalizeWrapperEnv
+//   dril_sac.hip          create / destroy, the parameter, env and prediction verbs, the replay ring, dril_sac_train / dril_sac_iterate, profiling
+//   dril_sac_net.hip      the contractions of one net (net_forward, net_backward, actor_hidden) and the two kernels of the collection forward
+//   dril_sac_update.hip   one gradient step (sac_one_update) with its kernels, the statistics rows, dril_sac_update and its debug verbs
+//   dril_sac_collect.hip  the collection: the head, push and env-step kernels, one collected step, dril_sac_collect_rollout / _continue
+//   dril_sac_wrap.hip     MonitorWrapperEnv / NormalizeWrapperEnv around the handle's device envs: dril_sac_monitor_*, dril_sac_normalize_*
 //   dril_sac_ext.hip      the DRIL_ENV_EXTERNAL verbs on host and device arrays, and the two wrappers around such a handle's envs
 //   dril_sac_eval.hip     evaluate_agent and collect_trajectory on the device
 // A kernel is defined in the unit that launches it; what kernels of several units share is dril_sac_device.h.
@@ -125,6 +127,8 @@ inline NetBufs q_bufs(dril_sac_handle* h, float* h1, float* h2, float* out) { re
 
 // ---- dril_sac.hip ----
 int ssync(dril_sac_handle* h);   // drains the handle's stream; inside a sync-free device verb the wait is counted
+
+// ---- dril_sac_net.hip ----
 int gemm(dril_sac_handle* h, GemmArgs g, int Z);
 int net_forward(dril_sac_handle* h, const float* P, NetOff off, long long zP, int in, int O, const float* X, int ldx, long long zX, int n,
                 NetBufs b, int Z, int zdivX = 1, bool hidden_only = false, bool first_done = false);
@@ -132,10 +136,18 @@ int net_backward(dril_sac_handle* h, const float* P, NetOff off, long long zP, i
                  NetBufs b, const float* dOut, float* G, float* dX, int Z, bool have_dz2 = false, bool skip_w1 = false);
 // predict_actions_raw up to the output layer for the envs' current observations; *out: the argument block of the head that follows
 int actor_hidden(dril_sac_handle* h, int use_random, const float* inj_noise, CollectHeadArgs* out);
+
+// ---- dril_sac_update.hip ----
 // one update!(agent, alg, batch), enqueued.  `slot`: index into the injected batches (-1: Philox); `out`: device statistics row; ssq_row_in: a row of the pending table
 int sac_one_update(dril_sac_handle* h, int slot, float* out, unsigned long long* stamp = nullptr, double* ssq_row_in = nullptr);
+// room for the statistics rows of n gradient steps in the table of dril_sac_update
+int ensure_stats(dril_sac_handle* h, int n);
 // the statistics rows of the last n gradient steps, stream drained (rows_dev / ssq_dev: the pending table of dril_sac_update_enqueue; null: the table of dril_sac_update)
 int fetch_stats(dril_sac_handle* h, int n, dril_sac_stats* out, const float* rows_dev = nullptr, const double* ssq_dev = nullptr);
+// n gradient steps enqueued back to back, one drain, their statistics (out: null = none); injected: step k takes batch k of dril_sac_debug_set_batches
+int run_updates(dril_sac_handle* h, int n_updates, bool injected, dril_sac_stats* out);
+
+// ---- dril_sac_collect.hip ----
 int ensure_obs(dril_sac_handle* h);
 void ring_advance(dril_sac_handle* h);
 CollectEnvArgs env_kernel_args(dril_sac_handle* h, const CollectHeadArgs& ca, const PushArgs& pa, const MonitorArgs& mon);
@@ -147,17 +159,30 @@ struct EvalEnvArgs { CollectEnvArgs env; EvalAcctArgs acct; NzEvalArgs nz; };
 struct TrajEnvArgs { CollectEnvArgs env; NzEvalArgs nz; TrajRec rec; TrajMaps maps; int32_t t; };
 hipError_t launch_eval_env(dril_sac_handle* h, const EvalEnvArgs& a);
 hipError_t launch_traj_env(dril_sac_handle* h, const TrajEnvArgs& a);
-// MonitorWrapperEnv: its arrays, the row of the step being enqueued, the window launch after a collection's last step, log_stats over the window
+// one step of collect_trajectories for all envs, enqueued (the caller has called collect_prepare); `first` / `last`: the step's place in its collection
+int collect_step(dril_sac_handle* h, int use_random, const float* inj_noise, unsigned long long* stamp = nullptr, bool first = true, bool last = true);
+// before the steps of a collection: the observation of the envs' present state (the raw one under NormalizeWrapperEnv) and MonitorWrapperEnv's block of n_steps rows
+int collect_prepare(dril_sac_handle* h, int n_steps);
+// a whole collection of n_steps, drained; cont: it continues the collection the previous call began (dril_sac_collect_continue)
+int collect(dril_sac_handle* h, int n_steps, int use_random, double* fps, bool cont = false);
+
+// ---- dril_sac_wrap.hip ----
+// MonitorWrapperEnv: its arrays, the block of a collection's rows, the row of the step being enqueued, the window launch after a collection's last step, log_stats over the window
 void monitor_free(dril_sac_handle* h);
 hipError_t monitor_alloc(dril_sac_handle* h, int32_t window, size_t rows);
+int monitor_begin(dril_sac_handle* h, int n_steps);
 MonitorArgs monitor_row(dril_sac_handle* h);
 int monitor_end(dril_sac_handle* h);
 int monitor_read(dril_sac_handle* h, float* ep_rew_mean, float* ep_len_mean, int32_t* n_episodes);
-// NormalizeWrapperEnv: its arrays, the moments and apply launches
+// NormalizeWrapperEnv: its arrays, the raw observation of the envs' present state, the moments and apply launches, observe(env) into `out` and at the head of a collection
 void normalize_free(dril_sac_handle* h);
 hipError_t normalize_alloc(dril_sac_handle* h, size_t rows);
+int nz_ensure_raw(dril_sac_handle* h);
 int nz_moments_over(dril_sac_handle* h, const float* raw, const float* rew, int* rows);
+int nz_moments(dril_sac_handle* h, bool obs, bool ret, int* rows);
 int nz_apply(dril_sac_handle* h, NzApplyArgs p, int rows, bool upd_obs, bool upd_ret);
+int nz_observe(dril_sac_handle* h, bool update, float* out);
+int nz_collect_begin(dril_sac_handle* h);
 // the bodies of the verbs that read or write a wrapper that is on: one definition for dril_sac_normalize_* (device envs) and dril_sac_ext_normalize_* (external handles)
 int nzv_get_config(dril_sac_handle* h, const std::string& verb, dril_sac_normalize_config* cfg);
 int nzv_get_stats(dril_sac_handle* h, const std::string& verb, float* obs_mean, float* obs_var, int64_t* obs_count, float* ret_mean, float* ret_var, int64_t* ret_count);

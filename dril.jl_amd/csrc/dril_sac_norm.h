@@ -1,7 +1,7 @@
 // dril_sac_norm.h — what is the SAC handle's own of NormalizeWrapperEnv (src/environment_wrappers/normalizeWrapperEnv.jl) around its device envs, for any
 // observation width the handle accepts (1 .. 1024): the table shape and the argument blocks of its kernels.  Everything it shares with the PPO handle's wrapper on
 // device env plug-ins (dril_ppo_norm.h) — scalars, the moments kernel, the head of the apply kernel, the host state — is dril_norm_wrap.h.  The kernels stand with
-// their launches: sac_norm_env_kernel and sac_norm_apply_kernel in dril_sac.hip, sac_eval_account_norm_kernel in dril_sac_eval.hip; the wrapper of an external
+// their launches: sac_norm_env_kernel in dril_sac_collect.hip, sac_norm_apply_kernel in dril_sac_wrap.hip, sac_eval_account_norm_kernel in dril_sac_eval.hip; the wrapper of an external
 // handle (dril_sac_ext_norm.h) shares the table shape and the LDS layout.
 //
 // A collected step is two launches of the wrapper where the plain collection is one:

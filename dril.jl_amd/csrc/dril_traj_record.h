@@ -2,7 +2,7 @@
 // do with the action, the reward, the done flags and the observation of its step — the active test, what is written where, finalisation, and the precedence of the
 // episode's end over the max_steps cut — and the copy-out of a finished recording.  No HIP dependency (traj_copy_out apart: HIP compiles only), in the manner of
 // dril_eval_account.h.  Who runs it: dril_eval.hip (traj_record_kernel through traj_record_lane, traj_record_rows_kernel through traj_record_lane_rows), dril_kernels.hip
-// (evaluate_modes_kernel's recording mode through traj_record_env) and the SAC handle (sac_traj_env_kernel of dril_sac.hip through traj_record_env, sac_traj_record_kernel of dril_sac_eval.hip through traj_record_lane,
+// (evaluate_modes_kernel's recording mode through traj_record_env) and the SAC handle (sac_traj_env_kernel of dril_sac_collect.hip through traj_record_env, sac_traj_record_kernel of dril_sac_eval.hip through traj_record_lane,
 // both with null clamp pointers); tests/test_traj_device.py, test_sac_traj.py and test_eval_persistent_modes.py drive the same lines with g++.  The setup around the rule: dril_traj_run.h.
 //
 // The recording is step-major on the device, [t][m][.], so one step's writes are contiguous M-sized rows; traj_reorder puts it into the caller's per-trajectory layout.

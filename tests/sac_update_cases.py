@@ -1,4 +1,4 @@
-"""The case table of the SAC update! step (sac_one_update of dril.jl_amd/csrc/dril_sac.hip: sac_gather[_l1]_kernel, sac_actor_out_ent_kernel<PRE>, sac_q_out_head_kernel,
+"""The case table of the SAC update! step (sac_one_update of dril.jl_amd/csrc/dril_sac_update.hip: sac_gather[_l1]_kernel, sac_actor_out_ent_kernel<PRE>, sac_q_out_head_kernel,
 sac_dx_squash_kernel, sac_adam_kernel / sac_step_end_kernel with first_layer_opt_block, and the unfused sac_ent_next / sac_critic_head / sac_actor_head / sac_squash_bwd
 kernels), its inputs, the float64 reference, the per-element error bounds and the assertion functions (test infrastructure of tests/test_sac_update_cases.py and
 tests/test_gpu_sac_update.py; conventions and helpers of tests/grad_cases.py).
@@ -308,7 +308,7 @@ def critic_range(row):
 # float64 forward / reverse passes with their scales
 # =====================================================================================================================
 def _tanh_own(h):
-    """the SAC kernels and the contractions' epilogue call tanhf (dril_sac.hip, include/device/dril_activations.h), 2 ulp of the result — not the exp2 / rcp form of the PPO
+    """the SAC kernels and the contractions' epilogue call tanhf (dril_sac_update.hip, dril_sac_net.hip, include/device/dril_activations.h), 2 ulp of the result — not the exp2 / rcp form of the PPO
     kernels, whose scale grad_cases._tanh_own is 3 (1 - h) + |h|"""
     return 2 * np.abs(h)
 
