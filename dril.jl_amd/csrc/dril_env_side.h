@@ -15,6 +15,7 @@
 #include "../../include/device/dril_env_plugin.h"   // DrilEnvPluginDesc / DrilEnvPluginArgs: the same definitions a plug-in is compiled with
 #include "../../include/device/dril_env_world.h"    // the limits of a world (N agents per state): descriptor word `agents`
 #include "../../include/device/dril_env_rollout.h"  // DrilEnvRolloutDesc / DrilEnvRolloutArgs: the fused rollout a plug-in may carry
+#include "../../include/device/dril_env_rollout_pop.h"  // DrilEnvRolloutPopDesc: the population entry of the fused rollout a plug-in may carry
 #include "../../include/device/dril_env_evaluate.h" // DrilEnvEvaluateDesc / DrilEnvEvaluateArgs: the fused evaluation a plug-in may carry
 #include "dril_internal.h"
 
@@ -98,6 +99,37 @@ inline EnvModuleRollout find_module_rollout(hipModule_t mod) {
     if (!r.reason.empty()) r.fn = r.fn_scaled = nullptr;
     return r;
 }
+// The population entry of the fused rollout (DRIL_ENV_PLUGIN_ROLLOUT_POP, include/device/dril_env_rollout_pop.h), looked up like the rollout itself: two kernels and a
+// descriptor, all optional; `reason` is empty when the kernel can be launched, else it names the header and the macro.  Nothing of the module is launched.
+struct EnvModuleRolloutPop { hipFunction_t fn = nullptr, fn_scaled = nullptr; DrilEnvRolloutPopDesc desc{}; bool has_desc = false; std::string reason; };
+inline EnvModuleRolloutPop find_module_rollout_pop(hipModule_t mod) {
+    EnvModuleRolloutPop r;
+    r.fn = env_module_optional(mod, "dril_env_plugin_rollout_pop"); r.fn_scaled = env_module_optional(mod, "dril_env_plugin_rollout_pop_scaled");
+    hipDeviceptr_t dptr = nullptr; size_t bytes = 0;
+    if (hipModuleGetGlobal(&dptr, &bytes, mod, "dril_env_plugin_rollout_pop_desc") != hipSuccess) { (void)hipGetLastError(); dptr = nullptr; }
+    const std::string rebuild = ": rebuild the plug-in against this library's include/device/dril_env_rollout_pop.h";
+    if (!r.fn || !dptr) { r.fn = r.fn_scaled = nullptr; r.reason = "the code object has no population entry of the fused rollout (dril_env_plugin_rollout_pop): add #include \"device/dril_env_rollout_pop.h\" and DRIL_ENV_PLUGIN_ROLLOUT_POP(Env) after DRIL_ENV_PLUGIN_ROLLOUT(Env) to the plug-in's source and rebuild"; return r; }
+    if (bytes != sizeof(DrilEnvRolloutPopDesc) || hipMemcpy(&r.desc, dptr, sizeof(r.desc), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError(); r.fn = r.fn_scaled = nullptr;
+        r.reason = "dril_env_plugin_rollout_pop_desc is " + std::to_string(bytes) + " bytes, this library reads " + std::to_string(sizeof(DrilEnvRolloutPopDesc)) + rebuild; return r; }
+    r.has_desc = true;
+    if (r.desc.abi_version != DRIL_ENV_ROLLOUT_POP_ABI) r.reason = "population rollout ABI " + std::to_string(r.desc.abi_version) + ", this library speaks " + std::to_string(DRIL_ENV_ROLLOUT_POP_ABI) + rebuild;
+    else if (r.desc.args_size != sizeof(DrilEnvRolloutArgs)) r.reason = "a member's block of the population rollout is " + std::to_string(r.desc.args_size) + " bytes, this library passes " + std::to_string(sizeof(DrilEnvRolloutArgs)) + rebuild;
+    else if (r.desc.tile < 1 || r.desc.threads < r.desc.tile || r.desc.threads > 1024 || r.desc.max_width < 1) r.reason = "the population rollout's descriptor is out of range (tile " + std::to_string(r.desc.tile) + ", threads " + std::to_string(r.desc.threads) + ", max width " + std::to_string(r.desc.max_width) + ")";
+    else if ((r.desc.has_scaled != 0) != (r.fn_scaled != nullptr)) r.reason = std::string("the population rollout's descriptor says has_scaled = ") + std::to_string(r.desc.has_scaled) + ", but dril_env_plugin_rollout_pop_scaled is " + (r.fn_scaled ? "present" : "absent");
+    if (!r.reason.empty()) r.fn = r.fn_scaled = nullptr;
+    return r;
+}
+// size and 64-bit FNV-1a hash of a code object file's bytes: what tells two handles' plug-ins apart (a population's members run ONE member's kernel)
+inline bool hash_code_object(const char* path, uint64_t* size, uint64_t* hash) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return false;
+    uint64_t h = 1469598103934665603ull, n = 0; unsigned char buf[4096]; size_t got;
+    while ((got = std::fread(buf, 1, sizeof(buf), f)) > 0) { n += got; for (size_t i = 0; i < got; ++i) { h ^= buf[i]; h *= 1099511628211ull; } }
+    std::fclose(f);
+    *size = n; *hash = h;
+    return true;
+}
 // The fused evaluation of a loaded, checked plug-in (DRIL_ENV_PLUGIN_EVALUATE, include/device/dril_env_evaluate.h), looked up like the rollout: two kernels and a
 // descriptor, all optional; `reason` is empty when the kernel can be launched.  Nothing of the module is launched.
 struct EnvModuleEvaluate { hipFunction_t fn = nullptr, fn_scaled = nullptr; DrilEnvEvaluateDesc desc{}; bool has_desc = false; std::string reason; };
@@ -164,6 +196,8 @@ struct DeviceEnvs {
     std::vector<float> obs_low, obs_high; bool obs_declared = false, scaling = false;
     hipFunction_t mod_observe_scaled = nullptr, mod_step_scaled = nullptr;
     EnvModuleRollout rollout;   // the plug-in's fused rollout, when its code object carries one (PPO handles: dril_rollout_fused_enable)
+    EnvModuleRolloutPop rollout_pop;   // the population entry of that rollout, when the code object carries one (dril_population_join)
+    uint64_t code_size = 0, code_hash = 0;   // the code object file as it was loaded: its size and the FNV-1a hash of its bytes
     EnvModuleEvaluate evaluate; // the plug-in's fused evaluation, when its code object carries one (PPO handles: path 2 of the evaluation / trajectory verbs)
 
     // what the envs are; for DRIL_ENV_MODULE also the plug-in: loaded, its descriptor kept, episode_len 0 replaced by the descriptor's, its three kernels found.
@@ -184,7 +218,8 @@ struct DeviceEnvs {
             if (e != hipSuccess) { msg = std::string("hipModuleGetFunction(") + names[i] + "): " + hipGetErrorString(e); release(); return DRIL_ERR_HIP; }
         }
         mod_observe_scaled = env_module_optional(module, "dril_env_plugin_observe_scaled"); mod_step_scaled = env_module_optional(module, "dril_env_plugin_step_scaled");
-        rollout = find_module_rollout(module); evaluate = find_module_evaluate(module);
+        rollout = find_module_rollout(module); rollout_pop = find_module_rollout_pop(module); evaluate = find_module_evaluate(module);
+        if (!hash_code_object(module_path, &code_size, &code_hash)) { msg = std::string("cannot read code object ") + module_path; release(); return DRIL_ERR_INVALID_ARG; }
         const int rs = read_module_obs_space(module, desc, obs_low, obs_high, &obs_declared, msg);
         if (rs) release();
         return rs;
@@ -260,6 +295,13 @@ struct DeviceEnvs {
         if (!f) return hipErrorInvalidDeviceFunction;
         void* params[] = {&g};
         return hipModuleLaunchKernel(f, (unsigned)((E + rollout.desc.tile - 1) / rollout.desc.tile), 1, 1, (unsigned)rollout.desc.threads, 1, 1, 0, s, params, nullptr);
+    }
+    // n members' fused collections in one launch: grid (ceil(E / tile), n), row y takes d_members[y] (device memory; every member with this E and this code object)
+    hipError_t launch_rollout_pop(const DrilEnvRolloutArgs* d_members, int n, hipStream_t s) const {
+        const hipFunction_t f = scaling ? rollout_pop.fn_scaled : rollout_pop.fn;
+        if (!f || n < 1) return hipErrorInvalidDeviceFunction;
+        void* params[] = {&d_members, &n};
+        return hipModuleLaunchKernel(f, (unsigned)((E + rollout_pop.desc.tile - 1) / rollout_pop.desc.tile), (unsigned)n, 1, (unsigned)rollout_pop.desc.threads, 1, 1, 0, s, params, nullptr);
     }
     // the fused evaluation: ceil(E / tile) workgroups, each takes its envs through the g.r.T steps of the launch
     hipError_t launch_evaluate(DrilEnvEvaluateArgs g, hipStream_t s) const {

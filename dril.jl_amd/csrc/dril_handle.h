@@ -184,6 +184,10 @@ std::string norm_rollout_unavailable(const dril_handle* h);
 bool norm_rollout_applies(const dril_handle* h);
 NormRolloutArgs norm_rollout_args(const dril_handle* h);
 void norm_rollout_done(dril_handle* h);
+// a plug-in's fused collection (dril_rollout_fused_enable): "" when the handle's net fits the plug-in's kernel, else why not; the argument block of its ONE launch, read
+// from the handle as it stands (collect_rollout, and a population for each of its members)
+std::string fused_rollout_unavailable(const dril_handle* h);
+DrilEnvRolloutArgs module_rollout_args(const dril_handle* h);
 int collect_rollout(dril_handle* h, double* fps, bool do_sync);
 
 // ---- dril_ext.hip ----
@@ -209,6 +213,9 @@ void small_update_done(dril_handle* h, const UpdatePlan& p);
 std::string update_fused_unavailable(const dril_handle* h);
 bool update_fused_applies(const dril_handle* h, const UpdatePlan& p);
 void update_fused_done(dril_handle* h, const UpdatePlan& p, int64_t launches);
+// that update's argument block but for the launch's own words (small_update_chunk per launch; the launcher fills the LDS plan): small_update_args and the rollout
+// buffer's arrays.  keys as in small_update_args
+int generic_update_args(dril_handle* h, const UpdatePlan& p, uint64_t* keys, GenericUpdateArgs& g);
 int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home);
 int update_finish(dril_handle* h, const UpdatePlan& p, const UpdateHome& home, dril_ppo_stats* out);
 bool update_direct_f32(const dril_handle* h);

@@ -250,6 +250,10 @@ struct GenericUpdateArgs {
 std::string generic_update_unfit(const GenericDims& d, int P);   // "" when the net is inside the kernel's caps, else which cap it misses and what to do
 int generic_update_tile(const GenericDims& d);                   // samples per tile the launcher picks (32 or 16; 0: does not fit)
 hipError_t launch_ppo_update_generic_small(const GenericDims& d, GenericUpdateArgs a, hipStream_t s);
+// n members of a population in one launch (ppo_update_generic_small_pop_kernel, a 1-D grid of n workgroups; GenericDims equal across the members).  prepare: checks the
+// host copies of the blocks as a solo launch checks its own and fills what the launcher fills (lay, D .. need_z) — before they are copied to d_members
+hipError_t prepare_ppo_update_generic_small_pop(const GenericDims& d, GenericUpdateArgs* h_members, int n);
+hipError_t launch_ppo_update_generic_small_pop(const GenericDims& d, const GenericUpdateArgs* d_members, int n, hipStream_t s);
 
 // device-array verbs of DRIL_ENV_EXTERNAL (dril_ext_device.hip).  ExtBounds: the ClampAdapter's table, one (low, high) per action dimension; low >= high = not clamped
 struct ExtBounds { float lo[64], hi[64]; };

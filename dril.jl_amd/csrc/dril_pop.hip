@@ -17,6 +17,8 @@ using namespace dril::ppo;
 // rollout_duo_kernel and ppo_update_small_kernel P times.  Normalising members (NormalizeWrapperEnv with dril_norm_rollout_enable on) collect through one
 // rollout_norm_pop_kernel launch, after each member's opening observe.  It keeps no copy of member state: every verb reads each handle with the solo path's own functions
 // (rollout_args, update_begin, small_update_args, update_enqueue_home, update_finish, update_resolve), so a member's result is that of its handle driven alone, bit for bit.
+// Handles of ONE device env plug-in code object whose solo iteration is the fused rollout plus the one-launch generic update join as well ("Plug-in members"): their
+// collections are one launch of the code object's dril_env_plugin_rollout_pop, their updates one launch of ppo_update_generic_small_pop_kernel per chunk, no cap.
 // While joined, the members share the population's stream: whatever a member's own verbs enqueue between population calls is ordered with the batched launches.
 struct dril_population {
     std::vector<dril_handle*> members; std::vector<hipStream_t> own_streams;
@@ -24,6 +26,9 @@ struct dril_population {
     PinnedBuf<NormRolloutArgs> h_nargs; DevBuf<NormRolloutArgs> d_nargs;   // normalising members: the blocks of rollout_norm_pop_kernel, pinned / device [n]
     PinnedBuf<RolloutArgs> h_rargs; DevBuf<RolloutArgs> d_rargs; PinnedBuf<SmallUpdateArgs> h_uargs; DevBuf<SmallUpdateArgs> d_uargs;   // pinned / device: [n] and [n_chunks][n]
     DevBuf<unsigned long long> xchg;                             // n x kSmallXchgWords
+    // plug-in members (docs/population.md, "Plug-in members"): the blocks of the plug-in's dril_env_plugin_rollout_pop, pinned / device [n], and of
+    // ppo_update_generic_small_pop_kernel, pinned [n_chunks + 1][n] (the launch table, and behind it one block per member) / device [n_chunks][n]
+    PinnedBuf<DrilEnvRolloutArgs> h_margs; DevBuf<DrilEnvRolloutArgs> d_margs; PinnedBuf<GenericUpdateArgs> h_gargs; DevBuf<GenericUpdateArgs> d_gargs;
     std::vector<PinnedBuf<char>> home_blocks; std::vector<UpdateHome> homes;   // one pinned block per member: where its update's results land
     std::vector<int> failed;                                     // status of a member that failed in the current call (it sits out the rest of the iteration)
     struct dril_population_info info{};
@@ -37,12 +42,33 @@ struct dril_population {
 namespace {
 int pop_fail(dril_population* p, int code, const std::string& msg) { p->err = msg; return code; }
 #define POPCHK(p, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return pop_fail(p, DRIL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
-// "" when the handle can be a member, else why not (the shape on which a solo iteration is one rollout_duo_kernel launch and one ppo_update_small_kernel launch)
+// whether the collection of a plug-in handle is ONE launch of its code object's fused rollout kernel, the population entry aside
+bool module_rollout_fused(const dril_handle* h) { return h->env.module && !h->env.is_world() && h->fused_rollout && !h->pn.on && !h->force_stepwise && fused_rollout_unavailable(h).empty(); }
+// "" when a device env plug-in handle can be a member, else why not and what to do: its solo iteration is exactly one dril_env_plugin_rollout launch plus
+// ceil(steps / update_fused_chunk) launches of ppo_update_generic_small_kernel, and its code object carries the population entry of the rollout
+std::string pop_plugin_ineligible(const dril_handle* h) {
+    const std::string who = std::string("device env plug-in \"") + h->env.desc.name + "\": ";
+    if (h->pn.on) return who + "NormalizeWrapperEnv is on (dril_normalize_enable): its collection is step-granular; populations take plug-in handles that collect with the fused rollout";
+    if (h->force_stepwise) return who + "DRIL_FORCE_STEPWISE is set: every collection of this handle runs the step-granular launches; unset it and create the handle again";
+    if (!h->fused_rollout) return who + "its collection is step-granular: a plug-in handle becomes eligible with the one-launch collection, dril_rollout_fused_enable(h, 1), and the one-launch update, dril_update_fused_enable(h, 1)";
+    { const std::string why = fused_rollout_unavailable(h); if (!why.empty()) return who + "its fused rollout is not available: " + why; }
+    if (!h->update_fused) return who + "its update runs the per-step kernels: a plug-in handle becomes eligible with the one-launch update, dril_update_fused_enable(h, 1)";
+    { const std::string why = update_fused_unavailable(h); if (!why.empty()) return who + "its one-launch update is not available: " + why; }
+    if (update_plan(h).total_steps < 1) return who + "epochs < 1: there is no update to batch";
+    const EnvModuleRolloutPop& r = h->env.rollout_pop;
+    if (!r.reason.empty()) return who + r.reason;
+    if (h->env.scaling && !r.fn_scaled) return who + "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_rollout_pop_scaled kernel: rebuild it with this library's include/device/dril_env_rollout_pop.h (DRIL_ENV_PLUGIN_ROLLOUT_POP)";
+    if (r.desc.tile != h->env.rollout.desc.tile || r.desc.threads != h->env.rollout.desc.threads || r.desc.max_width != h->env.rollout.desc.max_width) return who + "the population entry was compiled with another tile, thread count or maximum width than the fused rollout of the same code object: rebuild the plug-in from one source";
+    return "";
+}
+// "" when the handle can be a member, else why not (the shape on which a solo iteration is one rollout_duo_kernel launch and one ppo_update_small_kernel launch; for a
+// device env plug-in: pop_plugin_ineligible)
 std::string pop_ineligible(const dril_handle* h, int& code) {
     code = DRIL_ERR_UNSUPPORTED;
     if (h->external) return "an external handle (DRIL_ENV_EXTERNAL): its envs live with the caller";
     if (h->env.is_world()) return "a world of a device env plug-in";
-    if (h->env.module || !env_kind_info(h->cfg.env_kind)) return "a device env plug-in handle (DRIL_ENV_MODULE): populations take the built-in env kinds";
+    if (h->env.module) return pop_plugin_ineligible(h);
+    if (!env_kind_info(h->cfg.env_kind)) return "a device env plug-in handle (DRIL_ENV_MODULE): populations take the built-in env kinds";
     if (h->pn.on || (normalizing(h) && !h->norm_rollout)) return "a normalising handle (NormalizeWrapperEnv collects step by step): a built-in handle becomes eligible with the one-launch collection, dril_norm_rollout_enable(h, 1)";
     if (normalizing(h)) { const std::string why = norm_rollout_unavailable(h); if (!why.empty()) return "a normalising handle whose one-launch collection is not available: " + why; }
     if (h->cfg.world_size > 1 || comm_ready(h)) return "world_size > 1: members are single-rank handles";
@@ -58,9 +84,20 @@ std::string pop_mismatch(const dril_handle* a, const dril_handle* b, int& code) 
     const dril_config &x = a->cfg, &y = b->cfg;
     code = DRIL_ERR_INVALID_ARG;
     if (x.device != y.device) return "mixed devices (device " + std::to_string(y.device) + " against member 0's " + std::to_string(x.device) + ")";
+    if ((a->env.module != nullptr) != (b->env.module != nullptr)) return "mixed members (device env plug-in handles and built-in env kinds do not share a launch: one population each)";
+    if (a->env.module) {
+        if (a->env.code_hash != b->env.code_hash || a->env.code_size != b->env.code_size) return std::string("mixed code objects (plug-in \"") + b->env.desc.name + "\" against member 0's \"" + a->env.desc.name + "\": the members run ONE code object's kernel)";
+        if (a->env.scaling != b->env.scaling) return "mixed scaling (ScalingWrapperEnv must be on for every member or for none)";
+    }
     if (x.env_kind != y.env_kind) return "mixed env kinds (" + std::to_string(y.env_kind) + " against member 0's " + std::to_string(x.env_kind) + ")";
     if (x.n_envs != y.n_envs || x.n_steps != y.n_steps || x.batch_size != y.batch_size || x.epochs != y.epochs) return "mixed shapes (n_envs, n_steps, batch_size and epochs must equal member 0's)";
     if (x.hidden1 != y.hidden1 || x.hidden2 != y.hidden2 || x.n_hidden != y.n_hidden || x.activation != y.activation) return "mixed shapes (hidden dims and activation must equal member 0's)";
+    if (a->env.module) {
+        const GenericDims &g = a->gd, &k = b->gd;
+        bool same = g.nh == k.nh && g.act == k.act && g.D == k.D && g.A == k.A && g.discrete == k.discrete;
+        for (int l = 0; same && l < g.nh; ++l) same = g.H[l] == k.H[l];
+        if (!same) return "mixed shapes (the number of hidden layers, every width and the activation must equal member 0's)";
+    }
     if (x.normalize_advantage != y.normalize_advantage) return "mixed shapes (normalize_advantage must equal member 0's)";
     if ((x.norm_obs != 0) != (y.norm_obs != 0) || (x.norm_reward != 0) != (y.norm_reward != 0) || (x.norm_training != 0) != (y.norm_training != 0) || a->norm_rollout != b->norm_rollout)
         return "mixed NormalizeWrapperEnv (norm_obs, norm_reward, norm_training and dril_norm_rollout_enable must equal member 0's; clips, epsilon, norm_gamma and the statistics are free)";
@@ -108,14 +145,15 @@ void pop_call_begin(dril_population* p) {
 // f16-piece forward, collect_rollout itself for the others; then per member what follows the launch in collect_rollout (monitor window, GAE)
 int pop_collect(dril_population* p, double* fps, bool do_sync, int& first) {
     const int n = (int)p->members.size();
-    std::vector<int> batched, nbatched, solo;                     // one rollout_duo_pop_kernel launch; one rollout_norm_pop_kernel launch; alone
+    std::vector<int> batched, nbatched, mbatched, solo;           // one rollout_duo_pop_kernel launch; one rollout_norm_pop_kernel launch; one launch of the plug-in's dril_env_plugin_rollout_pop; alone
     for (int m = 0; m < n; ++m) {
         dril_handle* h = p->members[m];
         if (p->failed[m]) continue;
         if (fps) fps[m] = 0;
         if (!h->env.ready) { pop_member_failed(p, m, fail(h, DRIL_ERR_NOT_INITIALISED, "dril_collect_rollout before dril_env_reset"), "dril_population_collect_rollout", first); continue; }
         { const int rcw = ensure_wimg(h); if (rcw) { pop_member_failed(p, m, rcw, "dril_population_collect_rollout", first); continue; } }
-        if (rollout_fused_applies(h) && h->cfg.hidden1 == 64 && rollout_duo_applies(h->cfg.hidden1, h->env.E) && !fwd_exact(h)) batched.push_back(m);
+        if (module_rollout_fused(h) && h->env.rollout_pop.reason.empty() && p->h_margs) mbatched.push_back(m);
+        else if (rollout_fused_applies(h) && h->cfg.hidden1 == 64 && rollout_duo_applies(h->cfg.hidden1, h->env.E) && !fwd_exact(h)) batched.push_back(m);
         else if (norm_rollout_applies(h)) nbatched.push_back(m);
         else solo.push_back(m);
     }
@@ -174,6 +212,34 @@ int pop_collect(dril_population* p, double* fps, bool do_sync, int& first) {
             if (rc) pop_member_failed(p, m, rc, "dril_population_collect_rollout", first);
         }
     }
+    if (!mbatched.empty()) {                                      // collect_rollout's fused plug-in route, member by member around ONE launch of member 0's kernel
+        const int nbat = (int)mbatched.size();
+        for (int k = 0; k < nbat; ++k) p->h_margs[k] = module_rollout_args(p->members[mbatched[k]]);   // (an injected noise table rides in the member's block)
+        hipError_t e = hipMemcpyAsync(p->d_margs, p->h_margs, sizeof(DrilEnvRolloutArgs) * (size_t)nbat, hipMemcpyHostToDevice, p->stream);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (fps && e == hipSuccess) e = hipStreamSynchronize(p->stream);
+        pop_ev_begin(p, 0);
+        if (e == hipSuccess) e = p->members[mbatched[0]]->env.launch_rollout_pop(p->d_margs, nbat, p->stream);
+        pop_ev_end(p);
+        double f = 0;
+        if (fps && e == hipSuccess) {
+            e = hipStreamSynchronize(p->stream);
+            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            f = (double)p->members[0]->N / (dt > 0 ? dt : 1e-12);
+        }
+        p->info.last_rollout_launches += 1; p->info.total_rollout_launches += 1;
+        for (int k = 0; k < nbat; ++k) {
+            const int m = mbatched[k]; dril_handle* h = p->members[m];
+            int rc = e == hipSuccess ? DRIL_OK : fail(h, DRIL_ERR_HIP, std::string("dril_env_plugin_rollout_pop: ") + hipGetErrorString(e));
+            if (!rc) {                                              // what collect_rollout leaves around collect_rollout_module_fused
+                if (fps) fps[m] = f;
+                h->gws.launches = 0; h->rollout_launches = 1 + (h->mon_cur_ret ? 1 : 0);
+                rc = monitor_collect_rollout(h); h->noise_set = false;
+            }
+            if (!rc) rc = compute_gae(h);
+            if (rc) pop_member_failed(p, m, rc, "dril_population_collect_rollout", first);
+        }
+    }
     for (int m : solo) {
         double f = 0; const int rc = collect_rollout(p->members[m], fps ? &f : nullptr, false);
         if (fps) fps[m] = f;
@@ -189,12 +255,22 @@ int pop_collect(dril_population* p, double* fps, bool do_sync, int& first) {
 int pop_update(dril_population* p, dril_ppo_stats* out, int& first) {
     const int n = (int)p->members.size();
     struct Run { int m; UpdatePlan plan; UpdateTry t; };
-    std::vector<Run> batched; std::vector<int> solo;
+    std::vector<Run> batched, gbatched; std::vector<int> solo;    // one ppo_update_small_pop_kernel launch per chunk; one ppo_update_generic_small_pop_kernel launch per chunk; alone
     for (int m = 0; m < n; ++m) {
         dril_handle* h = p->members[m];
         if (p->failed[m]) continue;
         if (out) std::memset(&out[m], 0, sizeof(dril_ppo_stats));
         const UpdatePlan plan = update_plan(h);
+        if (!small_persistent_applies(h, plan) && update_fused_applies(h, plan) && plan.total_steps == p->total_steps && p->h_gargs) {   // ppo_update's one-launch route of a generic handle
+            GenericUpdateArgs g{};
+            h->update_fused_path = 0; h->update_fused_launches = 0;
+            int rc = update_begin(h, plan);
+            if (!rc) rc = generic_update_args(h, plan, p->homes[m].keys, g);
+            if (rc) { pop_member_failed(p, m, rc, "dril_population_ppo_update", first); continue; }
+            p->h_gargs[(size_t)p->n_chunks * n + gbatched.size()] = g;                     // behind the launch table, as below
+            gbatched.push_back(Run{m, plan, UpdateTry{}});
+            continue;
+        }
         if (!small_persistent_applies(h, plan) || update_direct_f32(h) || plan.total_steps != p->total_steps) { solo.push_back(m); continue; }
         Run r{m, plan, UpdateTry{}};
         SmallUpdateArgs u{};
@@ -226,6 +302,35 @@ int pop_update(dril_population* p, dril_ppo_stats* out, int& first) {
             }
         pop_ev_end(p);
     }
+    // the generic members: one launch of n workgroups per chunk (no cap: the workgroups never wait for one another); a member that stopped (target_kl, a non-finite
+    // gradient) idles through the later chunks on its own stop_flag.  The route is f32 throughout: no redo follows
+    const int ngen = (int)gbatched.size();
+    hipError_t eg = hipSuccess;
+    if (ngen > 0) {
+        int c = 0;
+        for (int64_t s0 = 0; s0 < p->total_steps; s0 += p->chunk, ++c)
+            for (int k = 0; k < ngen; ++k) {
+                GenericUpdateArgs& g = p->h_gargs[(size_t)c * ngen + k];
+                g = p->h_gargs[(size_t)p->n_chunks * n + k];
+                small_update_chunk(gbatched[k].plan, p->chunk, s0, g.u);
+            }
+        const GenericDims& gd = p->members[gbatched[0].m]->gd;
+        eg = prepare_ppo_update_generic_small_pop(gd, p->h_gargs, p->n_chunks * ngen);
+        if (eg == hipSuccess) eg = hipMemcpyAsync(p->d_gargs, p->h_gargs, sizeof(GenericUpdateArgs) * (size_t)p->n_chunks * ngen, hipMemcpyHostToDevice, p->stream);
+        pop_ev_begin(p, 1);
+        for (c = 0; c < p->n_chunks && eg == hipSuccess; ++c) {
+            eg = launch_ppo_update_generic_small_pop(gd, p->d_gargs + (size_t)c * ngen, ngen, p->stream);
+            p->info.last_update_launches += 1; p->info.total_update_launches += 1;
+        }
+        pop_ev_end(p);
+    }
+    std::vector<char> genq((size_t)ngen, 0);
+    for (int k = 0; k < ngen; ++k) {
+        const int m = gbatched[k].m; dril_handle* h = p->members[m];
+        int rc = eg == hipSuccess ? DRIL_OK : fail(h, DRIL_ERR_HIP, std::string("ppo_update_generic_small_pop_kernel: ") + hipGetErrorString(eg));
+        if (!rc) { update_fused_done(h, gbatched[k].plan, p->n_chunks); rc = update_enqueue_home(h, gbatched[k].plan, p->homes[m]); }
+        if (rc) pop_member_failed(p, m, rc, "dril_population_ppo_update", first); else genq[k] = 1;
+    }
     std::vector<char> enq((size_t)nbat, 0);
     for (int k = 0; k < nbat; ++k) {
         const int m = batched[k].m; dril_handle* h = p->members[m];
@@ -233,7 +338,13 @@ int pop_update(dril_population* p, dril_ppo_stats* out, int& first) {
         if (!rc) { small_update_done(h, batched[k].plan); rc = update_enqueue_home(h, batched[k].plan, p->homes[m]); }
         if (rc) pop_member_failed(p, m, rc, "dril_population_ppo_update", first); else enq[k] = 1;
     }
-    if (nbat > 0) { const int rc = pop_sync(p); if (rc) return rc; }                       // ONE drain for the whole population
+    if (nbat > 0 || ngen > 0) { const int rc = pop_sync(p); if (rc) return rc; }           // ONE drain for the whole population
+    for (int k = 0; k < ngen; ++k) {
+        if (!genq[k]) continue;
+        const int m = gbatched[k].m;
+        const int rc = update_finish(p->members[m], gbatched[k].plan, p->homes[m], out ? &out[m] : nullptr);
+        if (rc) pop_member_failed(p, m, rc, "dril_population_ppo_update", first);              // (its error does not stop the others)
+    }
     for (int k = 0; k < nbat; ++k) {
         if (!enq[k]) continue;
         const int m = batched[k].m; dril_handle* h = p->members[m];
@@ -266,7 +377,7 @@ int pop_evaluate(dril_population* p, const dril_eval_options* o, dril_eval_stats
         Run r{}; r.m = m;
         int rc = eval_prepare(h, o, r.pl);
         if (rc) { pop_member_failed(p, m, rc, verb, first); continue; }
-        if (!r.pl.persistent || r.pl.fused || normalizing(h) || fwd_exact(h) || h->cfg.hidden1 != 64) { solo.push_back(m); continue; }   // not evaluate_kernel<K, 64, false, true>: alone, below
+        if (h->env.module || !r.pl.persistent || r.pl.fused || normalizing(h) || fwd_exact(h) || h->cfg.hidden1 != 64) { solo.push_back(m); continue; }   // not evaluate_kernel<K, 64, false, true>: alone, below
         rc = eval_set_aside(h, r.pl.keep);
         if (rc) { pop_member_failed(p, m, rc, verb, first); continue; }
         EvalAcct acct{};
@@ -359,8 +470,9 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
     p->device = h0->cfg.device;
     p->cap = h0->num_cus / 4 > 0 ? h0->num_cus / 4 : 1;                               // two workgroups per member, at most half the CUs per launch
     if (const char* e = debug_env("DRIL_POP_CAP")) { const int c = std::atoi(e); if (c > 0 && c < p->cap) p->cap = c; }   // tests: more than one launch per verb
-    p->chunk = h0->small_chunk;
-    for (int m = 0; m < n; ++m) if (members[m]->small_chunk < p->chunk) p->chunk = members[m]->small_chunk;
+    const bool plugin = h0->env.module != nullptr;                                     // (pop_mismatch: then every member is a handle of the same code object)
+    p->chunk = plugin ? h0->update_fused_chunk : h0->small_chunk;
+    for (int m = 0; m < n; ++m) { const int64_t c = plugin ? members[m]->update_fused_chunk : members[m]->small_chunk; if (c < p->chunk) p->chunk = c; }
     p->total_steps = update_plan(h0).total_steps;
     p->n_chunks = (int)((p->total_steps + p->chunk - 1) / p->chunk);
     JCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
@@ -371,6 +483,10 @@ DRIL_EXPORT int32_t dril_population_join(dril_handle** members, int32_t n, dril_
     JCHK(p->d_nargs.alloc((size_t)n));
     JCHK(p->d_uargs.alloc((size_t)p->n_chunks * n));
     JCHK(p->xchg.alloc((size_t)n * kSmallXchgWords));
+    if (plugin) {
+        JCHK(p->h_margs.alloc((size_t)n)); JCHK(p->d_margs.alloc((size_t)n));
+        JCHK(p->h_gargs.alloc(((size_t)p->n_chunks + 1) * n)); JCHK(p->d_gargs.alloc((size_t)p->n_chunks * n));
+    }
     JCHK(p->h_eargs.alloc((size_t)n));
     JCHK(p->d_eargs.alloc((size_t)n));
     JCHK(p->h_eval_counters.alloc((size_t)n));

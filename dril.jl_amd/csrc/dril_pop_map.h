@@ -20,15 +20,9 @@ DRIL_POP_HD constexpr int pop_grid(int n) { return 2 * kPopXcds * ((n + kPopXcds
 DRIL_POP_HD constexpr int pop_block_member(int b) { return kPopXcds * (b / (2 * kPopXcds)) + b % kPopXcds; }
 DRIL_POP_HD constexpr int pop_block_role(int b) { return (b / kPopXcds) & 1; }
 
-#if defined(__HIPCC__)
-// A pointer read out of a member's argument block is a generic pointer to the compiler, and every access through it a flat one; a kernel argument is known to be
-// global.  The round trip through the global address space gives the block's pointers that knowledge back (null stays null), so a member's loop issues the same
-// global loads, stores and atomics as its solo twin.  The empty asm keeps the optimiser from folding the two casts away; the pointers are uniform (scalar registers).
-template <class T> __device__ __forceinline__ T* pop_global(T* p) {
-    auto g = (__attribute__((address_space(1))) T*)p;
-    asm("" : "+s"(g));
-    return (T*)g;
-}
-#endif
-
 }  // namespace dril
+
+// pop_global (device code): the global-address-space round trip of a pointer read out of a member's argument block, shared with the plug-ins' population kernels
+#if defined(__HIPCC__)
+#include "../../include/device/dril_pop_global.h"
+#endif

@@ -89,31 +89,10 @@ int collect_rollout_module(dril_handle* h) {
 // the fused collection (dril_rollout_fused_enable): ONE launch of the plug-in's own rollout kernel (include/device/dril_env_rollout.h) does what the loop of
 // collect_rollout_module does in 6+ launches per env step, and leaves env state, counters, monitor sums and the per-step arrays as that loop leaves them
 int collect_rollout_module_fused(dril_handle* h) {
-    DrilEnvRolloutArgs g{};
-    g.env = h->env.args();
-    g.env.terminated = h->e_term; g.env.truncated = h->e_trunc; g.env.terminal_obs = h->e_tobs; g.env.obs = h->e_obs;
-    g.env.mon_cur_ret = h->mon_cur_ret; g.env.mon_cur_len = h->mon_cur_len;
-    g.T = h->cfg.n_steps; g.n_hidden = h->gd.nh; g.activation = h->gd.act; g.n_params = h->P;
-    for (int l = 0; l < h->gd.nh; ++l) g.hidden[l] = h->gd.H[l];
-    g.actor_off = h->actor.w1; g.critic_off = h->critic.w1; g.log_std_off = h->log_std_off;
-    g.params = h->params; g.noise = h->noise_set ? h->noise_dev : nullptr;
-    g.obs = h->obs; g.act = h->act; g.rew = h->rew; g.logp = h->logp; g.val = h->val; g.boot = h->boot; g.flags = h->flags; g.last_values = h->last_values;
-    if (h->mon_cur_ret) { g.ep_ret = h->ep_ret; g.ep_len = h->ep_len; }
+    const DrilEnvRolloutArgs g = module_rollout_args(h);
     h->rollout_launches += 1;
     HIPCHK(h, h->env.launch_rollout(g, h->stream));
     return monitor_collect_rollout(h);
-}
-// "" when the handle's net fits the plug-in's fused rollout kernel, else why not
-std::string fused_rollout_unavailable(const dril_handle* h) {
-    if (!h->env.module) return "the fused rollout is the collection kernel of a device env plug-in (DRIL_ENV_MODULE): the built-in envs collect with the library's own rollout_kernel, host envs (DRIL_ENV_EXTERNAL) step on the host";
-    if (h->env.is_world()) return std::string("env plug-in \"") + h->env.desc.name + "\" is a world of " + std::to_string(h->env.agents()) + " agents: worlds have no fused rollout yet (DRIL_ENV_PLUGIN_ROLLOUT refuses a world at compile time); collect step-granular, which is the default";
-    const EnvModuleRollout& r = h->env.rollout;
-    if (!r.reason.empty()) return std::string("env plug-in \"") + h->env.desc.name + "\": " + r.reason;
-    const int W = r.desc.max_width;
-    if (h->D > W) return "the observation has " + std::to_string(h->D) + " dims, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->D) + " or more";
-    for (int l = 0; l < h->gd.nh; ++l) if (h->gd.H[l] > W) return "hidden layer " + std::to_string(l + 1) + " is " + std::to_string(h->gd.H[l]) + " wide, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->gd.H[l]) + " or more";
-    if (h->env.scaling && !r.fn_scaled) return "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_rollout_scaled kernel: rebuild it with this library's include/device/dril_env_rollout.h";
-    return "";
 }
 
 void* buf_ptr(dril_handle* h, int which, size_t* bytes) {
@@ -152,6 +131,33 @@ std::string fused_evaluate_unavailable(const dril_handle* h) {
     if (h->D > W) return "the observation has " + std::to_string(h->D) + " dims, the plug-in's fused evaluation was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->D) + " or more";
     for (int l = 0; l < h->gd.nh; ++l) if (h->gd.H[l] > W) return "hidden layer " + std::to_string(l + 1) + " is " + std::to_string(h->gd.H[l]) + " wide, the plug-in's fused evaluation was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->gd.H[l]) + " or more";
     if (h->env.scaling && !r.fn_scaled) return "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_evaluate_scaled kernel: rebuild it with this library's include/device/dril_env_evaluate.h";
+    return "";
+}
+
+// the argument block of the plug-in's fused rollout kernel, read from the handle as it stands (collect_rollout_module_fused, and a population for each of its members)
+DrilEnvRolloutArgs module_rollout_args(const dril_handle* h) {
+    DrilEnvRolloutArgs g{};
+    g.env = h->env.args();
+    g.env.terminated = h->e_term; g.env.truncated = h->e_trunc; g.env.terminal_obs = h->e_tobs; g.env.obs = h->e_obs;
+    g.env.mon_cur_ret = h->mon_cur_ret; g.env.mon_cur_len = h->mon_cur_len;
+    g.T = h->cfg.n_steps; g.n_hidden = h->gd.nh; g.activation = h->gd.act; g.n_params = h->P;
+    for (int l = 0; l < h->gd.nh; ++l) g.hidden[l] = h->gd.H[l];
+    g.actor_off = h->actor.w1; g.critic_off = h->critic.w1; g.log_std_off = h->log_std_off;
+    g.params = h->params; g.noise = h->noise_set ? h->noise_dev : nullptr;
+    g.obs = h->obs; g.act = h->act; g.rew = h->rew; g.logp = h->logp; g.val = h->val; g.boot = h->boot; g.flags = h->flags; g.last_values = h->last_values;
+    if (h->mon_cur_ret) { g.ep_ret = h->ep_ret; g.ep_len = h->ep_len; }
+    return g;
+}
+// "" when the handle's net fits the plug-in's fused rollout kernel, else why not
+std::string fused_rollout_unavailable(const dril_handle* h) {
+    if (!h->env.module) return "the fused rollout is the collection kernel of a device env plug-in (DRIL_ENV_MODULE): the built-in envs collect with the library's own rollout_kernel, host envs (DRIL_ENV_EXTERNAL) step on the host";
+    if (h->env.is_world()) return std::string("env plug-in \"") + h->env.desc.name + "\" is a world of " + std::to_string(h->env.agents()) + " agents: worlds have no fused rollout yet (DRIL_ENV_PLUGIN_ROLLOUT refuses a world at compile time); collect step-granular, which is the default";
+    const EnvModuleRollout& r = h->env.rollout;
+    if (!r.reason.empty()) return std::string("env plug-in \"") + h->env.desc.name + "\": " + r.reason;
+    const int W = r.desc.max_width;
+    if (h->D > W) return "the observation has " + std::to_string(h->D) + " dims, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->D) + " or more";
+    for (int l = 0; l < h->gd.nh; ++l) if (h->gd.H[l] > W) return "hidden layer " + std::to_string(l + 1) + " is " + std::to_string(h->gd.H[l]) + " wide, the plug-in's fused rollout was compiled for widths up to " + std::to_string(W) + ": rebuild it with -DDRIL_ENV_ROLLOUT_MAX_WIDTH=" + std::to_string(h->gd.H[l]) + " or more";
+    if (h->env.scaling && !r.fn_scaled) return "ScalingWrapperEnv is on, but the code object has no dril_env_plugin_rollout_scaled kernel: rebuild it with this library's include/device/dril_env_rollout.h";
     return "";
 }
 

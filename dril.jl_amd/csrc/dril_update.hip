@@ -219,6 +219,12 @@ void update_fused_done(dril_handle* h, const UpdatePlan& p, int64_t launches) {
     h->adam_steps += p.total_steps; h->wimg_dirty = true; h->last_variant = 7; h->used_f16 = false;
     h->update_fused_path = 1; h->update_fused_launches = launches;
 }
+int generic_update_args(dril_handle* h, const UpdatePlan& p, uint64_t* keys, GenericUpdateArgs& g) {
+    g = GenericUpdateArgs{};
+    { const int rc = small_update_args(h, p, keys, g.u); if (rc) return rc; }
+    g.obs = h->obs; g.actions = h->act; g.adv = h->adv; g.ret = h->ret; g.logp = h->logp;
+    return DRIL_OK;
+}
 int update_enqueue_home(dril_handle* h, const UpdatePlan& p, const UpdateHome& home) {
     h->update_counter += 1;
     prof_begin(h, DRIL_K_EXPLAINED_VAR);
@@ -350,9 +356,8 @@ int ppo_update_once(dril_handle* h, dril_ppo_stats* out) {
     if (fused) {
         std::vector<uint64_t> keys((size_t)h->cfg.epochs);
         GenericUpdateArgs g{};
-        { int rca = small_update_args(h, plan, keys.data(), g.u); if (rca) return rca; }
+        { int rca = generic_update_args(h, plan, keys.data(), g); if (rca) return rca; }
         HIPCHK(h, hipStreamSynchronize(h->stream));                                    // (keys is a stack-lifetime host buffer)
-        g.obs = h->obs; g.actions = h->act; g.adv = h->adv; g.ret = h->ret; g.logp = h->logp;
         int64_t launches = 0;
         for (int64_t s0 = 0; s0 < total_steps; s0 += h->update_fused_chunk, ++launches) {
             small_update_chunk(plan, h->update_fused_chunk, s0, g.u);

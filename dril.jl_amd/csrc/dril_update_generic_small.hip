@@ -22,6 +22,7 @@
 
 #include "dril_grad_common.h"
 #include "dril_ppo_head.h"
+#include "dril_pop_map.h"
 
 namespace dril {
 
@@ -147,8 +148,11 @@ __device__ __forceinline__ void gu_backward_weights(float* G, int lw, int I, int
     }
 }
 
+// the kernel's body: the run of optimiser steps a.u.step0 .. + a.u.nsteps of ONE handle by ONE workgroup (the solo kernel on its argument, the population kernel on its member's block)
+// L: a's LDS plan (a.lay), named apart because its arrays are indexed at run time: the solo kernel reads them from its kernel argument, the population kernel from the
+// member table itself — a private copy of such arrays would live in scratch memory
 template <int TS>
-__global__ __launch_bounds__(kGuThreads, 1) void ppo_update_generic_small_kernel(GenericUpdateArgs a) {
+__device__ __forceinline__ void gu_update_body(const GenericUpdateArgs& a, const GuLayout& L) {
     constexpr int TSP = GuTile<TS>::TSP;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ long long sidx[64];
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(kGuThreads, 1) void ppo_update_generic_small_kernel
     __shared__ float smom[2];
     __shared__ double sacc[8];
     __shared__ double sred[16];
-    const SmallUpdateArgs& u = a.u; const GuLayout& L = a.lay;
+    const SmallUpdateArgs& u = a.u;
     if (*u.stop_flag) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int PP = L.PP, A = a.A, D = a.D, nl = L.nl, act = a.act_code;
@@ -311,8 +315,10 @@ __global__ __launch_bounds__(kGuThreads, 1) void ppo_update_generic_small_kernel
         auto adam = [&](int p, int off) {
             float g = G[off];
             if (scale != 1.0f) g = g * scale;
-            const float m = u.beta1 * am[p] + (1.0f - u.beta1) * g;
-            const float v = u.beta2 * av[p] + (1.0f - u.beta2) * g * g;
+            // which of the two products joins the FMA is written out: left to the compiler the solo and the population kernel contracted the first line differently
+            // (one rounding apart).  These are the forms the solo kernel has always compiled to
+            const float m = fmaf(g, 1.0f - u.beta1, u.beta1 * am[p]);
+            const float v = fmaf(u.beta2, av[p], (1.0f - u.beta2) * g * g);
             am[p] = m; av[p] = v;
             Wp[off] -= m / (1.0f - bt1) / (sqrtf(v / (1.0f - bt2)) + u.eps) * u.lr;
         };
@@ -339,6 +345,29 @@ __global__ __launch_bounds__(kGuThreads, 1) void ppo_update_generic_small_kernel
         }
     if (!a.discrete && tid < A) u.params[u.Pa + u.Pc + tid] = Wp[L.ls + tid];
     if (tid == 0) { u.bt[0] = bt1; u.bt[1] = bt2; u.bt[2] = bt1; u.bt[3] = bt2; }     // both ping-pong slots: the host's step parity no longer matters
+}
+
+template <int TS>
+__global__ __launch_bounds__(kGuThreads, 1) void ppo_update_generic_small_kernel(GenericUpdateArgs a) { gu_update_body<TS>(a, a.lay); }
+
+// ppo_update_generic_small_pop_kernel — n members of a population (dril_population_*, docs/population.md, "Plug-in members") in one launch: workgroup m copies
+// members[m] (uniform loads), takes what it dereferences through the global address space once (pop_global) and runs the body above on the copy (the LDS plan is read from the table in place): the solo kernel's
+// device code on the solo launch's own argument block.  Workgroups share nothing (each member has its own parameters, moments, buffers, flags and statistics rows) and
+// never wait for one another: no co-residency is needed, no cap on n — workgroups beyond what is resident start when others have finished.  A member whose stop_flag
+// is set (target_kl, a non-finite gradient in an earlier launch of the chunked sequence) leaves at once, as in the solo kernel.
+template <int TS>
+__global__ __launch_bounds__(kGuThreads, 1) void ppo_update_generic_small_pop_kernel(const GenericUpdateArgs* __restrict__ members, int n) {
+    if ((int)blockIdx.x >= n) return;
+    const GenericUpdateArgs& src = members[blockIdx.x];
+    GenericUpdateArgs a;                                                               // every field but lay, which the body reads in place
+    a.u = src.u; a.D = src.D; a.A = src.A; a.discrete = src.discrete; a.act_code = src.act_code; a.need_z = src.need_z;
+    a.obs = src.obs; a.actions = src.actions; a.adv = src.adv; a.ret = src.ret; a.logp = src.logp;
+    SmallUpdateArgs& u = a.u;
+    u.params = pop_global(u.params); u.adam_m = pop_global(u.adam_m); u.adam_v = pop_global(u.adam_v); u.bt = pop_global(u.bt); u.val_old = pop_global(u.val_old);
+    u.perm = pop_global(u.perm); u.keys = pop_global(u.keys); u.step_stats = pop_global(u.step_stats); u.norm_out = pop_global(u.norm_out);
+    u.nan_flag = pop_global(u.nan_flag); u.stop_flag = pop_global(u.stop_flag);
+    a.obs = pop_global(a.obs); a.actions = pop_global(a.actions); a.adv = pop_global(a.adv); a.ret = pop_global(a.ret); a.logp = pop_global(a.logp);
+    gu_update_body<TS>(a, src.lay);
 }
 
 // the LDS plan of a net shape at a tile width; total_bytes includes the static words of the kernel
@@ -399,6 +428,34 @@ hipError_t launch_ppo_update_generic_small(const GenericDims& d, GenericUpdateAr
     } else {
         { hipError_t e = set_max_dynamic_lds((const void*)ppo_update_generic_small_kernel<16>, lds); if (e != hipSuccess) return e; }
         ppo_update_generic_small_kernel<16><<<1, kGuThreads, lds, s>>>(a);
+    }
+    return hipGetLastError();
+}
+
+// n members in one launch: h_members (host copies of the blocks at d_members, as the caller filled them; lay, D .. need_z are set HERE in both, so call before the copy
+// to the device) are checked like a solo launch's block; GenericDims is equal across the members, and with it the tile width and the LDS plan
+hipError_t prepare_ppo_update_generic_small_pop(const GenericDims& d, GenericUpdateArgs* h_members, int n) {
+    const int TS = generic_update_tile(d);
+    if (!TS || n < 1 || !h_members) return hipErrorInvalidValue;
+    const GuLayout lay = gu_layout(d, TS);
+    for (int m = 0; m < n; ++m) {
+        GenericUpdateArgs& a = h_members[m]; const SmallUpdateArgs& u = a.u;
+        if (!generic_update_unfit(d, u.P).empty() || u.B < 1 || u.B > 64 || u.nb < 1 || u.nsteps < 0 || u.step0 < 0 || !u.params || !u.adam_m || !u.adam_v || !u.bt || !u.step_stats ||
+            !u.stop_flag || !u.nan_flag || !u.keys || !a.obs || !a.actions || !a.adv || !a.ret || !a.logp || !u.val_old) return hipErrorInvalidValue;
+        a.lay = lay; a.D = d.D; a.A = d.A; a.discrete = d.discrete; a.act_code = d.act; a.need_z = (d.act == 6 || d.act == 7) ? 1 : 0;
+    }
+    return hipSuccess;
+}
+hipError_t launch_ppo_update_generic_small_pop(const GenericDims& d, const GenericUpdateArgs* d_members, int n, hipStream_t s) {
+    const int TS = generic_update_tile(d);
+    if (!TS || n < 1 || !d_members) return hipErrorInvalidValue;
+    const size_t lds = gu_lds_bytes(gu_layout(d, TS));
+    if (TS == 32) {
+        { hipError_t e = set_max_dynamic_lds((const void*)ppo_update_generic_small_pop_kernel<32>, lds); if (e != hipSuccess) return e; }
+        ppo_update_generic_small_pop_kernel<32><<<n, kGuThreads, lds, s>>>(d_members, n);
+    } else {
+        { hipError_t e = set_max_dynamic_lds((const void*)ppo_update_generic_small_pop_kernel<16>, lds); if (e != hipSuccess) return e; }
+        ppo_update_generic_small_pop_kernel<16><<<n, kGuThreads, lds, s>>>(d_members, n);
     }
     return hipGetLastError();
 }

@@ -1877,11 +1877,25 @@ def train_(agent: Agent, env: DeviceParallelEnv, alg: PPO, max_steps: int, callb
                 raise
 
 
-def train_population_(agents: Sequence[Agent], envs: Sequence[DeviceParallelEnv], algs: Sequence[PPO], max_steps: int):
+def _population_envs(what: str, envs) -> bool:
+    """the env types a population's members train and evaluate on: DeviceParallelEnv of a built-in kind, or DeviceModuleEnv(path, n, fused_rollout=True) of one
+    code object (the library compares the files); True for the second"""
+    plugin = all(type(e) is DeviceModuleEnv for e in envs)
+    for e in envs:
+        if not plugin and type(e) is not DeviceParallelEnv:
+            raise TypeError(f"{what}: members are DeviceParallelEnv of a built-in kind, or all of them DeviceModuleEnv(path, n, fused_rollout=True) of one code object "
+                            "(host and device-array envs: one call per member)")
+    return plugin
+
+
+def train_population_(agents: Sequence[Agent], envs: Sequence[DeviceParallelEnv], algs: Sequence[PPO], max_steps: int, fused_update: bool = False):
     """The list form of train_: train_population_(agents, envs, algs, max_steps) -> [(learn_stats, timer), ...], one pair per agent, each equal to what
     train_(agents[i], envs[i], algs[i], max_steps) returns and leaves behind (parameters and optimiser state are copied back on every exit path) — but every
     iteration of all agents is one batched rollout launch and one batched update launch (Population, docs/population.md).  The envs are DeviceParallelEnv of one
     built-in kind and shape; the algs may differ in everything the kernels take at run time (learning rate, gamma, clip ranges, coefficients, target_kl, ...).
+    Device env plug-ins: a list of DeviceModuleEnv(path, n, fused_rollout=True) of ONE code object built with DRIL_ENV_PLUGIN_ROLLOUT_POP and one shape;
+    `fused_update=True` switches each bound handle to the one-launch update as train_ does (dril_update_fused_enable) — a plug-in member needs both opt-ins, and
+    without them the library's refusal is raised (docs/population.md, "Plug-in members").
     Callbacks are out of scope here: hooks observe and steer one agent's loop step by step, so per-member train_ remains the way to use them.  `timer` holds the
     wall seconds of the whole population (the members share every launch)."""
     agents, envs, algs = list(agents), list(envs), list(algs)
@@ -1889,13 +1903,13 @@ def train_population_(agents: Sequence[Agent], envs: Sequence[DeviceParallelEnv]
         raise ValueError("train_population_: empty population")
     if not (len(agents) == len(envs) == len(algs)):
         raise ValueError(f"train_population_: {len(agents)} agents, {len(envs)} envs and {len(algs)} algs: one of each per member")
-    for e in envs:
-        if type(e) is not DeviceParallelEnv:
-            raise TypeError("train_population_: members train on DeviceParallelEnv of a built-in kind (plug-in, host and device-array envs: train_ per member)")
+    _population_envs("train_population_", envs)
     t0 = time.perf_counter()
     handles = []
     for agent, env, alg in zip(agents, envs, algs):
         h = env.bind(alg, agent.layer)
+        if fused_update:
+            h.update_fused_enable(True)
         h.set_params(flatten_params(agent.train_state.parameters))
         h.set_optimizer_state(agent.train_state.optimizer_state)
         handles.append(h)
@@ -2032,16 +2046,14 @@ def evaluate_population(agents: Sequence[Agent], envs: Sequence[DeviceParallelEn
                         population: Optional[Population] = None) -> list:
     """The list form of evaluate_agent(agent, env, isolated=True): one stats dict per agent (the keys of evaluate_agent(..., return_stats=True)), each equal to what
     the per-agent call returns, with one batched launch and one look per K env steps for all of them (Population.evaluate, docs/population.md "Evaluation"); the
-    envs are left as they were.  Each env is bound as train_population_ binds it.  The handles are joined into a population for the call; handles that already are
+    envs are left as they were (plug-in members — DeviceModuleEnv, as train_population_ takes them — are evaluated one by one inside the call).  Each env is bound as train_population_ binds it.  The handles are joined into a population for the call; handles that already are
     joined are evaluated through the population the caller passes as `population=` (its members, in the order of `agents`).  seed=None: every env's own seed."""
     agents, envs = list(agents), list(envs)
     if not agents:
         raise ValueError("evaluate_population: empty population")
     if len(agents) != len(envs):
         raise ValueError(f"evaluate_population: {len(agents)} agents and {len(envs)} envs: one of each per member")
-    for e in envs:
-        if type(e) is not DeviceParallelEnv:
-            raise TypeError("evaluate_population: members are DeviceParallelEnv of a built-in kind (plug-in, host and device-array envs: evaluate_agent per member)")
+    _population_envs("evaluate_population", envs)
     handles = []
     for agent, env in zip(agents, envs):
         h = env.bind(agent.alg, agent.layer)

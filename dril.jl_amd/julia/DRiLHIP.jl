@@ -618,8 +618,14 @@ The list form of `train!`: P agents, each on its own DeviceParallelEnv of one bu
 rollout launch and one batched update launch (docs/population.md), and every agent ends bit-identical to `train!(agents[i], envs[i], algs[i], max_steps)`.
 Returns a vector of `(learn_stats, to)`; the TimerOutput is the population's (the members share every launch).  Callbacks are out of scope: per-member `train!`
 remains the way to use hooks.  Static-checked only, as everything in this file (tools/check_shim.py).
+Device env plug-ins: `OnDeviceModule(path, n; fused_rollout = true)` envs of ONE code object built with DRIL_ENV_PLUGIN_ROLLOUT_POP join the same way (an
+`OnDeviceModule` is a `DeviceParallelEnv` of kind `:Module`, so this is their method too); each bound handle is switched to the one-launch update
+(dril_update_fused_enable) first, which a plug-in member needs — `train_population!(...; fused_update = false)` leaves that to the caller and the refusal to the library.
 """
 function train!(agents::Vector, envs::Vector{<:DeviceParallelEnv}, algs::Vector{<:PPO}, max_steps::Int)
+    return train_population!(agents, envs, algs, max_steps; fused_update = !isempty(envs) && all(e -> e.kind === :Module, envs))
+end
+function train_population!(agents::Vector, envs::Vector{<:DeviceParallelEnv}, algs::Vector{<:PPO}, max_steps::Int; fused_update::Bool = true)
     P = length(agents)
     (P >= 1 && length(envs) == P && length(algs) == P) || throw(ArgumentError("train!: $(length(agents)) agents, $(length(envs)) envs and $(length(algs)) algs: one of each per member, at least one"))
     to = TimerOutput()
@@ -631,6 +637,7 @@ function train!(agents::Vector, envs::Vector{<:DeviceParallelEnv}, algs::Vector{
         @timeit to "setup" begin
             for m in 1:P
                 bind_agent!(envs[m], agents[m], algs[m]); push_params!(envs[m], agents[m])
+                fused_update && check(ccall((:dril_update_fused_enable, LIB[]), Int32, (Ptr{Cvoid}, Int32), envs[m].handle, Int32(1)), envs[m].handle)
                 if !push_optimizer_state!(envs[m], agents[m]) && envs[m].optimizer_owner !== agents[m].train_state
                     check(ccall((:dril_reset_optimizer, LIB[]), Int32, (Ptr{Cvoid},), envs[m].handle), envs[m].handle)
                 end

@@ -1,0 +1,6 @@
+// cartpole_pop_plugin.hip — the CartPole-v1 plug-in of cartpole_fused_plugin.hip with the population entry (include/device/dril_env_rollout_pop.h): the same env and
+// rollout kernel, and a code object that also holds dril_env_plugin_rollout_pop — the collections of all members of a population in one launch (docs/population.md).
+//     hipcc --genco --offload-arch=gfx950 --no-gpu-bundle-output -O3 -fno-slp-vectorize -I include examples/envs/cartpole_pop_plugin.hip -o examples/envs/cartpole_pop_plugin.hsaco
+#include "cartpole_fused_plugin.hip"
+#include "device/dril_env_rollout_pop.h"
+DRIL_ENV_PLUGIN_ROLLOUT_POP(CartPolePlugin)

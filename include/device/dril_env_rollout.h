@@ -199,8 +199,11 @@ template <class Env, bool scaled> inline void dril_env_rollout_host(const DrilEn
 #define DRIL_ENV_ROLLOUT_DESC_QUAL
 #else
 // ---- the kernel ----------------------------------------------------------------------------------------------------------------------------------------------
+// (always inlined: a code object may call the body from more than one kernel — dril_env_rollout_pop.h —, and an out-of-line copy would take the argument block and the
+// parameter vector by generic pointers, turning the kernel's global and LDS accesses into flat ones; with one caller the compiler inlined them anyway)
+#define DRIL_ENV_ROLLOUT_INLINE __attribute__((always_inline)) inline
 // the tile's rows of a (E x D) array as panel [k][c]: column c = env e0 + c; columns past the batch, and columns with where[e] == 0, are zero
-template <int TC> __device__ inline void dril_rollout_load_panel(float* panel, const float* src, const uint8_t* where, int D, int e0, int ncol) {
+template <int TC> __device__ DRIL_ENV_ROLLOUT_INLINE void dril_rollout_load_panel(float* panel, const float* src, const uint8_t* where, int D, int e0, int ncol) {
     for (int i = threadIdx.x; i < D * TC; i += DRIL_ENV_ROLLOUT_THREADS) {
         const int c = i / D, k = i - c * D;
         float v = 0.f;
@@ -209,7 +212,7 @@ template <int TC> __device__ inline void dril_rollout_load_panel(float* panel, c
     }
 }
 // net(panel `in`) for the tile's columns; both panels are clobbered; returns the panel whose rows 0 .. out-1 hold the output.  Ends behind a barrier
-template <int TC> __device__ inline const float* dril_rollout_net(const DrilEnvRolloutArgs& g, const float* P, int D, int out, int off, float* in, float* other) {
+template <int TC> __device__ DRIL_ENV_ROLLOUT_INLINE const float* dril_rollout_net(const DrilEnvRolloutArgs& g, const float* P, int D, int out, int off, float* in, float* other) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int K = D, w = off;
     for (int l = 0; l <= g.n_hidden; ++l) {
@@ -236,7 +239,7 @@ template <int TC> __device__ inline const float* dril_rollout_net(const DrilEnvR
 // both nets on the panel `in` in ONE pass (their hidden layers have the same shapes): net z's activations are rows [z W, (z + 1) W) of a panel, so this form needs
 // 2 x the widest hidden layer <= DRIL_ENV_ROLLOUT_MAX_WIDTH.  Returns the panel whose rows 0 .. A-1 hold the actor's output and row A the critic's value.  A (row,
 // column) is the same chain of FMAs as in dril_rollout_net: which form ran changes no result.  Ends behind a barrier
-template <int TC> __device__ inline const float* dril_rollout_both(const DrilEnvRolloutArgs& g, const float* P, int D, int A, float* in, float* other) {
+template <int TC> __device__ DRIL_ENV_ROLLOUT_INLINE const float* dril_rollout_both(const DrilEnvRolloutArgs& g, const float* P, int D, int A, float* in, float* other) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int K = D, wa = g.actor_off, wc = g.critic_off;
     for (int l = 0; l <= g.n_hidden; ++l) {
@@ -261,7 +264,7 @@ template <int TC> __device__ inline const float* dril_rollout_both(const DrilEnv
     return in;
 }
 // all T steps of the workgroup's tile; P: the parameter vector the forward reads — global memory, or its copy in LDS (the address space is known at each call site)
-template <class Env, bool scaled> __device__ inline void dril_env_rollout_steps(const DrilEnvRolloutArgs& g, const float* P, float* p0, float* p1, float* values, int* any_truncated) {
+template <class Env, bool scaled> __device__ DRIL_ENV_ROLLOUT_INLINE void dril_env_rollout_steps(const DrilEnvRolloutArgs& g, const float* P, float* p0, float* p1, float* values, int* any_truncated) {
     constexpr int TC = DRIL_ENV_ROLLOUT_TILE, D = Env::D;
     const int tid = threadIdx.x, E = g.env.E, e0 = blockIdx.x * TC;
     const int ncol = E - e0 < TC ? E - e0 : TC, e = e0 + tid;
@@ -299,7 +302,7 @@ template <class Env, bool scaled> __device__ inline void dril_env_rollout_steps(
         }
     }
 }
-template <class Env, bool scaled> __device__ inline void dril_env_rollout_run(const DrilEnvRolloutArgs& g) {
+template <class Env, bool scaled> __device__ DRIL_ENV_ROLLOUT_INLINE void dril_env_rollout_run(const DrilEnvRolloutArgs& g) {
     constexpr int TC = DRIL_ENV_ROLLOUT_TILE;
     __shared__ float4 panels[2 * DRIL_ENV_ROLLOUT_MAX_WIDTH * TC / 4];
     __shared__ float4 staged[DRIL_ENV_ROLLOUT_STAGE_FLOATS / 4 + 1];

@@ -720,7 +720,12 @@ int32_t dril_train(dril_handle* h, int64_t max_steps, dril_ppo_stats* stats, dou
  * normalize_advantage.  Free per member: seed, learning rate, gamma, gae_lambda, clip_range, clip_range_vf, ent_coef, vf_coef, max_grad_norm, target_kl (and their
  * has_ flags), Adam betas / eps, monitor_window, parameters, optimiser state.
  * dril_population_join refuses, naming the member index and the reason in dril_population_last_error(NULL), and leaves every handle as it was:
- *   DRIL_ERR_UNSUPPORTED  an external handle, a device env plug-in handle or a world; a normalising handle; a generic or wide net; batch_size > 64; world_size > 1;
+ * Device env plug-in handles (DRIL_ENV_MODULE) join too when their solo iteration is the one-launch form on both sides: dril_rollout_fused_enable and
+ * dril_update_fused_enable on and available, and a code object built with DRIL_ENV_PLUGIN_ROLLOUT_POP (include/device/dril_env_rollout_pop.h).  The population then
+ * launches the plug-in's dril_env_plugin_rollout_pop once and ppo_update_generic_small_pop_kernel once per chunk of optimiser steps, with no cap on members; equal
+ * across such members are also the code object (size and hash of the file), ScalingWrapperEnv on / off and the net's layers; plug-in and built-in members do not mix
+ * (DRIL_ERR_INVALID_ARG).  dril_population_evaluate_device evaluates plug-in members one by one (docs/population.md, "Plug-in members").
+ *   DRIL_ERR_UNSUPPORTED  an external handle, a world, a device env plug-in handle without both opt-ins or without the population entry; a normalising handle; a generic or wide net; batch_size > 64; world_size > 1;
  *                         a handle whose iteration is not one rollout_duo_kernel launch + one ppo_update_small_kernel launch (DRIL_GRAD_VARIANT, DRIL_FORCE_STEPWISE, ...)
  *   DRIL_ERR_INVALID_ARG  n < 1 or n > DRIL_POPULATION_MAX, a null entry, the same handle twice, a handle already in a population, mixed kinds / shapes / devices
  * A member that cannot take the batched launch in one iteration (a latched or out-of-range exact-f32 forward / update, a redo after a non-finite f16 step, a
